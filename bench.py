@@ -184,7 +184,29 @@ def parse():
                          "trajectory (--kitti-out); reported as \"kitti_replay\".  Skipped when the directory is absent.")
     ap.add_argument("--kitti-out", default=None, help="trajectory file of the replay (KITTI pose format; default <dir>/tloam_hip_poses.txt)")
     ap.add_argument("--kitti-max-frames", type=int, default=0)
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the headline's last timed scan_match returned to its caller (rank 0) "
+                         "as DIR/<name>.npy, float64: the result pose and the tloam_stats fields (timing fields excepted)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+# what a caller of tloam_scan_match receives, by the names of its tloam_stats fields (host_wait_us is a time, not a result)
+DUMP_STATS = ("outer_iterations", "gn_evaluations", "gn_iterations", "accepted_steps", "n_corr", "converged_early",
+              "weight_range_violations", "kind_cost", "mu", "solver_cost", "se3", "gn_sweeps")
+
+
+def dump_outputs(path, T, c_stats):
+    """`--dump-outputs`: the result pose (4x4, row-major) and every result field of the stats, one float64 .npy each"""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"pose": T}
+    for name in DUMP_STATS:
+        v = getattr(c_stats, name)
+        arrays[name] = v[:] if hasattr(v, "_length_") else v
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(v, dtype=np.float64))
 
 
 _LINE_FD = None
@@ -226,6 +248,9 @@ def main():
     # TLOAM_BENCH_FORCE_MULTI=1 (under torchrun, WORLD_SIZE=1): drive the N>1 code path -- process group,
     # replica aggregation and the RCCL-sharded block -- on a single-GPU box
     multi = world > 1 or os.environ.get("TLOAM_BENCH_FORCE_MULTI") == "1"
+    if args.sharded_child and os.environ.get("TLOAM_BENCH_CHILD_FAIL") == str(rank):
+        # test hook: this rank's child ends abnormally -- before it opens the device, so nothing on the GPU is disturbed
+        os._exit(3)
 
     import torch  # plumbing only: process group, barrier, device sync (imported first so that one HIP runtime is shared)
     from tloam_amd import registration as reg
@@ -258,8 +283,6 @@ def main():
     if args.sharded_child:
         # a rank's child (sharded_in_children): the sharded 1 M frame and nothing else; rank 0's child hands the result to its parent
         cfg = reg.default_config(planar_maxnum=big, ground_maxnum=big, edge_maxnum=big, sphere_maxnum=big)
-        if os.environ.get("TLOAM_BENCH_CHILD_CRASH") == str(rank):   # test hook: this rank's child dies the way a GPU fault kills it
-            os.abort()
         sharded = {}
         finished = within(lambda: sharded_frame(args, reg, synth, torch, dist, cfg, synth.M1_SRC, synth.M1_TGT, rank, world,
                                                 local_rank, barrier, cdev, sharded), args.sharded_timeout)
@@ -279,7 +302,7 @@ def main():
                         "caps lifted) -- BASELINE.json configs[2]"),
     }
 
-    def run_frames(wl, steps, warmup, seed):
+    def run_frames(wl, steps, warmup, seed, dump=None):
         """One context, `warmup` untimed + `steps` timed scan_match calls between barriers, every input resident in HBM
         before the clock starts.  KITTI-density workload: every step is its OWN frame of the synthetic sequence (frames
         0 .. warmup + steps - 1, staged in the context's HBM frame store and activated by an O(1) tloam_frame_select) --
@@ -342,6 +365,8 @@ def main():
         elapsed = time.perf_counter() - t0
         # (the last timed frame, for the sanity figures below)
         scene, T, st = scenes[(warmup + steps - 1) % len(scenes)], np.frombuffer(res_buf).reshape(4, 4).T.copy(), c_stats.as_dict()
+        if dump and rank == 0:
+            dump_outputs(dump, T, c_stats)
         gn_iters_job = float(gn_iters)
         if multi:
             tt = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
@@ -422,7 +447,7 @@ def main():
                 "last_frame": {"gn_sweeps": int(st["gn_sweeps"]), "gn_evaluations": int(st["gn_evaluations"])}}
 
     # ---- headline: the configuration the metric is quoted on (KITTI-00 scan density); every rank its own frame pair
-    head = run_frames(args.workload, args.steps, args.warmup, args.seed + rank)
+    head = run_frames(args.workload, args.steps, args.warmup, args.seed + rank, dump=args.dump_outputs)
     # ---- the HBM-roofline characterisation workload (configs[2]) in the same command: its K3 is `roofline`
     other = "m1" if args.workload == "kitti" else "kitti"
     side = None
@@ -561,11 +586,12 @@ def main():
     if multi and side is not None:
         # (on a deadline: RCCL with N > 1 ranks and the mailbox over xGMI run for the first time on the driver's 8-GPU node --
         #  a collective that never returns must not cost the run its line.  What has finished by then is reported.)
-        # In a child process of every rank (a GPU fault there does not take the line with it) -- except when MORE THAN FOUR ranks
-        # share ONE device (TLOAM_BENCH_ONE_DEVICE, a development set-up): sixteen processes oversubscribe the device's hardware
-        # queues, the runlist is time-sliced in milliseconds and a gather that spins on a peer's post waits for the peer's queue to
-        # be mapped again -- 22 ms per exchange instead of 29 us (profiles of round 6).  On one GPU per rank it is two processes.
-        in_process = os.environ.get("TLOAM_BENCH_SHARDED_IN_PROCESS") == "1" or (one_dev and world > 4)
+        # In a child process of every rank (a GPU fault there does not take the line with it) -- except when MORE THAN TWO ranks
+        # share ONE device (TLOAM_BENCH_ONE_DEVICE, a development set-up): a rank and its child are two processes with the device
+        # open, and a shared device takes at most six; with more processes still, the device's hardware queues are oversubscribed,
+        # the runlist is time-sliced in milliseconds and a gather that spins on a peer's post waits for the peer's queue to be
+        # mapped again -- 22 ms per exchange instead of 29 us (profiles of round 6).  On one GPU per rank it is two processes.
+        in_process = os.environ.get("TLOAM_BENCH_SHARDED_IN_PROCESS") == "1" or (one_dev and world > 2)
         stuck = False
         if in_process:
             sharded = {}

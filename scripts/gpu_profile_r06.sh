@@ -38,7 +38,7 @@ timeout 300 rocprofv3 --kernel-trace -d $O/mtrace -o t -- python $R/bench.py --w
 cd $R
 # 6. the N > 1 line as the driver launches it, all ranks on the one GPU of this box (TLOAM_BENCH_ONE_DEVICE): the self-verifying
 #    sharded frame (every form against the one-rank solve), NOT a scaling curve
-for N in 2 4 8; do
+for N in 2 4; do   # (a shared device takes at most six processes with it open: no 8 ranks on one GPU)
   TLOAM_BENCH_ONE_DEVICE=1 timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29520 + N)) bench.py --gpus $N --steps 20 --warmup 5 --m1-steps 4 > $P/${TAG}_bench_gpus${N}_one_device.json 2> $O/bench_gpus$N.err
 done
 # 7. the reduced chip (tests/test_gpu_cu_mask.py leaves its records in gpurun_out/)

@@ -122,36 +122,38 @@ def test_oracle_and_golden_match_the_reference(path):
         assert dt < 1e-6 and dr < 1e-6, ("golden", k, dt, dr)
 
 
-@NO_REF
-@pytest.mark.gpu
-@pytest.mark.parametrize("path", REF or ["-"], ids=[os.path.basename(p)[5:-8] for p in REF] or ["none"])
-def test_hip_path_matches_the_reference(path, hip_module):
-    """The PRODUCT against the reference itself: tloam_scan_match through the C ABI on the inputs the reference was run on, with
-    max_iterations = 1..n_outer -- the pose after every outer GNC iteration within the north-star tolerance -- and the
-    minimiser's counters of the full run against the reference's Solver::Summary of every Solve."""
-    reg = hip_module
-    last = {}
+# The GPU twin exists once per reference file: with tests/golden_ref/ empty there is nothing for it to run, and the CPU test
+# above already reports the missing pin as its skip (in every suite, not only on a GPU machine).
+if REF:
+    @pytest.mark.gpu
+    @pytest.mark.parametrize("path", REF, ids=[os.path.basename(p)[5:-8] for p in REF])
+    def test_hip_path_matches_the_reference(path, hip_module):
+        """The PRODUCT against the reference itself: tloam_scan_match through the C ABI on the inputs the reference was run on, with
+        max_iterations = 1..n_outer -- the pose after every outer GNC iteration within the north-star tolerance -- and the
+        minimiser's counters of the full run against the reference's Solver::Summary of every Solve."""
+        reg = hip_module
+        last = {}
 
-    def hip_runner(cfg, z):
-        H = reg.HipRegistration(reg.default_config(**cfg))
-        for kind in range(4):
-            H.set_source(kind, z[f"src{kind}"]); H.set_target(kind, z[f"tgt{kind}"])
-        rc, T, st = H.scan_match(z["T_pred"])
-        H.close()
-        assert rc == 0
-        last.update(st=st, k=cfg["max_iterations"])
-        return T, None
+        def hip_runner(cfg, z):
+            H = reg.HipRegistration(reg.default_config(**cfg))
+            for kind in range(4):
+                H.set_source(kind, z[f"src{kind}"]); H.set_target(kind, z[f"tgt{kind}"])
+            rc, T, st = H.scan_match(z["T_pred"])
+            H.close()
+            assert rc == 0
+            last.update(st=st, k=cfg["max_iterations"])
+            return T, None
 
-    z, cfg, ref = _check_case_against(path, hip_runner, "hip")
-    solves = _read_solves(path)
-    n_outer = max(ref)
-    calls = sorted(j for (k, j) in solves if k == n_outer)
-    if calls and last.get("k") == n_outer:
-        # (the device keeps no per-iteration trace; its counters over the whole frame against the reference's Summaries)
-        it_ref = sum(max(solves[(n_outer, j)]["iters"]) for j in calls)
-        ok_ref = sum(sum(v["step_ok"] for i, v in solves[(n_outer, j)]["iters"].items() if i >= 1) for j in calls)
-        assert last["st"]["accepted_steps"] == ok_ref, ("accepted steps", last["st"]["accepted_steps"], ok_ref)
-        assert last["st"]["gn_iterations"] in (it_ref, it_ref + len(calls)), ("iterations", last["st"]["gn_iterations"], it_ref)
+        z, cfg, ref = _check_case_against(path, hip_runner, "hip")
+        solves = _read_solves(path)
+        n_outer = max(ref)
+        calls = sorted(j for (k, j) in solves if k == n_outer)
+        if calls and last.get("k") == n_outer:
+            # (the device keeps no per-iteration trace; its counters over the whole frame against the reference's Summaries)
+            it_ref = sum(max(solves[(n_outer, j)]["iters"]) for j in calls)
+            ok_ref = sum(sum(v["step_ok"] for i, v in solves[(n_outer, j)]["iters"].items() if i >= 1) for j in calls)
+            assert last["st"]["accepted_steps"] == ok_ref, ("accepted steps", last["st"]["accepted_steps"], ok_ref)
+            assert last["st"]["gn_iterations"] in (it_ref, it_ref + len(calls)), ("iterations", last["st"]["gn_iterations"], it_ref)
 
 
 def test_ref_file_reader_and_comparator_have_teeth(tmp_path):

@@ -12,9 +12,10 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_default_bench_line_is_the_only_thing_on_stdout_and_carries_the_flat_scalars(hip_module):
+def test_default_bench_line_is_the_only_thing_on_stdout_and_carries_the_flat_scalars(hip_module, tmp_path):
+    dump = tmp_path / "outputs"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--m1-steps", "3", "--kitti-frames", "12",
-           "--loop-frames", "12", "--no-cpu-baseline"]
+           "--loop-frames", "12", "--no-cpu-baseline", "--dump-outputs", str(dump)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     # (the loop-back RCCL set-up of the shard-size figures makes RCCL print its version banner through C stdio -- at EXIT, i.e.
@@ -37,3 +38,11 @@ def test_default_bench_line_is_the_only_thing_on_stdout_and_carries_the_flat_sca
     assert rf["gn_iteration_frac"] < rf["in_frame_frac"] < 1.0
     shard = [k for k in d if k.startswith("shard_iteration_us")]
     assert shard and all(not isinstance(d[k], (dict, list)) for k in shard), shard
+    # --dump-outputs: what the last timed scan_match handed back, float64 -- a rigid pose and the counters the line quotes
+    import numpy as np
+    T = np.load(dump / "pose.npy")
+    assert T.dtype == np.float64 and T.shape == (4, 4) and np.allclose(T[:3, :3] @ T[:3, :3].T, np.eye(3), atol=1e-9)
+    assert np.array_equal(T[3], [0.0, 0.0, 0.0, 1.0])
+    assert np.load(dump / "n_corr.npy").tolist() == d["config"]["n_corr"]
+    assert np.load(dump / "outer_iterations.npy") == d["config"]["outer_iterations"]
+    assert sum(os.path.getsize(p) for p in dump.iterdir()) < 64 << 20
