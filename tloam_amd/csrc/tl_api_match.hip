@@ -102,7 +102,9 @@ constexpr size_t kFinRowsDoubles = (size_t)(4 * 256 + 64) * 16;   // the blocks'
 // (a quarter of the) one-wave blocks of a direct finish: a fixed function of the capacity, so that the riding form and the launch of
 // its own cut the rows alike.  (Twice as many blocks on ONE ticket measured 52 instead of 31 us for the frame's last finish: the
 // arrivals on the ticket are what it waits for -- hence the two-level hand-over of finish_direct_block.)
-int direct_wblocks(const tloam_ctx* c) {
+// (The same function gives the block count of every finish -- enqueue_finish, the riding large finish: the summation tree,
+// hence the bits, must not depend on the path or on timing.)
+int finish_wblocks(const tloam_ctx* c) {
   size_t cap = 0;
   for (int k = 0; k < kKinds; ++k) cap += c->kd[k].c_cap;
   return (int)std::min<size_t>(256, std::max<size_t>(64, cap / 2048));
@@ -112,7 +114,7 @@ int* direct_blk_cnt(const tloam_ctx* c, int iter) { return c->blk_cnt.p + (size_
 FinishLargeArgs direct_finish_args(tloam_ctx* c, const CorrView* cv_iter, const WeightParams* wp, const HostMirror& hm, OuterCtl ctl,
                                    int iter, int riding, int built) {
   ctl.direct = riding ? 2 : 1;
-  FinishLargeArgs fin{cv_iter, wp, c->seg_n.p, c->sums16.p, hm, ctl, c->fin_rows.p, c->fin_tickets.p, direct_wblocks(c), {}, nullptr, 0, 0};
+  FinishLargeArgs fin{cv_iter, wp, c->seg_n.p, c->sums16.p, hm, ctl, c->fin_rows.p, c->fin_tickets.p, finish_wblocks(c), {}, nullptr, 0, 0};
   for (int k = 0; k < kKinds; ++k) fin.w_next[k] = direct_w_stream(c, k, (iter + 1) & 1);
   fin.blk_cnt = direct_blk_cnt(c, iter);
   fin.nblk = (int)c->blk_cnt_n;
@@ -127,45 +129,39 @@ FinishLargeArgs direct_finish_args(tloam_ctx* c, const CorrView* cv_iter, const 
 constexpr int kK3SampleStride = 3;
 // the device-side period counter of the GN iterations, once tloam_gn_iter_timer has armed it (null otherwise: the kernels skip it)
 unsigned long long* iter_span_of(const tloam_ctx* c) { return c->iter_timing ? c->iter_span.p : nullptr; }
-int launch_k3_timed(tloam_ctx* c, bool force) {
+// one sweep launch of the batch: launch(ev_start, ev_stop) with a pair from the event pool on every kK3SampleStride-th launch
+// (when the timer is armed), with two null events otherwise
+template <class Launch>
+int launch_sampled(tloam_ctx* c, Launch launch) {
   const bool sample = c->k3_timing && (c->k3_seq++ % kK3SampleStride) == 0;
   const int idx = c->batch_launches++;
-  if (sample) {
-    if (c->ev_used + 2 > c->ev_pool.size()) {
-      const size_t old = c->ev_pool.size();
-      c->ev_pool.resize(old + 256);
-      for (size_t i = old; i < c->ev_pool.size(); ++i) HIPC(c, hipEventCreate(&c->ev_pool[i]));
-    }
-    launch_k3(c->cv, c->state.p, c->partials.p, c->k3_grid, c->k3_single, c->k3_wide, force, c->stream, c->ev_pool[c->ev_used],
-              c->ev_pool[c->ev_used + 1]);
-    c->ev_used += 2;
-    c->ev_batch_idx.push_back(idx);
-  } else {
-    launch_k3(c->cv, c->state.p, c->partials.p, c->k3_grid, c->k3_single, c->k3_wide, force, c->stream);
+  if (!sample) {
+    launch(nullptr, nullptr);
+    return TLOAM_OK;
   }
+  if (c->ev_used + 2 > c->ev_pool.size()) {
+    const size_t old = c->ev_pool.size();
+    c->ev_pool.resize(old + 256);
+    for (size_t i = old; i < c->ev_pool.size(); ++i) HIPC(c, hipEventCreate(&c->ev_pool[i]));
+  }
+  launch(c->ev_pool[c->ev_used], c->ev_pool[c->ev_used + 1]);
+  c->ev_used += 2;
+  c->ev_batch_idx.push_back(idx);
   return TLOAM_OK;
+}
+int launch_k3_timed(tloam_ctx* c, bool force) {
+  return launch_sampled(c, [&](hipEvent_t e0, hipEvent_t e1) {
+    launch_k3(c->cv, c->state.p, c->partials.p, c->k3_grid, c->k3_single, c->k3_wide, force, c->stream, e0, e1);
+  });
 }
 // the same for the one-launch GN iteration (k3_sweep_step): the pair then brackets sweep + fold + step; the streaming part
 // alone is what the kernel's own span counter measures (K3Step::span, read by tloam_k3_timer_span)
 int launch_k3_step_timed(tloam_ctx* c) {
-  const bool sample = c->k3_timing && (c->k3_seq++ % kK3SampleStride) == 0;
-  const int idx = c->batch_launches++;
   const MboxView* mb = (exchanging(c) && c->comm == COMM_MAILBOX) ? &c->mbox : nullptr;
-  if (sample) {
-    if (c->ev_used + 2 > c->ev_pool.size()) {
-      const size_t old = c->ev_pool.size();
-      c->ev_pool.resize(old + 256);
-      for (size_t i = old; i < c->ev_pool.size(); ++i) HIPC(c, hipEventCreate(&c->ev_pool[i]));
-    }
-    launch_k3_step(c->cv, c->state.p, c->partials.p, c->k3_grid, c->k3_single, c->k3_wide, c->k3_ticket.p, c->k3_span.p, mb, c->stream,
-                   c->ev_pool[c->ev_used], c->ev_pool[c->ev_used + 1], iter_span_of(c));
-    c->ev_used += 2;
-    c->ev_batch_idx.push_back(idx);
-  } else {
-    launch_k3_step(c->cv, c->state.p, c->partials.p, c->k3_grid, c->k3_single, c->k3_wide, c->k3_ticket.p, c->k3_span.p, mb, c->stream, nullptr,
-                   nullptr, iter_span_of(c));
-  }
-  return TLOAM_OK;
+  return launch_sampled(c, [&](hipEvent_t e0, hipEvent_t e1) {
+    launch_k3_step(c->cv, c->state.p, c->partials.p, c->k3_grid, c->k3_single, c->k3_wide, c->k3_ticket.p, c->k3_span.p, mb, c->stream, e0,
+                   e1, iter_span_of(c));
+  });
 }
 // fold the recorded event pairs into the accumulated timers (stream must be idle).  The launches of the batch belong
 // to `nsolve` Solves starting at batch positions start[i]; of each, the first working[i] launches did a sweep, the
@@ -615,6 +611,25 @@ size_t total_seg_cap(const tloam_ctx* c) {
   for (int k = 0; k < kKinds; ++k) cap += c->kd[k].c_cap;
   return cap;
 }
+// a result slot's `incomplete` word as the outcome of its outer iteration: OS_COMM_ERROR and OS_INCOMPLETE become the error
+// they stand for, with last_error; any other word is TLOAM_OK (a caller that tops an unfinished Solve up does so before it asks).
+// *hand_over_timed_out (may be null) is set when the in-launch hand-over of one rank timed out: the device loop's fall-back.
+int slot_error(tloam_ctx* c, int incomplete, bool* hand_over_timed_out) {
+  if (incomplete == OS_COMM_ERROR) {
+    if (exchanging(c)) {
+      c->last_error = "mailbox exchange timed out: a peer rank did not post (dead process or diverged call sequence)";
+      return TLOAM_E_RCCL;
+    }
+    c->last_error = "in-launch hand-over of the fused GN iteration timed out (a block of the grid never posted its row)";
+    if (hand_over_timed_out) *hand_over_timed_out = true;
+    return TLOAM_E_HIP;
+  }
+  if (incomplete == OS_INCOMPLETE) {
+    c->last_error = "the minimiser did not terminate within its evaluation budget";
+    return TLOAM_E_INVALID;
+  }
+  return TLOAM_OK;
+}
 // one 1024-thread block does weights + sums + publish in a single launch
 bool finish_small_path(const tloam_ctx* c) { return one_rank(c) && total_seg_cap(c) <= 16384; }
 int enqueue_finish(tloam_ctx* c, const WeightParams& wp, const HostMirror& hm, const OuterCtl& ctl, int iter = 0, int built = 1) {
@@ -623,9 +638,7 @@ int enqueue_finish(tloam_ctx* c, const WeightParams& wp, const HostMirror& hm, c
     launch_finish_direct(fin, c->state.p, c->stream);
     return TLOAM_OK;
   }
-  // fixed function of the capacity (so the summation tree, hence the bits, do not depend on timing)
-  const size_t cap = total_seg_cap(c);
-  const int wblocks = (int)std::min<size_t>(256, std::max<size_t>(64, cap / 2048));
+  const int wblocks = finish_wblocks(c);
   if (finish_small_path(c)) {
     launch_weights_finish_small(c->cv, c->sv, wp, c->seg_n.p, c->sums16.p, c->state.p, hm, ctl, c->stream);
     return TLOAM_OK;
@@ -746,15 +759,8 @@ int tloam_sm_outer(tloam_ctx* c, int* done, tloam_stats* stats) {
     rc = wait_state(c, hm);
     if (rc != TLOAM_OK) return rc;
     if (!c->h_state->incomplete) break;
-    if (c->h_state->incomplete == OS_COMM_ERROR) {
-      c->last_error = exchanging(c) ? "mailbox exchange timed out: a peer rank did not post (dead process or diverged call sequence)"
-                                    : "in-launch hand-over of the fused GN iteration timed out (a block of the grid never posted its row)";
-      return exchanging(c) ? TLOAM_E_RCCL : TLOAM_E_HIP;
-    }
-    if (attempt > 0 || planned >= kSolveSweeps) {
-      c->last_error = "the minimiser did not terminate within its evaluation budget";
-      return TLOAM_E_INVALID;
-    }
+    if (c->h_state->incomplete == OS_COMM_ERROR) return slot_error(c, OS_COMM_ERROR, nullptr);
+    if (attempt > 0 || planned >= kSolveSweeps) return slot_error(c, OS_INCOMPLETE, nullptr);
     rc = enqueue_solve(c, /*armed=*/true, kSolveSweeps - planned, &wp);  // top up, then weights + finish again
     if (rc != TLOAM_OK) return rc;
   }
@@ -829,7 +835,7 @@ int enqueue_outer_iterations(tloam_ctx* c, int first, double mu, const BuildPara
   const bool ride = prepare_small_path(c) && finish_small_path(c) && build_finish_small_fits(c->sv);
   // ... and 1 M-class frames the same way with k_weights + k_outer_finish (k_build_finish_large)
   const bool ride_large = !ride && one_rank(c) && !finish_small_path(c) && build_finish_large_fits(c->sv);
-  const int wblocks_large = (int)std::min<size_t>(256, std::max<size_t>(64, total_seg_cap(c) / 2048));   // as enqueue_finish
+  const int wblocks_large = finish_wblocks(c);
   if (ride_large) HIPC(c, c->fin_rows.reserve((size_t)4 * 256 * 8));
   bool pending = false;   // the finish of the previous iteration has not been enqueued yet (it rides on this search)
   bool pending_large = false;
@@ -959,11 +965,7 @@ int scan_match_device_loop(tloam_ctx* c, bool* weight_violation) {
       return TLOAM_E_HIP;
     }
     if (S->incomplete == OS_SKIPPED) break;   // the loop had ended before this iteration
-    if (S->incomplete == OS_COMM_ERROR) {
-      c->last_error = "in-launch hand-over of the fused GN iteration timed out (a block of the grid never posted its row)";
-      c->hand_over_timed_out = true;
-      return TLOAM_E_HIP;
-    }
+    if (S->incomplete == OS_COMM_ERROR) return slot_error(c, OS_COMM_ERROR, &c->hand_over_timed_out);
     if (S->incomplete == OS_INCOMPLETE) {
       // The Solve of this iteration ran out of its planned budget: the device stopped the loop there (the sweeps of
       // the later iterations, gated only on `done`, have meanwhile continued this same Solve; their builds, refreshes
@@ -1000,15 +1002,8 @@ int scan_match_device_loop(tloam_ctx* c, bool* weight_violation) {
         if (rc != TLOAM_OK) return rc;
       }
       S = &c->h_state[iter];
-      if (S->incomplete == OS_INCOMPLETE) {
-        c->last_error = "the minimiser did not terminate within its evaluation budget";
-        return TLOAM_E_INVALID;
-      }
-      if (S->incomplete == OS_COMM_ERROR) {
-        c->last_error = "in-launch hand-over of the fused GN iteration timed out (a block of the grid never posted its row)";
-        c->hand_over_timed_out = true;
-        return TLOAM_E_HIP;
-      }
+      rc = slot_error(c, S->incomplete, &c->hand_over_timed_out);
+      if (rc != TLOAM_OK) return rc;
     }
     const int sweeps_before = c->stats.gn_sweeps;
     // the compact set of this iteration was (re)built iff the pose had moved since the last build

@@ -654,6 +654,9 @@ __device__ __forceinline__ bool poll_fold_tagged(const double* __restrict__ part
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   return ok_all;
 }
+__device__ __forceinline__ unsigned long long mbox_next_id(const MboxView& mb) {
+  return __hip_atomic_load(mb.ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1ull;
+}
 template <int W = 4>
 __device__ __forceinline__ void k3_last_block_reduce(double* __restrict__ partials, const double (*red)[32], const K3Fuse& fuse) {
   __shared__ double s_grp[8 * 33];
@@ -662,10 +665,60 @@ __device__ __forceinline__ void k3_last_block_reduce(double* __restrict__ partia
   fold_rows<true>(partials, (int)gridDim.x, s_grp, s_tot);
   if (threadIdx.x < kReduceBuf) fuse.out48[threadIdx.x] = s_tot[threadIdx.x];
   if (threadIdx.x == 0) __hip_atomic_store(fuse.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-armed
-  if (fuse.mb.nranks > 0) {
-    const unsigned long long id = __hip_atomic_load(fuse.mb.ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1ull;
-    mbox_post(fuse.mb, id, s_tot, kReduceBuf, threadIdx.x);
+  if (fuse.mb.nranks > 0) mbox_post(fuse.mb, mbox_next_id(fuse.mb), s_tot, kReduceBuf, threadIdx.x);
+}
+
+// ---- the sweep of one launch, shared by k3_accumulate and k3_sweep_step ----------------------------------------------
+// Speculative first fetch: the wave's first chunk of the planar segment is requested straight from the preloaded arguments,
+// BEFORE the dependent scalar loads of the state (done flag, pose, segment sizes) come back -- their latency overlaps the
+// first HBM round trip.  The capacity bound keeps it in range.  `early` runs once that fetch is requested and before the state
+// is read (k3_sweep_step's span stamp and state copy into LDS).  Once the Solve is done nothing more happens (after a tolerance
+// exit the remaining launches are no-ops, uniformly over the grid and the ranks; `force` sweeps all the same); otherwise the waves' totals go to red[W][32],
+// a barrier publishes them, and `tail` hands them on: the block's row, the last block's fold (+ post), or fold, exchange and step.
+// (The tail is inlined INTO the body rather than run after it returns: as a call after the body the fused k3_accumulate forms took
+// two more SGPRs.)  STAMPS: k3_accumulate's TLOAM_K3_PROFILE stamps, kept in ts.
+struct SweepStamps { unsigned long long t[4]; };
+template <bool SINGLE, int W, bool STAMPS, class Early, class Tail>
+__device__ __forceinline__ void sweep_body(const double* seg0, int stride0, int cap0, bool w2, bool force, const GnState* st,
+                                           const int* seg_n, const CorrView& cv, double (*red)[32], SweepStamps& ts, Early early, Tail tail) {
+  // the wave index is wave-uniform: tell the compiler (readfirstlane) so that chunk -> segment
+  // pointers are scalar (SGPR) work instead of per-lane loads of the kernel-argument table
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int gw = blockIdx.x * W + wave;
+#ifdef TLOAM_K3_PROFILE
+  if (STAMPS) {
+    ts.t[0] = __builtin_amdgcn_s_memtime();
+    ts.t[1] = wall_clock64();  // 100 MHz, one base for the whole device
   }
+#endif
+  ChunkData pre;
+  SingleWork wk{-1, 0};
+  const bool spec = !SINGLE && (TLOAM_K3_PLANE_DEPTH <= 2) && (gw + 1) * kChunk <= cap0;
+  if (SINGLE) {
+    wk = single_work_of(cv, cap0, gw, lane);
+    single_fetch(cv, seg0, stride0, wk, pre, w2);
+  } else if (spec) {
+    fetch_spec<TLOAM_K3_NT>(seg0, stride0, gw * kChunk + lane * 2, pre, w2);
+  }
+  early();
+  if (!force && st->done) return;
+  const Rt T = st->Rt_eval;        // exp(point), hoisted out of the per-block Evaluate (:22,:58,:98)
+#ifdef TLOAM_K3_PROFILE
+  if (STAMPS) ts.t[2] = __builtin_amdgcn_s_memtime();
+#endif
+  Acc a;
+  if (SINGLE) sweep_single(cv, seg_n, T, wk, pre, a);
+  else sweep_all(cv, seg_n, T, gw, gridDim.x * W, lane, a, pre, spec);
+#ifdef TLOAM_K3_PROFILE
+  if (STAMPS) {
+    __builtin_amdgcn_s_waitcnt(0);
+    ts.t[3] = __builtin_amdgcn_s_memtime();
+  }
+#endif
+  const double tot = wave_reduce_acc(a, lane);
+  if ((lane & 1) == 0) red[wave][lane >> 1] = tot;
+  __syncthreads();
+  tail();
 }
 
 // Argument order: the first twelve dwords -- the planar segment as (base, stride, capacity), the flag, the state,
@@ -674,62 +727,30 @@ __device__ __forceinline__ void k3_last_block_reduce(double* __restrict__ partia
 // are requested in the first instructions, before the kernel-argument segment itself has been read.
 // W: waves per block.  4, two blocks per CU; 8 (WIDE, streaming form on a full-chip grid): one block per CU, the same waves over the
 // same chunks, HALF the rows for the one block that folds them afterwards.
+// force: bit 0 sweeps a finished Solve all the same (timing aids), bit 1 = w2_flag.  FUSE: the last block folds the rows and
+// posts them (k3_last_block_reduce); otherwise every block writes its row for k_reduce / k_reduce_and_step.
 template <bool SINGLE, bool FUSE, int W = 4>
 __global__ __launch_bounds__(64 * W, TLOAM_K3_WAVES) void k3_accumulate(const double* __restrict__ seg0, int stride0, int cap0,
                                                         int force, GnState* __restrict__ st,
                                                         const int* __restrict__ seg_n, double* __restrict__ partials,
                                                         CorrView cv, K3Fuse fuse) {
   __shared__ double red[W][32];
-  // the wave index is wave-uniform: tell the compiler (readfirstlane) so that chunk -> segment
-  // pointers are scalar (SGPR) work instead of per-lane loads of the kernel-argument table
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int gw = blockIdx.x * W + wave;
-  // Speculative first fetch: the wave's first chunk of the planar segment is requested straight from the
-  // preloaded arguments, BEFORE the dependent scalar loads of the state (done flag, pose, segment sizes)
-  // come back -- their latency overlaps the first HBM round trip.  The capacity bound keeps it in range.
+  SweepStamps ts;
+  sweep_body<SINGLE, W, true>(seg0, stride0, cap0, (force & 2) != 0, (force & 1) != 0, st, seg_n, cv, red, ts, [] {}, [&] {
+    if (FUSE) {
+      k3_last_block_reduce<W>(partials, red, fuse);
+    } else if (threadIdx.x < kAccStride) {
+      partials[(size_t)blockIdx.x * kAccStride + threadIdx.x] = block_row<W>(red, threadIdx.x);
+    }
 #ifdef TLOAM_K3_PROFILE
-  const unsigned long long ts0 = __builtin_amdgcn_s_memtime();
-  const unsigned long long wc0 = wall_clock64();  // 100 MHz, one base for the whole device
+    if (threadIdx.x == 0) {  // development aid (scripts/k3_profile.py): wave 0's timeline in the spare columns
+      const unsigned long long ts3 = __builtin_amdgcn_s_memtime();
+      double* row = partials + (size_t)blockIdx.x * kAccStride;
+      row[28] = (double)(ts.t[1] & 0xffffffffull); row[29] = (double)(ts.t[2] - ts.t[0]); row[30] = (double)(ts.t[3] - ts.t[2]);
+      row[31] = (double)(ts3 - ts.t[3]) + 65536.0 * (double)(wall_clock64() - ts.t[1]);
+    }
 #endif
-  ChunkData pre;
-  SingleWork wk{-1, 0};
-  const bool spec = !SINGLE && (TLOAM_K3_PLANE_DEPTH <= 2) && (gw + 1) * kChunk <= cap0;
-  const bool w2 = (force & 2) != 0;   // (bit 1 of the flag word: the planar weights are in the second stream)
-  force &= 1;
-  if (SINGLE) {
-    wk = single_work_of(cv, cap0, gw, lane);
-    single_fetch(cv, seg0, stride0, wk, pre, w2);
-  } else if (spec) {
-    fetch_spec<TLOAM_K3_NT>(seg0, stride0, gw * kChunk + lane * 2, pre, w2);
-  }
-  if (!force && st->done) return;  // after a tolerance exit the remaining launches are no-ops
-  const Rt T = st->Rt_eval;        // exp(point), hoisted out of the per-block Evaluate (:22,:58,:98)
-  Acc a;
-#ifdef TLOAM_K3_PROFILE
-  const unsigned long long ts1 = __builtin_amdgcn_s_memtime();
-#endif
-  if (SINGLE) sweep_single(cv, seg_n, T, wk, pre, a);
-  else sweep_all(cv, seg_n, T, gw, gridDim.x * W, lane, a, pre, spec);
-#ifdef TLOAM_K3_PROFILE
-  __builtin_amdgcn_s_waitcnt(0);
-  const unsigned long long ts2 = __builtin_amdgcn_s_memtime();
-#endif
-  const double tot = wave_reduce_acc(a, lane);
-  if ((lane & 1) == 0) red[wave][lane >> 1] = tot;
-  __syncthreads();
-  if (FUSE) {
-    k3_last_block_reduce<W>(partials, red, fuse);
-  } else if (threadIdx.x < kAccStride) {
-    partials[(size_t)blockIdx.x * kAccStride + threadIdx.x] = block_row<W>(red, threadIdx.x);
-  }
-#ifdef TLOAM_K3_PROFILE
-  if (threadIdx.x == 0) {  // development aid (scripts/k3_profile.py): wave 0's timeline in the spare columns
-    const unsigned long long ts3 = __builtin_amdgcn_s_memtime();
-    double* row = partials + (size_t)blockIdx.x * kAccStride;
-    row[28] = (double)(wc0 & 0xffffffffull); row[29] = (double)(ts1 - ts0); row[30] = (double)(ts2 - ts1);
-    row[31] = (double)(ts3 - ts2) + 65536.0 * (double)(wall_clock64() - wc0);
-  }
-#endif
+  });
 }
 
 
@@ -788,27 +809,32 @@ void k3_plan(const int cap[kKinds], int device_cus, int* grid, bool* single, boo
 static int w2_flag(const CorrView& cv) {
   return (cv.k[0].w != nullptr && cv.k[0].w == cv.k[0].px + (size_t)(SS_W2 - SS_PX) * (size_t)cv.k[0].stride) ? 2 : 0;
 }
+// the sweep kernels' launch: the planar segment (base, stride, capacity), the flag word (| w2_flag), the state and the segment
+// sizes lead the argument list -- the preloaded dwords -- then the kernel's own arguments.  With an event pair, HIP events bound
+// to THIS dispatch (start/stop taken from the kernel's own dispatch packet): their elapsed time is the kernel duration itself,
+// the number rocprofv3 --kernel-trace reports.
+template <class Kern, class... Rest>
+static void launch_sweep(Kern kern, int grid, int threads, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop, const CorrView& cv,
+                         int flag, GnState* st, Rest... rest) {
+  if (ev_start && ev_stop) {
+    hipExtLaunchKernelGGL(kern, dim3(grid), dim3(threads), 0, s, ev_start, ev_stop, 0, (const double*)cv.k[0].px, cv.k[0].stride,
+                          cv.k[0].cap, flag | w2_flag(cv), st, cv.seg_n, rest...);
+  } else {
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), 0, s, (const double*)cv.k[0].px, cv.k[0].stride, cv.k[0].cap,
+                       flag | w2_flag(cv), st, cv.seg_n, rest...);
+  }
+}
 void launch_k3(const CorrView& cv, GnState* st, double* partials, int grid, bool single, bool wide, bool force, hipStream_t s,
                hipEvent_t ev_start, hipEvent_t ev_stop) {
   auto kern = single ? k3_accumulate<true, false> : wide ? k3_accumulate<false, false, 8> : k3_accumulate<false, false>;
-  const int threads = wide ? 512 : 256;
   K3Fuse none;
   memset(&none, 0, sizeof(none));
-  if (ev_start && ev_stop) {
-    // HIP events bound to THIS dispatch (start/stop taken from the kernel's own dispatch packet):
-    // their elapsed time is the kernel duration itself, the number rocprofv3 --kernel-trace reports
-    hipExtLaunchKernelGGL(kern, dim3(grid), dim3(threads), 0, s, ev_start, ev_stop, 0, (const double*)cv.k[0].px, cv.k[0].stride,
-                          cv.k[0].cap, (force ? 1 : 0) | w2_flag(cv), st, cv.seg_n, partials, cv, none);
-  } else {
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), 0, s, (const double*)cv.k[0].px, cv.k[0].stride, cv.k[0].cap, (force ? 1 : 0) | w2_flag(cv), st,
-                       cv.seg_n, partials, cv, none);
-  }
+  launch_sweep(kern, grid, wide ? 512 : 256, s, ev_start, ev_stop, cv, force ? 1 : 0, st, partials, cv, none);
 }
 void launch_k3_fused(const CorrView& cv, GnState* st, double* partials, int grid, bool single, bool wide, bool force,
                      const K3Fuse& fuse, hipStream_t s) {
   auto kern = single ? k3_accumulate<true, true> : wide ? k3_accumulate<false, true, 8> : k3_accumulate<false, true>;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(wide ? 512 : 256), 0, s, (const double*)cv.k[0].px, cv.k[0].stride, cv.k[0].cap, (force ? 1 : 0) | w2_flag(cv), st,
-                     cv.seg_n, partials, cv, fuse);
+  launch_sweep(kern, grid, wide ? 512 : 256, s, nullptr, nullptr, cv, force ? 1 : 0, st, partials, cv, fuse);
 }
 
 // ================================================================================================
@@ -887,6 +913,27 @@ __device__ __forceinline__ void load_state_lds(const GnState* st, GnState* sm, i
   for (int i = lane; i < kWords; i += 64)
     reinterpret_cast<unsigned long long*>(sm)[i] = reinterpret_cast<const unsigned long long*>(st)[i];
 }
+// the state into LDS as ONE coalesced load, one word per thread of the block's first 256 -- issued in the kernel's first
+// instructions, in flight beside the sweep or the rows; the caller's barrier publishes it
+__device__ __forceinline__ void load_state_words(const GnState* st, GnState* sm) {
+  constexpr int kWords = (int)(sizeof(GnState) / 8);
+  static_assert(kWords <= 256, "one word per thread");
+  if (threadIdx.x < kWords)
+    reinterpret_cast<unsigned long long*>(sm)[threadIdx.x] = reinterpret_cast<const unsigned long long*>(st)[threadIdx.x];
+}
+// a peer (or a block of the grid) never posted: stop the minimiser; the host reports TLOAM_E_RCCL / OS_COMM_ERROR
+__device__ __forceinline__ void stop_comm_error(GnState* st) {
+  if (threadIdx.x == 0) { st->done = 1; st->comm_error = 1; }
+}
+// one wave receives mailbox exchange `id` (mbox_gather) and books it: ctr[0] = id, ctr[1] = 1 once an exchange has timed out
+__device__ __forceinline__ bool mbox_receive(const MboxView& mb, unsigned long long id, double* out /* LDS */, int count, int lane) {
+  const bool ok = mbox_gather(mb, id, out, count, lane);
+  if (lane == 0) {
+    mb.ctr[0] = id;
+    if (!ok) mb.ctr[1] = 1ull;
+  }
+  return ok;
+}
 __global__ __launch_bounds__(64) void k_gn_step(GnState* st, const double* __restrict__ in48, unsigned long long* iter_span) {
   __shared__ double tot[kReduceBuf];
   __shared__ double scr[32];
@@ -911,15 +958,10 @@ __global__ __launch_bounds__(64) void k_gn_step_mbox(GnState* st, MboxView mb, u
   load_state_lds(st, &s_in, threadIdx.x);
   __syncthreads();
   if (s_in.done) return;  // (the sweep of this launch was a no-op on every rank: nothing was posted)
-  const unsigned long long id = __hip_atomic_load(mb.ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1ull;
-  const bool ok = mbox_gather(mb, id, tot, kReduceBuf, threadIdx.x);
-  if (threadIdx.x == 0) {
-    mb.ctr[0] = id;
-    if (!ok) mb.ctr[1] = 1ull;
-  }
+  const bool ok = mbox_receive(mb, mbox_next_id(mb), tot, kReduceBuf, threadIdx.x);
   __syncthreads();
-  if (!ok) {  // a peer never posted: stop the minimiser, the host reports TLOAM_E_RCCL
-    if (threadIdx.x == 0) { st->done = 1; st->comm_error = 1; }
+  if (!ok) {
+    stop_comm_error(st);
     return;
   }
   const bool first = s_in.phase == PH_ITER0;
@@ -932,13 +974,8 @@ void launch_gn_step_mbox(GnState* st, const MboxView& mb, hipStream_t s, unsigne
 // timing aid (tloam_time_sharded_sweep): the gather half of the step without the minimiser
 __global__ __launch_bounds__(64) void k_mbox_gather_only(double* out48, MboxView mb) {
   __shared__ double tot[kMboxSlot];
-  const unsigned long long id = __hip_atomic_load(mb.ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1ull;
-  const bool ok = mbox_gather(mb, id, tot, kReduceBuf, threadIdx.x);
+  mbox_receive(mb, mbox_next_id(mb), tot, kReduceBuf, threadIdx.x);
   if (threadIdx.x < kReduceBuf) out48[threadIdx.x] = tot[threadIdx.x];
-  if (threadIdx.x == 0) {
-    mb.ctr[0] = id;
-    if (!ok) mb.ctr[1] = 1ull;
-  }
 }
 void launch_mbox_gather_only(double* out48, const MboxView& mb, hipStream_t s) {
   hipLaunchKernelGGL(k_mbox_gather_only, dim3(1), dim3(64), 0, s, out48, mb);
@@ -949,15 +986,11 @@ __global__ __launch_bounds__(64) void k_mbox_allreduce(double* buf, int count, M
   const int t = threadIdx.x;
   if (t < count) vals[t] = buf[t];
   __syncthreads();
-  const unsigned long long id = __hip_atomic_load(mb.ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1ull;
+  const unsigned long long id = mbox_next_id(mb);
   mbox_post(mb, id, vals, count, t);
-  const bool ok = mbox_gather(mb, id, vals, count, t);
+  mbox_receive(mb, id, vals, count, t);
   __syncthreads();
   if (t < count) buf[t] = vals[t];
-  if (t == 0) {
-    mb.ctr[0] = id;
-    if (!ok) mb.ctr[1] = 1ull;
-  }
 }
 void launch_mbox_allreduce(double* buf, int count, const MboxView& mb, hipStream_t s) {
   hipLaunchKernelGGL(k_mbox_allreduce, dim3(1), dim3(64), 0, s, buf, count, mb);
@@ -975,12 +1008,7 @@ __global__ __launch_bounds__(kRedThreads) void k_reduce_and_step(const double* _
   // the minimiser state comes in as ONE coalesced load into LDS, in flight together with the partial rows (the
   // step's ~100 scattered field loads were a second memory round trip in front of the serial fp64 chain); the
   // `done` flag of a finished Solve is read from that copy -- no round trip of its own in front of the loads
-  {
-    constexpr int kWords = (int)(sizeof(GnState) / 8);
-    static_assert(kWords <= kRedThreads, "one word per thread");
-    const unsigned long long w = threadIdx.x < kWords ? reinterpret_cast<const unsigned long long*>(st)[threadIdx.x] : 0ull;
-    if (threadIdx.x < kWords) reinterpret_cast<unsigned long long*>(&s_in)[threadIdx.x] = w;
-  }
+  load_state_words(st, &s_in);
 #ifdef TLOAM_STEP_PROFILE
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   if (threadIdx.x == 0) st->dbg[7] = (double)__builtin_readcyclecounter();   // the state has arrived
@@ -1027,63 +1055,39 @@ __global__ __launch_bounds__(64 * W, 2) void k3_sweep_step(const double* __restr
   __shared__ double s_grp[8 * 33];
   __shared__ double tot[kMboxSlot];
   __shared__ GnState s_in;
-  const bool w2 = (unused & 2) != 0;   // (as k3_accumulate's flag word)
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int gw = blockIdx.x * W + wave;
-  ChunkData pre;
-  SingleWork wk{-1, 0};
-  const bool spec = !SINGLE && (gw + 1) * kChunk <= cap0;
-  if (SINGLE) {
-    wk = single_work_of(cv, cap0, gw, lane);
-    single_fetch(cv, seg0, stride0, wk, pre, w2);
-  } else if (spec) {
-    fetch_spec<TLOAM_K3_NT>(seg0, stride0, gw * kChunk + lane * 2, pre, w2);
-  }
-  if (fs.span && blockIdx.x == 0 && threadIdx.x == 0)   // (device-scope: read by the last block, on another XCD)
-    __hip_atomic_store(fs.span, (unsigned long long)wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  {
-    constexpr int kWords = (int)(sizeof(GnState) / 8);
-    static_assert(kWords <= 256, "one word per thread");   // (the first 256 threads of a wide block)
-    if (threadIdx.x < kWords)
-      reinterpret_cast<unsigned long long*>(&s_in)[threadIdx.x] = reinterpret_cast<const unsigned long long*>(st)[threadIdx.x];
-  }
-  if (st->done) return;            // after a tolerance exit the remaining launches are no-ops (uniform over the grid and the ranks)
-  const Rt T = st->Rt_eval;
-  Acc a;
-  if (SINGLE) sweep_single(cv, seg_n, T, wk, pre, a);
-  else sweep_all(cv, seg_n, T, gw, gridDim.x * W, lane, a, pre, spec);
-  const double wtot = wave_reduce_acc(a, lane);
-  if ((lane & 1) == 0) red[wave][lane >> 1] = wtot;
-  __syncthreads();                 // (also publishes s_in)
-  if (!k3_take_ticket<W>(partials, red, fs.ticket)) return;
-  // ---- the last block: every row has reached the coherence point
-  if (fs.span && threadIdx.x == 0) {
-    const unsigned long long t1 = wall_clock64();
-    const unsigned long long t0 = __hip_atomic_load(fs.span, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    fs.span[1] += t1 - t0;
-    fs.span[2] += 1ull;
-  }
-  fold_rows<true>(partials, (int)gridDim.x, s_grp, tot);
-  if (threadIdx.x == 0) __hip_atomic_store(fs.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-armed for the next launch
-  if (threadIdx.x >= 64) return;
-  if (fs.mb.nranks > 0) {
-    // exchange: this rank's totals to every rank, every rank's totals from the local mailbox, added in rank order
-    const unsigned long long id = __hip_atomic_load(fs.mb.ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1ull;
-    mbox_post(fs.mb, id, tot, kReduceBuf, (int)threadIdx.x);
-    const bool ok = mbox_gather(fs.mb, id, tot, kReduceBuf, (int)threadIdx.x);
-    if (threadIdx.x == 0) {
-      fs.mb.ctr[0] = id;
-      if (!ok) fs.mb.ctr[1] = 1ull;
+  SweepStamps ts;
+  sweep_body<SINGLE, W, false>(seg0, stride0, cap0, (unused & 2) != 0 /* as k3_accumulate's flag word */, false, st, seg_n, cv, red,
+                               ts, [&] {
+    if (fs.span && blockIdx.x == 0 && threadIdx.x == 0)   // (device-scope: read by the last block, on another XCD)
+      __hip_atomic_store(fs.span, (unsigned long long)wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    load_state_words(st, &s_in);   // (the first 256 threads of a wide block; the body's barrier publishes it)
+  }, [&] {
+    if (!k3_take_ticket<W>(partials, red, fs.ticket)) return;
+    // ---- the last block: every row has reached the coherence point
+    if (fs.span && threadIdx.x == 0) {
+      const unsigned long long t1 = wall_clock64();
+      const unsigned long long t0 = __hip_atomic_load(fs.span, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      fs.span[1] += t1 - t0;
+      fs.span[2] += 1ull;
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // one wave: its LDS stores are in order
-    if (!ok) {  // a peer never posted: stop the minimiser, the host reports TLOAM_E_RCCL
-      if (threadIdx.x == 0) { st->done = 1; st->comm_error = 1; }
-      return;
+    fold_rows<true>(partials, (int)gridDim.x, s_grp, tot);
+    if (threadIdx.x == 0) __hip_atomic_store(fs.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-armed for the next launch
+    if (threadIdx.x >= 64) return;
+    if (fs.mb.nranks > 0) {
+      // exchange: this rank's totals to every rank, every rank's totals from the local mailbox, added in rank order
+      const unsigned long long id = mbox_next_id(fs.mb);
+      mbox_post(fs.mb, id, tot, kReduceBuf, (int)threadIdx.x);
+      const bool ok = mbox_receive(fs.mb, id, tot, kReduceBuf, (int)threadIdx.x);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // one wave: its LDS stores are in order
+      if (!ok) {
+        stop_comm_error(st);
+        return;
+      }
     }
-  }
-  const bool first = s_in.phase == PH_ITER0;
-  gn_consume(st, tot, (int)threadIdx.x, &s_in, s_grp /* free again: the fold is over */);
-  if (threadIdx.x == 0) iter_span_note(fs.iter_span, first);
+    const bool first = s_in.phase == PH_ITER0;
+    gn_consume(st, tot, (int)threadIdx.x, &s_in, s_grp /* free again: the fold is over */);
+    if (threadIdx.x == 0) iter_span_note(fs.iter_span, first);
+  });
 }
 void launch_k3_step(const CorrView& cv, GnState* st, double* partials, int grid, bool single, bool wide, int* ticket, unsigned long long* span,
                     const MboxView* mb_or_null, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop, unsigned long long* iter_span) {
@@ -1094,13 +1098,7 @@ void launch_k3_step(const CorrView& cv, GnState* st, double* partials, int grid,
   fs.span = span;
   fs.iter_span = iter_span;
   if (mb_or_null) fs.mb = *mb_or_null;
-  if (ev_start && ev_stop) {
-    hipExtLaunchKernelGGL(kern, dim3(grid), dim3(wide ? 512 : 256), 0, s, ev_start, ev_stop, 0, (const double*)cv.k[0].px, cv.k[0].stride,
-                          cv.k[0].cap, w2_flag(cv), st, cv.seg_n, partials, cv, fs);
-  } else {
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(wide ? 512 : 256), 0, s, (const double*)cv.k[0].px, cv.k[0].stride, cv.k[0].cap, w2_flag(cv), st, cv.seg_n,
-                       partials, cv, fs);
-  }
+  launch_sweep(kern, grid, wide ? 512 : 256, s, ev_start, ev_stop, cv, 0, st, partials, cv, fs);
 }
 
 // ---- one GN iteration of a KITTI-size set in ONE launch ----------------------------------------------------------
@@ -1189,9 +1187,8 @@ __global__ __launch_bounds__(256, 1) void k_sweep_step_small(const double* __res
 }
 void launch_sweep_step_small(const CorrView& cv, GnState* st, double* partials, int* ticket, int grid, hipStream_t s,
                              unsigned long long* iter_span) {
-  const int tagged = grid <= kTaggedRows ? 1 : 0;
-  hipLaunchKernelGGL(k_sweep_step_small, dim3(grid), dim3(256), 0, s, (const double*)cv.k[0].px, cv.k[0].stride, cv.k[0].cap, tagged | w2_flag(cv), st,
-                     cv.seg_n, partials, ticket, cv, iter_span);
+  launch_sweep(k_sweep_step_small, grid, 256, s, nullptr, nullptr, cv, grid <= kTaggedRows ? 1 : 0 /* tagged */, st, partials, ticket, cv,
+               iter_span);
 }
 #include "tl_prep.hpp"   // SolvePrep: the Solve's own caps / compaction / refresh (kind_set_of, self_compact, self_refresh)
 
