@@ -384,6 +384,53 @@ int tloam_extract_planar_sphere(tloam_ctx* ctx, const tloam_feature_config* cfg,
                                 size_t* n_planar_submap, int32_t* sphere_scan_index, size_t* n_sphere_scan,
                                 int32_t* sphere_submap_index, size_t* n_sphere_submap);
 
+/* ---- segmentation node on the device (additive to ABI 8) -----------------------------------------
+ * Segmentation::spinOnce (src/models/segmentation/segmentation.cpp:40-93): near / non-finite filter, rings, height split,
+ * regional ground fit, DCVC clustering, edge / general extraction -- one raw scan in, what the node publishes out, as index
+ * lists into the caller's array in the reference's output order (DESIGN.md section 11 declares the orders the reference
+ * leaves open, and its one deviation: DCVC clusters are the connected components of its neighbour edges taken as
+ * undirected).  Only sensor_model 64 and quadrant 4 are supported (TLOAM_E_INVALID otherwise). */
+typedef struct tloam_seg_config {
+  /* velodyne: */
+  int32_t sensor_model;        /* 64 */
+  int32_t reserved0;
+  double scan_period;          /* 0.1 (unused by the stage) */
+  double sensor_height;        /* 1.73 */
+  double vertical_res;         /* 0.4 */
+  double init_angle;           /* -24.9 */
+  double sensor_min_range;     /* 1.0 */
+  double sensor_max_range;     /* 120.0 */
+  double near_dis;             /* 3.0 (points closer than near_dis^2 = 9 m are dropped, :485) */
+  /* groundSeg: */
+  int32_t quadrant;            /* 4 */
+  int32_t num_sec;             /* 3 */
+  double dis;                  /* 0.3 */
+  int32_t max_iter;            /* 3 */
+  int32_t ground_seed_num;     /* 20 */
+  int32_t ring_min_num;        /* 131 */
+  int32_t reserved1;
+  /* DCVC: */
+  double start_r;              /* 0.35 */
+  double delta_r;              /* 0.0004 */
+  double delta_p;              /* 1.2 */
+  double delta_a;              /* 1.2 */
+  int32_t min_seg;             /* 80 */
+  int32_t reserved2;
+} tloam_seg_config;
+void tloam_seg_default_config(tloam_seg_config* cfg);
+/* One scan (AoS, firing order).  Every output may be NULL; the index arrays hold up to n entries, boxes up to
+ * box_capacity x 6 doubles (centre xyz, dimensions xyz per kept cluster, in label order; *n_boxes is the cluster count).
+ * ring[n]: beam id per input point, -1 where the first filter removed it.  object_index: object_scan before clustering.
+ * segmented_label: the 1-based rank of the point's cluster.  The context counts its calls: the first one starts DCVC's
+ * minPolar / maxPolar at 5.0, every later one at 0.0 (the reference's header value, then resetParams).
+ * TLOAM_E_TOO_FEW_POINTS when object_scan is empty or no cluster survives (the node publishes nothing): the counts of the
+ * stages that completed are written, the rest are 0; the call still counts as a frame. */
+int tloam_segment(tloam_ctx* ctx, const tloam_seg_config* cfg, const double* xyz_aos, size_t n, int32_t* ring,
+                  int32_t* ground_index, size_t* n_ground, int32_t* object_index, size_t* n_object,
+                  int32_t* segmented_index, int32_t* segmented_label, size_t* n_segmented, int32_t* edge_index,
+                  size_t* n_edge, int32_t* general_index, size_t* n_general, double* boxes, size_t box_capacity,
+                  size_t* n_boxes);
+
 /* ---- multi-GPU: correspondence set sharded over ranks, one all-reduce per sweep --------
  * (nothing in the reference).  Call before set_source / set_correspondences.
  * (a) native RCCL over xGMI: unique_id = the 128 bytes of an ncclUniqueId made on rank 0

@@ -141,6 +141,7 @@ void tloam_destroy(tloam_ctx* c) {
   c->frame_store.clear();
   c->submap.release();
   c->feat.release();
+  c->seg.release();
   if (c->h_state) (void)hipHostFree(c->h_state);
   if (c->h_mirror) (void)hipHostFree(c->h_mirror);
   if (c->h_small) (void)hipHostFree(c->h_small);

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "tl_common.hpp"
+#include "tl_seg.hpp"
 
 
 namespace tlh {
@@ -144,6 +145,25 @@ struct FeatBuffers {
   }
 };
 
+// device buffers of the segmentation node (tl_api_seg.hip; grow-only, kept across calls) and its frame counter
+struct SegBuffers {
+  DBuf<double> aos, pol_val, bounds, boxes, cv;
+  DBuf<tl::SegCtl> ctl;
+  DBuf<int> ring, cur, cur_reg, ng, reg_mem, reg_g, reg_v, ground, obj, vox, hkey, hval, parent, csize, croot, cl_root, cl_off,
+      cl_size, seg_local, seg_orig, seg_label, ring_list, sorted, genbuf, edge_sec, sec_cnt, sec_base, edge, general;
+  DBuf<unsigned char> reg_flag, picked;
+  unsigned long long frames = 0;   // calls so far: the first one seeds minPolar / maxPolar with 5.0, later ones with 0.0
+  void release() {
+    DBuf<double>* d[] = {&aos, &pol_val, &bounds, &boxes, &cv};
+    for (auto* b : d) b->release();
+    DBuf<int>* i[] = {&ring, &cur, &cur_reg, &ng, &reg_mem, &reg_g, &reg_v, &ground, &obj, &vox, &hkey, &hval, &parent, &csize,
+                      &croot, &cl_root, &cl_off, &cl_size, &seg_local, &seg_orig, &seg_label, &ring_list, &sorted, &genbuf,
+                      &edge_sec, &sec_cnt, &sec_base, &edge, &general};
+    for (auto* b : i) b->release();
+    ctl.release(); reg_flag.release(); picked.release();
+  }
+};
+
 // up to four SoA clouds (x, y, z, n) a search grid is built over -- the registered targets, or any other cloud
 struct CloudRef { const double *x, *y, *z; size_t n; };
 }  // namespace tlh
@@ -154,6 +174,7 @@ struct tloam_ctx {
   tloam_tls_config cfg;
   SubmapState submap;
   FeatBuffers feat;
+  SegBuffers seg;
   int device = 0;
   hipStream_t stream = nullptr;
   KindData kd[kKinds];

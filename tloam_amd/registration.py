@@ -47,6 +47,17 @@ class FeatureConfig(C.Structure):
                 ("planar_vertic_thres", C.c_double)]
 
 
+class SegConfig(C.Structure):
+    """tloam_seg_config: the `velodyne`, `groundSeg` and `DCVC` blocks of config/mapping/segmentation.yaml."""
+    _fields_ = [("sensor_model", C.c_int32), ("reserved0", C.c_int32), ("scan_period", C.c_double),
+                ("sensor_height", C.c_double), ("vertical_res", C.c_double), ("init_angle", C.c_double),
+                ("sensor_min_range", C.c_double), ("sensor_max_range", C.c_double), ("near_dis", C.c_double),
+                ("quadrant", C.c_int32), ("num_sec", C.c_int32), ("dis", C.c_double), ("max_iter", C.c_int32),
+                ("ground_seed_num", C.c_int32), ("ring_min_num", C.c_int32), ("reserved1", C.c_int32),
+                ("start_r", C.c_double), ("delta_r", C.c_double), ("delta_p", C.c_double), ("delta_a", C.c_double),
+                ("min_seg", C.c_int32), ("reserved2", C.c_int32)]
+
+
 class TlsConfig(C.Structure):
     """tloam_tls_config: the 16 keys of the `TLS:` block (config/mapping/lidar_odometry.yaml:23-39)."""
     _fields_ = [
@@ -162,6 +173,9 @@ def load_library():
         "tloam_pca_info": (C.c_int, [vp, C.POINTER(FeatureConfig), dp, sz, dp, dp, dp, dp, ip, ip]),
         "tloam_extract_planar_sphere": (C.c_int, [vp, C.POINTER(FeatureConfig), dp, sz, ip, C.POINTER(sz), ip,
                                                   C.POINTER(sz), ip, C.POINTER(sz), ip, C.POINTER(sz)]),
+        "tloam_seg_default_config": (None, [C.POINTER(SegConfig)]),
+        "tloam_segment": (C.c_int, [vp, C.POINTER(SegConfig), dp, sz, ip, ip, C.POINTER(sz), ip, C.POINTER(sz), ip, ip,
+                                    C.POINTER(sz), ip, C.POINTER(sz), ip, C.POINTER(sz), dp, sz, C.POINTER(sz)]),
         "tloam_rccl_unique_id": (C.c_int, [vp]),
         "tloam_comm_init_rccl": (C.c_int, [vp, C.c_int, C.c_int, vp]),
         "tloam_comm_init_callback": (C.c_int, [vp, C.c_int, C.c_int, ALLREDUCE_FN, vp]),
@@ -189,7 +203,8 @@ EXPORTED_SYMBOLS = (
     "tloam_time_accumulate", "tloam_time_sharded_sweep", "tloam_time_build", "tloam_k3_timer", "tloam_k3_timer_all", "tloam_k3_span", "tloam_gn_iter_timer", "tloam_time_read_stream", "tloam_get_info", "tloam_debug_state", "tloam_debug_partials", "tloam_debug_se3",
     "tloam_debug_raise_fault",
     "tloam_submap_default_config", "tloam_submap_init", "tloam_submap_update", "tloam_get_target",
-    "tloam_feature_default_config", "tloam_pca_info", "tloam_extract_planar_sphere", "tloam_rccl_unique_id", "tloam_comm_init_rccl",
+    "tloam_feature_default_config", "tloam_pca_info", "tloam_extract_planar_sphere",
+    "tloam_seg_default_config", "tloam_segment", "tloam_rccl_unique_id", "tloam_comm_init_rccl",
     "tloam_comm_mailbox_export", "tloam_comm_init_mailbox",
     "tloam_comm_init_callback", "tloam_shard_range", "tloam_shard_ranges_frame", "tloam_se3_exp", "tloam_se3_log", "tloam_se3_plus",
 )
@@ -444,6 +459,32 @@ class HipRegistration:
         self._check(rc, "tloam_extract_planar_sphere")
         return tuple(l[: k.value].copy() for l, k in zip(lists, cnt))
 
+    # ---- segmentation node (Segmentation::spinOnce, segmentation.cpp:40-93)
+    def segment(self, xyz, cfg: SegConfig | None = None):
+        """one raw scan -> dict: status (0, or -2 when the node publishes nothing), ring (per input point, -1 filtered),
+        ground, object, segmented + label, edge, general (index lists into `xyz`), boxes (clusters x 6).  Raises on
+        any other status."""
+        cfg = cfg or default_seg_config()
+        a = _aos(xyz)
+        n = len(a)
+        m = max(n, 1)
+        ring = np.zeros(m, np.int32)
+        lists = {k: np.zeros(m, np.int32) for k in ("ground", "object", "segmented", "label", "edge", "general")}
+        boxes = np.zeros((m, 6))
+        cnt = {k: C.c_size_t(0) for k in ("ground", "object", "segmented", "edge", "general", "boxes")}
+        rc = self.L.tloam_segment(self.h, C.byref(cfg), _dp(a), n, _ip(ring), _ip(lists["ground"]), C.byref(cnt["ground"]),
+                                  _ip(lists["object"]), C.byref(cnt["object"]), _ip(lists["segmented"]), _ip(lists["label"]),
+                                  C.byref(cnt["segmented"]), _ip(lists["edge"]), C.byref(cnt["edge"]), _ip(lists["general"]),
+                                  C.byref(cnt["general"]), _dp(boxes), m, C.byref(cnt["boxes"]))
+        if rc not in (0, -2):
+            self._check(rc, "tloam_segment")
+        out = {"status": rc, "ring": ring[:n].copy()}
+        for k in ("ground", "object", "segmented", "edge", "general"):
+            out[k] = lists[k][: cnt[k].value].copy()
+        out["label"] = lists["label"][: cnt["segmented"].value].copy()
+        out["boxes"] = boxes[: cnt["boxes"].value].copy()
+        return out
+
     def fitness(self):
         f, r = C.c_double(0), C.c_double(0)
         rc = self.L.tloam_fitness(self.h, C.byref(f), C.byref(r))
@@ -611,6 +652,16 @@ def default_feature_config(**over) -> FeatureConfig:
     cfg = FeatureConfig()
     load_library().tloam_feature_default_config(C.byref(cfg))
     for k, v in over.items():
+        setattr(cfg, k, v)
+    return cfg
+
+
+def default_seg_config(**over) -> SegConfig:
+    cfg = SegConfig()
+    load_library().tloam_seg_default_config(C.byref(cfg))
+    for k, v in over.items():
+        if not hasattr(cfg, k):
+            raise KeyError(k)
         setattr(cfg, k, v)
     return cfg
 

@@ -3,7 +3,8 @@ scanMatching that BASELINE.json configs[0]/[1] name literally (SURVEY 8(f) next-
 data is present:
 
     read_velodyne_bin                 readVelodyneToO3d                      read_file.hpp:307-327
-      -> label_scan                   (stand-in, see below)
+      -> label_scan                   (stand-in, see below; the default)
+         or tloam_segment             Segmentation::spinOnce                 segmentation.cpp:40-93        [device]
       -> tloam_extract_planar_sphere  featureExtract::extractPlanarSphere    feature_extract.cpp:133-197   [device]
       -> tloam_set_source_frame / tloam_scan_match                           front_end.cpp:314-322          [device]
       -> tloam_submap_update          FrontEnd::updateSubmap                 front_end.cpp:201-275          [device]
@@ -13,7 +14,12 @@ data is present:
 scope): it is a small geometric labeller -- ground by height over the lowest returns, edge = tall,
 isolated columns of a 2-D occupancy grid, the rest handed to the PCA feature extraction -- that only exists so that
 the stages around it can be driven end to end.  Trajectories produced with it are therefore not comparable with the
-reference's doc/tloam_XX.txt beyond plausibility; swapping in a real segmentation changes nothing downstream.
+reference's doc/tloam_XX.txt beyond plausibility.
+
+`segmenter="device"` swaps in the reference's segmentation node on the device (`tloam_segment`):
+ground = its /ground_points, edge = /edge_points, the PCA features come from /general_points.  Everything downstream
+stays as it is, `_voxel_first` included (the stand-in for FrontEnd::processCloud's VoxelDownSample of the edge and
+ground clouds, front_end.cpp:183,186).  A frame the node publishes nothing for (TLOAM_E_TOO_FEW_POINTS) raises.
 
 Host-side glue only (numpy + the C ABI through tloam_amd.registration); no oracle, no CPU fallback of any device stage."""
 from __future__ import annotations
@@ -69,10 +75,26 @@ def label_scan(xyz: np.ndarray, sensor_height: float = 1.73, max_range: float = 
     return (_voxel_first(xyz[ground_m], 0.3), _voxel_first(rest[is_edge], 0.1), np.ascontiguousarray(rest[~is_edge]))
 
 
-def features_of_scan(H, xyz: np.ndarray, feature_cfg=None, sensor_height: float = 1.73):
+def segment_scan(H, xyz: np.ndarray, seg_cfg=None):
+    """-> (ground, edge, general) from the device segmentation node, ground / edge voxel-thinned like label_scan's"""
+    S = H.segment(xyz, seg_cfg)
+    if S["status"] != 0:
+        raise RuntimeError("tloam_segment: the node publishes nothing for this scan (TLOAM_E_TOO_FEW_POINTS)")
+    return (_voxel_first(np.ascontiguousarray(xyz[S["ground"]]), 0.3), _voxel_first(np.ascontiguousarray(xyz[S["edge"]]), 0.1),
+            np.ascontiguousarray(xyz[S["general"]]))
+
+
+def features_of_scan(H, xyz: np.ndarray, feature_cfg=None, sensor_height: float = 1.73, segmenter: str = "label_scan",
+                     seg_cfg=None):
     """One raw scan -> the clouds FrontEnd hands on (front_end.cpp:183-198): scan-side Frame (planar_scan, ground,
-    edge, sphere_scan) and the submap-side selections (planar_submap, sphere_submap).  PCA lists on the device."""
-    ground, edge, other = label_scan(xyz, sensor_height)
+    edge, sphere_scan) and the submap-side selections (planar_submap, sphere_submap).  PCA lists on the device.
+    segmenter: "label_scan" (the stand-in, default) or "device" (tloam_segment)."""
+    if segmenter == "label_scan":
+        ground, edge, other = label_scan(xyz, sensor_height)
+    elif segmenter == "device":
+        ground, edge, other = segment_scan(H, xyz, seg_cfg)
+    else:
+        raise ValueError(f"unknown segmenter {segmenter!r}")
     ps, pm, ss, sm = H.extract_planar_sphere(other, feature_cfg)
     sel = lambda idx: np.ascontiguousarray(other[np.asarray(idx, np.int64) % max(len(other), 1)]) if len(other) else other  # noqa: E731
     planar_scan, planar_submap, sphere_scan, sphere_submap = sel(ps), sel(pm), sel(ss), sel(sm)
@@ -94,17 +116,18 @@ def list_scans(path: str):
 
 
 def replay(H, scan_files, out_poses: str | None = None, feature_cfg=None, sensor_height: float = 1.73, max_frames=None,
-           sync=None):
+           sync=None, segmenter: str = "label_scan", seg_cfg=None):
     """FrontEnd::updateLidarOdometry (front_end.cpp:278-337) over a list of `.bin` scans on the device.  Returns the
-    poses (map <- sensor, 4x4) and per-stage host-to-host timings in ms."""
+    poses (map <- sensor, 4x4) and per-stage host-to-host timings in ms.  A scan may also be given as an (N, 3) array.
+    segmenter: see features_of_scan."""
     poses, t_feat, t_match, t_submap, iters = [], [], [], [], 0
     files = scan_files[: max_frames] if max_frames else scan_files
     out = open(out_poses, "w") if out_poses else None
     try:
         for f, path in enumerate(files):
-            xyz, _ = kitti_io.read_velodyne_bin(path)
+            xyz = np.asarray(path, np.float64).reshape(-1, 3) if isinstance(path, np.ndarray) else kitti_io.read_velodyne_bin(path)[0]
             t0 = time.perf_counter()
-            frame, planar_submap, sphere_submap = features_of_scan(H, xyz, feature_cfg, sensor_height)
+            frame, planar_submap, sphere_submap = features_of_scan(H, xyz, feature_cfg, sensor_height, segmenter, seg_cfg)
             t1 = time.perf_counter()
             if f == 0:                                   # first frame: the submap IS the scan (front_end.cpp:283-304)
                 H.submap_init(planar_submap, sphere_submap, frame.edge, frame.ground)
@@ -115,7 +138,8 @@ def replay(H, scan_files, out_poses: str | None = None, feature_cfg=None, sensor
                 H.set_input_source(frame)
                 rc, T, st = H.scan_match(pred)
                 if rc not in (0, -7):
-                    raise RuntimeError(f"frame {f} ({os.path.basename(path)}): scan_match status {rc}")
+                    name = os.path.basename(path) if isinstance(path, str) else "array"
+                    raise RuntimeError(f"frame {f} ({name}): scan_match status {rc}")
                 iters += st["gn_sweeps"]
                 t2 = time.perf_counter()
                 H.submap_update(T, planar_submap, sphere_submap, frame.edge, frame.ground)
