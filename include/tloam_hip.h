@@ -431,6 +431,53 @@ int tloam_segment(tloam_ctx* ctx, const tloam_seg_config* cfg, const double* xyz
                   size_t* n_edge, int32_t* general_index, size_t* n_general, double* boxes, size_t box_capacity,
                   size_t* n_boxes);
 
+/* ---- per-scan voxel grid and the whole odometry frame on the device (additive to ABI 8) ----------
+ * tloam_voxel_down_sample: PointCloud2::VoxelDownSample (PointCloud2.cpp:358-403) of one cloud -- bounds = the cloud's
+ * min / max -+ voxel / 2, every occupied voxel emits the mean of its points (summed in index order), voxels in order of first
+ * occurrence (the order the submap path declares).  *n_out receives the size even when capacity is too small (then nothing is
+ * copied and TLOAM_E_INVALID is returned).  voxel <= 0 and "voxel_size is too small" (a voxel index beyond 2^21 on an axis)
+ * are TLOAM_E_INVALID, as in tloam_submap_*. */
+int tloam_voxel_down_sample(tloam_ctx* ctx, double voxel, const double* xyz_aos, size_t n, double* out_aos, size_t capacity,
+                            size_t* n_out);
+
+/* FrontEnd (front_end.cpp:181-199, :278-337) fed by Segmentation::spinOnce: the stage configurations of the shipped yaml files
+ * (segmentation.yaml, feature.yaml, lidar_odometry.yaml) and the one key the frame adds, edge_down_sample
+ * (lidar_odometry.yaml:8).  The per-scan ground voxel is submap.ground_down_sample (lidar_odometry.yaml:6). */
+typedef struct tloam_odom_config {
+  tloam_seg_config seg;
+  tloam_feature_config feature;
+  tloam_submap_config submap;
+  double edge_down_sample;     /* 0.1 */
+} tloam_odom_config;
+void tloam_odom_default_config(tloam_odom_config* cfg);
+
+/* What one tloam_odometry_frame did.  Cloud sizes are those of the frame's stages (0 where a stage did not run).
+ * h2d_bytes / d2h_bytes / host_syncs count the copy commands and host waits of the frame's own stages around the scan match
+ * (the match's own traffic is that of tloam_scan_match and is not counted): DESIGN.md section 12. */
+typedef struct tloam_odom_stats {
+  tloam_stats match;           /* the scan match of the frame (zero on the first frame) */
+  int64_t frame;               /* frames accepted since the reset before this one: 0 = the first frame */
+  int64_t n_ground, n_edge, n_general;     /* segmentation: /ground_points, /edge_points, /general_points */
+  int64_t n_edge_ds, n_ground_ds;          /* processCloud's VoxelDownSample of edge (edge_down_sample) and ground */
+  int64_t n_planar_scan, n_sphere_scan, n_planar_submap, n_sphere_submap;   /* extractPlanarSphere's selections */
+  int64_t h2d_bytes, d2h_bytes, host_syncs;
+} tloam_odom_stats;
+
+/* FrontEnd::setInitPose plus a fresh odometry state: the next frame is the first one.  cfg NULL: the defaults; init NULL:
+ * identity.  TLOAM_E_INVALID for a configuration a stage refuses or a non-finite init pose. */
+int tloam_odometry_reset(tloam_ctx* ctx, const tloam_odom_config* cfg, const double init_pose_colmajor[16]);
+/* One raw scan (AoS, firing order) -> the pose of FrontEnd::updateLidarOdometry.  First frame after a reset: segment, PCA,
+ * tloam_submap_init(planar submap selection, sphere submap selection, raw edge, raw ground); the pose is the init pose.  Later
+ * frames: segment, processCloud (voxel ground / edge, PCA, selections), source frame, scan match from the constant-velocity
+ * prediction, tloam_submap_update.  Only the raw scan crosses to the device; every other cloud stays in HBM.
+ * TLOAM_E_TOO_FEW_POINTS: segmentation published nothing, or a cloud the frame hands on (the four source clouds and four
+ * targets of the match; on the first frame the four submap clouds) has fewer than 10 points -- the frame is skipped and the
+ * odometry state (poses, submap, frame index) is unchanged.  TLOAM_E_WEIGHT_RANGE as tloam_scan_match: pose and stats are
+ * written and the frame counts.  TLOAM_E_NOT_READY before tloam_odometry_reset; TLOAM_E_INVALID on a context with nranks > 1.
+ * Afterwards tloam_get_target / tloam_fitness / tloam_get_correspondences / tloam_get_weights describe this frame. */
+int tloam_odometry_frame(tloam_ctx* ctx, const double* xyz_aos, size_t n, double pose_out_colmajor[16],
+                         tloam_odom_stats* stats);
+
 /* ---- multi-GPU: correspondence set sharded over ranks, one all-reduce per sweep --------
  * (nothing in the reference).  Call before set_source / set_correspondences.
  * (a) native RCCL over xGMI: unique_id = the 128 bytes of an ncclUniqueId made on rank 0

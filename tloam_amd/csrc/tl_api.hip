@@ -142,6 +142,7 @@ void tloam_destroy(tloam_ctx* c) {
   c->submap.release();
   c->feat.release();
   c->seg.release();
+  c->odom.release();
   if (c->h_state) (void)hipHostFree(c->h_state);
   if (c->h_mirror) (void)hipHostFree(c->h_mirror);
   if (c->h_small) (void)hipHostFree(c->h_small);

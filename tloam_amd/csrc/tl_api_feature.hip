@@ -15,19 +15,21 @@ void tloam_feature_default_config(tloam_feature_config* cfg) {
   cfg->planar_vertic_thres = 0.25;
 }
 
-namespace {
-// calculatePCAInfo on the device; the per-point arrays stay in F
-int feature_pca(tloam_ctx* c, const tloam_feature_config& cfg, const double* xyz, size_t n, FeatBuffers& F, FeatArgs* out) {
+}  // extern "C"
+
+namespace tlh {
+// the per-point arrays of calculatePCAInfo for n points, the input cloud (F.aos) among them
+int feature_reserve(tloam_ctx* c, const tloam_feature_config& cfg, size_t n, FeatBuffers& F) {
   if (cfg.K < 3 || cfg.K > 20 || !(cfg.radius >= 0.0)) return TLOAM_E_INVALID;  // assert(r_ >= 0.0 && K_ >= 3) :55
   const size_t m = std::max<size_t>(n, 1);
   HIPC(c, F.aos.reserve(3 * m)); HIPC(c, F.x.reserve(m)); HIPC(c, F.y.reserve(m)); HIPC(c, F.z.reserve(m));
   HIPC(c, F.flatness.reserve(m)); HIPC(c, F.cvr.reserve(m)); HIPC(c, F.sphericity.reserve(m)); HIPC(c, F.normal.reserve(3 * m));
   HIPC(c, F.num_sum.reserve(m)); HIPC(c, F.neigh.reserve(m * (size_t)cfg.K));
-  if (n > 0) {
-    // (the borrowed cloud straight through the copy command: for 2.4 MB that beats pinned staging + copy kernel, 0.425 against
-    //  0.478 ms per call, three interleaved rounds -- the staging pays below ~1 MB, where the command's fixed cost dominates)
-    HIPC(c, hipMemcpyAsync(F.aos.p, xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice, c->stream));
-  }
+  return TLOAM_OK;
+}
+
+// calculatePCAInfo on the cloud resident in F.aos; the per-point arrays stay in F.  One host synchronisation (the bounds)
+int feature_pca_run(tloam_ctx* c, const tloam_feature_config& cfg, size_t n, FeatBuffers& F, FeatArgs* out) {
   GridView views[kKinds];
   // (the reference's assert admits r_ == 0: SearchHybrid then finds nobody -- not even the point itself, its squared distance 0
   //  is not below 0 -- and every point comes out with zero neighbours.  The grid still needs cells of SOME size: the walk's own
@@ -71,7 +73,40 @@ int feature_pca(tloam_ctx* c, const tloam_feature_config& cfg, const double* xyz
   *out = A;
   return TLOAM_OK;
 }
+
+// the candidate lists of extractPlanarSphere ranked on the device (FeatRankOut in F.out, the sizes in F.scan[n]); no host wait
+int feature_select_launch(tloam_ctx* c, const tloam_feature_config& cfg, size_t n, FeatBuffers& F, const FeatArgs& A) {
+  hipError_t e = hipSuccess;
+  if ((e = F.flags.reserve(n + 1)) == hipSuccess && (e = F.scan.reserve(n + 1)) == hipSuccess &&
+      (e = F.scan_tmp.reserve(scan_tmp_elems(n + 1))) == hipSuccess && (e = F.f2.reserve(2 * n)) == hipSuccess &&
+      (e = F.gf.reserve(2 * n)) == hipSuccess && (e = F.out.reserve(3 * n + 2)) == hipSuccess &&
+      (e = F.idx2.reserve(2 * n)) == hipSuccess && (e = F.gi.reserve(2 * n)) == hipSuccess &&
+      (e = F.bkt.reserve(2 * n)) == hipSuccess && (e = F.pos.reserve(2 * n)) == hipSuccess &&
+      (e = F.rank_ctl.reserve(1)) == hipSuccess) {
+    const FeatSelect S{cfg.cvr_submap, cfg.planar_submap_thres, cfg.planar_vertic_thres};
+    launch_feat_select(A, S, F.flags.p, F.scan.p, F.scan_tmp.p, F.f2.p, F.idx2.p, F.rank_ctl.p, F.bkt.p, F.pos.p, F.gf.p, F.gi.p,
+                       F.out.p, c->stream);
+  }
+  if (e != hipSuccess) { c->last_error = hipGetErrorString(e); return TLOAM_E_HIP; }
+  return TLOAM_OK;
+}
+}  // namespace tlh
+
+namespace {
+// calculatePCAInfo of a host cloud
+int feature_pca(tloam_ctx* c, const tloam_feature_config& cfg, const double* xyz, size_t n, FeatBuffers& F, FeatArgs* out) {
+  const int rc = feature_reserve(c, cfg, n, F);
+  if (rc != TLOAM_OK) return rc;
+  if (n > 0) {
+    // (the borrowed cloud straight through the copy command: for 2.4 MB that beats pinned staging + copy kernel, 0.425 against
+    //  0.478 ms per call, three interleaved rounds -- the staging pays below ~1 MB, where the command's fixed cost dominates)
+    HIPC(c, hipMemcpyAsync(F.aos.p, xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice, c->stream));
+  }
+  return feature_pca_run(c, cfg, n, F, out);
+}
 }  // namespace
+
+extern "C" {
 
 int tloam_pca_info(tloam_ctx* c, const tloam_feature_config* cfg, const double* xyz, size_t n, double* flatness,
                    double* cvr, double* sphericity, double* normal, int32_t* num_sum, int32_t* neigh) {
@@ -111,16 +146,9 @@ int tloam_extract_planar_sphere(tloam_ctx* c, const tloam_feature_config* cfg, c
   size_t np = 0, ns = 0;
   unsigned long long total = 0;
   if (rc == TLOAM_OK) {
+    rc = feature_select_launch(c, *cfg, n, F, A);
     hipError_t e = hipSuccess;
-    if ((e = F.flags.reserve(n + 1)) == hipSuccess && (e = F.scan.reserve(n + 1)) == hipSuccess &&
-        (e = F.scan_tmp.reserve(scan_tmp_elems(n + 1))) == hipSuccess && (e = F.f2.reserve(2 * n)) == hipSuccess &&
-        (e = F.gf.reserve(2 * n)) == hipSuccess && (e = F.out.reserve(3 * n + 2)) == hipSuccess &&
-        (e = F.idx2.reserve(2 * n)) == hipSuccess && (e = F.gi.reserve(2 * n)) == hipSuccess &&
-        (e = F.bkt.reserve(2 * n)) == hipSuccess && (e = F.pos.reserve(2 * n)) == hipSuccess &&
-        (e = F.rank_ctl.reserve(1)) == hipSuccess) {
-      const FeatSelect S{cfg->cvr_submap, cfg->planar_submap_thres, cfg->planar_vertic_thres};
-      launch_feat_select(A, S, F.flags.p, F.scan.p, F.scan_tmp.p, F.f2.p, F.idx2.p, F.rank_ctl.p, F.bkt.p, F.pos.p, F.gf.p, F.gi.p,
-                         F.out.p, c->stream);
+    if (rc == TLOAM_OK) {
       e = hipMemcpyAsync(&total, F.scan.p + n, sizeof(total), hipMemcpyDeviceToHost, c->stream);
       if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
       np = (size_t)(total >> 32); ns = (size_t)(total & 0xffffffffull);

@@ -87,11 +87,7 @@ int check_device_faults(tloam_ctx* c) {
 // counts in doubles.
 static int stage_fill(tloam_ctx* c, const double* const parts[], const size_t counts[], int nparts, size_t offs[], size_t* total_out,
                       int* half_out) {
-  size_t total = 0;
-  for (int i = 0; i < nparts; ++i) {
-    offs[i] = total;
-    total += counts[i] + (counts[i] & 1u);   // the next piece starts on an even double
-  }
+  const size_t total = staged_offsets(counts, nparts, offs);
   *total_out = total;
   *half_out = -1;
   if (total == 0) return TLOAM_OK;
@@ -152,6 +148,14 @@ int stage_release(tloam_ctx* c, int half, bool completed) {
   HIPC(c, hipEventRecord(c->stage_ev[half], c->stream));
   c->stage_busy[half] = true;
   return TLOAM_OK;
+}
+size_t staged_offsets(const size_t counts[], int nparts, size_t offs[]) {
+  size_t total = 0;
+  for (int i = 0; i < nparts; ++i) {
+    offs[i] = total;
+    total += counts[i] + (counts[i] & 1u);   // the next piece starts on an even double
+  }
+  return total;
 }
 size_t staged_size(const size_t counts[], int nparts) {   // doubles the pieces take up, padding included
   size_t total = 0;
@@ -346,6 +350,35 @@ void exchange_clouds(tloam_ctx* c, FrameClouds& F) {
   std::swap(c->src_pack, F.src_pack);
   c->have_build = false;
 }
+// setInputSource(const Frame&) in two halves around the transfer: this rank's blocks of the four clouds and the size of the
+// registered frame's block (cnt4: doubles per kind, laid out as staged_offsets lays them out) ...
+int source_frame_reserve(tloam_ctx* c, const size_t n[4], size_t cnt4[4]) {
+  size_t lo4[kKinds], hi4[kKinds];
+  tloam_shard_ranges_frame(n, c->rank, c->nranks, lo4, hi4);
+  for (int k = 0; k < kKinds; ++k) {
+    KindData& K = c->kd[k];
+    K.n_src_full = n[k];
+    K.src_lo = lo4[k];
+    K.n_src = hi4[k] - lo4[k];
+    cnt4[k] = 3 * K.n_src;
+  }
+  const size_t total = std::max<size_t>(tlh::staged_size(cnt4, kKinds), 3);
+  if (total > c->src_pack.cap) {
+    // (a kernel of an earlier frame may still read the old block: nothing of this context is in flight in the reference's
+    //  call pattern, but a growing buffer is rare enough to afford the certainty)
+    HIPC(c, hipStreamSynchronize(c->stream));
+    HIPC(c, c->src_pack.reserve(total));
+  }
+  return TLOAM_OK;
+}
+// ... and, once the block is filled (ok) or not, the sources registered at the offsets off[]
+void source_frame_commit(tloam_ctx* c, bool ok, const size_t off[4]) {
+  for (int k = 0; k < kKinds; ++k) {
+    // (a failed staging / upload leaves the block undefined: the sources are NOT registered, the next solve says so)
+    c->kd[k].src_ptr = ok ? c->src_pack.p + off[k] : nullptr;
+    c->kd[k].src_set = ok;
+  }
+}
 }  // namespace tlh
 
 extern "C" {
@@ -371,35 +404,19 @@ int set_source_async(tloam_ctx* c, int kind, const double* xyz, size_t n) {
 // (front_end.cpp:314 is followed at once by scanMatching, :321: the wait moves to that call's first wait for the device)
 int set_source_frame_packed(tloam_ctx* c, const double* const xyz[4], const size_t n[4]) {
   size_t off[kKinds] = {0, 0, 0, 0};
-  size_t lo4[kKinds], hi4[kKinds], cnt4[kKinds];
+  size_t cnt4[kKinds];
   for (int k = 0; k < kKinds; ++k)   // (refused as a whole, before anything of the registered frame has been touched)
     if ((n[k] > 0 && !xyz[k]) || n[k] > kMaxPoints) return TLOAM_E_INVALID;
-  tloam_shard_ranges_frame(n, c->rank, c->nranks, lo4, hi4);
-  for (int k = 0; k < kKinds; ++k) {
-    KindData& K = c->kd[k];
-    K.n_src_full = n[k];
-    K.src_lo = lo4[k];
-    K.n_src = hi4[k] - lo4[k];
-    cnt4[k] = 3 * K.n_src;
-  }
-  const size_t total = std::max<size_t>(tlh::staged_size(cnt4, kKinds), 3);
-  if (total > c->src_pack.cap) {
-    // (a kernel of an earlier frame may still read the old block: nothing of this context is in flight in the reference's
-    //  call pattern, but a growing buffer is rare enough to afford the certainty)
-    HIPC(c, hipStreamSynchronize(c->stream));
-    HIPC(c, c->src_pack.reserve(total));
-  }
+  const int rc0 = tlh::source_frame_reserve(c, n, cnt4);
+  if (rc0 != TLOAM_OK) return rc0;
   const double* parts[kKinds];
   for (int k = 0; k < kKinds; ++k) parts[k] = c->kd[k].n_src > 0 ? xyz[k] + 3 * c->kd[k].src_lo : nullptr;
   const int rc = tlh::stage_and_upload(c, parts, cnt4, kKinds, c->src_pack.p, off);
-  for (int k = 0; k < kKinds; ++k) {
-    // (a failed staging / upload leaves the block undefined: the sources are NOT registered, the next solve says so)
-    c->kd[k].src_ptr = rc == TLOAM_OK ? c->src_pack.p + off[k] : nullptr;
-    c->kd[k].src_set = rc == TLOAM_OK;
-  }
+  tlh::source_frame_commit(c, rc == TLOAM_OK, off);
   return rc;
 }
-int set_target_async(tloam_ctx* c, int kind, const double* xyz, size_t n, bool convert = true) {
+int set_target_async(tloam_ctx* c, int kind, const double* xyz, size_t n, bool convert = true,
+                     hipMemcpyKind from = hipMemcpyHostToDevice) {
   if (kind < 0 || kind >= kKinds || (n > 0 && !xyz) || n > kMaxPoints) return TLOAM_E_INVALID;
   KindData& K = c->kd[kind];
   K.n_tgt = n;
@@ -409,7 +426,7 @@ int set_target_async(tloam_ctx* c, int kind, const double* xyz, size_t n, bool c
   HIPC(c, K.tgt_aos.reserve(3 * m));
   HIPC(c, K.tx.reserve(m)); HIPC(c, K.ty.reserve(m)); HIPC(c, K.tz.reserve(m));
   if (n > 0) {
-    HIPC(c, hipMemcpyAsync(K.tgt_aos.p, xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemcpyAsync(K.tgt_aos.p, xyz, sizeof(double) * 3 * n, from, c->stream));
     if (convert) launch_aos_to_soa(K.tgt_aos.p, n, K.tx.p, K.ty.p, K.tz.p, c->stream);  // AoS -> SoA on the device
   }
   K.tgt_set = true;
@@ -429,12 +446,7 @@ int tloam_set_source(tloam_ctx* c, int kind, const double* xyz, size_t n) {
 int tloam_set_target(tloam_ctx* c, int kind, const double* xyz, size_t n) {
   if (!c) return TLOAM_E_INVALID;
   HIPC(c, hipSetDevice(c->device));
-  int rc = set_target_async(c, kind, xyz, n);
-  if (rc == TLOAM_OK) rc = enqueue_target_bounds(c);
-  if (rc != TLOAM_OK) return rc;
-  HIPC(c, hipStreamSynchronize(c->stream));
-  finish_target_bounds(c);
-  return TLOAM_OK;
+  return tlh::set_target_copy(c, kind, xyz, n, hipMemcpyHostToDevice);
 }
 
 int tloam_set_source_frame(tloam_ctx* c, const double* const xyz[4], const size_t n[4]) {
@@ -524,3 +536,15 @@ int tloam_frame_select(tloam_ctx* c, int slot) {
 }
 
 }  // extern "C"
+
+namespace tlh {
+// tloam_set_target of a cloud on the host (hipMemcpyHostToDevice) or already on this device (hipMemcpyDeviceToDevice)
+int set_target_copy(tloam_ctx* c, int kind, const double* xyz, size_t n, hipMemcpyKind from) {
+  int rc = set_target_async(c, kind, xyz, n, true, from);
+  if (rc == TLOAM_OK) rc = enqueue_target_bounds(c);
+  if (rc != TLOAM_OK) return rc;
+  HIPC(c, hipStreamSynchronize(c->stream));
+  finish_target_bounds(c);
+  return TLOAM_OK;
+}
+}  // namespace tlh

@@ -60,16 +60,13 @@ void tloam_seg_default_config(tloam_seg_config* c) {
   c->start_r = 0.35; c->delta_r = 0.0004; c->delta_p = 1.2; c->delta_a = 1.2; c->min_seg = 80;
 }
 
-int tloam_segment(tloam_ctx* c, const tloam_seg_config* cfg, const double* xyz, size_t n, int32_t* ring,
-                  int32_t* ground_index, size_t* n_ground, int32_t* object_index, size_t* n_object,
-                  int32_t* segmented_index, int32_t* segmented_label, size_t* n_segmented, int32_t* edge_index,
-                  size_t* n_edge, int32_t* general_index, size_t* n_general, double* boxes, size_t box_capacity,
-                  size_t* n_boxes) {
-  size_t* counts[6] = {n_ground, n_object, n_segmented, n_edge, n_general, n_boxes};
-  for (size_t* p : counts)
-    if (p) *p = 0;
-  if (!c || !cfg || (n > 0 && !xyz) || n > kMaxPoints || !config_ok(*cfg)) return TLOAM_E_INVALID;
-  HIPC(c, hipSetDevice(c->device));
+}  // extern "C"
+
+namespace tlh {
+bool seg_config_ok(const tloam_seg_config& cfg) { return config_ok(cfg); }
+
+// the upload-independent head of tloam_segment: the call is counted, the parameters formed, the buffers sized for n points
+int segment_begin(tloam_ctx* c, const tloam_seg_config& cfg, size_t n, SegParams* out) {
   SegBuffers& S = c->seg;
   const bool first = S.frames == 0;   // minPolar / maxPolar: 5.0 on the node's first frame, 0.0 after resetParams (:1123)
   S.frames++;                         // (a frame that fails advances it too: DESIGN.md 11)
@@ -78,14 +75,14 @@ int tloam_segment(tloam_ctx* c, const tloam_seg_config* cfg, const double* xyz, 
   SegParams P;
   memset(&P, 0, sizeof(P));
   P.n = (int)n;
-  P.num_sec = cfg->num_sec;
-  P.n_regions = cfg->quadrant * cfg->num_sec;
-  P.n_bounds = section_bounds(*cfg, P.sec_bounds);
-  P.near_th = cfg->near_dis * cfg->near_dis;
-  P.sensor_height = cfg->sensor_height; P.min_range = cfg->sensor_min_range; P.max_range = cfg->sensor_max_range;
-  P.plane_dis = cfg->dis; P.max_iter = cfg->max_iter; P.seed_num = cfg->ground_seed_num; P.ring_min = cfg->ring_min_num;
-  P.min_seg = cfg->min_seg; P.start_r = cfg->start_r; P.delta_r = cfg->delta_r; P.delta_p = cfg->delta_p;
-  P.delta_a = cfg->delta_a; P.polar_seed = first ? 5.0 : 0.0;
+  P.num_sec = cfg.num_sec;
+  P.n_regions = cfg.quadrant * cfg.num_sec;
+  P.n_bounds = section_bounds(cfg, P.sec_bounds);
+  P.near_th = cfg.near_dis * cfg.near_dis;
+  P.sensor_height = cfg.sensor_height; P.min_range = cfg.sensor_min_range; P.max_range = cfg.sensor_max_range;
+  P.plane_dis = cfg.dis; P.max_iter = cfg.max_iter; P.seed_num = cfg.ground_seed_num; P.ring_min = cfg.ring_min_num;
+  P.min_seg = cfg.min_seg; P.start_r = cfg.start_r; P.delta_r = cfg.delta_r; P.delta_p = cfg.delta_p;
+  P.delta_a = cfg.delta_a; P.polar_seed = first ? 5.0 : 0.0;
   size_t hcap = 16;
   while (hcap < 2 * n) hcap <<= 1;
   P.hash_mask = (int)(hcap - 1);
@@ -102,7 +99,14 @@ int tloam_segment(tloam_ctx* c, const tloam_seg_config* cfg, const double* xyz, 
   HIPC(c, S.genbuf.reserve(n)); HIPC(c, S.picked.reserve(n)); HIPC(c, S.edge_sec.reserve(kSegSectors * kSegEdgePerSector));
   HIPC(c, S.sec_cnt.reserve(2 * kSegSectors)); HIPC(c, S.sec_base.reserve(kSegSectors)); HIPC(c, S.edge.reserve(n));
   HIPC(c, S.general.reserve(n));
+  *out = P;
+  return TLOAM_OK;
+}
 
+// the stage on the scan resident in seg.aos: ends in the control block, no host synchronisation
+int segment_launch(tloam_ctx* c, const SegParams& P) {
+  SegBuffers& S = c->seg;
+  const size_t n = (size_t)P.n, hcap = (size_t)P.hash_mask + 1;
   SegBufs B;
   B.aos = S.aos.p; B.ctl = S.ctl.p; B.ring = S.ring.p; B.cur = S.cur.p; B.cur_reg = S.cur_reg.p; B.ng = S.ng.p;
   B.reg_mem = S.reg_mem.p; B.reg_flag = S.reg_flag.p; B.reg_g = S.reg_g.p; B.reg_v = S.reg_v.p; B.ground = S.ground.p;
@@ -112,13 +116,34 @@ int tloam_segment(tloam_ctx* c, const tloam_seg_config* cfg, const double* xyz, 
   B.boxes = S.boxes.p; B.ring_list = S.ring_list.p; B.cv = S.cv.p; B.sorted = S.sorted.p; B.genbuf = S.genbuf.p;
   B.picked = S.picked.p; B.edge_sec = S.edge_sec.p; B.sec_cnt = S.sec_cnt.p; B.sec_base = S.sec_base.p; B.edge = S.edge.p;
   B.general = S.general.p;
-
-  HIPC(c, hipMemcpyAsync(S.aos.p, xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice, c->stream));
   HIPC(c, hipMemsetAsync(S.hkey.p, 0xff, sizeof(int) * hcap, c->stream));   // empty slot: key -1
   HIPC(c, hipMemsetAsync(S.hval.p, 0x7f, sizeof(int) * hcap, c->stream));   // above every index (atomicMin)
   HIPC(c, hipMemsetAsync(S.csize.p, 0, sizeof(int) * n, c->stream));
   launch_segment(P, B, c->stream);
   HIPC(c, hipGetLastError());
+  return TLOAM_OK;
+}
+}  // namespace tlh
+
+extern "C" {
+
+int tloam_segment(tloam_ctx* c, const tloam_seg_config* cfg, const double* xyz, size_t n, int32_t* ring,
+                  int32_t* ground_index, size_t* n_ground, int32_t* object_index, size_t* n_object,
+                  int32_t* segmented_index, int32_t* segmented_label, size_t* n_segmented, int32_t* edge_index,
+                  size_t* n_edge, int32_t* general_index, size_t* n_general, double* boxes, size_t box_capacity,
+                  size_t* n_boxes) {
+  size_t* counts[6] = {n_ground, n_object, n_segmented, n_edge, n_general, n_boxes};
+  for (size_t* p : counts)
+    if (p) *p = 0;
+  if (!c || !cfg || (n > 0 && !xyz) || n > kMaxPoints || !config_ok(*cfg)) return TLOAM_E_INVALID;
+  HIPC(c, hipSetDevice(c->device));
+  SegBuffers& S = c->seg;
+  SegParams P;
+  int rc = segment_begin(c, *cfg, n, &P);
+  if (rc != TLOAM_OK) return rc;
+  HIPC(c, hipMemcpyAsync(S.aos.p, xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice, c->stream));
+  rc = segment_launch(c, P);
+  if (rc != TLOAM_OK) return rc;
 
   SegCtl ctl;
   HIPC(c, hipMemcpyAsync(&ctl, S.ctl.p, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));

@@ -38,7 +38,9 @@ int submap_reserve_work(tloam_ctx* c, size_t n) {
 // [s ? n0 : 0, s ? n : n0) -> target[kind[s]] = VoxelDownSample(Crop(segment, box[s]), voxel[s]); sizes to counts[s].
 // A single cloud: n0 == n, kind[1] ignored.
 struct CropVoxelSeg { int kind; size_t n; const double* lo; const double* hi; double voxel; };
-int submap_job(tloam_ctx* c, const CropVoxelSeg seg[2], int nseg, VoxelJob* Jout, VoxelWork* Wout) {
+// out: the down-sampled clouds go there (SoA per segment) instead of the target arrays of seg[s].kind
+int submap_job(tloam_ctx* c, const CropVoxelSeg seg[2], int nseg, VoxelJob* Jout, VoxelWork* Wout,
+               double* const (*out)[3] = nullptr) {
   SubmapState& S = c->submap;
   const size_t n0 = seg[0].n, n = n0 + (nseg > 1 ? seg[1].n : 0);
   int rc = submap_reserve_work(c, n);
@@ -52,6 +54,10 @@ int submap_job(tloam_ctx* c, const CropVoxelSeg seg[2], int nseg, VoxelJob* Jout
     const CropVoxelSeg& G = seg[s < nseg ? s : 0];
     for (int a = 0; a < 3; ++a) { J.lo[s][a] = G.lo[a]; J.hi[s][a] = G.hi[a]; }
     J.voxel[s] = G.voxel;
+    if (out) {
+      for (int a = 0; a < 3; ++a) W.out[s][a] = out[s][a];
+      continue;
+    }
     KindData& K = c->kd[G.kind];
     if (s < nseg) {
       const size_t m = std::max<size_t>(G.n, 1);
@@ -83,10 +89,10 @@ int submap_crop_voxel(tloam_ctx* c, const CropVoxelSeg seg[2], int nseg) {
   launch_crop_voxel(J, W, c->stream);
   return TLOAM_OK;
 }
-int submap_upload(tloam_ctx* c, const double* xyz, size_t n) {  // host AoS -> in_aos (device)
+int submap_upload(tloam_ctx* c, const double* xyz, size_t n, hipMemcpyKind from = hipMemcpyHostToDevice) {  // AoS -> in_aos (device)
   SubmapState& S = c->submap;
   HIPC(c, S.in_aos.reserve(3 * std::max<size_t>(n, 1)));
-  if (n > 0) HIPC(c, hipMemcpyAsync(S.in_aos.p, xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice, c->stream));
+  if (n > 0) HIPC(c, hipMemcpyAsync(S.in_aos.p, xyz, sizeof(double) * 3 * n, from, c->stream));
   return TLOAM_OK;
 }
 int submap_finish(tloam_ctx* c, size_t* n_edge, size_t* n_ground) {  // the ONE host sync of an update
@@ -126,22 +132,35 @@ int tloam_submap_init(tloam_ctx* c, const tloam_submap_config* cfg, const double
       n_planar > kMaxPoints || n_sphere > kMaxPoints || n_edge > kMaxPoints || n_ground > kMaxPoints)
     return TLOAM_E_INVALID;
   HIPC(c, hipSetDevice(c->device));
-  SubmapState& S = c->submap;
   tloam_submap_config want;
   if (cfg) want = *cfg;
   else tloam_submap_default_config(&want);
-  if (want.planar_frame_size < 1 || want.sphere_frame_size < 1 || !(want.edge_down_sample_submap > 0.0) ||
-      !(want.ground_down_sample_submap > 0.0) || !(want.ground_down_sample > 0.0))
+  if (!tlh::submap_config_ok(want))
     return TLOAM_E_INVALID;  // "[VoxelDownSample] voxel_size <= 0." (PointCloud2.cpp:361-363); the submap in place stays
+  return tlh::submap_init_body(c, want, planar, n_planar, sphere, n_sphere, edge, n_edge, ground, n_ground, hipMemcpyHostToDevice);
+}
+
+}  // extern "C"
+
+namespace tlh {
+bool submap_config_ok(const tloam_submap_config& want) {
+  return want.planar_frame_size >= 1 && want.sphere_frame_size >= 1 && want.edge_down_sample_submap > 0.0 &&
+         want.ground_down_sample_submap > 0.0 && want.ground_down_sample > 0.0;
+}
+
+// the first-frame branch on four clouds on the host (hipMemcpyHostToDevice) or on this device (hipMemcpyDeviceToDevice)
+int submap_init_body(tloam_ctx* c, const tloam_submap_config& want, const double* planar, size_t n_planar, const double* sphere,
+                     size_t n_sphere, const double* edge, size_t n_edge, const double* ground, size_t n_ground, hipMemcpyKind from) {
+  SubmapState& S = c->submap;
   S.release();
   S.cfg = want;
   // :286 / :290-291 submap += cloud on empty submaps: the clouds as given
-  int rc = tloam_set_target(c, TLOAM_KIND_EDGE, edge, n_edge);
-  if (rc == TLOAM_OK) rc = tloam_set_target(c, TLOAM_KIND_PLANAR, planar, n_planar);
-  if (rc == TLOAM_OK) rc = tloam_set_target(c, TLOAM_KIND_SPHERE, sphere, n_sphere);
+  int rc = set_target_copy(c, TLOAM_KIND_EDGE, edge, n_edge, from);
+  if (rc == TLOAM_OK) rc = set_target_copy(c, TLOAM_KIND_PLANAR, planar, n_planar, from);
+  if (rc == TLOAM_OK) rc = set_target_copy(c, TLOAM_KIND_SPHERE, sphere, n_sphere, from);
   if (rc != TLOAM_OK) return rc;
   // :287 ground += ground->VoxelDownSample(ground_down_sample)
-  rc = submap_upload(c, ground, n_ground);
+  rc = submap_upload(c, ground, n_ground, from);
   if (rc != TLOAM_OK) return rc;
   const size_t m = std::max<size_t>(n_ground, 1);
   HIPC(c, S.wx.reserve(m)); HIPC(c, S.wy.reserve(m)); HIPC(c, S.wz.reserve(m));
@@ -165,10 +184,13 @@ int tloam_submap_init(tloam_ctx* c, const tloam_submap_config* cfg, const double
   S.inited = true;
   return TLOAM_OK;
 }
+}  // namespace tlh
 
 static int submap_update_body(tloam_ctx* c, const double pose[16], const double* planar, size_t n_planar,
                               const double* sphere, size_t n_sphere, const double* edge, size_t n_edge,
-                              const double* ground, size_t n_ground);
+                              const double* ground, size_t n_ground, DBuf<double>* resident = nullptr);
+
+extern "C" {
 
 int tloam_submap_update(tloam_ctx* c, const double pose[16], const double* planar, size_t n_planar,
                         const double* sphere, size_t n_sphere, const double* edge, size_t n_edge,
@@ -190,9 +212,28 @@ int tloam_submap_update(tloam_ctx* c, const double pose[16], const double* plana
   return rc;
 }
 
+}  // extern "C"
+
+namespace tlh {
+// tloam_submap_update on clouds already on this device: `block` holds planar | edge | ground, AoS, at the offsets staged_offsets
+// gives the counts (3 n_planar, 3 n_edge, 3 n_ground), with room for two doubles behind; it becomes the newest planar ring
+// frame's buffer (and gets the buffer of the frame that falls out, or none, in exchange)
+int submap_update_resident(tloam_ctx* c, const double pose[16], size_t n_planar, size_t n_sphere, size_t n_edge, size_t n_ground,
+                           DBuf<double>& block) {
+  if (!c->submap.inited) return TLOAM_E_NOT_READY;
+  for (int i = 0; i < 16; ++i)
+    if (!(pose[i] - pose[i] == 0.0)) return TLOAM_E_BAD_POSE;
+  const int rc = submap_update_body(c, pose, nullptr, n_planar, nullptr, n_sphere, nullptr, n_edge, nullptr, n_ground, &block);
+  if (rc != TLOAM_OK) (void)hipStreamSynchronize(c->stream);
+  return rc;
+}
+}  // namespace tlh
+
+extern "C" {
+
 static int submap_update_body(tloam_ctx* c, const double pose[16], const double* planar, size_t n_planar,
                               const double* sphere, size_t n_sphere, const double* edge, size_t n_edge,
-                              const double* ground, size_t n_ground) {
+                              const double* ground, size_t n_ground, DBuf<double>* resident) {
   SubmapState& S = c->submap;
   (void)sphere;
   bool fused_front = false;
@@ -225,6 +266,11 @@ static int submap_update_body(tloam_ctx* c, const double pose[16], const double*
     if (!upload) return TLOAM_OK;
     const double* parts[3] = {xyz, edge, ground};
     const size_t counts[3] = {3 * n, 3 * n_edge, 3 * n_ground};
+    if (resident) {   // the clouds are in the caller's device block already: it becomes the frame's buffer, nothing is staged
+      std::swap(f->aos, *resident);
+      tlh::staged_offsets(counts, 3, stage_off);
+      return TLOAM_OK;
+    }
     const size_t all = std::max<size_t>(tlh::staged_size(counts, 3), 2) + 2;   // (+ 2: read / written in 16-byte steps)
     if (f->aos.cap < all) HIPC(c, hipStreamSynchronize(c->stream));   // regrowth: nothing may be in flight
     HIPC(c, f->aos.reserve(all));
@@ -364,6 +410,65 @@ static int submap_update_body(tloam_ctx* c, const double pose[16], const double*
   c->kd[TLOAM_KIND_EDGE].n_tgt = ne;
   c->kd[TLOAM_KIND_GROUND].n_tgt = ng;
   c->kd[TLOAM_KIND_EDGE].tgt_set = c->kd[TLOAM_KIND_GROUND].tgt_set = true;
+  return TLOAM_OK;
+}
+
+}  // extern "C"
+
+namespace tlh {
+// PointCloud2::VoxelDownSample of the SoA cloud(s) in submap.wx / wy / wz as ONE job of one or two segments (seg[s].n points
+// each, back to back) with no crop, the means into out[s] (SoA).  Enqueued only; the sizes land in submap.counts, the overflow
+// flag in submap.overflow (device words)
+int voxel_down_sample_launch(tloam_ctx* c, const size_t n[2], const double voxel[2], int nseg, double* const out[2][3]) {
+  const CropVoxelSeg seg[2] = {{TLOAM_KIND_EDGE, n[0], kNoLo, kNoHi, voxel[0]},
+                               {TLOAM_KIND_GROUND, nseg > 1 ? n[1] : 0, kNoLo, kNoHi, voxel[nseg > 1 ? 1 : 0]}};
+  VoxelJob J;
+  VoxelWork W;
+  const int rc = submap_job(c, seg, nseg, &J, &W, out);
+  if (rc != TLOAM_OK) return rc;
+  W.host_seg = nullptr;            // (the caller reads the sizes with the rest of its control words)
+  c->submap.pending_seq = 0ull;
+  launch_crop_voxel(J, W, c->stream);
+  return TLOAM_OK;
+}
+}  // namespace tlh
+
+extern "C" {
+
+int tloam_voxel_down_sample(tloam_ctx* c, double voxel, const double* xyz, size_t n, double* out, size_t capacity,
+                            size_t* n_out) {
+  if (n_out) *n_out = 0;
+  if (!c || !n_out || (n > 0 && !xyz) || n > kMaxPoints) return TLOAM_E_INVALID;
+  if (!(voxel > 0.0)) {
+    c->last_error = "[VoxelDownSample] voxel_size <= 0.";  // PointCloud2.cpp:361-363
+    return TLOAM_E_INVALID;
+  }
+  HIPC(c, hipSetDevice(c->device));
+  SubmapState& S = c->submap;
+  OdomState& O = c->odom;
+  const size_t m = std::max<size_t>(n, 1);
+  HIPC(c, S.wx.reserve(m)); HIPC(c, S.wy.reserve(m)); HIPC(c, S.wz.reserve(m)); HIPC(c, O.vox_out.reserve(3 * m));
+  int rc = submap_upload(c, xyz, n);
+  if (rc != TLOAM_OK) return rc;
+  launch_aos_to_soa(S.in_aos.p, n, S.wx.p, S.wy.p, S.wz.p, c->stream);
+  // one segment, a single-cloud job as tloam_submap_init's ground (its sizes come back through the result mirror)
+  const CropVoxelSeg seg[2] = {{TLOAM_KIND_GROUND, n, kNoLo, kNoHi, voxel}, {TLOAM_KIND_GROUND, 0, kNoLo, kNoHi, voxel}};
+  double* const outs[2][3] = {{O.vox_out.p, O.vox_out.p + m, O.vox_out.p + 2 * m}, {O.vox_out.p, O.vox_out.p + m, O.vox_out.p + 2 * m}};
+  VoxelJob J;
+  VoxelWork W;
+  rc = submap_job(c, seg, 1, &J, &W, outs);
+  if (rc != TLOAM_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
+  launch_crop_voxel(J, W, c->stream);
+  size_t nv = 0, unused = 0;
+  rc = submap_finish(c, &nv, &unused);
+  if (rc != TLOAM_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
+  *n_out = nv;
+  if (nv == 0) return TLOAM_OK;
+  if (capacity < nv || !out) return TLOAM_E_INVALID;
+  HIPC(c, c->misc.reserve(3 * nv));
+  launch_soa_to_aos(O.vox_out.p, O.vox_out.p + m, O.vox_out.p + 2 * m, nv, c->misc.p, c->stream);
+  HIPC(c, hipMemcpyAsync(out, c->misc.p, sizeof(double) * 3 * nv, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));
   return TLOAM_OK;
 }
 

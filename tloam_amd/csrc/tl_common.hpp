@@ -485,6 +485,36 @@ void launch_submap_front(int count, const double* const aos[], const size_t n[],
 // (copy_dst: frame `copy_frame`'s cloud is read from pinned host memory and copied to this device buffer on the way; every
 //  AoS cloud the launch reads must start on a 16-byte boundary and may be read up to one double past its end)
 
+// ---- the odometry frame (tl_odom.hip): index lists -> point rows, device to device -----------------
+// One job: row i of the destination = source point idx2[idx1[i]] (a missing list is the identity), for i < min(*count, n).
+// Coordinates at x[p * stride], y[p * stride], z[p * stride]: stride 3 with (x, y, z) = (base, base + 1, base + 2) is AoS,
+// stride 1 with three arrays is SoA.  Indices outside [0, n1) / [0, src_n) are not followed (the row is left as it was).
+struct GatherJob {
+  const double *sx, *sy, *sz;
+  double *dx, *dy, *dz;
+  const int* idx1;
+  const int* idx2;
+  const int* count;   // device word: the list's length (nullptr: n)
+  int n;              // rows the grid covers: an upper bound of the length, known to the host
+  int n1, src_n;      // bounds of idx1's values (the length of idx2's list) and of the source point index
+  int ss, ds;         // strides of source and destination, in doubles
+};
+constexpr int kGatherMaxJobs = 8;
+struct GatherArgs { GatherJob j[kGatherMaxJobs]; };
+void launch_gather_lists(const GatherArgs& A, int jobs, hipStream_t s);
+// after launch_feat_select and a two-segment voxel job: ctl[0..6] = planar / sphere candidates, the lengths of the scan
+// selections (the prefix of the ranked list extractPlanarSphere keeps, :178-190), the two voxel counts, the voxel overflow flag
+struct OdomCountArgs {
+  const unsigned long long* total;   // scan[n] of launch_feat_select: planar << 32 | sphere
+  const double* ranked;              // FeatRankOut: planar flatness, then sphere flatness
+  int planar_num, sphere_num;
+  double planar_scan_thres, cvr_scan;
+  const unsigned long long* vox_n;   // VoxelWork::n_out
+  const int* vox_overflow;           // VoxelWork::overflow
+  int* ctl;
+};
+void launch_odom_counts(const OdomCountArgs& A, hipStream_t s);
+
 // ---- PCA feature extraction (tl_feature.hip; feature_extract.cpp:47-197) -----------------------
 struct FeatArgs {
   GridView g;                 // grid over the cloud itself (cell >= radius)

@@ -1,6 +1,7 @@
 // tl_ctx.hpp -- host-side context of the C ABI (include/tloam_hip.h), shared by the API translation units (tl_api.hip:
 // lifetime, tl_api_frames.hip: HBM residency + search grids, tl_api_match.hip: the scanMatching driver, tl_api_comm.hip: multi-GPU
-// exchange, tl_api_submap.hip: device-resident submap, tl_api_feature.hip: PCA features).
+// exchange, tl_api_submap.hip: device-resident submap, tl_api_feature.hip: PCA features, tl_api_seg.hip: segmentation,
+// tl_api_odom.hip: the whole odometry frame).
 #pragma once
 
 #include <dlfcn.h>
@@ -164,6 +165,19 @@ struct SegBuffers {
   }
 };
 
+// the odometry frame (tl_api_odom.hip): FrontEnd's state between frames and the device scratch of its glue
+struct OdomState {
+  bool ready = false;              // tloam_odometry_reset has been called
+  tloam_odom_config cfg;
+  double last[16], predict[16];    // FrontEnd::last_pose / predicate_pose (front_end.cpp:281-282, :329-332), column-major
+  long long frame = 0;             // frames accepted since the reset
+  DBuf<double> vox_out;            // SoA output of the per-scan voxel job (edge x, y, z, then ground x, y, z) / tloam_voxel_down_sample
+  DBuf<double> block;              // planar | edge | ground of the submap update (swapped into the planar ring), or the first
+                                   // frame's four clouds
+  DBuf<int> ctl;                   // k_odom_counts
+  void release() { vox_out.release(); block.release(); ctl.release(); ready = false; }
+};
+
 // up to four SoA clouds (x, y, z, n) a search grid is built over -- the registered targets, or any other cloud
 struct CloudRef { const double *x, *y, *z; size_t n; };
 }  // namespace tlh
@@ -175,6 +189,7 @@ struct tloam_ctx {
   SubmapState submap;
   FeatBuffers feat;
   SegBuffers seg;
+  OdomState odom;
   int device = 0;
   hipStream_t stream = nullptr;
   KindData kd[kKinds];
@@ -379,6 +394,25 @@ int stage_in_place(tloam_ctx* c, const double* const parts[], const size_t count
                    int* half);
 int stage_release(tloam_ctx* c, int half, bool completed);
 size_t staged_size(const size_t counts[], int nparts);
+size_t staged_offsets(const size_t counts[], int nparts, size_t offs[]);   // where staging puts the pieces; returns the total
+int source_frame_reserve(tloam_ctx* c, const size_t n[4], size_t cnt4[4]);
+void source_frame_commit(tloam_ctx* c, bool ok, const size_t off[4]);
+int set_target_copy(tloam_ctx* c, int kind, const double* xyz, size_t n, hipMemcpyKind from);
+// tl_api_seg.hip: tloam_segment as "begin" (count the call, size the buffers), upload into seg.aos, "launch"
+bool seg_config_ok(const tloam_seg_config& cfg);
+int segment_begin(tloam_ctx* c, const tloam_seg_config& cfg, size_t n, tl::SegParams* out);
+int segment_launch(tloam_ctx* c, const tl::SegParams& P);
+// tl_api_feature.hip: calculatePCAInfo / the ranking of extractPlanarSphere on the cloud resident in feat.aos
+int feature_reserve(tloam_ctx* c, const tloam_feature_config& cfg, size_t n, FeatBuffers& F);
+int feature_pca_run(tloam_ctx* c, const tloam_feature_config& cfg, size_t n, FeatBuffers& F, tl::FeatArgs* out);
+int feature_select_launch(tloam_ctx* c, const tloam_feature_config& cfg, size_t n, FeatBuffers& F, const tl::FeatArgs& A);
+// tl_api_submap.hip
+bool submap_config_ok(const tloam_submap_config& cfg);
+int submap_init_body(tloam_ctx* c, const tloam_submap_config& want, const double* planar, size_t n_planar, const double* sphere,
+                     size_t n_sphere, const double* edge, size_t n_edge, const double* ground, size_t n_ground, hipMemcpyKind from);
+int submap_update_resident(tloam_ctx* c, const double pose[16], size_t n_planar, size_t n_sphere, size_t n_edge, size_t n_ground,
+                           DBuf<double>& block);
+int voxel_down_sample_launch(tloam_ctx* c, const size_t n[2], const double voxel[2], int nseg, double* const out[2][3]);
 int build_grids_over(tloam_ctx* c, GridBuffers& G, const double radius[tl::kKinds], const CloudRef clouds[tl::kKinds],
                      tl::GridView out[tl::kKinds], const double (*known_boxes)[6] = nullptr,
                      tl::FrameInitHook* frame = nullptr);

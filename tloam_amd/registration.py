@@ -58,6 +58,11 @@ class SegConfig(C.Structure):
                 ("min_seg", C.c_int32), ("reserved2", C.c_int32)]
 
 
+class OdomConfig(C.Structure):
+    """tloam_odom_config: the three stage configurations plus edge_down_sample (lidar_odometry.yaml:8)."""
+    _fields_ = [("seg", SegConfig), ("feature", FeatureConfig), ("submap", SubmapConfig), ("edge_down_sample", C.c_double)]
+
+
 class TlsConfig(C.Structure):
     """tloam_tls_config: the 16 keys of the `TLS:` block (config/mapping/lidar_odometry.yaml:23-39)."""
     _fields_ = [
@@ -101,6 +106,19 @@ class Stats(C.Structure):
                 "bad_weights": self.weight_range_violations, "kind_cost": self.kind_cost[:], "mu": self.mu,
                 "solver_cost": self.solver_cost, "se3": np.frombuffer(self.se3, dtype=np.float64).copy(),
                 "gn_sweeps": self.gn_sweeps, "host_wait_us": self.host_wait_us}
+
+
+class OdomStats(C.Structure):
+    """tloam_odom_stats."""
+    _fields_ = [("match", Stats), ("frame", C.c_int64), ("n_ground", C.c_int64), ("n_edge", C.c_int64),
+                ("n_general", C.c_int64), ("n_edge_ds", C.c_int64), ("n_ground_ds", C.c_int64),
+                ("n_planar_scan", C.c_int64), ("n_sphere_scan", C.c_int64), ("n_planar_submap", C.c_int64),
+                ("n_sphere_submap", C.c_int64), ("h2d_bytes", C.c_int64), ("d2h_bytes", C.c_int64), ("host_syncs", C.c_int64)]
+
+    def as_dict(self):
+        d = {name: getattr(self, name) for name, _ in self._fields_[1:]}
+        d["match"] = self.match.as_dict()
+        return d
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p)
@@ -176,6 +194,10 @@ def load_library():
         "tloam_seg_default_config": (None, [C.POINTER(SegConfig)]),
         "tloam_segment": (C.c_int, [vp, C.POINTER(SegConfig), dp, sz, ip, ip, C.POINTER(sz), ip, C.POINTER(sz), ip, ip,
                                     C.POINTER(sz), ip, C.POINTER(sz), ip, C.POINTER(sz), dp, sz, C.POINTER(sz)]),
+        "tloam_voxel_down_sample": (C.c_int, [vp, C.c_double, dp, sz, dp, sz, C.POINTER(sz)]),
+        "tloam_odom_default_config": (None, [C.POINTER(OdomConfig)]),
+        "tloam_odometry_reset": (C.c_int, [vp, C.POINTER(OdomConfig), dp]),
+        "tloam_odometry_frame": (C.c_int, [vp, dp, sz, dp, C.POINTER(OdomStats)]),
         "tloam_rccl_unique_id": (C.c_int, [vp]),
         "tloam_comm_init_rccl": (C.c_int, [vp, C.c_int, C.c_int, vp]),
         "tloam_comm_init_callback": (C.c_int, [vp, C.c_int, C.c_int, ALLREDUCE_FN, vp]),
@@ -204,7 +226,8 @@ EXPORTED_SYMBOLS = (
     "tloam_debug_raise_fault",
     "tloam_submap_default_config", "tloam_submap_init", "tloam_submap_update", "tloam_get_target",
     "tloam_feature_default_config", "tloam_pca_info", "tloam_extract_planar_sphere",
-    "tloam_seg_default_config", "tloam_segment", "tloam_rccl_unique_id", "tloam_comm_init_rccl",
+    "tloam_seg_default_config", "tloam_segment", "tloam_voxel_down_sample", "tloam_odom_default_config",
+    "tloam_odometry_reset", "tloam_odometry_frame", "tloam_rccl_unique_id", "tloam_comm_init_rccl",
     "tloam_comm_mailbox_export", "tloam_comm_init_mailbox",
     "tloam_comm_init_callback", "tloam_shard_range", "tloam_shard_ranges_frame", "tloam_se3_exp", "tloam_se3_log", "tloam_se3_plus",
 )
@@ -485,6 +508,37 @@ class HipRegistration:
         out["boxes"] = boxes[: cnt["boxes"].value].copy()
         return out
 
+    # ---- per-scan voxel grid and the whole odometry frame (FrontEnd::updateLidarOdometry, front_end.cpp:278-337)
+    def voxel_down_sample(self, xyz, voxel):
+        """PointCloud2::VoxelDownSample on the device: voxel means in order of first occurrence.  Raises on
+        TLOAM_E_INVALID (voxel <= 0, voxel too small)."""
+        a = _aos(xyz)
+        out = np.zeros((max(len(a), 1), 3))
+        n = C.c_size_t(0)
+        rc = self.L.tloam_voxel_down_sample(self.h, float(voxel), _dp(a), len(a), _dp(out), len(out), C.byref(n))
+        self._check(rc, "tloam_voxel_down_sample")
+        return out[: n.value].copy()
+
+    def odometry_reset(self, init_pose=None, cfg: OdomConfig | None = None):
+        """FrontEnd::setInitPose + a fresh odometry state (the next frame is the first one)."""
+        T = None if init_pose is None else _colmajor(init_pose)
+        self._check(self.L.tloam_odometry_reset(self.h, C.byref(cfg) if cfg is not None else None, _dp(T)),
+                    "tloam_odometry_reset")
+
+    def odometry_frame(self, xyz):
+        """one raw scan -> (rc, pose 4x4, stats dict).  rc: 0, -2 (TLOAM_E_TOO_FEW_POINTS: the frame is skipped) or
+        -7 (TLOAM_E_WEIGHT_RANGE: pose written, as scan_match); raises on any other status."""
+        a = _aos(xyz)
+        T = np.zeros(16)
+        st = OdomStats()
+        rc = self.L.tloam_odometry_frame(self.h, _dp(a), len(a), _dp(T), C.byref(st))
+        if rc not in (0, -2, -7):
+            self._check(rc, "tloam_odometry_frame")
+        if rc != -2 and st.frame > 0:   # the getters' capacities: this frame's source clouds, in kind order
+            for k, m in enumerate((st.n_planar_scan, st.n_ground_ds, st.n_edge_ds, st.n_sphere_scan)):
+                self._n[("s", k)] = int(m)
+        return rc, T.reshape(4, 4).T.copy(), st.as_dict()
+
     def fitness(self):
         f, r = C.c_double(0), C.c_double(0)
         rc = self.L.tloam_fitness(self.h, C.byref(f), C.byref(r))
@@ -663,6 +717,25 @@ def default_seg_config(**over) -> SegConfig:
         if not hasattr(cfg, k):
             raise KeyError(k)
         setattr(cfg, k, v)
+    return cfg
+
+
+def default_odom_config(**over) -> OdomConfig:
+    """tloam_odom_default_config; keyword overrides name a top-level field (edge_down_sample) or one of a stage's
+    fields as `<stage>__<field>`, e.g. feature__radius=0.3."""
+    cfg = OdomConfig()
+    load_library().tloam_odom_default_config(C.byref(cfg))
+    for k, v in over.items():
+        if "__" in k:
+            stage, field = k.split("__", 1)
+            sub = getattr(cfg, stage)
+            if not hasattr(sub, field):
+                raise KeyError(k)
+            setattr(sub, field, v)
+        elif hasattr(cfg, k):
+            setattr(cfg, k, v)
+        else:
+            raise KeyError(k)
     return cfg
 
 

@@ -21,6 +21,10 @@ ground = its /ground_points, edge = /edge_points, the PCA features come from /ge
 stays as it is, `_voxel_first` included (the stand-in for FrontEnd::processCloud's VoxelDownSample of the edge and
 ground clouds, front_end.cpp:183,186).  A frame the node publishes nothing for (TLOAM_E_TOO_FEW_POINTS) raises.
 
+`pipeline="device"` replaces all of the above with one `tloam_odometry_frame` per scan: the
+reference's front end -- the segmentation node, processCloud's VoxelDownSample (averages, not `_voxel_first`), no
+`at_least()` padding -- with every cloud in HBM; a frame the device skips (TLOAM_E_TOO_FEW_POINTS) is left out and listed.
+
 Host-side glue only (numpy + the C ABI through tloam_amd.registration); no oracle, no CPU fallback of any device stage."""
 from __future__ import annotations
 
@@ -115,11 +119,55 @@ def list_scans(path: str):
     return []
 
 
+def _read_scan(path):
+    return np.asarray(path, np.float64).reshape(-1, 3) if isinstance(path, np.ndarray) else kitti_io.read_velodyne_bin(path)[0]
+
+
+def replay_device(H, scan_files, out_poses: str | None = None, odom_cfg=None, init_pose=None, max_frames=None):
+    """pipeline="device": one tloam_odometry_frame per scan.  Frames the device skips
+    (TLOAM_E_TOO_FEW_POINTS) are left out of the poses and listed in the stats as `skipped` (their positions in
+    `scan_files`); `frame_of_pose` gives each pose's position."""
+    files = scan_files[: max_frames] if max_frames else scan_files
+    H.odometry_reset(init_pose, odom_cfg)
+    poses, at, skipped, t_frame, iters = [], [], [], [], 0
+    out = open(out_poses, "w") if out_poses else None
+    try:
+        for f, path in enumerate(files):
+            xyz = _read_scan(path)
+            t0 = time.perf_counter()
+            rc, T, st = H.odometry_frame(xyz)
+            t1 = time.perf_counter()
+            if rc == -2:
+                skipped.append(f)
+                continue
+            if rc not in (0, -7):
+                raise RuntimeError(f"frame {f}: odometry_frame status {rc}")
+            iters += st["match"]["gn_sweeps"]
+            poses.append(T)
+            at.append(f)
+            if out:
+                out.write(kitti_io.format_pose_line(T))
+            if st["frame"] > 0:
+                t_frame.append((t1 - t0) * 1e3)
+    finally:
+        if out:
+            out.close()
+    m = lambda v: round(float(np.mean(v)), 4) if v else None  # noqa: E731
+    return poses, {"frames": len(poses), "skipped": skipped, "frame_of_pose": at, "ms_odometry_frame": m(t_frame),
+                   "gn_iters_per_frame": round(iters / max(len(poses) - 1, 1), 2)}
+
+
 def replay(H, scan_files, out_poses: str | None = None, feature_cfg=None, sensor_height: float = 1.73, max_frames=None,
-           sync=None, segmenter: str = "label_scan", seg_cfg=None):
+           sync=None, segmenter: str = "label_scan", seg_cfg=None, pipeline: str = "host", odom_cfg=None, init_pose=None):
     """FrontEnd::updateLidarOdometry (front_end.cpp:278-337) over a list of `.bin` scans on the device.  Returns the
     poses (map <- sensor, 4x4) and per-stage host-to-host timings in ms.  A scan may also be given as an (N, 3) array.
-    segmenter: see features_of_scan."""
+    segmenter: see features_of_scan.  pipeline: "host" (the stages driven from here, the default) or "device" (the whole
+    frame in one call, replay_device: the reference's front end -- segmentation, processCloud's voxel grids, no padding;
+    feature_cfg / sensor_height / segmenter / seg_cfg / sync do not apply, odom_cfg / init_pose do)."""
+    if pipeline == "device":
+        return replay_device(H, scan_files, out_poses, odom_cfg, init_pose, max_frames)
+    if pipeline != "host":
+        raise ValueError(f"unknown pipeline {pipeline!r}")
     poses, t_feat, t_match, t_submap, iters = [], [], [], [], 0
     files = scan_files[: max_frames] if max_frames else scan_files
     out = open(out_poses, "w") if out_poses else None
