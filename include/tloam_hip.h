@@ -478,6 +478,42 @@ int tloam_odometry_reset(tloam_ctx* ctx, const tloam_odom_config* cfg, const dou
 int tloam_odometry_frame(tloam_ctx* ctx, const double* xyz_aos, size_t n, double pose_out_colmajor[16],
                          tloam_odom_stats* stats);
 
+/* ---- the global map and the registered scan of the odometry frame (additive to ABI 8) --------------
+ * FrontEnd::updateSubmap's mapping branch (front_end.cpp:269-274): with mapping on, every later frame appends
+ * VoxelDownSample(raw.Transform(pose), voxel) to a map kept in HBM (the first frame returns at :304, before updateSubmap, and
+ * appends nothing).  Voxels in order of first occurrence, means summed in index order (as tloam_voxel_down_sample); non-finite
+ * returns are left out.  A frame whose transformed scan puts a voxel index beyond 2^21 on an axis appends nothing and counts in
+ * overflow_frames; its pose is not affected.  DESIGN.md section 13. */
+typedef struct tloam_map_config {
+  int32_t enabled;         /* mapping_flag (lidar_odometry.yaml:21): 0 */
+  int32_t reserved0;
+  double voxel;            /* 1.0 (front_end.cpp:272) */
+  int64_t reserve_points;  /* points of HBM reserved when enabled; 0 = 2^21 (48 MiB); the map grows past it by doubling */
+} tloam_map_config;
+void tloam_map_default_config(tloam_map_config* cfg);
+/* cfg NULL: the defaults.  Empties the map; the configuration persists across tloam_odometry_reset.  Allowed between frames.
+ * voxel <= 0 (or not finite) or reserve_points < 0: TLOAM_E_INVALID.  Disabling releases the map's device memory. */
+int tloam_map_configure(tloam_ctx* ctx, const tloam_map_config* cfg);
+
+typedef struct tloam_map_info {
+  int64_t n_points;                /* points in the map */
+  int64_t n_frames;                /* frames that appended since the last reset / configure */
+  int64_t last_first, last_count;  /* the newest appending frame's span in the map */
+  int64_t capacity_points;         /* points the map holds before it grows */
+  int64_t overflow_frames;         /* frames whose scan left the voxel grid: appended nothing */
+} tloam_map_info;
+int tloam_map_get_info(tloam_ctx* ctx, tloam_map_info* info);
+/* points [first, first + count) of the map, AoS.  A range beyond n_points: TLOAM_E_INVALID. */
+int tloam_map_read(tloam_ctx* ctx, size_t first, size_t count, double* out_aos);
+/* The raw scan of the last accepted frame transformed by its lidar_odom_pose (front_end.cpp:84-86, /raw_cloud) -- identity on
+ * the first frame, whatever the init pose (front_end.hpp:106).  With mapping on it is what the map stage transformed; with
+ * mapping off the resident scan is transformed now.  *n receives the size even when capacity is too small (then nothing is
+ * copied and TLOAM_E_INVALID is returned).  TLOAM_E_NOT_READY before the first accepted frame, and once the scan is no longer
+ * resident: a later call on the context (tloam_segment, a skipped frame) has overwritten the segmentation's input buffer and
+ * the map stage holds no transformed copy of it. */
+int tloam_registered_scan(tloam_ctx* ctx, size_t capacity, size_t* n, double* out_aos);
+/* Every map call on a context with nranks > 1: TLOAM_E_INVALID, as the frame. */
+
 /* ---- multi-GPU: correspondence set sharded over ranks, one all-reduce per sweep --------
  * (nothing in the reference).  Call before set_source / set_correspondences.
  * (a) native RCCL over xGMI: unique_id = the 128 bytes of an ncclUniqueId made on rank 0

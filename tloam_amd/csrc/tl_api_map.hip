@@ -1,0 +1,284 @@
+// tl_api_map.hip -- C ABI of the odometry frame's global map and registered scan (include/tloam_hip.h: tloam_map_*,
+// tloam_registered_scan): FrontEnd::spinOnce's /raw_cloud (front_end.cpp:84-86) and updateSubmap's mapping branch
+// (:269-274), driven from tl_api_odom.hip (kernels in tl_map.hip).
+//
+// A later frame with mapping on: the map's storage is grown at the start of the frame, before anything of the odometry state
+// changes (map_frame_reserve); after the scan match, the map's voxel job (tl_map.hip) appends the frame's voxels at the map's
+// current end, its emit kernel posting the count to a pinned segment (map_stage_launch); the host reads it after the
+// frame's last wait, which already follows it in the stream (map_stage_collect); an accepted frame commits it (map_frame_end).
+#include <float.h>
+
+#include "tl_ctx.hpp"
+
+using namespace tl;
+
+namespace {
+
+constexpr size_t kMapDefaultReserve = (size_t)1 << 21;   // points (48 MiB of SoA doubles): tloam_map_config.reserve_points = 0
+
+bool map_config_ok(const tloam_map_config& m) {
+  return m.voxel > 0.0 && m.voxel <= DBL_MAX && m.reserve_points >= 0;   // "[VoxelDownSample] voxel_size <= 0." (PointCloud2.cpp:361-363)
+}
+
+// the storage holds `need` points: new arrays of max(need, 2 cap), the points so far copied device to device behind whatever is
+// in flight, the old arrays retired until the frame has drained the stream (map_frame_end)
+int map_grow(tloam_ctx* c, size_t need) {
+  MapState& M = c->map;
+  if (need <= M.cap) return TLOAM_OK;
+  DBuf<double>* cur[3] = {&M.x, &M.y, &M.z};
+  for (int a = 0; a < 3; ++a)
+    if (M.retired[a].p) {   // (a regrowth whose frame has not ended: not on the frame's path)
+      HIPC(c, hipStreamSynchronize(c->stream));
+      M.retired[a].release();
+    }
+  const size_t want = std::max(need, 2 * M.cap);
+  DBuf<double> nb[3];
+  for (int a = 0; a < 3; ++a) {
+    hipError_t e = nb[a].reserve(want);
+    if (e == hipSuccess && M.n_points > 0)
+      e = hipMemcpyAsync(nb[a].p, cur[a]->p, sizeof(double) * (size_t)M.n_points, hipMemcpyDeviceToDevice, c->stream);
+    if (e != hipSuccess) {
+      (void)hipStreamSynchronize(c->stream);
+      for (auto& b : nb) b.release();
+      c->last_error = std::string("global map growth: ") + hipGetErrorString(e);
+      return TLOAM_E_HIP;
+    }
+  }
+  for (int a = 0; a < 3; ++a) {
+    M.retired[a] = *cur[a];
+    *cur[a] = nb[a];
+  }
+  M.cap = std::min(std::min(M.x.cap, M.y.cap), M.z.cap);
+  return TLOAM_OK;
+}
+
+}  // namespace
+
+namespace tlh {
+
+void map_empty(tloam_ctx* c) {
+  MapState& M = c->map;
+  M.n_points = M.n_frames = M.last_first = M.last_count = M.overflow_frames = 0;
+  M.pending_seq = 0;
+  M.have_count = false;
+  M.xf_seq = 0;
+}
+
+void map_release(tloam_ctx* c) {
+  MapState& M = c->map;
+  M.release_storage();
+  if (M.h_seg) (void)hipHostFree(M.h_seg);
+  M.h_seg = M.h_seg_dev = nullptr;
+  map_empty(c);
+}
+
+// the start of a later frame: the map holds what this frame can append (at most one voxel per point), the voxel job's scratch
+// holds the scan.  Nothing of the odometry state has changed yet: a failure here leaves the frame undone
+int map_frame_reserve(tloam_ctx* c, size_t n) {
+  MapState& M = c->map;
+  M.pending_seq = 0;
+  M.have_count = false;
+  if (!M.cfg.enabled) return TLOAM_OK;
+  int rc = map_grow(c, (size_t)M.n_points + n);
+  if (rc != TLOAM_OK) return rc;
+  const size_t m = std::max<size_t>(n, 1), cap = voxel_table_size(m), blocks = (m + 256) / 256 + 1;
+  if (M.wx.cap < m || M.wy.cap < m || M.wz.cap < m) M.xf_seq = 0;   // (the last registered scan goes with the old scratch)
+  HIPC(c, M.wx.reserve(m)); HIPC(c, M.wy.reserve(m)); HIPC(c, M.wz.reserve(m));
+  HIPC(c, M.min_partial.reserve(3 * blocks)); HIPC(c, M.vmin.reserve(8)); HIPC(c, M.counts.reserve(8));
+  if (!M.ctl.p) {   // [1] the ticket of k_map_front: zero between launches, so zero before the first
+    HIPC(c, M.ctl.reserve(8));
+    HIPC(c, hipMemsetAsync(M.ctl.p, 0, 8 * sizeof(int), c->stream));
+  }
+  HIPC(c, M.keys.reserve(cap + 1)); HIPC(c, M.head.reserve(cap + 1)); HIPC(c, M.first.reserve(cap + 1));
+  HIPC(c, M.count.reserve(cap + 1)); HIPC(c, M.bigslot.reserve(cap + 1));
+  HIPC(c, M.leader.reserve(blocks + 1));
+  HIPC(c, M.slot_of_pt.reserve(m)); HIPC(c, M.next.reserve(m)); HIPC(c, M.members.reserve(m));
+  HIPC(c, M.bigq.reserve((size_t)map_big_max(m))); HIPC(c, M.bigfill.reserve((size_t)map_big_max(m)));
+  return TLOAM_OK;
+}
+
+// after the scan match: global_map += raw.Transform(pose).VoxelDownSample(voxel) (:269-274) on the scan resident in seg.aos,
+// the means written at the map's end (map_frame_reserve made room for n).  Enqueued only
+int map_stage_launch(tloam_ctx* c, const double pose[16], size_t n) {
+  MapState& M = c->map;
+  if (!M.cfg.enabled) return TLOAM_OK;
+  MapVoxWork W;
+  memset(&W, 0, sizeof(W));
+  W.x = M.wx.p; W.y = M.wy.p; W.z = M.wz.p;
+  W.n = n;
+  W.voxel = M.cfg.voxel;
+  W.lo = -DBL_MAX; W.hi = DBL_MAX;   // no crop; a non-finite return is in no voxel
+  W.mask = voxel_table_size(std::max<size_t>(n, 1)) - 1;
+  W.min_partial = M.min_partial.p; W.vmin = M.vmin.p;
+  W.keys = M.keys.p; W.head = M.head.p; W.first = M.first.p; W.count = M.count.p; W.bigslot = M.bigslot.p;
+  W.slot_of_pt = M.slot_of_pt.p; W.next = M.next.p; W.members = M.members.p;
+  W.leader = M.leader.p; W.ctl = M.ctl.p; W.bigq = M.bigq.p; W.bigfill = M.bigfill.p;
+  W.big_max = map_big_max(std::max<size_t>(n, 1));
+  const size_t at = (size_t)M.n_points;
+  W.ox = M.x.p + at; W.oy = M.y.p + at; W.oz = M.z.p + at;
+  W.n_out = M.counts.p;
+  W.host_seg = M.h_seg_dev;
+  W.host_seq = ++M.seq;
+  W.use_ticket = (c->vox_ticket || (long long)(n + 256) / 256 > (long long)map_emit_resident_blocks(c->device_cus)) ? 1 : 0;
+  W.fault = c->h_fault_dev + kFaultVoxEmit;
+  MapFrontArgs A;
+  memset(&A, 0, sizeof(A));
+  A.aos = c->seg.aos.p; A.n = n;
+  for (int k = 0; k < 16; ++k) A.M[k] = pose[k];
+  launch_map_voxel(A, W, c->stream);
+  M.pending_seq = W.host_seq;
+  M.xf_seq = c->seg.aos_seq;
+  M.xf_n = n;
+  return TLOAM_OK;
+}
+
+// after the frame's last wait (the submap's sizes, posted by a kernel behind the map stage's): the map stage's count and overflow
+// flag are in pinned memory already -- read, not waited for
+int map_stage_collect(tloam_ctx* c, tloam_odom_stats* st) {
+  MapState& M = c->map;
+  if (!M.pending_seq) return TLOAM_OK;
+  unsigned long long pay[7];
+  int rc = wait_segment(c, M.h_seg, M.pending_seq, pay);
+  if (rc < 0) return rc;
+  unsigned long long count = 0;
+  int ov = 0;
+  if (rc == TLOAM_OK) {
+    count = pay[0];
+    ov = pay[2] != 0;
+  } else {   // (the stream has drained and the segment is not there: the device words)
+    HIPC(c, hipMemcpyAsync(&count, M.counts.p, sizeof(count), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(&ov, M.ctl.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    st->d2h_bytes += (int64_t)(sizeof(count) + sizeof(int));
+    st->host_syncs++;
+  }
+  st->d2h_bytes += 8 * (int64_t)sizeof(unsigned long long);   // the segment
+  M.pending_seq = 0;
+  rc = check_device_faults(c);   // (k_map_emit's bounded look-back)
+  if (rc != TLOAM_OK) return rc;
+  M.have_count = true;
+  M.new_points = (int64_t)count;
+  M.overflowed = ov != 0;
+  return TLOAM_OK;
+}
+
+// the frame has ended (the stream has drained): storage a regrowth replaced is freed; an accepted frame's voxels join the map
+void map_frame_end(tloam_ctx* c, bool accepted) {
+  MapState& M = c->map;
+  for (auto& b : M.retired) b.release();
+  if (accepted && M.have_count) {
+    if (M.overflowed) {
+      M.overflow_frames++;   // "[VoxelDownSample] voxel_size is too small." (PointCloud2.cpp:370-372): appends nothing here
+    } else {
+      M.last_first = M.n_points;
+      M.last_count = M.new_points;
+      M.n_points += M.new_points;
+      M.n_frames++;
+    }
+  }
+  M.have_count = false;
+  M.pending_seq = 0;
+}
+
+}  // namespace tlh
+
+extern "C" {
+
+void tloam_map_default_config(tloam_map_config* cfg) {
+  if (!cfg) return;
+  memset(cfg, 0, sizeof(*cfg));
+  cfg->enabled = 0;      // mapping_flag (lidar_odometry.yaml:21)
+  cfg->voxel = 1.0;      // front_end.cpp:272
+  cfg->reserve_points = 0;
+}
+
+int tloam_map_configure(tloam_ctx* c, const tloam_map_config* cfg) {
+  if (!c || c->nranks > 1) return TLOAM_E_INVALID;
+  tloam_map_config want;
+  if (cfg) want = *cfg;
+  else tloam_map_default_config(&want);
+  if (!map_config_ok(want)) return TLOAM_E_INVALID;
+  HIPC(c, hipSetDevice(c->device));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  MapState& M = c->map;
+  map_empty(c);
+  if (!want.enabled) {   // mapping off: the frame's memory is what it was without the map
+    map_release(c);
+    M.cfg = want;
+    return TLOAM_OK;
+  }
+  if (!M.h_seg) {
+    unsigned long long* h = nullptr;
+    HIPC(c, hipHostMalloc((void**)&h, 8 * sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent));
+    memset(h, 0, 8 * sizeof(unsigned long long));
+    const hipError_t e = hipHostGetDevicePointer((void**)&M.h_seg_dev, h, 0);
+    if (e != hipSuccess) {
+      (void)hipHostFree(h);
+      c->last_error = std::string("hipHostGetDevicePointer: ") + hipGetErrorString(e);
+      return TLOAM_E_HIP;
+    }
+    M.h_seg = h;
+  }
+  const size_t reserve = want.reserve_points > 0 ? (size_t)want.reserve_points : kMapDefaultReserve;
+  if (M.cap < reserve) {   // (the map is empty: nothing to copy)
+    M.x.release(); M.y.release(); M.z.release();
+    M.cap = 0;
+    const int rc = map_grow(c, reserve);
+    if (rc != TLOAM_OK) return rc;
+    for (auto& b : M.retired) b.release();
+  }
+  M.cfg = want;
+  return TLOAM_OK;
+}
+
+int tloam_map_get_info(tloam_ctx* c, tloam_map_info* info) {
+  if (!c || !info || c->nranks > 1) return TLOAM_E_INVALID;
+  const MapState& M = c->map;
+  info->n_points = M.n_points;
+  info->n_frames = M.n_frames;
+  info->last_first = M.last_first;
+  info->last_count = M.last_count;
+  info->capacity_points = (int64_t)M.cap;
+  info->overflow_frames = M.overflow_frames;
+  return TLOAM_OK;
+}
+
+int tloam_map_read(tloam_ctx* c, size_t first, size_t count, double* out) {
+  if (!c || c->nranks > 1) return TLOAM_E_INVALID;
+  const MapState& M = c->map;
+  const size_t np = (size_t)M.n_points;
+  if (first > np || count > np - first) return TLOAM_E_INVALID;
+  if (count == 0) return TLOAM_OK;
+  if (!out) return TLOAM_E_INVALID;
+  HIPC(c, hipSetDevice(c->device));
+  HIPC(c, c->misc.reserve(3 * count));
+  launch_soa_to_aos(M.x.p + first, M.y.p + first, M.z.p + first, count, c->misc.p, c->stream);
+  HIPC(c, hipMemcpyAsync(out, c->misc.p, sizeof(double) * 3 * count, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  return TLOAM_OK;
+}
+
+int tloam_registered_scan(tloam_ctx* c, size_t capacity, size_t* n, double* out) {
+  if (n) *n = 0;
+  if (!c || !n || c->nranks > 1) return TLOAM_E_INVALID;
+  const OdomState& O = c->odom;
+  const MapState& M = c->map;
+  if (!O.ready || !O.reg_valid) return TLOAM_E_NOT_READY;
+  // the map stage's transform of that very scan (mapping on), else the scan itself if it is still the segmentation's input
+  const bool from_map = M.xf_seq != 0 && M.xf_seq == O.reg_seq && M.wx.p;
+  const bool from_seg = c->seg.aos_seq == O.reg_seq && c->seg.aos.p;
+  if (!from_map && !from_seg) return TLOAM_E_NOT_READY;
+  const size_t m = O.reg_n;
+  *n = m;
+  if (m == 0) return TLOAM_OK;
+  if (capacity < m || !out) return TLOAM_E_INVALID;
+  HIPC(c, hipSetDevice(c->device));
+  HIPC(c, c->misc.reserve(3 * m));
+  if (from_map) launch_soa_to_aos(M.wx.p, M.wy.p, M.wz.p, m, c->misc.p, c->stream);
+  else launch_transform_aos(c->seg.aos.p, m, O.reg_pose, c->misc.p, c->stream);
+  HIPC(c, hipMemcpyAsync(out, c->misc.p, sizeof(double) * 3 * m, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  return TLOAM_OK;
+}
+
+}  // extern "C"

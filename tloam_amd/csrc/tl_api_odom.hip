@@ -64,9 +64,13 @@ int odometry_frame_body(tloam_ctx* c, const double* xyz, size_t n, double pose[1
   SubmapState& M = c->submap;
   const bool first = O.frame == 0;
 
+  // ---- the global map (mapping on, later frames): room for what this frame can append, before anything else changes
+  int rc = first ? TLOAM_OK : map_frame_reserve(c, n);
+  if (rc != TLOAM_OK) return rc;
+
   // ---- Segmentation::spinOnce on the raw scan: the one upload of the frame
   SegParams P;
-  int rc = segment_begin(c, cfg.seg, n, &P);
+  rc = segment_begin(c, cfg.seg, n, &P);
   if (rc != TLOAM_OK) return rc;
   HIPC(c, hipMemcpyAsync(S.aos.p, xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice, c->stream));
   st->h2d_bytes += (int64_t)(sizeof(double) * 3 * n);
@@ -160,7 +164,7 @@ int odometry_frame_body(tloam_ctx* c, const double* xyz, size_t n, double pose[1
     if (rc != TLOAM_OK) return rc;
     st->host_syncs += 4;   // tloam_submap_init's: the three targets' bounds, the ground voxel's sizes
     memcpy(pose, O.last, sizeof(double) * 16);   // the init pose
-    return TLOAM_OK;
+    return TLOAM_OK;   // (:304 returns before updateSubmap: the first frame adds nothing to the global map)
   }
 
   if (cnt[6]) {
@@ -204,10 +208,16 @@ int odometry_frame_body(tloam_ctx* c, const double* xyz, size_t n, double pose[1
   memset(&st->match, 0, sizeof(st->match));
   const int mrc = tloam_scan_match(c, O.predict, nullptr, pose, nullptr, 0, &st->match);
   if (mrc != TLOAM_OK && mrc != TLOAM_E_WEIGHT_RANGE) return mrc;
+  // ---- updateSubmap's mapping branch (:269-274), enqueued ahead of the submap update so that wait 4 follows it: the raw scan
+  // transformed by the pose, voxel-gridded, appended to the global map (mapping on; tl_api_map.hip)
+  rc = map_stage_launch(c, pose, n);
+  if (rc != TLOAM_OK) return rc;
   // ---- updateSubmap (:336) with the planar submap selection, the sphere one's size, edge / ground as down-sampled
   rc = submap_update_resident(c, pose, np, ns, ne_ds, ng_ds, O.block);
   if (rc != TLOAM_OK) return rc;
   st->host_syncs++;   // wait 4: the submap's sizes
+  rc = map_stage_collect(c, st);   // (the map stage's count: already in pinned memory)
+  if (rc != TLOAM_OK) return rc;
   return mrc;
 }
 
@@ -242,6 +252,8 @@ int tloam_odometry_reset(tloam_ctx* c, const tloam_odom_config* cfg, const doubl
   memcpy(O.predict, T, sizeof(T));   // predicate_pose = init_pose (:282)
   O.frame = 0;
   O.ready = true;
+  O.reg_valid = false;   // no registered scan before the first frame
+  map_empty(c);          // the global map starts again; its configuration stays
   return TLOAM_OK;
 }
 
@@ -259,7 +271,16 @@ int tloam_odometry_frame(tloam_ctx* c, const double* xyz, size_t n, double pose_
   double T[16];
   const int rc = odometry_frame_body(c, xyz, n, T, &st);
   (void)hipStreamSynchronize(c->stream);   // (a failed stage may have left work in flight; the success paths have drained)
-  if (rc == TLOAM_OK || rc == TLOAM_E_WEIGHT_RANGE) {
+  const bool accepted = rc == TLOAM_OK || rc == TLOAM_E_WEIGHT_RANGE;
+  map_frame_end(c, accepted);
+  if (accepted) {
+    // spinOnce's /raw_cloud (:84-86): this scan by lidar_odom_pose -- still Identity on the first frame (front_end.hpp:106),
+    // whatever the init pose
+    O.reg_valid = true;
+    O.reg_seq = c->seg.aos_seq;
+    O.reg_n = n;
+    if (O.frame > 0) memcpy(O.reg_pose, T, sizeof(T));
+    else for (int i = 0; i < 16; ++i) O.reg_pose[i] = (i % 5 == 0) ? 1.0 : 0.0;
     if (O.frame > 0) {   // step_pose = last_pose^-1 * lidar_odom_pose; predicate_pose = lidar_odom_pose * step_pose (:329-332)
       double inv[16], step[16];
       rigid_inverse(O.last, inv);

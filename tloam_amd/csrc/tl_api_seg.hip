@@ -71,6 +71,7 @@ int segment_begin(tloam_ctx* c, const tloam_seg_config& cfg, size_t n, SegParams
   const bool first = S.frames == 0;   // minPolar / maxPolar: 5.0 on the node's first frame, 0.0 after resetParams (:1123)
   S.frames++;                         // (a frame that fails advances it too: DESIGN.md 11)
   if (n == 0) return TLOAM_E_TOO_FEW_POINTS;   // object_scan is empty (:1089-1092)
+  S.aos_seq++;                        // the input buffer is about to be reallocated / overwritten (tloam_registered_scan)
 
   SegParams P;
   memset(&P, 0, sizeof(P));

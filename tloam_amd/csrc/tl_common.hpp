@@ -515,6 +515,46 @@ struct OdomCountArgs {
 };
 void launch_odom_counts(const OdomCountArgs& A, hipStream_t s);
 
+// ---- the global map of the odometry frame (tl_map.hip) ------------------------
+// VoxelDownSample of one transformed scan whose voxels can hold hundreds of returns (1 m cells on a raw scan): the leader of a voxel
+// (its smallest member) comes from an atomicMin, not from a walk of the member list; voxels of up to kMapVoxLocal members are
+// averaged by their leader as in k_vox_emit, larger ones by a workgroup each, their members sorted by index in LDS
+struct MapFrontArgs {
+  const double* aos;          // the raw scan, AoS
+  size_t n;
+  double M[16];               // column-major pose
+};
+struct MapVoxWork {
+  double *x, *y, *z;          // the transformed scan, SoA (written by k_map_front)
+  size_t n;
+  double voxel;
+  double lo, hi;              // box on every axis, inclusive: the finite doubles (a non-finite return is in no voxel)
+  unsigned long long mask;    // hash-table capacity - 1 (voxel_table_size(n))
+  double* min_partial;        // [blocks of k_map_front][3]
+  double* vmin;               // [3] voxel_min_bound
+  unsigned long long* keys;   // [mask + 1]
+  int *head, *first, *count, *bigslot;   // [mask + 1]: member list head, smallest member, members, big-voxel number
+  int *slot_of_pt, *next;     // [n]: hash slot of every point (-1: none), next member of its voxel's list
+  int* members;               // [n]: the members of the big voxels, one piece per voxel
+  unsigned long long* leader; // [emit blocks + 1]: look-back words of k_map_emit
+  int* ctl;                   // [0] overflow, [1] ticket of k_map_front, [2] start tickets of k_map_emit, [3] big voxels, [4] their members
+  int4* bigq;                 // [big_max]: (slot, output position, first member in `members`, members)
+  int* bigfill;               // [big_max]
+  int big_max;                // n / (kMapVoxLocal + 1) + 1
+  double *ox, *oy, *oz;       // the means: the map at its current end
+  unsigned long long* n_out;  // [1] voxels
+  unsigned long long* host_seg;   // pinned: [0] voxels, [2] overflow, [7] check word (as VoxelWork::host_seg)
+  unsigned long long host_seq;
+  int use_ticket;
+  unsigned* fault;
+};
+constexpr int kMapVoxLocal = 32;
+inline int map_big_max(size_t n) { return (int)(n / (kMapVoxLocal + 1) + 1); }
+// front | insert | emit | scatter | big: no host synchronisation; the count reaches the host segment with k_map_emit
+void launch_map_voxel(const MapFrontArgs& A, const MapVoxWork& W, hipStream_t s);
+int map_emit_resident_blocks(int device_cus);
+void launch_transform_aos(const double* aos, size_t n, const double M[16], double* out, hipStream_t s);
+
 // ---- PCA feature extraction (tl_feature.hip; feature_extract.cpp:47-197) -----------------------
 struct FeatArgs {
   GridView g;                 // grid over the cloud itself (cell >= radius)

@@ -1,7 +1,7 @@
 // tl_ctx.hpp -- host-side context of the C ABI (include/tloam_hip.h), shared by the API translation units (tl_api.hip:
 // lifetime, tl_api_frames.hip: HBM residency + search grids, tl_api_match.hip: the scanMatching driver, tl_api_comm.hip: multi-GPU
 // exchange, tl_api_submap.hip: device-resident submap, tl_api_feature.hip: PCA features, tl_api_seg.hip: segmentation,
-// tl_api_odom.hip: the whole odometry frame).
+// tl_api_odom.hip: the whole odometry frame, tl_api_map.hip: its global map and registered scan).
 #pragma once
 
 #include <dlfcn.h>
@@ -154,6 +154,7 @@ struct SegBuffers {
       cl_size, seg_local, seg_orig, seg_label, ring_list, sorted, genbuf, edge_sec, sec_cnt, sec_base, edge, general;
   DBuf<unsigned char> reg_flag, picked;
   unsigned long long frames = 0;   // calls so far: the first one seeds minPolar / maxPolar with 5.0, later ones with 0.0
+  unsigned long long aos_seq = 0;  // uploads into `aos` so far (segment_begin): what tloam_registered_scan checks residency by
   void release() {
     DBuf<double>* d[] = {&aos, &pol_val, &bounds, &boxes, &cv};
     for (auto* b : d) b->release();
@@ -175,7 +176,45 @@ struct OdomState {
   DBuf<double> block;              // planar | edge | ground of the submap update (swapped into the planar ring), or the first
                                    // frame's four clouds
   DBuf<int> ctl;                   // k_odom_counts
-  void release() { vox_out.release(); block.release(); ctl.release(); ready = false; }
+  // the last accepted frame's registered scan (tloam_registered_scan): its scan's upload number (SegBuffers::aos_seq), its
+  // size, its lidar_odom_pose (identity on the first frame, front_end.hpp:106)
+  bool reg_valid = false;
+  unsigned long long reg_seq = 0;
+  size_t reg_n = 0;
+  double reg_pose[16];
+  void release() { vox_out.release(); block.release(); ctl.release(); ready = false; reg_valid = false; }
+};
+
+// the global map of the odometry frame (tl_api_map.hip): the map itself (SoA, grown by doubling), the
+// scratch of its per-frame voxel job, and the pinned segment its last kernel reports the frame's count through
+struct MapState {
+  tloam_map_config cfg = {0, 0, 1.0, 0};   // tloam_map_default_config until tloam_map_configure
+  DBuf<double> x, y, z;            // the map: n_points rows of cap
+  size_t cap = 0;
+  DBuf<double> retired[3];         // storage a regrowth replaced: freed once the frame has drained the stream
+  int64_t n_points = 0, n_frames = 0, last_first = 0, last_count = 0, overflow_frames = 0;
+  DBuf<double> wx, wy, wz, min_partial, vmin;   // the transformed scan (kept: the registered scan of a mapping frame)
+  DBuf<unsigned long long> keys, leader, counts;
+  DBuf<int> head, first, count, bigslot, slot_of_pt, next, members, bigfill, ctl;
+  DBuf<int4> bigq;
+  unsigned long long* h_seg = nullptr;      // pinned, device-visible: [0] voxels, [2] overflow, [7] check word
+  unsigned long long* h_seg_dev = nullptr;
+  unsigned long long seq = 0;               // numbers of the segments the map stage has posted
+  unsigned long long pending_seq = 0;       // the map stage of the frame in flight (0: none)
+  bool have_count = false;                  // its result, read at the frame's last wait, committed if the frame is accepted
+  int64_t new_points = 0;
+  bool overflowed = false;
+  unsigned long long xf_seq = 0;            // upload number of the scan whose transform is in (wx, wy, wz) (0: none)
+  size_t xf_n = 0;
+  void release_storage() {
+    x.release(); y.release(); z.release(); cap = 0;
+    for (auto& b : retired) b.release();
+    wx.release(); wy.release(); wz.release(); min_partial.release(); vmin.release();
+    keys.release(); leader.release(); counts.release();
+    head.release(); first.release(); count.release(); bigslot.release(); slot_of_pt.release(); next.release(); members.release();
+    bigfill.release(); ctl.release(); bigq.release();
+    xf_seq = 0;
+  }
 };
 
 // up to four SoA clouds (x, y, z, n) a search grid is built over -- the registered targets, or any other cloud
@@ -190,6 +229,7 @@ struct tloam_ctx {
   FeatBuffers feat;
   SegBuffers seg;
   OdomState odom;
+  MapState map;
   int device = 0;
   hipStream_t stream = nullptr;
   KindData kd[kKinds];
@@ -412,6 +452,14 @@ int submap_init_body(tloam_ctx* c, const tloam_submap_config& want, const double
                      size_t n_sphere, const double* edge, size_t n_edge, const double* ground, size_t n_ground, hipMemcpyKind from);
 int submap_update_resident(tloam_ctx* c, const double pose[16], size_t n_planar, size_t n_sphere, size_t n_edge, size_t n_ground,
                            DBuf<double>& block);
+// tl_api_map.hip: the odometry frame's map stage -- reserve at the start of a later frame, launch after the match, collect the
+// count after the frame's last wait, commit when the frame is accepted; map_release at destroy
+int map_frame_reserve(tloam_ctx* c, size_t n);
+int map_stage_launch(tloam_ctx* c, const double pose[16], size_t n);
+int map_stage_collect(tloam_ctx* c, tloam_odom_stats* st);
+void map_frame_end(tloam_ctx* c, bool accepted);
+void map_empty(tloam_ctx* c);
+void map_release(tloam_ctx* c);
 int voxel_down_sample_launch(tloam_ctx* c, const size_t n[2], const double voxel[2], int nseg, double* const out[2][3]);
 int build_grids_over(tloam_ctx* c, GridBuffers& G, const double radius[tl::kKinds], const CloudRef clouds[tl::kKinds],
                      tl::GridView out[tl::kKinds], const double (*known_boxes)[6] = nullptr,

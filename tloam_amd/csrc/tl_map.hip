@@ -1,0 +1,373 @@
+// tl_map.hip -- the device side of the odometry frame's global map (tl_api_map.hip): FrontEnd::updateSubmap's
+// mapping branch, global_map += raw.Transform(lidar_odom_pose).VoxelDownSample(1.0) (front_end.cpp:269-274), on the raw scan
+// the frame already holds in HBM.
+//
+// Launches (a later frame with mapping on, after the scan match; no host synchronisation in between):
+//   k_map_front       grid x 256   the raw scan transformed (Open3D TransformPoints, the expression of k_transform_to_soa) into
+//                                  SoA scratch; the same launch empties the hash table and finishes the min bound of the
+//                                  transformed cloud (block partials, the last block by ticket) -- k_submap_front's work for one segment
+//   k_map_insert      grid x 256   voxel -> hash slot; the slot's member list, count and smallest member (atomics)
+//   k_map_emit        grid x 256   leaders in first-occurrence order (single-pass look-back scan, as k_vox_emit); a voxel of up to
+//                                  kMapVoxLocal members averaged by its leader, a larger one booked; the count to pinned memory
+//   k_map_scatter     grid x 256   the members of the booked voxels into one piece each
+//   k_map_big         <= 1024 x 256  one workgroup per booked voxel: members ordered by index, summed in that order
+//   k_transform_aos   grid x 256   the registered scan of a frame whose map stage did not run, AoS -> AoS
+// The submap's voxel job (tl_submap.hip) finds a leader by walking the member list from every member and heap-sorts a crowded
+// voxel in one lane: fine for thinned edge / ground clouds, 13 ms per frame on 1 m cells of a raw scan.
+// Compiled with -ffp-contract=off: the transform and voxel_min_bound round as the oracle's pc_transform / pc_voxel_down_sample.
+#include <string.h>
+
+#include <algorithm>
+#include <atomic>
+
+#include "tl_common.hpp"
+
+namespace tl {
+namespace {
+
+constexpr unsigned long long kEmptyKey = ~0ull;   // VoxelWork::keys of a free slot (tl_submap.hip kEmpty)
+
+__device__ __forceinline__ unsigned long long mix64(unsigned long long x) {  // splitmix64 finaliser (as tl_submap.hip)
+  x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
+  x ^= x >> 27; x *= 0x94d049bb133111ebull;
+  x ^= x >> 31;
+  return x;
+}
+
+__device__ __forceinline__ bool in_box(const MapVoxWork& W, double x, double y, double z) {   // inclusive, as Crop
+  return x >= W.lo && x <= W.hi && y >= W.lo && y <= W.hi && z >= W.lo && z <= W.hi;
+}
+
+__device__ __forceinline__ void transform_point(const double* M, double x, double y, double z, double* px, double* py, double* pz) {
+  // new = T * (x, y, z, 1), rows accumulated left to right; point = new.head<3>() / new(3)
+  double r[4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a) r[a] = ((M[a] * x + M[4 + a] * y) + M[8 + a] * z) + M[12 + a] * 1.0;
+  *px = r[0] / r[3];
+  *py = r[1] / r[3];
+  *pz = r[2] / r[3];
+}
+
+__global__ __launch_bounds__(256) void k_map_front(MapFrontArgs A, MapVoxWork W, int emit_blocks) {
+  __shared__ double sm[3][256];
+  __shared__ int s_last;
+  const int tid = threadIdx.x;
+  const size_t i = (size_t)blockIdx.x * 256 + tid, stride = (size_t)gridDim.x * 256;
+  if (blockIdx.x == 0 && tid == 0) { W.ctl[0] = 0; W.ctl[2] = 0; W.ctl[3] = 0; W.ctl[4] = 0; }
+  for (size_t t = i; t <= W.mask; t += stride) {
+    W.keys[t] = kEmptyKey;
+    W.head[t] = -1;
+    W.first[t] = 0x7fffffff;
+    W.count[t] = 0;
+  }
+  for (size_t t = i; t <= (size_t)emit_blocks; t += stride) W.leader[t] = 0ull;
+  for (size_t t = i; t < (size_t)W.big_max; t += stride) W.bigfill[t] = 0;
+  double m[3] = {__builtin_inf(), __builtin_inf(), __builtin_inf()};
+  if (i < A.n) {
+    double x, y, z;
+    transform_point(A.M, A.aos[3 * i], A.aos[3 * i + 1], A.aos[3 * i + 2], &x, &y, &z);
+    W.x[i] = x; W.y[i] = y; W.z[i] = z;
+    if (in_box(W, x, y, z)) { m[0] = x; m[1] = y; m[2] = z; }
+  }
+#pragma unroll
+  for (int a = 0; a < 3; ++a) sm[a][tid] = m[a];
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    if (tid < st)
+#pragma unroll
+      for (int a = 0; a < 3; ++a) sm[a][tid] = fmin(sm[a][tid], sm[a][tid + st]);
+    __syncthreads();
+  }
+  // the block's row is handed over with device-scope stores, their completion waited for, then the ticket (as k_vox_min2)
+  if (tid < 3) __hip_atomic_store(W.min_partial + (size_t)blockIdx.x * 3 + tid, sm[tid][0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (tid == 0)
+    s_last = (__hip_atomic_fetch_add(W.ctl + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1) ? 1 : 0;
+  __syncthreads();
+  if (!s_last) return;
+  // voxel_min_bound = GetMinBound() - voxel_size * 0.5 (PointCloud2.cpp:366); no finite point: (0, 0, 0).  One wave per axis:
+  // min is exact in any order
+  const int wave = tid >> 6, lane = tid & 63;
+  if (wave < 3) {
+    double v = __builtin_inf();
+    for (int b = lane; b < (int)gridDim.x; b += 64)
+      v = fmin(v, __hip_atomic_load(W.min_partial + (size_t)b * 3 + wave, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, 64));
+    if (!(v < __builtin_inf())) v = 0.0;
+    if (lane == 0) W.vmin[wave] = v - W.voxel * 0.5;
+  }
+  if (tid == 0) __hip_atomic_store(W.ctl + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-armed
+}
+
+// the voxel of every point in the box -> hash slot; the point joins the slot's member list, count and smallest index
+__global__ __launch_bounds__(256) void k_map_insert(MapVoxWork W) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= W.n) return;
+  const double x = W.x[i], y = W.y[i], z = W.z[i];
+  if (!in_box(W, x, y, z)) { W.slot_of_pt[i] = -1; return; }
+  // ref_coord = (p - voxel_min_bound) / voxel_size; index = int(floor(ref_coord))   (PointCloud2.cpp:380-383)
+  const long long ix = (long long)floor((x - W.vmin[0]) / W.voxel);
+  const long long iy = (long long)floor((y - W.vmin[1]) / W.voxel);
+  const long long iz = (long long)floor((z - W.vmin[2]) / W.voxel);
+  if (ix < 0 || iy < 0 || iz < 0 || ix >= (1ll << 21) || iy >= (1ll << 21) || iz >= (1ll << 21)) {
+    W.ctl[0] = 1;   // "[VoxelDownSample] voxel_size is too small." (:370-372)
+    W.slot_of_pt[i] = -1;
+    return;
+  }
+  const unsigned long long key = (unsigned long long)ix | ((unsigned long long)iy << 21) | ((unsigned long long)iz << 42);
+  unsigned long long h = mix64(key) & W.mask;
+  for (;;) {
+    const unsigned long long prev = atomicCAS(&W.keys[h], kEmptyKey, key);
+    if (prev == kEmptyKey || prev == key) break;
+    h = (h + 1) & W.mask;
+  }
+  W.slot_of_pt[i] = (int)h;
+  W.next[i] = atomicExch(&W.head[h], (int)i);
+  atomicMin(&W.first[h], (int)i);
+  atomicAdd(&W.count[h], 1);
+}
+
+// per point: a leader of a voxel of up to kMapVoxLocal members orders them by index in LDS (the order AddPoint is called in,
+// :379-385), sums and averages; its output position -- the leaders in front of it, i.e. first-occurrence order -- comes from a
+// single-pass scan over the blocks inside the launch (k_vox_emit's look-back).  The leader of a larger voxel books the voxel for
+// k_map_big: a number, the output position, a piece of `members`
+__global__ __launch_bounds__(256) void k_map_emit(MapVoxWork W, int nblocks) {
+  __shared__ int s_mem[kMapVoxLocal * 256];   // s_mem[k * 256 + t]: member k of thread t's voxel (conflict-free columns)
+  __shared__ unsigned long long s_wave[4];
+  __shared__ unsigned long long s_prefix;
+  __shared__ int s_bid;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int bid = (int)blockIdx.x;
+  if (W.use_ticket) {   // places in the order the blocks start (a grid larger than the device holds at once): see k_vox_emit
+    if (tid == 0) s_bid = atomicAdd(&W.ctl[2], 1);
+    __syncthreads();
+    bid = s_bid;
+  }
+  const size_t i = (size_t)bid * 256 + tid;
+  const int h = i < W.n ? W.slot_of_pt[i] : -1;
+  const bool leader = h >= 0 && W.first[h] == (int)i;
+  const int m = leader ? W.count[h] : 0;
+  double sx = 0.0, sy = 0.0, sz = 0.0;
+  if (leader && m <= kMapVoxLocal) {
+    int k = 0;
+    for (int j = W.head[h]; j >= 0 && k < kMapVoxLocal; j = W.next[j]) s_mem[(k++) * 256 + tid] = j;
+    for (int a = 1; a < k; ++a) {   // insertion sort of this thread's column
+      const int key = s_mem[a * 256 + tid];
+      int b = a - 1;
+      while (b >= 0 && s_mem[b * 256 + tid] > key) { s_mem[(b + 1) * 256 + tid] = s_mem[b * 256 + tid]; --b; }
+      s_mem[(b + 1) * 256 + tid] = key;
+    }
+    // AccumulatedPoint: point_ += p in index order, GetAveragePoint = point_ / double(num) (:253-272)
+    for (int q = 0; q < k; ++q) {
+      const int j = s_mem[q * 256 + tid];
+      sx += W.x[j]; sy += W.y[j]; sz += W.z[j];
+    }
+    const double dn = (double)m;
+    sx /= dn; sy /= dn; sz /= dn;
+  }
+  // ---- the leader's output position: block-exclusive scan of the flags ...
+  const unsigned long long flag = leader ? 1ull : 0ull;
+  unsigned long long incl = flag;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const unsigned long long o = __shfl_up(incl, off, 64);
+    if (lane >= off) incl += o;
+  }
+  if (lane == 63) s_wave[wave] = incl;
+  __syncthreads();
+  unsigned long long wave_base = 0ull, block_total = 0ull;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    if (w < wave) wave_base += s_wave[w];
+    block_total += s_wave[w];
+  }
+  // ... and the blocks in front (status 1: the block's own count, 2: the count up to and including the block; bounded wait)
+  if (tid == 0) {
+    unsigned long long prefix = 0ull;
+    if (bid == 0) {
+      __hip_atomic_store(&W.leader[0], (2ull << 62) | block_total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else {
+      __hip_atomic_store(&W.leader[bid], (1ull << 62) | block_total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const unsigned long long t0 = wall_clock64();
+      unsigned spins = 0;
+      for (int p = bid - 1;;) {
+        const unsigned long long w = __hip_atomic_load(&W.leader[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned st = (unsigned)(w >> 62);
+        if (st == 0u) {
+          if ((++spins & 63u) == 0 && wall_clock64() - t0 > 100000000ull) {   // ~1 s: a block in front never started
+            if (W.fault) { __hip_atomic_store(W.fault, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); __threadfence_system(); }
+            break;   // (the frame's result is discarded by the host, tl_api_map.hip)
+          }
+          __builtin_amdgcn_s_sleep(1);
+          continue;
+        }
+        prefix += w & ~(3ull << 62);
+        if (st == 2u) break;
+        --p;
+      }
+      __hip_atomic_store(&W.leader[bid], (2ull << 62) | (prefix + block_total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    s_prefix = prefix;
+  }
+  __syncthreads();
+  if (leader) {
+    const unsigned long long p = s_prefix + wave_base + (incl - flag);
+    if (m <= kMapVoxLocal) {
+      W.ox[p] = sx; W.oy[p] = sy; W.oz[p] = sz;
+    } else {
+      const int q = atomicAdd(&W.ctl[3], 1);   // (< big_max: a big voxel has more than kMapVoxLocal members)
+      const int off = atomicAdd(&W.ctl[4], m);
+      W.bigq[q] = make_int4(h, (int)p, off, m);
+      W.bigslot[h] = q;
+    }
+  }
+  if (bid == nblocks - 1 && tid < 8) {   // the block that holds the last point: the total = the size of the down-sampled cloud
+    const unsigned long long total = s_prefix + block_total;
+    if (tid == 0) W.n_out[0] = total;
+    // ... and straight to the host (tlh::wait_segment: word 7 = check_mix(sequence number) XOR seg_word of the payload words)
+    unsigned long long w = tid == 0 ? total : tid == 2 ? (unsigned long long)W.ctl[0] : 0ull;
+    unsigned long long x = tid < 7 ? seg_word(w, tid) : 0ull;
+    x ^= __shfl_xor(x, 1, 64);
+    x ^= __shfl_xor(x, 2, 64);
+    x ^= __shfl_xor(x, 4, 64);
+    if (tid == 7) w = check_mix(W.host_seq) ^ x;
+    __hip_atomic_store(&W.host_seg[tid], w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
+// the members of every big voxel into its piece of `members` (in no particular order: k_map_big orders them)
+__global__ __launch_bounds__(256) void k_map_scatter(MapVoxWork W) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= W.n) return;
+  const int h = W.slot_of_pt[i];
+  if (h < 0 || W.count[h] <= kMapVoxLocal) return;
+  const int q = W.bigslot[h];
+  const int4 b = W.bigq[q];
+  W.members[b.z + atomicAdd(&W.bigfill[q], 1)] = (int)i;
+}
+
+// one workgroup per big voxel: its members sorted by index (bitonic, in LDS), then summed in that order by one lane from
+// coordinates the workgroup stages in LDS, 256 at a time.  A voxel of more than kMapSortLds members is not sorted: the workgroup
+// walks the points from the voxel's first member on, 256 at a time, and picks its members out in index order as it goes
+constexpr int kMapSortLds = 8192;
+__global__ __launch_bounds__(256) void k_map_big(MapVoxWork W) {
+  __shared__ int s_idx[kMapSortLds];
+  __shared__ double s_c[3][256];
+  __shared__ int s_wave[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nbig = W.ctl[3];
+  for (int q = (int)blockIdx.x; q < nbig; q += (int)gridDim.x) {
+    const int4 b = W.bigq[q];
+    const int h = b.x, p = b.y, off = b.z, m = b.w;
+    // AccumulatedPoint: point_ += p in index order (:253-272); lane 0 of the workgroup adds, the others stage
+    double sx = 0.0, sy = 0.0, sz = 0.0;
+    if (m <= kMapSortLds) {
+      const int* mem = W.members + off;
+      int P = 1;
+      while (P < m) P <<= 1;
+      for (int t = tid; t < P; t += 256) s_idx[t] = t < m ? mem[t] : 0x7fffffff;
+      __syncthreads();
+      for (int k = 2; k <= P; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+          for (int t = tid; t < P; t += 256) {
+            const int u = t ^ j;
+            if (u > t) {
+              const int a = s_idx[t], c = s_idx[u];
+              if ((a > c) == ((t & k) == 0)) { s_idx[t] = c; s_idx[u] = a; }
+            }
+          }
+          __syncthreads();
+        }
+      for (int c0 = 0; c0 < m; c0 += 256) {
+        const int k = c0 + tid;
+        if (k < m) {
+          const int j = s_idx[k];
+          s_c[0][tid] = W.x[j]; s_c[1][tid] = W.y[j]; s_c[2][tid] = W.z[j];
+        }
+        __syncthreads();
+        if (tid == 0) {
+          const int e = min(256, m - c0);
+          for (int r = 0; r < e; ++r) { sx += s_c[0][r]; sy += s_c[1][r]; sz += s_c[2][r]; }
+        }
+        __syncthreads();
+      }
+    } else {
+      int found = 0;   // (block-uniform)
+      for (size_t base = (size_t)W.first[h]; base < W.n && found < m; base += 256) {
+        const size_t j = base + tid;
+        const bool hit = j < W.n && W.slot_of_pt[j] == h;
+        const unsigned long long bal = __ballot(hit);
+        if (lane == 0) s_wave[wave] = __popcll(bal);
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+          before += w < wave ? s_wave[w] : 0;
+          total += s_wave[w];
+        }
+        if (hit) {
+          const int pos = before + __popcll(bal & ((1ull << lane) - 1ull));
+          s_c[0][pos] = W.x[j]; s_c[1][pos] = W.y[j]; s_c[2][pos] = W.z[j];
+        }
+        __syncthreads();
+        if (tid == 0)
+          for (int r = 0; r < total; ++r) { sx += s_c[0][r]; sy += s_c[1][r]; sz += s_c[2][r]; }
+        found += total;
+        __syncthreads();
+      }
+    }
+    if (tid == 0) {
+      const double dn = (double)m;
+      W.ox[p] = sx / dn; W.oy[p] = sy / dn; W.oz[p] = sz / dn;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_transform_aos(const double* __restrict__ aos, size_t n, MapFrontArgs A,
+                                                       double* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  double x, y, z;
+  transform_point(A.M, aos[3 * i], aos[3 * i + 1], aos[3 * i + 2], &x, &y, &z);
+  out[3 * i] = x; out[3 * i + 1] = y; out[3 * i + 2] = z;
+}
+
+inline unsigned blocks_of(size_t n) { return (unsigned)((n + 255) / 256); }
+
+}  // namespace
+
+void launch_map_voxel(const MapFrontArgs& A, const MapVoxWork& W, hipStream_t s) {
+  const size_t n = W.n;
+  const int emit_blocks = (int)blocks_of(n + 1);   // (n + 1: an empty job still has a block that reports a size of 0)
+  hipLaunchKernelGGL(k_map_front, dim3(blocks_of(std::max<size_t>(n, 1))), dim3(256), 0, s, A, W, emit_blocks);
+  if (n > 0) hipLaunchKernelGGL(k_map_insert, dim3(blocks_of(n)), dim3(256), 0, s, W);
+  hipLaunchKernelGGL(k_map_emit, dim3(emit_blocks), dim3(256), 0, s, W, emit_blocks);
+  if (n <= (size_t)kMapVoxLocal) return;   // (no voxel can be big)
+  hipLaunchKernelGGL(k_map_scatter, dim3(blocks_of(n)), dim3(256), 0, s, W);
+  hipLaunchKernelGGL(k_map_big, dim3((unsigned)std::min(W.big_max, 1024)), dim3(256), 0, s, W);
+}
+
+int map_emit_resident_blocks(int device_cus) {   // as vox_emit_resident_blocks (tl_submap.hip), for k_map_emit
+  static std::atomic<int> per_cu_cache{-1};
+  int per_cu = per_cu_cache.load(std::memory_order_relaxed);
+  if (per_cu < 0) {
+    int occ = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_map_emit, 256, 0) != hipSuccess || occ < 1) { (void)hipGetLastError(); occ = 1; }
+    per_cu = occ;
+    per_cu_cache.store(occ, std::memory_order_relaxed);
+  }
+  const long long all = (long long)device_cus * per_cu;
+  return (int)(all - all / 16);
+}
+
+void launch_transform_aos(const double* aos, size_t n, const double M[16], double* out, hipStream_t s) {
+  if (n == 0) return;
+  MapFrontArgs A;
+  memset(&A, 0, sizeof(A));
+  for (int k = 0; k < 16; ++k) A.M[k] = M[k];
+  hipLaunchKernelGGL(k_transform_aos, dim3(blocks_of(n)), dim3(256), 0, s, aos, n, A, out);
+}
+
+}  // namespace tl

@@ -1,0 +1,67 @@
+"""PCD export of the global map.
+
+The reference declares a `saveMap` service (srv/saveMap.srv) and never serves it; this is the file a user of the map needs.
+PCD v0.7 (the Point Cloud Library's format), fields `x y z`, each `F 8` (float64), so the device's doubles are written and
+read back bit for bit.  `DATA binary` by default; `ascii=True` writes every value with 17 significant digits (also exact).
+"""
+from __future__ import annotations
+
+import numpy as np
+
+_FIELDS = ("x", "y", "z")
+
+
+def write_pcd(path: str, xyz, ascii: bool = False) -> None:
+    """Writes an (n, 3) cloud as PCD v0.7 with float64 x y z."""
+    a = np.ascontiguousarray(np.asarray(xyz, dtype="<f8").reshape(-1, 3))
+    n = len(a)
+    header = ("# .PCD v0.7 - Point Cloud Data file format\n"
+              "VERSION 0.7\n"
+              "FIELDS x y z\n"
+              "SIZE 8 8 8\n"
+              "TYPE F F F\n"
+              "COUNT 1 1 1\n"
+              f"WIDTH {n}\n"
+              "HEIGHT 1\n"
+              "VIEWPOINT 0 0 0 1 0 0 0\n"
+              f"POINTS {n}\n"
+              f"DATA {'ascii' if ascii else 'binary'}\n")
+    with open(path, "wb") as fh:
+        fh.write(header.encode("ascii"))
+        if ascii:
+            fh.write("".join(f"{x:.17g} {y:.17g} {z:.17g}\n" for x, y, z in a.tolist()).encode("ascii"))
+        else:
+            fh.write(a.tobytes())
+
+
+def read_pcd(path: str) -> np.ndarray:
+    """Reads a PCD v0.7 file whose fields are x y z, float64 (`F 8`), DATA ascii or binary -> (n, 3) float64."""
+    with open(path, "rb") as fh:
+        raw = fh.read()
+    head, pos = {}, 0
+    while True:
+        end = raw.index(b"\n", pos)
+        line = raw[pos:end].decode("ascii").strip()
+        pos = end + 1
+        if not line or line.startswith("#"):
+            continue
+        key, _, val = line.partition(" ")
+        head[key.upper()] = val.split()
+        if key.upper() == "DATA":
+            break
+    if tuple(head.get("FIELDS", ())) != _FIELDS or head.get("SIZE") != ["8"] * 3 or head.get("TYPE") != ["F"] * 3 \
+            or head.get("COUNT", ["1"] * 3) != ["1"] * 3:
+        raise ValueError(f"{path}: only FIELDS x y z with SIZE 8 / TYPE F / COUNT 1 are read")
+    n = int(head["POINTS"][0])
+    kind = head["DATA"][0]
+    if kind == "binary":
+        body = raw[pos: pos + 24 * n]
+        if len(body) != 24 * n:
+            raise ValueError(f"{path}: {len(body)} bytes of data for {n} points")
+        return np.frombuffer(body, dtype="<f8").reshape(n, 3).astype(np.float64)
+    if kind == "ascii":
+        vals = np.array(raw[pos:].split(), dtype=np.float64)
+        if len(vals) != 3 * n:
+            raise ValueError(f"{path}: {len(vals)} values for {n} points")
+        return vals.reshape(n, 3)
+    raise ValueError(f"{path}: DATA {kind} is not supported")

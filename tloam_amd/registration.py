@@ -63,6 +63,20 @@ class OdomConfig(C.Structure):
     _fields_ = [("seg", SegConfig), ("feature", FeatureConfig), ("submap", SubmapConfig), ("edge_down_sample", C.c_double)]
 
 
+class MapConfig(C.Structure):
+    """tloam_map_config: mapping_flag (lidar_odometry.yaml:21), the map's voxel (front_end.cpp:272), the HBM reserved."""
+    _fields_ = [("enabled", C.c_int32), ("reserved0", C.c_int32), ("voxel", C.c_double), ("reserve_points", C.c_int64)]
+
+
+class MapInfo(C.Structure):
+    """tloam_map_info."""
+    _fields_ = [("n_points", C.c_int64), ("n_frames", C.c_int64), ("last_first", C.c_int64), ("last_count", C.c_int64),
+                ("capacity_points", C.c_int64), ("overflow_frames", C.c_int64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 class TlsConfig(C.Structure):
     """tloam_tls_config: the 16 keys of the `TLS:` block (config/mapping/lidar_odometry.yaml:23-39)."""
     _fields_ = [
@@ -198,6 +212,11 @@ def load_library():
         "tloam_odom_default_config": (None, [C.POINTER(OdomConfig)]),
         "tloam_odometry_reset": (C.c_int, [vp, C.POINTER(OdomConfig), dp]),
         "tloam_odometry_frame": (C.c_int, [vp, dp, sz, dp, C.POINTER(OdomStats)]),
+        "tloam_map_default_config": (None, [C.POINTER(MapConfig)]),
+        "tloam_map_configure": (C.c_int, [vp, C.POINTER(MapConfig)]),
+        "tloam_map_get_info": (C.c_int, [vp, C.POINTER(MapInfo)]),
+        "tloam_map_read": (C.c_int, [vp, sz, sz, dp]),
+        "tloam_registered_scan": (C.c_int, [vp, sz, C.POINTER(sz), dp]),
         "tloam_rccl_unique_id": (C.c_int, [vp]),
         "tloam_comm_init_rccl": (C.c_int, [vp, C.c_int, C.c_int, vp]),
         "tloam_comm_init_callback": (C.c_int, [vp, C.c_int, C.c_int, ALLREDUCE_FN, vp]),
@@ -227,7 +246,8 @@ EXPORTED_SYMBOLS = (
     "tloam_submap_default_config", "tloam_submap_init", "tloam_submap_update", "tloam_get_target",
     "tloam_feature_default_config", "tloam_pca_info", "tloam_extract_planar_sphere",
     "tloam_seg_default_config", "tloam_segment", "tloam_voxel_down_sample", "tloam_odom_default_config",
-    "tloam_odometry_reset", "tloam_odometry_frame", "tloam_rccl_unique_id", "tloam_comm_init_rccl",
+    "tloam_odometry_reset", "tloam_odometry_frame", "tloam_map_default_config", "tloam_map_configure", "tloam_map_get_info",
+    "tloam_map_read", "tloam_registered_scan", "tloam_rccl_unique_id", "tloam_comm_init_rccl",
     "tloam_comm_mailbox_export", "tloam_comm_init_mailbox",
     "tloam_comm_init_callback", "tloam_shard_range", "tloam_shard_ranges_frame", "tloam_se3_exp", "tloam_se3_log", "tloam_se3_plus",
 )
@@ -539,6 +559,35 @@ class HipRegistration:
                 self._n[("s", k)] = int(m)
         return rc, T.reshape(4, 4).T.copy(), st.as_dict()
 
+    # ---- the global map and the registered scan (FrontEnd::spinOnce :84-92, updateSubmap :269-274)
+    def map_configure(self, cfg: MapConfig | None = None, **over):
+        """mapping on / off (default_map_config(**over) when cfg is None); empties the map.  Kept across odometry_reset."""
+        cfg = cfg if cfg is not None else default_map_config(**over)
+        self._check(self.L.tloam_map_configure(self.h, C.byref(cfg)), "tloam_map_configure")
+
+    def map_info(self) -> dict:
+        info = MapInfo()
+        self._check(self.L.tloam_map_get_info(self.h, C.byref(info)), "tloam_map_get_info")
+        return info.as_dict()
+
+    def map_read(self, first=0, count=None):
+        """points [first, first + count) of the global map as an (m, 3) float64 array (count None: to the end)"""
+        if count is None:
+            count = max(self.map_info()["n_points"] - int(first), 0)
+        out = np.zeros((max(int(count), 1), 3))
+        self._check(self.L.tloam_map_read(self.h, int(first), int(count), _dp(out)), "tloam_map_read")
+        return out[: int(count)].copy()
+
+    def registered_scan(self):
+        """the last accepted frame's raw scan transformed by its pose (/raw_cloud, front_end.cpp:84-86) as (n, 3)"""
+        n = C.c_size_t(0)
+        rc = self.L.tloam_registered_scan(self.h, 0, C.byref(n), None)
+        if rc not in (0, -1) or (rc == -1 and n.value == 0):
+            self._check(rc, "tloam_registered_scan")
+        out = np.zeros((max(n.value, 1), 3))
+        self._check(self.L.tloam_registered_scan(self.h, n.value, C.byref(n), _dp(out)), "tloam_registered_scan")
+        return out[: n.value].copy()
+
     def fitness(self):
         f, r = C.c_double(0), C.c_double(0)
         rc = self.L.tloam_fitness(self.h, C.byref(f), C.byref(r))
@@ -736,6 +785,17 @@ def default_odom_config(**over) -> OdomConfig:
             setattr(cfg, k, v)
         else:
             raise KeyError(k)
+    return cfg
+
+
+def default_map_config(**over) -> MapConfig:
+    """tloam_map_default_config (mapping off, voxel 1.0) with keyword overrides, e.g. enabled=1"""
+    cfg = MapConfig()
+    load_library().tloam_map_default_config(C.byref(cfg))
+    for k, v in over.items():
+        if not hasattr(cfg, k):
+            raise KeyError(k)
+        setattr(cfg, k, v)
     return cfg
 
 

@@ -24,6 +24,7 @@ ground clouds, front_end.cpp:183,186).  A frame the node publishes nothing for (
 `pipeline="device"` replaces all of the above with one `tloam_odometry_frame` per scan: the
 reference's front end -- the segmentation node, processCloud's VoxelDownSample (averages, not `_voxel_first`), no
 `at_least()` padding -- with every cloud in HBM; a frame the device skips (TLOAM_E_TOO_FEW_POINTS) is left out and listed.
+With a map configuration it also keeps the global map on the device and can write it as PCD.
 
 Host-side glue only (numpy + the C ABI through tloam_amd.registration); no oracle, no CPU fallback of any device stage."""
 from __future__ import annotations
@@ -34,7 +35,7 @@ import time
 
 import numpy as np
 
-from . import kitti_io
+from . import kitti_io, map_io
 from .synth import Frame
 
 
@@ -123,11 +124,16 @@ def _read_scan(path):
     return np.asarray(path, np.float64).reshape(-1, 3) if isinstance(path, np.ndarray) else kitti_io.read_velodyne_bin(path)[0]
 
 
-def replay_device(H, scan_files, out_poses: str | None = None, odom_cfg=None, init_pose=None, max_frames=None):
+def replay_device(H, scan_files, out_poses: str | None = None, odom_cfg=None, init_pose=None, max_frames=None,
+                  map_cfg=None, out_map: str | None = None):
     """pipeline="device": one tloam_odometry_frame per scan.  Frames the device skips
     (TLOAM_E_TOO_FEW_POINTS) are left out of the poses and listed in the stats as `skipped` (their positions in
-    `scan_files`); `frame_of_pose` gives each pose's position."""
+    `scan_files`); `frame_of_pose` gives each pose's position.
+    map_cfg (a MapConfig): the global map is configured with it before the run; the stats get its
+    `map` info, and out_map names a PCD file the map is written to (tloam_amd/map_io.py)."""
     files = scan_files[: max_frames] if max_frames else scan_files
+    if map_cfg is not None:
+        H.map_configure(map_cfg)
     H.odometry_reset(init_pose, odom_cfg)
     poses, at, skipped, t_frame, iters = [], [], [], [], 0
     out = open(out_poses, "w") if out_poses else None
@@ -153,8 +159,13 @@ def replay_device(H, scan_files, out_poses: str | None = None, odom_cfg=None, in
         if out:
             out.close()
     m = lambda v: round(float(np.mean(v)), 4) if v else None  # noqa: E731
-    return poses, {"frames": len(poses), "skipped": skipped, "frame_of_pose": at, "ms_odometry_frame": m(t_frame),
-                   "gn_iters_per_frame": round(iters / max(len(poses) - 1, 1), 2)}
+    stats = {"frames": len(poses), "skipped": skipped, "frame_of_pose": at, "ms_odometry_frame": m(t_frame),
+             "gn_iters_per_frame": round(iters / max(len(poses) - 1, 1), 2)}
+    if map_cfg is not None:
+        stats["map"] = H.map_info()
+        if out_map:
+            map_io.write_pcd(out_map, H.map_read())
+    return poses, stats
 
 
 def replay(H, scan_files, out_poses: str | None = None, feature_cfg=None, sensor_height: float = 1.73, max_frames=None,
