@@ -514,6 +514,45 @@ int tloam_map_read(tloam_ctx* ctx, size_t first, size_t count, double* out_aos);
 int tloam_registered_scan(tloam_ctx* ctx, size_t capacity, size_t* n, double* out_aos);
 /* Every map call on a context with nranks > 1: TLOAM_E_INVALID, as the frame. */
 
+/* ---- the merged voxel map of the odometry frame (additive to ABI 8; nothing in the reference) --------------
+ * One voxel grid for the whole run, origin o and voxel v fixed by the configuration; each occupied voxel keeps the count N and
+ * the int64 sums Q of the quantised offsets of every return that ever fell in it.  The frames that add are those that append
+ * to the tloam_map_* map when it is on (accepted later frames); their input is the registered scan (tloam_registered_scan's
+ * doubles), non-finite returns left out.  Per point and axis: s = (p - o) / v, i = (int64) floor(s),
+ * q = (int64) floor((s - i) * 2^24 + 0.5) in [0, 2^24].  A frame with |i| >= 2^20 on an axis for any finite point adds
+ * nothing and counts in overflow_frames; its pose is not affected.  Centroid per axis:
+ * c = o + v * ((double) i + ((double) Q / (double) N) * 2^-24) -- within v * 2^-25 of the mean before its last rounding.
+ * Voxel ids in order of creation; a frame's new voxels in order of their smallest point index in its scan.  DESIGN.md 14. */
+typedef struct tloam_voxel_map_config {
+  int32_t enabled;          /* 0 */
+  int32_t reserved0;
+  double voxel;             /* v: 1.0 */
+  double origin[3];         /* o: (0, 0, 0) */
+  int64_t reserve_voxels;   /* voxels of HBM reserved when enabled; 0 = 2^20; grows past it by doubling */
+} tloam_voxel_map_config;
+void tloam_voxel_map_default_config(tloam_voxel_map_config* cfg);
+/* cfg NULL: the defaults.  Empties the map; the configuration persists across tloam_odometry_reset (which empties the map).
+ * voxel <= 0 or not finite, a non-finite origin or reserve_voxels < 0: TLOAM_E_INVALID.  Disabling releases its device memory. */
+int tloam_voxel_map_configure(tloam_ctx* ctx, const tloam_voxel_map_config* cfg);
+
+typedef struct tloam_voxel_map_info {
+  int64_t n_voxels;          /* occupied voxels */
+  int64_t n_points;          /* returns in them: the sum of N */
+  int64_t n_frames;          /* frames that added since the last reset / configure */
+  int64_t last_new;          /* voxels the newest adding frame created */
+  int64_t capacity_voxels;   /* voxels the map holds before it grows */
+  int64_t overflow_frames;   /* frames whose scan left the grid: added nothing */
+} tloam_voxel_map_info;
+int tloam_voxel_map_get_info(tloam_ctx* ctx, tloam_voxel_map_info* info);
+/* voxels [first, first + count) in id order: centroids AoS and counts N.  Either output may be NULL.  A range beyond n_voxels:
+ * TLOAM_E_INVALID. */
+int tloam_voxel_map_read(tloam_ctx* ctx, size_t first, size_t count, double* centroids_aos, int64_t* counts);
+/* The voxels whose centroid lies in [lo, hi] on every axis (inclusive) and whose N >= min_count, in id order.  *n receives the
+ * size even when capacity is too small (then nothing is copied and TLOAM_E_INVALID is returned).  Either output may be NULL. */
+int tloam_voxel_map_read_box(tloam_ctx* ctx, const double lo[3], const double hi[3], int64_t min_count, size_t capacity,
+                             size_t* n, double* centroids_aos, int64_t* counts);
+/* Every voxel map call on a context with nranks > 1: TLOAM_E_INVALID. */
+
 /* ---- multi-GPU: correspondence set sharded over ranks, one all-reduce per sweep --------
  * (nothing in the reference).  Call before set_source / set_correspondences.
  * (a) native RCCL over xGMI: unique_id = the 128 bytes of an ncclUniqueId made on rank 0

@@ -1,0 +1,188 @@
+"""The merged voxel map without a GPU: the ctypes mirrors of tloam_voxel_map_config / _info against the C
+header, the defaults, the new entry points in the built library, properties of the int64 restatement (tests/voxel_map_np.py)
+the device is checked against, and the voxel PCD round trip."""
+import ctypes as C
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+
+import voxel_map_np as V  # noqa: E402
+from tloam_amd import map_io  # noqa: E402
+from tloam_amd import registration as reg  # noqa: E402
+
+ROOT = os.path.dirname(HERE)
+VMAP_SYMBOLS = ("tloam_voxel_map_default_config", "tloam_voxel_map_configure", "tloam_voxel_map_get_info",
+                "tloam_voxel_map_read", "tloam_voxel_map_read_box")
+
+
+def test_voxel_map_struct_layout_matches_the_c_header():
+    src = r'''
+#include <stdio.h>
+#include <stddef.h>
+#include "tloam_hip.h"
+int main(void) {
+  printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(tloam_voxel_map_config),
+         offsetof(tloam_voxel_map_config, enabled), offsetof(tloam_voxel_map_config, reserved0),
+         offsetof(tloam_voxel_map_config, voxel), offsetof(tloam_voxel_map_config, origin),
+         offsetof(tloam_voxel_map_config, reserve_voxels), sizeof(tloam_voxel_map_info),
+         offsetof(tloam_voxel_map_info, n_voxels), offsetof(tloam_voxel_map_info, n_points),
+         offsetof(tloam_voxel_map_info, n_frames), offsetof(tloam_voxel_map_info, last_new),
+         offsetof(tloam_voxel_map_info, capacity_voxels), offsetof(tloam_voxel_map_info, overflow_frames));
+  return 0;
+}'''
+    with tempfile.TemporaryDirectory() as d:
+        c = os.path.join(d, "t.c"); exe = os.path.join(d, "t")
+        open(c, "w").write(src)
+        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
+        vals = list(map(int, subprocess.check_output([exe]).split()))
+    M, I = reg.VoxelMapConfig, reg.VoxelMapInfo
+    assert vals == [C.sizeof(M), M.enabled.offset, M.reserved0.offset, M.voxel.offset, M.origin.offset,
+                    M.reserve_voxels.offset, C.sizeof(I), I.n_voxels.offset, I.n_points.offset, I.n_frames.offset,
+                    I.last_new.offset, I.capacity_voxels.offset, I.overflow_frames.offset]
+    assert vals[:6] == [48, 0, 4, 8, 16, 40] and vals[6] == 48
+
+
+def test_voxel_map_defaults():
+    cfg = reg.default_voxel_map_config()
+    assert cfg.enabled == 0 and cfg.voxel == 1.0 and list(cfg.origin) == [0.0, 0.0, 0.0] and cfg.reserve_voxels == 0
+    over = reg.default_voxel_map_config(enabled=1, voxel=0.5, origin=(1.0, -2.0, 3.5), reserve_voxels=64)
+    assert over.enabled == 1 and over.voxel == 0.5 and list(over.origin) == [1.0, -2.0, 3.5] and over.reserve_voxels == 64
+    with pytest.raises(KeyError):
+        reg.default_voxel_map_config(size=1.0)
+
+
+def test_voxel_map_symbols_are_exported():
+    L = reg.load_library()
+    for name in VMAP_SYMBOLS:
+        assert name in reg.EXPORTED_SYMBOLS
+        getattr(L, name)
+    out = subprocess.check_output(["nm", "-D", "--defined-only", reg.LIB_PATH], text=True)
+    exported = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    assert set(VMAP_SYMBOLS) <= exported
+
+
+def cloud(rng, n, spread=20.0):
+    """clustered returns: many per voxel, as a raw scan has"""
+    centres = rng.uniform(-spread, spread, (max(n // 200, 1), 3))
+    return centres[rng.integers(0, len(centres), n)] + rng.normal(0.0, 0.7, (n, 3))
+
+
+@pytest.mark.parametrize("seed", (1, 2, 3))
+def test_sums_do_not_depend_on_the_partition(seed):
+    rng = np.random.default_rng(seed)
+    pts = cloud(rng, 20000)
+    _, i, q, over = V.quantise(pts, 1.0, (0.3, -0.2, 0.1))
+    assert not over
+    keys, _, N, Q = V.frame_sums(i, q)
+    for _ in range(3):
+        perm = rng.permutation(len(i))
+        cuts = np.sort(rng.choice(np.arange(1, len(i)), size=rng.integers(1, 12), replace=False))
+        acc = {}
+        for part in np.split(perm, cuts):
+            k, _, n, qq = V.frame_sums(i[part], q[part])
+            for kk, nn, q3 in zip(k.tolist(), n.tolist(), qq.tolist()):
+                a = acc.setdefault(kk, [0, 0, 0, 0])
+                a[0] += nn; a[1] += q3[0]; a[2] += q3[1]; a[3] += q3[2]
+        assert sorted(acc) == sorted(keys.tolist())
+        for kk, nn, q3 in zip(keys.tolist(), N.tolist(), Q.tolist()):
+            assert acc[kk] == [nn, *q3]
+    # frames added one by one equal the same points as one frame (counts and sums; the ids are those of first occurrence)
+    M1, M2 = V.VoxelMapNP(1.0, (0.3, -0.2, 0.1)), V.VoxelMapNP(1.0, (0.3, -0.2, 0.1))
+    M1.add_frame(pts)
+    for part in np.array_split(pts, 5):
+        M2.add_frame(part)
+    assert M1.keys.tolist() == M2.keys.tolist()
+    assert M1.N.tolist() == M2.N.tolist() and M1.Q.tolist() == M2.Q.tolist()
+    assert M1.centroids().tobytes() == M2.centroids().tobytes()
+
+
+@pytest.mark.parametrize("voxel,origin", ((1.0, (0.0, 0.0, 0.0)), (0.25, (10.5, -3.0, 2.0)), (3.0, (-100.0, 7.0, 0.0))))
+def test_centroid_error_is_within_the_bound(voxel, origin):
+    rng = np.random.default_rng(7)
+    pts = cloud(rng, 30000, spread=60.0)
+    M = V.VoxelMapNP(voxel, origin)
+    assert M.add_frame(pts)
+    c = M.centroids()
+    # the exact mean per voxel, in long double where the platform has it
+    _, i, _, _ = V.quantise(pts, voxel, origin)
+    inv = np.array([M.id_of[int(k)] for k in V.pack(i)])
+    acc = np.zeros((len(M.keys), 3), np.longdouble)
+    np.add.at(acc, inv, pts.astype(np.longdouble))
+    mean = acc / M.N[:, None].astype(np.longdouble)
+    err = np.abs(c.astype(np.longdouble) - mean).max()
+    # v * 2^-25 from the quantisation, a few ulps of the coordinates from the roundings of s, the mean and c
+    scale = np.abs(np.asarray(origin)).max() + 60.0 + voxel
+    bound = voxel * 2.0 ** -25 + 8 * scale * np.finfo(np.float64).eps
+    assert err <= bound, (float(err), bound)
+    assert (M.N >= 1).all() and M.N.sum() == len(pts)
+
+
+def test_faces_and_the_edge_of_the_grid():
+    lim = V.LIMIT
+    # on a face: s exactly an integer -> that voxel, q = 0; just below: the voxel before, q = 2^24
+    pts = np.array([[0.0, 1.0, -1.0], [np.nextafter(1.0, 0.0), 0.0, 0.0], [0.5, 0.5, 0.5]])
+    _, i, q, over = V.quantise(pts)
+    assert not over
+    assert i.tolist() == [[0, 1, -1], [0, 0, 0], [0, 0, 0]]
+    assert q[0].tolist() == [0, 0, 0] and q[1, 0] == 1 << 24 and q[2].tolist() == [1 << 23] * 3
+    # |i| = 2^20 - 1 is in the grid on both sides, 2^20 and -2^20 are not
+    edge = np.array([[lim - 0.5, -(lim - 1.0), 0.0], [-(lim - 1) + 0.0, lim - 1.0, lim - 0.25]])
+    _, i, q, over = V.quantise(edge)
+    assert not over and np.abs(i).max() == lim - 1 and i.min() == -(lim - 1)
+    keys = V.pack(i)
+    assert (keys >= 0).all() and (keys < (1 << 63)).all()
+    for bad in ([lim + 0.0, 0.0, 0.0], [0.0, -lim - 0.5, 0.0], [0.0, 0.0, -lim + 0.0]):
+        _, _, _, over = V.quantise(np.array([[1.0, 2.0, 3.0], bad]))
+        assert over, bad
+    M = V.VoxelMapNP()
+    assert M.add_frame(edge)
+    assert not M.add_frame(np.array([[lim + 1.0, 0.0, 0.0]])) and M.overflow_frames == 1 and M.n_frames == 1
+    c = M.centroids()
+    assert ((c >= M.i) & (c <= M.i + 1)).all()   # (v = 1, o = 0: a centroid lies in its voxel, faces included)
+    # non-finite rows are left out; they do not shift the order of the others
+    nf = np.array([[np.nan, 0.0, 0.0], [2.5, 0.5, 0.5], [np.inf, 1.0, 1.0], [0.5, 0.5, 0.5]])
+    M = V.VoxelMapNP()
+    M.add_frame(nf)
+    assert M.i.tolist() == [[2, 0, 0], [0, 0, 0]] and M.N.tolist() == [1, 1]
+
+
+def test_ids_follow_first_occurrence_across_frames():
+    M = V.VoxelMapNP()
+    M.add_frame(np.array([[5.5, 0.5, 0.5], [1.5, 0.5, 0.5], [5.2, 0.1, 0.9]]))
+    assert M.i[:, 0].tolist() == [5, 1] and M.N.tolist() == [2, 1]
+    M.add_frame(np.array([[9.5, 0.5, 0.5], [1.5, 0.5, 0.5], [3.5, 0.5, 0.5], [9.1, 0.2, 0.2]]))
+    assert M.i[:, 0].tolist() == [5, 1, 9, 3] and M.N.tolist() == [2, 2, 2, 1] and M.last_new == 2
+    assert M.box((0, 0, 0), (6, 1, 1), 2).tolist() == [0, 1]
+    assert M.box((0, 0, 0), (100, 1, 1), 1).tolist() == [0, 1, 2, 3]
+    assert M.box((100, 0, 0), (101, 1, 1), 1).tolist() == []
+
+
+@pytest.mark.parametrize("ascii", (False, True))
+def test_voxel_pcd_round_trip_is_bit_exact(tmp_path, ascii):
+    rng = np.random.default_rng(5)
+    cen = np.concatenate([rng.normal(0, 50, (997, 3)), [[0.0, -0.0, 5e-324], [1e308, -1e-300, np.pi]]])
+    cnt = rng.integers(1, 1 << 40, len(cen)).astype(np.int64)
+    path = str(tmp_path / "vmap.pcd")
+    map_io.write_voxel_pcd(path, cen, cnt, ascii=ascii)
+    c2, n2 = map_io.read_voxel_pcd(path)
+    assert c2.dtype == np.float64 and c2.shape == cen.shape and n2.dtype == np.int64
+    assert c2.tobytes() == cen.tobytes() and n2.tobytes() == cnt.tobytes()
+    head = open(path, "rb").read(400).decode("ascii", errors="replace")
+    for line in ("VERSION 0.7", "FIELDS x y z count", "SIZE 8 8 8 8", "TYPE F F F I", f"POINTS {len(cen)}"):
+        assert line in head
+    empty = str(tmp_path / "empty.pcd")
+    map_io.write_voxel_pcd(empty, np.zeros((0, 3)), np.zeros(0, np.int64), ascii=ascii)
+    c3, n3 = map_io.read_voxel_pcd(empty)
+    assert c3.shape == (0, 3) and n3.shape == (0,)
+    with pytest.raises(ValueError):   # the x y z file of the append map is not a voxel map file
+        map_io.write_pcd(empty, cen[:4])
+        map_io.read_voxel_pcd(empty)
+    with pytest.raises(ValueError):
+        map_io.write_voxel_pcd(empty, cen[:4], cnt[:3])

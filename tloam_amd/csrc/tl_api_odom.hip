@@ -67,6 +67,8 @@ int odometry_frame_body(tloam_ctx* c, const double* xyz, size_t n, double pose[1
   // ---- the global map (mapping on, later frames): room for what this frame can append, before anything else changes
   int rc = first ? TLOAM_OK : map_frame_reserve(c, n);
   if (rc != TLOAM_OK) return rc;
+  rc = first ? TLOAM_OK : vmap_frame_reserve(c, n);   // (the merged voxel map, likewise: tl_api_vmap.hip)
+  if (rc != TLOAM_OK) return rc;
 
   // ---- Segmentation::spinOnce on the raw scan: the one upload of the frame
   SegParams P;
@@ -212,11 +214,15 @@ int odometry_frame_body(tloam_ctx* c, const double* xyz, size_t n, double pose[1
   // transformed by the pose, voxel-gridded, appended to the global map (mapping on; tl_api_map.hip)
   rc = map_stage_launch(c, pose, n);
   if (rc != TLOAM_OK) return rc;
+  rc = vmap_stage_launch(c, pose, n);   // the merged voxel map's staging of the same scan (voxel map on)
+  if (rc != TLOAM_OK) return rc;
   // ---- updateSubmap (:336) with the planar submap selection, the sphere one's size, edge / ground as down-sampled
   rc = submap_update_resident(c, pose, np, ns, ne_ds, ng_ds, O.block);
   if (rc != TLOAM_OK) return rc;
   st->host_syncs++;   // wait 4: the submap's sizes
   rc = map_stage_collect(c, st);   // (the map stage's count: already in pinned memory)
+  if (rc != TLOAM_OK) return rc;
+  rc = vmap_stage_collect(c, st);   // (likewise)
   if (rc != TLOAM_OK) return rc;
   return mrc;
 }
@@ -254,6 +260,7 @@ int tloam_odometry_reset(tloam_ctx* c, const tloam_odom_config* cfg, const doubl
   O.ready = true;
   O.reg_valid = false;   // no registered scan before the first frame
   map_empty(c);          // the global map starts again; its configuration stays
+  vmap_empty(c);         // the merged voxel map too
   return TLOAM_OK;
 }
 
@@ -273,6 +280,7 @@ int tloam_odometry_frame(tloam_ctx* c, const double* xyz, size_t n, double pose_
   (void)hipStreamSynchronize(c->stream);   // (a failed stage may have left work in flight; the success paths have drained)
   const bool accepted = rc == TLOAM_OK || rc == TLOAM_E_WEIGHT_RANGE;
   map_frame_end(c, accepted);
+  vmap_frame_end(c, accepted);
   if (accepted) {
     // spinOnce's /raw_cloud (:84-86): this scan by lidar_odom_pose -- still Identity on the first frame (front_end.hpp:106),
     // whatever the init pose

@@ -519,6 +519,17 @@ void launch_odom_counts(const OdomCountArgs& A, hipStream_t s);
 // VoxelDownSample of one transformed scan whose voxels can hold hundreds of returns (1 m cells on a raw scan): the leader of a voxel
 // (its smallest member) comes from an atomicMin, not from a walk of the member list; voxels of up to kMapVoxLocal members are
 // averaged by their leader as in k_vox_emit, larger ones by a workgroup each, their members sorted by index in LDS
+// Open3D TransformPoints: new = T * (x, y, z, 1), rows accumulated left to right; point = new.head<3>() / new(3).  Units that
+// call it are compiled with -ffp-contract=off (the oracle's pc_transform rounds so)
+__device__ __forceinline__ void map_transform_point(const double* M, double x, double y, double z, double* px, double* py,
+                                                    double* pz) {
+  double r[4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a) r[a] = ((M[a] * x + M[4 + a] * y) + M[8 + a] * z) + M[12 + a] * 1.0;
+  *px = r[0] / r[3];
+  *py = r[1] / r[3];
+  *pz = r[2] / r[3];
+}
 struct MapFrontArgs {
   const double* aos;          // the raw scan, AoS
   size_t n;
@@ -554,6 +565,63 @@ inline int map_big_max(size_t n) { return (int)(n / (kMapVoxLocal + 1) + 1); }
 void launch_map_voxel(const MapFrontArgs& A, const MapVoxWork& W, hipStream_t s);
 int map_emit_resident_blocks(int device_cus);
 void launch_transform_aos(const double* aos, size_t n, const double M[16], double* out, hipStream_t s);
+
+// ---- the merged voxel map of the odometry frame (tl_vmap.hip) ------------------------
+// One grid for the whole run (origin, voxel fixed); per voxel an int64 count and int64 sums of the quantised offsets
+// q = floor(frac(s) * 2^24 + 0.5), so that the sums are the same in any order.  A voxel's key packs i + 2^20 of each axis in
+// 21 bits (bit 63 clear: ~0 marks a free slot).  Persistent state in id order (keys, N, Qx, Qy, Qz) and an open-addressing
+// table slot -> id (-1: free) of load <= 1/2; a frame is staged in a table of its own and committed only once it is accepted
+constexpr int kVmapBits = 20;                       // |i| < 2^20 on every axis
+constexpr double kVmapQScale = 16777216.0;          // 2^24
+struct VmapStageWork {
+  const double *sx, *sy, *sz; // the transformed scan, SoA (the append map's k_map_front), or null: transform `aos` here
+  const double* aos;          // the raw scan, AoS
+  double M[16];               // column-major pose
+  size_t n;
+  double voxel, origin[3];
+  // the frame's table [fmask + 1]
+  unsigned long long fmask;
+  unsigned long long* fkey;
+  int* flead;                 // smallest point index of the voxel in this scan
+  unsigned long long* fsum;   // [4][fmask + 1]: N, Qx, Qy, Qz of the frame
+  int* fid;                   // the voxel's id (existing or new)
+  int* slot_of_pt;            // [n]
+  // the persistent table (read only here)
+  unsigned long long pmask;
+  const int* ptab;
+  const unsigned long long* pkey;
+  long long base;             // voxels before this frame: the first new id
+  unsigned long long* look;   // [emit blocks + 1] look-back words of k_vmap_emit
+  unsigned long long* ctl;    // [0] overflow, [1] finite points, [2] start tickets of k_vmap_emit, [3] fault, [4] new voxels
+  unsigned long long* host_seg;   // pinned: [0] new voxels, [1] points, [2] overflow, [3] fault, [7] check word
+  unsigned long long host_seq;
+};
+struct VmapTable {            // the persistent map
+  unsigned long long pmask;
+  int* ptab;
+  unsigned long long* pkey;
+  long long *pn, *pqx, *pqy, *pqz;
+};
+struct VmapReadArgs {
+  const unsigned long long* pkey;
+  const long long *pn, *pqx, *pqy, *pqz;
+  double voxel, origin[3];
+  size_t first, count;        // ids [first, first + count)
+  double lo[3], hi[3];        // read_box: the box (inclusive) ...
+  long long min_count;        // ... and the smallest N
+  double* out_c;              // AoS centroids (compacted for read_box)
+  long long* out_n;           // counts (may be null)
+  unsigned long long* look;   // read_box: [blocks + 1] look-back words, zero before the launch
+  unsigned long long* ctl;    // read_box: [0] start tickets, [1] fault, [2] selected voxels; zero before the launch
+};
+// clear | stage | emit: no host synchronisation; the new-voxel count reaches the host segment with k_vmap_emit
+void launch_vmap_stage(const VmapStageWork& W, hipStream_t s);
+// an accepted frame's staged voxels into the persistent map (the new ones keyed and entered in the table)
+void launch_vmap_commit(const VmapStageWork& W, const VmapTable& T, hipStream_t s);
+// the table of `T` (all slots free) rebuilt from the keys of ids [0, n)
+void launch_vmap_rehash(const VmapTable& T, size_t n, hipStream_t s);
+void launch_vmap_read(const VmapReadArgs& A, hipStream_t s);
+void launch_vmap_read_box(const VmapReadArgs& A, hipStream_t s);
 
 // ---- PCA feature extraction (tl_feature.hip; feature_extract.cpp:47-197) -----------------------
 struct FeatArgs {

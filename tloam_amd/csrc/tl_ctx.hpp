@@ -1,7 +1,8 @@
 // tl_ctx.hpp -- host-side context of the C ABI (include/tloam_hip.h), shared by the API translation units (tl_api.hip:
 // lifetime, tl_api_frames.hip: HBM residency + search grids, tl_api_match.hip: the scanMatching driver, tl_api_comm.hip: multi-GPU
 // exchange, tl_api_submap.hip: device-resident submap, tl_api_feature.hip: PCA features, tl_api_seg.hip: segmentation,
-// tl_api_odom.hip: the whole odometry frame, tl_api_map.hip: its global map and registered scan).
+// tl_api_odom.hip: the whole odometry frame, tl_api_map.hip: its global map and registered scan, tl_api_vmap.hip: its merged
+// voxel map).
 #pragma once
 
 #include <dlfcn.h>
@@ -217,6 +218,41 @@ struct MapState {
   }
 };
 
+// the merged voxel map of the odometry frame (tl_api_vmap.hip): the persistent map in id order and its
+// table (grown by doubling, rehashed from the keys), the frame's staging, and the pinned segment k_vmap_emit reports through
+struct VmapState {
+  tloam_voxel_map_config cfg = {0, 0, 1.0, {0.0, 0.0, 0.0}, 0};   // tloam_voxel_map_default_config until configured
+  DBuf<unsigned long long> key;    // [cap] per id
+  DBuf<long long> n, qx, qy, qz;   // [cap] per id
+  DBuf<int> tab;                   // [tmask + 1] slot -> id, -1 free
+  size_t cap = 0;
+  unsigned long long tmask = 0;
+  bool tab_dirty = false;          // emptied since the table was last cleared: cleared at the next frame / read
+  DBuf<unsigned long long> r_key;  // storage a regrowth replaced: freed once the frame has drained the stream
+  DBuf<long long> r_n, r_qx, r_qy, r_qz;
+  DBuf<int> r_tab;
+  int64_t n_voxels = 0, n_points = 0, n_frames = 0, last_new = 0, overflow_frames = 0;
+  // the frame's staging: its table, the slot of every point, the look-back words, control words; reads' scratch
+  DBuf<unsigned long long> fkey, fsum, look, ctl;
+  DBuf<int> flead, fid, slot_of_pt;
+  unsigned long long fmask = 0;    // the staged frame's table size - 1
+  DBuf<double> rd_c;
+  DBuf<long long> rd_n;
+  unsigned long long* h_seg = nullptr;      // pinned, device-visible: [0] new voxels, [1] points, [2] overflow, [3] fault, [7] check
+  unsigned long long* h_seg_dev = nullptr;
+  unsigned long long seq = 0;
+  unsigned long long pending_seq = 0;       // the stage of the frame in flight (0: none)
+  bool have_count = false;                  // its result, read at the frame's last wait, committed if the frame is accepted
+  int64_t new_voxels = 0, new_points = 0;
+  bool overflowed = false;
+  void release_storage() {
+    key.release(); n.release(); qx.release(); qy.release(); qz.release(); tab.release(); cap = 0; tmask = 0;
+    r_key.release(); r_n.release(); r_qx.release(); r_qy.release(); r_qz.release(); r_tab.release();
+    fkey.release(); fsum.release(); look.release(); ctl.release(); flead.release(); fid.release(); slot_of_pt.release();
+    rd_c.release(); rd_n.release();
+  }
+};
+
 // up to four SoA clouds (x, y, z, n) a search grid is built over -- the registered targets, or any other cloud
 struct CloudRef { const double *x, *y, *z; size_t n; };
 }  // namespace tlh
@@ -230,6 +266,7 @@ struct tloam_ctx {
   SegBuffers seg;
   OdomState odom;
   MapState map;
+  VmapState vmap;
   int device = 0;
   hipStream_t stream = nullptr;
   KindData kd[kKinds];
@@ -460,6 +497,13 @@ int map_stage_collect(tloam_ctx* c, tloam_odom_stats* st);
 void map_frame_end(tloam_ctx* c, bool accepted);
 void map_empty(tloam_ctx* c);
 void map_release(tloam_ctx* c);
+// tl_api_vmap.hip: the merged voxel map's stage, at the same four points of the frame
+int vmap_frame_reserve(tloam_ctx* c, size_t n);
+int vmap_stage_launch(tloam_ctx* c, const double pose[16], size_t n);
+int vmap_stage_collect(tloam_ctx* c, tloam_odom_stats* st);
+void vmap_frame_end(tloam_ctx* c, bool accepted);
+void vmap_empty(tloam_ctx* c);
+void vmap_release(tloam_ctx* c);
 int voxel_down_sample_launch(tloam_ctx* c, const size_t n[2], const double voxel[2], int nseg, double* const out[2][3]);
 int build_grids_over(tloam_ctx* c, GridBuffers& G, const double radius[tl::kKinds], const CloudRef clouds[tl::kKinds],
                      tl::GridView out[tl::kKinds], const double (*known_boxes)[6] = nullptr,

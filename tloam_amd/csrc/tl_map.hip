@@ -38,16 +38,6 @@ __device__ __forceinline__ bool in_box(const MapVoxWork& W, double x, double y, 
   return x >= W.lo && x <= W.hi && y >= W.lo && y <= W.hi && z >= W.lo && z <= W.hi;
 }
 
-__device__ __forceinline__ void transform_point(const double* M, double x, double y, double z, double* px, double* py, double* pz) {
-  // new = T * (x, y, z, 1), rows accumulated left to right; point = new.head<3>() / new(3)
-  double r[4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a) r[a] = ((M[a] * x + M[4 + a] * y) + M[8 + a] * z) + M[12 + a] * 1.0;
-  *px = r[0] / r[3];
-  *py = r[1] / r[3];
-  *pz = r[2] / r[3];
-}
-
 __global__ __launch_bounds__(256) void k_map_front(MapFrontArgs A, MapVoxWork W, int emit_blocks) {
   __shared__ double sm[3][256];
   __shared__ int s_last;
@@ -65,7 +55,7 @@ __global__ __launch_bounds__(256) void k_map_front(MapFrontArgs A, MapVoxWork W,
   double m[3] = {__builtin_inf(), __builtin_inf(), __builtin_inf()};
   if (i < A.n) {
     double x, y, z;
-    transform_point(A.M, A.aos[3 * i], A.aos[3 * i + 1], A.aos[3 * i + 2], &x, &y, &z);
+    map_transform_point(A.M, A.aos[3 * i], A.aos[3 * i + 1], A.aos[3 * i + 2], &x, &y, &z);
     W.x[i] = x; W.y[i] = y; W.z[i] = z;
     if (in_box(W, x, y, z)) { m[0] = x; m[1] = y; m[2] = z; }
   }
@@ -330,7 +320,7 @@ __global__ __launch_bounds__(256) void k_transform_aos(const double* __restrict_
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   double x, y, z;
-  transform_point(A.M, aos[3 * i], aos[3 * i + 1], aos[3 * i + 2], &x, &y, &z);
+  map_transform_point(A.M, aos[3 * i], aos[3 * i + 1], aos[3 * i + 2], &x, &y, &z);
   out[3 * i] = x; out[3 * i + 1] = y; out[3 * i + 2] = z;
 }
 

@@ -1,4 +1,4 @@
-"""PCD export of the global map.
+"""PCD export of the global map and of the merged voxel map (section 14).
 
 The reference declares a `saveMap` service (srv/saveMap.srv) and never serves it; this is the file a user of the map needs.
 PCD v0.7 (the Point Cloud Library's format), fields `x y z`, each `F 8` (float64), so the device's doubles are written and
@@ -64,4 +64,74 @@ def read_pcd(path: str) -> np.ndarray:
         if len(vals) != 3 * n:
             raise ValueError(f"{path}: {len(vals)} values for {n} points")
         return vals.reshape(n, 3)
+    raise ValueError(f"{path}: DATA {kind} is not supported")
+
+
+# ---- the merged voxel map: centroids and the count of returns behind each
+_VOX_FIELDS = ("x", "y", "z", "count")
+_VOX_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("count", "<i8")])
+
+
+def write_voxel_pcd(path: str, centroids, counts, ascii: bool = False) -> None:
+    """Writes the voxel map's (n, 3) centroids and (n,) counts as PCD v0.7: x y z float64 (`F 8`), count int64 (`I 8`)."""
+    c = np.asarray(centroids, dtype="<f8").reshape(-1, 3)
+    k = np.asarray(counts, dtype="<i8").reshape(-1)
+    if len(c) != len(k):
+        raise ValueError(f"{len(c)} centroids, {len(k)} counts")
+    n = len(c)
+    rec = np.empty(n, _VOX_DTYPE)
+    rec["x"], rec["y"], rec["z"], rec["count"] = c[:, 0], c[:, 1], c[:, 2], k
+    header = ("# .PCD v0.7 - Point Cloud Data file format\n"
+              "VERSION 0.7\n"
+              "FIELDS x y z count\n"
+              "SIZE 8 8 8 8\n"
+              "TYPE F F F I\n"
+              "COUNT 1 1 1 1\n"
+              f"WIDTH {n}\n"
+              "HEIGHT 1\n"
+              "VIEWPOINT 0 0 0 1 0 0 0\n"
+              f"POINTS {n}\n"
+              f"DATA {'ascii' if ascii else 'binary'}\n")
+    with open(path, "wb") as fh:
+        fh.write(header.encode("ascii"))
+        if ascii:
+            fh.write("".join(f"{x:.17g} {y:.17g} {z:.17g} {int(m)}\n"
+                             for (x, y, z), m in zip(c.tolist(), k.tolist())).encode("ascii"))
+        else:
+            fh.write(rec.tobytes())
+
+
+def read_voxel_pcd(path: str):
+    """Reads a file of write_voxel_pcd (DATA ascii or binary) -> (centroids (n, 3) float64, counts (n,) int64)."""
+    with open(path, "rb") as fh:
+        raw = fh.read()
+    head, pos = {}, 0
+    while True:
+        end = raw.index(b"\n", pos)
+        line = raw[pos:end].decode("ascii").strip()
+        pos = end + 1
+        if not line or line.startswith("#"):
+            continue
+        key, _, val = line.partition(" ")
+        head[key.upper()] = val.split()
+        if key.upper() == "DATA":
+            break
+    if tuple(head.get("FIELDS", ())) != _VOX_FIELDS or head.get("SIZE") != ["8"] * 4 \
+            or head.get("TYPE") != ["F", "F", "F", "I"] or head.get("COUNT", ["1"] * 4) != ["1"] * 4:
+        raise ValueError(f"{path}: only FIELDS x y z count with SIZE 8 / TYPE F F F I / COUNT 1 are read")
+    n = int(head["POINTS"][0])
+    kind = head["DATA"][0]
+    if kind == "binary":
+        body = raw[pos: pos + 32 * n]
+        if len(body) != 32 * n:
+            raise ValueError(f"{path}: {len(body)} bytes of data for {n} voxels")
+        rec = np.frombuffer(body, dtype=_VOX_DTYPE)
+        return np.stack([rec["x"], rec["y"], rec["z"]], axis=1).astype(np.float64), rec["count"].astype(np.int64)
+    if kind == "ascii":
+        rows = raw[pos:].split()
+        if len(rows) != 4 * n:
+            raise ValueError(f"{path}: {len(rows)} values for {n} voxels")
+        cols = [rows[i::4] for i in range(4)]
+        cen = np.array(cols[:3], dtype=np.float64).T.reshape(n, 3)
+        return np.ascontiguousarray(cen), np.array([int(v) for v in cols[3]], dtype=np.int64)
     raise ValueError(f"{path}: DATA {kind} is not supported")

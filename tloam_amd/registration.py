@@ -77,6 +77,21 @@ class MapInfo(C.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
+class VoxelMapConfig(C.Structure):
+    """tloam_voxel_map_config: the merged voxel map's switch, voxel v, origin o, the HBM reserved."""
+    _fields_ = [("enabled", C.c_int32), ("reserved0", C.c_int32), ("voxel", C.c_double), ("origin", C.c_double * 3),
+                ("reserve_voxels", C.c_int64)]
+
+
+class VoxelMapInfo(C.Structure):
+    """tloam_voxel_map_info."""
+    _fields_ = [("n_voxels", C.c_int64), ("n_points", C.c_int64), ("n_frames", C.c_int64), ("last_new", C.c_int64),
+                ("capacity_voxels", C.c_int64), ("overflow_frames", C.c_int64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 class TlsConfig(C.Structure):
     """tloam_tls_config: the 16 keys of the `TLS:` block (config/mapping/lidar_odometry.yaml:23-39)."""
     _fields_ = [
@@ -217,6 +232,11 @@ def load_library():
         "tloam_map_get_info": (C.c_int, [vp, C.POINTER(MapInfo)]),
         "tloam_map_read": (C.c_int, [vp, sz, sz, dp]),
         "tloam_registered_scan": (C.c_int, [vp, sz, C.POINTER(sz), dp]),
+        "tloam_voxel_map_default_config": (None, [C.POINTER(VoxelMapConfig)]),
+        "tloam_voxel_map_configure": (C.c_int, [vp, C.POINTER(VoxelMapConfig)]),
+        "tloam_voxel_map_get_info": (C.c_int, [vp, C.POINTER(VoxelMapInfo)]),
+        "tloam_voxel_map_read": (C.c_int, [vp, sz, sz, dp, C.POINTER(C.c_int64)]),
+        "tloam_voxel_map_read_box": (C.c_int, [vp, dp, dp, C.c_int64, sz, C.POINTER(sz), dp, C.POINTER(C.c_int64)]),
         "tloam_rccl_unique_id": (C.c_int, [vp]),
         "tloam_comm_init_rccl": (C.c_int, [vp, C.c_int, C.c_int, vp]),
         "tloam_comm_init_callback": (C.c_int, [vp, C.c_int, C.c_int, ALLREDUCE_FN, vp]),
@@ -247,7 +267,8 @@ EXPORTED_SYMBOLS = (
     "tloam_feature_default_config", "tloam_pca_info", "tloam_extract_planar_sphere",
     "tloam_seg_default_config", "tloam_segment", "tloam_voxel_down_sample", "tloam_odom_default_config",
     "tloam_odometry_reset", "tloam_odometry_frame", "tloam_map_default_config", "tloam_map_configure", "tloam_map_get_info",
-    "tloam_map_read", "tloam_registered_scan", "tloam_rccl_unique_id", "tloam_comm_init_rccl",
+    "tloam_map_read", "tloam_registered_scan", "tloam_voxel_map_default_config", "tloam_voxel_map_configure",
+    "tloam_voxel_map_get_info", "tloam_voxel_map_read", "tloam_voxel_map_read_box", "tloam_rccl_unique_id", "tloam_comm_init_rccl",
     "tloam_comm_mailbox_export", "tloam_comm_init_mailbox",
     "tloam_comm_init_callback", "tloam_shard_range", "tloam_shard_ranges_frame", "tloam_se3_exp", "tloam_se3_log", "tloam_se3_plus",
 )
@@ -259,6 +280,10 @@ def _dp(a):
 
 def _ip(a):
     return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _lp(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int64))
 
 
 def _aos(x):
@@ -588,6 +613,42 @@ class HipRegistration:
         self._check(self.L.tloam_registered_scan(self.h, n.value, C.byref(n), _dp(out)), "tloam_registered_scan")
         return out[: n.value].copy()
 
+    # ---- the merged voxel map
+    def voxel_map_configure(self, cfg: VoxelMapConfig | None = None, **over):
+        """voxel map on / off (default_voxel_map_config(**over) when cfg is None); empties it.  Kept across odometry_reset."""
+        cfg = cfg if cfg is not None else default_voxel_map_config(**over)
+        self._check(self.L.tloam_voxel_map_configure(self.h, C.byref(cfg)), "tloam_voxel_map_configure")
+
+    def voxel_map_info(self) -> dict:
+        info = VoxelMapInfo()
+        self._check(self.L.tloam_voxel_map_get_info(self.h, C.byref(info)), "tloam_voxel_map_get_info")
+        return info.as_dict()
+
+    def voxel_map_read(self, first=0, count=None):
+        """voxels [first, first + count) in id order -> (centroids (m, 3) float64, counts (m,) int64); count None: to the end"""
+        if count is None:
+            count = max(self.voxel_map_info()["n_voxels"] - int(first), 0)
+        m = int(count)
+        cen, cnt = np.zeros((max(m, 1), 3)), np.zeros(max(m, 1), np.int64)
+        self._check(self.L.tloam_voxel_map_read(self.h, int(first), m, _dp(cen), _lp(cnt)), "tloam_voxel_map_read")
+        return cen[:m].copy(), cnt[:m].copy()
+
+    def voxel_map_read_box(self, lo, hi, min_count=1):
+        """the voxels whose centroid lies in [lo, hi] (inclusive, every axis) with N >= min_count, in id order ->
+        (centroids (m, 3), counts (m,))"""
+        lo = np.ascontiguousarray(lo, dtype=np.float64).reshape(3)
+        hi = np.ascontiguousarray(hi, dtype=np.float64).reshape(3)
+        n = C.c_size_t(0)
+        rc = self.L.tloam_voxel_map_read_box(self.h, _dp(lo), _dp(hi), int(min_count), 0, C.byref(n), None, None)
+        if rc not in (0, -1) or (rc == -1 and n.value == 0):
+            self._check(rc, "tloam_voxel_map_read_box")
+        m = n.value
+        cen, cnt = np.zeros((max(m, 1), 3)), np.zeros(max(m, 1), np.int64)
+        if m:
+            self._check(self.L.tloam_voxel_map_read_box(self.h, _dp(lo), _dp(hi), int(min_count), m, C.byref(n), _dp(cen),
+                                                        _lp(cnt)), "tloam_voxel_map_read_box")
+        return cen[: n.value].copy(), cnt[: n.value].copy()
+
     def fitness(self):
         f, r = C.c_double(0), C.c_double(0)
         rc = self.L.tloam_fitness(self.h, C.byref(f), C.byref(r))
@@ -795,6 +856,19 @@ def default_map_config(**over) -> MapConfig:
     for k, v in over.items():
         if not hasattr(cfg, k):
             raise KeyError(k)
+        setattr(cfg, k, v)
+    return cfg
+
+
+def default_voxel_map_config(**over) -> VoxelMapConfig:
+    """tloam_voxel_map_default_config (off, voxel 1.0, origin 0) with keyword overrides, e.g. enabled=1, origin=(0, 0, 5)"""
+    cfg = VoxelMapConfig()
+    load_library().tloam_voxel_map_default_config(C.byref(cfg))
+    for k, v in over.items():
+        if not hasattr(cfg, k):
+            raise KeyError(k)
+        if k == "origin":
+            v = (C.c_double * 3)(*[float(x) for x in v])
         setattr(cfg, k, v)
     return cfg
 
