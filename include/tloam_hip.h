@@ -553,6 +553,49 @@ int tloam_voxel_map_read_box(tloam_ctx* ctx, const double lo[3], const double hi
                              size_t* n, double* centroids_aos, int64_t* counts);
 /* Every voxel map call on a context with nranks > 1: TLOAM_E_INVALID. */
 
+/* ---- deskew of the odometry frame's scan under constant velocity (additive to ABI 8) ---------------
+ * A spinning sensor sweeps for one scan_period; every return is in the sensor frame of its own firing time.  With deskew on, a
+ * frame corrects its scan with the motion xi = log(step), step = last_pose^-1 * lidar_odom_pose as stored when the previous
+ * frame was accepted (identity until the second frame has been accepted): return i, at sweep time s_i (in frame intervals,
+ * relative to the pose's instant), becomes p'_i = exp(s_i xi) p_i.
+ *   azimuth mode:  s_i = wrap_[0,2pi)(direction * (atan2(y, x) - start_azimuth)) / 2pi - ref_fraction
+ *   timed mode:    s_i = t_i / cfg.seg.scan_period, t_i in seconds relative to the pose's instant (tloam_odometry_frame_timed)
+ * A return with a non-finite coordinate, or with s_i == 0, is copied bit for bit.  A frame whose step is bitwise the identity
+ * corrects nothing and equals a frame with deskew off.  Segmentation runs on the raw scan; its index lists take the corrected
+ * coordinates, and so do the registered scan, the global map and the merged voxel map.  DESIGN.md 15. */
+typedef struct tloam_deskew_config {
+  int32_t enabled;         /* 0 */
+  int32_t time_source;     /* 0 azimuth, 1 per-point times (tloam_odometry_frame_timed) */
+  int32_t direction;       /* +1 counter-clockwise seen from +z (the order the q4 -> q1 ring step implies), -1 clockwise */
+  int32_t reserved0;
+  double start_azimuth;    /* rad: 0 */
+  double ref_fraction;     /* azimuth mode: the sweep fraction the pose describes: 0 */
+} tloam_deskew_config;
+void tloam_deskew_default_config(tloam_deskew_config* cfg);
+/* cfg NULL: the defaults.  Non-finite values, direction not +-1, an unknown time_source: TLOAM_E_INVALID.  Persists across
+ * tloam_odometry_reset; clears the info below. */
+int tloam_deskew_configure(tloam_ctx* ctx, const tloam_deskew_config* cfg);
+
+typedef struct tloam_deskew_info {
+  int64_t frames_deskewed;       /* accepted frames whose scan was corrected, since the last reset / configure */
+  int64_t last_frame;            /* the frame number of the last of them (tloam_odom_stats.frame), -1 none */
+  double last_twist[6];          /* its xi = (upsilon, omega), Sophus order */
+  double last_max_shift;         /* its max |p' - p| over the finite returns, m */
+  double next_motion_colmajor[16];   /* the step the next frame takes xi from */
+} tloam_deskew_info;
+int tloam_deskew_get_info(tloam_ctx* ctx, tloam_deskew_info* info);
+
+/* tloam_odometry_frame with per-point times t_sec[n] (seconds, relative to the pose's instant); deskew must be configured with
+ * time_source 1.  A non-finite time or |t_i / scan_period| > 2 refuses the frame with TLOAM_E_INVALID and leaves the odometry
+ * state unchanged.  t_sec NULL, or deskew off / in azimuth mode: TLOAM_E_INVALID; so is tloam_odometry_frame in timed mode. */
+int tloam_odometry_frame_timed(tloam_ctx* ctx, const double* xyz_aos, const double* t_sec, size_t n,
+                               double pose_out_colmajor[16], tloam_odom_stats* stats);
+/* The correction alone, on the device, with the frame's kernel: motion is the step (a rigid transform; xi = its log), t_sec NULL
+ * in azimuth mode.  cfg->enabled is not looked at.  In timed mode a bad time is TLOAM_E_INVALID (out_aos then undefined). */
+int tloam_deskew_scan(tloam_ctx* ctx, const tloam_deskew_config* cfg, double scan_period, const double motion_colmajor[16],
+                      const double* xyz_aos, const double* t_sec, size_t n, double* out_aos);
+/* Every deskew call on a context with nranks > 1: TLOAM_E_INVALID. */
+
 /* ---- multi-GPU: correspondence set sharded over ranks, one all-reduce per sweep --------
  * (nothing in the reference).  Call before set_source / set_correspondences.
  * (a) native RCCL over xGMI: unique_id = the 128 bytes of an ncclUniqueId made on rank 0

@@ -145,6 +145,7 @@ void tloam_destroy(tloam_ctx* c) {
   c->odom.release();
   tlh::map_release(c);
   tlh::vmap_release(c);
+  c->deskew.release();
   if (c->h_state) (void)hipHostFree(c->h_state);
   if (c->h_mirror) (void)hipHostFree(c->h_mirror);
   if (c->h_small) (void)hipHostFree(c->h_small);

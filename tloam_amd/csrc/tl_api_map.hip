@@ -123,7 +123,7 @@ int map_stage_launch(tloam_ctx* c, const double pose[16], size_t n) {
   W.fault = c->h_fault_dev + kFaultVoxEmit;
   MapFrontArgs A;
   memset(&A, 0, sizeof(A));
-  A.aos = c->seg.aos.p; A.n = n;
+  A.aos = frame_scan(c); A.n = n;   // (the deskewed copy when the frame corrected its scan)
   for (int k = 0; k < 16; ++k) A.M[k] = pose[k];
   launch_map_voxel(A, W, c->stream);
   M.pending_seq = W.host_seq;
@@ -275,7 +275,7 @@ int tloam_registered_scan(tloam_ctx* c, size_t capacity, size_t* n, double* out)
   HIPC(c, hipSetDevice(c->device));
   HIPC(c, c->misc.reserve(3 * m));
   if (from_map) launch_soa_to_aos(M.wx.p, M.wy.p, M.wz.p, m, c->misc.p, c->stream);
-  else launch_transform_aos(c->seg.aos.p, m, O.reg_pose, c->misc.p, c->stream);
+  else launch_transform_aos(O.reg_deskewed ? c->deskew.aos.p : c->seg.aos.p, m, O.reg_pose, c->misc.p, c->stream);
   HIPC(c, hipMemcpyAsync(out, c->misc.p, sizeof(double) * 3 * m, hipMemcpyDeviceToHost, c->stream));
   HIPC(c, hipStreamSynchronize(c->stream));
   return TLOAM_OK;

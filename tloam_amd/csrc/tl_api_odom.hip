@@ -55,8 +55,11 @@ GatherJob soa_rows(const double* sx, const double* sy, const double* sz, int n, 
 
 constexpr size_t kMinCloud = 10;   // registration.cpp:928-929
 
+int odometry_frame_impl(tloam_ctx* c, const double* xyz, const double* t_sec, size_t n, double pose_out[16],
+                        tloam_odom_stats* stats);
+
 // the frame after the reset is known; everything up to the scan match.  Returns the status; the sizes go to *st
-int odometry_frame_body(tloam_ctx* c, const double* xyz, size_t n, double pose[16], tloam_odom_stats* st) {
+int odometry_frame_body(tloam_ctx* c, const double* xyz, const double* t_sec, size_t n, double pose[16], tloam_odom_stats* st) {
   OdomState& O = c->odom;
   const tloam_odom_config& cfg = O.cfg;
   SegBuffers& S = c->seg;
@@ -76,14 +79,25 @@ int odometry_frame_body(tloam_ctx* c, const double* xyz, size_t n, double pose[1
   if (rc != TLOAM_OK) return rc;
   HIPC(c, hipMemcpyAsync(S.aos.p, xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice, c->stream));
   st->h2d_bytes += (int64_t)(sizeof(double) * 3 * n);
-  rc = segment_launch(c, P);
+  rc = deskew_frame_upload(c, t_sec, n, st);   // (deskew on: the times, timed mode; tl_api_deskew.hip)
+  if (rc != TLOAM_OK) return rc;
+  rc = segment_launch(c, P);   // on the raw scan: its ring recovery and gates follow the firing geometry
+  if (rc != TLOAM_OK) return rc;
+  // ---- deskew (on, with motion): the corrected copy every later stage of the frame reads (frame_scan)
+  unsigned long long bad_time = 0;
+  rc = deskew_frame_launch(c, n, &bad_time, st);
   if (rc != TLOAM_OK) return rc;
   SegCtl ctl;
   HIPC(c, hipMemcpyAsync(&ctl, S.ctl.p, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));   // wait 1: the sizes of the segmentation's lists
+  HIPC(c, hipStreamSynchronize(c->stream));   // wait 1: the sizes of the segmentation's lists (and the deskew's time check)
   st->d2h_bytes += (int64_t)sizeof(ctl);
   st->host_syncs++;
+  if (bad_time) {
+    c->last_error = "tloam_odometry_frame_timed: a time is not finite or more than two sweeps from the pose's instant";
+    return TLOAM_E_INVALID;
+  }
   if (ctl.invalid) return TLOAM_E_INVALID;
+  const double* scan = frame_scan(c);
   if (ctl.n_obj <= 0 || ctl.n_clusters <= 0) return TLOAM_E_TOO_FEW_POINTS;   // the node publishes nothing
   const size_t ng = (size_t)ctl.n_ground, ne = (size_t)ctl.n_edge, nge = (size_t)ctl.n_general;
   st->n_ground = (int64_t)ng; st->n_edge = (int64_t)ne; st->n_general = (int64_t)nge;
@@ -99,9 +113,9 @@ int odometry_frame_body(tloam_ctx* c, const double* xyz, size_t n, double pose[1
   {
     GatherArgs G;
     memset(&G, 0, sizeof(G));
-    G.j[0] = aos_rows(S.aos.p, (int)n, F.aos.p, (int)nge, S.general.p, (int)nge, nullptr, &S.ctl.p->n_general);
-    G.j[1] = aos_rows(S.aos.p, (int)n, M.wx.p, (int)ne, S.edge.p, (int)ne, nullptr, &S.ctl.p->n_edge);
-    G.j[2] = aos_rows(S.aos.p, (int)n, M.wx.p + ne, (int)ng, S.ground.p, (int)ng, nullptr, &S.ctl.p->n_ground);
+    G.j[0] = aos_rows(scan, (int)n, F.aos.p, (int)nge, S.general.p, (int)nge, nullptr, &S.ctl.p->n_general);
+    G.j[1] = aos_rows(scan, (int)n, M.wx.p, (int)ne, S.edge.p, (int)ne, nullptr, &S.ctl.p->n_edge);
+    G.j[2] = aos_rows(scan, (int)n, M.wx.p + ne, (int)ng, S.ground.p, (int)ng, nullptr, &S.ctl.p->n_ground);
     for (int j = 1; j < 3; ++j) {   // the voxel job's input: SoA, edge then ground back to back
       const size_t base = j == 1 ? 0 : ne;
       G.j[j].dy = M.wy.p + base; G.j[j].dz = M.wz.p + base; G.j[j].ds = 1;
@@ -156,10 +170,10 @@ int odometry_frame_body(tloam_ctx* c, const double* xyz, size_t n, double pose[1
     HIPC(c, O.block.reserve(total + 2));
     GatherArgs G;
     memset(&G, 0, sizeof(G));
-    G.j[0] = aos_rows(S.aos.p, (int)n, O.block.p + off[0], (int)np, pidx, (int)nge, S.general.p);
-    G.j[1] = aos_rows(S.aos.p, (int)n, O.block.p + off[1], (int)ns, nullptr, (int)nge, S.general.p);   // ranks (:188)
-    G.j[2] = aos_rows(S.aos.p, (int)n, O.block.p + off[2], (int)ne, S.edge.p, (int)ne, nullptr);
-    G.j[3] = aos_rows(S.aos.p, (int)n, O.block.p + off[3], (int)ng, S.ground.p, (int)ng, nullptr);
+    G.j[0] = aos_rows(scan, (int)n, O.block.p + off[0], (int)np, pidx, (int)nge, S.general.p);
+    G.j[1] = aos_rows(scan, (int)n, O.block.p + off[1], (int)ns, nullptr, (int)nge, S.general.p);   // ranks (:188)
+    G.j[2] = aos_rows(scan, (int)n, O.block.p + off[2], (int)ne, S.edge.p, (int)ne, nullptr);
+    G.j[3] = aos_rows(scan, (int)n, O.block.p + off[3], (int)ng, S.ground.p, (int)ng, nullptr);
     launch_gather_lists(G, 4, c->stream);
     rc = submap_init_body(c, cfg.submap, O.block.p + off[0], np, O.block.p + off[1], ns, O.block.p + off[2], ne,
                           O.block.p + off[3], ng, hipMemcpyDeviceToDevice);
@@ -195,11 +209,11 @@ int odometry_frame_body(tloam_ctx* c, const double* xyz, size_t n, double pose[1
     GatherArgs G;
     memset(&G, 0, sizeof(G));
     double* sp = c->src_pack.p;
-    G.j[0] = aos_rows(S.aos.p, (int)n, sp + soff[TLOAM_KIND_PLANAR], (int)nps, pidx, (int)nge, S.general.p);
+    G.j[0] = aos_rows(scan, (int)n, sp + soff[TLOAM_KIND_PLANAR], (int)nps, pidx, (int)nge, S.general.p);
     G.j[1] = soa_rows(vox_ground, vox_ground + ng, vox_ground + 2 * ng, (int)ng_ds, sp + soff[TLOAM_KIND_GROUND]);
     G.j[2] = soa_rows(vox_edge, vox_edge + ne, vox_edge + 2 * ne, (int)ne_ds, sp + soff[TLOAM_KIND_EDGE]);
-    G.j[3] = aos_rows(S.aos.p, (int)n, sp + soff[TLOAM_KIND_SPHERE], (int)nss, nullptr, (int)nge, S.general.p);   // ranks (:186)
-    G.j[4] = aos_rows(S.aos.p, (int)n, O.block.p + roff[0], (int)np, pidx, (int)nge, S.general.p);
+    G.j[3] = aos_rows(scan, (int)n, sp + soff[TLOAM_KIND_SPHERE], (int)nss, nullptr, (int)nge, S.general.p);   // ranks (:186)
+    G.j[4] = aos_rows(scan, (int)n, O.block.p + roff[0], (int)np, pidx, (int)nge, S.general.p);
     G.j[5] = soa_rows(vox_edge, vox_edge + ne, vox_edge + 2 * ne, (int)ne_ds, O.block.p + roff[1]);
     G.j[6] = soa_rows(vox_ground, vox_ground + ng, vox_ground + 2 * ng, (int)ng_ds, O.block.p + roff[2]);
     launch_gather_lists(G, 7, c->stream);
@@ -256,16 +270,35 @@ int tloam_odometry_reset(tloam_ctx* c, const tloam_odom_config* cfg, const doubl
   O.cfg = want;
   memcpy(O.last, T, sizeof(T));      // last_pose = init_pose (:281)
   memcpy(O.predict, T, sizeof(T));   // predicate_pose = init_pose (:282)
+  for (int i = 0; i < 16; ++i) O.step[i] = (i % 5 == 0) ? 1.0 : 0.0;   // no motion before the second frame is accepted
   O.frame = 0;
   O.ready = true;
   O.reg_valid = false;   // no registered scan before the first frame
   map_empty(c);          // the global map starts again; its configuration stays
   vmap_empty(c);         // the merged voxel map too
+  c->deskew.clear_info(); // (its configuration stays too)
   return TLOAM_OK;
 }
 
 int tloam_odometry_frame(tloam_ctx* c, const double* xyz, size_t n, double pose_out[16], tloam_odom_stats* stats) {
   if (stats) memset(stats, 0, sizeof(*stats));
+  if (c && c->deskew.cfg.enabled && c->deskew.cfg.time_source == 1) return TLOAM_E_INVALID;   // timed mode takes times
+  return odometry_frame_impl(c, xyz, nullptr, n, pose_out, stats);
+}
+
+int tloam_odometry_frame_timed(tloam_ctx* c, const double* xyz, const double* t_sec, size_t n, double pose_out[16],
+                               tloam_odom_stats* stats) {
+  if (stats) memset(stats, 0, sizeof(*stats));
+  if (!c || !t_sec || !c->deskew.cfg.enabled || c->deskew.cfg.time_source != 1) return TLOAM_E_INVALID;
+  return odometry_frame_impl(c, xyz, t_sec, n, pose_out, stats);
+}
+
+}  // extern "C"
+
+namespace {
+
+int odometry_frame_impl(tloam_ctx* c, const double* xyz, const double* t_sec, size_t n, double pose_out[16],
+                        tloam_odom_stats* stats) {
   if (!c || !pose_out || (n > 0 && !xyz) || n > kMaxPoints || n > (size_t)INT32_MAX / 3) return TLOAM_E_INVALID;
   if (c->nranks > 1) return TLOAM_E_INVALID;   // multi-rank frames: not offered (the match would need every rank's clouds)
   if (!c->odom.ready) return TLOAM_E_NOT_READY;
@@ -276,24 +309,27 @@ int tloam_odometry_frame(tloam_ctx* c, const double* xyz, size_t n, double pose_
   memset(&st, 0, sizeof(st));
   st.frame = O.frame;
   double T[16];
-  const int rc = odometry_frame_body(c, xyz, n, T, &st);
+  const int rc = odometry_frame_body(c, xyz, t_sec, n, T, &st);
   (void)hipStreamSynchronize(c->stream);   // (a failed stage may have left work in flight; the success paths have drained)
   const bool accepted = rc == TLOAM_OK || rc == TLOAM_E_WEIGHT_RANGE;
   map_frame_end(c, accepted);
   vmap_frame_end(c, accepted);
+  const bool deskewed = c->deskew.active;
+  deskew_frame_end(c, accepted, O.frame);
   if (accepted) {
     // spinOnce's /raw_cloud (:84-86): this scan by lidar_odom_pose -- still Identity on the first frame (front_end.hpp:106),
     // whatever the init pose
     O.reg_valid = true;
     O.reg_seq = c->seg.aos_seq;
     O.reg_n = n;
+    O.reg_deskewed = deskewed;
     if (O.frame > 0) memcpy(O.reg_pose, T, sizeof(T));
     else for (int i = 0; i < 16; ++i) O.reg_pose[i] = (i % 5 == 0) ? 1.0 : 0.0;
     if (O.frame > 0) {   // step_pose = last_pose^-1 * lidar_odom_pose; predicate_pose = lidar_odom_pose * step_pose (:329-332)
-      double inv[16], step[16];
+      double inv[16];
       rigid_inverse(O.last, inv);
-      mat_mul(inv, T, step);
-      mat_mul(T, step, O.predict);
+      mat_mul(inv, T, O.step);   // (kept: the next frame's deskew motion)
+      mat_mul(T, O.step, O.predict);
       memcpy(O.last, T, sizeof(T));
     }
     O.frame++;
@@ -303,4 +339,4 @@ int tloam_odometry_frame(tloam_ctx* c, const double* xyz, size_t n, double pose_
   return rc;
 }
 
-}  // extern "C"
+}  // namespace

@@ -158,7 +158,7 @@ int vmap_stage_launch(tloam_ctx* c, const double pose[16], size_t n) {
   VmapStageWork W = stage_work(c);
   const MapState& M = c->map;
   if (M.cfg.enabled) { W.sx = M.wx.p; W.sy = M.wy.p; W.sz = M.wz.p; }   // (map_stage_launch has just written them)
-  W.aos = c->seg.aos.p;
+  W.aos = frame_scan(c);   // (the deskewed copy when the frame corrected its scan)
   for (int k = 0; k < 16; ++k) W.M[k] = pose[k];
   W.n = n;
   W.host_seg = V.h_seg_dev;

@@ -623,6 +623,20 @@ void launch_vmap_rehash(const VmapTable& T, size_t n, hipStream_t s);
 void launch_vmap_read(const VmapReadArgs& A, hipStream_t s);
 void launch_vmap_read_box(const VmapReadArgs& A, hipStream_t s);
 
+// ---- deskew of a scan under constant velocity (tl_deskew.hip) -------------
+struct DeskewArgs {
+  const double* in;               // AoS xyz [3n]
+  const double* t;                // timed mode: seconds relative to the pose's instant [n]; null: azimuth mode
+  double* out;                    // AoS [3n]; null: the times are checked and nothing is written
+  unsigned long long* max_shift;  // bits of max |p' - p| (atomic max; zero before the launch); null: not reduced
+  unsigned long long* bad;        // set to 1 when a time is refused (zero before the launch); null in azimuth mode
+  long long n;
+  double xi[6];                   // the frame's motion log(step): (upsilon, omega)
+  double period;                  // timed: s = t / period
+  double direction, start, ref;   // azimuth: s = wrap_[0,2pi)(direction * (atan2(y, x) - start)) / 2pi - ref
+};
+void launch_deskew(const DeskewArgs& A, hipStream_t s);
+
 // ---- PCA feature extraction (tl_feature.hip; feature_extract.cpp:47-197) -----------------------
 struct FeatArgs {
   GridView g;                 // grid over the cloud itself (cell >= radius)

@@ -172,6 +172,7 @@ struct OdomState {
   bool ready = false;              // tloam_odometry_reset has been called
   tloam_odom_config cfg;
   double last[16], predict[16];    // FrontEnd::last_pose / predicate_pose (front_end.cpp:281-282, :329-332), column-major
+  double step[16];                 // step_pose of the last accepted later frame (identity before): the deskew's motion
   long long frame = 0;             // frames accepted since the reset
   DBuf<double> vox_out;            // SoA output of the per-scan voxel job (edge x, y, z, then ground x, y, z) / tloam_voxel_down_sample
   DBuf<double> block;              // planar | edge | ground of the submap update (swapped into the planar ring), or the first
@@ -183,6 +184,7 @@ struct OdomState {
   unsigned long long reg_seq = 0;
   size_t reg_n = 0;
   double reg_pose[16];
+  bool reg_deskewed = false;       // its scan is the deskewed copy (DeskewState::aos), not the segmentation's input
   void release() { vox_out.release(); block.release(); ctl.release(); ready = false; reg_valid = false; }
 };
 
@@ -253,6 +255,29 @@ struct VmapState {
   }
 };
 
+// the odometry frame's deskew (tl_api_deskew.hip): its configuration, the frame's corrected copy of the scan
+// and its times, two max-shift words (the frame in flight writes the one the last accepted deskewed frame did not), the flag of a
+// refused time; tloam_deskew_scan's own buffers
+struct DeskewState {
+  tloam_deskew_config cfg = {0, 0, 1, 0, 0.0, 0.0};   // tloam_deskew_default_config until tloam_deskew_configure
+  DBuf<double> aos, t;
+  DBuf<unsigned long long> ctl;    // [0], [1] max |p' - p| bits, [2] bad-time flag
+  DBuf<double> s_in, s_out, s_t;
+  DBuf<unsigned long long> s_ctl;
+  bool active = false;             // the frame in flight reads its scan from `aos`
+  bool timed = false;              // the frame in flight came with times
+  int slot = 0;                    // the max-shift word the frame in flight writes
+  int committed = -1;              // the one of the last accepted deskewed frame (-1: none)
+  double xi[6] = {0, 0, 0, 0, 0, 0};   // the frame in flight's motion
+  int64_t frames = 0, last_frame = -1;
+  double last_twist[6] = {0, 0, 0, 0, 0, 0};
+  void clear_info() { frames = 0; last_frame = -1; committed = -1; for (double& v : last_twist) v = 0.0; }
+  void release() {
+    aos.release(); t.release(); ctl.release(); s_in.release(); s_out.release(); s_t.release(); s_ctl.release();
+    clear_info();
+  }
+};
+
 // up to four SoA clouds (x, y, z, n) a search grid is built over -- the registered targets, or any other cloud
 struct CloudRef { const double *x, *y, *z; size_t n; };
 }  // namespace tlh
@@ -267,6 +292,7 @@ struct tloam_ctx {
   OdomState odom;
   MapState map;
   VmapState vmap;
+  DeskewState deskew;
   int device = 0;
   hipStream_t stream = nullptr;
   KindData kd[kKinds];
@@ -504,6 +530,13 @@ int vmap_stage_collect(tloam_ctx* c, tloam_odom_stats* st);
 void vmap_frame_end(tloam_ctx* c, bool accepted);
 void vmap_empty(tloam_ctx* c);
 void vmap_release(tloam_ctx* c);
+// tl_api_deskew.hip: the frame's deskew -- sized and its times uploaded after the scan's upload, launched after the segmentation's
+// (the refused-time flag read with the frame's first wait), committed when the frame ends
+int deskew_frame_upload(tloam_ctx* c, const double* t_sec, size_t n, tloam_odom_stats* st);
+int deskew_frame_launch(tloam_ctx* c, size_t n, unsigned long long* bad_host, tloam_odom_stats* st);
+void deskew_frame_end(tloam_ctx* c, bool accepted, int64_t frame);
+// the frame's scan as its stages after the segmentation read it: the deskewed copy when the frame corrected it
+inline const double* frame_scan(const tloam_ctx* c) { return c->deskew.active ? c->deskew.aos.p : c->seg.aos.p; }
 int voxel_down_sample_launch(tloam_ctx* c, const size_t n[2], const double voxel[2], int nseg, double* const out[2][3]);
 int build_grids_over(tloam_ctx* c, GridBuffers& G, const double radius[tl::kKinds], const CloudRef clouds[tl::kKinds],
                      tl::GridView out[tl::kKinds], const double (*known_boxes)[6] = nullptr,

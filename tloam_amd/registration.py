@@ -92,6 +92,24 @@ class VoxelMapInfo(C.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
+class DeskewConfig(C.Structure):
+    """tloam_deskew_config: the deskew's switch, its time source (0 azimuth, 1 per-point times), the sweep's direction (+1
+    counter-clockwise seen from +z), the azimuth it starts at and the sweep fraction the pose describes."""
+    _fields_ = [("enabled", C.c_int32), ("time_source", C.c_int32), ("direction", C.c_int32), ("reserved0", C.c_int32),
+                ("start_azimuth", C.c_double), ("ref_fraction", C.c_double)]
+
+
+class DeskewInfo(C.Structure):
+    """tloam_deskew_info."""
+    _fields_ = [("frames_deskewed", C.c_int64), ("last_frame", C.c_int64), ("last_twist", C.c_double * 6),
+                ("last_max_shift", C.c_double), ("next_motion_colmajor", C.c_double * 16)]
+
+    def as_dict(self):
+        return {"frames_deskewed": int(self.frames_deskewed), "last_frame": int(self.last_frame),
+                "last_twist": np.array(self.last_twist[:]), "last_max_shift": float(self.last_max_shift),
+                "next_motion": np.array(self.next_motion_colmajor[:]).reshape(4, 4).T.copy()}
+
+
 class TlsConfig(C.Structure):
     """tloam_tls_config: the 16 keys of the `TLS:` block (config/mapping/lidar_odometry.yaml:23-39)."""
     _fields_ = [
@@ -237,6 +255,11 @@ def load_library():
         "tloam_voxel_map_get_info": (C.c_int, [vp, C.POINTER(VoxelMapInfo)]),
         "tloam_voxel_map_read": (C.c_int, [vp, sz, sz, dp, C.POINTER(C.c_int64)]),
         "tloam_voxel_map_read_box": (C.c_int, [vp, dp, dp, C.c_int64, sz, C.POINTER(sz), dp, C.POINTER(C.c_int64)]),
+        "tloam_deskew_default_config": (None, [C.POINTER(DeskewConfig)]),
+        "tloam_deskew_configure": (C.c_int, [vp, C.POINTER(DeskewConfig)]),
+        "tloam_deskew_get_info": (C.c_int, [vp, C.POINTER(DeskewInfo)]),
+        "tloam_odometry_frame_timed": (C.c_int, [vp, dp, dp, sz, dp, C.POINTER(OdomStats)]),
+        "tloam_deskew_scan": (C.c_int, [vp, C.POINTER(DeskewConfig), C.c_double, dp, dp, dp, sz, dp]),
         "tloam_rccl_unique_id": (C.c_int, [vp]),
         "tloam_comm_init_rccl": (C.c_int, [vp, C.c_int, C.c_int, vp]),
         "tloam_comm_init_callback": (C.c_int, [vp, C.c_int, C.c_int, ALLREDUCE_FN, vp]),
@@ -268,7 +291,8 @@ EXPORTED_SYMBOLS = (
     "tloam_seg_default_config", "tloam_segment", "tloam_voxel_down_sample", "tloam_odom_default_config",
     "tloam_odometry_reset", "tloam_odometry_frame", "tloam_map_default_config", "tloam_map_configure", "tloam_map_get_info",
     "tloam_map_read", "tloam_registered_scan", "tloam_voxel_map_default_config", "tloam_voxel_map_configure",
-    "tloam_voxel_map_get_info", "tloam_voxel_map_read", "tloam_voxel_map_read_box", "tloam_rccl_unique_id", "tloam_comm_init_rccl",
+    "tloam_voxel_map_get_info", "tloam_voxel_map_read", "tloam_voxel_map_read_box", "tloam_deskew_default_config",
+    "tloam_deskew_configure", "tloam_deskew_get_info", "tloam_odometry_frame_timed", "tloam_deskew_scan", "tloam_rccl_unique_id", "tloam_comm_init_rccl",
     "tloam_comm_mailbox_export", "tloam_comm_init_mailbox",
     "tloam_comm_init_callback", "tloam_shard_range", "tloam_shard_ranges_frame", "tloam_se3_exp", "tloam_se3_log", "tloam_se3_plus",
 )
@@ -570,15 +594,22 @@ class HipRegistration:
         self._check(self.L.tloam_odometry_reset(self.h, C.byref(cfg) if cfg is not None else None, _dp(T)),
                     "tloam_odometry_reset")
 
-    def odometry_frame(self, xyz):
+    def odometry_frame(self, xyz, times=None):
         """one raw scan -> (rc, pose 4x4, stats dict).  rc: 0, -2 (TLOAM_E_TOO_FEW_POINTS: the frame is skipped) or
-        -7 (TLOAM_E_WEIGHT_RANGE: pose written, as scan_match); raises on any other status."""
+        -7 (TLOAM_E_WEIGHT_RANGE: pose written, as scan_match); raises on any other status.  times: per-point seconds relative
+        to the pose's instant -- tloam_odometry_frame_timed (deskew configured with time_source 1)."""
         a = _aos(xyz)
         T = np.zeros(16)
         st = OdomStats()
-        rc = self.L.tloam_odometry_frame(self.h, _dp(a), len(a), _dp(T), C.byref(st))
+        if times is None:
+            rc = self.L.tloam_odometry_frame(self.h, _dp(a), len(a), _dp(T), C.byref(st))
+        else:
+            t = np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
+            if len(t) != len(a):
+                raise ValueError(f"{len(t)} times for {len(a)} points")
+            rc = self.L.tloam_odometry_frame_timed(self.h, _dp(a), _dp(t), len(a), _dp(T), C.byref(st))
         if rc not in (0, -2, -7):
-            self._check(rc, "tloam_odometry_frame")
+            self._check(rc, "tloam_odometry_frame_timed" if times is not None else "tloam_odometry_frame")
         if rc != -2 and st.frame > 0:   # the getters' capacities: this frame's source clouds, in kind order
             for k, m in enumerate((st.n_planar_scan, st.n_ground_ds, st.n_edge_ds, st.n_sphere_scan)):
                 self._n[("s", k)] = int(m)
@@ -648,6 +679,31 @@ class HipRegistration:
             self._check(self.L.tloam_voxel_map_read_box(self.h, _dp(lo), _dp(hi), int(min_count), m, C.byref(n), _dp(cen),
                                                         _lp(cnt)), "tloam_voxel_map_read_box")
         return cen[: n.value].copy(), cnt[: n.value].copy()
+
+    # ---- deskew of the frame's scan under constant velocity
+    def deskew_configure(self, cfg: DeskewConfig | None = None, **over):
+        """deskew on / off (default_deskew_config(**over) when cfg is None).  Kept across odometry_reset."""
+        cfg = cfg if cfg is not None else default_deskew_config(**over)
+        self._check(self.L.tloam_deskew_configure(self.h, C.byref(cfg)), "tloam_deskew_configure")
+
+    def deskew_info(self) -> dict:
+        info = DeskewInfo()
+        self._check(self.L.tloam_deskew_get_info(self.h, C.byref(info)), "tloam_deskew_get_info")
+        return info.as_dict()
+
+    def deskew_scan(self, xyz, motion, cfg: DeskewConfig | None = None, scan_period=0.1, times=None):
+        """the correction alone, on the device: (n, 3) scan, motion = the step (4x4 rigid), times in seconds (timed mode) ->
+        the deskewed (n, 3) scan"""
+        cfg = cfg if cfg is not None else default_deskew_config(enabled=1, time_source=0 if times is None else 1)
+        a = _aos(xyz)
+        t = None if times is None else np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
+        if t is not None and len(t) != len(a):
+            raise ValueError(f"{len(t)} times for {len(a)} points")
+        out = np.zeros((max(len(a), 1), 3))
+        M = _colmajor(motion)
+        self._check(self.L.tloam_deskew_scan(self.h, C.byref(cfg), float(scan_period), _dp(M), _dp(a), _dp(t), len(a),
+                                             _dp(out)), "tloam_deskew_scan")
+        return out[: len(a)].copy()
 
     def fitness(self):
         f, r = C.c_double(0), C.c_double(0)
@@ -869,6 +925,17 @@ def default_voxel_map_config(**over) -> VoxelMapConfig:
             raise KeyError(k)
         if k == "origin":
             v = (C.c_double * 3)(*[float(x) for x in v])
+        setattr(cfg, k, v)
+    return cfg
+
+
+def default_deskew_config(**over) -> DeskewConfig:
+    """tloam_deskew_default_config (off, azimuth mode, counter-clockwise, start 0, ref 0) with keyword overrides"""
+    cfg = DeskewConfig()
+    load_library().tloam_deskew_default_config(C.byref(cfg))
+    for k, v in over.items():
+        if not hasattr(cfg, k):
+            raise KeyError(k)
         setattr(cfg, k, v)
     return cfg
 

@@ -125,13 +125,19 @@ def _read_scan(path):
 
 
 def replay_device(H, scan_files, out_poses: str | None = None, odom_cfg=None, init_pose=None, max_frames=None,
-                  map_cfg=None, out_map: str | None = None):
+                  map_cfg=None, out_map: str | None = None, deskew_cfg=None):
     """pipeline="device": one tloam_odometry_frame per scan.  Frames the device skips
     (TLOAM_E_TOO_FEW_POINTS) are left out of the poses and listed in the stats as `skipped` (their positions in
     `scan_files`); `frame_of_pose` gives each pose's position.
     map_cfg (a MapConfig): the global map is configured with it before the run; the stats get its
-    `map` info, and out_map names a PCD file the map is written to (tloam_amd/map_io.py)."""
+    `map` info, and out_map names a PCD file the map is written to (tloam_amd/map_io.py).
+    deskew_cfg (a DeskewConfig, azimuth mode: `.bin` scans carry no per-point times): the frames deskew their scans under the
+    constant-velocity motion; the stats get its `deskew` info."""
     files = scan_files[: max_frames] if max_frames else scan_files
+    if deskew_cfg is not None:
+        if deskew_cfg.enabled and deskew_cfg.time_source != 0:
+            raise ValueError("replay_device deskews in azimuth mode only (time_source 0): scan files carry no times")
+        H.deskew_configure(deskew_cfg)
     if map_cfg is not None:
         H.map_configure(map_cfg)
     H.odometry_reset(init_pose, odom_cfg)
@@ -161,6 +167,9 @@ def replay_device(H, scan_files, out_poses: str | None = None, odom_cfg=None, in
     m = lambda v: round(float(np.mean(v)), 4) if v else None  # noqa: E731
     stats = {"frames": len(poses), "skipped": skipped, "frame_of_pose": at, "ms_odometry_frame": m(t_frame),
              "gn_iters_per_frame": round(iters / max(len(poses) - 1, 1), 2)}
+    if deskew_cfg is not None:
+        info = H.deskew_info()
+        stats["deskew"] = {"frames_deskewed": info["frames_deskewed"], "last_max_shift": info["last_max_shift"]}
     if map_cfg is not None:
         stats["map"] = H.map_info()
         if out_map:
