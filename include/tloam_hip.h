@@ -596,6 +596,70 @@ int tloam_deskew_scan(tloam_ctx* ctx, const tloam_deskew_config* cfg, double sca
                       const double* xyz_aos, const double* t_sec, size_t n, double* out_aos);
 /* Every deskew call on a context with nranks > 1: TLOAM_E_INVALID. */
 
+/* ---- place recognition: Scan Context keyframes and loop search on the device (additive to ABI 8) ----
+ * Off by default; when off, every frame, stat, map and launch is what it is without it.  With it on, an accepted odometry frame
+ * is a keyframe when it is the first since the reset / configure, or when its returned pose has moved >= kf_dist or turned
+ * >= kf_angle (the angle of the relative rotation) from the last keyframe's pose.  A keyframe stores the Scan Context
+ * descriptor of the scan the frame used (the deskewed copy when deskew corrected it), both keys, the pose and the frame number
+ * (tloam_odom_stats.frame), and is searched against keyframes 0 .. q - exclude_recent: the num_candidates nearest ring keys,
+ * then every column shift of each; the best pair (min d, ties to the lower shift, then the lower keyframe) with d < dist_thres
+ * is a loop record.  Descriptor: n_rings x n_sectors fp64, row-major by ring; bin = max(z + height_offset) over the finite
+ * returns with 0 < r < max_radius (r = sqrt(x*x + y*y)), ring = floor(r / (max_radius / n_rings)), sector =
+ * floor((atan2(y, x) + pi) / (2 pi / n_sectors)), both clamped; an empty bin is 0.0.  The frame's work is enqueued after its
+ * last wait and not waited for: host_syncs and d2h_bytes do not change.  DESIGN.md 16. */
+typedef struct tloam_place_config {
+  int32_t enabled;           /* 0 */
+  int32_t n_rings;           /* 20, in [1, 64] */
+  int32_t n_sectors;         /* 60, in [2, 360] */
+  int32_t num_candidates;    /* 10, in [1, 32] */
+  int32_t exclude_recent;    /* 50, >= 1: keyframe q is searched against 0 .. q - exclude_recent */
+  int32_t reserved0;
+  double max_radius;         /* m: 80 */
+  double height_offset;      /* m: 2.0, added to z (finite) */
+  double kf_dist;            /* m: 1.0 */
+  double kf_angle;           /* rad: 0.2 */
+  double dist_thres;         /* 0.30 (measured): a loop when the best d is below it */
+  int64_t reserve_keyframes; /* 0: the default room (1024); the database doubles when full */
+} tloam_place_config;
+void tloam_place_default_config(tloam_place_config* cfg);
+/* cfg NULL: the defaults.  Empties the database (so does tloam_odometry_reset; the configuration persists across it).
+ * Non-finite or non-positive max_radius / kf_dist / kf_angle / dist_thres, a non-finite height_offset, a count out of its
+ * range, enabled not 0 / 1, reserve_keyframes < 0: TLOAM_E_INVALID. */
+int tloam_place_configure(tloam_ctx* ctx, const tloam_place_config* cfg);
+
+typedef struct tloam_place_info {
+  int64_t n_keyframes;
+  int64_t n_loops;           /* read from the device: this call waits for the work in flight */
+  int64_t last_keyframe_frame; /* the frame number of the last keyframe, -1 none */
+  int64_t capacity_keyframes;
+} tloam_place_info;
+int tloam_place_get_info(tloam_ctx* ctx, tloam_place_info* info);
+
+typedef struct tloam_place_loop {
+  int64_t query_keyframe, query_frame;
+  int64_t match_keyframe, match_frame;
+  int32_t shift;             /* the candidate's column (j + shift) mod n_sectors matches the query's column j */
+  int32_t reserved0;
+  double dist;               /* d of the pair */
+  double yaw;                /* shift * 2 pi / n_sectors wrapped to (-pi, pi]: the query's heading relative to the match's */
+} tloam_place_loop;
+
+/* Keyframes [first, first + count): frame numbers [count], poses [16 count] column-major, ring keys [n_rings count], sector keys
+ * [n_sectors count], descriptors [n_rings n_sectors count].  Any output may be NULL.  Out of range: TLOAM_E_INVALID. */
+int tloam_place_read_keyframes(tloam_ctx* ctx, size_t first, size_t count, int64_t* frames, double* poses_colmajor,
+                               double* ring_keys, double* sector_keys, double* descriptors);
+/* Loop records [first, first + count) in the order they were found; the range is checked against n_loops. */
+int tloam_place_read_loops(tloam_ctx* ctx, size_t first, size_t count, tloam_place_loop* loops);
+/* One scan (AoS, sensor frame) with a pose the caller supplies: described, added as a keyframe whatever the keyframe policy
+ * says, and searched, as a frame's keyframe is.  Place recognition must be enabled.  keyframe_out (may be NULL): its id. */
+int tloam_place_add_scan(tloam_ctx* ctx, const double* xyz_aos, size_t n, const double pose_colmajor[16], int64_t frame_id,
+                         int64_t* keyframe_out);
+/* The descriptor [n_rings n_sectors] and keys of one scan under cfg (NULL: the context's configuration; cfg->enabled is not
+ * looked at).  The database is not touched.  Any output may be NULL. */
+int tloam_place_describe(tloam_ctx* ctx, const tloam_place_config* cfg, const double* xyz_aos, size_t n, double* descriptor,
+                         double* ring_key, double* sector_key);
+/* Every place recognition call on a context with nranks > 1: TLOAM_E_INVALID. */
+
 /* ---- multi-GPU: correspondence set sharded over ranks, one all-reduce per sweep --------
  * (nothing in the reference).  Call before set_source / set_correspondences.
  * (a) native RCCL over xGMI: unique_id = the 128 bytes of an ncclUniqueId made on rank 0

@@ -146,6 +146,7 @@ void tloam_destroy(tloam_ctx* c) {
   tlh::map_release(c);
   tlh::vmap_release(c);
   c->deskew.release();
+  c->place.release();
   if (c->h_state) (void)hipHostFree(c->h_state);
   if (c->h_mirror) (void)hipHostFree(c->h_mirror);
   if (c->h_small) (void)hipHostFree(c->h_small);

@@ -72,6 +72,8 @@ int odometry_frame_body(tloam_ctx* c, const double* xyz, const double* t_sec, si
   if (rc != TLOAM_OK) return rc;
   rc = first ? TLOAM_OK : vmap_frame_reserve(c, n);   // (the merged voxel map, likewise: tl_api_vmap.hip)
   if (rc != TLOAM_OK) return rc;
+  rc = place_frame_reserve(c, n);   // (place recognition: room for one more keyframe, any frame; tl_api_place.hip)
+  if (rc != TLOAM_OK) return rc;
 
   // ---- Segmentation::spinOnce on the raw scan: the one upload of the frame
   SegParams P;
@@ -276,6 +278,7 @@ int tloam_odometry_reset(tloam_ctx* c, const tloam_odom_config* cfg, const doubl
   O.reg_valid = false;   // no registered scan before the first frame
   map_empty(c);          // the global map starts again; its configuration stays
   vmap_empty(c);         // the merged voxel map too
+  place_empty(c);        // and the keyframe database (its configuration stays)
   c->deskew.clear_info(); // (its configuration stays too)
   return TLOAM_OK;
 }
@@ -314,6 +317,9 @@ int odometry_frame_impl(tloam_ctx* c, const double* xyz, const double* t_sec, si
   const bool accepted = rc == TLOAM_OK || rc == TLOAM_E_WEIGHT_RANGE;
   map_frame_end(c, accepted);
   vmap_frame_end(c, accepted);
+  // place recognition: an accepted keyframe described from the scan the frame used, committed and searched -- enqueued after the
+  // frame's last wait, not waited for (tl_api_place.hip)
+  place_frame_end(c, accepted, O.frame, T, frame_scan(c), n);
   const bool deskewed = c->deskew.active;
   deskew_frame_end(c, accepted, O.frame);
   if (accepted) {

@@ -637,6 +637,42 @@ struct DeskewArgs {
 };
 void launch_deskew(const DeskewArgs& A, hipStream_t s);
 
+// ---- place recognition: Scan Context descriptors and the keyframe search (tl_place.hip) ----------
+constexpr int kPlaceMaxRings = 64, kPlaceMaxSectors = 360, kPlaceMaxCandidates = 32;
+struct PlaceDescArgs {
+  const double* aos;              // AoS xyz [3n], sensor frame
+  long long n;
+  unsigned long long* bins;       // [R S] order-preserving images of the bin maxima; all zero before (k_place_keys zeroes them after)
+  double* desc;                   // [R S] row-major by ring
+  double* ring_key;               // [R]
+  double* sector_key;             // [S]
+  long long* frame_out;           // commit (null: describe only): the keyframe's frame number and pose
+  double* pose_out;               // [16] column-major
+  long long frame;
+  double pose[16];
+  int R, S;
+  double max_radius, height_offset;
+};
+void launch_place_describe(const PlaceDescArgs& A, hipStream_t s);   // k_place_bin (n > 0), k_place_keys
+
+struct PlaceCandidate { double d; int shift; int keyframe; };
+struct PlaceSearchArgs {
+  const double* desc;             // the database [K][R S], ring keys [K][R], frame numbers [K]
+  const double* ring_key;
+  const long long* frames;
+  double* kdist;                  // scratch [m]
+  int* taken;                     // scratch [m]
+  PlaceCandidate* cand;           // scratch [num_candidates]
+  tloam_place_loop* loops;        // the loop records [K]
+  unsigned long long* n_loops;    // their count
+  int q;                          // the query keyframe
+  int m;                          // keyframes 0 .. m-1 are searched (m >= 1)
+  int ncand;                      // min(num_candidates, m)
+  int R, S;
+  double dist_thres;
+};
+void launch_place_search(const PlaceSearchArgs& A, hipStream_t s);   // k_place_rank, k_place_shift, k_place_pick
+
 // ---- PCA feature extraction (tl_feature.hip; feature_extract.cpp:47-197) -----------------------
 struct FeatArgs {
   GridView g;                 // grid over the cloud itself (cell >= radius)

@@ -2,7 +2,7 @@
 // lifetime, tl_api_frames.hip: HBM residency + search grids, tl_api_match.hip: the scanMatching driver, tl_api_comm.hip: multi-GPU
 // exchange, tl_api_submap.hip: device-resident submap, tl_api_feature.hip: PCA features, tl_api_seg.hip: segmentation,
 // tl_api_odom.hip: the whole odometry frame, tl_api_map.hip: its global map and registered scan, tl_api_vmap.hip: its merged
-// voxel map).
+// voxel map, tl_api_deskew.hip: its deskew, tl_api_place.hip: place recognition).
 #pragma once
 
 #include <dlfcn.h>
@@ -278,6 +278,40 @@ struct DeskewState {
   }
 };
 
+// place recognition (tl_api_place.hip): its configuration, the keyframe database in HBM (per keyframe the
+// descriptor, both keys, the pose, the frame number; the loop records, at most one per keyframe, and their count), the search's
+// scratch, the bins of the descriptor in flight (zero between descriptors), the storage a growth replaced (freed when the frame has
+// drained the stream), and the buffers of tloam_place_add_scan / _describe
+struct PlaceState {
+  tloam_place_config cfg = {0, 20, 60, 10, 50, 0, 80.0, 2.0, 1.0, 0.2, 0.30, 0};   // tloam_place_default_config
+  DBuf<double> desc, rkey, skey, pose, kdist;
+  DBuf<long long> frame;
+  DBuf<int> taken;
+  DBuf<tloam_place_loop> loops;
+  DBuf<double> r_desc, r_rkey, r_skey, r_pose, r_kdist;   // retired by a growth
+  DBuf<long long> r_frame;
+  DBuf<int> r_taken;
+  DBuf<tloam_place_loop> r_loops;
+  DBuf<unsigned long long> bins, ctl;   // ctl[0]: the number of loop records
+  DBuf<PlaceCandidate> cand;
+  DBuf<double> s_aos, s_desc, s_rkey, s_skey;
+  size_t cap = 0;                  // keyframes the database holds
+  int64_t n_kf = 0;
+  int64_t last_kf_frame = -1;
+  double last_pose[16];            // the last keyframe's pose (n_kf > 0)
+  bool in_flight = false;          // a frame's place launches may still be reading its scan
+  void release_retired() {
+    r_desc.release(); r_rkey.release(); r_skey.release(); r_pose.release(); r_kdist.release(); r_frame.release();
+    r_taken.release(); r_loops.release();
+  }
+  void release() {
+    desc.release(); rkey.release(); skey.release(); pose.release(); kdist.release(); frame.release(); taken.release();
+    loops.release(); release_retired(); bins.release(); ctl.release(); cand.release();
+    s_aos.release(); s_desc.release(); s_rkey.release(); s_skey.release();
+    cap = 0; n_kf = 0; last_kf_frame = -1; in_flight = false;
+  }
+};
+
 // up to four SoA clouds (x, y, z, n) a search grid is built over -- the registered targets, or any other cloud
 struct CloudRef { const double *x, *y, *z; size_t n; };
 }  // namespace tlh
@@ -293,6 +327,7 @@ struct tloam_ctx {
   MapState map;
   VmapState vmap;
   DeskewState deskew;
+  PlaceState place;
   int device = 0;
   hipStream_t stream = nullptr;
   KindData kd[kKinds];
@@ -537,6 +572,11 @@ int deskew_frame_launch(tloam_ctx* c, size_t n, unsigned long long* bad_host, tl
 void deskew_frame_end(tloam_ctx* c, bool accepted, int64_t frame);
 // the frame's scan as its stages after the segmentation read it: the deskewed copy when the frame corrected it
 inline const double* frame_scan(const tloam_ctx* c) { return c->deskew.active ? c->deskew.aos.p : c->seg.aos.p; }
+// tl_api_place.hip: place recognition -- the database grown at the start of a frame; an accepted keyframe described, committed
+// and searched by launches enqueued after the frame's last wait
+int place_frame_reserve(tloam_ctx* c, size_t n);
+void place_frame_end(tloam_ctx* c, bool accepted, int64_t frame, const double pose[16], const double* scan, size_t n);
+void place_empty(tloam_ctx* c);
 int voxel_down_sample_launch(tloam_ctx* c, const size_t n[2], const double voxel[2], int nseg, double* const out[2][3]);
 int build_grids_over(tloam_ctx* c, GridBuffers& G, const double radius[tl::kKinds], const CloudRef clouds[tl::kKinds],
                      tl::GridView out[tl::kKinds], const double (*known_boxes)[6] = nullptr,

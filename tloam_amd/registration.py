@@ -110,6 +110,36 @@ class DeskewInfo(C.Structure):
                 "next_motion": np.array(self.next_motion_colmajor[:]).reshape(4, 4).T.copy()}
 
 
+class PlaceConfig(C.Structure):
+    """tloam_place_config: place recognition's switch, the Scan Context grid (rings x sectors within max_radius, z +
+    height_offset), the search (num_candidates ring-key neighbours older than exclude_recent keyframes, a loop below
+    dist_thres), the keyframe policy (kf_dist, kf_angle) and the HBM reserved."""
+    _fields_ = [("enabled", C.c_int32), ("n_rings", C.c_int32), ("n_sectors", C.c_int32), ("num_candidates", C.c_int32),
+                ("exclude_recent", C.c_int32), ("reserved0", C.c_int32), ("max_radius", C.c_double),
+                ("height_offset", C.c_double), ("kf_dist", C.c_double), ("kf_angle", C.c_double), ("dist_thres", C.c_double),
+                ("reserve_keyframes", C.c_int64)]
+
+
+class PlaceInfo(C.Structure):
+    """tloam_place_info."""
+    _fields_ = [("n_keyframes", C.c_int64), ("n_loops", C.c_int64), ("last_keyframe_frame", C.c_int64),
+                ("capacity_keyframes", C.c_int64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+class PlaceLoop(C.Structure):
+    """tloam_place_loop: one loop record."""
+    _fields_ = [("query_keyframe", C.c_int64), ("query_frame", C.c_int64), ("match_keyframe", C.c_int64),
+                ("match_frame", C.c_int64), ("shift", C.c_int32), ("reserved0", C.c_int32), ("dist", C.c_double),
+                ("yaw", C.c_double)]
+
+    def as_dict(self):
+        return {"query": int(self.query_keyframe), "query_frame": int(self.query_frame), "match": int(self.match_keyframe),
+                "match_frame": int(self.match_frame), "shift": int(self.shift), "d": float(self.dist), "yaw": float(self.yaw)}
+
+
 class TlsConfig(C.Structure):
     """tloam_tls_config: the 16 keys of the `TLS:` block (config/mapping/lidar_odometry.yaml:23-39)."""
     _fields_ = [
@@ -260,6 +290,13 @@ def load_library():
         "tloam_deskew_get_info": (C.c_int, [vp, C.POINTER(DeskewInfo)]),
         "tloam_odometry_frame_timed": (C.c_int, [vp, dp, dp, sz, dp, C.POINTER(OdomStats)]),
         "tloam_deskew_scan": (C.c_int, [vp, C.POINTER(DeskewConfig), C.c_double, dp, dp, dp, sz, dp]),
+        "tloam_place_default_config": (None, [C.POINTER(PlaceConfig)]),
+        "tloam_place_configure": (C.c_int, [vp, C.POINTER(PlaceConfig)]),
+        "tloam_place_get_info": (C.c_int, [vp, C.POINTER(PlaceInfo)]),
+        "tloam_place_read_keyframes": (C.c_int, [vp, sz, sz, C.POINTER(C.c_int64), dp, dp, dp, dp]),
+        "tloam_place_read_loops": (C.c_int, [vp, sz, sz, C.POINTER(PlaceLoop)]),
+        "tloam_place_add_scan": (C.c_int, [vp, dp, sz, dp, C.c_int64, C.POINTER(C.c_int64)]),
+        "tloam_place_describe": (C.c_int, [vp, C.POINTER(PlaceConfig), dp, sz, dp, dp, dp]),
         "tloam_rccl_unique_id": (C.c_int, [vp]),
         "tloam_comm_init_rccl": (C.c_int, [vp, C.c_int, C.c_int, vp]),
         "tloam_comm_init_callback": (C.c_int, [vp, C.c_int, C.c_int, ALLREDUCE_FN, vp]),
@@ -292,7 +329,9 @@ EXPORTED_SYMBOLS = (
     "tloam_odometry_reset", "tloam_odometry_frame", "tloam_map_default_config", "tloam_map_configure", "tloam_map_get_info",
     "tloam_map_read", "tloam_registered_scan", "tloam_voxel_map_default_config", "tloam_voxel_map_configure",
     "tloam_voxel_map_get_info", "tloam_voxel_map_read", "tloam_voxel_map_read_box", "tloam_deskew_default_config",
-    "tloam_deskew_configure", "tloam_deskew_get_info", "tloam_odometry_frame_timed", "tloam_deskew_scan", "tloam_rccl_unique_id", "tloam_comm_init_rccl",
+    "tloam_deskew_configure", "tloam_deskew_get_info", "tloam_odometry_frame_timed", "tloam_deskew_scan", "tloam_place_default_config",
+    "tloam_place_configure", "tloam_place_get_info", "tloam_place_read_keyframes", "tloam_place_read_loops", "tloam_place_add_scan",
+    "tloam_place_describe", "tloam_rccl_unique_id", "tloam_comm_init_rccl",
     "tloam_comm_mailbox_export", "tloam_comm_init_mailbox",
     "tloam_comm_init_callback", "tloam_shard_range", "tloam_shard_ranges_frame", "tloam_se3_exp", "tloam_se3_log", "tloam_se3_plus",
 )
@@ -705,6 +744,65 @@ class HipRegistration:
                                              _dp(out)), "tloam_deskew_scan")
         return out[: len(a)].copy()
 
+    # ---- place recognition: Scan Context keyframes and loop search
+    def place_configure(self, cfg: PlaceConfig | None = None, **over):
+        """place recognition on / off (default_place_config(**over) when cfg is None); empties the keyframe database.  Kept
+        across odometry_reset (which empties the database too)."""
+        cfg = cfg if cfg is not None else default_place_config(**over)
+        self._check(self.L.tloam_place_configure(self.h, C.byref(cfg)), "tloam_place_configure")
+        self._place_cfg = cfg
+
+    def _place_grid(self):
+        cfg = getattr(self, "_place_cfg", None) or default_place_config()
+        return int(cfg.n_rings), int(cfg.n_sectors)
+
+    def place_info(self) -> dict:
+        """keyframes, loops (this waits for the device's work in flight), the last keyframe's frame, capacity"""
+        info = PlaceInfo()
+        self._check(self.L.tloam_place_get_info(self.h, C.byref(info)), "tloam_place_get_info")
+        return info.as_dict()
+
+    def place_add_scan(self, xyz, pose, frame_id=-1) -> int:
+        """one scan (sensor frame) with the caller's pose (4x4), added as a keyframe and searched -> its keyframe id"""
+        a = _aos(xyz)
+        M = _colmajor(pose)
+        kf = C.c_int64(-1)
+        self._check(self.L.tloam_place_add_scan(self.h, _dp(a), len(a), _dp(M), int(frame_id), C.byref(kf)),
+                    "tloam_place_add_scan")
+        return int(kf.value)
+
+    def place_describe(self, xyz, cfg: PlaceConfig | None = None):
+        """the Scan Context of one scan -> (descriptor (n_rings, n_sectors), ring_key, sector_key); cfg None: the context's"""
+        R, S = (int(cfg.n_rings), int(cfg.n_sectors)) if cfg is not None else self._place_grid()
+        a = _aos(xyz)
+        d, rk, sk = np.zeros((R, S)), np.zeros(R), np.zeros(S)
+        self._check(self.L.tloam_place_describe(self.h, C.byref(cfg) if cfg is not None else None, _dp(a), len(a), _dp(d),
+                                                _dp(rk), _dp(sk)), "tloam_place_describe")
+        return d, rk, sk
+
+    def place_read_keyframes(self, first=0, count=None) -> dict:
+        """keyframes [first, first + count) -> frames (m,), poses (m, 4, 4), ring_keys (m, R), sector_keys (m, S),
+        descriptors (m, R, S)"""
+        R, S = self._place_grid()
+        if count is None:
+            count = max(self.place_info()["n_keyframes"] - int(first), 0)
+        m = int(count)
+        fr, P = np.zeros(max(m, 1), np.int64), np.zeros((max(m, 1), 16))
+        rk, sk, d = np.zeros((max(m, 1), R)), np.zeros((max(m, 1), S)), np.zeros((max(m, 1), R, S))
+        self._check(self.L.tloam_place_read_keyframes(self.h, int(first), m, _lp(fr), _dp(P), _dp(rk), _dp(sk), _dp(d)),
+                    "tloam_place_read_keyframes")
+        return {"frames": fr[:m].copy(), "poses": P[:m].reshape(m, 4, 4).transpose(0, 2, 1).copy(), "ring_keys": rk[:m].copy(),
+                "sector_keys": sk[:m].copy(), "descriptors": d[:m].copy()}
+
+    def place_loops(self, first=0, count=None) -> list:
+        """loop records [first, first + count) in the order they were found, as dicts"""
+        if count is None:
+            count = max(self.place_info()["n_loops"] - int(first), 0)
+        m = int(count)
+        buf = (PlaceLoop * max(m, 1))()
+        self._check(self.L.tloam_place_read_loops(self.h, int(first), m, buf), "tloam_place_read_loops")
+        return [buf[i].as_dict() for i in range(m)]
+
     def fitness(self):
         f, r = C.c_double(0), C.c_double(0)
         rc = self.L.tloam_fitness(self.h, C.byref(f), C.byref(r))
@@ -933,6 +1031,18 @@ def default_deskew_config(**over) -> DeskewConfig:
     """tloam_deskew_default_config (off, azimuth mode, counter-clockwise, start 0, ref 0) with keyword overrides"""
     cfg = DeskewConfig()
     load_library().tloam_deskew_default_config(C.byref(cfg))
+    for k, v in over.items():
+        if not hasattr(cfg, k):
+            raise KeyError(k)
+        setattr(cfg, k, v)
+    return cfg
+
+
+def default_place_config(**over) -> PlaceConfig:
+    """tloam_place_default_config (off; 20 x 60 within 80 m, height offset 2; 10 candidates older than 50 keyframes, a loop
+    below 0.30; a keyframe every 1 m or 0.2 rad) with keyword overrides"""
+    cfg = PlaceConfig()
+    load_library().tloam_place_default_config(C.byref(cfg))
     for k, v in over.items():
         if not hasattr(cfg, k):
             raise KeyError(k)

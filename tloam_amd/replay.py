@@ -125,14 +125,16 @@ def _read_scan(path):
 
 
 def replay_device(H, scan_files, out_poses: str | None = None, odom_cfg=None, init_pose=None, max_frames=None,
-                  map_cfg=None, out_map: str | None = None, deskew_cfg=None):
+                  map_cfg=None, out_map: str | None = None, deskew_cfg=None, place_cfg=None):
     """pipeline="device": one tloam_odometry_frame per scan.  Frames the device skips
     (TLOAM_E_TOO_FEW_POINTS) are left out of the poses and listed in the stats as `skipped` (their positions in
     `scan_files`); `frame_of_pose` gives each pose's position.
     map_cfg (a MapConfig): the global map is configured with it before the run; the stats get its
     `map` info, and out_map names a PCD file the map is written to (tloam_amd/map_io.py).
     deskew_cfg (a DeskewConfig, azimuth mode: `.bin` scans carry no per-point times): the frames deskew their scans under the
-    constant-velocity motion; the stats get its `deskew` info."""
+    constant-velocity motion; the stats get its `deskew` info.
+    place_cfg (a PlaceConfig): place recognition picks keyframes and searches them for loops; the
+    stats get its `place` info and the `loops` found (read once, after the last frame)."""
     files = scan_files[: max_frames] if max_frames else scan_files
     if deskew_cfg is not None:
         if deskew_cfg.enabled and deskew_cfg.time_source != 0:
@@ -140,6 +142,8 @@ def replay_device(H, scan_files, out_poses: str | None = None, odom_cfg=None, in
         H.deskew_configure(deskew_cfg)
     if map_cfg is not None:
         H.map_configure(map_cfg)
+    if place_cfg is not None:
+        H.place_configure(place_cfg)
     H.odometry_reset(init_pose, odom_cfg)
     poses, at, skipped, t_frame, iters = [], [], [], [], 0
     out = open(out_poses, "w") if out_poses else None
@@ -170,6 +174,9 @@ def replay_device(H, scan_files, out_poses: str | None = None, odom_cfg=None, in
     if deskew_cfg is not None:
         info = H.deskew_info()
         stats["deskew"] = {"frames_deskewed": info["frames_deskewed"], "last_max_shift": info["last_max_shift"]}
+    if place_cfg is not None:
+        stats["place"] = H.place_info()
+        stats["loops"] = H.place_loops() if place_cfg.enabled else []
     if map_cfg is not None:
         stats["map"] = H.map_info()
         if out_map:
