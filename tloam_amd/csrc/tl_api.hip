@@ -143,8 +143,8 @@ void tloam_destroy(tloam_ctx* c) {
   c->feat.release();
   c->seg.release();
   c->odom.release();
-  tlh::map_release(c);
-  tlh::vmap_release(c);
+  c->map.release();
+  c->vmap.release();
   c->deskew.release();
   c->place.release();
   if (c->h_state) (void)hipHostFree(c->h_state);

@@ -129,7 +129,7 @@ int tloam_deskew_configure(tloam_ctx* c, const tloam_deskew_config* cfg) {
   if (!deskew_config_ok(want)) return TLOAM_E_INVALID;
   // (the buffers stay: the registered scan of the last frame may be the deskewed copy)
   c->deskew.cfg = want;
-  c->deskew.clear_info();
+  c->deskew.clear();
   return TLOAM_OK;
 }
 

@@ -25,29 +25,15 @@ bool map_config_ok(const tloam_map_config& m) {
 int map_grow(tloam_ctx* c, size_t need) {
   MapState& M = c->map;
   if (need <= M.cap) return TLOAM_OK;
-  DBuf<double>* cur[3] = {&M.x, &M.y, &M.z};
-  for (int a = 0; a < 3; ++a)
-    if (M.retired[a].p) {   // (a regrowth whose frame has not ended: not on the frame's path)
-      HIPC(c, hipStreamSynchronize(c->stream));
-      M.retired[a].release();
-    }
+  if (!M.retired.empty()) {   // (a regrowth whose frame has not ended: not on the frame's path)
+    HIPC(c, hipStreamSynchronize(c->stream));
+    M.retired.release();
+  }
   const size_t want = std::max(need, 2 * M.cap);
-  DBuf<double> nb[3];
-  for (int a = 0; a < 3; ++a) {
-    hipError_t e = nb[a].reserve(want);
-    if (e == hipSuccess && M.n_points > 0)
-      e = hipMemcpyAsync(nb[a].p, cur[a]->p, sizeof(double) * (size_t)M.n_points, hipMemcpyDeviceToDevice, c->stream);
-    if (e != hipSuccess) {
-      (void)hipStreamSynchronize(c->stream);
-      for (auto& b : nb) b.release();
-      c->last_error = std::string("global map growth: ") + hipGetErrorString(e);
-      return TLOAM_E_HIP;
-    }
-  }
-  for (int a = 0; a < 3; ++a) {
-    M.retired[a] = *cur[a];
-    *cur[a] = nb[a];
-  }
+  Grower g(c, M.retired);
+  for (DBuf<double>* a : {&M.x, &M.y, &M.z}) g.add(*a, want, (size_t)M.n_points);
+  const int rc = g.commit("global map growth: ");
+  if (rc != TLOAM_OK) return rc;
   M.cap = std::min(std::min(M.x.cap, M.y.cap), M.z.cap);
   return TLOAM_OK;
 }
@@ -55,22 +41,6 @@ int map_grow(tloam_ctx* c, size_t need) {
 }  // namespace
 
 namespace tlh {
-
-void map_empty(tloam_ctx* c) {
-  MapState& M = c->map;
-  M.n_points = M.n_frames = M.last_first = M.last_count = M.overflow_frames = 0;
-  M.pending_seq = 0;
-  M.have_count = false;
-  M.xf_seq = 0;
-}
-
-void map_release(tloam_ctx* c) {
-  MapState& M = c->map;
-  M.release_storage();
-  if (M.h_seg) (void)hipHostFree(M.h_seg);
-  M.h_seg = M.h_seg_dev = nullptr;
-  map_empty(c);
-}
 
 // the start of a later frame: the map holds what this frame can append (at most one voxel per point), the voxel job's scratch
 // holds the scan.  Nothing of the odometry state has changed yet: a failure here leaves the frame undone
@@ -117,7 +87,7 @@ int map_stage_launch(tloam_ctx* c, const double pose[16], size_t n) {
   const size_t at = (size_t)M.n_points;
   W.ox = M.x.p + at; W.oy = M.y.p + at; W.oz = M.z.p + at;
   W.n_out = M.counts.p;
-  W.host_seg = M.h_seg_dev;
+  W.host_seg = M.seg.dev;
   W.host_seq = ++M.seq;
   W.use_ticket = (c->vox_ticket || (long long)(n + 256) / 256 > (long long)map_emit_resident_blocks(c->device_cus)) ? 1 : 0;
   W.fault = c->h_fault_dev + kFaultVoxEmit;
@@ -136,36 +106,30 @@ int map_stage_launch(tloam_ctx* c, const double pose[16], size_t n) {
 // flag are in pinned memory already -- read, not waited for
 int map_stage_collect(tloam_ctx* c, tloam_odom_stats* st) {
   MapState& M = c->map;
-  if (!M.pending_seq) return TLOAM_OK;
   unsigned long long pay[7];
-  int rc = wait_segment(c, M.h_seg, M.pending_seq, pay);
-  if (rc < 0) return rc;
-  unsigned long long count = 0;
-  int ov = 0;
-  if (rc == TLOAM_OK) {
-    count = pay[0];
-    ov = pay[2] != 0;
-  } else {   // (the stream has drained and the segment is not there: the device words)
+  int rc = collect_segment(c, M.seg, M.pending_seq, st, pay, [&](unsigned long long w[7]) -> int {
+    unsigned long long count = 0;
+    int ov = 0;
     HIPC(c, hipMemcpyAsync(&count, M.counts.p, sizeof(count), hipMemcpyDeviceToHost, c->stream));
     HIPC(c, hipMemcpyAsync(&ov, M.ctl.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPC(c, hipStreamSynchronize(c->stream));
-    st->d2h_bytes += (int64_t)(sizeof(count) + sizeof(int));
-    st->host_syncs++;
-  }
-  st->d2h_bytes += 8 * (int64_t)sizeof(unsigned long long);   // the segment
-  M.pending_seq = 0;
+    w[0] = count;
+    w[2] = ov;
+    return (int)(sizeof(count) + sizeof(int));
+  });
+  if (rc != TLOAM_OK) return rc < 0 ? rc : TLOAM_OK;   // (1: nothing pending)
   rc = check_device_faults(c);   // (k_map_emit's bounded look-back)
   if (rc != TLOAM_OK) return rc;
   M.have_count = true;
-  M.new_points = (int64_t)count;
-  M.overflowed = ov != 0;
+  M.new_points = (int64_t)pay[0];
+  M.overflowed = pay[2] != 0;
   return TLOAM_OK;
 }
 
 // the frame has ended (the stream has drained): storage a regrowth replaced is freed; an accepted frame's voxels join the map
 void map_frame_end(tloam_ctx* c, bool accepted) {
   MapState& M = c->map;
-  for (auto& b : M.retired) b.release();
+  M.retired.release();
   if (accepted && M.have_count) {
     if (M.overflowed) {
       M.overflow_frames++;   // "[VoxelDownSample] voxel_size is too small." (PointCloud2.cpp:370-372): appends nothing here
@@ -201,31 +165,20 @@ int tloam_map_configure(tloam_ctx* c, const tloam_map_config* cfg) {
   HIPC(c, hipSetDevice(c->device));
   HIPC(c, hipStreamSynchronize(c->stream));
   MapState& M = c->map;
-  map_empty(c);
+  M.clear();
   if (!want.enabled) {   // mapping off: the frame's memory is what it was without the map
-    map_release(c);
+    M.release();
     M.cfg = want;
     return TLOAM_OK;
   }
-  if (!M.h_seg) {
-    unsigned long long* h = nullptr;
-    HIPC(c, hipHostMalloc((void**)&h, 8 * sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent));
-    memset(h, 0, 8 * sizeof(unsigned long long));
-    const hipError_t e = hipHostGetDevicePointer((void**)&M.h_seg_dev, h, 0);
-    if (e != hipSuccess) {
-      (void)hipHostFree(h);
-      c->last_error = std::string("hipHostGetDevicePointer: ") + hipGetErrorString(e);
-      return TLOAM_E_HIP;
-    }
-    M.h_seg = h;
-  }
+  HIPC(c, M.seg.alloc());
   const size_t reserve = want.reserve_points > 0 ? (size_t)want.reserve_points : kMapDefaultReserve;
   if (M.cap < reserve) {   // (the map is empty: nothing to copy)
     M.x.release(); M.y.release(); M.z.release();
     M.cap = 0;
     const int rc = map_grow(c, reserve);
     if (rc != TLOAM_OK) return rc;
-    for (auto& b : M.retired) b.release();
+    M.retired.release();
   }
   M.cfg = want;
   return TLOAM_OK;

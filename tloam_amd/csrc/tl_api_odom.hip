@@ -276,10 +276,10 @@ int tloam_odometry_reset(tloam_ctx* c, const tloam_odom_config* cfg, const doubl
   O.frame = 0;
   O.ready = true;
   O.reg_valid = false;   // no registered scan before the first frame
-  map_empty(c);          // the global map starts again; its configuration stays
-  vmap_empty(c);         // the merged voxel map too
-  place_empty(c);        // and the keyframe database (its configuration stays)
-  c->deskew.clear_info(); // (its configuration stays too)
+  c->map.clear();                // the global map starts again; its configuration stays
+  c->vmap.clear();               // the merged voxel map too
+  c->place.clear(c->stream);     // and the keyframe database (its configuration stays)
+  c->deskew.clear();             // (its configuration stays too)
   return TLOAM_OK;
 }
 

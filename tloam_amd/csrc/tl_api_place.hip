@@ -42,21 +42,14 @@ bool moved(const double A[16], const double B[16], double kf_dist, double kf_ang
   return dist >= kf_dist || acos(cs) >= kf_angle;
 }
 
-template <class T>
-hipError_t grow_into(DBuf<T>& fresh, const DBuf<T>& cur, size_t want, size_t keep, hipStream_t s) {
-  hipError_t e = fresh.reserve(want);
-  if (e == hipSuccess && keep) e = hipMemcpyAsync(fresh.p, cur.p, sizeof(T) * keep, hipMemcpyDeviceToDevice, s);
-  return e;
-}
-
 // the database holds `need` keyframes: new storage of max(need, 2 cap), the keyframes so far copied device to device behind
 // whatever is in flight, the old storage retired until the stream has drained.  A failure leaves the database as it was
 int place_grow(tloam_ctx* c, size_t need) {
   PlaceState& P = c->place;
   if (need <= P.cap) return TLOAM_OK;
-  if (P.r_desc.p) {   // (a regrowth whose frame has not ended: not on the frame's path)
+  if (!P.retired.empty()) {   // (a regrowth whose frame has not ended: not on the frame's path)
     HIPC(c, hipStreamSynchronize(c->stream));
-    P.release_retired();
+    P.retired.release();
   }
   const size_t want = std::max(need, 2 * P.cap);
   if (want > kPlaceMaxKeyframes) {
@@ -64,32 +57,17 @@ int place_grow(tloam_ctx* c, size_t need) {
     return TLOAM_E_HIP;
   }
   const size_t R = (size_t)P.cfg.n_rings, S = (size_t)P.cfg.n_sectors, keep = (size_t)P.n_kf;
-  DBuf<double> nd, nr, ns, np, nk;
-  DBuf<long long> nf;
-  DBuf<int> nt;
-  DBuf<tloam_place_loop> nl;
-  hipError_t e = grow_into(nd, P.desc, want * R * S, keep * R * S, c->stream);
-  if (e == hipSuccess) e = grow_into(nr, P.rkey, want * R, keep * R, c->stream);
-  if (e == hipSuccess) e = grow_into(ns, P.skey, want * S, keep * S, c->stream);
-  if (e == hipSuccess) e = grow_into(np, P.pose, want * 16, keep * 16, c->stream);
-  if (e == hipSuccess) e = grow_into(nf, P.frame, want, keep, c->stream);
-  if (e == hipSuccess) e = grow_into(nl, P.loops, want, keep, c->stream);   // (at most one loop per keyframe)
-  if (e == hipSuccess) e = nk.reserve(want);
-  if (e == hipSuccess) e = nt.reserve(want);
-  if (e != hipSuccess) {
-    (void)hipStreamSynchronize(c->stream);
-    nd.release(); nr.release(); ns.release(); np.release(); nk.release(); nf.release(); nt.release(); nl.release();
-    c->last_error = std::string("place recognition database growth: ") + hipGetErrorString(e);
-    return TLOAM_E_HIP;
-  }
-  P.r_desc = P.desc; P.desc = nd;
-  P.r_rkey = P.rkey; P.rkey = nr;
-  P.r_skey = P.skey; P.skey = ns;
-  P.r_pose = P.pose; P.pose = np;
-  P.r_kdist = P.kdist; P.kdist = nk;
-  P.r_frame = P.frame; P.frame = nf;
-  P.r_taken = P.taken; P.taken = nt;
-  P.r_loops = P.loops; P.loops = nl;
+  Grower g(c, P.retired);
+  g.add(P.desc, want * R * S, keep * R * S);
+  g.add(P.rkey, want * R, keep * R);
+  g.add(P.skey, want * S, keep * S);
+  g.add(P.pose, want * 16, keep * 16);
+  g.add(P.frame, want, keep);
+  g.add(P.loops, want, keep);   // (at most one loop per keyframe)
+  g.add(P.kdist, want);
+  g.add(P.taken, want);
+  const int rc = g.commit("place recognition database growth: ");
+  if (rc != TLOAM_OK) return rc;
   P.cap = want;
   return TLOAM_OK;
 }
@@ -140,7 +118,7 @@ int place_alloc(tloam_ctx* c, size_t reserve) {
   const int rc = place_grow(c, reserve);
   if (rc != TLOAM_OK) return rc;
   HIPC(c, hipStreamSynchronize(c->stream));
-  P.release_retired();
+  P.retired.release();
   return TLOAM_OK;
 }
 
@@ -163,13 +141,6 @@ int64_t device_loops(tloam_ctx* c, int* rc) {   // waits for the work in flight
 
 namespace tlh {
 
-void place_empty(tloam_ctx* c) {
-  PlaceState& P = c->place;
-  P.n_kf = 0;
-  P.last_kf_frame = -1;
-  if (P.ctl.p) (void)hipMemsetAsync(P.ctl.p, 0, sizeof(unsigned long long), c->stream);   // (behind whatever is in flight)
-}
-
 // the start of a frame: room for one more keyframe, before anything of the odometry state changes.  A failure leaves the frame
 // undone
 int place_frame_reserve(tloam_ctx* c, size_t n) {
@@ -185,7 +156,7 @@ int place_frame_reserve(tloam_ctx* c, size_t n) {
 // described, committed and searched by launches nothing waits for
 void place_frame_end(tloam_ctx* c, bool accepted, int64_t frame, const double pose[16], const double* scan, size_t n) {
   PlaceState& P = c->place;
-  P.release_retired();
+  P.retired.release();
   P.in_flight = false;
   if (!accepted || !P.cfg.enabled || P.cap < (size_t)P.n_kf + 1) return;
   if (P.n_kf > 0 && !moved(P.last_pose, pose, P.cfg.kf_dist, P.cfg.kf_angle)) return;
@@ -289,7 +260,7 @@ int tloam_place_add_scan(tloam_ctx* c, const double* xyz, size_t n, const double
     if (!std::isfinite(pose[i])) return TLOAM_E_INVALID;
   HIPC(c, hipSetDevice(c->device));
   HIPC(c, hipStreamSynchronize(c->stream));   // (not a frame: whatever is in flight may read the buffers replaced below)
-  P.release_retired();
+  P.retired.release();
   P.in_flight = false;
   int rc = place_grow(c, (size_t)P.n_kf + 1);
   if (rc != TLOAM_OK) return rc;
@@ -300,7 +271,7 @@ int tloam_place_add_scan(tloam_ctx* c, const double* xyz, size_t n, const double
   const int64_t q = P.n_kf;
   enqueue_keyframe(c, P.s_aos.p, n, pose, frame_id);
   HIPC(c, hipStreamSynchronize(c->stream));
-  P.release_retired();
+  P.retired.release();
   if (keyframe_out) *keyframe_out = q;
   return TLOAM_OK;
 }

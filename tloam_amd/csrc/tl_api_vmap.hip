@@ -35,9 +35,9 @@ VmapTable table_of(VmapState& V) {
 int vmap_grow(tloam_ctx* c, size_t need) {
   VmapState& V = c->vmap;
   if (need <= V.cap) return TLOAM_OK;
-  if (V.r_key.p || V.r_tab.p) {   // (a regrowth whose frame has not ended: not on the frame's path)
+  if (!V.retired.empty()) {   // (a regrowth whose frame has not ended: not on the frame's path)
     HIPC(c, hipStreamSynchronize(c->stream));
-    V.r_key.release(); V.r_n.release(); V.r_qx.release(); V.r_qy.release(); V.r_qz.release(); V.r_tab.release();
+    V.retired.release();
   }
   const size_t want = std::max(need, 2 * V.cap);
   if (want > kVmapMaxVoxels) {
@@ -46,41 +46,18 @@ int vmap_grow(tloam_ctx* c, size_t need) {
   }
   size_t tsize = 1024;
   while (tsize < 2 * want) tsize <<= 1;
-  DBuf<unsigned long long> nk;
-  DBuf<long long> nn[4];
-  DBuf<int> nt;
-  DBuf<long long>* cur[4] = {&V.n, &V.qx, &V.qy, &V.qz};
   const size_t nv = (size_t)V.n_voxels;
-  hipError_t e = nk.reserve(want);
-  if (e == hipSuccess && nv) e = hipMemcpyAsync(nk.p, V.key.p, sizeof(unsigned long long) * nv, hipMemcpyDeviceToDevice, c->stream);
-  for (int a = 0; a < 4 && e == hipSuccess; ++a) {
-    e = nn[a].reserve(want);
-    if (e == hipSuccess && nv) e = hipMemcpyAsync(nn[a].p, cur[a]->p, sizeof(long long) * nv, hipMemcpyDeviceToDevice, c->stream);
-  }
-  if (e == hipSuccess) e = nt.reserve(tsize);
-  if (e == hipSuccess) e = hipMemsetAsync(nt.p, 0xff, sizeof(int) * tsize, c->stream);
-  if (e != hipSuccess) {
-    (void)hipStreamSynchronize(c->stream);
-    nk.release(); nt.release();
-    for (auto& b : nn) b.release();
-    c->last_error = std::string("voxel map growth: ") + hipGetErrorString(e);
-    return TLOAM_E_HIP;
-  }
-  V.r_key = V.key; V.key = nk;
-  V.r_n = V.n; V.n = nn[0];
-  V.r_qx = V.qx; V.qx = nn[1];
-  V.r_qy = V.qy; V.qy = nn[2];
-  V.r_qz = V.qz; V.qz = nn[3];
-  V.r_tab = V.tab; V.tab = nt;
+  Grower g(c, V.retired);
+  g.add(V.key, want, nv);
+  for (DBuf<long long>* a : {&V.n, &V.qx, &V.qy, &V.qz}) g.add(*a, want, nv);
+  if (int* t = g.add(V.tab, tsize)) g.check(hipMemsetAsync(t, 0xff, sizeof(int) * tsize, c->stream));
+  const int rc = g.commit("voxel map growth: ");
+  if (rc != TLOAM_OK) return rc;
   V.cap = want;
   V.tmask = tsize - 1;
   V.tab_dirty = false;
   launch_vmap_rehash(table_of(V), nv, c->stream);
   return TLOAM_OK;
-}
-
-void release_retired(VmapState& V) {
-  V.r_key.release(); V.r_n.release(); V.r_qx.release(); V.r_qy.release(); V.r_qz.release(); V.r_tab.release();
 }
 
 VmapStageWork stage_work(tloam_ctx* c) {   // the staged frame's buffers, as k_vmap_commit reads them
@@ -109,23 +86,6 @@ VmapReadArgs read_args(const VmapState& V) {
 }  // namespace
 
 namespace tlh {
-
-void vmap_empty(tloam_ctx* c) {
-  VmapState& V = c->vmap;
-  V.n_voxels = V.n_points = V.n_frames = V.last_new = V.overflow_frames = 0;
-  V.pending_seq = 0;
-  V.have_count = false;
-  if (V.tab.p) V.tab_dirty = true;   // (cleared on the stream at the next frame: the ids it holds are gone)
-}
-
-void vmap_release(tloam_ctx* c) {
-  VmapState& V = c->vmap;
-  V.release_storage();
-  if (V.h_seg) (void)hipHostFree(V.h_seg);
-  V.h_seg = V.h_seg_dev = nullptr;
-  vmap_empty(c);
-  V.tab_dirty = false;
-}
 
 // the start of a later frame: the map holds what this frame can add (at most one new voxel per point), the staging holds the
 // scan.  Nothing of the odometry state has changed yet: a failure here leaves the frame undone
@@ -161,7 +121,7 @@ int vmap_stage_launch(tloam_ctx* c, const double pose[16], size_t n) {
   W.aos = frame_scan(c);   // (the deskewed copy when the frame corrected its scan)
   for (int k = 0; k < 16; ++k) W.M[k] = pose[k];
   W.n = n;
-  W.host_seg = V.h_seg_dev;
+  W.host_seg = V.seg.dev;
   W.host_seq = ++V.seq;
   launch_vmap_stage(W, c->stream);
   V.pending_seq = W.host_seq;
@@ -171,20 +131,15 @@ int vmap_stage_launch(tloam_ctx* c, const double pose[16], size_t n) {
 // after the frame's last wait: the stage's counts are in pinned memory already -- read, not waited for
 int vmap_stage_collect(tloam_ctx* c, tloam_odom_stats* st) {
   VmapState& V = c->vmap;
-  if (!V.pending_seq) return TLOAM_OK;
   unsigned long long pay[7];
-  int rc = wait_segment(c, V.h_seg, V.pending_seq, pay);
-  if (rc < 0) return rc;
-  if (rc != TLOAM_OK) {   // (the stream has drained and the segment is not there: the device words)
+  const int rc = collect_segment(c, V.seg, V.pending_seq, st, pay, [&](unsigned long long p[7]) -> int {
     unsigned long long w[8];
     HIPC(c, hipMemcpyAsync(w, V.ctl.p, sizeof(w), hipMemcpyDeviceToHost, c->stream));
     HIPC(c, hipStreamSynchronize(c->stream));
-    st->d2h_bytes += (int64_t)sizeof(w);
-    st->host_syncs++;
-    pay[0] = w[4]; pay[1] = w[1]; pay[2] = w[0]; pay[3] = w[3];
-  }
-  st->d2h_bytes += 8 * (int64_t)sizeof(unsigned long long);   // the segment
-  V.pending_seq = 0;
+    p[0] = w[4]; p[1] = w[1]; p[2] = w[0]; p[3] = w[3];
+    return (int)sizeof(w);
+  });
+  if (rc != TLOAM_OK) return rc < 0 ? rc : TLOAM_OK;   // (1: nothing pending)
   if (pay[3]) {
     c->last_error = "voxel map: a look-back of k_vmap_emit timed out";
     return TLOAM_E_HIP;
@@ -200,7 +155,7 @@ int vmap_stage_collect(tloam_ctx* c, tloam_odom_stats* st) {
 // by a launch nothing waits for (later frames and reads are behind it on the stream), an unaccepted one's dropped
 void vmap_frame_end(tloam_ctx* c, bool accepted) {
   VmapState& V = c->vmap;
-  release_retired(V);
+  V.retired.release();
   if (accepted && V.have_count) {
     if (V.overflowed) {
       V.overflow_frames++;   // a finite point beyond 2^20 voxels of the origin: the frame adds nothing
@@ -238,24 +193,13 @@ int tloam_voxel_map_configure(tloam_ctx* c, const tloam_voxel_map_config* cfg) {
   HIPC(c, hipSetDevice(c->device));
   HIPC(c, hipStreamSynchronize(c->stream));
   VmapState& V = c->vmap;
-  vmap_empty(c);
+  V.clear();
   if (!want.enabled) {   // off: the frame's memory is what it was without the voxel map
-    vmap_release(c);
+    V.release();
     V.cfg = want;
     return TLOAM_OK;
   }
-  if (!V.h_seg) {
-    unsigned long long* h = nullptr;
-    HIPC(c, hipHostMalloc((void**)&h, 8 * sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent));
-    memset(h, 0, 8 * sizeof(unsigned long long));
-    const hipError_t e = hipHostGetDevicePointer((void**)&V.h_seg_dev, h, 0);
-    if (e != hipSuccess) {
-      (void)hipHostFree(h);
-      c->last_error = std::string("hipHostGetDevicePointer: ") + hipGetErrorString(e);
-      return TLOAM_E_HIP;
-    }
-    V.h_seg = h;
-  }
+  HIPC(c, V.seg.alloc());
   const size_t reserve = want.reserve_voxels > 0 ? (size_t)want.reserve_voxels : kVmapDefaultReserve;
   if (V.cap < reserve) {   // (the map is empty: nothing to copy)
     V.key.release(); V.n.release(); V.qx.release(); V.qy.release(); V.qz.release(); V.tab.release();
@@ -263,7 +207,7 @@ int tloam_voxel_map_configure(tloam_ctx* c, const tloam_voxel_map_config* cfg) {
     const int rc = vmap_grow(c, reserve);
     if (rc != TLOAM_OK) return rc;
     HIPC(c, hipStreamSynchronize(c->stream));
-    release_retired(V);
+    V.retired.release();
   }
   V.cfg = want;
   return TLOAM_OK;

@@ -52,6 +52,47 @@ struct DBuf {
   }
 };
 
+// device storage a regrowth replaced: freed once the stream has drained, the launches in flight may still read it
+struct Retired {
+  std::vector<void*> p;
+  template <class T>
+  void take(DBuf<T>& b) {
+    if (b.p) p.push_back(b.p);
+    b.p = nullptr;
+    b.cap = 0;
+  }
+  void release() {
+    for (void* q : p) (void)hipFree(q);
+    p.clear();
+  }
+  bool empty() const { return p.empty(); }
+};
+
+// a pinned, device-visible segment of 8 words (mapped | coherent, zeroed) a stage's last kernel reports its result through
+struct PinnedSeg {
+  unsigned long long* h = nullptr;     // as the host reads it
+  unsigned long long* dev = nullptr;   // as the device addresses it
+  hipError_t alloc() {   // (kept if there is one)
+    if (h) return hipSuccess;
+    unsigned long long* q = nullptr;
+    hipError_t e = hipHostMalloc((void**)&q, 8 * sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent);
+    if (e != hipSuccess) return e;
+    memset(q, 0, 8 * sizeof(unsigned long long));
+    e = hipHostGetDevicePointer((void**)&dev, q, 0);
+    if (e != hipSuccess) {
+      (void)hipHostFree(q);
+      dev = nullptr;
+      return e;
+    }
+    h = q;
+    return hipSuccess;
+  }
+  void release() {
+    if (h) (void)hipHostFree(h);
+    h = dev = nullptr;
+  }
+};
+
 struct KindData {
   // source (this rank's block)
   size_t n_src_full = 0, src_lo = 0, n_src = 0;
@@ -194,14 +235,13 @@ struct MapState {
   tloam_map_config cfg = {0, 0, 1.0, 0};   // tloam_map_default_config until tloam_map_configure
   DBuf<double> x, y, z;            // the map: n_points rows of cap
   size_t cap = 0;
-  DBuf<double> retired[3];         // storage a regrowth replaced: freed once the frame has drained the stream
+  Retired retired;                 // storage a regrowth replaced: freed once the frame has drained the stream
   int64_t n_points = 0, n_frames = 0, last_first = 0, last_count = 0, overflow_frames = 0;
   DBuf<double> wx, wy, wz, min_partial, vmin;   // the transformed scan (kept: the registered scan of a mapping frame)
   DBuf<unsigned long long> keys, leader, counts;
   DBuf<int> head, first, count, bigslot, slot_of_pt, next, members, bigfill, ctl;
   DBuf<int4> bigq;
-  unsigned long long* h_seg = nullptr;      // pinned, device-visible: [0] voxels, [2] overflow, [7] check word
-  unsigned long long* h_seg_dev = nullptr;
+  PinnedSeg seg;                            // [0] voxels, [2] overflow, [7] check word
   unsigned long long seq = 0;               // numbers of the segments the map stage has posted
   unsigned long long pending_seq = 0;       // the map stage of the frame in flight (0: none)
   bool have_count = false;                  // its result, read at the frame's last wait, committed if the frame is accepted
@@ -209,14 +249,21 @@ struct MapState {
   bool overflowed = false;
   unsigned long long xf_seq = 0;            // upload number of the scan whose transform is in (wx, wy, wz) (0: none)
   size_t xf_n = 0;
-  void release_storage() {
+  void clear() {   // the run's map goes; its configuration and storage stay
+    n_points = n_frames = last_first = last_count = overflow_frames = 0;
+    pending_seq = 0;
+    have_count = false;
+    xf_seq = 0;
+  }
+  void release() {
     x.release(); y.release(); z.release(); cap = 0;
-    for (auto& b : retired) b.release();
+    retired.release();
     wx.release(); wy.release(); wz.release(); min_partial.release(); vmin.release();
     keys.release(); leader.release(); counts.release();
     head.release(); first.release(); count.release(); bigslot.release(); slot_of_pt.release(); next.release(); members.release();
     bigfill.release(); ctl.release(); bigq.release();
-    xf_seq = 0;
+    seg.release();
+    clear();
   }
 };
 
@@ -230,9 +277,7 @@ struct VmapState {
   size_t cap = 0;
   unsigned long long tmask = 0;
   bool tab_dirty = false;          // emptied since the table was last cleared: cleared at the next frame / read
-  DBuf<unsigned long long> r_key;  // storage a regrowth replaced: freed once the frame has drained the stream
-  DBuf<long long> r_n, r_qx, r_qy, r_qz;
-  DBuf<int> r_tab;
+  Retired retired;                 // storage a regrowth replaced: freed once the frame has drained the stream
   int64_t n_voxels = 0, n_points = 0, n_frames = 0, last_new = 0, overflow_frames = 0;
   // the frame's staging: its table, the slot of every point, the look-back words, control words; reads' scratch
   DBuf<unsigned long long> fkey, fsum, look, ctl;
@@ -240,18 +285,26 @@ struct VmapState {
   unsigned long long fmask = 0;    // the staged frame's table size - 1
   DBuf<double> rd_c;
   DBuf<long long> rd_n;
-  unsigned long long* h_seg = nullptr;      // pinned, device-visible: [0] new voxels, [1] points, [2] overflow, [3] fault, [7] check
-  unsigned long long* h_seg_dev = nullptr;
+  PinnedSeg seg;                            // [0] new voxels, [1] points, [2] overflow, [3] fault, [7] check
   unsigned long long seq = 0;
   unsigned long long pending_seq = 0;       // the stage of the frame in flight (0: none)
   bool have_count = false;                  // its result, read at the frame's last wait, committed if the frame is accepted
   int64_t new_voxels = 0, new_points = 0;
   bool overflowed = false;
-  void release_storage() {
+  void clear() {   // the run's map goes; its configuration and storage stay
+    n_voxels = n_points = n_frames = last_new = overflow_frames = 0;
+    pending_seq = 0;
+    have_count = false;
+    if (tab.p) tab_dirty = true;   // (cleared on the stream at the next frame: the ids it holds are gone)
+  }
+  void release() {
     key.release(); n.release(); qx.release(); qy.release(); qz.release(); tab.release(); cap = 0; tmask = 0;
-    r_key.release(); r_n.release(); r_qx.release(); r_qy.release(); r_qz.release(); r_tab.release();
+    retired.release();
     fkey.release(); fsum.release(); look.release(); ctl.release(); flead.release(); fid.release(); slot_of_pt.release();
     rd_c.release(); rd_n.release();
+    seg.release();
+    clear();
+    tab_dirty = false;
   }
 };
 
@@ -271,10 +324,10 @@ struct DeskewState {
   double xi[6] = {0, 0, 0, 0, 0, 0};   // the frame in flight's motion
   int64_t frames = 0, last_frame = -1;
   double last_twist[6] = {0, 0, 0, 0, 0, 0};
-  void clear_info() { frames = 0; last_frame = -1; committed = -1; for (double& v : last_twist) v = 0.0; }
+  void clear() { frames = 0; last_frame = -1; committed = -1; for (double& v : last_twist) v = 0.0; }
   void release() {
     aos.release(); t.release(); ctl.release(); s_in.release(); s_out.release(); s_t.release(); s_ctl.release();
-    clear_info();
+    clear();
   }
 };
 
@@ -288,10 +341,7 @@ struct PlaceState {
   DBuf<long long> frame;
   DBuf<int> taken;
   DBuf<tloam_place_loop> loops;
-  DBuf<double> r_desc, r_rkey, r_skey, r_pose, r_kdist;   // retired by a growth
-  DBuf<long long> r_frame;
-  DBuf<int> r_taken;
-  DBuf<tloam_place_loop> r_loops;
+  Retired retired;
   DBuf<unsigned long long> bins, ctl;   // ctl[0]: the number of loop records
   DBuf<PlaceCandidate> cand;
   DBuf<double> s_aos, s_desc, s_rkey, s_skey;
@@ -300,13 +350,14 @@ struct PlaceState {
   int64_t last_kf_frame = -1;
   double last_pose[16];            // the last keyframe's pose (n_kf > 0)
   bool in_flight = false;          // a frame's place launches may still be reading its scan
-  void release_retired() {
-    r_desc.release(); r_rkey.release(); r_skey.release(); r_pose.release(); r_kdist.release(); r_frame.release();
-    r_taken.release(); r_loops.release();
+  void clear(hipStream_t s) {   // the run's keyframes and loops go; the configuration and storage stay
+    n_kf = 0;
+    last_kf_frame = -1;
+    if (ctl.p) (void)hipMemsetAsync(ctl.p, 0, sizeof(unsigned long long), s);   // (behind whatever is in flight)
   }
   void release() {
     desc.release(); rkey.release(); skey.release(); pose.release(); kdist.release(); frame.release(); taken.release();
-    loops.release(); release_retired(); bins.release(); ctl.release(); cand.release();
+    loops.release(); retired.release(); bins.release(); ctl.release(); cand.release();
     s_aos.release(); s_desc.release(); s_rkey.release(); s_skey.release();
     cap = 0; n_kf = 0; last_kf_frame = -1; in_flight = false;
   }
@@ -512,6 +563,63 @@ inline int kind_active(const tloam_tls_config& c, int k) {
   return 0;
 }
 inline size_t round_up(size_t v, size_t m) { return (v + m - 1) / m * m; }
+
+// `fresh` holds `want` rows, the first `keep` of `cur` copied into it device to device on the stream
+template <class T>
+hipError_t grow_into(DBuf<T>& fresh, const DBuf<T>& cur, size_t want, size_t keep, hipStream_t s) {
+  hipError_t e = fresh.reserve(want);
+  if (e == hipSuccess && keep) e = hipMemcpyAsync(fresh.p, cur.p, sizeof(T) * keep, hipMemcpyDeviceToDevice, s);
+  return e;
+}
+
+// One growth of a store, all its arrays or none: add() gives an array fresh storage of `want` rows behind whatever is in flight,
+// the first `keep` rows copied (0: the array is rebuilt, not copied), and returns it (nullptr once anything failed); commit()
+// swaps every fresh array in and parks the old storage in the store's Retired -- or, after a failure, frees the fresh arrays,
+// leaves the store as it was and returns TLOAM_E_HIP with `what` in last_error
+class Grower {
+ public:
+  Grower(tloam_ctx* c, Retired& parked) : c_(c), parked_(parked) {}
+  template <class T>
+  T* add(DBuf<T>& cur, size_t want, size_t keep = 0) {
+    if (e_ != hipSuccess) return nullptr;
+    DBuf<T> fresh;
+    e_ = grow_into(fresh, cur, want, keep, c_->stream);
+    if (fresh.p) arrays_.push_back({&cur, fresh.p, fresh.cap, &swap_in<T>});
+    return e_ == hipSuccess ? fresh.p : nullptr;
+  }
+  void check(hipError_t e) {   // a step on the fresh storage (the first failure counts)
+    if (e_ == hipSuccess) e_ = e;
+  }
+  int commit(const char* what) {
+    if (e_ != hipSuccess) {
+      (void)hipStreamSynchronize(c_->stream);
+      for (const Array& a : arrays_) (void)hipFree(a.fresh);
+      c_->last_error = std::string(what) + hipGetErrorString(e_);
+      return TLOAM_E_HIP;
+    }
+    for (const Array& a : arrays_) a.swap(a.cur, a.fresh, a.cap, parked_);
+    return TLOAM_OK;
+  }
+
+ private:
+  struct Array {
+    void* cur;     // the store's DBuf<T>
+    void* fresh;
+    size_t cap;
+    void (*swap)(void* cur, void* fresh, size_t cap, Retired& parked);
+  };
+  template <class T>
+  static void swap_in(void* cur, void* fresh, size_t cap, Retired& parked) {
+    DBuf<T>& b = *static_cast<DBuf<T>*>(cur);
+    parked.take(b);
+    b.p = static_cast<T*>(fresh);
+    b.cap = cap;
+  }
+  tloam_ctx* c_;
+  Retired& parked_;
+  hipError_t e_ = hipSuccess;
+  std::vector<Array> arrays_;
+};
 inline bool one_rank(const tloam_ctx* c) { return c->nranks == 1 && !c->loopback; }    // the single-rank launch forms apply
 inline bool exchanging(const tloam_ctx* c) { return c->nranks > 1 || c->loopback; }    // the sharded launch forms run
 // tl_api_comm.hip
@@ -527,6 +635,25 @@ void exchange_clouds(tloam_ctx* c, FrameClouds& F);    // the registered clouds 
 int check_device_faults(tloam_ctx* c);
 int wait_word(tloam_ctx* c, const unsigned long long* p, unsigned long long seq);
 int wait_segment(tloam_ctx* c, const unsigned long long* seg, unsigned long long seq, unsigned long long payload[7]);
+// After the frame's last wait: the payload of the stage segment the frame in flight posted as number `pending` (0: none posted,
+// nothing to collect: returns 1), in pinned memory already -- read, not waited for.  Should the stream have drained without it,
+// `device_words(pay)` copies the stage's own device words into `pay` and synchronises, returning the bytes it copied or a status
+template <class DeviceWords>
+int collect_segment(tloam_ctx* c, const PinnedSeg& seg, unsigned long long& pending, tloam_odom_stats* st,
+                    unsigned long long pay[7], DeviceWords device_words) {
+  if (!pending) return 1;
+  const int rc = wait_segment(c, seg.h, pending, pay);
+  if (rc < 0) return rc;
+  if (rc != TLOAM_OK) {   // (the stream has drained and the segment is not there: the device words)
+    const int bytes = device_words(pay);
+    if (bytes < 0) return bytes;
+    st->d2h_bytes += bytes;
+    st->host_syncs++;
+  }
+  st->d2h_bytes += 8 * (int64_t)sizeof(unsigned long long);   // the segment
+  pending = 0;
+  return TLOAM_OK;
+}
 int stage_and_upload(tloam_ctx* c, const double* const parts[], const size_t counts[], int nparts, double* dev_dst, size_t offs[]);
 int stage_in_place(tloam_ctx* c, const double* const parts[], const size_t counts[], int nparts, size_t offs[], const double** dev_view,
                    int* half);
@@ -551,20 +678,16 @@ int submap_init_body(tloam_ctx* c, const tloam_submap_config& want, const double
 int submap_update_resident(tloam_ctx* c, const double pose[16], size_t n_planar, size_t n_sphere, size_t n_edge, size_t n_ground,
                            DBuf<double>& block);
 // tl_api_map.hip: the odometry frame's map stage -- reserve at the start of a later frame, launch after the match, collect the
-// count after the frame's last wait, commit when the frame is accepted; map_release at destroy
+// count after the frame's last wait, commit when the frame is accepted; MapState::release at destroy
 int map_frame_reserve(tloam_ctx* c, size_t n);
 int map_stage_launch(tloam_ctx* c, const double pose[16], size_t n);
 int map_stage_collect(tloam_ctx* c, tloam_odom_stats* st);
 void map_frame_end(tloam_ctx* c, bool accepted);
-void map_empty(tloam_ctx* c);
-void map_release(tloam_ctx* c);
 // tl_api_vmap.hip: the merged voxel map's stage, at the same four points of the frame
 int vmap_frame_reserve(tloam_ctx* c, size_t n);
 int vmap_stage_launch(tloam_ctx* c, const double pose[16], size_t n);
 int vmap_stage_collect(tloam_ctx* c, tloam_odom_stats* st);
 void vmap_frame_end(tloam_ctx* c, bool accepted);
-void vmap_empty(tloam_ctx* c);
-void vmap_release(tloam_ctx* c);
 // tl_api_deskew.hip: the frame's deskew -- sized and its times uploaded after the scan's upload, launched after the segmentation's
 // (the refused-time flag read with the frame's first wait), committed when the frame ends
 int deskew_frame_upload(tloam_ctx* c, const double* t_sec, size_t n, tloam_odom_stats* st);
@@ -576,7 +699,6 @@ inline const double* frame_scan(const tloam_ctx* c) { return c->deskew.active ? 
 // and searched by launches enqueued after the frame's last wait
 int place_frame_reserve(tloam_ctx* c, size_t n);
 void place_frame_end(tloam_ctx* c, bool accepted, int64_t frame, const double pose[16], const double* scan, size_t n);
-void place_empty(tloam_ctx* c);
 int voxel_down_sample_launch(tloam_ctx* c, const size_t n[2], const double voxel[2], int nseg, double* const out[2][3]);
 int build_grids_over(tloam_ctx* c, GridBuffers& G, const double radius[tl::kKinds], const CloudRef clouds[tl::kKinds],
                      tl::GridView out[tl::kKinds], const double (*known_boxes)[6] = nullptr,

@@ -63,6 +63,11 @@ class OdomConfig(C.Structure):
     _fields_ = [("seg", SegConfig), ("feature", FeatureConfig), ("submap", SubmapConfig), ("edge_down_sample", C.c_double)]
 
 
+def _int_fields(info):
+    """An info struct of integer fields as {name: int}."""
+    return {name: int(getattr(info, name)) for name, _ in info._fields_}
+
+
 class MapConfig(C.Structure):
     """tloam_map_config: mapping_flag (lidar_odometry.yaml:21), the map's voxel (front_end.cpp:272), the HBM reserved."""
     _fields_ = [("enabled", C.c_int32), ("reserved0", C.c_int32), ("voxel", C.c_double), ("reserve_points", C.c_int64)]
@@ -73,8 +78,7 @@ class MapInfo(C.Structure):
     _fields_ = [("n_points", C.c_int64), ("n_frames", C.c_int64), ("last_first", C.c_int64), ("last_count", C.c_int64),
                 ("capacity_points", C.c_int64), ("overflow_frames", C.c_int64)]
 
-    def as_dict(self):
-        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+    as_dict = _int_fields
 
 
 class VoxelMapConfig(C.Structure):
@@ -88,8 +92,7 @@ class VoxelMapInfo(C.Structure):
     _fields_ = [("n_voxels", C.c_int64), ("n_points", C.c_int64), ("n_frames", C.c_int64), ("last_new", C.c_int64),
                 ("capacity_voxels", C.c_int64), ("overflow_frames", C.c_int64)]
 
-    def as_dict(self):
-        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+    as_dict = _int_fields
 
 
 class DeskewConfig(C.Structure):
@@ -125,8 +128,7 @@ class PlaceInfo(C.Structure):
     _fields_ = [("n_keyframes", C.c_int64), ("n_loops", C.c_int64), ("last_keyframe_frame", C.c_int64),
                 ("capacity_keyframes", C.c_int64)]
 
-    def as_dict(self):
-        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+    as_dict = _int_fields
 
 
 class PlaceLoop(C.Structure):
@@ -357,14 +359,22 @@ def _colmajor(T):
     return np.ascontiguousarray(np.asarray(T, dtype=np.float64).T).reshape(-1)
 
 
-def default_config(**over) -> TlsConfig:
-    cfg = TlsConfig()
-    load_library().tloam_default_config(C.byref(cfg))
+def _strict_config(cls, default_fn, over, coerce=None):
+    """`cls` as the library's `default_fn` fills it, then the keyword overrides (passed through `coerce[name]` where it has
+    one); a name the struct does not have raises KeyError."""
+    cfg = cls()
+    getattr(load_library(), default_fn)(C.byref(cfg))
     for k, v in over.items():
         if not hasattr(cfg, k):
             raise KeyError(k)
+        if coerce and k in coerce:
+            v = coerce[k](v)
         setattr(cfg, k, v)
     return cfg
+
+
+def default_config(**over) -> TlsConfig:
+    return _strict_config(TlsConfig, "tloam_default_config", over)
 
 
 def shard_range(n, rank, nranks):
@@ -975,13 +985,7 @@ def default_feature_config(**over) -> FeatureConfig:
 
 
 def default_seg_config(**over) -> SegConfig:
-    cfg = SegConfig()
-    load_library().tloam_seg_default_config(C.byref(cfg))
-    for k, v in over.items():
-        if not hasattr(cfg, k):
-            raise KeyError(k)
-        setattr(cfg, k, v)
-    return cfg
+    return _strict_config(SegConfig, "tloam_seg_default_config", over)
 
 
 def default_odom_config(**over) -> OdomConfig:
@@ -1005,49 +1009,24 @@ def default_odom_config(**over) -> OdomConfig:
 
 def default_map_config(**over) -> MapConfig:
     """tloam_map_default_config (mapping off, voxel 1.0) with keyword overrides, e.g. enabled=1"""
-    cfg = MapConfig()
-    load_library().tloam_map_default_config(C.byref(cfg))
-    for k, v in over.items():
-        if not hasattr(cfg, k):
-            raise KeyError(k)
-        setattr(cfg, k, v)
-    return cfg
+    return _strict_config(MapConfig, "tloam_map_default_config", over)
 
 
 def default_voxel_map_config(**over) -> VoxelMapConfig:
     """tloam_voxel_map_default_config (off, voxel 1.0, origin 0) with keyword overrides, e.g. enabled=1, origin=(0, 0, 5)"""
-    cfg = VoxelMapConfig()
-    load_library().tloam_voxel_map_default_config(C.byref(cfg))
-    for k, v in over.items():
-        if not hasattr(cfg, k):
-            raise KeyError(k)
-        if k == "origin":
-            v = (C.c_double * 3)(*[float(x) for x in v])
-        setattr(cfg, k, v)
-    return cfg
+    return _strict_config(VoxelMapConfig, "tloam_voxel_map_default_config", over,
+                          {"origin": lambda v: (C.c_double * 3)(*[float(x) for x in v])})
 
 
 def default_deskew_config(**over) -> DeskewConfig:
     """tloam_deskew_default_config (off, azimuth mode, counter-clockwise, start 0, ref 0) with keyword overrides"""
-    cfg = DeskewConfig()
-    load_library().tloam_deskew_default_config(C.byref(cfg))
-    for k, v in over.items():
-        if not hasattr(cfg, k):
-            raise KeyError(k)
-        setattr(cfg, k, v)
-    return cfg
+    return _strict_config(DeskewConfig, "tloam_deskew_default_config", over)
 
 
 def default_place_config(**over) -> PlaceConfig:
     """tloam_place_default_config (off; 20 x 60 within 80 m, height offset 2; 10 candidates older than 50 keyframes, a loop
     below 0.30; a keyframe every 1 m or 0.2 rad) with keyword overrides"""
-    cfg = PlaceConfig()
-    load_library().tloam_place_default_config(C.byref(cfg))
-    for k, v in over.items():
-        if not hasattr(cfg, k):
-            raise KeyError(k)
-        setattr(cfg, k, v)
-    return cfg
+    return _strict_config(PlaceConfig, "tloam_place_default_config", over)
 
 
 def default_submap_config(**over) -> SubmapConfig:
