@@ -660,6 +660,74 @@ int tloam_place_describe(tloam_ctx* ctx, const tloam_place_config* cfg, const do
                          double* ring_key, double* sector_key);
 /* Every place recognition call on a context with nranks > 1: TLOAM_E_INVALID. */
 
+/* ---- loop verification: keyframe clouds and a two-stage TLS match (additive to ABI 8) ----------------
+ * Off by default; when off, every frame, stat, map, place record and launch is what it is without it.  With it on, every keyframe
+ * of the odometry frame also keeps eight clouds (AoS fp64, sensor frame) in one device arena: side 0, by kind, the four clouds its
+ * frame gave the match (none on the first frame), side 1 the four its frame gave the submap (planar / sphere selections, edge /
+ * ground: raw on the first frame, down-sampled later).  They are gathered by one launch after the frame's last wait; host_syncs
+ * and the byte counts of a frame do not change.  A verification of (query q, match m): the target clouds of keyframes
+ * [m - window, m + window] clamped to [0, q - 1], ascending, moved into m's frame by rigid_inverse(P_m) * P_k and put end to end
+ * per kind; the source is q's source clouds.  A coarse match (the `coarse` TLS configuration) from the initial guess, then a fine
+ * one (the context's own configuration) from its result, both on private child contexts: nothing of the context's registered
+ * clouds, grids or results changes.  Score: every source point moved by the fine pose, its nearest target of the same kind;
+ * inliers are those closer than inlier_dist, overlap = inliers / points, rmse = sqrt(sum d^2 / inliers).  Accepted when both
+ * matches return TLOAM_OK, overlap >= min_overlap and rmse <= max_rmse.  DESIGN.md 17. */
+typedef struct tloam_loop_config {
+  int32_t enabled;           /* 0 */
+  int32_t window;            /* 2: target keyframes m - window .. m + window (>= 0) */
+  int32_t init_mode;         /* 0: Rz(loop record's yaw), zero translation; 1: rigid_inverse(P_m) * P_q from the stored poses */
+  int32_t reserved0;
+  double inlier_dist;        /* m (measured) */
+  double min_overlap;        /* (measured) */
+  double max_rmse;           /* m (measured) */
+  int64_t reserve_points;    /* 0: the default arena (2^20 points); it doubles when full */
+  tloam_tls_config coarse;   /* the coarse stage's TLS configuration: the shipped one with wider distance thresholds */
+} tloam_loop_config;
+void tloam_loop_default_config(tloam_loop_config* cfg);
+/* cfg NULL: the defaults.  Empties the keyframe database, its clouds and the constraints (so does tloam_odometry_reset; the
+ * configuration persists across it).  Non-finite or non-positive inlier_dist / min_overlap / max_rmse, min_overlap > 1,
+ * window < 0, an unknown init_mode, enabled not 0 / 1, reserve_points < 0, a coarse configuration out of range:
+ * TLOAM_E_INVALID. */
+int tloam_loop_configure(tloam_ctx* ctx, const tloam_loop_config* cfg);
+
+typedef struct tloam_loop_info {
+  int64_t n_constraints;
+  int64_t n_accepted;
+  int64_t arena_points;      /* points the keyframe clouds take */
+  int64_t arena_capacity_points;
+} tloam_loop_info;
+int tloam_loop_get_info(tloam_ctx* ctx, tloam_loop_info* info);
+
+typedef struct tloam_loop_constraint {
+  int64_t query_keyframe, query_frame;
+  int64_t match_keyframe, match_frame;
+  int32_t status;            /* TLOAM_OK, the first failing stage's status, or TLOAM_E_NOT_READY (a side without clouds) */
+  int32_t accepted;
+  double rel_pose_colmajor[16];   /* match <- query: the fine stage's result */
+  double init_colmajor[16];       /* the initial guess of the coarse stage */
+  tloam_stats coarse, fine;
+  double overlap, rmse;
+  int64_t inliers, points;
+  double dist, yaw;          /* the loop record's (0 for a pair) */
+} tloam_loop_constraint;
+
+/* Keyframe clouds from the caller (for tloam_place_add_scan keyframes, or hosts with their own front end); verification must be
+ * on.  src / tgt: four clouds each by kind (AoS); a NULL side leaves that side as it is.  Keyframe out of range: TLOAM_E_INVALID. */
+int tloam_place_set_keyframe_clouds(tloam_ctx* ctx, int64_t keyframe, const double* const src_aos[4], const size_t n_src[4],
+                                    const double* const tgt_aos[4], const size_t n_tgt[4]);
+/* One stored cloud (side 0 source, 1 target; kind TLOAM_KIND_*).  *n is its size even when capacity is too small (then nothing is
+ * copied and TLOAM_E_INVALID is returned).  out may be NULL to ask for the size. */
+int tloam_place_read_keyframe_clouds(tloam_ctx* ctx, int64_t keyframe, int side, int kind, size_t capacity, size_t* n,
+                                     double* out_aos);
+/* Verifies, in order, every loop record not verified yet, and appends one constraint each; *n_verified (may be NULL): how many. */
+int tloam_loop_verify_pending(tloam_ctx* ctx, int64_t* n_verified);
+/* One pair (0 <= match < query < keyframes) from the caller's initial guess (NULL: rigid_inverse(P_m) * P_q); not appended. */
+int tloam_loop_verify_pair(tloam_ctx* ctx, int64_t query, int64_t match, const double init_colmajor_or_null[16],
+                           tloam_loop_constraint* out);
+/* Constraints [first, first + count). */
+int tloam_loop_read_constraints(tloam_ctx* ctx, size_t first, size_t count, tloam_loop_constraint* out);
+/* Every loop verification call on a context with nranks > 1: TLOAM_E_INVALID. */
+
 /* ---- multi-GPU: correspondence set sharded over ranks, one all-reduce per sweep --------
  * (nothing in the reference).  Call before set_source / set_correspondences.
  * (a) native RCCL over xGMI: unique_id = the 128 bytes of an ncclUniqueId made on rank 0

@@ -1,0 +1,87 @@
+"""numpy restatement of loop verification's host and device arithmetic: the target window, T_rel in the
+operation order of tl_api_odom.hip's mat_mul / rigid_inverse, the assembly's point transform, and the score."""
+import numpy as np
+
+
+def window(q, m, w):
+    """target keyframes of (q, m): [m - w, m + w] clamped to [0, q - 1], ascending"""
+    return list(range(max(m - w, 0), min(m + w, q - 1) + 1))
+
+
+def mat_mul(A, B):
+    """4x4 product, each entry ((a0 b0 + a1 b1) + a2 b2) + a3 b3"""
+    A, B = np.asarray(A, float), np.asarray(B, float)
+    r = np.zeros((4, 4))
+    for i in range(4):
+        for j in range(4):
+            r[i, j] = ((A[i, 0] * B[0, j] + A[i, 1] * B[1, j]) + A[i, 2] * B[2, j]) + A[i, 3] * B[3, j]
+    return r
+
+
+def rigid_inverse(T):
+    """(R^T, -R^T t), each entry of -R^T t summed in index order"""
+    T = np.asarray(T, float)
+    r = np.eye(4)
+    r[:3, :3] = T[:3, :3].T
+    for i in range(3):
+        r[i, 3] = -((T[0, i] * T[0, 3] + T[1, i] * T[1, 3]) + T[2, i] * T[2, 3])
+    return r
+
+
+def t_rel(P_m, P_k):
+    return mat_mul(rigid_inverse(P_m), P_k)
+
+
+def move(T, xyz):
+    """x' = ((R00 x + R01 y) + R02 z) + t0 per axis, as k_loop_assemble / k_loop_score round it"""
+    T = np.asarray(T, float)
+    p = np.asarray(xyz, float).reshape(-1, 3)
+    x, y, z = p[:, 0], p[:, 1], p[:, 2]
+    out = np.empty_like(p)
+    for i in range(3):
+        out[:, i] = ((T[i, 0] * x + T[i, 1] * y) + T[i, 2] * z) + T[i, 3]
+    return out
+
+
+def assemble(q, m, w, poses, tgt):
+    """(the target clouds by kind, in m's frame): tgt[k][kind] the stored target clouds of keyframe k"""
+    ks = window(q, m, w)
+    out = []
+    for kind in range(4):
+        parts = [move(t_rel(poses[m], poses[k]), tgt[k][kind]) for k in ks if len(tgt[k][kind])]
+        out.append(np.concatenate(parts) if parts else np.zeros((0, 3)))
+    return out
+
+
+def nearest_d2(q, t):
+    """squared distance of every query to its nearest target, d0 d0 + d1 d1 + d2 d2 in that order (inf without targets)"""
+    if len(t) == 0:
+        return np.full(len(q), np.inf)
+    best = np.full(len(q), np.inf)
+    for s in range(0, len(t), 2048):
+        c = t[s:s + 2048]
+        d0 = q[:, None, 0] - c[None, :, 0]
+        d1 = q[:, None, 1] - c[None, :, 1]
+        d2 = q[:, None, 2] - c[None, :, 2]
+        r = d0 * d0
+        r = r + d1 * d1
+        r = r + d2 * d2
+        best = np.minimum(best, r.min(axis=1))
+    return best
+
+
+def score(src, tgt, T, inlier_dist):
+    """(overlap, rmse, inliers, points): every source point moved by T, an inlier when its nearest target of the same kind is
+    closer than inlier_dist"""
+    r2 = inlier_dist * inlier_dist
+    inl, ss, pts = 0, 0.0, 0
+    for kind in range(4):
+        p = move(T, src[kind])
+        d = nearest_d2(p, np.asarray(tgt[kind], float).reshape(-1, 3)) if len(p) else np.zeros(0)
+        keep = d < r2
+        inl += int(keep.sum())
+        ss += float(d[keep].sum())
+        pts += len(p)
+    overlap = inl / pts if pts else 0.0
+    rmse = np.sqrt(ss / inl) if inl else np.inf
+    return overlap, rmse, inl, pts

@@ -460,9 +460,17 @@ int tloam_set_target_frame(tloam_ctx* c, const double* const xyz[4], const size_
   for (int k = 0; k < kKinds; ++k)   // (refused as a whole, before any of the registered targets has been replaced)
     if ((n[k] > 0 && !xyz[k]) || n[k] > kMaxPoints) return TLOAM_E_INVALID;
   HIPC(c, hipSetDevice(c->device));
+  return tlh::set_target_frame_from(c, xyz, n, hipMemcpyHostToDevice);
+}
+}  // extern "C"
+
+namespace tlh {
+// tloam_set_target_frame of four clouds on the host (hipMemcpyHostToDevice) or already on this device (hipMemcpyDeviceToDevice:
+// loop verification's assembled targets, tl_api_loop.hip)
+int set_target_frame_from(tloam_ctx* c, const double* const xyz[4], const size_t n[4], hipMemcpyKind from) {
   int rc = TLOAM_OK;
   // four copies, then ONE launch that converts all four clouds and takes their bounds (rows into pinned memory)
-  for (int k = 0; k < kKinds && rc == TLOAM_OK; ++k) rc = set_target_async(c, k, xyz[k], n[k], /*convert=*/false);
+  for (int k = 0; k < kKinds && rc == TLOAM_OK; ++k) rc = set_target_async(c, k, xyz[k], n[k], /*convert=*/false, from);
   if (rc == TLOAM_OK) {
     IngestArgs A;
     for (int k = 0; k < kKinds; ++k) {
@@ -496,6 +504,9 @@ int tloam_set_target_frame(tloam_ctx* c, const double* const xyz[4], const size_
   }
   return rc;
 }
+}  // namespace tlh
+
+extern "C" {
 
 // ---- frames staged ahead of their solve ------------------------------------------------------------
 int tloam_frame_stash(tloam_ctx* c, int slot) {

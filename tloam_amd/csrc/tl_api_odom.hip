@@ -44,6 +44,12 @@ GatherJob aos_rows(const double* src, int src_n, double* dst, int n, const int* 
   J.n = n; J.n1 = n1; J.src_n = src_n;
   return J;
 }
+LoopSpan span(const double* src, size_t n, const int* idx = nullptr) {   // a cloud the frame hands on, for the keyframe clouds
+  LoopSpan L;
+  memset(&L, 0, sizeof(L));
+  L.src = src; L.idx = idx; L.n = (long long)n;
+  return L;
+}
 GatherJob soa_rows(const double* sx, const double* sy, const double* sz, int n, double* dst) {   // SoA -> AoS, row for row
   GatherJob J;
   J.sx = sx; J.sy = sy; J.sz = sz; J.ss = 1;
@@ -163,6 +169,13 @@ int odometry_frame_body(tloam_ctx* c, const double* xyz, const double* t_sec, si
   st->n_planar_scan = (int64_t)nps; st->n_sphere_scan = (int64_t)nss;
   const int* pidx = reinterpret_cast<const int*>(F.out.p + np + ns);   // FeatRankOut: the planar list's point indices
 
+  {   // ---- loop verification on: room in the keyframe cloud arena for this frame's eight clouds (tl_api_place.hip)
+    const size_t ne_ds = first ? 0 : (size_t)cnt[4], ng_ds = first ? 0 : (size_t)cnt[5];
+    const size_t n8[8] = {first ? 0 : nps, ng_ds, ne_ds, first ? 0 : nss, np, first ? ng : ng_ds, first ? ne : ne_ds, ns};
+    rc = place_clouds_reserve(c, n8);
+    if (rc != TLOAM_OK) return rc;
+  }
+
   if (first) {
     // ---- :283-304: the submap IS this scan -- raw edge (not down-sampled, :286), the selections; ground voxel'd inside
     if (np < kMinCloud || ns < kMinCloud) return TLOAM_E_TOO_FEW_POINTS;
@@ -177,6 +190,10 @@ int odometry_frame_body(tloam_ctx* c, const double* xyz, const double* t_sec, si
     G.j[2] = aos_rows(scan, (int)n, O.block.p + off[2], (int)ne, S.edge.p, (int)ne, nullptr);
     G.j[3] = aos_rows(scan, (int)n, O.block.p + off[3], (int)ng, S.ground.p, (int)ng, nullptr);
     launch_gather_lists(G, 4, c->stream);
+    const double* B = O.block.p;   // (the keyframe's target clouds: as submap_init_body receives them; no source clouds)
+    const LoopSpan kfc[8] = {span(nullptr, 0), span(nullptr, 0), span(nullptr, 0), span(nullptr, 0),
+                             span(B + off[0], np), span(B + off[3], ng), span(B + off[2], ne), span(B + off[1], ns)};
+    place_clouds_note(c, kfc);
     rc = submap_init_body(c, cfg.submap, O.block.p + off[0], np, O.block.p + off[1], ns, O.block.p + off[2], ne,
                           O.block.p + off[3], ng, hipMemcpyDeviceToDevice);
     if (rc != TLOAM_OK) return rc;
@@ -221,6 +238,14 @@ int odometry_frame_body(tloam_ctx* c, const double* xyz, const double* t_sec, si
     launch_gather_lists(G, 7, c->stream);
   }
   source_frame_commit(c, true, soff);
+  {   // the keyframe's clouds: the source frame, and the submap update's (its block; the sphere selection gathered by rank)
+    const double* sp = c->src_pack.p;
+    const double* B = O.block.p;   // (swapped into the planar ring by the update: the storage itself stays)
+    const LoopSpan kfc[8] = {span(sp + soff[0], nps), span(sp + soff[1], ng_ds), span(sp + soff[2], ne_ds), span(sp + soff[3], nss),
+                             span(B + roff[0], np), span(B + roff[2], ng_ds), span(B + roff[1], ne_ds),
+                             span(scan, ns, S.general.p)};
+    place_clouds_note(c, kfc);
+  }
 
   // ---- scanMatching from the constant-velocity prediction (:321, :329-332)
   memset(&st->match, 0, sizeof(st->match));
@@ -278,7 +303,8 @@ int tloam_odometry_reset(tloam_ctx* c, const tloam_odom_config* cfg, const doubl
   O.reg_valid = false;   // no registered scan before the first frame
   c->map.clear();                // the global map starts again; its configuration stays
   c->vmap.clear();               // the merged voxel map too
-  c->place.clear(c->stream);     // and the keyframe database (its configuration stays)
+  c->place.clear(c->stream);     // and the keyframe database (its configuration stays), with its clouds
+  c->loop.clear();               // and the verified constraints (likewise)
   c->deskew.clear();             // (its configuration stays too)
   return TLOAM_OK;
 }

@@ -89,6 +89,11 @@ void enqueue_keyframe(tloam_ctx* c, const double* scan, size_t n, const double p
   D.R = g.n_rings; D.S = g.n_sectors;
   D.max_radius = g.max_radius; D.height_offset = g.height_offset;
   launch_place_describe(D, c->stream);
+  PlaceState::Keyframe K;
+  memset(&K, 0, sizeof(K));
+  K.frame = frame;
+  memcpy(K.pose, pose, sizeof(K.pose));
+  P.kf.push_back(K);
   const long long m = (long long)q - g.exclude_recent + 1;   // keyframes 0 .. q - exclude_recent
   if (m > 0) {
     PlaceSearchArgs A;
@@ -145,6 +150,7 @@ namespace tlh {
 // undone
 int place_frame_reserve(tloam_ctx* c, size_t n) {
   PlaceState& P = c->place;
+  P.pend.nspan = 0;
   if (!P.cfg.enabled) return TLOAM_OK;
   if (P.in_flight && (c->seg.aos.cap < 3 * n || (c->deskew.cfg.enabled && c->deskew.aos.cap < 3 * n)))
     HIPC(c, hipStreamSynchronize(c->stream));   // (the last keyframe's launches read the scan buffer this frame regrows)
@@ -162,6 +168,54 @@ void place_frame_end(tloam_ctx* c, bool accepted, int64_t frame, const double po
   if (P.n_kf > 0 && !moved(P.last_pose, pose, P.cfg.kf_dist, P.cfg.kf_angle)) return;
   enqueue_keyframe(c, scan, n, pose, frame);
   P.in_flight = true;
+  if (P.pend.nspan != 8) return;
+  // loop verification on: the frame's eight clouds into the arena (room was made at the frame's reserve), ONE launch behind the
+  // place launches, reading buffers the next frame rewrites only after its first wait
+  PlaceState::Keyframe& K = P.kf.back();
+  for (int j = 0; j < 8; ++j) {
+    K.off[j] = P.arena_used + 3 * (size_t)P.pend.start[j];
+    K.n[j] = (size_t)(P.pend.start[j + 1] - P.pend.start[j]);
+    P.pend.s[j].dst = P.arena.p + K.off[j];
+  }
+  launch_place_clouds(P.pend, c->stream);
+  P.arena_used += 3 * (size_t)P.pend.start[8];
+  P.pend.nspan = 0;
+}
+
+bool place_clouds_on(const tloam_ctx* c) { return c->place.cfg.enabled && c->loop.cfg.enabled; }
+
+// the arena holds arena_used + need doubles: new storage of max(that, 2 cap), the clouds so far copied device to device behind
+// whatever is in flight, the old storage retired until the stream has drained.  A failure leaves the arena as it was
+int arena_grow(tloam_ctx* c, size_t need) {
+  PlaceState& P = c->place;
+  if (P.arena_used + need <= P.arena.cap) return TLOAM_OK;
+  const int64_t rp = c->loop.cfg.reserve_points;
+  const size_t first = 3 * (rp > 0 ? (size_t)rp : ((size_t)1 << 20));
+  const size_t want = std::max(P.arena_used + need, P.arena.cap ? 2 * P.arena.cap : first);
+  Grower g(c, P.retired);
+  g.add(P.arena, want, P.arena_used);
+  return g.commit("keyframe cloud arena growth: ");
+}
+
+// after the frame's wait 3 (the sizes are on the host, nothing waits): room for the frame's eight clouds, should it be a keyframe
+int place_clouds_reserve(tloam_ctx* c, const size_t n[8]) {
+  if (!place_clouds_on(c)) return TLOAM_OK;
+  size_t all = 0;
+  for (int j = 0; j < 8; ++j) all += 3 * n[j];
+  return arena_grow(c, all);
+}
+
+// the frame's eight spans (dst filled in at the commit); rows counted from the first span's
+void place_clouds_note(tloam_ctx* c, const LoopSpan spans[8]) {
+  if (!place_clouds_on(c)) return;
+  LoopSpanArgs& A = c->place.pend;
+  A.start[0] = 0;
+  for (int j = 0; j < 8; ++j) {
+    A.s[j] = spans[j];
+    A.s[j].rigid = 0;
+    A.start[j + 1] = A.start[j] + spans[j].n;
+  }
+  A.nspan = 8;
 }
 
 }  // namespace tlh
@@ -193,6 +247,7 @@ int tloam_place_configure(tloam_ctx* c, const tloam_place_config* cfg) {
   HIPC(c, hipStreamSynchronize(c->stream));
   PlaceState& P = c->place;
   P.release();   // (empty: a new layout, or off -- the frame's memory is then what it was without place recognition)
+  c->loop.clear();   // (the constraints name keyframes that are gone)
   P.cfg = want;
   if (!want.enabled) return TLOAM_OK;
   const int rc = place_alloc(c, want.reserve_keyframes > 0 ? (size_t)want.reserve_keyframes : kPlaceDefaultReserve);

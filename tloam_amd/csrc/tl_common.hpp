@@ -673,6 +673,36 @@ struct PlaceSearchArgs {
 };
 void launch_place_search(const PlaceSearchArgs& A, hipStream_t s);   // k_place_rank, k_place_shift, k_place_pick
 
+// ---- loop verification: keyframe clouds, the local target, the score (tl_loop.hip) ------------------
+constexpr int kLoopSpans = 16;    // spans per launch of k_place_clouds / k_loop_assemble
+struct LoopSpan {
+  const double* src;              // AoS xyz; rows idx[i] of it when idx is set, else rows i
+  const int* idx;
+  double* dst;                    // AoS xyz [3n]
+  long long n;
+  int rigid;                      // 1: x' = ((R00 x + R01 y) + R02 z) + t0 per axis; 0: the bytes as they are
+  int reserved0;
+  double R[9], t[3];              // row-major rotation, translation
+};
+struct LoopSpanArgs {
+  LoopSpan s[kLoopSpans];
+  long long start[kLoopSpans + 1];   // rows before span j (start[nspan] = all rows)
+  int nspan;
+};
+void launch_place_clouds(const LoopSpanArgs& A, hipStream_t s);    // k_place_clouds: a keyframe's eight clouds into the arena
+void launch_loop_assemble(const LoopSpanArgs& A, hipStream_t s);   // k_loop_assemble: a verification's source and target
+constexpr int kLoopScoreBlocks = 256;
+struct LoopScoreArgs {
+  const double* src[kKinds];      // the source clouds, AoS
+  long long n[kKinds];
+  GridView g[kKinds];             // the fine stage's grids over the target clouds (g.n == 0: no target of the kind)
+  int reach[kKinds];              // cells walked around the query's: ceil(inlier_dist / cell)
+  double R[9], t[3];              // the fine pose
+  double r2;                      // inlier_dist^2: a point is an inlier when its nearest target is closer
+  double* partial;                // [kLoopScoreBlocks][kKinds][2]: inliers, sum of their squared distances
+};
+void launch_loop_score(const LoopScoreArgs& A, hipStream_t s);
+
 // ---- PCA feature extraction (tl_feature.hip; feature_extract.cpp:47-197) -----------------------
 struct FeatArgs {
   GridView g;                 // grid over the cloud itself (cell >= radius)

@@ -350,17 +350,47 @@ struct PlaceState {
   int64_t last_kf_frame = -1;
   double last_pose[16];            // the last keyframe's pose (n_kf > 0)
   bool in_flight = false;          // a frame's place launches may still be reading its scan
+  // loop verification on (tl_api_loop.hip): every keyframe's eight clouds in one arena (AoS, grown by
+  // doubling through Grower, the old storage into `retired`), and the host's table of the keyframes -- frame number, pose, and
+  // (offset, count) of each cloud -- so that nothing about them has to be read back
+  struct Keyframe {
+    int64_t frame;
+    double pose[16];
+    size_t off[8], n[8];   // [side * 4 + kind]: side 0 the source clouds, 1 the target clouds; off in doubles
+  };
+  std::vector<Keyframe> kf;        // [n_kf], kept whether or not verification is on
+  DBuf<double> arena;
+  size_t arena_used = 0;           // doubles
+  tl::LoopSpanArgs pend;           // the frame in flight's eight spans (pend.nspan 0: none), committed with its keyframe
   void clear(hipStream_t s) {   // the run's keyframes and loops go; the configuration and storage stay
     n_kf = 0;
     last_kf_frame = -1;
+    kf.clear();
+    arena_used = 0;
+    pend.nspan = 0;
     if (ctl.p) (void)hipMemsetAsync(ctl.p, 0, sizeof(unsigned long long), s);   // (behind whatever is in flight)
   }
   void release() {
     desc.release(); rkey.release(); skey.release(); pose.release(); kdist.release(); frame.release(); taken.release();
     loops.release(); retired.release(); bins.release(); ctl.release(); cand.release();
     s_aos.release(); s_desc.release(); s_rkey.release(); s_skey.release();
+    arena.release(); kf.clear(); arena_used = 0; pend.nspan = 0;
     cap = 0; n_kf = 0; last_kf_frame = -1; in_flight = false;
   }
+};
+
+// loop verification (tl_api_loop.hip): its configuration, the two private child contexts of the coarse and
+// the fine stage (created lazily, on the parent's device), the verified constraints, the next loop record to verify, scratch
+struct LoopState {
+  tloam_loop_config cfg{};   // (zero: off)
+  bool cfg_set = false;            // tloam_loop_configure has been called (else tloam_loop_default_config's, off)
+  tloam_ctx* coarse = nullptr;
+  tloam_ctx* fine = nullptr;
+  std::vector<tloam_loop_constraint> out;
+  size_t next_record = 0;
+  DBuf<double> tgt, partial;       // the assembled targets (per kind, end to end), the score's block partials
+  double* h_partial = nullptr;     // pinned mirror of `partial`
+  void clear() { out.clear(); next_record = 0; }
 };
 
 // up to four SoA clouds (x, y, z, n) a search grid is built over -- the registered targets, or any other cloud
@@ -379,6 +409,7 @@ struct tloam_ctx {
   VmapState vmap;
   DeskewState deskew;
   PlaceState place;
+  LoopState loop;
   int device = 0;
   hipStream_t stream = nullptr;
   KindData kd[kKinds];
@@ -699,6 +730,14 @@ inline const double* frame_scan(const tloam_ctx* c) { return c->deskew.active ? 
 // and searched by launches enqueued after the frame's last wait
 int place_frame_reserve(tloam_ctx* c, size_t n);
 void place_frame_end(tloam_ctx* c, bool accepted, int64_t frame, const double pose[16], const double* scan, size_t n);
+// loop verification on: room in the keyframe cloud arena for the frame's eight clouds (after the frame's wait 3: nothing is
+// waited for), then the eight spans noted for place_frame_end's k_place_clouds (spans 0-3 the source kinds, 4-7 the target kinds)
+bool place_clouds_on(const tloam_ctx* c);
+int place_clouds_reserve(tloam_ctx* c, const size_t n[8]);
+void place_clouds_note(tloam_ctx* c, const tl::LoopSpan spans[8]);
+int arena_grow(tloam_ctx* c, size_t need_doubles);   // (tl_api_place.hip) the arena holds arena_used + need doubles
+void loop_release(tloam_ctx* c);                      // (tl_api_loop.hip) at destroy: the child contexts, the scratch
+int set_target_frame_from(tloam_ctx* c, const double* const xyz[4], const size_t n[4], hipMemcpyKind from);   // tl_api_frames.hip
 int voxel_down_sample_launch(tloam_ctx* c, const size_t n[2], const double voxel[2], int nseg, double* const out[2][3]);
 int build_grids_over(tloam_ctx* c, GridBuffers& G, const double radius[tl::kKinds], const CloudRef clouds[tl::kKinds],
                      tl::GridView out[tl::kKinds], const double (*known_boxes)[6] = nullptr,

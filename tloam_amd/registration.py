@@ -142,6 +142,14 @@ class PlaceLoop(C.Structure):
                 "match_frame": int(self.match_frame), "shift": int(self.shift), "d": float(self.dist), "yaw": float(self.yaw)}
 
 
+class LoopInfo(C.Structure):
+    """tloam_loop_info."""
+    _fields_ = [("n_constraints", C.c_int64), ("n_accepted", C.c_int64), ("arena_points", C.c_int64),
+                ("arena_capacity_points", C.c_int64)]
+
+    as_dict = _int_fields
+
+
 class TlsConfig(C.Structure):
     """tloam_tls_config: the 16 keys of the `TLS:` block (config/mapping/lidar_odometry.yaml:23-39)."""
     _fields_ = [
@@ -155,6 +163,15 @@ class TlsConfig(C.Structure):
         ("cost_threshold", C.c_double), ("gnc_factor", C.c_double),
         ("noise_bound", C.c_double), ("fitness_thres", C.c_double),
     ]
+
+
+class LoopConfig(C.Structure):
+    """tloam_loop_config: loop verification's switch, the target window around the match keyframe, the initial guess (0: the
+    loop record's yaw, 1: the stored poses), the score's inlier distance and the acceptance bounds, the arena reserved, and the
+    coarse stage's TLS configuration."""
+    _fields_ = [("enabled", C.c_int32), ("window", C.c_int32), ("init_mode", C.c_int32), ("reserved0", C.c_int32),
+                ("inlier_dist", C.c_double), ("min_overlap", C.c_double), ("max_rmse", C.c_double),
+                ("reserve_points", C.c_int64), ("coarse", TlsConfig)]
 
 
 class CtxInfo(C.Structure):
@@ -185,6 +202,24 @@ class Stats(C.Structure):
                 "bad_weights": self.weight_range_violations, "kind_cost": self.kind_cost[:], "mu": self.mu,
                 "solver_cost": self.solver_cost, "se3": np.frombuffer(self.se3, dtype=np.float64).copy(),
                 "gn_sweeps": self.gn_sweeps, "host_wait_us": self.host_wait_us}
+
+
+class LoopConstraint(C.Structure):
+    """tloam_loop_constraint: one verified pair."""
+    _fields_ = [("query_keyframe", C.c_int64), ("query_frame", C.c_int64), ("match_keyframe", C.c_int64),
+                ("match_frame", C.c_int64), ("status", C.c_int32), ("accepted", C.c_int32),
+                ("rel_pose_colmajor", C.c_double * 16), ("init_colmajor", C.c_double * 16), ("coarse", Stats), ("fine", Stats),
+                ("overlap", C.c_double), ("rmse", C.c_double), ("inliers", C.c_int64), ("points", C.c_int64),
+                ("dist", C.c_double), ("yaw", C.c_double)]
+
+    def as_dict(self):
+        return {"query": int(self.query_keyframe), "query_frame": int(self.query_frame), "match": int(self.match_keyframe),
+                "match_frame": int(self.match_frame), "status": int(self.status), "accepted": bool(self.accepted),
+                "rel_pose": np.array(self.rel_pose_colmajor[:]).reshape(4, 4).T.copy(),
+                "init": np.array(self.init_colmajor[:]).reshape(4, 4).T.copy(),
+                "coarse": self.coarse.as_dict(), "fine": self.fine.as_dict(), "overlap": float(self.overlap),
+                "rmse": float(self.rmse), "inliers": int(self.inliers), "points": int(self.points), "d": float(self.dist),
+                "yaw": float(self.yaw)}
 
 
 class OdomStats(C.Structure):
@@ -299,6 +334,15 @@ def load_library():
         "tloam_place_read_loops": (C.c_int, [vp, sz, sz, C.POINTER(PlaceLoop)]),
         "tloam_place_add_scan": (C.c_int, [vp, dp, sz, dp, C.c_int64, C.POINTER(C.c_int64)]),
         "tloam_place_describe": (C.c_int, [vp, C.POINTER(PlaceConfig), dp, sz, dp, dp, dp]),
+        "tloam_loop_default_config": (None, [C.POINTER(LoopConfig)]),
+        "tloam_loop_configure": (C.c_int, [vp, C.POINTER(LoopConfig)]),
+        "tloam_loop_get_info": (C.c_int, [vp, C.POINTER(LoopInfo)]),
+        "tloam_place_set_keyframe_clouds": (C.c_int, [vp, C.c_int64, C.POINTER(dp), C.POINTER(sz), C.POINTER(dp),
+                                                      C.POINTER(sz)]),
+        "tloam_place_read_keyframe_clouds": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, sz, C.POINTER(sz), dp]),
+        "tloam_loop_verify_pending": (C.c_int, [vp, C.POINTER(C.c_int64)]),
+        "tloam_loop_verify_pair": (C.c_int, [vp, C.c_int64, C.c_int64, dp, C.POINTER(LoopConstraint)]),
+        "tloam_loop_read_constraints": (C.c_int, [vp, sz, sz, C.POINTER(LoopConstraint)]),
         "tloam_rccl_unique_id": (C.c_int, [vp]),
         "tloam_comm_init_rccl": (C.c_int, [vp, C.c_int, C.c_int, vp]),
         "tloam_comm_init_callback": (C.c_int, [vp, C.c_int, C.c_int, ALLREDUCE_FN, vp]),
@@ -333,7 +377,9 @@ EXPORTED_SYMBOLS = (
     "tloam_voxel_map_get_info", "tloam_voxel_map_read", "tloam_voxel_map_read_box", "tloam_deskew_default_config",
     "tloam_deskew_configure", "tloam_deskew_get_info", "tloam_odometry_frame_timed", "tloam_deskew_scan", "tloam_place_default_config",
     "tloam_place_configure", "tloam_place_get_info", "tloam_place_read_keyframes", "tloam_place_read_loops", "tloam_place_add_scan",
-    "tloam_place_describe", "tloam_rccl_unique_id", "tloam_comm_init_rccl",
+    "tloam_place_describe", "tloam_loop_default_config", "tloam_loop_configure", "tloam_loop_get_info",
+    "tloam_place_set_keyframe_clouds", "tloam_place_read_keyframe_clouds", "tloam_loop_verify_pending", "tloam_loop_verify_pair",
+    "tloam_loop_read_constraints", "tloam_rccl_unique_id", "tloam_comm_init_rccl",
     "tloam_comm_mailbox_export", "tloam_comm_init_mailbox",
     "tloam_comm_init_callback", "tloam_shard_range", "tloam_shard_ranges_frame", "tloam_se3_exp", "tloam_se3_log", "tloam_se3_plus",
 )
@@ -813,6 +859,69 @@ class HipRegistration:
         self._check(self.L.tloam_place_read_loops(self.h, int(first), m, buf), "tloam_place_read_loops")
         return [buf[i].as_dict() for i in range(m)]
 
+    # ---- loop verification: keyframe clouds and a two-stage TLS match
+    def loop_configure(self, cfg: LoopConfig | None = None, **over):
+        """loop verification on / off (default_loop_config(**over) when cfg is None); empties the keyframe database, its clouds
+        and the constraints.  Kept across odometry_reset (which empties them too)."""
+        cfg = cfg if cfg is not None else default_loop_config(**over)
+        self._check(self.L.tloam_loop_configure(self.h, C.byref(cfg)), "tloam_loop_configure")
+
+    def loop_info(self) -> dict:
+        """constraints, accepted ones, the points the keyframe clouds take and the arena's capacity"""
+        info = LoopInfo()
+        self._check(self.L.tloam_loop_get_info(self.h, C.byref(info)), "tloam_loop_get_info")
+        return info.as_dict()
+
+    def place_set_keyframe_clouds(self, keyframe, src=None, tgt=None):
+        """a keyframe's clouds from the caller: src / tgt are four (n, 3) clouds by kind, or None to leave that side"""
+        def side(clouds):
+            if clouds is None:
+                return None, None, []
+            a = [_aos(x) for x in clouds]
+            assert len(a) == 4
+            return (dp * 4)(*[_dp(x) for x in a]), (C.c_size_t * 4)(*[len(x) for x in a]), a
+        dp = C.POINTER(C.c_double)
+        sp, sn, keep_s = side(src)
+        tp, tn, keep_t = side(tgt)
+        self._check(self.L.tloam_place_set_keyframe_clouds(self.h, int(keyframe), sp, sn, tp, tn),
+                    "tloam_place_set_keyframe_clouds")
+        del keep_s, keep_t
+
+    def place_read_keyframe_clouds(self, keyframe, side=None, kind=None):
+        """one stored cloud (side 0 source / 1 target, kind TLOAM_KIND_*) as (n, 3); side None: [[4 source], [4 target]]"""
+        if side is None:
+            return [[self.place_read_keyframe_clouds(keyframe, s, k) for k in range(4)] for s in range(2)]
+        n = C.c_size_t(0)
+        self._check(self.L.tloam_place_read_keyframe_clouds(self.h, int(keyframe), int(side), int(kind), 0, C.byref(n), None),
+                    "tloam_place_read_keyframe_clouds")
+        out = np.zeros((max(n.value, 1), 3))
+        self._check(self.L.tloam_place_read_keyframe_clouds(self.h, int(keyframe), int(side), int(kind), n.value, C.byref(n),
+                                                            _dp(out)), "tloam_place_read_keyframe_clouds")
+        return out[: n.value].copy()
+
+    def loop_verify_pending(self) -> int:
+        """verifies every loop record not verified yet (one constraint each) -> how many"""
+        n = C.c_int64(0)
+        self._check(self.L.tloam_loop_verify_pending(self.h, C.byref(n)), "tloam_loop_verify_pending")
+        return int(n.value)
+
+    def loop_verify_pair(self, query, match, init=None) -> dict:
+        """one pair from the caller's initial guess (4x4; None: rigid_inverse(P_m) P_q); not appended"""
+        out = LoopConstraint()
+        M = None if init is None else _colmajor(init)
+        self._check(self.L.tloam_loop_verify_pair(self.h, int(query), int(match), _dp(M), C.byref(out)),
+                    "tloam_loop_verify_pair")
+        return out.as_dict()
+
+    def loop_constraints(self, first=0, count=None) -> list:
+        """constraints [first, first + count) as dicts"""
+        if count is None:
+            count = max(self.loop_info()["n_constraints"] - int(first), 0)
+        m = int(count)
+        buf = (LoopConstraint * max(m, 1))()
+        self._check(self.L.tloam_loop_read_constraints(self.h, int(first), m, buf), "tloam_loop_read_constraints")
+        return [buf[i].as_dict() for i in range(m)]
+
     def fitness(self):
         f, r = C.c_double(0), C.c_double(0)
         rc = self.L.tloam_fitness(self.h, C.byref(f), C.byref(r))
@@ -1027,6 +1136,20 @@ def default_place_config(**over) -> PlaceConfig:
     """tloam_place_default_config (off; 20 x 60 within 80 m, height offset 2; 10 candidates older than 50 keyframes, a loop
     below 0.30; a keyframe every 1 m or 0.2 rad) with keyword overrides"""
     return _strict_config(PlaceConfig, "tloam_place_default_config", over)
+
+
+def default_loop_config(**over) -> LoopConfig:
+    """tloam_loop_default_config (off; a window of 2, the loop record's yaw as the guess; the measured score bounds; the coarse
+    stage's TLS values) with keyword overrides; `coarse__<name>` sets a field of the coarse TLS configuration"""
+    flat = {k: v for k, v in over.items() if not k.startswith("coarse__")}
+    cfg = _strict_config(LoopConfig, "tloam_loop_default_config", flat)
+    for k, v in over.items():
+        if k.startswith("coarse__"):
+            name = k[len("coarse__"):]
+            if not hasattr(cfg.coarse, name):
+                raise KeyError(k)
+            setattr(cfg.coarse, name, v)
+    return cfg
 
 
 def default_submap_config(**over) -> SubmapConfig:

@@ -125,7 +125,7 @@ def _read_scan(path):
 
 
 def replay_device(H, scan_files, out_poses: str | None = None, odom_cfg=None, init_pose=None, max_frames=None,
-                  map_cfg=None, out_map: str | None = None, deskew_cfg=None, place_cfg=None):
+                  map_cfg=None, out_map: str | None = None, deskew_cfg=None, place_cfg=None, loop_cfg=None):
     """pipeline="device": one tloam_odometry_frame per scan.  Frames the device skips
     (TLOAM_E_TOO_FEW_POINTS) are left out of the poses and listed in the stats as `skipped` (their positions in
     `scan_files`); `frame_of_pose` gives each pose's position.
@@ -134,7 +134,9 @@ def replay_device(H, scan_files, out_poses: str | None = None, odom_cfg=None, in
     deskew_cfg (a DeskewConfig, azimuth mode: `.bin` scans carry no per-point times): the frames deskew their scans under the
     constant-velocity motion; the stats get its `deskew` info.
     place_cfg (a PlaceConfig): place recognition picks keyframes and searches them for loops; the
-    stats get its `place` info and the `loops` found (read once, after the last frame)."""
+    stats get its `place` info and the `loops` found (read once, after the last frame).
+    loop_cfg (a LoopConfig): the keyframes keep their clouds and the pending loops are verified once, after the last frame
+    (DESIGN.md section 17); the stats get its `loop` info and the `constraints`."""
     files = scan_files[: max_frames] if max_frames else scan_files
     if deskew_cfg is not None:
         if deskew_cfg.enabled and deskew_cfg.time_source != 0:
@@ -144,6 +146,8 @@ def replay_device(H, scan_files, out_poses: str | None = None, odom_cfg=None, in
         H.map_configure(map_cfg)
     if place_cfg is not None:
         H.place_configure(place_cfg)
+    if loop_cfg is not None:
+        H.loop_configure(loop_cfg)
     H.odometry_reset(init_pose, odom_cfg)
     poses, at, skipped, t_frame, iters = [], [], [], [], 0
     out = open(out_poses, "w") if out_poses else None
@@ -177,6 +181,11 @@ def replay_device(H, scan_files, out_poses: str | None = None, odom_cfg=None, in
     if place_cfg is not None:
         stats["place"] = H.place_info()
         stats["loops"] = H.place_loops() if place_cfg.enabled else []
+    if loop_cfg is not None:
+        if loop_cfg.enabled:
+            H.loop_verify_pending()
+        stats["loop"] = H.loop_info()
+        stats["constraints"] = H.loop_constraints()
     if map_cfg is not None:
         stats["map"] = H.map_info()
         if out_map:
