@@ -728,6 +728,74 @@ int tloam_loop_verify_pair(tloam_ctx* ctx, int64_t query, int64_t match, const d
 int tloam_loop_read_constraints(tloam_ctx* ctx, size_t first, size_t count, tloam_loop_constraint* out);
 /* Every loop verification call on a context with nranks > 1: TLOAM_E_INVALID. */
 
+/* ---- pose-graph optimisation of the keyframes (additive to ABI 8) -------------------------------------
+ * Runs only when called: with it never called, every frame, stat, map, place record, constraint and launch is what it is
+ * without it.  Nodes: N rigid poses P_0 .. P_{N-1}, node 0 fixed.  Edges (i, j, Z, w[6]): Z the measured rigid_inverse(P_i) * P_j,
+ * w six inverse variances in tangent order (upsilon, omega).  Edges 0 .. N-2 are the chain, edge k = (k, k + 1); the loops
+ * follow.  Residual e = log(rigid_inverse(Z) * rigid_inverse(P_i) * P_j), cost = sum w[a] e[a]^2, update P_n <- P_n * exp(d_n),
+ * Jacobians J_j = I, J_i = -Ad(rigid_inverse(P_j) * P_i).  Plain Gauss-Newton; each step's normal equations are solved by
+ * conjugate gradients preconditioned with the chain, matrix-free over the edges, in one launch.  An iteration ends the run when
+ * its new cost is not finite (the step is dropped), else when max |d| < step_tol (the step is kept), else when the new cost is
+ * above the previous one (the step is dropped), else after max_iterations.  Reductions have a fixed order: two runs give the
+ * same bits.  DESIGN.md 18. */
+typedef struct tloam_graph_config {
+  int32_t max_iterations;    /* 30, in [1, 1000]: Gauss-Newton iterations */
+  int32_t max_cg_iterations; /* 20000, in [1, 10^6]: conjugate-gradient iterations of one Gauss-Newton step */
+  double step_tol;           /* 1e-7 (>= 0, finite; below it the cost no longer resolves a step: DESIGN.md 18) */
+  double cg_tol;             /* 1e-10: a solve ends at r^T M^-1 r <= cg_tol^2 r_0^T M^-1 r_0 (>= 0, finite) */
+  double odom_sigma_t;       /* m   per keyframe step: 0.05 (margin unmeasured) */
+  double odom_sigma_r;       /* rad per keyframe step: 0.005 */
+  double loop_sigma_t;       /* m:   0.05 (section 17's measured worst case) */
+  double loop_sigma_r;       /* rad: 0.01 */
+} tloam_graph_config;
+void tloam_graph_default_config(tloam_graph_config* cfg);
+/* cfg NULL: the defaults.  Persists across tloam_odometry_reset.  Drops the corrected poses (so do tloam_odometry_reset,
+ * tloam_place_configure and tloam_loop_configure).  A count out of its range, a negative or non-finite tolerance, a non-finite
+ * or non-positive sigma: TLOAM_E_INVALID. */
+int tloam_graph_configure(tloam_ctx* ctx, const tloam_graph_config* cfg);
+
+typedef struct tloam_graph_edge {
+  int64_t i, j;
+  double rel_pose_colmajor[16];   /* Z: node j in node i's frame */
+  double weight[6];               /* inverse variances (upsilon, omega), >= 0; a chain edge's > 0 */
+} tloam_graph_edge;
+
+#define TLOAM_GRAPH_STOP_NOT_RUN 0    /* one node or no loop edge: the input poses are the result */
+#define TLOAM_GRAPH_STOP_STEP 1       /* max |d| < step_tol */
+#define TLOAM_GRAPH_STOP_ITERATIONS 2 /* max_iterations */
+#define TLOAM_GRAPH_STOP_COST 3       /* the new cost was not finite or above the previous one: that step was not applied */
+#define TLOAM_GRAPH_STOP_CG_LIMIT 4   /* as STEP or ITERATIONS, but the last step's linear solve ended on max_cg_iterations */
+typedef struct tloam_graph_info {
+  int64_t n_nodes, n_edges, n_loop_edges;
+  int32_t iterations;        /* Gauss-Newton iterations run */
+  int32_t stop_reason;       /* TLOAM_GRAPH_STOP_* */
+  int32_t reverted;          /* 1: the last step was dropped (stop_reason COST) */
+  int32_t reserved0;
+  int64_t cg_iterations;     /* all steps together */
+  double initial_cost, final_cost;
+  double last_step;          /* max |d| of the last step computed */
+  double last_cg_residual;   /* sqrt(r^T M^-1 r / r_0^T M^-1 r_0) at the end of the last solve */
+} tloam_graph_info;
+
+/* The caller's graph; touches nothing else in the context.  poses_in / poses_out: [16 n_nodes] column-major (may be the same
+ * storage).  cfg NULL: the context's configuration.  An index out of range, i == j, a chain that is not (k, k + 1) in order, a
+ * non-rigid or non-finite pose, a negative or non-finite weight, a chain weight of 0, n_nodes < 1: TLOAM_E_INVALID.  One node or
+ * no loop edge: the solver is not run, poses_out holds poses_in's bits.  Node 0's output is its input's bits.  info may be NULL. */
+int tloam_graph_solve(tloam_ctx* ctx, const tloam_graph_config* cfg, size_t n_nodes, const double* poses_in_colmajor, size_t n_edges,
+                      const tloam_graph_edge* edges, double* poses_out_colmajor, tloam_graph_info* info);
+/* The context's graph: nodes the keyframes' stored poses, chain edge k with Z = rigid_inverse(P_k) * P_{k+1} and the odometry
+ * weights (1 / sigma^2), one loop edge (match_keyframe, query_keyframe, rel_pose_colmajor) with the loop weights per constraint
+ * with accepted != 0, in their order.  Place recognition must be on (else TLOAM_E_INVALID).  Fewer than two keyframes or no
+ * accepted constraint: TLOAM_OK, corrected = stored.  Pending loop records are not verified here.  The stored keyframe poses,
+ * the odometry state and both maps are not changed.  info may be NULL. */
+int tloam_graph_optimize(tloam_ctx* ctx, tloam_graph_info* info);
+/* Corrected poses of keyframes [first, first + count), [16 count] column-major, as of the last tloam_graph_optimize
+ * (TLOAM_E_NOT_READY before it; keyframes added since are out of range: TLOAM_E_INVALID). */
+int tloam_graph_read_poses(tloam_ctx* ctx, size_t first, size_t count, double* poses_colmajor);
+/* P'_k * rigid_inverse(P_k) * pose_in for a pose taken near keyframe k (-1: the last corrected one), on the host. */
+int tloam_graph_correct_pose(tloam_ctx* ctx, int64_t keyframe, const double pose_in_colmajor[16], double pose_out_colmajor[16]);
+/* Every graph call on a context with nranks > 1: TLOAM_E_INVALID. */
+
 /* ---- multi-GPU: correspondence set sharded over ranks, one all-reduce per sweep --------
  * (nothing in the reference).  Call before set_source / set_correspondences.
  * (a) native RCCL over xGMI: unique_id = the 128 bytes of an ncclUniqueId made on rank 0

@@ -32,6 +32,7 @@ UNITS = [
     ("tl_deskew.hip", ["-ffp-contract=off"]),   # the deskew: sweep time, exp(s xi) and the point action as DESIGN.md 15 states
     ("tl_place.hip", ["-ffp-contract=off"]),    # place recognition: Scan Context bins, keys and shift distances as DESIGN.md 16 states
     ("tl_loop.hip", ["-ffp-contract=off"]),     # loop verification: the target's transform and the score's distances as DESIGN.md 17 states
+    ("tl_graph.hip", ["-ffp-contract=off"]),    # pose-graph optimisation: residuals, adjoints and sums as DESIGN.md 18 states
     # K3 / K5: no implicit contraction -- the same inlined residual code is compiled into several kernels (streaming sweep,
     # one-wave-per-chunk sweep, the one-launch Solve) and has to round alike in all of them (the tests compare those paths
     # bit for bit; with `fast` and with `on` the optimiser fused the same source line differently from kernel to kernel):
@@ -50,6 +51,7 @@ UNITS = [
     ("tl_api_deskew.hip", ["-ffp-contract=off"]),   # the deskew's configuration and xi = log(step), formed on the host
     ("tl_api_place.hip", ["-ffp-contract=off"]),    # place recognition's keyframe policy and database
     ("tl_api_loop.hip", ["-ffp-contract=off"]),     # loop verification: T_rel and the initial guesses formed on the host
+    ("tl_api_graph.hip", ["-ffp-contract=off"]),    # pose-graph optimisation: the chain's Z and the weights formed on the host
     ("tl_probe.hip", []),        # read-stream bandwidth probe (the on-box ceiling of the bench's roofline block)
 ]
 HEADERS = ["tl_common.hpp", "tl_se3.hpp", "tl_knn.hpp", "tl_walk.hpp", "tl_ctx.hpp", "tl_step.hpp", "tl_finish.hpp", "tl_prep.hpp", "tl_seg.hpp", os.path.join("..", "..", "include", "tloam_hip.h")]

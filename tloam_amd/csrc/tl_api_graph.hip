@@ -1,0 +1,295 @@
+// tl_api_graph.hip -- C ABI of the keyframe pose-graph optimisation (include/tloam_hip.h: tloam_graph_*; DESIGN.md section 18;
+// the kernel in tl_graph.hip).
+//
+// A solve checks the caller's graph, turns poses and measurements into (unit quaternion, translation) on the host -- the form the
+// device's exp / log / compose of tl_se3.hpp work on --, builds the table of every node's edge ends in edge order, uploads, and
+// runs one launch per Gauss-Newton iteration, reading one small record back after each: the host only decides whether to go on.
+// tloam_graph_optimize puts the context's graph together from the host's keyframe table and the verified constraints and runs the
+// same solve; nothing else in the context is read or written.
+#include <float.h>
+#include <math.h>
+
+#include "tl_ctx.hpp"
+
+using namespace tl;
+
+namespace {
+
+constexpr size_t kGraphMaxNodes = (size_t)1 << 22;   // rows and table entries are 32-bit integers: 12 * edges stays inside them
+constexpr size_t kGraphMaxEdges = (size_t)1 << 24;
+
+bool graph_config_ok(const tloam_graph_config& g) {
+  auto sigma = [](double v) { return v > 0.0 && v <= DBL_MAX; };
+  auto tol = [](double v) { return v >= 0.0 && v <= DBL_MAX; };
+  return g.max_iterations >= 1 && g.max_iterations <= 1000 && g.max_cg_iterations >= 1 && g.max_cg_iterations <= 1000000 &&
+         tol(g.step_tol) && tol(g.cg_tol) && sigma(g.odom_sigma_t) && sigma(g.odom_sigma_r) && sigma(g.loop_sigma_t) &&
+         sigma(g.loop_sigma_r);
+}
+
+// the operation order of tl_api_odom.hip's / tl_api_loop.hip's mat_mul and rigid_inverse (column-major 4x4): the chain's Z is
+// formed as loop verification forms its T_rel
+void mat_mul(const double A[16], const double B[16], double out[16]) {
+  double r[16];
+  for (int j = 0; j < 4; ++j)
+    for (int i = 0; i < 4; ++i) r[4 * j + i] = ((A[i] * B[4 * j] + A[4 + i] * B[4 * j + 1]) + A[8 + i] * B[4 * j + 2]) + A[12 + i] * B[4 * j + 3];
+  memcpy(out, r, sizeof(r));
+}
+void rigid_inverse(const double T[16], double out[16]) {
+  double r[16];
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) r[4 * j + i] = T[4 * i + j];
+    r[12 + i] = -((T[4 * i] * T[12] + T[4 * i + 1] * T[13]) + T[4 * i + 2] * T[14]);
+    r[4 * i + 3] = 0.0;
+  }
+  r[15] = 1.0;
+  memcpy(out, r, sizeof(r));
+}
+
+Pose pose_inverse(const Pose& T) {
+  Pose I;
+  I.qw = T.qw; I.qx = -T.qx; I.qy = -T.qy; I.qz = -T.qz;
+  const Vec3 t = rotate(I, Vec3{T.tx, T.ty, T.tz});
+  I.tx = -t.x; I.ty = -t.y; I.tz = -t.z;
+  return I;
+}
+
+void sigma_weights(double st, double sr, double w[6]) {
+  for (int a = 0; a < 6; ++a) w[a] = a < 3 ? 1.0 / (st * st) : 1.0 / (sr * sr);
+}
+
+// the checked solve behind tloam_graph_solve and tloam_graph_optimize
+int graph_solve(tloam_ctx* c, const tloam_graph_config& cfg, size_t n, const double* poses_in, size_t m, const tloam_graph_edge* edges,
+                double* poses_out, tloam_graph_info* info) {
+  if (n < 1 || n > kGraphMaxNodes || m > kGraphMaxEdges || !poses_in || !poses_out || m < n - 1 || (m > 0 && !edges))
+    return TLOAM_E_INVALID;
+  std::vector<Pose> P(n), Zinv(m);
+  for (size_t k = 0; k < n; ++k)
+    if (!pose_from_matrix(poses_in + 16 * k, &P[k])) return TLOAM_E_INVALID;
+  for (size_t e = 0; e < m; ++e) {
+    const tloam_graph_edge& E = edges[e];
+    if (e < n - 1 ? (E.i != (int64_t)e || E.j != (int64_t)e + 1) : (E.i < 0 || E.j < 0 || E.i >= (int64_t)n || E.j >= (int64_t)n || E.i == E.j))
+      return TLOAM_E_INVALID;
+    for (int a = 0; a < 6; ++a)
+      if (!(E.weight[a] >= 0.0 && E.weight[a] <= DBL_MAX) || (e < n - 1 && E.weight[a] == 0.0)) return TLOAM_E_INVALID;
+    Pose Z;
+    if (!pose_from_matrix(E.rel_pose_colmajor, &Z)) return TLOAM_E_INVALID;
+    Zinv[e] = pose_inverse(Z);
+  }
+  tloam_graph_info I;
+  memset(&I, 0, sizeof(I));
+  I.n_nodes = (int64_t)n;
+  I.n_edges = (int64_t)m;
+  I.n_loop_edges = (int64_t)(m - (n - 1));
+  I.stop_reason = TLOAM_GRAPH_STOP_NOT_RUN;
+  if (n < 2 || m == n - 1) {   // the chain alone carries no correction: the input's bits
+    memmove(poses_out, poses_in, sizeof(double) * 16 * n);
+    if (info) *info = I;
+    return TLOAM_OK;
+  }
+  // every node's edge ends, in edge order
+  std::vector<int> ints(2 * m + (n + 1) + 2 * m);
+  int* ij = ints.data();
+  int* start = ij + 2 * m;
+  int* ent = start + (n + 1);
+  std::vector<double> w(6 * m);
+  for (size_t k = 0; k <= n; ++k) start[k] = 0;
+  for (size_t e = 0; e < m; ++e) {
+    ij[2 * e] = (int)edges[e].i;
+    ij[2 * e + 1] = (int)edges[e].j;
+    start[edges[e].i + 1]++;
+    start[edges[e].j + 1]++;
+    memcpy(&w[6 * e], edges[e].weight, sizeof(double) * 6);
+  }
+  for (size_t k = 0; k < n; ++k) start[k + 1] += start[k];
+  {
+    std::vector<int> fill(start, start + n);
+    for (size_t e = 0; e < m; ++e) {
+      ent[fill[edges[e].j]++] = (int)(2 * e);
+      ent[fill[edges[e].i]++] = (int)(2 * e + 1);
+    }
+  }
+  // device storage, carved from the context's two grow-only buffers
+  GraphState& G = c->graph;
+  constexpr size_t kPose = sizeof(Pose) / sizeof(double), kRt = sizeof(Rt) / sizeof(double);
+  static_assert(sizeof(Pose) == 7 * sizeof(double) && sizeof(Rt) == 12 * sizeof(double), "carved as doubles");
+  const size_t doubles = 2 * kPose * n + kPose * m + 6 * m + kRt * m + 12 * m + 2 * kRt * n + 36 * n;
+  HIPC(c, hipSetDevice(c->device));
+  HIPC(c, hipStreamSynchronize(c->stream));   // (an earlier solve's storage may be replaced below)
+  HIPC(c, G.dws.reserve(doubles));
+  HIPC(c, G.iws.reserve(ints.size()));
+  HIPC(c, G.rec.reserve(1));
+  double* d = G.dws.p;
+  auto take = [&d](size_t count) { double* p = d; d += count; return p; };
+  Pose* dP[2] = {(Pose*)take(kPose * n), (Pose*)take(kPose * n)};
+  GraphArgs A;
+  memset(&A, 0, sizeof(A));
+  A.n = (int)n;
+  A.m = (int)m;
+  A.chunk = (int)((n - 1 + kGraphThreads - 1) / kGraphThreads);
+  A.max_cg = cfg.max_cg_iterations;
+  A.cg_tol2 = cfg.cg_tol * cfg.cg_tol;
+  double* dZ = take(kPose * m);
+  double* dw = take(6 * m);
+  A.Zinv = (const Pose*)dZ;
+  A.w = dw;
+  A.A = (Rt*)take(kRt * m);
+  A.contrib = take(12 * m);
+  A.Q = (Rt*)take(kRt * n);
+  A.Qi = (Rt*)take(kRt * n);
+  A.x = take(6 * n); A.r = take(6 * n); A.z = take(6 * n); A.p = take(6 * n); A.ap = take(6 * n); A.tmp = take(6 * n);
+  A.ij = (const int2*)G.iws.p;
+  A.node_start = G.iws.p + 2 * m;
+  A.node_ent = G.iws.p + 2 * m + (n + 1);
+  A.rec = G.rec.p;
+  const hipMemcpyKind H2D = hipMemcpyHostToDevice, D2H = hipMemcpyDeviceToHost;
+  HIPC(c, hipMemcpyAsync(dP[0], P.data(), sizeof(Pose) * n, H2D, c->stream));
+  HIPC(c, hipMemcpyAsync(dZ, Zinv.data(), sizeof(Pose) * m, H2D, c->stream));
+  HIPC(c, hipMemcpyAsync(dw, w.data(), sizeof(double) * 6 * m, H2D, c->stream));
+  HIPC(c, hipMemcpyAsync(G.iws.p, ints.data(), sizeof(int) * ints.size(), H2D, c->stream));
+  // Gauss-Newton: one launch and one record per iteration
+  int cur = 0;
+  double cost = 0.0;
+  bool limit = false;
+  I.stop_reason = TLOAM_GRAPH_STOP_ITERATIONS;
+  for (int it = 0; it < cfg.max_iterations; ++it) {
+    A.P = dP[cur];
+    A.Pn = dP[cur ^ 1];
+    launch_graph_step(A, c->stream);
+    HIPC(c, hipGetLastError());
+    GraphRecord R;
+    HIPC(c, hipMemcpyAsync(&R, G.rec.p, sizeof(R), D2H, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    if (it == 0) I.initial_cost = cost = R.cost_before;
+    I.iterations = it + 1;
+    I.cg_iterations += R.cg_iterations;
+    I.last_step = R.max_step;
+    I.last_cg_residual = R.cg_residual;
+    limit = R.cg_limit != 0;
+    const bool small = R.max_step < cfg.step_tol;   // (a step below step_tol is kept on its size: the cost no longer resolves it)
+    if (!std::isfinite(R.cost_after) || (R.cost_after > cost && !small)) {
+      I.stop_reason = TLOAM_GRAPH_STOP_COST;
+      I.reverted = 1;
+      break;
+    }
+    cur ^= 1;
+    cost = R.cost_after;
+    if (small) {
+      I.stop_reason = TLOAM_GRAPH_STOP_STEP;
+      break;
+    }
+  }
+  if (limit && I.stop_reason != TLOAM_GRAPH_STOP_COST) I.stop_reason = TLOAM_GRAPH_STOP_CG_LIMIT;
+  I.final_cost = cost;
+  HIPC(c, hipMemcpyAsync(P.data(), dP[cur], sizeof(Pose) * n, D2H, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  double first[16];
+  memcpy(first, poses_in, sizeof(first));   // (node 0 is fixed: its input's bits, also when the arrays are one)
+  for (size_t k = 1; k < n; ++k) pose_to_matrix(P[k], poses_out + 16 * k);
+  memcpy(poses_out, first, sizeof(first));
+  if (info) *info = I;
+  return TLOAM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void tloam_graph_default_config(tloam_graph_config* cfg) {
+  if (!cfg) return;
+  memset(cfg, 0, sizeof(*cfg));
+  cfg->max_iterations = 30;
+  cfg->max_cg_iterations = 20000;
+  cfg->step_tol = 1e-7;      // below it a step's change of the cost is rounding (measured)
+  cfg->cg_tol = 1e-10;       // keeps the poses within 1e-10 of a direct solve's (measured)
+  cfg->odom_sigma_t = 0.05;  // a keyframe step's odometry: not measured, DESIGN.md 18
+  cfg->odom_sigma_r = 0.005;
+  cfg->loop_sigma_t = 0.05;  // measured worst case of a verified loop
+  cfg->loop_sigma_r = 0.01;
+}
+
+int tloam_graph_configure(tloam_ctx* c, const tloam_graph_config* cfg) {
+  if (!c || c->nranks > 1) return TLOAM_E_INVALID;
+  tloam_graph_config want;
+  if (cfg) want = *cfg;
+  else tloam_graph_default_config(&want);
+  if (!graph_config_ok(want)) return TLOAM_E_INVALID;
+  c->graph.cfg = want;
+  c->graph.drop();
+  return TLOAM_OK;
+}
+
+int tloam_graph_solve(tloam_ctx* c, const tloam_graph_config* cfg, size_t n_nodes, const double* poses_in, size_t n_edges,
+                      const tloam_graph_edge* edges, double* poses_out, tloam_graph_info* info) {
+  if (!c || c->nranks > 1 || (cfg && !graph_config_ok(*cfg))) return TLOAM_E_INVALID;
+  return graph_solve(c, cfg ? *cfg : c->graph.cfg, n_nodes, poses_in, n_edges, edges, poses_out, info);
+}
+
+int tloam_graph_optimize(tloam_ctx* c, tloam_graph_info* info) {
+  if (!c || c->nranks > 1 || !c->place.cfg.enabled) return TLOAM_E_INVALID;
+  const PlaceState& P = c->place;
+  GraphState& G = c->graph;
+  const size_t n = P.kf.size();
+  std::vector<double> poses(16 * n);
+  for (size_t k = 0; k < n; ++k) memcpy(&poses[16 * k], P.kf[k].pose, sizeof(double) * 16);
+  std::vector<tloam_graph_edge> edges;
+  tloam_graph_edge E;
+  memset(&E, 0, sizeof(E));
+  sigma_weights(G.cfg.odom_sigma_t, G.cfg.odom_sigma_r, E.weight);
+  for (size_t k = 0; k + 1 < n; ++k) {
+    double inv[16];
+    E.i = (int64_t)k;
+    E.j = (int64_t)k + 1;
+    rigid_inverse(P.kf[k].pose, inv);
+    mat_mul(inv, P.kf[k + 1].pose, E.rel_pose_colmajor);
+    edges.push_back(E);
+  }
+  sigma_weights(G.cfg.loop_sigma_t, G.cfg.loop_sigma_r, E.weight);
+  for (const tloam_loop_constraint& L : c->loop.out) {
+    if (!L.accepted) continue;
+    E.i = L.match_keyframe;
+    E.j = L.query_keyframe;
+    memcpy(E.rel_pose_colmajor, L.rel_pose_colmajor, sizeof(E.rel_pose_colmajor));
+    edges.push_back(E);
+  }
+  tloam_graph_info I;
+  memset(&I, 0, sizeof(I));
+  std::vector<double> out(16 * n);
+  if (n >= 1) {
+    const int rc = graph_solve(c, G.cfg, n, poses.data(), edges.size(), edges.data(), out.data(), &I);
+    if (rc != TLOAM_OK) return rc;
+  }
+  G.corrected.swap(out);
+  G.have = true;
+  if (info) *info = I;
+  return TLOAM_OK;
+}
+
+int tloam_graph_read_poses(tloam_ctx* c, size_t first, size_t count, double* poses) {
+  if (!c || c->nranks > 1) return TLOAM_E_INVALID;
+  const GraphState& G = c->graph;
+  if (!G.have) return TLOAM_E_NOT_READY;
+  const size_t n = G.corrected.size() / 16;
+  if (first > n || count > n - first) return TLOAM_E_INVALID;
+  if (count == 0) return TLOAM_OK;
+  if (!poses) return TLOAM_E_INVALID;
+  memcpy(poses, G.corrected.data() + 16 * first, sizeof(double) * 16 * count);
+  return TLOAM_OK;
+}
+
+int tloam_graph_correct_pose(tloam_ctx* c, int64_t keyframe, const double pose_in[16], double pose_out[16]) {
+  if (!c || c->nranks > 1 || !pose_in || !pose_out) return TLOAM_E_INVALID;
+  const GraphState& G = c->graph;
+  if (!G.have) return TLOAM_E_NOT_READY;
+  const int64_t n = (int64_t)(G.corrected.size() / 16);
+  if (keyframe == -1) keyframe = n - 1;
+  if (keyframe < 0 || keyframe >= n || (size_t)keyframe >= c->place.kf.size()) return TLOAM_E_INVALID;
+  for (int i = 0; i < 16; ++i)
+    if (!std::isfinite(pose_in[i])) return TLOAM_E_INVALID;
+  double inv[16], delta[16];
+  rigid_inverse(c->place.kf[(size_t)keyframe].pose, inv);
+  mat_mul(&G.corrected[16 * (size_t)keyframe], inv, delta);
+  mat_mul(delta, pose_in, pose_out);
+  return TLOAM_OK;
+}
+
+}  // extern "C"

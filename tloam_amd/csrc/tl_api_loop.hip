@@ -276,6 +276,7 @@ int tloam_loop_configure(tloam_ctx* c, const tloam_loop_config* cfg) {
   P.in_flight = false;
   P.arena.release();
   L.clear();
+  c->graph.drop();   // (the corrected poses are those of keyframes that are gone)
   L.cfg = want;
   L.cfg_set = true;
   if (!want.enabled) {

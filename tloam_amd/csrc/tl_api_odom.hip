@@ -305,6 +305,7 @@ int tloam_odometry_reset(tloam_ctx* c, const tloam_odom_config* cfg, const doubl
   c->vmap.clear();               // the merged voxel map too
   c->place.clear(c->stream);     // and the keyframe database (its configuration stays), with its clouds
   c->loop.clear();               // and the verified constraints (likewise)
+  c->graph.drop();               // and the corrected keyframe poses (likewise)
   c->deskew.clear();             // (its configuration stays too)
   return TLOAM_OK;
 }

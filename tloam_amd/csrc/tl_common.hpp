@@ -703,6 +703,32 @@ struct LoopScoreArgs {
 };
 void launch_loop_score(const LoopScoreArgs& A, hipStream_t s);
 
+// ---- pose-graph optimisation of the keyframes (tl_graph.hip) ----------------------------------------
+constexpr int kGraphThreads = 512;    // k_graph_step is ONE workgroup: its barriers order the conjugate gradients, nothing spins
+struct GraphRecord {                  // what one Gauss-Newton iteration reports
+  double cost_before, cost_after, max_step, cg_residual;
+  int cg_iterations, cg_limit;        // cg_limit 1: the solve ended on max_cg
+};
+struct GraphArgs {
+  int n, m;                       // nodes, edges (edges 0 .. n-2 the chain)
+  int chunk;                      // nodes per thread: thread t owns nodes 1 + t chunk .. 1 + (t + 1) chunk - 1
+  int max_cg;
+  double cg_tol2;                 // cg_tol^2
+  const Pose* P;                  // [n] the poses linearised at
+  Pose* Pn;                       // [n] the stepped poses
+  const int2* ij;                 // [m]
+  const Pose* Zinv;               // [m] rigid_inverse(Z)
+  const double* w;                // [m][6]
+  const int* node_start;          // [n + 1] a node's entries of node_ent, in edge order
+  const int* node_ent;            // 2 edge + side: side 0 the edge ends at the node (j), 1 it starts there (i)
+  Rt* A;                          // [m] rigid_inverse(P_j) * P_i: J_i = -Ad(A)
+  double* contrib;                // [2 m][6] an edge's terms for its j and its i node
+  Rt *Q, *Qi;                     // [n] rigid_inverse(P_0) * P_k and its inverse
+  double *x, *r, *z, *p, *ap, *tmp;   // [n][6]
+  GraphRecord* rec;
+};
+void launch_graph_step(const GraphArgs& A, hipStream_t s);   // k_graph_step: linearise, solve, step, the new cost
+
 // ---- PCA feature extraction (tl_feature.hip; feature_extract.cpp:47-197) -----------------------
 struct FeatArgs {
   GridView g;                 // grid over the cloud itself (cell >= radius)

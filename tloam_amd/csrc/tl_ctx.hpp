@@ -393,6 +393,19 @@ struct LoopState {
   void clear() { out.clear(); next_record = 0; }
 };
 
+// pose-graph optimisation of the keyframes (tl_api_graph.hip): its configuration, the solver's device
+// storage (doubles and integers, carved per call; grow-only), and the corrected keyframe poses of the last tloam_graph_optimize
+struct GraphState {
+  tloam_graph_config cfg = {30, 20000, 1e-7, 1e-10, 0.05, 0.005, 0.05, 0.01};   // tloam_graph_default_config
+  DBuf<double> dws;
+  DBuf<int> iws;
+  DBuf<tl::GraphRecord> rec;
+  bool have = false;               // tloam_graph_optimize has run since the last reset / configure
+  std::vector<double> corrected;   // [16 n] column-major
+  void drop() { have = false; corrected.clear(); }
+  void release() { dws.release(); iws.release(); rec.release(); drop(); }
+};
+
 // up to four SoA clouds (x, y, z, n) a search grid is built over -- the registered targets, or any other cloud
 struct CloudRef { const double *x, *y, *z; size_t n; };
 }  // namespace tlh
@@ -410,6 +423,7 @@ struct tloam_ctx {
   DeskewState deskew;
   PlaceState place;
   LoopState loop;
+  GraphState graph;
   int device = 0;
   hipStream_t stream = nullptr;
   KindData kd[kKinds];

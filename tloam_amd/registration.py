@@ -150,6 +150,37 @@ class LoopInfo(C.Structure):
     as_dict = _int_fields
 
 
+class GraphConfig(C.Structure):
+    """tloam_graph_config: the pose-graph optimisation's iteration limits and tolerances, and the sigmas the context's graph
+    weights its chain (odometry) and loop edges with."""
+    _fields_ = [("max_iterations", C.c_int32), ("max_cg_iterations", C.c_int32), ("step_tol", C.c_double),
+                ("cg_tol", C.c_double), ("odom_sigma_t", C.c_double), ("odom_sigma_r", C.c_double),
+                ("loop_sigma_t", C.c_double), ("loop_sigma_r", C.c_double)]
+
+
+class GraphEdge(C.Structure):
+    """tloam_graph_edge: (i, j, Z = rigid_inverse(P_i) P_j column-major, six inverse variances)."""
+    _fields_ = [("i", C.c_int64), ("j", C.c_int64), ("rel_pose_colmajor", C.c_double * 16), ("weight", C.c_double * 6)]
+
+
+GRAPH_STOP = {0: "not_run", 1: "step", 2: "iterations", 3: "cost", 4: "cg_limit"}
+
+
+class GraphInfo(C.Structure):
+    """tloam_graph_info."""
+    _fields_ = [("n_nodes", C.c_int64), ("n_edges", C.c_int64), ("n_loop_edges", C.c_int64), ("iterations", C.c_int32),
+                ("stop_reason", C.c_int32), ("reverted", C.c_int32), ("reserved0", C.c_int32), ("cg_iterations", C.c_int64),
+                ("initial_cost", C.c_double), ("final_cost", C.c_double), ("last_step", C.c_double),
+                ("last_cg_residual", C.c_double)]
+
+    def as_dict(self):
+        return {"n_nodes": int(self.n_nodes), "n_edges": int(self.n_edges), "n_loop_edges": int(self.n_loop_edges),
+                "iterations": int(self.iterations), "stop_reason": int(self.stop_reason), "stop": GRAPH_STOP[int(self.stop_reason)],
+                "reverted": int(self.reverted), "cg_iterations": int(self.cg_iterations), "initial_cost": float(self.initial_cost),
+                "final_cost": float(self.final_cost), "last_step": float(self.last_step),
+                "last_cg_residual": float(self.last_cg_residual)}
+
+
 class TlsConfig(C.Structure):
     """tloam_tls_config: the 16 keys of the `TLS:` block (config/mapping/lidar_odometry.yaml:23-39)."""
     _fields_ = [
@@ -343,6 +374,12 @@ def load_library():
         "tloam_loop_verify_pending": (C.c_int, [vp, C.POINTER(C.c_int64)]),
         "tloam_loop_verify_pair": (C.c_int, [vp, C.c_int64, C.c_int64, dp, C.POINTER(LoopConstraint)]),
         "tloam_loop_read_constraints": (C.c_int, [vp, sz, sz, C.POINTER(LoopConstraint)]),
+        "tloam_graph_default_config": (None, [C.POINTER(GraphConfig)]),
+        "tloam_graph_configure": (C.c_int, [vp, C.POINTER(GraphConfig)]),
+        "tloam_graph_solve": (C.c_int, [vp, C.POINTER(GraphConfig), sz, dp, sz, C.POINTER(GraphEdge), dp, C.POINTER(GraphInfo)]),
+        "tloam_graph_optimize": (C.c_int, [vp, C.POINTER(GraphInfo)]),
+        "tloam_graph_read_poses": (C.c_int, [vp, sz, sz, dp]),
+        "tloam_graph_correct_pose": (C.c_int, [vp, C.c_int64, dp, dp]),
         "tloam_rccl_unique_id": (C.c_int, [vp]),
         "tloam_comm_init_rccl": (C.c_int, [vp, C.c_int, C.c_int, vp]),
         "tloam_comm_init_callback": (C.c_int, [vp, C.c_int, C.c_int, ALLREDUCE_FN, vp]),
@@ -379,7 +416,8 @@ EXPORTED_SYMBOLS = (
     "tloam_place_configure", "tloam_place_get_info", "tloam_place_read_keyframes", "tloam_place_read_loops", "tloam_place_add_scan",
     "tloam_place_describe", "tloam_loop_default_config", "tloam_loop_configure", "tloam_loop_get_info",
     "tloam_place_set_keyframe_clouds", "tloam_place_read_keyframe_clouds", "tloam_loop_verify_pending", "tloam_loop_verify_pair",
-    "tloam_loop_read_constraints", "tloam_rccl_unique_id", "tloam_comm_init_rccl",
+    "tloam_loop_read_constraints", "tloam_graph_default_config", "tloam_graph_configure", "tloam_graph_solve", "tloam_graph_optimize",
+    "tloam_graph_read_poses", "tloam_graph_correct_pose", "tloam_rccl_unique_id", "tloam_comm_init_rccl",
     "tloam_comm_mailbox_export", "tloam_comm_init_mailbox",
     "tloam_comm_init_callback", "tloam_shard_range", "tloam_shard_ranges_frame", "tloam_se3_exp", "tloam_se3_log", "tloam_se3_plus",
 )
@@ -922,6 +960,54 @@ class HipRegistration:
         self._check(self.L.tloam_loop_read_constraints(self.h, int(first), m, buf), "tloam_loop_read_constraints")
         return [buf[i].as_dict() for i in range(m)]
 
+    # ---- pose-graph optimisation of the keyframes
+    def graph_configure(self, cfg: GraphConfig | None = None, **over):
+        """the context's graph configuration (default_graph_config(**over) when cfg is None); drops the corrected poses.  Kept
+        across odometry_reset."""
+        cfg = cfg if cfg is not None else default_graph_config(**over)
+        self._check(self.L.tloam_graph_configure(self.h, C.byref(cfg)), "tloam_graph_configure")
+
+    def graph_solve(self, poses, i, j, Z, w, cfg: GraphConfig | None = None):
+        """the caller's graph: poses (n, 4, 4); edges i, j (m,), Z (m, 4, 4), w (m, 6), the first n - 1 the chain ->
+        (poses (n, 4, 4), info dict); cfg None: the context's configuration"""
+        P = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 4, 4).transpose(0, 2, 1))
+        Zc = np.asarray(Z, np.float64).reshape(-1, 4, 4).transpose(0, 2, 1).reshape(-1, 16)
+        wv = np.asarray(w, np.float64).reshape(-1, 6)
+        m = len(Zc)
+        edges = (GraphEdge * max(m, 1))()
+        if m:
+            rec = np.frombuffer(edges, dtype=np.dtype([("i", np.int64), ("j", np.int64), ("Z", np.float64, 16),
+                                                       ("w", np.float64, 6)]), count=m)
+            rec["i"], rec["j"], rec["Z"], rec["w"] = np.asarray(i, np.int64), np.asarray(j, np.int64), Zc, wv
+        out = np.zeros_like(P)
+        info = GraphInfo()
+        self._check(self.L.tloam_graph_solve(self.h, C.byref(cfg) if cfg is not None else None, len(P), _dp(P), m, edges,
+                                             _dp(out), C.byref(info)), "tloam_graph_solve")
+        return out.transpose(0, 2, 1).copy(), info.as_dict()
+
+    def graph_optimize(self) -> dict:
+        """optimises the context's graph (keyframe poses, odometry chain, accepted constraints) -> info dict"""
+        info = GraphInfo()
+        self._check(self.L.tloam_graph_optimize(self.h, C.byref(info)), "tloam_graph_optimize")
+        self._graph_n = int(info.n_nodes)   # (how many corrected poses graph_poses reads by default)
+        return info.as_dict()
+
+    def graph_poses(self, first=0, count=None):
+        """corrected keyframe poses [first, first + count) of the last graph_optimize, (m, 4, 4); count None: all of them"""
+        if count is None:
+            count = max(getattr(self, "_graph_n", 0) - int(first), 0)
+        m = int(count)
+        out = np.zeros((max(m, 1), 16))
+        self._check(self.L.tloam_graph_read_poses(self.h, int(first), m, _dp(out)), "tloam_graph_read_poses")
+        return out[:m].reshape(m, 4, 4).transpose(0, 2, 1).copy()
+
+    def graph_correct_pose(self, keyframe, pose):
+        """P'_k rigid_inverse(P_k) pose for a pose taken near keyframe k (-1: the last corrected one)"""
+        out = np.zeros(16)
+        self._check(self.L.tloam_graph_correct_pose(self.h, int(keyframe), _dp(_colmajor(pose)), _dp(out)),
+                    "tloam_graph_correct_pose")
+        return out.reshape(4, 4).T.copy()
+
     def fitness(self):
         f, r = C.c_double(0), C.c_double(0)
         rc = self.L.tloam_fitness(self.h, C.byref(f), C.byref(r))
@@ -1150,6 +1236,12 @@ def default_loop_config(**over) -> LoopConfig:
                 raise KeyError(k)
             setattr(cfg.coarse, name, v)
     return cfg
+
+
+def default_graph_config(**over) -> GraphConfig:
+    """tloam_graph_default_config (30 Gauss-Newton iterations of at most 20000 conjugate-gradient iterations, step_tol 1e-7,
+    cg_tol 1e-10, the odometry and loop sigmas) with keyword overrides"""
+    return _strict_config(GraphConfig, "tloam_graph_default_config", over)
 
 
 def default_submap_config(**over) -> SubmapConfig:
