@@ -796,6 +796,63 @@ int tloam_graph_read_poses(tloam_ctx* ctx, size_t first, size_t count, double* p
 int tloam_graph_correct_pose(tloam_ctx* ctx, int64_t keyframe, const double pose_in_colmajor[16], double pose_out_colmajor[16]);
 /* Every graph call on a context with nranks > 1: TLOAM_E_INVALID. */
 
+/* ---- the closed map: the keyframe clouds merged under corrected poses (additive to ABI 8) ----------------------
+ * A third map beside tloam_map_* and tloam_voxel_map_*.  Runs only when called: with it never called, every frame, stat, map,
+ * place record, constraint, corrected pose and launch is what it is without it.  Input: the context's keyframes 0 .. K-1 with
+ * their stored clouds (loop verification must be on, else TLOAM_E_INVALID).  cloud_mask has bit side * 4 + kind set for every
+ * cloud slot that takes part; a keyframe's input is its selected clouds end to end in ascending slot order, points in stored
+ * order.  A keyframe without points in the selected slots adds nothing (empty_keyframes).  Per point: the world point is the
+ * keyframe's pose applied as tloam_registered_scan applies it; quantisation, key, N, Q and centroid are tloam_voxel_map_*'s
+ * (above), non-finite world points left out.  A keyframe with |i| >= 2^20 on an axis for any finite point adds nothing
+ * (overflow_keyframes); the others are not affected.  Voxel ids in order of the smallest global point index, global meaning
+ * keyframes ascending, then the concatenation above.  The sums are int64: two builds, or two contexts, give the same bits.
+ * DESIGN.md 19. */
+typedef struct tloam_closed_map_config {
+  double voxel;             /* v: 1.0 */
+  double origin[3];         /* o: (0, 0, 0) */
+  int32_t cloud_mask;       /* 0xF0: side 1, the four clouds the keyframe's frame gave the submap */
+  int32_t reserved0;
+  int64_t reserve_voxels;   /* voxels of HBM the first build reserves; 0 = 2^20; grows past it inside a build */
+} tloam_closed_map_config;
+void tloam_closed_map_default_config(tloam_closed_map_config* cfg);
+/* cfg NULL: the defaults.  Empties the closed map (so do tloam_odometry_reset, tloam_place_configure and tloam_loop_configure;
+ * tloam_graph_configure and a later tloam_graph_optimize do not: the closed map says which poses it was built with); the
+ * configuration persists across tloam_odometry_reset.  voxel <= 0 or not finite, a non-finite origin, a mask of 0 or with bits
+ * beyond 8, reserve_voxels < 0: TLOAM_E_INVALID. */
+int tloam_closed_map_configure(tloam_ctx* ctx, const tloam_closed_map_config* cfg);
+
+#define TLOAM_CLOSED_MAP_POSES_STORED 0     /* the stored keyframe poses */
+#define TLOAM_CLOSED_MAP_POSES_CORRECTED 1  /* the corrected poses of the last tloam_graph_optimize */
+#define TLOAM_CLOSED_MAP_POSES_CALLER 2     /* the caller's */
+typedef struct tloam_closed_map_info {
+  int64_t n_keyframes;         /* K of the last build */
+  int64_t added_keyframes;     /* K - empty_keyframes - overflow_keyframes */
+  int64_t empty_keyframes;     /* no point in the selected slots */
+  int64_t overflow_keyframes;  /* a finite point left the grid: added nothing */
+  int64_t n_voxels;            /* occupied voxels */
+  int64_t n_points;            /* points in them: the sum of N */
+  int64_t capacity_voxels;     /* voxels the rows hold before they grow */
+  int32_t pose_source;         /* of the last build */
+  int32_t launches;            /* kernel launches of the last build: the same for every K, span count and point count */
+} tloam_closed_map_info;
+int tloam_closed_map_get_info(tloam_ctx* ctx, tloam_closed_map_info* info);
+/* Builds the closed map from all keyframes at once, replacing the previous one.  pose_source 0: the stored poses; 1: the
+ * corrected poses (TLOAM_E_NOT_READY before any tloam_graph_optimize; a keyframe added since that optimise takes
+ * tloam_graph_correct_pose(ctx, -1, P_k, ...), bit for bit); 2: poses_colmajor [16 n_poses] (n_poses != K, a non-finite or
+ * non-rigid pose: TLOAM_E_INVALID).  A refused call leaves the previous closed map as it was.  A build that fails
+ * (TLOAM_E_HIP: an allocation, a bounded wait of a kernel running out) leaves the closed map empty.  Nothing else in the
+ * context changes.  info may be NULL. */
+int tloam_closed_map_build(tloam_ctx* ctx, int pose_source, const double* poses_colmajor_or_null, size_t n_poses,
+                           tloam_closed_map_info* info_or_null);
+/* As tloam_voxel_map_read / tloam_voxel_map_read_box, on the closed map.  TLOAM_E_NOT_READY without a built closed map. */
+int tloam_closed_map_read(tloam_ctx* ctx, size_t first, size_t count, double* centroids_aos, int64_t* counts);
+int tloam_closed_map_read_box(tloam_ctx* ctx, const double lo[3], const double hi[3], int64_t min_count, size_t capacity,
+                              size_t* n, double* centroids_aos, int64_t* counts);
+/* The poses keyframes [first, first + count) were built with, [16 count] column-major.  A range beyond n_keyframes:
+ * TLOAM_E_INVALID; TLOAM_E_NOT_READY without a built closed map. */
+int tloam_closed_map_read_poses(tloam_ctx* ctx, size_t first, size_t count, double* poses_colmajor);
+/* Every closed map call on a context with nranks > 1: TLOAM_E_INVALID. */
+
 /* ---- multi-GPU: correspondence set sharded over ranks, one all-reduce per sweep --------
  * (nothing in the reference).  Call before set_source / set_correspondences.
  * (a) native RCCL over xGMI: unique_id = the 128 bytes of an ncclUniqueId made on rank 0

@@ -148,6 +148,7 @@ void tloam_destroy(tloam_ctx* c) {
   c->deskew.release();
   tlh::loop_release(c);
   c->graph.release();
+  c->cmap.release();
   c->place.release();
   if (c->h_state) (void)hipHostFree(c->h_state);
   if (c->h_mirror) (void)hipHostFree(c->h_mirror);

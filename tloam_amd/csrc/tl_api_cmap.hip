@@ -1,0 +1,307 @@
+// tl_api_cmap.hip -- C ABI of the closed map (include/tloam_hip.h: tloam_closed_map_*; kernels in
+// tl_cmap.hip, reads by tl_vmap.hip's k_vmap_read / k_vmap_box).
+//
+// A build takes the host's keyframe table (PlaceState::kf: where every stored cloud lies in the arena) and a pose per keyframe,
+// uploads one span table and the poses, and enqueues four launches on the context's stream -- behind any k_place_clouds still in
+// flight.  The rows are sized before the numbering writes them: a build of no more points than the rows hold waits once, at its
+// end; a larger one reads the count of distinct voxels first.  The staging (the build table, a slot per point) is the build's
+// own and is freed when it ends.  Nothing else in the context is read or written.
+#include <float.h>
+#include <math.h>
+
+#include "tl_ctx.hpp"
+
+using namespace tl;
+
+namespace {
+
+constexpr size_t kCmapDefaultReserve = (size_t)1 << 20;   // voxels (40 MiB of rows, 8 MiB of table): reserve_voxels = 0
+constexpr size_t kCmapMaxPoints = (size_t)1 << 30;        // slots and ids are 32-bit
+
+bool cmap_config_ok(const tloam_closed_map_config& m) {
+  return m.voxel > 0.0 && m.voxel <= DBL_MAX && std::isfinite(m.origin[0]) && std::isfinite(m.origin[1]) &&
+         std::isfinite(m.origin[2]) && m.cloud_mask > 0 && m.cloud_mask <= 0xFF && m.reserve_voxels >= 0;
+}
+
+bool cmap_on(const tloam_ctx* c) { return c && c->nranks == 1 && place_clouds_on(c); }
+
+// a build's device staging, freed with it (hipFree waits for the launches that use it)
+struct Staging {
+  DBuf<unsigned long long> fkey, flead, fsum, look, ctl;
+  DBuf<int> slot_of_pt, kf_over;
+  DBuf<CmapSpan> span;
+  DBuf<double> pose;
+  ~Staging() {
+    fkey.release(); flead.release(); fsum.release(); look.release(); ctl.release(); slot_of_pt.release(); kf_over.release();
+    span.release(); pose.release();
+  }
+};
+
+// the rows hold `need` voxels; the closed map is being replaced, so nothing is copied
+int rows_reserve(tloam_ctx* c, size_t need) {
+  CmapState& M = c->cmap;
+  if (need <= M.cap) return TLOAM_OK;
+  const size_t want = std::max(need, 2 * M.cap);
+  size_t tsize = 1024;
+  while (tsize < 2 * want) tsize <<= 1;
+  HIPC(c, hipStreamSynchronize(c->stream));   // (a launch in flight may still write the rows replaced)
+  M.release_rows();
+  HIPC(c, M.key.reserve(want));
+  for (DBuf<long long>* a : {&M.n, &M.qx, &M.qy, &M.qz}) HIPC(c, a->reserve(want));
+  HIPC(c, M.tab.reserve(tsize));
+  M.cap = want;
+  M.tmask = tsize - 1;
+  return TLOAM_OK;
+}
+
+VmapReadArgs read_args(const CmapState& M) {
+  VmapReadArgs A;
+  memset(&A, 0, sizeof(A));
+  A.pkey = M.key.p; A.pn = M.n.p; A.pqx = M.qx.p; A.pqy = M.qy.p; A.pqz = M.qz.p;
+  A.voxel = M.cfg.voxel;
+  for (int a = 0; a < 3; ++a) A.origin[a] = M.cfg.origin[a];
+  return A;
+}
+
+// the enqueue, the waits and the counts of a build whose inputs have been checked; the closed map has been dropped
+int build_body(tloam_ctx* c, const std::vector<double>& poses, tloam_closed_map_info& I) {
+  CmapState& M = c->cmap;
+  const PlaceState& P = c->place;
+  const size_t K = P.kf.size();
+  // the span table: keyframes ascending, a keyframe's selected clouds in slot order, empty clouds left out
+  std::vector<CmapSpan> spans;
+  long long n = 0;
+  for (size_t k = 0; k < K; ++k) {
+    const long long before = n;
+    for (int j = 0; j < 8; ++j) {
+      if (!((M.cfg.cloud_mask >> j) & 1) || P.kf[k].n[j] == 0) continue;
+      spans.push_back(CmapSpan{(long long)P.kf[k].off[j], n, (int)k, 0});
+      n += (long long)P.kf[k].n[j];
+    }
+    if (n == before) I.empty_keyframes++;
+  }
+  if ((size_t)n > kCmapMaxPoints) {
+    c->last_error = "closed map: more than 2^30 points";
+    return TLOAM_E_HIP;
+  }
+  const int nspan = (int)spans.size();
+  spans.push_back(CmapSpan{0, n, 0, 0});   // (the end: span[nspan].start = n)
+  HIPC(c, hipSetDevice(c->device));
+  int rc = rows_reserve(c, M.cfg.reserve_voxels > 0 ? (size_t)M.cfg.reserve_voxels : kCmapDefaultReserve);
+  if (rc != TLOAM_OK) return rc;
+  Staging S;
+  const size_t m = std::max<size_t>((size_t)n, 1), T = voxel_table_size(m), blocks = (m + 255) / 256;
+  HIPC(c, S.fkey.reserve(T)); HIPC(c, S.flead.reserve(T)); HIPC(c, S.fsum.reserve(4 * T)); HIPC(c, S.slot_of_pt.reserve(m));
+  HIPC(c, S.look.reserve(blocks + 1)); HIPC(c, S.ctl.reserve(8)); HIPC(c, S.kf_over.reserve(std::max<size_t>(K, 1)));
+  HIPC(c, S.span.reserve(spans.size())); HIPC(c, S.pose.reserve(std::max<size_t>(16 * K, 16)));
+  const hipMemcpyKind H2D = hipMemcpyHostToDevice, D2H = hipMemcpyDeviceToHost;
+  HIPC(c, hipMemcpyAsync(S.span.p, spans.data(), sizeof(CmapSpan) * spans.size(), H2D, c->stream));
+  if (K) HIPC(c, hipMemcpyAsync(S.pose.p, poses.data(), sizeof(double) * 16 * K, H2D, c->stream));
+  static const bool no_runs = getenv("TLOAM_CMAP_NO_RUNS") != nullptr;   // A/B of the wave's run aggregation
+  CmapWork W;
+  memset(&W, 0, sizeof(W));
+  W.arena = P.arena.p;
+  W.span = S.span.p;
+  W.nspan = nspan;
+  W.runs = no_runs ? 0 : 1;
+  W.n = n;
+  W.pose = S.pose.p;
+  W.kf_over = S.kf_over.p;
+  W.nkf = (int)K;
+  W.voxel = M.cfg.voxel;
+  for (int a = 0; a < 3; ++a) W.origin[a] = M.cfg.origin[a];
+  W.fmask = T - 1;
+  W.fkey = S.fkey.p; W.flead = S.flead.p; W.fsum = S.fsum.p; W.slot_of_pt = S.slot_of_pt.p;
+  W.look = S.look.p; W.ctl = S.ctl.p;
+  I.launches = launch_cmap_stage(W, c->stream);
+  HIPC(c, hipGetLastError());
+  unsigned long long ctl[8];
+  if ((size_t)n > M.cap) {   // more points than rows: the rows are sized by the count of distinct voxels
+    HIPC(c, hipMemcpyAsync(ctl, S.ctl.p, sizeof(ctl), D2H, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    rc = rows_reserve(c, (size_t)ctl[0]);
+    if (rc != TLOAM_OK) return rc;
+  }
+  HIPC(c, hipMemsetAsync(M.tab.p, 0xff, sizeof(int) * (size_t)(M.tmask + 1), c->stream));
+  W.rows.pmask = M.tmask; W.rows.ptab = M.tab.p; W.rows.pkey = M.key.p;
+  W.rows.pn = M.n.p; W.rows.pqx = M.qx.p; W.rows.pqy = M.qy.p; W.rows.pqz = M.qz.p;
+  W.row_cap = (long long)M.cap;
+  I.launches += launch_cmap_emit(W, c->stream);
+  HIPC(c, hipGetLastError());
+  std::vector<int> over(std::max<size_t>(K, 1));
+  HIPC(c, hipMemcpyAsync(ctl, S.ctl.p, sizeof(ctl), D2H, c->stream));
+  if (K) HIPC(c, hipMemcpyAsync(over.data(), S.kf_over.p, sizeof(int) * K, D2H, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  if (ctl[3]) {
+    c->last_error = "closed map: a look-back of k_cmap_emit timed out";
+    return TLOAM_E_HIP;
+  }
+  if (ctl[4] != ctl[0] || ctl[4] > M.cap) {
+    c->last_error = "closed map: the voxels numbered are not the voxels counted";
+    return TLOAM_E_HIP;
+  }
+  for (size_t k = 0; k < K; ++k) I.overflow_keyframes += over[k] ? 1 : 0;
+  I.added_keyframes = (int64_t)K - I.empty_keyframes - I.overflow_keyframes;
+  I.n_voxels = (int64_t)ctl[4];
+  I.n_points = (int64_t)ctl[1];
+  return TLOAM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void tloam_closed_map_default_config(tloam_closed_map_config* cfg) {
+  if (!cfg) return;
+  memset(cfg, 0, sizeof(*cfg));
+  cfg->voxel = 1.0;
+  cfg->origin[0] = cfg->origin[1] = cfg->origin[2] = 0.0;
+  cfg->cloud_mask = 0xF0;
+  cfg->reserve_voxels = 0;
+}
+
+int tloam_closed_map_configure(tloam_ctx* c, const tloam_closed_map_config* cfg) {
+  if (!c || c->nranks > 1) return TLOAM_E_INVALID;
+  tloam_closed_map_config want;
+  if (cfg) want = *cfg;
+  else tloam_closed_map_default_config(&want);
+  if (!cmap_config_ok(want)) return TLOAM_E_INVALID;
+  CmapState& M = c->cmap;
+  M.drop();
+  if (M.cap) {   // (the next build reserves what the new configuration asks for)
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    M.release_rows();
+  }
+  M.cfg = want;
+  return TLOAM_OK;
+}
+
+int tloam_closed_map_get_info(tloam_ctx* c, tloam_closed_map_info* info) {
+  if (!c || !info || c->nranks > 1) return TLOAM_E_INVALID;
+  *info = c->cmap.info;
+  info->capacity_voxels = (int64_t)c->cmap.cap;
+  return TLOAM_OK;
+}
+
+int tloam_closed_map_build(tloam_ctx* c, int pose_source, const double* poses, size_t n_poses, tloam_closed_map_info* info) {
+  if (!cmap_on(c) || pose_source < TLOAM_CLOSED_MAP_POSES_STORED || pose_source > TLOAM_CLOSED_MAP_POSES_CALLER)
+    return TLOAM_E_INVALID;
+  const PlaceState& P = c->place;
+  const GraphState& G = c->graph;
+  const size_t K = P.kf.size();
+  std::vector<double> used(16 * K);
+  if (pose_source == TLOAM_CLOSED_MAP_POSES_CALLER) {
+    if (n_poses != K || (K > 0 && !poses)) return TLOAM_E_INVALID;
+    for (size_t k = 0; k < K; ++k) {
+      Pose unused;
+      for (int i = 0; i < 16; ++i)
+        if (!std::isfinite(poses[16 * k + i])) return TLOAM_E_INVALID;
+      if (!pose_from_matrix(poses + 16 * k, &unused)) return TLOAM_E_INVALID;   // (the rigid test of tloam_graph_solve)
+    }
+    if (K) memcpy(used.data(), poses, sizeof(double) * 16 * K);
+  } else if (pose_source == TLOAM_CLOSED_MAP_POSES_CORRECTED) {
+    const size_t nc = G.corrected.size() / 16;
+    if (!G.have || (nc == 0 && K > 0)) return TLOAM_E_NOT_READY;
+    for (size_t k = 0; k < K; ++k) {
+      if (k < nc) memcpy(&used[16 * k], &G.corrected[16 * k], sizeof(double) * 16);
+      else graph_correct_pose(c, nc - 1, P.kf[k].pose, &used[16 * k]);   // a keyframe added since the optimise
+    }
+  } else {
+    for (size_t k = 0; k < K; ++k) memcpy(&used[16 * k], P.kf[k].pose, sizeof(double) * 16);
+  }
+  CmapState& M = c->cmap;
+  M.drop();   // from here on a failure leaves the closed map empty
+  tloam_closed_map_info I;
+  memset(&I, 0, sizeof(I));
+  I.n_keyframes = (int64_t)K;
+  I.pose_source = pose_source;
+  const int rc = build_body(c, used, I);
+  if (rc != TLOAM_OK) {
+    (void)hipStreamSynchronize(c->stream);   // (nothing of the build is in flight when its staging goes)
+    return rc;
+  }
+  M.info = I;
+  M.poses.swap(used);
+  M.built = true;
+  if (info) {
+    *info = I;
+    info->capacity_voxels = (int64_t)M.cap;
+  }
+  return TLOAM_OK;
+}
+
+int tloam_closed_map_read(tloam_ctx* c, size_t first, size_t count, double* centroids_aos, int64_t* counts) {
+  if (!c || c->nranks > 1) return TLOAM_E_INVALID;
+  CmapState& M = c->cmap;
+  if (!M.built) return TLOAM_E_NOT_READY;
+  const size_t nv = (size_t)M.info.n_voxels;
+  if (first > nv || count > nv - first) return TLOAM_E_INVALID;
+  if (count == 0 || (!centroids_aos && !counts)) return TLOAM_OK;
+  HIPC(c, hipSetDevice(c->device));
+  HIPC(c, hipStreamSynchronize(c->stream));   // (the scratch may be replaced)
+  HIPC(c, M.rd_c.reserve(3 * count)); HIPC(c, M.rd_n.reserve(count));
+  VmapReadArgs A = read_args(M);
+  A.first = first; A.count = count;
+  A.out_c = M.rd_c.p; A.out_n = M.rd_n.p;
+  launch_vmap_read(A, c->stream);
+  if (centroids_aos)
+    HIPC(c, hipMemcpyAsync(centroids_aos, M.rd_c.p, sizeof(double) * 3 * count, hipMemcpyDeviceToHost, c->stream));
+  if (counts) HIPC(c, hipMemcpyAsync(counts, M.rd_n.p, sizeof(int64_t) * count, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  return TLOAM_OK;
+}
+
+int tloam_closed_map_read_box(tloam_ctx* c, const double lo[3], const double hi[3], int64_t min_count, size_t capacity, size_t* n,
+                              double* centroids_aos, int64_t* counts) {
+  if (n) *n = 0;
+  if (!c || !lo || !hi || !n || c->nranks > 1) return TLOAM_E_INVALID;
+  CmapState& M = c->cmap;
+  if (!M.built) return TLOAM_E_NOT_READY;
+  const size_t nv = (size_t)M.info.n_voxels;
+  if (nv == 0) return TLOAM_OK;
+  HIPC(c, hipSetDevice(c->device));
+  HIPC(c, hipStreamSynchronize(c->stream));   // (the scratch may be replaced)
+  const size_t blocks = (nv + 255) / 256;
+  HIPC(c, M.rd_c.reserve(3 * nv)); HIPC(c, M.rd_n.reserve(nv));
+  HIPC(c, M.look.reserve(blocks + 1)); HIPC(c, M.ctl.reserve(8));
+  HIPC(c, hipMemsetAsync(M.look.p, 0, sizeof(unsigned long long) * (blocks + 1), c->stream));
+  HIPC(c, hipMemsetAsync(M.ctl.p, 0, sizeof(unsigned long long) * 8, c->stream));
+  VmapReadArgs A = read_args(M);
+  A.first = 0; A.count = nv;
+  for (int a = 0; a < 3; ++a) { A.lo[a] = lo[a]; A.hi[a] = hi[a]; }
+  A.min_count = min_count;
+  A.out_c = M.rd_c.p; A.out_n = M.rd_n.p;
+  A.look = M.look.p; A.ctl = M.ctl.p;
+  launch_vmap_read_box(A, c->stream);
+  unsigned long long w[3];
+  HIPC(c, hipMemcpyAsync(w, M.ctl.p, sizeof(w), hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  if (w[1]) {
+    c->last_error = "closed map: a look-back of k_vmap_box timed out";
+    return TLOAM_E_HIP;
+  }
+  const size_t m = (size_t)w[2];
+  *n = m;
+  if (m == 0) return TLOAM_OK;
+  if (capacity < m) return TLOAM_E_INVALID;
+  if (centroids_aos)
+    HIPC(c, hipMemcpyAsync(centroids_aos, M.rd_c.p, sizeof(double) * 3 * m, hipMemcpyDeviceToHost, c->stream));
+  if (counts) HIPC(c, hipMemcpyAsync(counts, M.rd_n.p, sizeof(int64_t) * m, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  return TLOAM_OK;
+}
+
+int tloam_closed_map_read_poses(tloam_ctx* c, size_t first, size_t count, double* poses) {
+  if (!c || c->nranks > 1) return TLOAM_E_INVALID;
+  const CmapState& M = c->cmap;
+  if (!M.built) return TLOAM_E_NOT_READY;
+  const size_t K = M.poses.size() / 16;
+  if (first > K || count > K - first) return TLOAM_E_INVALID;
+  if (count == 0) return TLOAM_OK;
+  if (!poses) return TLOAM_E_INVALID;
+  memcpy(poses, M.poses.data() + 16 * first, sizeof(double) * 16 * count);
+  return TLOAM_OK;
+}
+
+}  // extern "C"

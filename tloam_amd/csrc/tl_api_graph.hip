@@ -192,6 +192,15 @@ int graph_solve(tloam_ctx* c, const tloam_graph_config& cfg, size_t n, const dou
 
 }  // namespace
 
+namespace tlh {
+void graph_correct_pose(const tloam_ctx* c, size_t keyframe, const double pose_in[16], double pose_out[16]) {
+  double inv[16], delta[16];
+  rigid_inverse(c->place.kf[keyframe].pose, inv);
+  mat_mul(&c->graph.corrected[16 * keyframe], inv, delta);
+  mat_mul(delta, pose_in, pose_out);
+}
+}  // namespace tlh
+
 extern "C" {
 
 void tloam_graph_default_config(tloam_graph_config* cfg) {
@@ -285,10 +294,7 @@ int tloam_graph_correct_pose(tloam_ctx* c, int64_t keyframe, const double pose_i
   if (keyframe < 0 || keyframe >= n || (size_t)keyframe >= c->place.kf.size()) return TLOAM_E_INVALID;
   for (int i = 0; i < 16; ++i)
     if (!std::isfinite(pose_in[i])) return TLOAM_E_INVALID;
-  double inv[16], delta[16];
-  rigid_inverse(c->place.kf[(size_t)keyframe].pose, inv);
-  mat_mul(&G.corrected[16 * (size_t)keyframe], inv, delta);
-  mat_mul(delta, pose_in, pose_out);
+  tlh::graph_correct_pose(c, (size_t)keyframe, pose_in, pose_out);
   return TLOAM_OK;
 }
 

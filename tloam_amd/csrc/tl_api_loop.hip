@@ -277,6 +277,7 @@ int tloam_loop_configure(tloam_ctx* c, const tloam_loop_config* cfg) {
   P.arena.release();
   L.clear();
   c->graph.drop();   // (the corrected poses are those of keyframes that are gone)
+  c->cmap.drop();    // (so is the closed map)
   L.cfg = want;
   L.cfg_set = true;
   if (!want.enabled) {

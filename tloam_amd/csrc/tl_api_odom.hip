@@ -306,6 +306,7 @@ int tloam_odometry_reset(tloam_ctx* c, const tloam_odom_config* cfg, const doubl
   c->place.clear(c->stream);     // and the keyframe database (its configuration stays), with its clouds
   c->loop.clear();               // and the verified constraints (likewise)
   c->graph.drop();               // and the corrected keyframe poses (likewise)
+  c->cmap.drop();                // and the closed map built from those keyframes (likewise)
   c->deskew.clear();             // (its configuration stays too)
   return TLOAM_OK;
 }

@@ -623,6 +623,42 @@ void launch_vmap_rehash(const VmapTable& T, size_t n, hipStream_t s);
 void launch_vmap_read(const VmapReadArgs& A, hipStream_t s);
 void launch_vmap_read_box(const VmapReadArgs& A, hipStream_t s);
 
+// ---- the closed map: every keyframe's clouds under its own pose into one grid (tl_cmap.hip) ---------
+// The voxel map's grid, key, q and centroid (above); its rows are read by k_vmap_read / k_vmap_box.  The input is a table of
+// spans of the keyframe cloud arena in global point order -- keyframes ascending, a keyframe's selected clouds in slot order --
+// and the K poses, both in HBM: a point finds its span from its global index, so a build is the same launches for any K
+struct CmapSpan {
+  long long off;              // first double of the span in the arena
+  long long start;            // global index of its first point
+  int kf;
+  int reserved0;
+};
+struct CmapWork {
+  const double* arena;
+  const CmapSpan* span;       // [nspan + 1], spans of at least one point; span[nspan].start = n
+  int nspan;
+  int runs;                   // 1: runs of equal keys among a wave's consecutive lanes are summed before the table is touched
+  long long n;                // points of all spans
+  const double* pose;         // [nkf][16] column-major
+  int* kf_over;               // [nkf] 1: a finite point of the keyframe left the grid (k_cmap_flag): it adds nothing
+  int nkf;
+  double voxel, origin[3];
+  // the build table [fmask + 1]
+  unsigned long long fmask;
+  unsigned long long* fkey;
+  unsigned long long* flead;  // smallest global index of the voxel
+  unsigned long long* fsum;   // [4][fmask + 1]: N, Qx, Qy, Qz
+  int* slot_of_pt;            // [n]
+  unsigned long long* look;   // [emit blocks + 1] look-back words of k_cmap_emit
+  unsigned long long* ctl;    // [0] distinct voxels (k_cmap_stage), [1] points added, [2] start tickets of k_cmap_emit, [3] fault,
+                              // [4] voxels numbered (k_cmap_emit)
+  VmapTable rows;             // the closed map (k_cmap_emit): a voxel beyond row_cap is numbered and not written
+  long long row_cap;
+};
+// clear | flag | stage, then emit: no host synchronisation in either; each returns the launches it made
+int launch_cmap_stage(const CmapWork& W, hipStream_t s);
+int launch_cmap_emit(const CmapWork& W, hipStream_t s);
+
 // ---- deskew of a scan under constant velocity (tl_deskew.hip) -------------
 struct DeskewArgs {
   const double* in;               // AoS xyz [3n]

@@ -2,7 +2,7 @@
 // lifetime, tl_api_frames.hip: HBM residency + search grids, tl_api_match.hip: the scanMatching driver, tl_api_comm.hip: multi-GPU
 // exchange, tl_api_submap.hip: device-resident submap, tl_api_feature.hip: PCA features, tl_api_seg.hip: segmentation,
 // tl_api_odom.hip: the whole odometry frame, tl_api_map.hip: its global map and registered scan, tl_api_vmap.hip: its merged
-// voxel map, tl_api_deskew.hip: its deskew, tl_api_place.hip: place recognition).
+// voxel map, tl_api_deskew.hip: its deskew, tl_api_place.hip: place recognition, tl_api_cmap.hip: the closed map).
 #pragma once
 
 #include <dlfcn.h>
@@ -406,6 +406,39 @@ struct GraphState {
   void release() { dws.release(); iws.release(); rec.release(); drop(); }
 };
 
+// the closed map (tl_api_cmap.hip): its configuration, its rows in id order and their table (the voxel map's
+// layout: k_vmap_read / k_vmap_box read them), what the last build reports and the poses it used, the reads' scratch.  A build's
+// staging is its own and freed when it ends
+struct CmapState {
+  tloam_closed_map_config cfg = {1.0, {0.0, 0.0, 0.0}, 0xF0, 0, 0};   // tloam_closed_map_default_config until configured
+  DBuf<unsigned long long> key;    // [cap] per id
+  DBuf<long long> n, qx, qy, qz;   // [cap] per id
+  DBuf<int> tab;                   // [tmask + 1] slot -> id, -1 free
+  size_t cap = 0;
+  unsigned long long tmask = 0;
+  bool built = false;              // a build has succeeded since the last drop
+  tloam_closed_map_info info{};    // of the last build (zero when dropped; capacity_voxels filled in when asked)
+  std::vector<double> poses;       // [16 K] column-major: the poses the last build used
+  DBuf<double> rd_c;
+  DBuf<long long> rd_n;
+  DBuf<unsigned long long> look, ctl;
+  void drop() {   // the closed map goes; its configuration and storage stay
+    built = false;
+    info = tloam_closed_map_info{};
+    poses.clear();
+  }
+  void release_rows() {
+    key.release(); n.release(); qx.release(); qy.release(); qz.release(); tab.release();
+    cap = 0;
+    tmask = 0;
+  }
+  void release() {
+    release_rows();
+    rd_c.release(); rd_n.release(); look.release(); ctl.release();
+    drop();
+  }
+};
+
 // up to four SoA clouds (x, y, z, n) a search grid is built over -- the registered targets, or any other cloud
 struct CloudRef { const double *x, *y, *z; size_t n; };
 }  // namespace tlh
@@ -424,6 +457,7 @@ struct tloam_ctx {
   PlaceState place;
   LoopState loop;
   GraphState graph;
+  CmapState cmap;
   int device = 0;
   hipStream_t stream = nullptr;
   KindData kd[kKinds];
@@ -751,6 +785,8 @@ int place_clouds_reserve(tloam_ctx* c, const size_t n[8]);
 void place_clouds_note(tloam_ctx* c, const tl::LoopSpan spans[8]);
 int arena_grow(tloam_ctx* c, size_t need_doubles);   // (tl_api_place.hip) the arena holds arena_used + need doubles
 void loop_release(tloam_ctx* c);                      // (tl_api_loop.hip) at destroy: the child contexts, the scratch
+// (tl_api_graph.hip) what tloam_graph_correct_pose computes, after its checks of the context: P'_k * rigid_inverse(P_k) * pose_in
+void graph_correct_pose(const tloam_ctx* c, size_t keyframe, const double pose_in[16], double pose_out[16]);
 int set_target_frame_from(tloam_ctx* c, const double* const xyz[4], const size_t n[4], hipMemcpyKind from);   // tl_api_frames.hip
 int voxel_down_sample_launch(tloam_ctx* c, const size_t n[2], const double voxel[2], int nseg, double* const out[2][3]);
 int build_grids_over(tloam_ctx* c, GridBuffers& G, const double radius[tl::kKinds], const CloudRef clouds[tl::kKinds],

@@ -95,6 +95,22 @@ class VoxelMapInfo(C.Structure):
     as_dict = _int_fields
 
 
+class ClosedMapConfig(C.Structure):
+    """tloam_closed_map_config: the closed map's voxel v, origin o, the cloud slots that take part (bit side * 4 + kind), the HBM
+    the first build reserves."""
+    _fields_ = [("voxel", C.c_double), ("origin", C.c_double * 3), ("cloud_mask", C.c_int32), ("reserved0", C.c_int32),
+                ("reserve_voxels", C.c_int64)]
+
+
+class ClosedMapInfo(C.Structure):
+    """tloam_closed_map_info."""
+    _fields_ = [("n_keyframes", C.c_int64), ("added_keyframes", C.c_int64), ("empty_keyframes", C.c_int64),
+                ("overflow_keyframes", C.c_int64), ("n_voxels", C.c_int64), ("n_points", C.c_int64),
+                ("capacity_voxels", C.c_int64), ("pose_source", C.c_int32), ("launches", C.c_int32)]
+
+    as_dict = _int_fields
+
+
 class DeskewConfig(C.Structure):
     """tloam_deskew_config: the deskew's switch, its time source (0 azimuth, 1 per-point times), the sweep's direction (+1
     counter-clockwise seen from +z), the azimuth it starts at and the sweep fraction the pose describes."""
@@ -380,6 +396,13 @@ def load_library():
         "tloam_graph_optimize": (C.c_int, [vp, C.POINTER(GraphInfo)]),
         "tloam_graph_read_poses": (C.c_int, [vp, sz, sz, dp]),
         "tloam_graph_correct_pose": (C.c_int, [vp, C.c_int64, dp, dp]),
+        "tloam_closed_map_default_config": (None, [C.POINTER(ClosedMapConfig)]),
+        "tloam_closed_map_configure": (C.c_int, [vp, C.POINTER(ClosedMapConfig)]),
+        "tloam_closed_map_get_info": (C.c_int, [vp, C.POINTER(ClosedMapInfo)]),
+        "tloam_closed_map_build": (C.c_int, [vp, C.c_int, dp, sz, C.POINTER(ClosedMapInfo)]),
+        "tloam_closed_map_read": (C.c_int, [vp, sz, sz, dp, C.POINTER(C.c_int64)]),
+        "tloam_closed_map_read_box": (C.c_int, [vp, dp, dp, C.c_int64, sz, C.POINTER(sz), dp, C.POINTER(C.c_int64)]),
+        "tloam_closed_map_read_poses": (C.c_int, [vp, sz, sz, dp]),
         "tloam_rccl_unique_id": (C.c_int, [vp]),
         "tloam_comm_init_rccl": (C.c_int, [vp, C.c_int, C.c_int, vp]),
         "tloam_comm_init_callback": (C.c_int, [vp, C.c_int, C.c_int, ALLREDUCE_FN, vp]),
@@ -417,7 +440,9 @@ EXPORTED_SYMBOLS = (
     "tloam_place_describe", "tloam_loop_default_config", "tloam_loop_configure", "tloam_loop_get_info",
     "tloam_place_set_keyframe_clouds", "tloam_place_read_keyframe_clouds", "tloam_loop_verify_pending", "tloam_loop_verify_pair",
     "tloam_loop_read_constraints", "tloam_graph_default_config", "tloam_graph_configure", "tloam_graph_solve", "tloam_graph_optimize",
-    "tloam_graph_read_poses", "tloam_graph_correct_pose", "tloam_rccl_unique_id", "tloam_comm_init_rccl",
+    "tloam_graph_read_poses", "tloam_graph_correct_pose", "tloam_closed_map_default_config", "tloam_closed_map_configure",
+    "tloam_closed_map_get_info", "tloam_closed_map_build", "tloam_closed_map_read", "tloam_closed_map_read_box",
+    "tloam_closed_map_read_poses", "tloam_rccl_unique_id", "tloam_comm_init_rccl",
     "tloam_comm_mailbox_export", "tloam_comm_init_mailbox",
     "tloam_comm_init_callback", "tloam_shard_range", "tloam_shard_ranges_frame", "tloam_se3_exp", "tloam_se3_log", "tloam_se3_plus",
 )
@@ -1008,6 +1033,63 @@ class HipRegistration:
                     "tloam_graph_correct_pose")
         return out.reshape(4, 4).T.copy()
 
+    # ---- the closed map: the keyframe clouds merged under corrected poses
+    def closed_map_configure(self, cfg: ClosedMapConfig | None = None, **over):
+        """the closed map's configuration (default_closed_map_config(**over) when cfg is None); empties it.  Kept across
+        odometry_reset."""
+        cfg = cfg if cfg is not None else default_closed_map_config(**over)
+        self._check(self.L.tloam_closed_map_configure(self.h, C.byref(cfg)), "tloam_closed_map_configure")
+
+    def closed_map_build(self, pose_source=1, poses=None) -> dict:
+        """builds the closed map from every keyframe's stored clouds, replacing the previous one -> info dict.  pose_source 0: the
+        stored keyframe poses, 1: the corrected poses of the last graph_optimize, 2: `poses` (K, 4, 4)"""
+        P, n = None, 0
+        if poses is not None:
+            P = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 4, 4).transpose(0, 2, 1))
+            n = len(P)
+        info = ClosedMapInfo()
+        self._check(self.L.tloam_closed_map_build(self.h, int(pose_source), _dp(P), n, C.byref(info)), "tloam_closed_map_build")
+        return info.as_dict()
+
+    def closed_map_info(self) -> dict:
+        info = ClosedMapInfo()
+        self._check(self.L.tloam_closed_map_get_info(self.h, C.byref(info)), "tloam_closed_map_get_info")
+        return info.as_dict()
+
+    def closed_map_read(self, first=0, count=None):
+        """voxels [first, first + count) in id order -> (centroids (m, 3) float64, counts (m,) int64); count None: to the end"""
+        if count is None:
+            count = max(self.closed_map_info()["n_voxels"] - int(first), 0)
+        m = int(count)
+        cen, cnt = np.zeros((max(m, 1), 3)), np.zeros(max(m, 1), np.int64)
+        self._check(self.L.tloam_closed_map_read(self.h, int(first), m, _dp(cen), _lp(cnt)), "tloam_closed_map_read")
+        return cen[:m].copy(), cnt[:m].copy()
+
+    def closed_map_read_box(self, lo, hi, min_count=1):
+        """the voxels whose centroid lies in [lo, hi] (inclusive, every axis) with N >= min_count, in id order ->
+        (centroids (m, 3), counts (m,))"""
+        lo = np.ascontiguousarray(lo, dtype=np.float64).reshape(3)
+        hi = np.ascontiguousarray(hi, dtype=np.float64).reshape(3)
+        n = C.c_size_t(0)
+        rc = self.L.tloam_closed_map_read_box(self.h, _dp(lo), _dp(hi), int(min_count), 0, C.byref(n), None, None)
+        if rc not in (0, -1) or (rc == -1 and n.value == 0):
+            self._check(rc, "tloam_closed_map_read_box")
+        m = n.value
+        cen, cnt = np.zeros((max(m, 1), 3)), np.zeros(max(m, 1), np.int64)
+        if m:
+            self._check(self.L.tloam_closed_map_read_box(self.h, _dp(lo), _dp(hi), int(min_count), m, C.byref(n), _dp(cen),
+                                                         _lp(cnt)), "tloam_closed_map_read_box")
+        return cen[: n.value].copy(), cnt[: n.value].copy()
+
+    def closed_map_poses(self, first=0, count=None):
+        """the poses keyframes [first, first + count) were built with, (m, 4, 4); count None: to the end"""
+        if count is None:
+            count = max(self.closed_map_info()["n_keyframes"] - int(first), 0)
+        m = int(count)
+        out = np.zeros((max(m, 1), 16))
+        self._check(self.L.tloam_closed_map_read_poses(self.h, int(first), m, _dp(out)), "tloam_closed_map_read_poses")
+        return out[:m].reshape(m, 4, 4).transpose(0, 2, 1).copy()
+
     def fitness(self):
         f, r = C.c_double(0), C.c_double(0)
         rc = self.L.tloam_fitness(self.h, C.byref(f), C.byref(r))
@@ -1242,6 +1324,13 @@ def default_graph_config(**over) -> GraphConfig:
     """tloam_graph_default_config (30 Gauss-Newton iterations of at most 20000 conjugate-gradient iterations, step_tol 1e-7,
     cg_tol 1e-10, the odometry and loop sigmas) with keyword overrides"""
     return _strict_config(GraphConfig, "tloam_graph_default_config", over)
+
+
+def default_closed_map_config(**over) -> ClosedMapConfig:
+    """tloam_closed_map_default_config (voxel 1.0, origin 0, cloud_mask 0xF0) with keyword overrides, e.g. voxel=0.25,
+    origin=(0, 0, 5), cloud_mask=0x0F"""
+    return _strict_config(ClosedMapConfig, "tloam_closed_map_default_config", over,
+                          {"origin": lambda v: (C.c_double * 3)(*[float(x) for x in v])})
 
 
 def default_submap_config(**over) -> SubmapConfig:
