@@ -1,5 +1,5 @@
 // tl_api_cmap.hip -- C ABI of the closed map (include/tloam_hip.h: tloam_closed_map_*; kernels in
-// tl_cmap.hip, reads by tl_vmap.hip's k_vmap_read / k_vmap_box).
+// tl_cmap.hip, reads by tlh::voxel_rows_read / _read_box of tl_api_vmap.hip).
 //
 // A build takes the host's keyframe table (PlaceState::kf: where every stored cloud lies in the arena) and a pose per keyframe,
 // uploads one span table and the poses, and enqueues four launches on the context's stream -- behind any k_place_clouds still in
@@ -52,15 +52,6 @@ int rows_reserve(tloam_ctx* c, size_t need) {
   M.cap = want;
   M.tmask = tsize - 1;
   return TLOAM_OK;
-}
-
-VmapReadArgs read_args(const CmapState& M) {
-  VmapReadArgs A;
-  memset(&A, 0, sizeof(A));
-  A.pkey = M.key.p; A.pn = M.n.p; A.pqx = M.qx.p; A.pqy = M.qy.p; A.pqz = M.qz.p;
-  A.voxel = M.cfg.voxel;
-  for (int a = 0; a < 3; ++a) A.origin[a] = M.cfg.origin[a];
-  return A;
 }
 
 // the enqueue, the waits and the counts of a build whose inputs have been checked; the closed map has been dropped
@@ -235,21 +226,7 @@ int tloam_closed_map_read(tloam_ctx* c, size_t first, size_t count, double* cent
   if (!c || c->nranks > 1) return TLOAM_E_INVALID;
   CmapState& M = c->cmap;
   if (!M.built) return TLOAM_E_NOT_READY;
-  const size_t nv = (size_t)M.info.n_voxels;
-  if (first > nv || count > nv - first) return TLOAM_E_INVALID;
-  if (count == 0 || (!centroids_aos && !counts)) return TLOAM_OK;
-  HIPC(c, hipSetDevice(c->device));
-  HIPC(c, hipStreamSynchronize(c->stream));   // (the scratch may be replaced)
-  HIPC(c, M.rd_c.reserve(3 * count)); HIPC(c, M.rd_n.reserve(count));
-  VmapReadArgs A = read_args(M);
-  A.first = first; A.count = count;
-  A.out_c = M.rd_c.p; A.out_n = M.rd_n.p;
-  launch_vmap_read(A, c->stream);
-  if (centroids_aos)
-    HIPC(c, hipMemcpyAsync(centroids_aos, M.rd_c.p, sizeof(double) * 3 * count, hipMemcpyDeviceToHost, c->stream));
-  if (counts) HIPC(c, hipMemcpyAsync(counts, M.rd_n.p, sizeof(int64_t) * count, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));
-  return TLOAM_OK;
+  return voxel_rows_read(c, voxel_rows_of(M, (size_t)M.info.n_voxels, "closed map"), first, count, centroids_aos, counts);
 }
 
 int tloam_closed_map_read_box(tloam_ctx* c, const double lo[3], const double hi[3], int64_t min_count, size_t capacity, size_t* n,
@@ -258,38 +235,8 @@ int tloam_closed_map_read_box(tloam_ctx* c, const double lo[3], const double hi[
   if (!c || !lo || !hi || !n || c->nranks > 1) return TLOAM_E_INVALID;
   CmapState& M = c->cmap;
   if (!M.built) return TLOAM_E_NOT_READY;
-  const size_t nv = (size_t)M.info.n_voxels;
-  if (nv == 0) return TLOAM_OK;
-  HIPC(c, hipSetDevice(c->device));
-  HIPC(c, hipStreamSynchronize(c->stream));   // (the scratch may be replaced)
-  const size_t blocks = (nv + 255) / 256;
-  HIPC(c, M.rd_c.reserve(3 * nv)); HIPC(c, M.rd_n.reserve(nv));
-  HIPC(c, M.look.reserve(blocks + 1)); HIPC(c, M.ctl.reserve(8));
-  HIPC(c, hipMemsetAsync(M.look.p, 0, sizeof(unsigned long long) * (blocks + 1), c->stream));
-  HIPC(c, hipMemsetAsync(M.ctl.p, 0, sizeof(unsigned long long) * 8, c->stream));
-  VmapReadArgs A = read_args(M);
-  A.first = 0; A.count = nv;
-  for (int a = 0; a < 3; ++a) { A.lo[a] = lo[a]; A.hi[a] = hi[a]; }
-  A.min_count = min_count;
-  A.out_c = M.rd_c.p; A.out_n = M.rd_n.p;
-  A.look = M.look.p; A.ctl = M.ctl.p;
-  launch_vmap_read_box(A, c->stream);
-  unsigned long long w[3];
-  HIPC(c, hipMemcpyAsync(w, M.ctl.p, sizeof(w), hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));
-  if (w[1]) {
-    c->last_error = "closed map: a look-back of k_vmap_box timed out";
-    return TLOAM_E_HIP;
-  }
-  const size_t m = (size_t)w[2];
-  *n = m;
-  if (m == 0) return TLOAM_OK;
-  if (capacity < m) return TLOAM_E_INVALID;
-  if (centroids_aos)
-    HIPC(c, hipMemcpyAsync(centroids_aos, M.rd_c.p, sizeof(double) * 3 * m, hipMemcpyDeviceToHost, c->stream));
-  if (counts) HIPC(c, hipMemcpyAsync(counts, M.rd_n.p, sizeof(int64_t) * m, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));
-  return TLOAM_OK;
+  return voxel_rows_read_box(c, voxel_rows_of(M, (size_t)M.info.n_voxels, "closed map"), lo, hi, min_count, capacity, n,
+                             centroids_aos, counts);
 }
 
 int tloam_closed_map_read_poses(tloam_ctx* c, size_t first, size_t count, double* poses) {

@@ -74,15 +74,6 @@ VmapStageWork stage_work(tloam_ctx* c) {   // the staged frame's buffers, as k_v
   return W;
 }
 
-VmapReadArgs read_args(const VmapState& V) {
-  VmapReadArgs A;
-  memset(&A, 0, sizeof(A));
-  A.pkey = V.key.p; A.pn = V.n.p; A.pqx = V.qx.p; A.pqy = V.qy.p; A.pqz = V.qz.p;
-  A.voxel = V.cfg.voxel;
-  for (int a = 0; a < 3; ++a) A.origin[a] = V.cfg.origin[a];
-  return A;
-}
-
 }  // namespace
 
 namespace tlh {
@@ -171,6 +162,59 @@ void vmap_frame_end(tloam_ctx* c, bool accepted) {
   V.pending_seq = 0;
 }
 
+int voxel_rows_read(tloam_ctx* c, const VoxelRows& R, size_t first, size_t count, double* centroids_aos, int64_t* counts) {
+  if (first > R.nv || count > R.nv - first) return TLOAM_E_INVALID;
+  if (count == 0 || (!centroids_aos && !counts)) return TLOAM_OK;
+  HIPC(c, hipSetDevice(c->device));
+  HIPC(c, hipStreamSynchronize(c->stream));   // (the scratch may be replaced)
+  HIPC(c, R.rd_c.reserve(3 * count)); HIPC(c, R.rd_n.reserve(count));
+  VmapReadArgs A = R.base;
+  A.first = first; A.count = count;
+  A.out_c = R.rd_c.p; A.out_n = R.rd_n.p;
+  launch_vmap_read(A, c->stream);
+  if (centroids_aos)
+    HIPC(c, hipMemcpyAsync(centroids_aos, R.rd_c.p, sizeof(double) * 3 * count, hipMemcpyDeviceToHost, c->stream));
+  if (counts) HIPC(c, hipMemcpyAsync(counts, R.rd_n.p, sizeof(int64_t) * count, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  return TLOAM_OK;
+}
+
+int voxel_rows_read_box(tloam_ctx* c, const VoxelRows& R, const double lo[3], const double hi[3], int64_t min_count, size_t capacity,
+                        size_t* n, double* centroids_aos, int64_t* counts) {
+  const size_t nv = R.nv;
+  if (nv == 0) return TLOAM_OK;
+  HIPC(c, hipSetDevice(c->device));
+  HIPC(c, hipStreamSynchronize(c->stream));   // (the scratch may be replaced)
+  const size_t blocks = (nv + 255) / 256;
+  HIPC(c, R.rd_c.reserve(3 * nv)); HIPC(c, R.rd_n.reserve(nv));
+  HIPC(c, R.look.reserve(blocks + 1)); HIPC(c, R.ctl.reserve(8));
+  HIPC(c, hipMemsetAsync(R.look.p, 0, sizeof(unsigned long long) * (blocks + 1), c->stream));
+  HIPC(c, hipMemsetAsync(R.ctl.p, 0, sizeof(unsigned long long) * 8, c->stream));
+  VmapReadArgs A = R.base;
+  A.first = 0; A.count = nv;
+  for (int a = 0; a < 3; ++a) { A.lo[a] = lo[a]; A.hi[a] = hi[a]; }
+  A.min_count = min_count;
+  A.out_c = R.rd_c.p; A.out_n = R.rd_n.p;
+  A.look = R.look.p; A.ctl = R.ctl.p;
+  launch_vmap_read_box(A, c->stream);
+  unsigned long long w[3];
+  HIPC(c, hipMemcpyAsync(w, R.ctl.p, sizeof(w), hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  if (w[1]) {
+    c->last_error = std::string(R.name) + ": a look-back of k_vmap_box timed out";
+    return TLOAM_E_HIP;
+  }
+  const size_t m = (size_t)w[2];
+  *n = m;
+  if (m == 0) return TLOAM_OK;
+  if (capacity < m) return TLOAM_E_INVALID;
+  if (centroids_aos)
+    HIPC(c, hipMemcpyAsync(centroids_aos, R.rd_c.p, sizeof(double) * 3 * m, hipMemcpyDeviceToHost, c->stream));
+  if (counts) HIPC(c, hipMemcpyAsync(counts, R.rd_n.p, sizeof(int64_t) * m, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  return TLOAM_OK;
+}
+
 }  // namespace tlh
 
 extern "C" {
@@ -227,61 +271,15 @@ int tloam_voxel_map_get_info(tloam_ctx* c, tloam_voxel_map_info* info) {
 
 int tloam_voxel_map_read(tloam_ctx* c, size_t first, size_t count, double* centroids_aos, int64_t* counts) {
   if (!c || c->nranks > 1) return TLOAM_E_INVALID;
-  VmapState& V = c->vmap;
-  const size_t nv = (size_t)V.n_voxels;
-  if (first > nv || count > nv - first) return TLOAM_E_INVALID;
-  if (count == 0 || (!centroids_aos && !counts)) return TLOAM_OK;
-  HIPC(c, hipSetDevice(c->device));
-  HIPC(c, hipStreamSynchronize(c->stream));   // (the scratch may be replaced)
-  HIPC(c, V.rd_c.reserve(3 * count)); HIPC(c, V.rd_n.reserve(count));
-  VmapReadArgs A = read_args(V);
-  A.first = first; A.count = count;
-  A.out_c = V.rd_c.p; A.out_n = V.rd_n.p;
-  launch_vmap_read(A, c->stream);
-  if (centroids_aos)
-    HIPC(c, hipMemcpyAsync(centroids_aos, V.rd_c.p, sizeof(double) * 3 * count, hipMemcpyDeviceToHost, c->stream));
-  if (counts) HIPC(c, hipMemcpyAsync(counts, V.rd_n.p, sizeof(int64_t) * count, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));
-  return TLOAM_OK;
+  return voxel_rows_read(c, voxel_rows_of(c->vmap, (size_t)c->vmap.n_voxels, "voxel map"), first, count, centroids_aos, counts);
 }
 
 int tloam_voxel_map_read_box(tloam_ctx* c, const double lo[3], const double hi[3], int64_t min_count, size_t capacity, size_t* n,
                              double* centroids_aos, int64_t* counts) {
   if (n) *n = 0;
   if (!c || !lo || !hi || !n || c->nranks > 1) return TLOAM_E_INVALID;
-  VmapState& V = c->vmap;
-  const size_t nv = (size_t)V.n_voxels;
-  if (nv == 0) return TLOAM_OK;
-  HIPC(c, hipSetDevice(c->device));
-  HIPC(c, hipStreamSynchronize(c->stream));   // (the scratch may be replaced)
-  const size_t blocks = (nv + 255) / 256;
-  HIPC(c, V.rd_c.reserve(3 * nv)); HIPC(c, V.rd_n.reserve(nv));
-  HIPC(c, V.look.reserve(blocks + 1)); HIPC(c, V.ctl.reserve(8));
-  HIPC(c, hipMemsetAsync(V.look.p, 0, sizeof(unsigned long long) * (blocks + 1), c->stream));
-  HIPC(c, hipMemsetAsync(V.ctl.p, 0, sizeof(unsigned long long) * 8, c->stream));
-  VmapReadArgs A = read_args(V);
-  A.first = 0; A.count = nv;
-  for (int a = 0; a < 3; ++a) { A.lo[a] = lo[a]; A.hi[a] = hi[a]; }
-  A.min_count = min_count;
-  A.out_c = V.rd_c.p; A.out_n = V.rd_n.p;
-  A.look = V.look.p; A.ctl = V.ctl.p;
-  launch_vmap_read_box(A, c->stream);
-  unsigned long long w[3];
-  HIPC(c, hipMemcpyAsync(w, V.ctl.p, sizeof(w), hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));
-  if (w[1]) {
-    c->last_error = "voxel map: a look-back of k_vmap_box timed out";
-    return TLOAM_E_HIP;
-  }
-  const size_t m = (size_t)w[2];
-  *n = m;
-  if (m == 0) return TLOAM_OK;
-  if (capacity < m) return TLOAM_E_INVALID;
-  if (centroids_aos)
-    HIPC(c, hipMemcpyAsync(centroids_aos, V.rd_c.p, sizeof(double) * 3 * m, hipMemcpyDeviceToHost, c->stream));
-  if (counts) HIPC(c, hipMemcpyAsync(counts, V.rd_n.p, sizeof(int64_t) * m, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));
-  return TLOAM_OK;
+  return voxel_rows_read_box(c, voxel_rows_of(c->vmap, (size_t)c->vmap.n_voxels, "voxel map"), lo, hi, min_count, capacity, n,
+                             centroids_aos, counts);
 }
 
 }  // extern "C"

@@ -1,34 +1,24 @@
 // tl_cmap.hip -- the device side of the closed map (tl_api_cmap.hip): every keyframe's stored clouds,
-// each under its keyframe's pose, merged into one grid of the voxel map's kind (tl_vmap.hip: key, q, N, Q, centroid).
+// each under its keyframe's pose, merged into one grid of the voxel map's kind (tl_voxel.hpp: key, q, N, Q, centroid).
 //
 // Launches of a build, the same four for any number of keyframes, spans and points (no host synchronisation between the first
 // three):
 //   k_cmap_clear    grid x 256   empties the build table, the look-back words, the control words and the keyframes' flags
 //   k_cmap_flag     grid x 256   per point: its span from its global index, transform, quantise; a finite point beyond the grid
 //                                raises its keyframe's flag (a plain store of 1: every writer writes the same value)
-//   k_cmap_stage    grid x 256   per point of an unflagged keyframe: the same, then as k_vmap_stage -- runs of equal keys in a wave
-//                                summed by shuffles, the run's head enters the table and takes the 64-bit atomic minimum of the
+//   k_cmap_stage    grid x 256   per point of an unflagged keyframe: the same, then runs of equal keys in a wave summed by
+//                                shuffles (wave_run_sums), the run's head enters the table and takes the 64-bit atomic minimum of the
 //                                global index, its tail adds N and Q with int64 atomics; the distinct voxels are counted
 //   k_cmap_emit     grid x 256   per point: the leader of a voxel numbers it after every earlier leader (single-pass look-back scan
 //                                over start tickets, bounded) and writes its row and its table entry: the build is the commit
 // Reads are k_vmap_read / k_vmap_box on the closed map's rows.
-// Compiled with -ffp-contract=off: the transform rounds as k_map_front's and k_vmap_stage's, s and q as DESIGN.md 14 states them.
+// Compiled with -ffp-contract=off: map_transform_point and vmap_quantise round as DESIGN.md 13 and 14 state them.
 #include <algorithm>
 
-#include "tl_common.hpp"
+#include "tl_voxel.hpp"
 
 namespace tl {
 namespace {
-
-constexpr unsigned long long kFree = ~0ull;   // build-table key of a free slot (a voxel key has bit 63 clear)
-constexpr unsigned long long kLookTimeout = 100000000ull;   // ~1 s of wall_clock64 (100 MHz)
-
-__device__ __forceinline__ unsigned long long mix64(unsigned long long x) {  // splitmix64 finaliser (as tl_vmap.hip)
-  x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
-  x ^= x >> 27; x *= 0x94d049bb133111ebull;
-  x ^= x >> 31;
-  return x;
-}
 
 // the last span of [lo, hi] that starts at or before g
 __device__ __forceinline__ int span_of(const CmapSpan* sp, int lo, int hi, long long g) {
@@ -56,60 +46,15 @@ __device__ __forceinline__ void block_spans(const CmapWork& W, int s_span[2]) {
   __syncthreads();
 }
 
-// point g (< W.n): its keyframe, and 0: not finite, 1: in the grid (key, q), 2: finite and beyond the grid
-__device__ __forceinline__ int cmap_point(const CmapWork& W, long long g, int s_lo, int s_hi, int* kf, unsigned long long* key,
-                                          unsigned q[3]) {
+// point g (< W.n): its keyframe, and where it falls in the grid (key and q when inside)
+__device__ __forceinline__ VmapCell cmap_point(const CmapWork& W, long long g, int s_lo, int s_hi, int* kf, unsigned long long* key,
+                                               unsigned q[3]) {
   const CmapSpan S = W.span[span_of(W.span, s_lo, s_hi, g)];
   const double* x = W.arena + S.off + 3 * (g - S.start);
   *kf = S.kf;
   double p[3];
   map_transform_point(W.pose + 16 * (size_t)S.kf, x[0], x[1], x[2], &p[0], &p[1], &p[2]);
-  if (!(__builtin_isfinite(p[0]) && __builtin_isfinite(p[1]) && __builtin_isfinite(p[2]))) return 0;
-  bool over = false;
-  unsigned long long k = 0ull;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const double s = (p[a] - W.origin[a]) / W.voxel;
-    const double f = floor(s);
-    if (!(fabs(f) < (double)(1ll << kVmapBits))) { over = true; continue; }   // (also an infinite s)
-    q[a] = (unsigned)(long long)floor((s - f) * kVmapQScale + 0.5);   // s - f and the scaling are exact: q in [0, 2^24]
-    k |= (unsigned long long)((long long)f + (1ll << kVmapBits)) << (21 * a);
-  }
-  *key = k;
-  return over ? 2 : 1;
-}
-
-// (as tl_vmap.hip's) the exclusive prefix of this block's total over the blocks numbered below `bid`, in a single pass: status
-// 1 = the block's own total, 2 = the total up to and including it.  Blocks number themselves by a start ticket, so every block
-// waited on has started; the wait is still bounded (~1 s: then `*fault` is raised and the host discards the build).  Thread 0 only
-__device__ unsigned long long lookback_prefix(unsigned long long* look, long long bid, unsigned long long block_total,
-                                              unsigned long long* fault) {
-  unsigned long long prefix = 0ull;
-  if (bid == 0) {
-    __hip_atomic_store(&look[0], (2ull << 62) | block_total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return 0ull;
-  }
-  __hip_atomic_store(&look[bid], (1ull << 62) | block_total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const unsigned long long t0 = wall_clock64();
-  unsigned spins = 0;
-  for (long long p = bid - 1;;) {
-    const unsigned long long w = __hip_atomic_load(&look[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned st = (unsigned)(w >> 62);
-    if (st == 0u) {
-      if ((++spins & 63u) == 0 && wall_clock64() - t0 > kLookTimeout) {
-        __hip_atomic_store(fault, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __threadfence();   // (raised before the wrong prefix below can be read)
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
-      continue;
-    }
-    prefix += w & ~(3ull << 62);
-    if (st == 2u) break;
-    --p;
-  }
-  __hip_atomic_store(&look[bid], (2ull << 62) | (prefix + block_total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  return prefix;
+  return vmap_quantise(p, W.origin, W.voxel, key, q);
 }
 
 __global__ __launch_bounds__(256) void k_cmap_clear(CmapWork W, long long emit_blocks) {
@@ -133,18 +78,12 @@ __global__ __launch_bounds__(256) void k_cmap_flag(CmapWork W) {
   int kf;
   unsigned long long key;
   unsigned q[3];
-  if (cmap_point(W, g, s_span[0], s_span[1], &kf, &key, q) == 2) W.kf_over[kf] = 1;
+  if (cmap_point(W, g, s_span[0], s_span[1], &kf, &key, q) == kVmapBeyond) W.kf_over[kf] = 1;
 }
 
 // one point's voxel entered in the build table: its slot; *fresh when the voxel was not there
 __device__ __forceinline__ int cmap_enter(const CmapWork& W, unsigned long long key, unsigned long long g, bool* fresh) {
-  unsigned long long h = mix64(key) & W.fmask;
-  for (;;) {
-    const unsigned long long prev = atomicCAS(&W.fkey[h], kFree, key);
-    if (prev == kFree) { *fresh = true; break; }
-    if (prev == key) break;
-    h = (h + 1) & W.fmask;
-  }
+  const unsigned long long h = table_enter(W.fkey, W.fmask, key, fresh);
   atomicMin(&W.flead[h], g);
   return (int)h;
 }
@@ -160,42 +99,19 @@ __global__ __launch_bounds__(256) void k_cmap_stage(CmapWork W) {
   unsigned q[3] = {0u, 0u, 0u};
   if (g < W.n) {
     int kf;
-    ok = cmap_point(W, g, s_span[0], s_span[1], &kf, &key, q) == 1 && W.kf_over[kf] == 0;
+    ok = cmap_point(W, g, s_span[0], s_span[1], &kf, &key, q) == kVmapInside && W.kf_over[kf] == 0;
   }
   const unsigned long long okb = __ballot(ok);
   const size_t T = (size_t)W.fmask + 1;
   int slot = -1;
   if (kRuns) {
-    // runs of equal keys among the wave's consecutive lanes.  A run may cross a span: the keys decide, and its head is still its
-    // smallest global index
-    const unsigned long long kprev = __shfl_up(key, 1, 64), knext = __shfl_down(key, 1, 64);
-    const bool ok_prev = lane > 0 && ((okb >> (lane - 1)) & 1ull);
-    const bool ok_next = lane < 63 && ((okb >> (lane + 1)) & 1ull);
-    const bool head = ok && !(ok_prev && kprev == key);
-    const bool tail = ok && !(ok_next && knext == key);
-    const unsigned long long heads = __ballot(head);
-    const unsigned long long upto = lane == 63 ? ~0ull : ((1ull << (lane + 1)) - 1ull);
-    const int hl = (heads & upto) ? 63 - __clzll(heads & upto) : 0;   // the head of this lane's run
-    unsigned v[4] = {ok ? 1u : 0u, q[0], q[1], q[2]};   // inclusive prefix sums over the wave (64 * 2^24 fits 32 bits)
+    // a run may cross a span: the keys decide, and its head is still its smallest global index
+    const WaveRun r = wave_run_sums(ok, key, q);
+    if (r.head) slot = cmap_enter(W, key, (unsigned long long)g, &fresh);
+    slot = __shfl(slot, r.head_lane, 64);
+    if (r.tail) {
 #pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const unsigned o = __shfl_up(v[k], off, 64);
-        if (lane >= off) v[k] += o;
-      }
-    }
-    unsigned before[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const unsigned b = __shfl(v[k], hl > 0 ? hl - 1 : 0, 64);
-      before[k] = hl > 0 ? b : 0u;
-    }
-    if (head) slot = cmap_enter(W, key, (unsigned long long)g, &fresh);
-    slot = __shfl(slot, hl, 64);
-    if (tail) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) atomicAdd(&W.fsum[k * T + slot], (unsigned long long)(v[k] - before[k]));
+      for (int k = 0; k < 4; ++k) atomicAdd(&W.fsum[k * T + slot], (unsigned long long)r.sum[k]);
     }
   } else if (ok) {
     slot = cmap_enter(W, key, (unsigned long long)g, &fresh);
@@ -217,23 +133,14 @@ __global__ __launch_bounds__(256) void k_cmap_emit(CmapWork W, long long nblocks
   __shared__ unsigned long long s_wave[4];
   __shared__ unsigned long long s_prefix;
   __shared__ long long s_bid;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) s_bid = (long long)atomicAdd(&W.ctl[2], 1ull);
-  __syncthreads();
-  const long long bid = s_bid;
+  const int tid = threadIdx.x;
+  const long long bid = block_ticket(&W.ctl[2], &s_bid);
   const long long g = bid * 256 + tid;
   const int h = g < W.n ? W.slot_of_pt[g] : -1;
   const bool leader = h >= 0 && W.flead[h] == (unsigned long long)g;
-  const unsigned long long bal = __ballot(leader);
-  if (lane == 0) s_wave[wave] = (unsigned long long)__popcll(bal);
-  __syncthreads();
-  int pos = __popcll(bal & ((1ull << lane) - 1ull)), total = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    pos += w < wave ? (int)s_wave[w] : 0;
-    total += (int)s_wave[w];
-  }
-  if (tid == 0) s_prefix = lookback_prefix(W.look, bid, (unsigned long long)total, &W.ctl[3]);
+  int pos, total;
+  block_flag_scan(leader, s_wave, &pos, &total);
+  if (tid == 0) s_prefix = lookback_prefix(W.look, bid, (unsigned long long)total, LookFaultDevice{&W.ctl[3]});
   __syncthreads();
   const long long id = (long long)s_prefix + pos;
   if (leader && id < W.row_cap) {
@@ -245,8 +152,7 @@ __global__ __launch_bounds__(256) void k_cmap_emit(CmapWork W, long long nblocks
     P.pqx[id] = (long long)W.fsum[T + h];
     P.pqy[id] = (long long)W.fsum[2 * T + h];
     P.pqz[id] = (long long)W.fsum[3 * T + h];
-    for (unsigned long long t = mix64(key) & P.pmask;; t = (t + 1) & P.pmask)
-      if (atomicCAS(&P.ptab[t], -1, (int)id) == -1) break;
+    id_table_insert(P.ptab, P.pmask, key, (int)id);
   }
   if (bid == nblocks - 1 && tid == 0) W.ctl[4] = s_prefix + (unsigned long long)total;
 }

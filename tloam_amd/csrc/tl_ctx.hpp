@@ -767,6 +767,31 @@ int vmap_frame_reserve(tloam_ctx* c, size_t n);
 int vmap_stage_launch(tloam_ctx* c, const double pose[16], size_t n);
 int vmap_stage_collect(tloam_ctx* c, tloam_odom_stats* st);
 void vmap_frame_end(tloam_ctx* c, bool accepted);
+// tl_api_vmap.hip: the one read path of voxel rows -- the merged voxel map's and the closed map's (k_vmap_read / k_vmap_box).
+// What a read needs of either state: the rows as the kernels see them, the reads' scratch, the voxels held, the errors' name
+struct VoxelRows {
+  tl::VmapReadArgs base;
+  DBuf<double>& rd_c;
+  DBuf<long long>& rd_n;
+  DBuf<unsigned long long>& look;
+  DBuf<unsigned long long>& ctl;
+  size_t nv;
+  const char* name;
+};
+template <class State>
+VoxelRows voxel_rows_of(State& S, size_t nv, const char* name) {
+  tl::VmapReadArgs A;
+  memset(&A, 0, sizeof(A));
+  A.pkey = S.key.p; A.pn = S.n.p; A.pqx = S.qx.p; A.pqy = S.qy.p; A.pqz = S.qz.p;
+  A.voxel = S.cfg.voxel;
+  for (int a = 0; a < 3; ++a) A.origin[a] = S.cfg.origin[a];
+  return VoxelRows{A, S.rd_c, S.rd_n, S.look, S.ctl, nv, name};
+}
+// ids [first, first + count) / the voxels in the box with N >= min_count in id order, to the host; the caller has checked its
+// context (and that a closed map is built)
+int voxel_rows_read(tloam_ctx* c, const VoxelRows& R, size_t first, size_t count, double* centroids_aos, int64_t* counts);
+int voxel_rows_read_box(tloam_ctx* c, const VoxelRows& R, const double lo[3], const double hi[3], int64_t min_count, size_t capacity,
+                        size_t* n, double* centroids_aos, int64_t* counts);
 // tl_api_deskew.hip: the frame's deskew -- sized and its times uploaded after the scan's upload, launched after the segmentation's
 // (the refused-time flag read with the frame's first wait), committed when the frame ends
 int deskew_frame_upload(tloam_ctx* c, const double* t_sec, size_t n, tloam_odom_stats* st);

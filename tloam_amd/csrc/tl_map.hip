@@ -7,7 +7,7 @@
 //                                  SoA scratch; the same launch empties the hash table and finishes the min bound of the
 //                                  transformed cloud (block partials, the last block by ticket) -- k_submap_front's work for one segment
 //   k_map_insert      grid x 256   voxel -> hash slot; the slot's member list, count and smallest member (atomics)
-//   k_map_emit        grid x 256   leaders in first-occurrence order (single-pass look-back scan, as k_vox_emit); a voxel of up to
+//   k_map_emit        grid x 256   leaders in first-occurrence order (the look-back scan of tl_voxel.hpp); a voxel of up to
 //                                  kMapVoxLocal members averaged by its leader, a larger one booked; the count to pinned memory
 //   k_map_scatter     grid x 256   the members of the booked voxels into one piece each
 //   k_map_big         <= 1024 x 256  one workgroup per booked voxel: members ordered by index, summed in that order
@@ -20,19 +20,10 @@
 #include <algorithm>
 #include <atomic>
 
-#include "tl_common.hpp"
+#include "tl_voxel.hpp"
 
 namespace tl {
 namespace {
-
-constexpr unsigned long long kEmptyKey = ~0ull;   // VoxelWork::keys of a free slot (tl_submap.hip kEmpty)
-
-__device__ __forceinline__ unsigned long long mix64(unsigned long long x) {  // splitmix64 finaliser (as tl_submap.hip)
-  x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
-  x ^= x >> 27; x *= 0x94d049bb133111ebull;
-  x ^= x >> 31;
-  return x;
-}
 
 __device__ __forceinline__ bool in_box(const MapVoxWork& W, double x, double y, double z) {   // inclusive, as Crop
   return x >= W.lo && x <= W.hi && y >= W.lo && y <= W.hi && z >= W.lo && z <= W.hi;
@@ -45,7 +36,7 @@ __global__ __launch_bounds__(256) void k_map_front(MapFrontArgs A, MapVoxWork W,
   const size_t i = (size_t)blockIdx.x * 256 + tid, stride = (size_t)gridDim.x * 256;
   if (blockIdx.x == 0 && tid == 0) { W.ctl[0] = 0; W.ctl[2] = 0; W.ctl[3] = 0; W.ctl[4] = 0; }
   for (size_t t = i; t <= W.mask; t += stride) {
-    W.keys[t] = kEmptyKey;
+    W.keys[t] = kFree;
     W.head[t] = -1;
     W.first[t] = 0x7fffffff;
     W.count[t] = 0;
@@ -107,12 +98,7 @@ __global__ __launch_bounds__(256) void k_map_insert(MapVoxWork W) {
     return;
   }
   const unsigned long long key = (unsigned long long)ix | ((unsigned long long)iy << 21) | ((unsigned long long)iz << 42);
-  unsigned long long h = mix64(key) & W.mask;
-  for (;;) {
-    const unsigned long long prev = atomicCAS(&W.keys[h], kEmptyKey, key);
-    if (prev == kEmptyKey || prev == key) break;
-    h = (h + 1) & W.mask;
-  }
+  const unsigned long long h = table_enter(W.keys, W.mask, key);
   W.slot_of_pt[i] = (int)h;
   W.next[i] = atomicExch(&W.head[h], (int)i);
   atomicMin(&W.first[h], (int)i);
@@ -121,20 +107,17 @@ __global__ __launch_bounds__(256) void k_map_insert(MapVoxWork W) {
 
 // per point: a leader of a voxel of up to kMapVoxLocal members orders them by index in LDS (the order AddPoint is called in,
 // :379-385), sums and averages; its output position -- the leaders in front of it, i.e. first-occurrence order -- comes from a
-// single-pass scan over the blocks inside the launch (k_vox_emit's look-back).  The leader of a larger voxel books the voxel for
+// single-pass scan over the blocks inside the launch (tl_voxel.hpp).  The leader of a larger voxel books the voxel for
 // k_map_big: a number, the output position, a piece of `members`
 __global__ __launch_bounds__(256) void k_map_emit(MapVoxWork W, int nblocks) {
   __shared__ int s_mem[kMapVoxLocal * 256];   // s_mem[k * 256 + t]: member k of thread t's voxel (conflict-free columns)
   __shared__ unsigned long long s_wave[4];
   __shared__ unsigned long long s_prefix;
   __shared__ int s_bid;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
+  // places in the order the blocks start when the grid is larger than the device holds at once: see k_vox_emit
   int bid = (int)blockIdx.x;
-  if (W.use_ticket) {   // places in the order the blocks start (a grid larger than the device holds at once): see k_vox_emit
-    if (tid == 0) s_bid = atomicAdd(&W.ctl[2], 1);
-    __syncthreads();
-    bid = s_bid;
-  }
+  if (W.use_ticket) bid = block_ticket(&W.ctl[2], &s_bid);
   const size_t i = (size_t)bid * 256 + tid;
   const int h = i < W.n ? W.slot_of_pt[i] : -1;
   const bool leader = h >= 0 && W.first[h] == (int)i;
@@ -157,53 +140,13 @@ __global__ __launch_bounds__(256) void k_map_emit(MapVoxWork W, int nblocks) {
     const double dn = (double)m;
     sx /= dn; sy /= dn; sz /= dn;
   }
-  // ---- the leader's output position: block-exclusive scan of the flags ...
-  const unsigned long long flag = leader ? 1ull : 0ull;
-  unsigned long long incl = flag;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const unsigned long long o = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += o;
-  }
-  if (lane == 63) s_wave[wave] = incl;
-  __syncthreads();
-  unsigned long long wave_base = 0ull, block_total = 0ull;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    if (w < wave) wave_base += s_wave[w];
-    block_total += s_wave[w];
-  }
-  // ... and the blocks in front (status 1: the block's own count, 2: the count up to and including the block; bounded wait)
-  if (tid == 0) {
-    unsigned long long prefix = 0ull;
-    if (bid == 0) {
-      __hip_atomic_store(&W.leader[0], (2ull << 62) | block_total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-      __hip_atomic_store(&W.leader[bid], (1ull << 62) | block_total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const unsigned long long t0 = wall_clock64();
-      unsigned spins = 0;
-      for (int p = bid - 1;;) {
-        const unsigned long long w = __hip_atomic_load(&W.leader[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned st = (unsigned)(w >> 62);
-        if (st == 0u) {
-          if ((++spins & 63u) == 0 && wall_clock64() - t0 > 100000000ull) {   // ~1 s: a block in front never started
-            if (W.fault) { __hip_atomic_store(W.fault, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); __threadfence_system(); }
-            break;   // (the frame's result is discarded by the host, tl_api_map.hip)
-          }
-          __builtin_amdgcn_s_sleep(1);
-          continue;
-        }
-        prefix += w & ~(3ull << 62);
-        if (st == 2u) break;
-        --p;
-      }
-      __hip_atomic_store(&W.leader[bid], (2ull << 62) | (prefix + block_total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    s_prefix = prefix;
-  }
+  // ---- the leader's output position: the leaders in front of it in the block, and in the blocks in front
+  unsigned long long before, block_total;
+  block_packed_scan(leader ? 1ull : 0ull, s_wave, &before, &block_total);
+  if (tid == 0) s_prefix = lookback_prefix(W.leader, bid, block_total, LookFaultHost{W.fault});   // (the host discards a faulted frame)
   __syncthreads();
   if (leader) {
-    const unsigned long long p = s_prefix + wave_base + (incl - flag);
+    const unsigned long long p = s_prefix + before;
     if (m <= kMapVoxLocal) {
       W.ox[p] = sx; W.oy[p] = sy; W.oz[p] = sz;
     } else {
@@ -216,14 +159,8 @@ __global__ __launch_bounds__(256) void k_map_emit(MapVoxWork W, int nblocks) {
   if (bid == nblocks - 1 && tid < 8) {   // the block that holds the last point: the total = the size of the down-sampled cloud
     const unsigned long long total = s_prefix + block_total;
     if (tid == 0) W.n_out[0] = total;
-    // ... and straight to the host (tlh::wait_segment: word 7 = check_mix(sequence number) XOR seg_word of the payload words)
-    unsigned long long w = tid == 0 ? total : tid == 2 ? (unsigned long long)W.ctl[0] : 0ull;
-    unsigned long long x = tid < 7 ? seg_word(w, tid) : 0ull;
-    x ^= __shfl_xor(x, 1, 64);
-    x ^= __shfl_xor(x, 2, 64);
-    x ^= __shfl_xor(x, 4, 64);
-    if (tid == 7) w = check_mix(W.host_seq) ^ x;
-    __hip_atomic_store(&W.host_seg[tid], w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    // ... and straight to the host
+    post_host_segment(W.host_seg, W.host_seq, tid == 0 ? total : tid == 2 ? (unsigned long long)W.ctl[0] : 0ull, tid);
   }
 }
 
@@ -246,7 +183,7 @@ __global__ __launch_bounds__(256) void k_map_big(MapVoxWork W) {
   __shared__ int s_idx[kMapSortLds];
   __shared__ double s_c[3][256];
   __shared__ int s_wave[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int nbig = W.ctl[3];
   for (int q = (int)blockIdx.x; q < nbig; q += (int)gridDim.x) {
     const int4 b = W.bigq[q];
@@ -288,17 +225,9 @@ __global__ __launch_bounds__(256) void k_map_big(MapVoxWork W) {
       for (size_t base = (size_t)W.first[h]; base < W.n && found < m; base += 256) {
         const size_t j = base + tid;
         const bool hit = j < W.n && W.slot_of_pt[j] == h;
-        const unsigned long long bal = __ballot(hit);
-        if (lane == 0) s_wave[wave] = __popcll(bal);
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-          before += w < wave ? s_wave[w] : 0;
-          total += s_wave[w];
-        }
+        int pos, total;
+        block_flag_scan(hit, s_wave, &pos, &total);
         if (hit) {
-          const int pos = before + __popcll(bal & ((1ull << lane) - 1ull));
           s_c[0][pos] = W.x[j]; s_c[1][pos] = W.y[j]; s_c[2][pos] = W.z[j];
         }
         __syncthreads();
@@ -339,7 +268,7 @@ void launch_map_voxel(const MapFrontArgs& A, const MapVoxWork& W, hipStream_t s)
   hipLaunchKernelGGL(k_map_big, dim3((unsigned)std::min(W.big_max, 1024)), dim3(256), 0, s, W);
 }
 
-int map_emit_resident_blocks(int device_cus) {   // as vox_emit_resident_blocks (tl_submap.hip), for k_map_emit
+int map_emit_resident_blocks(int device_cus) {   // vox_emit_resident_blocks (tl_submap.hip) for k_map_emit
   static std::atomic<int> per_cu_cache{-1};
   int per_cu = per_cu_cache.load(std::memory_order_relaxed);
   if (per_cu < 0) {

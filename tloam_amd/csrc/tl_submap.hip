@@ -22,20 +22,11 @@
 #include <algorithm>
 #include <string.h>
 
-#include "tl_common.hpp"
+#include "tl_voxel.hpp"
 
 namespace tl {
 
 namespace {
-constexpr unsigned long long kEmpty = ~0ull;
-
-__device__ __forceinline__ unsigned long long mix64(unsigned long long x) {  // splitmix64 finaliser
-  x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
-  x ^= x >> 27; x *= 0x94d049bb133111ebull;
-  x ^= x >> 31;
-  return x;
-}
-
 struct Mat16 { double m[16]; };  // column-major 4x4
 
 // Open3D TransformPoints: new = T * (x, y, z, 1); point = new.head<3>() / new(3).  Each row is accumulated
@@ -138,7 +129,7 @@ __global__ __launch_bounds__(256) void k_vox_min2(VoxelJob J, VoxelWork W, int e
   __shared__ int s_last;
   if (blockIdx.x == 0 && threadIdx.x == 0) { W.overflow[0] = 0; W.leader_scan[0] = 0ull; W.leader_scan[1] = 0ull; }
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i <= J.mask; i += (size_t)gridDim.x * 256) {
-    W.keys[i] = kEmpty;
+    W.keys[i] = kFree;
     W.cnt[i] = kNoHead;
   }
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i <= (size_t)emit_blocks; i += (size_t)gridDim.x * 256) W.leader[i] = 0ull;
@@ -206,17 +197,12 @@ __global__ __launch_bounds__(256) void k_vox_insert2(VoxelJob J, VoxelWork W) {
   // is the empty marker: reported like an index out of range
   const unsigned long long key = (unsigned long long)ix | ((unsigned long long)iy << 21) | ((unsigned long long)iz << 42) |
                                  ((unsigned long long)seg << 63);
-  if (key == kEmpty) {
+  if (key == kFree) {
     W.overflow[0] = 1;
     W.slot_of_pt[i] = -1;
     return;
   }
-  unsigned long long h = mix64(key) & J.mask;
-  for (;;) {
-    const unsigned long long prev = atomicCAS(&W.keys[h], kEmpty, key);
-    if (prev == kEmpty || prev == key) break;
-    h = (h + 1) & J.mask;
-  }
+  const unsigned long long h = table_enter(W.keys, J.mask, key);
   W.slot_of_pt[i] = (int)h;
   W.urank[i] = (int)atomicExch(&W.cnt[h], (unsigned long long)i);   // next[i] = the old head (-1: none), head = i
 }
@@ -237,18 +223,14 @@ __global__ __launch_bounds__(256) void k_vox_emit(VoxelJob J, VoxelWork W, int n
   __shared__ unsigned long long s_wave[4];
   __shared__ unsigned long long s_prefix;
   __shared__ int s_bid;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   // A block only ever waits for blocks of LOWER place.  While the whole grid is resident on the device (the host checks:
   // vox_emit_resident_blocks) the place is the block index -- every lower block is running.  (A ticket taken at the start of
   // every block -- ~500 returning atomics on one word, served one after the other -- was a quarter of the launch: 0.0913-0.0921
   // against 0.0881-0.0886 ms per update, round 4.)  A larger grid, a partitioned or CU-masked device: places in the order the
   // blocks START (W.use_ticket), so that a block only ever waits for blocks that started before it.  The wait is bounded either way.
   int bid = (int)blockIdx.x;
-  if (W.use_ticket) {
-    if (tid == 0) s_bid = (int)atomicAdd(&W.leader_scan[0], 1ull);
-    __syncthreads();
-    bid = s_bid;
-  }
+  if (W.use_ticket) bid = block_ticket(&W.leader_scan[0], &s_bid);
   const size_t i = (size_t)bid * 256 + tid;
   const int h = i < J.n ? W.slot_of_pt[i] : -1;
   const int seg = i >= J.n0 ? 1 : 0;
@@ -295,53 +277,13 @@ __global__ __launch_bounds__(256) void k_vox_emit(VoxelJob J, VoxelWork W, int n
     const double dn = (double)m;
     sx /= dn; sy /= dn; sz /= dn;
   }
-  // ---- the leader's output position: leaders of its segment in front of it.  Block-exclusive scan of the packed flags ...
-  const unsigned long long flag = leader ? (seg ? (1ull << 32) : 1ull) : 0ull;
-  unsigned long long incl = flag;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const unsigned long long o = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += o;
-  }
-  if (lane == 63) s_wave[wave] = incl;
+  // ---- the leader's output position: the leaders of its segment in front of it, in the block (the two segments' flags packed
+  // in one word) and in the blocks in front
+  unsigned long long in_block, block_total;
+  block_packed_scan(leader ? (seg ? (1ull << 32) : 1ull) : 0ull, s_wave, &in_block, &block_total);
+  if (tid == 0) s_prefix = lookback_prefix(W.leader, bid, block_total, LookFaultHost{W.fault});   // (the host discards a faulted update)
   __syncthreads();
-  unsigned long long wave_base = 0ull, block_total = 0ull;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    if (w < wave) wave_base += s_wave[w];
-    block_total += s_wave[w];
-  }
-  // ... and the blocks in front: publish this block's count, then look back (status 1: the block's own count, 2: the count of
-  // everything up to and including the block)
-  if (tid == 0) {
-    unsigned long long prefix = 0ull;
-    if (bid == 0) {
-      __hip_atomic_store(&W.leader[0], (2ull << 62) | block_total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-      __hip_atomic_store(&W.leader[bid], (1ull << 62) | block_total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const unsigned long long t0 = wall_clock64();
-      unsigned spins = 0;
-      for (int p = bid - 1;;) {
-        const unsigned long long w = __hip_atomic_load(&W.leader[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned st = (unsigned)(w >> 62);
-        if (st == 0u) {
-          if ((++spins & 63u) == 0 && wall_clock64() - t0 > 100000000ull) {   // ~1 s: a block in front never started
-            if (W.fault) { __hip_atomic_store(W.fault, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); __threadfence_system(); }
-            break;   // (the update's result is discarded by the host, tl_api_submap.hip)
-          }
-          __builtin_amdgcn_s_sleep(1);
-          continue;
-        }
-        prefix += w & ~(3ull << 62);
-        if (st == 2u) break;
-        --p;
-      }
-      __hip_atomic_store(&W.leader[bid], (2ull << 62) | (prefix + block_total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    s_prefix = prefix;
-  }
-  __syncthreads();
-  const unsigned long long before = s_prefix + wave_base + (incl - flag);
+  const unsigned long long before = s_prefix + in_block;
   if (leader) {
     const unsigned long long p = seg ? ((before >> 32) & kCntMask) : (before & kCntMask);
     W.out[seg][0][p] = sx; W.out[seg][1][p] = sy; W.out[seg][2][p] = sz;
@@ -353,13 +295,7 @@ __global__ __launch_bounds__(256) void k_vox_emit(VoxelJob J, VoxelWork W, int n
     if (W.host_seg) {  // ... and straight to the host: every leader's stores precede this block's in no particular order, so the
                        // host reads the clouds only through the stream (it waits for this word, then enqueues behind the launch)
       unsigned long long w = tid == 0 ? n0_out : tid == 1 ? n1_out : tid == 2 ? (unsigned long long)W.overflow[0] : 0ull;
-      // word 7 = check_mix(sequence number) XOR seg_word of the payload words (tlh::wait_segment: a torn segment reads as "not there yet")
-      unsigned long long x = tid < 7 ? seg_word(w, tid) : 0ull;
-      x ^= __shfl_xor(x, 1, 64);
-      x ^= __shfl_xor(x, 2, 64);
-      x ^= __shfl_xor(x, 4, 64);
-      if (tid == 7) w = check_mix(W.host_seq) ^ x;
-      __hip_atomic_store(&W.host_seg[tid], w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      post_host_segment(W.host_seg, W.host_seq, w, tid);
     }
   }
 }
@@ -459,7 +395,7 @@ __global__ __launch_bounds__(256) void k_submap_front(RingArgs R, int ring_count
   const int lb = s * (int)gridDim.x + (int)blockIdx.x, nlb = 2 * (int)gridDim.x;   // this block among the assembling ones
   if (lb == 0 && threadIdx.x == 0) { W.overflow[0] = 0; W.leader_scan[0] = 0ull; W.leader_scan[1] = 0ull; }
   for (size_t t = (size_t)lb * 256 + threadIdx.x; t <= J.mask; t += (size_t)nlb * 256) {
-    W.keys[t] = kEmpty;
+    W.keys[t] = kFree;
     W.cnt[t] = kNoHead;
   }
   for (size_t t = (size_t)lb * 256 + threadIdx.x; t <= (size_t)emit_blocks; t += (size_t)nlb * 256) W.leader[t] = 0ull;

@@ -10,84 +10,15 @@
 //                                in leader order by a single-pass look-back scan; counts and overflow to pinned memory
 // an accepted frame (after the frame's last wait, not waited for):
 //   k_vmap_commit   grid x 256   per frame voxel: N and Q added into its id's row; a new one keyed and entered in the table
-// Compiled with -ffp-contract=off: the transform rounds as k_map_front's, s, q and the centroids as DESIGN.md 14 states them.
+// Compiled with -ffp-contract=off: map_transform_point, vmap_quantise and centroid round as DESIGN.md 13 and 14 state them.
 #include <string.h>
 
 #include <algorithm>
 
-#include "tl_common.hpp"
+#include "tl_voxel.hpp"
 
 namespace tl {
 namespace {
-
-constexpr unsigned long long kFree = ~0ull;   // frame-table key of a free slot (a voxel key has bit 63 clear)
-constexpr unsigned long long kLookTimeout = 100000000ull;   // ~1 s of wall_clock64 (100 MHz)
-
-__device__ __forceinline__ unsigned long long mix64(unsigned long long x) {  // splitmix64 finaliser (as tl_map.hip)
-  x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
-  x ^= x >> 27; x *= 0x94d049bb133111ebull;
-  x ^= x >> 31;
-  return x;
-}
-
-__device__ __forceinline__ long long key_axis(unsigned long long key, int a) {
-  return (long long)((key >> (21 * a)) & 0x1fffffull) - (1ll << kVmapBits);
-}
-
-// c = o + v * ((double) i + ((double) Q / (double) N) * 2^-24), in that order
-__device__ __forceinline__ double centroid(double o, double v, long long i, long long Q, long long N) {
-  return o + v * ((double)i + ((double)Q / (double)N) * (1.0 / kVmapQScale));
-}
-
-// The exclusive prefix of this block's `block_total` over the blocks numbered below `bid`, in a single pass: status 1 = the
-// block's own total, 2 = the total up to and including it (as k_map_emit).  Blocks number themselves by a start ticket, so every
-// block waited on has started; the wait is still bounded (~1 s: then `*fault` is raised and the result is discarded by the host).
-// Thread 0 only.
-__device__ unsigned long long lookback_prefix(unsigned long long* look, int bid, unsigned long long block_total,
-                                              unsigned long long* fault) {
-  unsigned long long prefix = 0ull;
-  if (bid == 0) {
-    __hip_atomic_store(&look[0], (2ull << 62) | block_total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return 0ull;
-  }
-  __hip_atomic_store(&look[bid], (1ull << 62) | block_total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const unsigned long long t0 = wall_clock64();
-  unsigned spins = 0;
-  for (int p = bid - 1;;) {
-    const unsigned long long w = __hip_atomic_load(&look[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned st = (unsigned)(w >> 62);
-    if (st == 0u) {
-      if ((++spins & 63u) == 0 && wall_clock64() - t0 > kLookTimeout) {
-        __hip_atomic_store(fault, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __threadfence();   // (raised before the wrong prefix below can be read)
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
-      continue;
-    }
-    prefix += w & ~(3ull << 62);
-    if (st == 2u) break;
-    --p;
-  }
-  __hip_atomic_store(&look[bid], (2ull << 62) | (prefix + block_total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  return prefix;
-}
-
-// block-wide exclusive scan of one flag per thread: (position in the block, the block's total)
-__device__ __forceinline__ void block_flag_scan(bool flag, unsigned long long* s_wave, int* pos, int* total) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const unsigned long long bal = __ballot(flag);
-  if (lane == 0) s_wave[wave] = (unsigned long long)__popcll(bal);
-  __syncthreads();
-  int before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    before += w < wave ? (int)s_wave[w] : 0;
-    all += (int)s_wave[w];
-  }
-  *pos = before + __popcll(bal & ((1ull << lane) - 1ull));
-  *total = all;
-}
 
 __global__ __launch_bounds__(256) void k_vmap_clear(VmapStageWork W, int emit_blocks) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
@@ -111,64 +42,25 @@ __global__ __launch_bounds__(256) void k_vmap_stage(VmapStageWork W) {
     double p[3];
     if (W.sx) { p[0] = W.sx[i]; p[1] = W.sy[i]; p[2] = W.sz[i]; }
     else map_transform_point(W.M, W.aos[3 * i], W.aos[3 * i + 1], W.aos[3 * i + 2], &p[0], &p[1], &p[2]);
-    if (__builtin_isfinite(p[0]) && __builtin_isfinite(p[1]) && __builtin_isfinite(p[2])) {
-      ok = true;
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        const double s = (p[a] - W.origin[a]) / W.voxel;
-        const double f = floor(s);
-        if (!(fabs(f) < (double)(1ll << kVmapBits))) { over = true; continue; }   // (also an infinite s)
-        q[a] = (unsigned)(long long)floor((s - f) * kVmapQScale + 0.5);   // s - f and the scaling are exact: q in [0, 2^24]
-        key |= (unsigned long long)((long long)f + (1ll << kVmapBits)) << (21 * a);
-      }
-      if (over) ok = false;
-    }
+    const VmapCell cell = vmap_quantise(p, W.origin, W.voxel, &key, q);
+    ok = cell == kVmapInside;
+    over = cell == kVmapBeyond;
   }
   if (over) __hip_atomic_store(&W.ctl[0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  // runs of equal keys among the wave's consecutive lanes (neighbouring returns of a ring share their voxel)
-  const unsigned long long kprev = __shfl_up(key, 1, 64), knext = __shfl_down(key, 1, 64);
-  const unsigned long long okb = __ballot(ok);
-  const bool ok_prev = lane > 0 && ((okb >> (lane - 1)) & 1ull);
-  const bool ok_next = lane < 63 && ((okb >> (lane + 1)) & 1ull);
-  const bool head = ok && !(ok_prev && kprev == key);
-  const bool tail = ok && !(ok_next && knext == key);
-  const unsigned long long heads = __ballot(head);
-  const unsigned long long upto = lane == 63 ? ~0ull : ((1ull << (lane + 1)) - 1ull);
-  const int hl = (heads & upto) ? 63 - __clzll(heads & upto) : 0;   // the head of this lane's run
-  // inclusive prefix sums over the wave (64 * 2^24 fits 32 bits)
-  unsigned v[4] = {ok ? 1u : 0u, q[0], q[1], q[2]};
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const unsigned o = __shfl_up(v[k], off, 64);
-      if (lane >= off) v[k] += o;
-    }
-  }
-  unsigned before[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const unsigned b = __shfl(v[k], hl > 0 ? hl - 1 : 0, 64);
-    before[k] = hl > 0 ? b : 0u;
-  }
+  const WaveRun r = wave_run_sums(ok, key, q);
   int slot = -1;
-  if (head) {
-    unsigned long long h = mix64(key) & W.fmask;
-    for (;;) {
-      const unsigned long long prev = atomicCAS(&W.fkey[h], kFree, key);
-      if (prev == kFree || prev == key) break;
-      h = (h + 1) & W.fmask;
-    }
-    slot = (int)h;
-    atomicMin(&W.flead[h], (int)i);   // the run's head is its smallest index
+  if (r.head) {
+    slot = (int)table_enter(W.fkey, W.fmask, key);
+    atomicMin(&W.flead[slot], (int)i);   // the run's head is its smallest index
   }
-  slot = __shfl(slot, hl, 64);
+  slot = __shfl(slot, r.head_lane, 64);
   if (i < W.n) W.slot_of_pt[i] = ok ? slot : -1;
-  if (tail) {
+  if (r.tail) {
     const size_t T = (size_t)W.fmask + 1;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) atomicAdd(&W.fsum[k * T + slot], (unsigned long long)(v[k] - before[k]));
+    for (int k = 0; k < 4; ++k) atomicAdd(&W.fsum[k * T + slot], (unsigned long long)r.sum[k]);
   }
+  const unsigned long long okb = __ballot(ok);
   if (lane == 0 && okb) atomicAdd(&W.ctl[1], (unsigned long long)__popcll(okb));
 }
 
@@ -179,9 +71,7 @@ __global__ __launch_bounds__(256) void k_vmap_emit(VmapStageWork W, int nblocks)
   __shared__ unsigned long long s_prefix;
   __shared__ int s_bid;
   const int tid = threadIdx.x;
-  if (tid == 0) s_bid = (int)atomicAdd(&W.ctl[2], 1ull);
-  __syncthreads();
-  const int bid = s_bid;
+  const int bid = block_ticket(&W.ctl[2], &s_bid);
   const size_t i = (size_t)bid * 256 + tid;
   const int h = i < W.n ? W.slot_of_pt[i] : -1;
   const bool leader = h >= 0 && W.flead[h] == (int)i;
@@ -197,7 +87,7 @@ __global__ __launch_bounds__(256) void k_vmap_emit(VmapStageWork W, int nblocks)
   const bool fresh = leader && found < 0;
   int pos, total;
   block_flag_scan(fresh, s_wave, &pos, &total);
-  if (tid == 0) s_prefix = lookback_prefix(W.look, bid, (unsigned long long)total, &W.ctl[3]);
+  if (tid == 0) s_prefix = lookback_prefix(W.look, bid, (unsigned long long)total, LookFaultDevice{&W.ctl[3]});
   __syncthreads();
   if (leader) W.fid[h] = fresh ? (int)(W.base + (long long)(s_prefix + pos)) : found;
   if (bid == nblocks - 1 && tid < 8) {   // the block that holds the last point: the frame's new voxels
@@ -206,13 +96,7 @@ __global__ __launch_bounds__(256) void k_vmap_emit(VmapStageWork W, int nblocks)
                          : tid == 1 ? __hip_atomic_load(&W.ctl[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
                          : tid == 2 ? __hip_atomic_load(&W.ctl[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
                          : tid == 3 ? __hip_atomic_load(&W.ctl[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
-    // (word 7 = check_mix(sequence number) XOR seg_word of the payload words: tlh::wait_segment)
-    unsigned long long x = tid < 7 ? seg_word(w, tid) : 0ull;
-    x ^= __shfl_xor(x, 1, 64);
-    x ^= __shfl_xor(x, 2, 64);
-    x ^= __shfl_xor(x, 4, 64);
-    if (tid == 7) w = check_mix(W.host_seq) ^ x;
-    __hip_atomic_store(&W.host_seg[tid], w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    post_host_segment(W.host_seg, W.host_seq, w, tid);
   }
 }
 
@@ -230,8 +114,7 @@ __global__ __launch_bounds__(256) void k_vmap_commit(VmapStageWork W, VmapTable 
   if (id >= W.base) {
     P.pkey[id] = key;
     P.pn[id] = n; P.pqx[id] = qx; P.pqy[id] = qy; P.pqz[id] = qz;
-    for (unsigned long long t = mix64(key) & P.pmask;; t = (t + 1) & P.pmask)
-      if (atomicCAS(&P.ptab[t], -1, id) == -1) break;
+    id_table_insert(P.ptab, P.pmask, key, id);
   } else {
     P.pn[id] += n; P.pqx[id] += qx; P.pqy[id] += qy; P.pqz[id] += qz;
   }
@@ -240,9 +123,7 @@ __global__ __launch_bounds__(256) void k_vmap_commit(VmapStageWork W, VmapTable 
 __global__ __launch_bounds__(256) void k_vmap_rehash(VmapTable P, size_t n) {
   const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (id >= n) return;
-  const unsigned long long key = P.pkey[id];
-  for (unsigned long long t = mix64(key) & P.pmask;; t = (t + 1) & P.pmask)
-    if (atomicCAS(&P.ptab[t], -1, (int)id) == -1) break;
+  id_table_insert(P.ptab, P.pmask, P.pkey[id], (int)id);
 }
 
 __device__ __forceinline__ void voxel_centroid(const VmapReadArgs& A, size_t id, double c[3], long long* N) {
@@ -270,9 +151,7 @@ __global__ __launch_bounds__(256) void k_vmap_box(VmapReadArgs A, int nblocks) {
   __shared__ unsigned long long s_prefix;
   __shared__ int s_bid;
   const int tid = threadIdx.x;
-  if (tid == 0) s_bid = (int)atomicAdd(&A.ctl[0], 1ull);
-  __syncthreads();
-  const int bid = s_bid;
+  const int bid = block_ticket(&A.ctl[0], &s_bid);
   const size_t id = A.first + (size_t)bid * 256 + tid;
   double c[3] = {0.0, 0.0, 0.0};
   long long n = 0;
@@ -285,7 +164,7 @@ __global__ __launch_bounds__(256) void k_vmap_box(VmapReadArgs A, int nblocks) {
   }
   int pos, total;
   block_flag_scan(sel, s_wave, &pos, &total);
-  if (tid == 0) s_prefix = lookback_prefix(A.look, bid, (unsigned long long)total, &A.ctl[1]);
+  if (tid == 0) s_prefix = lookback_prefix(A.look, bid, (unsigned long long)total, LookFaultDevice{&A.ctl[1]});
   __syncthreads();
   if (sel) {
     const size_t p = (size_t)(s_prefix + pos);

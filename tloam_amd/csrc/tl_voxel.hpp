@@ -1,0 +1,234 @@
+// tl_voxel.hpp -- what the device voxel grids share: the submap's down-sample (tl_submap.hip), the
+// global map (tl_map.hip), the merged voxel map (tl_vmap.hip) and the closed map (tl_cmap.hip).  One definition each of the key
+// hash and the two table inserts, of the block scans, of the single-pass look-back with its one bound, of the eight-word post to
+// the host, and of the voxel map's key / q arithmetic and its run sums.  Device code only.
+// An includer must be compiled with -ffp-contract=off: vmap_quantise and centroid are the bit-for-bit contract of DESIGN.md 14.
+#pragma once
+
+#include "tl_common.hpp"
+
+namespace tl {
+
+// The key of a free slot in every grid's open-addressing table: a voxel key never has all bits set (the voxel map's has bit 63
+// clear; the submap's all-ones key is refused at its insert).
+constexpr unsigned long long kFree = ~0ull;
+
+// splitmix64 finaliser: the slot a key starts probing at is mix64(key) & mask.
+__device__ __forceinline__ unsigned long long mix64(unsigned long long x) {
+  x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
+  x ^= x >> 27; x *= 0x94d049bb133111ebull;
+  x ^= x >> 31;
+  return x;
+}
+
+// `key` entered in the table keys[mask + 1] (free slots hold kFree, linear probing): the slot that holds it, the same for every
+// caller with that key.  The table's load is at most 1/2, so a slot is found.  *was_free: this call took the slot.
+__device__ __forceinline__ unsigned long long table_enter(unsigned long long* keys, unsigned long long mask, unsigned long long key,
+                                                          bool* was_free) {
+  unsigned long long h = mix64(key) & mask;
+  for (;;) {
+    const unsigned long long prev = atomicCAS(&keys[h], kFree, key);
+    if (prev == kFree) { *was_free = true; break; }
+    if (prev == key) break;
+    h = (h + 1) & mask;
+  }
+  return h;
+}
+__device__ __forceinline__ unsigned long long table_enter(unsigned long long* keys, unsigned long long mask, unsigned long long key) {
+  bool unused = false;
+  return table_enter(keys, mask, key, &unused);
+}
+
+// `id` entered in the slot -> id table ptab[pmask + 1] (-1: free) at the first free slot from its key's.  Each id is entered once.
+__device__ __forceinline__ void id_table_insert(int* ptab, unsigned long long pmask, unsigned long long key, int id) {
+  for (unsigned long long t = mix64(key) & pmask;; t = (t + 1) & pmask)
+    if (atomicCAS(&ptab[t], -1, id) == -1) break;
+}
+
+// The block's place in the order the blocks START, from a counter that is zero before the launch; ends in a barrier.  A block
+// that looks back over places below its own then only ever waits for blocks that are running.
+template <typename Bid, typename Ctr>
+__device__ __forceinline__ Bid block_ticket(Ctr* ticket, Bid* s_bid) {
+  if (threadIdx.x == 0) *s_bid = (Bid)atomicAdd(ticket, (Ctr)1);
+  __syncthreads();
+  return *s_bid;
+}
+
+// Block-wide (256 threads) exclusive scan of one flag per thread by ballot and popcount: *pos = flags set in the threads below
+// this one, *total = flags set in the block.  One barrier; s_wave[4] is free again after the caller's next barrier.
+template <typename T>
+__device__ __forceinline__ void block_flag_scan(bool flag, T* s_wave, int* pos, int* total) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const unsigned long long bal = __ballot(flag);
+  if (lane == 0) s_wave[wave] = (T)__popcll(bal);
+  __syncthreads();
+  int before = 0, all = 0;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    before += w < wave ? (int)s_wave[w] : 0;
+    all += (int)s_wave[w];
+  }
+  *pos = before + __popcll(bal & ((1ull << lane) - 1ull));
+  *total = all;
+}
+
+// The same for a 64-bit word per thread that packs several counts (the submap's two segments in one word), by shuffles:
+// *before = the sum of `v` over the threads below this one, *total = over the block.  No field may overflow into the next.
+__device__ __forceinline__ void block_packed_scan(unsigned long long v, unsigned long long* s_wave, unsigned long long* before,
+                                                  unsigned long long* total) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  unsigned long long incl = v;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const unsigned long long o = __shfl_up(incl, off, 64);
+    if (lane >= off) incl += o;
+  }
+  if (lane == 63) s_wave[wave] = incl;
+  __syncthreads();
+  unsigned long long wave_base = 0ull, block_total = 0ull;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    if (w < wave) wave_base += s_wave[w];
+    block_total += s_wave[w];
+  }
+  *before = wave_base + (incl - v);
+  *total = block_total;
+}
+
+// The single-pass look-back: the sum of `block_total` over the blocks of places below `bid`.  look[] (one word per block, zero
+// before the launch) carries a status in its top two bits -- 1: the block's own total, 2: the total up to and including the block
+// -- over 62 bits of count; all its accesses are relaxed atomics at agent scope.  A block publishes 1, walks down adding totals
+// until it meets a 2, then publishes its own 2.  Thread 0 only.
+// The wait on a word that is still 0 is BOUNDED, here and nowhere else: kLookTimeout ticks of wall_clock64 (100 MHz: ~1 s),
+// the clock polled every 64th spin with s_sleep(1) between spins.  Places come from block_ticket, or from blockIdx while the host
+// knows the whole grid resident, so the bound is never met on a healthy device; when it is, `fault.raise()` runs before the
+// (wrong) prefix is published, and the host discards the result.  The two ways of raising:
+constexpr unsigned long long kLookTimeout = 100000000ull;
+struct LookFaultDevice {   // a 64-bit control word in device memory, read by the host after the stream has drained
+  unsigned long long* word;
+  __device__ __forceinline__ void raise() const {
+    __hip_atomic_store(word, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __threadfence();
+  }
+};
+struct LookFaultHost {     // a 32-bit word of pinned host memory (null: none), read by the host while the stream runs
+  unsigned* word;
+  __device__ __forceinline__ void raise() const {
+    if (word) { __hip_atomic_store(word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); __threadfence_system(); }
+  }
+};
+template <typename Bid, typename Fault>
+__device__ __forceinline__ unsigned long long lookback_prefix(unsigned long long* look, Bid bid, unsigned long long block_total,
+                                                              Fault fault) {
+  unsigned long long prefix = 0ull;
+  if (bid == 0) {
+    __hip_atomic_store(&look[0], (2ull << 62) | block_total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  } else {
+    __hip_atomic_store(&look[bid], (1ull << 62) | block_total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long t0 = wall_clock64();
+    unsigned spins = 0;
+    for (Bid p = bid - 1;;) {
+      const unsigned long long w = __hip_atomic_load(&look[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const unsigned st = (unsigned)(w >> 62);
+      if (st == 0u) {
+        if ((++spins & 63u) == 0 && wall_clock64() - t0 > kLookTimeout) {   // a block in front never started
+          fault.raise();
+          break;
+        }
+        __builtin_amdgcn_s_sleep(1);
+        continue;
+      }
+      prefix += w & ~(3ull << 62);
+      if (st == 2u) break;
+      --p;
+    }
+    __hip_atomic_store(&look[bid], (2ull << 62) | (prefix + block_total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  return prefix;
+}
+
+// Eight words to a pinned 64-byte segment the host polls (tlh::wait_segment): lanes 0..6 bring the payload words in `w`, lane 7
+// stores check_mix(host_seq) XOR seg_word of the seven, so that a torn or stale segment reads as "not there yet".  One
+// system-scope store per lane.  Called by threads 0..7 of one wave, all of them.
+__device__ __forceinline__ void post_host_segment(unsigned long long* host_seg, unsigned long long host_seq, unsigned long long w,
+                                                  int tid) {
+  unsigned long long x = tid < 7 ? seg_word(w, tid) : 0ull;
+  x ^= __shfl_xor(x, 1, 64);
+  x ^= __shfl_xor(x, 2, 64);
+  x ^= __shfl_xor(x, 4, 64);
+  if (tid == 7) w = check_mix(host_seq) ^ x;
+  __hip_atomic_store(&host_seg[tid], w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// ---- the voxel map's grid (the merged voxel map and the closed map): DESIGN.md 14 states this arithmetic, and here it is ----
+// Per axis s = (p - origin) / voxel, i = floor(s), q = floor((s - i) * 2^24 + 0.5) in [0, 2^24] (s - i and the scaling are
+// exact); the key packs i + 2^kVmapBits of each axis in 21 bits.  A point with |i| >= 2^kVmapBits on an axis (an infinite s
+// too) is beyond the grid: *key and q[] are then not to be used.
+enum VmapCell { kVmapNotFinite = 0, kVmapInside = 1, kVmapBeyond = 2 };
+__device__ __forceinline__ VmapCell vmap_quantise(const double p[3], const double origin[3], double voxel, unsigned long long* key,
+                                                  unsigned q[3]) {
+  if (!(__builtin_isfinite(p[0]) && __builtin_isfinite(p[1]) && __builtin_isfinite(p[2]))) return kVmapNotFinite;
+  bool over = false;
+  unsigned long long k = 0ull;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const double s = (p[a] - origin[a]) / voxel;
+    const double f = floor(s);
+    if (!(fabs(f) < (double)(1ll << kVmapBits))) { over = true; continue; }
+    q[a] = (unsigned)(long long)floor((s - f) * kVmapQScale + 0.5);
+    k |= (unsigned long long)((long long)f + (1ll << kVmapBits)) << (21 * a);
+  }
+  *key = k;
+  return over ? kVmapBeyond : kVmapInside;
+}
+
+// the voxel index of axis `a` out of a key
+__device__ __forceinline__ long long key_axis(unsigned long long key, int a) {
+  return (long long)((key >> (21 * a)) & 0x1fffffull) - (1ll << kVmapBits);
+}
+
+// c = o + v * ((double) i + ((double) Q / (double) N) * 2^-24), in that order
+__device__ __forceinline__ double centroid(double o, double v, long long i, long long Q, long long N) {
+  return o + v * ((double)i + ((double)Q / (double)N) * (1.0 / kVmapQScale));
+}
+
+// Runs of equal keys among a wave's consecutive `ok` lanes (neighbouring returns of a ring share their voxel), summed by
+// shuffles so that a run costs the table one insert and four atomics instead of one each per point.  Called by the whole wave.
+// head / tail: this lane begins / ends its run; head_lane: the lane that begins it (the run's smallest point index);
+// sum[]: at the tail, the run's N, Qx, Qy, Qz (64 * 2^24 fits 32 bits).  What a lane that is not ok passes in q is ignored.
+struct WaveRun {
+  bool head, tail;
+  int head_lane;
+  unsigned sum[4];
+};
+__device__ __forceinline__ WaveRun wave_run_sums(bool ok, unsigned long long key, const unsigned q[3]) {
+  const int lane = threadIdx.x & 63;
+  WaveRun r;
+  const unsigned long long kprev = __shfl_up(key, 1, 64), knext = __shfl_down(key, 1, 64);
+  const unsigned long long okb = __ballot(ok);
+  const bool ok_prev = lane > 0 && ((okb >> (lane - 1)) & 1ull);
+  const bool ok_next = lane < 63 && ((okb >> (lane + 1)) & 1ull);
+  r.head = ok && !(ok_prev && kprev == key);
+  r.tail = ok && !(ok_next && knext == key);
+  const unsigned long long heads = __ballot(r.head);
+  const unsigned long long upto = lane == 63 ? ~0ull : ((1ull << (lane + 1)) - 1ull);
+  const int hl = (heads & upto) ? 63 - __clzll(heads & upto) : 0;
+  r.head_lane = hl;
+  unsigned v[4] = {ok ? 1u : 0u, q[0], q[1], q[2]};   // inclusive prefix sums over the wave
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const unsigned o = __shfl_up(v[k], off, 64);
+      if (lane >= off) v[k] += o;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const unsigned b = __shfl(v[k], hl > 0 ? hl - 1 : 0, 64);
+    r.sum[k] = v[k] - (hl > 0 ? b : 0u);
+  }
+  return r;
+}
+
+}  // namespace tl
