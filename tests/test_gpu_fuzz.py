@@ -47,3 +47,14 @@ def test_random_submap_sequences_and_feature_clouds_bit_for_bit(hip_module):
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
     assert "rows sweep ok: 200 submap sequences + 200 feature clouds" in r.stdout
+
+
+def test_whole_pipeline_contexts_give_their_memory_back(hip_module):
+    """The second phase of tests/tools/churn_contexts.py alone, twelve rounds (nine after the baseline x 64 MB per configured store
+    = 576 MB >= 512 MB: one store leaked per round breaks the tool's 256 MB bound): a context with every optional store
+    configured, an odometry run with keyframes, a verified pair, graph_optimize, closed_map_build, reads, destroy -- the device
+    and host footprint stay put and every round computes the first round's bits."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "tools", "churn_contexts.py"), "0", "12"],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
+    assert "pipeline churn ok: 12 rounds" in r.stdout

@@ -76,33 +76,27 @@ int tloam_create(const tloam_tls_config* cfg, int device_id, tloam_ctx** out) {
   c->fused_large = getenv("TLOAM_FUSED_LARGE") != nullptr;
   if (const char* e = getenv("TLOAM_PLANNED_SWEEPS")) c->dbg_planned_sweeps = atoi(e);
   memset(&c->stats, 0, sizeof(c->stats));
-  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipHostMalloc((void**)&c->h_state, sizeof(GnState) * kMirrorSlots, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-      hipHostMalloc((void**)&c->h_small, sizeof(double) * 4096, hipHostMallocDefault) != hipSuccess) {
-    delete c;
+  // pinned host memory: the state's mirror and a small scratch; and, device-visible, what the kernels write their results into
+  // (result slots, bounding-box rows, fault words): required -- there is no copy + synchronise variant of the paths that use them
+  constexpr size_t kBoxDoubles = (size_t)kKinds * 64 * 6 + 8;
+  const unsigned flags = hipHostMallocMapped | hipHostMallocCoherent;
+  const bool up = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess &&
+                  c->h_state.alloc(kMirrorSlots, flags) == hipSuccess && c->h_small.alloc(4096, hipHostMallocDefault) == hipSuccess &&
+                  c->h_mirror.alloc(kMirrorSlots, flags) == hipSuccess && ((uintptr_t)c->h_mirror.h & 63u) == 0 &&
+                  c->h_mirror.map() == hipSuccess && c->h_bbox.alloc(kBoxDoubles, flags) == hipSuccess &&
+                  c->h_bbox.map() == hipSuccess && c->h_fault.alloc(kFaultWords, flags) == hipSuccess &&
+                  c->h_fault.map() == hipSuccess;
+  if (up) {
+    c->h_state.zero();
+    c->h_mirror.zero();
+    c->h_bbox.zero();
+    c->h_fault.zero();
+  }
+  if (!up || ensure_common(c) != TLOAM_OK) {
+    (void)hipGetLastError();
+    tloam_destroy(c);
     return TLOAM_E_HIP;
   }
-  memset(c->h_state, 0, sizeof(GnState) * kMirrorSlots);
-  {
-    // pinned, device-visible host memory the kernels write their results into (result slots, bounding-box rows, fault words):
-    // required -- there is no copy + synchronise variant of the paths that use them
-    constexpr size_t kBoxBytes = sizeof(double) * ((size_t)kKinds * 64 * 6 + 8);
-    const unsigned flags = hipHostMallocMapped | hipHostMallocCoherent;
-    if (hipHostMalloc((void**)&c->h_mirror, sizeof(MirrorSlot) * kMirrorSlots, flags) != hipSuccess ||
-        ((uintptr_t)c->h_mirror & 63u) != 0 || hipHostGetDevicePointer((void**)&c->h_mirror_dev, c->h_mirror, 0) != hipSuccess ||
-        hipHostMalloc((void**)&c->h_bbox, kBoxBytes, flags) != hipSuccess ||
-        hipHostGetDevicePointer((void**)&c->h_bbox_dev, c->h_bbox, 0) != hipSuccess ||
-        hipHostMalloc((void**)&c->h_fault, sizeof(unsigned) * kFaultWords, flags) != hipSuccess ||
-        hipHostGetDevicePointer((void**)&c->h_fault_dev, c->h_fault, 0) != hipSuccess) {
-      (void)hipGetLastError();
-      tloam_destroy(c);
-      return TLOAM_E_HIP;
-    }
-    memset(c->h_mirror, 0, sizeof(MirrorSlot) * kMirrorSlots);
-    memset(c->h_bbox, 0, kBoxBytes);
-    memset(c->h_fault, 0, sizeof(unsigned) * kFaultWords);
-  }
-  if (ensure_common(c) != TLOAM_OK) { tloam_destroy(c); return TLOAM_E_HIP; }
   (void)hipMemsetAsync(c->state.p, 0, sizeof(GnState), c->stream);
   (void)hipMemsetAsync(c->seg_n.p, 0, 8 * sizeof(int), c->stream);
   (void)hipStreamSynchronize(c->stream);
@@ -110,51 +104,18 @@ int tloam_create(const tloam_tls_config* cfg, int device_id, tloam_ctx** out) {
   return TLOAM_OK;
 }
 
+// Every device and pinned buffer is freed by the struct that declares it when the context is deleted (tl_ctx.hpp); what is left to
+// do by hand is what was made through other calls: the exchange's handles, the child contexts, the events and the stream.  (A frame
+// slot still selected needs nothing: its clouds are in kd[], the context's own in the slot, each owned once.)
 void tloam_destroy(tloam_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   tlh::comm_release(c);
-  c->scan1p_q.release(); c->k3_ticket.release(); c->k3_span.release(); c->iter_span.release(); c->state_scratch.release(); c->blk_cnt.release(); c->row_of_pos.release(); c->fin_tickets.release(); c->fin_rows.release(); c->flagb.release();
-  for (auto& e : c->ev_pool) (void)hipEventDestroy(e);
-  // (a slot still selected: its clouds are in kd[], the context's own in the slot -- put them back first, so that every
-  //  buffer is released exactly once below)
-  if (c->frame_selected >= 0) { exchange_clouds(c, *c->frame_store[c->frame_selected]); c->frame_selected = -1; }
-  for (int k = 0; k < kKinds; ++k) {
-    KindData& K = c->kd[k];
-    K.src_aos.release(); K.tgt_aos.release(); K.tx.release(); K.ty.release(); K.tz.release();
-    K.c_idx.release(); K.c_buf.release();
-  }
-  c->src_pack.release();
-  for (int h = 0; h < 2; ++h) {
-    if (c->h_stage[h]) (void)hipHostFree(c->h_stage[h]);
-    if (c->stage_ev[h]) (void)hipEventDestroy(c->stage_ev[h]);
-  }
-  c->sx.release(); c->sy.release(); c->sz.release(); c->w_src.release();
-  c->fit_x.release(); c->fit_y.release(); c->fit_z.release();
-  c->raw.release(); c->flags.release(); c->scan.release(); c->scan_tmp.release(); c->seg_n.release();
-  c->tile_cnt.release(); c->tile_scan.release(); c->tile_of_slot.release(); c->tile_fill.release(); c->qrec.release();
-  c->partials.release(); c->red48.release(); c->sums16.release(); c->wpart.release(); c->rank_counts.release();
-  c->se3_dev.release(); c->bbox_dev.release(); c->misc.release(); c->state.release(); c->grids.release(); c->grids_next.release();
-  for (auto* f : c->frame_store)
-    if (f) { f->release(); delete f; }
-  c->frame_store.clear();
-  c->submap.release();
-  c->feat.release();
-  c->seg.release();
-  c->odom.release();
-  c->map.release();
-  c->vmap.release();
-  c->deskew.release();
   tlh::loop_release(c);
-  c->graph.release();
-  c->cmap.release();
-  c->place.release();
-  if (c->h_state) (void)hipHostFree(c->h_state);
-  if (c->h_mirror) (void)hipHostFree(c->h_mirror);
-  if (c->h_small) (void)hipHostFree(c->h_small);
-  if (c->h_bbox) (void)hipHostFree(c->h_bbox);
-  if (c->h_fault) (void)hipHostFree(c->h_fault);
+  for (auto& e : c->ev_pool) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->stage_ev)
+    if (e) (void)hipEventDestroy(e);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }

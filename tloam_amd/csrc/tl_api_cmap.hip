@@ -31,26 +31,22 @@ struct Staging {
   DBuf<int> slot_of_pt, kf_over;
   DBuf<CmapSpan> span;
   DBuf<double> pose;
-  ~Staging() {
-    fkey.release(); flead.release(); fsum.release(); look.release(); ctl.release(); slot_of_pt.release(); kf_over.release();
-    span.release(); pose.release();
-  }
 };
 
 // the rows hold `need` voxels; the closed map is being replaced, so nothing is copied
 int rows_reserve(tloam_ctx* c, size_t need) {
-  CmapState& M = c->cmap;
-  if (need <= M.cap) return TLOAM_OK;
-  const size_t want = std::max(need, 2 * M.cap);
+  VoxelRowStore& R = c->cmap.rows;
+  if (need <= R.cap) return TLOAM_OK;
+  const size_t want = std::max(need, 2 * R.cap);
   size_t tsize = 1024;
   while (tsize < 2 * want) tsize <<= 1;
   HIPC(c, hipStreamSynchronize(c->stream));   // (a launch in flight may still write the rows replaced)
-  M.release_rows();
-  HIPC(c, M.key.reserve(want));
-  for (DBuf<long long>* a : {&M.n, &M.qx, &M.qy, &M.qz}) HIPC(c, a->reserve(want));
-  HIPC(c, M.tab.reserve(tsize));
-  M.cap = want;
-  M.tmask = tsize - 1;
+  R = VoxelRowStore();
+  HIPC(c, R.key.reserve(want));
+  for (DBuf<long long>* a : {&R.n, &R.qx, &R.qy, &R.qz}) HIPC(c, a->reserve(want));
+  HIPC(c, R.tab.reserve(tsize));
+  R.cap = want;
+  R.tmask = tsize - 1;
   return TLOAM_OK;
 }
 
@@ -107,16 +103,15 @@ int build_body(tloam_ctx* c, const std::vector<double>& poses, tloam_closed_map_
   I.launches = launch_cmap_stage(W, c->stream);
   HIPC(c, hipGetLastError());
   unsigned long long ctl[8];
-  if ((size_t)n > M.cap) {   // more points than rows: the rows are sized by the count of distinct voxels
+  if ((size_t)n > M.rows.cap) {   // more points than rows: the rows are sized by the count of distinct voxels
     HIPC(c, hipMemcpyAsync(ctl, S.ctl.p, sizeof(ctl), D2H, c->stream));
     HIPC(c, hipStreamSynchronize(c->stream));
     rc = rows_reserve(c, (size_t)ctl[0]);
     if (rc != TLOAM_OK) return rc;
   }
-  HIPC(c, hipMemsetAsync(M.tab.p, 0xff, sizeof(int) * (size_t)(M.tmask + 1), c->stream));
-  W.rows.pmask = M.tmask; W.rows.ptab = M.tab.p; W.rows.pkey = M.key.p;
-  W.rows.pn = M.n.p; W.rows.pqx = M.qx.p; W.rows.pqy = M.qy.p; W.rows.pqz = M.qz.p;
-  W.row_cap = (long long)M.cap;
+  HIPC(c, hipMemsetAsync(M.rows.tab.p, 0xff, sizeof(int) * (size_t)(M.rows.tmask + 1), c->stream));
+  W.rows = M.rows.table();
+  W.row_cap = (long long)M.rows.cap;
   I.launches += launch_cmap_emit(W, c->stream);
   HIPC(c, hipGetLastError());
   std::vector<int> over(std::max<size_t>(K, 1));
@@ -127,7 +122,7 @@ int build_body(tloam_ctx* c, const std::vector<double>& poses, tloam_closed_map_
     c->last_error = "closed map: a look-back of k_cmap_emit timed out";
     return TLOAM_E_HIP;
   }
-  if (ctl[4] != ctl[0] || ctl[4] > M.cap) {
+  if (ctl[4] != ctl[0] || ctl[4] > M.rows.cap) {
     c->last_error = "closed map: the voxels numbered are not the voxels counted";
     return TLOAM_E_HIP;
   }
@@ -159,10 +154,10 @@ int tloam_closed_map_configure(tloam_ctx* c, const tloam_closed_map_config* cfg)
   if (!cmap_config_ok(want)) return TLOAM_E_INVALID;
   CmapState& M = c->cmap;
   M.drop();
-  if (M.cap) {   // (the next build reserves what the new configuration asks for)
+  if (M.rows.cap) {   // (the next build reserves what the new configuration asks for)
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipStreamSynchronize(c->stream));
-    M.release_rows();
+    M.rows = VoxelRowStore();
   }
   M.cfg = want;
   return TLOAM_OK;
@@ -171,7 +166,7 @@ int tloam_closed_map_configure(tloam_ctx* c, const tloam_closed_map_config* cfg)
 int tloam_closed_map_get_info(tloam_ctx* c, tloam_closed_map_info* info) {
   if (!c || !info || c->nranks > 1) return TLOAM_E_INVALID;
   *info = c->cmap.info;
-  info->capacity_voxels = (int64_t)c->cmap.cap;
+  info->capacity_voxels = (int64_t)c->cmap.rows.cap;
   return TLOAM_OK;
 }
 
@@ -217,7 +212,7 @@ int tloam_closed_map_build(tloam_ctx* c, int pose_source, const double* poses, s
   M.built = true;
   if (info) {
     *info = I;
-    info->capacity_voxels = (int64_t)M.cap;
+    info->capacity_voxels = (int64_t)M.rows.cap;
   }
   return TLOAM_OK;
 }

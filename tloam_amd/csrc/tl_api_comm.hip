@@ -100,7 +100,6 @@ void comm_release(tloam_ctx* c) {
   for (int r = 0; r < kMaxRanks; ++r)
     if (c->mbox_opened[r]) (void)hipIpcCloseMemHandle(c->mbox_opened[r]);
   if (c->mbox_local) (void)hipFree(c->mbox_local);
-  c->mbox_ctr.release();
 }
 }  // namespace tlh
 

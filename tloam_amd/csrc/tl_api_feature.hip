@@ -45,7 +45,7 @@ int feature_pca_run(tloam_ctx* c, const tloam_feature_config& cfg, size_t n, Fea
     IngestArgs I;
     memset(&I, 0, sizeof(I));
     I.aos[0] = F.aos.p; I.x[0] = F.x.p; I.y[0] = F.y.p; I.z[0] = F.z.p; I.n[0] = (int)n;
-    launch_ingest_targets(I, c->h_bbox_dev, c->stream);
+    launch_ingest_targets(I, c->h_bbox.dev, c->stream);
     HIPC(c, hipStreamSynchronize(c->stream));
     tlh::reduce_box_rows(c->h_bbox, boxes);
     known = boxes;

@@ -97,16 +97,11 @@ static int stage_fill(tloam_ctx* c, const double* const parts[], const size_t co
     HIPC(c, hipEventSynchronize(c->stage_ev[h]));
     c->stage_busy[h] = false;
   }
-  if (total + 2 > c->h_stage_cap[h]) {   // (+ 2: a kernel reading a piece in 16-byte steps may touch one double past its end)
-    if (c->h_stage[h]) (void)hipHostFree(c->h_stage[h]);
-    c->h_stage[h] = nullptr;
-    c->h_stage_dev[h] = nullptr;
-    c->h_stage_cap[h] = 0;
+  if (total + 2 > c->h_stage[h].n) {   // (+ 2: a kernel reading a piece in 16-byte steps may touch one double past its end)
     const size_t want = total + total / 2 + 2;
-    HIPC(c, hipHostMalloc((void**)&c->h_stage[h], want * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
-    c->h_stage_cap[h] = want;
+    HIPC(c, c->h_stage[h].alloc(want, hipHostMallocMapped | hipHostMallocCoherent));   // (the old block goes first)
     c->h_stage[h][want - 1] = c->h_stage[h][want - 2] = 0.0;
-    if (hipHostGetDevicePointer((void**)&c->h_stage_dev[h], c->h_stage[h], 0) != hipSuccess) c->h_stage_dev[h] = nullptr;
+    (void)c->h_stage[h].map();   // (no device view on this system: .dev stays nullptr, the pieces are copied)
   }
   if (!c->stage_ev[h]) HIPC(c, hipEventCreateWithFlags(&c->stage_ev[h], hipEventDisableTiming));
   for (int i = 0; i < nparts; ++i) {
@@ -123,8 +118,8 @@ int stage_and_upload(tloam_ctx* c, const double* const parts[], const size_t cou
   if (rc != TLOAM_OK || h < 0) return rc;
   // up to a few MB a kernel that reads the pinned block in place does the copy (for 226 KB the copy command costs the calling
   // thread and the copy engine more than a launch: 0.197 / 0.201 against 0.206 / 0.206 ms set_source + scan_match, round 4)
-  if (c->h_stage_dev[h] && total <= (size_t)1 << 19)
-    launch_blit_doubles(c->h_stage_dev[h], dev_dst, total, c->stream);
+  if (c->h_stage[h].dev && total <= (size_t)1 << 19)
+    launch_blit_doubles(c->h_stage[h].dev, dev_dst, total, c->stream);
   else
     HIPC(c, hipMemcpyAsync(dev_dst, c->h_stage[h], sizeof(double) * total, hipMemcpyHostToDevice, c->stream));
   HIPC(c, hipEventRecord(c->stage_ev[h], c->stream));
@@ -137,8 +132,8 @@ int stage_in_place(tloam_ctx* c, const double* const parts[], const size_t count
   *dev_view = nullptr;
   const int rc = stage_fill(c, parts, counts, nparts, offs, &total, half);
   if (rc != TLOAM_OK || *half < 0) return rc;
-  if (!c->h_stage_dev[*half]) return TLOAM_E_NOT_READY;   // (the caller looked at stage_in_place_ok first)
-  *dev_view = c->h_stage_dev[*half];
+  if (!c->h_stage[*half].dev) return TLOAM_E_NOT_READY;   // (the caller looked at stage_in_place_ok first)
+  *dev_view = c->h_stage[*half].dev;
   return TLOAM_OK;
 }
 // completed: the caller has waited for the kernels that read the half; otherwise an event behind them is recorded
@@ -198,7 +193,7 @@ int build_grids_over(tloam_ctx* c, GridBuffers& G, const double radius[kKinds], 
   } else {
     // rows straight into pinned host memory: no copy kernel.  (Publishing a completion word from the last of the
     // 256 blocks -- system-scope fence per block -- was measured: it costs more than this synchronisation.)
-    launch_bbox_all(gs, c->h_bbox_dev, c->stream);
+    launch_bbox_all(gs, c->h_bbox.dev, c->stream);
     HIPC(c, hipStreamSynchronize(c->stream));
     reduce_box_rows(c->h_bbox, boxes);
   }
@@ -291,7 +286,7 @@ int build_grids_over(tloam_ctx* c, GridBuffers& G, const double radius[kKinds], 
       //  reservation just made did not move it)
       if (frame->fi.tile_cnt == c->tile_cnt.p) { qbin = frame->qbin; frame->qbin_done = true; }
     }
-    launch_grid_scan_finalize_scatter_1p(gs, G.cell_cnt.p, nc + 1, G.cell_start.p, G.scan1p.p, c->h_fault_dev + kFaultScan1p, G.cell_of_pt.p,
+    launch_grid_scan_finalize_scatter_1p(gs, G.cell_cnt.p, nc + 1, G.cell_start.p, G.scan1p.p, c->h_fault.dev + kFaultScan1p, G.cell_of_pt.p,
                                          G.rank_of_pt.p, G.gp.p, c->stream, qbin, out);
     return TLOAM_OK;
   }
@@ -325,7 +320,7 @@ int enqueue_target_bounds(tloam_ctx* c) {
     gs.tx[k] = K.tx.p; gs.ty[k] = K.ty.p; gs.tz[k] = K.tz.p;
     gs.n[k] = K.tgt_set ? (int)K.n_tgt : 0;
   }
-  launch_bbox_all(gs, c->h_bbox_dev, c->stream);
+  launch_bbox_all(gs, c->h_bbox.dev, c->stream);
   return TLOAM_OK;
 }
 void finish_target_bounds(tloam_ctx* c) {  // after the stream has been synchronised
@@ -478,7 +473,7 @@ int set_target_frame_from(tloam_ctx* c, const double* const xyz[4], const size_t
       A.aos[k] = K.tgt_aos.p; A.x[k] = K.tx.p; A.y[k] = K.ty.p; A.z[k] = K.tz.p;
       A.n[k] = (int)K.n_tgt;
     }
-    launch_ingest_targets(A, c->h_bbox_dev, c->stream);
+    launch_ingest_targets(A, c->h_bbox.dev, c->stream);
   }
   HIPC(c, hipStreamSynchronize(c->stream));
   if (rc == TLOAM_OK) finish_target_bounds(c);
@@ -513,7 +508,7 @@ int tloam_frame_stash(tloam_ctx* c, int slot) {
   if (!c || slot < 0 || slot > (1 << 20)) return TLOAM_E_INVALID;
   if (c->active) return TLOAM_E_NOT_READY;
   HIPC(c, hipSetDevice(c->device));
-  if ((size_t)slot >= c->frame_store.size()) c->frame_store.resize((size_t)slot + 1, nullptr);
+  if ((size_t)slot >= c->frame_store.size()) c->frame_store.resize((size_t)slot + 1);
   if (c->frame_selected == slot) {
     // the slot's frame is the registered one (possibly just updated through tloam_set_*): kd[] holds it, the slot holds the
     // context's own clouds.  Exchange them back -- the frame goes into the slot, the context's own clouds become the
@@ -524,11 +519,10 @@ int tloam_frame_stash(tloam_ctx* c, int slot) {
   }
   if (c->frame_selected >= 0) return TLOAM_E_NOT_READY;   // another slot's frame is registered: select -1 first
   if (!c->frame_store[slot]) {
-    c->frame_store[slot] = new (std::nothrow) FrameClouds();
+    c->frame_store[slot].reset(new (std::nothrow) FrameClouds());
     if (!c->frame_store[slot]) return TLOAM_E_INVALID;
   } else {
     HIPC(c, hipStreamSynchronize(c->stream));   // nothing in flight may still read the buffers being replaced
-    c->frame_store[slot]->release();
     *c->frame_store[slot] = FrameClouds();
   }
   exchange_clouds(c, *c->frame_store[slot]);

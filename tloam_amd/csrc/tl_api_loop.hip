@@ -235,9 +235,10 @@ void loop_release(tloam_ctx* c) {
   drop_child(L.coarse);
   drop_child(L.fine);
   (void)hipSetDevice(c->device);
-  L.tgt.release();
-  L.partial.release();
-  L.clear();
+  LoopState fresh;   // (the scratch freed, the constraints gone; the configuration stays)
+  fresh.cfg = L.cfg;
+  fresh.cfg_set = L.cfg_set;
+  L = std::move(fresh);
 }
 }  // namespace tlh
 

@@ -24,17 +24,18 @@ bool map_config_ok(const tloam_map_config& m) {
 // in flight, the old arrays retired until the frame has drained the stream (map_frame_end)
 int map_grow(tloam_ctx* c, size_t need) {
   MapState& M = c->map;
-  if (need <= M.cap) return TLOAM_OK;
+  MapState::Points& P = M.pts;
+  if (need <= P.cap) return TLOAM_OK;
   if (!M.retired.empty()) {   // (a regrowth whose frame has not ended: not on the frame's path)
     HIPC(c, hipStreamSynchronize(c->stream));
     M.retired.release();
   }
-  const size_t want = std::max(need, 2 * M.cap);
+  const size_t want = std::max(need, 2 * P.cap);
   Grower g(c, M.retired);
-  for (DBuf<double>* a : {&M.x, &M.y, &M.z}) g.add(*a, want, (size_t)M.n_points);
+  for (DBuf<double>* a : {&P.x, &P.y, &P.z}) g.add(*a, want, (size_t)M.n_points);
   const int rc = g.commit("global map growth: ");
   if (rc != TLOAM_OK) return rc;
-  M.cap = std::min(std::min(M.x.cap, M.y.cap), M.z.cap);
+  P.cap = std::min(std::min(P.x.cap, P.y.cap), P.z.cap);
   return TLOAM_OK;
 }
 
@@ -85,12 +86,12 @@ int map_stage_launch(tloam_ctx* c, const double pose[16], size_t n) {
   W.leader = M.leader.p; W.ctl = M.ctl.p; W.bigq = M.bigq.p; W.bigfill = M.bigfill.p;
   W.big_max = map_big_max(std::max<size_t>(n, 1));
   const size_t at = (size_t)M.n_points;
-  W.ox = M.x.p + at; W.oy = M.y.p + at; W.oz = M.z.p + at;
+  W.ox = M.pts.x.p + at; W.oy = M.pts.y.p + at; W.oz = M.pts.z.p + at;
   W.n_out = M.counts.p;
   W.host_seg = M.seg.dev;
   W.host_seq = ++M.seq;
   W.use_ticket = (c->vox_ticket || (long long)(n + 256) / 256 > (long long)map_emit_resident_blocks(c->device_cus)) ? 1 : 0;
-  W.fault = c->h_fault_dev + kFaultVoxEmit;
+  W.fault = c->h_fault.dev + kFaultVoxEmit;
   MapFrontArgs A;
   memset(&A, 0, sizeof(A));
   A.aos = frame_scan(c); A.n = n;   // (the deskewed copy when the frame corrected its scan)
@@ -167,15 +168,16 @@ int tloam_map_configure(tloam_ctx* c, const tloam_map_config* cfg) {
   MapState& M = c->map;
   M.clear();
   if (!want.enabled) {   // mapping off: the frame's memory is what it was without the map
-    M.release();
+    const unsigned long long seq = M.seq;
+    M = MapState();   // (every buffer and the segment freed)
+    M.seq = seq;
     M.cfg = want;
     return TLOAM_OK;
   }
   HIPC(c, M.seg.alloc());
   const size_t reserve = want.reserve_points > 0 ? (size_t)want.reserve_points : kMapDefaultReserve;
-  if (M.cap < reserve) {   // (the map is empty: nothing to copy)
-    M.x.release(); M.y.release(); M.z.release();
-    M.cap = 0;
+  if (M.pts.cap < reserve) {   // (the map is empty: nothing to copy)
+    M.pts = MapState::Points();
     const int rc = map_grow(c, reserve);
     if (rc != TLOAM_OK) return rc;
     M.retired.release();
@@ -191,7 +193,7 @@ int tloam_map_get_info(tloam_ctx* c, tloam_map_info* info) {
   info->n_frames = M.n_frames;
   info->last_first = M.last_first;
   info->last_count = M.last_count;
-  info->capacity_points = (int64_t)M.cap;
+  info->capacity_points = (int64_t)M.pts.cap;
   info->overflow_frames = M.overflow_frames;
   return TLOAM_OK;
 }
@@ -205,7 +207,7 @@ int tloam_map_read(tloam_ctx* c, size_t first, size_t count, double* out) {
   if (!out) return TLOAM_E_INVALID;
   HIPC(c, hipSetDevice(c->device));
   HIPC(c, c->misc.reserve(3 * count));
-  launch_soa_to_aos(M.x.p + first, M.y.p + first, M.z.p + first, count, c->misc.p, c->stream);
+  launch_soa_to_aos(M.pts.x.p + first, M.pts.y.p + first, M.pts.z.p + first, count, c->misc.p, c->stream);
   HIPC(c, hipMemcpyAsync(out, c->misc.p, sizeof(double) * 3 * count, hipMemcpyDeviceToHost, c->stream));
   HIPC(c, hipStreamSynchronize(c->stream));
   return TLOAM_OK;

@@ -198,7 +198,7 @@ int harvest_k3_events(tloam_ctx* c, int working) {
 // stream drained without the number arriving, copy the state and synchronise.
 HostMirror next_mirror(tloam_ctx* c, int slot = 0) {
   HostMirror hm;
-  hm.out = c->h_mirror_dev + slot;
+  hm.out = c->h_mirror.dev + slot;
   hm.seq = ++c->mirror_seq;
   return hm;
 }
@@ -552,7 +552,7 @@ int enqueue_build(tloam_ctx* c, const BuildParams& bp, const GridView grids[kKin
     launch_build_finish_large(c->sv, grids, bp, c->state.p, c->tile_scan.p + ntiles, c->qrec.p, *ride, c->stream, c->direct ? &ds : nullptr);
   } else {
     launch_build(c->sv, grids, bp, c->state.p, c->tile_of_slot.p, c->tile_cnt.p, c->tile_scan.p, c->tile_fill.p,
-                 c->qrec.p, c->scan_tmp.p, rebin, c->stream, gate, c->scan1p_q_use ? c->scan1p_q.p : nullptr, c->h_fault_dev + kFaultScan1p,
+                 c->qrec.p, c->scan_tmp.p, rebin, c->stream, gate, c->scan1p_q_use ? c->scan1p_q.p : nullptr, c->h_fault.dev + kFaultScan1p,
                  c->direct ? &c->cv : nullptr, c->direct ? &ds : nullptr, rebin && c->qbin_rode);
     if (rebin) c->qbin_rode = false;   // (consumed: a second sort of this frame -- a re-run -- bins for itself)
   }
@@ -1310,17 +1310,15 @@ int tloam_knn(tloam_ctx* c, int kind, const double* q, size_t nq, double radius,
     double radii[kKinds] = {0, 0, 0, 0};
     radii[kind] = radius;
     rc = build_grids(c, tmp, radii, views);
-    if (rc != TLOAM_OK) { tmp.release(); return rc; }
+    if (rc != TLOAM_OK) return rc;
   }
   DBuf<double> qa, qx, qy, qz, d2;
   DBuf<int> idx, cnt;
-  auto cleanup = [&]() { qa.release(); qx.release(); qy.release(); qz.release(); d2.release(); idx.release(); cnt.release(); tmp.release(); };
   hipError_t e = hipSuccess;
   if ((e = qa.reserve(3 * nq + 3)) != hipSuccess || (e = qx.reserve(nq + 1)) != hipSuccess ||
       (e = qy.reserve(nq + 1)) != hipSuccess || (e = qz.reserve(nq + 1)) != hipSuccess ||
       (e = d2.reserve(nq * k + 1)) != hipSuccess || (e = idx.reserve(nq * k + 1)) != hipSuccess ||
       (e = cnt.reserve(nq + 1)) != hipSuccess) {
-    cleanup();
     c->last_error = hipGetErrorString(e);
     return TLOAM_E_HIP;
   }
@@ -1332,8 +1330,7 @@ int tloam_knn(tloam_ctx* c, int kind, const double* q, size_t nq, double radius,
     (void)hipMemcpyAsync(out_d2, d2.p, sizeof(double) * nq * k, hipMemcpyDeviceToHost, c->stream);
     (void)hipMemcpyAsync(out_cnt, cnt.p, sizeof(int) * nq, hipMemcpyDeviceToHost, c->stream);
   }
-  e = hipStreamSynchronize(c->stream);
-  cleanup();
+  e = hipStreamSynchronize(c->stream);   // (before the locals go)
   if (e != hipSuccess) { c->last_error = hipGetErrorString(e); return TLOAM_E_HIP; }
   return check_device_faults(c);
 }

@@ -246,7 +246,7 @@ int tloam_place_configure(tloam_ctx* c, const tloam_place_config* cfg) {
   HIPC(c, hipSetDevice(c->device));
   HIPC(c, hipStreamSynchronize(c->stream));
   PlaceState& P = c->place;
-  P.release();   // (empty: a new layout, or off -- the frame's memory is then what it was without place recognition)
+  P = PlaceState();   // (empty: a new layout, or off -- the frame's memory is then what it was without place recognition)
   c->loop.clear();   // (the constraints name keyframes that are gone)
   c->graph.drop();   // (so do the corrected poses)
   c->cmap.drop();    // (and the closed map was built from them)
@@ -254,7 +254,8 @@ int tloam_place_configure(tloam_ctx* c, const tloam_place_config* cfg) {
   if (!want.enabled) return TLOAM_OK;
   const int rc = place_alloc(c, want.reserve_keyframes > 0 ? (size_t)want.reserve_keyframes : kPlaceDefaultReserve);
   if (rc != TLOAM_OK) {
-    P.release();
+    P = PlaceState();
+    P.cfg = want;
     P.cfg.enabled = 0;
     return rc;
   }

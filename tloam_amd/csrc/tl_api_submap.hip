@@ -72,10 +72,10 @@ int submap_job(tloam_ctx* c, const CropVoxelSeg seg[2], int nseg, VoxelJob* Jout
   W.leader = S.leader.p; W.leader_scan = S.leader_scan.p; W.scan_tmp = S.scan_tmp.p; W.overflow = S.overflow.p;
   W.n_out = S.counts.p;
   // the last slot of the result mirror is free outside scanMatching: the sizes come back through it
-  W.host_seg = &c->h_mirror_dev[kMirrorSlots - 1].w[0];
+  W.host_seg = &c->h_mirror.dev[kMirrorSlots - 1].w[0];
   W.host_seq = ++c->mirror_seq;
   W.use_ticket = (c->vox_ticket || (long long)(n + 256) / 256 > (long long)vox_emit_resident_blocks(c->device_cus)) ? 1 : 0;
-  W.fault = c->h_fault_dev + kFaultVoxEmit;
+  W.fault = c->h_fault.dev + kFaultVoxEmit;
   S.pending_seq = W.host_seq;
   *Jout = J;
   *Wout = W;
@@ -152,7 +152,7 @@ bool submap_config_ok(const tloam_submap_config& want) {
 int submap_init_body(tloam_ctx* c, const tloam_submap_config& want, const double* planar, size_t n_planar, const double* sphere,
                      size_t n_sphere, const double* edge, size_t n_edge, const double* ground, size_t n_ground, hipMemcpyKind from) {
   SubmapState& S = c->submap;
-  S.release();
+  S = SubmapState();   // (the ring frames and the pipeline's scratch are freed; not inited)
   S.cfg = want;
   // :286 / :290-291 submap += cloud on empty submaps: the clouds as given
   int rc = set_target_copy(c, TLOAM_KIND_EDGE, edge, n_edge, from);
@@ -251,16 +251,17 @@ static int submap_update_body(tloam_ctx* c, const double pose[16], const double*
   const double* stage_view = nullptr;   // the staging half as the device sees it (in_place)
   size_t stage_off[3] = {0, 0, 0};      // first double of planar | edge | ground in the staged block
   int stage_half = -1;
-  auto push = [&](std::vector<RingFrame*>& ring, const double* xyz, size_t n, int keep, bool upload) -> int {
-    RingFrame* f = nullptr;
+  auto push = [&](std::vector<std::unique_ptr<RingFrame>>& ring, const double* xyz, size_t n, int keep, bool upload) -> int {
+    std::unique_ptr<RingFrame> fresh;
     if ((int)ring.size() >= keep) {  // recycle the frame that falls out
-      f = ring.front();
+      fresh = std::move(ring.front());
       ring.erase(ring.begin());
-      while ((int)ring.size() >= keep) { ring.front()->aos.release(); delete ring.front(); ring.erase(ring.begin()); }
+      while ((int)ring.size() >= keep) ring.erase(ring.begin());
     } else {
-      f = new RingFrame();
+      fresh.reset(new RingFrame());
     }
-    ring.push_back(f);
+    ring.push_back(std::move(fresh));
+    RingFrame* const f = ring.back().get();
     f->n = n;
     memcpy(f->pose, pose, sizeof(double) * 16);
     if (!upload) return TLOAM_OK;
@@ -290,7 +291,7 @@ static int submap_update_body(tloam_ctx* c, const double pose[16], const double*
   if (rc != TLOAM_OK) return rc;
   // :220-243 both submaps are rebuilt from submap_planar_buffer (the sphere loop iterates the PLANAR buffer)
   size_t total = 0;
-  for (auto* f : S.planar_ring) total += f->n;
+  for (const auto& f : S.planar_ring) total += f->n;
   {
     KindData& P = c->kd[TLOAM_KIND_PLANAR];
     KindData& Q = c->kd[TLOAM_KIND_SPHERE];
@@ -303,7 +304,7 @@ static int submap_update_body(tloam_ctx* c, const double pose[16], const double*
       fused_front = true;
     } else {
       size_t off = 0;
-      for (auto* f : S.planar_ring) {  // one launch per buffered frame writes both submaps
+      for (const auto& f : S.planar_ring) {  // one launch per buffered frame writes both submaps
         launch_transform_to_soa2(f->aos.p, f->n, f->pose, P.tx.p + off, P.ty.p + off, P.tz.p + off, Q.tx.p + off,
                                  Q.ty.p + off, Q.tz.p + off, c->stream);
         off += f->n;
@@ -351,10 +352,9 @@ static int submap_update_body(tloam_ctx* c, const double pose[16], const double*
         HIPC(c, nb.reserve(std::max(need, b->cap + b->cap / 2)));
         if (n_old[s] > 0 && b->p) {
           const hipError_t e = hipMemcpy(nb.p, b->p, sizeof(double) * n_old[s], hipMemcpyDeviceToDevice);
-          if (e != hipSuccess) { nb.release(); c->last_error = hipGetErrorString(e); return TLOAM_E_HIP; }
+          if (e != hipSuccess) { c->last_error = hipGetErrorString(e); return TLOAM_E_HIP; }
         }
-        b->release();
-        *b = nb;
+        *b = std::move(nb);   // (the old array is freed)
       }
     }
   }
@@ -382,7 +382,7 @@ static int submap_update_body(tloam_ctx* c, const double pose[16], const double*
       size_t ring_max = 0;
       const double* aos[16]; size_t nn[16]; const double* poses[16];
       int cnt = 0;
-      for (auto* f : S.planar_ring) { aos[cnt] = f->aos.p; nn[cnt] = f->n; poses[cnt] = f->pose; ring_max = std::max(ring_max, f->n); ++cnt; }
+      for (const auto& f : S.planar_ring) { aos[cnt] = f->aos.p; nn[cnt] = f->n; poses[cnt] = f->pose; ring_max = std::max(ring_max, f->n); ++cnt; }
       if (stage_view) aos[cnt - 1] = stage_view + stage_off[0];   // the newest frame: read in the staging, copied to f->aos on the way
       const size_t rows = submap_front_rows(ring_max, std::max(n_in[0], n_in[1]));
       if (S.min_partial.cap < rows * 6) HIPC(c, hipStreamSynchronize(c->stream));   // regrowth: nothing may be in flight

@@ -22,24 +22,18 @@ bool vmap_config_ok(const tloam_voxel_map_config& m) {
          std::isfinite(m.origin[2]) && m.reserve_voxels >= 0;
 }
 
-VmapTable table_of(VmapState& V) {
-  VmapTable T;
-  T.pmask = V.tmask; T.ptab = V.tab.p; T.pkey = V.key.p;
-  T.pn = V.n.p; T.pqx = V.qx.p; T.pqy = V.qy.p; T.pqz = V.qz.p;
-  return T;
-}
-
 // the map holds `need` voxels: new rows of max(need, 2 cap) with the voxels so far copied device to device behind whatever is in
 // flight, a new table (load <= 1/2) rebuilt from the id-ordered keys -- ids and order never change --, the old storage retired
 // until the frame has drained the stream (vmap_frame_end).  A failure leaves the map as it was
 int vmap_grow(tloam_ctx* c, size_t need) {
   VmapState& V = c->vmap;
-  if (need <= V.cap) return TLOAM_OK;
+  VoxelRowStore& R = V.rows;
+  if (need <= R.cap) return TLOAM_OK;
   if (!V.retired.empty()) {   // (a regrowth whose frame has not ended: not on the frame's path)
     HIPC(c, hipStreamSynchronize(c->stream));
     V.retired.release();
   }
-  const size_t want = std::max(need, 2 * V.cap);
+  const size_t want = std::max(need, 2 * R.cap);
   if (want > kVmapMaxVoxels) {
     c->last_error = "voxel map: more than 2^30 voxels";
     return TLOAM_E_HIP;
@@ -48,15 +42,15 @@ int vmap_grow(tloam_ctx* c, size_t need) {
   while (tsize < 2 * want) tsize <<= 1;
   const size_t nv = (size_t)V.n_voxels;
   Grower g(c, V.retired);
-  g.add(V.key, want, nv);
-  for (DBuf<long long>* a : {&V.n, &V.qx, &V.qy, &V.qz}) g.add(*a, want, nv);
-  if (int* t = g.add(V.tab, tsize)) g.check(hipMemsetAsync(t, 0xff, sizeof(int) * tsize, c->stream));
+  g.add(R.key, want, nv);
+  for (DBuf<long long>* a : {&R.n, &R.qx, &R.qy, &R.qz}) g.add(*a, want, nv);
+  if (int* t = g.add(R.tab, tsize)) g.check(hipMemsetAsync(t, 0xff, sizeof(int) * tsize, c->stream));
   const int rc = g.commit("voxel map growth: ");
   if (rc != TLOAM_OK) return rc;
-  V.cap = want;
-  V.tmask = tsize - 1;
+  R.cap = want;
+  R.tmask = tsize - 1;
   V.tab_dirty = false;
-  launch_vmap_rehash(table_of(V), nv, c->stream);
+  launch_vmap_rehash(R.table(), nv, c->stream);
   return TLOAM_OK;
 }
 
@@ -66,7 +60,7 @@ VmapStageWork stage_work(tloam_ctx* c) {   // the staged frame's buffers, as k_v
   memset(&W, 0, sizeof(W));
   W.fmask = V.fmask;
   W.fkey = V.fkey.p; W.flead = V.flead.p; W.fsum = V.fsum.p; W.fid = V.fid.p; W.slot_of_pt = V.slot_of_pt.p;
-  W.pmask = V.tmask; W.ptab = V.tab.p; W.pkey = V.key.p;
+  W.pmask = V.rows.tmask; W.ptab = V.rows.tab.p; W.pkey = V.rows.key.p;
   W.base = V.n_voxels;
   W.look = V.look.p; W.ctl = V.ctl.p;
   W.voxel = V.cfg.voxel;
@@ -88,7 +82,7 @@ int vmap_frame_reserve(tloam_ctx* c, size_t n) {
   int rc = vmap_grow(c, (size_t)V.n_voxels + n);
   if (rc != TLOAM_OK) return rc;
   if (V.tab_dirty) {
-    HIPC(c, hipMemsetAsync(V.tab.p, 0xff, sizeof(int) * (size_t)(V.tmask + 1), c->stream));
+    HIPC(c, hipMemsetAsync(V.rows.tab.p, 0xff, sizeof(int) * (size_t)(V.rows.tmask + 1), c->stream));
     V.tab_dirty = false;
   }
   const size_t m = std::max<size_t>(n, 1), T = voxel_table_size(m), blocks = (m + 256) / 256 + 1;
@@ -151,7 +145,7 @@ void vmap_frame_end(tloam_ctx* c, bool accepted) {
     if (V.overflowed) {
       V.overflow_frames++;   // a finite point beyond 2^20 voxels of the origin: the frame adds nothing
     } else {
-      launch_vmap_commit(stage_work(c), table_of(V), c->stream);
+      launch_vmap_commit(stage_work(c), V.rows.table(), c->stream);
       V.n_voxels += V.new_voxels;
       V.n_points += V.new_points;
       V.last_new = V.new_voxels;
@@ -239,15 +233,16 @@ int tloam_voxel_map_configure(tloam_ctx* c, const tloam_voxel_map_config* cfg) {
   VmapState& V = c->vmap;
   V.clear();
   if (!want.enabled) {   // off: the frame's memory is what it was without the voxel map
-    V.release();
+    const unsigned long long seq = V.seq;
+    V = VmapState();   // (every buffer and the segment freed)
+    V.seq = seq;
     V.cfg = want;
     return TLOAM_OK;
   }
   HIPC(c, V.seg.alloc());
   const size_t reserve = want.reserve_voxels > 0 ? (size_t)want.reserve_voxels : kVmapDefaultReserve;
-  if (V.cap < reserve) {   // (the map is empty: nothing to copy)
-    V.key.release(); V.n.release(); V.qx.release(); V.qy.release(); V.qz.release(); V.tab.release();
-    V.cap = 0;
+  if (V.rows.cap < reserve) {   // (the map is empty: nothing to copy)
+    V.rows = VoxelRowStore();
     const int rc = vmap_grow(c, reserve);
     if (rc != TLOAM_OK) return rc;
     HIPC(c, hipStreamSynchronize(c->stream));
@@ -264,7 +259,7 @@ int tloam_voxel_map_get_info(tloam_ctx* c, tloam_voxel_map_info* info) {
   info->n_points = V.n_points;
   info->n_frames = V.n_frames;
   info->last_new = V.last_new;
-  info->capacity_voxels = (int64_t)V.cap;
+  info->capacity_voxels = (int64_t)V.rows.cap;
   info->overflow_frames = V.overflow_frames;
   return TLOAM_OK;
 }

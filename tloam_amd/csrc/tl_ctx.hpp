@@ -3,6 +3,7 @@
 // exchange, tl_api_submap.hip: device-resident submap, tl_api_feature.hip: PCA features, tl_api_seg.hip: segmentation,
 // tl_api_odom.hip: the whole odometry frame, tl_api_map.hip: its global map and registered scan, tl_api_vmap.hip: its merged
 // voxel map, tl_api_deskew.hip: its deskew, tl_api_place.hip: place recognition, tl_api_cmap.hip: the closed map).
+// Memory: every buffer below belongs to the struct that declares it and dies with it (the owning types come first).
 #pragma once
 
 #include <dlfcn.h>
@@ -12,8 +13,10 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "tl_common.hpp"
@@ -25,12 +28,27 @@ using namespace tl;
 
 
 // ------------------------------------------------------------------------------------------------
-//  grow-only device buffer
+//  who owns memory: a device or pinned-host buffer belongs to the struct that declares it and is freed when that struct dies --
+//  with the context (tloam_destroy's `delete`), with a function's locals, or where a state is assigned a fresh value to give
+//  its memory back mid-life.  Nothing lists buffers to free them.  The owners are DBuf, Retired and Pinned below (move-only:
+//  a moved-from owner is empty); none is ever global or static, so none outlives the runtime.
 // ------------------------------------------------------------------------------------------------
+//  grow-only device buffer
 template <class T>
 struct DBuf {
   T* p = nullptr;
   size_t cap = 0;  // elements
+  DBuf() = default;
+  DBuf(DBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+  DBuf& operator=(DBuf&& o) noexcept {
+    if (this != &o) {
+      release();
+      p = std::exchange(o.p, nullptr);
+      cap = std::exchange(o.cap, 0);
+    }
+    return *this;
+  }
+  ~DBuf() { release(); }
   hipError_t reserve(size_t n) {
     if (n <= cap) return hipSuccess;
     size_t want = std::max(n, cap + cap / 2);
@@ -45,7 +63,7 @@ struct DBuf {
     cap = want;
     return hipSuccess;
   }
-  void release() {
+  void release() {   // the early free, for the places that give memory back mid-life
     if (p) (void)hipFree(p);
     p = nullptr;
     cap = 0;
@@ -55,6 +73,17 @@ struct DBuf {
 // device storage a regrowth replaced: freed once the stream has drained, the launches in flight may still read it
 struct Retired {
   std::vector<void*> p;
+  Retired() = default;
+  Retired(Retired&& o) noexcept : p(std::move(o.p)) { o.p.clear(); }
+  Retired& operator=(Retired&& o) noexcept {
+    if (this != &o) {
+      release();
+      p = std::move(o.p);
+      o.p.clear();
+    }
+    return *this;
+  }
+  ~Retired() { release(); }
   template <class T>
   void take(DBuf<T>& b) {
     if (b.p) p.push_back(b.p);
@@ -68,28 +97,58 @@ struct Retired {
   bool empty() const { return p.empty(); }
 };
 
-// a pinned, device-visible segment of 8 words (mapped | coherent, zeroed) a stage's last kernel reports its result through
-struct PinnedSeg {
-  unsigned long long* h = nullptr;     // as the host reads it
-  unsigned long long* dev = nullptr;   // as the device addresses it
-  hipError_t alloc() {   // (kept if there is one)
-    if (h) return hipSuccess;
-    unsigned long long* q = nullptr;
-    hipError_t e = hipHostMalloc((void**)&q, 8 * sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent);
-    if (e != hipSuccess) return e;
-    memset(q, 0, 8 * sizeof(unsigned long long));
-    e = hipHostGetDevicePointer((void**)&dev, q, 0);
-    if (e != hipSuccess) {
-      (void)hipHostFree(q);
-      dev = nullptr;
-      return e;
+// pinned host memory: `n` elements allocated with the flags given, and -- after map() -- the address the device reads them at.
+// Reads as the host pointer
+template <class T>
+struct Pinned {
+  T* h = nullptr;     // as the host reads it
+  T* dev = nullptr;   // as the device addresses it (nullptr: not mapped)
+  size_t n = 0;       // elements
+  Pinned() = default;
+  Pinned(Pinned&& o) noexcept : h(std::exchange(o.h, nullptr)), dev(std::exchange(o.dev, nullptr)), n(std::exchange(o.n, 0)) {}
+  Pinned& operator=(Pinned&& o) noexcept {
+    if (this != &o) {
+      release();
+      h = std::exchange(o.h, nullptr);
+      dev = std::exchange(o.dev, nullptr);
+      n = std::exchange(o.n, 0);
     }
-    h = q;
-    return hipSuccess;
+    return *this;
   }
+  ~Pinned() { release(); }
+  hipError_t alloc(size_t count, unsigned flags) {   // (what it held goes first)
+    release();
+    const hipError_t e = hipHostMalloc((void**)&h, count * sizeof(T), flags);
+    if (e != hipSuccess) h = nullptr;
+    else n = count;
+    return e;
+  }
+  hipError_t map() {
+    const hipError_t e = hipHostGetDevicePointer((void**)&dev, h, 0);
+    if (e != hipSuccess) dev = nullptr;
+    return e;
+  }
+  void zero() { memset(h, 0, n * sizeof(T)); }
   void release() {
     if (h) (void)hipHostFree(h);
     h = dev = nullptr;
+    n = 0;
+  }
+  operator T*() const { return h; }
+  T* operator->() const { return h; }
+};
+
+// a pinned, device-visible segment of 8 words (mapped | coherent, zeroed) a stage's last kernel reports its result through
+struct PinnedSeg : Pinned<unsigned long long> {
+  hipError_t alloc() {   // (kept if there is one)
+    if (h) return hipSuccess;
+    hipError_t e = Pinned::alloc(8, hipHostMallocMapped | hipHostMallocCoherent);
+    if (e == hipSuccess) {
+      zero();
+      e = map();
+    }
+    if (e != hipSuccess) release();
+    return e;
   }
 };
 
@@ -126,10 +185,6 @@ struct FrameClouds {
   bool src_set[tl::kKinds] = {}, tgt_set[tl::kKinds] = {};
   double tgt_box[tl::kKinds][6] = {};
   bool tgt_box_valid[tl::kKinds] = {};
-  void release() {
-    for (int k = 0; k < tl::kKinds; ++k) { src_aos[k].release(); tgt_aos[k].release(); tx[k].release(); ty[k].release(); tz[k].release(); src_ptr[k] = nullptr; }
-    src_pack.release();
-  }
 };
 
 struct GridBuffers {
@@ -138,10 +193,6 @@ struct GridBuffers {
   DBuf<unsigned long long> cell_cnt, cell_scan, scan_tmp;
   DBuf<unsigned long long> scan1p;   // control words of the single-pass scan (large tables), zero when allocated
   DBuf<double> bbox;
-  void release() {
-    gp.release(); cell_start.release(); cell_of_pt.release(); rank_of_pt.release();
-    cell_cnt.release(); cell_scan.release(); scan_tmp.release(); scan1p.release(); bbox.release();
-  }
 };
 
 
@@ -157,19 +208,10 @@ struct SubmapState {
   bool inited = false;
   unsigned long long pending_seq = 0ull;  // sequence number the last kernel of the update in flight stores into the host slot
   tloam_submap_config cfg;
-  std::vector<RingFrame*> planar_ring, sphere_ring;  // oldest first (std::deque in the reference)
+  std::vector<std::unique_ptr<RingFrame>> planar_ring, sphere_ring;  // oldest first (std::deque in the reference)
   DBuf<double> in_aos, wx, wy, wz, min_partial, vmin;
   DBuf<unsigned long long> keys, cnt, off, leader, leader_scan, scan_tmp, counts;
   DBuf<int> slot_of_pt, urank, members, sorted, overflow;
-  void release() {
-    for (auto* f : planar_ring) { f->aos.release(); delete f; }
-    for (auto* f : sphere_ring) { f->aos.release(); delete f; }
-    planar_ring.clear(); sphere_ring.clear();
-    in_aos.release(); wx.release(); wy.release(); wz.release(); min_partial.release(); vmin.release();
-    keys.release(); cnt.release(); off.release(); leader.release(); leader_scan.release(); scan_tmp.release();
-    counts.release(); slot_of_pt.release(); urank.release(); members.release(); sorted.release(); overflow.release();
-    inited = false;
-  }
 };
 
 // scratch of the PCA feature path (grow-only, kept across calls)
@@ -180,12 +222,6 @@ struct FeatBuffers {
   DBuf<unsigned long long> flags, scan, scan_tmp;
   DBuf<tl::FeatRankCtl> rank_ctl;
   GridBuffers grid;
-  void release() {
-    aos.release(); x.release(); y.release(); z.release(); flatness.release(); cvr.release(); sphericity.release();
-    normal.release(); f2.release(); gf.release(); out.release(); num_sum.release(); neigh.release();
-    idx2.release(); gi.release(); bkt.release(); pos.release(); flags.release(); scan.release();
-    scan_tmp.release(); rank_ctl.release(); grid.release();
-  }
 };
 
 // device buffers of the segmentation node (tl_api_seg.hip; grow-only, kept across calls) and its frame counter
@@ -197,15 +233,6 @@ struct SegBuffers {
   DBuf<unsigned char> reg_flag, picked;
   unsigned long long frames = 0;   // calls so far: the first one seeds minPolar / maxPolar with 5.0, later ones with 0.0
   unsigned long long aos_seq = 0;  // uploads into `aos` so far (segment_begin): what tloam_registered_scan checks residency by
-  void release() {
-    DBuf<double>* d[] = {&aos, &pol_val, &bounds, &boxes, &cv};
-    for (auto* b : d) b->release();
-    DBuf<int>* i[] = {&ring, &cur, &cur_reg, &ng, &reg_mem, &reg_g, &reg_v, &ground, &obj, &vox, &hkey, &hval, &parent, &csize,
-                      &croot, &cl_root, &cl_off, &cl_size, &seg_local, &seg_orig, &seg_label, &ring_list, &sorted, &genbuf,
-                      &edge_sec, &sec_cnt, &sec_base, &edge, &general};
-    for (auto* b : i) b->release();
-    ctl.release(); reg_flag.release(); picked.release();
-  }
 };
 
 // the odometry frame (tl_api_odom.hip): FrontEnd's state between frames and the device scratch of its glue
@@ -226,15 +253,16 @@ struct OdomState {
   size_t reg_n = 0;
   double reg_pose[16];
   bool reg_deskewed = false;       // its scan is the deskewed copy (DeskewState::aos), not the segmentation's input
-  void release() { vox_out.release(); block.release(); ctl.release(); ready = false; reg_valid = false; }
 };
 
 // the global map of the odometry frame (tl_api_map.hip): the map itself (SoA, grown by doubling), the
 // scratch of its per-frame voxel job, and the pinned segment its last kernel reports the frame's count through
 struct MapState {
   tloam_map_config cfg = {0, 0, 1.0, 0};   // tloam_map_default_config until tloam_map_configure
-  DBuf<double> x, y, z;            // the map: n_points rows of cap
-  size_t cap = 0;
+  struct Points {
+    DBuf<double> x, y, z;          // the map: n_points rows of cap
+    size_t cap = 0;
+  } pts;
   Retired retired;                 // storage a regrowth replaced: freed once the frame has drained the stream
   int64_t n_points = 0, n_frames = 0, last_first = 0, last_count = 0, overflow_frames = 0;
   DBuf<double> wx, wy, wz, min_partial, vmin;   // the transformed scan (kept: the registered scan of a mapping frame)
@@ -255,15 +283,21 @@ struct MapState {
     have_count = false;
     xf_seq = 0;
   }
-  void release() {
-    x.release(); y.release(); z.release(); cap = 0;
-    retired.release();
-    wx.release(); wy.release(); wz.release(); min_partial.release(); vmin.release();
-    keys.release(); leader.release(); counts.release();
-    head.release(); first.release(); count.release(); bigslot.release(); slot_of_pt.release(); next.release(); members.release();
-    bigfill.release(); ctl.release(); bigq.release();
-    seg.release();
-    clear();
+};
+
+// voxel rows in id order and their table: the layout the merged voxel map and the closed map share (k_vmap_read / k_vmap_box
+// read either: voxel_rows_of below)
+struct VoxelRowStore {
+  DBuf<unsigned long long> key;    // [cap] per id
+  DBuf<long long> n, qx, qy, qz;   // [cap] per id
+  DBuf<int> tab;                   // [tmask + 1] slot -> id, -1 free
+  size_t cap = 0;
+  unsigned long long tmask = 0;
+  tl::VmapTable table() const {    // as the kernels see them
+    tl::VmapTable T;
+    T.pmask = tmask; T.ptab = tab.p; T.pkey = key.p;
+    T.pn = n.p; T.pqx = qx.p; T.pqy = qy.p; T.pqz = qz.p;
+    return T;
   }
 };
 
@@ -271,11 +305,7 @@ struct MapState {
 // table (grown by doubling, rehashed from the keys), the frame's staging, and the pinned segment k_vmap_emit reports through
 struct VmapState {
   tloam_voxel_map_config cfg = {0, 0, 1.0, {0.0, 0.0, 0.0}, 0};   // tloam_voxel_map_default_config until configured
-  DBuf<unsigned long long> key;    // [cap] per id
-  DBuf<long long> n, qx, qy, qz;   // [cap] per id
-  DBuf<int> tab;                   // [tmask + 1] slot -> id, -1 free
-  size_t cap = 0;
-  unsigned long long tmask = 0;
+  VoxelRowStore rows;
   bool tab_dirty = false;          // emptied since the table was last cleared: cleared at the next frame / read
   Retired retired;                 // storage a regrowth replaced: freed once the frame has drained the stream
   int64_t n_voxels = 0, n_points = 0, n_frames = 0, last_new = 0, overflow_frames = 0;
@@ -295,16 +325,7 @@ struct VmapState {
     n_voxels = n_points = n_frames = last_new = overflow_frames = 0;
     pending_seq = 0;
     have_count = false;
-    if (tab.p) tab_dirty = true;   // (cleared on the stream at the next frame: the ids it holds are gone)
-  }
-  void release() {
-    key.release(); n.release(); qx.release(); qy.release(); qz.release(); tab.release(); cap = 0; tmask = 0;
-    retired.release();
-    fkey.release(); fsum.release(); look.release(); ctl.release(); flead.release(); fid.release(); slot_of_pt.release();
-    rd_c.release(); rd_n.release();
-    seg.release();
-    clear();
-    tab_dirty = false;
+    if (rows.tab.p) tab_dirty = true;   // (cleared on the stream at the next frame: the ids it holds are gone)
   }
 };
 
@@ -325,10 +346,6 @@ struct DeskewState {
   int64_t frames = 0, last_frame = -1;
   double last_twist[6] = {0, 0, 0, 0, 0, 0};
   void clear() { frames = 0; last_frame = -1; committed = -1; for (double& v : last_twist) v = 0.0; }
-  void release() {
-    aos.release(); t.release(); ctl.release(); s_in.release(); s_out.release(); s_t.release(); s_ctl.release();
-    clear();
-  }
 };
 
 // place recognition (tl_api_place.hip): its configuration, the keyframe database in HBM (per keyframe the
@@ -370,13 +387,6 @@ struct PlaceState {
     pend.nspan = 0;
     if (ctl.p) (void)hipMemsetAsync(ctl.p, 0, sizeof(unsigned long long), s);   // (behind whatever is in flight)
   }
-  void release() {
-    desc.release(); rkey.release(); skey.release(); pose.release(); kdist.release(); frame.release(); taken.release();
-    loops.release(); retired.release(); bins.release(); ctl.release(); cand.release();
-    s_aos.release(); s_desc.release(); s_rkey.release(); s_skey.release();
-    arena.release(); kf.clear(); arena_used = 0; pend.nspan = 0;
-    cap = 0; n_kf = 0; last_kf_frame = -1; in_flight = false;
-  }
 };
 
 // loop verification (tl_api_loop.hip): its configuration, the two private child contexts of the coarse and
@@ -389,7 +399,6 @@ struct LoopState {
   std::vector<tloam_loop_constraint> out;
   size_t next_record = 0;
   DBuf<double> tgt, partial;       // the assembled targets (per kind, end to end), the score's block partials
-  double* h_partial = nullptr;     // pinned mirror of `partial`
   void clear() { out.clear(); next_record = 0; }
 };
 
@@ -403,7 +412,6 @@ struct GraphState {
   bool have = false;               // tloam_graph_optimize has run since the last reset / configure
   std::vector<double> corrected;   // [16 n] column-major
   void drop() { have = false; corrected.clear(); }
-  void release() { dws.release(); iws.release(); rec.release(); drop(); }
 };
 
 // the closed map (tl_api_cmap.hip): its configuration, its rows in id order and their table (the voxel map's
@@ -411,11 +419,7 @@ struct GraphState {
 // staging is its own and freed when it ends
 struct CmapState {
   tloam_closed_map_config cfg = {1.0, {0.0, 0.0, 0.0}, 0xF0, 0, 0};   // tloam_closed_map_default_config until configured
-  DBuf<unsigned long long> key;    // [cap] per id
-  DBuf<long long> n, qx, qy, qz;   // [cap] per id
-  DBuf<int> tab;                   // [tmask + 1] slot -> id, -1 free
-  size_t cap = 0;
-  unsigned long long tmask = 0;
+  VoxelRowStore rows;
   bool built = false;              // a build has succeeded since the last drop
   tloam_closed_map_info info{};    // of the last build (zero when dropped; capacity_voxels filled in when asked)
   std::vector<double> poses;       // [16 K] column-major: the poses the last build used
@@ -426,16 +430,6 @@ struct CmapState {
     built = false;
     info = tloam_closed_map_info{};
     poses.clear();
-  }
-  void release_rows() {
-    key.release(); n.release(); qx.release(); qy.release(); qz.release(); tab.release();
-    cap = 0;
-    tmask = 0;
-  }
-  void release() {
-    release_rows();
-    rd_c.release(); rd_n.release(); look.release(); ctl.release();
-    drop();
   }
 };
 
@@ -487,8 +481,8 @@ struct tloam_ctx {
   DBuf<int> seg_n;
   DBuf<double> partials, red48, sums16, wpart, rank_counts, se3_dev, bbox_dev, misc;
   DBuf<GnState> state;
-  GnState* h_state = nullptr;  // pinned mirror
-  double* h_small = nullptr;   // pinned scratch (>= 64*6*4 doubles)
+  Pinned<GnState> h_state;     // pinned mirror
+  Pinned<double> h_small;      // pinned scratch (>= 64*6*4 doubles)
   int k3_grid = 1;
   bool k3_single = false;
   bool k3_wide = false;        // the streaming sweep goes out as blocks of eight waves (k3_plan); k3_grid = blocks launched = rows
@@ -501,8 +495,7 @@ struct tloam_ctx {
   bool hand_over_timed_out = false;  // the last TLOAM_E_HIP of the device loop was OS_COMM_ERROR on one rank
   int dbg_fail_handover = 0;       // TLOAM_DEBUG_FAIL_HANDOVER=n: the next n one-launch Solves time out in their first hand-over (test hook)
   int device_cus = 0;              // multiProcessorCount of the device (k_solve_all and the single-pass scans need all their blocks resident at once)
-  double* h_bbox = nullptr;        // pinned, device-visible: [4][64][6] bounding-box rows
-  double* h_bbox_dev = nullptr;
+  Pinned<double> h_bbox;           // pinned, device-visible: [4][64][6] bounding-box rows
   // bounds of the registered target clouds, taken at hand-over (set_target*: the call synchronises anyway), so that
   // scanMatching can size its search grids without a host round trip of its own
   double tgt_box[tl::kKinds][6];
@@ -512,26 +505,23 @@ struct tloam_ctx {
   long hs_n = 0;
   double hs_exit = 0.0;
   double hs_entry = 0.0;          // > 0: stamping, entry time of the scan_match in progress (us, steady clock)
-  tl::MirrorSlot* h_mirror = nullptr;       // pinned, device-visible result slots (HostMirror targets), 64-byte aligned
-  tl::MirrorSlot* h_mirror_dev = nullptr;   // ... as the device addresses them
+  Pinned<tl::MirrorSlot> h_mirror;          // pinned, device-visible result slots (HostMirror targets), 64-byte aligned
   unsigned long long mirror_seq = 0;
   // fault words a kernel raises when a bounded in-launch wait runs out (pinned, device-visible; see check_device_faults):
   // [0] single-pass look-back scan (tl_nn.hip), [1] k_vox_emit's look-back (tl_submap.hip)
-  unsigned* h_fault = nullptr;
-  unsigned* h_fault_dev = nullptr;
+  Pinned<unsigned> h_fault;
   bool scan1p_retried = false;     // tloam_scan_match has re-run a frame after a look-back scan timed out (once per context)
   bool vox_ticket = false;         // set after k_vox_emit's look-back timed out: its blocks take start tickets from then on
   DBuf<double> src_pack;                        // the registered Frame's four source clouds in one piece (tloam_set_source_frame)
   // pinned staging of tloam_set_source_frame: the borrowed host clouds are copied here (two halves, used alternately; an
   // event per half says when the device has read it) and go to HBM with ONE asynchronous copy -- the call returns without
   // waiting for the device, the frame's first kernel is ordered behind the copy by the stream
-  double* h_stage[2] = {nullptr, nullptr};
-  double* h_stage_dev[2] = {nullptr, nullptr};  // the halves as the device addresses them (kernels that read the staging in place)
-  size_t h_stage_cap[2] = {0, 0};               // doubles
+  Pinned<double> h_stage[2];                    // (.dev: the halves as the device addresses them, for kernels that read the
+                                                //  staging in place; .n: doubles)
   hipEvent_t stage_ev[2] = {nullptr, nullptr};
   bool stage_busy[2] = {false, false};
   int stage_next = 0;
-  std::vector<tlh::FrameClouds*> frame_store;   // tloam_frame_stash / tloam_frame_select
+  std::vector<std::unique_ptr<tlh::FrameClouds>> frame_store;   // tloam_frame_stash / tloam_frame_select
   int frame_selected = -1;                      // slot whose clouds are the registered ones (-1: the context's own)
   int dbg_planned_sweeps = 0;      // TLOAM_PLANNED_SWEEPS: force the sweep budget per Solve (exercises the top-up)
   std::vector<int> planned_sweeps; // per outer iteration x 3: sweeps the Solve needed in the last three frames
@@ -550,7 +540,7 @@ struct tloam_ctx {
   // one-shot peer exchange (tl_common.hpp MboxView): the local buffer (fine-grained device memory, exported through
   // HIP IPC), the peers' buffers as mapped here, the device-resident exchange counter, the ticket of the fused sweep
   double* mbox_local = nullptr;
-  void* mbox_opened[tl::kMaxRanks] = {};   // hipIpcOpenMemHandle results (closed at destroy)
+  void* mbox_opened[tl::kMaxRanks] = {};   // hipIpcOpenMemHandle results (closed at destroy: comm_release, like mbox_local)
   tl::MboxView mbox{};
   DBuf<unsigned long long> mbox_ctr;
   DBuf<int> k3_ticket;
@@ -654,7 +644,7 @@ hipError_t grow_into(DBuf<T>& fresh, const DBuf<T>& cur, size_t want, size_t kee
 // One growth of a store, all its arrays or none: add() gives an array fresh storage of `want` rows behind whatever is in flight,
 // the first `keep` rows copied (0: the array is rebuilt, not copied), and returns it (nullptr once anything failed); commit()
 // swaps every fresh array in and parks the old storage in the store's Retired -- or, after a failure, frees the fresh arrays,
-// leaves the store as it was and returns TLOAM_E_HIP with `what` in last_error
+// leaves the store as it was and returns TLOAM_E_HIP with `what` in last_error.  Until then the fresh arrays are the Grower's
 class Grower {
  public:
   Grower(tloam_ctx* c, Retired& parked) : c_(c), parked_(parked) {}
@@ -663,8 +653,12 @@ class Grower {
     if (e_ != hipSuccess) return nullptr;
     DBuf<T> fresh;
     e_ = grow_into(fresh, cur, want, keep, c_->stream);
-    if (fresh.p) arrays_.push_back({&cur, fresh.p, fresh.cap, &swap_in<T>});
-    return e_ == hipSuccess ? fresh.p : nullptr;
+    T* const q = fresh.p;
+    if (q) {
+      arrays_.push_back({&cur, fresh.cap, &swap_in<T>});
+      fresh_.take(fresh);
+    }
+    return e_ == hipSuccess ? q : nullptr;
   }
   void check(hipError_t e) {   // a step on the fresh storage (the first failure counts)
     if (e_ == hipSuccess) e_ = e;
@@ -672,19 +666,19 @@ class Grower {
   int commit(const char* what) {
     if (e_ != hipSuccess) {
       (void)hipStreamSynchronize(c_->stream);
-      for (const Array& a : arrays_) (void)hipFree(a.fresh);
+      fresh_.release();
       c_->last_error = std::string(what) + hipGetErrorString(e_);
       return TLOAM_E_HIP;
     }
-    for (const Array& a : arrays_) a.swap(a.cur, a.fresh, a.cap, parked_);
+    for (size_t i = 0; i < arrays_.size(); ++i) arrays_[i].swap(arrays_[i].cur, fresh_.p[i], arrays_[i].cap, parked_);
+    fresh_.p.clear();   // (the store's now)
     return TLOAM_OK;
   }
 
  private:
   struct Array {
     void* cur;     // the store's DBuf<T>
-    void* fresh;
-    size_t cap;
+    size_t cap;    // of its fresh storage, fresh_.p[same index]
     void (*swap)(void* cur, void* fresh, size_t cap, Retired& parked);
   };
   template <class T>
@@ -698,6 +692,7 @@ class Grower {
   Retired& parked_;
   hipError_t e_ = hipSuccess;
   std::vector<Array> arrays_;
+  Retired fresh_;   // the fresh arrays are the Grower's until commit() hands them to the store (freed with it otherwise)
 };
 inline bool one_rank(const tloam_ctx* c) { return c->nranks == 1 && !c->loopback; }    // the single-rank launch forms apply
 inline bool exchanging(const tloam_ctx* c) { return c->nranks > 1 || c->loopback; }    // the sharded launch forms run
@@ -757,7 +752,7 @@ int submap_init_body(tloam_ctx* c, const tloam_submap_config& want, const double
 int submap_update_resident(tloam_ctx* c, const double pose[16], size_t n_planar, size_t n_sphere, size_t n_edge, size_t n_ground,
                            DBuf<double>& block);
 // tl_api_map.hip: the odometry frame's map stage -- reserve at the start of a later frame, launch after the match, collect the
-// count after the frame's last wait, commit when the frame is accepted; MapState::release at destroy
+// count after the frame's last wait, commit when the frame is accepted
 int map_frame_reserve(tloam_ctx* c, size_t n);
 int map_stage_launch(tloam_ctx* c, const double pose[16], size_t n);
 int map_stage_collect(tloam_ctx* c, tloam_odom_stats* st);
@@ -782,7 +777,7 @@ template <class State>
 VoxelRows voxel_rows_of(State& S, size_t nv, const char* name) {
   tl::VmapReadArgs A;
   memset(&A, 0, sizeof(A));
-  A.pkey = S.key.p; A.pn = S.n.p; A.pqx = S.qx.p; A.pqy = S.qy.p; A.pqz = S.qz.p;
+  A.pkey = S.rows.key.p; A.pn = S.rows.n.p; A.pqx = S.rows.qx.p; A.pqy = S.rows.qy.p; A.pqz = S.rows.qz.p;
   A.voxel = S.cfg.voxel;
   for (int a = 0; a < 3; ++a) A.origin[a] = S.cfg.origin[a];
   return VoxelRows{A, S.rd_c, S.rd_n, S.look, S.ctl, nv, name};
@@ -809,7 +804,7 @@ bool place_clouds_on(const tloam_ctx* c);
 int place_clouds_reserve(tloam_ctx* c, const size_t n[8]);
 void place_clouds_note(tloam_ctx* c, const tl::LoopSpan spans[8]);
 int arena_grow(tloam_ctx* c, size_t need_doubles);   // (tl_api_place.hip) the arena holds arena_used + need doubles
-void loop_release(tloam_ctx* c);                      // (tl_api_loop.hip) at destroy: the child contexts, the scratch
+void loop_release(tloam_ctx* c);                      // (tl_api_loop.hip) at destroy / off: the child contexts, the scratch
 // (tl_api_graph.hip) what tloam_graph_correct_pose computes, after its checks of the context: P'_k * rigid_inverse(P_k) * pose_in
 void graph_correct_pose(const tloam_ctx* c, size_t keyframe, const double pose_in[16], double pose_out[16]);
 int set_target_frame_from(tloam_ctx* c, const double* const xyz[4], const size_t n[4], hipMemcpyKind from);   // tl_api_frames.hip

@@ -56,21 +56,21 @@ int tloam_time_read_stream(tloam_ctx* c, size_t bytes, int launches, double* gbp
   HIPC(c, hipSetDevice(c->device));
   const size_t n = bytes / 8 / kProbeStreams / 128 * 128;        // elements per stream, whole chunks
   const size_t stride = n + 256;
-  double *d = nullptr, *out = nullptr;
+  DBuf<double> d, out;   // (freed when the call returns, behind its synchronise)
   const int blocks = (c->device_cus > 0 ? c->device_cus : 256) * 2;
-  HIPC(c, hipMalloc((void**)&d, sizeof(double) * stride * kProbeStreams));
-  hipError_t e = hipMalloc((void**)&out, sizeof(double) * (size_t)blocks * 256);
-  if (e != hipSuccess) { (void)hipFree(d); HIPC(c, e); }
+  HIPC(c, d.reserve(stride * kProbeStreams));
+  HIPC(c, out.reserve((size_t)blocks * 256));
+  hipError_t e;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   float ms = 0.f;
   const int nchunks = (int)(n / 128);
-  e = hipMemsetAsync(d, 0, sizeof(double) * stride * kProbeStreams, c->stream);
+  e = hipMemsetAsync(d.p, 0, sizeof(double) * stride * kProbeStreams, c->stream);
   if (e == hipSuccess) e = hipEventCreate(&e0);
   if (e == hipSuccess) e = hipEventCreate(&e1);
   if (e == hipSuccess) {
-    for (int i = 0; i < 3; ++i) hipLaunchKernelGGL(k_read_stream<true>, dim3(blocks), dim3(256), 0, c->stream, d, stride, nchunks, out);
+    for (int i = 0; i < 3; ++i) hipLaunchKernelGGL(k_read_stream<true>, dim3(blocks), dim3(256), 0, c->stream, d.p, stride, nchunks, out.p);
     e = hipEventRecord(e0, c->stream);
-    for (int i = 0; i < launches; ++i) hipLaunchKernelGGL(k_read_stream<true>, dim3(blocks), dim3(256), 0, c->stream, d, stride, nchunks, out);
+    for (int i = 0; i < launches; ++i) hipLaunchKernelGGL(k_read_stream<true>, dim3(blocks), dim3(256), 0, c->stream, d.p, stride, nchunks, out.p);
     if (e == hipSuccess) e = hipEventRecord(e1, c->stream);
     if (e == hipSuccess) e = hipEventSynchronize(e1);
     if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
@@ -78,8 +78,6 @@ int tloam_time_read_stream(tloam_ctx* c, size_t bytes, int launches, double* gbp
   if (e0) (void)hipEventDestroy(e0);
   if (e1) (void)hipEventDestroy(e1);
   (void)hipStreamSynchronize(c->stream);
-  (void)hipFree(d);
-  (void)hipFree(out);
   HIPC(c, e);
   *gbps = (double)n * 8.0 * kProbeStreams * launches / ((double)ms * 1e-3) / 1e9;
   return TLOAM_OK;
