@@ -796,6 +796,66 @@ int tloam_graph_read_poses(tloam_ctx* ctx, size_t first, size_t count, double* p
 int tloam_graph_correct_pose(tloam_ctx* ctx, int64_t keyframe, const double pose_in_colmajor[16], double pose_out_colmajor[16]);
 /* Every graph call on a context with nranks > 1: TLOAM_E_INVALID. */
 
+/* ---- robust mode of the pose graph: GNC-TLS on the loop edges (additive to ABI 8) ---------------------------------
+ * Off by default: with it off or never configured, every call, bit, launch and byte is what it is without it.  A loop edge that
+ * joins two places which only look alike passes verification and, as a plain quadratic term, bends every corrected pose.  The
+ * robust mode carries the front end's truncated least squares to the loop edges by graduated non-convexity.  Each loop edge e
+ * (edges N-1 .. m-1) has a scale s_e in [0, 1], at first 1; the chain is never scaled; a solve's weights are s_e * w_e.  Its
+ * statistic is r_e = sum_a w_e[a] e_e[a]^2 at the current poses with the caller's weights (a ascending); c2 = noise_chi2.
+ *   1. the solve above from the input poses, all s = 1;  2. r;  3. max r <= c2: done -- the plain solve's bits, no outer
+ *   iteration (ALL_INLIERS);  4. else mu = c2 / (2 max r - c2);  5. outer iteration t = 1 .. max_outer: lo = mu / (mu + 1) c2,
+ *   hi = (mu + 1) / mu c2; s_e = 1 where r_e <= lo, 0 where r_e >= hi or r_e is not finite, else sqrt(c2 mu (mu + 1) / r_e) - mu
+ *   (held to [0, 1]); the solve above from the current poses with the scaled weights; r at its result; every s_e 0 or 1: done
+ *   (BINARY); else mu *= mu_factor;  6. max_outer used up: OUTER_LIMIT, the last poses and scales stand.
+ * An inner solve that ends on TLOAM_GRAPH_STOP_COST keeps the poses before its dropped step and the outer loop goes on.  A
+ * rejected edge stays rejected only while r_e >= hi: nothing re-admits an edge after the run.  A true edge can end rejected (a
+ * second self-consistent fixed point).  Costs one launch and one small read per outer iteration, and two more of
+ * each per run, on top of the inner solves'.  Reductions have a fixed order: two runs give the same bits. */
+typedef struct tloam_graph_robust_config {
+  int32_t enabled;     /* 0 */
+  int32_t max_outer;   /* 100, in [1, 10000] */
+  double noise_chi2;   /* 36 (> 0, finite): an inlier's largest r.  6 sigma in one component; 16.81 is the 99 % point of
+                          chi-squared with 6 degrees of freedom and rejected true edges on the test graphs */
+  double mu_factor;    /* 1.4 (> 1, finite): the usual GNC value; 2.0 made the same decisions in half the outer iterations */
+} tloam_graph_robust_config;
+void tloam_graph_robust_default_config(tloam_graph_robust_config* cfg);
+/* cfg NULL: the defaults (off).  Persists across tloam_odometry_reset.  Drops the corrected poses, as tloam_graph_configure
+ * does.  A value out of its range: TLOAM_E_INVALID. */
+int tloam_graph_robust_configure(tloam_ctx* ctx, const tloam_graph_robust_config* cfg);
+
+#define TLOAM_GRAPH_ROBUST_STOP_OFF 0          /* the mode is off: the plain solve */
+#define TLOAM_GRAPH_ROBUST_STOP_ALL_INLIERS 1  /* max r <= noise_chi2 after the plain solve (or the solver was not run) */
+#define TLOAM_GRAPH_ROBUST_STOP_BINARY 2       /* every scale is 0 or 1 */
+#define TLOAM_GRAPH_ROBUST_STOP_OUTER_LIMIT 3  /* max_outer */
+typedef struct tloam_graph_robust_info {
+  int32_t outer_iterations;
+  int32_t stop_reason;                 /* TLOAM_GRAPH_ROBUST_STOP_* */
+  int64_t gn_iterations;               /* all inner solves together, the first included */
+  int64_t cg_iterations;
+  int64_t rejected, kept, undecided;   /* loop edges with s == 0, s == 1, in between, at the end */
+  double mu_first, mu_last;            /* mu of the first and of the last outer iteration (0: there was none) */
+  double max_chi2_first;               /* max r after the plain solve */
+} tloam_graph_robust_info;
+
+/* tloam_graph_solve with the robust mode: the same validation.  rcfg NULL: the context's robust configuration; a value out of
+ * its range: TLOAM_E_INVALID.  info describes the last inner solve, except that initial_cost is the first solve's.
+ * loop_scale_out / loop_chi2_out: [n_edges - (n_nodes - 1)], the loop edges' final s and r (r at poses_out); either may be
+ * NULL, so may info and rinfo.  With enabled == 0 it is tloam_graph_solve bit for bit: no further launch or read, the scales
+ * are 1 and r, which nothing computed, is NaN. */
+int tloam_graph_solve_robust(tloam_ctx* ctx, const tloam_graph_config* cfg, const tloam_graph_robust_config* rcfg, size_t n_nodes,
+                             const double* poses_in_colmajor, size_t n_edges, const tloam_graph_edge* edges,
+                             double* poses_out_colmajor, tloam_graph_info* info, tloam_graph_robust_info* rinfo,
+                             double* loop_scale_out, double* loop_chi2_out);
+/* tloam_graph_optimize runs the robust algorithm when the context's robust configuration is enabled; tloam_graph_read_poses,
+ * tloam_graph_correct_pose and tloam_closed_map_build(pose_source = 1) then use its poses.
+ * Loop edges [first, first + count) of the last tloam_graph_optimize: the index of the edge's constraint as
+ * tloam_loop_read_constraints numbers them, its scale and its r (any of the three may be NULL).  TLOAM_E_NOT_READY before an
+ * optimise; after a non-robust one every scale is 1 and r is NaN. */
+int tloam_graph_read_loop_scales(tloam_ctx* ctx, size_t first, size_t count, int64_t* constraint_index, double* scale, double* chi2);
+/* Of the last tloam_graph_optimize (TLOAM_E_NOT_READY before it). */
+int tloam_graph_get_robust_info(tloam_ctx* ctx, tloam_graph_robust_info* out);
+/* Every robust graph call on a context with nranks > 1: TLOAM_E_INVALID. */
+
 /* ---- the closed map: the keyframe clouds merged under corrected poses (additive to ABI 8) ----------------------
  * A third map beside tloam_map_* and tloam_voxel_map_*.  Runs only when called: with it never called, every frame, stat, map,
  * place record, constraint, corrected pose and launch is what it is without it.  Input: the context's keyframes 0 .. K-1 with

@@ -764,6 +764,27 @@ struct GraphArgs {
   GraphRecord* rec;
 };
 void launch_graph_step(const GraphArgs& A, hipStream_t s);   // k_graph_step: linearise, solve, step, the new cost
+// the robust mode: the loop edges' statistics r_e at A.P with the base weights, their scales, the solver's
+// weights w = s * w0
+constexpr int kGraphReweightOnes = 0;   // s = 1 (after the plain solve: only r is wanted)
+constexpr int kGraphReweightRule = 1;   // s from r by the scale rule at mu
+constexpr int kGraphReweightKeep = 2;   // s as stored (after the last solve: only r is wanted)
+struct GraphRobustRecord {
+  double max_r;                   // over the loop edges (a NaN is passed over)
+  double sum_sr;                  // sum of s_e r_e: the loop edges' share of the cost the next solve starts from
+  int rejected, kept, undecided;  // s == 0, s == 1, in between
+  int reserved0;
+};
+struct GraphReweightArgs {
+  int mode;                       // kGraphReweight*
+  double mu, c2;                  // c2: noise_chi2
+  const double* w0;               // [m][6] the base weights
+  double* w;                      // [m][6] the solver's weights: rows n-1 .. m-1 are written
+  double* s;                      // [m - (n - 1)] the loop edges' scales
+  double* r;                      // [m - (n - 1)] their statistics
+  GraphRobustRecord* rec;
+};
+void launch_graph_reweight(const GraphArgs& A, const GraphReweightArgs& W, hipStream_t s);   // k_graph_reweight (A.w is not read)
 
 // ---- PCA feature extraction (tl_feature.hip; feature_extract.cpp:47-197) -----------------------
 struct FeatArgs {

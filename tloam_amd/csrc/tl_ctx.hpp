@@ -411,7 +411,19 @@ struct GraphState {
   DBuf<tl::GraphRecord> rec;
   bool have = false;               // tloam_graph_optimize has run since the last reset / configure
   std::vector<double> corrected;   // [16 n] column-major
-  void drop() { have = false; corrected.clear(); }
+  // the robust mode: its configuration (off), k_graph_reweight's record, and of the last optimise what it
+  // reports, the loop edges' constraint indices, scales and statistics
+  tloam_graph_robust_config rcfg = {0, 100, 36.0, 1.4};   // tloam_graph_robust_default_config
+  DBuf<tl::GraphRobustRecord> rrec;
+  tloam_graph_robust_info rinfo{};
+  std::vector<int64_t> loop_constraint;
+  std::vector<double> loop_scale, loop_chi2;
+  void drop() {
+    have = false;
+    corrected.clear();
+    rinfo = {};
+    loop_constraint.clear(); loop_scale.clear(); loop_chi2.clear();
+  }
 };
 
 // the closed map (tl_api_cmap.hip): its configuration, its rows in id order and their table (the voxel map's

@@ -11,6 +11,9 @@
 // (the table the host built), p . Ap | x, r, and the chain preconditioner as a suffix and a prefix sum over the nodes (a thread's
 // chunk serially, the chunks by a wave scan, the waves in order) | r . z, p.  Every sum has a fixed order and there are no atomics:
 // two runs give the same bits.
+//   k_graph_reweight 1 x 512  robust mode only, once per outer iteration: a thread strides the loop edges; an
+//                             edge's r = sum_a w0_a e_a^2 at P (edge_residual's expression, base weights), its scale by the rule at
+//                             mu, the solver's weights s * w0; max r, the three counts and sum s r in block_max / block_sum order
 // Compiled with -ffp-contract=off, like the other stages whose numpy restatement (tests/graph_np.py) states the arithmetic.
 #include "tl_common.hpp"
 
@@ -315,7 +318,59 @@ __global__ __launch_bounds__(kGraphThreads) void k_graph_step(GraphArgs A) {
   }
 }
 
+// One workgroup, like the solver: the reductions keep a fixed order.  B is A with the base weights in place of the solver's, so
+// that edge_residual states r as it states the cost's terms
+__global__ __launch_bounds__(kGraphThreads) void k_graph_reweight(GraphArgs B, GraphReweightArgs W) {
+  __shared__ double s_red[5][kWaves];
+  const int first = B.n - 1;   // the loop edges are first .. m-1
+  const double lo = W.mu / (W.mu + 1.0) * W.c2, hi = (W.mu + 1.0) / W.mu * W.c2;   // (read under kGraphReweightRule only)
+  double mx = 0.0, sr = 0.0, n_rej = 0.0, n_kept = 0.0, n_mid = 0.0;   // (counts as doubles: exact, and block_sum adds them)
+  for (int e = first + (int)threadIdx.x; e < B.m; e += kT) {
+    Pose Tij;
+    double g[6];
+    const double r = edge_residual(B, B.P, e, &Tij, g);
+    const int l = e - first;
+    double s = 1.0;
+    if (W.mode == kGraphReweightKeep) s = W.s[l];
+    if (W.mode == kGraphReweightRule) {
+      if (r <= lo) s = 1.0;
+      else if (!(r < hi)) s = 0.0;   // (a non-finite r is rejected)
+      else s = fmin(fmax(sqrt(W.c2 * W.mu * (W.mu + 1.0) / r) - W.mu, 0.0), 1.0);   // (rounding at the two ends)
+    }
+    W.s[l] = s;
+    W.r[l] = r;
+#pragma unroll
+    for (int a = 0; a < 6; ++a) W.w[6 * (size_t)e + a] = s * W.w0[6 * (size_t)e + a];
+    mx = fmax(mx, r);
+    sr = sr + s * r;
+    n_rej = n_rej + (s == 0.0 ? 1.0 : 0.0);
+    n_kept = n_kept + (s == 1.0 ? 1.0 : 0.0);
+    n_mid = n_mid + (s != 0.0 && s != 1.0 ? 1.0 : 0.0);
+  }
+  const double max_r = block_max(mx, s_red[0]);
+  const double sum_sr = block_sum(sr, s_red[1]);
+  const double rejected = block_sum(n_rej, s_red[2]);
+  const double kept = block_sum(n_kept, s_red[3]);
+  const double undecided = block_sum(n_mid, s_red[4]);
+  if (threadIdx.x == 0) {
+    GraphRobustRecord R;
+    R.max_r = max_r;
+    R.sum_sr = sum_sr;
+    R.rejected = (int)rejected;
+    R.kept = (int)kept;
+    R.undecided = (int)undecided;
+    R.reserved0 = 0;
+    *W.rec = R;
+  }
+}
+
 }  // namespace
+
+void launch_graph_reweight(const GraphArgs& A, const GraphReweightArgs& W, hipStream_t s) {
+  GraphArgs B = A;
+  B.w = W.w0;
+  hipLaunchKernelGGL(k_graph_reweight, dim3(1), dim3(kGraphThreads), 0, s, B, W);
+}
 
 void launch_graph_step(const GraphArgs& A, hipStream_t s) {
   hipLaunchKernelGGL(k_graph_step, dim3(1), dim3(kGraphThreads), 0, s, A);

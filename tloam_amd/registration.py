@@ -197,6 +197,28 @@ class GraphInfo(C.Structure):
                 "last_cg_residual": float(self.last_cg_residual)}
 
 
+class GraphRobustConfig(C.Structure):
+    """tloam_graph_robust_config: the robust mode of the pose graph, GNC-TLS on the loop edges."""
+    _fields_ = [("enabled", C.c_int32), ("max_outer", C.c_int32), ("noise_chi2", C.c_double), ("mu_factor", C.c_double)]
+
+
+GRAPH_ROBUST_STOP = {0: "off", 1: "all_inliers", 2: "binary", 3: "outer_limit"}
+
+
+class GraphRobustInfo(C.Structure):
+    """tloam_graph_robust_info."""
+    _fields_ = [("outer_iterations", C.c_int32), ("stop_reason", C.c_int32), ("gn_iterations", C.c_int64),
+                ("cg_iterations", C.c_int64), ("rejected", C.c_int64), ("kept", C.c_int64), ("undecided", C.c_int64),
+                ("mu_first", C.c_double), ("mu_last", C.c_double), ("max_chi2_first", C.c_double)]
+
+    def as_dict(self):
+        return {"outer_iterations": int(self.outer_iterations), "stop_reason": int(self.stop_reason),
+                "stop": GRAPH_ROBUST_STOP[int(self.stop_reason)], "gn_iterations": int(self.gn_iterations),
+                "cg_iterations": int(self.cg_iterations), "rejected": int(self.rejected), "kept": int(self.kept),
+                "undecided": int(self.undecided), "mu_first": float(self.mu_first), "mu_last": float(self.mu_last),
+                "max_chi2_first": float(self.max_chi2_first)}
+
+
 class TlsConfig(C.Structure):
     """tloam_tls_config: the 16 keys of the `TLS:` block (config/mapping/lidar_odometry.yaml:23-39)."""
     _fields_ = [
@@ -396,6 +418,12 @@ def load_library():
         "tloam_graph_optimize": (C.c_int, [vp, C.POINTER(GraphInfo)]),
         "tloam_graph_read_poses": (C.c_int, [vp, sz, sz, dp]),
         "tloam_graph_correct_pose": (C.c_int, [vp, C.c_int64, dp, dp]),
+        "tloam_graph_robust_default_config": (None, [C.POINTER(GraphRobustConfig)]),
+        "tloam_graph_robust_configure": (C.c_int, [vp, C.POINTER(GraphRobustConfig)]),
+        "tloam_graph_solve_robust": (C.c_int, [vp, C.POINTER(GraphConfig), C.POINTER(GraphRobustConfig), sz, dp, sz,
+                                               C.POINTER(GraphEdge), dp, C.POINTER(GraphInfo), C.POINTER(GraphRobustInfo), dp, dp]),
+        "tloam_graph_read_loop_scales": (C.c_int, [vp, sz, sz, C.POINTER(C.c_int64), dp, dp]),
+        "tloam_graph_get_robust_info": (C.c_int, [vp, C.POINTER(GraphRobustInfo)]),
         "tloam_closed_map_default_config": (None, [C.POINTER(ClosedMapConfig)]),
         "tloam_closed_map_configure": (C.c_int, [vp, C.POINTER(ClosedMapConfig)]),
         "tloam_closed_map_get_info": (C.c_int, [vp, C.POINTER(ClosedMapInfo)]),
@@ -440,7 +468,8 @@ EXPORTED_SYMBOLS = (
     "tloam_place_describe", "tloam_loop_default_config", "tloam_loop_configure", "tloam_loop_get_info",
     "tloam_place_set_keyframe_clouds", "tloam_place_read_keyframe_clouds", "tloam_loop_verify_pending", "tloam_loop_verify_pair",
     "tloam_loop_read_constraints", "tloam_graph_default_config", "tloam_graph_configure", "tloam_graph_solve", "tloam_graph_optimize",
-    "tloam_graph_read_poses", "tloam_graph_correct_pose", "tloam_closed_map_default_config", "tloam_closed_map_configure",
+    "tloam_graph_read_poses", "tloam_graph_correct_pose", "tloam_graph_robust_default_config", "tloam_graph_robust_configure",
+    "tloam_graph_solve_robust", "tloam_graph_read_loop_scales", "tloam_graph_get_robust_info", "tloam_closed_map_default_config", "tloam_closed_map_configure",
     "tloam_closed_map_get_info", "tloam_closed_map_build", "tloam_closed_map_read", "tloam_closed_map_read_box",
     "tloam_closed_map_read_poses", "tloam_rccl_unique_id", "tloam_comm_init_rccl",
     "tloam_comm_mailbox_export", "tloam_comm_init_mailbox",
@@ -992,9 +1021,9 @@ class HipRegistration:
         cfg = cfg if cfg is not None else default_graph_config(**over)
         self._check(self.L.tloam_graph_configure(self.h, C.byref(cfg)), "tloam_graph_configure")
 
-    def graph_solve(self, poses, i, j, Z, w, cfg: GraphConfig | None = None):
-        """the caller's graph: poses (n, 4, 4); edges i, j (m,), Z (m, 4, 4), w (m, 6), the first n - 1 the chain ->
-        (poses (n, 4, 4), info dict); cfg None: the context's configuration"""
+    @staticmethod
+    def _graph_arrays(poses, i, j, Z, w):
+        """-> (poses column-major (n, 4, 4), number of edges, the tloam_graph_edge array)"""
         P = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 4, 4).transpose(0, 2, 1))
         Zc = np.asarray(Z, np.float64).reshape(-1, 4, 4).transpose(0, 2, 1).reshape(-1, 16)
         wv = np.asarray(w, np.float64).reshape(-1, 6)
@@ -1004,17 +1033,61 @@ class HipRegistration:
             rec = np.frombuffer(edges, dtype=np.dtype([("i", np.int64), ("j", np.int64), ("Z", np.float64, 16),
                                                        ("w", np.float64, 6)]), count=m)
             rec["i"], rec["j"], rec["Z"], rec["w"] = np.asarray(i, np.int64), np.asarray(j, np.int64), Zc, wv
+        return P, m, edges
+
+    def graph_solve(self, poses, i, j, Z, w, cfg: GraphConfig | None = None):
+        """the caller's graph: poses (n, 4, 4); edges i, j (m,), Z (m, 4, 4), w (m, 6), the first n - 1 the chain ->
+        (poses (n, 4, 4), info dict); cfg None: the context's configuration"""
+        P, m, edges = self._graph_arrays(poses, i, j, Z, w)
         out = np.zeros_like(P)
         info = GraphInfo()
         self._check(self.L.tloam_graph_solve(self.h, C.byref(cfg) if cfg is not None else None, len(P), _dp(P), m, edges,
                                              _dp(out), C.byref(info)), "tloam_graph_solve")
         return out.transpose(0, 2, 1).copy(), info.as_dict()
 
+    # ---- its robust mode: GNC-TLS on the loop edges (DESIGN.md section 20)
+    def graph_robust_configure(self, cfg: GraphRobustConfig | None = None, **over):
+        """the context's robust configuration (default_graph_robust_config(**over) when cfg is None: off unless enabled=1);
+        drops the corrected poses.  Kept across odometry_reset."""
+        cfg = cfg if cfg is not None else default_graph_robust_config(**over)
+        self._check(self.L.tloam_graph_robust_configure(self.h, C.byref(cfg)), "tloam_graph_robust_configure")
+
+    def graph_solve_robust(self, poses, i, j, Z, w, cfg: GraphConfig | None = None, rcfg: GraphRobustConfig | None = None):
+        """graph_solve with the robust mode -> (poses (n, 4, 4), info dict of the last inner solve, robust info dict, the loop
+        edges' scales (m - (n - 1),), their statistics r); cfg / rcfg None: the context's configurations"""
+        P, m, edges = self._graph_arrays(poses, i, j, Z, w)
+        nl = max(m - (len(P) - 1), 0)
+        out = np.zeros_like(P)
+        scale, chi2 = np.zeros(max(nl, 1)), np.zeros(max(nl, 1))
+        info, rinfo = GraphInfo(), GraphRobustInfo()
+        self._check(self.L.tloam_graph_solve_robust(self.h, C.byref(cfg) if cfg is not None else None,
+                                                    C.byref(rcfg) if rcfg is not None else None, len(P), _dp(P), m, edges, _dp(out),
+                                                    C.byref(info), C.byref(rinfo), _dp(scale), _dp(chi2)), "tloam_graph_solve_robust")
+        return out.transpose(0, 2, 1).copy(), info.as_dict(), rinfo.as_dict(), scale[:nl].copy(), chi2[:nl].copy()
+
+    def graph_read_loop_scales(self, first=0, count=None):
+        """the loop edges [first, first + count) of the last graph_optimize -> (constraint indices as loop_constraints numbers
+        them, scales, statistics r); count None: all of them"""
+        if count is None:
+            count = max(getattr(self, "_graph_loops", 0) - int(first), 0)
+        m = int(count)
+        idx, scale, chi2 = np.zeros(max(m, 1), np.int64), np.zeros(max(m, 1)), np.zeros(max(m, 1))
+        self._check(self.L.tloam_graph_read_loop_scales(self.h, int(first), m, idx.ctypes.data_as(C.POINTER(C.c_int64)), _dp(scale),
+                                                        _dp(chi2)), "tloam_graph_read_loop_scales")
+        return idx[:m].copy(), scale[:m].copy(), chi2[:m].copy()
+
+    def graph_robust_info(self) -> dict:
+        """tloam_graph_get_robust_info: the robust mode's report of the last graph_optimize"""
+        info = GraphRobustInfo()
+        self._check(self.L.tloam_graph_get_robust_info(self.h, C.byref(info)), "tloam_graph_get_robust_info")
+        return info.as_dict()
+
     def graph_optimize(self) -> dict:
         """optimises the context's graph (keyframe poses, odometry chain, accepted constraints) -> info dict"""
         info = GraphInfo()
         self._check(self.L.tloam_graph_optimize(self.h, C.byref(info)), "tloam_graph_optimize")
         self._graph_n = int(info.n_nodes)   # (how many corrected poses graph_poses reads by default)
+        self._graph_loops = int(info.n_loop_edges)
         return info.as_dict()
 
     def graph_poses(self, first=0, count=None):
@@ -1324,6 +1397,12 @@ def default_graph_config(**over) -> GraphConfig:
     """tloam_graph_default_config (30 Gauss-Newton iterations of at most 20000 conjugate-gradient iterations, step_tol 1e-7,
     cg_tol 1e-10, the odometry and loop sigmas) with keyword overrides"""
     return _strict_config(GraphConfig, "tloam_graph_default_config", over)
+
+
+def default_graph_robust_config(**over) -> GraphRobustConfig:
+    """tloam_graph_robust_default_config (off; noise_chi2 36, mu_factor 1.4, at most 100 outer iterations) with keyword
+    overrides, e.g. enabled=1"""
+    return _strict_config(GraphRobustConfig, "tloam_graph_robust_default_config", over)
 
 
 def default_closed_map_config(**over) -> ClosedMapConfig:

@@ -3,7 +3,8 @@
 `laps(n, ...)`: n keyframes `spacing` apart along `n_laps` laps of a closed course (a circle with a gentle climb and pitch, so
 that all six degrees of freedom are exercised).  Chain edge k measures rigid_inverse(T_k) * T_{k+1} with seeded noise, so the
 chained initial guess drifts; every `loop_every`-th keyframe of the later laps has a loop edge to the keyframe one lap earlier,
-with its own noise.  Weights are the inverse variances of that noise.  `open_chain`: the same without loop edges."""
+with its own noise.  Weights are the inverse variances of that noise.  `open_chain`: the same without loop edges.
+`false_loops(g, n_bad, seed)`: redirects some of a graph's loop edges to another place."""
 from __future__ import annotations
 
 import numpy as np
@@ -76,6 +77,23 @@ def laps(n, seed=0, n_laps=2, spacing=1.0, loop_every=5, odom_sigma=(0.01, 0.001
 
 def open_chain(n, seed=0, **kw):
     return laps(n, seed, loop_every=0, **kw)
+
+
+def false_loops(g, n_bad, seed=0, min_gap=20):
+    """Makes `n_bad` randomly chosen loop edges of `g` false, in place: such an edge (i, j) keeps its ends and its weights, and
+    measures rigid_inverse(truth[i]) * truth[k] for a random keyframe k at least `min_gap` keyframes from both i and j -- a place
+    that looked like another.  -> their edge indices, ascending"""
+    rng = np.random.default_rng(9000 + seed)
+    n = len(g["truth"])
+    first = n - 1
+    bad = np.sort(first + rng.choice(g["n_loops"], size=n_bad, replace=False))
+    g["Z"] = np.array(g["Z"], copy=True)
+    for e in bad:
+        i, j = int(g["i"][e]), int(g["j"][e])
+        ks = np.array([k for k in range(n) if abs(k - i) >= min_gap and abs(k - j) >= min_gap])
+        k = int(rng.choice(ks))
+        g["Z"][e] = _inv(g["truth"][i]) @ g["truth"][k]
+    return bad.astype(np.int64)
 
 
 def position_error(P, truth):
