@@ -913,6 +913,54 @@ int tloam_closed_map_read_box(tloam_ctx* ctx, const double lo[3], const double h
 int tloam_closed_map_read_poses(tloam_ctx* ctx, size_t first, size_t count, double* poses_colmajor);
 /* Every closed map call on a context with nranks > 1: TLOAM_E_INVALID. */
 
+/* ---- the carve of the closed map: per voxel, the rays that passed through it (additive to ABI 8) ----------------
+ * A lidar return also says that nothing was between the sensor and the point.  A carve counts, per occupied voxel of the built
+ * closed map, the rays of the build's keyframes 0 .. K-1 that passed through it: M beside N.  Runs only when called; nothing
+ * of the closed map or the context is changed, and tloam_closed_map_read / _read_box still return every voxel.
+ * Rays: the points of the clouds selected by ray_mask (the bits of cloud_mask; 0: the build's mask), keyframes ascending, slots
+ * ascending, points in stored order.  A ray runs from O, the translation of the keyframe's pose, to E, the point under that
+ * pose.  It is skipped when E is not finite, when its length L is 0 or > max_range, or when the cell of O or E has
+ * |i| >= 2^20 on an axis.  The cells it visits are those of a walk through the grid from the cell of O, the cell of E left
+ * out; a visited cell that is a voxel of the closed map with centroid C is missed when the foot of C on the ray lies at
+ * 0 <= t < 1 - end_margin / L and C is within radius of the ray.  All sums are integers: two carves, or two contexts, give the
+ * same bits.  DESIGN.md 21 states the arithmetic. */
+typedef struct tloam_closed_map_carve_config {
+  double max_range;    /* 60.0 m: longer rays are skipped */
+  double end_margin;   /* 1.0 m in front of the return in which nothing is missed */
+  double radius;       /* 0.25 m: the largest distance from a centroid to a ray that misses it; +inf allowed */
+  int32_t ray_mask;    /* 0: the closed map's cloud_mask */
+  int32_t reserved0;
+} tloam_closed_map_carve_config;
+void tloam_closed_map_carve_default_config(tloam_closed_map_carve_config* cfg);
+/* cfg NULL: the defaults.  Drops the counts (not the closed map); persists across tloam_odometry_reset.  max_range not > 0 or
+ * not finite, end_margin < 0 or not finite, radius not > 0 (NaN too), a mask with bits beyond 8: TLOAM_E_INVALID, and the
+ * counts stay. */
+int tloam_closed_map_carve_configure(tloam_ctx* ctx, const tloam_closed_map_carve_config* cfg);
+typedef struct tloam_closed_map_carve_info {
+  int64_t n_keyframes;     /* K of the closed map carved */
+  int64_t n_rays;          /* the points of the selected clouds, skipped ones included */
+  int64_t skipped_rays;
+  int64_t steps;           /* cells visited */
+  int64_t tested;          /* of them, voxels of the closed map */
+  int64_t misses;          /* the sum of M */
+  int64_t voxels_missed;   /* voxels with M > 0 */
+  int32_t launches;        /* kernel launches of the carve: the same for every K, mask and ray count */
+  int32_t reserved0;
+} tloam_closed_map_carve_info;
+/* Of the last carve; zero when there are no counts. */
+int tloam_closed_map_get_carve_info(tloam_ctx* ctx, tloam_closed_map_carve_info* info);
+/* Counts M for the built closed map, replacing the previous counts.  TLOAM_E_NOT_READY without a built closed map.  Whatever
+ * empties or replaces the closed map drops the counts; keyframes added since the build cast no rays.  info may be NULL. */
+int tloam_closed_map_carve(tloam_ctx* ctx, tloam_closed_map_carve_info* info_or_null);
+/* M of voxels [first, first + count) in id order.  TLOAM_E_NOT_READY without counts. */
+int tloam_closed_map_read_misses(tloam_ctx* ctx, size_t first, size_t count, int64_t* misses);
+/* tloam_closed_map_read_box's rule, order and capacity convention, a voxel additionally left out when
+ * M >= min_miss && (double) M > miss_ratio * (double) N.  lo and hi both NULL: the whole map.  TLOAM_E_NOT_READY without counts. */
+int tloam_closed_map_read_carved(tloam_ctx* ctx, const double* lo_or_null, const double* hi_or_null, int64_t min_count,
+                                 int64_t min_miss, double miss_ratio, size_t capacity, size_t* n, double* centroids_aos,
+                                 int64_t* counts, int64_t* misses);
+/* Every carve call on a context with nranks > 1: TLOAM_E_INVALID. */
+
 /* ---- multi-GPU: correspondence set sharded over ranks, one all-reduce per sweep --------
  * (nothing in the reference).  Call before set_source / set_correspondences.
  * (a) native RCCL over xGMI: unique_id = the 128 bytes of an ncclUniqueId made on rank 0

@@ -1,0 +1,191 @@
+// tl_carve.hip -- the device side of the closed map's carve (tl_api_carve.hip): per occupied voxel of the
+// closed map the number M of keyframe rays that passed through it, beside the number N of returns that fell in it.
+//
+// Launches of a carve, the same three for any number of keyframes, spans and rays (no host synchronisation between them):
+//   k_carve_clear   grid x 256   zeroes M and the control words
+//   k_carve_rays    grid x 256   per ray: its span from its global index (as k_cmap_flag), transform, the walk through the grid's
+//                                cells, every visited cell looked up in the closed map's slot table (read only), the miss test
+//                                against an occupied cell's centroid, an int64 atomic add on its M; the ray's counters summed
+//                                over the wave by shuffles, one atomic per counter and wave
+//   k_carve_count   grid x 256   per voxel: M > 0 counted by ballot, one atomic per wave
+// The carved read is k_carve_box: k_vmap_box's selection, order and compaction, with the voxels seen through left out.
+//
+// Compiled with -ffp-contract=off.  The operation order of a ray (tests/closed_map_carve_np.py restates it), per axis a:
+//   O_a = P[12 + a],  E = map_transform_point(P, p),  D_a = E_a - O_a,  DD = (Dx*Dx + Dy*Dy) + Dz*Dz,  L = sqrt(DD)
+//   s0_a = (O_a - o_a) / v,  s1_a = (E_a - o_a) / v,  c_a = floor(s0_a),  ce_a = floor(s1_a),  d_a = s1_a - s0_a
+//   tMax_a = ((c_a + 1) - s0_a) / d_a  (d_a > 0),  (c_a - s0_a) / d_a  (d_a < 0),  +inf  (d_a == 0 or c_a == ce_a)
+//   tDelta_a = step_a / d_a,  step_a = sign(d_a)
+//   n = sum_a |ce_a - c_a| steps; before each one the current cell is visited; the step takes the axis of the smallest tMax
+//   (a tie: the lowest axis), c_a += step_a, tMax_a = +inf when c_a == ce_a, else tMax_a + tDelta_a
+//   an occupied visited cell with centroid C:  u_a = C_a - O_a,  tt = ((ux*Dx + uy*Dy) + uz*Dz) / DD,  w_a = u_a - tt * D_a,
+//   a miss when 0 <= tt, tt < 1 - end_margin / L and (wx*wx + wy*wy) + wz*wz <= radius * radius
+#include <algorithm>
+
+#include "tl_voxel.hpp"
+
+namespace tl {
+namespace {
+
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+// the id of the closed map's voxel `key`, -1 when it has none
+__device__ __forceinline__ int carve_find(const CarveWork& W, unsigned long long key) {
+  for (unsigned long long t = mix64(key) & W.pmask;; t = (t + 1) & W.pmask) {
+    const int id = W.ptab[t];
+    if (id < 0) return -1;
+    if (W.pkey[id] == key) return id;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_carve_clear(CarveWork W) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+  for (size_t t = i; t < (size_t)W.nv; t += stride) W.miss[t] = 0ull;
+  if (i < 8) W.ctl[i] = 0ull;
+}
+
+__global__ __launch_bounds__(256) void k_carve_rays(CarveWork W) {
+  __shared__ int s_span[2];
+  block_spans(W, s_span);
+  const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+  const double kInf = __builtin_huge_val(), kLimit = (double)(1ll << kVmapBits);
+  unsigned long long skipped = 0ull, steps = 0ull, tested = 0ull, misses = 0ull;
+  if (g < W.n) {
+    const CmapSpan S = W.span[span_of(W.span, s_span[0], s_span[1], g)];
+    const double* x = W.arena + S.off + 3 * (g - S.start);
+    const double* P = W.pose + 16 * (size_t)S.kf;
+    const double Ox = P[12], Oy = P[13], Oz = P[14];
+    double Ex, Ey, Ez;
+    map_transform_point(P, x[0], x[1], x[2], &Ex, &Ey, &Ez);
+    const double Dx = Ex - Ox, Dy = Ey - Oy, Dz = Ez - Oz;
+    const double DD = (Dx * Dx + Dy * Dy) + Dz * Dz;
+    const double L = sqrt(DD);
+    const double s0x = (Ox - W.origin[0]) / W.voxel, s0y = (Oy - W.origin[1]) / W.voxel, s0z = (Oz - W.origin[2]) / W.voxel;
+    const double s1x = (Ex - W.origin[0]) / W.voxel, s1y = (Ey - W.origin[1]) / W.voxel, s1z = (Ez - W.origin[2]) / W.voxel;
+    const double fx = floor(s0x), fy = floor(s0y), fz = floor(s0z), gx = floor(s1x), gy = floor(s1y), gz = floor(s1z);
+    bool ok = __builtin_isfinite(Ex) && __builtin_isfinite(Ey) && __builtin_isfinite(Ez);
+    ok = ok && !(L > W.max_range) && !(L == 0.0);
+    ok = ok && fabs(fx) < kLimit && fabs(fy) < kLimit && fabs(fz) < kLimit && fabs(gx) < kLimit && fabs(gy) < kLimit &&
+         fabs(gz) < kLimit;
+    if (!ok) {
+      skipped = 1ull;
+    } else {
+      int cx = (int)fx, cy = (int)fy, cz = (int)fz;
+      const int ex = (int)gx, ey = (int)gy, ez = (int)gz;
+      const double dx = s1x - s0x, dy = s1y - s0y, dz = s1z - s0z;
+      const int stx = dx > 0.0 ? 1 : dx < 0.0 ? -1 : 0, sty = dy > 0.0 ? 1 : dy < 0.0 ? -1 : 0, stz = dz > 0.0 ? 1 : dz < 0.0 ? -1 : 0;
+      double tx = cx == ex ? kInf : dx > 0.0 ? ((fx + 1.0) - s0x) / dx : dx < 0.0 ? (fx - s0x) / dx : kInf;
+      double ty = cy == ey ? kInf : dy > 0.0 ? ((fy + 1.0) - s0y) / dy : dy < 0.0 ? (fy - s0y) / dy : kInf;
+      double tz = cz == ez ? kInf : dz > 0.0 ? ((fz + 1.0) - s0z) / dz : dz < 0.0 ? (fz - s0z) / dz : kInf;
+      const double tdx = (double)stx / dx, tdy = (double)sty / dy, tdz = (double)stz / dz;   // (not read on an axis that never steps)
+      const int n = abs(ex - cx) + abs(ey - cy) + abs(ez - cz);
+      const double tlim = 1.0 - W.end_margin / L;
+      steps = (unsigned long long)n;
+      for (int k = 0; k < n; ++k) {
+        const unsigned long long key = (unsigned long long)(cx + (1 << kVmapBits)) |
+                                       ((unsigned long long)(cy + (1 << kVmapBits)) << 21) |
+                                       ((unsigned long long)(cz + (1 << kVmapBits)) << 42);
+        const int id = carve_find(W, key);
+        if (id >= 0) {
+          tested++;
+          const long long N = W.pn[id];
+          const double ux = centroid(W.origin[0], W.voxel, cx, W.pqx[id], N) - Ox;
+          const double uy = centroid(W.origin[1], W.voxel, cy, W.pqy[id], N) - Oy;
+          const double uz = centroid(W.origin[2], W.voxel, cz, W.pqz[id], N) - Oz;
+          const double tt = ((ux * Dx + uy * Dy) + uz * Dz) / DD;
+          const double wx = ux - tt * Dx, wy = uy - tt * Dy, wz = uz - tt * Dz;
+          if (0.0 <= tt && tt < tlim && (wx * wx + wy * wy) + wz * wz <= W.radius2) {
+            misses++;
+            atomicAdd(&W.miss[id], 1ull);
+          }
+        }
+        const bool y = ty < tx;
+        const bool z = tz < (y ? ty : tx);
+        if (z) {
+          cz += stz;
+          tz = cz == ez ? kInf : tz + tdz;
+        } else if (y) {
+          cy += sty;
+          ty = cy == ey ? kInf : ty + tdy;
+        } else {
+          cx += stx;
+          tx = cx == ex ? kInf : tx + tdx;
+        }
+      }
+    }
+  }
+  skipped = wave_sum(skipped); steps = wave_sum(steps); tested = wave_sum(tested); misses = wave_sum(misses);
+  if ((threadIdx.x & 63) == 0) {
+    if (skipped) atomicAdd(&W.ctl[0], skipped);
+    if (steps) atomicAdd(&W.ctl[1], steps);
+    if (tested) atomicAdd(&W.ctl[2], tested);
+    if (misses) atomicAdd(&W.ctl[3], misses);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_carve_count(CarveWork W) {
+  const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
+  const unsigned long long bal = __ballot(id < W.nv && W.miss[id] > 0ull);
+  if ((threadIdx.x & 63) == 0 && bal) atomicAdd(&W.ctl[4], (unsigned long long)__popcll(bal));
+}
+
+// the voxels of k_vmap_box's selection (the box only when A.boxed) that were not seen through, compacted in id order
+__global__ __launch_bounds__(256) void k_carve_box(CarveReadArgs A, int nblocks) {
+  __shared__ unsigned long long s_wave[4];
+  __shared__ unsigned long long s_prefix;
+  __shared__ int s_bid;
+  const VmapReadArgs& R = A.rows;
+  const int tid = threadIdx.x;
+  const int bid = block_ticket(&R.ctl[0], &s_bid);
+  const size_t id = (size_t)bid * 256 + tid;
+  double c[3] = {0.0, 0.0, 0.0};
+  long long n = 0, m = 0;
+  bool sel = false;
+  if (id < R.count) {
+    const unsigned long long key = R.pkey[id];
+    const long long Q[3] = {R.pqx[id], R.pqy[id], R.pqz[id]};
+    n = R.pn[id];
+    m = A.miss[id];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) c[a] = centroid(R.origin[a], R.voxel, key_axis(key, a), Q[a], n);
+    sel = n >= R.min_count;
+    if (A.boxed) {
+#pragma unroll
+      for (int a = 0; a < 3; ++a) sel = sel && c[a] >= R.lo[a] && c[a] <= R.hi[a];
+    }
+    sel = sel && !(m >= A.min_miss && (double)m > A.miss_ratio * (double)n);
+  }
+  int pos, total;
+  block_flag_scan(sel, s_wave, &pos, &total);
+  if (tid == 0) s_prefix = lookback_prefix(R.look, bid, (unsigned long long)total, LookFaultDevice{&R.ctl[1]});
+  __syncthreads();
+  if (sel) {
+    const size_t p = (size_t)(s_prefix + pos);
+    if (R.out_c) { R.out_c[3 * p] = c[0]; R.out_c[3 * p + 1] = c[1]; R.out_c[3 * p + 2] = c[2]; }
+    if (R.out_n) R.out_n[p] = n;
+    if (A.out_m) A.out_m[p] = m;
+  }
+  if (bid == nblocks - 1 && tid == 0) R.ctl[2] = s_prefix + total;
+}
+
+inline unsigned blocks_of(long long n) { return (unsigned)std::max<long long>((n + 255) / 256, 1); }   // (nothing still launches)
+
+}  // namespace
+
+int launch_carve(const CarveWork& W, hipStream_t s) {
+  hipLaunchKernelGGL(k_carve_clear, dim3(std::min(blocks_of(W.nv), 2048u)), dim3(256), 0, s, W);
+  hipLaunchKernelGGL(k_carve_rays, dim3(blocks_of(W.n)), dim3(256), 0, s, W);
+  hipLaunchKernelGGL(k_carve_count, dim3(blocks_of(W.nv)), dim3(256), 0, s, W);
+  return 3;
+}
+
+void launch_carve_read(const CarveReadArgs& A, hipStream_t s) {
+  if (A.rows.count == 0) return;
+  const int nb = (int)blocks_of((long long)A.rows.count);
+  hipLaunchKernelGGL(k_carve_box, dim3(nb), dim3(256), 0, s, A, nb);
+}
+
+}  // namespace tl

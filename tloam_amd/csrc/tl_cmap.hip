@@ -20,32 +20,6 @@
 namespace tl {
 namespace {
 
-// the last span of [lo, hi] that starts at or before g
-__device__ __forceinline__ int span_of(const CmapSpan* sp, int lo, int hi, long long g) {
-  while (lo < hi) {
-    const int m = (lo + hi + 1) >> 1;
-    if (sp[m].start <= g) lo = m;
-    else hi = m - 1;
-  }
-  return lo;
-}
-
-// the spans of the block's first and last point, found once per block: a point then searches between them (usually one span)
-__device__ __forceinline__ void block_spans(const CmapWork& W, int s_span[2]) {
-  if (threadIdx.x == 0) {
-    const long long first = (long long)blockIdx.x * 256;
-    const long long last = first + 255 < W.n ? first + 255 : W.n - 1;
-    int lo = 0, hi = 0;
-    if (first < W.n) {
-      lo = span_of(W.span, 0, W.nspan - 1, first);
-      hi = span_of(W.span, lo, W.nspan - 1, last);
-    }
-    s_span[0] = lo;
-    s_span[1] = hi;
-  }
-  __syncthreads();
-}
-
 // point g (< W.n): its keyframe, and where it falls in the grid (key and q when inside)
 __device__ __forceinline__ VmapCell cmap_point(const CmapWork& W, long long g, int s_lo, int s_hi, int* kf, unsigned long long* key,
                                                unsigned q[3]) {

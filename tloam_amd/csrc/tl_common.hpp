@@ -659,6 +659,40 @@ struct CmapWork {
 int launch_cmap_stage(const CmapWork& W, hipStream_t s);
 int launch_cmap_emit(const CmapWork& W, hipStream_t s);
 
+// ---- the carve of the closed map: per occupied voxel, the rays of the keyframes that passed through it (tl_carve.hip,
+// DESIGN.md section 21).  A ray is a stored point of a keyframe: from the translation of the keyframe's pose to the point under
+// that pose.  The rays come from a span table of the closed map's kind (CmapSpan) written for the carve's ray mask; the map is
+// looked up through its own slot table and nothing in it is written: the counts are an array of their own, in id order
+struct CarveWork {
+  const double* arena;
+  const CmapSpan* span;       // [nspan + 1], as CmapWork::span
+  int nspan;
+  int nkf;
+  long long n;                // rays: the points of all spans
+  const double* pose;         // [nkf][16] column-major: the poses the closed map was built with
+  double voxel, origin[3];
+  double max_range, end_margin, radius2;   // radius2 = radius * radius (+inf: the distance does not decide)
+  // the closed map, read only
+  unsigned long long pmask;
+  const int* ptab;
+  const unsigned long long* pkey;
+  const long long *pn, *pqx, *pqy, *pqz;
+  long long nv;               // its voxels
+  unsigned long long* miss;   // [nv] M in id order
+  unsigned long long* ctl;    // [0] skipped rays, [1] steps, [2] tested, [3] misses, [4] voxels with M > 0
+};
+// clear | rays | count: no host synchronisation; returns the launches it made (the same for every size)
+int launch_carve(const CarveWork& W, hipStream_t s);
+struct CarveReadArgs {
+  VmapReadArgs rows;          // the closed map's rows, the box (when `boxed`), min_count, the outputs, look and ctl as k_vmap_box's
+  const long long* miss;      // [count] M in id order
+  long long min_miss;
+  double miss_ratio;          // a voxel is left out when M >= min_miss && (double) M > miss_ratio * (double) N
+  long long* out_m;           // the misses of the voxels kept (may be null)
+  int boxed;                  // 0: the whole map
+};
+void launch_carve_read(const CarveReadArgs& A, hipStream_t s);
+
 // ---- deskew of a scan under constant velocity (tl_deskew.hip) -------------
 struct DeskewArgs {
   const double* in;               // AoS xyz [3n]

@@ -2,7 +2,7 @@
 // lifetime, tl_api_frames.hip: HBM residency + search grids, tl_api_match.hip: the scanMatching driver, tl_api_comm.hip: multi-GPU
 // exchange, tl_api_submap.hip: device-resident submap, tl_api_feature.hip: PCA features, tl_api_seg.hip: segmentation,
 // tl_api_odom.hip: the whole odometry frame, tl_api_map.hip: its global map and registered scan, tl_api_vmap.hip: its merged
-// voxel map, tl_api_deskew.hip: its deskew, tl_api_place.hip: place recognition, tl_api_cmap.hip: the closed map).
+// voxel map, tl_api_deskew.hip: its deskew, tl_api_place.hip: place recognition, tl_api_cmap.hip: the closed map, tl_api_carve.hip: its carve).
 // Memory: every buffer below belongs to the struct that declares it and dies with it (the owning types come first).
 #pragma once
 
@@ -438,10 +438,22 @@ struct CmapState {
   DBuf<double> rd_c;
   DBuf<long long> rd_n;
   DBuf<unsigned long long> look, ctl;
-  void drop() {   // the closed map goes; its configuration and storage stay
+  // the carve (tl_api_carve.hip): its configuration, M in id order beside the rows, what the last carve
+  // reports, the carved read's scratch.  The counts belong to the closed map they were counted in and go with it
+  tloam_closed_map_carve_config carve_cfg = {60.0, 1.0, 0.25, 0, 0};   // tloam_closed_map_carve_default_config until configured
+  DBuf<unsigned long long> miss, carve_ctl;
+  DBuf<long long> rd_m;
+  bool carved = false;             // a carve has succeeded since the last drop
+  tloam_closed_map_carve_info carve_info{};
+  void drop_carve() {
+    carved = false;
+    carve_info = tloam_closed_map_carve_info{};
+  }
+  void drop() {   // the closed map goes, and the carve's counts with it; the configurations and storage stay
     built = false;
     info = tloam_closed_map_info{};
     poses.clear();
+    drop_carve();
   }
 };
 

@@ -1,7 +1,8 @@
 // tl_voxel.hpp -- what the device voxel grids share: the submap's down-sample (tl_submap.hip), the
-// global map (tl_map.hip), the merged voxel map (tl_vmap.hip) and the closed map (tl_cmap.hip).  One definition each of the key
-// hash and the two table inserts, of the block scans, of the single-pass look-back with its one bound, of the eight-word post to
-// the host, and of the voxel map's key / q arithmetic and its run sums.  Device code only.
+// global map (tl_map.hip), the merged voxel map (tl_vmap.hip), the closed map (tl_cmap.hip) and its carve (tl_carve.hip).  One
+// definition each of the key hash and the two table inserts, of the block scans, of the single-pass look-back with its one bound,
+// of the eight-word post to the host, of the voxel map's key / q arithmetic and its run sums, and of the span table's search.
+// Device code only.
 // An includer must be compiled with -ffp-contract=off: vmap_quantise and centroid are the bit-for-bit contract of DESIGN.md 14.
 #pragma once
 
@@ -229,6 +230,35 @@ __device__ __forceinline__ WaveRun wave_run_sums(bool ok, unsigned long long key
     r.sum[k] = v[k] - (hl > 0 ? b : 0u);
   }
   return r;
+}
+
+// ---- a span table in global point order (CmapSpan: the closed map's build and its carve) ----
+// the last span of [lo, hi] that starts at or before g
+__device__ __forceinline__ int span_of(const CmapSpan* sp, int lo, int hi, long long g) {
+  while (lo < hi) {
+    const int m = (lo + hi + 1) >> 1;
+    if (sp[m].start <= g) lo = m;
+    else hi = m - 1;
+  }
+  return lo;
+}
+
+// the spans of the block's first and last point, found once per block: a point then searches between them (usually one span).
+// Work: CmapWork or CarveWork (span, nspan, n)
+template <class Work>
+__device__ __forceinline__ void block_spans(const Work& W, int s_span[2]) {
+  if (threadIdx.x == 0) {
+    const long long first = (long long)blockIdx.x * 256;
+    const long long last = first + 255 < W.n ? first + 255 : W.n - 1;
+    int lo = 0, hi = 0;
+    if (first < W.n) {
+      lo = span_of(W.span, 0, W.nspan - 1, first);
+      hi = span_of(W.span, lo, W.nspan - 1, last);
+    }
+    s_span[0] = lo;
+    s_span[1] = hi;
+  }
+  __syncthreads();
 }
 
 }  // namespace tl

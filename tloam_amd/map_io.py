@@ -1,4 +1,5 @@
-"""PCD export of the global map and of the merged voxel map (section 14).
+"""PCD export of the global map, of the merged voxel map (section 14) and of the carved closed map
+(section 21).
 
 The reference declares a `saveMap` service (srv/saveMap.srv) and never serves it; this is the file a user of the map needs.
 PCD v0.7 (the Point Cloud Library's format), fields `x y z`, each `F 8` (float64), so the device's doubles are written and
@@ -135,3 +136,12 @@ def read_voxel_pcd(path: str):
         cen = np.array(cols[:3], dtype=np.float64).T.reshape(n, 3)
         return np.ascontiguousarray(cen), np.array([int(v) for v in cols[3]], dtype=np.int64)
     raise ValueError(f"{path}: DATA {kind} is not supported")
+
+
+# ---- the carved closed map: the voxels that were not seen through
+def write_carved_closed_map_pcd(path: str, H, lo=None, hi=None, min_count=1, min_miss=3, miss_ratio=1.0, ascii: bool = False) -> int:
+    """Writes what `H.closed_map_read_carved` keeps of a carved closed map (a HipRegistration after closed_map_build and
+    closed_map_carve) as a file of write_voxel_pcd: centroids and counts N -> the voxels written."""
+    cen, cnt, _ = H.closed_map_read_carved(lo, hi, min_count, min_miss, miss_ratio)
+    write_voxel_pcd(path, cen, cnt, ascii=ascii)
+    return len(cnt)

@@ -111,6 +111,22 @@ class ClosedMapInfo(C.Structure):
     as_dict = _int_fields
 
 
+class ClosedMapCarveConfig(C.Structure):
+    """tloam_closed_map_carve_config: the longest ray, the margin in front of a return in which nothing is missed, the largest
+    distance from a centroid to a ray that misses it, the cloud slots whose points are rays (0: the build's)."""
+    _fields_ = [("max_range", C.c_double), ("end_margin", C.c_double), ("radius", C.c_double), ("ray_mask", C.c_int32),
+                ("reserved0", C.c_int32)]
+
+
+class ClosedMapCarveInfo(C.Structure):
+    """tloam_closed_map_carve_info."""
+    _fields_ = [("n_keyframes", C.c_int64), ("n_rays", C.c_int64), ("skipped_rays", C.c_int64), ("steps", C.c_int64),
+                ("tested", C.c_int64), ("misses", C.c_int64), ("voxels_missed", C.c_int64), ("launches", C.c_int32),
+                ("reserved0", C.c_int32)]
+
+    as_dict = _int_fields
+
+
 class DeskewConfig(C.Structure):
     """tloam_deskew_config: the deskew's switch, its time source (0 azimuth, 1 per-point times), the sweep's direction (+1
     counter-clockwise seen from +z), the azimuth it starts at and the sweep fraction the pose describes."""
@@ -431,6 +447,13 @@ def load_library():
         "tloam_closed_map_read": (C.c_int, [vp, sz, sz, dp, C.POINTER(C.c_int64)]),
         "tloam_closed_map_read_box": (C.c_int, [vp, dp, dp, C.c_int64, sz, C.POINTER(sz), dp, C.POINTER(C.c_int64)]),
         "tloam_closed_map_read_poses": (C.c_int, [vp, sz, sz, dp]),
+        "tloam_closed_map_carve_default_config": (None, [C.POINTER(ClosedMapCarveConfig)]),
+        "tloam_closed_map_carve_configure": (C.c_int, [vp, C.POINTER(ClosedMapCarveConfig)]),
+        "tloam_closed_map_get_carve_info": (C.c_int, [vp, C.POINTER(ClosedMapCarveInfo)]),
+        "tloam_closed_map_carve": (C.c_int, [vp, C.POINTER(ClosedMapCarveInfo)]),
+        "tloam_closed_map_read_misses": (C.c_int, [vp, sz, sz, C.POINTER(C.c_int64)]),
+        "tloam_closed_map_read_carved": (C.c_int, [vp, dp, dp, C.c_int64, C.c_int64, C.c_double, sz, C.POINTER(sz), dp,
+                                                   C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
         "tloam_rccl_unique_id": (C.c_int, [vp]),
         "tloam_comm_init_rccl": (C.c_int, [vp, C.c_int, C.c_int, vp]),
         "tloam_comm_init_callback": (C.c_int, [vp, C.c_int, C.c_int, ALLREDUCE_FN, vp]),
@@ -471,7 +494,9 @@ EXPORTED_SYMBOLS = (
     "tloam_graph_read_poses", "tloam_graph_correct_pose", "tloam_graph_robust_default_config", "tloam_graph_robust_configure",
     "tloam_graph_solve_robust", "tloam_graph_read_loop_scales", "tloam_graph_get_robust_info", "tloam_closed_map_default_config", "tloam_closed_map_configure",
     "tloam_closed_map_get_info", "tloam_closed_map_build", "tloam_closed_map_read", "tloam_closed_map_read_box",
-    "tloam_closed_map_read_poses", "tloam_rccl_unique_id", "tloam_comm_init_rccl",
+    "tloam_closed_map_read_poses", "tloam_closed_map_carve_default_config", "tloam_closed_map_carve_configure",
+    "tloam_closed_map_get_carve_info", "tloam_closed_map_carve", "tloam_closed_map_read_misses", "tloam_closed_map_read_carved",
+    "tloam_rccl_unique_id", "tloam_comm_init_rccl",
     "tloam_comm_mailbox_export", "tloam_comm_init_mailbox",
     "tloam_comm_init_callback", "tloam_shard_range", "tloam_shard_ranges_frame", "tloam_se3_exp", "tloam_se3_log", "tloam_se3_plus",
 )
@@ -1163,6 +1188,53 @@ class HipRegistration:
         self._check(self.L.tloam_closed_map_read_poses(self.h, int(first), m, _dp(out)), "tloam_closed_map_read_poses")
         return out[:m].reshape(m, 4, 4).transpose(0, 2, 1).copy()
 
+    # ---- the carve of the closed map: per voxel, the rays that passed through it
+    def closed_map_carve_configure(self, cfg: ClosedMapCarveConfig | None = None, **over):
+        """the carve's configuration (default_closed_map_carve_config(**over) when cfg is None); drops the counts, not the closed
+        map.  Kept across odometry_reset."""
+        cfg = cfg if cfg is not None else default_closed_map_carve_config(**over)
+        self._check(self.L.tloam_closed_map_carve_configure(self.h, C.byref(cfg)), "tloam_closed_map_carve_configure")
+
+    def closed_map_carve(self) -> dict:
+        """counts, per voxel of the built closed map, the keyframe rays that passed through it -> info dict"""
+        info = ClosedMapCarveInfo()
+        self._check(self.L.tloam_closed_map_carve(self.h, C.byref(info)), "tloam_closed_map_carve")
+        return info.as_dict()
+
+    def closed_map_carve_info(self) -> dict:
+        info = ClosedMapCarveInfo()
+        self._check(self.L.tloam_closed_map_get_carve_info(self.h, C.byref(info)), "tloam_closed_map_get_carve_info")
+        return info.as_dict()
+
+    def closed_map_misses(self, first=0, count=None):
+        """M of voxels [first, first + count) in id order, (m,) int64; count None: to the end"""
+        if count is None:
+            count = max(self.closed_map_info()["n_voxels"] - int(first), 0)
+        m = int(count)
+        out = np.zeros(max(m, 1), np.int64)
+        self._check(self.L.tloam_closed_map_read_misses(self.h, int(first), m, _lp(out)), "tloam_closed_map_read_misses")
+        return out[:m].copy()
+
+    def closed_map_read_carved(self, lo=None, hi=None, min_count=1, min_miss=3, miss_ratio=1.0):
+        """closed_map_read_box's voxels (lo and hi None: the whole map) without those seen through -- M >= min_miss and
+        M > miss_ratio * N -- in id order -> (centroids (m, 3), counts (m,), misses (m,))"""
+        if (lo is None) != (hi is None):
+            raise ValueError("lo and hi go together")
+        if lo is not None:
+            lo = np.ascontiguousarray(lo, dtype=np.float64).reshape(3)
+            hi = np.ascontiguousarray(hi, dtype=np.float64).reshape(3)
+        head = (self.h, _dp(lo), _dp(hi), int(min_count), int(min_miss), float(miss_ratio))
+        n = C.c_size_t(0)
+        rc = self.L.tloam_closed_map_read_carved(*head, 0, C.byref(n), None, None, None)
+        if rc not in (0, -1) or (rc == -1 and n.value == 0):
+            self._check(rc, "tloam_closed_map_read_carved")
+        m = n.value
+        cen, cnt, mis = np.zeros((max(m, 1), 3)), np.zeros(max(m, 1), np.int64), np.zeros(max(m, 1), np.int64)
+        if m:
+            self._check(self.L.tloam_closed_map_read_carved(*head, m, C.byref(n), _dp(cen), _lp(cnt), _lp(mis)),
+                        "tloam_closed_map_read_carved")
+        return cen[: n.value].copy(), cnt[: n.value].copy(), mis[: n.value].copy()
+
     def fitness(self):
         f, r = C.c_double(0), C.c_double(0)
         rc = self.L.tloam_fitness(self.h, C.byref(f), C.byref(r))
@@ -1410,6 +1482,12 @@ def default_closed_map_config(**over) -> ClosedMapConfig:
     origin=(0, 0, 5), cloud_mask=0x0F"""
     return _strict_config(ClosedMapConfig, "tloam_closed_map_default_config", over,
                           {"origin": lambda v: (C.c_double * 3)(*[float(x) for x in v])})
+
+
+def default_closed_map_carve_config(**over) -> ClosedMapCarveConfig:
+    """tloam_closed_map_carve_default_config (max_range 60, end_margin 1, radius 0.25, ray_mask 0: the build's) with keyword
+    overrides, e.g. max_range=20.0, radius=float("inf")"""
+    return _strict_config(ClosedMapCarveConfig, "tloam_closed_map_carve_default_config", over)
 
 
 def default_submap_config(**over) -> SubmapConfig:
