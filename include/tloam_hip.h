@@ -961,6 +961,58 @@ int tloam_closed_map_read_carved(tloam_ctx* ctx, const double* lo_or_null, const
                                  int64_t* counts, int64_t* misses);
 /* Every carve call on a context with nranks > 1: TLOAM_E_INVALID. */
 
+/* ---- the surfels of the closed map: per voxel a normal and three variances (additive to ABI 8) --------------------
+ * The closed map knows where surfaces are; a surfel pass adds how they face.  Per occupied voxel of the built closed map it
+ * gathers the second moments of the points that fell in it and solves them for a normal and the variances along the three
+ * principal axes.  Runs only when called; nothing of the closed map, of a carve's counts or of the context is changed.
+ * Points: exactly the build's -- the clouds of the build's cloud_mask of keyframes 0 .. K-1, keyframes ascending, slots
+ * ascending, stored order, each under the pose the build used; a point that is not finite under its pose is left out, and a
+ * keyframe with a finite point at |i| >= 2^20 adds nothing.  A point whose cell is not a voxel of the map (its clouds were
+ * re-attached since the build) adds nothing and is counted in orphan_points.
+ * Per point, integers: r = q >> 8 of the voxel map's q (2^-16 of a voxel), w_a = round-half-up of ((O_a - E_a) / v) * 256
+ * clamped to +-2^30, with E the point and O the translation of its keyframe's pose.  Per voxel thirteen int64 sums:
+ * Ns, R_a = sum r_a, S_ab = sum r_a r_b (xx xy xz yy yz zz), W_a = sum w_a -- the same bits in any order, pass and context.
+ * Per voxel with Ns >= min_points, in fp64: the mean m = R / Ns, the covariance c_ab = S_ab / Ns - m_a m_b, its eigenvalues
+ * ascending and the eigenvector n of the smallest, turned so that n . W >= 0 (towards where it was seen from); the variances are
+ * the eigenvalues in m^2.  A voxel of fewer points is unsolved: n and the variances are zero.  Collinear or coincident points
+ * are solved as they come; tloam_closed_map_read_surfels_box's gate is what rejects them.  DESIGN.md 22 states the arithmetic. */
+typedef struct tloam_closed_map_surfel_config {
+  int32_t min_points;   /* 5: a voxel of fewer points is not solved; >= 3 */
+  int32_t reserved0;
+} tloam_closed_map_surfel_config;
+void tloam_closed_map_surfel_default_config(tloam_closed_map_surfel_config* cfg);
+/* cfg NULL: the defaults.  Drops the surfels (not the closed map or the carve's counts); persists across tloam_odometry_reset.
+ * min_points < 3: TLOAM_E_INVALID, and the surfels stay. */
+int tloam_closed_map_surfel_configure(tloam_ctx* ctx, const tloam_closed_map_surfel_config* cfg);
+typedef struct tloam_closed_map_surfel_info {
+  int64_t n_keyframes;     /* K of the closed map */
+  int64_t n_points;        /* points summed: the sum of Ns */
+  int64_t orphan_points;   /* points whose cell is not a voxel of the map */
+  int64_t solved_voxels;   /* voxels with Ns >= min_points */
+  int32_t launches;        /* kernel launches of the pass: the same for every K, mask and point count */
+  int32_t reserved0;
+} tloam_closed_map_surfel_info;
+/* Of the last pass; zero when there are no surfels. */
+int tloam_closed_map_get_surfel_info(tloam_ctx* ctx, tloam_closed_map_surfel_info* info);
+/* Gathers and solves the surfels of the built closed map, replacing the previous ones.  TLOAM_E_NOT_READY without a built closed
+ * map.  Whatever empties or replaces the closed map drops the surfels; keyframes added since the build add nothing.  The first
+ * pass allocates 152 bytes per voxel of the closed map's capacity.  info may be NULL. */
+int tloam_closed_map_surfels(tloam_ctx* ctx, tloam_closed_map_surfel_info* info_or_null);
+/* The thirteen sums of voxels [first, first + count) in id order, out[13 * count]: Ns, Rx Ry Rz, Sxx Sxy Sxz Syy Syz Szz,
+ * Wx Wy Wz.  TLOAM_E_NOT_READY without surfels. */
+int tloam_closed_map_read_moments(tloam_ctx* ctx, size_t first, size_t count, int64_t* out);
+/* Normals [3 count], variances ascending [3 count] (m^2) and Ns [count] of voxels [first, first + count) in id order; any of
+ * the three may be NULL.  TLOAM_E_NOT_READY without surfels. */
+int tloam_closed_map_read_surfels(tloam_ctx* ctx, size_t first, size_t count, double* normals_aos, double* evals_aos,
+                                  int64_t* counts);
+/* tloam_closed_map_read_carved's rule (N >= min_count, the box; lo and hi both NULL: the whole map), order and capacity
+ * convention, a voxel kept only when it is solved, ev2 > 0, ev0 <= max_sigma * max_sigma (max_sigma = +inf allowed) and
+ * (ev1 - ev0) >= min_planarity * ev2.  counts: Ns.  Any output may be NULL.  TLOAM_E_NOT_READY without surfels. */
+int tloam_closed_map_read_surfels_box(tloam_ctx* ctx, const double* lo_or_null, const double* hi_or_null, int64_t min_count,
+                                      double max_sigma, double min_planarity, size_t capacity, size_t* n, double* centroids_aos,
+                                      double* normals_aos, double* evals_aos, int64_t* counts);
+/* Every surfel call on a context with nranks > 1: TLOAM_E_INVALID. */
+
 /* ---- multi-GPU: correspondence set sharded over ranks, one all-reduce per sweep --------
  * (nothing in the reference).  Call before set_source / set_correspondences.
  * (a) native RCCL over xGMI: unique_id = the 128 bytes of an ncclUniqueId made on rank 0

@@ -1,0 +1,212 @@
+// tl_api_surfel.hip -- C ABI of the closed map's surfels (include/tloam_hip.h: tloam_closed_map_surfel*, _surfels, _read_moments,
+// _read_surfels, _read_surfels_box; kernels in tl_surfel.hip).
+//
+// A pass takes the built closed map (CmapState: its table, the poses and the cloud mask it was built with) and the host's
+// keyframe table (PlaceState::kf) for the build's keyframes, uploads one span table and the poses, and enqueues four launches on
+// the context's stream; it waits once, for the counters.  The sums, normals and variances live beside the rows in id order and go
+// with the closed map (CmapState::drop).  Nothing of the closed map, of a carve's counts or of anything else in the context is
+// written.
+#include <math.h>
+
+#include "tl_ctx.hpp"
+
+using namespace tl;
+
+namespace {
+
+// the enqueue, the wait and the counters of a pass; the previous surfels have been dropped
+int surfel_body(tloam_ctx* c, tloam_closed_map_surfel_info& I) {
+  CmapState& M = c->cmap;
+  const PlaceState& P = c->place;
+  const size_t K = M.poses.size() / 16;   // the build's keyframes: later ones add nothing
+  std::vector<CmapSpan> spans;            // the build's span table: keyframes ascending, the build's clouds in slot order
+  long long n = 0;
+  for (size_t k = 0; k < K && k < P.kf.size(); ++k)
+    for (int j = 0; j < 8; ++j) {
+      if (!((M.cfg.cloud_mask >> j) & 1) || P.kf[k].n[j] == 0) continue;
+      spans.push_back(CmapSpan{(long long)P.kf[k].off[j], n, (int)k, 0});
+      n += (long long)P.kf[k].n[j];
+    }
+  const int nspan = (int)spans.size();
+  spans.push_back(CmapSpan{0, n, 0, 0});   // (the end: span[nspan].start = n)
+  const size_t nv = (size_t)M.info.n_voxels, cap = std::max<size_t>(M.rows.cap, 1);
+  HIPC(c, hipSetDevice(c->device));
+  if (M.surfel_sums.cap < kSurfelSums * cap || M.surfel_over.cap < std::max<size_t>(K, 1) || M.surfel_ctl.cap < 8)
+    HIPC(c, hipStreamSynchronize(c->stream));   // (the arrays replaced may still be read)
+  HIPC(c, M.surfel_sums.reserve(kSurfelSums * cap)); HIPC(c, M.surfel_nrm.reserve(3 * cap)); HIPC(c, M.surfel_ev.reserve(3 * cap));
+  HIPC(c, M.surfel_over.reserve(std::max<size_t>(K, 1))); HIPC(c, M.surfel_ctl.reserve(8));
+  DBuf<CmapSpan> dspan;   // the pass's own, freed with it (hipFree waits for the launches that use them)
+  DBuf<double> dpose;
+  HIPC(c, dspan.reserve(spans.size())); HIPC(c, dpose.reserve(std::max<size_t>(16 * K, 16)));
+  HIPC(c, hipMemcpyAsync(dspan.p, spans.data(), sizeof(CmapSpan) * spans.size(), hipMemcpyHostToDevice, c->stream));
+  if (K) HIPC(c, hipMemcpyAsync(dpose.p, M.poses.data(), sizeof(double) * 16 * K, hipMemcpyHostToDevice, c->stream));
+  SurfelWork W;
+  memset(&W, 0, sizeof(W));
+  W.arena = P.arena.p;
+  W.span = dspan.p;
+  W.nspan = nspan;
+  W.nkf = (int)K;
+  W.n = n;
+  W.pose = dpose.p;
+  W.kf_over = M.surfel_over.p;
+  W.voxel = M.cfg.voxel;
+  for (int a = 0; a < 3; ++a) W.origin[a] = M.cfg.origin[a];
+  const VmapTable T = M.rows.table();
+  W.pmask = T.pmask; W.ptab = T.ptab; W.pkey = T.pkey;
+  W.nv = (long long)nv;
+  W.runs = getenv("TLOAM_SURFEL_NO_RUNS") ? 0 : 1;   // A/B of the wave's run aggregation, read per pass
+  W.min_points = M.surfel_cfg.min_points;
+  W.sums = M.surfel_sums.p;
+  W.normal = M.surfel_nrm.p;
+  W.eval = M.surfel_ev.p;
+  W.ctl = M.surfel_ctl.p;
+  I.launches = launch_surfels(W, c->stream);
+  HIPC(c, hipGetLastError());
+  unsigned long long ctl[8];
+  HIPC(c, hipMemcpyAsync(ctl, M.surfel_ctl.p, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  I.n_keyframes = (int64_t)K;
+  I.n_points = (int64_t)ctl[0];
+  I.orphan_points = (int64_t)ctl[1];
+  I.solved_voxels = (int64_t)ctl[2];
+  return TLOAM_OK;
+}
+
+// ids [first, first + count) of the built map with surfels: TLOAM_OK when the range is one
+int surfel_range(const tloam_ctx* c, size_t first, size_t count) {
+  if (!c || c->nranks > 1) return TLOAM_E_INVALID;
+  const CmapState& M = c->cmap;
+  if (!M.built || !M.surfeled) return TLOAM_E_NOT_READY;
+  const size_t nv = (size_t)M.info.n_voxels;
+  if (first > nv || count > nv - first) return TLOAM_E_INVALID;
+  return TLOAM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void tloam_closed_map_surfel_default_config(tloam_closed_map_surfel_config* cfg) {
+  if (!cfg) return;
+  memset(cfg, 0, sizeof(*cfg));
+  cfg->min_points = 5;
+}
+
+int tloam_closed_map_surfel_configure(tloam_ctx* c, const tloam_closed_map_surfel_config* cfg) {
+  if (!c || c->nranks > 1) return TLOAM_E_INVALID;
+  tloam_closed_map_surfel_config want;
+  if (cfg) want = *cfg;
+  else tloam_closed_map_surfel_default_config(&want);
+  if (want.min_points < 3) return TLOAM_E_INVALID;
+  c->cmap.drop_surfels();
+  c->cmap.surfel_cfg = want;
+  return TLOAM_OK;
+}
+
+int tloam_closed_map_get_surfel_info(tloam_ctx* c, tloam_closed_map_surfel_info* info) {
+  if (!c || !info || c->nranks > 1) return TLOAM_E_INVALID;
+  *info = c->cmap.surfel_info;
+  return TLOAM_OK;
+}
+
+int tloam_closed_map_surfels(tloam_ctx* c, tloam_closed_map_surfel_info* info) {
+  if (!c || c->nranks > 1) return TLOAM_E_INVALID;
+  CmapState& M = c->cmap;
+  if (!M.built) return TLOAM_E_NOT_READY;
+  M.drop_surfels();   // from here on a failure leaves no surfels
+  tloam_closed_map_surfel_info I;
+  memset(&I, 0, sizeof(I));
+  const int rc = surfel_body(c, I);
+  if (rc != TLOAM_OK) {
+    (void)hipStreamSynchronize(c->stream);   // (nothing of the pass is in flight when its span table goes)
+    return rc;
+  }
+  M.surfel_info = I;
+  M.surfeled = true;
+  if (info) *info = I;
+  return TLOAM_OK;
+}
+
+int tloam_closed_map_read_moments(tloam_ctx* c, size_t first, size_t count, int64_t* out) {
+  const int rc = surfel_range(c, first, count);
+  if (rc != TLOAM_OK || count == 0) return rc;
+  if (!out) return TLOAM_E_INVALID;
+  const CmapState& M = c->cmap;
+  HIPC(c, hipSetDevice(c->device));
+  HIPC(c, hipMemcpyAsync(out, M.surfel_sums.p + kSurfelSums * first, sizeof(int64_t) * kSurfelSums * count, hipMemcpyDeviceToHost,
+                         c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  return TLOAM_OK;
+}
+
+int tloam_closed_map_read_surfels(tloam_ctx* c, size_t first, size_t count, double* normals_aos, double* evals_aos, int64_t* counts) {
+  const int rc = surfel_range(c, first, count);
+  if (rc != TLOAM_OK || count == 0) return rc;
+  const CmapState& M = c->cmap;
+  const hipMemcpyKind D2H = hipMemcpyDeviceToHost;
+  HIPC(c, hipSetDevice(c->device));
+  if (normals_aos) HIPC(c, hipMemcpyAsync(normals_aos, M.surfel_nrm.p + 3 * first, sizeof(double) * 3 * count, D2H, c->stream));
+  if (evals_aos) HIPC(c, hipMemcpyAsync(evals_aos, M.surfel_ev.p + 3 * first, sizeof(double) * 3 * count, D2H, c->stream));
+  std::vector<int64_t> sums(counts ? kSurfelSums * count : 0);   // Ns is the first of a voxel's thirteen sums
+  if (counts)
+    HIPC(c, hipMemcpyAsync(sums.data(), M.surfel_sums.p + kSurfelSums * first, sizeof(int64_t) * sums.size(), D2H, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  if (counts)
+    for (size_t i = 0; i < count; ++i) counts[i] = sums[kSurfelSums * i];
+  return TLOAM_OK;
+}
+
+int tloam_closed_map_read_surfels_box(tloam_ctx* c, const double* lo, const double* hi, int64_t min_count, double max_sigma,
+                                      double min_planarity, size_t capacity, size_t* n, double* centroids_aos, double* normals_aos,
+                                      double* evals_aos, int64_t* counts) {
+  if (n) *n = 0;
+  if (!c || !n || (lo == nullptr) != (hi == nullptr) || c->nranks > 1) return TLOAM_E_INVALID;
+  CmapState& M = c->cmap;
+  if (!M.built || !M.surfeled) return TLOAM_E_NOT_READY;
+  const size_t nv = (size_t)M.info.n_voxels;
+  if (nv == 0) return TLOAM_OK;
+  HIPC(c, hipSetDevice(c->device));
+  HIPC(c, hipStreamSynchronize(c->stream));   // (the scratch may be replaced)
+  const size_t blocks = (nv + 255) / 256;
+  HIPC(c, M.rd_c.reserve(3 * nv)); HIPC(c, M.rd_n.reserve(nv)); HIPC(c, M.rd_nrm.reserve(3 * nv)); HIPC(c, M.rd_ev.reserve(3 * nv));
+  HIPC(c, M.look.reserve(blocks + 1)); HIPC(c, M.ctl.reserve(8));
+  HIPC(c, hipMemsetAsync(M.look.p, 0, sizeof(unsigned long long) * (blocks + 1), c->stream));
+  HIPC(c, hipMemsetAsync(M.ctl.p, 0, sizeof(unsigned long long) * 8, c->stream));
+  SurfelReadArgs A;
+  A.rows = voxel_rows_of(M, nv, "closed map").base;
+  A.rows.first = 0; A.rows.count = nv;
+  for (int a = 0; a < 3; ++a) { A.rows.lo[a] = lo ? lo[a] : 0.0; A.rows.hi[a] = hi ? hi[a] : 0.0; }
+  A.rows.min_count = min_count;
+  A.rows.out_c = M.rd_c.p; A.rows.out_n = M.rd_n.p;
+  A.rows.look = M.look.p; A.rows.ctl = M.ctl.p;
+  A.sums = M.surfel_sums.p;
+  A.normal = M.surfel_nrm.p;
+  A.eval = M.surfel_ev.p;
+  A.min_points = M.surfel_cfg.min_points;
+  A.boxed = lo ? 1 : 0;
+  A.max_sigma2 = max_sigma * max_sigma;
+  A.min_planarity = min_planarity;
+  A.out_nrm = M.rd_nrm.p; A.out_ev = M.rd_ev.p;
+  launch_surfel_read(A, c->stream);
+  HIPC(c, hipGetLastError());
+  unsigned long long w[3];
+  HIPC(c, hipMemcpyAsync(w, M.ctl.p, sizeof(w), hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  if (w[1]) {
+    c->last_error = "closed map: a look-back of k_surfel_box timed out";
+    return TLOAM_E_HIP;
+  }
+  const size_t m = (size_t)w[2];
+  *n = m;
+  if (m == 0) return TLOAM_OK;
+  if (capacity < m) return TLOAM_E_INVALID;
+  const hipMemcpyKind D2H = hipMemcpyDeviceToHost;
+  if (centroids_aos) HIPC(c, hipMemcpyAsync(centroids_aos, M.rd_c.p, sizeof(double) * 3 * m, D2H, c->stream));
+  if (normals_aos) HIPC(c, hipMemcpyAsync(normals_aos, M.rd_nrm.p, sizeof(double) * 3 * m, D2H, c->stream));
+  if (evals_aos) HIPC(c, hipMemcpyAsync(evals_aos, M.rd_ev.p, sizeof(double) * 3 * m, D2H, c->stream));
+  if (counts) HIPC(c, hipMemcpyAsync(counts, M.rd_n.p, sizeof(int64_t) * m, D2H, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  return TLOAM_OK;
+}
+
+}  // extern "C"

@@ -693,6 +693,46 @@ struct CarveReadArgs {
 };
 void launch_carve_read(const CarveReadArgs& A, hipStream_t s);
 
+// ---- the surfels of the closed map: per voxel the second moments of its points, and from them a normal and three variances
+// (tl_surfel.hip).  The points are the build's: a span table of the closed map's kind written for the
+// build's cloud mask, under the poses of the build.  The map is looked up through its own slot table and nothing in it is
+// written: the sums and the results are arrays of their own, in id order
+constexpr int kSurfelSums = 13;   // Ns, Rx Ry Rz, Sxx Sxy Sxz Syy Syz Szz, Wx Wy Wz
+struct SurfelWork {
+  const double* arena;
+  const CmapSpan* span;       // [nspan + 1], as CmapWork::span
+  int nspan;
+  int nkf;
+  long long n;                // the points of all spans
+  const double* pose;         // [nkf][16] column-major: the poses the closed map was built with
+  int* kf_over;               // [nkf] 1: a finite point of the keyframe left the grid (k_surfel_flag): it adds nothing
+  double voxel, origin[3];
+  // the closed map's table, read only
+  unsigned long long pmask;
+  const int* ptab;
+  const unsigned long long* pkey;
+  long long nv;               // its voxels
+  int runs;                   // 1: runs of equal voxels among a wave's consecutive lanes are summed before the atomics
+  int min_points;             // a voxel of fewer points is not solved
+  unsigned long long* sums;   // [nv][kSurfelSums] int64 (two's complement) in id order
+  double* normal;             // [nv][3]
+  double* eval;               // [nv][3] ascending, m^2
+  unsigned long long* ctl;    // [0] points summed, [1] orphan points, [2] solved voxels
+};
+// clear | flag | accum | solve: no host synchronisation; returns the launches it made (the same for every size)
+int launch_surfels(const SurfelWork& W, hipStream_t s);
+struct SurfelReadArgs {
+  VmapReadArgs rows;          // the closed map's rows, the box (when `boxed`), min_count, out_c, out_n (Ns), look and ctl as k_vmap_box's
+  const unsigned long long* sums;
+  const double *normal, *eval;
+  int min_points;
+  int boxed;                  // 0: the whole map
+  double max_sigma2;          // a voxel is kept when it is solved, ev2 > 0, ev0 <= max_sigma2 and ev1 - ev0 >= min_planarity * ev2
+  double min_planarity;
+  double *out_nrm, *out_ev;   // [3] per voxel kept (may be null)
+};
+void launch_surfel_read(const SurfelReadArgs& A, hipStream_t s);
+
 // ---- deskew of a scan under constant velocity (tl_deskew.hip) -------------
 struct DeskewArgs {
   const double* in;               // AoS xyz [3n]

@@ -2,7 +2,8 @@
 // lifetime, tl_api_frames.hip: HBM residency + search grids, tl_api_match.hip: the scanMatching driver, tl_api_comm.hip: multi-GPU
 // exchange, tl_api_submap.hip: device-resident submap, tl_api_feature.hip: PCA features, tl_api_seg.hip: segmentation,
 // tl_api_odom.hip: the whole odometry frame, tl_api_map.hip: its global map and registered scan, tl_api_vmap.hip: its merged
-// voxel map, tl_api_deskew.hip: its deskew, tl_api_place.hip: place recognition, tl_api_cmap.hip: the closed map, tl_api_carve.hip: its carve).
+// voxel map, tl_api_deskew.hip: its deskew, tl_api_place.hip: place recognition, tl_api_cmap.hip: the closed map, tl_api_carve.hip: its carve,
+// tl_api_surfel.hip: its surfels).
 // Memory: every buffer below belongs to the struct that declares it and dies with it (the owning types come first).
 #pragma once
 
@@ -449,11 +450,25 @@ struct CmapState {
     carved = false;
     carve_info = tloam_closed_map_carve_info{};
   }
-  void drop() {   // the closed map goes, and the carve's counts with it; the configurations and storage stay
+  // the surfels (tl_api_surfel.hip): their configuration, the thirteen sums, the normals and the variances
+  // in id order beside the rows (allocated by the first pass, for the rows' capacity), what the last pass reports, the box read's
+  // scratch.  They belong to the closed map they were gathered in and go with it; a carve does not touch them
+  tloam_closed_map_surfel_config surfel_cfg = {5, 0};   // tloam_closed_map_surfel_default_config until configured
+  DBuf<unsigned long long> surfel_sums, surfel_ctl;
+  DBuf<double> surfel_nrm, surfel_ev, rd_nrm, rd_ev;
+  DBuf<int> surfel_over;
+  bool surfeled = false;           // a surfel pass has succeeded since the last drop
+  tloam_closed_map_surfel_info surfel_info{};
+  void drop_surfels() {
+    surfeled = false;
+    surfel_info = tloam_closed_map_surfel_info{};
+  }
+  void drop() {   // the closed map goes, and the carve's counts and the surfels with it; the configurations and storage stay
     built = false;
     info = tloam_closed_map_info{};
     poses.clear();
     drop_carve();
+    drop_surfels();
   }
 };
 

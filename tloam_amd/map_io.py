@@ -1,5 +1,5 @@
-"""PCD export of the global map, of the merged voxel map (section 14) and of the carved closed map
-(section 21).
+"""PCD export of the global map, of the merged voxel map (section 14), of the carved closed map
+(section 21) and of the closed map's surfels (section 22).
 
 The reference declares a `saveMap` service (srv/saveMap.srv) and never serves it; this is the file a user of the map needs.
 PCD v0.7 (the Point Cloud Library's format), fields `x y z`, each `F 8` (float64), so the device's doubles are written and
@@ -144,4 +144,88 @@ def write_carved_closed_map_pcd(path: str, H, lo=None, hi=None, min_count=1, min
     closed_map_carve) as a file of write_voxel_pcd: centroids and counts N -> the voxels written."""
     cen, cnt, _ = H.closed_map_read_carved(lo, hi, min_count, min_miss, miss_ratio)
     write_voxel_pcd(path, cen, cnt, ascii=ascii)
+    return len(cnt)
+
+
+# ---- the closed map's surfels (DESIGN.md section 22): centroids, unit normals and the count of points behind each
+_SURFEL_FIELDS = ("x", "y", "z", "normal_x", "normal_y", "normal_z", "count")
+_SURFEL_DTYPE = np.dtype([(f, "<f8") for f in _SURFEL_FIELDS[:6]] + [("count", "<i8")])
+
+
+def write_surfel_pcd(path: str, centroids, normals, counts, ascii: bool = False) -> None:
+    """Writes (n, 3) centroids, (n, 3) normals and (n,) counts as PCD v0.7: x y z normal_x normal_y normal_z float64 (`F 8`),
+    count int64 (`I 8`)."""
+    c = np.asarray(centroids, dtype="<f8").reshape(-1, 3)
+    m = np.asarray(normals, dtype="<f8").reshape(-1, 3)
+    k = np.asarray(counts, dtype="<i8").reshape(-1)
+    if not len(c) == len(m) == len(k):
+        raise ValueError(f"{len(c)} centroids, {len(m)} normals, {len(k)} counts")
+    n = len(c)
+    rec = np.empty(n, _SURFEL_DTYPE)
+    for a in range(3):
+        rec[_SURFEL_FIELDS[a]], rec[_SURFEL_FIELDS[3 + a]] = c[:, a], m[:, a]
+    rec["count"] = k
+    header = ("# .PCD v0.7 - Point Cloud Data file format\n"
+              "VERSION 0.7\n"
+              f"FIELDS {' '.join(_SURFEL_FIELDS)}\n"
+              "SIZE 8 8 8 8 8 8 8\n"
+              "TYPE F F F F F F I\n"
+              "COUNT 1 1 1 1 1 1 1\n"
+              f"WIDTH {n}\n"
+              "HEIGHT 1\n"
+              "VIEWPOINT 0 0 0 1 0 0 0\n"
+              f"POINTS {n}\n"
+              f"DATA {'ascii' if ascii else 'binary'}\n")
+    with open(path, "wb") as fh:
+        fh.write(header.encode("ascii"))
+        if ascii:
+            fh.write("".join(" ".join(f"{v:.17g}" for v in (*p, *q)) + f" {int(j)}\n"
+                             for p, q, j in zip(c.tolist(), m.tolist(), k.tolist())).encode("ascii"))
+        else:
+            fh.write(rec.tobytes())
+
+
+def read_surfel_pcd(path: str):
+    """Reads a file of write_surfel_pcd (DATA ascii or binary) -> (centroids (n, 3), normals (n, 3) float64, counts (n,) int64)."""
+    with open(path, "rb") as fh:
+        raw = fh.read()
+    head, pos = {}, 0
+    while True:
+        end = raw.index(b"\n", pos)
+        line = raw[pos:end].decode("ascii").strip()
+        pos = end + 1
+        if not line or line.startswith("#"):
+            continue
+        key, _, val = line.partition(" ")
+        head[key.upper()] = val.split()
+        if key.upper() == "DATA":
+            break
+    if tuple(head.get("FIELDS", ())) != _SURFEL_FIELDS or head.get("SIZE") != ["8"] * 7 \
+            or head.get("TYPE") != ["F"] * 6 + ["I"] or head.get("COUNT", ["1"] * 7) != ["1"] * 7:
+        raise ValueError(f"{path}: only FIELDS {' '.join(_SURFEL_FIELDS)} with SIZE 8 / TYPE F F F F F F I / COUNT 1 are read")
+    n = int(head["POINTS"][0])
+    kind = head["DATA"][0]
+    if kind == "binary":
+        body = raw[pos: pos + 56 * n]
+        if len(body) != 56 * n:
+            raise ValueError(f"{path}: {len(body)} bytes of data for {n} surfels")
+        rec = np.frombuffer(body, dtype=_SURFEL_DTYPE)
+        cols = [rec[f].astype(np.float64) for f in _SURFEL_FIELDS[:6]]
+        return np.stack(cols[:3], axis=1), np.stack(cols[3:], axis=1), rec["count"].astype(np.int64)
+    if kind == "ascii":
+        rows = raw[pos:].split()
+        if len(rows) != 7 * n:
+            raise ValueError(f"{path}: {len(rows)} values for {n} surfels")
+        vals = np.array([rows[i::7] for i in range(6)], dtype=np.float64).T.reshape(n, 6)
+        return (np.ascontiguousarray(vals[:, :3]), np.ascontiguousarray(vals[:, 3:]),
+                np.array([int(v) for v in rows[6::7]], dtype=np.int64))
+    raise ValueError(f"{path}: DATA {kind} is not supported")
+
+
+def write_closed_map_surfel_pcd(path: str, H, lo=None, hi=None, min_count=1, max_sigma=float("inf"), min_planarity=0.05,
+                                ascii: bool = False) -> int:
+    """Writes what `H.closed_map_read_surfels_box` keeps (a HipRegistration after closed_map_build and closed_map_surfels) as a
+    file of write_surfel_pcd -> the surfels written."""
+    cen, nrm, _, cnt = H.closed_map_read_surfels_box(lo, hi, min_count, max_sigma, min_planarity)
+    write_surfel_pcd(path, cen, nrm, cnt, ascii=ascii)
     return len(cnt)

@@ -127,6 +127,19 @@ class ClosedMapCarveInfo(C.Structure):
     as_dict = _int_fields
 
 
+class ClosedMapSurfelConfig(C.Structure):
+    """tloam_closed_map_surfel_config: the fewest points a voxel is solved from."""
+    _fields_ = [("min_points", C.c_int32), ("reserved0", C.c_int32)]
+
+
+class ClosedMapSurfelInfo(C.Structure):
+    """tloam_closed_map_surfel_info."""
+    _fields_ = [("n_keyframes", C.c_int64), ("n_points", C.c_int64), ("orphan_points", C.c_int64), ("solved_voxels", C.c_int64),
+                ("launches", C.c_int32), ("reserved0", C.c_int32)]
+
+    as_dict = _int_fields
+
+
 class DeskewConfig(C.Structure):
     """tloam_deskew_config: the deskew's switch, its time source (0 azimuth, 1 per-point times), the sweep's direction (+1
     counter-clockwise seen from +z), the azimuth it starts at and the sweep fraction the pose describes."""
@@ -454,6 +467,14 @@ def load_library():
         "tloam_closed_map_read_misses": (C.c_int, [vp, sz, sz, C.POINTER(C.c_int64)]),
         "tloam_closed_map_read_carved": (C.c_int, [vp, dp, dp, C.c_int64, C.c_int64, C.c_double, sz, C.POINTER(sz), dp,
                                                    C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+        "tloam_closed_map_surfel_default_config": (None, [C.POINTER(ClosedMapSurfelConfig)]),
+        "tloam_closed_map_surfel_configure": (C.c_int, [vp, C.POINTER(ClosedMapSurfelConfig)]),
+        "tloam_closed_map_get_surfel_info": (C.c_int, [vp, C.POINTER(ClosedMapSurfelInfo)]),
+        "tloam_closed_map_surfels": (C.c_int, [vp, C.POINTER(ClosedMapSurfelInfo)]),
+        "tloam_closed_map_read_moments": (C.c_int, [vp, sz, sz, C.POINTER(C.c_int64)]),
+        "tloam_closed_map_read_surfels": (C.c_int, [vp, sz, sz, dp, dp, C.POINTER(C.c_int64)]),
+        "tloam_closed_map_read_surfels_box": (C.c_int, [vp, dp, dp, C.c_int64, C.c_double, C.c_double, sz, C.POINTER(sz), dp, dp, dp,
+                                                        C.POINTER(C.c_int64)]),
         "tloam_rccl_unique_id": (C.c_int, [vp]),
         "tloam_comm_init_rccl": (C.c_int, [vp, C.c_int, C.c_int, vp]),
         "tloam_comm_init_callback": (C.c_int, [vp, C.c_int, C.c_int, ALLREDUCE_FN, vp]),
@@ -496,6 +517,8 @@ EXPORTED_SYMBOLS = (
     "tloam_closed_map_get_info", "tloam_closed_map_build", "tloam_closed_map_read", "tloam_closed_map_read_box",
     "tloam_closed_map_read_poses", "tloam_closed_map_carve_default_config", "tloam_closed_map_carve_configure",
     "tloam_closed_map_get_carve_info", "tloam_closed_map_carve", "tloam_closed_map_read_misses", "tloam_closed_map_read_carved",
+    "tloam_closed_map_surfel_default_config", "tloam_closed_map_surfel_configure", "tloam_closed_map_get_surfel_info",
+    "tloam_closed_map_surfels", "tloam_closed_map_read_moments", "tloam_closed_map_read_surfels", "tloam_closed_map_read_surfels_box",
     "tloam_rccl_unique_id", "tloam_comm_init_rccl",
     "tloam_comm_mailbox_export", "tloam_comm_init_mailbox",
     "tloam_comm_init_callback", "tloam_shard_range", "tloam_shard_ranges_frame", "tloam_se3_exp", "tloam_se3_log", "tloam_se3_plus",
@@ -1235,6 +1258,67 @@ class HipRegistration:
                         "tloam_closed_map_read_carved")
         return cen[: n.value].copy(), cnt[: n.value].copy(), mis[: n.value].copy()
 
+    # ---- the surfels of the closed map: per voxel a normal and three variances
+    def closed_map_surfel_configure(self, cfg: ClosedMapSurfelConfig | None = None, **over):
+        """the surfels' configuration (default_closed_map_surfel_config(**over) when cfg is None); drops the surfels, not the
+        closed map or the carve's counts.  Kept across odometry_reset."""
+        cfg = cfg if cfg is not None else default_closed_map_surfel_config(**over)
+        self._check(self.L.tloam_closed_map_surfel_configure(self.h, C.byref(cfg)), "tloam_closed_map_surfel_configure")
+
+    def closed_map_surfels(self) -> dict:
+        """gathers, per voxel of the built closed map, the second moments of its points and solves them -> info dict"""
+        info = ClosedMapSurfelInfo()
+        self._check(self.L.tloam_closed_map_surfels(self.h, C.byref(info)), "tloam_closed_map_surfels")
+        return info.as_dict()
+
+    def closed_map_surfel_info(self) -> dict:
+        info = ClosedMapSurfelInfo()
+        self._check(self.L.tloam_closed_map_get_surfel_info(self.h, C.byref(info)), "tloam_closed_map_get_surfel_info")
+        return info.as_dict()
+
+    def closed_map_moments(self, first=0, count=None):
+        """the thirteen sums (Ns, R, S xx xy xz yy yz zz, W) of voxels [first, first + count) in id order, (m, 13) int64;
+        count None: to the end"""
+        if count is None:
+            count = max(self.closed_map_info()["n_voxels"] - int(first), 0)
+        m = int(count)
+        out = np.zeros((max(m, 1), 13), np.int64)
+        self._check(self.L.tloam_closed_map_read_moments(self.h, int(first), m, _lp(out)), "tloam_closed_map_read_moments")
+        return out[:m].copy()
+
+    def closed_map_read_surfels(self, first=0, count=None):
+        """voxels [first, first + count) in id order -> (normals (m, 3), variances ascending (m, 3) in m^2, Ns (m,) int64);
+        count None: to the end.  An unsolved voxel's normal and variances are zero"""
+        if count is None:
+            count = max(self.closed_map_info()["n_voxels"] - int(first), 0)
+        m = int(count)
+        nrm, ev, cnt = np.zeros((max(m, 1), 3)), np.zeros((max(m, 1), 3)), np.zeros(max(m, 1), np.int64)
+        self._check(self.L.tloam_closed_map_read_surfels(self.h, int(first), m, _dp(nrm), _dp(ev), _lp(cnt)),
+                    "tloam_closed_map_read_surfels")
+        return nrm[:m].copy(), ev[:m].copy(), cnt[:m].copy()
+
+    def closed_map_read_surfels_box(self, lo=None, hi=None, min_count=1, max_sigma=float("inf"), min_planarity=0.05):
+        """closed_map_read_box's voxels (lo and hi None: the whole map) whose surfel is solved with ev2 > 0,
+        ev0 <= max_sigma^2 and ev1 - ev0 >= min_planarity * ev2, in id order ->
+        (centroids (m, 3), normals (m, 3), variances (m, 3), Ns (m,))"""
+        if (lo is None) != (hi is None):
+            raise ValueError("lo and hi go together")
+        if lo is not None:
+            lo = np.ascontiguousarray(lo, dtype=np.float64).reshape(3)
+            hi = np.ascontiguousarray(hi, dtype=np.float64).reshape(3)
+        head = (self.h, _dp(lo), _dp(hi), int(min_count), float(max_sigma), float(min_planarity))
+        n = C.c_size_t(0)
+        rc = self.L.tloam_closed_map_read_surfels_box(*head, 0, C.byref(n), None, None, None, None)
+        if rc not in (0, -1) or (rc == -1 and n.value == 0):
+            self._check(rc, "tloam_closed_map_read_surfels_box")
+        m = n.value
+        cen, nrm, ev = np.zeros((max(m, 1), 3)), np.zeros((max(m, 1), 3)), np.zeros((max(m, 1), 3))
+        cnt = np.zeros(max(m, 1), np.int64)
+        if m:
+            self._check(self.L.tloam_closed_map_read_surfels_box(*head, m, C.byref(n), _dp(cen), _dp(nrm), _dp(ev), _lp(cnt)),
+                        "tloam_closed_map_read_surfels_box")
+        return cen[: n.value].copy(), nrm[: n.value].copy(), ev[: n.value].copy(), cnt[: n.value].copy()
+
     def fitness(self):
         f, r = C.c_double(0), C.c_double(0)
         rc = self.L.tloam_fitness(self.h, C.byref(f), C.byref(r))
@@ -1488,6 +1572,11 @@ def default_closed_map_carve_config(**over) -> ClosedMapCarveConfig:
     """tloam_closed_map_carve_default_config (max_range 60, end_margin 1, radius 0.25, ray_mask 0: the build's) with keyword
     overrides, e.g. max_range=20.0, radius=float("inf")"""
     return _strict_config(ClosedMapCarveConfig, "tloam_closed_map_carve_default_config", over)
+
+
+def default_closed_map_surfel_config(**over) -> ClosedMapSurfelConfig:
+    """tloam_closed_map_surfel_default_config (min_points 5) with keyword overrides."""
+    return _strict_config(ClosedMapSurfelConfig, "tloam_closed_map_surfel_default_config", over)
 
 
 def default_submap_config(**over) -> SubmapConfig:
