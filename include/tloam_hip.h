@@ -1013,6 +1013,73 @@ int tloam_closed_map_read_surfels_box(tloam_ctx* ctx, const double* lo_or_null, 
                                       double* normals_aos, double* evals_aos, int64_t* counts);
 /* Every surfel call on a context with nranks > 1: TLOAM_E_INVALID. */
 
+/* ---- localisation of a scan in the closed map: point-to-plane Gauss-Newton on the surfels (additive to ABI 8) ------
+ * The closed map with surfels is a localisation target: a voxel whose surfel passes the gate of
+ * tloam_closed_map_read_surfels_box (solved, ev2 > 0, ev0 <= max_sigma^2, ev1 - ev0 >= min_planarity * ev2) is a plane through
+ * the voxel's centroid c with the surfel's normal n.  Runs only when called; nothing of the closed map, of a carve's counts, of
+ * the surfels or of the context's odometry is changed.
+ * Per point p of the scan (sensor frame) and pose matrix M: E = M p (rows accumulated left to right, as the closed map's build);
+ * a point that is not finite there is left out; its cell i by the closed map's quantisation, a point with |i| >= 2^20 on an
+ * axis is unmatched; of the 27 cells i + (dx, dy, dz) -- dz outermost, dx innermost, each from -1 to 1 -- the eligible voxel
+ * with the smallest D = |E - c|^2 under a strict < (the first visited wins a tie); r = n . (E - c); the point is used when it
+ * is matched and |r| <= tau.  Over the used points with unit weights J = [n, E x n], H = sum J^T J, g = sum J^T r,
+ * cost = sum r^2 / 2.  The sums are formed without floating-point atomics, in an order fixed by the point index alone: two
+ * calls, and two contexts, return the same bits.
+ * Iteration k = 0 ..: the state is a unit quaternion and a translation, M = its matrix; tau_k = max(min_residual,
+ * max_residual0 * shrink^k); H d = -g by a 6 x 6 Cholesky; the state becomes exp(d) * state (d = (translation, rotation), the
+ * convention of tloam_se3_exp); converged when |d[0:3]| < step_tol_t and |d[3:6]| < step_tol_r.  An iteration is degenerate when
+ * used < min_matches, a sum is not finite, or a Cholesky pivot is not > min_pivot_ratio * H_kk: the call then ends with status
+ * DEGENERATE and pose_out = prior, bit for bit.  DESIGN.md 23 states the arithmetic. */
+typedef struct tloam_closed_map_localise_config {
+  double max_residual0;     /* 1.0: tau of iteration 0 (m); > 0 */
+  double shrink;            /* 0.7: tau's factor per iteration; in (0, 1] */
+  double min_residual;      /* 0.1: tau's floor (m); >= 0 */
+  double max_sigma;         /* +inf: the gate's largest sqrt(ev0) (m); >= 0 */
+  double min_planarity;     /* 0.05: the gate's smallest (ev1 - ev0) / ev2; finite */
+  double step_tol_t;        /* 1e-6 (m); >= 0 */
+  double step_tol_r;        /* 1e-7 (rad); >= 0 */
+  double min_pivot_ratio;   /* 1e-9; in [0, 1) */
+  int32_t max_iterations;   /* 20; 1 .. 64 */
+  int32_t min_matches;      /* 50; >= 1 */
+} tloam_closed_map_localise_config;
+void tloam_closed_map_localise_default_config(tloam_closed_map_localise_config* cfg);
+/* cfg NULL: the defaults.  A value out of its range (NaN too): TLOAM_E_INVALID, and the old configuration stays.  Persists across
+ * tloam_odometry_reset.  Changes nothing of the closed map, the carve or the surfels. */
+int tloam_closed_map_localise_configure(tloam_ctx* ctx, const tloam_closed_map_localise_config* cfg);
+enum { TLOAM_LOCALISE_CONVERGED = 0, TLOAM_LOCALISE_MAX_ITERATIONS = 1, TLOAM_LOCALISE_DEGENERATE = 2 };
+typedef struct tloam_closed_map_localise_info {
+  int32_t status;       /* TLOAM_LOCALISE_* */
+  int32_t iterations;   /* executed, the degenerate one included */
+  int64_t matched;      /* of the last executed sweep */
+  int64_t used;
+  double rms;           /* sqrt(2 cost / used) of the last executed sweep (0 when used == 0) */
+  int32_t launches;     /* sweep and step launches of the call: 2 max_iterations, the same for every input */
+  int32_t prepared;     /* 1: the call rebuilt the cached voxel records (one more launch) */
+} tloam_closed_map_localise_info;
+typedef struct tloam_closed_map_localise_record {   /* one executed iteration */
+  double pose_colmajor[16];   /* the pose the sweep ran at (before the step) */
+  double tau;
+  double cost;
+  double d[6];                /* the step (translation, rotation); zero for the degenerate iteration */
+  int64_t matched;
+  int64_t used;
+} tloam_closed_map_localise_record;
+/* Localises points_aos (n points, sensor frame) from `prior` (column-major, a rigid transform).  TLOAM_E_NOT_READY without a
+ * built closed map with surfels; TLOAM_E_INVALID for n == 0, a NULL argument or a prior that is not a rigid transform; a refused
+ * call leaves everything as it was.  One wait: the scan is uploaded and max_iterations pairs of launches are enqueued; a pair
+ * behind the last executed iteration returns on entry.  info may be NULL. */
+int tloam_closed_map_localise(tloam_ctx* ctx, const double* points_aos, size_t n, const double* prior_colmajor,
+                              double* pose_out_colmajor, tloam_closed_map_localise_info* info_or_null);
+/* The executed iterations of the last tloam_closed_map_localise on this context; *n is set to their number even when capacity
+ * is too small (then nothing is copied and TLOAM_E_INVALID is returned).  records may be NULL to ask for the size. */
+int tloam_closed_map_localise_log(tloam_ctx* ctx, size_t capacity, size_t* n, tloam_closed_map_localise_record* records);
+/* One sweep at the given matrix (a rigid transform, used as it stands) and tau (>= 0, +inf allowed), no step: per point the
+ * matched voxel's id (-1: none) and r (0 where unmatched), either NULL; out28 = H's upper triangle by rows (21), g (6), cost;
+ * counts2 = matched, used.  Errors as tloam_closed_map_localise. */
+int tloam_closed_map_linearise(tloam_ctx* ctx, const double* points_aos, size_t n, const double* pose_colmajor, double tau,
+                               int32_t* ids_or_null, double* residuals_or_null, double* out28, int64_t* counts2);
+/* Every localisation call on a context with nranks > 1: TLOAM_E_INVALID. */
+
 /* ---- multi-GPU: correspondence set sharded over ranks, one all-reduce per sweep --------
  * (nothing in the reference).  Call before set_source / set_correspondences.
  * (a) native RCCL over xGMI: unique_id = the 128 bytes of an ncclUniqueId made on rank 0

@@ -733,6 +733,74 @@ struct SurfelReadArgs {
 };
 void launch_surfel_read(const SurfelReadArgs& A, hipStream_t s);
 
+// ---- localisation of a scan in the closed map: point-to-plane Gauss-Newton on the surfels (tl_localise.hip, DESIGN.md
+// section 23).  The map is looked up through its own slot table and nothing of it, of the carve or of the surfels is written
+struct LocRecord {            // what a probe hit reads of a voxel: one 64-byte line
+  double c[3];                // the row centroid
+  double n[3];                // the surfel's normal
+  int eligible;               // the surfel passes the gate
+  int pad[3];
+};
+static_assert(sizeof(LocRecord) == 64, "a voxel record is one cache line");
+constexpr int kLocTerms = 28;       // H's upper triangle by rows (21), g (6), cost
+constexpr int kLocRow = 32;         // a block's partial row: the terms, matched, used (as doubles: exact below 2^53), two unused
+constexpr int kLocMaxIterations = 64;
+struct LocLog {               // tloam_closed_map_localise_record
+  double pose[16];
+  double tau, cost;
+  double d[6];
+  long long matched, used;
+};
+struct LocState {             // the stage's words in HBM: written by the host before a call, by k_loc_step during it
+  double M[16];               // the matrix the next sweep runs at
+  double tau;                 // ... and its truncation
+  double pw;                  // max_residual0 * shrink^k
+  Pose T;                     // the state
+  double sums[kLocRow];       // of the last executed sweep
+  int done;                   // the call has ended: the launches behind return on entry
+  int status;
+  int iterations;
+  int reserved0;
+};
+struct LocPrepArgs {
+  const unsigned long long* pkey;
+  const long long *pn, *pqx, *pqy, *pqz;
+  const unsigned long long* sums;   // the surfels' thirteen per voxel
+  const double *normal, *eval;
+  long long nv;
+  double voxel, origin[3];
+  int min_points;
+  double max_sigma2, min_planarity;
+  LocRecord* rec;
+};
+struct LocSweepArgs {
+  const double* pts;          // the scan, AoS
+  long long n;
+  LocState* st;
+  double voxel, origin[3];
+  unsigned long long pmask;   // the closed map's table, read only
+  const int* ptab;
+  const unsigned long long* pkey;
+  long long nv;
+  const LocRecord* rec;
+  double* partial;            // [blocks][kLocRow]
+  int* ids;                   // [n] or null
+  double* res;                // [n] or null
+};
+struct LocStepArgs {
+  LocState* st;
+  const double* partial;
+  int nblocks;
+  int k;                      // the iteration; -1: sum only (tloam_closed_map_linearise)
+  int max_iterations, min_matches;
+  double shrink, min_residual, step_tol_t, step_tol_r, min_pivot_ratio;
+  LocLog* log;                // [max_iterations]
+};
+inline int loc_blocks(long long n) { return (int)((n + 255) / 256); }
+void launch_loc_prepare(const LocPrepArgs& A, hipStream_t s);
+void launch_loc_sweep(const LocSweepArgs& A, hipStream_t s);
+void launch_loc_step(const LocStepArgs& A, hipStream_t s);
+
 // ---- deskew of a scan under constant velocity (tl_deskew.hip) -------------
 struct DeskewArgs {
   const double* in;               // AoS xyz [3n]

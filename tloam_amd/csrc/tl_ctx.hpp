@@ -459,9 +459,25 @@ struct CmapState {
   DBuf<int> surfel_over;
   bool surfeled = false;           // a surfel pass has succeeded since the last drop
   tloam_closed_map_surfel_info surfel_info{};
+  // the localisation (tl_api_localise.hip): its configuration, the voxel records {c, n, eligible} cached
+  // beside the rows (allocated by the first call, for the rows' capacity; rebuilt when the surfels or the gate change), the
+  // uploaded scan, the blocks' partial rows, the per-point outputs of a linearise, the state words and the log of the last call
+  tloam_closed_map_localise_config loc_cfg = {1.0, 0.7, 0.1, HUGE_VAL, 0.05, 1e-6, 1e-7, 1e-9, 20, 50};   // _localise_default_config
+  DBuf<tl::LocRecord> loc_rec;
+  DBuf<double> loc_pts, loc_partial, loc_res;
+  DBuf<int> loc_ids;
+  DBuf<tl::LocState> loc_state;
+  DBuf<tl::LocLog> loc_log;
+  bool loc_ready = false;          // the records are those of the surfels and the gate at hand
+  std::vector<tloam_closed_map_localise_record> loc_records;   // of the last localise call
+  void drop_localise() {
+    loc_ready = false;
+    loc_records.clear();
+  }
   void drop_surfels() {
     surfeled = false;
     surfel_info = tloam_closed_map_surfel_info{};
+    drop_localise();
   }
   void drop() {   // the closed map goes, and the carve's counts and the surfels with it; the configurations and storage stay
     built = false;

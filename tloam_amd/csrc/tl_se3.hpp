@@ -213,7 +213,7 @@ inline bool pose_from_matrix(const double M[16], Pose* out) {
   return true;
 }
 
-inline void pose_to_matrix(const Pose& T, double M[16]) {
+TL_HD void pose_to_matrix(const Pose& T, double M[16]) {
   double R[9];
   rotation_matrix(T, R);
   for (int c = 0; c < 3; ++c)

@@ -140,6 +140,38 @@ class ClosedMapSurfelInfo(C.Structure):
     as_dict = _int_fields
 
 
+class ClosedMapLocaliseConfig(C.Structure):
+    """tloam_closed_map_localise_config: the truncation's schedule (max_residual0 * shrink^k, floored at min_residual), the
+    gate on the surfels (max_sigma, min_planarity), the step tolerances, the Cholesky's pivot ratio, the iteration limit and the
+    fewest used points."""
+    _fields_ = [("max_residual0", C.c_double), ("shrink", C.c_double), ("min_residual", C.c_double), ("max_sigma", C.c_double),
+                ("min_planarity", C.c_double), ("step_tol_t", C.c_double), ("step_tol_r", C.c_double),
+                ("min_pivot_ratio", C.c_double), ("max_iterations", C.c_int32), ("min_matches", C.c_int32)]
+
+
+class ClosedMapLocaliseInfo(C.Structure):
+    """tloam_closed_map_localise_info."""
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("matched", C.c_int64), ("used", C.c_int64), ("rms", C.c_double),
+                ("launches", C.c_int32), ("prepared", C.c_int32)]
+
+    def as_dict(self):
+        return {"status": int(self.status), "iterations": int(self.iterations), "matched": int(self.matched),
+                "used": int(self.used), "rms": float(self.rms), "launches": int(self.launches), "prepared": int(self.prepared)}
+
+
+class ClosedMapLocaliseRecord(C.Structure):
+    """tloam_closed_map_localise_record: one executed iteration."""
+    _fields_ = [("pose_colmajor", C.c_double * 16), ("tau", C.c_double), ("cost", C.c_double), ("d", C.c_double * 6),
+                ("matched", C.c_int64), ("used", C.c_int64)]
+
+    def as_dict(self):
+        return {"pose": np.array(self.pose_colmajor[:]).reshape(4, 4).T.copy(), "tau": float(self.tau), "cost": float(self.cost),
+                "d": np.array(self.d[:]), "matched": int(self.matched), "used": int(self.used)}
+
+
+LOCALISE_CONVERGED, LOCALISE_MAX_ITERATIONS, LOCALISE_DEGENERATE = 0, 1, 2
+
+
 class DeskewConfig(C.Structure):
     """tloam_deskew_config: the deskew's switch, its time source (0 azimuth, 1 per-point times), the sweep's direction (+1
     counter-clockwise seen from +z), the azimuth it starts at and the sweep fraction the pose describes."""
@@ -471,6 +503,11 @@ def load_library():
         "tloam_closed_map_surfel_configure": (C.c_int, [vp, C.POINTER(ClosedMapSurfelConfig)]),
         "tloam_closed_map_get_surfel_info": (C.c_int, [vp, C.POINTER(ClosedMapSurfelInfo)]),
         "tloam_closed_map_surfels": (C.c_int, [vp, C.POINTER(ClosedMapSurfelInfo)]),
+        "tloam_closed_map_localise_default_config": (None, [C.POINTER(ClosedMapLocaliseConfig)]),
+        "tloam_closed_map_localise_configure": (C.c_int, [vp, C.POINTER(ClosedMapLocaliseConfig)]),
+        "tloam_closed_map_localise": (C.c_int, [vp, dp, sz, dp, dp, C.POINTER(ClosedMapLocaliseInfo)]),
+        "tloam_closed_map_localise_log": (C.c_int, [vp, sz, C.POINTER(sz), C.POINTER(ClosedMapLocaliseRecord)]),
+        "tloam_closed_map_linearise": (C.c_int, [vp, dp, sz, dp, C.c_double, C.POINTER(C.c_int32), dp, dp, C.POINTER(C.c_int64)]),
         "tloam_closed_map_read_moments": (C.c_int, [vp, sz, sz, C.POINTER(C.c_int64)]),
         "tloam_closed_map_read_surfels": (C.c_int, [vp, sz, sz, dp, dp, C.POINTER(C.c_int64)]),
         "tloam_closed_map_read_surfels_box": (C.c_int, [vp, dp, dp, C.c_int64, C.c_double, C.c_double, sz, C.POINTER(sz), dp, dp, dp,
@@ -519,6 +556,8 @@ EXPORTED_SYMBOLS = (
     "tloam_closed_map_get_carve_info", "tloam_closed_map_carve", "tloam_closed_map_read_misses", "tloam_closed_map_read_carved",
     "tloam_closed_map_surfel_default_config", "tloam_closed_map_surfel_configure", "tloam_closed_map_get_surfel_info",
     "tloam_closed_map_surfels", "tloam_closed_map_read_moments", "tloam_closed_map_read_surfels", "tloam_closed_map_read_surfels_box",
+    "tloam_closed_map_localise_default_config", "tloam_closed_map_localise_configure", "tloam_closed_map_localise",
+    "tloam_closed_map_localise_log", "tloam_closed_map_linearise",
     "tloam_rccl_unique_id", "tloam_comm_init_rccl",
     "tloam_comm_mailbox_export", "tloam_comm_init_mailbox",
     "tloam_comm_init_callback", "tloam_shard_range", "tloam_shard_ranges_frame", "tloam_se3_exp", "tloam_se3_log", "tloam_se3_plus",
@@ -1319,6 +1358,44 @@ class HipRegistration:
                         "tloam_closed_map_read_surfels_box")
         return cen[: n.value].copy(), nrm[: n.value].copy(), ev[: n.value].copy(), cnt[: n.value].copy()
 
+    # ---- localisation of a scan in the closed map: point-to-plane Gauss-Newton on the surfels
+    def closed_map_localise_configure(self, cfg: ClosedMapLocaliseConfig | None = None, **over):
+        """the localisation's configuration (default_closed_map_localise_config(**over) when cfg is None).  Kept across
+        odometry_reset; a refused configuration leaves the old one."""
+        cfg = cfg if cfg is not None else default_closed_map_localise_config(**over)
+        self._check(self.L.tloam_closed_map_localise_configure(self.h, C.byref(cfg)), "tloam_closed_map_localise_configure")
+
+    def closed_map_localise(self, points, prior):
+        """the scan `points` (n, 3; sensor frame) registered against the closed map's surfels from the pose `prior` (4 x 4)
+        -> (pose (4, 4), info dict).  A DEGENERATE status returns the prior"""
+        pts = _aos(points)
+        pr, out = _colmajor(prior), np.zeros(16)
+        info = ClosedMapLocaliseInfo()
+        self._check(self.L.tloam_closed_map_localise(self.h, _dp(pts), len(pts), _dp(pr), _dp(out), C.byref(info)),
+                    "tloam_closed_map_localise")
+        return out.reshape(4, 4).T.copy(), info.as_dict()
+
+    def closed_map_localise_log(self) -> list:
+        """the executed iterations of the last closed_map_localise: dicts of pose (before the step), tau, cost, d, matched, used"""
+        n = C.c_size_t(0)
+        self._check(self.L.tloam_closed_map_localise_log(self.h, 0, C.byref(n), None), "tloam_closed_map_localise_log")
+        if not n.value:
+            return []
+        rec = (ClosedMapLocaliseRecord * n.value)()
+        self._check(self.L.tloam_closed_map_localise_log(self.h, n.value, C.byref(n), rec), "tloam_closed_map_localise_log")
+        return [r.as_dict() for r in rec[: n.value]]
+
+    def closed_map_linearise(self, points, pose, tau) -> dict:
+        """one sweep at `pose` (4 x 4) with truncation `tau`, no step -> dict(ids (n,) int32, -1 unmatched; residuals (n,);
+        H (21,) upper triangle by rows; g (6,); cost; matched; used)"""
+        pts = _aos(points)
+        ids, res = np.zeros(max(len(pts), 1), np.int32), np.zeros(max(len(pts), 1))
+        out, cnt = np.zeros(28), np.zeros(2, np.int64)
+        self._check(self.L.tloam_closed_map_linearise(self.h, _dp(pts), len(pts), _dp(_colmajor(pose)), float(tau), _ip(ids),
+                                                      _dp(res), _dp(out), _lp(cnt)), "tloam_closed_map_linearise")
+        return {"ids": ids[: len(pts)].copy(), "residuals": res[: len(pts)].copy(), "H": out[:21].copy(), "g": out[21:27].copy(),
+                "cost": float(out[27]), "matched": int(cnt[0]), "used": int(cnt[1])}
+
     def fitness(self):
         f, r = C.c_double(0), C.c_double(0)
         rc = self.L.tloam_fitness(self.h, C.byref(f), C.byref(r))
@@ -1572,6 +1649,11 @@ def default_closed_map_carve_config(**over) -> ClosedMapCarveConfig:
     """tloam_closed_map_carve_default_config (max_range 60, end_margin 1, radius 0.25, ray_mask 0: the build's) with keyword
     overrides, e.g. max_range=20.0, radius=float("inf")"""
     return _strict_config(ClosedMapCarveConfig, "tloam_closed_map_carve_default_config", over)
+
+
+def default_closed_map_localise_config(**over) -> ClosedMapLocaliseConfig:
+    """tloam_closed_map_localise_default_config with keyword overrides."""
+    return _strict_config(ClosedMapLocaliseConfig, "tloam_closed_map_localise_default_config", over)
 
 
 def default_closed_map_surfel_config(**over) -> ClosedMapSurfelConfig:
