@@ -1080,6 +1080,90 @@ int tloam_closed_map_linearise(tloam_ctx* ctx, const double* points_aos, size_t 
                                int32_t* ids_or_null, double* residuals_or_null, double* out28, int64_t* counts2);
 /* Every localisation call on a context with nranks > 1: TLOAM_E_INVALID. */
 
+/* ---- several hypotheses of one scan, and relocalisation without a prior (additive to ABI 8) -----------
+ * tloam_closed_map_localise_batch localises ONE scan from B priors (B in 1 .. 32) in one set of launches: one upload of the
+ * scan, the voxel records rebuilt when stale, max_iterations pairs of launches for all hypotheses together (the hypothesis is a
+ * grid dimension of the sweep and a workgroup of the step), one wait.  Hypothesis h returns the pose, the info and the log of
+ * tloam_closed_map_localise called alone with priors[h], bit for bit: both forms run one device body, and a hypothesis's sums
+ * are formed in the single call's order -- lane, wave, block by point index -- whatever B is.  A hypothesis that has ended
+ * leaves its launches on entry; infos[h].launches is 2 max_iterations for every h and every input.
+ * *best_out: among the hypotheses whose status is not DEGENERATE the largest `used`; on a tie the smaller cost (sum r^2 / 2 of
+ * the last executed sweep); then the lower index; -1 when every hypothesis is degenerate (every poses_out[h] is then its prior,
+ * bit for bit).
+ * Errors as tloam_closed_map_localise, checked over all B priors before anything is touched; B == 0 or B > 32:
+ * TLOAM_E_INVALID.  A refused call leaves the last single call's log and the last batch's logs as they were.  Memory is
+ * grow-only: B * ceil(n / 256) * 256 bytes of partial sums, B blocks of state words, B * 64 log records. */
+int tloam_closed_map_localise_batch(tloam_ctx* ctx, const double* points_aos, size_t n, const double* priors_colmajor /*[16 B]*/,
+                                    size_t B, double* poses_out_colmajor /*[16 B]*/,
+                                    tloam_closed_map_localise_info* infos /*[B]*/, int32_t* best_out);
+/* The executed iterations of hypothesis `hypothesis` of the last tloam_closed_map_localise_batch (or of the last
+ * tloam_closed_map_relocalise, which runs on the same storage) on this context; capacity convention of
+ * tloam_closed_map_localise_log.  TLOAM_E_INVALID for a hypothesis the last batch did not have. */
+int tloam_closed_map_localise_batch_log(tloam_ctx* ctx, size_t hypothesis, size_t capacity, size_t* n,
+                                        tloam_closed_map_localise_record* records);
+
+/* tloam_closed_map_relocalise: scan in, pose out, no prior, one wait.  Needs place recognition enabled (the keyframe database)
+ * and a built closed map with surfels.
+ * 1. The scan's descriptor and ring key are those of tloam_place_describe under the context's place configuration.
+ * 2. The candidates are keyframes 0 .. K-1 of the closed map's last build (tloam_closed_map_info.n_keyframes; no
+ *    exclude_recent): the min(num_candidates, K) nearest in ring key, ties to the lower keyframe, each with its best column
+ *    shift and distance d by the rules and the arithmetic of the loop search.  The query is not added to the database, and no
+ *    loop record is written.
+ * 3. Hypothesis h: yaw_h as tloam_place_loop.yaw; prior_h = P_build[keyframe_h] * Rz(yaw_h), P_build the pose the build used
+ *    (tloam_closed_map_read_poses) -- the candidate's column j + shift matches the query's column j, so the query's heading
+ *    is the keyframe's plus yaw.  Formed on the device.  A candidate whose d is not < max_dist is `skipped`: never swept, its
+ *    pose is its prior, its localise info is zero but for status = DEGENERATE, launches and prepared.
+ * 4. All hypotheses go through the batched localiser under the context's localise configuration: hypothesis h has the bits of
+ *    tloam_closed_map_localise_batch called with the priors reported.
+ * 5. The pick is the batch's rule over the hypotheses not skipped.  FOUND when the winner has
+ *    used >= min_used_ratio * (finite points of the scan) and rms <= max_rms; else NOT_FOUND: pose_out is not written, best = -1
+ *    and the best's fields of the info are zero (keyframe -1).
+ * The defaults are choices, not measurements.  info.launches: the two of the description, the two of the search, the priors and
+ * 2 max_iterations -- the same for every input (the records' rebuild, when `prepared`, is one more). */
+typedef struct tloam_closed_map_relocalise_config {
+  int32_t num_candidates;   /* 8; 1 .. 32: keyframes localised from */
+  int32_t reserved0;
+  double max_dist;          /* +inf: a candidate whose Scan Context d is not < max_dist is not localised from; > 0 */
+  double min_used_ratio;    /* 0.5: accepted when used >= min_used_ratio * (finite points of the scan); in [0, 1] */
+  double max_rms;           /* +inf (m); > 0 */
+} tloam_closed_map_relocalise_config;
+enum { TLOAM_RELOCALISE_FOUND = 0, TLOAM_RELOCALISE_NOT_FOUND = 1 };
+typedef struct tloam_closed_map_relocalise_info {
+  int32_t status;           /* TLOAM_RELOCALISE_* */
+  int32_t n_hypotheses;     /* min(num_candidates, K) */
+  int32_t best;             /* index into the hypotheses; -1: none */
+  int32_t launches;
+  int64_t keyframe;         /* of the best, as are the fields below */
+  int32_t shift;
+  int32_t reserved0;
+  double dist;
+  double yaw;
+  tloam_closed_map_localise_info localise;
+} tloam_closed_map_relocalise_info;
+typedef struct tloam_closed_map_relocalise_hypothesis {
+  int64_t keyframe;
+  int32_t shift;
+  int32_t skipped;
+  double dist;
+  double yaw;
+  double prior_colmajor[16];
+  double pose_colmajor[16];
+  tloam_closed_map_localise_info localise;
+} tloam_closed_map_relocalise_hypothesis;
+void tloam_closed_map_relocalise_default_config(tloam_closed_map_relocalise_config* cfg);
+/* cfg NULL: the defaults.  A value out of its range (NaN too): TLOAM_E_INVALID, and the old configuration stays.  Persists across
+ * tloam_odometry_reset. */
+int tloam_closed_map_relocalise_configure(tloam_ctx* ctx, const tloam_closed_map_relocalise_config* cfg);
+/* TLOAM_E_NOT_READY when place recognition is not enabled or there is no built closed map with surfels; TLOAM_E_INVALID for
+ * n == 0, a NULL points or pose_out, or nranks > 1.  A refused call leaves everything as it was.  The keyframe database -- its
+ * count, keys, descriptors and loop records -- the closed map and its surfels are only read.  info may be NULL. */
+int tloam_closed_map_relocalise(tloam_ctx* ctx, const double* points_aos, size_t n, double* pose_out_colmajor,
+                                tloam_closed_map_relocalise_info* info_or_null);
+/* The hypotheses of the last tloam_closed_map_relocalise, in candidate order; capacity convention of
+ * tloam_closed_map_localise_log. */
+int tloam_closed_map_relocalise_hypotheses(tloam_ctx* ctx, size_t capacity, size_t* n,
+                                           tloam_closed_map_relocalise_hypothesis* hypotheses);
+
 /* ---- multi-GPU: correspondence set sharded over ranks, one all-reduce per sweep --------
  * (nothing in the reference).  Call before set_source / set_correspondences.
  * (a) native RCCL over xGMI: unique_id = the 128 bytes of an ncclUniqueId made on rank 0

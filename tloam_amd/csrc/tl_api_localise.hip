@@ -32,14 +32,15 @@ int loc_check(const tloam_ctx* c, const double* points_aos, size_t n, const doub
   return TLOAM_OK;
 }
 
-// the buffers sized, the scan uploaded and the records rebuilt when stale (*prepared); ids, res: a linearise's per-point outputs are asked for
-int loc_begin(tloam_ctx* c, const double* points_aos, size_t n, bool ids, bool res, int* prepared) {
+// the buffers sized (for B hypotheses), the scan uploaded and the records rebuilt when stale (*prepared); ids, res: a linearise's
+// per-point outputs are asked for
+int loc_begin(tloam_ctx* c, const double* points_aos, size_t n, bool ids, bool res, int* prepared, size_t B = 1) {
   CmapState& M = c->cmap;
   const size_t nv = (size_t)M.info.n_voxels, cap = std::max<size_t>(M.rows.cap, 1);
   HIPC(c, hipSetDevice(c->device));
   HIPC(c, M.loc_rec.reserve(cap)); HIPC(c, M.loc_pts.reserve(3 * n));
-  HIPC(c, M.loc_partial.reserve((size_t)loc_blocks((long long)n) * kLocRow));
-  HIPC(c, M.loc_state.reserve(1)); HIPC(c, M.loc_log.reserve(kLocMaxIterations));
+  HIPC(c, M.loc_partial.reserve(B * (size_t)loc_blocks((long long)n) * kLocRow));
+  HIPC(c, M.loc_state.reserve(B)); HIPC(c, M.loc_log.reserve(B * kLocMaxIterations));
   if (ids) HIPC(c, M.loc_ids.reserve(n));
   if (res) HIPC(c, M.loc_res.reserve(n));
   HIPC(c, hipMemcpyAsync(M.loc_pts.p, points_aos, sizeof(double) * 3 * n, hipMemcpyHostToDevice, c->stream));
@@ -103,17 +104,22 @@ int loc_failed(tloam_ctx* c, int rc) {
   return rc;
 }
 
-int localise_body(tloam_ctx* c, const double* points_aos, size_t n, const Pose& T0, LocState* st, tloam_closed_map_localise_info* I) {
-  CmapState& M = c->cmap;
-  const tloam_closed_map_localise_config& g = M.loc_cfg;
-  int rc = loc_begin(c, points_aos, n, false, false, &I->prepared);
-  if (rc != TLOAM_OK) return rc;
+// the state words a localisation starts from
+void loc_state0(const tloam_closed_map_localise_config& g, const Pose& T0, LocState* st) {
   memset(st, 0, sizeof(*st));
   st->T = T0;
   pose_to_matrix(T0, st->M);
   st->pw = g.max_residual0;
   st->tau = fmax(g.min_residual, st->pw);
   st->status = TLOAM_LOCALISE_MAX_ITERATIONS;
+}
+
+int localise_body(tloam_ctx* c, const double* points_aos, size_t n, const Pose& T0, LocState* st, tloam_closed_map_localise_info* I) {
+  CmapState& M = c->cmap;
+  const tloam_closed_map_localise_config& g = M.loc_cfg;
+  int rc = loc_begin(c, points_aos, n, false, false, &I->prepared);
+  if (rc != TLOAM_OK) return rc;
+  loc_state0(g, T0, st);
   HIPC(c, hipMemcpyAsync(M.loc_state.p, st, sizeof(*st), hipMemcpyHostToDevice, c->stream));
   const LocSweepArgs W = sweep_args(M, n, nullptr, nullptr);
   for (int k = 0; k < g.max_iterations; ++k) {
@@ -125,6 +131,51 @@ int localise_body(tloam_ctx* c, const double* points_aos, size_t n, const Pose& 
   HIPC(c, hipMemcpyAsync(st, M.loc_state.p, sizeof(*st), hipMemcpyDeviceToHost, c->stream));
   HIPC(c, hipStreamSynchronize(c->stream));
   return TLOAM_OK;
+}
+
+
+// max_iterations pairs of batched launches over the B states on the device
+void batch_pairs(tloam_ctx* c, size_t n, int B, int32_t* launches) {
+  CmapState& M = c->cmap;
+  const LocSweepArgs W = sweep_args(M, n, nullptr, nullptr);
+  for (int k = 0; k < M.loc_cfg.max_iterations; ++k) {
+    launch_loc_sweep_batch(W, B, c->stream);
+    launch_loc_step_batch(step_args(M, n, k), B, c->stream);
+    *launches += 2;
+  }
+}
+
+// what a hypothesis's state words and log say, as the single call reports them (info.launches and .prepared are the caller's)
+void loc_report(const CmapState& M, const LocState& st, const LocLog* log, const double* prior, double* pose_out,
+                tloam_closed_map_localise_info* I, std::vector<tloam_closed_map_localise_record>* records) {
+  const int it = std::min(std::max(st.iterations, 0), M.loc_cfg.max_iterations);
+  records->assign((size_t)it, tloam_closed_map_localise_record{});
+  if (it) memcpy(records->data(), log, sizeof(LocLog) * (size_t)it);
+  I->status = st.status;
+  I->iterations = it;
+  I->matched = (int64_t)st.sums[kLocTerms];
+  I->used = (int64_t)st.sums[kLocTerms + 1];
+  I->rms = I->used > 0 ? sqrt(2.0 * st.sums[27] / (double)I->used) : 0.0;
+  if (st.status == TLOAM_LOCALISE_DEGENERATE) memcpy(pose_out, prior, sizeof(double) * 16);
+  else pose_to_matrix(st.T, pose_out);
+}
+
+// the pick among hypotheses (skip[h] set: left out): not DEGENERATE, the largest used, then the smaller cost of the last executed
+// sweep, then the lower index; -1: none
+int loc_pick(const LocState* st, const int* skip, int B) {
+  int best = -1;
+  for (int h = 0; h < B; ++h) {
+    if ((skip && skip[h]) || st[h].status == TLOAM_LOCALISE_DEGENERATE) continue;
+    if (best < 0) { best = h; continue; }
+    const long long u = (long long)st[h].sums[kLocTerms + 1], ub = (long long)st[best].sums[kLocTerms + 1];
+    if (u > ub || (u == ub && st[h].sums[27] < st[best].sums[27])) best = h;
+  }
+  return best;
+}
+
+bool reloc_config_ok(const tloam_closed_map_relocalise_config& w) {
+  return w.num_candidates >= 1 && w.num_candidates <= kLocMaxBatch && w.max_dist > 0.0 && w.min_used_ratio >= 0.0 &&
+         w.min_used_ratio <= 1.0 && w.max_rms > 0.0;
 }
 
 }  // namespace
@@ -227,6 +278,194 @@ int tloam_closed_map_linearise(tloam_ctx* c, const double* points_aos, size_t n,
   memcpy(out28, st.sums, sizeof(double) * kLocTerms);
   counts2[0] = (int64_t)st.sums[kLocTerms];
   counts2[1] = (int64_t)st.sums[kLocTerms + 1];
+  return TLOAM_OK;
+}
+
+int tloam_closed_map_localise_batch(tloam_ctx* c, const double* points_aos, size_t n, const double* priors, size_t B,
+                                    double* poses_out, tloam_closed_map_localise_info* infos, int32_t* best_out) {
+  if (!priors || !poses_out || !infos || !best_out || B == 0 || B > (size_t)kLocMaxBatch) return TLOAM_E_INVALID;
+  std::vector<LocState> st(B);
+  {
+    Pose T0;
+    for (size_t h = 0; h < B; ++h) {   // every prior before anything is touched
+      const int rc0 = loc_check(c, points_aos, n, priors + 16 * h, &T0);
+      if (rc0 != TLOAM_OK) return rc0;
+      loc_state0(c->cmap.loc_cfg, T0, &st[h]);
+    }
+  }
+  CmapState& M = c->cmap;
+  int prepared = 0, launches = 0;
+  std::vector<LocLog> log(B * kLocMaxIterations);
+  auto body = [&]() -> int {
+    const int rc = loc_begin(c, points_aos, n, false, false, &prepared, B);
+    if (rc != TLOAM_OK) return rc;
+    HIPC(c, hipMemcpyAsync(M.loc_state.p, st.data(), sizeof(LocState) * B, hipMemcpyHostToDevice, c->stream));
+    batch_pairs(c, n, (int)B, &launches);
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipMemcpyAsync(st.data(), M.loc_state.p, sizeof(LocState) * B, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(log.data(), M.loc_log.p, sizeof(LocLog) * log.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    return TLOAM_OK;
+  };
+  const int rc = body();
+  if (rc != TLOAM_OK) return loc_failed(c, rc);
+  M.loc_ready = true;
+  M.loc_batch_records.resize(B);
+  for (size_t h = 0; h < B; ++h) {
+    memset(&infos[h], 0, sizeof(infos[h]));
+    loc_report(M, st[h], log.data() + h * kLocMaxIterations, priors + 16 * h, poses_out + 16 * h, &infos[h],
+               &M.loc_batch_records[h]);
+    infos[h].launches = launches;
+    infos[h].prepared = prepared;
+  }
+  *best_out = loc_pick(st.data(), nullptr, (int)B);
+  return TLOAM_OK;
+}
+
+int tloam_closed_map_localise_batch_log(tloam_ctx* c, size_t hypothesis, size_t capacity, size_t* n,
+                                        tloam_closed_map_localise_record* records) {
+  if (n) *n = 0;
+  if (!c || !n || c->nranks > 1 || hypothesis >= c->cmap.loc_batch_records.size()) return TLOAM_E_INVALID;
+  const std::vector<tloam_closed_map_localise_record>& R = c->cmap.loc_batch_records[hypothesis];
+  *n = R.size();
+  if (!records || R.empty()) return TLOAM_OK;
+  if (capacity < R.size()) return TLOAM_E_INVALID;
+  memcpy(records, R.data(), sizeof(R[0]) * R.size());
+  return TLOAM_OK;
+}
+
+void tloam_closed_map_relocalise_default_config(tloam_closed_map_relocalise_config* cfg) {
+  if (!cfg) return;
+  memset(cfg, 0, sizeof(*cfg));
+  cfg->num_candidates = 8;
+  cfg->max_dist = HUGE_VAL; cfg->min_used_ratio = 0.5; cfg->max_rms = HUGE_VAL;
+}
+
+int tloam_closed_map_relocalise_configure(tloam_ctx* c, const tloam_closed_map_relocalise_config* cfg) {
+  if (!c || c->nranks > 1) return TLOAM_E_INVALID;
+  tloam_closed_map_relocalise_config want;
+  if (cfg) want = *cfg;
+  else tloam_closed_map_relocalise_default_config(&want);
+  if (!reloc_config_ok(want)) return TLOAM_E_INVALID;
+  want.reserved0 = 0;
+  c->cmap.reloc_cfg = want;
+  return TLOAM_OK;
+}
+
+int tloam_closed_map_relocalise(tloam_ctx* c, const double* points_aos, size_t n, double* pose_out,
+                                tloam_closed_map_relocalise_info* info) {
+  if (!c || c->nranks > 1 || !points_aos || !pose_out || n == 0 || n > kMaxPoints || n > (size_t)INT32_MAX / 3)
+    return TLOAM_E_INVALID;
+  CmapState& M = c->cmap;
+  PlaceState& P = c->place;
+  const int64_t K = M.info.n_keyframes;
+  if (!P.cfg.enabled || !M.built || !M.surfeled || K < 1 || K > P.n_kf || M.poses.size() != 16 * (size_t)K)
+    return TLOAM_E_NOT_READY;
+  const tloam_closed_map_relocalise_config& r = M.reloc_cfg;
+  const tloam_place_config& g = P.cfg;
+  const int B = (int)std::min<int64_t>(r.num_candidates, K);
+  const size_t R = (size_t)g.n_rings, S = (size_t)g.n_sectors;
+  int prepared = 0, launches = 0;
+  std::vector<LocState> st((size_t)B);
+  std::vector<RelocHyp> hyp((size_t)B);
+  std::vector<LocLog> log((size_t)B * kLocMaxIterations);
+  auto body = [&]() -> int {
+    const int rc = loc_begin(c, points_aos, n, false, false, &prepared, (size_t)B);
+    if (rc != TLOAM_OK) return rc;
+    HIPC(c, P.s_desc.reserve(R * S)); HIPC(c, P.s_rkey.reserve(R)); HIPC(c, P.s_skey.reserve(S));
+    HIPC(c, M.reloc_cand.reserve(kLocMaxBatch)); HIPC(c, M.reloc_hyp.reserve(kLocMaxBatch));
+    HIPC(c, M.reloc_poses.reserve(16 * (size_t)K));
+    HIPC(c, hipMemcpyAsync(M.reloc_poses.p, M.poses.data(), sizeof(double) * 16 * (size_t)K, hipMemcpyHostToDevice, c->stream));
+    PlaceDescArgs D;   // the scan's descriptor and ring key, as tloam_place_describe forms them, from the uploaded scan
+    memset(&D, 0, sizeof(D));
+    D.aos = M.loc_pts.p; D.n = (long long)n;
+    D.bins = P.bins.p; D.desc = P.s_desc.p; D.ring_key = P.s_rkey.p; D.sector_key = P.s_skey.p;
+    D.R = g.n_rings; D.S = g.n_sectors;
+    D.max_radius = g.max_radius; D.height_offset = g.height_offset;
+    launch_place_describe(D, c->stream);
+    PlaceSearchArgs A;   // keyframes 0 .. K-1 ranked by ring key, each candidate's best shift; no loop record
+    memset(&A, 0, sizeof(A));
+    A.desc = P.desc.p; A.ring_key = P.rkey.p;
+    A.q_desc = P.s_desc.p; A.q_ring_key = P.s_rkey.p;
+    A.kdist = P.kdist.p; A.taken = P.taken.p; A.cand = M.reloc_cand.p;
+    A.m = (int)K; A.ncand = B;
+    A.R = g.n_rings; A.S = g.n_sectors;
+    launch_place_candidates(A, c->stream);
+    RelocPriorArgs Q;
+    memset(&Q, 0, sizeof(Q));
+    Q.cand = M.reloc_cand.p; Q.poses = M.reloc_poses.p;
+    Q.B = B; Q.S = g.n_sectors;
+    Q.max_dist = r.max_dist;
+    Q.max_residual0 = M.loc_cfg.max_residual0; Q.min_residual = M.loc_cfg.min_residual;
+    Q.hyp = M.reloc_hyp.p; Q.st = M.loc_state.p;
+    launch_reloc_priors(Q, c->stream);
+    launches += 5;
+    batch_pairs(c, n, B, &launches);
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipMemcpyAsync(st.data(), M.loc_state.p, sizeof(LocState) * (size_t)B, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(hyp.data(), M.reloc_hyp.p, sizeof(RelocHyp) * (size_t)B, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(log.data(), M.loc_log.p, sizeof(LocLog) * log.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    return TLOAM_OK;
+  };
+  const int rc = body();
+  if (rc != TLOAM_OK) return loc_failed(c, rc);
+  M.loc_ready = true;
+  M.reloc_hyps.assign((size_t)B, tloam_closed_map_relocalise_hypothesis{});
+  M.loc_batch_records.resize((size_t)B);
+  std::vector<int> skip((size_t)B);
+  double finite = 0.0;
+  bool have_finite = false;
+  for (int h = 0; h < B; ++h) {
+    tloam_closed_map_relocalise_hypothesis& H = M.reloc_hyps[(size_t)h];
+    const RelocHyp& d = hyp[(size_t)h];
+    H.keyframe = d.keyframe; H.shift = d.shift; H.skipped = d.skipped;
+    H.dist = d.d; H.yaw = d.yaw;
+    memcpy(H.prior_colmajor, d.prior, sizeof(d.prior));
+    skip[(size_t)h] = d.skipped;
+    if (d.skipped) {   // never swept: the pose is the prior
+      memcpy(H.pose_colmajor, d.prior, sizeof(d.prior));
+      H.localise.status = TLOAM_LOCALISE_DEGENERATE;
+      M.loc_batch_records[(size_t)h].clear();
+    } else {
+      loc_report(M, st[(size_t)h], log.data() + (size_t)h * kLocMaxIterations, d.prior, H.pose_colmajor, &H.localise,
+                 &M.loc_batch_records[(size_t)h]);
+      if (!have_finite) { finite = st[(size_t)h].sums[kLocFinite]; have_finite = true; }
+    }
+    H.localise.launches = 2 * M.loc_cfg.max_iterations;
+    H.localise.prepared = prepared;
+  }
+  int best = loc_pick(st.data(), skip.data(), B);
+  if (best >= 0) {
+    const tloam_closed_map_localise_info& L = M.reloc_hyps[(size_t)best].localise;
+    if (!((double)L.used >= r.min_used_ratio * finite && L.rms <= r.max_rms)) best = -1;
+  }
+  tloam_closed_map_relocalise_info I;
+  memset(&I, 0, sizeof(I));
+  I.status = best >= 0 ? TLOAM_RELOCALISE_FOUND : TLOAM_RELOCALISE_NOT_FOUND;
+  I.n_hypotheses = B;
+  I.best = best;
+  I.launches = launches;
+  I.keyframe = -1;
+  if (best >= 0) {
+    const tloam_closed_map_relocalise_hypothesis& H = M.reloc_hyps[(size_t)best];
+    I.keyframe = H.keyframe; I.shift = H.shift; I.dist = H.dist; I.yaw = H.yaw;
+    I.localise = H.localise;
+    memcpy(pose_out, H.pose_colmajor, sizeof(H.pose_colmajor));
+  }
+  if (info) *info = I;
+  return TLOAM_OK;
+}
+
+int tloam_closed_map_relocalise_hypotheses(tloam_ctx* c, size_t capacity, size_t* n,
+                                           tloam_closed_map_relocalise_hypothesis* hypotheses) {
+  if (n) *n = 0;
+  if (!c || !n || c->nranks > 1) return TLOAM_E_INVALID;
+  const std::vector<tloam_closed_map_relocalise_hypothesis>& H = c->cmap.reloc_hyps;
+  *n = H.size();
+  if (!hypotheses || H.empty()) return TLOAM_OK;
+  if (capacity < H.size()) return TLOAM_E_INVALID;
+  memcpy(hypotheses, H.data(), sizeof(H[0]) * H.size());
   return TLOAM_OK;
 }
 

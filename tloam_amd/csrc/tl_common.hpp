@@ -745,6 +745,8 @@ static_assert(sizeof(LocRecord) == 64, "a voxel record is one cache line");
 constexpr int kLocTerms = 28;       // H's upper triangle by rows (21), g (6), cost
 constexpr int kLocRow = 32;         // a block's partial row: the terms, matched, used (as doubles: exact below 2^53), two unused
 constexpr int kLocMaxIterations = 64;
+constexpr int kLocMaxBatch = 32;    // hypotheses of one scan in one set of launches (tloam_closed_map_localise_batch)
+constexpr int kLocFinite = 30;      // the batched sweep's row slot of the scan's finite points (unused, zero, in the single form)
 struct LocLog {               // tloam_closed_map_localise_record
   double pose[16];
   double tau, cost;
@@ -800,6 +802,28 @@ inline int loc_blocks(long long n) { return (int)((n + 255) / 256); }
 void launch_loc_prepare(const LocPrepArgs& A, hipStream_t s);
 void launch_loc_sweep(const LocSweepArgs& A, hipStream_t s);
 void launch_loc_step(const LocStepArgs& A, hipStream_t s);
+// B hypotheses: st [B], partial [B][blocks][kLocRow], log [B][kLocMaxIterations]; ids and res unused
+void launch_loc_sweep_batch(const LocSweepArgs& A, int B, hipStream_t s);
+void launch_loc_step_batch(const LocStepArgs& A, int B, hipStream_t s);
+
+// relocalisation: a candidate of the place search made a hypothesis of the batched localiser
+struct PlaceCandidate;
+struct RelocHyp {
+  long long keyframe;
+  int shift, skipped;           // skipped: d is not < max_dist (or the build's pose is no rigid transform): never swept
+  double d, yaw;
+  double prior[16];             // P_build[keyframe] * Rz(yaw), column-major
+};
+struct RelocPriorArgs {
+  const PlaceCandidate* cand;   // [B] of k_place_rank / k_place_shift
+  const double* poses;          // [K][16] the poses the closed map's build used
+  int B, S;
+  double max_dist;
+  double max_residual0, min_residual;
+  RelocHyp* hyp;                // [B]
+  LocState* st;                 // [B] the batched localiser's state words
+};
+void launch_reloc_priors(const RelocPriorArgs& A, hipStream_t s);
 
 // ---- deskew of a scan under constant velocity (tl_deskew.hip) -------------
 struct DeskewArgs {
@@ -843,6 +867,8 @@ struct PlaceSearchArgs {
   PlaceCandidate* cand;           // scratch [num_candidates]
   tloam_place_loop* loops;        // the loop records [K]
   unsigned long long* n_loops;    // their count
+  const double* q_desc;           // the query's descriptor and ring key when it is not a keyframe (null: keyframe q's)
+  const double* q_ring_key;
   int q;                          // the query keyframe
   int m;                          // keyframes 0 .. m-1 are searched (m >= 1)
   int ncand;                      // min(num_candidates, m)
@@ -850,6 +876,7 @@ struct PlaceSearchArgs {
   double dist_thres;
 };
 void launch_place_search(const PlaceSearchArgs& A, hipStream_t s);   // k_place_rank, k_place_shift, k_place_pick
+void launch_place_candidates(const PlaceSearchArgs& A, hipStream_t s);   // k_place_rank, k_place_shift: cand[0 .. ncand), no record
 
 // ---- loop verification: keyframe clouds, the local target, the score (tl_loop.hip) ------------------
 constexpr int kLoopSpans = 16;    // spans per launch of k_place_clouds / k_loop_assemble

@@ -470,9 +470,20 @@ struct CmapState {
   DBuf<tl::LocLog> loc_log;
   bool loc_ready = false;          // the records are those of the surfels and the gate at hand
   std::vector<tloam_closed_map_localise_record> loc_records;   // of the last localise call
+  // the batched localiser and the relocalisation on top of it: per hypothesis the log of the last batch
+  // (or relocalise), the relocalisation's configuration, its candidates, hypotheses and the build's poses on the device, and the
+  // hypotheses of the last relocalise
+  std::vector<std::vector<tloam_closed_map_localise_record>> loc_batch_records;
+  tloam_closed_map_relocalise_config reloc_cfg = {8, 0, HUGE_VAL, 0.5, HUGE_VAL};   // _relocalise_default_config
+  DBuf<tl::PlaceCandidate> reloc_cand;
+  DBuf<tl::RelocHyp> reloc_hyp;
+  DBuf<double> reloc_poses;
+  std::vector<tloam_closed_map_relocalise_hypothesis> reloc_hyps;
   void drop_localise() {
     loc_ready = false;
     loc_records.clear();
+    loc_batch_records.clear();
+    reloc_hyps.clear();
   }
   void drop_surfels() {
     surfeled = false;

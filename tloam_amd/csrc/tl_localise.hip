@@ -8,6 +8,12 @@
 //                                by shuffles and over the block's four waves through LDS; one partial row per block
 //   k_loc_step      1 x 64       the partial rows added in block order, the degeneracy tests, the 6 x 6 Cholesky, the pose
 //                                update, the log record and the `done` word
+// and for B hypotheses of one scan (tloam_closed_map_localise_batch, _relocalise):
+//   k_loc_sweep_batch  (grid, B) x 256   k_loc_sweep's body, the hypothesis on blockIdx.y: its own state words and partial rows;
+//                                        one more sum, the scan's finite points (row slot kLocFinite)
+//   k_loc_step_batch   B x 64            k_loc_step's body, a wave per hypothesis
+// Both forms run one device body, and a hypothesis's sums are ordered by the point index alone, so hypothesis h of a batch has
+// the bits of the single call from its prior.
 // A sweep or a step that finds `done` set returns on entry (a wave-uniform branch), so a call is the same launches for every
 // input.  No block waits on another block.  No floating-point atomics: the order of every sum is fixed by the point index
 // (lane, wave, block), so two calls give the same bits.
@@ -57,17 +63,25 @@ __global__ __launch_bounds__(256) void k_loc_prepare(LocPrepArgs A) {
   A.rec[id] = R;
 }
 
-__global__ __launch_bounds__(256) void k_loc_sweep(LocSweepArgs W) {
-  __shared__ double s_row[4][kLocRow];
-  if (W.st->done) return;   // (the same word for every thread of the grid)
+// The sweep of one block of one hypothesis: the body of k_loc_sweep and of k_loc_sweep_batch, so that a hypothesis of a batch
+// rounds as the single call does.  NT sums are carried: the terms, matched, used and (kFinite) the scan's finite points
+template <bool kFinite>
+__device__ __forceinline__ void loc_sweep_body(const LocSweepArgs& W, const LocState* st, double* partial,
+                                               double (*s_row)[kLocRow]) {
+  constexpr int NT = kLocTerms + 2 + (kFinite ? 1 : 0);
+  if (st->done) return;   // (the same word for every thread of the hypothesis's blocks)
   const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  double t[kLocTerms + 2];
+  double t[NT];
 #pragma unroll
-  for (int k = 0; k < kLocTerms + 2; ++k) t[k] = 0.0;
+  for (int k = 0; k < NT; ++k) t[k] = 0.0;
   if (g < W.n) {
-    const double* M = W.st->M;
-    const double tau = W.st->tau;
+    const double* M = st->M;
+    const double tau = st->tau;
+    if (kFinite) {
+      const double px = W.pts[3 * g], py = W.pts[3 * g + 1], pz = W.pts[3 * g + 2];
+      if (px - px == 0.0 && py - py == 0.0 && pz - pz == 0.0) t[kLocFinite] = 1.0;
+    }
     double E[3];
     map_transform_point(M, W.pts[3 * g], W.pts[3 * g + 1], W.pts[3 * g + 2], &E[0], &E[1], &E[2]);
     unsigned long long key;
@@ -121,7 +135,7 @@ __global__ __launch_bounds__(256) void k_loc_sweep(LocSweepArgs W) {
   }
   // over the wave: a butterfly, the same order in every launch; then the four waves in order
 #pragma unroll
-  for (int k = 0; k < kLocTerms + 2; ++k) {
+  for (int k = 0; k < NT; ++k) {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) t[k] += __shfl_xor(t[k], off, 64);
     if (lane == 0) s_row[wave][k] = t[k];
@@ -130,9 +144,20 @@ __global__ __launch_bounds__(256) void k_loc_sweep(LocSweepArgs W) {
   if (threadIdx.x < kLocRow) {
     const int k = threadIdx.x;
     double s = 0.0;
-    if (k < kLocTerms + 2) s = ((s_row[0][k] + s_row[1][k]) + s_row[2][k]) + s_row[3][k];
-    W.partial[(size_t)blockIdx.x * kLocRow + k] = s;
+    if (k < NT) s = ((s_row[0][k] + s_row[1][k]) + s_row[2][k]) + s_row[3][k];
+    partial[(size_t)blockIdx.x * kLocRow + k] = s;
   }
+}
+
+__global__ __launch_bounds__(256) void k_loc_sweep(LocSweepArgs W) {
+  __shared__ double s_row[4][kLocRow];
+  loc_sweep_body<false>(W, W.st, W.partial, s_row);
+}
+
+// hypothesis blockIdx.y of a batch: its own state words and its own gridDim.x partial rows; ids and res are not written
+__global__ __launch_bounds__(256) void k_loc_sweep_batch(LocSweepArgs W) {
+  __shared__ double s_row[4][kLocRow];
+  loc_sweep_body<true>(W, W.st + blockIdx.y, W.partial + (size_t)blockIdx.y * gridDim.x * kLocRow, s_row);
 }
 
 // H d = -g by Cholesky; false: a pivot is not > ratio * H_kk
@@ -176,13 +201,13 @@ __device__ bool loc_solve6(const double* sums, double ratio, double d[6]) {
   return true;
 }
 
-__global__ __launch_bounds__(64) void k_loc_step(LocStepArgs A) {
-  __shared__ double s_sum[kLocRow];
-  LocState* S = A.st;
+// The step of one hypothesis by one wave: the body of k_loc_step and of k_loc_step_batch
+__device__ __forceinline__ void loc_step_body(const LocStepArgs& A, LocState* S, const double* partial, LocLog* log,
+                                              double* s_sum) {
   if (S->done) return;
   const int lane = threadIdx.x;
   if (lane < kLocRow) {   // a lane per column, the rows in block order
-    const double* col = A.partial + lane;
+    const double* col = partial + lane;
     double s = 0.0;
     int b = 0;
     for (; b + 32 <= A.nblocks; b += 32) {   // 32 rows fetched ahead, added in order: the loads overlap, the order stays
@@ -216,13 +241,13 @@ __global__ __launch_bounds__(64) void k_loc_step(LocStepArgs A) {
   S->iterations = A.k + 1;
   if (!ok) {
     for (int i = 0; i < 6; ++i) R.d[i] = 0.0;
-    A.log[A.k] = R;
+    log[A.k] = R;
     S->status = TLOAM_LOCALISE_DEGENERATE;
     S->done = 1;
     return;
   }
   for (int i = 0; i < 6; ++i) R.d[i] = d[i];
-  A.log[A.k] = R;
+  log[A.k] = R;
   const Pose T = compose(se3_exp(d), S->T);
   S->T = T;
   double M[16];
@@ -242,7 +267,73 @@ __global__ __launch_bounds__(64) void k_loc_step(LocStepArgs A) {
   }
 }
 
+__global__ __launch_bounds__(64) void k_loc_step(LocStepArgs A) {
+  __shared__ double s_sum[kLocRow];
+  loc_step_body(A, A.st, A.partial, A.log, s_sum);
+}
+
+// hypothesis blockIdx.x of a batch: its state words, its nblocks partial rows, its kLocMaxIterations log records
+__global__ __launch_bounds__(64) void k_loc_step_batch(LocStepArgs A) {
+  __shared__ double s_sum[kLocRow];
+  const size_t h = blockIdx.x;
+  loc_step_body(A, A.st + h, A.partial + h * (size_t)A.nblocks * kLocRow, A.log + h * kLocMaxIterations, s_sum);
+}
+
+// ---- relocalisation: the place search's candidates made hypotheses of the batched localiser -----------
+// A lane per candidate h: yaw = shift * (2 pi / S), less 2 pi when above pi (k_place_pick's); c = cos(yaw), s = sin(yaw);
+// prior = P * Rz(yaw) with P the pose the closed map's build used for the keyframe: column 0 = c * P0 + s * P1,
+// column 1 = c * P1 - s * P0, columns 2 and 3 are P's, the fourth row is P's.  The state words are those the host forms for
+// tloam_closed_map_localise from that prior: the quaternion by pose_from_matrix, M by pose_to_matrix.  A candidate whose d is
+// not < max_dist starts with `done` set.
+__global__ __launch_bounds__(64) void k_reloc_priors(RelocPriorArgs A) {
+  const int h = threadIdx.x;
+  if (h >= A.B) return;
+  const PlaceCandidate C = A.cand[h];
+  const double* P = A.poses + 16 * (size_t)C.keyframe;
+  double yaw = (double)C.shift * ((2.0 * kPi) / (double)A.S);
+  if (yaw > kPi) yaw = yaw - 2.0 * kPi;
+  const double cy = cos(yaw), sy = sin(yaw);
+  RelocHyp* H = A.hyp + h;   // (the prior is formed in place: pose_from_matrix indexes it by a run-time axis)
+  H->keyframe = C.keyframe;
+  H->shift = C.shift;
+  H->d = C.d;
+  H->yaw = yaw;
+  double* Q = H->prior;
+  for (int r = 0; r < 3; ++r) {
+    Q[r] = cy * P[r] + sy * P[4 + r];
+    Q[4 + r] = cy * P[4 + r] - sy * P[r];
+    Q[8 + r] = P[8 + r];
+    Q[12 + r] = P[12 + r];
+  }
+  Q[3] = P[3]; Q[7] = P[7]; Q[11] = P[11]; Q[15] = P[15];
+  Pose T;
+  const bool rigid = pose_from_matrix(Q, &T);
+  const int skipped = (!(C.d < A.max_dist) || !rigid) ? 1 : 0;
+  H->skipped = skipped;
+  LocState* S = A.st + h;
+  for (int i = 0; i < kLocRow; ++i) S->sums[i] = 0.0;
+  if (rigid) {
+    double M[16];
+    pose_to_matrix(T, M);
+    for (int i = 0; i < 16; ++i) S->M[i] = M[i];
+    S->T = T;
+  } else {
+    for (int i = 0; i < 16; ++i) S->M[i] = Q[i];
+    S->T = Pose{};
+  }
+  S->pw = A.max_residual0;
+  S->tau = fmax(A.min_residual, A.max_residual0);
+  S->done = skipped;
+  S->status = skipped ? TLOAM_LOCALISE_DEGENERATE : TLOAM_LOCALISE_MAX_ITERATIONS;
+  S->iterations = 0;
+  S->reserved0 = 0;
+}
+
 }  // namespace
+
+void launch_reloc_priors(const RelocPriorArgs& A, hipStream_t s) {
+  hipLaunchKernelGGL(k_reloc_priors, dim3(1), dim3(64), 0, s, A);
+}
 
 void launch_loc_prepare(const LocPrepArgs& A, hipStream_t s) {
   if (A.nv <= 0) return;
@@ -255,6 +346,14 @@ void launch_loc_sweep(const LocSweepArgs& A, hipStream_t s) {
 
 void launch_loc_step(const LocStepArgs& A, hipStream_t s) {
   hipLaunchKernelGGL(k_loc_step, dim3(1), dim3(64), 0, s, A);
+}
+
+void launch_loc_sweep_batch(const LocSweepArgs& A, int B, hipStream_t s) {
+  hipLaunchKernelGGL(k_loc_sweep_batch, dim3(loc_blocks(A.n), B), dim3(256), 0, s, A);
+}
+
+void launch_loc_step_batch(const LocStepArgs& A, int B, hipStream_t s) {
+  hipLaunchKernelGGL(k_loc_step_batch, dim3(B), dim3(64), 0, s, A);
 }
 
 }  // namespace tl

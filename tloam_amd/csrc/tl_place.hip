@@ -13,6 +13,8 @@
 //                               id, by ncand rounds of a block argmin
 //   k_place_shift  ncand x 64k  a workgroup per candidate, a lane per shift: column norms in LDS, d(s) summed over columns in
 //                               order; the block's argmin (ties to the lower shift)
+//                               (the relocalisation of DESIGN.md section 24 runs these two with a query that is no keyframe:
+//                               q_desc, q_ring_key)
 //   k_place_pick   1 x 64       the best pair over the candidates (d, then shift, then keyframe id); d < dist_thres appends a
 //                               loop record
 // Compiled with -ffp-contract=off: every sum, product and quotient rounds as tests/place_np.py restates it.
@@ -97,7 +99,7 @@ __global__ __launch_bounds__(256) void k_place_rank(PlaceSearchArgs A) {
   __shared__ double s_d[4];
   __shared__ int s_i[4];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const double* kq = A.ring_key + (size_t)A.q * A.R;
+  const double* kq = A.q_ring_key ? A.q_ring_key : A.ring_key + (size_t)A.q * A.R;
   for (int j = t; j < A.m; j += 256) {
     const double* kc = A.ring_key + (size_t)j * A.R;
     double acc = 0.0;
@@ -141,7 +143,7 @@ __global__ __launch_bounds__(384) void k_place_shift(PlaceSearchArgs A) {
   const int s = threadIdx.x, lane = s & 63, wave = s >> 6, S = A.S, R = A.R;
   const size_t RS = (size_t)R * S;
   const int c = A.cand[blockIdx.x].keyframe;
-  const double* __restrict__ dq = A.desc + (size_t)A.q * RS;
+  const double* __restrict__ dq = A.q_desc ? A.q_desc : A.desc + (size_t)A.q * RS;
   const double* __restrict__ dc = A.desc + (size_t)c * RS;
   if (s < S) {
     double aq = 0.0, ac = 0.0;
@@ -221,11 +223,16 @@ void launch_place_describe(const PlaceDescArgs& A, hipStream_t s) {
   hipLaunchKernelGGL(k_place_keys, dim3(1), dim3(512), 0, s, A);
 }
 
-void launch_place_search(const PlaceSearchArgs& A, hipStream_t s) {
+void launch_place_candidates(const PlaceSearchArgs& A, hipStream_t s) {
   if (A.m <= 0 || A.ncand <= 0) return;
   hipLaunchKernelGGL(k_place_rank, dim3(1), dim3(256), 0, s, A);
   const unsigned threads = (unsigned)((A.S + 63) / 64 * 64);
   hipLaunchKernelGGL(k_place_shift, dim3((unsigned)A.ncand), dim3(threads), 0, s, A);
+}
+
+void launch_place_search(const PlaceSearchArgs& A, hipStream_t s) {
+  if (A.m <= 0 || A.ncand <= 0) return;
+  launch_place_candidates(A, s);
   hipLaunchKernelGGL(k_place_pick, dim3(1), dim3(64), 0, s, A);
 }
 

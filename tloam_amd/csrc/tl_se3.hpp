@@ -166,7 +166,7 @@ TL_HD void se3_plus(const double x[6], const double delta[6], double out[6]) {
 
 // se3.hpp:497-504 SE3(Matrix4): false where Sophus would SOPHUS_ENSURE-abort.
 // M is column-major 4x4 (Eigen::Isometry3d::matrix()).
-inline bool pose_from_matrix(const double M[16], Pose* out) {
+__host__ __device__ inline bool pose_from_matrix(const double M[16], Pose* out) {
   auto m = [&](int r, int c) { return M[c * 4 + r]; };
   // (a non-finite translation passes Sophus' checks -- they look at the rotation and the last row -- and the reference then
   //  computes on NaNs; here it is a bad pose like the others: a status code instead of a NaN result)

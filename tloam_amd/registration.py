@@ -170,6 +170,40 @@ class ClosedMapLocaliseRecord(C.Structure):
 
 
 LOCALISE_CONVERGED, LOCALISE_MAX_ITERATIONS, LOCALISE_DEGENERATE = 0, 1, 2
+LOCALISE_MAX_BATCH = 32
+
+
+class ClosedMapRelocaliseConfig(C.Structure):
+    """tloam_closed_map_relocalise_config: how many keyframes are localised from, the Scan Context distance above which a
+    candidate is skipped, and the acceptance of the winner.  The defaults are choices, not measurements."""
+    _fields_ = [("num_candidates", C.c_int32), ("reserved0", C.c_int32), ("max_dist", C.c_double),
+                ("min_used_ratio", C.c_double), ("max_rms", C.c_double)]
+
+
+class ClosedMapRelocaliseInfo(C.Structure):
+    """tloam_closed_map_relocalise_info."""
+    _fields_ = [("status", C.c_int32), ("n_hypotheses", C.c_int32), ("best", C.c_int32), ("launches", C.c_int32),
+                ("keyframe", C.c_int64), ("shift", C.c_int32), ("reserved0", C.c_int32), ("dist", C.c_double), ("yaw", C.c_double),
+                ("localise", ClosedMapLocaliseInfo)]
+
+    def as_dict(self):
+        return {"status": int(self.status), "n_hypotheses": int(self.n_hypotheses), "best": int(self.best),
+                "launches": int(self.launches), "keyframe": int(self.keyframe), "shift": int(self.shift),
+                "dist": float(self.dist), "yaw": float(self.yaw), "localise": self.localise.as_dict()}
+
+
+class ClosedMapRelocaliseHypothesis(C.Structure):
+    """tloam_closed_map_relocalise_hypothesis."""
+    _fields_ = [("keyframe", C.c_int64), ("shift", C.c_int32), ("skipped", C.c_int32), ("dist", C.c_double), ("yaw", C.c_double),
+                ("prior_colmajor", C.c_double * 16), ("pose_colmajor", C.c_double * 16), ("localise", ClosedMapLocaliseInfo)]
+
+    def as_dict(self):
+        return {"keyframe": int(self.keyframe), "shift": int(self.shift), "skipped": int(self.skipped), "dist": float(self.dist),
+                "yaw": float(self.yaw), "prior": np.array(self.prior_colmajor[:]).reshape(4, 4).T.copy(),
+                "pose": np.array(self.pose_colmajor[:]).reshape(4, 4).T.copy(), "localise": self.localise.as_dict()}
+
+
+RELOCALISE_FOUND, RELOCALISE_NOT_FOUND = 0, 1
 
 
 class DeskewConfig(C.Structure):
@@ -508,6 +542,13 @@ def load_library():
         "tloam_closed_map_localise": (C.c_int, [vp, dp, sz, dp, dp, C.POINTER(ClosedMapLocaliseInfo)]),
         "tloam_closed_map_localise_log": (C.c_int, [vp, sz, C.POINTER(sz), C.POINTER(ClosedMapLocaliseRecord)]),
         "tloam_closed_map_linearise": (C.c_int, [vp, dp, sz, dp, C.c_double, C.POINTER(C.c_int32), dp, dp, C.POINTER(C.c_int64)]),
+        "tloam_closed_map_localise_batch": (C.c_int, [vp, dp, sz, dp, sz, dp, C.POINTER(ClosedMapLocaliseInfo),
+                                                      C.POINTER(C.c_int32)]),
+        "tloam_closed_map_localise_batch_log": (C.c_int, [vp, sz, sz, C.POINTER(sz), C.POINTER(ClosedMapLocaliseRecord)]),
+        "tloam_closed_map_relocalise_default_config": (None, [C.POINTER(ClosedMapRelocaliseConfig)]),
+        "tloam_closed_map_relocalise_configure": (C.c_int, [vp, C.POINTER(ClosedMapRelocaliseConfig)]),
+        "tloam_closed_map_relocalise": (C.c_int, [vp, dp, sz, dp, C.POINTER(ClosedMapRelocaliseInfo)]),
+        "tloam_closed_map_relocalise_hypotheses": (C.c_int, [vp, sz, C.POINTER(sz), C.POINTER(ClosedMapRelocaliseHypothesis)]),
         "tloam_closed_map_read_moments": (C.c_int, [vp, sz, sz, C.POINTER(C.c_int64)]),
         "tloam_closed_map_read_surfels": (C.c_int, [vp, sz, sz, dp, dp, C.POINTER(C.c_int64)]),
         "tloam_closed_map_read_surfels_box": (C.c_int, [vp, dp, dp, C.c_int64, C.c_double, C.c_double, sz, C.POINTER(sz), dp, dp, dp,
@@ -557,7 +598,9 @@ EXPORTED_SYMBOLS = (
     "tloam_closed_map_surfel_default_config", "tloam_closed_map_surfel_configure", "tloam_closed_map_get_surfel_info",
     "tloam_closed_map_surfels", "tloam_closed_map_read_moments", "tloam_closed_map_read_surfels", "tloam_closed_map_read_surfels_box",
     "tloam_closed_map_localise_default_config", "tloam_closed_map_localise_configure", "tloam_closed_map_localise",
-    "tloam_closed_map_localise_log", "tloam_closed_map_linearise",
+    "tloam_closed_map_localise_log", "tloam_closed_map_linearise", "tloam_closed_map_localise_batch",
+    "tloam_closed_map_localise_batch_log", "tloam_closed_map_relocalise_default_config", "tloam_closed_map_relocalise_configure",
+    "tloam_closed_map_relocalise", "tloam_closed_map_relocalise_hypotheses",
     "tloam_rccl_unique_id", "tloam_comm_init_rccl",
     "tloam_comm_mailbox_export", "tloam_comm_init_mailbox",
     "tloam_comm_init_callback", "tloam_shard_range", "tloam_shard_ranges_frame", "tloam_se3_exp", "tloam_se3_log", "tloam_se3_plus",
@@ -1396,6 +1439,67 @@ class HipRegistration:
         return {"ids": ids[: len(pts)].copy(), "residuals": res[: len(pts)].copy(), "H": out[:21].copy(), "g": out[21:27].copy(),
                 "cost": float(out[27]), "matched": int(cnt[0]), "used": int(cnt[1])}
 
+    # ---- several hypotheses of one scan, and relocalisation without a prior
+    def closed_map_localise_batch(self, points, priors):
+        """the scan `points` registered from every pose of `priors` (B, 4, 4; B in 1 .. 32) in one set of launches
+        -> (poses (B, 4, 4), [info dict] * B, best).  Hypothesis h has the bits of closed_map_localise(points, priors[h]);
+        best is -1 when every hypothesis is DEGENERATE"""
+        pts = _aos(points)
+        priors = np.asarray(priors, np.float64)
+        if priors.ndim != 3 or priors.shape[1:] != (4, 4):
+            raise ValueError("priors: (B, 4, 4)")
+        B = len(priors)
+        pr = np.ascontiguousarray(priors.transpose(0, 2, 1)).reshape(-1)   # column-major, hypothesis by hypothesis
+        out = np.zeros(16 * max(B, 1))
+        infos = (ClosedMapLocaliseInfo * max(B, 1))()
+        best = C.c_int32(-1)
+        self._check(self.L.tloam_closed_map_localise_batch(self.h, _dp(pts), len(pts), _dp(pr), B, _dp(out), infos,
+                                                           C.byref(best)), "tloam_closed_map_localise_batch")
+        poses = out[: 16 * B].reshape(B, 4, 4).transpose(0, 2, 1).copy()
+        return poses, [infos[h].as_dict() for h in range(B)], int(best.value)
+
+    def closed_map_localise_batch_log(self, h) -> list:
+        """the executed iterations of hypothesis h of the last closed_map_localise_batch (or closed_map_relocalise)"""
+        n = C.c_size_t(0)
+        self._check(self.L.tloam_closed_map_localise_batch_log(self.h, int(h), 0, C.byref(n), None),
+                    "tloam_closed_map_localise_batch_log")
+        if not n.value:
+            return []
+        rec = (ClosedMapLocaliseRecord * n.value)()
+        self._check(self.L.tloam_closed_map_localise_batch_log(self.h, int(h), n.value, C.byref(n), rec),
+                    "tloam_closed_map_localise_batch_log")
+        return [r.as_dict() for r in rec[: n.value]]
+
+    def closed_map_relocalise_configure(self, cfg: ClosedMapRelocaliseConfig | None = None, **over):
+        """the relocalisation's configuration (default_closed_map_relocalise_config(**over) when cfg is None).  Kept across
+        odometry_reset; a refused configuration leaves the old one."""
+        cfg = cfg if cfg is not None else default_closed_map_relocalise_config(**over)
+        self._check(self.L.tloam_closed_map_relocalise_configure(self.h, C.byref(cfg)), "tloam_closed_map_relocalise_configure")
+
+    def closed_map_relocalise(self, points):
+        """the scan `points` (n, 3; sensor frame) localised in the closed map without a prior: place recognition's candidates,
+        a hypothesis from each, the batched localiser, the pick -> (pose (4, 4) or None when NOT_FOUND, info dict)"""
+        pts = _aos(points)
+        out = np.zeros(16)
+        info = ClosedMapRelocaliseInfo()
+        self._check(self.L.tloam_closed_map_relocalise(self.h, _dp(pts), len(pts), _dp(out), C.byref(info)),
+                    "tloam_closed_map_relocalise")
+        pose = out.reshape(4, 4).T.copy() if info.status == RELOCALISE_FOUND else None
+        return pose, info.as_dict()
+
+    def closed_map_relocalise_hypotheses(self) -> list:
+        """the hypotheses of the last closed_map_relocalise, in candidate order: dicts of keyframe, shift, skipped, dist, yaw,
+        prior, pose and the localise info"""
+        n = C.c_size_t(0)
+        self._check(self.L.tloam_closed_map_relocalise_hypotheses(self.h, 0, C.byref(n), None),
+                    "tloam_closed_map_relocalise_hypotheses")
+        if not n.value:
+            return []
+        hyp = (ClosedMapRelocaliseHypothesis * n.value)()
+        self._check(self.L.tloam_closed_map_relocalise_hypotheses(self.h, n.value, C.byref(n), hyp),
+                    "tloam_closed_map_relocalise_hypotheses")
+        return [x.as_dict() for x in hyp[: n.value]]
+
     def fitness(self):
         f, r = C.c_double(0), C.c_double(0)
         rc = self.L.tloam_fitness(self.h, C.byref(f), C.byref(r))
@@ -1649,6 +1753,11 @@ def default_closed_map_carve_config(**over) -> ClosedMapCarveConfig:
     """tloam_closed_map_carve_default_config (max_range 60, end_margin 1, radius 0.25, ray_mask 0: the build's) with keyword
     overrides, e.g. max_range=20.0, radius=float("inf")"""
     return _strict_config(ClosedMapCarveConfig, "tloam_closed_map_carve_default_config", over)
+
+
+def default_closed_map_relocalise_config(**over) -> ClosedMapRelocaliseConfig:
+    """tloam_closed_map_relocalise_default_config with keyword overrides."""
+    return _strict_config(ClosedMapRelocaliseConfig, "tloam_closed_map_relocalise_default_config", over)
 
 
 def default_closed_map_localise_config(**over) -> ClosedMapLocaliseConfig:
