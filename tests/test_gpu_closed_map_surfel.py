@@ -335,3 +335,56 @@ def test_lifecycle(hip_module):
         with invalid(reg):
             call()
     H.close()
+
+
+# ---- 7: the three box reads are one selection ------------------------------------------------------------------------------
+def test_the_three_box_reads_are_one_selection(hip_module):
+    """closed_map_read_box, _read_carved with a min_miss no voxel reaches and _read_surfels_box with its gate open run one
+    device body: the same voxels in the same order.  The ghost scene at 0.25 m is 762 voxels -- three blocks, the last of 250 --
+    and the box keeps voxels of every block, so the ticket order, the look-back chain and the last block's total all take part."""
+    import ctypes as C
+    poses, clouds, _, _ = CS.ghost_scene()
+    H, V = built(hip_module, poses, clouds, CS.MASK, 0.25)
+    H.closed_map_carve_configure(max_range=CS.GHOST["max_range"])
+    H.closed_map_carve()
+    H.closed_map_surfel_configure(min_points=3)
+    H.closed_map_surfels()
+    cen, cnt = H.closed_map_read()
+    _, ev, ns = H.closed_map_read_surfels()
+    M = H.closed_map_misses()
+    nv = len(cnt)
+    assert 512 < nv < 1024 and nv % 256 != 0
+    solved = (ns >= 3) & (ev[:, 2] > 0.0)
+    lo, hi, mc = np.array([1.0, 2.2, 0.9]), np.array([9.0, 5.2, 3.1]), 2
+    never, inf = 1 << 62, float("inf")
+    for box in (False, True):
+        keep = cnt >= mc
+        if box:
+            keep &= np.all((cen >= lo) & (cen <= hi), axis=1)
+        where = dict(lo=lo, hi=hi) if box else dict()
+        ids, ids_s = np.flatnonzero(keep), np.flatnonzero(keep & solved)
+        blocks = {int(i) // 256 for i in ids_s}
+        assert blocks == {0, 1, 2} and 0 < len(ids_s) < len(ids) < nv, box
+        carved = H.closed_map_read_carved(min_count=mc, min_miss=never, **where)
+        assert bits(carved[0]) == bits(cen[ids]) and carved[1].tobytes() == cnt[ids].tobytes(), box
+        assert carved[2].tobytes() == M[ids].tobytes(), box
+        if box:
+            plain = H.closed_map_read_box(lo, hi, mc)
+            assert bits(plain[0]) == bits(carved[0]) and plain[1].tobytes() == carved[1].tobytes()
+        surf = H.closed_map_read_surfels_box(min_count=mc, max_sigma=inf, min_planarity=-inf, **where)
+        assert bits(surf[0]) == bits(cen[ids_s]) and surf[3].tobytes() == ns[ids_s].tobytes(), box
+        assert bits(surf[0]) == bits(carved[0][solved[ids]]), box      # the carved read's voxels, the unsolved ones left out
+    # a capacity one short: INVALID, *n the size, nothing copied (the box is the last pass's: ids, ids_s)
+    dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))  # noqa: E731
+    out = np.full((len(ids), 3), 7.0)
+    n = C.c_size_t(0)
+    calls = ((ids, lambda cap: H.L.tloam_closed_map_read_box(H.h, dp(lo), dp(hi), mc, cap, C.byref(n), dp(out), None)),
+             (ids, lambda cap: H.L.tloam_closed_map_read_carved(H.h, dp(lo), dp(hi), mc, never, 1.0, cap, C.byref(n), dp(out), None,
+                                                                None)),
+             (ids_s, lambda cap: H.L.tloam_closed_map_read_surfels_box(H.h, dp(lo), dp(hi), mc, inf, -inf, cap, C.byref(n), dp(out),
+                                                                       None, None, None)))
+    for want, call in calls:
+        out[:] = 7.0
+        assert call(len(want) - 1) == -1 and n.value == len(want) and np.all(out == 7.0)
+        assert call(len(want)) == 0 and n.value == len(want) and bits(out[:len(want)]) == bits(cen[want])
+    H.close()

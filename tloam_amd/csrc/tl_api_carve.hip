@@ -26,40 +26,23 @@ int carve_body(tloam_ctx* c, tloam_closed_map_carve_info& I) {
   const int mask = M.carve_cfg.ray_mask ? M.carve_cfg.ray_mask : M.cfg.cloud_mask;
   std::vector<CmapSpan> spans;
   long long n = 0;
-  for (size_t k = 0; k < K && k < P.kf.size(); ++k)
-    for (int j = 0; j < 8; ++j) {
-      if (!((mask >> j) & 1) || P.kf[k].n[j] == 0) continue;
-      spans.push_back(CmapSpan{(long long)P.kf[k].off[j], n, (int)k, 0});
-      n += (long long)P.kf[k].n[j];
-    }
-  const int nspan = (int)spans.size();
-  spans.push_back(CmapSpan{0, n, 0, 0});   // (the end: span[nspan].start = n)
+  cmap_span_table(P, K, mask, &spans, &n, nullptr);
   const size_t nv = (size_t)M.info.n_voxels;
   HIPC(c, hipSetDevice(c->device));
   if (M.miss.cap < std::max<size_t>(nv, 1) || M.carve_ctl.cap < 8)
     HIPC(c, hipStreamSynchronize(c->stream));   // (the counts replaced may still be read)
   HIPC(c, M.miss.reserve(std::max<size_t>(nv, 1))); HIPC(c, M.carve_ctl.reserve(8));
-  DBuf<CmapSpan> dspan;   // the carve's own, freed with it (hipFree waits for the launches that use them)
-  DBuf<double> dpose;
-  HIPC(c, dspan.reserve(spans.size())); HIPC(c, dpose.reserve(std::max<size_t>(16 * K, 16)));
-  HIPC(c, hipMemcpyAsync(dspan.p, spans.data(), sizeof(CmapSpan) * spans.size(), hipMemcpyHostToDevice, c->stream));
-  if (K) HIPC(c, hipMemcpyAsync(dpose.p, M.poses.data(), sizeof(double) * 16 * K, hipMemcpyHostToDevice, c->stream));
+  SpanUpload up;   // the carve's own, freed with it
   CarveWork W;
   memset(&W, 0, sizeof(W));
-  W.arena = P.arena.p;
-  W.span = dspan.p;
-  W.nspan = nspan;
-  W.nkf = (int)K;
-  W.n = n;
-  W.pose = dpose.p;
+  const int rc = up.upload(c, spans, n, M.poses.data(), K, &W.in);
+  if (rc != TLOAM_OK) return rc;
   W.voxel = M.cfg.voxel;
   for (int a = 0; a < 3; ++a) W.origin[a] = M.cfg.origin[a];
   W.max_range = M.carve_cfg.max_range;
   W.end_margin = M.carve_cfg.end_margin;
   W.radius2 = M.carve_cfg.radius * M.carve_cfg.radius;
-  const VmapTable T = M.rows.table();
-  W.pmask = T.pmask; W.ptab = T.ptab; W.pkey = T.pkey;
-  W.pn = T.pn; W.pqx = T.pqx; W.pqy = T.pqy; W.pqz = T.pqz;
+  W.map = M.rows.view();
   W.nv = (long long)nv;
   W.miss = M.miss.p;
   W.ctl = M.carve_ctl.p;
@@ -127,13 +110,10 @@ int tloam_closed_map_carve(tloam_ctx* c, tloam_closed_map_carve_info* info) {
 }
 
 int tloam_closed_map_read_misses(tloam_ctx* c, size_t first, size_t count, int64_t* misses) {
-  if (!c || c->nranks > 1) return TLOAM_E_INVALID;
-  const CmapState& M = c->cmap;
-  if (!M.built || !M.carved) return TLOAM_E_NOT_READY;
-  const size_t nv = (size_t)M.info.n_voxels;
-  if (first > nv || count > nv - first) return TLOAM_E_INVALID;
-  if (count == 0) return TLOAM_OK;
+  const int rc = cmap_side_range(c, c && c->cmap.carved, first, count);
+  if (rc != TLOAM_OK || count == 0) return rc;
   if (!misses) return TLOAM_E_INVALID;
+  const CmapState& M = c->cmap;
   HIPC(c, hipSetDevice(c->device));
   HIPC(c, hipMemcpyAsync(misses, M.miss.p + first, sizeof(int64_t) * count, hipMemcpyDeviceToHost, c->stream));
   HIPC(c, hipStreamSynchronize(c->stream));
@@ -147,46 +127,18 @@ int tloam_closed_map_read_carved(tloam_ctx* c, const double* lo, const double* h
   if (!c || !n || (lo == nullptr) != (hi == nullptr) || c->nranks > 1) return TLOAM_E_INVALID;
   CmapState& M = c->cmap;
   if (!M.built || !M.carved) return TLOAM_E_NOT_READY;
-  const size_t nv = (size_t)M.info.n_voxels;
-  if (nv == 0) return TLOAM_OK;
-  HIPC(c, hipSetDevice(c->device));
-  HIPC(c, hipStreamSynchronize(c->stream));   // (the scratch may be replaced)
-  const size_t blocks = (nv + 255) / 256;
-  HIPC(c, M.rd_c.reserve(3 * nv)); HIPC(c, M.rd_n.reserve(nv)); HIPC(c, M.rd_m.reserve(nv));
-  HIPC(c, M.look.reserve(blocks + 1)); HIPC(c, M.ctl.reserve(8));
-  HIPC(c, hipMemsetAsync(M.look.p, 0, sizeof(unsigned long long) * (blocks + 1), c->stream));
-  HIPC(c, hipMemsetAsync(M.ctl.p, 0, sizeof(unsigned long long) * 8, c->stream));
   CarveReadArgs A;
-  A.rows = voxel_rows_of(M, nv, "closed map").base;
-  A.rows.first = 0; A.rows.count = nv;
-  for (int a = 0; a < 3; ++a) { A.rows.lo[a] = lo ? lo[a] : 0.0; A.rows.hi[a] = hi ? hi[a] : 0.0; }
-  A.rows.min_count = min_count;
-  A.rows.out_c = M.rd_c.p; A.rows.out_n = M.rd_n.p;
-  A.rows.look = M.look.p; A.rows.ctl = M.ctl.p;
   A.miss = (const long long*)M.miss.p;
   A.min_miss = min_miss;
   A.miss_ratio = miss_ratio;
-  A.out_m = M.rd_m.p;
   A.boxed = lo ? 1 : 0;
-  launch_carve_read(A, c->stream);
-  HIPC(c, hipGetLastError());
-  unsigned long long w[3];
-  HIPC(c, hipMemcpyAsync(w, M.ctl.p, sizeof(w), hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));
-  if (w[1]) {
-    c->last_error = "closed map: a look-back of k_carve_box timed out";
-    return TLOAM_E_HIP;
-  }
-  const size_t m = (size_t)w[2];
-  *n = m;
-  if (m == 0) return TLOAM_OK;
-  if (capacity < m) return TLOAM_E_INVALID;
-  const hipMemcpyKind D2H = hipMemcpyDeviceToHost;
-  if (centroids_aos) HIPC(c, hipMemcpyAsync(centroids_aos, M.rd_c.p, sizeof(double) * 3 * m, D2H, c->stream));
-  if (counts) HIPC(c, hipMemcpyAsync(counts, M.rd_n.p, sizeof(int64_t) * m, D2H, c->stream));
-  if (misses) HIPC(c, hipMemcpyAsync(misses, M.rd_m.p, sizeof(int64_t) * m, D2H, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));
-  return TLOAM_OK;
+  return voxel_rows_read_box(c, voxel_rows_of(M, (size_t)M.info.n_voxels, "closed map"), lo, hi, min_count, capacity, n,
+                             centroids_aos, counts, "k_carve_box", {BoxColumn{misses, &M.rd_m, 1, sizeof(int64_t)}},
+                             [&](const VmapReadArgs& rows) {
+                               A.rows = rows;
+                               A.out_m = (long long*)M.rd_m.p;
+                               launch_carve_read(A, c->stream);
+                             });
 }
 
 }  // extern "C"

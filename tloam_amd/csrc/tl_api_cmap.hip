@@ -1,5 +1,6 @@
 // tl_api_cmap.hip -- C ABI of the closed map (include/tloam_hip.h: tloam_closed_map_*; kernels in
-// tl_cmap.hip, reads by tlh::voxel_rows_read / _read_box of tl_api_vmap.hip).
+// tl_cmap.hip, reads by tlh::voxel_rows_read / _read_box).  The span table, its upload and the side arrays' range check that the
+// carve and the surfels share with the build are defined here (tlh::cmap_span_table, SpanUpload, cmap_side_range).
 //
 // A build takes the host's keyframe table (PlaceState::kf: where every stored cloud lies in the arena) and a pose per keyframe,
 // uploads one span table and the poses, and enqueues four launches on the context's stream -- behind any k_place_clouds still in
@@ -29,8 +30,7 @@ bool cmap_on(const tloam_ctx* c) { return c && c->nranks == 1 && place_clouds_on
 struct Staging {
   DBuf<unsigned long long> fkey, flead, fsum, look, ctl;
   DBuf<int> slot_of_pt, kf_over;
-  DBuf<CmapSpan> span;
-  DBuf<double> pose;
+  SpanUpload up;
 };
 
 // the rows hold `need` voxels; the closed map is being replaced, so nothing is copied
@@ -55,24 +55,13 @@ int build_body(tloam_ctx* c, const std::vector<double>& poses, tloam_closed_map_
   CmapState& M = c->cmap;
   const PlaceState& P = c->place;
   const size_t K = P.kf.size();
-  // the span table: keyframes ascending, a keyframe's selected clouds in slot order, empty clouds left out
   std::vector<CmapSpan> spans;
   long long n = 0;
-  for (size_t k = 0; k < K; ++k) {
-    const long long before = n;
-    for (int j = 0; j < 8; ++j) {
-      if (!((M.cfg.cloud_mask >> j) & 1) || P.kf[k].n[j] == 0) continue;
-      spans.push_back(CmapSpan{(long long)P.kf[k].off[j], n, (int)k, 0});
-      n += (long long)P.kf[k].n[j];
-    }
-    if (n == before) I.empty_keyframes++;
-  }
+  cmap_span_table(P, K, M.cfg.cloud_mask, &spans, &n, &I.empty_keyframes);
   if ((size_t)n > kCmapMaxPoints) {
     c->last_error = "closed map: more than 2^30 points";
     return TLOAM_E_HIP;
   }
-  const int nspan = (int)spans.size();
-  spans.push_back(CmapSpan{0, n, 0, 0});   // (the end: span[nspan].start = n)
   HIPC(c, hipSetDevice(c->device));
   int rc = rows_reserve(c, M.cfg.reserve_voxels > 0 ? (size_t)M.cfg.reserve_voxels : kCmapDefaultReserve);
   if (rc != TLOAM_OK) return rc;
@@ -80,21 +69,14 @@ int build_body(tloam_ctx* c, const std::vector<double>& poses, tloam_closed_map_
   const size_t m = std::max<size_t>((size_t)n, 1), T = voxel_table_size(m), blocks = (m + 255) / 256;
   HIPC(c, S.fkey.reserve(T)); HIPC(c, S.flead.reserve(T)); HIPC(c, S.fsum.reserve(4 * T)); HIPC(c, S.slot_of_pt.reserve(m));
   HIPC(c, S.look.reserve(blocks + 1)); HIPC(c, S.ctl.reserve(8)); HIPC(c, S.kf_over.reserve(std::max<size_t>(K, 1)));
-  HIPC(c, S.span.reserve(spans.size())); HIPC(c, S.pose.reserve(std::max<size_t>(16 * K, 16)));
-  const hipMemcpyKind H2D = hipMemcpyHostToDevice, D2H = hipMemcpyDeviceToHost;
-  HIPC(c, hipMemcpyAsync(S.span.p, spans.data(), sizeof(CmapSpan) * spans.size(), H2D, c->stream));
-  if (K) HIPC(c, hipMemcpyAsync(S.pose.p, poses.data(), sizeof(double) * 16 * K, H2D, c->stream));
+  const hipMemcpyKind D2H = hipMemcpyDeviceToHost;
   static const bool no_runs = getenv("TLOAM_CMAP_NO_RUNS") != nullptr;   // A/B of the wave's run aggregation
   CmapWork W;
   memset(&W, 0, sizeof(W));
-  W.arena = P.arena.p;
-  W.span = S.span.p;
-  W.nspan = nspan;
+  rc = S.up.upload(c, spans, n, poses.data(), K, &W.in);
+  if (rc != TLOAM_OK) return rc;
   W.runs = no_runs ? 0 : 1;
-  W.n = n;
-  W.pose = S.pose.p;
   W.kf_over = S.kf_over.p;
-  W.nkf = (int)K;
   W.voxel = M.cfg.voxel;
   for (int a = 0; a < 3; ++a) W.origin[a] = M.cfg.origin[a];
   W.fmask = T - 1;
@@ -134,6 +116,42 @@ int build_body(tloam_ctx* c, const std::vector<double>& poses, tloam_closed_map_
 }
 
 }  // namespace
+
+namespace tlh {
+
+void cmap_span_table(const PlaceState& P, size_t K, int mask, std::vector<CmapSpan>* spans, long long* n, int64_t* empty_keyframes) {
+  long long at = 0;
+  for (size_t k = 0; k < K && k < P.kf.size(); ++k) {
+    const long long before = at;
+    for (int j = 0; j < 8; ++j) {
+      if (!((mask >> j) & 1) || P.kf[k].n[j] == 0) continue;
+      spans->push_back(CmapSpan{(long long)P.kf[k].off[j], at, (int)k, 0});
+      at += (long long)P.kf[k].n[j];
+    }
+    if (at == before && empty_keyframes) ++*empty_keyframes;
+  }
+  spans->push_back(CmapSpan{0, at, 0, 0});   // (the end: span[nspan].start = n)
+  *n = at;
+}
+
+int SpanUpload::upload(tloam_ctx* c, const std::vector<CmapSpan>& spans, long long n, const double* poses, size_t K, SpanInput* in) {
+  HIPC(c, span.reserve(spans.size())); HIPC(c, pose.reserve(std::max<size_t>(16 * K, 16)));
+  HIPC(c, hipMemcpyAsync(span.p, spans.data(), sizeof(CmapSpan) * spans.size(), hipMemcpyHostToDevice, c->stream));
+  if (K) HIPC(c, hipMemcpyAsync(pose.p, poses, sizeof(double) * 16 * K, hipMemcpyHostToDevice, c->stream));
+  *in = SpanInput{c->place.arena.p, span.p, (int)spans.size() - 1, (int)K, n, pose.p};
+  return TLOAM_OK;
+}
+
+int cmap_side_range(const tloam_ctx* c, bool ran, size_t first, size_t count) {
+  if (!c || c->nranks > 1) return TLOAM_E_INVALID;
+  const CmapState& M = c->cmap;
+  if (!M.built || !ran) return TLOAM_E_NOT_READY;
+  const size_t nv = (size_t)M.info.n_voxels;
+  if (first > nv || count > nv - first) return TLOAM_E_INVALID;
+  return TLOAM_OK;
+}
+
+}  // namespace tlh
 
 extern "C" {
 
@@ -231,7 +249,8 @@ int tloam_closed_map_read_box(tloam_ctx* c, const double lo[3], const double hi[
   CmapState& M = c->cmap;
   if (!M.built) return TLOAM_E_NOT_READY;
   return voxel_rows_read_box(c, voxel_rows_of(M, (size_t)M.info.n_voxels, "closed map"), lo, hi, min_count, capacity, n,
-                             centroids_aos, counts);
+                             centroids_aos, counts, "k_vmap_box", {},
+                             [&](const VmapReadArgs& A) { launch_vmap_read_box(A, c->stream); });
 }
 
 int tloam_closed_map_read_poses(tloam_ctx* c, size_t first, size_t count, double* poses) {

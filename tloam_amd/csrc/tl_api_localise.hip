@@ -48,7 +48,7 @@ int loc_begin(tloam_ctx* c, const double* points_aos, size_t n, bool ids, bool r
   if (!M.loc_ready) {
     LocPrepArgs A;
     memset(&A, 0, sizeof(A));
-    A.pkey = M.rows.key.p; A.pn = M.rows.n.p; A.pqx = M.rows.qx.p; A.pqy = M.rows.qy.p; A.pqz = M.rows.qz.p;
+    A.map = M.rows.view();
     A.sums = M.surfel_sums.p; A.normal = M.surfel_nrm.p; A.eval = M.surfel_ev.p;
     A.nv = (long long)nv;
     A.voxel = M.cfg.voxel;
@@ -72,8 +72,7 @@ LocSweepArgs sweep_args(const CmapState& M, size_t n, int* ids, double* res) {
   W.st = M.loc_state.p;
   W.voxel = M.cfg.voxel;
   for (int a = 0; a < 3; ++a) W.origin[a] = M.cfg.origin[a];
-  const VmapTable T = M.rows.table();
-  W.pmask = T.pmask; W.ptab = T.ptab; W.pkey = T.pkey;
+  W.map = M.rows.view();
   W.nv = (long long)M.info.n_voxels;
   W.rec = M.loc_rec.p;
   W.partial = M.loc_partial.p;

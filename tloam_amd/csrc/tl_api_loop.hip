@@ -34,23 +34,6 @@ bool loop_config_ok(const tloam_loop_config& L) {
          L.reserve_points >= 0 && L.reserve_points <= (int64_t)kMaxPoints && tls_config_ok(L.coarse);
 }
 
-// the operation order of tl_api_odom.hip's mat_mul / rigid_inverse (column-major 4x4)
-void mat_mul(const double A[16], const double B[16], double out[16]) {
-  double r[16];
-  for (int j = 0; j < 4; ++j)
-    for (int i = 0; i < 4; ++i) r[4 * j + i] = ((A[i] * B[4 * j] + A[4 + i] * B[4 * j + 1]) + A[8 + i] * B[4 * j + 2]) + A[12 + i] * B[4 * j + 3];
-  memcpy(out, r, sizeof(r));
-}
-void rigid_inverse(const double T[16], double out[16]) {
-  double r[16];
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j) r[4 * j + i] = T[4 * i + j];
-    r[12 + i] = -((T[4 * i] * T[12] + T[4 * i + 1] * T[13]) + T[4 * i + 2] * T[14]);
-    r[4 * i + 3] = 0.0;
-  }
-  r[15] = 1.0;
-  memcpy(out, r, sizeof(r));
-}
 void rigid_rows(const double T[16], double R[9], double t[3]) {   // column-major 4x4 -> row-major R, t
   for (int i = 0; i < 3; ++i) {
     for (int j = 0; j < 3; ++j) R[3 * i + j] = T[4 * j + i];

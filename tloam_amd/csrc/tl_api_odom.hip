@@ -13,23 +13,6 @@ using namespace tl;
 
 namespace {
 
-void mat_mul(const double A[16], const double B[16], double out[16]) {   // column-major 4x4, sums over k in ascending order
-  double r[16];
-  for (int j = 0; j < 4; ++j)
-    for (int i = 0; i < 4; ++i) r[4 * j + i] = ((A[i] * B[4 * j] + A[4 + i] * B[4 * j + 1]) + A[8 + i] * B[4 * j + 2]) + A[12 + i] * B[4 * j + 3];
-  memcpy(out, r, sizeof(r));
-}
-void rigid_inverse(const double T[16], double out[16]) {   // Eigen::Isometry3d::inverse: (R^T, -R^T t)
-  double r[16];
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j) r[4 * j + i] = T[4 * i + j];
-    r[12 + i] = -((T[4 * i] * T[12] + T[4 * i + 1] * T[13]) + T[4 * i + 2] * T[14]);
-    r[4 * i + 3] = 0.0;
-  }
-  r[15] = 1.0;
-  memcpy(out, r, sizeof(r));
-}
-
 bool odom_config_ok(const tloam_odom_config& c) {
   return tlh::seg_config_ok(c.seg) && c.feature.K >= 3 && c.feature.K <= 20 && c.feature.radius >= 0.0 &&
          tlh::submap_config_ok(c.submap) && c.edge_down_sample > 0.0;

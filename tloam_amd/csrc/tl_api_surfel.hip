@@ -19,40 +19,24 @@ int surfel_body(tloam_ctx* c, tloam_closed_map_surfel_info& I) {
   CmapState& M = c->cmap;
   const PlaceState& P = c->place;
   const size_t K = M.poses.size() / 16;   // the build's keyframes: later ones add nothing
-  std::vector<CmapSpan> spans;            // the build's span table: keyframes ascending, the build's clouds in slot order
+  std::vector<CmapSpan> spans;            // the build's span table
   long long n = 0;
-  for (size_t k = 0; k < K && k < P.kf.size(); ++k)
-    for (int j = 0; j < 8; ++j) {
-      if (!((M.cfg.cloud_mask >> j) & 1) || P.kf[k].n[j] == 0) continue;
-      spans.push_back(CmapSpan{(long long)P.kf[k].off[j], n, (int)k, 0});
-      n += (long long)P.kf[k].n[j];
-    }
-  const int nspan = (int)spans.size();
-  spans.push_back(CmapSpan{0, n, 0, 0});   // (the end: span[nspan].start = n)
+  cmap_span_table(P, K, M.cfg.cloud_mask, &spans, &n, nullptr);
   const size_t nv = (size_t)M.info.n_voxels, cap = std::max<size_t>(M.rows.cap, 1);
   HIPC(c, hipSetDevice(c->device));
   if (M.surfel_sums.cap < kSurfelSums * cap || M.surfel_over.cap < std::max<size_t>(K, 1) || M.surfel_ctl.cap < 8)
     HIPC(c, hipStreamSynchronize(c->stream));   // (the arrays replaced may still be read)
   HIPC(c, M.surfel_sums.reserve(kSurfelSums * cap)); HIPC(c, M.surfel_nrm.reserve(3 * cap)); HIPC(c, M.surfel_ev.reserve(3 * cap));
   HIPC(c, M.surfel_over.reserve(std::max<size_t>(K, 1))); HIPC(c, M.surfel_ctl.reserve(8));
-  DBuf<CmapSpan> dspan;   // the pass's own, freed with it (hipFree waits for the launches that use them)
-  DBuf<double> dpose;
-  HIPC(c, dspan.reserve(spans.size())); HIPC(c, dpose.reserve(std::max<size_t>(16 * K, 16)));
-  HIPC(c, hipMemcpyAsync(dspan.p, spans.data(), sizeof(CmapSpan) * spans.size(), hipMemcpyHostToDevice, c->stream));
-  if (K) HIPC(c, hipMemcpyAsync(dpose.p, M.poses.data(), sizeof(double) * 16 * K, hipMemcpyHostToDevice, c->stream));
+  SpanUpload up;   // the pass's own, freed with it
   SurfelWork W;
   memset(&W, 0, sizeof(W));
-  W.arena = P.arena.p;
-  W.span = dspan.p;
-  W.nspan = nspan;
-  W.nkf = (int)K;
-  W.n = n;
-  W.pose = dpose.p;
+  const int rc = up.upload(c, spans, n, M.poses.data(), K, &W.in);
+  if (rc != TLOAM_OK) return rc;
   W.kf_over = M.surfel_over.p;
   W.voxel = M.cfg.voxel;
   for (int a = 0; a < 3; ++a) W.origin[a] = M.cfg.origin[a];
-  const VmapTable T = M.rows.table();
-  W.pmask = T.pmask; W.ptab = T.ptab; W.pkey = T.pkey;
+  W.map = M.rows.view();
   W.nv = (long long)nv;
   W.runs = getenv("TLOAM_SURFEL_NO_RUNS") ? 0 : 1;   // A/B of the wave's run aggregation, read per pass
   W.min_points = M.surfel_cfg.min_points;
@@ -69,16 +53,6 @@ int surfel_body(tloam_ctx* c, tloam_closed_map_surfel_info& I) {
   I.n_points = (int64_t)ctl[0];
   I.orphan_points = (int64_t)ctl[1];
   I.solved_voxels = (int64_t)ctl[2];
-  return TLOAM_OK;
-}
-
-// ids [first, first + count) of the built map with surfels: TLOAM_OK when the range is one
-int surfel_range(const tloam_ctx* c, size_t first, size_t count) {
-  if (!c || c->nranks > 1) return TLOAM_E_INVALID;
-  const CmapState& M = c->cmap;
-  if (!M.built || !M.surfeled) return TLOAM_E_NOT_READY;
-  const size_t nv = (size_t)M.info.n_voxels;
-  if (first > nv || count > nv - first) return TLOAM_E_INVALID;
   return TLOAM_OK;
 }
 
@@ -128,7 +102,7 @@ int tloam_closed_map_surfels(tloam_ctx* c, tloam_closed_map_surfel_info* info) {
 }
 
 int tloam_closed_map_read_moments(tloam_ctx* c, size_t first, size_t count, int64_t* out) {
-  const int rc = surfel_range(c, first, count);
+  const int rc = cmap_side_range(c, c && c->cmap.surfeled, first, count);
   if (rc != TLOAM_OK || count == 0) return rc;
   if (!out) return TLOAM_E_INVALID;
   const CmapState& M = c->cmap;
@@ -140,7 +114,7 @@ int tloam_closed_map_read_moments(tloam_ctx* c, size_t first, size_t count, int6
 }
 
 int tloam_closed_map_read_surfels(tloam_ctx* c, size_t first, size_t count, double* normals_aos, double* evals_aos, int64_t* counts) {
-  const int rc = surfel_range(c, first, count);
+  const int rc = cmap_side_range(c, c && c->cmap.surfeled, first, count);
   if (rc != TLOAM_OK || count == 0) return rc;
   const CmapState& M = c->cmap;
   const hipMemcpyKind D2H = hipMemcpyDeviceToHost;
@@ -163,22 +137,7 @@ int tloam_closed_map_read_surfels_box(tloam_ctx* c, const double* lo, const doub
   if (!c || !n || (lo == nullptr) != (hi == nullptr) || c->nranks > 1) return TLOAM_E_INVALID;
   CmapState& M = c->cmap;
   if (!M.built || !M.surfeled) return TLOAM_E_NOT_READY;
-  const size_t nv = (size_t)M.info.n_voxels;
-  if (nv == 0) return TLOAM_OK;
-  HIPC(c, hipSetDevice(c->device));
-  HIPC(c, hipStreamSynchronize(c->stream));   // (the scratch may be replaced)
-  const size_t blocks = (nv + 255) / 256;
-  HIPC(c, M.rd_c.reserve(3 * nv)); HIPC(c, M.rd_n.reserve(nv)); HIPC(c, M.rd_nrm.reserve(3 * nv)); HIPC(c, M.rd_ev.reserve(3 * nv));
-  HIPC(c, M.look.reserve(blocks + 1)); HIPC(c, M.ctl.reserve(8));
-  HIPC(c, hipMemsetAsync(M.look.p, 0, sizeof(unsigned long long) * (blocks + 1), c->stream));
-  HIPC(c, hipMemsetAsync(M.ctl.p, 0, sizeof(unsigned long long) * 8, c->stream));
   SurfelReadArgs A;
-  A.rows = voxel_rows_of(M, nv, "closed map").base;
-  A.rows.first = 0; A.rows.count = nv;
-  for (int a = 0; a < 3; ++a) { A.rows.lo[a] = lo ? lo[a] : 0.0; A.rows.hi[a] = hi ? hi[a] : 0.0; }
-  A.rows.min_count = min_count;
-  A.rows.out_c = M.rd_c.p; A.rows.out_n = M.rd_n.p;
-  A.rows.look = M.look.p; A.rows.ctl = M.ctl.p;
   A.sums = M.surfel_sums.p;
   A.normal = M.surfel_nrm.p;
   A.eval = M.surfel_ev.p;
@@ -186,27 +145,14 @@ int tloam_closed_map_read_surfels_box(tloam_ctx* c, const double* lo, const doub
   A.boxed = lo ? 1 : 0;
   A.max_sigma2 = max_sigma * max_sigma;
   A.min_planarity = min_planarity;
-  A.out_nrm = M.rd_nrm.p; A.out_ev = M.rd_ev.p;
-  launch_surfel_read(A, c->stream);
-  HIPC(c, hipGetLastError());
-  unsigned long long w[3];
-  HIPC(c, hipMemcpyAsync(w, M.ctl.p, sizeof(w), hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));
-  if (w[1]) {
-    c->last_error = "closed map: a look-back of k_surfel_box timed out";
-    return TLOAM_E_HIP;
-  }
-  const size_t m = (size_t)w[2];
-  *n = m;
-  if (m == 0) return TLOAM_OK;
-  if (capacity < m) return TLOAM_E_INVALID;
-  const hipMemcpyKind D2H = hipMemcpyDeviceToHost;
-  if (centroids_aos) HIPC(c, hipMemcpyAsync(centroids_aos, M.rd_c.p, sizeof(double) * 3 * m, D2H, c->stream));
-  if (normals_aos) HIPC(c, hipMemcpyAsync(normals_aos, M.rd_nrm.p, sizeof(double) * 3 * m, D2H, c->stream));
-  if (evals_aos) HIPC(c, hipMemcpyAsync(evals_aos, M.rd_ev.p, sizeof(double) * 3 * m, D2H, c->stream));
-  if (counts) HIPC(c, hipMemcpyAsync(counts, M.rd_n.p, sizeof(int64_t) * m, D2H, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));
-  return TLOAM_OK;
+  return voxel_rows_read_box(c, voxel_rows_of(M, (size_t)M.info.n_voxels, "closed map"), lo, hi, min_count, capacity, n,
+                             centroids_aos, counts, "k_surfel_box",
+                             {BoxColumn{normals_aos, &M.rd_nrm, 3, sizeof(double)}, BoxColumn{evals_aos, &M.rd_ev, 3, sizeof(double)}},
+                             [&](const VmapReadArgs& rows) {
+                               A.rows = rows;
+                               A.out_nrm = (double*)M.rd_nrm.p; A.out_ev = (double*)M.rd_ev.p;
+                               launch_surfel_read(A, c->stream);
+                             });
 }
 
 }  // extern "C"

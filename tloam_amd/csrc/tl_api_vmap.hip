@@ -173,42 +173,6 @@ int voxel_rows_read(tloam_ctx* c, const VoxelRows& R, size_t first, size_t count
   return TLOAM_OK;
 }
 
-int voxel_rows_read_box(tloam_ctx* c, const VoxelRows& R, const double lo[3], const double hi[3], int64_t min_count, size_t capacity,
-                        size_t* n, double* centroids_aos, int64_t* counts) {
-  const size_t nv = R.nv;
-  if (nv == 0) return TLOAM_OK;
-  HIPC(c, hipSetDevice(c->device));
-  HIPC(c, hipStreamSynchronize(c->stream));   // (the scratch may be replaced)
-  const size_t blocks = (nv + 255) / 256;
-  HIPC(c, R.rd_c.reserve(3 * nv)); HIPC(c, R.rd_n.reserve(nv));
-  HIPC(c, R.look.reserve(blocks + 1)); HIPC(c, R.ctl.reserve(8));
-  HIPC(c, hipMemsetAsync(R.look.p, 0, sizeof(unsigned long long) * (blocks + 1), c->stream));
-  HIPC(c, hipMemsetAsync(R.ctl.p, 0, sizeof(unsigned long long) * 8, c->stream));
-  VmapReadArgs A = R.base;
-  A.first = 0; A.count = nv;
-  for (int a = 0; a < 3; ++a) { A.lo[a] = lo[a]; A.hi[a] = hi[a]; }
-  A.min_count = min_count;
-  A.out_c = R.rd_c.p; A.out_n = R.rd_n.p;
-  A.look = R.look.p; A.ctl = R.ctl.p;
-  launch_vmap_read_box(A, c->stream);
-  unsigned long long w[3];
-  HIPC(c, hipMemcpyAsync(w, R.ctl.p, sizeof(w), hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));
-  if (w[1]) {
-    c->last_error = std::string(R.name) + ": a look-back of k_vmap_box timed out";
-    return TLOAM_E_HIP;
-  }
-  const size_t m = (size_t)w[2];
-  *n = m;
-  if (m == 0) return TLOAM_OK;
-  if (capacity < m) return TLOAM_E_INVALID;
-  if (centroids_aos)
-    HIPC(c, hipMemcpyAsync(centroids_aos, R.rd_c.p, sizeof(double) * 3 * m, hipMemcpyDeviceToHost, c->stream));
-  if (counts) HIPC(c, hipMemcpyAsync(counts, R.rd_n.p, sizeof(int64_t) * m, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));
-  return TLOAM_OK;
-}
-
 }  // namespace tlh
 
 extern "C" {
@@ -274,7 +238,8 @@ int tloam_voxel_map_read_box(tloam_ctx* c, const double lo[3], const double hi[3
   if (n) *n = 0;
   if (!c || !lo || !hi || !n || c->nranks > 1) return TLOAM_E_INVALID;
   return voxel_rows_read_box(c, voxel_rows_of(c->vmap, (size_t)c->vmap.n_voxels, "voxel map"), lo, hi, min_count, capacity, n,
-                             centroids_aos, counts);
+                             centroids_aos, counts, "k_vmap_box", {},
+                             [&](const VmapReadArgs& A) { launch_vmap_read_box(A, c->stream); });
 }
 
 }  // extern "C"

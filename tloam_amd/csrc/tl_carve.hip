@@ -3,12 +3,12 @@
 //
 // Launches of a carve, the same three for any number of keyframes, spans and rays (no host synchronisation between them):
 //   k_carve_clear   grid x 256   zeroes M and the control words
-//   k_carve_rays    grid x 256   per ray: its span from its global index (as k_cmap_flag), transform, the walk through the grid's
-//                                cells, every visited cell looked up in the closed map's slot table (read only), the miss test
+//   k_carve_rays    grid x 256   per ray: its span from its global index, transform (span_point), the walk through the grid's
+//                                cells, every visited cell looked up in the closed map's slot table (id_table_find), the miss test
 //                                against an occupied cell's centroid, an int64 atomic add on its M; the ray's counters summed
 //                                over the wave by shuffles, one atomic per counter and wave
 //   k_carve_count   grid x 256   per voxel: M > 0 counted by ballot, one atomic per wave
-// The carved read is k_carve_box: k_vmap_box's selection, order and compaction, with the voxels seen through left out.
+// The carved read is k_carve_box: the box read's one body (tl_voxel.hpp: voxel_box_body), with the voxels seen through left out.
 //
 // Compiled with -ffp-contract=off.  The operation order of a ray (tests/closed_map_carve_np.py restates it), per axis a:
 //   O_a = P[12 + a],  E = map_transform_point(P, p),  D_a = E_a - O_a,  DD = (Dx*Dx + Dy*Dy) + Dz*Dz,  L = sqrt(DD)
@@ -32,15 +32,6 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
   return v;
 }
 
-// the id of the closed map's voxel `key`, -1 when it has none
-__device__ __forceinline__ int carve_find(const CarveWork& W, unsigned long long key) {
-  for (unsigned long long t = mix64(key) & W.pmask;; t = (t + 1) & W.pmask) {
-    const int id = W.ptab[t];
-    if (id < 0) return -1;
-    if (W.pkey[id] == key) return id;
-  }
-}
-
 __global__ __launch_bounds__(256) void k_carve_clear(CarveWork W) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
   for (size_t t = i; t < (size_t)W.nv; t += stride) W.miss[t] = 0ull;
@@ -49,17 +40,16 @@ __global__ __launch_bounds__(256) void k_carve_clear(CarveWork W) {
 
 __global__ __launch_bounds__(256) void k_carve_rays(CarveWork W) {
   __shared__ int s_span[2];
-  block_spans(W, s_span);
+  block_spans(W.in, s_span);
   const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
   const double kInf = __builtin_huge_val(), kLimit = (double)(1ll << kVmapBits);
   unsigned long long skipped = 0ull, steps = 0ull, tested = 0ull, misses = 0ull;
-  if (g < W.n) {
-    const CmapSpan S = W.span[span_of(W.span, s_span[0], s_span[1], g)];
-    const double* x = W.arena + S.off + 3 * (g - S.start);
-    const double* P = W.pose + 16 * (size_t)S.kf;
-    const double Ox = P[12], Oy = P[13], Oz = P[14];
-    double Ex, Ey, Ez;
-    map_transform_point(P, x[0], x[1], x[2], &Ex, &Ey, &Ez);
+  if (g < W.in.n) {
+    int kf;
+    const double* P;
+    double E[3];
+    span_point(W.in, g, s_span[0], s_span[1], &kf, &P, E);
+    const double Ox = P[12], Oy = P[13], Oz = P[14], Ex = E[0], Ey = E[1], Ez = E[2];
     const double Dx = Ex - Ox, Dy = Ey - Oy, Dz = Ez - Oz;
     const double DD = (Dx * Dx + Dy * Dy) + Dz * Dz;
     const double L = sqrt(DD);
@@ -88,13 +78,13 @@ __global__ __launch_bounds__(256) void k_carve_rays(CarveWork W) {
         const unsigned long long key = (unsigned long long)(cx + (1 << kVmapBits)) |
                                        ((unsigned long long)(cy + (1 << kVmapBits)) << 21) |
                                        ((unsigned long long)(cz + (1 << kVmapBits)) << 42);
-        const int id = carve_find(W, key);
+        const int id = id_table_find(W.map.ptab, W.map.pmask, W.map.pkey, key);
         if (id >= 0) {
           tested++;
-          const long long N = W.pn[id];
-          const double ux = centroid(W.origin[0], W.voxel, cx, W.pqx[id], N) - Ox;
-          const double uy = centroid(W.origin[1], W.voxel, cy, W.pqy[id], N) - Oy;
-          const double uz = centroid(W.origin[2], W.voxel, cz, W.pqz[id], N) - Oz;
+          const long long N = W.map.pn[id];
+          const double ux = centroid(W.origin[0], W.voxel, cx, W.map.pqx[id], N) - Ox;
+          const double uy = centroid(W.origin[1], W.voxel, cy, W.map.pqy[id], N) - Oy;
+          const double uz = centroid(W.origin[2], W.voxel, cz, W.map.pqz[id], N) - Oz;
           const double tt = ((ux * Dx + uy * Dy) + uz * Dz) / DD;
           const double wx = ux - tt * Dx, wy = uy - tt * Dy, wz = uz - tt * Dz;
           if (0.0 <= tt && tt < tlim && (wx * wx + wy * wy) + wz * wz <= W.radius2) {
@@ -132,59 +122,35 @@ __global__ __launch_bounds__(256) void k_carve_count(CarveWork W) {
   if ((threadIdx.x & 63) == 0 && bal) atomicAdd(&W.ctl[4], (unsigned long long)__popcll(bal));
 }
 
-// the voxels of k_vmap_box's selection (the box only when A.boxed) that were not seen through, compacted in id order
+// the box read (the box only when A.boxed) with the voxels seen through left out; their misses beside the counts
+struct BoxCarved {
+  const CarveReadArgs& A;
+  __device__ __forceinline__ bool keep(size_t id, long long n, const double*) const {
+    const long long m = A.miss[id];
+    return !(m >= A.min_miss && (double)m > A.miss_ratio * (double)n);
+  }
+  __device__ __forceinline__ long long emit(size_t id, size_t p, long long n) const {
+    if (A.out_m) A.out_m[p] = A.miss[id];
+    return n;
+  }
+};
 __global__ __launch_bounds__(256) void k_carve_box(CarveReadArgs A, int nblocks) {
-  __shared__ unsigned long long s_wave[4];
-  __shared__ unsigned long long s_prefix;
-  __shared__ int s_bid;
-  const VmapReadArgs& R = A.rows;
-  const int tid = threadIdx.x;
-  const int bid = block_ticket(&R.ctl[0], &s_bid);
-  const size_t id = (size_t)bid * 256 + tid;
-  double c[3] = {0.0, 0.0, 0.0};
-  long long n = 0, m = 0;
-  bool sel = false;
-  if (id < R.count) {
-    const unsigned long long key = R.pkey[id];
-    const long long Q[3] = {R.pqx[id], R.pqy[id], R.pqz[id]};
-    n = R.pn[id];
-    m = A.miss[id];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) c[a] = centroid(R.origin[a], R.voxel, key_axis(key, a), Q[a], n);
-    sel = n >= R.min_count;
-    if (A.boxed) {
-#pragma unroll
-      for (int a = 0; a < 3; ++a) sel = sel && c[a] >= R.lo[a] && c[a] <= R.hi[a];
-    }
-    sel = sel && !(m >= A.min_miss && (double)m > A.miss_ratio * (double)n);
-  }
-  int pos, total;
-  block_flag_scan(sel, s_wave, &pos, &total);
-  if (tid == 0) s_prefix = lookback_prefix(R.look, bid, (unsigned long long)total, LookFaultDevice{&R.ctl[1]});
-  __syncthreads();
-  if (sel) {
-    const size_t p = (size_t)(s_prefix + pos);
-    if (R.out_c) { R.out_c[3 * p] = c[0]; R.out_c[3 * p + 1] = c[1]; R.out_c[3 * p + 2] = c[2]; }
-    if (R.out_n) R.out_n[p] = n;
-    if (A.out_m) A.out_m[p] = m;
-  }
-  if (bid == nblocks - 1 && tid == 0) R.ctl[2] = s_prefix + total;
+  voxel_box_body(A.rows, A.boxed != 0, nblocks, BoxCarved{A});
 }
-
-inline unsigned blocks_of(long long n) { return (unsigned)std::max<long long>((n + 255) / 256, 1); }   // (nothing still launches)
 
 }  // namespace
 
 int launch_carve(const CarveWork& W, hipStream_t s) {
-  hipLaunchKernelGGL(k_carve_clear, dim3(std::min(blocks_of(W.nv), 2048u)), dim3(256), 0, s, W);
-  hipLaunchKernelGGL(k_carve_rays, dim3(blocks_of(W.n)), dim3(256), 0, s, W);
-  hipLaunchKernelGGL(k_carve_count, dim3(blocks_of(W.nv)), dim3(256), 0, s, W);
+  const unsigned nv_blocks = blocks_of((size_t)std::max<long long>(W.nv, 1));   // (nothing still launches)
+  hipLaunchKernelGGL(k_carve_clear, dim3(std::min(nv_blocks, 2048u)), dim3(256), 0, s, W);
+  hipLaunchKernelGGL(k_carve_rays, dim3(blocks_of((size_t)std::max<long long>(W.in.n, 1))), dim3(256), 0, s, W);
+  hipLaunchKernelGGL(k_carve_count, dim3(nv_blocks), dim3(256), 0, s, W);
   return 3;
 }
 
 void launch_carve_read(const CarveReadArgs& A, hipStream_t s) {
   if (A.rows.count == 0) return;
-  const int nb = (int)blocks_of((long long)A.rows.count);
+  const int nb = (int)blocks_of(A.rows.count);
   hipLaunchKernelGGL(k_carve_box, dim3(nb), dim3(256), 0, s, A, nb);
 }
 

@@ -20,14 +20,12 @@
 namespace tl {
 namespace {
 
-// point g (< W.n): its keyframe, and where it falls in the grid (key and q when inside)
-__device__ __forceinline__ VmapCell cmap_point(const CmapWork& W, long long g, int s_lo, int s_hi, int* kf, unsigned long long* key,
+// point g (< W.in.n): its keyframe, and where it falls in the grid (key and q when inside)
+__device__ __forceinline__ VmapCell cmap_point(const CmapWork& W, long long g, const int s_span[2], int* kf, unsigned long long* key,
                                                unsigned q[3]) {
-  const CmapSpan S = W.span[span_of(W.span, s_lo, s_hi, g)];
-  const double* x = W.arena + S.off + 3 * (g - S.start);
-  *kf = S.kf;
+  const double* P;
   double p[3];
-  map_transform_point(W.pose + 16 * (size_t)S.kf, x[0], x[1], x[2], &p[0], &p[1], &p[2]);
+  span_point(W.in, g, s_span[0], s_span[1], kf, &P, p);
   return vmap_quantise(p, W.origin, W.voxel, key, q);
 }
 
@@ -40,19 +38,19 @@ __global__ __launch_bounds__(256) void k_cmap_clear(CmapWork W, long long emit_b
     W.fsum[t] = 0ull; W.fsum[T + t] = 0ull; W.fsum[2 * T + t] = 0ull; W.fsum[3 * T + t] = 0ull;
   }
   for (size_t t = i; t <= (size_t)emit_blocks; t += stride) W.look[t] = 0ull;
-  for (size_t t = i; t < (size_t)W.nkf; t += stride) W.kf_over[t] = 0;
+  for (size_t t = i; t < (size_t)W.in.nkf; t += stride) W.kf_over[t] = 0;
   if (i < 8) W.ctl[i] = 0ull;
 }
 
 __global__ __launch_bounds__(256) void k_cmap_flag(CmapWork W) {
   __shared__ int s_span[2];
-  block_spans(W, s_span);
+  block_spans(W.in, s_span);
   const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (g >= W.n) return;
+  if (g >= W.in.n) return;
   int kf;
   unsigned long long key;
   unsigned q[3];
-  if (cmap_point(W, g, s_span[0], s_span[1], &kf, &key, q) == kVmapBeyond) W.kf_over[kf] = 1;
+  if (cmap_point(W, g, s_span, &kf, &key, q) == kVmapBeyond) W.kf_over[kf] = 1;
 }
 
 // one point's voxel entered in the build table: its slot; *fresh when the voxel was not there
@@ -65,15 +63,15 @@ __device__ __forceinline__ int cmap_enter(const CmapWork& W, unsigned long long 
 template <bool kRuns>
 __global__ __launch_bounds__(256) void k_cmap_stage(CmapWork W) {
   __shared__ int s_span[2];
-  block_spans(W, s_span);
+  block_spans(W.in, s_span);
   const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
   const int lane = threadIdx.x & 63;
   bool ok = false, fresh = false;
   unsigned long long key = 0ull;
   unsigned q[3] = {0u, 0u, 0u};
-  if (g < W.n) {
+  if (g < W.in.n) {
     int kf;
-    ok = cmap_point(W, g, s_span[0], s_span[1], &kf, &key, q) == kVmapInside && W.kf_over[kf] == 0;
+    ok = cmap_point(W, g, s_span, &kf, &key, q) == kVmapInside && W.kf_over[kf] == 0;
   }
   const unsigned long long okb = __ballot(ok);
   const size_t T = (size_t)W.fmask + 1;
@@ -93,7 +91,7 @@ __global__ __launch_bounds__(256) void k_cmap_stage(CmapWork W) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) atomicAdd(&W.fsum[(k + 1) * T + slot], (unsigned long long)q[k]);
   }
-  if (g < W.n) W.slot_of_pt[g] = ok ? slot : -1;
+  if (g < W.in.n) W.slot_of_pt[g] = ok ? slot : -1;
   const unsigned long long freshb = __ballot(fresh);
   if (lane == 0 && okb) {
     atomicAdd(&W.ctl[1], (unsigned long long)__popcll(okb));
@@ -110,7 +108,7 @@ __global__ __launch_bounds__(256) void k_cmap_emit(CmapWork W, long long nblocks
   const int tid = threadIdx.x;
   const long long bid = block_ticket(&W.ctl[2], &s_bid);
   const long long g = bid * 256 + tid;
-  const int h = g < W.n ? W.slot_of_pt[g] : -1;
+  const int h = g < W.in.n ? W.slot_of_pt[g] : -1;
   const bool leader = h >= 0 && W.flead[h] == (unsigned long long)g;
   int pos, total;
   block_flag_scan(leader, s_wave, &pos, &total);
@@ -131,14 +129,11 @@ __global__ __launch_bounds__(256) void k_cmap_emit(CmapWork W, long long nblocks
   if (bid == nblocks - 1 && tid == 0) W.ctl[4] = s_prefix + (unsigned long long)total;
 }
 
-inline long long blocks_of(long long n) { return std::max<long long>((n + 255) / 256, 1); }   // (an empty build still launches)
-
 }  // namespace
 
 int launch_cmap_stage(const CmapWork& W, hipStream_t s) {
-  const long long nb = blocks_of(W.n);
-  const size_t T = (size_t)W.fmask + 1;
-  hipLaunchKernelGGL(k_cmap_clear, dim3((unsigned)std::min<size_t>((T + 255) / 256, 2048)), dim3(256), 0, s, W, nb);
+  const long long nb = blocks_of((size_t)std::max<long long>(W.in.n, 1));   // (an empty build still launches)
+  hipLaunchKernelGGL(k_cmap_clear, dim3(std::min(blocks_of((size_t)W.fmask + 1), 2048u)), dim3(256), 0, s, W, nb);
   hipLaunchKernelGGL(k_cmap_flag, dim3((unsigned)nb), dim3(256), 0, s, W);
   if (W.runs) hipLaunchKernelGGL(k_cmap_stage<true>, dim3((unsigned)nb), dim3(256), 0, s, W);
   else hipLaunchKernelGGL(k_cmap_stage<false>, dim3((unsigned)nb), dim3(256), 0, s, W);
@@ -146,7 +141,7 @@ int launch_cmap_stage(const CmapWork& W, hipStream_t s) {
 }
 
 int launch_cmap_emit(const CmapWork& W, hipStream_t s) {
-  const long long nb = blocks_of(W.n);
+  const long long nb = blocks_of((size_t)std::max<long long>(W.in.n, 1));
   hipLaunchKernelGGL(k_cmap_emit, dim3((unsigned)nb), dim3(256), 0, s, W, nb);
   return 1;
 }

@@ -602,9 +602,14 @@ struct VmapTable {            // the persistent map
   unsigned long long* pkey;
   long long *pn, *pqx, *pqy, *pqz;
 };
-struct VmapReadArgs {
+struct VmapTableView {        // the same, read only: what every stage on top of a map takes of it (VoxelRowStore::view)
+  unsigned long long pmask;
+  const int* ptab;
   const unsigned long long* pkey;
   const long long *pn, *pqx, *pqy, *pqz;
+};
+struct VmapReadArgs {
+  VmapTableView map;
   double voxel, origin[3];
   size_t first, count;        // ids [first, first + count)
   double lo[3], hi[3];        // read_box: the box (inclusive) ...
@@ -633,15 +638,18 @@ struct CmapSpan {
   int kf;
   int reserved0;
 };
-struct CmapWork {
+struct SpanInput {            // what the build, the carve and the surfel pass read their points from
   const double* arena;
   const CmapSpan* span;       // [nspan + 1], spans of at least one point; span[nspan].start = n
   int nspan;
-  int runs;                   // 1: runs of equal keys among a wave's consecutive lanes are summed before the table is touched
+  int nkf;
   long long n;                // points of all spans
   const double* pose;         // [nkf][16] column-major
-  int* kf_over;               // [nkf] 1: a finite point of the keyframe left the grid (k_cmap_flag): it adds nothing
-  int nkf;
+};
+struct CmapWork {
+  SpanInput in;
+  int runs;                   // 1: runs of equal keys among a wave's consecutive lanes are summed before the table is touched
+  int* kf_over;               // [in.nkf] 1: a finite point of the keyframe left the grid (k_cmap_flag): it adds nothing
   double voxel, origin[3];
   // the build table [fmask + 1]
   unsigned long long fmask;
@@ -664,19 +672,10 @@ int launch_cmap_emit(const CmapWork& W, hipStream_t s);
 // that pose.  The rays come from a span table of the closed map's kind (CmapSpan) written for the carve's ray mask; the map is
 // looked up through its own slot table and nothing in it is written: the counts are an array of their own, in id order
 struct CarveWork {
-  const double* arena;
-  const CmapSpan* span;       // [nspan + 1], as CmapWork::span
-  int nspan;
-  int nkf;
-  long long n;                // rays: the points of all spans
-  const double* pose;         // [nkf][16] column-major: the poses the closed map was built with
+  SpanInput in;               // the rays: the points of all spans, under the poses the closed map was built with
   double voxel, origin[3];
   double max_range, end_margin, radius2;   // radius2 = radius * radius (+inf: the distance does not decide)
-  // the closed map, read only
-  unsigned long long pmask;
-  const int* ptab;
-  const unsigned long long* pkey;
-  const long long *pn, *pqx, *pqy, *pqz;
+  VmapTableView map;          // the closed map
   long long nv;               // its voxels
   unsigned long long* miss;   // [nv] M in id order
   unsigned long long* ctl;    // [0] skipped rays, [1] steps, [2] tested, [3] misses, [4] voxels with M > 0
@@ -699,18 +698,10 @@ void launch_carve_read(const CarveReadArgs& A, hipStream_t s);
 // written: the sums and the results are arrays of their own, in id order
 constexpr int kSurfelSums = 13;   // Ns, Rx Ry Rz, Sxx Sxy Sxz Syy Syz Szz, Wx Wy Wz
 struct SurfelWork {
-  const double* arena;
-  const CmapSpan* span;       // [nspan + 1], as CmapWork::span
-  int nspan;
-  int nkf;
-  long long n;                // the points of all spans
-  const double* pose;         // [nkf][16] column-major: the poses the closed map was built with
-  int* kf_over;               // [nkf] 1: a finite point of the keyframe left the grid (k_surfel_flag): it adds nothing
+  SpanInput in;               // the points of all spans, under the poses the closed map was built with
+  int* kf_over;               // [in.nkf] 1: a finite point of the keyframe left the grid (k_surfel_flag): it adds nothing
   double voxel, origin[3];
-  // the closed map's table, read only
-  unsigned long long pmask;
-  const int* ptab;
-  const unsigned long long* pkey;
+  VmapTableView map;          // the closed map
   long long nv;               // its voxels
   int runs;                   // 1: runs of equal voxels among a wave's consecutive lanes are summed before the atomics
   int min_points;             // a voxel of fewer points is not solved
@@ -765,8 +756,7 @@ struct LocState {             // the stage's words in HBM: written by the host b
   int reserved0;
 };
 struct LocPrepArgs {
-  const unsigned long long* pkey;
-  const long long *pn, *pqx, *pqy, *pqz;
+  VmapTableView map;          // the closed map
   const unsigned long long* sums;   // the surfels' thirteen per voxel
   const double *normal, *eval;
   long long nv;
@@ -780,9 +770,7 @@ struct LocSweepArgs {
   long long n;
   LocState* st;
   double voxel, origin[3];
-  unsigned long long pmask;   // the closed map's table, read only
-  const int* ptab;
-  const unsigned long long* pkey;
+  VmapTableView map;          // the closed map
   long long nv;
   const LocRecord* rec;
   double* partial;            // [blocks][kLocRow]

@@ -14,6 +14,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <initializer_list>
 #include <memory>
 #include <new>
 #include <string>
@@ -300,6 +301,10 @@ struct VoxelRowStore {
     T.pn = n.p; T.pqx = qx.p; T.pqy = qy.p; T.pqz = qz.p;
     return T;
   }
+  tl::VmapTableView view() const {   // ... and as the stages that only read them do
+    const tl::VmapTable T = table();
+    return tl::VmapTableView{T.pmask, T.ptab, T.pkey, T.pn, T.pqx, T.pqy, T.pqz};
+  }
 };
 
 // the merged voxel map of the odometry frame (tl_api_vmap.hip): the persistent map in id order and its
@@ -443,7 +448,7 @@ struct CmapState {
   // reports, the carved read's scratch.  The counts belong to the closed map they were counted in and go with it
   tloam_closed_map_carve_config carve_cfg = {60.0, 1.0, 0.25, 0, 0};   // tloam_closed_map_carve_default_config until configured
   DBuf<unsigned long long> miss, carve_ctl;
-  DBuf<long long> rd_m;
+  DBuf<unsigned char> rd_m;        // (a box read's own columns are scratch in bytes: BoxColumn)
   bool carved = false;             // a carve has succeeded since the last drop
   tloam_closed_map_carve_info carve_info{};
   void drop_carve() {
@@ -455,7 +460,8 @@ struct CmapState {
   // scratch.  They belong to the closed map they were gathered in and go with it; a carve does not touch them
   tloam_closed_map_surfel_config surfel_cfg = {5, 0};   // tloam_closed_map_surfel_default_config until configured
   DBuf<unsigned long long> surfel_sums, surfel_ctl;
-  DBuf<double> surfel_nrm, surfel_ev, rd_nrm, rd_ev;
+  DBuf<double> surfel_nrm, surfel_ev;
+  DBuf<unsigned char> rd_nrm, rd_ev;
   DBuf<int> surfel_over;
   bool surfeled = false;           // a surfel pass has succeeded since the last drop
   tloam_closed_map_surfel_info surfel_info{};
@@ -674,6 +680,24 @@ constexpr size_t kMaxPoints = (size_t)1 << 28;
 
 namespace tlh {
 // ---- small helpers shared by the API units
+// column-major 4x4 products, sums over k in ascending order, and Eigen::Isometry3d::inverse (R^T, -R^T t): the odometry's
+// prediction, loop verification's T_rel and the pose graph's Z round alike (their units are compiled with -ffp-contract=off)
+static inline void mat_mul(const double A[16], const double B[16], double out[16]) {
+  double r[16];
+  for (int j = 0; j < 4; ++j)
+    for (int i = 0; i < 4; ++i) r[4 * j + i] = ((A[i] * B[4 * j] + A[4 + i] * B[4 * j + 1]) + A[8 + i] * B[4 * j + 2]) + A[12 + i] * B[4 * j + 3];
+  memcpy(out, r, sizeof(r));
+}
+static inline void rigid_inverse(const double T[16], double out[16]) {
+  double r[16];
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) r[4 * j + i] = T[4 * i + j];
+    r[12 + i] = -((T[4 * i] * T[12] + T[4 * i + 1] * T[13]) + T[4 * i + 2] * T[14]);
+    r[4 * i + 3] = 0.0;
+  }
+  r[15] = 1.0;
+  memcpy(out, r, sizeof(r));
+}
 inline double kind_radius(const tloam_tls_config& c, int k) {
   switch (k) {
     case TLOAM_KIND_PLANAR: return c.planar_dist_thres;
@@ -828,8 +852,9 @@ int vmap_frame_reserve(tloam_ctx* c, size_t n);
 int vmap_stage_launch(tloam_ctx* c, const double pose[16], size_t n);
 int vmap_stage_collect(tloam_ctx* c, tloam_odom_stats* st);
 void vmap_frame_end(tloam_ctx* c, bool accepted);
-// tl_api_vmap.hip: the one read path of voxel rows -- the merged voxel map's and the closed map's (k_vmap_read / k_vmap_box).
-// What a read needs of either state: the rows as the kernels see them, the reads' scratch, the voxels held, the errors' name
+// tl_api_vmap.hip: the one read path of voxel rows -- the merged voxel map's and the closed map's (k_vmap_read and the three box
+// kernels).  What a read needs of either state: the rows as the kernels see them, the reads' scratch, the voxels held, the
+// errors' name
 struct VoxelRows {
   tl::VmapReadArgs base;
   DBuf<double>& rd_c;
@@ -843,16 +868,77 @@ template <class State>
 VoxelRows voxel_rows_of(State& S, size_t nv, const char* name) {
   tl::VmapReadArgs A;
   memset(&A, 0, sizeof(A));
-  A.pkey = S.rows.key.p; A.pn = S.rows.n.p; A.pqx = S.rows.qx.p; A.pqy = S.rows.qy.p; A.pqz = S.rows.qz.p;
+  A.map = S.rows.view();
   A.voxel = S.cfg.voxel;
   for (int a = 0; a < 3; ++a) A.origin[a] = S.cfg.origin[a];
   return VoxelRows{A, S.rd_c, S.rd_n, S.look, S.ctl, nv, name};
 }
-// ids [first, first + count) / the voxels in the box with N >= min_count in id order, to the host; the caller has checked its
-// context (and that a closed map is built)
+// ids [first, first + count) to the host; the caller has checked its context (and that a closed map is built)
 int voxel_rows_read(tloam_ctx* c, const VoxelRows& R, size_t first, size_t count, double* centroids_aos, int64_t* counts);
-int voxel_rows_read_box(tloam_ctx* c, const VoxelRows& R, const double lo[3], const double hi[3], int64_t min_count, size_t capacity,
-                        size_t* n, double* centroids_aos, int64_t* counts);
+// The host half of a box read: the voxels of the box (null: the whole map) with N >= min_count that the kernel keeps, in id
+// order, to the host.  `launch` is handed the filled rows (scratch reserved, look and ctl zeroed) and enqueues `kernel`, named
+// in the timeout's message; `extra` are the read's own columns beside the centroids and the counts
+struct BoxColumn {
+  void* host;                 // where the caller wants it (null: not asked for)
+  DBuf<unsigned char>* dev;   // the column's device scratch, in bytes
+  size_t per_voxel, elem;     // elements per voxel, bytes per element
+};
+template <class Launch>
+int voxel_rows_read_box(tloam_ctx* c, const VoxelRows& R, const double* lo, const double* hi, int64_t min_count, size_t capacity,
+                        size_t* n, double* centroids_aos, int64_t* counts, const char* kernel, std::initializer_list<BoxColumn> extra,
+                        Launch launch) {
+  const size_t nv = R.nv;
+  if (nv == 0) return TLOAM_OK;
+  HIPC(c, hipSetDevice(c->device));
+  HIPC(c, hipStreamSynchronize(c->stream));   // (the scratch may be replaced)
+  const size_t blocks = (nv + 255) / 256;
+  HIPC(c, R.rd_c.reserve(3 * nv)); HIPC(c, R.rd_n.reserve(nv));
+  for (const BoxColumn& x : extra) HIPC(c, x.dev->reserve(x.per_voxel * x.elem * nv));
+  HIPC(c, R.look.reserve(blocks + 1)); HIPC(c, R.ctl.reserve(8));
+  HIPC(c, hipMemsetAsync(R.look.p, 0, sizeof(unsigned long long) * (blocks + 1), c->stream));
+  HIPC(c, hipMemsetAsync(R.ctl.p, 0, sizeof(unsigned long long) * 8, c->stream));
+  tl::VmapReadArgs A = R.base;
+  A.first = 0; A.count = nv;
+  for (int a = 0; a < 3; ++a) { A.lo[a] = lo ? lo[a] : 0.0; A.hi[a] = hi ? hi[a] : 0.0; }
+  A.min_count = min_count;
+  A.out_c = R.rd_c.p; A.out_n = R.rd_n.p;
+  A.look = R.look.p; A.ctl = R.ctl.p;
+  launch(A);
+  HIPC(c, hipGetLastError());
+  unsigned long long w[3];
+  HIPC(c, hipMemcpyAsync(w, R.ctl.p, sizeof(w), hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  if (w[1]) {
+    c->last_error = std::string(R.name) + ": a look-back of " + kernel + " timed out";
+    return TLOAM_E_HIP;
+  }
+  const size_t m = (size_t)w[2];
+  *n = m;
+  if (m == 0) return TLOAM_OK;
+  if (capacity < m) return TLOAM_E_INVALID;
+  const hipMemcpyKind D2H = hipMemcpyDeviceToHost;
+  if (centroids_aos) HIPC(c, hipMemcpyAsync(centroids_aos, R.rd_c.p, sizeof(double) * 3 * m, D2H, c->stream));
+  if (counts) HIPC(c, hipMemcpyAsync(counts, R.rd_n.p, sizeof(int64_t) * m, D2H, c->stream));
+  for (const BoxColumn& x : extra)
+    if (x.host) HIPC(c, hipMemcpyAsync(x.host, x.dev->p, x.per_voxel * x.elem * m, D2H, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  return TLOAM_OK;
+}
+// tl_api_cmap.hip: the closed map's span table for `mask` over keyframes [0, min(K, kf.size())): keyframes ascending, a keyframe's
+// selected clouds in slot order, empty clouds left out, the end sentinel (spans->back().start = *n) last; *empty_keyframes (may be
+// null) counts the keyframes that add no span
+void cmap_span_table(const PlaceState& P, size_t K, int mask, std::vector<tl::CmapSpan>* spans, long long* n,
+                     int64_t* empty_keyframes);
+// ... and its device copy beside the K poses, a stage's own: freed with it (hipFree waits for the launches that use them)
+struct SpanUpload {
+  DBuf<tl::CmapSpan> span;
+  DBuf<double> pose;
+  // both uploaded on the context's stream; *in: what the kernels take (arena, span, nspan, nkf, n, pose)
+  int upload(tloam_ctx* c, const std::vector<tl::CmapSpan>& spans, long long n, const double* poses, size_t K, tl::SpanInput* in);
+};
+// ids [first, first + count) of a side array of the built closed map (`ran`: the stage that fills it has run): TLOAM_OK when the
+// range is one
+int cmap_side_range(const tloam_ctx* c, bool ran, size_t first, size_t count);
 // tl_api_deskew.hip: the frame's deskew -- sized and its times uploaded after the scan's upload, launched after the segmentation's
 // (the refused-time flag read with the frame's first wait), committed when the frame ends
 int deskew_frame_upload(tloam_ctx* c, const double* t_sec, size_t n, tloam_odom_stats* st);

@@ -2,7 +2,8 @@
 // point-to-plane Gauss-Newton on the surfels.
 //
 // Launches (no host synchronisation between them; nothing of the closed map, the carve or the surfels is written):
-//   k_loc_prepare   grid x 256   per voxel one 64-byte record {c, n, eligible}: a probe hit then costs one cache line
+//   k_loc_prepare   grid x 256   per voxel one 64-byte record {c, n, eligible}: a probe hit then costs one cache line; eligible
+//                                is tl_voxel.hpp's surfel_gate, the gate of the surfels' box read
 //   k_loc_sweep     grid x 256   per point: transform, quantise, 27 read-only probes of the closed map's slot table, the nearest
 //                                eligible centroid, residual, truncation; the 28 terms and the two counts summed over the wave
 //                                by shuffles and over the block's four waves through LDS; one partial row per block
@@ -34,31 +35,19 @@
 namespace tl {
 namespace {
 
-// the id of the closed map's voxel `key`, -1 when it has none (tl_surfel.hip's surfel_find)
-__device__ __forceinline__ int loc_find(const LocSweepArgs& W, unsigned long long key) {
-  for (unsigned long long t = mix64(key) & W.pmask;; t = (t + 1) & W.pmask) {
-    const int id = W.ptab[t];
-    if (id < 0) return -1;
-    if (W.pkey[id] == key) return id;
-  }
-}
-
 __global__ __launch_bounds__(256) void k_loc_prepare(LocPrepArgs A) {
   const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
   if (id >= A.nv) return;
-  const unsigned long long key = A.pkey[id];
-  const long long Q[3] = {A.pqx[id], A.pqy[id], A.pqz[id]};
-  const long long n = A.pn[id];
-  const long long ns = (long long)A.sums[id * kSurfelSums];
   LocRecord R;
+  long long n;
+  voxel_centroid(A.map, A.origin, A.voxel, (size_t)id, R.c, &n);
   double ev[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    R.c[a] = centroid(A.origin[a], A.voxel, key_axis(key, a), Q[a], n);
     R.n[a] = A.normal[3 * id + a];
     ev[a] = A.eval[3 * id + a];
   }
-  R.eligible = ns >= (long long)A.min_points && ev[2] > 0.0 && ev[0] <= A.max_sigma2 && (ev[1] - ev[0]) >= A.min_planarity * ev[2];
+  R.eligible = surfel_gate((long long)A.sums[id * kSurfelSums], ev, A.min_points, A.max_sigma2, A.min_planarity);
   R.pad[0] = R.pad[1] = R.pad[2] = 0;
   A.rec[id] = R;
 }
@@ -99,7 +88,7 @@ __device__ __forceinline__ void loc_sweep_body(const LocSweepArgs& W, const LocS
             if (c0 <= -lim || c0 >= lim || c1 <= -lim || c1 >= lim || c2 <= -lim || c2 >= lim) continue;   // beyond the grid: no voxel
             const unsigned long long ck = (unsigned long long)(c0 + lim) | ((unsigned long long)(c1 + lim) << 21) |
                                           ((unsigned long long)(c2 + lim) << 42);
-            const int id = loc_find(W, ck);
+            const int id = id_table_find(W.map.ptab, W.map.pmask, W.map.pkey, ck);
             if (id < 0) continue;
             const LocRecord* R = W.rec + id;
             if (!R->eligible) continue;

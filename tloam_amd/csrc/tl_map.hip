@@ -253,8 +253,6 @@ __global__ __launch_bounds__(256) void k_transform_aos(const double* __restrict_
   out[3 * i] = x; out[3 * i + 1] = y; out[3 * i + 2] = z;
 }
 
-inline unsigned blocks_of(size_t n) { return (unsigned)((n + 255) / 256); }
-
 }  // namespace
 
 void launch_map_voxel(const MapFrontArgs& A, const MapVoxWork& W, hipStream_t s) {

@@ -4,14 +4,14 @@
 // Launches of a pass, the same four for any number of keyframes, spans and points (no host synchronisation between them):
 //   k_surfel_clear   grid x 256   zeroes the thirteen sums, the keyframes' flags and the control words
 //   k_surfel_flag    grid x 256   per point: its span from its global index, transform, quantise; a finite point beyond the grid
-//                                 raises its keyframe's flag (as k_cmap_flag: a plain store of 1)
+//                                 raises its keyframe's flag (a plain store of 1: every writer writes the same value)
 //   k_surfel_accum   grid x 256   per point of an unflagged keyframe: the same, the voxel's id from the closed map's slot table
-//                                 (read only; none: an orphan), then the thirteen integers; runs of equal ids among a wave's
+//                                 (id_table_find; none: an orphan), then the thirteen integers; runs of equal ids among a wave's
 //                                 consecutive lanes are summed by shuffle scans and the run's tail does the thirteen int64 atomic
 //                                 adds (a wave without such a run, and the plain form, add per point: the same bits)
 //   k_surfel_solve   grid x 256   per voxel: mean, covariance, eig3_sym, orientation, scale; the solved voxels counted by ballot,
 //                                 one atomic per wave
-// The box read is k_surfel_box: k_carve_box's selection, order and compaction with the surfel gate.
+// The box read is k_surfel_box: the box read's one body (tl_voxel.hpp: voxel_box_body) with the surfel gate (surfel_gate).
 //
 // Compiled with -ffp-contract=off.  The arithmetic (tests/closed_map_surfel_np.py restates it), per point of keyframe k and axis a:
 //   E = map_transform_point(P_k, p),  O_a = P_k[12 + a],  (i, q) = vmap_quantise(E),  r_a = q_a >> 8  (2^-16 of a voxel)
@@ -31,44 +31,31 @@ namespace {
 
 constexpr double kSurfelWClamp = 1073741824.0;   // 2^30
 
-// the id of the closed map's voxel `key`, -1 when it has none
-__device__ __forceinline__ int surfel_find(const SurfelWork& W, unsigned long long key) {
-  for (unsigned long long t = mix64(key) & W.pmask;; t = (t + 1) & W.pmask) {
-    const int id = W.ptab[t];
-    if (id < 0) return -1;
-    if (W.pkey[id] == key) return id;
-  }
-}
-
-// point g (< W.n): its keyframe, its pose, the point under it, and where that falls in the grid (key and q when inside)
-__device__ __forceinline__ VmapCell surfel_point(const SurfelWork& W, long long g, int s_lo, int s_hi, int* kf, const double** P,
+// point g (< W.in.n): its keyframe, its pose, the point under it, and where that falls in the grid (key and q when inside)
+__device__ __forceinline__ VmapCell surfel_point(const SurfelWork& W, long long g, const int s_span[2], int* kf, const double** P,
                                                  double E[3], unsigned long long* key, unsigned q[3]) {
-  const CmapSpan S = W.span[span_of(W.span, s_lo, s_hi, g)];
-  const double* x = W.arena + S.off + 3 * (g - S.start);
-  *kf = S.kf;
-  *P = W.pose + 16 * (size_t)S.kf;
-  map_transform_point(*P, x[0], x[1], x[2], &E[0], &E[1], &E[2]);
+  span_point(W.in, g, s_span[0], s_span[1], kf, P, E);
   return vmap_quantise(E, W.origin, W.voxel, key, q);
 }
 
 __global__ __launch_bounds__(256) void k_surfel_clear(SurfelWork W) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
   for (size_t t = i; t < (size_t)W.nv * kSurfelSums; t += stride) W.sums[t] = 0ull;
-  for (size_t t = i; t < (size_t)W.nkf; t += stride) W.kf_over[t] = 0;
+  for (size_t t = i; t < (size_t)W.in.nkf; t += stride) W.kf_over[t] = 0;
   if (i < 8) W.ctl[i] = 0ull;
 }
 
 __global__ __launch_bounds__(256) void k_surfel_flag(SurfelWork W) {
   __shared__ int s_span[2];
-  block_spans(W, s_span);
+  block_spans(W.in, s_span);
   const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (g >= W.n) return;
+  if (g >= W.in.n) return;
   int kf;
   const double* P;
   double E[3];
   unsigned long long key;
   unsigned q[3];
-  if (surfel_point(W, g, s_span[0], s_span[1], &kf, &P, E, &key, q) == kVmapBeyond) W.kf_over[kf] = 1;
+  if (surfel_point(W, g, s_span, &kf, &P, E, &key, q) == kVmapBeyond) W.kf_over[kf] = 1;
 }
 
 // inclusive prefix sum of `v` over the wave's lanes
@@ -92,21 +79,21 @@ __device__ __forceinline__ T run_sum(T incl, int head_lane) {
 template <bool kRuns>
 __global__ __launch_bounds__(256) void k_surfel_accum(SurfelWork W) {
   __shared__ int s_span[2];
-  block_spans(W, s_span);
+  block_spans(W.in, s_span);
   const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
   const int lane = threadIdx.x & 63;
   bool ok = false, orphan = false;
   int id = -1;
   unsigned r[3] = {0u, 0u, 0u};
   long long w[3] = {0, 0, 0};
-  if (g < W.n) {
+  if (g < W.in.n) {
     int kf;
     const double* P;
     double E[3];
     unsigned long long key;
     unsigned q[3];
-    if (surfel_point(W, g, s_span[0], s_span[1], &kf, &P, E, &key, q) == kVmapInside && W.kf_over[kf] == 0) {
-      id = surfel_find(W, key);
+    if (surfel_point(W, g, s_span, &kf, &P, E, &key, q) == kVmapInside && W.kf_over[kf] == 0) {
+      id = id_table_find(W.map.ptab, W.map.pmask, W.map.pkey, key);
       ok = id >= 0;
       orphan = !ok;
 #pragma unroll
@@ -192,69 +179,43 @@ __global__ __launch_bounds__(256) void k_surfel_solve(SurfelWork W) {
   if ((threadIdx.x & 63) == 0 && bal) atomicAdd(&W.ctl[2], (unsigned long long)__popcll(bal));
 }
 
-// the voxels of k_vmap_box's selection (the box only when A.boxed) whose surfel passes the gate, compacted in id order
+// the box read (the box only when A.boxed) of the voxels whose surfel passes the gate; the normals and the variances beside the
+// centroids, and Ns where the plain read has N
+struct BoxSurfel {
+  const SurfelReadArgs& A;
+  __device__ __forceinline__ bool keep(size_t id, long long, const double*) const {
+    const double ev[3] = {A.eval[3 * id], A.eval[3 * id + 1], A.eval[3 * id + 2]};
+    return surfel_gate((long long)A.sums[id * kSurfelSums], ev, A.min_points, A.max_sigma2, A.min_planarity);
+  }
+  __device__ __forceinline__ long long emit(size_t id, size_t p, long long) const {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      if (A.out_nrm) A.out_nrm[3 * p + a] = A.normal[3 * id + a];
+      if (A.out_ev) A.out_ev[3 * p + a] = A.eval[3 * id + a];
+    }
+    return (long long)A.sums[id * kSurfelSums];
+  }
+};
 __global__ __launch_bounds__(256) void k_surfel_box(SurfelReadArgs A, int nblocks) {
-  __shared__ unsigned long long s_wave[4];
-  __shared__ unsigned long long s_prefix;
-  __shared__ int s_bid;
-  const VmapReadArgs& R = A.rows;
-  const int tid = threadIdx.x;
-  const int bid = block_ticket(&R.ctl[0], &s_bid);
-  const size_t id = (size_t)bid * 256 + tid;
-  double c[3] = {0.0, 0.0, 0.0}, nr[3] = {0.0, 0.0, 0.0}, ev[3] = {0.0, 0.0, 0.0};
-  long long ns = 0;
-  bool sel = false;
-  if (id < R.count) {
-    const unsigned long long key = R.pkey[id];
-    const long long Q[3] = {R.pqx[id], R.pqy[id], R.pqz[id]};
-    const long long n = R.pn[id];
-    ns = (long long)A.sums[id * kSurfelSums];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      c[a] = centroid(R.origin[a], R.voxel, key_axis(key, a), Q[a], n);
-      nr[a] = A.normal[3 * id + a];
-      ev[a] = A.eval[3 * id + a];
-    }
-    sel = n >= R.min_count;
-    if (A.boxed) {
-#pragma unroll
-      for (int a = 0; a < 3; ++a) sel = sel && c[a] >= R.lo[a] && c[a] <= R.hi[a];
-    }
-    sel = sel && ns >= (long long)A.min_points && ev[2] > 0.0 && ev[0] <= A.max_sigma2 && (ev[1] - ev[0]) >= A.min_planarity * ev[2];
-  }
-  int pos, total;
-  block_flag_scan(sel, s_wave, &pos, &total);
-  if (tid == 0) s_prefix = lookback_prefix(R.look, bid, (unsigned long long)total, LookFaultDevice{&R.ctl[1]});
-  __syncthreads();
-  if (sel) {
-    const size_t p = (size_t)(s_prefix + pos);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      if (R.out_c) R.out_c[3 * p + a] = c[a];
-      if (A.out_nrm) A.out_nrm[3 * p + a] = nr[a];
-      if (A.out_ev) A.out_ev[3 * p + a] = ev[a];
-    }
-    if (R.out_n) R.out_n[p] = ns;
-  }
-  if (bid == nblocks - 1 && tid == 0) R.ctl[2] = s_prefix + total;
+  voxel_box_body(A.rows, A.boxed != 0, nblocks, BoxSurfel{A});
 }
-
-inline unsigned blocks_of(long long n) { return (unsigned)std::max<long long>((n + 255) / 256, 1); }   // (nothing still launches)
 
 }  // namespace
 
 int launch_surfels(const SurfelWork& W, hipStream_t s) {
-  hipLaunchKernelGGL(k_surfel_clear, dim3(std::min(blocks_of(W.nv * kSurfelSums), 2048u)), dim3(256), 0, s, W);
-  hipLaunchKernelGGL(k_surfel_flag, dim3(blocks_of(W.n)), dim3(256), 0, s, W);
-  if (W.runs) hipLaunchKernelGGL(k_surfel_accum<true>, dim3(blocks_of(W.n)), dim3(256), 0, s, W);
-  else hipLaunchKernelGGL(k_surfel_accum<false>, dim3(blocks_of(W.n)), dim3(256), 0, s, W);
-  hipLaunchKernelGGL(k_surfel_solve, dim3(blocks_of(W.nv)), dim3(256), 0, s, W);
+  const size_t nv = (size_t)std::max<long long>(W.nv, 1);   // (nothing still launches)
+  const unsigned pt_blocks = blocks_of((size_t)std::max<long long>(W.in.n, 1));
+  hipLaunchKernelGGL(k_surfel_clear, dim3(std::min(blocks_of(nv * kSurfelSums), 2048u)), dim3(256), 0, s, W);
+  hipLaunchKernelGGL(k_surfel_flag, dim3(pt_blocks), dim3(256), 0, s, W);
+  if (W.runs) hipLaunchKernelGGL(k_surfel_accum<true>, dim3(pt_blocks), dim3(256), 0, s, W);
+  else hipLaunchKernelGGL(k_surfel_accum<false>, dim3(pt_blocks), dim3(256), 0, s, W);
+  hipLaunchKernelGGL(k_surfel_solve, dim3(blocks_of(nv)), dim3(256), 0, s, W);
   return 4;
 }
 
 void launch_surfel_read(const SurfelReadArgs& A, hipStream_t s) {
   if (A.rows.count == 0) return;
-  const int nb = (int)blocks_of((long long)A.rows.count);
+  const int nb = (int)blocks_of(A.rows.count);
   hipLaunchKernelGGL(k_surfel_box, dim3(nb), dim3(256), 0, s, A, nb);
 }
 

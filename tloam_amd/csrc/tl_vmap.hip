@@ -75,15 +75,7 @@ __global__ __launch_bounds__(256) void k_vmap_emit(VmapStageWork W, int nblocks)
   const size_t i = (size_t)bid * 256 + tid;
   const int h = i < W.n ? W.slot_of_pt[i] : -1;
   const bool leader = h >= 0 && W.flead[h] == (int)i;
-  int found = -1;
-  if (leader) {
-    const unsigned long long key = W.fkey[h];
-    for (unsigned long long t = mix64(key) & W.pmask;; t = (t + 1) & W.pmask) {
-      const int id = W.ptab[t];
-      if (id < 0) break;
-      if (W.pkey[id] == key) { found = id; break; }
-    }
-  }
+  const int found = leader ? id_table_find(W.ptab, W.pmask, W.pkey, W.fkey[h]) : -1;
   const bool fresh = leader && found < 0;
   int pos, total;
   block_flag_scan(fresh, s_wave, &pos, &total);
@@ -126,55 +118,18 @@ __global__ __launch_bounds__(256) void k_vmap_rehash(VmapTable P, size_t n) {
   id_table_insert(P.ptab, P.pmask, P.pkey[id], (int)id);
 }
 
-__device__ __forceinline__ void voxel_centroid(const VmapReadArgs& A, size_t id, double c[3], long long* N) {
-  const unsigned long long key = A.pkey[id];
-  const long long n = A.pn[id];
-  const long long Q[3] = {A.pqx[id], A.pqy[id], A.pqz[id]};
-#pragma unroll
-  for (int a = 0; a < 3; ++a) c[a] = centroid(A.origin[a], A.voxel, key_axis(key, a), Q[a], n);
-  *N = n;
-}
-
 __global__ __launch_bounds__(256) void k_vmap_read(VmapReadArgs A) {
   const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (k >= A.count) return;
   double c[3];
   long long n;
-  voxel_centroid(A, A.first + k, c, &n);
+  voxel_centroid(A.map, A.origin, A.voxel, A.first + k, c, &n);
   if (A.out_c) { A.out_c[3 * k] = c[0]; A.out_c[3 * k + 1] = c[1]; A.out_c[3 * k + 2] = c[2]; }
   if (A.out_n) A.out_n[k] = n;
 }
 
-// the voxels in the box with N >= min_count, compacted in id order (block scan + look-back over start tickets)
-__global__ __launch_bounds__(256) void k_vmap_box(VmapReadArgs A, int nblocks) {
-  __shared__ unsigned long long s_wave[4];
-  __shared__ unsigned long long s_prefix;
-  __shared__ int s_bid;
-  const int tid = threadIdx.x;
-  const int bid = block_ticket(&A.ctl[0], &s_bid);
-  const size_t id = A.first + (size_t)bid * 256 + tid;
-  double c[3] = {0.0, 0.0, 0.0};
-  long long n = 0;
-  bool sel = false;
-  if (id < A.first + A.count) {
-    voxel_centroid(A, id, c, &n);
-    sel = n >= A.min_count;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) sel = sel && c[a] >= A.lo[a] && c[a] <= A.hi[a];
-  }
-  int pos, total;
-  block_flag_scan(sel, s_wave, &pos, &total);
-  if (tid == 0) s_prefix = lookback_prefix(A.look, bid, (unsigned long long)total, LookFaultDevice{&A.ctl[1]});
-  __syncthreads();
-  if (sel) {
-    const size_t p = (size_t)(s_prefix + pos);
-    if (A.out_c) { A.out_c[3 * p] = c[0]; A.out_c[3 * p + 1] = c[1]; A.out_c[3 * p + 2] = c[2]; }
-    if (A.out_n) A.out_n[p] = n;
-  }
-  if (bid == nblocks - 1 && tid == 0) A.ctl[2] = s_prefix + total;
-}
-
-inline unsigned blocks_of(size_t n) { return (unsigned)((n + 255) / 256); }
+// the voxels in the box with N >= min_count, compacted in id order (tl_voxel.hpp: voxel_box_body)
+__global__ __launch_bounds__(256) void k_vmap_box(VmapReadArgs A, int nblocks) { voxel_box_body(A, true, nblocks, BoxPlain{}); }
 
 }  // namespace
 

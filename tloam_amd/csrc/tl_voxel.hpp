@@ -1,8 +1,10 @@
 // tl_voxel.hpp -- what the device voxel grids share: the submap's down-sample (tl_submap.hip), the
-// global map (tl_map.hip), the merged voxel map (tl_vmap.hip), the closed map (tl_cmap.hip) and its carve (tl_carve.hip).  One
-// definition each of the key hash and the two table inserts, of the block scans, of the single-pass look-back with its one bound,
-// of the eight-word post to the host, of the voxel map's key / q arithmetic and its run sums, and of the span table's search.
-// Device code only.
+// global map (tl_map.hip), the merged voxel map (tl_vmap.hip), the closed map (tl_cmap.hip), its carve (tl_carve.hip), its
+// surfels (tl_surfel.hip) and the localiser (tl_localise.hip).  One definition each of the key hash, the two table inserts and
+// the slot table's lookup, of the block scans, of the single-pass look-back with its one bound, of the eight-word post to the
+// host, of the voxel map's key / q arithmetic, its row centroid and its run sums, of the compacting box read's body
+// (k_vmap_box, k_carve_box, k_surfel_box), of the surfel gate, and of the span table's search and its point.
+// Device code, and the launches' blocks_of.
 // An includer must be compiled with -ffp-contract=off: vmap_quantise and centroid are the bit-for-bit contract of DESIGN.md 14.
 #pragma once
 
@@ -45,6 +47,19 @@ __device__ __forceinline__ void id_table_insert(int* ptab, unsigned long long pm
   for (unsigned long long t = mix64(key) & pmask;; t = (t + 1) & pmask)
     if (atomicCAS(&ptab[t], -1, id) == -1) break;
 }
+
+// the id of voxel `key` in the slot -> id table of a map (read only), -1 when it has none
+__device__ __forceinline__ int id_table_find(const int* ptab, unsigned long long pmask, const unsigned long long* pkey,
+                                             unsigned long long key) {
+  for (unsigned long long t = mix64(key) & pmask;; t = (t + 1) & pmask) {
+    const int id = ptab[t];
+    if (id < 0) return -1;
+    if (pkey[id] == key) return id;
+  }
+}
+
+// 256-thread blocks over n items; a launch that runs for nothing too asks for blocks_of(max(n, 1))
+inline unsigned blocks_of(size_t n) { return (unsigned)((n + 255) / 256); }
 
 // The block's place in the order the blocks START, from a counter that is zero before the launch; ends in a barrier.  A block
 // that looks back over places below its own then only ever waits for blocks that are running.
@@ -193,6 +208,66 @@ __device__ __forceinline__ double centroid(double o, double v, long long i, long
   return o + v * ((double)i + ((double)Q / (double)N) * (1.0 / kVmapQScale));
 }
 
+// the row of voxel `id`: its centroid and its count
+__device__ __forceinline__ void voxel_centroid(const VmapTableView& T, const double origin[3], double voxel, size_t id, double c[3],
+                                               long long* N) {
+  const unsigned long long key = T.pkey[id];
+  const long long n = T.pn[id];
+  const long long Q[3] = {T.pqx[id], T.pqy[id], T.pqz[id]};
+#pragma unroll
+  for (int a = 0; a < 3; ++a) c[a] = centroid(origin[a], voxel, key_axis(key, a), Q[a], n);
+  *N = n;
+}
+
+// The compacting box read of one block: the voxels of ids [R.first, R.first + R.count) with N >= R.min_count, inside the box
+// (inclusive) when `boxed`, that X keeps, written in id order (block scan + look-back over start tickets); the last block leaves
+// their number in R.ctl[2].  What the three reads differ in is X:
+//   X.keep(id, n, c)   the read's own test of a voxel of count n and centroid c
+//   X.emit(id, p, n)   writes the read's own columns of voxel id at place p, and returns what goes to R.out_n
+struct BoxPlain {   // the plain read: the box and min_count decide, N is the count
+  __device__ __forceinline__ bool keep(size_t, long long, const double*) const { return true; }
+  __device__ __forceinline__ long long emit(size_t, size_t, long long n) const { return n; }
+};
+template <class Extra>
+__device__ __forceinline__ void voxel_box_body(const VmapReadArgs& R, bool boxed, int nblocks, const Extra& X) {
+  __shared__ unsigned long long s_wave[4];
+  __shared__ unsigned long long s_prefix;
+  __shared__ int s_bid;
+  const int tid = threadIdx.x;
+  const int bid = block_ticket(&R.ctl[0], &s_bid);
+  const size_t id = R.first + (size_t)bid * 256 + tid;
+  double c[3] = {0.0, 0.0, 0.0};
+  long long n = 0;
+  bool sel = false;
+  if (id < R.first + R.count) {
+    voxel_centroid(R.map, R.origin, R.voxel, id, c, &n);
+    sel = n >= R.min_count;
+    if (boxed) {
+#pragma unroll
+      for (int a = 0; a < 3; ++a) sel = sel && c[a] >= R.lo[a] && c[a] <= R.hi[a];
+    }
+    sel = sel && X.keep(id, n, c);
+  }
+  int pos, total;
+  block_flag_scan(sel, s_wave, &pos, &total);
+  if (tid == 0) s_prefix = lookback_prefix(R.look, bid, (unsigned long long)total, LookFaultDevice{&R.ctl[1]});
+  __syncthreads();
+  if (sel) {
+    const size_t p = (size_t)(s_prefix + pos);
+    if (R.out_c) { R.out_c[3 * p] = c[0]; R.out_c[3 * p + 1] = c[1]; R.out_c[3 * p + 2] = c[2]; }
+    const long long count = X.emit(id, p, n);
+    if (R.out_n) R.out_n[p] = count;
+  }
+  if (bid == nblocks - 1 && tid == 0) R.ctl[2] = s_prefix + total;
+}
+
+// the surfel gate, for the box read (k_surfel_box) and the localiser's records (k_loc_prepare) alike: solved, not a point, thin
+// enough and planar enough
+__device__ __forceinline__ bool surfel_gate(long long ns, const double ev[3], int min_points, double max_sigma2,
+                                            double min_planarity) {
+  return ns >= (long long)min_points && ev[2] > 0.0 && ev[0] <= max_sigma2 && (ev[1] - ev[0]) >= min_planarity * ev[2];
+}
+
 // Runs of equal keys among a wave's consecutive `ok` lanes (neighbouring returns of a ring share their voxel), summed by
 // shuffles so that a run costs the table one insert and four atomics instead of one each per point.  Called by the whole wave.
 // head / tail: this lane begins / ends its run; head_lane: the lane that begins it (the run's smallest point index);
@@ -232,7 +307,7 @@ __device__ __forceinline__ WaveRun wave_run_sums(bool ok, unsigned long long key
   return r;
 }
 
-// ---- a span table in global point order (CmapSpan: the closed map's build and its carve) ----
+// ---- a span table in global point order (SpanInput: the closed map's build, its carve and its surfels) ----
 // the last span of [lo, hi] that starts at or before g
 __device__ __forceinline__ int span_of(const CmapSpan* sp, int lo, int hi, long long g) {
   while (lo < hi) {
@@ -244,9 +319,7 @@ __device__ __forceinline__ int span_of(const CmapSpan* sp, int lo, int hi, long 
 }
 
 // the spans of the block's first and last point, found once per block: a point then searches between them (usually one span).
-// Work: CmapWork or CarveWork (span, nspan, n)
-template <class Work>
-__device__ __forceinline__ void block_spans(const Work& W, int s_span[2]) {
+__device__ __forceinline__ void block_spans(const SpanInput& W, int s_span[2]) {
   if (threadIdx.x == 0) {
     const long long first = (long long)blockIdx.x * 256;
     const long long last = first + 255 < W.n ? first + 255 : W.n - 1;
@@ -259,6 +332,16 @@ __device__ __forceinline__ void block_spans(const Work& W, int s_span[2]) {
     s_span[1] = hi;
   }
   __syncthreads();
+}
+
+// point g (< in.n) of the table, its span searched between s_lo and s_hi: its keyframe, that keyframe's pose, the point under it
+__device__ __forceinline__ void span_point(const SpanInput& in, long long g, int s_lo, int s_hi, int* kf, const double** P,
+                                           double E[3]) {
+  const CmapSpan S = in.span[span_of(in.span, s_lo, s_hi, g)];
+  const double* x = in.arena + S.off + 3 * (g - S.start);
+  *kf = S.kf;
+  *P = in.pose + 16 * (size_t)S.kf;
+  map_transform_point(*P, x[0], x[1], x[2], &E[0], &E[1], &E[2]);
 }
 
 }  // namespace tl
