@@ -1,4 +1,4 @@
-"""-m gpu: several hypotheses of one scan in one set of launches (k_loc_sweep_batch, k_loc_step_batch)
+"""-m gpu: several hypotheses of one scan in one set of launches (k_loc_sweep, k_loc_step over B hypotheses)
 against the single call from each prior: pose, info and log bit for bit, the pick by its rule, the lifecycle.  The scenes are
 those of tests/test_gpu_closed_map_localise.py."""
 import os
@@ -194,6 +194,14 @@ def test_lifecycle(hip_module):
     H.closed_map_localise(scan, priors[1])
     assert [log_bytes(H.closed_map_localise_batch_log(h)) for h in range(2)] == logs
     assert log_bytes(H.closed_map_localise_log()) == logs[1]
+    # ... also from a prior that is in neither: one run path, two record stores
+    H.closed_map_localise(scan, LS.offset(truth, -0.1, 0.01))
+    alone = log_bytes(H.closed_map_localise_log())
+    assert alone and alone not in logs
+    assert [log_bytes(H.closed_map_localise_batch_log(h)) for h in range(2)] == logs
+    H.closed_map_localise_batch(scan, priors)
+    assert log_bytes(H.closed_map_localise_log()) == alone
+    assert [log_bytes(H.closed_map_localise_batch_log(h)) for h in range(2)] == logs
     # launches: 2 max_iterations for every input
     H.closed_map_localise_configure(max_iterations=7)
     seen = {i["launches"] for p in (scan, scan[:10], scan + 100.0) for i in H.closed_map_localise_batch(p, priors)[1]}

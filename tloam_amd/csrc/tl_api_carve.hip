@@ -21,43 +21,33 @@ bool carve_config_ok(const tloam_closed_map_carve_config& m) {
 // the enqueue, the wait and the counters of a carve; the previous counts have been dropped
 int carve_body(tloam_ctx* c, tloam_closed_map_carve_info& I) {
   CmapState& M = c->cmap;
-  const PlaceState& P = c->place;
-  const size_t K = M.poses.size() / 16;   // the build's keyframes: later ones cast no rays
-  const int mask = M.carve_cfg.ray_mask ? M.carve_cfg.ray_mask : M.cfg.cloud_mask;
-  std::vector<CmapSpan> spans;
-  long long n = 0;
-  cmap_span_table(P, K, mask, &spans, &n, nullptr);
-  const size_t nv = (size_t)M.info.n_voxels;
-  HIPC(c, hipSetDevice(c->device));
-  if (M.miss.cap < std::max<size_t>(nv, 1) || M.carve_ctl.cap < 8)
-    HIPC(c, hipStreamSynchronize(c->stream));   // (the counts replaced may still be read)
-  HIPC(c, M.miss.reserve(std::max<size_t>(nv, 1))); HIPC(c, M.carve_ctl.reserve(8));
-  SpanUpload up;   // the carve's own, freed with it
-  CarveWork W;
-  memset(&W, 0, sizeof(W));
-  const int rc = up.upload(c, spans, n, M.poses.data(), K, &W.in);
+  const tloam_closed_map_carve_config& g = M.carve_cfg;
+  const size_t nv = std::max<size_t>((size_t)M.info.n_voxels, 1);
+  CmapPassOut R;
+  const int rc = cmap_pass<CarveWork>(
+      c, g.ray_mask ? g.ray_mask : M.cfg.cloud_mask, M.carve_ctl,
+      [&]() -> int {
+        if (M.miss.cap < nv || M.carve_ctl.cap < 8) HIPC(c, hipStreamSynchronize(c->stream));   // (the counts replaced may still be read)
+        HIPC(c, M.miss.reserve(nv)); HIPC(c, M.carve_ctl.reserve(8));
+        return TLOAM_OK;
+      },
+      [&](CarveWork& W) {
+        W.max_range = g.max_range;
+        W.end_margin = g.end_margin;
+        W.radius2 = g.radius * g.radius;
+        W.miss = M.miss.p;
+        return launch_carve(W, c->stream);
+      },
+      &R);
   if (rc != TLOAM_OK) return rc;
-  W.voxel = M.cfg.voxel;
-  for (int a = 0; a < 3; ++a) W.origin[a] = M.cfg.origin[a];
-  W.max_range = M.carve_cfg.max_range;
-  W.end_margin = M.carve_cfg.end_margin;
-  W.radius2 = M.carve_cfg.radius * M.carve_cfg.radius;
-  W.map = M.rows.view();
-  W.nv = (long long)nv;
-  W.miss = M.miss.p;
-  W.ctl = M.carve_ctl.p;
-  I.launches = launch_carve(W, c->stream);
-  HIPC(c, hipGetLastError());
-  unsigned long long ctl[8];
-  HIPC(c, hipMemcpyAsync(ctl, M.carve_ctl.p, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));
-  I.n_keyframes = (int64_t)K;
-  I.n_rays = (int64_t)n;
-  I.skipped_rays = (int64_t)ctl[0];
-  I.steps = (int64_t)ctl[1];
-  I.tested = (int64_t)ctl[2];
-  I.misses = (int64_t)ctl[3];
-  I.voxels_missed = (int64_t)ctl[4];
+  I.launches = R.launches;
+  I.n_keyframes = (int64_t)R.K;
+  I.n_rays = (int64_t)R.n;
+  I.skipped_rays = (int64_t)R.ctl[0];
+  I.steps = (int64_t)R.ctl[1];
+  I.tested = (int64_t)R.ctl[2];
+  I.misses = (int64_t)R.ctl[3];
+  I.voxels_missed = (int64_t)R.ctl[4];
   return TLOAM_OK;
 }
 
@@ -76,9 +66,7 @@ void tloam_closed_map_carve_default_config(tloam_closed_map_carve_config* cfg) {
 
 int tloam_closed_map_carve_configure(tloam_ctx* c, const tloam_closed_map_carve_config* cfg) {
   if (!c || c->nranks > 1) return TLOAM_E_INVALID;
-  tloam_closed_map_carve_config want;
-  if (cfg) want = *cfg;
-  else tloam_closed_map_carve_default_config(&want);
+  const tloam_closed_map_carve_config want = cfg_or_default(cfg, tloam_closed_map_carve_default_config);
   if (!carve_config_ok(want)) return TLOAM_E_INVALID;
   c->cmap.drop_carve();
   c->cmap.carve_cfg = want;
@@ -92,21 +80,8 @@ int tloam_closed_map_get_carve_info(tloam_ctx* c, tloam_closed_map_carve_info* i
 }
 
 int tloam_closed_map_carve(tloam_ctx* c, tloam_closed_map_carve_info* info) {
-  if (!c || c->nranks > 1) return TLOAM_E_INVALID;
-  CmapState& M = c->cmap;
-  if (!M.built) return TLOAM_E_NOT_READY;
-  M.drop_carve();   // from here on a failure leaves no counts
-  tloam_closed_map_carve_info I;
-  memset(&I, 0, sizeof(I));
-  const int rc = carve_body(c, I);
-  if (rc != TLOAM_OK) {
-    (void)hipStreamSynchronize(c->stream);   // (nothing of the carve is in flight when its span table goes)
-    return rc;
-  }
-  M.carve_info = I;
-  M.carved = true;
-  if (info) *info = I;
-  return TLOAM_OK;
+  return cmap_pass_entry(c, &CmapState::drop_carve, &CmapState::carve_info, &CmapState::carved, info,
+                         [&](tloam_closed_map_carve_info& I) { return carve_body(c, I); });
 }
 
 int tloam_closed_map_read_misses(tloam_ctx* c, size_t first, size_t count, int64_t* misses) {

@@ -166,9 +166,7 @@ void tloam_closed_map_default_config(tloam_closed_map_config* cfg) {
 
 int tloam_closed_map_configure(tloam_ctx* c, const tloam_closed_map_config* cfg) {
   if (!c || c->nranks > 1) return TLOAM_E_INVALID;
-  tloam_closed_map_config want;
-  if (cfg) want = *cfg;
-  else tloam_closed_map_default_config(&want);
+  const tloam_closed_map_config want = cfg_or_default(cfg, tloam_closed_map_default_config);
   if (!cmap_config_ok(want)) return TLOAM_E_INVALID;
   CmapState& M = c->cmap;
   M.drop();

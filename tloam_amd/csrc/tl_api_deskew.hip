@@ -123,9 +123,7 @@ void tloam_deskew_default_config(tloam_deskew_config* cfg) {
 
 int tloam_deskew_configure(tloam_ctx* c, const tloam_deskew_config* cfg) {
   if (!c || c->nranks > 1) return TLOAM_E_INVALID;
-  tloam_deskew_config want;
-  if (cfg) want = *cfg;
-  else tloam_deskew_default_config(&want);
+  const tloam_deskew_config want = cfg_or_default(cfg, tloam_deskew_default_config);
   if (!deskew_config_ok(want)) return TLOAM_E_INVALID;
   // (the buffers stay: the registered scan of the last frame may be the deskewed copy)
   c->deskew.cfg = want;

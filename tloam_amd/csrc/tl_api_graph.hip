@@ -290,9 +290,7 @@ void tloam_graph_default_config(tloam_graph_config* cfg) {
 
 int tloam_graph_configure(tloam_ctx* c, const tloam_graph_config* cfg) {
   if (!c || c->nranks > 1) return TLOAM_E_INVALID;
-  tloam_graph_config want;
-  if (cfg) want = *cfg;
-  else tloam_graph_default_config(&want);
+  const tloam_graph_config want = cfg_or_default(cfg, tloam_graph_default_config);
   if (!graph_config_ok(want)) return TLOAM_E_INVALID;
   c->graph.cfg = want;
   c->graph.drop();
@@ -317,9 +315,7 @@ void tloam_graph_robust_default_config(tloam_graph_robust_config* cfg) {
 
 int tloam_graph_robust_configure(tloam_ctx* c, const tloam_graph_robust_config* cfg) {
   if (!c || c->nranks > 1) return TLOAM_E_INVALID;
-  tloam_graph_robust_config want;
-  if (cfg) want = *cfg;
-  else tloam_graph_robust_default_config(&want);
+  const tloam_graph_robust_config want = cfg_or_default(cfg, tloam_graph_robust_default_config);
   if (!robust_config_ok(want)) return TLOAM_E_INVALID;
   c->graph.rcfg = want;
   c->graph.drop();

@@ -1,8 +1,10 @@
 // tl_api_localise.hip -- C ABI of the localisation of a scan in the closed map (include/tloam_hip.h: tloam_closed_map_localise*,
 // _linearise; kernels in tl_localise.hip).
 //
-// A call takes the built closed map with its surfels (CmapState), uploads the scan and the stage's state words, enqueues the
-// voxel records' rebuild when they are stale and max_iterations pairs of (sweep, step) on the context's stream, and waits once.
+// A call takes the built closed map with its surfels (CmapState) and goes through loc_run: the scan uploaded, the voxel records'
+// rebuild enqueued when they are stale, the B states seeded (uploaded as the host forms them from the priors, or formed on the
+// device by the relocalisation's launches), max_iterations pairs of (sweep, step) over the B hypotheses on the context's stream,
+// the states and the logs read back, one wait.  The single call is B = 1.
 // A pair behind the last executed iteration returns on entry, so the launches are the same for every input.  Nothing of the
 // closed map, of a carve's counts, of the surfels or of anything else in the context is written.
 // Compiled with -ffp-contract=off: the prior's quaternion and its matrix are formed here as the restatement forms them.
@@ -113,40 +115,51 @@ void loc_state0(const tloam_closed_map_localise_config& g, const Pose& T0, LocSt
   st->status = TLOAM_LOCALISE_MAX_ITERATIONS;
 }
 
-int localise_body(tloam_ctx* c, const double* points_aos, size_t n, const Pose& T0, LocState* st, tloam_closed_map_localise_info* I) {
-  CmapState& M = c->cmap;
-  const tloam_closed_map_localise_config& g = M.loc_cfg;
-  int rc = loc_begin(c, points_aos, n, false, false, &I->prepared);
-  if (rc != TLOAM_OK) return rc;
-  loc_state0(g, T0, st);
-  HIPC(c, hipMemcpyAsync(M.loc_state.p, st, sizeof(*st), hipMemcpyHostToDevice, c->stream));
-  const LocSweepArgs W = sweep_args(M, n, nullptr, nullptr);
-  for (int k = 0; k < g.max_iterations; ++k) {
-    launch_loc_sweep(W, c->stream);
-    launch_loc_step(step_args(M, n, k), c->stream);
-    I->launches += 2;
-  }
-  HIPC(c, hipGetLastError());
-  HIPC(c, hipMemcpyAsync(st, M.loc_state.p, sizeof(*st), hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));
+// One run of the localiser over B hypotheses of one scan.  seed() leaves the B states on the device -- upload_states, or the
+// launches that form them there, counted into `launches`; more_reads() enqueues what else the caller reads back with the wait
+struct LocRun {
+  std::vector<LocState> st;    // [B] as seeded by the host (upload_states), then as the run left them
+  std::vector<LocLog> log;     // [B][kLocMaxIterations]
+  int prepared = 0, launches = 0;
+  explicit LocRun(size_t B) : st(B), log(B * kLocMaxIterations) {}
+};
+int upload_states(tloam_ctx* c, const LocRun& R) {
+  HIPC(c, hipMemcpyAsync(c->cmap.loc_state.p, R.st.data(), sizeof(LocState) * R.st.size(), hipMemcpyHostToDevice, c->stream));
   return TLOAM_OK;
 }
-
-
-// max_iterations pairs of batched launches over the B states on the device
-void batch_pairs(tloam_ctx* c, size_t n, int B, int32_t* launches) {
+int no_reads() { return TLOAM_OK; }
+template <class Seed, class Reads>
+int loc_run(tloam_ctx* c, const double* points_aos, size_t n, LocRun& R, Seed seed, Reads more_reads) {
   CmapState& M = c->cmap;
-  const LocSweepArgs W = sweep_args(M, n, nullptr, nullptr);
-  for (int k = 0; k < M.loc_cfg.max_iterations; ++k) {
-    launch_loc_sweep_batch(W, B, c->stream);
-    launch_loc_step_batch(step_args(M, n, k), B, c->stream);
-    *launches += 2;
-  }
+  const int B = (int)R.st.size();
+  auto body = [&]() -> int {
+    int rc = loc_begin(c, points_aos, n, false, false, &R.prepared, (size_t)B);
+    if (rc == TLOAM_OK) rc = seed();
+    if (rc != TLOAM_OK) return rc;
+    const LocSweepArgs W = sweep_args(M, n, nullptr, nullptr);
+    for (int k = 0; k < M.loc_cfg.max_iterations; ++k) {
+      launch_loc_sweep(W, B, c->stream);
+      launch_loc_step(step_args(M, n, k), B, c->stream);
+      R.launches += 2;
+    }
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipMemcpyAsync(R.st.data(), M.loc_state.p, sizeof(LocState) * R.st.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(R.log.data(), M.loc_log.p, sizeof(LocLog) * R.log.size(), hipMemcpyDeviceToHost, c->stream));
+    rc = more_reads();
+    if (rc != TLOAM_OK) return rc;
+    HIPC(c, hipStreamSynchronize(c->stream));
+    return TLOAM_OK;
+  };
+  const int rc = body();
+  if (rc != TLOAM_OK) return loc_failed(c, rc);
+  M.loc_ready = true;
+  return TLOAM_OK;
 }
 
 // what a hypothesis's state words and log say, as the single call reports them (info.launches and .prepared are the caller's)
 void loc_report(const CmapState& M, const LocState& st, const LocLog* log, const double* prior, double* pose_out,
                 tloam_closed_map_localise_info* I, std::vector<tloam_closed_map_localise_record>* records) {
+  static_assert(sizeof(LocLog) == sizeof(tloam_closed_map_localise_record), "the log is read back as it is");
   const int it = std::min(std::max(st.iterations, 0), M.loc_cfg.max_iterations);
   records->assign((size_t)it, tloam_closed_map_localise_record{});
   if (it) memcpy(records->data(), log, sizeof(LocLog) * (size_t)it);
@@ -192,9 +205,7 @@ void tloam_closed_map_localise_default_config(tloam_closed_map_localise_config* 
 
 int tloam_closed_map_localise_configure(tloam_ctx* c, const tloam_closed_map_localise_config* cfg) {
   if (!c || c->nranks > 1) return TLOAM_E_INVALID;
-  tloam_closed_map_localise_config want;
-  if (cfg) want = *cfg;
-  else tloam_closed_map_localise_default_config(&want);
+  const tloam_closed_map_localise_config want = cfg_or_default(cfg, tloam_closed_map_localise_default_config);
   if (!config_ok(want)) return TLOAM_E_INVALID;
   CmapState& M = c->cmap;
   if (want.max_sigma != M.loc_cfg.max_sigma || want.min_planarity != M.loc_cfg.min_planarity) M.loc_ready = false;   // the gate
@@ -208,30 +219,15 @@ int tloam_closed_map_localise(tloam_ctx* c, const double* points_aos, size_t n, 
   const int rc0 = pose_out ? loc_check(c, points_aos, n, prior, &T0) : TLOAM_E_INVALID;
   if (rc0 != TLOAM_OK) return rc0;
   CmapState& M = c->cmap;
+  LocRun R(1);
+  loc_state0(M.loc_cfg, T0, &R.st[0]);
+  const int rc = loc_run(c, points_aos, n, R, [&] { return upload_states(c, R); }, no_reads);
+  if (rc != TLOAM_OK) return rc;
   tloam_closed_map_localise_info I;
   memset(&I, 0, sizeof(I));
-  LocState st;
-  const int rc = localise_body(c, points_aos, n, T0, &st, &I);
-  if (rc != TLOAM_OK) return loc_failed(c, rc);
-  M.loc_ready = true;
-  const int it = std::min(std::max(st.iterations, 0), M.loc_cfg.max_iterations);
-  std::vector<LocLog> log((size_t)it);
-  auto read_log = [&]() -> int {
-    HIPC(c, hipMemcpyAsync(log.data(), M.loc_log.p, sizeof(LocLog) * (size_t)it, hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipStreamSynchronize(c->stream));
-    return TLOAM_OK;
-  };
-  if (it && read_log() != TLOAM_OK) return loc_failed(c, TLOAM_E_HIP);
-  M.loc_records.assign((size_t)it, tloam_closed_map_localise_record{});
-  static_assert(sizeof(LocLog) == sizeof(tloam_closed_map_localise_record), "the log is read back as it is");
-  if (it) memcpy(M.loc_records.data(), log.data(), sizeof(LocLog) * (size_t)it);
-  I.status = st.status;
-  I.iterations = it;
-  I.matched = (int64_t)st.sums[kLocTerms];
-  I.used = (int64_t)st.sums[kLocTerms + 1];
-  I.rms = I.used > 0 ? sqrt(2.0 * st.sums[27] / (double)I.used) : 0.0;
-  if (st.status == TLOAM_LOCALISE_DEGENERATE) memcpy(pose_out, prior, sizeof(double) * 16);
-  else pose_to_matrix(st.T, pose_out);
+  loc_report(M, R.st[0], R.log.data(), prior, pose_out, &I, &M.loc_records);
+  I.launches = R.launches;
+  I.prepared = R.prepared;
   if (info) *info = I;
   return TLOAM_OK;
 }
@@ -239,12 +235,7 @@ int tloam_closed_map_localise(tloam_ctx* c, const double* points_aos, size_t n, 
 int tloam_closed_map_localise_log(tloam_ctx* c, size_t capacity, size_t* n, tloam_closed_map_localise_record* records) {
   if (n) *n = 0;
   if (!c || !n || c->nranks > 1) return TLOAM_E_INVALID;
-  const std::vector<tloam_closed_map_localise_record>& R = c->cmap.loc_records;
-  *n = R.size();
-  if (!records || R.empty()) return TLOAM_OK;
-  if (capacity < R.size()) return TLOAM_E_INVALID;
-  memcpy(records, R.data(), sizeof(R[0]) * R.size());
-  return TLOAM_OK;
+  return copy_list(c->cmap.loc_records, capacity, n, records);
 }
 
 int tloam_closed_map_linearise(tloam_ctx* c, const double* points_aos, size_t n, const double* pose, double tau, int32_t* ids,
@@ -262,8 +253,8 @@ int tloam_closed_map_linearise(tloam_ctx* c, const double* points_aos, size_t n,
   st.tau = tau;
   auto body = [&]() -> int {
     HIPC(c, hipMemcpyAsync(M.loc_state.p, &st, sizeof(st), hipMemcpyHostToDevice, c->stream));
-    launch_loc_sweep(sweep_args(M, n, ids ? M.loc_ids.p : nullptr, residuals ? M.loc_res.p : nullptr), c->stream);
-    launch_loc_step(step_args(M, n, -1), c->stream);
+    launch_loc_sweep(sweep_args(M, n, ids ? M.loc_ids.p : nullptr, residuals ? M.loc_res.p : nullptr), 1, c->stream);
+    launch_loc_step(step_args(M, n, -1), 1, c->stream);
     HIPC(c, hipGetLastError());
     HIPC(c, hipMemcpyAsync(&st, M.loc_state.p, sizeof(st), hipMemcpyDeviceToHost, c->stream));
     if (ids) HIPC(c, hipMemcpyAsync(ids, M.loc_ids.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
@@ -283,41 +274,25 @@ int tloam_closed_map_linearise(tloam_ctx* c, const double* points_aos, size_t n,
 int tloam_closed_map_localise_batch(tloam_ctx* c, const double* points_aos, size_t n, const double* priors, size_t B,
                                     double* poses_out, tloam_closed_map_localise_info* infos, int32_t* best_out) {
   if (!priors || !poses_out || !infos || !best_out || B == 0 || B > (size_t)kLocMaxBatch) return TLOAM_E_INVALID;
-  std::vector<LocState> st(B);
-  {
-    Pose T0;
-    for (size_t h = 0; h < B; ++h) {   // every prior before anything is touched
-      const int rc0 = loc_check(c, points_aos, n, priors + 16 * h, &T0);
-      if (rc0 != TLOAM_OK) return rc0;
-      loc_state0(c->cmap.loc_cfg, T0, &st[h]);
-    }
+  LocRun R(B);
+  Pose T0;
+  for (size_t h = 0; h < B; ++h) {   // every prior before anything is touched
+    const int rc0 = loc_check(c, points_aos, n, priors + 16 * h, &T0);
+    if (rc0 != TLOAM_OK) return rc0;
+    loc_state0(c->cmap.loc_cfg, T0, &R.st[h]);
   }
   CmapState& M = c->cmap;
-  int prepared = 0, launches = 0;
-  std::vector<LocLog> log(B * kLocMaxIterations);
-  auto body = [&]() -> int {
-    const int rc = loc_begin(c, points_aos, n, false, false, &prepared, B);
-    if (rc != TLOAM_OK) return rc;
-    HIPC(c, hipMemcpyAsync(M.loc_state.p, st.data(), sizeof(LocState) * B, hipMemcpyHostToDevice, c->stream));
-    batch_pairs(c, n, (int)B, &launches);
-    HIPC(c, hipGetLastError());
-    HIPC(c, hipMemcpyAsync(st.data(), M.loc_state.p, sizeof(LocState) * B, hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipMemcpyAsync(log.data(), M.loc_log.p, sizeof(LocLog) * log.size(), hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipStreamSynchronize(c->stream));
-    return TLOAM_OK;
-  };
-  const int rc = body();
-  if (rc != TLOAM_OK) return loc_failed(c, rc);
-  M.loc_ready = true;
+  const int rc = loc_run(c, points_aos, n, R, [&] { return upload_states(c, R); }, no_reads);
+  if (rc != TLOAM_OK) return rc;
   M.loc_batch_records.resize(B);
   for (size_t h = 0; h < B; ++h) {
     memset(&infos[h], 0, sizeof(infos[h]));
-    loc_report(M, st[h], log.data() + h * kLocMaxIterations, priors + 16 * h, poses_out + 16 * h, &infos[h],
+    loc_report(M, R.st[h], R.log.data() + h * kLocMaxIterations, priors + 16 * h, poses_out + 16 * h, &infos[h],
                &M.loc_batch_records[h]);
-    infos[h].launches = launches;
-    infos[h].prepared = prepared;
+    infos[h].launches = R.launches;
+    infos[h].prepared = R.prepared;
   }
-  *best_out = loc_pick(st.data(), nullptr, (int)B);
+  *best_out = loc_pick(R.st.data(), nullptr, (int)B);
   return TLOAM_OK;
 }
 
@@ -325,12 +300,7 @@ int tloam_closed_map_localise_batch_log(tloam_ctx* c, size_t hypothesis, size_t 
                                         tloam_closed_map_localise_record* records) {
   if (n) *n = 0;
   if (!c || !n || c->nranks > 1 || hypothesis >= c->cmap.loc_batch_records.size()) return TLOAM_E_INVALID;
-  const std::vector<tloam_closed_map_localise_record>& R = c->cmap.loc_batch_records[hypothesis];
-  *n = R.size();
-  if (!records || R.empty()) return TLOAM_OK;
-  if (capacity < R.size()) return TLOAM_E_INVALID;
-  memcpy(records, R.data(), sizeof(R[0]) * R.size());
-  return TLOAM_OK;
+  return copy_list(c->cmap.loc_batch_records[hypothesis], capacity, n, records);
 }
 
 void tloam_closed_map_relocalise_default_config(tloam_closed_map_relocalise_config* cfg) {
@@ -342,9 +312,7 @@ void tloam_closed_map_relocalise_default_config(tloam_closed_map_relocalise_conf
 
 int tloam_closed_map_relocalise_configure(tloam_ctx* c, const tloam_closed_map_relocalise_config* cfg) {
   if (!c || c->nranks > 1) return TLOAM_E_INVALID;
-  tloam_closed_map_relocalise_config want;
-  if (cfg) want = *cfg;
-  else tloam_closed_map_relocalise_default_config(&want);
+  tloam_closed_map_relocalise_config want = cfg_or_default(cfg, tloam_closed_map_relocalise_default_config);
   if (!reloc_config_ok(want)) return TLOAM_E_INVALID;
   want.reserved0 = 0;
   c->cmap.reloc_cfg = want;
@@ -364,13 +332,9 @@ int tloam_closed_map_relocalise(tloam_ctx* c, const double* points_aos, size_t n
   const tloam_place_config& g = P.cfg;
   const int B = (int)std::min<int64_t>(r.num_candidates, K);
   const size_t R = (size_t)g.n_rings, S = (size_t)g.n_sectors;
-  int prepared = 0, launches = 0;
-  std::vector<LocState> st((size_t)B);
+  LocRun run((size_t)B);
   std::vector<RelocHyp> hyp((size_t)B);
-  std::vector<LocLog> log((size_t)B * kLocMaxIterations);
-  auto body = [&]() -> int {
-    const int rc = loc_begin(c, points_aos, n, false, false, &prepared, (size_t)B);
-    if (rc != TLOAM_OK) return rc;
+  auto seed = [&]() -> int {   // the place search's candidates made the B states, on the device
     HIPC(c, P.s_desc.reserve(R * S)); HIPC(c, P.s_rkey.reserve(R)); HIPC(c, P.s_skey.reserve(S));
     HIPC(c, M.reloc_cand.reserve(kLocMaxBatch)); HIPC(c, M.reloc_hyp.reserve(kLocMaxBatch));
     HIPC(c, M.reloc_poses.reserve(16 * (size_t)K));
@@ -398,18 +362,14 @@ int tloam_closed_map_relocalise(tloam_ctx* c, const double* points_aos, size_t n
     Q.max_residual0 = M.loc_cfg.max_residual0; Q.min_residual = M.loc_cfg.min_residual;
     Q.hyp = M.reloc_hyp.p; Q.st = M.loc_state.p;
     launch_reloc_priors(Q, c->stream);
-    launches += 5;
-    batch_pairs(c, n, B, &launches);
-    HIPC(c, hipGetLastError());
-    HIPC(c, hipMemcpyAsync(st.data(), M.loc_state.p, sizeof(LocState) * (size_t)B, hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipMemcpyAsync(hyp.data(), M.reloc_hyp.p, sizeof(RelocHyp) * (size_t)B, hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipMemcpyAsync(log.data(), M.loc_log.p, sizeof(LocLog) * log.size(), hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipStreamSynchronize(c->stream));
+    run.launches += 5;
     return TLOAM_OK;
   };
-  const int rc = body();
-  if (rc != TLOAM_OK) return loc_failed(c, rc);
-  M.loc_ready = true;
+  const int rc = loc_run(c, points_aos, n, run, seed, [&]() -> int {
+    HIPC(c, hipMemcpyAsync(hyp.data(), M.reloc_hyp.p, sizeof(RelocHyp) * (size_t)B, hipMemcpyDeviceToHost, c->stream));
+    return TLOAM_OK;
+  });
+  if (rc != TLOAM_OK) return rc;
   M.reloc_hyps.assign((size_t)B, tloam_closed_map_relocalise_hypothesis{});
   M.loc_batch_records.resize((size_t)B);
   std::vector<int> skip((size_t)B);
@@ -427,14 +387,14 @@ int tloam_closed_map_relocalise(tloam_ctx* c, const double* points_aos, size_t n
       H.localise.status = TLOAM_LOCALISE_DEGENERATE;
       M.loc_batch_records[(size_t)h].clear();
     } else {
-      loc_report(M, st[(size_t)h], log.data() + (size_t)h * kLocMaxIterations, d.prior, H.pose_colmajor, &H.localise,
+      loc_report(M, run.st[(size_t)h], run.log.data() + (size_t)h * kLocMaxIterations, d.prior, H.pose_colmajor, &H.localise,
                  &M.loc_batch_records[(size_t)h]);
-      if (!have_finite) { finite = st[(size_t)h].sums[kLocFinite]; have_finite = true; }
+      if (!have_finite) { finite = run.st[(size_t)h].sums[kLocFinite]; have_finite = true; }
     }
     H.localise.launches = 2 * M.loc_cfg.max_iterations;
-    H.localise.prepared = prepared;
+    H.localise.prepared = run.prepared;
   }
-  int best = loc_pick(st.data(), skip.data(), B);
+  int best = loc_pick(run.st.data(), skip.data(), B);
   if (best >= 0) {
     const tloam_closed_map_localise_info& L = M.reloc_hyps[(size_t)best].localise;
     if (!((double)L.used >= r.min_used_ratio * finite && L.rms <= r.max_rms)) best = -1;
@@ -444,7 +404,7 @@ int tloam_closed_map_relocalise(tloam_ctx* c, const double* points_aos, size_t n
   I.status = best >= 0 ? TLOAM_RELOCALISE_FOUND : TLOAM_RELOCALISE_NOT_FOUND;
   I.n_hypotheses = B;
   I.best = best;
-  I.launches = launches;
+  I.launches = run.launches;
   I.keyframe = -1;
   if (best >= 0) {
     const tloam_closed_map_relocalise_hypothesis& H = M.reloc_hyps[(size_t)best];
@@ -460,12 +420,7 @@ int tloam_closed_map_relocalise_hypotheses(tloam_ctx* c, size_t capacity, size_t
                                            tloam_closed_map_relocalise_hypothesis* hypotheses) {
   if (n) *n = 0;
   if (!c || !n || c->nranks > 1) return TLOAM_E_INVALID;
-  const std::vector<tloam_closed_map_relocalise_hypothesis>& H = c->cmap.reloc_hyps;
-  *n = H.size();
-  if (!hypotheses || H.empty()) return TLOAM_OK;
-  if (capacity < H.size()) return TLOAM_E_INVALID;
-  memcpy(hypotheses, H.data(), sizeof(H[0]) * H.size());
-  return TLOAM_OK;
+  return copy_list(c->cmap.reloc_hyps, capacity, n, hypotheses);
 }
 
 }  // extern "C"

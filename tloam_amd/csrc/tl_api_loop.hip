@@ -247,9 +247,7 @@ void tloam_loop_default_config(tloam_loop_config* cfg) {
 
 int tloam_loop_configure(tloam_ctx* c, const tloam_loop_config* cfg) {
   if (!c || c->nranks > 1) return TLOAM_E_INVALID;
-  tloam_loop_config want;
-  if (cfg) want = *cfg;
-  else tloam_loop_default_config(&want);
+  const tloam_loop_config want = cfg_or_default(cfg, tloam_loop_default_config);
   if (!loop_config_ok(want)) return TLOAM_E_INVALID;
   HIPC(c, hipSetDevice(c->device));
   HIPC(c, hipStreamSynchronize(c->stream));

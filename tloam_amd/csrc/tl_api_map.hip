@@ -159,9 +159,7 @@ void tloam_map_default_config(tloam_map_config* cfg) {
 
 int tloam_map_configure(tloam_ctx* c, const tloam_map_config* cfg) {
   if (!c || c->nranks > 1) return TLOAM_E_INVALID;
-  tloam_map_config want;
-  if (cfg) want = *cfg;
-  else tloam_map_default_config(&want);
+  const tloam_map_config want = cfg_or_default(cfg, tloam_map_default_config);
   if (!map_config_ok(want)) return TLOAM_E_INVALID;
   HIPC(c, hipSetDevice(c->device));
   HIPC(c, hipStreamSynchronize(c->stream));

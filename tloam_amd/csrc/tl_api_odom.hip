@@ -266,9 +266,7 @@ void tloam_odom_default_config(tloam_odom_config* cfg) {
 
 int tloam_odometry_reset(tloam_ctx* c, const tloam_odom_config* cfg, const double init[16]) {
   if (!c) return TLOAM_E_INVALID;
-  tloam_odom_config want;
-  if (cfg) want = *cfg;
-  else tloam_odom_default_config(&want);
+  const tloam_odom_config want = cfg_or_default(cfg, tloam_odom_default_config);
   if (!odom_config_ok(want)) return TLOAM_E_INVALID;
   double T[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   if (init) {

@@ -239,9 +239,7 @@ void tloam_place_default_config(tloam_place_config* cfg) {
 
 int tloam_place_configure(tloam_ctx* c, const tloam_place_config* cfg) {
   if (!c || c->nranks > 1) return TLOAM_E_INVALID;
-  tloam_place_config want;
-  if (cfg) want = *cfg;
-  else tloam_place_default_config(&want);
+  const tloam_place_config want = cfg_or_default(cfg, tloam_place_default_config);
   if (!place_config_ok(want, true)) return TLOAM_E_INVALID;
   HIPC(c, hipSetDevice(c->device));
   HIPC(c, hipStreamSynchronize(c->stream));

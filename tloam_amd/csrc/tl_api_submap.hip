@@ -132,9 +132,7 @@ int tloam_submap_init(tloam_ctx* c, const tloam_submap_config* cfg, const double
       n_planar > kMaxPoints || n_sphere > kMaxPoints || n_edge > kMaxPoints || n_ground > kMaxPoints)
     return TLOAM_E_INVALID;
   HIPC(c, hipSetDevice(c->device));
-  tloam_submap_config want;
-  if (cfg) want = *cfg;
-  else tloam_submap_default_config(&want);
+  const tloam_submap_config want = cfg_or_default(cfg, tloam_submap_default_config);
   if (!tlh::submap_config_ok(want))
     return TLOAM_E_INVALID;  // "[VoxelDownSample] voxel_size <= 0." (PointCloud2.cpp:361-363); the submap in place stays
   return tlh::submap_init_body(c, want, planar, n_planar, sphere, n_sphere, edge, n_edge, ground, n_ground, hipMemcpyHostToDevice);

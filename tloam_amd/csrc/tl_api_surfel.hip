@@ -17,42 +17,33 @@ namespace {
 // the enqueue, the wait and the counters of a pass; the previous surfels have been dropped
 int surfel_body(tloam_ctx* c, tloam_closed_map_surfel_info& I) {
   CmapState& M = c->cmap;
-  const PlaceState& P = c->place;
-  const size_t K = M.poses.size() / 16;   // the build's keyframes: later ones add nothing
-  std::vector<CmapSpan> spans;            // the build's span table
-  long long n = 0;
-  cmap_span_table(P, K, M.cfg.cloud_mask, &spans, &n, nullptr);
-  const size_t nv = (size_t)M.info.n_voxels, cap = std::max<size_t>(M.rows.cap, 1);
-  HIPC(c, hipSetDevice(c->device));
-  if (M.surfel_sums.cap < kSurfelSums * cap || M.surfel_over.cap < std::max<size_t>(K, 1) || M.surfel_ctl.cap < 8)
-    HIPC(c, hipStreamSynchronize(c->stream));   // (the arrays replaced may still be read)
-  HIPC(c, M.surfel_sums.reserve(kSurfelSums * cap)); HIPC(c, M.surfel_nrm.reserve(3 * cap)); HIPC(c, M.surfel_ev.reserve(3 * cap));
-  HIPC(c, M.surfel_over.reserve(std::max<size_t>(K, 1))); HIPC(c, M.surfel_ctl.reserve(8));
-  SpanUpload up;   // the pass's own, freed with it
-  SurfelWork W;
-  memset(&W, 0, sizeof(W));
-  const int rc = up.upload(c, spans, n, M.poses.data(), K, &W.in);
+  const size_t cap = std::max<size_t>(M.rows.cap, 1), K1 = std::max<size_t>(M.poses.size() / 16, 1);
+  CmapPassOut R;
+  const int rc = cmap_pass<SurfelWork>(
+      c, M.cfg.cloud_mask, M.surfel_ctl,   // the build's span table
+      [&]() -> int {
+        if (M.surfel_sums.cap < kSurfelSums * cap || M.surfel_over.cap < K1 || M.surfel_ctl.cap < 8)
+          HIPC(c, hipStreamSynchronize(c->stream));   // (the arrays replaced may still be read)
+        HIPC(c, M.surfel_sums.reserve(kSurfelSums * cap)); HIPC(c, M.surfel_nrm.reserve(3 * cap)); HIPC(c, M.surfel_ev.reserve(3 * cap));
+        HIPC(c, M.surfel_over.reserve(K1)); HIPC(c, M.surfel_ctl.reserve(8));
+        return TLOAM_OK;
+      },
+      [&](SurfelWork& W) {
+        W.kf_over = M.surfel_over.p;
+        W.runs = getenv("TLOAM_SURFEL_NO_RUNS") ? 0 : 1;   // A/B of the wave's run aggregation, read per pass
+        W.min_points = M.surfel_cfg.min_points;
+        W.sums = M.surfel_sums.p;
+        W.normal = M.surfel_nrm.p;
+        W.eval = M.surfel_ev.p;
+        return launch_surfels(W, c->stream);
+      },
+      &R);
   if (rc != TLOAM_OK) return rc;
-  W.kf_over = M.surfel_over.p;
-  W.voxel = M.cfg.voxel;
-  for (int a = 0; a < 3; ++a) W.origin[a] = M.cfg.origin[a];
-  W.map = M.rows.view();
-  W.nv = (long long)nv;
-  W.runs = getenv("TLOAM_SURFEL_NO_RUNS") ? 0 : 1;   // A/B of the wave's run aggregation, read per pass
-  W.min_points = M.surfel_cfg.min_points;
-  W.sums = M.surfel_sums.p;
-  W.normal = M.surfel_nrm.p;
-  W.eval = M.surfel_ev.p;
-  W.ctl = M.surfel_ctl.p;
-  I.launches = launch_surfels(W, c->stream);
-  HIPC(c, hipGetLastError());
-  unsigned long long ctl[8];
-  HIPC(c, hipMemcpyAsync(ctl, M.surfel_ctl.p, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));
-  I.n_keyframes = (int64_t)K;
-  I.n_points = (int64_t)ctl[0];
-  I.orphan_points = (int64_t)ctl[1];
-  I.solved_voxels = (int64_t)ctl[2];
+  I.launches = R.launches;
+  I.n_keyframes = (int64_t)R.K;
+  I.n_points = (int64_t)R.ctl[0];
+  I.orphan_points = (int64_t)R.ctl[1];
+  I.solved_voxels = (int64_t)R.ctl[2];
   return TLOAM_OK;
 }
 
@@ -68,9 +59,7 @@ void tloam_closed_map_surfel_default_config(tloam_closed_map_surfel_config* cfg)
 
 int tloam_closed_map_surfel_configure(tloam_ctx* c, const tloam_closed_map_surfel_config* cfg) {
   if (!c || c->nranks > 1) return TLOAM_E_INVALID;
-  tloam_closed_map_surfel_config want;
-  if (cfg) want = *cfg;
-  else tloam_closed_map_surfel_default_config(&want);
+  const tloam_closed_map_surfel_config want = cfg_or_default(cfg, tloam_closed_map_surfel_default_config);
   if (want.min_points < 3) return TLOAM_E_INVALID;
   c->cmap.drop_surfels();
   c->cmap.surfel_cfg = want;
@@ -84,21 +73,8 @@ int tloam_closed_map_get_surfel_info(tloam_ctx* c, tloam_closed_map_surfel_info*
 }
 
 int tloam_closed_map_surfels(tloam_ctx* c, tloam_closed_map_surfel_info* info) {
-  if (!c || c->nranks > 1) return TLOAM_E_INVALID;
-  CmapState& M = c->cmap;
-  if (!M.built) return TLOAM_E_NOT_READY;
-  M.drop_surfels();   // from here on a failure leaves no surfels
-  tloam_closed_map_surfel_info I;
-  memset(&I, 0, sizeof(I));
-  const int rc = surfel_body(c, I);
-  if (rc != TLOAM_OK) {
-    (void)hipStreamSynchronize(c->stream);   // (nothing of the pass is in flight when its span table goes)
-    return rc;
-  }
-  M.surfel_info = I;
-  M.surfeled = true;
-  if (info) *info = I;
-  return TLOAM_OK;
+  return cmap_pass_entry(c, &CmapState::drop_surfels, &CmapState::surfel_info, &CmapState::surfeled, info,
+                         [&](tloam_closed_map_surfel_info& I) { return surfel_body(c, I); });
 }
 
 int tloam_closed_map_read_moments(tloam_ctx* c, size_t first, size_t count, int64_t* out) {

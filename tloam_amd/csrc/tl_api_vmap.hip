@@ -188,9 +188,7 @@ void tloam_voxel_map_default_config(tloam_voxel_map_config* cfg) {
 
 int tloam_voxel_map_configure(tloam_ctx* c, const tloam_voxel_map_config* cfg) {
   if (!c || c->nranks > 1) return TLOAM_E_INVALID;
-  tloam_voxel_map_config want;
-  if (cfg) want = *cfg;
-  else tloam_voxel_map_default_config(&want);
+  const tloam_voxel_map_config want = cfg_or_default(cfg, tloam_voxel_map_default_config);
   if (!vmap_config_ok(want)) return TLOAM_E_INVALID;
   HIPC(c, hipSetDevice(c->device));
   HIPC(c, hipStreamSynchronize(c->stream));

@@ -734,10 +734,10 @@ struct LocRecord {            // what a probe hit reads of a voxel: one 64-byte 
 };
 static_assert(sizeof(LocRecord) == 64, "a voxel record is one cache line");
 constexpr int kLocTerms = 28;       // H's upper triangle by rows (21), g (6), cost
-constexpr int kLocRow = 32;         // a block's partial row: the terms, matched, used (as doubles: exact below 2^53), two unused
+constexpr int kLocRow = 32;         // a block's partial row: the terms, matched, used, finite (the counts as doubles: exact below 2^53), one unused
 constexpr int kLocMaxIterations = 64;
 constexpr int kLocMaxBatch = 32;    // hypotheses of one scan in one set of launches (tloam_closed_map_localise_batch)
-constexpr int kLocFinite = 30;      // the batched sweep's row slot of the scan's finite points (unused, zero, in the single form)
+constexpr int kLocFinite = 30;      // the row slot of the scan's finite points
 struct LocLog {               // tloam_closed_map_localise_record
   double pose[16];
   double tau, cost;
@@ -788,11 +788,10 @@ struct LocStepArgs {
 };
 inline int loc_blocks(long long n) { return (int)((n + 255) / 256); }
 void launch_loc_prepare(const LocPrepArgs& A, hipStream_t s);
-void launch_loc_sweep(const LocSweepArgs& A, hipStream_t s);
-void launch_loc_step(const LocStepArgs& A, hipStream_t s);
-// B hypotheses: st [B], partial [B][blocks][kLocRow], log [B][kLocMaxIterations]; ids and res unused
-void launch_loc_sweep_batch(const LocSweepArgs& A, int B, hipStream_t s);
-void launch_loc_step_batch(const LocStepArgs& A, int B, hipStream_t s);
+// B hypotheses (1: the single call, a linearise): st [B], partial [B][blocks][kLocRow], log [B][kLocMaxIterations]; ids and
+// res are written when non-null, which only B = 1 callers pass
+void launch_loc_sweep(const LocSweepArgs& A, int B, hipStream_t s);
+void launch_loc_step(const LocStepArgs& A, int B, hipStream_t s);
 
 // relocalisation: a candidate of the place search made a hypothesis of the batched localiser
 struct PlaceCandidate;

@@ -722,6 +722,24 @@ inline int kind_active(const tloam_tls_config& c, int k) {
   return 0;
 }
 inline size_t round_up(size_t v, size_t m) { return (v + m - 1) / m * m; }
+// what a configure entry point is asked for: *cfg, or what its default_config fills in when cfg is null
+template <class Cfg>
+Cfg cfg_or_default(const Cfg* cfg, void (*default_fn)(Cfg*)) {
+  Cfg want;
+  if (cfg) want = *cfg;
+  else default_fn(&want);
+  return want;
+}
+// a list getter over a host vector (the caller has checked n): *n is the list's length, whatever follows; the list is copied
+// when `out` is given and holds it.  A null `out` or an empty list is TLOAM_OK, a short capacity TLOAM_E_INVALID
+template <class T>
+int copy_list(const std::vector<T>& list, size_t capacity, size_t* n, T* out) {
+  *n = list.size();
+  if (!out || list.empty()) return TLOAM_OK;
+  if (capacity < list.size()) return TLOAM_E_INVALID;
+  memcpy(out, list.data(), sizeof(T) * list.size());
+  return TLOAM_OK;
+}
 
 // `fresh` holds `want` rows, the first `keep` of `cur` copied into it device to device on the stream
 template <class T>
@@ -936,6 +954,62 @@ struct SpanUpload {
   // both uploaded on the context's stream; *in: what the kernels take (arena, span, nspan, nkf, n, pose)
   int upload(tloam_ctx* c, const std::vector<tl::CmapSpan>& spans, long long n, const double* poses, size_t K, tl::SpanInput* in);
 };
+// One pass over the points the closed map was built from (the carve, the surfels): the span table for `mask` over the build's
+// keyframes uploaded beside the build's poses, the fields every pass's Work has filled (in, voxel, origin, map, nv, ctl), the
+// launches of fill_and_launch(W), which fills the rest and returns their number, the eight words of `ctl` read back, one wait.
+// reserve() sizes the pass's arrays, `ctl` among them, after waiting when one that it replaces may still be read
+struct CmapPassOut {
+  unsigned long long ctl[8];
+  size_t K;        // the build's keyframes: later ones add nothing
+  long long n;     // the points of all spans
+  int launches;
+};
+template <class Work, class Reserve, class Launch>
+int cmap_pass(tloam_ctx* c, int mask, const DBuf<unsigned long long>& ctl, Reserve reserve, Launch fill_and_launch, CmapPassOut* out) {
+  const CmapState& M = c->cmap;
+  out->K = M.poses.size() / 16;
+  std::vector<tl::CmapSpan> spans;
+  cmap_span_table(c->place, out->K, mask, &spans, &out->n, nullptr);
+  HIPC(c, hipSetDevice(c->device));
+  int rc = reserve();
+  if (rc != TLOAM_OK) return rc;
+  SpanUpload up;   // the pass's own, freed with it
+  Work W;
+  memset(&W, 0, sizeof(W));
+  rc = up.upload(c, spans, out->n, M.poses.data(), out->K, &W.in);
+  if (rc != TLOAM_OK) return rc;
+  W.voxel = M.cfg.voxel;
+  for (int a = 0; a < 3; ++a) W.origin[a] = M.cfg.origin[a];
+  W.map = M.rows.view();
+  W.nv = (long long)M.info.n_voxels;
+  W.ctl = ctl.p;
+  out->launches = fill_and_launch(W);
+  HIPC(c, hipGetLastError());
+  HIPC(c, hipMemcpyAsync(out->ctl, ctl.p, sizeof(out->ctl), hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  return TLOAM_OK;
+}
+// ... and its public entry point: the context and the built map checked, the previous result dropped (from there on a failure
+// leaves none), body(I) run, the stream drained when it fails (nothing of the pass is in flight when its span table goes), its
+// info and flag committed when it succeeds
+template <class Info, class Body>
+int cmap_pass_entry(tloam_ctx* c, void (CmapState::*drop)(), Info CmapState::*last, bool CmapState::*ran, Info* info, Body body) {
+  if (!c || c->nranks > 1) return TLOAM_E_INVALID;
+  CmapState& M = c->cmap;
+  if (!M.built) return TLOAM_E_NOT_READY;
+  (M.*drop)();
+  Info I;
+  memset(&I, 0, sizeof(I));
+  const int rc = body(I);
+  if (rc != TLOAM_OK) {
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+  }
+  M.*last = I;
+  M.*ran = true;
+  if (info) *info = I;
+  return TLOAM_OK;
+}
 // ids [first, first + count) of a side array of the built closed map (`ran`: the stage that fills it has run): TLOAM_OK when the
 // range is one
 int cmap_side_range(const tloam_ctx* c, bool ran, size_t first, size_t count);

@@ -4,20 +4,19 @@
 // Launches (no host synchronisation between them; nothing of the closed map, the carve or the surfels is written):
 //   k_loc_prepare   grid x 256   per voxel one 64-byte record {c, n, eligible}: a probe hit then costs one cache line; eligible
 //                                is tl_voxel.hpp's surfel_gate, the gate of the surfels' box read
-//   k_loc_sweep     grid x 256   per point: transform, quantise, 27 read-only probes of the closed map's slot table, the nearest
-//                                eligible centroid, residual, truncation; the 28 terms and the two counts summed over the wave
-//                                by shuffles and over the block's four waves through LDS; one partial row per block
-//   k_loc_step      1 x 64       the partial rows added in block order, the degeneracy tests, the 6 x 6 Cholesky, the pose
-//                                update, the log record and the `done` word
-// and for B hypotheses of one scan (tloam_closed_map_localise_batch, _relocalise):
-//   k_loc_sweep_batch  (grid, B) x 256   k_loc_sweep's body, the hypothesis on blockIdx.y: its own state words and partial rows;
-//                                        one more sum, the scan's finite points (row slot kLocFinite)
-//   k_loc_step_batch   B x 64            k_loc_step's body, a wave per hypothesis
-// Both forms run one device body, and a hypothesis's sums are ordered by the point index alone, so hypothesis h of a batch has
-// the bits of the single call from its prior.
+//   k_loc_sweep     (grid, B) x 256   per point: transform, quantise, 27 read-only probes of the closed map's slot table, the
+//                                     nearest eligible centroid, residual, truncation; the 28 terms, the two counts and the scan's
+//                                     finite points (row slot kLocFinite) summed over the wave by shuffles and over the block's
+//                                     four waves through LDS; one partial row per block
+//   k_loc_step      B x 64            the partial rows added in block order, the degeneracy tests, the 6 x 6 Cholesky, the pose
+//                                     update, the log record and the `done` word
+// B hypotheses of one scan (tloam_closed_map_localise_batch, _relocalise) share the launches: hypothesis h
+// is blockIdx.y of the sweep and blockIdx.x (a wave) of the step, with its own state words st[h], its own partial rows
+// partial[h][block] and its own log[h][kLocMaxIterations].  tloam_closed_map_localise and _linearise are B = 1.  A hypothesis's
+// sums are ordered by the point index alone, so hypothesis h of a batch has the bits of the single call from its prior.
 // A sweep or a step that finds `done` set returns on entry (a wave-uniform branch), so a call is the same launches for every
 // input.  No block waits on another block.  No floating-point atomics: the order of every sum is fixed by the point index
-// (lane, wave, block), so two calls give the same bits.
+// (lane, wave, block, then the blocks' rows in block order in the step), so two calls give the same bits.
 //
 // Compiled with -ffp-contract=off.  The arithmetic (tests/closed_map_localise_np.py restates it), per point p and matrix M:
 //   E = map_transform_point(M, p),  (i, q) = vmap_quantise(E);  for dz, dy, dx in -1 .. 1 (dx innermost) the voxel of cell
@@ -52,12 +51,12 @@ __global__ __launch_bounds__(256) void k_loc_prepare(LocPrepArgs A) {
   A.rec[id] = R;
 }
 
-// The sweep of one block of one hypothesis: the body of k_loc_sweep and of k_loc_sweep_batch, so that a hypothesis of a batch
-// rounds as the single call does.  NT sums are carried: the terms, matched, used and (kFinite) the scan's finite points
-template <bool kFinite>
-__device__ __forceinline__ void loc_sweep_body(const LocSweepArgs& W, const LocState* st, double* partial,
-                                               double (*s_row)[kLocRow]) {
-  constexpr int NT = kLocTerms + 2 + (kFinite ? 1 : 0);
+// The sweep of one block of hypothesis blockIdx.y.  NT sums are carried: the terms, matched, used and the scan's finite points
+__global__ __launch_bounds__(256) void k_loc_sweep(LocSweepArgs W) {
+  __shared__ double s_row[4][kLocRow];
+  constexpr int NT = kLocFinite + 1;
+  const LocState* st = W.st + blockIdx.y;
+  double* partial = W.partial + (size_t)blockIdx.y * gridDim.x * kLocRow;
   if (st->done) return;   // (the same word for every thread of the hypothesis's blocks)
   const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -67,12 +66,10 @@ __device__ __forceinline__ void loc_sweep_body(const LocSweepArgs& W, const LocS
   if (g < W.n) {
     const double* M = st->M;
     const double tau = st->tau;
-    if (kFinite) {
-      const double px = W.pts[3 * g], py = W.pts[3 * g + 1], pz = W.pts[3 * g + 2];
-      if (px - px == 0.0 && py - py == 0.0 && pz - pz == 0.0) t[kLocFinite] = 1.0;
-    }
+    const double px = W.pts[3 * g], py = W.pts[3 * g + 1], pz = W.pts[3 * g + 2];
+    if (px - px == 0.0 && py - py == 0.0 && pz - pz == 0.0) t[kLocFinite] = 1.0;
     double E[3];
-    map_transform_point(M, W.pts[3 * g], W.pts[3 * g + 1], W.pts[3 * g + 2], &E[0], &E[1], &E[2]);
+    map_transform_point(M, px, py, pz, &E[0], &E[1], &E[2]);
     unsigned long long key;
     unsigned q[3];
     int best = -1;
@@ -138,17 +135,6 @@ __device__ __forceinline__ void loc_sweep_body(const LocSweepArgs& W, const LocS
   }
 }
 
-__global__ __launch_bounds__(256) void k_loc_sweep(LocSweepArgs W) {
-  __shared__ double s_row[4][kLocRow];
-  loc_sweep_body<false>(W, W.st, W.partial, s_row);
-}
-
-// hypothesis blockIdx.y of a batch: its own state words and its own gridDim.x partial rows; ids and res are not written
-__global__ __launch_bounds__(256) void k_loc_sweep_batch(LocSweepArgs W) {
-  __shared__ double s_row[4][kLocRow];
-  loc_sweep_body<true>(W, W.st + blockIdx.y, W.partial + (size_t)blockIdx.y * gridDim.x * kLocRow, s_row);
-}
-
 // H d = -g by Cholesky; false: a pivot is not > ratio * H_kk
 __device__ bool loc_solve6(const double* sums, double ratio, double d[6]) {
   double H[6][6], L[6][6];
@@ -190,9 +176,13 @@ __device__ bool loc_solve6(const double* sums, double ratio, double d[6]) {
   return true;
 }
 
-// The step of one hypothesis by one wave: the body of k_loc_step and of k_loc_step_batch
-__device__ __forceinline__ void loc_step_body(const LocStepArgs& A, LocState* S, const double* partial, LocLog* log,
-                                              double* s_sum) {
+// The step of hypothesis blockIdx.x by one wave
+__global__ __launch_bounds__(64) void k_loc_step(LocStepArgs A) {
+  __shared__ double s_sum[kLocRow];
+  const size_t h = blockIdx.x;
+  LocState* S = A.st + h;
+  const double* partial = A.partial + h * (size_t)A.nblocks * kLocRow;
+  LocLog* log = A.log + h * kLocMaxIterations;
   if (S->done) return;
   const int lane = threadIdx.x;
   if (lane < kLocRow) {   // a lane per column, the rows in block order
@@ -256,18 +246,6 @@ __device__ __forceinline__ void loc_step_body(const LocStepArgs& A, LocState* S,
   }
 }
 
-__global__ __launch_bounds__(64) void k_loc_step(LocStepArgs A) {
-  __shared__ double s_sum[kLocRow];
-  loc_step_body(A, A.st, A.partial, A.log, s_sum);
-}
-
-// hypothesis blockIdx.x of a batch: its state words, its nblocks partial rows, its kLocMaxIterations log records
-__global__ __launch_bounds__(64) void k_loc_step_batch(LocStepArgs A) {
-  __shared__ double s_sum[kLocRow];
-  const size_t h = blockIdx.x;
-  loc_step_body(A, A.st + h, A.partial + h * (size_t)A.nblocks * kLocRow, A.log + h * kLocMaxIterations, s_sum);
-}
-
 // ---- relocalisation: the place search's candidates made hypotheses of the batched localiser -----------
 // A lane per candidate h: yaw = shift * (2 pi / S), less 2 pi when above pi (k_place_pick's); c = cos(yaw), s = sin(yaw);
 // prior = P * Rz(yaw) with P the pose the closed map's build used for the keyframe: column 0 = c * P0 + s * P1,
@@ -329,20 +307,12 @@ void launch_loc_prepare(const LocPrepArgs& A, hipStream_t s) {
   hipLaunchKernelGGL(k_loc_prepare, dim3(loc_blocks(A.nv)), dim3(256), 0, s, A);
 }
 
-void launch_loc_sweep(const LocSweepArgs& A, hipStream_t s) {
-  hipLaunchKernelGGL(k_loc_sweep, dim3(loc_blocks(A.n)), dim3(256), 0, s, A);
+void launch_loc_sweep(const LocSweepArgs& A, int B, hipStream_t s) {
+  hipLaunchKernelGGL(k_loc_sweep, dim3(loc_blocks(A.n), B), dim3(256), 0, s, A);
 }
 
-void launch_loc_step(const LocStepArgs& A, hipStream_t s) {
-  hipLaunchKernelGGL(k_loc_step, dim3(1), dim3(64), 0, s, A);
-}
-
-void launch_loc_sweep_batch(const LocSweepArgs& A, int B, hipStream_t s) {
-  hipLaunchKernelGGL(k_loc_sweep_batch, dim3(loc_blocks(A.n), B), dim3(256), 0, s, A);
-}
-
-void launch_loc_step_batch(const LocStepArgs& A, int B, hipStream_t s) {
-  hipLaunchKernelGGL(k_loc_step_batch, dim3(B), dim3(64), 0, s, A);
+void launch_loc_step(const LocStepArgs& A, int B, hipStream_t s) {
+  hipLaunchKernelGGL(k_loc_step, dim3(B), dim3(64), 0, s, A);
 }
 
 }  // namespace tl

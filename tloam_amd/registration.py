@@ -627,6 +627,12 @@ def _colmajor(T):
     return np.ascontiguousarray(np.asarray(T, dtype=np.float64).T).reshape(-1)
 
 
+def _id_range(first, count, total):
+    """ids [first, first + count) of a list of total() entries (asked only when count is None: to the end) -> (first, count)"""
+    first = int(first)
+    return first, int(max(total() - first, 0) if count is None else count)
+
+
 def _strict_config(cls, default_fn, over, coerce=None):
     """`cls` as the library's `default_fn` fills it, then the keyword overrides (passed through `coerce[name]` where it has
     one); a name the struct does not have raises KeyError."""
@@ -722,6 +728,29 @@ class HipRegistration:
         if rc in (-4, -5):
             sys.stderr.write(f"[tloam_amd] {what}: {STATUS.get(rc, rc)}: {self.L.tloam_last_error(self.h).decode(errors='replace')}\n")
         return rc
+
+    def _read_list(self, fn, name, rec_type, *head):
+        """a list getter's two calls, fn(*head, capacity, n, records): the count, then the records -> [dict]"""
+        n = C.c_size_t(0)
+        self._check(fn(*head, 0, C.byref(n), None), name)
+        if not n.value:
+            return []
+        rec = (rec_type * n.value)()
+        self._check(fn(*head, n.value, C.byref(n), rec), name)
+        return [r.as_dict() for r in rec[: n.value]]
+
+    def _read_box(self, fn, name, head, columns):
+        """a box read's two calls, fn(*head, capacity, n, *columns): the probe for the count (a short capacity, -1, with n > 0 is
+        its answer), then the columns -- (width, or None for a vector; dtype float64 or int64) each -- fetched and trimmed"""
+        n = C.c_size_t(0)
+        rc = fn(*head, 0, C.byref(n), *[None] * len(columns))
+        if rc not in (0, -1) or (rc == -1 and n.value == 0):
+            self._check(rc, name)
+        m = n.value
+        cols = [np.zeros((max(m, 1), w) if w else max(m, 1), dt) for w, dt in columns]
+        if m:
+            self._check(fn(*head, m, C.byref(n), *[_dp(a) if a.dtype == np.float64 else _lp(a) for a in cols]), name)
+        return tuple(a[: n.value].copy() for a in cols)
 
     def _frame_call(self, fn, name, tag, frame):
         clouds = [_aos(frame.cloud(k)) for k in range(4)]
@@ -945,11 +974,10 @@ class HipRegistration:
 
     def map_read(self, first=0, count=None):
         """points [first, first + count) of the global map as an (m, 3) float64 array (count None: to the end)"""
-        if count is None:
-            count = max(self.map_info()["n_points"] - int(first), 0)
-        out = np.zeros((max(int(count), 1), 3))
-        self._check(self.L.tloam_map_read(self.h, int(first), int(count), _dp(out)), "tloam_map_read")
-        return out[: int(count)].copy()
+        first, m = _id_range(first, count, lambda: self.map_info()["n_points"])
+        out = np.zeros((max(m, 1), 3))
+        self._check(self.L.tloam_map_read(self.h, first, m, _dp(out)), "tloam_map_read")
+        return out[:m].copy()
 
     def registered_scan(self):
         """the last accepted frame's raw scan transformed by its pose (/raw_cloud, front_end.cpp:84-86) as (n, 3)"""
@@ -974,9 +1002,7 @@ class HipRegistration:
 
     def voxel_map_read(self, first=0, count=None):
         """voxels [first, first + count) in id order -> (centroids (m, 3) float64, counts (m,) int64); count None: to the end"""
-        if count is None:
-            count = max(self.voxel_map_info()["n_voxels"] - int(first), 0)
-        m = int(count)
+        first, m = _id_range(first, count, lambda: self.voxel_map_info()["n_voxels"])
         cen, cnt = np.zeros((max(m, 1), 3)), np.zeros(max(m, 1), np.int64)
         self._check(self.L.tloam_voxel_map_read(self.h, int(first), m, _dp(cen), _lp(cnt)), "tloam_voxel_map_read")
         return cen[:m].copy(), cnt[:m].copy()
@@ -986,16 +1012,8 @@ class HipRegistration:
         (centroids (m, 3), counts (m,))"""
         lo = np.ascontiguousarray(lo, dtype=np.float64).reshape(3)
         hi = np.ascontiguousarray(hi, dtype=np.float64).reshape(3)
-        n = C.c_size_t(0)
-        rc = self.L.tloam_voxel_map_read_box(self.h, _dp(lo), _dp(hi), int(min_count), 0, C.byref(n), None, None)
-        if rc not in (0, -1) or (rc == -1 and n.value == 0):
-            self._check(rc, "tloam_voxel_map_read_box")
-        m = n.value
-        cen, cnt = np.zeros((max(m, 1), 3)), np.zeros(max(m, 1), np.int64)
-        if m:
-            self._check(self.L.tloam_voxel_map_read_box(self.h, _dp(lo), _dp(hi), int(min_count), m, C.byref(n), _dp(cen),
-                                                        _lp(cnt)), "tloam_voxel_map_read_box")
-        return cen[: n.value].copy(), cnt[: n.value].copy()
+        return self._read_box(self.L.tloam_voxel_map_read_box, "tloam_voxel_map_read_box", (self.h, _dp(lo), _dp(hi), int(min_count)),
+                              [(3, np.float64), (None, np.int64)])
 
     # ---- deskew of the frame's scan under constant velocity (DESIGN.md section 15)
     def deskew_configure(self, cfg: DeskewConfig | None = None, **over):
@@ -1062,9 +1080,7 @@ class HipRegistration:
         """keyframes [first, first + count) -> frames (m,), poses (m, 4, 4), ring_keys (m, R), sector_keys (m, S),
         descriptors (m, R, S)"""
         R, S = self._place_grid()
-        if count is None:
-            count = max(self.place_info()["n_keyframes"] - int(first), 0)
-        m = int(count)
+        first, m = _id_range(first, count, lambda: self.place_info()["n_keyframes"])
         fr, P = np.zeros(max(m, 1), np.int64), np.zeros((max(m, 1), 16))
         rk, sk, d = np.zeros((max(m, 1), R)), np.zeros((max(m, 1), S)), np.zeros((max(m, 1), R, S))
         self._check(self.L.tloam_place_read_keyframes(self.h, int(first), m, _lp(fr), _dp(P), _dp(rk), _dp(sk), _dp(d)),
@@ -1074,9 +1090,7 @@ class HipRegistration:
 
     def place_loops(self, first=0, count=None) -> list:
         """loop records [first, first + count) in the order they were found, as dicts"""
-        if count is None:
-            count = max(self.place_info()["n_loops"] - int(first), 0)
-        m = int(count)
+        first, m = _id_range(first, count, lambda: self.place_info()["n_loops"])
         buf = (PlaceLoop * max(m, 1))()
         self._check(self.L.tloam_place_read_loops(self.h, int(first), m, buf), "tloam_place_read_loops")
         return [buf[i].as_dict() for i in range(m)]
@@ -1137,9 +1151,7 @@ class HipRegistration:
 
     def loop_constraints(self, first=0, count=None) -> list:
         """constraints [first, first + count) as dicts"""
-        if count is None:
-            count = max(self.loop_info()["n_constraints"] - int(first), 0)
-        m = int(count)
+        first, m = _id_range(first, count, lambda: self.loop_info()["n_constraints"])
         buf = (LoopConstraint * max(m, 1))()
         self._check(self.L.tloam_loop_read_constraints(self.h, int(first), m, buf), "tloam_loop_read_constraints")
         return [buf[i].as_dict() for i in range(m)]
@@ -1198,9 +1210,7 @@ class HipRegistration:
     def graph_read_loop_scales(self, first=0, count=None):
         """the loop edges [first, first + count) of the last graph_optimize -> (constraint indices as loop_constraints numbers
         them, scales, statistics r); count None: all of them"""
-        if count is None:
-            count = max(getattr(self, "_graph_loops", 0) - int(first), 0)
-        m = int(count)
+        first, m = _id_range(first, count, lambda: getattr(self, "_graph_loops", 0))
         idx, scale, chi2 = np.zeros(max(m, 1), np.int64), np.zeros(max(m, 1)), np.zeros(max(m, 1))
         self._check(self.L.tloam_graph_read_loop_scales(self.h, int(first), m, idx.ctypes.data_as(C.POINTER(C.c_int64)), _dp(scale),
                                                         _dp(chi2)), "tloam_graph_read_loop_scales")
@@ -1222,9 +1232,7 @@ class HipRegistration:
 
     def graph_poses(self, first=0, count=None):
         """corrected keyframe poses [first, first + count) of the last graph_optimize, (m, 4, 4); count None: all of them"""
-        if count is None:
-            count = max(getattr(self, "_graph_n", 0) - int(first), 0)
-        m = int(count)
+        first, m = _id_range(first, count, lambda: getattr(self, "_graph_n", 0))
         out = np.zeros((max(m, 1), 16))
         self._check(self.L.tloam_graph_read_poses(self.h, int(first), m, _dp(out)), "tloam_graph_read_poses")
         return out[:m].reshape(m, 4, 4).transpose(0, 2, 1).copy()
@@ -1261,9 +1269,7 @@ class HipRegistration:
 
     def closed_map_read(self, first=0, count=None):
         """voxels [first, first + count) in id order -> (centroids (m, 3) float64, counts (m,) int64); count None: to the end"""
-        if count is None:
-            count = max(self.closed_map_info()["n_voxels"] - int(first), 0)
-        m = int(count)
+        first, m = _id_range(first, count, lambda: self.closed_map_info()["n_voxels"])
         cen, cnt = np.zeros((max(m, 1), 3)), np.zeros(max(m, 1), np.int64)
         self._check(self.L.tloam_closed_map_read(self.h, int(first), m, _dp(cen), _lp(cnt)), "tloam_closed_map_read")
         return cen[:m].copy(), cnt[:m].copy()
@@ -1273,22 +1279,12 @@ class HipRegistration:
         (centroids (m, 3), counts (m,))"""
         lo = np.ascontiguousarray(lo, dtype=np.float64).reshape(3)
         hi = np.ascontiguousarray(hi, dtype=np.float64).reshape(3)
-        n = C.c_size_t(0)
-        rc = self.L.tloam_closed_map_read_box(self.h, _dp(lo), _dp(hi), int(min_count), 0, C.byref(n), None, None)
-        if rc not in (0, -1) or (rc == -1 and n.value == 0):
-            self._check(rc, "tloam_closed_map_read_box")
-        m = n.value
-        cen, cnt = np.zeros((max(m, 1), 3)), np.zeros(max(m, 1), np.int64)
-        if m:
-            self._check(self.L.tloam_closed_map_read_box(self.h, _dp(lo), _dp(hi), int(min_count), m, C.byref(n), _dp(cen),
-                                                         _lp(cnt)), "tloam_closed_map_read_box")
-        return cen[: n.value].copy(), cnt[: n.value].copy()
+        return self._read_box(self.L.tloam_closed_map_read_box, "tloam_closed_map_read_box", (self.h, _dp(lo), _dp(hi), int(min_count)),
+                              [(3, np.float64), (None, np.int64)])
 
     def closed_map_poses(self, first=0, count=None):
         """the poses keyframes [first, first + count) were built with, (m, 4, 4); count None: to the end"""
-        if count is None:
-            count = max(self.closed_map_info()["n_keyframes"] - int(first), 0)
-        m = int(count)
+        first, m = _id_range(first, count, lambda: self.closed_map_info()["n_keyframes"])
         out = np.zeros((max(m, 1), 16))
         self._check(self.L.tloam_closed_map_read_poses(self.h, int(first), m, _dp(out)), "tloam_closed_map_read_poses")
         return out[:m].reshape(m, 4, 4).transpose(0, 2, 1).copy()
@@ -1313,9 +1309,7 @@ class HipRegistration:
 
     def closed_map_misses(self, first=0, count=None):
         """M of voxels [first, first + count) in id order, (m,) int64; count None: to the end"""
-        if count is None:
-            count = max(self.closed_map_info()["n_voxels"] - int(first), 0)
-        m = int(count)
+        first, m = _id_range(first, count, lambda: self.closed_map_info()["n_voxels"])
         out = np.zeros(max(m, 1), np.int64)
         self._check(self.L.tloam_closed_map_read_misses(self.h, int(first), m, _lp(out)), "tloam_closed_map_read_misses")
         return out[:m].copy()
@@ -1329,16 +1323,8 @@ class HipRegistration:
             lo = np.ascontiguousarray(lo, dtype=np.float64).reshape(3)
             hi = np.ascontiguousarray(hi, dtype=np.float64).reshape(3)
         head = (self.h, _dp(lo), _dp(hi), int(min_count), int(min_miss), float(miss_ratio))
-        n = C.c_size_t(0)
-        rc = self.L.tloam_closed_map_read_carved(*head, 0, C.byref(n), None, None, None)
-        if rc not in (0, -1) or (rc == -1 and n.value == 0):
-            self._check(rc, "tloam_closed_map_read_carved")
-        m = n.value
-        cen, cnt, mis = np.zeros((max(m, 1), 3)), np.zeros(max(m, 1), np.int64), np.zeros(max(m, 1), np.int64)
-        if m:
-            self._check(self.L.tloam_closed_map_read_carved(*head, m, C.byref(n), _dp(cen), _lp(cnt), _lp(mis)),
-                        "tloam_closed_map_read_carved")
-        return cen[: n.value].copy(), cnt[: n.value].copy(), mis[: n.value].copy()
+        return self._read_box(self.L.tloam_closed_map_read_carved, "tloam_closed_map_read_carved", head,
+                              [(3, np.float64), (None, np.int64), (None, np.int64)])
 
     # ---- the surfels of the closed map: per voxel a normal and three variances
     def closed_map_surfel_configure(self, cfg: ClosedMapSurfelConfig | None = None, **over):
@@ -1361,9 +1347,7 @@ class HipRegistration:
     def closed_map_moments(self, first=0, count=None):
         """the thirteen sums (Ns, R, S xx xy xz yy yz zz, W) of voxels [first, first + count) in id order, (m, 13) int64;
         count None: to the end"""
-        if count is None:
-            count = max(self.closed_map_info()["n_voxels"] - int(first), 0)
-        m = int(count)
+        first, m = _id_range(first, count, lambda: self.closed_map_info()["n_voxels"])
         out = np.zeros((max(m, 1), 13), np.int64)
         self._check(self.L.tloam_closed_map_read_moments(self.h, int(first), m, _lp(out)), "tloam_closed_map_read_moments")
         return out[:m].copy()
@@ -1371,9 +1355,7 @@ class HipRegistration:
     def closed_map_read_surfels(self, first=0, count=None):
         """voxels [first, first + count) in id order -> (normals (m, 3), variances ascending (m, 3) in m^2, Ns (m,) int64);
         count None: to the end.  An unsolved voxel's normal and variances are zero"""
-        if count is None:
-            count = max(self.closed_map_info()["n_voxels"] - int(first), 0)
-        m = int(count)
+        first, m = _id_range(first, count, lambda: self.closed_map_info()["n_voxels"])
         nrm, ev, cnt = np.zeros((max(m, 1), 3)), np.zeros((max(m, 1), 3)), np.zeros(max(m, 1), np.int64)
         self._check(self.L.tloam_closed_map_read_surfels(self.h, int(first), m, _dp(nrm), _dp(ev), _lp(cnt)),
                     "tloam_closed_map_read_surfels")
@@ -1389,17 +1371,8 @@ class HipRegistration:
             lo = np.ascontiguousarray(lo, dtype=np.float64).reshape(3)
             hi = np.ascontiguousarray(hi, dtype=np.float64).reshape(3)
         head = (self.h, _dp(lo), _dp(hi), int(min_count), float(max_sigma), float(min_planarity))
-        n = C.c_size_t(0)
-        rc = self.L.tloam_closed_map_read_surfels_box(*head, 0, C.byref(n), None, None, None, None)
-        if rc not in (0, -1) or (rc == -1 and n.value == 0):
-            self._check(rc, "tloam_closed_map_read_surfels_box")
-        m = n.value
-        cen, nrm, ev = np.zeros((max(m, 1), 3)), np.zeros((max(m, 1), 3)), np.zeros((max(m, 1), 3))
-        cnt = np.zeros(max(m, 1), np.int64)
-        if m:
-            self._check(self.L.tloam_closed_map_read_surfels_box(*head, m, C.byref(n), _dp(cen), _dp(nrm), _dp(ev), _lp(cnt)),
-                        "tloam_closed_map_read_surfels_box")
-        return cen[: n.value].copy(), nrm[: n.value].copy(), ev[: n.value].copy(), cnt[: n.value].copy()
+        return self._read_box(self.L.tloam_closed_map_read_surfels_box, "tloam_closed_map_read_surfels_box", head,
+                              [(3, np.float64), (3, np.float64), (3, np.float64), (None, np.int64)])
 
     # ---- localisation of a scan in the closed map: point-to-plane Gauss-Newton on the surfels
     def closed_map_localise_configure(self, cfg: ClosedMapLocaliseConfig | None = None, **over):
@@ -1420,13 +1393,7 @@ class HipRegistration:
 
     def closed_map_localise_log(self) -> list:
         """the executed iterations of the last closed_map_localise: dicts of pose (before the step), tau, cost, d, matched, used"""
-        n = C.c_size_t(0)
-        self._check(self.L.tloam_closed_map_localise_log(self.h, 0, C.byref(n), None), "tloam_closed_map_localise_log")
-        if not n.value:
-            return []
-        rec = (ClosedMapLocaliseRecord * n.value)()
-        self._check(self.L.tloam_closed_map_localise_log(self.h, n.value, C.byref(n), rec), "tloam_closed_map_localise_log")
-        return [r.as_dict() for r in rec[: n.value]]
+        return self._read_list(self.L.tloam_closed_map_localise_log, "tloam_closed_map_localise_log", ClosedMapLocaliseRecord, self.h)
 
     def closed_map_linearise(self, points, pose, tau) -> dict:
         """one sweep at `pose` (4 x 4) with truncation `tau`, no step -> dict(ids (n,) int32, -1 unmatched; residuals (n,);
@@ -1460,15 +1427,8 @@ class HipRegistration:
 
     def closed_map_localise_batch_log(self, h) -> list:
         """the executed iterations of hypothesis h of the last closed_map_localise_batch (or closed_map_relocalise)"""
-        n = C.c_size_t(0)
-        self._check(self.L.tloam_closed_map_localise_batch_log(self.h, int(h), 0, C.byref(n), None),
-                    "tloam_closed_map_localise_batch_log")
-        if not n.value:
-            return []
-        rec = (ClosedMapLocaliseRecord * n.value)()
-        self._check(self.L.tloam_closed_map_localise_batch_log(self.h, int(h), n.value, C.byref(n), rec),
-                    "tloam_closed_map_localise_batch_log")
-        return [r.as_dict() for r in rec[: n.value]]
+        return self._read_list(self.L.tloam_closed_map_localise_batch_log, "tloam_closed_map_localise_batch_log",
+                               ClosedMapLocaliseRecord, self.h, int(h))
 
     def closed_map_relocalise_configure(self, cfg: ClosedMapRelocaliseConfig | None = None, **over):
         """the relocalisation's configuration (default_closed_map_relocalise_config(**over) when cfg is None).  Kept across
@@ -1490,15 +1450,8 @@ class HipRegistration:
     def closed_map_relocalise_hypotheses(self) -> list:
         """the hypotheses of the last closed_map_relocalise, in candidate order: dicts of keyframe, shift, skipped, dist, yaw,
         prior, pose and the localise info"""
-        n = C.c_size_t(0)
-        self._check(self.L.tloam_closed_map_relocalise_hypotheses(self.h, 0, C.byref(n), None),
-                    "tloam_closed_map_relocalise_hypotheses")
-        if not n.value:
-            return []
-        hyp = (ClosedMapRelocaliseHypothesis * n.value)()
-        self._check(self.L.tloam_closed_map_relocalise_hypotheses(self.h, n.value, C.byref(n), hyp),
-                    "tloam_closed_map_relocalise_hypotheses")
-        return [x.as_dict() for x in hyp[: n.value]]
+        return self._read_list(self.L.tloam_closed_map_relocalise_hypotheses, "tloam_closed_map_relocalise_hypotheses",
+                               ClosedMapRelocaliseHypothesis, self.h)
 
     def fitness(self):
         f, r = C.c_double(0), C.c_double(0)
