@@ -414,7 +414,8 @@ def dcvc_literal_fast(V):
 
 def dcvc_components(V):
     """the device's partition: connected components over the neighbour edges taken as undirected.  A point whose pitch
-    index is height + 1 does not see its own voxel: it is a node of its own."""
+    index is height + 1, or whose azimuth index is above 300 (all three of its columns clamp to 300, :898), does not see
+    its own voxel: it is a node of its own."""
     from scipy.sparse import coo_matrix
     from scipy.sparse.csgraph import connected_components
     n = len(V["pol"])
@@ -423,7 +424,7 @@ def dcvc_components(V):
     for k, mem in vm.items():
         i0 = mem[0]
         nb = _neighbours(i0, V, vm)
-        own = V["pit"][i0] <= V["height"]
+        own = V["pit"][i0] <= V["height"] and V["az"][i0] <= 300
         if own:
             rows += [i0] * (len(mem) - 1); cols += mem[1:]
             rows += [i0] * len(nb); cols += nb

@@ -87,7 +87,7 @@ int odometry_frame_body(tloam_ctx* c, const double* xyz, const double* t_sec, si
     c->last_error = "tloam_odometry_frame_timed: a time is not finite or more than two sweeps from the pose's instant";
     return TLOAM_E_INVALID;
   }
-  if (ctl.invalid) return TLOAM_E_INVALID;
+  if (ctl.invalid && ctl.n_obj > 0) return TLOAM_E_INVALID;   // (without an object point the node stops before polarBounds)
   const double* scan = frame_scan(c);
   if (ctl.n_obj <= 0 || ctl.n_clusters <= 0) return TLOAM_E_TOO_FEW_POINTS;   // the node publishes nothing
   const size_t ng = (size_t)ctl.n_ground, ne = (size_t)ctl.n_edge, nge = (size_t)ctl.n_general;

@@ -149,7 +149,8 @@ int tloam_segment(tloam_ctx* c, const tloam_seg_config* cfg, const double* xyz, 
   SegCtl ctl;
   HIPC(c, hipMemcpyAsync(&ctl, S.ctl.p, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
   HIPC(c, hipStreamSynchronize(c->stream));   // the one place sizes come back
-  if (ctl.invalid) return TLOAM_E_INVALID;     // the polarBounds loop would not end (:831)
+  // the polarBounds loop would not end (:831); without an object point the node never reaches it (:1088-1092)
+  if (ctl.invalid && ctl.n_obj > 0) return TLOAM_E_INVALID;
 
   const size_t ng = (size_t)ctl.n_ground, no = (size_t)ctl.n_obj, ns = (size_t)ctl.n_seg, ne = (size_t)ctl.n_edge,
                nge = (size_t)ctl.n_general, nb = (size_t)ctl.n_clusters;

@@ -504,8 +504,10 @@ __global__ __launch_bounds__(256) void k_seg_union(SegParams P, SegBufs B) {
   const int pol = v[0], pit = v[1], az = v[2], key = v[3];
   const int pn = c->polar_num, height = c->height, width = c->width;
   const int rep = B.hval[hash_find(B.hkey, key, P.hash_mask)];
-  const bool own_row = pit <= height;   // a point in row height + 1 does not see its own voxel (:888)
-  if (own_row && i != rep) {            // points of one voxel: joined through its smallest member, which walks
+  // a point in row height + 1 (:888) or in an azimuth column above 300 (:898: all three of its columns clamp to 300)
+  // does not see its own voxel
+  const bool own_seen = pit <= height && az <= 300;
+  if (own_seen && i != rep) {           // points of one voxel: joined through its smallest member, which walks
     uf_union(B.parent, i, rep);
     return;
   }
