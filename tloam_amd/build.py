@@ -45,6 +45,7 @@ UNITS = [
     ("tl_api.hip", []),          # context lifetime, configuration, sharding rules
     ("tl_api_frames.hip", []),   # HBM residency: hand-over of the clouds, search grids, staged frames
     ("tl_api_match.hip", []),    # the scanMatching driver
+    ("tl_api_sets.hip", []),     # its factor set outside a frame: getters, pre-built sets, accumulate / solve, the timing helpers
     ("tl_api_comm.hip", []),     # multi-GPU exchange (RCCL at run time, callback, mailbox)
     ("tl_api_submap.hip", []),
     ("tl_api_feature.hip", []),

@@ -1,6 +1,7 @@
 // tl_api.hip -- lifetime of the C ABI's context (include/tloam_hip.h): create / destroy, configuration, status strings,
 // the sharding rules, the host SE(3) helpers.  The other units: tl_api_frames.hip (HBM residency, search grids),
-// tl_api_match.hip (the scanMatching driver), tl_api_comm.hip (multi-GPU exchange), tl_api_submap.hip, tl_api_feature.hip.
+// tl_api_match.hip (the scanMatching driver), tl_api_sets.hip (its factor set outside a frame: getters, solve, timing helpers),
+// tl_api_comm.hip (multi-GPU exchange), tl_api_submap.hip, tl_api_feature.hip.
 //
 // There is no CPU fallback: without a usable device every computing entry point returns TLOAM_E_HIP.
 #include "tl_ctx.hpp"

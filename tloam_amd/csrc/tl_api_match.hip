@@ -1,22 +1,17 @@
 // tl_api_match.hip -- the host driver of LocalRegistration::scanMatching (registration.cpp:879-1133) behind the C ABI
-// (include/tloam_hip.h): stepwise (tloam_sm_*) and device-driven (tloam_scan_match) outer GNC loop, getFitnessScore,
-// introspection, pre-built correspondence sets, the bench's timing helpers.
+// (include/tloam_hip.h): the frame, stepwise (tloam_sm_begin / tloam_sm_outer / tloam_sm_end) and with the outer GNC loop driven
+// from the device (tloam_scan_match).  What a host does to the factor set outside a frame is tl_api_sets.hip, which shares the
+// helpers declared under this unit's name in tl_ctx.hpp.
 //
 // Host side mirrors the reference's control flow (outer GNC loop, mu schedule, plateau test);
 // every per-point / per-correspondence computation is a HIP kernel (tl_nn.hip, tl_gn.hip).
+// Helpers first, in namespaces; the four entry points, the only extern "C" of the unit, last.
 #include <atomic>
 #include <chrono>
 
 #include "tl_ctx.hpp"
 
 using namespace tl;
-
-namespace {
-int sync_stream(tloam_ctx* c) {
-  HIPC(c, hipStreamSynchronize(c->stream));
-  return TLOAM_OK;
-}
-}  // namespace
 
 namespace tlh {
 int reserve_seg(tloam_ctx* c, int k, size_t n) {
@@ -76,6 +71,73 @@ int ensure_common(tloam_ctx* c) {
   c->cv.seg_n = c->seg_n.p;
   return TLOAM_OK;
 }
+// (also called from the grid build when the sort's first pass rides on it: the SAME sizes, so that nothing is re-allocated -- and
+//  lost -- between that pass and the rest of the sort)
+int reserve_query_sort(tloam_ctx* c, const GridView grids[kKinds]) {
+  const size_t n_slots = (size_t)c->sv.slot_off[kKinds];
+  const size_t ntiles = (size_t)build_tile_count(grids, c->sv.slot_off);
+  // (tile counts follow the bounding boxes like the cell tables: grow with room to spare)
+  const size_t nt_res = (ntiles + 1 > c->tile_cnt.cap || ntiles + 1 > c->tile_scan.cap) ? 2 * ntiles + 64 : ntiles;
+  {
+    // The query-tile histogram is zeroed by the frame's start (k_frame_init / the extra blocks of the grid build's first launch),
+    // which has been enqueued by now: a histogram that has to be re-allocated HERE -- the scan's table was shorter than the
+    // histogram's, or the sizes asked for at the two places differ by the one element that crosses an allocation step -- is
+    // zeroed again.  (Until round 5 it was not: the counting sort then ranked the queries on what the new block happened to
+    // hold and scattered them out of bounds -- a GPU memory fault or a silently wrong query order on the first large frame of a
+    // context, whenever the block was not fresh; found by tests/tools/fuzz_call_order.py.)
+    const size_t before = c->tile_cnt.cap;
+    HIPC(c, c->tile_cnt.reserve(nt_res + 1));
+    if (c->tile_cnt.cap != before)
+      HIPC(c, hipMemsetAsync(c->tile_cnt.p, 0, c->tile_cnt.cap * sizeof(unsigned long long), c->stream));
+  }
+  HIPC(c, c->tile_scan.reserve(nt_res + 1));
+  HIPC(c, c->tile_fill.reserve(std::max<size_t>((size_t)nt_res, (size_t)n_slots + 1))  /* rank of every slot inside its tile */); HIPC(c, c->tile_of_slot.reserve(n_slots + 1));
+  HIPC(c, c->qrec.reserve(n_slots + 1));
+  HIPC(c, c->scan_tmp.reserve(scan_tmp_elems(std::max(nt_res + 1, n_slots + 1))));
+  c->scan1p_q_use = !c->no_scan_1p && scan_1p_applies(ntiles + 1, c->device_cus);
+  if (c->scan1p_q_use) {
+    const size_t before = c->scan1p_q.cap;
+    HIPC(c, c->scan1p_q.reserve(scan_1p_ctl_elems(nt_res + 1)));
+    if (c->scan1p_q.cap != before) HIPC(c, hipMemsetAsync(c->scan1p_q.p, 0, c->scan1p_q.cap * sizeof(unsigned long long), c->stream));
+  }
+  return TLOAM_OK;
+}
+BuildParams build_params(const tloam_ctx* c) {
+  BuildParams bp;
+  for (int k = 0; k < kKinds; ++k) {
+    bp.radius[k] = kind_radius(c->cfg, k);
+    bp.maxnum[k] = kind_maxnum(c->cfg, k);
+    bp.active[k] = kind_active(c->cfg, k);
+  }
+  bp.edge_dir_thres = c->cfg.edge_dir_thres;
+  return bp;
+}
+void outer_params(const tloam_ctx* c, BuildParams* bp, GridView grids[kKinds]) {
+  *bp = build_params(c);
+  for (int k = 0; k < kKinds; ++k) grids[k] = c->kd[k].gv;
+}
+// the sweep's launch form (grid, one-wave-per-chunk, wide) from the segments' capacities
+void plan_sweeps(tloam_ctx* c) {
+  int caps[kKinds];
+  for (int k = 0; k < kKinds; ++k) caps[k] = (int)c->kd[k].c_cap;
+  k3_plan(caps, c->device_cus, &c->k3_grid, &c->k3_single, &c->k3_wide);
+}
+double* direct_w_stream(const tloam_ctx* c, int k, int parity) {
+  return c->kd[k].c_buf.p + (size_t)(parity ? SS_W2 : SS_W) * c->kd[k].c_stride;
+}
+// the per-block rows of the sweeps (and, below 4096 words, the tagged rows / finish segments of the one-launch Solve): cleared
+// when (re)allocated, so that nothing in them ever carries a valid check word that this context did not write
+int reserve_partials(tloam_ctx* c) {
+  const size_t before = c->partials.cap;
+  HIPC(c, c->partials.reserve(std::max<size_t>((size_t)c->k3_grid * kAccStride, 4096)));
+  if (c->partials.cap != before) HIPC(c, hipMemsetAsync(c->partials.p, 0, c->partials.cap * sizeof(double), c->stream));
+  return TLOAM_OK;
+}
+double alg_bytes_of(const int n[kKinds]) {
+  // SURVEY 8(d): plane 72 B, line 88 B, point 64 B per correspondence (fp64 SoA, cost write included)
+  return 72.0 * ((double)n[TLOAM_KIND_PLANAR] + (double)n[TLOAM_KIND_GROUND]) + 88.0 * (double)n[TLOAM_KIND_EDGE] +
+         64.0 * (double)n[TLOAM_KIND_SPHERE];
+}
 }  // namespace tlh
 
 namespace {
@@ -90,25 +152,23 @@ bool direct_applies(const tloam_ctx* c, size_t n_slots) {
     if ((long long)c->kd[k].n_src > (long long)kind_maxnum(c->cfg, k) || c->kd[k].n_tgt == 0) return false;
   return true;
 }
-double* direct_w_stream(const tloam_ctx* c, int k, int parity) {
-  return c->kd[k].c_buf.p + (size_t)(parity ? SS_W2 : SS_W) * c->kd[k].c_stride;
-}
 // the Solve of outer iteration `iter` reads weight stream iter & 1 (c->cv), its finish writes the other one
 void direct_set_parity(tloam_ctx* c, int iter) {
   for (int k = 0; k < kKinds; ++k) c->cv.k[k].w = direct_w_stream(c, k, iter & 1);
 }
 // rows of the hand-over buffer of the finish, compact (riding) or direct
 constexpr size_t kFinRowsDoubles = (size_t)(4 * 256 + 64) * 16;   // the blocks' rows + the rows of their groups of 64
+size_t seg_cap_sum(const tloam_ctx* c) {   // the four segments' capacity: what sizes the finish (finish_wblocks, finish_small_path)
+  size_t cap = 0;
+  for (int k = 0; k < kKinds; ++k) cap += c->kd[k].c_cap;
+  return cap;
+}
 // (a quarter of the) one-wave blocks of a direct finish: a fixed function of the capacity, so that the riding form and the launch of
 // its own cut the rows alike.  (Twice as many blocks on ONE ticket measured 52 instead of 31 us for the frame's last finish: the
 // arrivals on the ticket are what it waits for -- hence the two-level hand-over of finish_direct_block.)
 // (The same function gives the block count of every finish -- enqueue_finish, the riding large finish: the summation tree,
 // hence the bits, must not depend on the path or on timing.)
-int finish_wblocks(const tloam_ctx* c) {
-  size_t cap = 0;
-  for (int k = 0; k < kKinds; ++k) cap += c->kd[k].c_cap;
-  return (int)std::min<size_t>(256, std::max<size_t>(64, cap / 2048));
-}
+int finish_wblocks(const tloam_ctx* c) { return (int)std::min<size_t>(256, std::max<size_t>(64, seg_cap_sum(c) / 2048)); }
 int* direct_blk_cnt(const tloam_ctx* c, int iter) { return c->blk_cnt.p + (size_t)(iter & 1) * c->blk_cnt_n * kKinds; }
 // built: 1 the set of outer iteration `iter` was built in it, 0 it is the previous one, -1 the device knows (GnState::run_build)
 FinishLargeArgs direct_finish_args(tloam_ctx* c, const CorrView* cv_iter, const WeightParams* wp, const HostMirror& hm, OuterCtl ctl,
@@ -149,12 +209,7 @@ int launch_sampled(tloam_ctx* c, Launch launch) {
   c->ev_batch_idx.push_back(idx);
   return TLOAM_OK;
 }
-int launch_k3_timed(tloam_ctx* c, bool force) {
-  return launch_sampled(c, [&](hipEvent_t e0, hipEvent_t e1) {
-    launch_k3(c->cv, c->state.p, c->partials.p, c->k3_grid, c->k3_single, c->k3_wide, force, c->stream, e0, e1);
-  });
-}
-// the same for the one-launch GN iteration (k3_sweep_step): the pair then brackets sweep + fold + step; the streaming part
+// the one-launch GN iteration (k3_sweep_step) so sampled: the pair then brackets sweep + fold + step; the streaming part
 // alone is what the kernel's own span counter measures (K3Step::span, read by tloam_k3_timer_span)
 int launch_k3_step_timed(tloam_ctx* c) {
   const MboxView* mb = (exchanging(c) && c->comm == COMM_MAILBOX) ? &c->mbox : nullptr;
@@ -186,10 +241,6 @@ int harvest_k3_events_multi(tloam_ctx* c, int nsolve, const int* start, const in
   c->ev_used = 0;
   c->ev_batch_idx.clear();
   return TLOAM_OK;
-}
-int harvest_k3_events(tloam_ctx* c, int working) {
-  const int zero = 0;
-  return harvest_k3_events_multi(c, 1, &zero, &working);
 }
 
 // Result of an outer iteration on the host.  With the mirror the finish kernel has been handed
@@ -228,18 +279,29 @@ int wait_state(tloam_ctx* c, const HostMirror& hm, int slot = 0) {
   return TLOAM_OK;
 }
 
-// one ceres::Solve on the current correspondence set, device resident: 1 + 4 sweeps at most;
-// sweeps after a tolerance exit are no-op launches (GnState.done).
-constexpr int kSolveSweeps = 5;  // max_num_iterations 4 -> at most 1 + 4 evaluations per Solve
 bool solve_small_path(const tloam_ctx* c) {
   return one_rank(c) && c->k3_single && !c->no_persistent_solve && solve_small_fits(c->k3_grid, c->device_cus);
 }
+}  // namespace
+
+namespace tlh {
+// the streaming sweep (launch_k3) as a sampled launch of the batch
+int launch_k3_timed(tloam_ctx* c, bool force) {
+  return launch_sampled(c, [&](hipEvent_t e0, hipEvent_t e1) {
+    launch_k3(c->cv, c->state.p, c->partials.p, c->k3_grid, c->k3_single, c->k3_wide, force, c->stream, e0, e1);
+  });
+}
+int harvest_k3_events(tloam_ctx* c, int working) {
+  const int zero = 0;
+  return harvest_k3_events_multi(c, 1, &zero, &working);
+}
+// one ceres::Solve on the current correspondence set, device resident: 1 + 4 sweeps at most;
+// sweeps after a tolerance exit are no-op launches (GnState.done).
 // prep: the launch also prepares the factor set (only with solve_small_path and SlotView::flagb, see self_prepare_path)
 // finish: ... and finishes the outer iteration, possibly running the following ones too (SolveFinish; needs prep).
 // wp: the weight thresholds of the outer iteration this Solve belongs to (null: a Solve outside scanMatching) -- the
 // one-launch Solve adds up the finish sums of its last evaluation for the finish kernel that follows.
-int enqueue_solve(tloam_ctx* c, bool armed, int sweeps, const WeightParams* wp = nullptr, const SolvePrep* prep = nullptr,
-                  const SolveFinish* finish = nullptr) {
+int enqueue_solve(tloam_ctx* c, bool armed, int sweeps, const WeightParams* wp, const SolvePrep* prep, const SolveFinish* finish) {
   if (!armed) launch_solve_init(c->state.p, c->stream);  // scan_match re-arms the minimiser in its finish kernel
   if (sweeps > 0 && solve_small_path(c)) {
     // KITTI-size set: the whole Solve (up to `sweeps` evaluations) is one launch (k_solve_all)
@@ -296,243 +358,12 @@ int enqueue_solve(tloam_ctx* c, bool armed, int sweeps, const WeightParams* wp =
   }
   return TLOAM_OK;
 }
-
-// the per-block rows of the sweeps (and, below 4096 words, the tagged rows / finish segments of the one-launch Solve): cleared
-// when (re)allocated, so that nothing in them ever carries a valid check word that this context did not write
-int reserve_partials(tloam_ctx* c) {
-  const size_t before = c->partials.cap;
-  HIPC(c, c->partials.reserve(std::max<size_t>((size_t)c->k3_grid * kAccStride, 4096)));
-  if (c->partials.cap != before) HIPC(c, hipMemsetAsync(c->partials.p, 0, c->partials.cap * sizeof(double), c->stream));
-  return TLOAM_OK;
-}
-
-double alg_bytes_of(const int n[kKinds]) {
-  // SURVEY 8(d): plane 72 B, line 88 B, point 64 B per correspondence (fp64 SoA, cost write included)
-  return 72.0 * ((double)n[TLOAM_KIND_PLANAR] + (double)n[TLOAM_KIND_GROUND]) + 88.0 * (double)n[TLOAM_KIND_EDGE] +
-         64.0 * (double)n[TLOAM_KIND_SPHERE];
-}
-
-}  // namespace
-
-extern "C" {
-
-// ---- scanMatching, stepwise ---------------------------------------------------------------------
-int tloam_sm_begin(tloam_ctx* c, const double predict[16], const double* omega3) {
-  if (!c || !predict) return TLOAM_E_INVALID;
-  HIPC(c, hipSetDevice(c->device));
-  for (int k = 0; k < kKinds; ++k)  // the reference asserts (registration.cpp:928-929)
-    if (c->kd[k].n_src_full < 10 || c->kd[k].n_tgt < 10) return TLOAM_E_TOO_FEW_POINTS;
-  for (int k = 0; k < kKinds; ++k)  // a hand-over that failed half way (staging, upload) left nothing registered
-    if (!c->kd[k].src_set || !c->kd[k].tgt_set) { c->last_error = "a source / target hand-over failed: hand the frame over again"; return TLOAM_E_NOT_READY; }
-  Pose P;
-  if (!pose_from_matrix(predict, &P)) return TLOAM_E_BAD_POSE;  // SOPHUS_ENSURE in the reference
-  double x[6];
-  se3_log(P, x);  // :881
-  if (sqrt(x[3] * x[3] + x[4] * x[4] + x[5] * x[5]) < 1e-2) {  // :884-886
-    double u[3] = {0.0, 0.0, 1.0};
-    if (omega3) {
-      const double nn = sqrt(omega3[0] * omega3[0] + omega3[1] * omega3[1] + omega3[2] * omega3[2]);
-      if (nn > 0.0) { u[0] = omega3[0] / nn; u[1] = omega3[1] / nn; u[2] = omega3[2] / nn; }
-    }
-    x[3] = u[0] * 1e-4; x[4] = u[1] * 1e-4; x[5] = u[2] * 1e-4;
-  }
-  int rc = ensure_common(c);
-  if (rc != TLOAM_OK) return rc;
-  // ---- per-source-slot arrays (:931-949 weights = 1, residual slots = 0)
-  size_t off = 0;
-  for (int k = 0; k < kKinds; ++k) {
-    c->sv.slot_off[k] = (int)off;
-    c->sv.src_lo[k] = (int)c->kd[k].src_lo;
-    off += c->kd[k].n_src;
-  }
-  c->sv.slot_off[kKinds] = (int)off;
-  const size_t ns = std::max<size_t>(off, 1);
-  HIPC(c, c->sx.reserve(ns)); HIPC(c, c->sy.reserve(ns)); HIPC(c, c->sz.reserve(ns)); HIPC(c, c->w_src.reserve(ns));
-  HIPC(c, c->raw.reserve(ns * 8));
-  HIPC(c, c->flags.reserve(ns + 1)); HIPC(c, c->scan.reserve(ns + 1));
-  HIPC(c, c->scan_tmp.reserve(scan_tmp_elems(ns + 1)));
-  c->sv.sx = c->sx.p; c->sv.sy = c->sy.p; c->sv.sz = c->sz.p; c->sv.w_src = c->w_src.p;
-  c->sv.raw = c->raw.p;
-  c->sv.flags = c->flags.p; c->sv.scan = c->scan.p;
-  c->direct = direct_applies(c, off);
-  c->set_stale = false;
-  c->w_parity = 0;
-  if (c->direct) {
-    HIPC(c, c->fin_rows.reserve(kFinRowsDoubles));
-    c->blk_cnt_n = (off + 63) / 64;   // one-wave blocks of the thread-per-query search (logical: the sorted queries, 64 each)
-    HIPC(c, c->blk_cnt.reserve(2 * c->blk_cnt_n * kKinds + 8));
-    HIPC(c, c->row_of_pos.reserve(off + 64));
-    if (!c->fin_tickets.p) {
-      HIPC(c, c->fin_tickets.reserve(128));
-      HIPC(c, hipMemsetAsync(c->fin_tickets.p, 0, c->fin_tickets.cap * sizeof(int), c->stream));
-    }
-  }
-  // ---- compact segments: at most min(n_src, maxnum) factors per kind (a direct set: one row per source point, which is the same)
-  size_t total_cap = 0;
-  for (int k = 0; k < kKinds; ++k) {
-    const size_t cap = std::min<size_t>(c->kd[k].n_src, (size_t)std::max(kind_maxnum(c->cfg, k), 0));
-    rc = reserve_seg(c, k, cap);
-    if (rc != TLOAM_OK) return rc;
-    total_cap += round_up(std::max<size_t>(cap, 1), kChunk);
-  }
-  c->prebuilt = false;
-  {
-    int caps[kKinds];
-    for (int k = 0; k < kKinds; ++k) caps[k] = (int)c->kd[k].c_cap;
-    k3_plan(caps, c->device_cus, &c->k3_grid, &c->k3_single, &c->k3_wide);
-    (void)total_cap;
-  }
-  {
-    // the one-launch Solve compacts the factor set itself when every kind's flag bytes fit a wave (SlotView::flagb)
-    bool fits = solve_small_path(c) && prepare_small_fits(c->sv);
-    for (int k = 0; k < kKinds; ++k) fits = fits && c->kd[k].n_src <= (size_t)kFlagbStride;
-    c->sv.flagb = nullptr;
-    if (fits) {
-      HIPC(c, c->flagb.reserve((size_t)kKinds * kFlagbStride));
-      c->sv.flagb = c->flagb.p;
-    }
-  }
-  rc = reserve_partials(c);
-  if (rc != TLOAM_OK) return rc;
-  // ---- the start of the frame -- scan-frame sources AoS -> SoA slots, weights = 1 (:931-949), flag-scan terminator,
-  //      minimiser state zeroed with `parameters` = x (passed by value) and armed for the first Solve -- rides on the
-  //      first launch of the grid build
-  FrameInitHook hook;
-  memset(&hook, 0, sizeof(hook));
-  for (int k = 0; k < kKinds; ++k) { hook.fi.src_aos[k] = c->kd[k].src_ptr; hook.fi.slot_off[k] = c->sv.slot_off[k]; }
-  hook.fi.slot_off[kKinds] = c->sv.slot_off[kKinds];
-  for (int i = 0; i < 6; ++i) hook.fi.x[i] = x[i];
-  hook.fi.no_eval_reuse = c->dbg_no_eval_reuse ? 1 : 0;
-  hook.fi.direct = c->direct ? 1 : 0;
-  if (c->direct) direct_set_parity(c, 0);
-  // 1 M-class single-rank frames: the first pass of the query sort rides on the last launch of the grid build (QueryBinRide)
-  QueryBinRide qbin;
-  memset(&qbin, 0, sizeof(qbin));
-  c->qbin_rode = false;
-  if (one_rank(c) && !c->no_qbin_ride && direct_set_size((int)std::min<size_t>(off, (size_t)INT32_MAX))) {
-    qbin.sv = c->sv;
-    for (int k = 0; k < kKinds; ++k) {
-      qbin.bp.radius[k] = kind_radius(c->cfg, k);
-      qbin.bp.maxnum[k] = kind_maxnum(c->cfg, k);
-      qbin.bp.active[k] = kind_active(c->cfg, k);
-    }
-    qbin.bp.edge_dir_thres = c->cfg.edge_dir_thres;
-    qbin.st = c->state.p;
-    hook.qbin = &qbin;
-  }
-  hook.b = FrameInitBufs{c->sx.p, c->sy.p, c->sz.p, c->w_src.p, c->flags.p, c->state.p, c->seg_n.p};
-  hook.n_slots = c->sv.slot_off[kKinds];
-  // ---- :889-915 four search structures over the submap clouds: one launch per build phase for all kinds
-  {
-    double radius[kKinds];
-    GridView views[kKinds];
-    for (int k = 0; k < kKinds; ++k) radius[k] = kind_radius(c->cfg, k);
-    // a sharded rank searches only the kinds it holds source points of (tloam_shard_ranges_frame): the other grids are not built
-    if (c->nranks > 1)
-      for (int k = 0; k < kKinds; ++k)
-        if (c->kd[k].n_src == 0) radius[k] = 0.0;
-    if (c->grids_ahead && c->grids_next_gen == c->tgt_gen && one_rank(c)) {
-      // built when the targets were handed over (tloam_set_target_frame): they become the context's search structures now;
-      // the frame's start is a launch of its own, below.  Used once: a second scanMatching over the same targets builds its own
-      std::swap(c->grids, c->grids_next);
-      for (int k = 0; k < kKinds; ++k) { c->kd[k].gv = c->gv_next[k]; c->kd[k].grid_valid = true; }
-      c->grids_ahead = false;
-    } else {
-      rc = build_grids(c, c->grids, radius, views, &hook);
-      if (rc != TLOAM_OK) return rc;
-      c->qbin_rode = hook.qbin_done;
-      // (a kind whose grid was skipped -- radius forced to 0 above: a sharded rank without source points of it -- has an EMPTY
-      //  view: it is not a search structure getFitnessScore or anybody else may use)
-      for (int k = 0; k < kKinds; ++k) { c->kd[k].gv = views[k]; c->kd[k].grid_valid = radius[k] > 0.0; }
-    }
-  }
-  if (!hook.consumed) {  // (no grid launch: cannot happen with >= 10 targets per kind, kept for safety)
-    GridView gviews[kKinds];
-    for (int k = 0; k < kKinds; ++k) gviews[k] = c->kd[k].gv;
-    const size_t ntiles = (size_t)build_tile_count(gviews, c->sv.slot_off);
-    HIPC(c, c->tile_cnt.reserve(ntiles + 1 > c->tile_cnt.cap ? 2 * ntiles + 64 : ntiles + 1));   // (room to spare, as build_grids_over)
-    hook.fi.tile_cnt = c->tile_cnt.p;
-    hook.fi.n_tile_cnt = (int)ntiles + 1;
-    launch_frame_init(hook.fi, hook.b, c->stream);
-  }
-  if (c->direct) {
-    // a kind whose target cloud has no finite point has no search grid: its queries are not in the sorted order, and the rows of a
-    // direct set ARE that order -- such a frame compacts (the frame's start, already enqueued, has set seg_n to the row counts)
-    bool all = true;
-    for (int k = 0; k < kKinds; ++k) all = all && c->kd[k].gv.n > 0;
-    if (!all) {
-      c->direct = false;
-      HIPC(c, hipMemsetAsync(c->seg_n.p, 0, kKinds * sizeof(int), c->stream));
-    }
-  }
-  c->wait_us = 0.0;
-  c->mu = 1.0;  // :961
-  c->noise_bound_sq = c->cfg.noise_bound * c->cfg.noise_bound;
-  if (c->noise_bound_sq < 1e-16) c->noise_bound_sq = 1e-2;  // :963-964
-  for (int k = 0; k < kKinds; ++k) { c->prev_cost[k] = INFINITY; c->cur_cost[k] = INFINITY; }  // :952-959
-  c->iter = 0;
-  c->active = true;
-  c->have_build = false;
-  memset(&c->stats, 0, sizeof(c->stats));
-  memcpy(c->stats.se3, x, sizeof(x));
-  c->ev_used = 0;
-  c->ev_batch_idx.clear();
-  c->batch_launches = 0;
-  return TLOAM_OK;
-}
+}  // namespace tlh
 
 // ---- pieces of one outer GNC iteration, shared by the stepwise API (the host decides between iterations) and by
 //      tloam_scan_match's device-driven loop (every iteration enqueued at once, one host wait per frame) -----------
 namespace {
 constexpr int kMaxOuterFast = kMirrorSlots;   // outer iterations the device-driven loop plans for
-
-void outer_params(const tloam_ctx* c, BuildParams* bp, GridView grids[kKinds]) {
-  for (int k = 0; k < kKinds; ++k) {
-    bp->radius[k] = kind_radius(c->cfg, k);
-    bp->maxnum[k] = kind_maxnum(c->cfg, k);
-    bp->active[k] = kind_active(c->cfg, k);
-    grids[k] = c->kd[k].gv;
-  }
-  bp->edge_dir_thres = c->cfg.edge_dir_thres;
-}
-int outer_reserve(tloam_ctx* c, const GridView grids[kKinds]) { return tlh::reserve_query_sort(c, grids); }
-}  // namespace
-extern "C++" {
-namespace tlh {
-// (also called from the grid build when the sort's first pass rides on it: the SAME sizes, so that nothing is re-allocated -- and
-//  lost -- between that pass and the rest of the sort)
-int reserve_query_sort(tloam_ctx* c, const GridView grids[kKinds]) {
-  const size_t n_slots = (size_t)c->sv.slot_off[kKinds];
-  const size_t ntiles = (size_t)build_tile_count(grids, c->sv.slot_off);
-  // (tile counts follow the bounding boxes like the cell tables: grow with room to spare)
-  const size_t nt_res = (ntiles + 1 > c->tile_cnt.cap || ntiles + 1 > c->tile_scan.cap) ? 2 * ntiles + 64 : ntiles;
-  {
-    // The query-tile histogram is zeroed by the frame's start (k_frame_init / the extra blocks of the grid build's first launch),
-    // which has been enqueued by now: a histogram that has to be re-allocated HERE -- the scan's table was shorter than the
-    // histogram's, or the sizes asked for at the two places differ by the one element that crosses an allocation step -- is
-    // zeroed again.  (Until round 5 it was not: the counting sort then ranked the queries on what the new block happened to
-    // hold and scattered them out of bounds -- a GPU memory fault or a silently wrong query order on the first large frame of a
-    // context, whenever the block was not fresh; found by tests/tools/fuzz_call_order.py.)
-    const size_t before = c->tile_cnt.cap;
-    HIPC(c, c->tile_cnt.reserve(nt_res + 1));
-    if (c->tile_cnt.cap != before)
-      HIPC(c, hipMemsetAsync(c->tile_cnt.p, 0, c->tile_cnt.cap * sizeof(unsigned long long), c->stream));
-  }
-  HIPC(c, c->tile_scan.reserve(nt_res + 1));
-  HIPC(c, c->tile_fill.reserve(std::max<size_t>((size_t)nt_res, (size_t)n_slots + 1))  /* rank of every slot inside its tile */); HIPC(c, c->tile_of_slot.reserve(n_slots + 1));
-  HIPC(c, c->qrec.reserve(n_slots + 1));
-  HIPC(c, c->scan_tmp.reserve(scan_tmp_elems(std::max(nt_res + 1, n_slots + 1))));
-  c->scan1p_q_use = !c->no_scan_1p && scan_1p_applies(ntiles + 1, c->device_cus);
-  if (c->scan1p_q_use) {
-    const size_t before = c->scan1p_q.cap;
-    HIPC(c, c->scan1p_q.reserve(scan_1p_ctl_elems(nt_res + 1)));
-    if (c->scan1p_q.cap != before) HIPC(c, hipMemsetAsync(c->scan1p_q.p, 0, c->scan1p_q.cap * sizeof(unsigned long long), c->stream));
-  }
-  return TLOAM_OK;
-}
-}  // namespace tlh
-}  // extern "C++"
-namespace {
 // :976-1020 the four builders (K1 + K2), the flag scan, the index-order caps.  Small single-rank frames: the scan, the
 // caps, the compaction AND the alternative (refresh) are one launch (k_prepare_small) -- `also_refresh` says whether this
 // call stands for both alternatives of a device-gated iteration.
@@ -605,12 +436,7 @@ WeightParams weight_params(const tloam_ctx* c, double mu, const BuildParams& bp)
   for (int k = 0; k < kKinds; ++k) wp.active[k] = bp.active[k];
   return wp;
 }
-// :1049-1086 thresholds + weight update, :1091-1094 cost sums, publish (+ device-side loop control when ctl.fast)
-size_t total_seg_cap(const tloam_ctx* c) {
-  size_t cap = 0;
-  for (int k = 0; k < kKinds; ++k) cap += c->kd[k].c_cap;
-  return cap;
-}
+double next_mu(const tloam_ctx* c, double mu, int iter) { return mu * exp((double)(iter + 1) * c->cfg.gnc_factor); }   // :1089
 // a result slot's `incomplete` word as the outcome of its outer iteration: OS_COMM_ERROR and OS_INCOMPLETE become the error
 // they stand for, with last_error; any other word is TLOAM_OK (a caller that tops an unfinished Solve up does so before it asks).
 // *hand_over_timed_out (may be null) is set when the in-launch hand-over of one rank timed out: the device loop's fall-back.
@@ -630,8 +456,9 @@ int slot_error(tloam_ctx* c, int incomplete, bool* hand_over_timed_out) {
   }
   return TLOAM_OK;
 }
+// :1049-1086 thresholds + weight update, :1091-1094 cost sums, publish (+ device-side loop control when ctl.fast)
 // one 1024-thread block does weights + sums + publish in a single launch
-bool finish_small_path(const tloam_ctx* c) { return one_rank(c) && total_seg_cap(c) <= 16384; }
+bool finish_small_path(const tloam_ctx* c) { return one_rank(c) && seg_cap_sum(c) <= 16384; }
 int enqueue_finish(tloam_ctx* c, const WeightParams& wp, const HostMirror& hm, const OuterCtl& ctl, int iter = 0, int built = 1) {
   if (c->direct) {   // (c->cv carries the weight stream of outer iteration `iter`: direct_set_parity)
     const FinishLargeArgs fin = direct_finish_args(c, &c->cv, &wp, hm, ctl, iter, /*riding=*/0, built);
@@ -666,7 +493,7 @@ bool account_outer(tloam_ctx* c, int iter, const GnState& S, double mu, int swee
     else { hist[2] = hist[1]; hist[1] = hist[0]; }
     hist[0] = used;
   }
-  c->mu = mu * exp((double)(iter + 1) * c->cfg.gnc_factor);  // :1089
+  c->mu = next_mu(c, mu, iter);
   tloam_stats& st = c->stats;
   st.outer_iterations = iter + 1;
   st.gn_evaluations = S.gn_evaluations;
@@ -708,71 +535,9 @@ double initial_mu(const tloam_ctx* c) {
   if (mu <= 0) mu = 1e-10;
   return mu;
 }
-}  // namespace
-
-int tloam_sm_outer(tloam_ctx* c, int* done, tloam_stats* stats) {
-  if (!c || !c->active) return TLOAM_E_NOT_READY;
-  HIPC(c, hipSetDevice(c->device));
-  const int iter = c->iter;
-  if (iter >= c->cfg.max_iterations) {  // loop condition :966
-    if (done) *done = 1;
-    if (stats) *stats = c->stats;
-    return TLOAM_OK;
-  }
-  int rc;
-  BuildParams bp;
-  GridView grids[kKinds];
-  outer_params(c, &bp, grids);
-  rc = outer_reserve(c, grids);
-  if (rc != TLOAM_OK) return rc;
-  // The correspondence search is a pure function of (pose, clouds).  In the reference's GNC dynamics the
-  // outer iterations after the first usually reject every step (SURVEY A.13), so the pose -- hence every
-  // neighbour list, fit and gate -- is bit-identical to the previous outer iteration: then only the
-  // captured weights and the zeroed side-channel slots of the compact set have to be refreshed.
-  const bool same_pose = iter > 0 && c->have_build && memcmp(c->build_x, c->stats.se3, sizeof(c->build_x)) == 0 &&
-                         !c->dbg_no_build_reuse;
-  if (c->direct) direct_set_parity(c, iter);
-  if (!same_pose) {
-    rc = enqueue_build(c, bp, grids, /*rebin=*/iter == 0, nullptr, nullptr, false, nullptr, iter);
-    if (rc != TLOAM_OK) return rc;
-    memcpy(c->build_x, c->stats.se3, sizeof(c->build_x));
-    c->have_build = true;
-  } else if (!c->direct) {
-    launch_refresh(c->sv, c->cv, c->stream);
-  }
-  if (iter == 0) c->mu = initial_mu(c);
-  // ---- :1036-1047 ceres::Solve, device resident.  Only as many sweeps as this outer iteration needed in the
-  //      last three frames are enqueued (typically 2 of 5 from the second iteration on: the retried rejected steps
-  //      are served by the evaluation reuse); the weight update and the finish kernel are gated on the
-  //      minimiser having terminated, and raise `incomplete` otherwise -- then the Solve is topped up.
-  const int planned = planned_sweeps_for(c, iter);
-  const double mu = c->mu;
-  const WeightParams wp = weight_params(c, mu, bp);
-  rc = enqueue_solve(c, /*armed=*/true, planned, &wp);  // armed by sm_begin / the previous iteration's finish kernel
-  if (rc != TLOAM_OK) return rc;
-  const OuterCtl host_decides{c->cfg.cost_threshold, 0, 0};
-  const int sweeps_before = c->stats.gn_sweeps;
-  for (int attempt = 0;; ++attempt) {
-    const HostMirror hm = next_mirror(c);
-    rc = enqueue_finish(c, wp, hm, host_decides, iter, same_pose ? 0 : 1);
-    if (rc != TLOAM_OK) return rc;
-    rc = wait_state(c, hm);
-    if (rc != TLOAM_OK) return rc;
-    if (!c->h_state->incomplete) break;
-    if (c->h_state->incomplete == OS_COMM_ERROR) return slot_error(c, OS_COMM_ERROR, nullptr);
-    if (attempt > 0 || planned >= kSolveSweeps) return slot_error(c, OS_INCOMPLETE, nullptr);
-    rc = enqueue_solve(c, /*armed=*/true, kSolveSweeps - planned, &wp);  // top up, then weights + finish again
-    if (rc != TLOAM_OK) return rc;
-  }
-  const GnState& S = *c->h_state;
-  rc = harvest_k3_events(c, S.gn_sweeps - sweeps_before);
-  if (rc != TLOAM_OK) return rc;
-  bool weight_violation = false;
-  const bool fin = account_outer(c, iter, S, mu, sweeps_before, &weight_violation);
-  if (c->direct) c->w_parity = (iter + 1) & 1;   // (c->cv stays on the stream this Solve captured)
-  if (done) *done = fin ? 1 : 0;
-  if (stats) *stats = c->stats;
-  return weight_violation ? TLOAM_E_WEIGHT_RANGE : TLOAM_OK;  // the iteration is complete either way (:871)
+// the set of outer iteration `iter` is (re)built iff the pose has moved since the last build (the frame's first always builds)
+bool pose_moved_since_build(const tloam_ctx* c, int iter) {
+  return iter == 0 || memcmp(c->build_x, c->stats.se3, sizeof(c->build_x)) != 0;
 }
 
 // ---- scanMatching with the outer GNC loop driven from the device ------------------------------------------------
@@ -787,7 +552,6 @@ int tloam_sm_outer(tloam_ctx* c, int* done, tloam_stats* stats) {
 // build + (search + Solve launch) per RUN of outer iterations -- the Solve launch ends its iteration itself and goes on
 // with the next one while the pose stands still.  Only the launches of the first kEnqueueAhead iterations are enqueued up
 // front; the host waits for the result slots IN ORDER and adds a (search, Solve) pair when a slot carries OS_NEEDS_HOST.
-namespace {
 struct DeviceLoopPlan {
   int planned[kMaxOuterFast] = {}, solve_start[kMaxOuterFast] = {}, used[kMaxOuterFast] = {};
   double mus[kMaxOuterFast] = {};
@@ -868,7 +632,7 @@ int enqueue_outer_iterations(tloam_ctx* c, int first, double mu, const BuildPara
       P.hms[iter] = next_mirror(c, iter);
       F.wp[iter] = weight_params(c, m, bp);
       F.hm[iter] = P.hms[iter];
-      m = m * exp((double)(iter + 1) * c->cfg.gnc_factor);  // :1089
+      m = next_mu(c, m, iter);
     }
     P.prep = prep;
     P.enq_end = first;
@@ -878,14 +642,10 @@ int enqueue_outer_iterations(tloam_ctx* c, int first, double mu, const BuildPara
     if (c->direct) direct_set_parity(c, iter);   // what this iteration's Solve (and its finish) read; the search does not care
     if (iter == 0) {
       rc = enqueue_build(c, bp, grids, /*rebin=*/true, nullptr, nullptr, in_solve);
-      prep.run_build = nullptr;
-      prep.run_refresh = nullptr;
     } else if (pending) {
       FinishSmallArgs fin{&c->cv, &wp_prev, c->seg_n.p, c->sums16.p, P.hms[iter - 1], ctl_prev, c->wpart.p, c->k3_ticket.p + 1};
       launch_build_finish_small(c->sv, grids, bp, st, fin, c->stream);
       if (!in_solve) launch_prepare_small(c->sv, c->cv, bp, c->seg_n.p, st, run_build, run_refresh, c->stream);
-      prep.run_build = run_build;
-      prep.run_refresh = run_refresh;
       pending = false;
     } else if (pending_large) {
       FinishLargeArgs fin{&c->cv, &wp_prev, c->seg_n.p, c->sums16.p, P.hms[iter - 1], ctl_prev, c->fin_rows.p, c->k3_ticket.p + 1,
@@ -896,15 +656,13 @@ int enqueue_outer_iterations(tloam_ctx* c, int first, double mu, const BuildPara
         fin = direct_finish_args(c, &cv_prev, &wp_prev, P.hms[iter - 1], ctl_prev, iter - 1, /*riding=*/1, iter - 1 == 0 ? 1 : -1);
       }
       rc = enqueue_build(c, bp, grids, /*rebin=*/false, run_build, run_refresh, in_solve, &fin, iter);
-      prep.run_build = run_build;
-      prep.run_refresh = run_refresh;
       pending_large = false;
     } else {
       rc = enqueue_build(c, bp, grids, /*rebin=*/false, run_build, run_refresh, in_solve, nullptr, iter);   // both alternatives, device-gated
-      prep.run_build = run_build;
-      prep.run_refresh = run_refresh;
     }
     if (rc != TLOAM_OK) return rc;
+    prep.run_build = iter == 0 ? nullptr : run_build;   // (the frame's first iteration always builds: no gate)
+    prep.run_refresh = iter == 0 ? nullptr : run_refresh;
     P.planned[iter] = planned_sweeps_for(c, iter);
     P.solve_start[iter] = c->batch_launches;
     const WeightParams wp_iter = weight_params(c, mu, bp);
@@ -925,8 +683,22 @@ int enqueue_outer_iterations(tloam_ctx* c, int first, double mu, const BuildPara
       rc = enqueue_finish(c, weight_params(c, mu, bp), P.hms[iter], ctl, iter, iter == 0 ? 1 : -1);
       if (rc != TLOAM_OK) return rc;
     }
-    mu = mu * exp((double)(iter + 1) * c->cfg.gnc_factor);  // :1089
+    mu = next_mu(c, mu, iter);
   }
+  return TLOAM_OK;
+}
+
+// The host's wait for outer iteration `iter`.  frame_first (behind everything the frame enqueues: its start, a top-up): the last
+// slot first -- it is written last (stream order), whatever the frame did; the iteration's own slot was written before it and
+// is already there -- this only unpacks it.  Finish-in-the-Solve mode: the slots are waited for in order -- the frame's result
+// is there when its last iteration's is, and a launch may have to be added on the way.
+int wait_slots(tloam_ctx* c, const DeviceLoopPlan& P, int iter, bool frame_first) {
+  const int M = c->cfg.max_iterations;
+  if (frame_first && !P.in_launch_finish) {
+    const int rc = wait_state(c, P.hms[M - 1], M - 1);
+    if (rc != TLOAM_OK) return rc;
+  }
+  if (iter < M - 1 || P.in_launch_finish) return wait_state(c, P.hms[iter], iter);
   return TLOAM_OK;
 }
 
@@ -935,26 +707,17 @@ int scan_match_device_loop(tloam_ctx* c, bool* weight_violation) {
   BuildParams bp;
   GridView grids[kKinds];
   outer_params(c, &bp, grids);
-  int rc = outer_reserve(c, grids);
+  int rc = reserve_query_sort(c, grids);
   if (rc != TLOAM_OK) return rc;
   GnState* st = c->state.p;
   DeviceLoopPlan P;
   rc = enqueue_outer_iterations(c, 0, initial_mu(c), bp, grids, P);
   if (rc != TLOAM_OK) return rc;
-  if (!P.in_launch_finish) {
-    rc = wait_state(c, P.hms[M - 1], M - 1);   // the last slot is written last (stream order), whatever the frame did
-    if (rc != TLOAM_OK) return rc;
-  }
   // ---- the frame's bookkeeping, iteration by iteration, from the mirrored slots
   int topups = 0;
   for (int iter = 0; iter < M; ++iter) {
-    if (iter < M - 1 || P.in_launch_finish) {
-      // (all launches enqueued: written before the last slot, already there -- this only unpacks it.  Finish-in-the-Solve
-      //  mode: the slots are waited for in order -- the frame's result is there when its last iteration's is, and a launch
-      //  may have to be added on the way)
-      rc = wait_state(c, P.hms[iter], iter);
-      if (rc != TLOAM_OK) return rc;
-    }
+    rc = wait_slots(c, P, iter, /*frame_first=*/iter == 0);
+    if (rc != TLOAM_OK) return rc;
     GnState* Sm = &c->h_state[iter];
     const bool needs_host = (Sm->incomplete & OS_NEEDS_HOST) != 0;
     if (Sm->incomplete & OS_SET_STALE) c->set_stale = true;   // (direct set: the loop ended beside a search that had already run)
@@ -986,28 +749,22 @@ int scan_match_device_loop(tloam_ctx* c, bool* weight_violation) {
       P.hms[iter] = next_mirror(c, iter);
       // (the finish that found the Solve unfinished has cleared the device's gates: whether this iteration built its set is the
       //  host's to say -- the pose the previous iteration ended at against the pose of the last build, as the bookkeeping below)
-      const int built_top = (iter == 0 || memcmp(c->build_x, c->stats.se3, sizeof(c->build_x)) != 0) ? 1 : 0;
+      const int built_top = pose_moved_since_build(c, iter) ? 1 : 0;
       rc = enqueue_finish(c, wp_top, P.hms[iter], OuterCtl{c->cfg.cost_threshold, 1, iter == M - 1 ? 1 : 0}, iter, built_top);
       if (rc != TLOAM_OK) return rc;
       if (iter + 1 < M) {
-        rc = enqueue_outer_iterations(c, iter + 1, P.mus[iter] * exp((double)(iter + 1) * c->cfg.gnc_factor), bp, grids, P);
+        rc = enqueue_outer_iterations(c, iter + 1, next_mu(c, P.mus[iter], iter), bp, grids, P);
         if (rc != TLOAM_OK) return rc;
       }
-      if (!P.in_launch_finish) {
-        rc = wait_state(c, P.hms[M - 1], M - 1);
-        if (rc != TLOAM_OK) return rc;
-      }
-      if (iter < M - 1 || P.in_launch_finish) {
-        rc = wait_state(c, P.hms[iter], iter);
-        if (rc != TLOAM_OK) return rc;
-      }
+      rc = wait_slots(c, P, iter, /*frame_first=*/true);
+      if (rc != TLOAM_OK) return rc;
       S = &c->h_state[iter];
       rc = slot_error(c, S->incomplete, &c->hand_over_timed_out);
       if (rc != TLOAM_OK) return rc;
     }
     const int sweeps_before = c->stats.gn_sweeps;
     // the compact set of this iteration was (re)built iff the pose had moved since the last build
-    if (iter == 0 || memcmp(c->build_x, c->stats.se3, sizeof(c->build_x)) != 0) memcpy(c->build_x, c->stats.se3, sizeof(c->build_x));
+    if (pose_moved_since_build(c, iter)) memcpy(c->build_x, c->stats.se3, sizeof(c->build_x));
     c->have_build = true;
     c->mu = P.mus[iter];
     bool wv = false;
@@ -1034,6 +791,225 @@ int scan_match_device_loop(tloam_ctx* c, bool* weight_violation) {
   return 0;
 }
 }  // namespace
+
+extern "C" {
+
+// ---- scanMatching, stepwise ---------------------------------------------------------------------
+int tloam_sm_begin(tloam_ctx* c, const double predict[16], const double* omega3) {
+  if (!c || !predict) return TLOAM_E_INVALID;
+  HIPC(c, hipSetDevice(c->device));
+  for (int k = 0; k < kKinds; ++k)  // the reference asserts (registration.cpp:928-929)
+    if (c->kd[k].n_src_full < 10 || c->kd[k].n_tgt < 10) return TLOAM_E_TOO_FEW_POINTS;
+  for (int k = 0; k < kKinds; ++k)  // a hand-over that failed half way (staging, upload) left nothing registered
+    if (!c->kd[k].src_set || !c->kd[k].tgt_set) { c->last_error = "a source / target hand-over failed: hand the frame over again"; return TLOAM_E_NOT_READY; }
+  Pose P;
+  if (!pose_from_matrix(predict, &P)) return TLOAM_E_BAD_POSE;  // SOPHUS_ENSURE in the reference
+  double x[6];
+  se3_log(P, x);  // :881
+  if (sqrt(x[3] * x[3] + x[4] * x[4] + x[5] * x[5]) < 1e-2) {  // :884-886
+    double u[3] = {0.0, 0.0, 1.0};
+    if (omega3) {
+      const double nn = sqrt(omega3[0] * omega3[0] + omega3[1] * omega3[1] + omega3[2] * omega3[2]);
+      if (nn > 0.0) { u[0] = omega3[0] / nn; u[1] = omega3[1] / nn; u[2] = omega3[2] / nn; }
+    }
+    x[3] = u[0] * 1e-4; x[4] = u[1] * 1e-4; x[5] = u[2] * 1e-4;
+  }
+  int rc = ensure_common(c);
+  if (rc != TLOAM_OK) return rc;
+  // ---- per-source-slot arrays (:931-949 weights = 1, residual slots = 0)
+  size_t off = 0;
+  for (int k = 0; k < kKinds; ++k) {
+    c->sv.slot_off[k] = (int)off;
+    c->sv.src_lo[k] = (int)c->kd[k].src_lo;
+    off += c->kd[k].n_src;
+  }
+  c->sv.slot_off[kKinds] = (int)off;
+  const size_t ns = std::max<size_t>(off, 1);
+  HIPC(c, c->sx.reserve(ns)); HIPC(c, c->sy.reserve(ns)); HIPC(c, c->sz.reserve(ns)); HIPC(c, c->w_src.reserve(ns));
+  HIPC(c, c->raw.reserve(ns * 8));
+  HIPC(c, c->flags.reserve(ns + 1)); HIPC(c, c->scan.reserve(ns + 1));
+  HIPC(c, c->scan_tmp.reserve(scan_tmp_elems(ns + 1)));
+  c->sv.sx = c->sx.p; c->sv.sy = c->sy.p; c->sv.sz = c->sz.p; c->sv.w_src = c->w_src.p;
+  c->sv.raw = c->raw.p;
+  c->sv.flags = c->flags.p; c->sv.scan = c->scan.p;
+  c->direct = direct_applies(c, off);
+  c->set_stale = false;
+  c->w_parity = 0;
+  if (c->direct) {
+    HIPC(c, c->fin_rows.reserve(kFinRowsDoubles));
+    c->blk_cnt_n = (off + 63) / 64;   // one-wave blocks of the thread-per-query search (logical: the sorted queries, 64 each)
+    HIPC(c, c->blk_cnt.reserve(2 * c->blk_cnt_n * kKinds + 8));
+    HIPC(c, c->row_of_pos.reserve(off + 64));
+    if (!c->fin_tickets.p) {
+      HIPC(c, c->fin_tickets.reserve(128));
+      HIPC(c, hipMemsetAsync(c->fin_tickets.p, 0, c->fin_tickets.cap * sizeof(int), c->stream));
+    }
+  }
+  // ---- compact segments: at most min(n_src, maxnum) factors per kind (a direct set: one row per source point, which is the same)
+  for (int k = 0; k < kKinds; ++k) {
+    const size_t cap = std::min<size_t>(c->kd[k].n_src, (size_t)std::max(kind_maxnum(c->cfg, k), 0));
+    rc = reserve_seg(c, k, cap);
+    if (rc != TLOAM_OK) return rc;
+  }
+  c->prebuilt = false;
+  plan_sweeps(c);
+  {
+    // the one-launch Solve compacts the factor set itself when every kind's flag bytes fit a wave (SlotView::flagb)
+    bool fits = solve_small_path(c) && prepare_small_fits(c->sv);
+    for (int k = 0; k < kKinds; ++k) fits = fits && c->kd[k].n_src <= (size_t)kFlagbStride;
+    c->sv.flagb = nullptr;
+    if (fits) {
+      HIPC(c, c->flagb.reserve((size_t)kKinds * kFlagbStride));
+      c->sv.flagb = c->flagb.p;
+    }
+  }
+  rc = reserve_partials(c);
+  if (rc != TLOAM_OK) return rc;
+  // ---- the start of the frame -- scan-frame sources AoS -> SoA slots, weights = 1 (:931-949), flag-scan terminator,
+  //      minimiser state zeroed with `parameters` = x (passed by value) and armed for the first Solve -- rides on the
+  //      first launch of the grid build
+  FrameInitHook hook;
+  memset(&hook, 0, sizeof(hook));
+  for (int k = 0; k < kKinds; ++k) { hook.fi.src_aos[k] = c->kd[k].src_ptr; hook.fi.slot_off[k] = c->sv.slot_off[k]; }
+  hook.fi.slot_off[kKinds] = c->sv.slot_off[kKinds];
+  for (int i = 0; i < 6; ++i) hook.fi.x[i] = x[i];
+  hook.fi.no_eval_reuse = c->dbg_no_eval_reuse ? 1 : 0;
+  hook.fi.direct = c->direct ? 1 : 0;
+  if (c->direct) direct_set_parity(c, 0);
+  // 1 M-class single-rank frames: the first pass of the query sort rides on the last launch of the grid build (QueryBinRide)
+  QueryBinRide qbin;
+  memset(&qbin, 0, sizeof(qbin));
+  c->qbin_rode = false;
+  if (one_rank(c) && !c->no_qbin_ride && direct_set_size((int)std::min<size_t>(off, (size_t)INT32_MAX))) {
+    qbin.sv = c->sv;
+    qbin.bp = build_params(c);
+    qbin.st = c->state.p;
+    hook.qbin = &qbin;
+  }
+  hook.b = FrameInitBufs{c->sx.p, c->sy.p, c->sz.p, c->w_src.p, c->flags.p, c->state.p, c->seg_n.p};
+  hook.n_slots = c->sv.slot_off[kKinds];
+  // ---- :889-915 four search structures over the submap clouds: one launch per build phase for all kinds
+  {
+    double radius[kKinds];
+    GridView views[kKinds];
+    for (int k = 0; k < kKinds; ++k) radius[k] = kind_radius(c->cfg, k);
+    // a sharded rank searches only the kinds it holds source points of (tloam_shard_ranges_frame): the other grids are not built
+    if (c->nranks > 1)
+      for (int k = 0; k < kKinds; ++k)
+        if (c->kd[k].n_src == 0) radius[k] = 0.0;
+    if (c->grids_ahead && c->grids_next_gen == c->tgt_gen && one_rank(c)) {
+      // built when the targets were handed over (tloam_set_target_frame): they become the context's search structures now;
+      // the frame's start is a launch of its own, below.  Used once: a second scanMatching over the same targets builds its own
+      std::swap(c->grids, c->grids_next);
+      for (int k = 0; k < kKinds; ++k) { c->kd[k].gv = c->gv_next[k]; c->kd[k].grid_valid = true; }
+      c->grids_ahead = false;
+    } else {
+      rc = build_grids(c, c->grids, radius, views, &hook);
+      if (rc != TLOAM_OK) return rc;
+      c->qbin_rode = hook.qbin_done;
+      // (a kind whose grid was skipped -- radius forced to 0 above: a sharded rank without source points of it -- has an EMPTY
+      //  view: it is not a search structure getFitnessScore or anybody else may use)
+      for (int k = 0; k < kKinds; ++k) { c->kd[k].gv = views[k]; c->kd[k].grid_valid = radius[k] > 0.0; }
+    }
+  }
+  if (!hook.consumed) {  // (no grid launch: cannot happen with >= 10 targets per kind, kept for safety)
+    GridView gviews[kKinds];
+    for (int k = 0; k < kKinds; ++k) gviews[k] = c->kd[k].gv;
+    const size_t ntiles = (size_t)build_tile_count(gviews, c->sv.slot_off);
+    HIPC(c, c->tile_cnt.reserve(ntiles + 1 > c->tile_cnt.cap ? 2 * ntiles + 64 : ntiles + 1));   // (room to spare, as build_grids_over)
+    hook.fi.tile_cnt = c->tile_cnt.p;
+    hook.fi.n_tile_cnt = (int)ntiles + 1;
+    launch_frame_init(hook.fi, hook.b, c->stream);
+  }
+  if (c->direct) {
+    // a kind whose target cloud has no finite point has no search grid: its queries are not in the sorted order, and the rows of a
+    // direct set ARE that order -- such a frame compacts (the frame's start, already enqueued, has set seg_n to the row counts)
+    bool all = true;
+    for (int k = 0; k < kKinds; ++k) all = all && c->kd[k].gv.n > 0;
+    if (!all) {
+      c->direct = false;
+      HIPC(c, hipMemsetAsync(c->seg_n.p, 0, kKinds * sizeof(int), c->stream));
+    }
+  }
+  c->wait_us = 0.0;
+  c->mu = 1.0;  // :961
+  c->noise_bound_sq = c->cfg.noise_bound * c->cfg.noise_bound;
+  if (c->noise_bound_sq < 1e-16) c->noise_bound_sq = 1e-2;  // :963-964
+  for (int k = 0; k < kKinds; ++k) { c->prev_cost[k] = INFINITY; c->cur_cost[k] = INFINITY; }  // :952-959
+  c->iter = 0;
+  c->active = true;
+  c->have_build = false;
+  memset(&c->stats, 0, sizeof(c->stats));
+  memcpy(c->stats.se3, x, sizeof(x));
+  c->ev_used = 0;
+  c->ev_batch_idx.clear();
+  c->batch_launches = 0;
+  return TLOAM_OK;
+}
+
+int tloam_sm_outer(tloam_ctx* c, int* done, tloam_stats* stats) {
+  if (!c || !c->active) return TLOAM_E_NOT_READY;
+  HIPC(c, hipSetDevice(c->device));
+  const int iter = c->iter;
+  if (iter >= c->cfg.max_iterations) {  // loop condition :966
+    if (done) *done = 1;
+    if (stats) *stats = c->stats;
+    return TLOAM_OK;
+  }
+  int rc;
+  BuildParams bp;
+  GridView grids[kKinds];
+  outer_params(c, &bp, grids);
+  rc = reserve_query_sort(c, grids);
+  if (rc != TLOAM_OK) return rc;
+  // The correspondence search is a pure function of (pose, clouds).  In the reference's GNC dynamics the
+  // outer iterations after the first usually reject every step (SURVEY A.13), so the pose -- hence every
+  // neighbour list, fit and gate -- is bit-identical to the previous outer iteration: then only the
+  // captured weights and the zeroed side-channel slots of the compact set have to be refreshed.
+  const bool same_pose = c->have_build && !pose_moved_since_build(c, iter) && !c->dbg_no_build_reuse;
+  if (c->direct) direct_set_parity(c, iter);
+  if (!same_pose) {
+    rc = enqueue_build(c, bp, grids, /*rebin=*/iter == 0, nullptr, nullptr, false, nullptr, iter);
+    if (rc != TLOAM_OK) return rc;
+    memcpy(c->build_x, c->stats.se3, sizeof(c->build_x));
+    c->have_build = true;
+  } else if (!c->direct) {
+    launch_refresh(c->sv, c->cv, c->stream);
+  }
+  if (iter == 0) c->mu = initial_mu(c);
+  // ---- :1036-1047 ceres::Solve, device resident.  Only as many sweeps as this outer iteration needed in the
+  //      last three frames are enqueued (typically 2 of 5 from the second iteration on: the retried rejected steps
+  //      are served by the evaluation reuse); the weight update and the finish kernel are gated on the
+  //      minimiser having terminated, and raise `incomplete` otherwise -- then the Solve is topped up.
+  const int planned = planned_sweeps_for(c, iter);
+  const double mu = c->mu;
+  const WeightParams wp = weight_params(c, mu, bp);
+  rc = enqueue_solve(c, /*armed=*/true, planned, &wp);  // armed by sm_begin / the previous iteration's finish kernel
+  if (rc != TLOAM_OK) return rc;
+  const OuterCtl host_decides{c->cfg.cost_threshold, 0, 0};
+  const int sweeps_before = c->stats.gn_sweeps;
+  for (int attempt = 0;; ++attempt) {
+    const HostMirror hm = next_mirror(c);
+    rc = enqueue_finish(c, wp, hm, host_decides, iter, same_pose ? 0 : 1);
+    if (rc != TLOAM_OK) return rc;
+    rc = wait_state(c, hm);
+    if (rc != TLOAM_OK) return rc;
+    if (!c->h_state->incomplete) break;
+    if (c->h_state->incomplete == OS_COMM_ERROR) return slot_error(c, OS_COMM_ERROR, nullptr);
+    if (attempt > 0 || planned >= kSolveSweeps) return slot_error(c, OS_INCOMPLETE, nullptr);
+    rc = enqueue_solve(c, /*armed=*/true, kSolveSweeps - planned, &wp);  // top up, then weights + finish again
+    if (rc != TLOAM_OK) return rc;
+  }
+  const GnState& S = *c->h_state;
+  rc = harvest_k3_events(c, S.gn_sweeps - sweeps_before);
+  if (rc != TLOAM_OK) return rc;
+  bool weight_violation = false;
+  const bool fin = account_outer(c, iter, S, mu, sweeps_before, &weight_violation);
+  if (c->direct) c->w_parity = (iter + 1) & 1;   // (c->cv stays on the stream this Solve captured)
+  if (done) *done = fin ? 1 : 0;
+  if (stats) *stats = c->stats;
+  return weight_violation ? TLOAM_E_WEIGHT_RANGE : TLOAM_OK;  // the iteration is complete either way (:871)
+}
 
 int tloam_sm_end(tloam_ctx* c, double result[16], tloam_stats* stats) {
   if (!c || !c->active || !result) return TLOAM_E_NOT_READY;
@@ -1134,532 +1110,6 @@ int tloam_scan_match(tloam_ctx* c, const double predict[16], const double* omega
     HIPC(c, hipStreamSynchronize(c->stream));
   }
   return weight_violation ? TLOAM_E_WEIGHT_RANGE : TLOAM_OK;
-}
-
-// ---- getFitnessScore (registration.cpp:257-296) -------------------------------------------------
-int tloam_fitness(tloam_ctx* c, double* fitness, double* rmse) {
-  if (!c || !fitness || !rmse) return TLOAM_E_INVALID;
-  *fitness = 0.0;
-  *rmse = 0.0;
-  if (!(c->cfg.fitness_thres > 0.0)) return TLOAM_OK;  // :258-261 (a NaN threshold finds nobody either)
-  if (c->active) return TLOAM_E_NOT_READY;  // between sm_begin and sm_end the context belongs to the solve
-  HIPC(c, hipSetDevice(c->device));
-  const int blocks = 64;
-  HIPC(c, c->misc.reserve(4096));
-  const int order[kKinds] = {TLOAM_KIND_EDGE, TLOAM_KIND_SPHERE, TLOAM_KIND_PLANAR, TLOAM_KIND_GROUND};  // :287-290
-  double fit_local[kKinds] = {0, 0, 0, 0}, err_local[kKinds] = {0, 0, 0, 0};
-  for (int o = 0; o < kKinds; ++o) {
-    const int k = order[o];
-    KindData& K = c->kd[k];
-    // the kd-trees are the ones built by the last scanMatching (:889-915); none yet -> no hits
-    if (!K.grid_valid || K.n_src == 0 || !K.src_set || !K.src_ptr) continue;   // (a hand-over that failed registered nothing)
-    // raw scan-frame source points (:271): this kind's AoS block as SoA, in scratch of its own (the slot arrays
-    // sx/sy/sz belong to scan_match: SlotView holds their addresses)
-    HIPC(c, c->fit_x.reserve(K.n_src)); HIPC(c, c->fit_y.reserve(K.n_src)); HIPC(c, c->fit_z.reserve(K.n_src));
-    launch_aos_to_soa(K.src_ptr, K.n_src, c->fit_x.p, c->fit_y.p, c->fit_z.p, c->stream);
-    launch_fitness(K.gv, c->fit_x.p, c->fit_y.p, c->fit_z.p, (int)K.n_src, c->cfg.fitness_thres, c->misc.p, blocks, c->stream);
-    HIPC(c, hipMemcpyAsync(c->h_small, c->misc.p, sizeof(double) * blocks * 2, hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipStreamSynchronize(c->stream));
-    for (int b = 0; b < blocks; ++b) { err_local[k] += c->h_small[2 * b]; fit_local[k] += c->h_small[2 * b + 1]; }
-  }
-  if (c->nranks > 1) {  // sharded sources: hits and squared errors add up across ranks
-    HIPC(c, c->misc.reserve(16));
-    for (int k = 0; k < kKinds; ++k) { c->h_small[k] = fit_local[k]; c->h_small[4 + k] = err_local[k]; }
-    HIPC(c, hipMemcpyAsync(c->misc.p, c->h_small, sizeof(double) * 8, hipMemcpyHostToDevice, c->stream));
-    int rc = allreduce(c, c->misc.p, 8);
-    if (rc != TLOAM_OK) return rc;
-    HIPC(c, hipMemcpyAsync(c->h_small, c->misc.p, sizeof(double) * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipStreamSynchronize(c->stream));
-    for (int k = 0; k < kKinds; ++k) { fit_local[k] = c->h_small[k]; err_local[k] = c->h_small[4 + k]; }
-  }
-  for (int o = 0; o < kKinds; ++o) {
-    const int k = order[o];
-    if (fit_local[k] > 0.0) {  // :278-284
-      *fitness += fit_local[k] / (double)c->kd[k].n_src_full;
-      *rmse += sqrt(err_local[k] / fit_local[k]);
-    }
-  }
-  return TLOAM_OK;
-}
-
-// ---- introspection --------------------------------------------------------------------------------
-static int download_soa3(tloam_ctx* c, const double* x, const double* y, const double* z, size_t n, double* aos) {
-  std::vector<double> tmp(3 * n);
-  HIPC(c, hipMemcpy(tmp.data(), x, sizeof(double) * n, hipMemcpyDeviceToHost));
-  HIPC(c, hipMemcpy(tmp.data() + n, y, sizeof(double) * n, hipMemcpyDeviceToHost));
-  HIPC(c, hipMemcpy(tmp.data() + 2 * n, z, sizeof(double) * n, hipMemcpyDeviceToHost));
-  for (size_t i = 0; i < n; ++i) { aos[3 * i] = tmp[i]; aos[3 * i + 1] = tmp[n + i]; aos[3 * i + 2] = tmp[2 * n + i]; }
-  return TLOAM_OK;
-}
-
-// ---- a direct set through the getters: rebuilt first if it is stale, then filtered (idx >= 0) and put into source-index order ----
-static int regen_direct_set(tloam_ctx* c) {
-  // the rows hold the geometry of a search that ran on the last Solve's own verdict before the loop ended (OS_SET_STALE): search
-  // again at the pose the SOLVED set was built at (x_build) -- same queries, same order, same arithmetic: the same rows
-  BuildParams bp;
-  GridView grids[kKinds];
-  outer_params(c, &bp, grids);
-  HIPC(c, c->state_scratch.reserve(1));
-  HIPC(c, hipMemcpyAsync(c->state_scratch.p, c->state.p, sizeof(GnState), hipMemcpyDeviceToDevice, c->stream));
-  launch_pose_from_x_build(c->state_scratch.p, c->stream);
-  const DirectSet ds{1, 0, 0, nullptr, c->tile_of_slot.p, c->tile_scan.p, c->row_of_pos.p};
-  launch_build(c->sv, grids, bp, c->state_scratch.p, c->tile_of_slot.p, c->tile_cnt.p, c->tile_scan.p, c->tile_fill.p, c->qrec.p,
-               c->scan_tmp.p, /*rebin=*/false, c->stream, nullptr, nullptr, nullptr, &c->cv, &ds);
-  HIPC(c, hipStreamSynchronize(c->stream));
-  c->set_stale = false;
-  return TLOAM_OK;
-}
-static int get_correspondences_direct(tloam_ctx* c, int kind, size_t capacity, size_t* n, int32_t* src_index, double* a, double* b,
-                                      double* d, double* w, double* cost) {
-  if (c->set_stale) { const int rc = regen_direct_set(c); if (rc != TLOAM_OK) return rc; }
-  const size_t rows = (size_t)(c->sv.slot_off[kind + 1] - c->sv.slot_off[kind]);   // (of the frame the solve began with, not of the cloud registered now)
-  const CorrSeg& s = c->cv.k[kind];
-  std::vector<int> idx(rows);
-  if (rows > 0) HIPC(c, hipMemcpy(idx.data(), s.idx, sizeof(int) * rows, hipMemcpyDeviceToHost));
-  std::vector<std::pair<int, size_t>> order;   // (source index, row) of the factors
-  order.reserve(rows);
-  for (size_t r = 0; r < rows; ++r)
-    if (idx[r] >= 0) order.emplace_back(idx[r], r);
-  std::sort(order.begin(), order.end());
-  const size_t m = order.size();
-  *n = m;
-  if (m > capacity) return TLOAM_E_INVALID;
-  if (m == 0) return TLOAM_OK;
-  std::vector<double> tmp(rows);
-  auto stream = [&](const double* dev, double* out, size_t stride_out, size_t off) -> int {
-    HIPC(c, hipMemcpy(tmp.data(), dev, sizeof(double) * rows, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < m; ++i) out[i * stride_out + off] = tmp[order[i].second];
-    return TLOAM_OK;
-  };
-  int rc = TLOAM_OK;
-  if (src_index) for (size_t i = 0; i < m; ++i) src_index[i] = order[i].first;
-  if (a && ((rc = stream(s.ax, a, 3, 0)) || (rc = stream(s.ay, a, 3, 1)) || (rc = stream(s.az, a, 3, 2)))) return rc;
-  if (b && kind == TLOAM_KIND_EDGE && ((rc = stream(s.bx, b, 3, 0)) || (rc = stream(s.by, b, 3, 1)) || (rc = stream(s.bz, b, 3, 2)))) return rc;
-  if (d && kind <= TLOAM_KIND_GROUND && (rc = stream(s.d, d, 1, 0))) return rc;
-  if (w && (rc = stream(s.w, w, 1, 0))) return rc;
-  if (cost && (rc = stream(s.cost, cost, 1, 0))) return rc;
-  return TLOAM_OK;
-}
-
-int tloam_get_correspondences(tloam_ctx* c, int kind, size_t capacity, size_t* n, int32_t* src_index, double* a,
-                              double* b, double* d, double* w, double* cost) {
-  if (!c || kind < 0 || kind >= kKinds || !n) return TLOAM_E_INVALID;
-  HIPC(c, hipSetDevice(c->device));
-  HIPC(c, hipStreamSynchronize(c->stream));
-  if (c->direct && !c->prebuilt) return get_correspondences_direct(c, kind, capacity, n, src_index, a, b, d, w, cost);
-  int segn[kKinds];
-  HIPC(c, hipMemcpy(segn, c->seg_n.p, sizeof(segn), hipMemcpyDeviceToHost));
-  const size_t m = (size_t)segn[kind];
-  *n = m;
-  if (m > capacity) return TLOAM_E_INVALID;
-  if (m == 0) return TLOAM_OK;
-  const CorrSeg& s = c->cv.k[kind];
-  int rc;
-  if (src_index) HIPC(c, hipMemcpy(src_index, s.idx, sizeof(int) * m, hipMemcpyDeviceToHost));
-  if (a && (rc = download_soa3(c, s.ax, s.ay, s.az, m, a)) != TLOAM_OK) return rc;
-  if (b && kind == TLOAM_KIND_EDGE && (rc = download_soa3(c, s.bx, s.by, s.bz, m, b)) != TLOAM_OK) return rc;
-  if (d && kind <= TLOAM_KIND_GROUND) HIPC(c, hipMemcpy(d, s.d, sizeof(double) * m, hipMemcpyDeviceToHost));
-  if (w) HIPC(c, hipMemcpy(w, s.w, sizeof(double) * m, hipMemcpyDeviceToHost));
-  if (cost) HIPC(c, hipMemcpy(cost, s.cost, sizeof(double) * m, hipMemcpyDeviceToHost));
-  return TLOAM_OK;
-}
-
-int tloam_get_weights(tloam_ctx* c, int kind, size_t capacity, size_t* n, double* w) {
-  if (!c || kind < 0 || kind >= kKinds || !n) return TLOAM_E_INVALID;
-  HIPC(c, hipSetDevice(c->device));
-  // the weights are those of the frame the last scanMatching BEGAN with (its slot table), whatever source cloud has been handed over
-  // since (until round 6 the size came from the registered cloud: a larger cloud handed over after a solve made this a copy past
-  // the end of the weights -- tests/tools/fuzz_call_order.py, TLOAM_E_HIP from a getter)
-  const bool begun = c->w_src.p != nullptr && c->sv.slot_off[kKinds] > 0;
-  const size_t m = begun ? (size_t)(c->sv.slot_off[kind + 1] - c->sv.slot_off[kind]) : c->kd[kind].n_src;
-  *n = m;
-  if (m > capacity || !begun) return TLOAM_E_INVALID;
-  HIPC(c, hipStreamSynchronize(c->stream));
-  if (c->direct && !c->prebuilt) {   // the current GNC weights live in the rows' weight stream `w_parity`: back to source-index order
-    if (w && m > 0 && !c->have_build) {   // (no search has run in this frame yet: registration.cpp:931-949, every weight is 1)
-      for (size_t i = 0; i < m; ++i) w[i] = 1.0;
-    } else if (w && m > 0) {
-      std::vector<int> idx(m);
-      std::vector<double> wr(m);
-      HIPC(c, hipMemcpy(idx.data(), c->cv.k[kind].idx, sizeof(int) * m, hipMemcpyDeviceToHost));
-      HIPC(c, hipMemcpy(wr.data(), direct_w_stream(c, kind, c->w_parity), sizeof(double) * m, hipMemcpyDeviceToHost));
-      for (size_t r = 0; r < m; ++r) w[(size_t)(idx[r] >= 0 ? idx[r] : ~idx[r]) - (size_t)c->sv.src_lo[kind]] = wr[r];
-    }
-    return TLOAM_OK;
-  }
-  if (w && m > 0) HIPC(c, hipMemcpy(w, c->w_src.p + c->sv.slot_off[kind], sizeof(double) * m, hipMemcpyDeviceToHost));
-  return TLOAM_OK;
-}
-
-int tloam_knn(tloam_ctx* c, int kind, const double* q, size_t nq, double radius, int k, int32_t* out_idx,
-              double* out_d2, int32_t* out_cnt) {
-  if (!c || kind < 0 || kind >= kKinds || !q || k < 1 || k > kMaxK || !(radius > 0.0) || !out_idx || !out_d2 || !out_cnt ||
-      nq > kMaxPoints / (size_t)k)
-    return TLOAM_E_INVALID;
-  HIPC(c, hipSetDevice(c->device));
-  KindData& K = c->kd[kind];
-  if (!K.tgt_set || K.n_tgt == 0) {
-    for (size_t i = 0; i < nq; ++i) out_cnt[i] = 0;
-    for (size_t i = 0; i < nq * (size_t)k; ++i) { out_idx[i] = -1; out_d2[i] = 0.0; }
-    return TLOAM_OK;
-  }
-  int rc;
-  GridBuffers tmp;  // a grid over the target currently set, sized for this radius; the scanMatching grids stay intact
-  GridView views[kKinds];
-  {
-    double radii[kKinds] = {0, 0, 0, 0};
-    radii[kind] = radius;
-    rc = build_grids(c, tmp, radii, views);
-    if (rc != TLOAM_OK) return rc;
-  }
-  DBuf<double> qa, qx, qy, qz, d2;
-  DBuf<int> idx, cnt;
-  hipError_t e = hipSuccess;
-  if ((e = qa.reserve(3 * nq + 3)) != hipSuccess || (e = qx.reserve(nq + 1)) != hipSuccess ||
-      (e = qy.reserve(nq + 1)) != hipSuccess || (e = qz.reserve(nq + 1)) != hipSuccess ||
-      (e = d2.reserve(nq * k + 1)) != hipSuccess || (e = idx.reserve(nq * k + 1)) != hipSuccess ||
-      (e = cnt.reserve(nq + 1)) != hipSuccess) {
-    c->last_error = hipGetErrorString(e);
-    return TLOAM_E_HIP;
-  }
-  if (nq > 0) {
-    (void)hipMemcpyAsync(qa.p, q, sizeof(double) * 3 * nq, hipMemcpyHostToDevice, c->stream);
-    launch_aos_to_soa(qa.p, nq, qx.p, qy.p, qz.p, c->stream);
-    launch_knn(views[kind], qx.p, qy.p, qz.p, (int)nq, radius, k, idx.p, d2.p, cnt.p, c->stream);
-    (void)hipMemcpyAsync(out_idx, idx.p, sizeof(int) * nq * k, hipMemcpyDeviceToHost, c->stream);
-    (void)hipMemcpyAsync(out_d2, d2.p, sizeof(double) * nq * k, hipMemcpyDeviceToHost, c->stream);
-    (void)hipMemcpyAsync(out_cnt, cnt.p, sizeof(int) * nq, hipMemcpyDeviceToHost, c->stream);
-  }
-  e = hipStreamSynchronize(c->stream);   // (before the locals go)
-  if (e != hipSuccess) { c->last_error = hipGetErrorString(e); return TLOAM_E_HIP; }
-  return check_device_faults(c);
-}
-
-// ---- pre-built correspondence sets ------------------------------------------------------------------
-int tloam_set_correspondences(tloam_ctx* c, int res_type, size_t n, const double* p, const double* a, const double* b,
-                              const double* d, const double* w) {
-  if (!c || res_type < 0 || res_type >= TLOAM_NUM_RES || n > kMaxPoints) return TLOAM_E_INVALID;
-  if (n > 0 && (!p || !a || !w || (res_type == TLOAM_RES_LINE && !b) || (res_type == TLOAM_RES_PLANE && !d)))
-    return TLOAM_E_INVALID;
-  HIPC(c, hipSetDevice(c->device));
-  int rc = ensure_common(c);
-  if (rc != TLOAM_OK) return rc;
-  const int kind = res_type == TLOAM_RES_PLANE ? TLOAM_KIND_PLANAR : (res_type == TLOAM_RES_LINE ? TLOAM_KIND_EDGE : TLOAM_KIND_SPHERE);
-  if (!c->prebuilt) {
-    c->direct = false;   // a pre-built set is compact
-    HIPC(c, hipMemsetAsync(c->seg_n.p, 0, 8 * sizeof(int), c->stream));
-    for (int k = 0; k < kKinds; ++k) {
-      rc = reserve_seg(c, k, 1);
-      if (rc != TLOAM_OK) return rc;
-      c->kd[k].pre_n_full = 0;
-    }
-    c->prebuilt = true;
-    c->active = false;
-  }
-  size_t lo = 0, hi = n;
-  tloam_shard_range(n, c->rank, c->nranks, &lo, &hi);
-  const size_t m = hi - lo;
-  KindData& K = c->kd[kind];
-  K.pre_lo = lo;
-  K.pre_n_full = n;
-  rc = reserve_seg(c, kind, m);
-  if (rc != TLOAM_OK) return rc;
-  HIPC(c, c->misc.reserve(3 * std::max<size_t>(m, 1)));
-  const CorrSeg& s = c->cv.k[kind];
-  if (m > 0) {
-    HIPC(c, hipMemcpyAsync(c->misc.p, p + 3 * lo, sizeof(double) * 3 * m, hipMemcpyHostToDevice, c->stream));
-    launch_aos_to_soa(c->misc.p, m, s.px, s.py, s.pz, c->stream);
-    HIPC(c, hipMemcpyAsync(c->misc.p, a + 3 * lo, sizeof(double) * 3 * m, hipMemcpyHostToDevice, c->stream));
-    launch_aos_to_soa(c->misc.p, m, s.ax, s.ay, s.az, c->stream);
-    if (res_type == TLOAM_RES_LINE) {
-      HIPC(c, hipMemcpyAsync(c->misc.p, b + 3 * lo, sizeof(double) * 3 * m, hipMemcpyHostToDevice, c->stream));
-      launch_aos_to_soa(c->misc.p, m, s.bx, s.by, s.bz, c->stream);
-    }
-    if (res_type == TLOAM_RES_PLANE) HIPC(c, hipMemcpyAsync(s.d, d + lo, sizeof(double) * m, hipMemcpyHostToDevice, c->stream));
-    HIPC(c, hipMemcpyAsync(s.w, w + lo, sizeof(double) * m, hipMemcpyHostToDevice, c->stream));
-    HIPC(c, hipMemsetAsync(s.cost, 0, sizeof(double) * m, c->stream));
-    std::vector<int> ids(m);
-    for (size_t i = 0; i < m; ++i) ids[i] = (int)(lo + i);
-    HIPC(c, hipMemcpyAsync(s.idx, ids.data(), sizeof(int) * m, hipMemcpyHostToDevice, c->stream));
-    HIPC(c, hipStreamSynchronize(c->stream));
-  }
-  const int mi = (int)m;
-  HIPC(c, hipMemcpyAsync(c->seg_n.p + kind, &mi, sizeof(int), hipMemcpyHostToDevice, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));
-  size_t total_cap = 0;
-  int nn[kKinds];
-  for (int k = 0; k < kKinds; ++k) {
-    total_cap += c->kd[k].c_cap;
-    nn[k] = (k == kind) ? mi : 0;
-  }
-  {  // algorithmic bytes of one sweep over the whole (job-wide) pre-built set
-    int full[kKinds] = {(int)c->kd[0].pre_n_full, 0, (int)c->kd[2].pre_n_full, (int)c->kd[3].pre_n_full};
-    c->k3_alg_bytes = alg_bytes_of(full);
-    (void)nn;
-  }
-  {
-    int caps[kKinds];
-    for (int k = 0; k < kKinds; ++k) caps[k] = (int)c->kd[k].c_cap;
-    k3_plan(caps, c->device_cus, &c->k3_grid, &c->k3_single, &c->k3_wide);
-    (void)total_cap;
-  }
-  return reserve_partials(c);
-}
-
-int tloam_accumulate(tloam_ctx* c, const double se3[6], double H[36], double g[6], double* cost) {
-  if (!c || !se3) return TLOAM_E_INVALID;
-  HIPC(c, hipSetDevice(c->device));
-  if (!c->partials.p) return TLOAM_E_NOT_READY;
-  memcpy(c->h_small, se3, sizeof(double) * 6);
-  HIPC(c, hipMemcpyAsync(c->se3_dev.p, c->h_small, sizeof(double) * 6, hipMemcpyHostToDevice, c->stream));
-  launch_set_eval(c->state.p, c->se3_dev.p, c->stream);
-  int rc = launch_k3_timed(c, true);
-  if (rc != TLOAM_OK) return rc;
-  launch_reduce(c->partials.p, c->k3_grid, c->state.p, c->red48.p, c->stream);
-  rc = allreduce(c, c->red48.p, kReduceBuf);
-  if (rc != TLOAM_OK) return rc;
-  HIPC(c, hipMemcpyAsync(c->h_small + 8, c->red48.p, sizeof(double) * kReduceBuf, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));
-  rc = harvest_k3_events(c, 1);
-  if (rc != TLOAM_OK) return rc;
-  const double* t = c->h_small + 8;
-  if (H) {
-    int u = 0;
-    for (int i = 0; i < 6; ++i)
-      for (int j = i; j < 6; ++j) { H[i * 6 + j] = t[u]; H[j * 6 + i] = t[u]; ++u; }
-  }
-  if (g) for (int i = 0; i < 6; ++i) g[i] = t[21 + i];
-  if (cost) *cost = t[27];
-  return TLOAM_OK;
-}
-
-int tloam_get_normal_equations(tloam_ctx* c, double H[36], double g[6], double* cost) {
-  if (!c) return TLOAM_E_INVALID;
-  HIPC(c, hipSetDevice(c->device));
-  HIPC(c, hipStreamSynchronize(c->stream));
-  GnState* S = (GnState*)malloc(sizeof(GnState));
-  if (!S) return TLOAM_E_INVALID;
-  const hipError_t e = hipMemcpy(S, c->state.p, sizeof(GnState), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) {
-    if (H) memcpy(H, S->H, sizeof(double) * 36);
-    if (g) memcpy(g, S->g, sizeof(double) * 6);
-    if (cost) *cost = S->x_cost;
-  }
-  free(S);
-  HIPC(c, e);
-  return TLOAM_OK;
-}
-
-int tloam_get_costs(tloam_ctx* c, int res_type, size_t capacity, size_t* n, double* cost) {
-  if (!c || res_type < 0 || res_type >= TLOAM_NUM_RES || !n) return TLOAM_E_INVALID;
-  const int kind = res_type == TLOAM_RES_PLANE ? TLOAM_KIND_PLANAR : (res_type == TLOAM_RES_LINE ? TLOAM_KIND_EDGE : TLOAM_KIND_SPHERE);
-  return tloam_get_correspondences(c, kind, capacity, n, nullptr, nullptr, nullptr, nullptr, nullptr, cost);
-}
-
-int tloam_solve(tloam_ctx* c, double se3[6], tloam_stats* stats) {
-  if (!c || !se3) return TLOAM_E_INVALID;
-  HIPC(c, hipSetDevice(c->device));
-  if (!c->partials.p) return TLOAM_E_NOT_READY;
-  HIPC(c, hipMemsetAsync(c->state.p, 0, sizeof(GnState), c->stream));
-  memcpy(c->h_small, se3, sizeof(double) * 6);
-  HIPC(c, hipMemcpyAsync(c->state.p, c->h_small, sizeof(double) * 6, hipMemcpyHostToDevice, c->stream));
-  if (c->dbg_no_eval_reuse) {
-    static const int one = 1;
-    HIPC(c, hipMemcpyAsync(&c->state.p->no_eval_reuse, &one, sizeof(int), hipMemcpyHostToDevice, c->stream));
-  }
-  int rc = enqueue_solve(c, /*armed=*/false, c->dbg_max_sweeps > 0 ? c->dbg_max_sweeps : kSolveSweeps);
-  if (rc != TLOAM_OK) return rc;
-  HIPC(c, hipMemcpyAsync(c->h_state, c->state.p, sizeof(GnState), hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));
-  const GnState& S = *c->h_state;
-  rc = harvest_k3_events(c, S.gn_sweeps);
-  if (rc != TLOAM_OK) return rc;
-  memcpy(se3, S.x, sizeof(double) * 6);
-  if (stats) {
-    memset(stats, 0, sizeof(*stats));
-    stats->gn_evaluations = S.gn_evaluations;
-    stats->gn_sweeps = S.gn_sweeps;
-    stats->gn_iterations = S.gn_iterations;
-    stats->accepted_steps = S.accepted_steps;
-    stats->solver_cost = S.x_cost;
-    memcpy(stats->se3, S.x, sizeof(double) * 6);
-  }
-  return TLOAM_OK;
-}
-
-int tloam_time_accumulate(tloam_ctx* c, const double se3[6], int launches, double* mean_us) {
-  if (!c || !se3 || launches < 1 || !mean_us) return TLOAM_E_INVALID;
-  HIPC(c, hipSetDevice(c->device));
-  if (!c->partials.p) return TLOAM_E_NOT_READY;
-  memcpy(c->h_small, se3, sizeof(double) * 6);
-  HIPC(c, hipMemcpyAsync(c->se3_dev.p, c->h_small, sizeof(double) * 6, hipMemcpyHostToDevice, c->stream));
-  launch_set_eval(c->state.p, c->se3_dev.p, c->stream);
-  hipEvent_t e0, e1;
-  HIPC(c, hipEventCreate(&e0));
-  HIPC(c, hipEventCreate(&e1));
-  HIPC(c, hipEventRecord(e0, c->stream));
-  for (int i = 0; i < launches; ++i) launch_k3(c->cv, c->state.p, c->partials.p, c->k3_grid, c->k3_single, c->k3_wide, true, c->stream);
-  HIPC(c, hipEventRecord(e1, c->stream));
-  HIPC(c, hipEventSynchronize(e1));
-  float ms = 0.f;
-  HIPC(c, hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  *mean_us = (double)ms * 1e3 / launches;
-  return TLOAM_OK;
-}
-
-// Sharded contexts (collective call: every rank, same arguments): `launches` sweeps of this rank's block of the
-// current set at se3, each followed (with_exchange != 0) by the exchange of the 48 doubles exactly as a GN iteration
-// does it -- mailbox: posted by the sweep's last block, gathered by a one-wave kernel; RCCL / callback: all-reduce of
-// the folded buffer -- bracketed by one HIP event pair.  with_exchange == 0: the sweeps alone (the last block
-// still folds the rows).  The difference of the two is the latency the exchange adds to a GN iteration.
-int tloam_time_sharded_sweep(tloam_ctx* c, const double se3[6], int launches, int with_exchange, double* mean_us) {
-  if (!c || !se3 || launches < 1 || !mean_us) return TLOAM_E_INVALID;
-  HIPC(c, hipSetDevice(c->device));
-  if (!c->partials.p) return TLOAM_E_NOT_READY;
-  memcpy(c->h_small, se3, sizeof(double) * 6);
-  HIPC(c, hipMemcpyAsync(c->se3_dev.p, c->h_small, sizeof(double) * 6, hipMemcpyHostToDevice, c->stream));
-  launch_set_eval(c->state.p, c->se3_dev.p, c->stream);
-  K3Fuse fuse;
-  memset(&fuse, 0, sizeof(fuse));
-  fuse.ticket = c->k3_ticket.p;
-  fuse.out48 = c->red48.p;
-  const bool mbox = with_exchange && c->comm == COMM_MAILBOX && exchanging(c);
-  if (mbox) fuse.mb = c->mbox;
-  hipEvent_t e0, e1;
-  HIPC(c, hipEventCreate(&e0));
-  HIPC(c, hipEventCreate(&e1));
-  HIPC(c, hipEventRecord(e0, c->stream));
-  int rc = TLOAM_OK;
-  for (int i = 0; i < launches && rc == TLOAM_OK; ++i) {
-    launch_k3_fused(c->cv, c->state.p, c->partials.p, c->k3_grid, c->k3_single, c->k3_wide, true, fuse, c->stream);
-    if (mbox) launch_mbox_gather_only(c->red48.p, c->mbox, c->stream);
-    else if (with_exchange) rc = allreduce(c, c->red48.p, kReduceBuf);
-  }
-  HIPC(c, hipEventRecord(e1, c->stream));
-  HIPC(c, hipEventSynchronize(e1));
-  float ms = 0.f;
-  HIPC(c, hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  *mean_us = (double)ms * 1e3 / launches;
-  return rc;
-}
-
-// Timing helper for the bench (roofline_k1): `launches` back-to-back runs of the correspondence-search kernel
-// (K1 + K2: SearchHybrid + the four builders) over the source slots of the last scan_match -- same pose, same grids,
-// same query order; the kernel only rewrites the raw records and flags it wrote before -- bracketed by one HIP event
-// pair.  *queries = source points searched per launch.
-int tloam_time_build(tloam_ctx* c, int launches, double* mean_us, int64_t* queries) {
-  if (!c || launches < 1 || !mean_us) return TLOAM_E_INVALID;
-  HIPC(c, hipSetDevice(c->device));
-  if (c->active || !c->have_build || !c->qrec.p) return TLOAM_E_NOT_READY;
-  BuildParams bp;
-  GridView grids[kKinds];
-  outer_params(c, &bp, grids);
-  hipEvent_t e0, e1;
-  HIPC(c, hipEventCreate(&e0));
-  HIPC(c, hipEventCreate(&e1));
-  HIPC(c, hipEventRecord(e0, c->stream));
-  for (int i = 0; i < launches; ++i)
-    launch_build(c->sv, grids, bp, c->state.p, c->tile_of_slot.p, c->tile_cnt.p, c->tile_scan.p, c->tile_fill.p, c->qrec.p,
-                 c->scan_tmp.p, /*rebin=*/false, c->stream, nullptr);
-  HIPC(c, hipEventRecord(e1, c->stream));
-  HIPC(c, hipEventSynchronize(e1));
-  float ms = 0.f;
-  HIPC(c, hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  *mean_us = (double)ms * 1e3 / launches;
-  if (queries) *queries = (int64_t)c->sv.slot_off[kKinds];
-  return TLOAM_OK;
-}
-
-int tloam_k3_timer(tloam_ctx* c, int reset, double* total_us, int64_t* launches, double* algorithmic_bytes) {
-  if (!c) return TLOAM_E_INVALID;
-  if (total_us) *total_us = c->k3_total_us;
-  if (launches) *launches = c->k3_launches;
-  if (algorithmic_bytes) *algorithmic_bytes = c->k3_alg_bytes;
-  if (reset) {
-    c->k3_total_us = c->k3_all_us = 0.0;
-    c->k3_launches = c->k3_all_launches = 0;
-  }
-  c->k3_timing = true;  // first call arms the per-launch event pairs
-  return TLOAM_OK;
-}
-
-// test aid: the device SE(3) arithmetic of the minimiser step (k_debug_se3), n items of (x, delta) -> 26 doubles each
-int tloam_debug_se3(tloam_ctx* c, int n, const double* x, const double* delta, double* out26) {
-  if (!c || n < 1 || !x || !delta || !out26) return TLOAM_E_INVALID;
-  HIPC(c, hipSetDevice(c->device));
-  HIPC(c, c->misc.reserve((size_t)n * 38 + 8));
-  double* dx = c->misc.p; double* dd = dx + 6 * (size_t)n; double* dout = dd + 6 * (size_t)n;
-  HIPC(c, hipMemcpyAsync(dx, x, sizeof(double) * 6 * n, hipMemcpyHostToDevice, c->stream));
-  HIPC(c, hipMemcpyAsync(dd, delta, sizeof(double) * 6 * n, hipMemcpyHostToDevice, c->stream));
-  launch_debug_se3(dx, dd, n, dout, c->stream);
-  HIPC(c, hipMemcpyAsync(out26, dout, sizeof(double) * 26 * n, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));
-  return TLOAM_OK;
-}
-
-// debugging aid: raw copy of the device-resident minimiser state (layout: tl_common.hpp GnState)
-int tloam_debug_state(tloam_ctx* c, double* out, int n_doubles) {
-  if (!c || !out) return TLOAM_E_INVALID;
-  HIPC(c, hipSetDevice(c->device));
-  HIPC(c, hipStreamSynchronize(c->stream));
-  const size_t bytes = std::min(sizeof(GnState), sizeof(double) * (size_t)n_doubles);
-  HIPC(c, hipMemcpy(out, c->state.p, bytes, hipMemcpyDeviceToHost));
-  return (int)(sizeof(GnState) / sizeof(double));
-}
-
-int tloam_debug_partials(tloam_ctx* c, double* out, int n_doubles) {
-  if (!c || !out) return TLOAM_E_INVALID;
-  HIPC(c, hipSetDevice(c->device));
-  HIPC(c, hipStreamSynchronize(c->stream));
-  const size_t n = std::min(c->partials.cap, (size_t)std::max(n_doubles, 0));   // (rows, then whatever a profiling build put behind them)
-  HIPC(c, hipMemcpy(out, c->partials.p, n * sizeof(double), hipMemcpyDeviceToHost));
-  return c->k3_grid;
-}
-
-// every K3 launch since the last reset, no-op launches (after a tolerance exit) included: the population
-// `rocprofv3 --kernel-trace --stats` averages over
-int tloam_k3_timer_all(tloam_ctx* c, double* total_us, int64_t* launches) {
-  if (!c) return TLOAM_E_INVALID;
-  if (total_us) *total_us = c->k3_all_us;
-  if (launches) *launches = c->k3_all_launches;
-  return TLOAM_OK;
-}
-
-// The period of a GN iteration as the DEVICE clocks it (iter_span_note, tl_gn.hip): between the ends of two consecutive
-// minimiser steps of one Solve -- sweep, launch boundaries, fold, exchange, step.  The first call arms it.
-int tloam_gn_iter_timer(tloam_ctx* c, int reset, double* total_us, int64_t* iterations) {
-  if (!c) return TLOAM_E_INVALID;
-  HIPC(c, hipSetDevice(c->device));
-  unsigned long long h[4] = {0, 0, 0, 0};
-  if (c->iter_span.p) {
-    HIPC(c, hipMemcpyAsync(h, c->iter_span.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipStreamSynchronize(c->stream));
-    if (reset) HIPC(c, hipMemsetAsync(c->iter_span.p, 0, sizeof(h), c->stream));
-  }
-  if (total_us) *total_us = (double)h[1] * 0.01;   // 100 MHz wall clock
-  if (iterations) *iterations = (int64_t)h[2];
-  c->iter_timing = true;
-  return TLOAM_OK;
-}
-
-int tloam_k3_span(tloam_ctx* c, int reset, double* total_us, int64_t* launches) {
-  if (!c) return TLOAM_E_INVALID;
-  HIPC(c, hipSetDevice(c->device));
-  unsigned long long h[4] = {0, 0, 0, 0};
-  if (c->k3_span.p) {
-    HIPC(c, hipMemcpyAsync(h, c->k3_span.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipStreamSynchronize(c->stream));
-    if (reset) HIPC(c, hipMemsetAsync(c->k3_span.p, 0, sizeof(h), c->stream));
-  }
-  if (total_us) *total_us = (double)h[1] * 0.01;   // 100 MHz wall clock
-  if (launches) *launches = (int64_t)h[2];
-  return TLOAM_OK;
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // tl_ctx.hpp -- host-side context of the C ABI (include/tloam_hip.h), shared by the API translation units (tl_api.hip:
-// lifetime, tl_api_frames.hip: HBM residency + search grids, tl_api_match.hip: the scanMatching driver, tl_api_comm.hip: multi-GPU
+// lifetime, tl_api_frames.hip: HBM residency + search grids, tl_api_match.hip: the scanMatching driver, tl_api_sets.hip: its factor set outside a frame, tl_api_comm.hip: multi-GPU
 // exchange, tl_api_submap.hip: device-resident submap, tl_api_feature.hip: PCA features, tl_api_seg.hip: segmentation,
 // tl_api_odom.hip: the whole odometry frame, tl_api_map.hip: its global map and registered scan, tl_api_vmap.hip: its merged
 // voxel map, tl_api_deskew.hip: its deskew, tl_api_place.hip: place recognition, tl_api_cmap.hip: the closed map, tl_api_carve.hip: its carve,
@@ -812,6 +812,18 @@ void comm_rccl_info(const tloam_ctx* c, int32_t* count, int32_t* user_rank);   /
 int reserve_seg(tloam_ctx* c, int k, size_t n);        // compact correspondence segment of kind k for n factors
 int ensure_common(tloam_ctx* c);                       // the context's small fixed device buffers
 int reserve_query_sort(tloam_ctx* c, const tl::GridView grids[tl::kKinds]);   // the buffers of the frame's query sort, sized by the grids
+// ... and what tl_api_sets.hip shares with the frame:
+constexpr int kSolveSweeps = 5;                        // max_num_iterations 4 -> at most 1 + 4 evaluations per Solve
+tl::BuildParams build_params(const tloam_ctx* c);      // the search's radii, caps and active kinds from the configuration
+void outer_params(const tloam_ctx* c, tl::BuildParams* bp, tl::GridView grids[tl::kKinds]);   // ... and the frame's four grids
+void plan_sweeps(tloam_ctx* c);                        // k3_grid / k3_single / k3_wide from the segments' capacities
+int reserve_partials(tloam_ctx* c);                    // the sweeps' per-block rows for k3_grid
+double* direct_w_stream(const tloam_ctx* c, int k, int parity);   // weight stream `parity` of kind k's direct rows
+double alg_bytes_of(const int n[tl::kKinds]);          // algorithmic bytes of one sweep over n factors per kind
+int launch_k3_timed(tloam_ctx* c, bool force);         // one streaming sweep, sampled by the K3 timer when it is armed
+int harvest_k3_events(tloam_ctx* c, int working);      // ... its samples folded into the timers after one Solve of `working` sweeps
+int enqueue_solve(tloam_ctx* c, bool armed, int sweeps, const tl::WeightParams* wp = nullptr, const tl::SolvePrep* prep = nullptr,
+                  const tl::SolveFinish* finish = nullptr);   // one ceres::Solve on the current set, device resident
 // tl_api_frames.hip
 void exchange_clouds(tloam_ctx* c, FrameClouds& F);    // the registered clouds <-> a FrameClouds (pointers and counts only)
 int check_device_faults(tloam_ctx* c);
