@@ -311,3 +311,72 @@ def test_sizes_of_consecutive_updates_that_xor_alike(hip_module, seed, trial):
                 a = H.get_target(k)
                 assert a.shape == want[f][k].shape and np.array_equal(a, want[f][k], equal_nan=True), (rep, f, k, a.shape, want[f][k].shape)
         H.close()
+
+
+def test_ring_longer_than_one_front_launch(hip_module):
+    """A planar ring of more than eight frames does not fit the one-launch front (k_submap_front takes eight): every buffered
+    frame is transformed by a launch of its own, the edge / ground clouds are assembled by k_assemble, the crop + voxel job runs
+    in full (k_vox_min2 first) and the frame's clouds are uploaded by one copy instead of being read in the pinned staging.
+    planar_frame_size 9 and 11 take that path once their rings hold nine frames; 8 is the last size the fused front takes, so
+    the boundary has both sides.  The oracle ends with 459 = 9 * 51 and 561 = 11 * 51 planar points: the rings are full."""
+    for size, full in ((8, 8 * 51), (9, 9 * 51), (11, 11 * 51)):
+        cfg = dict(planar_frame_size=size, sphere_frame_size=2, edge_crop_box_length=30.0, ground_crop_box_length=24.0)
+        A = _HipSubmap(hip_module, cfg)
+        B = ob.OracleSubmap(ob.make_submap_config(**cfg))
+        for f in range(13):
+            cl = ss.frame_clouds(3, f, n=(51, 21, 101, 103))
+            if f == 0:
+                A.init(*cl); assert B.init(*cl) == 0
+            else:
+                T = ss.frame_pose(f, step=1.0, yaw_rate=0.02)
+                A.update(T, *cl); assert B.update(T, *cl) == 0
+            for k in range(4):
+                a, b = A.get(k), B.get(k)
+                assert a.shape == b.shape, (size, f, k, a.shape, b.shape)
+                assert np.array_equal(a, b), (size, f, k)
+        assert len(B.get(0)) == full, (size, len(B.get(0)))
+        A.H.close()
+
+
+def _column_edge_cloud():
+    """One anchor point at the origin (it fixes voxel_min_bound at -0.5) and clusters of 31, 32, 33, 64 and 65 points at
+    (3 v + 3, 0, 0) + U[0, 0.3)^3, permuted and rounded through float32: with 1 m voxels every cluster is one voxel."""
+    rng = np.random.default_rng(32)
+    parts = [np.zeros((1, 3))]
+    for v, m in enumerate((31, 32, 33, 64, 65)):
+        parts.append(np.array([3.0 * v + 3.0, 0.0, 0.0]) + rng.uniform(0.0, 0.3, (m, 3)))
+    xyz = np.concatenate(parts)[rng.permutation(226)]
+    return np.ascontiguousarray(xyz.astype(np.float32).astype(np.float64))
+
+
+def test_voxels_at_the_lds_column_edge(hip_module):
+    """A voxel's leader orders up to 32 members in its LDS column; the 33rd sends the voxel to the heap sort in global scratch.
+    Voxels of exactly 1, 31, 32, 33, 64 and 65 members, byte for byte against the oracle: through tloam_voxel_down_sample (a
+    one-segment job), and through a submap update whose two-segment job carries the same voxels -- segment 0 is the old edge
+    submap, which is the cloud as given (1, 31, 32, 33, 64, 65 members), segment 1 the old ground submap (the cloud's six voxel
+    means) followed by the cloud again (2, 32, 33, 34, 65, 66 members).  The voxel sizes are 1 m throughout so that the clusters
+    stay one voxel each in every job."""
+    xyz = _column_edge_cloud()
+    want = ob.pc_voxel_down_sample(xyz, 1.0)
+    idx = np.floor((xyz - (xyz.min(axis=0) - 0.5)) / 1.0).astype(np.int64)
+    _, members = np.unique(idx, axis=0, return_counts=True)
+    assert sorted(members.tolist()) == [1, 31, 32, 33, 64, 65] and len(want) == 6
+    H = hip_module.HipRegistration()
+    got = H.voxel_down_sample(xyz, 1.0)
+    assert got.shape == want.shape and got.tobytes() == want.tobytes()
+    H.close()
+    cfg = dict(edge_crop_box_length=100.0, ground_crop_box_length=100.0, edge_down_sample_submap=1.0,
+               ground_down_sample_submap=1.0, ground_down_sample=1.0)
+    A = _HipSubmap(hip_module, cfg)
+    B = ob.OracleSubmap(ob.make_submap_config(**cfg))
+    planar, sphere = ss.frame_clouds(3, 0, n=(51, 21, 1, 1))[:2]
+    A.init(planar, sphere, xyz, xyz); assert B.init(planar, sphere, xyz, xyz) == 0
+    assert B.get(1).tobytes() == want.tobytes()          # the first frame's ground job is the one-segment job above
+    for k in range(4):
+        assert A.get(k).tobytes() == B.get(k).tobytes(), k
+    A.update(np.eye(4), planar, sphere, np.zeros((0, 3)), xyz); assert B.update(np.eye(4), planar, sphere, np.zeros((0, 3)), xyz) == 0
+    assert len(B.get(2)) == 6 and len(B.get(1)) == 6     # six voxels per segment: the clusters stayed whole
+    for k in range(4):
+        a, b = A.get(k), B.get(k)
+        assert a.shape == b.shape and a.tobytes() == b.tobytes(), k
+    A.H.close()

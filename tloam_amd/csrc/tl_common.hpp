@@ -435,13 +435,14 @@ struct VoxelJob {
   double voxel[2];           // voxel sizes
   unsigned long long mask;   // hash-table capacity - 1 (power of two >= 2 n)
 };
+constexpr int kVoxLocal = 32;   // members of a voxel its leader orders in LDS (k_vox_emit, k_map_emit); a fuller voxel goes another way
 struct VoxelWork {           // scratch, sized by the caller (see voxel_table_size)
-  double* min_partial;       // [256][6]
+  double* min_partial;       // [256][6], or [submap_front_rows][6] behind k_submap_front
   double* vmin;              // [2][3] voxel_min_bound per segment
-  unsigned long long *keys, *cnt, *off;   // [cap + 1]
-  int *slot_of_pt, *urank, *members, *sorted;  // [n]
-  unsigned long long *leader, *leader_scan;    // [n + 1]
-  unsigned long long* scan_tmp;
+  unsigned long long *keys, *cnt;   // [cap + 1]: the voxel keys, the head of every slot's member list
+  int *slot_of_pt, *urank, *members;   // [n]: hash slot of a point (-1: none), the next member of its list, the heap sort's scratch
+  unsigned long long* leader;          // [emit blocks + 1]: look-back words of k_vox_emit
+  unsigned long long* leader_scan;     // [2] control words: blocks of k_vox_emit started so far, cursor of `members`
   int* overflow;             // set when a voxel index leaves [0, 2^21)
   unsigned long long* n_out; // [2] receives the sizes of the down-sampled clouds
   // != nullptr: the sizes, the overflow flag and host_seq are also stored into one 64-byte segment of pinned host memory
@@ -457,8 +458,6 @@ struct VoxelWork {           // scratch, sized by the caller (see voxel_table_si
 };
 size_t voxel_table_size(size_t n);
 int vox_emit_resident_blocks(int device_cus);   // blocks of k_vox_emit the device holds at once, with a margin (tl_submap.hip)
-void launch_transform_to_soa(const double* aos, size_t n, const double M[16], double* ox, double* oy, double* oz,
-                             hipStream_t s);
 void launch_transform_to_soa2(const double* aos, size_t n, const double M[16], double* ax, double* ay, double* az,
                               double* bx, double* by, double* bz, hipStream_t s);
 struct AssembleArgs {          // per segment: old submap cloud (SoA) followed by the new scan cloud (AoS, to transform)
@@ -468,11 +467,7 @@ struct AssembleArgs {          // per segment: old submap cloud (SoA) followed b
   double M[16];                // column-major pose
 };
 void launch_assemble(const AssembleArgs& A, double* wx, double* wy, double* wz, hipStream_t s);
-int transform_ring_max();  // frames one launch_transform_ring call takes
-void launch_transform_ring(int count, const double* const aos[], const size_t n[], const double* const poses[],
-                           double* ax, double* ay, double* az, double* bx, double* by, double* bz, hipStream_t s);
-void launch_copy3(const double* ax, const double* ay, const double* az, size_t n, double* ox, double* oy, double* oz,
-                  hipStream_t s);
+int submap_front_ring_max();   // planar ring frames one launch_submap_front call takes
 void launch_soa_to_aos(const double* x, const double* y, const double* z, size_t n, double* aos, hipStream_t s);
 void launch_blit_doubles(const double* src_host_view, double* dst, size_t n, hipStream_t s);   // pinned host -> device by a kernel
 void launch_crop_voxel(const VoxelJob& J, const VoxelWork& W, hipStream_t s, bool front_done = false);
@@ -517,7 +512,7 @@ void launch_odom_counts(const OdomCountArgs& A, hipStream_t s);
 
 // ---- the global map of the odometry frame (tl_map.hip) ------------------------
 // VoxelDownSample of one transformed scan whose voxels can hold hundreds of returns (1 m cells on a raw scan): the leader of a voxel
-// (its smallest member) comes from an atomicMin, not from a walk of the member list; voxels of up to kMapVoxLocal members are
+// (its smallest member) comes from an atomicMin, not from a walk of the member list; voxels of up to kVoxLocal members are
 // averaged by their leader as in k_vox_emit, larger ones by a workgroup each, their members sorted by index in LDS
 // Open3D TransformPoints: new = T * (x, y, z, 1), rows accumulated left to right; point = new.head<3>() / new(3).  Units that
 // call it are compiled with -ffp-contract=off (the oracle's pc_transform rounds so)
@@ -551,7 +546,7 @@ struct MapVoxWork {
   int* ctl;                   // [0] overflow, [1] ticket of k_map_front, [2] start tickets of k_map_emit, [3] big voxels, [4] their members
   int4* bigq;                 // [big_max]: (slot, output position, first member in `members`, members)
   int* bigfill;               // [big_max]
-  int big_max;                // n / (kMapVoxLocal + 1) + 1
+  int big_max;                // n / (kVoxLocal + 1) + 1
   double *ox, *oy, *oz;       // the means: the map at its current end
   unsigned long long* n_out;  // [1] voxels
   unsigned long long* host_seg;   // pinned: [0] voxels, [2] overflow, [7] check word (as VoxelWork::host_seg)
@@ -559,8 +554,7 @@ struct MapVoxWork {
   int use_ticket;
   unsigned* fault;
 };
-constexpr int kMapVoxLocal = 32;
-inline int map_big_max(size_t n) { return (int)(n / (kMapVoxLocal + 1) + 1); }
+inline int map_big_max(size_t n) { return (int)(n / (kVoxLocal + 1) + 1); }
 // front | insert | emit | scatter | big: no host synchronisation; the count reaches the host segment with k_map_emit
 void launch_map_voxel(const MapFrontArgs& A, const MapVoxWork& W, hipStream_t s);
 int map_emit_resident_blocks(int device_cus);

@@ -212,8 +212,8 @@ struct SubmapState {
   tloam_submap_config cfg;
   std::vector<std::unique_ptr<RingFrame>> planar_ring, sphere_ring;  // oldest first (std::deque in the reference)
   DBuf<double> in_aos, wx, wy, wz, min_partial, vmin;
-  DBuf<unsigned long long> keys, cnt, off, leader, leader_scan, scan_tmp, counts;
-  DBuf<int> slot_of_pt, urank, members, sorted, overflow;
+  DBuf<unsigned long long> keys, cnt, leader, leader_scan, counts;
+  DBuf<int> slot_of_pt, urank, members, overflow;
 };
 
 // scratch of the PCA feature path (grow-only, kept across calls)

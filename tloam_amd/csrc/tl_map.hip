@@ -3,12 +3,12 @@
 // the frame already holds in HBM.
 //
 // Launches (a later frame with mapping on, after the scan match; no host synchronisation in between):
-//   k_map_front       grid x 256   the raw scan transformed (Open3D TransformPoints, the expression of k_transform_to_soa) into
+//   k_map_front       grid x 256   the raw scan transformed (Open3D TransformPoints: map_transform_point) into
 //                                  SoA scratch; the same launch empties the hash table and finishes the min bound of the
 //                                  transformed cloud (block partials, the last block by ticket) -- k_submap_front's work for one segment
 //   k_map_insert      grid x 256   voxel -> hash slot; the slot's member list, count and smallest member (atomics)
 //   k_map_emit        grid x 256   leaders in first-occurrence order (the look-back scan of tl_voxel.hpp); a voxel of up to
-//                                  kMapVoxLocal members averaged by its leader, a larger one booked; the count to pinned memory
+//                                  kVoxLocal members averaged by its leader, a larger one booked; the count to pinned memory
 //   k_map_scatter     grid x 256   the members of the booked voxels into one piece each
 //   k_map_big         <= 1024 x 256  one workgroup per booked voxel: members ordered by index, summed in that order
 //   k_transform_aos   grid x 256   the registered scan of a frame whose map stage did not run, AoS -> AoS
@@ -30,8 +30,6 @@ __device__ __forceinline__ bool in_box(const MapVoxWork& W, double x, double y, 
 }
 
 __global__ __launch_bounds__(256) void k_map_front(MapFrontArgs A, MapVoxWork W, int emit_blocks) {
-  __shared__ double sm[3][256];
-  __shared__ int s_last;
   const int tid = threadIdx.x;
   const size_t i = (size_t)blockIdx.x * 256 + tid, stride = (size_t)gridDim.x * 256;
   if (blockIdx.x == 0 && tid == 0) { W.ctl[0] = 0; W.ctl[2] = 0; W.ctl[3] = 0; W.ctl[4] = 0; }
@@ -50,36 +48,9 @@ __global__ __launch_bounds__(256) void k_map_front(MapFrontArgs A, MapVoxWork W,
     W.x[i] = x; W.y[i] = y; W.z[i] = z;
     if (in_box(W, x, y, z)) { m[0] = x; m[1] = y; m[2] = z; }
   }
-#pragma unroll
-  for (int a = 0; a < 3; ++a) sm[a][tid] = m[a];
-  __syncthreads();
-  for (int st = 128; st > 0; st >>= 1) {
-    if (tid < st)
-#pragma unroll
-      for (int a = 0; a < 3; ++a) sm[a][tid] = fmin(sm[a][tid], sm[a][tid + st]);
-    __syncthreads();
-  }
-  // the block's row is handed over with device-scope stores, their completion waited for, then the ticket (as k_vox_min2)
-  if (tid < 3) __hip_atomic_store(W.min_partial + (size_t)blockIdx.x * 3 + tid, sm[tid][0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0)
-    s_last = (__hip_atomic_fetch_add(W.ctl + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1) ? 1 : 0;
-  __syncthreads();
-  if (!s_last) return;
-  // voxel_min_bound = GetMinBound() - voxel_size * 0.5 (PointCloud2.cpp:366); no finite point: (0, 0, 0).  One wave per axis:
-  // min is exact in any order
-  const int wave = tid >> 6, lane = tid & 63;
-  if (wave < 3) {
-    double v = __builtin_inf();
-    for (int b = lane; b < (int)gridDim.x; b += 64)
-      v = fmin(v, __hip_atomic_load(W.min_partial + (size_t)b * 3 + wave, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, 64));
-    if (!(v < __builtin_inf())) v = 0.0;
-    if (lane == 0) W.vmin[wave] = v - W.voxel * 0.5;
-  }
-  if (tid == 0) __hip_atomic_store(W.ctl + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-armed
+  // voxel_min_bound of the transformed cloud, finished by the last block (&W.voxel: a one-element array -- with C == 3 columns
+  // voxel_min_bound only ever reads voxel[0])
+  voxel_min_bound<3, 3>(m, 0, W.min_partial, (int)blockIdx.x, (int)gridDim.x, W.ctl + 1, &W.voxel, W.vmin);
 }
 
 // the voxel of every point in the box -> hash slot; the point joins the slot's member list, count and smallest index
@@ -88,16 +59,12 @@ __global__ __launch_bounds__(256) void k_map_insert(MapVoxWork W) {
   if (i >= W.n) return;
   const double x = W.x[i], y = W.y[i], z = W.z[i];
   if (!in_box(W, x, y, z)) { W.slot_of_pt[i] = -1; return; }
-  // ref_coord = (p - voxel_min_bound) / voxel_size; index = int(floor(ref_coord))   (PointCloud2.cpp:380-383)
-  const long long ix = (long long)floor((x - W.vmin[0]) / W.voxel);
-  const long long iy = (long long)floor((y - W.vmin[1]) / W.voxel);
-  const long long iz = (long long)floor((z - W.vmin[2]) / W.voxel);
-  if (ix < 0 || iy < 0 || iz < 0 || ix >= (1ll << 21) || iy >= (1ll << 21) || iz >= (1ll << 21)) {
-    W.ctl[0] = 1;   // "[VoxelDownSample] voxel_size is too small." (:370-372)
+  unsigned long long key = 0ull;
+  if (!voxel_key(x, y, z, W.vmin, W.voxel, &key)) {
+    W.ctl[0] = 1;   // "[VoxelDownSample] voxel_size is too small." (PointCloud2.cpp:370-372)
     W.slot_of_pt[i] = -1;
     return;
   }
-  const unsigned long long key = (unsigned long long)ix | ((unsigned long long)iy << 21) | ((unsigned long long)iz << 42);
   const unsigned long long h = table_enter(W.keys, W.mask, key);
   W.slot_of_pt[i] = (int)h;
   W.next[i] = atomicExch(&W.head[h], (int)i);
@@ -105,12 +72,12 @@ __global__ __launch_bounds__(256) void k_map_insert(MapVoxWork W) {
   atomicAdd(&W.count[h], 1);
 }
 
-// per point: a leader of a voxel of up to kMapVoxLocal members orders them by index in LDS (the order AddPoint is called in,
+// per point: a leader of a voxel of up to kVoxLocal members orders them by index in LDS (the order AddPoint is called in,
 // :379-385), sums and averages; its output position -- the leaders in front of it, i.e. first-occurrence order -- comes from a
 // single-pass scan over the blocks inside the launch (tl_voxel.hpp).  The leader of a larger voxel books the voxel for
 // k_map_big: a number, the output position, a piece of `members`
 __global__ __launch_bounds__(256) void k_map_emit(MapVoxWork W, int nblocks) {
-  __shared__ int s_mem[kMapVoxLocal * 256];   // s_mem[k * 256 + t]: member k of thread t's voxel (conflict-free columns)
+  __shared__ int s_mem[kVoxLocal * 256];   // s_mem[k * 256 + t]: member k of thread t's voxel (conflict-free columns)
   __shared__ unsigned long long s_wave[4];
   __shared__ unsigned long long s_prefix;
   __shared__ int s_bid;
@@ -123,20 +90,11 @@ __global__ __launch_bounds__(256) void k_map_emit(MapVoxWork W, int nblocks) {
   const bool leader = h >= 0 && W.first[h] == (int)i;
   const int m = leader ? W.count[h] : 0;
   double sx = 0.0, sy = 0.0, sz = 0.0;
-  if (leader && m <= kMapVoxLocal) {
+  if (leader && m <= kVoxLocal) {
     int k = 0;
-    for (int j = W.head[h]; j >= 0 && k < kMapVoxLocal; j = W.next[j]) s_mem[(k++) * 256 + tid] = j;
-    for (int a = 1; a < k; ++a) {   // insertion sort of this thread's column
-      const int key = s_mem[a * 256 + tid];
-      int b = a - 1;
-      while (b >= 0 && s_mem[b * 256 + tid] > key) { s_mem[(b + 1) * 256 + tid] = s_mem[b * 256 + tid]; --b; }
-      s_mem[(b + 1) * 256 + tid] = key;
-    }
+    for (int j = W.head[h]; j >= 0 && k < kVoxLocal; j = W.next[j]) s_mem[(k++) * 256 + tid] = j;
     // AccumulatedPoint: point_ += p in index order, GetAveragePoint = point_ / double(num) (:253-272)
-    for (int q = 0; q < k; ++q) {
-      const int j = s_mem[q * 256 + tid];
-      sx += W.x[j]; sy += W.y[j]; sz += W.z[j];
-    }
+    leader_local_sum(s_mem, k, W.x, W.y, W.z, &sx, &sy, &sz);
     const double dn = (double)m;
     sx /= dn; sy /= dn; sz /= dn;
   }
@@ -147,10 +105,10 @@ __global__ __launch_bounds__(256) void k_map_emit(MapVoxWork W, int nblocks) {
   __syncthreads();
   if (leader) {
     const unsigned long long p = s_prefix + before;
-    if (m <= kMapVoxLocal) {
+    if (m <= kVoxLocal) {
       W.ox[p] = sx; W.oy[p] = sy; W.oz[p] = sz;
     } else {
-      const int q = atomicAdd(&W.ctl[3], 1);   // (< big_max: a big voxel has more than kMapVoxLocal members)
+      const int q = atomicAdd(&W.ctl[3], 1);   // (< big_max: a big voxel has more than kVoxLocal members)
       const int off = atomicAdd(&W.ctl[4], m);
       W.bigq[q] = make_int4(h, (int)p, off, m);
       W.bigslot[h] = q;
@@ -169,7 +127,7 @@ __global__ __launch_bounds__(256) void k_map_scatter(MapVoxWork W) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= W.n) return;
   const int h = W.slot_of_pt[i];
-  if (h < 0 || W.count[h] <= kMapVoxLocal) return;
+  if (h < 0 || W.count[h] <= kVoxLocal) return;
   const int q = W.bigslot[h];
   const int4 b = W.bigq[q];
   W.members[b.z + atomicAdd(&W.bigfill[q], 1)] = (int)i;
@@ -261,22 +219,14 @@ void launch_map_voxel(const MapFrontArgs& A, const MapVoxWork& W, hipStream_t s)
   hipLaunchKernelGGL(k_map_front, dim3(blocks_of(std::max<size_t>(n, 1))), dim3(256), 0, s, A, W, emit_blocks);
   if (n > 0) hipLaunchKernelGGL(k_map_insert, dim3(blocks_of(n)), dim3(256), 0, s, W);
   hipLaunchKernelGGL(k_map_emit, dim3(emit_blocks), dim3(256), 0, s, W, emit_blocks);
-  if (n <= (size_t)kMapVoxLocal) return;   // (no voxel can be big)
+  if (n <= (size_t)kVoxLocal) return;   // (no voxel can be big)
   hipLaunchKernelGGL(k_map_scatter, dim3(blocks_of(n)), dim3(256), 0, s, W);
   hipLaunchKernelGGL(k_map_big, dim3((unsigned)std::min(W.big_max, 1024)), dim3(256), 0, s, W);
 }
 
-int map_emit_resident_blocks(int device_cus) {   // vox_emit_resident_blocks (tl_submap.hip) for k_map_emit
+int map_emit_resident_blocks(int device_cus) {
   static std::atomic<int> per_cu_cache{-1};
-  int per_cu = per_cu_cache.load(std::memory_order_relaxed);
-  if (per_cu < 0) {
-    int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_map_emit, 256, 0) != hipSuccess || occ < 1) { (void)hipGetLastError(); occ = 1; }
-    per_cu = occ;
-    per_cu_cache.store(occ, std::memory_order_relaxed);
-  }
-  const long long all = (long long)device_cus * per_cu;
-  return (int)(all - all / 16);
+  return emit_resident_blocks(k_map_emit, per_cu_cache, device_cus);
 }
 
 void launch_transform_aos(const double* aos, size_t n, const double M[16], double* out, hipStream_t s) {

@@ -16,7 +16,8 @@
 // index are measure-zero after averaging).
 //
 // Voxel membership uses an open-addressing hash table keyed by the packed voxel coordinates
-// (ix | iy << 21 | iz << 42); per-voxel member lists are ordered by index with a rank-by-counting pass so the
+// (ix | iy << 21 | iz << 42, tl_voxel.hpp voxel_key); every point is pushed on its voxel's member list, the voxel's leader (its
+// smallest member) orders the members by index -- in LDS, a crowded voxel by a heap sort in global scratch -- so the
 // floating-point accumulation order is the reference's (ascending index).  Compiled with -ffp-contract=off.
 #include <atomic>
 #include <algorithm>
@@ -27,22 +28,7 @@
 namespace tl {
 
 namespace {
-struct Mat16 { double m[16]; };  // column-major 4x4
-
-// Open3D TransformPoints: new = T * (x, y, z, 1); point = new.head<3>() / new(3).  Each row is accumulated
-// left to right (assumed upstream behaviour: Open3D is not under /root/reference).
-__global__ void k_transform_to_soa(const double* __restrict__ aos, size_t n, Mat16 M, double* __restrict__ ox,
-                                   double* __restrict__ oy, double* __restrict__ oz) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const double x = aos[3 * i], y = aos[3 * i + 1], z = aos[3 * i + 2];
-  double r[4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a) r[a] = ((M.m[a] * x + M.m[4 + a] * y) + M.m[8 + a] * z) + M.m[12 + a] * 1.0;
-  ox[i] = r[0] / r[3];
-  oy[i] = r[1] / r[3];
-  oz[i] = r[2] / r[3];
-}
+struct Mat16 { double m[16]; };  // column-major 4x4, by value in a kernel's arguments
 
 // the same transformed cloud written to TWO outputs (the sphere submap is rebuilt from the planar buffer too)
 __global__ void k_transform_to_soa2(const double* __restrict__ aos, size_t n, Mat16 M, double* __restrict__ ax,
@@ -50,16 +36,13 @@ __global__ void k_transform_to_soa2(const double* __restrict__ aos, size_t n, Ma
                                     double* __restrict__ by, double* __restrict__ bz) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const double x = aos[3 * i], y = aos[3 * i + 1], z = aos[3 * i + 2];
-  double r[4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a) r[a] = ((M.m[a] * x + M.m[4 + a] * y) + M.m[8 + a] * z) + M.m[12 + a] * 1.0;
-  const double px = r[0] / r[3], py = r[1] / r[3], pz = r[2] / r[3];
+  double px, py, pz;
+  map_transform_point(M.m, aos[3 * i], aos[3 * i + 1], aos[3 * i + 2], &px, &py, &pz);
   ax[i] = px; ay[i] = py; az[i] = pz;
   bx[i] = px; by[i] = py; bz[i] = pz;
 }
 
-// the frames of the planar ring buffer (front_end.cpp:220-243) in ONE launch: blockIdx.y = frame
+// the frames of the planar ring buffer (front_end.cpp:220-243) in ONE launch (k_submap_front): blockIdx.y = frame
 constexpr int kRingMax = 8;
 struct RingArgs {
   const double* aos[kRingMax];
@@ -68,30 +51,6 @@ struct RingArgs {
   int copy_frame;      // k_submap_front: the frame whose cloud is read from pinned HOST memory and kept in ...
   double* copy_dst;    // ... this device buffer for the updates to come (-1 / null: every frame is on the device already)
 };
-__global__ void k_transform_ring(RingArgs R, double* __restrict__ ax, double* __restrict__ ay, double* __restrict__ az,
-                                 double* __restrict__ bx, double* __restrict__ by, double* __restrict__ bz) {
-  const int f = blockIdx.y;
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= R.n[f]) return;
-  const double* __restrict__ aos = R.aos[f];
-  const Mat16& M = R.M[f];
-  const double x = aos[3 * i], y = aos[3 * i + 1], z = aos[3 * i + 2];
-  double r[4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a) r[a] = ((M.m[a] * x + M.m[4 + a] * y) + M.m[8 + a] * z) + M.m[12 + a] * 1.0;
-  const double px = r[0] / r[3], py = r[1] / r[3], pz = r[2] / r[3];
-  const size_t o = R.off[f] + i;
-  ax[o] = px; ay[o] = py; az[o] = pz;
-  bx[o] = px; by[o] = py; bz[o] = pz;
-}
-
-__global__ void k_copy3(const double* __restrict__ ax, const double* __restrict__ ay, const double* __restrict__ az,
-                        size_t n, double* __restrict__ ox, double* __restrict__ oy, double* __restrict__ oz) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  ox[i] = ax[i]; oy[i] = ay[i]; oz[i] = az[i];
-}
-
 __global__ void k_soa_to_aos(const double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ z,
                              size_t n, double* __restrict__ aos) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -118,15 +77,13 @@ __device__ __forceinline__ bool in_box(const VoxelJob& J, int seg, double x, dou
 // Same voxels, same member order, same sums, same output order as the eleven-launch form: tests/test_gpu_submap.py compares with
 // the oracle bit for bit.
 constexpr unsigned long long kNoHead = ~0ull;
-constexpr int kVoxLocal = 32;           // members a leader orders in LDS; a fuller voxel is ordered in global scratch (heap sort)
 constexpr unsigned long long kCntMask = (1ull << 30) - 1ull;   // look-back word: [0..29] leaders of segment 0, [32..61] of segment 1, [62..63] status
 // VoxelWork::leader_scan, the control words of a job: [0] blocks of k_vox_emit started so far, [1] cursor of the sort scratch
 // VoxelWork::overflow: [0] voxel index out of range, [1] ticket of k_vox_min2 (zero between launches)
 // VoxelWork::cnt[h] = head of slot h's member list, VoxelWork::urank[i] = next member after point i (-1: none)
 // VoxelWork::leader[b] = look-back word of block b of k_vox_emit
+// A leader orders up to kVoxLocal members in LDS; a fuller voxel is ordered in global scratch (heap sort)
 __global__ __launch_bounds__(256) void k_vox_min2(VoxelJob J, VoxelWork W, int emit_blocks) {
-  __shared__ double sm[6][256];
-  __shared__ int s_last;
   if (blockIdx.x == 0 && threadIdx.x == 0) { W.overflow[0] = 0; W.leader_scan[0] = 0ull; W.leader_scan[1] = 0ull; }
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i <= J.mask; i += (size_t)gridDim.x * 256) {
     W.keys[i] = kFree;
@@ -144,37 +101,8 @@ __global__ __launch_bounds__(256) void k_vox_min2(VoxelJob J, VoxelWork W, int e
       else { m[3] = fmin(m[3], x); m[4] = fmin(m[4], y); m[5] = fmin(m[5], z); }
     }
   }
-#pragma unroll
-  for (int a = 0; a < 6; ++a) sm[a][threadIdx.x] = m[a];
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s)
-#pragma unroll
-      for (int a = 0; a < 6; ++a) sm[a][threadIdx.x] = fmin(sm[a][threadIdx.x], sm[a][threadIdx.x + s]);
-    __syncthreads();
-  }
-  // the row is handed over with device-scope stores, their completion is waited for, then the ticket (k3_take_ticket, tl_gn.hip)
-  if (threadIdx.x < 6)
-    __hip_atomic_store(W.min_partial + blockIdx.x * 6 + threadIdx.x, sm[threadIdx.x][0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0)
-    s_last = (__hip_atomic_fetch_add(W.overflow + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1) ? 1 : 0;
-  __syncthreads();
-  if (!s_last) return;
-  // voxel_min_bound = GetMinBound() - voxel_size * 0.5 (:366); an empty cloud has min bound (0, 0, 0).  One wave per
-  // (segment, axis): min is exact in any order
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  for (int a = wave; a < 6; a += 4) {
-    double v = __builtin_inf();
-    for (int b = lane; b < (int)gridDim.x; b += 64)
-      v = fmin(v, __hip_atomic_load(W.min_partial + b * 6 + a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, 64));
-    if (!(v < __builtin_inf())) v = 0.0;
-    if (lane == 0) W.vmin[a] = v - J.voxel[a < 3 ? 0 : 1] * 0.5;
-  }
-  if (threadIdx.x == 0) __hip_atomic_store(W.overflow + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-armed
+  // voxel_min_bound of both segments, finished by the last block
+  voxel_min_bound<6, 6>(m, 0, W.min_partial, (int)blockIdx.x, (int)gridDim.x, W.overflow + 1, J.voxel, W.vmin);
 }
 
 __global__ __launch_bounds__(256) void k_vox_insert2(VoxelJob J, VoxelWork W) {
@@ -183,20 +111,15 @@ __global__ __launch_bounds__(256) void k_vox_insert2(VoxelJob J, VoxelWork W) {
   const double x = J.x[i], y = J.y[i], z = J.z[i];
   const int seg = i >= J.n0 ? 1 : 0;
   if (!in_box(J, seg, x, y, z)) { W.slot_of_pt[i] = -1; return; }
-  // ref_coord = (p - voxel_min_bound) / voxel_size; index = int(floor(ref_coord))   (:380-383)
-  const double voxel = J.voxel[seg];
-  const long long ix = (long long)floor((x - W.vmin[3 * seg + 0]) / voxel);
-  const long long iy = (long long)floor((y - W.vmin[3 * seg + 1]) / voxel);
-  const long long iz = (long long)floor((z - W.vmin[3 * seg + 2]) / voxel);
-  if (ix < 0 || iy < 0 || iz < 0 || ix >= (1ll << 21) || iy >= (1ll << 21) || iz >= (1ll << 21)) {
+  // 3 x 21 bits of voxel coordinates, bit 63 = segment.  The all-ones key (segment 1, all three indices 2^21 - 1)
+  // is the empty marker: reported like an index out of range
+  unsigned long long key = 0ull;
+  if (!voxel_key(x, y, z, W.vmin + 3 * seg, J.voxel[seg], &key)) {
     W.overflow[0] = 1;  // "[VoxelDownSample] voxel_size is too small." (:370-372)
     W.slot_of_pt[i] = -1;
     return;
   }
-  // 3 x 21 bits of voxel coordinates, bit 63 = segment.  The all-ones key (segment 1, all three indices 2^21 - 1)
-  // is the empty marker: reported like an index out of range
-  const unsigned long long key = (unsigned long long)ix | ((unsigned long long)iy << 21) | ((unsigned long long)iz << 42) |
-                                 ((unsigned long long)seg << 63);
+  key |= (unsigned long long)seg << 63;
   if (key == kFree) {
     W.overflow[0] = 1;
     W.slot_of_pt[i] = -1;
@@ -249,16 +172,7 @@ __global__ __launch_bounds__(256) void k_vox_emit(VoxelJob J, VoxelWork W, int n
   double sx = 0.0, sy = 0.0, sz = 0.0;
   if (leader) {
     if (m <= kVoxLocal) {
-      for (int a = 1; a < m; ++a) {   // insertion sort of this thread's column
-        const int key = s_mem[a * 256 + tid];
-        int b = a - 1;
-        while (b >= 0 && s_mem[b * 256 + tid] > key) { s_mem[(b + 1) * 256 + tid] = s_mem[b * 256 + tid]; --b; }
-        s_mem[(b + 1) * 256 + tid] = key;
-      }
-      for (int q = 0; q < m; ++q) {
-        const int j = s_mem[q * 256 + tid];
-        sx += J.x[j]; sy += J.y[j]; sz += J.z[j];
-      }
+      leader_local_sum(s_mem, m, J.x, J.y, J.z, &sx, &sy, &sz);
     } else {
       // a crowded voxel: its members into a piece of the global scratch (only this thread ever touches it), heap sort, sum
       int* buf = W.members + atomicAdd(&W.leader_scan[1], (unsigned long long)m);
@@ -300,22 +214,14 @@ __global__ __launch_bounds__(256) void k_vox_emit(VoxelJob J, VoxelWork W, int n
   }
 }
 
-inline unsigned blocks_for(size_t n) { return (unsigned)((n + 255) / 256); }
 }  // namespace
 
-void launch_transform_to_soa(const double* aos, size_t n, const double M[16], double* ox, double* oy, double* oz,
-                             hipStream_t s) {
-  if (n == 0) return;
-  Mat16 m;
-  for (int i = 0; i < 16; ++i) m.m[i] = M[i];
-  hipLaunchKernelGGL(k_transform_to_soa, dim3(blocks_for(n)), dim3(256), 0, s, aos, n, m, ox, oy, oz);
-}
 void launch_transform_to_soa2(const double* aos, size_t n, const double M[16], double* ax, double* ay, double* az,
                               double* bx, double* by, double* bz, hipStream_t s) {
   if (n == 0) return;
   Mat16 m;
   for (int i = 0; i < 16; ++i) m.m[i] = M[i];
-  hipLaunchKernelGGL(k_transform_to_soa2, dim3(blocks_for(n)), dim3(256), 0, s, aos, n, m, ax, ay, az, bx, by, bz);
+  hipLaunchKernelGGL(k_transform_to_soa2, dim3(blocks_of(n)), dim3(256), 0, s, aos, n, m, ax, ay, az, bx, by, bz);
 }
 // Input assembly of the two-segment job in ONE launch (blockIdx.y = segment): [old submap | Transform(new scan)]
 // per segment, written back to back into (wx, wy, wz)
@@ -331,16 +237,14 @@ __global__ void k_assemble(AssembleArgs A, double* __restrict__ wx, double* __re
   }
   const size_t k = i - n_old;  // += scan->Transform(pose)
   const double* __restrict__ aos = A.aos[s];
-  const double x = aos[3 * k], y = aos[3 * k + 1], z = aos[3 * k + 2];
-  double r[4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a) r[a] = ((A.M[a] * x + A.M[4 + a] * y) + A.M[8 + a] * z) + A.M[12 + a] * 1.0;
-  wx[o] = r[0] / r[3]; wy[o] = r[1] / r[3]; wz[o] = r[2] / r[3];
+  double x, y, z;
+  map_transform_point(A.M, aos[3 * k], aos[3 * k + 1], aos[3 * k + 2], &x, &y, &z);
+  wx[o] = x; wy[o] = y; wz[o] = z;
 }
 void launch_assemble(const AssembleArgs& A, double* wx, double* wy, double* wz, hipStream_t s) {
   const size_t nmax = std::max(A.n_old[0] + A.n_new[0], A.n_old[1] + A.n_new[1]);
   if (nmax == 0) return;
-  hipLaunchKernelGGL(k_assemble, dim3(blocks_for(nmax), 2), dim3(256), 0, s, A, wx, wy, wz);
+  hipLaunchKernelGGL(k_assemble, dim3(blocks_of(nmax), 2), dim3(256), 0, s, A, wx, wy, wz);
 }
 // doubles [d0, d1) of `src` -> LDS, dst[d - (d0 & ~1)] = src[d]: one coalesced 16-byte load per lane and pass (src 16-byte
 // aligned; up to one double in front of d0 and one behind d1 come along).  The new scan's clouds are read where the host left
@@ -354,9 +258,9 @@ __device__ __forceinline__ void stage_doubles(const double* __restrict__ src, si
     dst[2 * (p - p0) + 1] = v.y;
   }
 }
-// ---- the front of a submap update in ONE launch: the planar ring (blockIdx.y < ring frames: k_transform_ring's work), the
-// assembly of [old submap | Transform(new scan)] of the edge and the ground cloud (the next two rows of blocks: k_assemble's
-// work) and, by those same blocks on the points they have just written, what k_vox_min2 would do next: the hash table of the
+// ---- the front of a submap update in ONE launch: the planar ring (blockIdx.y < ring frames: every buffered frame transformed
+// into both submaps), the assembly of [old submap | Transform(new scan)] of the edge and the ground cloud (the next two rows of
+// blocks: k_assemble's work) and, by those same blocks on the points they have just written, what k_vox_min2 would do next: the hash table of the
 // crop + voxel job emptied, the min bound of the cropped clouds as block partials, voxel_min_bound finished by the last block
 // (ticket).  launch_crop_voxel then starts at the insert pass: an update is front | insert | emit.
 __global__ __launch_bounds__(256) void k_submap_front(RingArgs R, int ring_count, AssembleArgs A, VoxelJob J, VoxelWork W, int emit_blocks,
@@ -378,19 +282,13 @@ __global__ __launch_bounds__(256) void k_submap_front(RingArgs R, int ring_count
         *reinterpret_cast<double2*>(R.copy_dst + 3 * b0 + 2 * p) = double2{s_stage[2 * p], s_stage[2 * p + 1]};
     }
     if (i >= nf) return;
-    const Mat16& M = R.M[f];
-    const double x = s_stage[3 * threadIdx.x], y = s_stage[3 * threadIdx.x + 1], z = s_stage[3 * threadIdx.x + 2];
-    double r[4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a) r[a] = ((M.m[a] * x + M.m[4 + a] * y) + M.m[8 + a] * z) + M.m[12 + a] * 1.0;
-    const double vx = r[0] / r[3], vy = r[1] / r[3], vz = r[2] / r[3];
+    double vx, vy, vz;
+    map_transform_point(R.M[f].m, s_stage[3 * threadIdx.x], s_stage[3 * threadIdx.x + 1], s_stage[3 * threadIdx.x + 2], &vx, &vy, &vz);
     const size_t o = R.off[f] + i;
     px[o] = vx; py[o] = vy; pz[o] = vz;
     qx[o] = vx; qy[o] = vy; qz[o] = vz;
     return;
   }
-  __shared__ double sm[3][256];
-  __shared__ int s_last;
   const int s = (int)blockIdx.y - ring_count;            // segment: 0 edge, 1 ground
   const int lb = s * (int)gridDim.x + (int)blockIdx.x, nlb = 2 * (int)gridDim.x;   // this block among the assembling ones
   if (lb == 0 && threadIdx.x == 0) { W.overflow[0] = 0; W.leader_scan[0] = 0ull; W.leader_scan[1] = 0ull; }
@@ -414,49 +312,16 @@ __global__ __launch_bounds__(256) void k_submap_front(RingArgs R, int ring_count
     } else {          // += scan->Transform(pose)
       const size_t k = i - n_old;
       const double* a = s_stage + (3 * k - ((3 * k0) & ~(size_t)1));
-      const double ax = a[0], ay = a[1], az = a[2];
-      double r[4];
-#pragma unroll
-      for (int a = 0; a < 4; ++a) r[a] = ((A.M[a] * ax + A.M[4 + a] * ay) + A.M[8 + a] * az) + A.M[12 + a] * 1.0;
-      x = r[0] / r[3]; y = r[1] / r[3]; z = r[2] / r[3];
+      map_transform_point(A.M, a[0], a[1], a[2], &x, &y, &z);
     }
     wx[o] = x; wy[o] = y; wz[o] = z;
     if (in_box(J, s, x, y, z)) { m[0] = x; m[1] = y; m[2] = z; }
   }
-#pragma unroll
-  for (int a = 0; a < 3; ++a) sm[a][threadIdx.x] = m[a];
-  __syncthreads();
-  for (int st = 128; st > 0; st >>= 1) {
-    if ((int)threadIdx.x < st)
-#pragma unroll
-      for (int a = 0; a < 3; ++a) sm[a][threadIdx.x] = fmin(sm[a][threadIdx.x], sm[a][threadIdx.x + st]);
-    __syncthreads();
-  }
-  if (threadIdx.x < 6) {   // this block's row: its segment's three columns, +inf in the other segment's
-    const int a = threadIdx.x;
-    const double v = (a / 3 == s) ? sm[a % 3][0] : __builtin_inf();
-    __hip_atomic_store(W.min_partial + (size_t)lb * 6 + a, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0)
-    s_last = (__hip_atomic_fetch_add(W.overflow + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nlb - 1) ? 1 : 0;
-  __syncthreads();
-  if (!s_last) return;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  for (int a = wave; a < 6; a += 4) {   // voxel_min_bound = GetMinBound() - voxel_size * 0.5 (:366); empty cloud: (0, 0, 0)
-    double v = __builtin_inf();
-    for (int b = lane; b < nlb; b += 64)
-      v = fmin(v, __hip_atomic_load(W.min_partial + (size_t)b * 6 + a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, 64));
-    if (!(v < __builtin_inf())) v = 0.0;
-    if (lane == 0) W.vmin[a] = v - J.voxel[a < 3 ? 0 : 1] * 0.5;
-  }
-  if (threadIdx.x == 0) __hip_atomic_store(W.overflow + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-armed
+  // this block's row: its segment's three columns, +inf in the other segment's; voxel_min_bound finished by the last block
+  voxel_min_bound<3, 6>(m, 3 * s, W.min_partial, lb, nlb, W.overflow + 1, J.voxel, W.vmin);
 }
 // rows of VoxelWork::min_partial the front launch needs (6 doubles each)
-size_t submap_front_rows(size_t n_ring_max, size_t n_seg_max) { return 2 * (size_t)blocks_for(std::max<size_t>(std::max(n_ring_max, n_seg_max), 1)); }
+size_t submap_front_rows(size_t n_ring_max, size_t n_seg_max) { return 2 * (size_t)blocks_of(std::max<size_t>(std::max(n_ring_max, n_seg_max), 1)); }
 void launch_submap_front(int count, const double* const aos[], const size_t n[], const double* const poses[], const AssembleArgs& A,
                          const VoxelJob& J, const VoxelWork& W, double* px, double* py, double* pz, double* qx, double* qy, double* qz,
                          double* wx, double* wy, double* wz, hipStream_t s, int copy_frame, double* copy_dst) {
@@ -474,33 +339,11 @@ void launch_submap_front(int count, const double* const aos[], const size_t n[],
     nmax = std::max(nmax, n[f]);
   }
   nmax = std::max(nmax, std::max(A.n_old[0] + A.n_new[0], A.n_old[1] + A.n_new[1]));
-  const int emit_blocks = (int)blocks_for(J.n + 1);
-  hipLaunchKernelGGL(k_submap_front, dim3(blocks_for(nmax), count + 2), dim3(256), 0, s, R, count, A, J, W, emit_blocks, px, py, pz, qx, qy,
+  const int emit_blocks = (int)blocks_of(J.n + 1);
+  hipLaunchKernelGGL(k_submap_front, dim3(blocks_of(nmax), count + 2), dim3(256), 0, s, R, count, A, J, W, emit_blocks, px, py, pz, qx, qy,
                      qz, wx, wy, wz);
 }
-int transform_ring_max() { return kRingMax; }
-void launch_transform_ring(int count, const double* const aos[], const size_t n[], const double* const poses[],
-                           double* ax, double* ay, double* az, double* bx, double* by, double* bz, hipStream_t s) {
-  RingArgs R;
-  memset(&R, 0, sizeof(R));
-  R.copy_frame = -1;
-  size_t off = 0, nmax = 0;
-  for (int f = 0; f < count; ++f) {
-    R.aos[f] = aos[f];
-    R.n[f] = n[f];
-    R.off[f] = off;
-    for (int i = 0; i < 16; ++i) R.M[f].m[i] = poses[f][i];
-    off += n[f];
-    nmax = std::max(nmax, n[f]);
-  }
-  if (count == 0 || nmax == 0) return;
-  hipLaunchKernelGGL(k_transform_ring, dim3(blocks_for(nmax), count), dim3(256), 0, s, R, ax, ay, az, bx, by, bz);
-}
-void launch_copy3(const double* ax, const double* ay, const double* az, size_t n, double* ox, double* oy, double* oz,
-                  hipStream_t s) {
-  if (n == 0) return;
-  hipLaunchKernelGGL(k_copy3, dim3(blocks_for(n)), dim3(256), 0, s, ax, ay, az, n, ox, oy, oz);
-}
+int submap_front_ring_max() { return kRingMax; }
 // n doubles (n even, both ends 16-byte aligned) from pinned host memory the device can address to device memory: what a
 // hipMemcpyAsync would do, as a kernel -- for a few hundred KB the copy command costs the calling thread and the copy engine
 // more than a launch that reads across PCIe with every load in flight at once
@@ -516,22 +359,12 @@ void launch_blit_doubles(const double* src_host_view, double* dst, size_t n, hip
 }
 void launch_soa_to_aos(const double* x, const double* y, const double* z, size_t n, double* aos, hipStream_t s) {
   if (n == 0) return;
-  hipLaunchKernelGGL(k_soa_to_aos, dim3(blocks_for(n)), dim3(256), 0, s, x, y, z, n, aos);
+  hipLaunchKernelGGL(k_soa_to_aos, dim3(blocks_of(n)), dim3(256), 0, s, x, y, z, n, aos);
 }
 
 int vox_emit_resident_blocks(int device_cus) {
-  // (one kernel, one architecture: the same for every gfx950 device of the process; contexts are created from several host
-  //  threads -- an atomic, and two threads that both find it unset both store the same value)
   static std::atomic<int> per_cu_cache{-1};
-  int per_cu = per_cu_cache.load(std::memory_order_relaxed);
-  if (per_cu < 0) {
-    int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_vox_emit, 256, 0) != hipSuccess || occ < 1) { (void)hipGetLastError(); occ = 1; }
-    per_cu = occ;
-    per_cu_cache.store(occ, std::memory_order_relaxed);
-  }
-  const long long all = (long long)device_cus * per_cu;
-  return (int)(all - all / 16);   // with room to spare for whatever else is on the device
+  return emit_resident_blocks(k_vox_emit, per_cu_cache, device_cus);
 }
 size_t voxel_table_size(size_t n) {
   size_t cap = 1024;
@@ -545,9 +378,9 @@ size_t voxel_table_size(size_t n) {
 void launch_crop_voxel(const VoxelJob& J, const VoxelWork& W, hipStream_t s, bool front_done) {
   const size_t n = J.n;
   constexpr int kMinBlocks = 256;
-  const int emit_blocks = (int)blocks_for(n + 1);   // (n + 1: an empty job still has a block that reports sizes of 0)
+  const int emit_blocks = (int)blocks_of(n + 1);   // (n + 1: an empty job still has a block that reports sizes of 0)
   if (!front_done) hipLaunchKernelGGL(k_vox_min2, dim3(kMinBlocks), dim3(256), 0, s, J, W, emit_blocks);
-  if (n > 0) hipLaunchKernelGGL(k_vox_insert2, dim3(blocks_for(n)), dim3(256), 0, s, J, W);
+  if (n > 0) hipLaunchKernelGGL(k_vox_insert2, dim3(blocks_of(n)), dim3(256), 0, s, J, W);
   hipLaunchKernelGGL(k_vox_emit, dim3(emit_blocks), dim3(256), 0, s, J, W, emit_blocks);
 }
 

@@ -3,10 +3,15 @@
 // surfels (tl_surfel.hip) and the localiser (tl_localise.hip).  One definition each of the key hash, the two table inserts and
 // the slot table's lookup, of the block scans, of the single-pass look-back with its one bound, of the eight-word post to the
 // host, of the voxel map's key / q arithmetic, its row centroid and its run sums, of the compacting box read's body
-// (k_vmap_box, k_carve_box, k_surfel_box), of the surfel gate, and of the span table's search and its point.
-// Device code, and the launches' blocks_of.
-// An includer must be compiled with -ffp-contract=off: vmap_quantise and centroid are the bit-for-bit contract of DESIGN.md 14.
+// (k_vmap_box, k_carve_box, k_surfel_box), of the surfel gate, and of the span table's search and its point; and of
+// PointCloud2::VoxelDownSample's arithmetic for the two units that restate it (the min bound's hand-over and finish, the voxel
+// key of a point, the leader's local sum, the blocks of an emit kernel the device holds at once).
+// Device code, and the launches' blocks_of and emit_resident_blocks.
+// An includer must be compiled with -ffp-contract=off: vmap_quantise and centroid are the bit-for-bit contract of DESIGN.md 14,
+// voxel_min_bound, voxel_key and leader_local_sum that of the oracle's pc_voxel_down_sample.
 #pragma once
+
+#include <atomic>
 
 #include "tl_common.hpp"
 
@@ -174,6 +179,100 @@ __device__ __forceinline__ void post_host_segment(unsigned long long* host_seg, 
   x ^= __shfl_xor(x, 4, 64);
   if (tid == 7) w = check_mix(host_seq) ^ x;
   __hip_atomic_store(&host_seg[tid], w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// ---- PointCloud2::VoxelDownSample (PointCloud2.cpp:358-403): what the submap's job (tl_submap.hip) and the global map's
+// (tl_map.hip) restate of it, once.  Bit for bit the oracle's pc_voxel_down_sample; the transformed point they start from is
+// map_transform_point (tl_common.hpp) ----
+// voxel_min_bound = GetMinBound() - voxel_size * 0.5 (:366), finished inside the launch that finds the minima.  m[]: this
+// thread's minima (+inf: none) of columns [col0, col0 + NM) of the C = 3 per segment columns.  The block's minima go to row
+// `row` of min_partial[rows][C] (+inf in the other columns) with agent-scope stores, their completion is waited for, then the
+// block takes a ticket (zero before the launch); the LAST of the `rows` blocks folds the rows, one wave per column (min is exact
+// in any order), writes vmin[a] = min - voxel[a / 3] * 0.5 -- an empty cloud has min bound 0 -- and re-arms the ticket.
+// Called by the whole block (256 threads).
+template <int NM, int C>
+__device__ __forceinline__ void voxel_min_bound(const double (&m)[NM], int col0, double* min_partial, int row, int rows, int* ticket,
+                                                const double* voxel, double* vmin) {
+  __shared__ double sm[NM][256];
+  __shared__ int s_last;
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int a = 0; a < NM; ++a) sm[a][tid] = m[a];
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    if (tid < st)
+#pragma unroll
+      for (int a = 0; a < NM; ++a) sm[a][tid] = fmin(sm[a][tid], sm[a][tid + st]);
+    __syncthreads();
+  }
+  if (tid < C) {
+    const double v = (tid >= col0 && tid < col0 + NM) ? sm[tid - col0][0] : __builtin_inf();
+    __hip_atomic_store(min_partial + (size_t)row * C + tid, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (tid == 0) s_last = (__hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == rows - 1) ? 1 : 0;
+  __syncthreads();
+  if (!s_last) return;
+  const int wave = tid >> 6, lane = tid & 63;
+  for (int a = wave; a < C; a += 4) {
+    double v = __builtin_inf();
+    for (int b = lane; b < rows; b += 64)
+      v = fmin(v, __hip_atomic_load(min_partial + (size_t)b * C + a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, 64));
+    if (!(v < __builtin_inf())) v = 0.0;
+    if (lane == 0) vmin[a] = v - voxel[(C > 3 && a >= 3) ? 1 : 0] * 0.5;
+  }
+  if (tid == 0) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-armed
+}
+
+// ref_coord = (p - voxel_min_bound) / voxel_size; index = int(floor(ref_coord)) (:380-383), packed 3 x 21 bits.  false: an index
+// leaves [0, 2^21) -- "[VoxelDownSample] voxel_size is too small." (:370-372); *key is then not to be used.
+__device__ __forceinline__ bool voxel_key(double x, double y, double z, const double* vmin, double voxel, unsigned long long* key) {
+  const long long ix = (long long)floor((x - vmin[0]) / voxel);
+  const long long iy = (long long)floor((y - vmin[1]) / voxel);
+  const long long iz = (long long)floor((z - vmin[2]) / voxel);
+  if (ix < 0 || iy < 0 || iz < 0 || ix >= (1ll << 21) || iy >= (1ll << 21) || iz >= (1ll << 21)) return false;
+  *key = (unsigned long long)ix | ((unsigned long long)iy << 21) | ((unsigned long long)iz << 42);
+  return true;
+}
+
+// AccumulatedPoint: point_ += p in index order (:253-272).  s_mem[q * 256 + tid], q < k <= kVoxLocal: the members of this
+// thread's voxel in any order (conflict-free columns); they are ordered by index (insertion sort: the order AddPoint is called
+// in, :379-385) and the points summed in that order.  GetAveragePoint's division by double(num) is the caller's.
+__device__ __forceinline__ void leader_local_sum(int* s_mem, int k, const double* __restrict__ x, const double* __restrict__ y,
+                                                 const double* __restrict__ z, double* sx, double* sy, double* sz) {
+  const int tid = threadIdx.x;
+  for (int a = 1; a < k; ++a) {
+    const int key = s_mem[a * 256 + tid];
+    int b = a - 1;
+    while (b >= 0 && s_mem[b * 256 + tid] > key) { s_mem[(b + 1) * 256 + tid] = s_mem[b * 256 + tid]; --b; }
+    s_mem[(b + 1) * 256 + tid] = key;
+  }
+  double ax = 0.0, ay = 0.0, az = 0.0;
+  for (int q = 0; q < k; ++q) {
+    const int j = s_mem[q * 256 + tid];
+    ax += x[j]; ay += y[j]; az += z[j];
+  }
+  *sx = ax; *sy = ay; *sz = az;
+}
+
+// Blocks of 256 threads of an emit kernel the device holds at once, with room to spare for whatever else is on it: a grid of up
+// to that many takes its look-back places from blockIdx.  per_cu_cache: the kernel's own (-1 before the first call; one kernel,
+// one architecture: the same for every gfx950 device of the process; contexts are created from several host threads -- an atomic,
+// and two threads that both find it unset both store the same value)
+template <class Kernel>
+inline int emit_resident_blocks(Kernel kernel, std::atomic<int>& per_cu_cache, int device_cus) {
+  int per_cu = per_cu_cache.load(std::memory_order_relaxed);
+  if (per_cu < 0) {
+    int occ = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, 256, 0) != hipSuccess || occ < 1) { (void)hipGetLastError(); occ = 1; }
+    per_cu = occ;
+    per_cu_cache.store(occ, std::memory_order_relaxed);
+  }
+  const long long all = (long long)device_cus * per_cu;
+  return (int)(all - all / 16);
 }
 
 // ---- the voxel map's grid (the merged voxel map and the closed map): DESIGN.md 14 states this arithmetic, and here it is ----
