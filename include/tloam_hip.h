@@ -1164,6 +1164,58 @@ int tloam_closed_map_relocalise(tloam_ctx* ctx, const double* points_aos, size_t
 int tloam_closed_map_relocalise_hypotheses(tloam_ctx* ctx, size_t capacity, size_t* n,
                                            tloam_closed_map_relocalise_hypothesis* hypotheses);
 
+/* ---- the closed map's snapshot: a built closed map out of a context and into a fresh one (additive to ABI 8) ------
+ * A memory blob; the library opens no files.  It holds, exactly, everything a context needs to answer every read of the closed
+ * map and every localisation in it with the bytes of the context that saved: the place, loop, closed map, carve and surfel
+ * configurations (every reserve_* / reserved field written as 0), the three infos (capacity_voxels written as 0), the keyframe
+ * database (frame, stored pose, ring key, sector key, descriptor of all keyframes), the build's poses, the rows in id order
+ * (key, N, Qx, Qy, Qz), the miss counts when carved, the thirteen sums when surfels exist, and with TLOAM_SNAPSHOT_CLOUDS the
+ * keyframes' eight clouds.  NOT saved: normals and variances (a pure function of the sums: recomputed at load, the same bits),
+ * the localiser's voxel records (rebuilt lazily as ever), table sizes and capacities, place loop records, verified constraints
+ * and corrected graph poses (the mapping session's working state), the localise and relocalise configurations (the querying
+ * session's business).  Nothing in the blob depends on capacity, table size or allocation history: two saves give the same
+ * bytes, and a save from a loaded context gives the blob it was loaded from.
+ * Format version 1, little-endian, every section 8-byte aligned: a 416-byte header (magic "TLCMSNP1", version, flags, the
+ * blob's bytes, the header's checksum, the counts, the grid, and a table of nine (kind, offset, bytes, checksum) entries, one
+ * per section kind in ascending order, an absent section with 0 bytes), then the sections end to end.  The checksum of m 64-bit
+ * words w_i is sum_i mix64(w_i + 0x9E3779B97F4A7C15 * (i + 1)) mod 2^64, mix64 the splitmix64 finaliser; the header's own is
+ * over the header with that field zero.  DESIGN.md 25 has the table.
+ * A blob is untrusted input: tloam_closed_map_load checks all of it -- header, table, configurations, poses and counts on the
+ * host, checksums, keys, row and sum ranges, descriptors and the rebuilt slot table on the device -- before anything in the
+ * context changes; a refused load is TLOAM_E_INVALID, tloam_last_error names the section and the test, and the context is as it
+ * was, byte for byte.  A load replaces the state tloam_place_configure empties (keyframes, loop constraints, corrected poses,
+ * closed map) and the five configurations.  Loaded without clouds the map is DETACHED: tloam_closed_map_build, _carve and
+ * _surfels return TLOAM_E_NOT_READY and leave it as it is, until tloam_closed_map_configure, tloam_place_configure,
+ * tloam_loop_configure or tloam_odometry_reset empty it as they always do (a carve or surfel configure drops its section as
+ * always, and a detached map cannot gather it again).  Loaded with clouds nothing is detached. */
+#define TLOAM_SNAPSHOT_CLOUDS 1   /* also the keyframes' eight clouds: the loaded map can be re-built, re-carved, re-surfelled */
+#define TLOAM_SNAPSHOT_FORMAT_VERSION 1
+typedef struct tloam_closed_map_snapshot_info {
+  int32_t format_version;
+  int32_t flags;                 /* TLOAM_SNAPSHOT_* of the save */
+  int64_t n_keyframes_database;  /* keyframes of the place database */
+  int64_t n_keyframes_map;       /* K of the build */
+  int64_t n_voxels;
+  int64_t n_points;
+  int32_t has_carve, has_surfels, has_clouds;
+  int32_t n_rings, n_sectors;
+  int32_t reserved0;
+  int64_t cloud_points;          /* points of all stored clouds (0 without them) */
+  double voxel;
+  double origin[3];
+  uint64_t bytes;                /* of the whole blob */
+} tloam_closed_map_snapshot_info;
+/* The size tloam_closed_map_save(flags) writes.  TLOAM_E_NOT_READY without a built closed map, TLOAM_E_INVALID for unknown flags. */
+int tloam_closed_map_save_size(tloam_ctx* ctx, int flags, size_t* bytes);
+/* Writes the blob.  *written: its size, also when capacity is too small (then nothing is written and TLOAM_E_INVALID is
+ * returned).  Changes nothing in the context. */
+int tloam_closed_map_save(tloam_ctx* ctx, int flags, void* buf, size_t capacity, size_t* written);
+/* Host only, no context, no GPU: the header and the section table checked (magic, version, checksum, every section inside the
+ * blob, aligned, in order, of the size the counts ask for), the counts reported.  TLOAM_E_INVALID otherwise. */
+int tloam_closed_map_probe(const void* buf, size_t bytes, tloam_closed_map_snapshot_info* info);
+int tloam_closed_map_load(tloam_ctx* ctx, const void* buf, size_t bytes, tloam_closed_map_snapshot_info* info_or_null);
+/* Every snapshot call with a context on one with nranks > 1: TLOAM_E_INVALID. */
+
 /* ---- multi-GPU: correspondence set sharded over ranks, one all-reduce per sweep --------
  * (nothing in the reference).  Call before set_source / set_correspondences.
  * (a) native RCCL over xGMI: unique_id = the 128 bytes of an ncclUniqueId made on rank 0

@@ -53,6 +53,10 @@ int carve_body(tloam_ctx* c, tloam_closed_map_carve_info& I) {
 
 }  // namespace
 
+namespace tlh {
+bool carve_config_valid(const tloam_closed_map_carve_config& cfg) { return carve_config_ok(cfg); }
+}  // namespace tlh
+
 extern "C" {
 
 void tloam_closed_map_carve_default_config(tloam_closed_map_carve_config* cfg) {
@@ -80,6 +84,7 @@ int tloam_closed_map_get_carve_info(tloam_ctx* c, tloam_closed_map_carve_info* i
 }
 
 int tloam_closed_map_carve(tloam_ctx* c, tloam_closed_map_carve_info* info) {
+  if (c && c->nranks == 1 && c->cmap.detached) return TLOAM_E_NOT_READY;   // (loaded without its clouds: DESIGN.md 25)
   return cmap_pass_entry(c, &CmapState::drop_carve, &CmapState::carve_info, &CmapState::carved, info,
                          [&](tloam_closed_map_carve_info& I) { return carve_body(c, I); });
 }

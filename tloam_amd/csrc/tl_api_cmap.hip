@@ -119,6 +119,9 @@ int build_body(tloam_ctx* c, const std::vector<double>& poses, tloam_closed_map_
 
 namespace tlh {
 
+bool cmap_config_valid(const tloam_closed_map_config& cfg) { return cmap_config_ok(cfg); }
+size_t cmap_default_reserve() { return kCmapDefaultReserve; }
+
 void cmap_span_table(const PlaceState& P, size_t K, int mask, std::vector<CmapSpan>* spans, long long* n, int64_t* empty_keyframes) {
   long long at = 0;
   for (size_t k = 0; k < K && k < P.kf.size(); ++k) {
@@ -189,6 +192,7 @@ int tloam_closed_map_get_info(tloam_ctx* c, tloam_closed_map_info* info) {
 int tloam_closed_map_build(tloam_ctx* c, int pose_source, const double* poses, size_t n_poses, tloam_closed_map_info* info) {
   if (!cmap_on(c) || pose_source < TLOAM_CLOSED_MAP_POSES_STORED || pose_source > TLOAM_CLOSED_MAP_POSES_CALLER)
     return TLOAM_E_INVALID;
+  if (c->cmap.detached) return TLOAM_E_NOT_READY;   // (loaded without its clouds: DESIGN.md 25)
   const PlaceState& P = c->place;
   const GraphState& G = c->graph;
   const size_t K = P.kf.size();

@@ -213,6 +213,8 @@ bool loop_on(const tloam_ctx* c) { return c && c->nranks == 1 && c->loop.cfg.ena
 }  // namespace
 
 namespace tlh {
+bool loop_config_valid(const tloam_loop_config& cfg) { return loop_config_ok(cfg); }
+
 void loop_release(tloam_ctx* c) {
   LoopState& L = c->loop;
   drop_child(L.coarse);

@@ -146,6 +146,9 @@ int64_t device_loops(tloam_ctx* c, int* rc) {   // waits for the work in flight
 
 namespace tlh {
 
+bool place_config_valid(const tloam_place_config& cfg) { return place_config_ok(cfg, true); }
+size_t place_default_reserve() { return kPlaceDefaultReserve; }
+
 // the start of a frame: room for one more keyframe, before anything of the odometry state changes.  A failure leaves the frame
 // undone
 int place_frame_reserve(tloam_ctx* c, size_t n) {

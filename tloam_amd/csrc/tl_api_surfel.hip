@@ -73,6 +73,7 @@ int tloam_closed_map_get_surfel_info(tloam_ctx* c, tloam_closed_map_surfel_info*
 }
 
 int tloam_closed_map_surfels(tloam_ctx* c, tloam_closed_map_surfel_info* info) {
+  if (c && c->nranks == 1 && c->cmap.detached) return TLOAM_E_NOT_READY;   // (loaded without its clouds: DESIGN.md 25)
   return cmap_pass_entry(c, &CmapState::drop_surfels, &CmapState::surfel_info, &CmapState::surfeled, info,
                          [&](tloam_closed_map_surfel_info& I) { return surfel_body(c, I); });
 }

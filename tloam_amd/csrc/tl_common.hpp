@@ -1077,4 +1077,48 @@ void launch_weights_finish_small(const CorrView& cv, const SlotView& sv, const W
 void launch_transform_cloud(double* aos, size_t n, const double M[16], hipStream_t s);
 void launch_debug_se3(const double* x, const double* delta, int n, double* out /* 26 per item */, hipStream_t s);
 
+// ---- the closed map's snapshot (tl_snapshot.hip): the device side of tloam_closed_map_save / _load.
+// A save gathers the device-born sections into the blob's layout and forms their checksums; a load checks an uploaded blob's
+// device-born sections word by word, and the slot table rebuilt from its keys.  Both work through a short list of PIECES --
+// runs of 64-bit words that belong to one section -- so the launches are the same for every map; no kernel indexes by a value
+// it read from a blob: every bound is a launch argument
+constexpr int kSnapPieces = 12;
+constexpr unsigned long long kSnapGolden = 0x9E3779B97F4A7C15ull;
+constexpr long long kSnapMaxN = 1ll << 30;   // points of a build (tl_api_cmap.hip), so of a voxel
+// control words: [section kind] its checksum (kinds 1 .. 9), then what k_snap_check and k_snap_table count
+enum SnapCtl {
+  kSnapBadFinite = 16,   // database words that are not finite doubles
+  kSnapBadKey = 17,      // keys with an axis field outside [1, 2^21 - 1] or bit 63 set
+  kSnapBadN = 18,        // N outside [1, 2^30]
+  kSnapBadQ = 19,        // Q outside [0, N * 2^24]
+  kSnapBadMiss = 20,     // M < 0
+  kSnapBadSums = 21,     // Ns, Sxx, Syy or Szz < 0
+  kSnapSumN = 22,        // the sum of N
+  kSnapBadFind = 23,     // ids the rebuilt table does not find under their own key
+  kSnapCtlWords = 24
+};
+enum SnapTest { kSnapTestNone = 0, kSnapTestFinite, kSnapTestKey, kSnapTestN, kSnapTestQ, kSnapTestMiss, kSnapTestSums };
+struct SnapPiece {
+  const unsigned long long* src;
+  unsigned long long* dst;          // k_snap_pack: where the words go (null: they are in place, only summed)
+  unsigned long long words;
+  unsigned long long first;         // index of src[0] within its section: the checksum's i
+  const long long* aux;             // kSnapTestQ: the N column, [aux_n]; word j of the piece is Q of row j % aux_n
+  unsigned long long aux_n;
+  int section;                      // the control word its checksum is added to
+  int test;                         // k_snap_check: SnapTest
+};
+struct SnapPieces {
+  SnapPiece piece[kSnapPieces];
+  int npieces;
+  unsigned long long* ctl;          // [kSnapCtlWords], zero before the launch
+};
+void launch_snap_pack(const SnapPieces& A, hipStream_t s);    // one launch: gather and checksum
+void launch_snap_check(const SnapPieces& A, hipStream_t s);   // one launch: checksum and test
+// the slot table of `T` (all slots free, at least 2 n of them) filled with ids [0, n), then every id looked up under its own
+// key: two launches; a duplicated key fails the lookup of one of its ids whichever insert came first
+void launch_snap_table(const VmapTable& T, size_t n, unsigned long long* ctl, hipStream_t s);
+// k_surfel_solve alone (tl_surfel.hip), on sums that are already there: W.nv, min_points, voxel, sums, normal, eval, ctl[2]
+void launch_surfel_solve(const SurfelWork& W, hipStream_t s);
+
 }  // namespace tl

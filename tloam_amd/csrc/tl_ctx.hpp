@@ -3,7 +3,7 @@
 // exchange, tl_api_submap.hip: device-resident submap, tl_api_feature.hip: PCA features, tl_api_seg.hip: segmentation,
 // tl_api_odom.hip: the whole odometry frame, tl_api_map.hip: its global map and registered scan, tl_api_vmap.hip: its merged
 // voxel map, tl_api_deskew.hip: its deskew, tl_api_place.hip: place recognition, tl_api_cmap.hip: the closed map, tl_api_carve.hip: its carve,
-// tl_api_surfel.hip: its surfels).
+// tl_api_surfel.hip: its surfels, tl_api_snapshot.hip: its snapshot).
 // Memory: every buffer below belongs to the struct that declares it and dies with it (the owning types come first).
 #pragma once
 
@@ -439,6 +439,8 @@ struct CmapState {
   tloam_closed_map_config cfg = {1.0, {0.0, 0.0, 0.0}, 0xF0, 0, 0};   // tloam_closed_map_default_config until configured
   VoxelRowStore rows;
   bool built = false;              // a build has succeeded since the last drop
+  bool detached = false;           // the map was loaded from a snapshot without its clouds: it cannot be built,
+                                   // carved or surfelled again until it is emptied
   tloam_closed_map_info info{};    // of the last build (zero when dropped; capacity_voxels filled in when asked)
   std::vector<double> poses;       // [16 K] column-major: the poses the last build used
   DBuf<double> rd_c;
@@ -498,6 +500,7 @@ struct CmapState {
   }
   void drop() {   // the closed map goes, and the carve's counts and the surfels with it; the configurations and storage stay
     built = false;
+    detached = false;
     info = tloam_closed_map_info{};
     poses.clear();
     drop_carve();
@@ -1025,6 +1028,14 @@ int cmap_pass_entry(tloam_ctx* c, void (CmapState::*drop)(), Info CmapState::*la
 // ids [first, first + count) of a side array of the built closed map (`ran`: the stage that fills it has run): TLOAM_OK when the
 // range is one
 int cmap_side_range(const tloam_ctx* c, bool ran, size_t first, size_t count);
+// what tloam_closed_map_load (tl_api_snapshot.hip) needs of the units whose state it installs: their configure's own tests of a
+// configuration, and the room a default configuration reserves
+bool place_config_valid(const tloam_place_config& cfg);             // tl_api_place.hip
+size_t place_default_reserve();
+bool loop_config_valid(const tloam_loop_config& cfg);               // tl_api_loop.hip
+bool cmap_config_valid(const tloam_closed_map_config& cfg);         // tl_api_cmap.hip
+size_t cmap_default_reserve();
+bool carve_config_valid(const tloam_closed_map_carve_config& cfg);  // tl_api_carve.hip
 // tl_api_deskew.hip: the frame's deskew -- sized and its times uploaded after the scan's upload, launched after the segmentation's
 // (the refused-time flag read with the frame's first wait), committed when the frame ends
 int deskew_frame_upload(tloam_ctx* c, const double* t_sec, size_t n, tloam_odom_stats* st);

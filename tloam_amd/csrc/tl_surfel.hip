@@ -213,6 +213,10 @@ int launch_surfels(const SurfelWork& W, hipStream_t s) {
   return 4;
 }
 
+void launch_surfel_solve(const SurfelWork& W, hipStream_t s) {
+  hipLaunchKernelGGL(k_surfel_solve, dim3(blocks_of((size_t)std::max<long long>(W.nv, 1))), dim3(256), 0, s, W);
+}
+
 void launch_surfel_read(const SurfelReadArgs& A, hipStream_t s) {
   if (A.rows.count == 0) return;
   const int nb = (int)blocks_of(A.rows.count);

@@ -1,11 +1,14 @@
 """PCD export of the global map, of the merged voxel map (section 14), of the carved closed map
-(section 21) and of the closed map's surfels (section 22).
+(section 21) and of the closed map's surfels (section 22); and the closed map's snapshot as a file (section 25): the one
+form that loses nothing and is read back.
 
 The reference declares a `saveMap` service (srv/saveMap.srv) and never serves it; this is the file a user of the map needs.
 PCD v0.7 (the Point Cloud Library's format), fields `x y z`, each `F 8` (float64), so the device's doubles are written and
 read back bit for bit.  `DATA binary` by default; `ascii=True` writes every value with 17 significant digits (also exact).
 """
 from __future__ import annotations
+
+import os
 
 import numpy as np
 
@@ -229,3 +232,26 @@ def write_closed_map_surfel_pcd(path: str, H, lo=None, hi=None, min_count=1, max
     cen, nrm, _, cnt = H.closed_map_read_surfels_box(lo, hi, min_count, max_sigma, min_planarity)
     write_surfel_pcd(path, cen, nrm, cnt, ascii=ascii)
     return len(cnt)
+
+
+def save_closed_map(path: str, H, clouds: bool = False) -> int:
+    """Writes H's closed map snapshot (H.closed_map_save(clouds)) to `path` -> the bytes written.  Written to a temporary
+    name beside it and renamed, so a reader never sees half a file."""
+    blob = H.closed_map_save(clouds=clouds)
+    tmp = f"{path}.tmp{os.getpid()}"
+    try:
+        with open(tmp, "wb") as fh:
+            fh.write(blob)
+            fh.flush()
+            os.fsync(fh.fileno())
+        os.replace(tmp, path)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+    return len(blob)
+
+
+def load_closed_map(path: str, H) -> dict:
+    """Loads the snapshot file at `path` into H (H.closed_map_load) -> what it held."""
+    with open(path, "rb") as fh:
+        return H.closed_map_load(fh.read())

@@ -206,6 +206,23 @@ class ClosedMapRelocaliseHypothesis(C.Structure):
 RELOCALISE_FOUND, RELOCALISE_NOT_FOUND = 0, 1
 
 
+SNAPSHOT_CLOUDS = 1   # TLOAM_SNAPSHOT_CLOUDS: the keyframes' eight clouds go into the snapshot too
+
+
+class ClosedMapSnapshotInfo(C.Structure):
+    """tloam_closed_map_snapshot_info: what a closed map snapshot says it holds."""
+    _fields_ = [("format_version", C.c_int32), ("flags", C.c_int32), ("n_keyframes_database", C.c_int64),
+                ("n_keyframes_map", C.c_int64), ("n_voxels", C.c_int64), ("n_points", C.c_int64), ("has_carve", C.c_int32),
+                ("has_surfels", C.c_int32), ("has_clouds", C.c_int32), ("n_rings", C.c_int32), ("n_sectors", C.c_int32),
+                ("reserved0", C.c_int32), ("cloud_points", C.c_int64), ("voxel", C.c_double), ("origin", C.c_double * 3),
+                ("bytes", C.c_uint64)]
+
+    def as_dict(self):
+        out = {name: getattr(self, name) for name, _ in self._fields_ if name not in ("origin", "reserved0")}
+        out["origin"] = tuple(self.origin)
+        return out
+
+
 class DeskewConfig(C.Structure):
     """tloam_deskew_config: the deskew's switch, its time source (0 azimuth, 1 per-point times), the sweep's direction (+1
     counter-clockwise seen from +z), the azimuth it starts at and the sweep fraction the pose describes."""
@@ -553,6 +570,10 @@ def load_library():
         "tloam_closed_map_read_surfels": (C.c_int, [vp, sz, sz, dp, dp, C.POINTER(C.c_int64)]),
         "tloam_closed_map_read_surfels_box": (C.c_int, [vp, dp, dp, C.c_int64, C.c_double, C.c_double, sz, C.POINTER(sz), dp, dp, dp,
                                                         C.POINTER(C.c_int64)]),
+        "tloam_closed_map_save_size": (C.c_int, [vp, C.c_int, C.POINTER(sz)]),
+        "tloam_closed_map_save": (C.c_int, [vp, C.c_int, vp, sz, C.POINTER(sz)]),
+        "tloam_closed_map_probe": (C.c_int, [vp, sz, C.POINTER(ClosedMapSnapshotInfo)]),
+        "tloam_closed_map_load": (C.c_int, [vp, vp, sz, C.POINTER(ClosedMapSnapshotInfo)]),
         "tloam_rccl_unique_id": (C.c_int, [vp]),
         "tloam_comm_init_rccl": (C.c_int, [vp, C.c_int, C.c_int, vp]),
         "tloam_comm_init_callback": (C.c_int, [vp, C.c_int, C.c_int, ALLREDUCE_FN, vp]),
@@ -601,6 +622,7 @@ EXPORTED_SYMBOLS = (
     "tloam_closed_map_localise_log", "tloam_closed_map_linearise", "tloam_closed_map_localise_batch",
     "tloam_closed_map_localise_batch_log", "tloam_closed_map_relocalise_default_config", "tloam_closed_map_relocalise_configure",
     "tloam_closed_map_relocalise", "tloam_closed_map_relocalise_hypotheses",
+    "tloam_closed_map_save_size", "tloam_closed_map_save", "tloam_closed_map_probe", "tloam_closed_map_load",
     "tloam_rccl_unique_id", "tloam_comm_init_rccl",
     "tloam_comm_mailbox_export", "tloam_comm_init_mailbox",
     "tloam_comm_init_callback", "tloam_shard_range", "tloam_shard_ranges_frame", "tloam_se3_exp", "tloam_se3_log", "tloam_se3_plus",
@@ -663,6 +685,17 @@ def shard_ranges_frame(n4, rank, nranks):
     lo, hi = (C.c_size_t * 4)(), (C.c_size_t * 4)()
     load_library().tloam_shard_ranges_frame(n, int(rank), int(nranks), lo, hi)
     return [(int(lo[k]), int(hi[k])) for k in range(4)]
+
+
+def closed_map_probe(blob) -> dict:
+    """what a closed map snapshot says it holds, from its header and section table alone (host only: no context, no GPU);
+    raises TloamHipError when they do not hold"""
+    blob = bytes(blob)
+    info = ClosedMapSnapshotInfo()
+    rc = load_library().tloam_closed_map_probe(blob, len(blob), C.byref(info))
+    if rc:
+        raise TloamHipError(f"tloam_closed_map_probe: {STATUS.get(rc, rc)}")
+    return info.as_dict()
 
 
 def se3_exp(x):
@@ -1288,6 +1321,27 @@ class HipRegistration:
         out = np.zeros((max(m, 1), 16))
         self._check(self.L.tloam_closed_map_read_poses(self.h, int(first), m, _dp(out)), "tloam_closed_map_read_poses")
         return out[:m].reshape(m, 4, 4).transpose(0, 2, 1).copy()
+
+    # ---- the closed map's snapshot: out of this context, into a fresh one
+    def closed_map_save(self, clouds=False) -> bytes:
+        """the built closed map, its carve and surfels when they exist, the keyframe database and the configurations as one
+        blob; clouds: also the keyframes' stored clouds, so that the loaded map can be built, carved and surfelled again"""
+        flags = SNAPSHOT_CLOUDS if clouds else 0
+        n = C.c_size_t(0)
+        self._check(self.L.tloam_closed_map_save_size(self.h, flags, C.byref(n)), "tloam_closed_map_save_size")
+        buf = C.create_string_buffer(max(n.value, 1))
+        self._check(self.L.tloam_closed_map_save(self.h, flags, buf, n.value, C.byref(n)), "tloam_closed_map_save")
+        return buf.raw[:n.value]
+
+    def closed_map_load(self, blob) -> dict:
+        """replaces this context's keyframes, loop constraints, corrected poses and closed map by the snapshot's -> what it
+        held (closed_map_probe's dict).  A refused blob raises TloamHipError and leaves the context as it was"""
+        blob = bytes(blob)
+        info = ClosedMapSnapshotInfo()
+        self._check(self.L.tloam_closed_map_load(self.h, blob, len(blob), C.byref(info)), "tloam_closed_map_load")
+        # (the keyframe getters size their outputs by the place configuration's layout, which is now the snapshot's)
+        self._place_cfg = default_place_config(enabled=1, n_rings=int(info.n_rings), n_sectors=int(info.n_sectors))
+        return info.as_dict()
 
     # ---- the carve of the closed map: per voxel, the rays that passed through it (DESIGN.md section 21)
     def closed_map_carve_configure(self, cfg: ClosedMapCarveConfig | None = None, **over):
