@@ -1164,6 +1164,82 @@ int tloam_closed_map_relocalise(tloam_ctx* ctx, const double* points_aos, size_t
 int tloam_closed_map_relocalise_hypotheses(tloam_ctx* ctx, size_t capacity, size_t* n,
                                            tloam_closed_map_relocalise_hypothesis* hypotheses);
 
+/* ---- a scan diffed against the closed map: new points, voxels seen through (additive to ABI 8) ------
+ * With the pose known (tloam_closed_map_localise), what of the scan is not in the map, and what of the map does the scan see
+ * through?  A diff reads the built closed map with its surfels and writes nothing of them: it runs on a detached (loaded) map,
+ * only when called, and no frame, map, carve, surfel, localisation or snapshot changes by a bit.
+ * Per point p (sensor frame) and pose matrix M, used as it stands: O = (M[12], M[13], M[14]), E = M p as the localiser forms it.
+ * Point side, a label per point:
+ *   TLOAM_DIFF_INVALID   E is not finite, or its cell has |i| >= 2^20 on an axis.
+ *   Otherwise the 27 cells i + (dx, dy, dz) in the localiser's order (dz outermost, dx innermost; a cell beyond the grid is no
+ *   voxel).  An occupied voxel counts unless carve_gate is set and the carved read would leave it out
+ *   (M >= min_miss && (double) M > miss_ratio * (double) N, M the stored misses).  For a voxel that counts d = E - c,
+ *   D = (d_x*d_x + d_y*d_y) + d_z*d_z; two minima under a strict < (the first visited wins a tie): the nearest ELIGIBLE voxel (the
+ *   localiser's gate under the current localise configuration) and the nearest voxel of any kind.
+ *   TLOAM_DIFF_SURFACE   an eligible voxel was found and fabs(r) <= plane_tol, r = (n_x*d_x + n_y*d_y) + n_z*d_z
+ *   TLOAM_DIFF_OCCUPIED  not SURFACE, and the nearest voxel has D <= near * near
+ *   TLOAM_DIFF_NEW       every other valid point
+ *   ids: the voxel that explained the point (-1: INVALID, NEW).  A valid point whose own cell is an occupied voxel adds 1 to that
+ *   voxel's `hits` (ungated, whatever its label).
+ * Map side: the rays are the scan's points in order, from O to E; the skip rule, the walk, the miss test and the counters are the
+ * carve's (above) with max_range, end_margin and radius of THIS configuration, and a miss adds 1 to the voxel's `through`.  An
+ * INVALID point is a skipped ray.
+ * `through` and `hits` are int64 per voxel in id order, cleared by every call unless flags holds TLOAM_DIFF_ACCUMULATE: the call
+ * then adds to what is there.  The labels are per call.  All sums are integers: two calls, and two contexts, give the same bytes.
+ * The counts go with the closed map (whatever empties or replaces it, a snapshot load too); a carve or a surfel pass leaves them.
+ * They are not part of a snapshot. */
+#define TLOAM_DIFF_ACCUMULATE 1
+enum { TLOAM_DIFF_INVALID = 0, TLOAM_DIFF_SURFACE = 1, TLOAM_DIFF_OCCUPIED = 2, TLOAM_DIFF_NEW = 3 };
+typedef struct tloam_closed_map_diff_config {   /* the defaults are choices, not measurements */
+  double max_range;     /* 60: a longer ray is skipped (m); > 0, finite */
+  double end_margin;    /* 1.0: nothing is seen through within this of the return (m); >= 0, finite */
+  double radius;        /* 0.25 (the carve's): the largest distance from a centroid to a ray that sees through it (m); > 0 */
+  double plane_tol;     /* 0.1 (the localiser's min_residual): SURFACE when |r| <= plane_tol (m); >= 0, finite */
+  double near;          /* 0.5: OCCUPIED when the nearest centroid of the 27 cells is within it (m); >= 0, finite.  The 27 cells
+                         * hold every centroid within `near` of the point while near <= voxel */
+  int64_t min_miss;     /* 3: the carve gate's M >= min_miss */
+  double miss_ratio;    /* 1.0: ... && M > miss_ratio * N; not NaN */
+  int32_t carve_gate;   /* 0; 1: voxels the carved read leaves out explain no point (needs a carved map) */
+  int32_t reserved0;
+} tloam_closed_map_diff_config;
+void tloam_closed_map_diff_default_config(tloam_closed_map_diff_config* cfg);
+/* cfg NULL: the defaults.  A value out of its range (NaN too): TLOAM_E_INVALID, and the old configuration stays.  Drops the
+ * counts, not the closed map; persists across tloam_odometry_reset. */
+int tloam_closed_map_diff_configure(tloam_ctx* ctx, const tloam_closed_map_diff_config* cfg);
+typedef struct tloam_closed_map_diff_info {
+  int64_t n_points;         /* of the call's scan */
+  int64_t n_invalid, n_surface, n_occupied, n_new;   /* its labels */
+  int64_t rays;             /* = n_points */
+  int64_t skipped_rays;
+  int64_t steps;            /* cells visited by the call's rays */
+  int64_t tested;           /* ... of them occupied */
+  int64_t through;          /* the sum of the stored `through` */
+  int64_t voxels_through;   /* voxels with through > 0 */
+  int64_t voxels_hit;       /* voxels with hits > 0 */
+  int64_t scans;            /* scans that have gone into the stored counts */
+  int32_t launches;         /* kernel launches of the call: the same for every input with equal prepared / accumulate */
+  int32_t prepared;         /* 1: the call rebuilt the cached voxel records (one more launch) */
+  int32_t cleared;          /* 1: the call cleared the counts first (no TLOAM_DIFF_ACCUMULATE) */
+  int32_t reserved0;
+} tloam_closed_map_diff_info;
+/* Of the last diff; zero when there are no counts. */
+int tloam_closed_map_get_diff_info(tloam_ctx* ctx, tloam_closed_map_diff_info* info);
+/* Diffs points_aos (n points, sensor frame) at pose_colmajor (a rigid transform, checked as the localiser's prior).  labels [n]
+ * (uint8) and ids [n] may be NULL.  TLOAM_E_NOT_READY without a built closed map with surfels, or with carve_gate set on a map
+ * that is not carved; TLOAM_E_INVALID for n == 0, a NULL scan or pose, unknown flags, a pose that is not a rigid transform.  A
+ * refused call leaves everything as it was.  One upload of the scan, a fixed set of launches, one wait. */
+int tloam_closed_map_diff(tloam_ctx* ctx, const double* points_aos, size_t n, const double* pose_colmajor, int flags,
+                          uint8_t* labels_or_null, int32_t* ids_or_null, tloam_closed_map_diff_info* info_or_null);
+/* through and hits of voxels [first, first + count) in id order (either may be NULL).  TLOAM_E_NOT_READY without counts. */
+int tloam_closed_map_read_diff(tloam_ctx* ctx, size_t first, size_t count, int64_t* through, int64_t* hits);
+/* tloam_closed_map_read_carved's rule (the box; lo and hi both NULL: the whole map), order and capacity convention, keeping
+ * exactly the voxels with through >= min_through && (double) through > gone_ratio * (double) hits.  counts: N.  Any output may
+ * be NULL.  TLOAM_E_NOT_READY without counts. */
+int tloam_closed_map_read_gone(tloam_ctx* ctx, const double* lo_or_null, const double* hi_or_null, int64_t min_through,
+                               double gone_ratio, size_t capacity, size_t* n, double* centroids_aos, int64_t* counts,
+                               int64_t* through, int64_t* hits);
+/* Every diff call on a context with nranks > 1: TLOAM_E_INVALID. */
+
 /* ---- the closed map's snapshot: a built closed map out of a context and into a fresh one (additive to ABI 8) ------
  * A memory blob; the library opens no files.  It holds, exactly, everything a context needs to answer every read of the closed
  * map and every localisation in it with the bytes of the context that saved: the place, loop, closed map, carve and surfel

@@ -38,32 +38,14 @@ int loc_check(const tloam_ctx* c, const double* points_aos, size_t n, const doub
 // per-point outputs are asked for
 int loc_begin(tloam_ctx* c, const double* points_aos, size_t n, bool ids, bool res, int* prepared, size_t B = 1) {
   CmapState& M = c->cmap;
-  const size_t nv = (size_t)M.info.n_voxels, cap = std::max<size_t>(M.rows.cap, 1);
   HIPC(c, hipSetDevice(c->device));
-  HIPC(c, M.loc_rec.reserve(cap)); HIPC(c, M.loc_pts.reserve(3 * n));
+  HIPC(c, M.loc_pts.reserve(3 * n));
   HIPC(c, M.loc_partial.reserve(B * (size_t)loc_blocks((long long)n) * kLocRow));
   HIPC(c, M.loc_state.reserve(B)); HIPC(c, M.loc_log.reserve(B * kLocMaxIterations));
   if (ids) HIPC(c, M.loc_ids.reserve(n));
   if (res) HIPC(c, M.loc_res.reserve(n));
   HIPC(c, hipMemcpyAsync(M.loc_pts.p, points_aos, sizeof(double) * 3 * n, hipMemcpyHostToDevice, c->stream));
-  *prepared = 0;
-  if (!M.loc_ready) {
-    LocPrepArgs A;
-    memset(&A, 0, sizeof(A));
-    A.map = M.rows.view();
-    A.sums = M.surfel_sums.p; A.normal = M.surfel_nrm.p; A.eval = M.surfel_ev.p;
-    A.nv = (long long)nv;
-    A.voxel = M.cfg.voxel;
-    for (int a = 0; a < 3; ++a) A.origin[a] = M.cfg.origin[a];
-    A.min_points = M.surfel_cfg.min_points;
-    A.max_sigma2 = M.loc_cfg.max_sigma * M.loc_cfg.max_sigma;
-    A.min_planarity = M.loc_cfg.min_planarity;
-    A.rec = M.loc_rec.p;
-    launch_loc_prepare(A, c->stream);
-    HIPC(c, hipGetLastError());
-    *prepared = 1;
-  }
-  return TLOAM_OK;
+  return loc_records_prepare(c, prepared);
 }
 
 LocSweepArgs sweep_args(const CmapState& M, size_t n, int* ids, double* res) {
@@ -191,6 +173,30 @@ bool reloc_config_ok(const tloam_closed_map_relocalise_config& w) {
 }
 
 }  // namespace
+
+namespace tlh {
+int loc_records_prepare(tloam_ctx* c, int* prepared) {
+  CmapState& M = c->cmap;
+  HIPC(c, M.loc_rec.reserve(std::max<size_t>(M.rows.cap, 1)));
+  *prepared = 0;
+  if (M.loc_ready) return TLOAM_OK;
+  LocPrepArgs A;
+  memset(&A, 0, sizeof(A));
+  A.map = M.rows.view();
+  A.sums = M.surfel_sums.p; A.normal = M.surfel_nrm.p; A.eval = M.surfel_ev.p;
+  A.nv = (long long)M.info.n_voxels;
+  A.voxel = M.cfg.voxel;
+  for (int a = 0; a < 3; ++a) A.origin[a] = M.cfg.origin[a];
+  A.min_points = M.surfel_cfg.min_points;
+  A.max_sigma2 = M.loc_cfg.max_sigma * M.loc_cfg.max_sigma;
+  A.min_planarity = M.loc_cfg.min_planarity;
+  A.rec = M.loc_rec.p;
+  launch_loc_prepare(A, c->stream);
+  HIPC(c, hipGetLastError());
+  *prepared = 1;
+  return TLOAM_OK;
+}
+}  // namespace tlh
 
 extern "C" {
 

@@ -3,14 +3,15 @@
 //
 // Launches of a carve, the same three for any number of keyframes, spans and rays (no host synchronisation between them):
 //   k_carve_clear   grid x 256   zeroes M and the control words
-//   k_carve_rays    grid x 256   per ray: its span from its global index, transform (span_point), the walk through the grid's
-//                                cells, every visited cell looked up in the closed map's slot table (id_table_find), the miss test
-//                                against an occupied cell's centroid, an int64 atomic add on its M; the ray's counters summed
-//                                over the wave by shuffles, one atomic per counter and wave
+//   k_carve_rays    grid x 256   per ray: its span from its global index, transform (span_point), then tl_voxel.hpp's ray_walk:
+//                                the walk through the grid's cells, every visited cell looked up in the closed map's slot table
+//                                (id_table_find), the miss test against an occupied cell's centroid; a miss is an int64 atomic
+//                                add on the voxel's M; the ray's counters summed over the wave by shuffles, one atomic per counter
+//                                and wave
 //   k_carve_count   grid x 256   per voxel: M > 0 counted by ballot, one atomic per wave
 // The carved read is k_carve_box: the box read's one body (tl_voxel.hpp: voxel_box_body), with the voxels seen through left out.
 //
-// Compiled with -ffp-contract=off.  The operation order of a ray (tests/closed_map_carve_np.py restates it), per axis a:
+// Compiled with -ffp-contract=off.  The operation order of a ray (ray_walk; tests/closed_map_carve_np.py restates it), per axis a:
 //   O_a = P[12 + a],  E = map_transform_point(P, p),  D_a = E_a - O_a,  DD = (Dx*Dx + Dy*Dy) + Dz*Dz,  L = sqrt(DD)
 //   s0_a = (O_a - o_a) / v,  s1_a = (E_a - o_a) / v,  c_a = floor(s0_a),  ce_a = floor(s1_a),  d_a = s1_a - s0_a
 //   tMax_a = ((c_a + 1) - s0_a) / d_a  (d_a > 0),  (c_a - s0_a) / d_a  (d_a < 0),  +inf  (d_a == 0 or c_a == ce_a)
@@ -26,12 +27,6 @@
 namespace tl {
 namespace {
 
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(256) void k_carve_clear(CarveWork W) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
   for (size_t t = i; t < (size_t)W.nv; t += stride) W.miss[t] = 0ull;
@@ -42,70 +37,15 @@ __global__ __launch_bounds__(256) void k_carve_rays(CarveWork W) {
   __shared__ int s_span[2];
   block_spans(W.in, s_span);
   const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
-  const double kInf = __builtin_huge_val(), kLimit = (double)(1ll << kVmapBits);
   unsigned long long skipped = 0ull, steps = 0ull, tested = 0ull, misses = 0ull;
   if (g < W.in.n) {
     int kf;
     const double* P;
     double E[3];
     span_point(W.in, g, s_span[0], s_span[1], &kf, &P, E);
-    const double Ox = P[12], Oy = P[13], Oz = P[14], Ex = E[0], Ey = E[1], Ez = E[2];
-    const double Dx = Ex - Ox, Dy = Ey - Oy, Dz = Ez - Oz;
-    const double DD = (Dx * Dx + Dy * Dy) + Dz * Dz;
-    const double L = sqrt(DD);
-    const double s0x = (Ox - W.origin[0]) / W.voxel, s0y = (Oy - W.origin[1]) / W.voxel, s0z = (Oz - W.origin[2]) / W.voxel;
-    const double s1x = (Ex - W.origin[0]) / W.voxel, s1y = (Ey - W.origin[1]) / W.voxel, s1z = (Ez - W.origin[2]) / W.voxel;
-    const double fx = floor(s0x), fy = floor(s0y), fz = floor(s0z), gx = floor(s1x), gy = floor(s1y), gz = floor(s1z);
-    bool ok = __builtin_isfinite(Ex) && __builtin_isfinite(Ey) && __builtin_isfinite(Ez);
-    ok = ok && !(L > W.max_range) && !(L == 0.0);
-    ok = ok && fabs(fx) < kLimit && fabs(fy) < kLimit && fabs(fz) < kLimit && fabs(gx) < kLimit && fabs(gy) < kLimit &&
-         fabs(gz) < kLimit;
-    if (!ok) {
-      skipped = 1ull;
-    } else {
-      int cx = (int)fx, cy = (int)fy, cz = (int)fz;
-      const int ex = (int)gx, ey = (int)gy, ez = (int)gz;
-      const double dx = s1x - s0x, dy = s1y - s0y, dz = s1z - s0z;
-      const int stx = dx > 0.0 ? 1 : dx < 0.0 ? -1 : 0, sty = dy > 0.0 ? 1 : dy < 0.0 ? -1 : 0, stz = dz > 0.0 ? 1 : dz < 0.0 ? -1 : 0;
-      double tx = cx == ex ? kInf : dx > 0.0 ? ((fx + 1.0) - s0x) / dx : dx < 0.0 ? (fx - s0x) / dx : kInf;
-      double ty = cy == ey ? kInf : dy > 0.0 ? ((fy + 1.0) - s0y) / dy : dy < 0.0 ? (fy - s0y) / dy : kInf;
-      double tz = cz == ez ? kInf : dz > 0.0 ? ((fz + 1.0) - s0z) / dz : dz < 0.0 ? (fz - s0z) / dz : kInf;
-      const double tdx = (double)stx / dx, tdy = (double)sty / dy, tdz = (double)stz / dz;   // (not read on an axis that never steps)
-      const int n = abs(ex - cx) + abs(ey - cy) + abs(ez - cz);
-      const double tlim = 1.0 - W.end_margin / L;
-      steps = (unsigned long long)n;
-      for (int k = 0; k < n; ++k) {
-        const unsigned long long key = (unsigned long long)(cx + (1 << kVmapBits)) |
-                                       ((unsigned long long)(cy + (1 << kVmapBits)) << 21) |
-                                       ((unsigned long long)(cz + (1 << kVmapBits)) << 42);
-        const int id = id_table_find(W.map.ptab, W.map.pmask, W.map.pkey, key);
-        if (id >= 0) {
-          tested++;
-          const long long N = W.map.pn[id];
-          const double ux = centroid(W.origin[0], W.voxel, cx, W.map.pqx[id], N) - Ox;
-          const double uy = centroid(W.origin[1], W.voxel, cy, W.map.pqy[id], N) - Oy;
-          const double uz = centroid(W.origin[2], W.voxel, cz, W.map.pqz[id], N) - Oz;
-          const double tt = ((ux * Dx + uy * Dy) + uz * Dz) / DD;
-          const double wx = ux - tt * Dx, wy = uy - tt * Dy, wz = uz - tt * Dz;
-          if (0.0 <= tt && tt < tlim && (wx * wx + wy * wy) + wz * wz <= W.radius2) {
-            misses++;
-            atomicAdd(&W.miss[id], 1ull);
-          }
-        }
-        const bool y = ty < tx;
-        const bool z = tz < (y ? ty : tx);
-        if (z) {
-          cz += stz;
-          tz = cz == ez ? kInf : tz + tdz;
-        } else if (y) {
-          cy += sty;
-          ty = cy == ey ? kInf : ty + tdy;
-        } else {
-          cx += stx;
-          tx = cx == ex ? kInf : tx + tdx;
-        }
-      }
-    }
+    const RayGrid G{W.voxel, {W.origin[0], W.origin[1], W.origin[2]}, W.max_range, W.end_margin, W.radius2};
+    ray_walk(G, W.map, P[12], P[13], P[14], E[0], E[1], E[2], &skipped, &steps, &tested, &misses,
+             [&](int id) { atomicAdd(&W.miss[id], 1ull); });
   }
   skipped = wave_sum(skipped); steps = wave_sum(steps); tested = wave_sum(tested); misses = wave_sum(misses);
   if ((threadIdx.x & 63) == 0) {

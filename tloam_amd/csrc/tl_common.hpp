@@ -806,6 +806,44 @@ struct RelocPriorArgs {
 };
 void launch_reloc_priors(const RelocPriorArgs& A, hipStream_t s);
 
+// ---- a scan diffed against the closed map (tl_diff.hip): a label per point from the localiser's voxel
+// records, and per voxel the rays of the scan that passed through it (`through`) and the returns that fell in it (`hits`).
+// Nothing of the closed map, the carve or the surfels is written: the counts are arrays of their own, in id order
+constexpr int kDiffCtl = 16;    // control words: [0..3] the label counts, [4] skipped rays, [5] steps, [6] tested, [7] the sum of
+                                // through, [8] voxels with through > 0, [9] voxels with hits > 0
+struct DiffWork {
+  const double* pts;          // the scan, AoS, sensor frame
+  long long n;
+  double M[16];               // the pose, column-major, as it stands
+  double voxel, origin[3];
+  double max_range, end_margin, radius2;   // the rays': radius2 = radius * radius
+  double plane_tol, near2;    // the labels': near2 = near * near
+  long long min_miss;         // the carve gate (when `gate`): a voxel with Mv >= min_miss && (double) Mv > miss_ratio * (double) N
+  double miss_ratio;          // explains no point
+  int gate;
+  int reserved0;
+  VmapTableView map;          // the closed map
+  long long nv;               // its voxels
+  const LocRecord* rec;       // [nv] the localiser's records
+  const long long* miss;      // [nv] the carve's M (read when `gate`)
+  unsigned long long* through;   // [nv]
+  unsigned long long* hits;      // [nv]
+  unsigned char* labels;      // [n]
+  int* ids;                   // [n] or null
+  unsigned long long* ctl;    // [kDiffCtl], zero before the launches
+};
+// (clear |) points | rays | count: no host synchronisation; returns the launches it made (the same for every size)
+int launch_diff(const DiffWork& W, bool clear, hipStream_t s);
+struct DiffReadArgs {
+  VmapReadArgs rows;          // the closed map's rows, the box (when `boxed`), min_count, the outputs, look and ctl as k_vmap_box's
+  const long long *through, *hits;   // [count] in id order
+  long long min_through;
+  double gone_ratio;          // a voxel is kept when through >= min_through && (double) through > gone_ratio * (double) hits
+  long long *out_through, *out_hits;   // of the voxels kept (may be null)
+  int boxed;                  // 0: the whole map
+};
+void launch_diff_read(const DiffReadArgs& A, hipStream_t s);
+
 // ---- deskew of a scan under constant velocity (tl_deskew.hip) -------------
 struct DeskewArgs {
   const double* in;               // AoS xyz [3n]

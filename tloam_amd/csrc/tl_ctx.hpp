@@ -498,13 +498,30 @@ struct CmapState {
     surfel_info = tloam_closed_map_surfel_info{};
     drop_localise();
   }
-  void drop() {   // the closed map goes, and the carve's counts and the surfels with it; the configurations and storage stay
+  // the diff of a scan against the map (tl_api_diff.hip): its configuration, through and hits in id order
+  // beside the rows, the control words, the per-point outputs of the last call, what the last diff reports, the gone read's
+  // scratch.  The scan is uploaded where the localiser's is (loc_pts) and the labels read the localiser's records (loc_rec).  The
+  // counts belong to the closed map they were counted in and go with it; a carve or a surfel pass does not touch them
+  tloam_closed_map_diff_config diff_cfg = {60.0, 1.0, 0.25, 0.1, 0.5, 3, 1.0, 0, 0};   // tloam_closed_map_diff_default_config
+  DBuf<unsigned long long> diff_through, diff_hits, diff_ctl;
+  DBuf<unsigned char> diff_labels;
+  DBuf<int> diff_ids;
+  DBuf<unsigned char> rd_through, rd_hits;
+  bool diffed = false;             // a diff has succeeded since the last drop: there are counts
+  tloam_closed_map_diff_info diff_info{};
+  void drop_diff() {
+    diffed = false;
+    diff_info = tloam_closed_map_diff_info{};
+  }
+  void drop() {   // the closed map goes, and the carve's counts, the surfels and the diff's counts with it; the configurations
+                  // and storage stay
     built = false;
     detached = false;
     info = tloam_closed_map_info{};
     poses.clear();
     drop_carve();
     drop_surfels();
+    drop_diff();
   }
 };
 
@@ -1036,6 +1053,9 @@ bool loop_config_valid(const tloam_loop_config& cfg);               // tl_api_lo
 bool cmap_config_valid(const tloam_closed_map_config& cfg);         // tl_api_cmap.hip
 size_t cmap_default_reserve();
 bool carve_config_valid(const tloam_closed_map_carve_config& cfg);  // tl_api_carve.hip
+// tl_api_localise.hip: the localiser's voxel records {c, n, eligible} sized and, when they are stale, their rebuild enqueued
+// (*prepared = 1; k_loc_prepare).  The caller sets CmapState::loc_ready once its call has succeeded (the localiser, the diff)
+int loc_records_prepare(tloam_ctx* c, int* prepared);
 // tl_api_deskew.hip: the frame's deskew -- sized and its times uploaded after the scan's upload, launched after the segmentation's
 // (the refused-time flag read with the frame's first wait), committed when the frame ends
 int deskew_frame_upload(tloam_ctx* c, const double* t_sec, size_t n, tloam_odom_stats* st);

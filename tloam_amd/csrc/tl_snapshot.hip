@@ -19,12 +19,6 @@
 namespace tl {
 namespace {
 
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;   // (lane 0's is the wave's)
-}
-
 __device__ __forceinline__ unsigned long long snap_term(unsigned long long w, unsigned long long i) {
   return mix64(w + kSnapGolden * (i + 1ull));
 }

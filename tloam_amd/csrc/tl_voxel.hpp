@@ -1,9 +1,10 @@
 // tl_voxel.hpp -- what the device voxel grids share: the submap's down-sample (tl_submap.hip), the
 // global map (tl_map.hip), the merged voxel map (tl_vmap.hip), the closed map (tl_cmap.hip), its carve (tl_carve.hip), its
-// surfels (tl_surfel.hip) and the localiser (tl_localise.hip).  One definition each of the key hash, the two table inserts and
-// the slot table's lookup, of the block scans, of the single-pass look-back with its one bound, of the eight-word post to the
-// host, of the voxel map's key / q arithmetic, its row centroid and its run sums, of the compacting box read's body
-// (k_vmap_box, k_carve_box, k_surfel_box), of the surfel gate, and of the span table's search and its point; and of
+// surfels (tl_surfel.hip), the localiser (tl_localise.hip) and the diff (tl_diff.hip).  One definition each of the key hash,
+// the two table inserts and the slot table's lookup, of the wave's integer sum, of the block scans, of the single-pass
+// look-back with its one bound, of the eight-word post to the host, of the voxel map's key / q arithmetic, its row centroid
+// and its run sums, of the compacting box read's body (k_vmap_box, k_carve_box, k_surfel_box, k_diff_box), of the surfel gate,
+// of the span table's search and its point, and of a ray's walk through the grid (k_carve_rays, k_diff_rays); and of
 // PointCloud2::VoxelDownSample's arithmetic for the two units that restate it (the min bound's hand-over and finish, the voxel
 // key of a point, the leader's local sum, the blocks of an emit kernel the device holds at once).
 // Device code, and the launches' blocks_of and emit_resident_blocks.
@@ -61,6 +62,13 @@ __device__ __forceinline__ int id_table_find(const int* ptab, unsigned long long
     if (id < 0) return -1;
     if (pkey[id] == key) return id;
   }
+}
+
+// the sum of `v` over the wave's 64 lanes, in every lane (an integer sum: the order does not show)
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
 }
 
 // 256-thread blocks over n items; a launch that runs for nothing too asks for blocks_of(max(n, 1))
@@ -441,6 +449,78 @@ __device__ __forceinline__ void span_point(const SpanInput& in, long long g, int
   *kf = S.kf;
   *P = in.pose + 16 * (size_t)S.kf;
   map_transform_point(*P, x[0], x[1], x[2], &E[0], &E[1], &E[2]);
+}
+
+// ---- a ray through a voxel map's grid (the carve, tl_carve.hip; the diff, tl_diff.hip) ----
+// The ray from O to E: the skip rule, the walk through the grid's cells, every visited cell looked up in the map's slot table,
+// the miss test against an occupied cell's centroid.  tl_carve.hip's header states the operation order; the state is held in
+// named scalars (no run-time indexed array: no scratch).  on_miss(id) is what a miss does; *skipped, *steps, *tested, *misses
+// are set for the ray (a skipped ray: 1, 0, 0, 0).
+struct RayGrid {
+  double voxel, origin[3];
+  double max_range, end_margin, radius2;   // radius2 = radius * radius
+};
+template <class OnMiss>
+__device__ __forceinline__ void ray_walk(const RayGrid& W, const VmapTableView& map, double Ox, double Oy, double Oz, double Ex,
+                                         double Ey, double Ez, unsigned long long* skipped, unsigned long long* steps,
+                                         unsigned long long* tested, unsigned long long* misses, OnMiss on_miss) {
+  const double kInf = __builtin_huge_val(), kLimit = (double)(1ll << kVmapBits);
+  const double Dx = Ex - Ox, Dy = Ey - Oy, Dz = Ez - Oz;
+  const double DD = (Dx * Dx + Dy * Dy) + Dz * Dz;
+  const double L = sqrt(DD);
+  const double s0x = (Ox - W.origin[0]) / W.voxel, s0y = (Oy - W.origin[1]) / W.voxel, s0z = (Oz - W.origin[2]) / W.voxel;
+  const double s1x = (Ex - W.origin[0]) / W.voxel, s1y = (Ey - W.origin[1]) / W.voxel, s1z = (Ez - W.origin[2]) / W.voxel;
+  const double fx = floor(s0x), fy = floor(s0y), fz = floor(s0z), gx = floor(s1x), gy = floor(s1y), gz = floor(s1z);
+  bool ok = __builtin_isfinite(Ex) && __builtin_isfinite(Ey) && __builtin_isfinite(Ez);
+  ok = ok && !(L > W.max_range) && !(L == 0.0);
+  ok = ok && fabs(fx) < kLimit && fabs(fy) < kLimit && fabs(fz) < kLimit && fabs(gx) < kLimit && fabs(gy) < kLimit &&
+       fabs(gz) < kLimit;
+  if (!ok) {
+    *skipped = 1ull;
+    return;
+  }
+  int cx = (int)fx, cy = (int)fy, cz = (int)fz;
+  const int ex = (int)gx, ey = (int)gy, ez = (int)gz;
+  const double dx = s1x - s0x, dy = s1y - s0y, dz = s1z - s0z;
+  const int stx = dx > 0.0 ? 1 : dx < 0.0 ? -1 : 0, sty = dy > 0.0 ? 1 : dy < 0.0 ? -1 : 0, stz = dz > 0.0 ? 1 : dz < 0.0 ? -1 : 0;
+  double tx = cx == ex ? kInf : dx > 0.0 ? ((fx + 1.0) - s0x) / dx : dx < 0.0 ? (fx - s0x) / dx : kInf;
+  double ty = cy == ey ? kInf : dy > 0.0 ? ((fy + 1.0) - s0y) / dy : dy < 0.0 ? (fy - s0y) / dy : kInf;
+  double tz = cz == ez ? kInf : dz > 0.0 ? ((fz + 1.0) - s0z) / dz : dz < 0.0 ? (fz - s0z) / dz : kInf;
+  const double tdx = (double)stx / dx, tdy = (double)sty / dy, tdz = (double)stz / dz;   // (not read on an axis that never steps)
+  const int n = abs(ex - cx) + abs(ey - cy) + abs(ez - cz);
+  const double tlim = 1.0 - W.end_margin / L;
+  *steps = (unsigned long long)n;
+  for (int k = 0; k < n; ++k) {
+    const unsigned long long key = (unsigned long long)(cx + (1 << kVmapBits)) |
+                                   ((unsigned long long)(cy + (1 << kVmapBits)) << 21) |
+                                   ((unsigned long long)(cz + (1 << kVmapBits)) << 42);
+    const int id = id_table_find(map.ptab, map.pmask, map.pkey, key);
+    if (id >= 0) {
+      (*tested)++;
+      const long long N = map.pn[id];
+      const double ux = centroid(W.origin[0], W.voxel, cx, map.pqx[id], N) - Ox;
+      const double uy = centroid(W.origin[1], W.voxel, cy, map.pqy[id], N) - Oy;
+      const double uz = centroid(W.origin[2], W.voxel, cz, map.pqz[id], N) - Oz;
+      const double tt = ((ux * Dx + uy * Dy) + uz * Dz) / DD;
+      const double wx = ux - tt * Dx, wy = uy - tt * Dy, wz = uz - tt * Dz;
+      if (0.0 <= tt && tt < tlim && (wx * wx + wy * wy) + wz * wz <= W.radius2) {
+        (*misses)++;
+        on_miss(id);
+      }
+    }
+    const bool y = ty < tx;
+    const bool z = tz < (y ? ty : tx);
+    if (z) {
+      cz += stz;
+      tz = cz == ez ? kInf : tz + tdz;
+    } else if (y) {
+      cy += sty;
+      ty = cy == ey ? kInf : ty + tdy;
+    } else {
+      cx += stx;
+      tx = cx == ex ? kInf : tx + tdx;
+    }
+  }
 }
 
 }  // namespace tl

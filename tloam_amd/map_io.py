@@ -1,6 +1,6 @@
 """PCD export of the global map, of the merged voxel map (section 14), of the carved closed map
-(section 21) and of the closed map's surfels (section 22); and the closed map's snapshot as a file (section 25): the one
-form that loses nothing and is read back.
+(section 21), of the closed map's surfels (section 22) and of a diffed scan with its labels (section 26); and the closed map's
+snapshot as a file (section 25): the one form that loses nothing and is read back.
 
 The reference declares a `saveMap` service (srv/saveMap.srv) and never serves it; this is the file a user of the map needs.
 PCD v0.7 (the Point Cloud Library's format), fields `x y z`, each `F 8` (float64), so the device's doubles are written and
@@ -234,10 +234,8 @@ def write_closed_map_surfel_pcd(path: str, H, lo=None, hi=None, min_count=1, max
     return len(cnt)
 
 
-def save_closed_map(path: str, H, clouds: bool = False) -> int:
-    """Writes H's closed map snapshot (H.closed_map_save(clouds)) to `path` -> the bytes written.  Written to a temporary
-    name beside it and renamed, so a reader never sees half a file."""
-    blob = H.closed_map_save(clouds=clouds)
+def _write_renamed(path: str, blob: bytes) -> None:
+    """`blob` written to a temporary name beside `path` and renamed, so a reader never sees half a file."""
     tmp = f"{path}.tmp{os.getpid()}"
     try:
         with open(tmp, "wb") as fh:
@@ -248,6 +246,13 @@ def save_closed_map(path: str, H, clouds: bool = False) -> int:
     finally:
         if os.path.exists(tmp):
             os.remove(tmp)
+
+
+def save_closed_map(path: str, H, clouds: bool = False) -> int:
+    """Writes H's closed map snapshot (H.closed_map_save(clouds)) to `path` -> the bytes written.  Written to a temporary
+    name beside it and renamed, so a reader never sees half a file."""
+    blob = H.closed_map_save(clouds=clouds)
+    _write_renamed(path, blob)
     return len(blob)
 
 
@@ -255,3 +260,33 @@ def load_closed_map(path: str, H) -> dict:
     """Loads the snapshot file at `path` into H (H.closed_map_load) -> what it held."""
     with open(path, "rb") as fh:
         return H.closed_map_load(fh.read())
+
+
+# ---- a scan diffed against the closed map (DESIGN.md section 26): the scan in the map's frame with its labels
+_LABEL_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("label", "u1")])
+
+
+def write_labelled_scan_pcd(path: str, points_world, labels) -> int:
+    """Writes a diffed scan as one PCD v0.7, DATA binary: x y z float64 (`F 8`) in the map's frame (the scan under the pose it
+    was diffed at) and `label` uint8 (`U 1`: 0 INVALID, 1 SURFACE, 2 OCCUPIED, 3 NEW, H.closed_map_diff's) -> the points
+    written.  Written to a temporary name beside `path` and renamed."""
+    p = np.asarray(points_world, dtype="<f8").reshape(-1, 3)
+    k = np.asarray(labels, dtype="u1").reshape(-1)
+    if len(p) != len(k):
+        raise ValueError(f"{len(p)} points, {len(k)} labels")
+    n = len(p)
+    rec = np.empty(n, _LABEL_DTYPE)
+    rec["x"], rec["y"], rec["z"], rec["label"] = p[:, 0], p[:, 1], p[:, 2], k
+    header = ("# .PCD v0.7 - Point Cloud Data file format\n"
+              "VERSION 0.7\n"
+              "FIELDS x y z label\n"
+              "SIZE 8 8 8 1\n"
+              "TYPE F F F U\n"
+              "COUNT 1 1 1 1\n"
+              f"WIDTH {n}\n"
+              "HEIGHT 1\n"
+              "VIEWPOINT 0 0 0 1 0 0 0\n"
+              f"POINTS {n}\n"
+              "DATA binary\n")
+    _write_renamed(path, header.encode("ascii") + rec.tobytes())
+    return n

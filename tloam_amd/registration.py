@@ -206,6 +206,29 @@ class ClosedMapRelocaliseHypothesis(C.Structure):
 RELOCALISE_FOUND, RELOCALISE_NOT_FOUND = 0, 1
 
 
+class ClosedMapDiffConfig(C.Structure):
+    """tloam_closed_map_diff_config: the rays' longest range, end margin and radius (the carve's meaning), the residual within
+    which a point lies on a surfel, the distance within which a centroid explains it, and the carve gate (min_miss, miss_ratio,
+    carve_gate).  The defaults are choices, not measurements."""
+    _fields_ = [("max_range", C.c_double), ("end_margin", C.c_double), ("radius", C.c_double), ("plane_tol", C.c_double),
+                ("near", C.c_double), ("min_miss", C.c_int64), ("miss_ratio", C.c_double), ("carve_gate", C.c_int32),
+                ("reserved0", C.c_int32)]
+
+
+class ClosedMapDiffInfo(C.Structure):
+    """tloam_closed_map_diff_info."""
+    _fields_ = [("n_points", C.c_int64), ("n_invalid", C.c_int64), ("n_surface", C.c_int64), ("n_occupied", C.c_int64),
+                ("n_new", C.c_int64), ("rays", C.c_int64), ("skipped_rays", C.c_int64), ("steps", C.c_int64), ("tested", C.c_int64),
+                ("through", C.c_int64), ("voxels_through", C.c_int64), ("voxels_hit", C.c_int64), ("scans", C.c_int64),
+                ("launches", C.c_int32), ("prepared", C.c_int32), ("cleared", C.c_int32), ("reserved0", C.c_int32)]
+
+    as_dict = _int_fields
+
+
+DIFF_ACCUMULATE = 1   # TLOAM_DIFF_ACCUMULATE: the call adds to the stored counts
+DIFF_INVALID, DIFF_SURFACE, DIFF_OCCUPIED, DIFF_NEW = 0, 1, 2, 3
+
+
 SNAPSHOT_CLOUDS = 1   # TLOAM_SNAPSHOT_CLOUDS: the keyframes' eight clouds go into the snapshot too
 
 
@@ -570,6 +593,14 @@ def load_library():
         "tloam_closed_map_read_surfels": (C.c_int, [vp, sz, sz, dp, dp, C.POINTER(C.c_int64)]),
         "tloam_closed_map_read_surfels_box": (C.c_int, [vp, dp, dp, C.c_int64, C.c_double, C.c_double, sz, C.POINTER(sz), dp, dp, dp,
                                                         C.POINTER(C.c_int64)]),
+        "tloam_closed_map_diff_default_config": (None, [C.POINTER(ClosedMapDiffConfig)]),
+        "tloam_closed_map_diff_configure": (C.c_int, [vp, C.POINTER(ClosedMapDiffConfig)]),
+        "tloam_closed_map_get_diff_info": (C.c_int, [vp, C.POINTER(ClosedMapDiffInfo)]),
+        "tloam_closed_map_diff": (C.c_int, [vp, dp, sz, dp, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_int32),
+                                            C.POINTER(ClosedMapDiffInfo)]),
+        "tloam_closed_map_read_diff": (C.c_int, [vp, sz, sz, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+        "tloam_closed_map_read_gone": (C.c_int, [vp, dp, dp, C.c_int64, C.c_double, sz, C.POINTER(sz), dp, C.POINTER(C.c_int64),
+                                                 C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
         "tloam_closed_map_save_size": (C.c_int, [vp, C.c_int, C.POINTER(sz)]),
         "tloam_closed_map_save": (C.c_int, [vp, C.c_int, vp, sz, C.POINTER(sz)]),
         "tloam_closed_map_probe": (C.c_int, [vp, sz, C.POINTER(ClosedMapSnapshotInfo)]),
@@ -622,6 +653,8 @@ EXPORTED_SYMBOLS = (
     "tloam_closed_map_localise_log", "tloam_closed_map_linearise", "tloam_closed_map_localise_batch",
     "tloam_closed_map_localise_batch_log", "tloam_closed_map_relocalise_default_config", "tloam_closed_map_relocalise_configure",
     "tloam_closed_map_relocalise", "tloam_closed_map_relocalise_hypotheses",
+    "tloam_closed_map_diff_default_config", "tloam_closed_map_diff_configure", "tloam_closed_map_get_diff_info",
+    "tloam_closed_map_diff", "tloam_closed_map_read_diff", "tloam_closed_map_read_gone",
     "tloam_closed_map_save_size", "tloam_closed_map_save", "tloam_closed_map_probe", "tloam_closed_map_load",
     "tloam_rccl_unique_id", "tloam_comm_init_rccl",
     "tloam_comm_mailbox_export", "tloam_comm_init_mailbox",
@@ -1507,6 +1540,51 @@ class HipRegistration:
         return self._read_list(self.L.tloam_closed_map_relocalise_hypotheses, "tloam_closed_map_relocalise_hypotheses",
                                ClosedMapRelocaliseHypothesis, self.h)
 
+    # ---- a scan diffed against the closed map: new points, voxels seen through
+    def closed_map_diff_configure(self, cfg: ClosedMapDiffConfig | None = None, **over):
+        """the diff's configuration (default_closed_map_diff_config(**over) when cfg is None); drops the counts, not the closed
+        map.  Kept across odometry_reset; a refused configuration leaves the old one."""
+        cfg = cfg if cfg is not None else default_closed_map_diff_config(**over)
+        self._check(self.L.tloam_closed_map_diff_configure(self.h, C.byref(cfg)), "tloam_closed_map_diff_configure")
+
+    def closed_map_diff(self, points, pose, accumulate=False, want_ids=False):
+        """the scan `points` (n, 3; sensor frame) at `pose` (4 x 4) against the closed map -> (labels (n,) uint8: DIFF_INVALID,
+        DIFF_SURFACE, DIFF_OCCUPIED, DIFF_NEW; ids (n,) int32 of the voxel that explained each point, -1 for none, or None
+        without want_ids; info dict).  accumulate: the per-voxel counts are added to the stored ones instead of replacing them"""
+        pts = _aos(points)
+        labels = np.zeros(max(len(pts), 1), np.uint8)
+        ids = np.zeros(max(len(pts), 1), np.int32) if want_ids else None
+        info = ClosedMapDiffInfo()
+        self._check(self.L.tloam_closed_map_diff(self.h, _dp(pts), len(pts), _dp(_colmajor(pose)),
+                                                 DIFF_ACCUMULATE if accumulate else 0, labels.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                 _ip(ids), C.byref(info)), "tloam_closed_map_diff")
+        return labels[: len(pts)].copy(), (ids[: len(pts)].copy() if want_ids else None), info.as_dict()
+
+    def closed_map_diff_info(self) -> dict:
+        info = ClosedMapDiffInfo()
+        self._check(self.L.tloam_closed_map_get_diff_info(self.h, C.byref(info)), "tloam_closed_map_get_diff_info")
+        return info.as_dict()
+
+    def closed_map_diff_counts(self, first=0, count=None):
+        """through and hits of voxels [first, first + count) in id order -> ((m,) int64, (m,) int64); count None: to the end"""
+        first, m = _id_range(first, count, lambda: self.closed_map_info()["n_voxels"])
+        through, hits = np.zeros(max(m, 1), np.int64), np.zeros(max(m, 1), np.int64)
+        self._check(self.L.tloam_closed_map_read_diff(self.h, int(first), m, _lp(through), _lp(hits)), "tloam_closed_map_read_diff")
+        return through[:m].copy(), hits[:m].copy()
+
+    def closed_map_read_gone(self, lo=None, hi=None, min_through=3, gone_ratio=1.0):
+        """the voxels (lo and hi None: of the whole map; else with their centroid in [lo, hi]) the diffed scans saw through --
+        through >= min_through and through > gone_ratio * hits -- in id order ->
+        (centroids (m, 3), counts (m,), through (m,), hits (m,))"""
+        if (lo is None) != (hi is None):
+            raise ValueError("lo and hi go together")
+        if lo is not None:
+            lo = np.ascontiguousarray(lo, dtype=np.float64).reshape(3)
+            hi = np.ascontiguousarray(hi, dtype=np.float64).reshape(3)
+        head = (self.h, _dp(lo), _dp(hi), int(min_through), float(gone_ratio))
+        return self._read_box(self.L.tloam_closed_map_read_gone, "tloam_closed_map_read_gone", head,
+                              [(3, np.float64), (None, np.int64), (None, np.int64), (None, np.int64)])
+
     def fitness(self):
         f, r = C.c_double(0), C.c_double(0)
         rc = self.L.tloam_fitness(self.h, C.byref(f), C.byref(r))
@@ -1760,6 +1838,12 @@ def default_closed_map_carve_config(**over) -> ClosedMapCarveConfig:
     """tloam_closed_map_carve_default_config (max_range 60, end_margin 1, radius 0.25, ray_mask 0: the build's) with keyword
     overrides, e.g. max_range=20.0, radius=float("inf")"""
     return _strict_config(ClosedMapCarveConfig, "tloam_closed_map_carve_default_config", over)
+
+
+def default_closed_map_diff_config(**over) -> ClosedMapDiffConfig:
+    """tloam_closed_map_diff_default_config (max_range 60, end_margin 1, radius 0.25, plane_tol 0.1, near 0.5, min_miss 3,
+    miss_ratio 1, carve_gate 0) with keyword overrides, e.g. max_range=20.0, carve_gate=1"""
+    return _strict_config(ClosedMapDiffConfig, "tloam_closed_map_diff_default_config", over)
 
 
 def default_closed_map_relocalise_config(**over) -> ClosedMapRelocaliseConfig:
