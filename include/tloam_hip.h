@@ -164,6 +164,28 @@ typedef struct tloam_ctx_info {
 } tloam_ctx_info;
 int tloam_get_info(tloam_ctx* ctx, tloam_ctx_info* out);
 
+/* The search grids of the context's LAST grid build, whichever call made it (tloam_scan_match / tloam_sm_begin,
+ * tloam_set_target_frame, tloam_knn, the feature extraction) -- additive to ABI 8.  Read-only and host-side: nothing is
+ * launched or waited for.  A kind that was not built has ncell = n = 0; a build that failed before its first launch leaves the
+ * previous report.  Tests use it to know which build path they ran.
+ * (tloam_knn keeps the grid it builds -- points, cell tables -- on the context until tloam_destroy, so a batch of queries
+ * allocates nothing; a single call with a large radius over a large target pins that much memory.) */
+#define TLOAM_GRID_SCAN_NONE 0        /* no build yet, or a build without a single cell                                     */
+#define TLOAM_GRID_SCAN_SMALL 1       /* at most 16 Ki table entries: one block scans the 64-bit histogram                  */
+#define TLOAM_GRID_SCAN_TILES 2       /* the frame-size path: 32-bit histogram, tile scan, finalize + scatter               */
+#define TLOAM_GRID_SCAN_SINGLE_PASS 3 /* more than 1024 tiles, all blocks resident: one look-back launch, 64-bit histogram   */
+#define TLOAM_GRID_SCAN_GENERIC 4     /* anything else: the multi-launch 64-bit scan                                         */
+typedef struct tloam_grid_info {
+  int32_t dim[TLOAM_NUM_KINDS][3];
+  int32_t n[TLOAM_NUM_KINDS];      /* target points in the kind's grid                                                      */
+  int64_t ncell[TLOAM_NUM_KINDS];
+  double cell[TLOAM_NUM_KINDS];    /* edge of a cell: >= radius * (1 + 1e-6), grown by 1.25 per step while the kind's cells
+                                    * exceed 4e6 or -- in a context whose caps admit no direct set -- max(16 Ki, 32 per point) */
+  int32_t scan_path;               /* TLOAM_GRID_SCAN_*                                                                      */
+  int32_t table_elem_bytes;        /* size of a histogram / scan entry on that path: 4 or 8 (0: no build)                     */
+} tloam_grid_info;
+int tloam_get_grid_info(tloam_ctx* ctx, tloam_grid_info* out);
+
 /* ---- inputs: RegistrationInterface::setInputSource / setInputTarget -------------------
  * (registration.cpp:232-248).  The reference keeps shared_ptrs; here the cloud is copied
  * to HBM (AoS -> SoA on device).  In a sharded context (tloam_comm_*) every rank passes

@@ -178,6 +178,12 @@ int tloam_get_info(tloam_ctx* c, tloam_ctx_info* out) {
   return TLOAM_OK;
 }
 
+int tloam_get_grid_info(tloam_ctx* c, tloam_grid_info* out) {
+  if (!c || !out) return TLOAM_E_INVALID;
+  *out = c->grid_info;
+  return TLOAM_OK;
+}
+
 int tloam_debug_raise_fault(tloam_ctx* c, int which) {
   if (!c || which < 0 || which >= kFaultWords || !c->h_fault) return TLOAM_E_INVALID;
   __atomic_store_n(&c->h_fault[which], 1u, __ATOMIC_RELEASE);

@@ -159,8 +159,8 @@ size_t staged_size(const size_t counts[], int nparts) {   // doubles the pieces 
 }
 // The four search grids share one set of buffers (points and cell tables concatenated), so that every
 // phase of the build is ONE launch for all kinds: bbox -> (host: dims) -> histogram -> scan -> finalize ->
-// scatter.  `GridBuffers` owns the storage; ctx->grids is the set built by scanMatching, tloam_knn uses a
-// temporary one.
+// scatter.  `GridBuffers` owns the storage; ctx->grids is the set built by scanMatching, tloam_knn keeps
+// one of its own on the context (ctx->grids_knn: sized by the largest query radius so far, freed with the context).
 // radius[k] <= 0: kind not rebuilt (its view is left empty).  One host synchronisation (bounding boxes).
 // rows of launch_bbox_all ([kind][64][6]) -> (lo[3], hi[3]) per kind
 void reduce_box_rows(const double* box_rows, double boxes[kKinds][6]) {
@@ -174,6 +174,9 @@ void reduce_box_rows(const double* box_rows, double boxes[kKinds][6]) {
     }
   }
 }
+// cells per target point a kind's table may have before its cell grows (never below 16 Ki cells); measured at 16 / 32 / 64:
+// profiles/grid_tables_time.json
+constexpr double kGridCellsPerPoint = 32.0;
 // known_boxes: the clouds' bounds are already on the host (targets: taken at set_target) -- no launch, no wait
 int build_grids_over(tloam_ctx* c, GridBuffers& G, const double radius[kKinds], const CloudRef clouds[kKinds],
                      GridView out[kKinds], const double (*known_boxes)[6], FrameInitHook* frame) {
@@ -197,19 +200,28 @@ int build_grids_over(tloam_ctx* c, GridBuffers& G, const double radius[kKinds], 
     HIPC(c, hipStreamSynchronize(c->stream));
     reduce_box_rows(c->h_bbox, boxes);
   }
+  // (A DIRECT set keeps its rows in the search's own order, which follows the query tiles and with them the grids' dimensions:
+  //  a context whose caps admit one -- more rows than the quad search takes -- keeps the radius-sized cells, so that such a
+  //  frame's sums are added in the order they always were.  Compacted sets are in slot order whatever the grids look like.)
+  long long caps = 0;
+  for (int k = 0; k < kKinds; ++k) caps += std::max(0, kind_maxnum(c->cfg, k));
+  const bool sparse_ok = !direct_set_size((int)std::min<long long>(caps, INT32_MAX));
   long long cell_total = 0;
   for (int k = 0; k < kKinds; ++k) {
     const double* lo = boxes[k];
     const double* hi = boxes[k] + 3;
     GridView& g = out[k];
     memset(&g, 0, sizeof(g));
-    gs.cell_base[k] = cell_total;
     // (a cloud without a single finite point has no bounds -- the rows come back as they were initialised, lo > hi -- and
     //  nothing to search: no grid, like an empty cloud.  Sizing a cell table from such a box was a GPU memory fault until
     //  round 5: tests/tools/fuzz_call_order.py, a one-point cloud whose point is NaN)
     if (gs.n[k] > 0 && !(lo[0] <= hi[0] && lo[1] <= hi[1] && lo[2] <= hi[2])) gs.n[k] = 0;
     if (gs.n[k] == 0) { gs.ncell[k] = 0; gs.dim[k][0] = gs.dim[k][1] = gs.dim[k][2] = 1; gs.inv_cell[k] = 1.0; continue; }
     double cell = radius[k] * (1.0 + 1e-6);  // every target within `radius` of a query lies in its 27 cells
+    // ... and any larger cell does as well (the walk covers the ball, the search is exact k-NN): a table is bounded by 4e6
+    // cells, and a SPARSE kind's by kGridCellsPerPoint cells per point -- 1500 sphere targets over a street's volume were 42 %
+    // of a frame's table bytes.  The bound trades table bytes against candidates per query, never results.
+    const double sparse_cap = sparse_ok ? std::max(16384.0, kGridCellsPerPoint * (double)gs.n[k]) : 4.0e6;
     double dims[3];
     for (;;) {
       double cells = 1.0;
@@ -217,7 +229,7 @@ int build_grids_over(tloam_ctx* c, GridBuffers& G, const double radius[kKinds], 
         dims[a] = floor((hi[a] - lo[a]) / cell) + 1.0;
         cells *= dims[a];
       }
-      if (cells <= 4.0e6) break;  // dense cell table bound (u64 histogram + scan per frame)
+      if (cells <= 4.0e6 && cells <= sparse_cap) break;
       cell *= 1.25;
     }
     g.cell = cell;
@@ -236,27 +248,73 @@ int build_grids_over(tloam_ctx* c, GridBuffers& G, const double radius[kKinds], 
     cell_total += ncell;
   }
   const size_t nc = (size_t)std::max<long long>(cell_total, 1);
+  // Which scan the table takes decides its layout.  The frame-size path (32-bit tables) starts kind k's ncell + 1 entries on a
+  // multiple of 4, in the histogram, the scan and cell_start alike: 16-byte accesses, and the terminator falls out of the scan.
+  // Everywhere else the kinds' cells are packed (cell_base[k] = the cells in front) and cell_start carries one terminator per
+  // kind, so its entries of kind k sit k places further on.
+  long long n_tab = 0;   // entries of the padded table
+  for (int k = 0; k < kKinds; ++k) n_tab += (gs.ncell[k] + 1 + 3) & ~3ll;
+  const bool single_pass = !c->no_scan_1p && scan_1p_applies(nc + 1, c->device_cus);
+  const int tiles = (cell_total == 0 || single_pass) ? 0 : grid_table_tiles((size_t)n_tab);
+  {
+    long long at = 0;
+    for (int k = 0; k < kKinds; ++k) {
+      gs.cell_base[k] = at;
+      at += tiles > 0 ? ((gs.ncell[k] + 1 + 3) & ~3ll) : gs.ncell[k];
+    }
+  }
   HIPC(c, G.gp.reserve(std::max<size_t>(tgt_total, 1))); HIPC(c, G.cell_of_pt.reserve(std::max<size_t>(tgt_total, 1)));
   HIPC(c, G.rank_of_pt.reserve(tgt_total + 1));
   // The cell count follows the bounding boxes, which change from frame to frame: a table that has to grow does so with
   // room to spare (a re-allocation inside scanMatching costs ~0.7 ms -- three times the frame)
-  const size_t nc_res = (nc + 1 > G.cell_cnt.cap || nc + kKinds + 1 > G.cell_start.cap) ? 2 * nc + 64 : nc;
-  HIPC(c, G.cell_start.reserve(nc_res + kKinds + 1));
-  {
-    // the cell histogram is all-zero between builds (k_grid_finalize_all re-zeroes what a build used): only a
-    // (re)allocation has to be cleared
+  // The cell histogram of either width is all-zero between builds (the launch that scans it re-zeroes what a build used):
+  // only a (re)allocation has to be cleared
+  if (tiles > 0) {
+    const size_t nt = (size_t)n_tab;
+    const size_t nt_res = (nt > G.cell_cnt32.cap || nt > G.cell_start.cap) ? 2 * nt + 64 : nt;
+    HIPC(c, G.cell_start.reserve(nt_res));
+    const size_t before = G.cell_cnt32.cap;
+    HIPC(c, G.cell_cnt32.reserve(nt_res));
+    if (G.cell_cnt32.cap != before) HIPC(c, hipMemsetAsync(G.cell_cnt32.p, 0, G.cell_cnt32.cap * sizeof(unsigned), c->stream));
+    HIPC(c, G.cell_scan32.reserve(nt_res));
+    HIPC(c, G.totals32.reserve(1024));
+  } else {
+    const size_t nc_res = (nc + 1 > G.cell_cnt.cap || nc + kKinds + 1 > G.cell_start.cap) ? 2 * nc + 64 : nc;
+    HIPC(c, G.cell_start.reserve(nc_res + kKinds + 1));
     const size_t before = G.cell_cnt.cap;
     HIPC(c, G.cell_cnt.reserve(nc_res + 1));
     if (G.cell_cnt.cap != before)
       HIPC(c, hipMemsetAsync(G.cell_cnt.p, 0, G.cell_cnt.cap * sizeof(unsigned long long), c->stream));
+    if (single_pass) {
+      const size_t before1p = G.scan1p.cap;
+      HIPC(c, G.scan1p.reserve(scan_1p_ctl_elems(nc_res + 1)));
+      if (G.scan1p.cap != before1p) HIPC(c, hipMemsetAsync(G.scan1p.p, 0, G.scan1p.cap * sizeof(unsigned long long), c->stream));
+    } else {
+      HIPC(c, G.cell_scan.reserve(nc_res + 1));
+      HIPC(c, G.scan_tmp.reserve(scan_tmp_elems(nc_res + 1)));
+    }
   }
-  HIPC(c, G.cell_scan.reserve(nc_res + 1));
-  HIPC(c, G.scan_tmp.reserve(scan_tmp_elems(nc_res + 1)));
   for (int k = 0; k < kKinds; ++k) {
     out[k].gp = G.gp.p + gs.tgt_off[k];
-    out[k].cell_start = G.cell_start.p + gs.cell_base[k] + k;
+    out[k].cell_start = G.cell_start.p + gs.cell_base[k] + (tiles > 0 ? 0 : k);
   }
-  if (cell_total == 0) return TLOAM_OK;
+  tloam_grid_info I;   // (published once nothing in front of the build's first launch can fail any more)
+  {
+    memset(&I, 0, sizeof(I));
+    for (int k = 0; k < kKinds; ++k) {
+      if (gs.ncell[k] == 0) continue;
+      for (int a = 0; a < 3; ++a) I.dim[k][a] = gs.dim[k][a];
+      I.n[k] = gs.n[k];
+      I.ncell[k] = gs.ncell[k];
+      I.cell[k] = out[k].cell;
+    }
+    I.scan_path = cell_total == 0 ? TLOAM_GRID_SCAN_NONE
+                  : single_pass   ? TLOAM_GRID_SCAN_SINGLE_PASS
+                  : tiles > 0     ? TLOAM_GRID_SCAN_TILES
+                  : nc + 1 <= 16384 ? TLOAM_GRID_SCAN_SMALL : TLOAM_GRID_SCAN_GENERIC;
+    I.table_elem_bytes = cell_total == 0 ? 0 : tiles > 0 ? 4 : 8;
+  }
+  if (cell_total == 0) { c->grid_info = I; return TLOAM_OK; }
   if (frame) {  // the start of the scan_match rides on the first launch (the query-tile histogram is sized by the grids)
     const size_t ntiles = (size_t)build_tile_count(out, frame->fi.slot_off);
     HIPC(c, c->tile_cnt.reserve(ntiles + 1 > c->tile_cnt.cap ? 2 * ntiles + 64 : ntiles + 1));
@@ -264,16 +322,15 @@ int build_grids_over(tloam_ctx* c, GridBuffers& G, const double radius[kKinds], 
     frame->fi.n_tile_cnt = (int)ntiles + 1;
     frame->consumed = true;
   }
+  c->grid_info = I;
   const bool stamp = frame && c->hs_entry > 0.0;   // (TLOAM_HOST_STAMPS: when the frame's FIRST launch went out / had been issued)
   if (stamp) c->hs[5] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count() - c->hs_entry;
-  launch_grid_count_all(gs, G.cell_cnt.p, G.cell_of_pt.p, G.rank_of_pt.p, c->stream, frame);
+  if (tiles > 0) launch_grid_count_all(gs, G.cell_cnt32.p, G.cell_of_pt.p, G.rank_of_pt.p, c->stream, frame);
+  else launch_grid_count_all(gs, G.cell_cnt.p, G.cell_of_pt.p, G.rank_of_pt.p, c->stream, frame);
   if (stamp) c->hs[6] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count() - c->hs_entry;
-  if (!c->no_scan_1p && scan_1p_applies(nc + 1, c->device_cus)) {
+  if (single_pass) {
     // 1 M-class tables: count | scan + finalize in ONE single-pass launch | scatter (three launches and one pass over the table
     // less than tile scan + scan of the totals + add + finalize)
-    const size_t before = G.scan1p.cap;
-    HIPC(c, G.scan1p.reserve(scan_1p_ctl_elems(nc_res + 1)));
-    if (G.scan1p.cap != before) HIPC(c, hipMemsetAsync(G.scan1p.p, 0, G.scan1p.cap * sizeof(unsigned long long), c->stream));
     const QueryBinRide* qbin = nullptr;
     if (frame && frame->qbin) {
       // the query sort's buffers, sized exactly as the sort itself will ask for them (nothing may be re-allocated in between)
@@ -290,10 +347,10 @@ int build_grids_over(tloam_ctx* c, GridBuffers& G, const double radius[kKinds], 
                                          G.rank_of_pt.p, G.gp.p, c->stream, qbin, out);
     return TLOAM_OK;
   }
-  const int tiles = scan_tiles_only(G.cell_cnt.p, G.cell_scan.p, nc + 1, G.scan_tmp.p, c->stream);
   if (tiles > 0) {
-    launch_grid_finalize_scatter_all(gs, G.cell_scan.p, G.scan_tmp.p, tiles, G.cell_start.p, G.cell_cnt.p, G.cell_of_pt.p,
-                                     G.rank_of_pt.p, G.gp.p, c->stream);
+    launch_grid_scan_tiles(G.cell_cnt32.p, G.cell_scan32.p, (size_t)n_tab, G.totals32.p, c->stream);
+    launch_grid_finalize_scatter_all(gs, G.cell_scan32.p, G.totals32.p, tiles, n_tab, G.cell_start.p, G.cell_of_pt.p, G.rank_of_pt.p,
+                                     G.gp.p, c->stream);
   } else {
     launch_exclusive_scan_u64(G.cell_cnt.p, G.cell_scan.p, nc + 1, G.scan_tmp.p, c->stream);
     launch_grid_finalize_all(gs, G.cell_scan.p, G.cell_start.p, G.cell_cnt.p, c->stream);

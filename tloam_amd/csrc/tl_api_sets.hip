@@ -218,7 +218,7 @@ int tloam_knn(tloam_ctx* c, int kind, const double* q, size_t nq, double radius,
     return TLOAM_OK;
   }
   int rc;
-  GridBuffers tmp;  // a grid over the target currently set, sized for this radius; the scanMatching grids stay intact
+  GridBuffers& tmp = c->grids_knn;  // a grid over the target currently set, sized for this radius; the scanMatching grids stay intact
   GridView views[kKinds];
   {
     double radii[kKinds] = {0, 0, 0, 0};

@@ -258,7 +258,8 @@ struct GridSet {
   const double* tz[kKinds];
   int n[kKinds];
   int tgt_off[kKinds];          // offset of the kind's points in the concatenated point arrays
-  long long cell_base[kKinds];  // offset of the kind's cells in the concatenated cell arrays
+  long long cell_base[kKinds];  // offset of the kind's cells in the concatenated cell arrays (cell_start: + kind, except on the
+                                // frame-size path -- see launch_grid_finalize_scatter_all)
   long long ncell[kKinds];
   double org[kKinds][3];
   double inv_cell[kKinds];
@@ -367,17 +368,24 @@ __device__ __forceinline__ void frame_init_body(const FrameInit& fi, const Frame
 #endif
 void launch_frame_init(const FrameInit& fi, const FrameInitBufs& b, hipStream_t s);
 void launch_bbox_all(const GridSet& gs, double* out /*[4][64][6], device or pinned host*/, hipStream_t s);
-void launch_grid_count_all(const GridSet& gs, unsigned long long* cell_cnt, int* cell_of_pt, int* rank_of_pt,
-                           hipStream_t s, const FrameInitHook* frame = nullptr);
+// T = the histogram's element: unsigned on the frame-size path, unsigned long long where the u64 scans follow
+template <typename T>
+void launch_grid_count_all(const GridSet& gs, T* cell_cnt, int* cell_of_pt, int* rank_of_pt, hipStream_t s,
+                           const FrameInitHook* frame = nullptr);
 void launch_grid_finalize_all(const GridSet& gs, const unsigned long long* cell_scan, int* cell_start,
                               unsigned long long* cell_cnt /* re-zeroed */, hipStream_t s);
-// medium-size builds: tile-local scan only (returns the tile count, 0 = not applicable), then finalize + scatter in ONE
-// launch that adds the tiles' offsets itself -- three launches per build instead of five
+// medium-size scans: tile-local scan only (returns the tile count, 0 = not applicable), the consumer adds the tiles' offsets
+// itself
 int scan_tiles_only(const unsigned long long* in, unsigned long long* out, size_t n, unsigned long long* totals, hipStream_t s,
                     const int* gate = nullptr);
-void launch_grid_finalize_scatter_all(const GridSet& gs, const unsigned long long* cell_scan, const unsigned long long* totals,
-                                      int tiles, int* cell_start, unsigned long long* cell_cnt, const int* cell_of_pt,
-                                      const int* rank_of_pt, double4* gp, hipStream_t s);
+// The frame-size grid build (a table of more than 16 Ki entries and at most 1024 scan tiles, grid_table_tiles(n) > 0): 32-bit
+// histogram, tile-local scan that leaves the histogram empty again, then finalize + scatter in ONE launch -- three launches per
+// build.  The table's layout differs from the other paths': kind k's ncell + 1 entries start at cell_base[k], a MULTIPLE OF 4,
+// in the histogram, the scan and cell_start alike (n_tab = the padded total, a multiple of 4; totals: 1024 entries).
+int grid_table_tiles(size_t n_tab);
+void launch_grid_scan_tiles(unsigned* cell_cnt /* re-zeroed */, unsigned* cell_scan, size_t n_tab, unsigned* totals, hipStream_t s);
+void launch_grid_finalize_scatter_all(const GridSet& gs, const unsigned* cell_scan, const unsigned* totals, int tiles, long long n_tab,
+                                      int* cell_start, const int* cell_of_pt, const int* rank_of_pt, double4* gp, hipStream_t s);
 void launch_grid_scatter_all(const GridSet& gs, const int* cell_of_pt, const unsigned long long* cell_scan,
                              const int* rank_of_pt, double4* gp, hipStream_t s);
 // large tables (more than 1024 scan tiles: the 1 M-class frames): ONE single-pass launch scans the histogram, writes cell_start

@@ -192,7 +192,8 @@ struct FrameClouds {
 struct GridBuffers {
   DBuf<double4> gp;
   DBuf<int> cell_start, cell_of_pt, rank_of_pt;
-  DBuf<unsigned long long> cell_cnt, cell_scan, scan_tmp;
+  DBuf<unsigned long long> cell_cnt, cell_scan, scan_tmp;   // the 64-bit histogram (all-zero between builds), its scan, the scan's scratch
+  DBuf<unsigned> cell_cnt32, cell_scan32, totals32;          // the frame-size path's own: 32-bit histogram (all-zero between builds), tile-local scan, tile totals
   DBuf<unsigned long long> scan1p;   // control words of the single-pass scan (large tables), zero when allocated
   DBuf<double> bbox;
 };
@@ -566,6 +567,8 @@ struct tloam_ctx {
   DBuf<int> tile_of_slot, tile_fill;
   DBuf<double4> qrec;  // tile-sorted query records (x, y, z, slot)
   GridBuffers grids;  // the four search grids of the last scanMatching (shared buffers)
+  GridBuffers grids_knn;       // ... the grid of the last tloam_knn (its own radius; kept, so that a query batch allocates nothing)
+  tloam_grid_info grid_info = {};   // the last grid build of any of them (tloam_get_grid_info)
   GridBuffers grids_next;      // ... and the set built AHEAD, over targets just handed over (tloam_set_target_frame); swapped in by the next sm_begin
   tl::GridView gv_next[tl::kKinds];
   SlotView sv{};

@@ -57,48 +57,68 @@ constexpr int kScanTile = kScanThreads * kScanItems;   // 2048 elements per bloc
 constexpr int kScanPer = 4;                            // consecutive elements per lane within a row
 constexpr int kScanRowElems = 64 * kScanPer;           // 256 elements = 2 KiB per wave row
 constexpr int kScanRows = kScanTile / (kScanThreads / 64) / kScanRowElems;   // rows per wave (2)
+// tuning numbers of the frame-size grid build (profiles/grid_tables_time.json has what was measured beside them)
+constexpr int kGridFinCellsPerBlock = 4096;     // table entries per finalize block: four 16-byte accesses per lane
+constexpr int kGridScatterPtsPerBlock = 256;    // points of the largest kind per scatter block: one per lane
 
 typedef unsigned long long u64x2 __attribute__((ext_vector_type(2), aligned(8)));   // (8-byte aligned: any element of a u64 array)
+typedef unsigned u32x4 __attribute__((ext_vector_type(4), aligned(16)));              // (the 32-bit tables: every row starts on 16 bytes)
+// a lane's four consecutive elements of a row, in 16-byte accesses: two for u64, ONE for 32-bit counts -- what the CU's L1 is
+// asked for is accesses per lane, not bytes (64 eight-byte loads per thread of a 16 Ki tile were half of what the single-pass
+// scans waited for)
+__device__ __forceinline__ void scan_load4(const unsigned long long* __restrict__ p, unsigned long long (&a)[4]) {
+  const u64x2* __restrict__ q = reinterpret_cast<const u64x2*>(p);
+  const u64x2 lo = q[0], hi = q[1];
+  a[0] = lo.x; a[1] = lo.y; a[2] = hi.x; a[3] = hi.y;
+}
+__device__ __forceinline__ void scan_load4(const unsigned* __restrict__ p, unsigned (&a)[4]) {
+  const u32x4 v = *reinterpret_cast<const u32x4*>(p);
+  a[0] = v.x; a[1] = v.y; a[2] = v.z; a[3] = v.w;
+}
+__device__ __forceinline__ void scan_store4(unsigned long long* __restrict__ p, unsigned long long r0, unsigned long long r1,
+                                            unsigned long long r2, unsigned long long r3) {
+  u64x2* __restrict__ q = reinterpret_cast<u64x2*>(p);
+  q[0] = u64x2{r0, r1};
+  q[1] = u64x2{r2, r3};
+}
+__device__ __forceinline__ void scan_store4(unsigned* __restrict__ p, unsigned r0, unsigned r1, unsigned r2, unsigned r3) {
+  *reinterpret_cast<u32x4*>(p) = u32x4{r0, r1, r2, r3};
+}
 // Wave-level exclusive scan of ROWS x 256 consecutive elements starting at `wbase`: lane l holds the four
-// elements 4l .. 4l+3 of each row, so a wave instruction covers 2 KiB (16 cache lines) and one shuffle scan
+// elements 4l .. 4l+3 of each row, so a wave instruction covers 1-2 KiB (8-16 cache lines) and one shuffle scan
 // serves 256 elements.  The fully blocked layout (8-16 consecutive elements per thread) made every wave
 // instruction touch 32-64 different lines, serialised by the texture addresser: 11.9 us for a 9.4 k-element
 // scan.  Returns the wave total; out[row i, 4l + j] = ex[i] + a[i][0] + .. + a[i][j-1].
-template <int ROWS>
-__device__ __forceinline__ unsigned long long wave_scan_rows(const unsigned long long* __restrict__ in, size_t n,
-                                                             size_t wbase, int lane, unsigned long long (&ex)[ROWS],
-                                                             unsigned long long (&a)[ROWS][kScanPer]) {
-  static_assert(kScanPer == 4, "a lane's elements of a row are loaded as two 16-byte halves");
+// T: unsigned long long (flag scans, the single-pass count scans) or unsigned (the frame-size cell tables: a count never
+// exceeds 2^28 points and the four kinds of a frame share one 2^28 slot space, so every prefix fits 32 bits).
+template <int ROWS, typename T>
+__device__ __forceinline__ T wave_scan_rows(const T* __restrict__ in, size_t n, size_t wbase, int lane, T (&ex)[ROWS],
+                                            T (&a)[ROWS][kScanPer]) {
+  static_assert(kScanPer == 4, "a lane's elements of a row are loaded in 16-byte accesses");
   if (wbase + (size_t)ROWS * kScanRowElems <= n) {
-    // a wave whose rows all lie inside the array (every wave but the last): a lane's four elements as TWO 16-byte loads -- what the
-    // CU's L1 is asked for is accesses per lane, not bytes (64 eight-byte loads per thread of a 16 Ki tile were half of what the
-    // single-pass scans waited for)
+    // a wave whose rows all lie inside the array (every wave but the last)
 #pragma unroll
-    for (int i = 0; i < ROWS; ++i) {
-      const u64x2* __restrict__ p = reinterpret_cast<const u64x2*>(in + wbase + (size_t)i * kScanRowElems + (size_t)lane * kScanPer);
-      const u64x2 lo = p[0], hi = p[1];
-      a[i][0] = lo.x; a[i][1] = lo.y; a[i][2] = hi.x; a[i][3] = hi.y;
-    }
+    for (int i = 0; i < ROWS; ++i) scan_load4(in + wbase + (size_t)i * kScanRowElems + (size_t)lane * kScanPer, a[i]);
   } else {
 #pragma unroll
     for (int i = 0; i < ROWS; ++i)
 #pragma unroll
       for (int j = 0; j < kScanPer; ++j) {  // unconditional (clamped) loads: all in flight together
         const size_t idx = wbase + (size_t)i * kScanRowElems + (size_t)lane * kScanPer + j;
-        const unsigned long long x = in[idx < n ? idx : n - 1];
-        a[i][j] = idx < n ? x : 0ull;
+        const T x = in[idx < n ? idx : n - 1];
+        a[i][j] = idx < n ? x : T(0);
       }
   }
-  unsigned long long carry = 0;
+  T carry = 0;
 #pragma unroll
   for (int i = 0; i < ROWS; ++i) {
-    unsigned long long s = 0;
+    T s = 0;
 #pragma unroll
     for (int j = 0; j < kScanPer; ++j) s += a[i][j];
-    unsigned long long inc = s;
+    T inc = s;
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
-      const unsigned long long t = __shfl_up(inc, off, 64);
+      const T t = __shfl_up(inc, off, 64);
       if (lane >= off) inc += t;
     }
     ex[i] = carry + inc - s;
@@ -106,23 +126,20 @@ __device__ __forceinline__ unsigned long long wave_scan_rows(const unsigned long
   }
   return carry;
 }
-template <int ROWS>
-__device__ __forceinline__ void wave_store_rows(unsigned long long* __restrict__ out, size_t n, size_t wbase, int lane,
-                                                unsigned long long add, const unsigned long long (&ex)[ROWS],
-                                                const unsigned long long (&a)[ROWS][kScanPer]) {
-  if (wbase + (size_t)ROWS * kScanRowElems <= n) {   // (as the loads: two 16-byte stores per lane and row)
+template <int ROWS, typename T>
+__device__ __forceinline__ void wave_store_rows(T* __restrict__ out, size_t n, size_t wbase, int lane, T add, const T (&ex)[ROWS],
+                                                const T (&a)[ROWS][kScanPer]) {
+  if (wbase + (size_t)ROWS * kScanRowElems <= n) {   // (as the loads: 16-byte stores)
 #pragma unroll
     for (int i = 0; i < ROWS; ++i) {
-      const unsigned long long r0 = add + ex[i], r1 = r0 + a[i][0], r2 = r1 + a[i][1], r3 = r2 + a[i][2];
-      u64x2* __restrict__ p = reinterpret_cast<u64x2*>(out + wbase + (size_t)i * kScanRowElems + (size_t)lane * kScanPer);
-      p[0] = u64x2{r0, r1};
-      p[1] = u64x2{r2, r3};
+      const T r0 = add + ex[i], r1 = r0 + a[i][0], r2 = r1 + a[i][1], r3 = r2 + a[i][2];
+      scan_store4(out + wbase + (size_t)i * kScanRowElems + (size_t)lane * kScanPer, r0, r1, r2, r3);
     }
     return;
   }
 #pragma unroll
   for (int i = 0; i < ROWS; ++i) {
-    unsigned long long run = add + ex[i];
+    T run = add + ex[i];
 #pragma unroll
     for (int j = 0; j < kScanPer; ++j) {
       const size_t idx = wbase + (size_t)i * kScanRowElems + (size_t)lane * kScanPer + j;
@@ -131,23 +148,66 @@ __device__ __forceinline__ void wave_store_rows(unsigned long long* __restrict__
     }
   }
 }
+// the rows a wave has just scanned, left all-zero (a histogram emptied for the next build while its lines are in hand)
+template <int ROWS, typename T>
+__device__ __forceinline__ void wave_zero_rows(T* __restrict__ p, size_t n, size_t wbase, int lane) {
+  if (wbase + (size_t)ROWS * kScanRowElems <= n) {
+#pragma unroll
+    for (int i = 0; i < ROWS; ++i) scan_store4(p + wbase + (size_t)i * kScanRowElems + (size_t)lane * kScanPer, T(0), T(0), T(0), T(0));
+    return;
+  }
+#pragma unroll
+  for (int i = 0; i < ROWS; ++i)
+#pragma unroll
+    for (int j = 0; j < kScanPer; ++j) {
+      const size_t idx = wbase + (size_t)i * kScanRowElems + (size_t)lane * kScanPer + j;
+      if (idx < n) p[idx] = T(0);
+    }
+}
 
-__global__ __launch_bounds__(kScanThreads) void k_scan_tile(const unsigned long long* __restrict__ in,
-                                                            unsigned long long* __restrict__ out, size_t n,
-                                                            unsigned long long* __restrict__ tile_total,
-                                                            const int* __restrict__ gate) {
-  __shared__ unsigned long long wave_tot[kScanThreads / 64];
+// tile-local exclusive scans + the tiles' totals.  REZERO: the tile of `in` is left all-zero once it has been read -- the cell
+// histogram of a grid build, empty again for the next one (`in` is then written through and promises no aliasing).
+template <typename T, bool REZERO> struct ScanIn { typedef const T* __restrict__ type; };
+template <typename T> struct ScanIn<T, true> { typedef T* type; };
+template <typename T, bool REZERO>
+__global__ __launch_bounds__(kScanThreads) void k_scan_tile(typename ScanIn<T, REZERO>::type in, T* __restrict__ out, size_t n,
+                                                            T* __restrict__ tile_total, const int* __restrict__ gate) {
+  __shared__ T wave_tot[kScanThreads / 64];
   if (gate && *gate == 0) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const size_t wbase = (size_t)blockIdx.x * kScanTile + (size_t)wave * (kScanRows * kScanRowElems);
-  unsigned long long ex[kScanRows], a[kScanRows][kScanPer];
-  const unsigned long long tot = wave_scan_rows<kScanRows>(in, n, wbase, lane, ex, a);
+  T ex[kScanRows], a[kScanRows][kScanPer];
+  const T tot = wave_scan_rows<kScanRows>(in, n, wbase, lane, ex, a);
+  if constexpr (REZERO) wave_zero_rows<kScanRows>(in, n, wbase, lane);
   if (lane == 0) wave_tot[wave] = tot;
   __syncthreads();
-  unsigned long long wave_off = 0;
+  T wave_off = 0;
   for (int w = 0; w < wave; ++w) wave_off += wave_tot[w];
   wave_store_rows<kScanRows>(out, n, wbase, lane, wave_off, ex, a);
   if (threadIdx.x == kScanThreads - 1) tile_total[blockIdx.x] = wave_off + tot;
+}
+// exclusive prefix of (<= 1024) tile totals into LDS, by a block of 256 threads: 4 consecutive tiles per thread.  Ends with a
+// barrier: toff[] may be read on return.
+template <typename T>
+__device__ __forceinline__ void tile_offsets_to_lds(const T* __restrict__ totals, int tiles, T (&toff)[1024], T (&wtot)[4]) {
+  const int t0 = threadIdx.x * 4;
+  T v[4], run = 0;
+#pragma unroll
+  for (int u = 0; u < 4; ++u) { v[u] = (t0 + u < tiles) ? totals[t0 + u] : T(0); run += v[u]; }
+  T incl = run;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const T o = __shfl_up(incl, off, 64);
+    if (lane >= off) incl += o;
+  }
+  if (lane == 63) wtot[wave] = incl;
+  __syncthreads();
+  T pre = incl - run;
+  for (int w = 0; w < wave; ++w) pre += wtot[w];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) { toff[t0 + u] = pre; pre += v[u]; }
+  __syncthreads();
 }
 __global__ __launch_bounds__(kScanThreads) void k_scan_add(unsigned long long* __restrict__ out, size_t n,
                                                            const unsigned long long* __restrict__ tile_off,
@@ -227,7 +287,7 @@ void launch_exclusive_scan_u64(const unsigned long long* in, unsigned long long*
   }
   unsigned long long* totals = tmp;
   unsigned long long* totals_scan = tmp + tiles;
-  hipLaunchKernelGGL(k_scan_tile, dim3((unsigned)tiles), dim3(kScanThreads), 0, s, in, out, n, totals, gate);
+  hipLaunchKernelGGL((k_scan_tile<unsigned long long, false>), dim3((unsigned)tiles), dim3(kScanThreads), 0, s, in, out, n, totals, gate);
   if (tiles <= 1024) {
     hipLaunchKernelGGL(k_scan_add_direct, dim3((unsigned)tiles), dim3(kScanThreads), 0, s, out, n, totals, gate);
   } else {
@@ -418,13 +478,22 @@ void launch_scan_counts_1p(const unsigned long long* in, unsigned long long* out
 }
 
 // first half of the medium-size scan only: tile-local exclusive scans + per-tile totals (the consumer adds the tiles'
-// offsets itself, see k_grid_finalize_scatter_all).  Returns the number of tiles; 0 = not applicable (use the full scan).
+// offsets itself, see k_compact and k_grid_finalize_scatter_all).  Returns the number of tiles; 0 = not applicable (use the full scan).
+static int scan_tile_count(size_t n) {
+  const size_t tiles = (n + kScanTile - 1) / kScanTile;
+  return (n <= (size_t)kSmallTile || tiles > 1024) ? 0 : (int)tiles;
+}
 int scan_tiles_only(const unsigned long long* in, unsigned long long* out, size_t n, unsigned long long* totals, hipStream_t s,
                     const int* gate) {
-  const size_t tiles = (n + kScanTile - 1) / kScanTile;
-  if (n <= (size_t)kSmallTile || tiles > 1024) return 0;
-  hipLaunchKernelGGL(k_scan_tile, dim3((unsigned)tiles), dim3(kScanThreads), 0, s, in, out, n, totals, gate);
-  return (int)tiles;
+  const int tiles = scan_tile_count(n);
+  if (tiles > 0)
+    hipLaunchKernelGGL((k_scan_tile<unsigned long long, false>), dim3((unsigned)tiles), dim3(kScanThreads), 0, s, in, out, n, totals, gate);
+  return tiles;
+}
+int grid_table_tiles(size_t n) { return scan_tile_count(n); }
+void launch_grid_scan_tiles(unsigned* cell_cnt, unsigned* cell_scan, size_t n, unsigned* totals, hipStream_t s) {
+  hipLaunchKernelGGL((k_scan_tile<unsigned, true>), dim3((unsigned)scan_tile_count(n)), dim3(kScanThreads), 0, s, cell_cnt, cell_scan, n,
+                     totals, (const int*)nullptr);
 }
 
 // ================================================================================================
@@ -522,7 +591,9 @@ void launch_bbox_all(const GridSet& gs, double* out, hipStream_t s) {
 
 
 // (y == kKinds: the rows of blocks that carry the start of the scan_match, see FrameInitHook)
-__global__ __launch_bounds__(256) void k_grid_count_all(GridSet gs, unsigned long long* __restrict__ cell_cnt,
+// T: the histogram's element (unsigned on the frame-size path, unsigned long long where the u64 scans follow)
+template <typename T>
+__global__ __launch_bounds__(256) void k_grid_count_all(GridSet gs, T* __restrict__ cell_cnt,
                                                         int* __restrict__ cell_of_pt, int* __restrict__ rank_of_pt,
                                                         FrameInit fi, FrameInitBufs fb) {
   const int k = blockIdx.y;
@@ -538,7 +609,7 @@ __global__ __launch_bounds__(256) void k_grid_count_all(GridSet gs, unsigned lon
     const int c = (cz * gs.dim[k][1] + cy) * gs.dim[k][0] + cx;
     cell_of_pt[gs.tgt_off[k] + i] = c;
     // the one atomic of the build: the histogram count doubles as the point's rank inside its cell
-    rank_of_pt[gs.tgt_off[k] + i] = (int)atomicAdd(&cell_cnt[gs.cell_base[k] + c], 1ull);
+    rank_of_pt[gs.tgt_off[k] + i] = (int)atomicAdd(&cell_cnt[gs.cell_base[k] + c], T(1));
   }
 }
 static int max_n(const GridSet& gs) {
@@ -546,8 +617,8 @@ static int max_n(const GridSet& gs) {
   for (int k = 0; k < kKinds; ++k) m = std::max(m, gs.n[k]);
   return m;
 }
-void launch_grid_count_all(const GridSet& gs, unsigned long long* cell_cnt, int* cell_of_pt, int* rank_of_pt,
-                           hipStream_t s, const FrameInitHook* frame) {
+template <typename T>
+void launch_grid_count_all(const GridSet& gs, T* cell_cnt, int* cell_of_pt, int* rank_of_pt, hipStream_t s, const FrameInitHook* frame) {
   int blocks = (max_n(gs) + 255) / 256;
   if (blocks > 4096) blocks = 4096;   // (1 M points: one point per thread -- every atomic / scattered store of the pass in flight at once)
   FrameInit fi;
@@ -555,9 +626,11 @@ void launch_grid_count_all(const GridSet& gs, unsigned long long* cell_cnt, int*
   memset(&fi, 0, sizeof(fi));
   memset(&fb, 0, sizeof(fb));
   if (frame) { fi = frame->fi; fb = frame->b; }
-  hipLaunchKernelGGL(k_grid_count_all, dim3(blocks, kKinds + (frame ? 1 : 0)), dim3(256), 0, s, gs, cell_cnt, cell_of_pt,
+  hipLaunchKernelGGL(k_grid_count_all<T>, dim3(blocks, kKinds + (frame ? 1 : 0)), dim3(256), 0, s, gs, cell_cnt, cell_of_pt,
                      rank_of_pt, fi, fb);
 }
+template void launch_grid_count_all<unsigned>(const GridSet&, unsigned*, int*, int*, hipStream_t, const FrameInitHook*);
+template void launch_grid_count_all<unsigned long long>(const GridSet&, unsigned long long*, int*, int*, hipStream_t, const FrameInitHook*);
 // cell_start of kind k lives at cell_start[cell_base[k] + k ...] (ncell + 1 entries per kind), relative to the
 // kind's own point block
 __global__ void k_grid_finalize_all(GridSet gs, const unsigned long long* __restrict__ cell_scan,
@@ -593,67 +666,57 @@ __global__ void k_grid_scatter_all(GridSet gs, const int* __restrict__ cell_of_p
         double4{gs.tx[k][i], gs.ty[k][i], gs.tz[k][i], __longlong_as_double((long long)i)};
   }
 }
-// finalize + scatter in ONE launch, straight from the TILE-LOCAL scan: every block first turns the (<= 1024) tile totals
-// into tile offsets in LDS (what k_scan_add_direct would add in place in a launch of its own), then blocks
-// [0, fin_blocks) of every kind write the cell table and re-zero the histogram, the others scatter the points.
-__global__ __launch_bounds__(256) void k_grid_finalize_scatter_all(GridSet gs, const unsigned long long* __restrict__ cell_scan,
-                                                                   const unsigned long long* __restrict__ totals, int tiles,
-                                                                   int fin_blocks, int* __restrict__ cell_start,
-                                                                   unsigned long long* __restrict__ cell_cnt,
+// finalize + scatter in ONE launch, straight from the TILE-LOCAL 32-bit scan (the frame-size path).  Every block first turns
+// the (<= 1024) tile totals into tile offsets in LDS (what k_scan_add_direct would add in place in a launch of its own); then
+// blocks [0, fin_blocks) write the cell table, the others scatter the points.  (The histogram is empty again already: the tile
+// scan re-zeroed the lines it had in hand -- doing it here instead measured the same.)
+// Table layout of this path (build_grids_over): kind k's ncell + 1 entries start at cell_base[k], a multiple of 4, in the
+// histogram, the scan AND cell_start alike -- the slot after a kind's last cell counts nothing, so its scanned value is the
+// kind's terminator, and a lane's four consecutive entries are one aligned 16-byte access that lies inside one kind and one
+// tile.  A kind's first scanned value is the number of points COUNTED in front of it, `first.v[k]`: the prefix of gs.n, not
+// tgt_off -- a kind dropped for want of a finite point keeps its place in the point arrays and counts nothing.  The table is
+// strided over by a few hundred blocks, so the prologue is paid that often and not once per 256 cells.
+struct GridFirst { unsigned v[kKinds]; };
+__global__ __launch_bounds__(256) void k_grid_finalize_scatter_all(GridSet gs, GridFirst first, const unsigned* __restrict__ cell_scan,
+                                                                   const unsigned* __restrict__ totals, int tiles, long long n_tab,
+                                                                   int fin_blocks, int sc_blocks, int* __restrict__ cell_start,
                                                                    const int* __restrict__ cell_of_pt,
                                                                    const int* __restrict__ rank_of_pt, double4* __restrict__ gp) {
-  __shared__ unsigned long long toff[1024];
-  __shared__ unsigned long long wtot[4];
-  {  // exclusive prefix of the tile totals: 4 consecutive tiles per thread
-    const int t0 = threadIdx.x * 4;
-    unsigned long long v[4], run = 0ull;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) { v[u] = (t0 + u < tiles) ? totals[t0 + u] : 0ull; run += v[u]; }
-    unsigned long long incl = run;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const unsigned long long o = __shfl_up(incl, off, 64);
-      if (lane >= off) incl += o;
-    }
-    if (lane == 63) wtot[wave] = incl;
-    __syncthreads();
-    unsigned long long pre = incl - run;
-    for (int w = 0; w < wave; ++w) pre += wtot[w];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) { toff[t0 + u] = pre; pre += v[u]; }
-    __syncthreads();
-  }
-  const int k = blockIdx.y;
-  const long long ncell = gs.ncell[k], base = gs.cell_base[k];
-  const unsigned long long first = cell_scan[base] + toff[base / kScanTile];
+  __shared__ unsigned toff[1024];
+  __shared__ unsigned wtot[4];
+  tile_offsets_to_lds(totals, tiles, toff, wtot);
   if ((int)blockIdx.x < fin_blocks) {
-    long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    const long long stride = (long long)fin_blocks * 256;
-    for (; i <= ncell; i += stride) {
-      cell_start[base + k + i] = (i < ncell) ? (int)(cell_scan[base + i] + toff[(base + i) / kScanTile] - first) : gs.n[k];
-      cell_cnt[base + i] = 0ull;  // the histogram has been scanned: leave it empty for the next build (no memset per frame)
+    typedef int int4a __attribute__((ext_vector_type(4), aligned(16)));
+    const long long stride = (long long)fin_blocks * 256 * 4;
+    for (long long e = ((long long)blockIdx.x * 256 + threadIdx.x) * 4; e < n_tab; e += stride) {   // (n_tab is a multiple of 4)
+      const u32x4 v = *reinterpret_cast<const u32x4*>(cell_scan + e);
+      int k = 0;
+#pragma unroll
+      for (int q = 1; q < kKinds; ++q) k += (e >= gs.cell_base[q]) ? 1 : 0;
+      const unsigned add = toff[e / kScanTile] - first.v[k];
+      *reinterpret_cast<int4a*>(cell_start + e) = int4a{(int)(v.x + add), (int)(v.y + add), (int)(v.z + add), (int)(v.w + add)};
     }
   } else {
-    const int n = gs.n[k];
-    const int nb = (int)gridDim.x - fin_blocks;
-    for (int i = ((int)blockIdx.x - fin_blocks) * 256 + threadIdx.x; i < n; i += nb * 256) {
-      const int c = cell_of_pt[gs.tgt_off[k] + i];
-      const int pos = (int)(cell_scan[base + c] + toff[(base + c) / kScanTile] - first) + rank_of_pt[gs.tgt_off[k] + i];
-      gp[gs.tgt_off[k] + pos] = double4{gs.tx[k][i], gs.ty[k][i], gs.tz[k][i], __longlong_as_double((long long)i)};
+    const int sb = (int)blockIdx.x - fin_blocks;
+    const int k = sb / sc_blocks;
+    const int n = gs.n[k], off = gs.tgt_off[k];
+    const long long base = gs.cell_base[k];
+    for (int i = (sb - k * sc_blocks) * 256 + (int)threadIdx.x; i < n; i += sc_blocks * 256) {
+      const long long e = base + cell_of_pt[off + i];
+      const int pos = (int)(cell_scan[e] + toff[e / kScanTile] - first.v[k]) + rank_of_pt[off + i];
+      gp[off + pos] = double4{gs.tx[k][i], gs.ty[k][i], gs.tz[k][i], __longlong_as_double((long long)i)};
     }
   }
 }
-void launch_grid_finalize_scatter_all(const GridSet& gs, const unsigned long long* cell_scan, const unsigned long long* totals,
-                                      int tiles, int* cell_start, unsigned long long* cell_cnt, const int* cell_of_pt,
-                                      const int* rank_of_pt, double4* gp, hipStream_t s) {
-  long long m = 1;
-  for (int k = 0; k < kKinds; ++k) m = std::max(m, gs.ncell[k] + 1);
-  const int fin_blocks = (int)std::min<long long>((m + 255) / 256, 2048);
-  int sc_blocks = (max_n(gs) + 255) / 256;
-  if (sc_blocks > 4096) sc_blocks = 4096;
-  hipLaunchKernelGGL(k_grid_finalize_scatter_all, dim3(fin_blocks + sc_blocks, kKinds), dim3(256), 0, s, gs, cell_scan, totals,
-                     tiles, fin_blocks, cell_start, cell_cnt, cell_of_pt, rank_of_pt, gp);
+void launch_grid_finalize_scatter_all(const GridSet& gs, const unsigned* cell_scan, const unsigned* totals, int tiles, long long n_tab,
+                                      int* cell_start, const int* cell_of_pt, const int* rank_of_pt, double4* gp, hipStream_t s) {
+  const int fin_blocks = (int)std::min<long long>((n_tab + kGridFinCellsPerBlock - 1) / kGridFinCellsPerBlock, 1024);
+  const int sc_blocks = std::min((max_n(gs) + kGridScatterPtsPerBlock - 1) / kGridScatterPtsPerBlock, 1024);
+  GridFirst first;
+  unsigned counted = 0;
+  for (int k = 0; k < kKinds; ++k) { first.v[k] = counted; counted += (unsigned)gs.n[k]; }
+  hipLaunchKernelGGL(k_grid_finalize_scatter_all, dim3(fin_blocks + kKinds * sc_blocks), dim3(256), 0, s, gs, first, cell_scan, totals, tiles,
+                     n_tab, fin_blocks, sc_blocks, cell_start, cell_of_pt, rank_of_pt, gp);
 }
 void launch_grid_scatter_all(const GridSet& gs, const int* cell_of_pt, const unsigned long long* cell_scan,
                              const int* rank_of_pt, double4* gp, hipStream_t s) {
@@ -1287,26 +1350,7 @@ __global__ __launch_bounds__(256) void k_compact(CompactArgs A) {
     }
     return;
   }
-  if (A.tiles > 0) {  // exclusive prefix of the tile totals (packed pairs of 32-bit counts add without carries): 4 tiles per thread
-    const int t0 = threadIdx.x * 4;
-    unsigned long long v[4], run = 0ull;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) { v[u] = (t0 + u < A.tiles) ? A.totals[t0 + u] : 0ull; run += v[u]; }
-    unsigned long long incl = run;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const unsigned long long o = __shfl_up(incl, off, 64);
-      if (lane >= off) incl += o;
-    }
-    if (lane == 63) wtot[wave] = incl;
-    __syncthreads();
-    unsigned long long pre = incl - run;
-    for (int w = 0; w < wave; ++w) pre += wtot[w];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) { toff[t0 + u] = pre; pre += v[u]; }
-    __syncthreads();
-  }
+  if (A.tiles > 0) tile_offsets_to_lds(A.totals, A.tiles, toff, wtot);   // (packed pairs of 32-bit counts add without carries)
   if (blockIdx.x == 0 && threadIdx.x < 6 && A.st) A.st->x_build[threadIdx.x] = A.st->x[threadIdx.x];
   const int slot = blockIdx.x * 256 + threadIdx.x;
   const int n_slots = A.sv.slot_off[kKinds];

@@ -387,6 +387,15 @@ class CtxInfo(C.Structure):
                 ("k3_wide", C.c_int32)]
 
 
+class GridInfo(C.Structure):
+    """tloam_grid_info."""
+    _fields_ = [("dim", (C.c_int32 * 3) * 4), ("n", C.c_int32 * 4), ("ncell", C.c_int64 * 4), ("cell", C.c_double * 4),
+                ("scan_path", C.c_int32), ("table_elem_bytes", C.c_int32)]
+
+
+GRID_SCAN_NONE, GRID_SCAN_SMALL, GRID_SCAN_TILES, GRID_SCAN_SINGLE_PASS, GRID_SCAN_GENERIC = range(5)
+
+
 class Stats(C.Structure):
     """tloam_stats."""
     _fields_ = [
@@ -497,6 +506,7 @@ def load_library():
         "tloam_gn_iter_timer": (C.c_int, [vp, C.c_int, dp, C.POINTER(C.c_int64)]),
         "tloam_time_read_stream": (C.c_int, [vp, sz, C.c_int, dp]),
         "tloam_get_info": (C.c_int, [vp, C.POINTER(CtxInfo)]),
+        "tloam_get_grid_info": (C.c_int, [vp, C.POINTER(GridInfo)]),
         "tloam_debug_state": (C.c_int, [vp, dp, C.c_int]),
         "tloam_debug_se3": (C.c_int, [vp, C.c_int, dp, dp, dp]),
         "tloam_debug_partials": (C.c_int, [vp, dp, C.c_int]),
@@ -629,7 +639,7 @@ EXPORTED_SYMBOLS = (
     "tloam_sm_outer", "tloam_sm_end", "tloam_fitness", "tloam_get_correspondences", "tloam_get_weights",
     "tloam_knn", "tloam_set_correspondences", "tloam_accumulate", "tloam_get_costs", "tloam_get_normal_equations",
     "tloam_solve",
-    "tloam_time_accumulate", "tloam_time_sharded_sweep", "tloam_time_build", "tloam_k3_timer", "tloam_k3_timer_all", "tloam_k3_span", "tloam_gn_iter_timer", "tloam_time_read_stream", "tloam_get_info", "tloam_debug_state", "tloam_debug_partials", "tloam_debug_se3",
+    "tloam_time_accumulate", "tloam_time_sharded_sweep", "tloam_time_build", "tloam_k3_timer", "tloam_k3_timer_all", "tloam_k3_span", "tloam_gn_iter_timer", "tloam_time_read_stream", "tloam_get_info", "tloam_get_grid_info", "tloam_debug_state", "tloam_debug_partials", "tloam_debug_se3",
     "tloam_debug_raise_fault",
     "tloam_submap_default_config", "tloam_submap_init", "tloam_submap_update", "tloam_get_target",
     "tloam_feature_default_config", "tloam_pca_info", "tloam_extract_planar_sphere",
@@ -1705,6 +1715,14 @@ class HipRegistration:
         ci = CtxInfo()
         self._check(self.L.tloam_get_info(self.h, C.byref(ci)), "tloam_get_info")
         return {f: getattr(ci, f) for f, _ in CtxInfo._fields_ if f != "reserved"}
+
+    def grid_info(self):
+        """tloam_get_grid_info as a dict: the search grids of the context's last grid build (per kind dim, n, ncell, cell; the
+        build path GRID_SCAN_* and the size of a table entry on it)."""
+        gi = GridInfo()
+        self._check(self.L.tloam_get_grid_info(self.h, C.byref(gi)), "tloam_get_grid_info")
+        return {"dim": [list(d) for d in gi.dim], "n": gi.n[:], "ncell": gi.ncell[:], "cell": gi.cell[:],
+                "scan_path": gi.scan_path, "table_elem_bytes": gi.table_elem_bytes}
 
     # ---- multi-GPU ---------------------------------------------------------------------------
     def comm_init_rccl(self, rank, nranks, unique_id: bytes):
