@@ -57,6 +57,8 @@ def nearest_d2(q, t):
     """squared distance of every query to its nearest target, d0 d0 + d1 d1 + d2 d2 in that order (inf without targets)"""
     if len(t) == 0:
         return np.full(len(q), np.inf)
+    if len(q) > 4096:   # (queries by blocks: the same minima, less memory)
+        return np.concatenate([nearest_d2(q[s:s + 4096], t) for s in range(0, len(q), 4096)])
     best = np.full(len(q), np.inf)
     for s in range(0, len(t), 2048):
         c = t[s:s + 2048]
@@ -85,3 +87,49 @@ def score(src, tgt, T, inlier_dist):
     overlap = inl / pts if pts else 0.0
     rmse = np.sqrt(ss / inl) if inl else np.inf
     return overlap, rmse, inl, pts
+
+
+SCORE_BLOCKS, SCORE_WAVES, SCORE_LANES = 256, 4, 64    # k_loop_score: 256 blocks of four waves of 64
+SCORE_THREADS = SCORE_BLOCKS * SCORE_WAVES * SCORE_LANES
+
+
+def device_sum(keep, d):
+    """(count, sum of d over keep) of one kind, added as k_loop_score and the host add them: thread t takes points t,
+    t + 65 536, ... in order from 0.0; each wave the xor butterfly v = v + v[lane ^ off], off = 32 .. 1, lane 0 kept; a block's
+    four waves ((w0 + w1) + w2) + w3; the blocks in order from 0.0"""
+    keep, d = np.asarray(keep, bool), np.asarray(d, float)
+    acc = np.zeros((2, SCORE_THREADS))
+    for s in range(0, len(d), SCORE_THREADS):
+        k, v = keep[s:s + SCORE_THREADS], d[s:s + SCORE_THREADS]
+        n = len(v)
+        acc[0, :n] = np.where(k, acc[0, :n] + 1.0, acc[0, :n])
+        acc[1, :n] = np.where(k, acc[1, :n] + np.where(k, v, 0.0), acc[1, :n])
+    acc = acc.reshape(2, SCORE_BLOCKS, SCORE_WAVES, SCORE_LANES)
+    lane = np.arange(SCORE_LANES)
+    for off in (32, 16, 8, 4, 2, 1):
+        acc = acc + acc[..., lane ^ off]
+    w = acc[..., 0]
+    blocks = ((w[:, :, 0] + w[:, :, 1]) + w[:, :, 2]) + w[:, :, 3]
+    out = np.zeros(2)
+    for b in range(SCORE_BLOCKS):
+        out = out + blocks[:, b]
+    return float(out[0]), float(out[1])
+
+
+def score_device_order(src, tgt, T, inlier_dist):
+    """score() with every sum in the order of k_loop_score and tloam_loop_verify_*'s host loop: device_sum per kind, the kinds
+    added in order 0..3 from 0.0; rmse = sqrt(ss / inl) (inf without inliers), overlap = inl / pts"""
+    r2 = inlier_dist * inlier_dist
+    inl, ss, pts = 0.0, 0.0, 0
+    for kind in range(4):
+        p = move(T, src[kind])
+        t = np.asarray(tgt[kind], float).reshape(-1, 3)
+        if len(p) and len(t):   # (a kind without targets has no grid: its points count, none is an inlier)
+            d = nearest_d2(p, t)
+            ck, sk = device_sum(d < r2, d)
+            inl = inl + ck
+            ss = ss + sk
+        pts += len(p)
+    overlap = inl / float(pts) if pts else 0.0
+    rmse = float(np.sqrt(ss / inl)) if inl > 0.0 else np.inf
+    return overlap, rmse, int(inl), pts

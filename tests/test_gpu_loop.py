@@ -299,9 +299,9 @@ def test_device_equals_the_public_calls(hip_module, ob_run):
         for k in want:
             if k != "host_wait_us":
                 assert np.asarray(got[k]).tobytes() == np.asarray(want[k]).tobytes(), k
-    ov, rmse, inl, pts = LN.score(src, tgt, T2, reg.default_loop_config().inlier_dist)
+    ov, rmse, inl, pts = LN.score_device_order(src, tgt, T2, reg.default_loop_config().inlier_dist)
     assert (inl, pts) == (c["inliers"], c["points"])
-    assert ov == c["overlap"] and abs(rmse - c["rmse"]) <= 1e-12 * rmse
+    assert ov == c["overlap"] and bits(rmse) == bits(c["rmse"])
 
 
 # ---- 5: bookkeeping --------------------------------------------------------------------------------------------------------

@@ -41,6 +41,17 @@ void rigid_rows(const double T[16], double R[9], double t[3]) {   // column-majo
   }
 }
 
+// the score's reach in cells: every target within inlier_dist of a query lies within ceil(inlier_dist / cell) cells of the
+// query's cell in each direction.  Formed in double and bounded before the cast (inlier_dist may be anything up to DBL_MAX):
+// a query's cell coordinate lies in [-2, dim + 1] (cell_coord), so a reach of the largest dimension + 2 already walks the whole
+// grid from anywhere, and cx + reach stays far inside int (a table holds at most 4e6 cells)
+int score_reach(double inlier_dist, const GridView& g) {
+  const double cells = ceil(inlier_dist * g.inv_cell);
+  const int whole = std::max(g.dim[0], std::max(g.dim[1], g.dim[2])) + 2;
+  if (!(cells > 1.0)) return 1;
+  return cells >= (double)whole ? whole : (int)cells;
+}
+
 void drop_child(tloam_ctx*& ch) {
   if (ch) tloam_destroy(ch);
   ch = nullptr;
@@ -176,7 +187,7 @@ int verify(tloam_ctx* c, int64_t q, int64_t m, const double init[16], tloam_loop
     S.n[k] = (long long)K.n_src;
     if (K.grid_valid && K.n_tgt > 0) {
       S.g[k] = K.gv;
-      S.reach[k] = std::max(1, (int)ceil(L.cfg.inlier_dist * K.gv.inv_cell));
+      S.reach[k] = score_reach(L.cfg.inlier_dist, K.gv);
     }
   }
   rigid_rows(r2, S.R, S.t);
