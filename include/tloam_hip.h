@@ -935,6 +935,58 @@ int tloam_closed_map_read_box(tloam_ctx* ctx, const double lo[3], const double h
 int tloam_closed_map_read_poses(tloam_ctx* ctx, size_t first, size_t count, double* poses_colmajor);
 /* Every closed map call on a context with nranks > 1: TLOAM_E_INVALID. */
 
+/* ---- the closed map extended in place by the keyframes added since its build (additive to ABI 8) -----------------
+ * With it never called, every call, bit and launch is what it is without it.  The call takes keyframes [K, n_kf): K the map's
+ * info.n_keyframes, n_kf the context's keyframes -- the ones added since the build, the load or the last extend, by the odometry
+ * frame or by tloam_place_add_scan + tloam_place_set_keyframe_clouds.  pose_source 0: their stored poses; 1: the build's rule for
+ * the same keyframes (TLOAM_E_NOT_READY before any tloam_graph_optimize); 2: poses_colmajor [16 (n_kf - K)], of the new keyframes
+ * only (n_poses != n_kf - K, a non-finite or non-rigid pose: TLOAM_E_INVALID).
+ * Rows: every rule of the build holds for the new keyframes (mask, concatenation, non-finite points, a keyframe with a point
+ * beyond the grid, an empty keyframe).  A point whose voxel is in the map adds to its N and Q; the others create voxels, with ids
+ * from the old n_voxels upward in order of the smallest index among the new points.  Rows, ids, n_voxels and n_points are then
+ * those of a build over all n_kf keyframes under the same poses, bit for bit; info.n_keyframes becomes n_kf, the keyframe counts
+ * grow by the new keyframes', pose_source becomes the call's, launches stays the build's, tloam_closed_map_read_poses sees the new
+ * keyframes.  The sums are integers per voxel and ids are handed out in order of the smallest global index, which a later
+ * keyframe can only append to: this is a rebuild, not an approximation of one.
+ * Surfels (when the map has them): the new points' thirteen integers are added (to zero for a new id) and every voxel a new point
+ * fell in is solved again: sums, normals, variances and the surfel info equal a full pass after a full build.
+ * Carve (when the map is carved): M of a new id starts at 0; the rays of the NEW keyframes (the carve configuration's ray_mask)
+ * are walked through the map as extended and their misses added; old rays are not walked again:
+ * M_ext = [M_before, 0 ...] + carve(V_ext, new keyframes only).  This is deliberately not a full carve's M: a voxel that appeared
+ * with the new keyframes is not held to account for rays cast before it existed, and an old ray was tested against the centroid
+ * its voxel had then.  carve_info: n_keyframes becomes n_kf; n_rays, skipped_rays, steps and tested grow by the call's; misses
+ * and voxels_missed are those of the stored M.  A later tloam_closed_map_carve replaces them with the full semantics.
+ * The localiser's voxel records go stale (the next localise or diff reports prepared) and the diff's counts are dropped.  Place,
+ * loop and graph state and the clouds are not written.  A detached map (loaded without its clouds) extends like any other -- only
+ * the new keyframes' clouds are read -- and stays detached.
+ * Refused, with every byte left as it was: no built map (TLOAM_E_NOT_READY); nranks > 1, keyframe clouds off, fewer keyframes
+ * than the map was built from, a bad pose_source or bad poses, n_points that would pass 2^30 (TLOAM_E_INVALID).  n_kf == K is
+ * TLOAM_OK and changes nothing.  A call that fails after its first launch (TLOAM_E_HIP: an allocation, a bounded wait running
+ * out) leaves the closed map empty, as a failed build does.  The staging is sized by the new points alone (a table of the power of
+ * two >= 2 n and a slot per point) and freed with the call.  DESIGN.md 27. */
+typedef struct tloam_closed_map_extend_info {
+  int64_t first_keyframe;      /* K before the call */
+  int64_t n_keyframes;         /* n_kf - K: the keyframes the call took */
+  int64_t added_keyframes;     /* of them: n_keyframes - empty_keyframes - overflow_keyframes */
+  int64_t empty_keyframes;
+  int64_t overflow_keyframes;
+  int64_t points;              /* points added to the rows */
+  int64_t new_voxels;          /* voxels created */
+  int64_t touched_voxels;      /* voxels a new point fell in, the new ones included */
+  int64_t rays;                /* carved maps: the call's rays, and of them ... */
+  int64_t skipped_rays;
+  int64_t steps;
+  int64_t tested;
+  int64_t misses;
+  int64_t solved_voxels;       /* maps with surfels: the map's solved voxels after the call */
+  int32_t grown;               /* 1: the rows were reallocated inside the call */
+  int32_t launches;            /* kernel launches of the call: they depend on surfels, carve and grown alone */
+} tloam_closed_map_extend_info;
+int tloam_closed_map_extend(tloam_ctx* ctx, int pose_source, const double* poses_colmajor_or_null, size_t n_poses,
+                            tloam_closed_map_extend_info* info_or_null);
+/* Of the last successful extend since the map was built or loaded; zero when there was none. */
+int tloam_closed_map_get_extend_info(tloam_ctx* ctx, tloam_closed_map_extend_info* info);
+
 /* ---- the carve of the closed map: per voxel, the rays that passed through it (additive to ABI 8) ----------------
  * A lidar return also says that nothing was between the sensor and the point.  A carve counts, per occupied voxel of the built
  * closed map, the rays of the build's keyframes 0 .. K-1 that passed through it: M beside N.  Runs only when called; nothing

@@ -30,6 +30,7 @@ UNITS = [
     ("tl_map.hip", ["-ffp-contract=off"]),      # the global map: transform and voxel_min_bound in the oracle's operation order
     ("tl_vmap.hip", ["-ffp-contract=off"]),     # the merged voxel map: transform, quantisation and centroids as DESIGN.md 14 states
     ("tl_cmap.hip", ["-ffp-contract=off"]),     # the closed map: transform and quantisation as DESIGN.md 14 states (tl_voxel.hpp)
+    ("tl_extend.hip", ["-ffp-contract=off"]),   # the closed map's extension: the staged voxels numbered and committed (tl_voxel.hpp asks for the flag)
     ("tl_carve.hip", ["-ffp-contract=off"]),    # the closed map's carve: the ray walk and the miss test as DESIGN.md 21 states
     ("tl_surfel.hip", ["-ffp-contract=off"]),   # the closed map's surfels: moments, covariance and eig3_sym as DESIGN.md 22 states
     ("tl_snapshot.hip", ["-ffp-contract=off"]), # the closed map's snapshot: integer checksums and range tests (tl_voxel.hpp asks for the flag)
@@ -60,6 +61,7 @@ UNITS = [
     ("tl_api_loop.hip", ["-ffp-contract=off"]),     # loop verification: T_rel and the initial guesses formed on the host
     ("tl_api_graph.hip", ["-ffp-contract=off"]),    # pose-graph optimisation: the chain's Z and the weights formed on the host
     ("tl_api_cmap.hip", []),     # the closed map; its poses come rounded from tl_api_graph.hip
+    ("tl_api_extend.hip", []),   # the closed map's extension; its poses come rounded from tl_api_graph.hip
     ("tl_api_carve.hip", []),    # the closed map's carve
     ("tl_api_surfel.hip", []),   # the closed map's surfels
     ("tl_api_localise.hip", ["-ffp-contract=off"]),   # localisation in the closed map: the prior's quaternion and matrix formed on the host
@@ -67,7 +69,7 @@ UNITS = [
     ("tl_api_snapshot.hip", []), # the closed map's snapshot: save, probe, load
     ("tl_probe.hip", []),        # read-stream bandwidth probe (the on-box ceiling of the bench's roofline block)
 ]
-HEADERS = ["tl_common.hpp", "tl_se3.hpp", "tl_knn.hpp", "tl_walk.hpp", "tl_voxel.hpp", "tl_ctx.hpp", "tl_step.hpp", "tl_finish.hpp", "tl_prep.hpp", "tl_seg.hpp", os.path.join("..", "..", "include", "tloam_hip.h")]
+HEADERS = ["tl_common.hpp", "tl_se3.hpp", "tl_knn.hpp", "tl_walk.hpp", "tl_voxel.hpp", "tl_ctx.hpp", "tl_step.hpp", "tl_finish.hpp", "tl_prep.hpp", "tl_seg.hpp", "tl_extend_host.hpp", os.path.join("..", "..", "include", "tloam_hip.h")]
 
 
 def _hipcc():

@@ -11,6 +11,7 @@
 #include <math.h>
 
 #include "tl_ctx.hpp"
+#include "tl_extend_host.hpp"
 
 using namespace tl;
 
@@ -57,7 +58,7 @@ int build_body(tloam_ctx* c, const std::vector<double>& poses, tloam_closed_map_
   const size_t K = P.kf.size();
   std::vector<CmapSpan> spans;
   long long n = 0;
-  cmap_span_table(P, K, M.cfg.cloud_mask, &spans, &n, &I.empty_keyframes);
+  cmap_span_table(P, 0, K, M.cfg.cloud_mask, &spans, &n, &I.empty_keyframes);
   if ((size_t)n > kCmapMaxPoints) {
     c->last_error = "closed map: more than 2^30 points";
     return TLOAM_E_HIP;
@@ -122,19 +123,9 @@ namespace tlh {
 bool cmap_config_valid(const tloam_closed_map_config& cfg) { return cmap_config_ok(cfg); }
 size_t cmap_default_reserve() { return kCmapDefaultReserve; }
 
-void cmap_span_table(const PlaceState& P, size_t K, int mask, std::vector<CmapSpan>* spans, long long* n, int64_t* empty_keyframes) {
-  long long at = 0;
-  for (size_t k = 0; k < K && k < P.kf.size(); ++k) {
-    const long long before = at;
-    for (int j = 0; j < 8; ++j) {
-      if (!((mask >> j) & 1) || P.kf[k].n[j] == 0) continue;
-      spans->push_back(CmapSpan{(long long)P.kf[k].off[j], at, (int)k, 0});
-      at += (long long)P.kf[k].n[j];
-    }
-    if (at == before && empty_keyframes) ++*empty_keyframes;
-  }
-  spans->push_back(CmapSpan{0, at, 0, 0});   // (the end: span[nspan].start = n)
-  *n = at;
+void cmap_span_table(const PlaceState& P, size_t first, size_t K, int mask, std::vector<CmapSpan>* spans, long long* n,
+                     int64_t* empty_keyframes) {
+  tlx::span_range_table(P.kf.data(), P.kf.size(), first, K, mask, spans, n, empty_keyframes);
 }
 
 int SpanUpload::upload(tloam_ctx* c, const std::vector<CmapSpan>& spans, long long n, const double* poses, size_t K, SpanInput* in) {
@@ -196,26 +187,18 @@ int tloam_closed_map_build(tloam_ctx* c, int pose_source, const double* poses, s
   const PlaceState& P = c->place;
   const GraphState& G = c->graph;
   const size_t K = P.kf.size();
-  std::vector<double> used(16 * K);
-  if (pose_source == TLOAM_CLOSED_MAP_POSES_CALLER) {
-    if (n_poses != K || (K > 0 && !poses)) return TLOAM_E_INVALID;
-    for (size_t k = 0; k < K; ++k) {
-      Pose unused;
-      for (int i = 0; i < 16; ++i)
-        if (!std::isfinite(poses[16 * k + i])) return TLOAM_E_INVALID;
-      if (!pose_from_matrix(poses + 16 * k, &unused)) return TLOAM_E_INVALID;   // (the rigid test of tloam_graph_solve)
-    }
-    if (K) memcpy(used.data(), poses, sizeof(double) * 16 * K);
-  } else if (pose_source == TLOAM_CLOSED_MAP_POSES_CORRECTED) {
-    const size_t nc = G.corrected.size() / 16;
-    if (!G.have || (nc == 0 && K > 0)) return TLOAM_E_NOT_READY;
-    for (size_t k = 0; k < K; ++k) {
-      if (k < nc) memcpy(&used[16 * k], &G.corrected[16 * k], sizeof(double) * 16);
-      else graph_correct_pose(c, nc - 1, P.kf[k].pose, &used[16 * k]);   // a keyframe added since the optimise
-    }
-  } else {
-    for (size_t k = 0; k < K; ++k) memcpy(&used[16 * k], P.kf[k].pose, sizeof(double) * 16);
-  }
+  // the pose rule is the extension's over the whole range (tl_extend_host.hpp): one body, so that an extension's rows are those
+  // of a build under the same poses
+  const size_t nc = G.corrected.size() / 16;
+  std::vector<double> used;
+  const int prc = tlx::extend_poses(
+      pose_source, poses, n_poses, 0, K, G.have, nc,
+      [&](size_t k, double* dst) { memcpy(dst, P.kf[k].pose, sizeof(double) * 16); },
+      [&](size_t k, double* dst) { memcpy(dst, &G.corrected[16 * k], sizeof(double) * 16); },
+      [&](size_t k, double* dst) { graph_correct_pose(c, nc - 1, P.kf[k].pose, dst); },   // a keyframe added since the optimise
+      [&](const double* pose) { Pose unused; return pose_from_matrix(pose, &unused); },   // (the rigid test of tloam_graph_solve)
+      &used);
+  if (prc != TLOAM_OK) return prc;
   CmapState& M = c->cmap;
   M.drop();   // from here on a failure leaves the closed map empty
   tloam_closed_map_info I;

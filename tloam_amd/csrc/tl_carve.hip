@@ -9,6 +9,8 @@
 //                                add on the voxel's M; the ray's counters summed over the wave by shuffles, one atomic per counter
 //                                and wave
 //   k_carve_count   grid x 256   per voxel: M > 0 counted by ballot, one atomic per wave
+// An extension of the closed map (tl_api_extend.hip) launches k_carve_rays over the new keyframes' rays and
+// k_carve_count without the clear: the misses are added to the M that is there.
 // The carved read is k_carve_box: the box read's one body (tl_voxel.hpp: voxel_box_body), with the voxels seen through left out.
 //
 // Compiled with -ffp-contract=off.  The operation order of a ray (ray_walk; tests/closed_map_carve_np.py restates it), per axis a:
@@ -83,9 +85,17 @@ __global__ __launch_bounds__(256) void k_carve_box(CarveReadArgs A, int nblocks)
 int launch_carve(const CarveWork& W, hipStream_t s) {
   const unsigned nv_blocks = blocks_of((size_t)std::max<long long>(W.nv, 1));   // (nothing still launches)
   hipLaunchKernelGGL(k_carve_clear, dim3(std::min(nv_blocks, 2048u)), dim3(256), 0, s, W);
+  return 1 + launch_carve_rays(W, s) + launch_carve_count(W, s);
+}
+
+int launch_carve_rays(const CarveWork& W, hipStream_t s) {
   hipLaunchKernelGGL(k_carve_rays, dim3(blocks_of((size_t)std::max<long long>(W.in.n, 1))), dim3(256), 0, s, W);
-  hipLaunchKernelGGL(k_carve_count, dim3(nv_blocks), dim3(256), 0, s, W);
-  return 3;
+  return 1;
+}
+
+int launch_carve_count(const CarveWork& W, hipStream_t s) {
+  hipLaunchKernelGGL(k_carve_count, dim3(blocks_of((size_t)std::max<long long>(W.nv, 1))), dim3(256), 0, s, W);
+  return 1;
 }
 
 void launch_carve_read(const CarveReadArgs& A, hipStream_t s) {

@@ -626,7 +626,8 @@ void launch_vmap_stage(const VmapStageWork& W, hipStream_t s);
 // an accepted frame's staged voxels into the persistent map (the new ones keyed and entered in the table)
 void launch_vmap_commit(const VmapStageWork& W, const VmapTable& T, hipStream_t s);
 // the table of `T` (all slots free) rebuilt from the keys of ids [0, n)
-void launch_vmap_rehash(const VmapTable& T, size_t n, hipStream_t s);
+// (n == 0 launches nothing, unless `even_empty`: a caller whose launch count must not depend on n)
+void launch_vmap_rehash(const VmapTable& T, size_t n, hipStream_t s, bool even_empty = false);
 void launch_vmap_read(const VmapReadArgs& A, hipStream_t s);
 void launch_vmap_read_box(const VmapReadArgs& A, hipStream_t s);
 
@@ -669,6 +670,28 @@ struct CmapWork {
 int launch_cmap_stage(const CmapWork& W, hipStream_t s);
 int launch_cmap_emit(const CmapWork& W, hipStream_t s);
 
+// ---- the closed map extended in place by later keyframes (tl_extend.hip).  The new keyframes' points are
+// staged by the build's own clear | flag | stage (launch_cmap_stage over a span table of the new keyframes alone: a staging table
+// and a slot per NEW point); the staged voxels are then numbered against the map's table and committed into its rows
+struct StagedVoxels {         // the staging table as the stages after the commit read it
+  unsigned long long fmask;
+  const unsigned long long* fkey;   // kFree: an empty slot
+  const int* fid;                   // the voxel's id in the map
+  const unsigned long long* fsum;   // [4][fmask + 1]: N, Qx, Qy, Qz the call added
+};
+struct ExtendWork {
+  CmapWork w;                 // the staging; w.rows / w.row_cap: the map being extended; w.ctl [2] start tickets of k_ext_emit,
+                              // [3] fault, [4] fresh voxels (k_ext_emit); [0] staged (= touched) voxels, [1] points (k_cmap_stage)
+  int* fid;                   // [w.fmask + 1] the id of a staged voxel (k_ext_emit)
+  long long base;             // the map's voxels before the call: the first fresh id
+  long long side_cap;         // ids the two arrays below hold (<= row_cap): the ids the call can reach
+  unsigned long long* miss;   // [side_cap] or null: M of a fresh id is zeroed
+  unsigned long long* sums;   // [side_cap][kSurfelSums] or null: the thirteen sums of a fresh id are zeroed
+};
+// emit (numbers the staged voxels; reads the map's table), then commit (writes the rows): each returns the launches it made
+int launch_extend_emit(const ExtendWork& X, hipStream_t s);
+int launch_extend_commit(const ExtendWork& X, hipStream_t s);
+
 // ---- the carve of the closed map: per occupied voxel, the rays of the keyframes that passed through it (tl_carve.hip,
 // DESIGN.md section 21).  A ray is a stored point of a keyframe: from the translation of the keyframe's pose to the point under
 // that pose.  The rays come from a span table of the closed map's kind (CmapSpan) written for the carve's ray mask; the map is
@@ -684,6 +707,10 @@ struct CarveWork {
 };
 // clear | rays | count: no host synchronisation; returns the launches it made (the same for every size)
 int launch_carve(const CarveWork& W, hipStream_t s);
+// its parts, for the extension: the rays of W.in walked and their misses ADDED to what W.miss and W.ctl hold; the
+// voxels with M > 0 added to W.ctl[4]
+int launch_carve_rays(const CarveWork& W, hipStream_t s);
+int launch_carve_count(const CarveWork& W, hipStream_t s);
 struct CarveReadArgs {
   VmapReadArgs rows;          // the closed map's rows, the box (when `boxed`), min_count, the outputs, look and ctl as k_vmap_box's
   const long long* miss;      // [count] M in id order
@@ -714,6 +741,10 @@ struct SurfelWork {
 };
 // clear | flag | accum | solve: no host synchronisation; returns the launches it made (the same for every size)
 int launch_surfels(const SurfelWork& W, hipStream_t s);
+// its parts, for the extension: the points of W.in (W.kf_over as the caller flagged it) ADDED to what W.sums and
+// W.ctl hold; then the voxels of a staging table solved again, a thread per slot, the voxels that became solved added to W.ctl[2]
+int launch_surfel_accum(const SurfelWork& W, hipStream_t s);
+int launch_surfel_solve_staged(const SurfelWork& W, const StagedVoxels& V, hipStream_t s);
 struct SurfelReadArgs {
   VmapReadArgs rows;          // the closed map's rows, the box (when `boxed`), min_count, out_c, out_n (Ns), look and ctl as k_vmap_box's
   const unsigned long long* sums;

@@ -514,11 +514,14 @@ struct CmapState {
     diffed = false;
     diff_info = tloam_closed_map_diff_info{};
   }
+  // the extension (tl_api_extend.hip): what the last extend of this map reports
+  tloam_closed_map_extend_info extend_info{};
   void drop() {   // the closed map goes, and the carve's counts, the surfels and the diff's counts with it; the configurations
                   // and storage stay
     built = false;
     detached = false;
     info = tloam_closed_map_info{};
+    extend_info = tloam_closed_map_extend_info{};
     poses.clear();
     drop_carve();
     drop_surfels();
@@ -977,10 +980,11 @@ int voxel_rows_read_box(tloam_ctx* c, const VoxelRows& R, const double* lo, cons
   HIPC(c, hipStreamSynchronize(c->stream));
   return TLOAM_OK;
 }
-// tl_api_cmap.hip: the closed map's span table for `mask` over keyframes [0, min(K, kf.size())): keyframes ascending, a keyframe's
-// selected clouds in slot order, empty clouds left out, the end sentinel (spans->back().start = *n) last; *empty_keyframes (may be
-// null) counts the keyframes that add no span
-void cmap_span_table(const PlaceState& P, size_t K, int mask, std::vector<tl::CmapSpan>* spans, long long* n,
+// tl_api_cmap.hip: the closed map's span table for `mask` over keyframes [first, min(K, kf.size())): keyframes ascending, a
+// keyframe's selected clouds in slot order, empty clouds left out, the end sentinel (spans->back().start = *n) last; a span's kf
+// counts from `first` (the poses and flags beside the table are those keyframes' alone); *empty_keyframes (may be null) counts the
+// keyframes that add no span
+void cmap_span_table(const PlaceState& P, size_t first, size_t K, int mask, std::vector<tl::CmapSpan>* spans, long long* n,
                      int64_t* empty_keyframes);
 // ... and its device copy beside the K poses, a stage's own: freed with it (hipFree waits for the launches that use them)
 struct SpanUpload {
@@ -1004,7 +1008,7 @@ int cmap_pass(tloam_ctx* c, int mask, const DBuf<unsigned long long>& ctl, Reser
   const CmapState& M = c->cmap;
   out->K = M.poses.size() / 16;
   std::vector<tl::CmapSpan> spans;
-  cmap_span_table(c->place, out->K, mask, &spans, &out->n, nullptr);
+  cmap_span_table(c->place, 0, out->K, mask, &spans, &out->n, nullptr);
   HIPC(c, hipSetDevice(c->device));
   int rc = reserve();
   if (rc != TLOAM_OK) return rc;

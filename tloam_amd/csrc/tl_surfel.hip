@@ -11,6 +11,10 @@
 //                                 adds (a wave without such a run, and the plain form, add per point: the same bits)
 //   k_surfel_solve   grid x 256   per voxel: mean, covariance, eig3_sym, orientation, scale; the solved voxels counted by ballot,
 //                                 one atomic per wave
+// An extension of the closed map (tl_api_extend.hip) launches k_surfel_accum over the new keyframes' spans
+// without the clear, then
+//   k_surfel_solve_staged  T/256 x 256   per slot of the extension's staging table: the voxel the slot added to solved again
+//                                 (surfel_solve_voxel, k_surfel_solve's body); the voxels that became solved counted
 // The box read is k_surfel_box: the box read's one body (tl_voxel.hpp: voxel_box_body) with the surfel gate (surfel_gate).
 //
 // Compiled with -ffp-contract=off.  The arithmetic (tests/closed_map_surfel_np.py restates it), per point of keyframe k and axis a:
@@ -142,10 +146,10 @@ __global__ __launch_bounds__(256) void k_surfel_accum(SurfelWork W) {
   }
 }
 
-__global__ __launch_bounds__(256) void k_surfel_solve(SurfelWork W) {
-  const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
+// voxel id (< W.nv) solved from its thirteen sums: its normal and variances written (zeros below min_points); true when solved
+__device__ __forceinline__ bool surfel_solve_voxel(const SurfelWork& W, long long id) {
   bool solved = false;
-  if (id < W.nv) {
+  {
     const long long* s = (const long long*)W.sums + (size_t)id * kSurfelSums;
     const long long Ns = s[0];
     double n[3] = {0.0, 0.0, 0.0}, ev[3] = {0.0, 0.0, 0.0};
@@ -175,7 +179,29 @@ __global__ __launch_bounds__(256) void k_surfel_solve(SurfelWork W) {
       W.eval[3 * id + a] = ev[a];
     }
   }
+  return solved;
+}
+
+__global__ __launch_bounds__(256) void k_surfel_solve(SurfelWork W) {
+  const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
+  const bool solved = id < W.nv && surfel_solve_voxel(W, id);
   const unsigned long long bal = __ballot(solved);
+  if ((threadIdx.x & 63) == 0 && bal) atomicAdd(&W.ctl[2], (unsigned long long)__popcll(bal));
+}
+
+// per slot of a staging table (the closed map's extension): the voxel the slot added to is solved again; one that had fewer than
+// min_points before the slot's N was added and is solved now is counted
+__global__ __launch_bounds__(256) void k_surfel_solve_staged(SurfelWork W, StagedVoxels V) {
+  const size_t s = (size_t)blockIdx.x * 256 + threadIdx.x;
+  bool newly = false;
+  if (s <= V.fmask && V.fkey[s] != kFree) {
+    const long long id = V.fid[s];
+    if (id >= 0 && id < W.nv) {
+      const long long before = ((const long long*)W.sums)[(size_t)id * kSurfelSums] - (long long)V.fsum[s];
+      newly = surfel_solve_voxel(W, id) && before < (long long)W.min_points;
+    }
+  }
+  const unsigned long long bal = __ballot(newly);
   if ((threadIdx.x & 63) == 0 && bal) atomicAdd(&W.ctl[2], (unsigned long long)__popcll(bal));
 }
 
@@ -207,10 +233,21 @@ int launch_surfels(const SurfelWork& W, hipStream_t s) {
   const unsigned pt_blocks = blocks_of((size_t)std::max<long long>(W.in.n, 1));
   hipLaunchKernelGGL(k_surfel_clear, dim3(std::min(blocks_of(nv * kSurfelSums), 2048u)), dim3(256), 0, s, W);
   hipLaunchKernelGGL(k_surfel_flag, dim3(pt_blocks), dim3(256), 0, s, W);
-  if (W.runs) hipLaunchKernelGGL(k_surfel_accum<true>, dim3(pt_blocks), dim3(256), 0, s, W);
-  else hipLaunchKernelGGL(k_surfel_accum<false>, dim3(pt_blocks), dim3(256), 0, s, W);
+  launch_surfel_accum(W, s);
   hipLaunchKernelGGL(k_surfel_solve, dim3(blocks_of(nv)), dim3(256), 0, s, W);
   return 4;
+}
+
+int launch_surfel_accum(const SurfelWork& W, hipStream_t s) {
+  const unsigned pt_blocks = blocks_of((size_t)std::max<long long>(W.in.n, 1));
+  if (W.runs) hipLaunchKernelGGL(k_surfel_accum<true>, dim3(pt_blocks), dim3(256), 0, s, W);
+  else hipLaunchKernelGGL(k_surfel_accum<false>, dim3(pt_blocks), dim3(256), 0, s, W);
+  return 1;
+}
+
+int launch_surfel_solve_staged(const SurfelWork& W, const StagedVoxels& V, hipStream_t s) {
+  hipLaunchKernelGGL(k_surfel_solve_staged, dim3(blocks_of((size_t)V.fmask + 1)), dim3(256), 0, s, W, V);
+  return 1;
 }
 
 void launch_surfel_solve(const SurfelWork& W, hipStream_t s) {

@@ -75,16 +75,13 @@ __global__ __launch_bounds__(256) void k_vmap_emit(VmapStageWork W, int nblocks)
   const size_t i = (size_t)bid * 256 + tid;
   const int h = i < W.n ? W.slot_of_pt[i] : -1;
   const bool leader = h >= 0 && W.flead[h] == (int)i;
-  const int found = leader ? id_table_find(W.ptab, W.pmask, W.pkey, W.fkey[h]) : -1;
-  const bool fresh = leader && found < 0;
-  int pos, total;
-  block_flag_scan(fresh, s_wave, &pos, &total);
-  if (tid == 0) s_prefix = lookback_prefix(W.look, bid, (unsigned long long)total, LookFaultDevice{&W.ctl[3]});
-  __syncthreads();
-  if (leader) W.fid[h] = fresh ? (int)(W.base + (long long)(s_prefix + pos)) : found;
+  unsigned long long upto;
+  const int id = staged_voxel_id(leader, leader ? W.fkey[h] : 0ull, W.pmask, W.ptab, W.pkey, W.base, W.look, bid, &W.ctl[3], s_wave,
+                                 &s_prefix, &upto);
+  if (leader) W.fid[h] = id;
   if (bid == nblocks - 1 && tid < 8) {   // the block that holds the last point: the frame's new voxels
-    if (tid == 0) W.ctl[4] = s_prefix + total;
-    unsigned long long w = tid == 0 ? s_prefix + total
+    if (tid == 0) W.ctl[4] = upto;
+    unsigned long long w = tid == 0 ? upto
                          : tid == 1 ? __hip_atomic_load(&W.ctl[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
                          : tid == 2 ? __hip_atomic_load(&W.ctl[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
                          : tid == 3 ? __hip_atomic_load(&W.ctl[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
@@ -103,13 +100,7 @@ __global__ __launch_bounds__(256) void k_vmap_commit(VmapStageWork W, VmapTable 
   const int id = W.fid[s];
   const long long n = (long long)W.fsum[s], qx = (long long)W.fsum[T + s], qy = (long long)W.fsum[2 * T + s],
                   qz = (long long)W.fsum[3 * T + s];
-  if (id >= W.base) {
-    P.pkey[id] = key;
-    P.pn[id] = n; P.pqx[id] = qx; P.pqy[id] = qy; P.pqz[id] = qz;
-    id_table_insert(P.ptab, P.pmask, key, id);
-  } else {
-    P.pn[id] += n; P.pqx[id] += qx; P.pqy[id] += qy; P.pqz[id] += qz;
-  }
+  staged_voxel_commit(P, id, id >= W.base, key, n, qx, qy, qz);
 }
 
 __global__ __launch_bounds__(256) void k_vmap_rehash(VmapTable P, size_t n) {
@@ -145,9 +136,9 @@ void launch_vmap_commit(const VmapStageWork& W, const VmapTable& T, hipStream_t 
   hipLaunchKernelGGL(k_vmap_commit, dim3(blocks_of((size_t)W.fmask + 1)), dim3(256), 0, s, W, T);
 }
 
-void launch_vmap_rehash(const VmapTable& T, size_t n, hipStream_t s) {
-  if (n == 0) return;
-  hipLaunchKernelGGL(k_vmap_rehash, dim3(blocks_of(n)), dim3(256), 0, s, T, n);
+void launch_vmap_rehash(const VmapTable& T, size_t n, hipStream_t s, bool even_empty) {
+  if (n == 0 && !even_empty) return;
+  hipLaunchKernelGGL(k_vmap_rehash, dim3(blocks_of(std::max<size_t>(n, 1))), dim3(256), 0, s, T, n);
 }
 
 void launch_vmap_read(const VmapReadArgs& A, hipStream_t s) {

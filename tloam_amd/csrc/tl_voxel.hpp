@@ -4,6 +4,7 @@
 // the two table inserts and the slot table's lookup, of the wave's integer sum, of the block scans, of the single-pass
 // look-back with its one bound, of the eight-word post to the host, of the voxel map's key / q arithmetic, its row centroid
 // and its run sums, of the compacting box read's body (k_vmap_box, k_carve_box, k_surfel_box, k_diff_box), of the surfel gate,
+// of an incremental add's numbering and row update (k_vmap_emit / k_vmap_commit, k_ext_emit / k_ext_commit),
 // of the span table's search and its point, and of a ray's walk through the grid (k_carve_rays, k_diff_rays); and of
 // PointCloud2::VoxelDownSample's arithmetic for the two units that restate it (the min bound's hand-over and finish, the voxel
 // key of a point, the leader's local sum, the blocks of an emit kernel the device holds at once).
@@ -412,6 +413,39 @@ __device__ __forceinline__ WaveRun wave_run_sums(bool ok, unsigned long long key
     r.sum[k] = v[k] - (hl > 0 ? b : 0u);
   }
   return r;
+}
+
+// ---- an incremental add to a map in id order (the merged voxel map's frame, tl_vmap.hip; the closed map's extension,
+// tl_extend.hip): the staged voxels numbered, then committed ----
+// The id of a staged voxel, at its leader (-1 in every other thread): the one its key has in the persistent table (read only), or
+// base + its place among the fresh leaders of the whole launch, in leader order (block scan + look-back over start tickets `bid`,
+// the bounded wait raising *fault).  *upto: the fresh voxels of this block and of every block before it.  Called by the whole block.
+template <typename Bid>
+__device__ __forceinline__ int staged_voxel_id(bool leader, unsigned long long key, unsigned long long pmask, const int* ptab,
+                                               const unsigned long long* pkey, long long base, unsigned long long* look, Bid bid,
+                                               unsigned long long* fault, unsigned long long* s_wave, unsigned long long* s_prefix,
+                                               unsigned long long* upto) {
+  const int found = leader ? id_table_find(ptab, pmask, pkey, key) : -1;
+  const bool fresh = leader && found < 0;
+  int pos, total;
+  block_flag_scan(fresh, s_wave, &pos, &total);
+  if (threadIdx.x == 0) *s_prefix = lookback_prefix(look, bid, (unsigned long long)total, LookFaultDevice{fault});
+  __syncthreads();
+  *upto = *s_prefix + (unsigned long long)total;
+  return !leader ? -1 : fresh ? (int)(base + (long long)(*s_prefix + pos)) : found;
+}
+
+// A staged voxel's sums into row `id` (one staged voxel per id: plain stores and adds); a fresh one is keyed and entered in the
+// table (load <= 1/2: a free slot is found).
+__device__ __forceinline__ void staged_voxel_commit(const VmapTable& P, int id, bool fresh, unsigned long long key, long long n,
+                                                    long long qx, long long qy, long long qz) {
+  if (fresh) {
+    P.pkey[id] = key;
+    P.pn[id] = n; P.pqx[id] = qx; P.pqy[id] = qy; P.pqz[id] = qz;
+    id_table_insert(P.ptab, P.pmask, key, id);
+  } else {
+    P.pn[id] += n; P.pqx[id] += qx; P.pqy[id] += qy; P.pqz[id] += qz;
+  }
 }
 
 // ---- a span table in global point order (SpanInput: the closed map's build, its carve and its surfels) ----

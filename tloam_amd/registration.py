@@ -127,6 +127,17 @@ class ClosedMapCarveInfo(C.Structure):
     as_dict = _int_fields
 
 
+class ClosedMapExtendInfo(C.Structure):
+    """tloam_closed_map_extend_info: what one extension of the closed map took and did."""
+    _fields_ = [("first_keyframe", C.c_int64), ("n_keyframes", C.c_int64), ("added_keyframes", C.c_int64),
+                ("empty_keyframes", C.c_int64), ("overflow_keyframes", C.c_int64), ("points", C.c_int64), ("new_voxels", C.c_int64),
+                ("touched_voxels", C.c_int64), ("rays", C.c_int64), ("skipped_rays", C.c_int64), ("steps", C.c_int64),
+                ("tested", C.c_int64), ("misses", C.c_int64), ("solved_voxels", C.c_int64), ("grown", C.c_int32),
+                ("launches", C.c_int32)]
+
+    as_dict = _int_fields
+
+
 class ClosedMapSurfelConfig(C.Structure):
     """tloam_closed_map_surfel_config: the fewest points a voxel is solved from."""
     _fields_ = [("min_points", C.c_int32), ("reserved0", C.c_int32)]
@@ -576,6 +587,8 @@ def load_library():
         "tloam_closed_map_read": (C.c_int, [vp, sz, sz, dp, C.POINTER(C.c_int64)]),
         "tloam_closed_map_read_box": (C.c_int, [vp, dp, dp, C.c_int64, sz, C.POINTER(sz), dp, C.POINTER(C.c_int64)]),
         "tloam_closed_map_read_poses": (C.c_int, [vp, sz, sz, dp]),
+        "tloam_closed_map_extend": (C.c_int, [vp, C.c_int, dp, sz, C.POINTER(ClosedMapExtendInfo)]),
+        "tloam_closed_map_get_extend_info": (C.c_int, [vp, C.POINTER(ClosedMapExtendInfo)]),
         "tloam_closed_map_carve_default_config": (None, [C.POINTER(ClosedMapCarveConfig)]),
         "tloam_closed_map_carve_configure": (C.c_int, [vp, C.POINTER(ClosedMapCarveConfig)]),
         "tloam_closed_map_get_carve_info": (C.c_int, [vp, C.POINTER(ClosedMapCarveInfo)]),
@@ -655,7 +668,8 @@ EXPORTED_SYMBOLS = (
     "tloam_graph_read_poses", "tloam_graph_correct_pose", "tloam_graph_robust_default_config", "tloam_graph_robust_configure",
     "tloam_graph_solve_robust", "tloam_graph_read_loop_scales", "tloam_graph_get_robust_info", "tloam_closed_map_default_config", "tloam_closed_map_configure",
     "tloam_closed_map_get_info", "tloam_closed_map_build", "tloam_closed_map_read", "tloam_closed_map_read_box",
-    "tloam_closed_map_read_poses", "tloam_closed_map_carve_default_config", "tloam_closed_map_carve_configure",
+    "tloam_closed_map_read_poses", "tloam_closed_map_extend", "tloam_closed_map_get_extend_info",
+    "tloam_closed_map_carve_default_config", "tloam_closed_map_carve_configure",
     "tloam_closed_map_get_carve_info", "tloam_closed_map_carve", "tloam_closed_map_read_misses", "tloam_closed_map_read_carved",
     "tloam_closed_map_surfel_default_config", "tloam_closed_map_surfel_configure", "tloam_closed_map_get_surfel_info",
     "tloam_closed_map_surfels", "tloam_closed_map_read_moments", "tloam_closed_map_read_surfels", "tloam_closed_map_read_surfels_box",
@@ -1364,6 +1378,24 @@ class HipRegistration:
         out = np.zeros((max(m, 1), 16))
         self._check(self.L.tloam_closed_map_read_poses(self.h, int(first), m, _dp(out)), "tloam_closed_map_read_poses")
         return out[:m].reshape(m, 4, 4).transpose(0, 2, 1).copy()
+
+    # ---- the closed map extended in place by the keyframes added since its build
+    def closed_map_extend(self, pose_source=0, poses=None) -> dict:
+        """adds the keyframes [info.n_keyframes, n_kf) -- the ones added since the build, the load or the last extend -- to the
+        built closed map in place, its surfels and its carve following -> info dict.  pose_source 0: their stored poses, 1: the
+        build's rule (corrected poses), 2: `poses` (n_kf - K, 4, 4), of the new keyframes only"""
+        P, n = None, 0
+        if poses is not None:
+            P = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 4, 4).transpose(0, 2, 1))
+            n = len(P)
+        info = ClosedMapExtendInfo()
+        self._check(self.L.tloam_closed_map_extend(self.h, int(pose_source), _dp(P), n, C.byref(info)), "tloam_closed_map_extend")
+        return info.as_dict()
+
+    def closed_map_extend_info(self) -> dict:
+        info = ClosedMapExtendInfo()
+        self._check(self.L.tloam_closed_map_get_extend_info(self.h, C.byref(info)), "tloam_closed_map_get_extend_info")
+        return info.as_dict()
 
     # ---- the closed map's snapshot: out of this context, into a fresh one (DESIGN.md section 25)
     def closed_map_save(self, clouds=False) -> bytes:
