@@ -1314,6 +1314,65 @@ int tloam_closed_map_read_gone(tloam_ctx* ctx, const double* lo_or_null, const d
                                int64_t* through, int64_t* hits);
 /* Every diff call on a context with nranks > 1: TLOAM_E_INVALID. */
 
+/* ---- the closed map ray-cast: predicted ranges along segments from a pose (additive to ABI 8) ------
+ * From this pose, what should the sensor see?  A ray-cast reads the built closed map with its surfels and writes nothing of
+ * them: it runs on a detached (loaded) map, only when called, and no frame, map, carve, surfel, diff count, localisation or
+ * snapshot changes by a bit.
+ * Per segment end p (sensor frame) and pose matrix M, used as it stands: the ray is the segment from O = (M[12], M[13], M[14])
+ * to E = M p as the localiser forms it ("direction d out to 80 m" is the end 80 d).  The skip rule, the set-up and the stepping
+ * are the carve's (above) with max_range of THIS configuration; a skipped ray has status TLOAM_RAYCAST_SKIPPED, range -1, id -1.
+ * Visited: the start cell, then every cell stepped into, the END CELL INCLUDED (n + 1 cells for n steps; a segment inside one
+ * cell visits that cell).  A visited cell that is a voxel COUNTS when N >= min_count and, with carve_gate set, the carved read
+ * would not leave it out (left out: M >= min_miss && (double) M > miss_ratio * (double) N, M the stored misses).
+ * Per counting voxel with the localiser's record {c, n, eligible} (eligible: the localiser's gate under the current localise and
+ * surfel configuration), D = E - O, DD = (Dx*Dx + Dy*Dy) + Dz*Dz, L = sqrt(DD):
+ *   u = c - O,  tt = ((ux*Dx + uy*Dy) + uz*Dz) / DD,  w = u - tt * D
+ *   centroid test: a hit when 0 <= tt && tt <= 1 && (wx*wx + wy*wy) + wz*wz <= radius2; then t = tt
+ *   plane test, used INSTEAD when planes != 0, the voxel is eligible and den = (nx*Dx + ny*Dy) + nz*Dz != 0:
+ *     tp = ((nx*ux + ny*uy) + nz*uz) / den,  e = tp * D - u
+ *     a hit when 0 <= tp && tp <= 1 && (ex*ex + ey*ey) + ez*ez <= radius2; then t = tp
+ *   planes == 2: a counting voxel that is not eligible or has den == 0 is passed through untested (not counted in `tested`)
+ *   radius = radius_cells * voxel and radius2 = radius * radius, formed on the host in that order
+ * The first hit in visiting order ends the walk: status TLOAM_RAYCAST_HIT_CENTROID or _HIT_PLANE, range = t * L, id the voxel.
+ * No hit by the end cell: TLOAM_RAYCAST_MISS, range -1, id -1.  All sums are integers: two calls, and two contexts, give the
+ * same bytes.  Nothing is stored beyond the last info and the configuration; whatever drops the closed map clears the info. */
+#define TLOAM_RAYCAST_SKIPPED 0
+#define TLOAM_RAYCAST_MISS 1
+#define TLOAM_RAYCAST_HIT_CENTROID 2
+#define TLOAM_RAYCAST_HIT_PLANE 3
+typedef struct tloam_closed_map_raycast_config {   /* the defaults are choices, not measurements */
+  double max_range;     /* 120: a longer segment is skipped (m); > 0, finite */
+  double radius_cells;  /* 0.75: the largest distance from the ray to a centroid (centroid test) or from the plane's crossing to
+                         * the centroid (plane test), in voxel sizes; > 0, <= 2, finite */
+  int64_t min_count;    /* 1: a voxel with fewer points is passed through; >= 1 */
+  int64_t min_miss;     /* 3: the carve gate's M >= min_miss; >= 0 */
+  double miss_ratio;    /* 1.0: ... && M > miss_ratio * N; not NaN */
+  int32_t planes;       /* 1; 0: the centroid test alone, 1: the plane test where it applies, 2: the plane test alone */
+  int32_t carve_gate;   /* 0; 1: voxels the carved read leaves out are passed through (needs a carved map) */
+} tloam_closed_map_raycast_config;
+void tloam_closed_map_raycast_default_config(tloam_closed_map_raycast_config* cfg);
+/* cfg NULL: the defaults.  A value out of its range (NaN too): TLOAM_E_INVALID, and the old configuration stays.  Clears the
+ * last info, not the closed map; persists across tloam_odometry_reset. */
+int tloam_closed_map_raycast_configure(tloam_ctx* ctx, const tloam_closed_map_raycast_config* cfg);
+typedef struct tloam_closed_map_raycast_info {
+  int64_t rays;             /* n of the call */
+  int64_t skipped, missed, hits_centroid, hits_plane;   /* its statuses */
+  int64_t steps;            /* cells visited, the hit cell included */
+  int64_t tested;           /* counting voxels that were put to a test */
+  int32_t launches;         /* kernel launches of the call: 1, or 2 when prepared */
+  int32_t prepared;         /* 1: the call rebuilt the cached voxel records (one more launch) */
+} tloam_closed_map_raycast_info;
+/* Of the last ray-cast; zero when there has been none since the closed map was last dropped. */
+int tloam_closed_map_get_raycast_info(tloam_ctx* ctx, tloam_closed_map_raycast_info* info);
+/* Casts the n >= 1 segments ends_aos (sensor frame) at pose_colmajor (a rigid transform, checked as the localiser's prior).
+ * status_out [n] (uint8) and range_out [n] (double, metres along the segment) are written for every ray, ids_out [n] when it
+ * is not NULL.  TLOAM_E_NOT_READY without a built closed map with surfels, or with carve_gate set on a map that is not carved;
+ * TLOAM_E_INVALID for n == 0, a NULL ends, pose, status_out or range_out, a pose that is not a rigid transform, or nranks > 1.
+ * A refused call leaves every output buffer and all stored state as it was.  One upload of the ends, one launch (two when the
+ * voxel records are stale: the records stay ready for the next localise or diff), one wait. */
+int tloam_closed_map_raycast(tloam_ctx* ctx, const double* ends_aos, size_t n, const double* pose_colmajor, uint8_t* status_out,
+                             double* range_out, int32_t* ids_out_or_null, tloam_closed_map_raycast_info* info_or_null);
+
 /* ---- the closed map's snapshot: a built closed map out of a context and into a fresh one (additive to ABI 8) ------
  * A memory blob; the library opens no files.  It holds, exactly, everything a context needs to answer every read of the closed
  * map and every localisation in it with the bytes of the context that saved: the place, loop, closed map, carve and surfel

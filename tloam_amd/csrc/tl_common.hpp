@@ -883,6 +883,30 @@ struct DiffReadArgs {
 };
 void launch_diff_read(const DiffReadArgs& A, hipStream_t s);
 
+// ---- the closed map ray-cast (tl_raycast.hip): per segment from the pose's translation the first voxel
+// it meets, from the localiser's voxel records.  Nothing of the closed map, the carve, the surfels or the diff is written
+constexpr int kRaycastCtl = 8;   // control words: [0] skipped, [1] missed, [2] centroid hits, [3] plane hits, [4] steps, [5] tested
+struct RaycastWork {
+  const double* ends;         // the segment ends, AoS, sensor frame
+  long long n;
+  double M[16];               // the pose, column-major, as it stands
+  double voxel, origin[3];
+  double max_range, radius2;  // radius2 = radius * radius, radius = radius_cells * voxel
+  long long min_count;        // a voxel with N < min_count is passed through
+  long long min_miss;         // the carve gate (when `gate`): so is one with Mv >= min_miss && (double) Mv > miss_ratio * (double) N
+  double miss_ratio;
+  int gate;
+  int planes;                 // 0 the centroid test alone, 1 the plane test where eligible, 2 the plane test alone
+  VmapTableView map;          // the closed map
+  const LocRecord* rec;       // [nv] the localiser's records
+  const long long* miss;      // [nv] the carve's M (read when `gate`)
+  unsigned char* status;      // [n]
+  double* range;              // [n]
+  int* ids;                   // [n] or null
+  unsigned long long* ctl;    // [kRaycastCtl], zero before the launch
+};
+void launch_raycast(const RaycastWork& W, hipStream_t s);   // one launch
+
 // ---- deskew of a scan under constant velocity (tl_deskew.hip) -------------
 struct DeskewArgs {
   const double* in;               // AoS xyz [3n]

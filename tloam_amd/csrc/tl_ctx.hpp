@@ -514,9 +514,19 @@ struct CmapState {
     diffed = false;
     diff_info = tloam_closed_map_diff_info{};
   }
+  // the ray-cast (tl_api_raycast.hip): its configuration, the per-ray outputs of the last call (13 bytes a
+  // ray, grow-only), the control words and what the last cast reports.  The ends are uploaded where the localiser's scan is
+  // (loc_pts) and the tests read the localiser's records (loc_rec).  Nothing else is stored
+  tloam_closed_map_raycast_config raycast_cfg = {120.0, 0.75, 1, 3, 1.0, 1, 0};   // tloam_closed_map_raycast_default_config
+  DBuf<unsigned char> raycast_status;
+  DBuf<double> raycast_range;
+  DBuf<int> raycast_ids;
+  DBuf<unsigned long long> raycast_ctl;
+  tloam_closed_map_raycast_info raycast_info{};
+  void drop_raycast() { raycast_info = tloam_closed_map_raycast_info{}; }
   // the extension (tl_api_extend.hip): what the last extend of this map reports
   tloam_closed_map_extend_info extend_info{};
-  void drop() {   // the closed map goes, and the carve's counts, the surfels and the diff's counts with it; the configurations
+  void drop() {   // the closed map goes, and the carve's counts, the surfels, the diff's counts and the last ray-cast's info with it; the configurations
                   // and storage stay
     built = false;
     detached = false;
@@ -526,6 +536,7 @@ struct CmapState {
     drop_carve();
     drop_surfels();
     drop_diff();
+    drop_raycast();
   }
 };
 

@@ -485,19 +485,29 @@ __device__ __forceinline__ void span_point(const SpanInput& in, long long g, int
   map_transform_point(*P, x[0], x[1], x[2], &E[0], &E[1], &E[2]);
 }
 
-// ---- a ray through a voxel map's grid (the carve, tl_carve.hip; the diff, tl_diff.hip) ----
-// The ray from O to E: the skip rule, the walk through the grid's cells, every visited cell looked up in the map's slot table,
-// the miss test against an occupied cell's centroid.  tl_carve.hip's header states the operation order; the state is held in
-// named scalars (no run-time indexed array: no scratch).  on_miss(id) is what a miss does; *skipped, *steps, *tested, *misses
-// are set for the ray (a skipped ray: 1, 0, 0, 0).
+// ---- a ray through a voxel map's grid (the carve, tl_carve.hip; the diff, tl_diff.hip; section 28: the
+// ray-cast, tl_raycast.hip) ----
+// The ray from O to E: the skip rule, the set-up of the walk through the grid's cells and its step exist once (RayCells: ray_begin,
+// ray_key, ray_step); tl_carve.hip's header states their operation order.  The state is held in named scalars (no run-time indexed
+// array: no scratch).  Two walks run on it: ray_walk visits the start cell and the first n - 1 cells stepped into and puts the
+// miss test to every voxel among them (the carve, the diff); ray_first_hit visits the end cell too and stops at the first voxel
+// its test accepts (the ray-cast).
 struct RayGrid {
   double voxel, origin[3];
   double max_range, end_margin, radius2;   // radius2 = radius * radius
 };
-template <class OnMiss>
-__device__ __forceinline__ void ray_walk(const RayGrid& W, const VmapTableView& map, double Ox, double Oy, double Oz, double Ex,
-                                         double Ey, double Ez, unsigned long long* skipped, unsigned long long* steps,
-                                         unsigned long long* tested, unsigned long long* misses, OnMiss on_miss) {
+struct RayCells {
+  double Dx, Dy, Dz, DD, L;    // D = E - O, DD = |D|^2 summed (x + y) + z, L = sqrt(DD)
+  int cx, cy, cz;              // the current cell
+  int ex, ey, ez;              // the end cell
+  int stx, sty, stz;
+  double tx, ty, tz;           // tMax: +inf on an axis that steps no more
+  double tdx, tdy, tdz;        // tDelta (not read on an axis that never steps)
+  int n;                       // the steps from the start cell to the end cell
+};
+// false: the ray is skipped (E not finite, L > max_range, L == 0, the cell of O or of E beyond the grid)
+__device__ __forceinline__ bool ray_begin(const RayGrid& W, double Ox, double Oy, double Oz, double Ex, double Ey, double Ez,
+                                          RayCells* R) {
   const double kInf = __builtin_huge_val(), kLimit = (double)(1ll << kVmapBits);
   const double Dx = Ex - Ox, Dy = Ey - Oy, Dz = Ez - Oz;
   const double DD = (Dx * Dx + Dy * Dy) + Dz * Dz;
@@ -509,52 +519,94 @@ __device__ __forceinline__ void ray_walk(const RayGrid& W, const VmapTableView& 
   ok = ok && !(L > W.max_range) && !(L == 0.0);
   ok = ok && fabs(fx) < kLimit && fabs(fy) < kLimit && fabs(fz) < kLimit && fabs(gx) < kLimit && fabs(gy) < kLimit &&
        fabs(gz) < kLimit;
-  if (!ok) {
+  if (!ok) return false;
+  R->Dx = Dx; R->Dy = Dy; R->Dz = Dz; R->DD = DD; R->L = L;
+  const int cx = (int)fx, cy = (int)fy, cz = (int)fz;
+  const int ex = (int)gx, ey = (int)gy, ez = (int)gz;
+  R->cx = cx; R->cy = cy; R->cz = cz;
+  R->ex = ex; R->ey = ey; R->ez = ez;
+  const double dx = s1x - s0x, dy = s1y - s0y, dz = s1z - s0z;
+  R->stx = dx > 0.0 ? 1 : dx < 0.0 ? -1 : 0; R->sty = dy > 0.0 ? 1 : dy < 0.0 ? -1 : 0; R->stz = dz > 0.0 ? 1 : dz < 0.0 ? -1 : 0;
+  R->tx = cx == ex ? kInf : dx > 0.0 ? ((fx + 1.0) - s0x) / dx : dx < 0.0 ? (fx - s0x) / dx : kInf;
+  R->ty = cy == ey ? kInf : dy > 0.0 ? ((fy + 1.0) - s0y) / dy : dy < 0.0 ? (fy - s0y) / dy : kInf;
+  R->tz = cz == ez ? kInf : dz > 0.0 ? ((fz + 1.0) - s0z) / dz : dz < 0.0 ? (fz - s0z) / dz : kInf;
+  R->tdx = (double)R->stx / dx; R->tdy = (double)R->sty / dy; R->tdz = (double)R->stz / dz;
+  R->n = abs(ex - cx) + abs(ey - cy) + abs(ez - cz);
+  return true;
+}
+// the current cell's key
+__device__ __forceinline__ unsigned long long ray_key(const RayCells& R) {
+  return (unsigned long long)(R.cx + (1 << kVmapBits)) | ((unsigned long long)(R.cy + (1 << kVmapBits)) << 21) |
+         ((unsigned long long)(R.cz + (1 << kVmapBits)) << 42);
+}
+// into the next cell: the axis of the smallest tMax, a tie going to the lowest axis
+__device__ __forceinline__ void ray_step(RayCells* R) {
+  const double kInf = __builtin_huge_val();
+  const bool y = R->ty < R->tx;
+  const bool z = R->tz < (y ? R->ty : R->tx);
+  if (z) {
+    R->cz += R->stz;
+    R->tz = R->cz == R->ez ? kInf : R->tz + R->tdz;
+  } else if (y) {
+    R->cy += R->sty;
+    R->ty = R->cy == R->ey ? kInf : R->ty + R->tdy;
+  } else {
+    R->cx += R->stx;
+    R->tx = R->cx == R->ex ? kInf : R->tx + R->tdx;
+  }
+}
+
+// Every visited cell looked up in the map's slot table, the miss test against an occupied cell's centroid.  on_miss(id) is what
+// a miss does; *skipped, *steps, *tested, *misses are set for the ray (a skipped ray: 1, 0, 0, 0).
+template <class OnMiss>
+__device__ __forceinline__ void ray_walk(const RayGrid& W, const VmapTableView& map, double Ox, double Oy, double Oz, double Ex,
+                                         double Ey, double Ez, unsigned long long* skipped, unsigned long long* steps,
+                                         unsigned long long* tested, unsigned long long* misses, OnMiss on_miss) {
+  RayCells R;
+  if (!ray_begin(W, Ox, Oy, Oz, Ex, Ey, Ez, &R)) {
     *skipped = 1ull;
     return;
   }
-  int cx = (int)fx, cy = (int)fy, cz = (int)fz;
-  const int ex = (int)gx, ey = (int)gy, ez = (int)gz;
-  const double dx = s1x - s0x, dy = s1y - s0y, dz = s1z - s0z;
-  const int stx = dx > 0.0 ? 1 : dx < 0.0 ? -1 : 0, sty = dy > 0.0 ? 1 : dy < 0.0 ? -1 : 0, stz = dz > 0.0 ? 1 : dz < 0.0 ? -1 : 0;
-  double tx = cx == ex ? kInf : dx > 0.0 ? ((fx + 1.0) - s0x) / dx : dx < 0.0 ? (fx - s0x) / dx : kInf;
-  double ty = cy == ey ? kInf : dy > 0.0 ? ((fy + 1.0) - s0y) / dy : dy < 0.0 ? (fy - s0y) / dy : kInf;
-  double tz = cz == ez ? kInf : dz > 0.0 ? ((fz + 1.0) - s0z) / dz : dz < 0.0 ? (fz - s0z) / dz : kInf;
-  const double tdx = (double)stx / dx, tdy = (double)sty / dy, tdz = (double)stz / dz;   // (not read on an axis that never steps)
-  const int n = abs(ex - cx) + abs(ey - cy) + abs(ez - cz);
-  const double tlim = 1.0 - W.end_margin / L;
-  *steps = (unsigned long long)n;
-  for (int k = 0; k < n; ++k) {
-    const unsigned long long key = (unsigned long long)(cx + (1 << kVmapBits)) |
-                                   ((unsigned long long)(cy + (1 << kVmapBits)) << 21) |
-                                   ((unsigned long long)(cz + (1 << kVmapBits)) << 42);
-    const int id = id_table_find(map.ptab, map.pmask, map.pkey, key);
+  const double tlim = 1.0 - W.end_margin / R.L;
+  *steps = (unsigned long long)R.n;
+  for (int k = 0; k < R.n; ++k) {
+    const int id = id_table_find(map.ptab, map.pmask, map.pkey, ray_key(R));
     if (id >= 0) {
       (*tested)++;
       const long long N = map.pn[id];
-      const double ux = centroid(W.origin[0], W.voxel, cx, map.pqx[id], N) - Ox;
-      const double uy = centroid(W.origin[1], W.voxel, cy, map.pqy[id], N) - Oy;
-      const double uz = centroid(W.origin[2], W.voxel, cz, map.pqz[id], N) - Oz;
-      const double tt = ((ux * Dx + uy * Dy) + uz * Dz) / DD;
-      const double wx = ux - tt * Dx, wy = uy - tt * Dy, wz = uz - tt * Dz;
+      const double ux = centroid(W.origin[0], W.voxel, R.cx, map.pqx[id], N) - Ox;
+      const double uy = centroid(W.origin[1], W.voxel, R.cy, map.pqy[id], N) - Oy;
+      const double uz = centroid(W.origin[2], W.voxel, R.cz, map.pqz[id], N) - Oz;
+      const double tt = ((ux * R.Dx + uy * R.Dy) + uz * R.Dz) / R.DD;
+      const double wx = ux - tt * R.Dx, wy = uy - tt * R.Dy, wz = uz - tt * R.Dz;
       if (0.0 <= tt && tt < tlim && (wx * wx + wy * wy) + wz * wz <= W.radius2) {
         (*misses)++;
         on_miss(id);
       }
     }
-    const bool y = ty < tx;
-    const bool z = tz < (y ? ty : tx);
-    if (z) {
-      cz += stz;
-      tz = cz == ez ? kInf : tz + tdz;
-    } else if (y) {
-      cy += sty;
-      ty = cy == ey ? kInf : ty + tdy;
-    } else {
-      cx += stx;
-      tx = cx == ex ? kInf : tx + tdx;
-    }
+    ray_step(&R);
   }
+}
+
+// The walk that stops: the start cell, then every cell stepped into, the end cell included (n + 1 cells), each looked up in the
+// map's slot table; test(id) is put to every voxel among them and the first one it accepts ends the walk.  Returns that voxel's
+// id, or -1 when no visited voxel is accepted; *visited: the cells looked up, the accepted one included.  (W.end_margin and
+// W.radius2 are not read: the test is the caller's.)
+template <class Test>
+__device__ __forceinline__ int ray_first_hit(const VmapTableView& map, RayCells* R, unsigned long long* visited, Test test) {
+  unsigned long long seen = 0ull;
+  int got = -1;
+  for (int k = 0; k <= R->n; ++k) {
+    const int id = id_table_find(map.ptab, map.pmask, map.pkey, ray_key(*R));
+    ++seen;
+    if (id >= 0 && test(id)) {
+      got = id;
+      break;
+    }
+    if (k < R->n) ray_step(R);
+  }
+  *visited = seen;
+  return got;
 }
 
 }  // namespace tl

@@ -290,3 +290,40 @@ def write_labelled_scan_pcd(path: str, points_world, labels) -> int:
               "DATA binary\n")
     _write_renamed(path, header.encode("ascii") + rec.tobytes())
     return n
+
+
+# ---- the closed map ray-cast: where the cast rays met the map
+_HIT_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("status", "u1")])
+
+
+def write_raycast_pcd(path: str, pose, ends, status, ranges) -> int:
+    """Writes the hit points of a ray-cast (H.closed_map_raycast(ends, pose) -> status, ranges) as one PCD v0.7, DATA binary:
+    x y z float64 (`F 8`) in the map's frame -- the point `range` along the segment from the pose's translation to the end under
+    the pose -- and `status` uint8 (`U 1`: 2 HIT_CENTROID, 3 HIT_PLANE).  Rays without a hit are left out -> the points written.
+    Written to a temporary name beside `path` and renamed."""
+    P = np.asarray(pose, dtype=np.float64).reshape(4, 4)
+    e = np.asarray(ends, dtype=np.float64).reshape(-1, 3)
+    k = np.asarray(status, dtype="u1").reshape(-1)
+    r = np.asarray(ranges, dtype=np.float64).reshape(-1)
+    if not len(e) == len(k) == len(r):
+        raise ValueError(f"{len(e)} ends, {len(k)} statuses, {len(r)} ranges")
+    hit = k >= 2
+    D = e[hit] @ P[:3, :3].T                          # E - O
+    L = np.sqrt((D * D).sum(axis=1))
+    X = P[:3, 3] + D * (r[hit] / L)[:, None]
+    n = int(hit.sum())
+    rec = np.empty(n, _HIT_DTYPE)
+    rec["x"], rec["y"], rec["z"], rec["status"] = X[:, 0], X[:, 1], X[:, 2], k[hit]
+    header = ("# .PCD v0.7 - Point Cloud Data file format\n"
+              "VERSION 0.7\n"
+              "FIELDS x y z status\n"
+              "SIZE 8 8 8 1\n"
+              "TYPE F F F U\n"
+              "COUNT 1 1 1 1\n"
+              f"WIDTH {n}\n"
+              "HEIGHT 1\n"
+              "VIEWPOINT 0 0 0 1 0 0 0\n"
+              f"POINTS {n}\n"
+              "DATA binary\n")
+    _write_renamed(path, header.encode("ascii") + rec.tobytes())
+    return n

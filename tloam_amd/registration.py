@@ -240,6 +240,27 @@ DIFF_ACCUMULATE = 1   # TLOAM_DIFF_ACCUMULATE: the call adds to the stored count
 DIFF_INVALID, DIFF_SURFACE, DIFF_OCCUPIED, DIFF_NEW = 0, 1, 2, 3
 
 
+class ClosedMapRaycastConfig(C.Structure):
+    """tloam_closed_map_raycast_config: the longest segment, the hit radius in voxel sizes, the fewest points of a voxel a ray
+    can hit, the carve gate (min_miss, miss_ratio, carve_gate) and which test a voxel is put to (planes: 0 the centroid test
+    alone, 1 the plane test where the voxel is eligible, 2 the plane test alone).  The defaults are
+    choices, not measurements."""
+    _fields_ = [("max_range", C.c_double), ("radius_cells", C.c_double), ("min_count", C.c_int64), ("min_miss", C.c_int64),
+                ("miss_ratio", C.c_double), ("planes", C.c_int32), ("carve_gate", C.c_int32)]
+
+
+class ClosedMapRaycastInfo(C.Structure):
+    """tloam_closed_map_raycast_info."""
+    _fields_ = [("rays", C.c_int64), ("skipped", C.c_int64), ("missed", C.c_int64), ("hits_centroid", C.c_int64),
+                ("hits_plane", C.c_int64), ("steps", C.c_int64), ("tested", C.c_int64), ("launches", C.c_int32),
+                ("prepared", C.c_int32)]
+
+    as_dict = _int_fields
+
+
+RAYCAST_SKIPPED, RAYCAST_MISS, RAYCAST_HIT_CENTROID, RAYCAST_HIT_PLANE = 0, 1, 2, 3   # TLOAM_RAYCAST_*
+
+
 SNAPSHOT_CLOUDS = 1   # TLOAM_SNAPSHOT_CLOUDS: the keyframes' eight clouds go into the snapshot too
 
 
@@ -622,6 +643,11 @@ def load_library():
         "tloam_closed_map_diff": (C.c_int, [vp, dp, sz, dp, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_int32),
                                             C.POINTER(ClosedMapDiffInfo)]),
         "tloam_closed_map_read_diff": (C.c_int, [vp, sz, sz, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+        "tloam_closed_map_raycast_default_config": (None, [C.POINTER(ClosedMapRaycastConfig)]),
+        "tloam_closed_map_raycast_configure": (C.c_int, [vp, C.POINTER(ClosedMapRaycastConfig)]),
+        "tloam_closed_map_get_raycast_info": (C.c_int, [vp, C.POINTER(ClosedMapRaycastInfo)]),
+        "tloam_closed_map_raycast": (C.c_int, [vp, dp, sz, dp, C.POINTER(C.c_uint8), dp, C.POINTER(C.c_int32),
+                                               C.POINTER(ClosedMapRaycastInfo)]),
         "tloam_closed_map_read_gone": (C.c_int, [vp, dp, dp, C.c_int64, C.c_double, sz, C.POINTER(sz), dp, C.POINTER(C.c_int64),
                                                  C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
         "tloam_closed_map_save_size": (C.c_int, [vp, C.c_int, C.POINTER(sz)]),
@@ -679,6 +705,8 @@ EXPORTED_SYMBOLS = (
     "tloam_closed_map_relocalise", "tloam_closed_map_relocalise_hypotheses",
     "tloam_closed_map_diff_default_config", "tloam_closed_map_diff_configure", "tloam_closed_map_get_diff_info",
     "tloam_closed_map_diff", "tloam_closed_map_read_diff", "tloam_closed_map_read_gone",
+    "tloam_closed_map_raycast_default_config", "tloam_closed_map_raycast_configure", "tloam_closed_map_get_raycast_info",
+    "tloam_closed_map_raycast",
     "tloam_closed_map_save_size", "tloam_closed_map_save", "tloam_closed_map_probe", "tloam_closed_map_load",
     "tloam_rccl_unique_id", "tloam_comm_init_rccl",
     "tloam_comm_mailbox_export", "tloam_comm_init_mailbox",
@@ -1627,6 +1655,33 @@ class HipRegistration:
         return self._read_box(self.L.tloam_closed_map_read_gone, "tloam_closed_map_read_gone", head,
                               [(3, np.float64), (None, np.int64), (None, np.int64), (None, np.int64)])
 
+    # ---- the closed map ray-cast: predicted ranges along segments from a pose
+    def closed_map_raycast_configure(self, cfg: ClosedMapRaycastConfig | None = None, **over):
+        """the ray-cast's configuration (default_closed_map_raycast_config(**over) when cfg is None); clears the last info, not
+        the closed map.  Kept across odometry_reset; a refused configuration leaves the old one."""
+        cfg = cfg if cfg is not None else default_closed_map_raycast_config(**over)
+        self._check(self.L.tloam_closed_map_raycast_configure(self.h, C.byref(cfg)), "tloam_closed_map_raycast_configure")
+
+    def closed_map_raycast(self, ends, pose, want_ids=False):
+        """the segments from `pose`'s translation to `ends` (n, 3; sensor frame) under `pose` (4 x 4) through the closed map ->
+        (status (n,) uint8: RAYCAST_SKIPPED, RAYCAST_MISS, RAYCAST_HIT_CENTROID, RAYCAST_HIT_PLANE; ranges (n,) float64, metres
+        along the segment to the first hit, -1.0 without one; ids (n,) int32 of the voxel hit, -1 for none, or None without
+        want_ids; info dict)"""
+        e = _aos(ends)
+        status = np.zeros(max(len(e), 1), np.uint8)
+        ranges = np.zeros(max(len(e), 1), np.float64)
+        ids = np.zeros(max(len(e), 1), np.int32) if want_ids else None
+        info = ClosedMapRaycastInfo()
+        self._check(self.L.tloam_closed_map_raycast(self.h, _dp(e), len(e), _dp(_colmajor(pose)),
+                                                    status.ctypes.data_as(C.POINTER(C.c_uint8)), _dp(ranges), _ip(ids),
+                                                    C.byref(info)), "tloam_closed_map_raycast")
+        return status[: len(e)].copy(), ranges[: len(e)].copy(), (ids[: len(e)].copy() if want_ids else None), info.as_dict()
+
+    def closed_map_raycast_info(self) -> dict:
+        info = ClosedMapRaycastInfo()
+        self._check(self.L.tloam_closed_map_get_raycast_info(self.h, C.byref(info)), "tloam_closed_map_get_raycast_info")
+        return info.as_dict()
+
     def fitness(self):
         f, r = C.c_double(0), C.c_double(0)
         rc = self.L.tloam_fitness(self.h, C.byref(f), C.byref(r))
@@ -1888,6 +1943,12 @@ def default_closed_map_carve_config(**over) -> ClosedMapCarveConfig:
     """tloam_closed_map_carve_default_config (max_range 60, end_margin 1, radius 0.25, ray_mask 0: the build's) with keyword
     overrides, e.g. max_range=20.0, radius=float("inf")"""
     return _strict_config(ClosedMapCarveConfig, "tloam_closed_map_carve_default_config", over)
+
+
+def default_closed_map_raycast_config(**over) -> ClosedMapRaycastConfig:
+    """tloam_closed_map_raycast_default_config (max_range 120, radius_cells 0.75, planes 1, min_count 1, min_miss 3,
+    miss_ratio 1, carve_gate 0) with `over` applied; an unknown field raises"""
+    return _strict_config(ClosedMapRaycastConfig, "tloam_closed_map_raycast_default_config", over)
 
 
 def default_closed_map_diff_config(**over) -> ClosedMapDiffConfig:
