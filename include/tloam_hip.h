@@ -1373,6 +1373,97 @@ int tloam_closed_map_get_raycast_info(tloam_ctx* ctx, tloam_closed_map_raycast_i
 int tloam_closed_map_raycast(tloam_ctx* ctx, const double* ends_aos, size_t n, const double* pose_colmajor, uint8_t* status_out,
                              double* range_out, int32_t* ids_out_or_null, tloam_closed_map_raycast_info* info_or_null);
 
+/* ---- free space for the closed map: an occupancy grid from the rays (additive to ABI 8) ------
+ * A grid beside the closed map that records where rays saw THROUGH, so that a cell reads occupied, free or unknown.  Off until
+ * tloam_closed_map_free_reset; nothing of the map, the carve, the surfels, a diff's counts, the localiser or the snapshot
+ * changes by a bit, and the grid is not saved.  Whatever drops the closed map (a build, a load, the configures that empty it)
+ * drops the grid; tloam_closed_map_extend leaves it alone: occupancy is resolved when the grid is READ, against the map as it
+ * then is, so new voxels need no rewrite.
+ * Storage: dense bricks of 4 x 4 x 4 cells of the map's grid (the same voxel and origin), one uint64 a brick, bit
+ * ((cz & 3) << 4) | ((cy & 3) << 2) | (cx & 3) set when a ray saw through cell c; the brick of a cell is c >> 2 per axis
+ * (flooring), the grid a box of bricks fixed at the reset, brick (bx, by, bz) at word ((bz - bz_lo) * nby + (by - by_lo)) * nbx
+ * + (bx - bx_lo).  Cells outside the box are counted, not recorded.
+ * The free condition of a ray from O to E (set-up, skip rule, visited cells and stepping are the carve's: the start cell and the
+ * first n - 1 cells stepped into, the end cell never): a visited cell has an entry parameter t_in, 0 for the start cell, else
+ * the tMax of the axis the step into it took, read before the step updates it; with tlim = 1.0 - end_margin / L the cell is
+ * marked when t_in < tlim, whether or not the map has a voxel there.  The marked cells are a prefix of the visited ones; a ray
+ * with L <= end_margin marks nothing.
+ * A voxel COUNTS when N >= min_count and not (carve_gate && M >= min_miss && (double) M > miss_ratio * (double) N).
+ * All sums are integers and bits are only ever set: two calls, and two contexts, give the same bytes.
+ * Every call here on a context with nranks > 1: TLOAM_E_INVALID. */
+#define TLOAM_OCCUPANCY_INVALID 0    /* the point is not finite, or its cell has |i| >= 2^20 */
+#define TLOAM_OCCUPANCY_UNKNOWN 1
+#define TLOAM_OCCUPANCY_FREE 2       /* not a counting voxel, inside the box, its bit set */
+#define TLOAM_OCCUPANCY_OCCUPIED 3   /* the cell is a voxel that counts */
+typedef struct tloam_closed_map_free_config {   /* the defaults are choices, not measurements */
+  double max_range;     /* 60: a longer ray is skipped (m); > 0, finite */
+  double end_margin;    /* 1.0: a cell entered within this distance of the ray's end is not marked (m); >= 0, finite */
+  int64_t max_bytes;    /* 1 GiB: a reset whose grid needs more is refused; >= 8 */
+  int64_t min_count;    /* 1: a voxel with fewer points does not count; >= 1 */
+  int64_t min_miss;     /* 3: the carve gate's M >= min_miss; >= 0 */
+  double miss_ratio;    /* 1.0: ... && M > miss_ratio * N; not NaN */
+  int32_t ray_mask;     /* 0: the build's cloud mask; else the keyframe clouds whose points are rays (bit side * 4 + kind), <= 0xFF */
+  int32_t carve_gate;   /* 0; 1: voxels the carved read leaves out do not count (needs a carved map when the grid is read) */
+} tloam_closed_map_free_config;
+void tloam_closed_map_free_default_config(tloam_closed_map_free_config* cfg);
+/* cfg NULL: the defaults.  A value out of its range (NaN too): TLOAM_E_INVALID, and the old configuration stays.  Drops the
+ * grid, not the closed map; persists across tloam_odometry_reset. */
+int tloam_closed_map_free_configure(tloam_ctx* ctx, const tloam_closed_map_free_config* cfg);
+typedef struct tloam_closed_map_free_info {
+  int64_t lo_cells[3];      /* the box: its lowest cell per axis (a multiple of 4) ... */
+  int64_t n_bricks[3];      /* ... its bricks per axis ... */
+  int64_t bytes;            /* ... and 8 * n_bricks[0] * n_bricks[1] * n_bricks[2] */
+  int64_t keyframes;        /* cumulative: keyframes [0, keyframes) have been walked by _free_add_keyframes */
+  int64_t scans;            /* cumulative: _free_add_scan calls */
+  int64_t free_cells;       /* popcount of the grid */
+  int64_t bricks_nonzero;
+  int64_t rays;             /* of the last add: its rays ... */
+  int64_t skipped_rays;
+  int64_t cells_marked;     /* ... the cells with the free condition inside the box, counted with multiplicity ... */
+  int64_t cells_outside;    /* ... and the same outside the box */
+  int32_t launches;         /* kernel launches of the last reset (1) or add (2) */
+  int32_t reserved0;
+} tloam_closed_map_free_info;
+/* All zero when there is no grid. */
+int tloam_closed_map_get_free_info(tloam_ctx* ctx, tloam_closed_map_free_info* info);
+/* Allocates and zeroes the grid over the cells [lo_cells, hi_cells] (inclusive, rounded out to bricks), or with both NULL over
+ * the auto box: over the K poses the closed map holds, per axis c_k = floor((O_k - o) / v), R = (int64) ceil(max_range / v) + 1,
+ * lo = min c_k - R, hi = max c_k + R, both clamped to +-(2^20 - 1), formed on the host in double in that order (without a
+ * pose: the cell 0); every non-skipped keyframe ray lies inside it.  TLOAM_E_INVALID for one NULL, lo > hi, a cell with
+ * |c| >= 2^20 or a grid of more than max_bytes; TLOAM_E_NOT_READY without a built closed map.  A refused reset leaves the
+ * previous grid as it was.  One launch, one wait. */
+int tloam_closed_map_free_reset(tloam_ctx* ctx, const int64_t* lo_cells_or_null, const int64_t* hi_cells_or_null);
+/* Walks the rays of keyframes [info.keyframes, K), K the keyframes the closed map holds: the ones the grid has not seen (after an
+ * extend, the new ones).  Ray set, order, O, E and skip rule are tloam_closed_map_carve's, under ray_mask.  TLOAM_E_NOT_READY
+ * without a grid, or on a map loaded without its clouds.  Two launches, one wait. */
+int tloam_closed_map_free_add_keyframes(tloam_ctx* ctx, tloam_closed_map_free_info* info_or_null);
+/* Walks the rays of the n >= 1 points points_aos (sensor frame) at pose_colmajor (a rigid transform, checked as the diff's): O,
+ * E and ray order are tloam_closed_map_diff's.  This is how a map loaded without its clouds gains free space.  TLOAM_E_NOT_READY
+ * without a grid; TLOAM_E_INVALID for n == 0, a NULL points or pose, or a bad pose; a refused call changes nothing.  Two
+ * launches, one wait. */
+int tloam_closed_map_free_add_scan(tloam_ctx* ctx, const double* points_aos, size_t n, const double* pose_colmajor,
+                                   tloam_closed_map_free_info* info_or_null);
+/* The grid's words [first, first + count) as they stand (the layout above): what a caller that keeps or ships a grid reads, and
+ * what the tests compare bit for bit.  TLOAM_E_NOT_READY without a grid, TLOAM_E_INVALID for a range beyond the grid. */
+int tloam_closed_map_read_free_words(tloam_ctx* ctx, size_t first, size_t count, uint64_t* words);
+/* The state of n >= 1 points (pose NULL: in the map frame; else in the sensor frame of pose_colmajor): state_out [n] (uint8,
+ * TLOAM_OCCUPANCY_*), ids_out [n] when not NULL (the voxel for OCCUPIED, else -1), counts_out [4] when not NULL (points per
+ * state).  TLOAM_E_NOT_READY without a grid, or with carve_gate set on a map that is not carved.  One launch, one wait. */
+int tloam_closed_map_occupancy(tloam_ctx* ctx, const double* points_aos, size_t n, const double* pose_colmajor_or_null,
+                               uint8_t* state_out, int32_t* ids_out_or_null, int64_t* counts_out_or_null);
+/* The centres o + (c + 0.5) * v of the FREE cells (a cell that is a counting voxel is left out), brick index ascending, then bit
+ * ascending; lo and hi (both or neither) a metric box applied to the centres, inclusive.  *n: their number; with capacity < *n
+ * nothing is written and TLOAM_E_INVALID is returned (tloam_closed_map_read_box's convention). */
+int tloam_closed_map_read_free(tloam_ctx* ctx, const double* lo_or_null, const double* hi_or_null, size_t capacity, size_t* n,
+                               double* centres_aos);
+/* A 2-D grid over the box's x-y footprint, y outer: *nx = 4 n_bricks[0], *ny = 4 n_bricks[1], state_out [*ny * *nx] (uint8).  The
+ * band is the cells floor((z_lo - o_z) / v) .. floor((z_hi - o_z) / v) clipped to the box.  A column is OCCUPIED if any band
+ * cell is a counting voxel, else FREE if at least min_free >= 1 band cells are FREE, else UNKNOWN.  TLOAM_E_INVALID for
+ * z_lo > z_hi, a bound that is not finite or min_free < 1; with capacity < *ny * *nx nothing is written, the size is reported
+ * and TLOAM_E_INVALID is returned. */
+int tloam_closed_map_free_columns(tloam_ctx* ctx, double z_lo, double z_hi, int64_t min_free, uint8_t* state_out, size_t capacity,
+                                  size_t* nx, size_t* ny);
+
 /* ---- the closed map's snapshot: a built closed map out of a context and into a fresh one (additive to ABI 8) ------
  * A memory blob; the library opens no files.  It holds, exactly, everything a context needs to answer every read of the closed
  * map and every localisation in it with the bytes of the context that saved: the place, loop, closed map, carve and surfel

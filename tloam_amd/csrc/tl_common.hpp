@@ -907,6 +907,70 @@ struct RaycastWork {
 };
 void launch_raycast(const RaycastWork& W, hipStream_t s);   // one launch
 
+// ---- the closed map's free space (tl_free.hip): a dense grid of 4 x 4 x 4-cell bricks, one 64-bit word a
+// brick, bit ((cz & 3) << 4) | ((cy & 3) << 2) | (cx & 3) set when a ray saw through the cell.  Nothing of the closed map, the
+// carve, the surfels or the diff is written; whether a cell is a voxel is resolved when the grid is read
+constexpr int kFreeCtl = 8;      // control words: [0] skipped rays, [1] cells marked, [2] cells outside, [3] free cells, [4] bricks nonzero
+struct FreeGrid {
+  unsigned long long* words;  // [nwords]: brick (bx, by, bz) at ((bz - blo[2]) * nb[1] + (by - blo[1])) * nb[0] + (bx - blo[0])
+  int blo[3];                 // the lowest brick of the box per axis (brick = cell >> 2)
+  int nb[3];                  // bricks per axis
+  long long nwords;
+};
+struct FreeWork {
+  SpanInput in;               // the keyframe form: the rays of all spans, under the poses the closed map holds
+  const double* pts;          // the scan form: the ends, AoS, sensor frame ...
+  long long n;
+  double M[16];               // ... at this pose, column-major, as it stands
+  double voxel, origin[3];
+  double max_range, end_margin;
+  VmapTableView map;          // the closed map (not read by the walk)
+  long long nv;
+  FreeGrid g;
+  unsigned long long* ctl;    // [kFreeCtl], zero before the launches
+};
+int launch_free_clear(const FreeGrid& g, hipStream_t s);                 // the words zeroed; returns the launches it made
+int launch_free_rays(const FreeWork& W, bool spans, hipStream_t s);      // rays | count: the same two launches for every size
+struct FreeQuery {            // what a read of the grid resolves occupancy with
+  VmapTableView map;          // the closed map
+  const long long* miss;      // [nv] the carve's M (read when `gate`)
+  long long min_count, min_miss;
+  double miss_ratio;
+  int gate;
+  int reserved0;
+  double voxel, origin[3];
+  FreeGrid g;
+};
+struct FreePointsArgs {
+  FreeQuery q;
+  const double* pts;          // AoS
+  long long n;
+  int posed;                  // 1: the points are in the sensor frame of M; 0: in the map frame
+  int reserved0;
+  double M[16];
+  unsigned char* state;       // [n]
+  int* ids;                   // [n] or null
+  unsigned long long* ctl;    // [0..3] points per state, zero before the launch
+};
+void launch_free_points(const FreePointsArgs& A, hipStream_t s);
+struct FreeCellsArgs {
+  FreeQuery q;
+  int boxed;                  // 1: only centres inside [lo, hi] (inclusive)
+  int reserved0;
+  double lo[3], hi[3];
+  double* out_c;              // AoS centres, brick index ascending, then bit ascending
+  unsigned long long* look;   // [blocks + 1] look-back words, zero before the launch
+  unsigned long long* ctl;    // [0] start tickets, [1] fault, [2] cells written; zero before the launch
+};
+void launch_free_cells(const FreeCellsArgs& A, hipStream_t s);
+struct FreeColumnsArgs {
+  FreeQuery q;
+  int z0, z1;                 // the band's cells, clipped to the box (z0 > z1: empty)
+  long long min_free;
+  unsigned char* state;       // [4 nb[1]][4 nb[0]], y outer
+};
+void launch_free_columns(const FreeColumnsArgs& A, hipStream_t s);
+
 // ---- deskew of a scan under constant velocity (tl_deskew.hip) -------------
 struct DeskewArgs {
   const double* in;               // AoS xyz [3n]

@@ -526,8 +526,27 @@ struct CmapState {
   void drop_raycast() { raycast_info = tloam_closed_map_raycast_info{}; }
   // the extension (tl_api_extend.hip): what the last extend of this map reports
   tloam_closed_map_extend_info extend_info{};
-  void drop() {   // the closed map goes, and the carve's counts, the surfels, the diff's counts and the last ray-cast's info with it; the configurations
-                  // and storage stay
+  // the free space (tl_api_free.hip): its configuration, the grid of brick words and its box, what the
+  // grid reports, the reads' scratch.  The grid belongs to the closed map it was gathered beside and goes with it (its memory
+  // too: it can be large); an extend leaves it alone
+  struct FreeState {
+    tloam_closed_map_free_config cfg = {60.0, 1.0, (int64_t)1 << 30, 1, 3, 1.0, 0, 0};   // tloam_closed_map_free_default_config
+    DBuf<unsigned long long> words, ctl, look, rd_ctl;
+    DBuf<double> rd_c;
+    DBuf<unsigned char> state;
+    DBuf<int> ids;
+    tl::FreeGrid grid{};
+    bool have = false;             // a reset has succeeded since the last drop
+    tloam_closed_map_free_info info{};
+    void drop() {
+      have = false;
+      info = tloam_closed_map_free_info{};
+      grid = tl::FreeGrid{};
+      words.release();             // (hipFree waits for the launches that use it)
+    }
+  } free;
+  void drop() {   // the closed map goes, and the carve's counts, the surfels, the diff's counts, the last ray-cast's info and the free-space
+                  // grid with it; the configurations and storage stay
     built = false;
     detached = false;
     info = tloam_closed_map_info{};
@@ -537,6 +556,7 @@ struct CmapState {
     drop_surfels();
     drop_diff();
     drop_raycast();
+    free.drop();
   }
 };
 
@@ -1007,7 +1027,8 @@ struct SpanUpload {
 // One pass over the points the closed map was built from (the carve, the surfels): the span table for `mask` over the build's
 // keyframes uploaded beside the build's poses, the fields every pass's Work has filled (in, voxel, origin, map, nv, ctl), the
 // launches of fill_and_launch(W), which fills the rest and returns their number, the eight words of `ctl` read back, one wait.
-// reserve() sizes the pass's arrays, `ctl` among them, after waiting when one that it replaces may still be read
+// reserve() sizes the pass's arrays, `ctl` among them, after waiting when one that it replaces may still be read.  `first`: the
+// pass runs over keyframes [first, K) alone (the free space's add after an extension): their spans, their poses
 struct CmapPassOut {
   unsigned long long ctl[8];
   size_t K;        // the build's keyframes: later ones add nothing
@@ -1015,18 +1036,20 @@ struct CmapPassOut {
   int launches;
 };
 template <class Work, class Reserve, class Launch>
-int cmap_pass(tloam_ctx* c, int mask, const DBuf<unsigned long long>& ctl, Reserve reserve, Launch fill_and_launch, CmapPassOut* out) {
+int cmap_pass(tloam_ctx* c, int mask, const DBuf<unsigned long long>& ctl, Reserve reserve, Launch fill_and_launch, CmapPassOut* out,
+              size_t first = 0) {
   const CmapState& M = c->cmap;
   out->K = M.poses.size() / 16;
+  first = std::min(first, out->K);
   std::vector<tl::CmapSpan> spans;
-  cmap_span_table(c->place, 0, out->K, mask, &spans, &out->n, nullptr);
+  cmap_span_table(c->place, first, out->K, mask, &spans, &out->n, nullptr);
   HIPC(c, hipSetDevice(c->device));
   int rc = reserve();
   if (rc != TLOAM_OK) return rc;
   SpanUpload up;   // the pass's own, freed with it
   Work W;
   memset(&W, 0, sizeof(W));
-  rc = up.upload(c, spans, out->n, M.poses.data(), out->K, &W.in);
+  rc = up.upload(c, spans, out->n, M.poses.data() + 16 * first, out->K - first, &W.in);
   if (rc != TLOAM_OK) return rc;
   W.voxel = M.cfg.voxel;
   for (int a = 0; a < 3; ++a) W.origin[a] = M.cfg.origin[a];

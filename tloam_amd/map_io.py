@@ -1,6 +1,7 @@
 """PCD export of the global map, of the merged voxel map (section 14), of the carved closed map
-(section 21), of the closed map's surfels (section 22) and of a diffed scan with its labels (section 26); and the closed map's
-snapshot as a file (section 25): the one form that loses nothing and is read back.
+(section 21), of the closed map's surfels (section 22), of a diffed scan with its labels (section 26) and of the free cells of
+the free-space grid (section 29); and the closed map's snapshot as a file (section 25): the one form that loses nothing and is
+read back.
 
 The reference declares a `saveMap` service (srv/saveMap.srv) and never serves it; this is the file a user of the map needs.
 PCD v0.7 (the Point Cloud Library's format), fields `x y z`, each `F 8` (float64), so the device's doubles are written and
@@ -327,3 +328,12 @@ def write_raycast_pcd(path: str, pose, ends, status, ranges) -> int:
               "DATA binary\n")
     _write_renamed(path, header.encode("ascii") + rec.tobytes())
     return n
+
+
+# ---- the closed map's free space: the centres of the cells rays saw through
+def write_free_pcd(path: str, H, lo=None, hi=None, ascii: bool = False) -> int:
+    """Writes what `H.closed_map_free_cells` reads of a free-space grid (a HipRegistration after closed_map_free_build) as a
+    file of write_pcd: the centres of the free cells, brick by brick -> the cells written."""
+    cen = H.closed_map_free_cells(lo, hi)
+    write_pcd(path, cen, ascii=ascii)
+    return len(cen)

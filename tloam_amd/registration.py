@@ -261,6 +261,29 @@ class ClosedMapRaycastInfo(C.Structure):
 RAYCAST_SKIPPED, RAYCAST_MISS, RAYCAST_HIT_CENTROID, RAYCAST_HIT_PLANE = 0, 1, 2, 3   # TLOAM_RAYCAST_*
 
 
+class FreeConfig(C.Structure):
+    """tloam_closed_map_free_config: the rays' longest range and end margin (the carve's meaning), the most bytes a grid may
+    take, which voxels count as occupied when the grid is read (min_count and the carve gate: min_miss, miss_ratio, carve_gate),
+    and the keyframe clouds whose points are rays.  The defaults are choices, not measurements."""
+    _fields_ = [("max_range", C.c_double), ("end_margin", C.c_double), ("max_bytes", C.c_int64), ("min_count", C.c_int64),
+                ("min_miss", C.c_int64), ("miss_ratio", C.c_double), ("ray_mask", C.c_int32), ("carve_gate", C.c_int32)]
+
+
+class FreeInfo(C.Structure):
+    """tloam_closed_map_free_info."""
+    _fields_ = [("lo_cells", C.c_int64 * 3), ("n_bricks", C.c_int64 * 3), ("bytes", C.c_int64), ("keyframes", C.c_int64),
+                ("scans", C.c_int64), ("free_cells", C.c_int64), ("bricks_nonzero", C.c_int64), ("rays", C.c_int64),
+                ("skipped_rays", C.c_int64), ("cells_marked", C.c_int64), ("cells_outside", C.c_int64), ("launches", C.c_int32),
+                ("reserved0", C.c_int32)]
+
+    def as_dict(self):
+        d = {name: int(getattr(self, name)) for name, _ in self._fields_[2:]}
+        return {"lo_cells": tuple(int(x) for x in self.lo_cells), "n_bricks": tuple(int(x) for x in self.n_bricks), **d}
+
+
+OCCUPANCY_INVALID, OCCUPANCY_UNKNOWN, OCCUPANCY_FREE, OCCUPANCY_OCCUPIED = 0, 1, 2, 3   # TLOAM_OCCUPANCY_*
+
+
 SNAPSHOT_CLOUDS = 1   # TLOAM_SNAPSHOT_CLOUDS: the keyframes' eight clouds go into the snapshot too
 
 
@@ -648,6 +671,17 @@ def load_library():
         "tloam_closed_map_get_raycast_info": (C.c_int, [vp, C.POINTER(ClosedMapRaycastInfo)]),
         "tloam_closed_map_raycast": (C.c_int, [vp, dp, sz, dp, C.POINTER(C.c_uint8), dp, C.POINTER(C.c_int32),
                                                C.POINTER(ClosedMapRaycastInfo)]),
+        "tloam_closed_map_free_default_config": (None, [C.POINTER(FreeConfig)]),
+        "tloam_closed_map_free_configure": (C.c_int, [vp, C.POINTER(FreeConfig)]),
+        "tloam_closed_map_get_free_info": (C.c_int, [vp, C.POINTER(FreeInfo)]),
+        "tloam_closed_map_free_reset": (C.c_int, [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+        "tloam_closed_map_free_add_keyframes": (C.c_int, [vp, C.POINTER(FreeInfo)]),
+        "tloam_closed_map_free_add_scan": (C.c_int, [vp, dp, sz, dp, C.POINTER(FreeInfo)]),
+        "tloam_closed_map_read_free_words": (C.c_int, [vp, sz, sz, C.POINTER(C.c_uint64)]),
+        "tloam_closed_map_occupancy": (C.c_int, [vp, dp, sz, dp, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+        "tloam_closed_map_read_free": (C.c_int, [vp, dp, dp, sz, C.POINTER(sz), dp]),
+        "tloam_closed_map_free_columns": (C.c_int, [vp, C.c_double, C.c_double, C.c_int64, C.POINTER(C.c_uint8), sz, C.POINTER(sz),
+                                                    C.POINTER(sz)]),
         "tloam_closed_map_read_gone": (C.c_int, [vp, dp, dp, C.c_int64, C.c_double, sz, C.POINTER(sz), dp, C.POINTER(C.c_int64),
                                                  C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
         "tloam_closed_map_save_size": (C.c_int, [vp, C.c_int, C.POINTER(sz)]),
@@ -707,6 +741,10 @@ EXPORTED_SYMBOLS = (
     "tloam_closed_map_diff", "tloam_closed_map_read_diff", "tloam_closed_map_read_gone",
     "tloam_closed_map_raycast_default_config", "tloam_closed_map_raycast_configure", "tloam_closed_map_get_raycast_info",
     "tloam_closed_map_raycast",
+    "tloam_closed_map_free_default_config", "tloam_closed_map_free_configure", "tloam_closed_map_get_free_info",
+    "tloam_closed_map_free_reset", "tloam_closed_map_free_add_keyframes", "tloam_closed_map_free_add_scan",
+    "tloam_closed_map_occupancy", "tloam_closed_map_read_free", "tloam_closed_map_free_columns",
+    "tloam_closed_map_read_free_words",
     "tloam_closed_map_save_size", "tloam_closed_map_save", "tloam_closed_map_probe", "tloam_closed_map_load",
     "tloam_rccl_unique_id", "tloam_comm_init_rccl",
     "tloam_comm_mailbox_export", "tloam_comm_init_mailbox",
@@ -1682,6 +1720,96 @@ class HipRegistration:
         self._check(self.L.tloam_closed_map_get_raycast_info(self.h, C.byref(info)), "tloam_closed_map_get_raycast_info")
         return info.as_dict()
 
+    # ---- free space for the closed map: an occupancy grid from the rays
+    def closed_map_free_configure(self, cfg: FreeConfig | None = None, **over):
+        """the free space's configuration (default_closed_map_free_config(**over) when cfg is None); drops the grid, not the
+        closed map.  Kept across odometry_reset; a refused configuration leaves the old one."""
+        cfg = cfg if cfg is not None else default_closed_map_free_config(**over)
+        self._check(self.L.tloam_closed_map_free_configure(self.h, C.byref(cfg)), "tloam_closed_map_free_configure")
+
+    def closed_map_free_info(self) -> dict:
+        info = FreeInfo()
+        self._check(self.L.tloam_closed_map_get_free_info(self.h, C.byref(info)), "tloam_closed_map_get_free_info")
+        return info.as_dict()
+
+    def closed_map_free_reset(self, lo_cells=None, hi_cells=None) -> dict:
+        """allocates and zeroes the grid over the cells [lo_cells, hi_cells] (inclusive, rounded out to bricks); both None: the
+        auto box around the closed map's poses -> info dict"""
+        if (lo_cells is None) != (hi_cells is None):
+            raise ValueError("lo_cells and hi_cells go together")
+        lo = hi = None
+        if lo_cells is not None:
+            lo = np.ascontiguousarray(lo_cells, dtype=np.int64).reshape(3)
+            hi = np.ascontiguousarray(hi_cells, dtype=np.int64).reshape(3)
+        self._check(self.L.tloam_closed_map_free_reset(self.h, _lp(lo), _lp(hi)), "tloam_closed_map_free_reset")
+        return self.closed_map_free_info()
+
+    def closed_map_free_add_keyframes(self) -> dict:
+        """walks the rays of the keyframes the grid has not seen (all of the map's after a reset, the new ones after an extend)
+        -> info dict"""
+        info = FreeInfo()
+        self._check(self.L.tloam_closed_map_free_add_keyframes(self.h, C.byref(info)), "tloam_closed_map_free_add_keyframes")
+        return info.as_dict()
+
+    def closed_map_free_add_scan(self, points, pose) -> dict:
+        """walks the rays of the scan `points` (n, 3; sensor frame) at `pose` (4 x 4) -> info dict"""
+        pts = _aos(points)
+        info = FreeInfo()
+        self._check(self.L.tloam_closed_map_free_add_scan(self.h, _dp(pts), len(pts), _dp(_colmajor(pose)), C.byref(info)),
+                    "tloam_closed_map_free_add_scan")
+        return info.as_dict()
+
+    def closed_map_free_build(self, lo_cells=None, hi_cells=None) -> dict:
+        """closed_map_free_reset, then closed_map_free_add_keyframes -> info dict"""
+        self.closed_map_free_reset(lo_cells, hi_cells)
+        return self.closed_map_free_add_keyframes()
+
+    def closed_map_free_words(self, first=0, count=None):
+        """the grid's words [first, first + count) -> (m,) uint64; count None: to the end"""
+        def total():
+            nb = self.closed_map_free_info()["n_bricks"]
+            return nb[0] * nb[1] * nb[2]
+        first, m = _id_range(first, count, total)
+        words = np.zeros(max(m, 1), np.uint64)
+        self._check(self.L.tloam_closed_map_read_free_words(self.h, int(first), m, words.ctypes.data_as(C.POINTER(C.c_uint64))),
+                    "tloam_closed_map_read_free_words")
+        return words[:m].copy()
+
+    def closed_map_occupancy(self, points, pose=None, want_ids=False):
+        """the state of `points` (n, 3; in the map frame, or with `pose` (4 x 4) in its sensor frame) -> (states (n,) uint8:
+        OCCUPANCY_INVALID, OCCUPANCY_UNKNOWN, OCCUPANCY_FREE, OCCUPANCY_OCCUPIED; ids (n,) int32 of the voxel of an OCCUPIED
+        point, -1 otherwise, or None without want_ids; counts (4,) int64 of points per state)"""
+        pts = _aos(points)
+        state = np.zeros(max(len(pts), 1), np.uint8)
+        ids = np.zeros(max(len(pts), 1), np.int32) if want_ids else None
+        counts = np.zeros(4, np.int64)
+        self._check(self.L.tloam_closed_map_occupancy(self.h, _dp(pts), len(pts), None if pose is None else _dp(_colmajor(pose)),
+                                                      state.ctypes.data_as(C.POINTER(C.c_uint8)), _ip(ids), _lp(counts)),
+                    "tloam_closed_map_occupancy")
+        return state[: len(pts)].copy(), (ids[: len(pts)].copy() if want_ids else None), counts
+
+    def closed_map_free_cells(self, lo=None, hi=None):
+        """the centres (m, 3) of the FREE cells (lo and hi None: of the whole grid; else with their centre in [lo, hi]), brick
+        index ascending, then bit ascending"""
+        if (lo is None) != (hi is None):
+            raise ValueError("lo and hi go together")
+        if lo is not None:
+            lo = np.ascontiguousarray(lo, dtype=np.float64).reshape(3)
+            hi = np.ascontiguousarray(hi, dtype=np.float64).reshape(3)
+        return self._read_box(self.L.tloam_closed_map_read_free, "tloam_closed_map_read_free", (self.h, _dp(lo), _dp(hi)),
+                              [(3, np.float64)])[0]
+
+    def closed_map_free_columns(self, z_lo, z_hi, min_free=1):
+        """the navigation grid (ny, nx) uint8 over the box's x-y footprint for the band of cells between heights z_lo and z_hi:
+        OCCUPANCY_OCCUPIED, OCCUPANCY_FREE (at least min_free free band cells) or OCCUPANCY_UNKNOWN per column"""
+        info = self.closed_map_free_info()
+        nx, ny = C.c_size_t(0), C.c_size_t(0)
+        out = np.zeros(max(16 * info["n_bricks"][0] * info["n_bricks"][1], 1), np.uint8)
+        self._check(self.L.tloam_closed_map_free_columns(self.h, float(z_lo), float(z_hi), int(min_free),
+                                                         out.ctypes.data_as(C.POINTER(C.c_uint8)), len(out), C.byref(nx), C.byref(ny)),
+                    "tloam_closed_map_free_columns")
+        return out[: nx.value * ny.value].reshape(ny.value, nx.value).copy()
+
     def fitness(self):
         f, r = C.c_double(0), C.c_double(0)
         rc = self.L.tloam_fitness(self.h, C.byref(f), C.byref(r))
@@ -1949,6 +2077,12 @@ def default_closed_map_raycast_config(**over) -> ClosedMapRaycastConfig:
     """tloam_closed_map_raycast_default_config (max_range 120, radius_cells 0.75, planes 1, min_count 1, min_miss 3,
     miss_ratio 1, carve_gate 0) with `over` applied; an unknown field raises"""
     return _strict_config(ClosedMapRaycastConfig, "tloam_closed_map_raycast_default_config", over)
+
+
+def default_closed_map_free_config(**over) -> FreeConfig:
+    """tloam_closed_map_free_default_config (max_range 60, end_margin 1, ray_mask 0: the build's, max_bytes 1 GiB, min_count 1,
+    min_miss 3, miss_ratio 1, carve_gate 0) with keyword overrides; an unknown field raises"""
+    return _strict_config(FreeConfig, "tloam_closed_map_free_default_config", over)
 
 
 def default_closed_map_diff_config(**over) -> ClosedMapDiffConfig:
