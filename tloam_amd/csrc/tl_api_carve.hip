@@ -108,9 +108,7 @@ int tloam_closed_map_read_carved(tloam_ctx* c, const double* lo, const double* h
   CmapState& M = c->cmap;
   if (!M.built || !M.carved) return TLOAM_E_NOT_READY;
   CarveReadArgs A;
-  A.miss = (const long long*)M.miss.p;
-  A.min_miss = min_miss;
-  A.miss_ratio = miss_ratio;
+  A.gate = CarveGate{(const long long*)M.miss.p, min_count, min_miss, miss_ratio, 1, 0};   // (min_count: the box read's own test)
   A.boxed = lo ? 1 : 0;
   return voxel_rows_read_box(c, voxel_rows_of(M, (size_t)M.info.n_voxels, "closed map"), lo, hi, min_count, capacity, n,
                              centroids_aos, counts, "k_carve_box", {BoxColumn{misses, &M.rd_m, 1, sizeof(int64_t)}},

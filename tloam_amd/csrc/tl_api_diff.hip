@@ -2,8 +2,9 @@
 // _read_gone; kernels in tl_diff.hip).
 //
 // A diff takes the built closed map with its surfels (CmapState: its rows, its table, the localiser's voxel records, the
-// carve's counts when the gate is on), uploads the scan where the localiser's goes, enqueues the records' rebuild when they are
-// stale and the diff's launches on the context's stream, and waits once, for the counters, the labels and the ids.  The counts
+// carve's counts when the gate is on) and goes through the scan-form runner (tl_ctx.hpp: cmap_scan_call): the scan uploaded
+// where the localiser's goes, the records' rebuild enqueued when they are stale, the diff's launches on the context's stream,
+// one wait, for the counters, the labels and the ids.  The pose check is the runner's neighbour pose_finite_rigid.  The counts
 // through and hits live beside the rows in id order and go with the closed map (CmapState::drop).  Nothing of the closed map, of
 // a carve, of the surfels or of anything else in the context is written, so a detached (loaded) map is diffed like any other.
 #include <math.h>
@@ -25,44 +26,40 @@ int diff_body(tloam_ctx* c, const double* points_aos, size_t n, const double* po
               int32_t* ids, unsigned long long ctl[kDiffCtl], int* prepared, int* launches) {
   CmapState& M = c->cmap;
   const tloam_closed_map_diff_config& g = M.diff_cfg;
-  const size_t nv = (size_t)M.info.n_voxels, cap = std::max<size_t>(nv, 1);
-  HIPC(c, hipSetDevice(c->device));
-  HIPC(c, M.loc_pts.reserve(3 * n)); HIPC(c, M.diff_labels.reserve(n));
-  if (ids) HIPC(c, M.diff_ids.reserve(n));
-  HIPC(c, M.diff_through.reserve(cap)); HIPC(c, M.diff_hits.reserve(cap)); HIPC(c, M.diff_ctl.reserve(kDiffCtl));
-  HIPC(c, hipMemcpyAsync(M.loc_pts.p, points_aos, sizeof(double) * 3 * n, hipMemcpyHostToDevice, c->stream));
-  const int rc = loc_records_prepare(c, prepared);
-  if (rc != TLOAM_OK) return rc;
-  HIPC(c, hipMemsetAsync(M.diff_ctl.p, 0, sizeof(unsigned long long) * kDiffCtl, c->stream));
-  if (fresh && !clear_launch) {   // accumulating into nothing: the counts start at zero without a launch of their own
-    HIPC(c, hipMemsetAsync(M.diff_through.p, 0, sizeof(unsigned long long) * cap, c->stream));
-    HIPC(c, hipMemsetAsync(M.diff_hits.p, 0, sizeof(unsigned long long) * cap, c->stream));
-  }
-  DiffWork W;
-  memset(&W, 0, sizeof(W));
-  W.pts = M.loc_pts.p;
-  W.n = (long long)n;
-  memcpy(W.M, pose, sizeof(W.M));   // the matrix as it stands
-  W.voxel = M.cfg.voxel;
-  for (int a = 0; a < 3; ++a) W.origin[a] = M.cfg.origin[a];
-  W.max_range = g.max_range; W.end_margin = g.end_margin; W.radius2 = g.radius * g.radius;
-  W.plane_tol = g.plane_tol; W.near2 = g.near * g.near;
-  W.min_miss = g.min_miss; W.miss_ratio = g.miss_ratio; W.gate = g.carve_gate;
-  W.map = M.rows.view();
-  W.nv = (long long)nv;
-  W.rec = M.loc_rec.p;
-  W.miss = (const long long*)M.miss.p;
-  W.through = M.diff_through.p; W.hits = M.diff_hits.p;
-  W.labels = M.diff_labels.p;
-  W.ids = ids ? M.diff_ids.p : nullptr;
-  W.ctl = M.diff_ctl.p;
-  *launches = launch_diff(W, clear_launch, c->stream) + *prepared;
-  HIPC(c, hipGetLastError());
-  HIPC(c, hipMemcpyAsync(ctl, M.diff_ctl.p, sizeof(unsigned long long) * kDiffCtl, hipMemcpyDeviceToHost, c->stream));
-  if (labels) HIPC(c, hipMemcpyAsync(labels, M.diff_labels.p, n, hipMemcpyDeviceToHost, c->stream));
-  if (ids) HIPC(c, hipMemcpyAsync(ids, M.diff_ids.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));
-  return TLOAM_OK;
+  const size_t cap = std::max<size_t>((size_t)M.info.n_voxels, 1);
+  return cmap_scan_call(
+      c, CmapScanCall{points_aos, n, pose, true, &M.scan_ctl, kDiffCtl, ctl}, prepared,
+      [&](auto room) -> int {
+        HIPC(c, room(M.scan_u8, n));
+        if (ids) HIPC(c, room(M.scan_ids, n));
+        HIPC(c, room(M.diff_through, cap)); HIPC(c, room(M.diff_hits, cap));
+        return TLOAM_OK;
+      },
+      [&](const MapGrid& grid, const ScanAt& scan) -> int {
+        if (fresh && !clear_launch) {   // accumulating into nothing: the counts start at zero without a launch of their own
+          HIPC(c, hipMemsetAsync(M.diff_through.p, 0, sizeof(unsigned long long) * cap, c->stream));
+          HIPC(c, hipMemsetAsync(M.diff_hits.p, 0, sizeof(unsigned long long) * cap, c->stream));
+        }
+        DiffWork W;
+        memset(&W, 0, sizeof(W));
+        W.scan = scan;
+        W.grid = grid;
+        W.max_range = g.max_range; W.end_margin = g.end_margin; W.radius2 = g.radius * g.radius;
+        W.plane_tol = g.plane_tol; W.near2 = g.near * g.near;
+        W.gate = CarveGate{(const long long*)M.miss.p, 1, g.min_miss, g.miss_ratio, g.carve_gate, 0};
+        W.rec = M.loc_rec.p;
+        W.through = M.diff_through.p; W.hits = M.diff_hits.p;
+        W.labels = M.scan_u8.p;
+        W.ids = ids ? M.scan_ids.p : nullptr;
+        W.ctl = M.scan_ctl.p;
+        *launches = launch_diff(W, clear_launch, c->stream) + *prepared;
+        return TLOAM_OK;
+      },
+      [&]() -> int {
+        if (labels) HIPC(c, hipMemcpyAsync(labels, M.scan_u8.p, n, hipMemcpyDeviceToHost, c->stream));
+        if (ids) HIPC(c, hipMemcpyAsync(ids, M.scan_ids.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
+        return TLOAM_OK;
+      });
 }
 
 }  // namespace
@@ -104,22 +101,16 @@ int tloam_closed_map_diff(tloam_ctx* c, const double* points_aos, size_t n, cons
     return TLOAM_E_INVALID;
   CmapState& M = c->cmap;
   if (!M.built || !M.surfeled || (M.diff_cfg.carve_gate && !M.carved)) return TLOAM_E_NOT_READY;
-  for (int i = 0; i < 16; ++i)
-    if (!(pose[i] - pose[i] == 0.0)) return TLOAM_E_INVALID;
-  Pose rigid;   // (only the check that `pose` is a rigid transform: the diff runs at the matrix as it stands)
-  if (!pose_from_matrix(pose, &rigid)) return TLOAM_E_INVALID;
+  if (!pose_finite_rigid(pose)) return TLOAM_E_INVALID;   // (only the check: the diff runs at the matrix as it stands)
   const bool accumulate = (flags & TLOAM_DIFF_ACCUMULATE) != 0;
   const bool fresh = !accumulate || !M.diffed;   // the counts start at zero
   unsigned long long ctl[kDiffCtl];
   int prepared = 0, launches = 0;
   const int rc = diff_body(c, points_aos, n, pose, fresh, !accumulate, labels, ids, ctl, &prepared, &launches);
-  if (rc != TLOAM_OK) {   // nothing of the call stays in flight; its counts are gone and the records are rebuilt by the next call
-    (void)hipStreamSynchronize(c->stream);
-    M.loc_ready = false;
+  if (rc != TLOAM_OK) {   // (the runner has drained the stream) its counts are gone
     M.drop_diff();
     return rc;
   }
-  M.loc_ready = true;
   tloam_closed_map_diff_info I;
   memset(&I, 0, sizeof(I));
   I.n_points = (int64_t)n;

@@ -174,10 +174,8 @@ int extend_body(tloam_ctx* c, size_t K, size_t n_kf, int pose_source, const std:
     memset(&SW, 0, sizeof(SW));
     SW.in = W.in;
     SW.kf_over = S.kf_over.p;   // the row pass's flags: the same rule, the same keyframes
-    SW.voxel = W.voxel;
-    for (int a = 0; a < 3; ++a) SW.origin[a] = W.origin[a];
-    SW.map = M.rows.view();
-    SW.nv = (long long)upper;
+    SW.grid = map_grid_of(M);   // (the rows as the commit left them)
+    SW.grid.nv = (long long)upper;
     SW.runs = getenv("TLOAM_SURFEL_NO_RUNS") ? 0 : 1;
     SW.min_points = M.surfel_cfg.min_points;
     SW.sums = M.surfel_sums.p; SW.normal = M.surfel_nrm.p; SW.eval = M.surfel_ev.p;
@@ -195,11 +193,9 @@ int extend_body(tloam_ctx* c, size_t K, size_t n_kf, int pose_source, const std:
     memset(&CW, 0, sizeof(CW));
     rc = S.up_rays.upload(c, ray_spans, n_rays, poses.data(), n_new, &CW.in);
     if (rc != TLOAM_OK) return rc;
-    CW.voxel = W.voxel;
-    for (int a = 0; a < 3; ++a) CW.origin[a] = W.origin[a];
+    CW.grid = map_grid_of(M);
+    CW.grid.nv = (long long)upper;
     CW.max_range = g.max_range; CW.end_margin = g.end_margin; CW.radius2 = g.radius * g.radius;
-    CW.map = M.rows.view();
-    CW.nv = (long long)upper;
     CW.miss = M.miss.p;
     CW.ctl = M.carve_ctl.p;
     E.launches += launch_carve_rays(CW, c->stream);

@@ -3,8 +3,8 @@
 //
 // The grid is a FreeState inside the closed map's state: a reset sizes it over a box of bricks and zeroes it, an add walks rays
 // into it -- the keyframes' through the pass runner the carve uses (cmap_pass, over the keyframes the grid has not seen), a live
-// scan's from one origin, uploaded where the localiser's scan goes -- and the reads resolve occupancy against the map as it is
-// when they run.  Every call enqueues a fixed number of launches on the context's stream and waits once.  Nothing of the closed
+// scan's from one origin through the scan-form runner (cmap_scan_call, as the occupancy of a scan's points) -- and the reads
+// resolve occupancy against the map as it is when they run, under the one carve gate (tl_common.hpp: CarveGate).  Every call enqueues a fixed number of launches on the context's stream and waits once.  Nothing of the closed
 // map, of a carve, of the surfels, of a diff or of anything else in the context is written.
 #include <math.h>
 
@@ -37,22 +37,12 @@ int free_read_ready(const tloam_ctx* c) {
   return c->cmap.free.cfg.carve_gate && !c->cmap.carved ? TLOAM_E_NOT_READY : TLOAM_OK;
 }
 
-bool pose_ok(const double* pose) {   // (the diff's check: finite, a rigid transform)
-  for (int i = 0; i < 16; ++i)
-    if (!(pose[i] - pose[i] == 0.0)) return false;
-  Pose rigid;
-  return pose_from_matrix(pose, &rigid);
-}
-
 FreeQuery free_query(const CmapState& M) {
   const FreeState& F = M.free;
   FreeQuery q;
   memset(&q, 0, sizeof(q));
-  q.map = M.rows.view();
-  q.miss = (const long long*)M.miss.p;
-  q.min_count = F.cfg.min_count; q.min_miss = F.cfg.min_miss; q.miss_ratio = F.cfg.miss_ratio; q.gate = F.cfg.carve_gate;
-  q.voxel = M.cfg.voxel;
-  for (int a = 0; a < 3; ++a) q.origin[a] = M.cfg.origin[a];
+  q.grid = map_grid_of(M);
+  q.gate = CarveGate{(const long long*)M.miss.p, F.cfg.min_count, F.cfg.min_miss, F.cfg.miss_ratio, F.cfg.carve_gate, 0};
   q.g = F.grid;
   return q;
 }
@@ -68,7 +58,8 @@ void free_note_add(FreeState& F, long long rays, const unsigned long long ctl[kF
   F.info.launches = launches;
 }
 
-// an add failed with its launches possibly in flight: the stream drained, the grid (half written, perhaps) gone
+// an add failed with its launches possibly in flight: the stream drained (again, after cmap_scan_call), the grid (half written,
+// perhaps) gone
 int free_add_failed(tloam_ctx* c, int rc) {
   (void)hipStreamSynchronize(c->stream);
   c->cmap.free.drop();
@@ -162,7 +153,7 @@ int tloam_closed_map_free_add_keyframes(tloam_ctx* c, tloam_closed_map_free_info
         HIPC(c, hipMemsetAsync(F.ctl.p, 0, sizeof(unsigned long long) * kFreeCtl, c->stream));
         return TLOAM_OK;
       },
-      [&](FreeWork& W) {
+      [&](FreeWork& W) {   // (W.scan stays zero: the keyframe form)
         W.max_range = g.max_range;
         W.end_margin = g.end_margin;
         W.g = F.grid;
@@ -181,38 +172,26 @@ int tloam_closed_map_free_add_scan(tloam_ctx* c, const double* points_aos, size_
   if (!c || c->nranks > 1 || !points_aos || !pose || n == 0 || n > kMaxPoints) return TLOAM_E_INVALID;
   const int ready = free_ready(c);
   if (ready != TLOAM_OK) return ready;
-  if (!pose_ok(pose)) return TLOAM_E_INVALID;
+  if (!pose_finite_rigid(pose)) return TLOAM_E_INVALID;
   CmapState& M = c->cmap;
   FreeState& F = M.free;
-  HIPC(c, hipSetDevice(c->device));
-  if (M.loc_pts.cap < 3 * n) HIPC(c, hipStreamSynchronize(c->stream));   // (the scan replaced may still be read)
-  HIPC(c, M.loc_pts.reserve(3 * n));
-  HIPC(c, F.ctl.reserve(kFreeCtl));
-  // (nothing of the grid has been touched so far: a failure above changes nothing)
   unsigned long long ctl[kFreeCtl];
-  int launches = 0;
-  const int rc = [&]() -> int {
-    HIPC(c, hipMemcpyAsync(M.loc_pts.p, points_aos, sizeof(double) * 3 * n, hipMemcpyHostToDevice, c->stream));
-    HIPC(c, hipMemsetAsync(F.ctl.p, 0, sizeof(unsigned long long) * kFreeCtl, c->stream));
-    FreeWork W;
-    memset(&W, 0, sizeof(W));
-    W.pts = M.loc_pts.p;
-    W.n = (long long)n;
-    memcpy(W.M, pose, sizeof(W.M));   // the matrix as it stands
-    W.voxel = M.cfg.voxel;
-    for (int a = 0; a < 3; ++a) W.origin[a] = M.cfg.origin[a];
-    W.max_range = F.cfg.max_range;
-    W.end_margin = F.cfg.end_margin;
-    W.map = M.rows.view();
-    W.nv = (long long)M.info.n_voxels;
-    W.g = F.grid;
-    W.ctl = F.ctl.p;
-    launches = launch_free_rays(W, false, c->stream);
-    HIPC(c, hipGetLastError());
-    HIPC(c, hipMemcpyAsync(ctl, F.ctl.p, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipStreamSynchronize(c->stream));
-    return TLOAM_OK;
-  }();
+  int launches = 0, prepared = 0;
+  const int rc = cmap_scan_call(
+      c, CmapScanCall{points_aos, n, pose, false, &F.ctl, kFreeCtl, ctl}, &prepared, [](auto) { return TLOAM_OK; },
+      [&](const MapGrid& grid, const ScanAt& scan) -> int {
+        FreeWork W;
+        memset(&W, 0, sizeof(W));
+        W.scan = scan;
+        W.grid = grid;
+        W.max_range = F.cfg.max_range;
+        W.end_margin = F.cfg.end_margin;
+        W.g = F.grid;
+        W.ctl = F.ctl.p;
+        launches = launch_free_rays(W, false, c->stream);
+        return TLOAM_OK;
+      },
+      [] { return TLOAM_OK; });
   if (rc != TLOAM_OK) return free_add_failed(c, rc);
   free_note_add(F, (long long)n, ctl, launches);
   F.info.scans += 1;
@@ -239,32 +218,35 @@ int tloam_closed_map_occupancy(tloam_ctx* c, const double* points_aos, size_t n,
   if (!c || c->nranks > 1 || !points_aos || !state_out || n == 0 || n > kMaxPoints) return TLOAM_E_INVALID;
   const int ready = free_read_ready(c);
   if (ready != TLOAM_OK) return ready;
-  if (pose && !pose_ok(pose)) return TLOAM_E_INVALID;
+  if (pose && !pose_finite_rigid(pose)) return TLOAM_E_INVALID;
   CmapState& M = c->cmap;
-  FreeState& F = M.free;
-  HIPC(c, hipSetDevice(c->device));
-  if (M.loc_pts.cap < 3 * n || F.state.cap < n || (ids_out && F.ids.cap < n)) HIPC(c, hipStreamSynchronize(c->stream));
-  HIPC(c, M.loc_pts.reserve(3 * n)); HIPC(c, F.state.reserve(n)); HIPC(c, F.rd_ctl.reserve(8));
-  if (ids_out) HIPC(c, F.ids.reserve(n));
-  HIPC(c, hipMemcpyAsync(M.loc_pts.p, points_aos, sizeof(double) * 3 * n, hipMemcpyHostToDevice, c->stream));
-  HIPC(c, hipMemsetAsync(F.rd_ctl.p, 0, sizeof(unsigned long long) * 8, c->stream));
-  FreePointsArgs A;
-  memset(&A, 0, sizeof(A));
-  A.q = free_query(M);
-  A.pts = M.loc_pts.p;
-  A.n = (long long)n;
-  A.posed = pose ? 1 : 0;
-  if (pose) memcpy(A.M, pose, sizeof(A.M));
-  A.state = F.state.p;
-  A.ids = ids_out ? F.ids.p : nullptr;
-  A.ctl = F.rd_ctl.p;
-  launch_free_points(A, c->stream);
-  HIPC(c, hipGetLastError());
   unsigned long long w[4];
-  HIPC(c, hipMemcpyAsync(w, F.rd_ctl.p, sizeof(w), hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipMemcpyAsync(state_out, F.state.p, n, hipMemcpyDeviceToHost, c->stream));
-  if (ids_out) HIPC(c, hipMemcpyAsync(ids_out, F.ids.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));
+  int prepared = 0;
+  const int rc = cmap_scan_call(
+      c, CmapScanCall{points_aos, n, pose, false, &M.scan_ctl, 4, w}, &prepared,
+      [&](auto room) -> int {
+        HIPC(c, room(M.scan_u8, n));
+        if (ids_out) HIPC(c, room(M.scan_ids, n));
+        return TLOAM_OK;
+      },
+      [&](const MapGrid&, const ScanAt& scan) -> int {
+        FreePointsArgs A;
+        memset(&A, 0, sizeof(A));
+        A.q = free_query(M);
+        A.scan = scan;
+        A.posed = pose ? 1 : 0;
+        A.state = M.scan_u8.p;
+        A.ids = ids_out ? M.scan_ids.p : nullptr;
+        A.ctl = M.scan_ctl.p;
+        launch_free_points(A, c->stream);
+        return TLOAM_OK;
+      },
+      [&]() -> int {
+        HIPC(c, hipMemcpyAsync(state_out, M.scan_u8.p, n, hipMemcpyDeviceToHost, c->stream));
+        if (ids_out) HIPC(c, hipMemcpyAsync(ids_out, M.scan_ids.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
+        return TLOAM_OK;
+      });
+  if (rc != TLOAM_OK) return rc;
   if (counts_out)
     for (int k = 0; k < 4; ++k) counts_out[k] = (int64_t)w[k];
   return TLOAM_OK;
@@ -282,9 +264,9 @@ int tloam_closed_map_read_free(tloam_ctx* c, const double* lo, const double* hi,
   HIPC(c, hipSetDevice(c->device));
   HIPC(c, hipStreamSynchronize(c->stream));   // (the scratch may be replaced)
   const size_t blocks = ((size_t)F.grid.nwords + 255) / 256;
-  HIPC(c, F.rd_c.reserve(3 * most)); HIPC(c, F.look.reserve(blocks + 1)); HIPC(c, F.rd_ctl.reserve(8));
+  HIPC(c, F.rd_c.reserve(3 * most)); HIPC(c, F.look.reserve(blocks + 1)); HIPC(c, M.scan_ctl.reserve(kDiffCtl));
   HIPC(c, hipMemsetAsync(F.look.p, 0, sizeof(unsigned long long) * (blocks + 1), c->stream));
-  HIPC(c, hipMemsetAsync(F.rd_ctl.p, 0, sizeof(unsigned long long) * 8, c->stream));
+  HIPC(c, hipMemsetAsync(M.scan_ctl.p, 0, sizeof(unsigned long long) * 8, c->stream));
   FreeCellsArgs A;
   memset(&A, 0, sizeof(A));
   A.q = free_query(M);
@@ -292,11 +274,11 @@ int tloam_closed_map_read_free(tloam_ctx* c, const double* lo, const double* hi,
   for (int a = 0; a < 3; ++a) { A.lo[a] = lo ? lo[a] : 0.0; A.hi[a] = hi ? hi[a] : 0.0; }
   A.out_c = F.rd_c.p;
   A.look = F.look.p;
-  A.ctl = F.rd_ctl.p;
+  A.ctl = M.scan_ctl.p;
   launch_free_cells(A, c->stream);
   HIPC(c, hipGetLastError());
   unsigned long long w[3];
-  HIPC(c, hipMemcpyAsync(w, F.rd_ctl.p, sizeof(w), hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipMemcpyAsync(w, M.scan_ctl.p, sizeof(w), hipMemcpyDeviceToHost, c->stream));
   HIPC(c, hipStreamSynchronize(c->stream));
   if (w[1]) {
     c->last_error = "closed map free space: a look-back of k_free_cells timed out";
@@ -329,18 +311,18 @@ int tloam_closed_map_free_columns(tloam_ctx* c, double z_lo, double z_hi, int64_
   *ny = cy;
   if (capacity < cols || !state_out) return TLOAM_E_INVALID;
   HIPC(c, hipSetDevice(c->device));
-  if (F.state.cap < cols) HIPC(c, hipStreamSynchronize(c->stream));
-  HIPC(c, F.state.reserve(cols));
+  if (M.scan_u8.cap < cols) HIPC(c, hipStreamSynchronize(c->stream));
+  HIPC(c, M.scan_u8.reserve(cols));
   FreeColumnsArgs A;
   memset(&A, 0, sizeof(A));
   A.q = free_query(M);
   A.z0 = (int)z0;
   A.z1 = (int)z1;
   A.min_free = min_free;
-  A.state = F.state.p;
+  A.state = M.scan_u8.p;
   launch_free_columns(A, c->stream);
   HIPC(c, hipGetLastError());
-  HIPC(c, hipMemcpyAsync(state_out, F.state.p, cols, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipMemcpyAsync(state_out, M.scan_u8.p, cols, hipMemcpyDeviceToHost, c->stream));
   HIPC(c, hipStreamSynchronize(c->stream));
   return TLOAM_OK;
 }

@@ -1,8 +1,9 @@
 // tl_api_localise.hip -- C ABI of the localisation of a scan in the closed map (include/tloam_hip.h: tloam_closed_map_localise*,
 // _linearise; kernels in tl_localise.hip).
 //
-// A call takes the built closed map with its surfels (CmapState) and goes through loc_run: the scan uploaded, the voxel records'
-// rebuild enqueued when they are stale, the B states seeded (uploaded as the host forms them from the priors, or formed on the
+// A call takes the built closed map with its surfels (CmapState) and goes through loc_run, a caller of the scan-form runner
+// (tl_ctx.hpp: cmap_scan_call, as the linearise is): the scan uploaded, the voxel records' rebuild enqueued when they are stale,
+// the B states seeded (uploaded as the host forms them from the priors, or formed on the
 // device by the relocalisation's launches), max_iterations pairs of (sweep, step) over the B hypotheses on the context's stream,
 // the states and the logs read back, one wait.  The single call is B = 1.
 // A pair behind the last executed iteration returns on entry, so the launches are the same for every input.  Nothing of the
@@ -28,36 +29,28 @@ int loc_check(const tloam_ctx* c, const double* points_aos, size_t n, const doub
   if (!c || c->nranks > 1 || !points_aos || !pose || n == 0 || n > kMaxPoints) return TLOAM_E_INVALID;
   const CmapState& M = c->cmap;
   if (!M.built || !M.surfeled) return TLOAM_E_NOT_READY;
-  for (int i = 0; i < 16; ++i)
-    if (!(pose[i] - pose[i] == 0.0)) return TLOAM_E_INVALID;
-  if (!pose_from_matrix(pose, T)) return TLOAM_E_INVALID;
+  return pose_finite_rigid(pose, T) ? TLOAM_OK : TLOAM_E_INVALID;
+}
+
+// the runner's call of a localiser: no pose (the states carry it), the records, no control words
+CmapScanCall loc_call(const double* points_aos, size_t n) { return CmapScanCall{points_aos, n, nullptr, true, nullptr, 0, nullptr}; }
+
+// the localiser's own buffers sized for B hypotheses of n points, through the runner's room(buffer, elements)
+template <class Room>
+int loc_rooms(tloam_ctx* c, Room room, size_t n, size_t B) {
+  CmapState& M = c->cmap;
+  HIPC(c, room(M.loc_partial, B * (size_t)loc_blocks((long long)n) * kLocRow));
+  HIPC(c, room(M.loc_state, B)); HIPC(c, room(M.loc_log, B * kLocMaxIterations));
   return TLOAM_OK;
 }
 
-// the buffers sized (for B hypotheses), the scan uploaded and the records rebuilt when stale (*prepared); ids, res: a linearise's
-// per-point outputs are asked for
-int loc_begin(tloam_ctx* c, const double* points_aos, size_t n, bool ids, bool res, int* prepared, size_t B = 1) {
-  CmapState& M = c->cmap;
-  HIPC(c, hipSetDevice(c->device));
-  HIPC(c, M.loc_pts.reserve(3 * n));
-  HIPC(c, M.loc_partial.reserve(B * (size_t)loc_blocks((long long)n) * kLocRow));
-  HIPC(c, M.loc_state.reserve(B)); HIPC(c, M.loc_log.reserve(B * kLocMaxIterations));
-  if (ids) HIPC(c, M.loc_ids.reserve(n));
-  if (res) HIPC(c, M.loc_res.reserve(n));
-  HIPC(c, hipMemcpyAsync(M.loc_pts.p, points_aos, sizeof(double) * 3 * n, hipMemcpyHostToDevice, c->stream));
-  return loc_records_prepare(c, prepared);
-}
-
-LocSweepArgs sweep_args(const CmapState& M, size_t n, int* ids, double* res) {
+LocSweepArgs sweep_args(const CmapState& M, const MapGrid& grid, const ScanAt& scan, int* ids, double* res) {
   LocSweepArgs W;
   memset(&W, 0, sizeof(W));
-  W.pts = M.loc_pts.p;
-  W.n = (long long)n;
+  W.pts = scan.pts;
+  W.n = scan.n;
   W.st = M.loc_state.p;
-  W.voxel = M.cfg.voxel;
-  for (int a = 0; a < 3; ++a) W.origin[a] = M.cfg.origin[a];
-  W.map = M.rows.view();
-  W.nv = (long long)M.info.n_voxels;
+  W.grid = grid;
   W.rec = M.loc_rec.p;
   W.partial = M.loc_partial.p;
   W.ids = ids;
@@ -78,13 +71,6 @@ LocStepArgs step_args(const CmapState& M, size_t n, int k) {
   A.step_tol_t = g.step_tol_t; A.step_tol_r = g.step_tol_r; A.min_pivot_ratio = g.min_pivot_ratio;
   A.log = M.loc_log.p;
   return A;
-}
-
-// a failed enqueue or wait: nothing of the call stays in flight, and the records are rebuilt by the next call
-int loc_failed(tloam_ctx* c, int rc) {
-  (void)hipStreamSynchronize(c->stream);
-  c->cmap.loc_ready = false;
-  return rc;
 }
 
 // the state words a localisation starts from
@@ -114,28 +100,24 @@ template <class Seed, class Reads>
 int loc_run(tloam_ctx* c, const double* points_aos, size_t n, LocRun& R, Seed seed, Reads more_reads) {
   CmapState& M = c->cmap;
   const int B = (int)R.st.size();
-  auto body = [&]() -> int {
-    int rc = loc_begin(c, points_aos, n, false, false, &R.prepared, (size_t)B);
-    if (rc == TLOAM_OK) rc = seed();
-    if (rc != TLOAM_OK) return rc;
-    const LocSweepArgs W = sweep_args(M, n, nullptr, nullptr);
-    for (int k = 0; k < M.loc_cfg.max_iterations; ++k) {
-      launch_loc_sweep(W, B, c->stream);
-      launch_loc_step(step_args(M, n, k), B, c->stream);
-      R.launches += 2;
-    }
-    HIPC(c, hipGetLastError());
-    HIPC(c, hipMemcpyAsync(R.st.data(), M.loc_state.p, sizeof(LocState) * R.st.size(), hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipMemcpyAsync(R.log.data(), M.loc_log.p, sizeof(LocLog) * R.log.size(), hipMemcpyDeviceToHost, c->stream));
-    rc = more_reads();
-    if (rc != TLOAM_OK) return rc;
-    HIPC(c, hipStreamSynchronize(c->stream));
-    return TLOAM_OK;
-  };
-  const int rc = body();
-  if (rc != TLOAM_OK) return loc_failed(c, rc);
-  M.loc_ready = true;
-  return TLOAM_OK;
+  return cmap_scan_call(
+      c, loc_call(points_aos, n), &R.prepared, [&](auto room) { return loc_rooms(c, room, n, (size_t)B); },
+      [&](const MapGrid& grid, const ScanAt& scan) -> int {
+        const int rc = seed();
+        if (rc != TLOAM_OK) return rc;
+        const LocSweepArgs W = sweep_args(M, grid, scan, nullptr, nullptr);
+        for (int k = 0; k < M.loc_cfg.max_iterations; ++k) {
+          launch_loc_sweep(W, B, c->stream);
+          launch_loc_step(step_args(M, n, k), B, c->stream);
+          R.launches += 2;
+        }
+        return TLOAM_OK;
+      },
+      [&]() -> int {
+        HIPC(c, hipMemcpyAsync(R.st.data(), M.loc_state.p, sizeof(LocState) * R.st.size(), hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipMemcpyAsync(R.log.data(), M.loc_log.p, sizeof(LocLog) * R.log.size(), hipMemcpyDeviceToHost, c->stream));
+        return more_reads();
+      });
 }
 
 // what a hypothesis's state words and log say, as the single call reports them (info.launches and .prepared are the caller's)
@@ -182,11 +164,8 @@ int loc_records_prepare(tloam_ctx* c, int* prepared) {
   if (M.loc_ready) return TLOAM_OK;
   LocPrepArgs A;
   memset(&A, 0, sizeof(A));
-  A.map = M.rows.view();
+  A.grid = map_grid_of(M);
   A.sums = M.surfel_sums.p; A.normal = M.surfel_nrm.p; A.eval = M.surfel_ev.p;
-  A.nv = (long long)M.info.n_voxels;
-  A.voxel = M.cfg.voxel;
-  for (int a = 0; a < 3; ++a) A.origin[a] = M.cfg.origin[a];
   A.min_points = M.surfel_cfg.min_points;
   A.max_sigma2 = M.loc_cfg.max_sigma * M.loc_cfg.max_sigma;
   A.min_planarity = M.loc_cfg.min_planarity;
@@ -251,26 +230,30 @@ int tloam_closed_map_linearise(tloam_ctx* c, const double* points_aos, size_t n,
   if (rc0 != TLOAM_OK) return rc0;
   CmapState& M = c->cmap;
   int prepared = 0;
-  int rc = loc_begin(c, points_aos, n, ids != nullptr, residuals != nullptr, &prepared);
-  if (rc != TLOAM_OK) return loc_failed(c, rc);
   LocState st;
   memset(&st, 0, sizeof(st));
   memcpy(st.M, pose, sizeof(double) * 16);   // the matrix as it stands
   st.tau = tau;
-  auto body = [&]() -> int {
-    HIPC(c, hipMemcpyAsync(M.loc_state.p, &st, sizeof(st), hipMemcpyHostToDevice, c->stream));
-    launch_loc_sweep(sweep_args(M, n, ids ? M.loc_ids.p : nullptr, residuals ? M.loc_res.p : nullptr), 1, c->stream);
-    launch_loc_step(step_args(M, n, -1), 1, c->stream);
-    HIPC(c, hipGetLastError());
-    HIPC(c, hipMemcpyAsync(&st, M.loc_state.p, sizeof(st), hipMemcpyDeviceToHost, c->stream));
-    if (ids) HIPC(c, hipMemcpyAsync(ids, M.loc_ids.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
-    if (residuals) HIPC(c, hipMemcpyAsync(residuals, M.loc_res.p, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipStreamSynchronize(c->stream));
-    return TLOAM_OK;
-  };
-  rc = body();
-  if (rc != TLOAM_OK) return loc_failed(c, rc);
-  M.loc_ready = true;
+  const int rc = cmap_scan_call(
+      c, loc_call(points_aos, n), &prepared,
+      [&](auto room) -> int {
+        if (ids) HIPC(c, room(M.scan_ids, n));
+        if (residuals) HIPC(c, room(M.loc_res, n));
+        return loc_rooms(c, room, n, 1);
+      },
+      [&](const MapGrid& grid, const ScanAt& scan) -> int {
+        HIPC(c, hipMemcpyAsync(M.loc_state.p, &st, sizeof(st), hipMemcpyHostToDevice, c->stream));
+        launch_loc_sweep(sweep_args(M, grid, scan, ids ? M.scan_ids.p : nullptr, residuals ? M.loc_res.p : nullptr), 1, c->stream);
+        launch_loc_step(step_args(M, n, -1), 1, c->stream);
+        return TLOAM_OK;
+      },
+      [&]() -> int {
+        HIPC(c, hipMemcpyAsync(&st, M.loc_state.p, sizeof(st), hipMemcpyDeviceToHost, c->stream));
+        if (ids) HIPC(c, hipMemcpyAsync(ids, M.scan_ids.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
+        if (residuals) HIPC(c, hipMemcpyAsync(residuals, M.loc_res.p, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+        return TLOAM_OK;
+      });
+  if (rc != TLOAM_OK) return rc;
   memcpy(out28, st.sums, sizeof(double) * kLocTerms);
   counts2[0] = (int64_t)st.sums[kLocTerms];
   counts2[1] = (int64_t)st.sums[kLocTerms + 1];

@@ -2,9 +2,9 @@
 // the kernel in tl_raycast.hip).
 //
 // A ray-cast takes the built closed map with its surfels (CmapState: its rows, its table, the localiser's voxel records, the
-// carve's counts when the gate is on), uploads the segment ends where the localiser's scan goes, enqueues the records' rebuild
-// when they are stale and the one launch on the context's stream, and waits once, for the counters, the statuses, the ranges and
-// the ids.  Nothing of the closed map, of a carve, of the surfels, of a diff's counts or of anything else in the context is
+// carve's counts when the gate is on) and goes through the scan-form runner (tl_ctx.hpp: cmap_scan_call): the segment ends
+// uploaded where the localiser's scan goes, the records' rebuild enqueued when they are stale, the one launch on the context's
+// stream, one wait, for the counters, the statuses, the ranges and the ids.  The pose check is pose_finite_rigid.  Nothing of the closed map, of a carve, of the surfels, of a diff's counts or of anything else in the context is
 // written, so a detached (loaded) map is cast through like any other.  Stored: the configuration and the last info.
 #include <math.h>
 
@@ -25,39 +25,36 @@ int raycast_body(tloam_ctx* c, const double* ends_aos, size_t n, const double* p
                  unsigned long long ctl[kRaycastCtl], int* prepared) {
   CmapState& M = c->cmap;
   const tloam_closed_map_raycast_config& g = M.raycast_cfg;
-  HIPC(c, hipSetDevice(c->device));
-  HIPC(c, M.loc_pts.reserve(3 * n)); HIPC(c, M.raycast_status.reserve(n)); HIPC(c, M.raycast_range.reserve(n));
-  if (ids) HIPC(c, M.raycast_ids.reserve(n));
-  HIPC(c, M.raycast_ctl.reserve(kRaycastCtl));
-  HIPC(c, hipMemcpyAsync(M.loc_pts.p, ends_aos, sizeof(double) * 3 * n, hipMemcpyHostToDevice, c->stream));
-  const int rc = loc_records_prepare(c, prepared);
-  if (rc != TLOAM_OK) return rc;
-  HIPC(c, hipMemsetAsync(M.raycast_ctl.p, 0, sizeof(unsigned long long) * kRaycastCtl, c->stream));
-  RaycastWork W;
-  memset(&W, 0, sizeof(W));
-  W.ends = M.loc_pts.p;
-  W.n = (long long)n;
-  memcpy(W.M, pose, sizeof(W.M));   // the matrix as it stands
-  W.voxel = M.cfg.voxel;
-  for (int a = 0; a < 3; ++a) W.origin[a] = M.cfg.origin[a];
-  W.max_range = g.max_range;
-  const double radius = g.radius_cells * M.cfg.voxel;
-  W.radius2 = radius * radius;
-  W.min_count = g.min_count; W.min_miss = g.min_miss; W.miss_ratio = g.miss_ratio; W.gate = g.carve_gate; W.planes = g.planes;
-  W.map = M.rows.view();
-  W.rec = M.loc_rec.p;
-  W.miss = (const long long*)M.miss.p;
-  W.status = M.raycast_status.p; W.range = M.raycast_range.p;
-  W.ids = ids ? M.raycast_ids.p : nullptr;
-  W.ctl = M.raycast_ctl.p;
-  launch_raycast(W, c->stream);
-  HIPC(c, hipGetLastError());
-  HIPC(c, hipMemcpyAsync(ctl, M.raycast_ctl.p, sizeof(unsigned long long) * kRaycastCtl, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipMemcpyAsync(status, M.raycast_status.p, n, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipMemcpyAsync(range, M.raycast_range.p, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
-  if (ids) HIPC(c, hipMemcpyAsync(ids, M.raycast_ids.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));
-  return TLOAM_OK;
+  return cmap_scan_call(
+      c, CmapScanCall{ends_aos, n, pose, true, &M.scan_ctl, kRaycastCtl, ctl}, prepared,
+      [&](auto room) -> int {
+        HIPC(c, room(M.scan_u8, n)); HIPC(c, room(M.raycast_range, n));
+        if (ids) HIPC(c, room(M.scan_ids, n));
+        return TLOAM_OK;
+      },
+      [&](const MapGrid& grid, const ScanAt& scan) -> int {
+        RaycastWork W;
+        memset(&W, 0, sizeof(W));
+        W.scan = scan;
+        W.grid = grid;
+        W.max_range = g.max_range;
+        const double radius = g.radius_cells * M.cfg.voxel;
+        W.radius2 = radius * radius;
+        W.gate = CarveGate{(const long long*)M.miss.p, g.min_count, g.min_miss, g.miss_ratio, g.carve_gate, 0};
+        W.planes = g.planes;
+        W.rec = M.loc_rec.p;
+        W.status = M.scan_u8.p; W.range = M.raycast_range.p;
+        W.ids = ids ? M.scan_ids.p : nullptr;
+        W.ctl = M.scan_ctl.p;
+        launch_raycast(W, c->stream);
+        return TLOAM_OK;
+      },
+      [&]() -> int {
+        HIPC(c, hipMemcpyAsync(status, M.scan_u8.p, n, hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipMemcpyAsync(range, M.raycast_range.p, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+        if (ids) HIPC(c, hipMemcpyAsync(ids, M.scan_ids.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
+        return TLOAM_OK;
+      });
 }
 
 }  // namespace
@@ -96,19 +93,11 @@ int tloam_closed_map_raycast(tloam_ctx* c, const double* ends_aos, size_t n, con
   if (!c || c->nranks > 1 || !ends_aos || !pose || !status || !range || n == 0 || n > kMaxPoints) return TLOAM_E_INVALID;
   CmapState& M = c->cmap;
   if (!M.built || !M.surfeled || (M.raycast_cfg.carve_gate && !M.carved)) return TLOAM_E_NOT_READY;
-  for (int i = 0; i < 16; ++i)
-    if (!(pose[i] - pose[i] == 0.0)) return TLOAM_E_INVALID;
-  Pose rigid;   // (only the check that `pose` is a rigid transform: the cast runs at the matrix as it stands)
-  if (!pose_from_matrix(pose, &rigid)) return TLOAM_E_INVALID;
+  if (!pose_finite_rigid(pose)) return TLOAM_E_INVALID;   // (only the check: the cast runs at the matrix as it stands)
   unsigned long long ctl[kRaycastCtl];
   int prepared = 0;
   const int rc = raycast_body(c, ends_aos, n, pose, status, range, ids, ctl, &prepared);
-  if (rc != TLOAM_OK) {   // nothing of the call stays in flight; the records are rebuilt by the next call
-    (void)hipStreamSynchronize(c->stream);
-    M.loc_ready = false;
-    return rc;
-  }
-  M.loc_ready = true;
+  if (rc != TLOAM_OK) return rc;
   tloam_closed_map_raycast_info I;
   memset(&I, 0, sizeof(I));
   I.rays = (int64_t)n;

@@ -484,8 +484,8 @@ int load_body(tloam_ctx* c, const unsigned char* b, const SnapHeader& H, const H
     HIPC(c, hipMemsetAsync(F->surfel_ctl.p, 0, sizeof(unsigned long long) * 8, c->stream));
     SurfelWork W;
     memset(&W, 0, sizeof(W));
-    W.voxel = X.cfg.cmap.voxel;
-    W.nv = (long long)nv;
+    W.grid.voxel = X.cfg.cmap.voxel;   // (all k_surfel_solve reads of the map)
+    W.grid.nv = (long long)nv;
     W.min_points = X.cfg.surfel.min_points;
     W.sums = F->sums.p; W.normal = F->nrm.p; W.eval = F->ev.p; W.ctl = F->surfel_ctl.p;
     launch_surfel_solve(W, c->stream);

@@ -11,7 +11,8 @@
 //   k_carve_count   grid x 256   per voxel: M > 0 counted by ballot, one atomic per wave
 // An extension of the closed map (tl_api_extend.hip) launches k_carve_rays over the new keyframes' rays and
 // k_carve_count without the clear: the misses are added to the M that is there.
-// The carved read is k_carve_box: the box read's one body (tl_voxel.hpp: voxel_box_body), with the voxels seen through left out.
+// The carved read is k_carve_box: the box read's one body (tl_voxel.hpp: voxel_box_body), with the voxels seen through left out
+// by the carve gate's own test (tl_common.hpp: CarveGate::seen_through, which the diff, the ray-cast and the free space ask too).
 //
 // Compiled with -ffp-contract=off.  The operation order of a ray (ray_walk; tests/closed_map_carve_np.py restates it), per axis a:
 //   O_a = P[12 + a],  E = map_transform_point(P, p),  D_a = E_a - O_a,  DD = (Dx*Dx + Dy*Dy) + Dz*Dz,  L = sqrt(DD)
@@ -31,7 +32,7 @@ namespace {
 
 __global__ __launch_bounds__(256) void k_carve_clear(CarveWork W) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
-  for (size_t t = i; t < (size_t)W.nv; t += stride) W.miss[t] = 0ull;
+  for (size_t t = i; t < (size_t)W.grid.nv; t += stride) W.miss[t] = 0ull;
   if (i < 8) W.ctl[i] = 0ull;
 }
 
@@ -45,34 +46,30 @@ __global__ __launch_bounds__(256) void k_carve_rays(CarveWork W) {
     const double* P;
     double E[3];
     span_point(W.in, g, s_span[0], s_span[1], &kf, &P, E);
-    const RayGrid G{W.voxel, {W.origin[0], W.origin[1], W.origin[2]}, W.max_range, W.end_margin, W.radius2};
-    ray_walk(G, W.map, P[12], P[13], P[14], E[0], E[1], E[2], &skipped, &steps, &tested, &misses,
-             [&](int id) { atomicAdd(&W.miss[id], 1ull); });
+    ray_walk(W.grid, W.max_range, W.end_margin, W.radius2, P[12], P[13], P[14], E[0], E[1], E[2], &skipped, &steps, &tested,
+             &misses, [&](int id) { atomicAdd(&W.miss[id], 1ull); });
   }
-  skipped = wave_sum(skipped); steps = wave_sum(steps); tested = wave_sum(tested); misses = wave_sum(misses);
-  if ((threadIdx.x & 63) == 0) {
-    if (skipped) atomicAdd(&W.ctl[0], skipped);
-    if (steps) atomicAdd(&W.ctl[1], steps);
-    if (tested) atomicAdd(&W.ctl[2], tested);
-    if (misses) atomicAdd(&W.ctl[3], misses);
-  }
+  wave_add(&W.ctl[0], skipped);
+  wave_add(&W.ctl[1], steps);
+  wave_add(&W.ctl[2], tested);
+  wave_add(&W.ctl[3], misses);
 }
 
 __global__ __launch_bounds__(256) void k_carve_count(CarveWork W) {
   const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
-  const unsigned long long bal = __ballot(id < W.nv && W.miss[id] > 0ull);
+  const unsigned long long bal = __ballot(id < W.grid.nv && W.miss[id] > 0ull);
   if ((threadIdx.x & 63) == 0 && bal) atomicAdd(&W.ctl[4], (unsigned long long)__popcll(bal));
 }
 
-// the box read (the box only when A.boxed) with the voxels seen through left out; their misses beside the counts
+// the box read (the box only when A.boxed) with the voxels seen through left out (the gate's own test, whatever gate.gate says:
+// the read is the gate's; min_count is the box read's); their misses beside the counts
 struct BoxCarved {
   const CarveReadArgs& A;
   __device__ __forceinline__ bool keep(size_t id, long long n, const double*) const {
-    const long long m = A.miss[id];
-    return !(m >= A.min_miss && (double)m > A.miss_ratio * (double)n);
+    return !A.gate.seen_through(A.gate.miss[id], n);
   }
   __device__ __forceinline__ long long emit(size_t id, size_t p, long long n) const {
-    if (A.out_m) A.out_m[p] = A.miss[id];
+    if (A.out_m) A.out_m[p] = A.gate.miss[id];
     return n;
   }
 };
@@ -83,7 +80,7 @@ __global__ __launch_bounds__(256) void k_carve_box(CarveReadArgs A, int nblocks)
 }  // namespace
 
 int launch_carve(const CarveWork& W, hipStream_t s) {
-  const unsigned nv_blocks = blocks_of((size_t)std::max<long long>(W.nv, 1));   // (nothing still launches)
+  const unsigned nv_blocks = blocks_of((size_t)std::max<long long>(W.grid.nv, 1));   // (nothing still launches)
   hipLaunchKernelGGL(k_carve_clear, dim3(std::min(nv_blocks, 2048u)), dim3(256), 0, s, W);
   return 1 + launch_carve_rays(W, s) + launch_carve_count(W, s);
 }
@@ -94,7 +91,7 @@ int launch_carve_rays(const CarveWork& W, hipStream_t s) {
 }
 
 int launch_carve_count(const CarveWork& W, hipStream_t s) {
-  hipLaunchKernelGGL(k_carve_count, dim3(blocks_of((size_t)std::max<long long>(W.nv, 1))), dim3(256), 0, s, W);
+  hipLaunchKernelGGL(k_carve_count, dim3(blocks_of((size_t)std::max<long long>(W.grid.nv, 1))), dim3(256), 0, s, W);
   return 1;
 }
 

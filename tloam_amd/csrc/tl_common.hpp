@@ -610,6 +610,39 @@ struct VmapTableView {        // the same, read only: what every stage on top of
   const unsigned long long* pkey;
   const long long *pn, *pqx, *pqy, *pqz;
 };
+// What the stages on top of the closed map share of their arguments (tlh::map_grid_of fills the first):
+struct MapGrid {              // the map a stage looks voxels up in: the grid, the rows' table, the voxels
+  double voxel, origin[3];
+  VmapTableView map;
+  long long nv;
+};
+struct ScanAt {               // a live scan (or a ray-cast's segment ends) at a pose
+  const double* pts;          // AoS, sensor frame
+  long long n;
+  double M[16];               // the pose, column-major, as it stands
+};
+// The carve gate: which voxels of the closed map count for a query.  One with N < min_count does not; with `gate` on, neither
+// does one the carve saw through.  The only definition: the carved read (tl_carve.hip), the diff, the ray-cast and the free
+// space's reads all ask it, so they agree about which voxels exist
+struct CarveGate {
+  const long long* miss;      // [nv] the carve's M (read when `gate`)
+  long long min_count, min_miss;
+  double miss_ratio;
+  int gate;
+  int reserved0;
+  __device__ __forceinline__ bool seen_through(long long Mv, long long N) const {
+    return Mv >= min_miss && (double)Mv > miss_ratio * (double)N;
+  }
+  // voxel `id` counts (N is read only when min_count > 1 or the gate is on, M only when the gate is on)
+  __device__ __forceinline__ bool counts(const VmapTableView& map, int id) const {
+    if (min_count > 1 || gate) {
+      const long long N = map.pn[id];
+      if (N < min_count) return false;
+      if (gate && seen_through(miss[id], N)) return false;
+    }
+    return true;
+  }
+};
 struct VmapReadArgs {
   VmapTableView map;
   double voxel, origin[3];
@@ -698,11 +731,9 @@ int launch_extend_commit(const ExtendWork& X, hipStream_t s);
 // looked up through its own slot table and nothing in it is written: the counts are an array of their own, in id order
 struct CarveWork {
   SpanInput in;               // the rays: the points of all spans, under the poses the closed map was built with
-  double voxel, origin[3];
+  MapGrid grid;               // the closed map
   double max_range, end_margin, radius2;   // radius2 = radius * radius (+inf: the distance does not decide)
-  VmapTableView map;          // the closed map
-  long long nv;               // its voxels
-  unsigned long long* miss;   // [nv] M in id order
+  unsigned long long* miss;   // [grid.nv] M in id order
   unsigned long long* ctl;    // [0] skipped rays, [1] steps, [2] tested, [3] misses, [4] voxels with M > 0
 };
 // clear | rays | count: no host synchronisation; returns the launches it made (the same for every size)
@@ -713,9 +744,7 @@ int launch_carve_rays(const CarveWork& W, hipStream_t s);
 int launch_carve_count(const CarveWork& W, hipStream_t s);
 struct CarveReadArgs {
   VmapReadArgs rows;          // the closed map's rows, the box (when `boxed`), min_count, the outputs, look and ctl as k_vmap_box's
-  const long long* miss;      // [count] M in id order
-  long long min_miss;
-  double miss_ratio;          // a voxel is left out when M >= min_miss && (double) M > miss_ratio * (double) N
+  CarveGate gate;             // a voxel is left out when gate.seen_through(M, N) (gate.gate is not asked: the read is the gate's)
   long long* out_m;           // the misses of the voxels kept (may be null)
   int boxed;                  // 0: the whole map
 };
@@ -729,14 +758,12 @@ constexpr int kSurfelSums = 13;   // Ns, Rx Ry Rz, Sxx Sxy Sxz Syy Syz Szz, Wx W
 struct SurfelWork {
   SpanInput in;               // the points of all spans, under the poses the closed map was built with
   int* kf_over;               // [in.nkf] 1: a finite point of the keyframe left the grid (k_surfel_flag): it adds nothing
-  double voxel, origin[3];
-  VmapTableView map;          // the closed map
-  long long nv;               // its voxels
+  MapGrid grid;               // the closed map
   int runs;                   // 1: runs of equal voxels among a wave's consecutive lanes are summed before the atomics
   int min_points;             // a voxel of fewer points is not solved
-  unsigned long long* sums;   // [nv][kSurfelSums] int64 (two's complement) in id order
-  double* normal;             // [nv][3]
-  double* eval;               // [nv][3] ascending, m^2
+  unsigned long long* sums;   // [grid.nv][kSurfelSums] int64 (two's complement) in id order
+  double* normal;             // [grid.nv][3]
+  double* eval;               // [grid.nv][3] ascending, m^2
   unsigned long long* ctl;    // [0] points summed, [1] orphan points, [2] solved voxels
 };
 // clear | flag | accum | solve: no host synchronisation; returns the launches it made (the same for every size)
@@ -789,11 +816,9 @@ struct LocState {             // the stage's words in HBM: written by the host b
   int reserved0;
 };
 struct LocPrepArgs {
-  VmapTableView map;          // the closed map
+  MapGrid grid;               // the closed map
   const unsigned long long* sums;   // the surfels' thirteen per voxel
   const double *normal, *eval;
-  long long nv;
-  double voxel, origin[3];
   int min_points;
   double max_sigma2, min_planarity;
   LocRecord* rec;
@@ -802,9 +827,7 @@ struct LocSweepArgs {
   const double* pts;          // the scan, AoS
   long long n;
   LocState* st;
-  double voxel, origin[3];
-  VmapTableView map;          // the closed map
-  long long nv;
+  MapGrid grid;               // the closed map
   const LocRecord* rec;
   double* partial;            // [blocks][kLocRow]
   int* ids;                   // [n] or null
@@ -851,20 +874,12 @@ void launch_reloc_priors(const RelocPriorArgs& A, hipStream_t s);
 constexpr int kDiffCtl = 16;    // control words: [0..3] the label counts, [4] skipped rays, [5] steps, [6] tested, [7] the sum of
                                 // through, [8] voxels with through > 0, [9] voxels with hits > 0
 struct DiffWork {
-  const double* pts;          // the scan, AoS, sensor frame
-  long long n;
-  double M[16];               // the pose, column-major, as it stands
-  double voxel, origin[3];
+  ScanAt scan;                // the scan
+  MapGrid grid;               // the closed map
   double max_range, end_margin, radius2;   // the rays': radius2 = radius * radius
   double plane_tol, near2;    // the labels': near2 = near * near
-  long long min_miss;         // the carve gate (when `gate`): a voxel with Mv >= min_miss && (double) Mv > miss_ratio * (double) N
-  double miss_ratio;          // explains no point
-  int gate;
-  int reserved0;
-  VmapTableView map;          // the closed map
-  long long nv;               // its voxels
+  CarveGate gate;             // a voxel that does not count explains no point (min_count = 1)
   const LocRecord* rec;       // [nv] the localiser's records
-  const long long* miss;      // [nv] the carve's M (read when `gate`)
   unsigned long long* through;   // [nv]
   unsigned long long* hits;      // [nv]
   unsigned char* labels;      // [n]
@@ -887,19 +902,13 @@ void launch_diff_read(const DiffReadArgs& A, hipStream_t s);
 // it meets, from the localiser's voxel records.  Nothing of the closed map, the carve, the surfels or the diff is written
 constexpr int kRaycastCtl = 8;   // control words: [0] skipped, [1] missed, [2] centroid hits, [3] plane hits, [4] steps, [5] tested
 struct RaycastWork {
-  const double* ends;         // the segment ends, AoS, sensor frame
-  long long n;
-  double M[16];               // the pose, column-major, as it stands
-  double voxel, origin[3];
+  ScanAt scan;                // the segment ends (scan.pts) and the pose
+  MapGrid grid;               // the closed map
   double max_range, radius2;  // radius2 = radius * radius, radius = radius_cells * voxel
-  long long min_count;        // a voxel with N < min_count is passed through
-  long long min_miss;         // the carve gate (when `gate`): so is one with Mv >= min_miss && (double) Mv > miss_ratio * (double) N
-  double miss_ratio;
-  int gate;
+  CarveGate gate;             // a voxel that does not count is passed through
   int planes;                 // 0 the centroid test alone, 1 the plane test where eligible, 2 the plane test alone
-  VmapTableView map;          // the closed map
+  int reserved0;
   const LocRecord* rec;       // [nv] the localiser's records
-  const long long* miss;      // [nv] the carve's M (read when `gate`)
   unsigned char* status;      // [n]
   double* range;              // [n]
   int* ids;                   // [n] or null
@@ -919,35 +928,24 @@ struct FreeGrid {
 };
 struct FreeWork {
   SpanInput in;               // the keyframe form: the rays of all spans, under the poses the closed map holds
-  const double* pts;          // the scan form: the ends, AoS, sensor frame ...
-  long long n;
-  double M[16];               // ... at this pose, column-major, as it stands
-  double voxel, origin[3];
+  ScanAt scan;                // the scan form: the ends at one pose
+  MapGrid grid;               // the closed map (its table is not read by the walk)
   double max_range, end_margin;
-  VmapTableView map;          // the closed map (not read by the walk)
-  long long nv;
   FreeGrid g;
   unsigned long long* ctl;    // [kFreeCtl], zero before the launches
 };
 int launch_free_clear(const FreeGrid& g, hipStream_t s);                 // the words zeroed; returns the launches it made
 int launch_free_rays(const FreeWork& W, bool spans, hipStream_t s);      // rays | count: the same two launches for every size
 struct FreeQuery {            // what a read of the grid resolves occupancy with
-  VmapTableView map;          // the closed map
-  const long long* miss;      // [nv] the carve's M (read when `gate`)
-  long long min_count, min_miss;
-  double miss_ratio;
-  int gate;
-  int reserved0;
-  double voxel, origin[3];
+  MapGrid grid;               // the closed map
+  CarveGate gate;             // which of its voxels count
   FreeGrid g;
 };
 struct FreePointsArgs {
   FreeQuery q;
-  const double* pts;          // AoS
-  long long n;
-  int posed;                  // 1: the points are in the sensor frame of M; 0: in the map frame
+  ScanAt scan;                // the points, and the pose when `posed`
+  int posed;                  // 1: the points are in the sensor frame of scan.M; 0: in the map frame
   int reserved0;
-  double M[16];
   unsigned char* state;       // [n]
   int* ids;                   // [n] or null
   unsigned long long* ctl;    // [0..3] points per state, zero before the launch

@@ -447,6 +447,12 @@ struct CmapState {
   DBuf<double> rd_c;
   DBuf<long long> rd_n;
   DBuf<unsigned long long> look, ctl;
+  // the scratch of one scan-form call (cmap_scan_call below: a linearise, a diff, a ray-cast, an occupancy query) and of the free
+  // space's other reads: a byte and an id per point, the control words (kDiffCtl: the largest user's).  Every call that uses
+  // them waits for its read-back before it returns, so no two users are ever live at once and nothing is read after the call
+  DBuf<unsigned char> scan_u8;
+  DBuf<int> scan_ids;
+  DBuf<unsigned long long> scan_ctl;
   // the carve (tl_api_carve.hip): its configuration, M in id order beside the rows, what the last carve
   // reports, the carved read's scratch.  The counts belong to the closed map they were counted in and go with it
   tloam_closed_map_carve_config carve_cfg = {60.0, 1.0, 0.25, 0, 0};   // tloam_closed_map_carve_default_config until configured
@@ -470,11 +476,11 @@ struct CmapState {
   tloam_closed_map_surfel_info surfel_info{};
   // the localisation (tl_api_localise.hip): its configuration, the voxel records {c, n, eligible} cached
   // beside the rows (allocated by the first call, for the rows' capacity; rebuilt when the surfels or the gate change), the
-  // uploaded scan, the blocks' partial rows, the per-point outputs of a linearise, the state words and the log of the last call
+  // uploaded scan, the blocks' partial rows, the residuals of a linearise (its ids: scan_ids), the state words and the log of the
+  // last call
   tloam_closed_map_localise_config loc_cfg = {1.0, 0.7, 0.1, HUGE_VAL, 0.05, 1e-6, 1e-7, 1e-9, 20, 50};   // _localise_default_config
   DBuf<tl::LocRecord> loc_rec;
   DBuf<double> loc_pts, loc_partial, loc_res;
-  DBuf<int> loc_ids;
   DBuf<tl::LocState> loc_state;
   DBuf<tl::LocLog> loc_log;
   bool loc_ready = false;          // the records are those of the surfels and the gate at hand
@@ -500,13 +506,11 @@ struct CmapState {
     drop_localise();
   }
   // the diff of a scan against the map (tl_api_diff.hip): its configuration, through and hits in id order
-  // beside the rows, the control words, the per-point outputs of the last call, what the last diff reports, the gone read's
-  // scratch.  The scan is uploaded where the localiser's is (loc_pts) and the labels read the localiser's records (loc_rec).  The
+  // beside the rows, what the last diff reports, the gone read's scratch.  The scan is uploaded where the localiser's is
+  // (loc_pts), the labels read the localiser's records (loc_rec) and go through the scan-form scratch (scan_u8, scan_ids).  The
   // counts belong to the closed map they were counted in and go with it; a carve or a surfel pass does not touch them
   tloam_closed_map_diff_config diff_cfg = {60.0, 1.0, 0.25, 0.1, 0.5, 3, 1.0, 0, 0};   // tloam_closed_map_diff_default_config
-  DBuf<unsigned long long> diff_through, diff_hits, diff_ctl;
-  DBuf<unsigned char> diff_labels;
-  DBuf<int> diff_ids;
+  DBuf<unsigned long long> diff_through, diff_hits;
   DBuf<unsigned char> rd_through, rd_hits;
   bool diffed = false;             // a diff has succeeded since the last drop: there are counts
   tloam_closed_map_diff_info diff_info{};
@@ -514,27 +518,22 @@ struct CmapState {
     diffed = false;
     diff_info = tloam_closed_map_diff_info{};
   }
-  // the ray-cast (tl_api_raycast.hip): its configuration, the per-ray outputs of the last call (13 bytes a
-  // ray, grow-only), the control words and what the last cast reports.  The ends are uploaded where the localiser's scan is
-  // (loc_pts) and the tests read the localiser's records (loc_rec).  Nothing else is stored
+  // the ray-cast (tl_api_raycast.hip): its configuration, the ranges of the last call (its statuses and
+  // ids: scan_u8, scan_ids) and what the last cast reports.  The ends are uploaded where the localiser's scan is (loc_pts) and
+  // the tests read the localiser's records (loc_rec).  Nothing else is stored
   tloam_closed_map_raycast_config raycast_cfg = {120.0, 0.75, 1, 3, 1.0, 1, 0};   // tloam_closed_map_raycast_default_config
-  DBuf<unsigned char> raycast_status;
   DBuf<double> raycast_range;
-  DBuf<int> raycast_ids;
-  DBuf<unsigned long long> raycast_ctl;
   tloam_closed_map_raycast_info raycast_info{};
   void drop_raycast() { raycast_info = tloam_closed_map_raycast_info{}; }
   // the extension (tl_api_extend.hip): what the last extend of this map reports
   tloam_closed_map_extend_info extend_info{};
   // the free space (tl_api_free.hip): its configuration, the grid of brick words and its box, what the
-  // grid reports, the reads' scratch.  The grid belongs to the closed map it was gathered beside and goes with it (its memory
+  // grid reports, the cells read's scratch (the other reads': scan_u8, scan_ids, scan_ctl).  The grid belongs to the closed map it was gathered beside and goes with it (its memory
   // too: it can be large); an extend leaves it alone
   struct FreeState {
     tloam_closed_map_free_config cfg = {60.0, 1.0, (int64_t)1 << 30, 1, 3, 1.0, 0, 0};   // tloam_closed_map_free_default_config
-    DBuf<unsigned long long> words, ctl, look, rd_ctl;
+    DBuf<unsigned long long> words, ctl, look;   // ctl: an add's counters (cmap_pass, cmap_scan_call)
     DBuf<double> rd_c;
-    DBuf<unsigned char> state;
-    DBuf<int> ids;
     tl::FreeGrid grid{};
     bool have = false;             // a reset has succeeded since the last drop
     tloam_closed_map_free_info info{};
@@ -1024,8 +1023,18 @@ struct SpanUpload {
   // both uploaded on the context's stream; *in: what the kernels take (arena, span, nspan, nkf, n, pose)
   int upload(tloam_ctx* c, const std::vector<tl::CmapSpan>& spans, long long n, const double* poses, size_t K, tl::SpanInput* in);
 };
+// the built closed map as its stages look voxels up in it: every Work's `grid`
+inline tl::MapGrid map_grid_of(const CmapState& M) {
+  tl::MapGrid G;
+  memset(&G, 0, sizeof(G));
+  G.voxel = M.cfg.voxel;
+  for (int a = 0; a < 3; ++a) G.origin[a] = M.cfg.origin[a];
+  G.map = M.rows.view();
+  G.nv = (long long)M.info.n_voxels;
+  return G;
+}
 // One pass over the points the closed map was built from (the carve, the surfels): the span table for `mask` over the build's
-// keyframes uploaded beside the build's poses, the fields every pass's Work has filled (in, voxel, origin, map, nv, ctl), the
+// keyframes uploaded beside the build's poses, the fields every pass's Work has filled (in, grid, ctl), the
 // launches of fill_and_launch(W), which fills the rest and returns their number, the eight words of `ctl` read back, one wait.
 // reserve() sizes the pass's arrays, `ctl` among them, after waiting when one that it replaces may still be read.  `first`: the
 // pass runs over keyframes [first, K) alone (the free space's add after an extension): their spans, their poses
@@ -1051,10 +1060,7 @@ int cmap_pass(tloam_ctx* c, int mask, const DBuf<unsigned long long>& ctl, Reser
   memset(&W, 0, sizeof(W));
   rc = up.upload(c, spans, out->n, M.poses.data() + 16 * first, out->K - first, &W.in);
   if (rc != TLOAM_OK) return rc;
-  W.voxel = M.cfg.voxel;
-  for (int a = 0; a < 3; ++a) W.origin[a] = M.cfg.origin[a];
-  W.map = M.rows.view();
-  W.nv = (long long)M.info.n_voxels;
+  W.grid = map_grid_of(M);
   W.ctl = ctl.p;
   out->launches = fill_and_launch(W);
   HIPC(c, hipGetLastError());
@@ -1095,8 +1101,73 @@ bool cmap_config_valid(const tloam_closed_map_config& cfg);         // tl_api_cm
 size_t cmap_default_reserve();
 bool carve_config_valid(const tloam_closed_map_carve_config& cfg);  // tl_api_carve.hip
 // tl_api_localise.hip: the localiser's voxel records {c, n, eligible} sized and, when they are stale, their rebuild enqueued
-// (*prepared = 1; k_loc_prepare).  The caller sets CmapState::loc_ready once its call has succeeded (the localiser, the diff)
+// (*prepared = 1; k_loc_prepare).  cmap_scan_call sets CmapState::loc_ready once the call that asked for them has succeeded
 int loc_records_prepare(tloam_ctx* c, int* prepared);
+// `pose` (column-major) is finite and a rigid transform: what every call that takes a live scan at a pose asks of it, after its
+// argument and readiness checks (TLOAM_E_INVALID when not).  *T (may be null): the pose as pose_from_matrix forms it.
+// (static: each includer's own copy, rounded under its own flags.)
+static inline bool pose_finite_rigid(const double* pose, tl::Pose* T = nullptr) {
+  for (int i = 0; i < 16; ++i)
+    if (!(pose[i] - pose[i] == 0.0)) return false;
+  tl::Pose rigid;
+  return tl::pose_from_matrix(pose, T ? T : &rigid);
+}
+// One scan-form call on the built closed map -- a live scan (or segment ends) at a pose, queried against the map: the localiser's
+// runs and its linearise, the diff, the ray-cast, the free space's add_scan and occupancy -- the counterpart of cmap_pass for
+// keyframe passes.  In order: the device set; the stream waited for once when a buffer about to grow is too small (the stream is
+// idle at entry of these synchronous calls: it costs nothing in steady state); loc_pts, the control words and whatever
+// rooms(room) names through room(buffer, elements) reserved; the scan uploaded; the localiser's records prepared when
+// `records` (*prepared); the control words zeroed; fill_and_launch(grid, scan), which fills the rest of its Work, launches and
+// returns a status; hipGetLastError; the control words read back into ctl_out; the caller's reads() enqueued; one wait.
+// A failure drains the stream and, when the records were involved, marks them stale; the caller then drops what it must
+// (drop_diff, free.drop()).  On success with records, loc_ready is set.
+struct CmapScanCall {
+  const double* points_aos;          // the scan, AoS, sensor frame
+  size_t n;
+  const double* pose;                // column-major, taken as it stands (null: none, scan.M is zero)
+  bool records;                      // the call reads the localiser's voxel records
+  DBuf<unsigned long long>* ctl;     // the control words (null: none) ...
+  size_t n_ctl;                      // ... their number, zeroed before the launches
+  unsigned long long* ctl_out;       // [n_ctl] as the launches left them
+};
+template <class Rooms, class Launch, class Reads>
+int cmap_scan_call(tloam_ctx* c, const CmapScanCall& q, int* prepared, Rooms rooms, Launch fill_and_launch, Reads reads) {
+  CmapState& M = c->cmap;
+  auto body = [&]() -> int {
+    HIPC(c, hipSetDevice(c->device));
+    auto all_rooms = [&](auto room) -> int {
+      HIPC(c, room(M.loc_pts, 3 * q.n));
+      if (q.ctl) HIPC(c, room(*q.ctl, std::max<size_t>(q.n_ctl, tl::kDiffCtl)));   // (the largest user's: never regrown)
+      return rooms(room);
+    };
+    bool grows = false;
+    (void)all_rooms([&](auto& buf, size_t n) { grows = grows || buf.cap < n; return hipSuccess; });
+    if (grows) HIPC(c, hipStreamSynchronize(c->stream));   // (what is replaced may still be read)
+    int rc = all_rooms([](auto& buf, size_t n) { return buf.reserve(n); });
+    if (rc != TLOAM_OK) return rc;
+    HIPC(c, hipMemcpyAsync(M.loc_pts.p, q.points_aos, sizeof(double) * 3 * q.n, hipMemcpyHostToDevice, c->stream));
+    *prepared = 0;
+    if (q.records && (rc = loc_records_prepare(c, prepared)) != TLOAM_OK) return rc;
+    if (q.ctl) HIPC(c, hipMemsetAsync(q.ctl->p, 0, sizeof(unsigned long long) * q.n_ctl, c->stream));
+    tl::ScanAt scan;
+    memset(&scan, 0, sizeof(scan));
+    scan.pts = M.loc_pts.p;
+    scan.n = (long long)q.n;
+    if (q.pose) memcpy(scan.M, q.pose, sizeof(scan.M));   // the matrix as it stands
+    rc = fill_and_launch(map_grid_of(M), scan);
+    if (rc != TLOAM_OK) return rc;
+    HIPC(c, hipGetLastError());
+    if (q.ctl) HIPC(c, hipMemcpyAsync(q.ctl_out, q.ctl->p, sizeof(unsigned long long) * q.n_ctl, hipMemcpyDeviceToHost, c->stream));
+    rc = reads();
+    if (rc != TLOAM_OK) return rc;
+    HIPC(c, hipStreamSynchronize(c->stream));
+    return TLOAM_OK;
+  };
+  const int rc = body();
+  if (rc != TLOAM_OK) (void)hipStreamSynchronize(c->stream);   // nothing of the call stays in flight
+  if (q.records) M.loc_ready = rc == TLOAM_OK;                  // (a failed call's records are rebuilt by the next)
+  return rc;
+}
 // tl_api_deskew.hip: the frame's deskew -- sized and its times uploaded after the scan's upload, launched after the segmentation's
 // (the refused-time flag read with the frame's first wait), committed when the frame ends
 int deskew_frame_upload(tloam_ctx* c, const double* t_sec, size_t n, tloam_odom_stats* st);

@@ -13,7 +13,8 @@
 //                                 shuffles, one atomic per counter and wave.  Two entry points over one body: the keyframes'
 //                                 spans (span_point, the carve's rays) and one origin (the diff's rays)
 //   k_free_count     grid x 256   popcount of the words and the nonzero words: a wave sum, one atomic per counter and wave
-//   k_free_points    grid x 256   the occupancy of a point: one id_table_find, one word read; the states counted by ballot
+//   k_free_points    grid x 256   the occupancy of a point: one cell_voxel, the carve gate (tl_common.hpp: CarveGate), one word
+//                                 read; the states counted by ballot (wave_count_states)
 //   k_free_cells     grid x 256   a thread per brick: the bits of the cells that pass (free, not a counting voxel, in the metric
 //                                 box), their popcount scanned over the block (block_packed_scan) and the blocks (lookback_prefix
 //                                 over start tickets), the centres scattered: brick index ascending, then bit ascending
@@ -59,9 +60,8 @@ __device__ __forceinline__ unsigned long long free_bit(int cx, int cy, int cz) {
 // one ray from O to E: *skipped, *marked, *outside are set for it (a skipped ray: 1, 0, 0)
 __device__ __forceinline__ void free_ray(const FreeWork& W, double Ox, double Oy, double Oz, double Ex, double Ey, double Ez,
                                          unsigned long long* skipped, unsigned long long* marked, unsigned long long* outside) {
-  const RayGrid G{W.voxel, {W.origin[0], W.origin[1], W.origin[2]}, W.max_range, W.end_margin, 0.0};
   RayCells R;
-  if (!ray_begin(G, Ox, Oy, Oz, Ex, Ey, Ez, &R)) {
+  if (!ray_begin(W.grid, W.max_range, Ox, Oy, Oz, Ex, Ey, Ez, &R)) {
     *skipped = 1ull;
     return;
   }
@@ -95,12 +95,9 @@ __device__ __forceinline__ void free_ray(const FreeWork& W, double Ox, double Oy
 
 __device__ __forceinline__ void free_post(const FreeWork& W, unsigned long long skipped, unsigned long long marked,
                                           unsigned long long outside) {
-  skipped = wave_sum(skipped); marked = wave_sum(marked); outside = wave_sum(outside);
-  if ((threadIdx.x & 63) == 0) {
-    if (skipped) atomicAdd(&W.ctl[0], skipped);
-    if (marked) atomicAdd(&W.ctl[1], marked);
-    if (outside) atomicAdd(&W.ctl[2], outside);
-  }
+  wave_add(&W.ctl[0], skipped);
+  wave_add(&W.ctl[1], marked);
+  wave_add(&W.ctl[2], outside);
 }
 
 __global__ __launch_bounds__(256) void k_free_rays(FreeWork W) {
@@ -121,10 +118,11 @@ __global__ __launch_bounds__(256) void k_free_rays(FreeWork W) {
 __global__ __launch_bounds__(256) void k_free_rays_scan(FreeWork W) {
   const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
   unsigned long long skipped = 0ull, marked = 0ull, outside = 0ull;
-  if (g < W.n) {
+  if (g < W.scan.n) {
+    const double* M = W.scan.M;
     double E[3];
-    map_transform_point(W.M, W.pts[3 * g], W.pts[3 * g + 1], W.pts[3 * g + 2], &E[0], &E[1], &E[2]);
-    free_ray(W, W.M[12], W.M[13], W.M[14], E[0], E[1], E[2], &skipped, &marked, &outside);
+    map_transform_point(M, W.scan.pts[3 * g], W.scan.pts[3 * g + 1], W.scan.pts[3 * g + 2], &E[0], &E[1], &E[2]);
+    free_ray(W, M[12], M[13], M[14], E[0], E[1], E[2], &skipped, &marked, &outside);
   }
   free_post(W, skipped, marked, outside);
 }
@@ -137,41 +135,27 @@ __global__ __launch_bounds__(256) void k_free_count(FreeWork W) {
     cells += (unsigned long long)__popcll(w);
     bricks += w ? 1ull : 0ull;
   }
-  cells = wave_sum(cells); bricks = wave_sum(bricks);
-  if ((threadIdx.x & 63) == 0) {
-    if (cells) atomicAdd(&W.ctl[3], cells);
-    if (bricks) atomicAdd(&W.ctl[4], bricks);
-  }
+  wave_add(&W.ctl[3], cells);
+  wave_add(&W.ctl[4], bricks);
 }
 
 // the id of the voxel of cell (cx, cy, cz) when it has one that counts, else -1
 __device__ __forceinline__ int free_counting_voxel(const FreeQuery& q, int cx, int cy, int cz) {
-  const int lim = 1 << kVmapBits;
-  if (cx <= -lim || cx >= lim || cy <= -lim || cy >= lim || cz <= -lim || cz >= lim) return -1;   // beyond the grid: no voxel
-  const unsigned long long key = (unsigned long long)(cx + lim) | ((unsigned long long)(cy + lim) << 21) |
-                                 ((unsigned long long)(cz + lim) << 42);
-  const int id = id_table_find(q.map.ptab, q.map.pmask, q.map.pkey, key);
-  if (id < 0) return -1;
-  const long long N = q.map.pn[id];
-  if (N < q.min_count) return -1;
-  if (q.gate) {
-    const long long Mv = q.miss[id];
-    if (Mv >= q.min_miss && (double)Mv > q.miss_ratio * (double)N) return -1;
-  }
-  return id;
+  const int id = cell_voxel(q.grid.map, cx, cy, cz);
+  return id >= 0 && q.gate.counts(q.grid.map, id) ? id : -1;
 }
 
 __global__ __launch_bounds__(256) void k_free_points(FreePointsArgs A) {
   const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
-  const bool live = g < A.n;
+  const bool live = g < A.scan.n;
   int state = TLOAM_OCCUPANCY_INVALID;
   if (live) {
-    double E[3] = {A.pts[3 * g], A.pts[3 * g + 1], A.pts[3 * g + 2]};
-    if (A.posed) map_transform_point(A.M, E[0], E[1], E[2], &E[0], &E[1], &E[2]);
+    double E[3] = {A.scan.pts[3 * g], A.scan.pts[3 * g + 1], A.scan.pts[3 * g + 2]};
+    if (A.posed) map_transform_point(A.scan.M, E[0], E[1], E[2], &E[0], &E[1], &E[2]);
     unsigned long long key;
     unsigned qq[3];
     int id = -1;
-    if (vmap_quantise(E, A.q.origin, A.q.voxel, &key, qq) == kVmapInside) {
+    if (vmap_quantise(E, A.q.grid.origin, A.q.grid.voxel, &key, qq) == kVmapInside) {
       const int cx = (int)key_axis(key, 0), cy = (int)key_axis(key, 1), cz = (int)key_axis(key, 2);
       id = free_counting_voxel(A.q, cx, cy, cz);
       if (id >= 0) {
@@ -185,11 +169,7 @@ __global__ __launch_bounds__(256) void k_free_points(FreePointsArgs A) {
     A.state[g] = (unsigned char)state;
     if (A.ids) A.ids[g] = id;
   }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const unsigned long long bal = __ballot(live && state == k);
-    if ((threadIdx.x & 63) == 0 && bal) atomicAdd(&A.ctl[k], (unsigned long long)__popcll(bal));
-  }
+  wave_count_states(live, state, A.ctl);
 }
 
 __global__ __launch_bounds__(256) void k_free_cells(FreeCellsArgs A, int nblocks) {
@@ -199,6 +179,7 @@ __global__ __launch_bounds__(256) void k_free_cells(FreeCellsArgs A, int nblocks
   const int tid = threadIdx.x;
   const int bid = block_ticket(&A.ctl[0], &s_bid);
   const FreeGrid& g = A.q.g;
+  const MapGrid& G = A.q.grid;
   const long long i = (long long)bid * 256 + tid;
   unsigned long long pass = 0ull;
   int x0 = 0, y0 = 0, z0 = 0;
@@ -216,8 +197,8 @@ __global__ __launch_bounds__(256) void k_free_cells(FreeCellsArgs A, int nblocks
       const int cx = x0 + (b & 3), cy = y0 + ((b >> 2) & 3), cz = z0 + (b >> 4);
       if (free_counting_voxel(A.q, cx, cy, cz) >= 0) continue;
       if (A.boxed) {
-        const double px = A.q.origin[0] + ((double)cx + 0.5) * A.q.voxel, py = A.q.origin[1] + ((double)cy + 0.5) * A.q.voxel,
-                     pz = A.q.origin[2] + ((double)cz + 0.5) * A.q.voxel;
+        const double px = G.origin[0] + ((double)cx + 0.5) * G.voxel, py = G.origin[1] + ((double)cy + 0.5) * G.voxel,
+                     pz = G.origin[2] + ((double)cz + 0.5) * G.voxel;
         if (!(px >= A.lo[0] && px <= A.hi[0] && py >= A.lo[1] && py <= A.hi[1] && pz >= A.lo[2] && pz <= A.hi[2])) continue;
       }
       pass |= 1ull << b;
@@ -231,9 +212,9 @@ __global__ __launch_bounds__(256) void k_free_cells(FreeCellsArgs A, int nblocks
   while (pass) {
     const int b = __builtin_ctzll(pass);
     pass &= pass - 1ull;
-    A.out_c[3 * p] = A.q.origin[0] + ((double)(x0 + (b & 3)) + 0.5) * A.q.voxel;
-    A.out_c[3 * p + 1] = A.q.origin[1] + ((double)(y0 + ((b >> 2) & 3)) + 0.5) * A.q.voxel;
-    A.out_c[3 * p + 2] = A.q.origin[2] + ((double)(z0 + (b >> 4)) + 0.5) * A.q.voxel;
+    A.out_c[3 * p] = G.origin[0] + ((double)(x0 + (b & 3)) + 0.5) * G.voxel;
+    A.out_c[3 * p + 1] = G.origin[1] + ((double)(y0 + ((b >> 2) & 3)) + 0.5) * G.voxel;
+    A.out_c[3 * p + 2] = G.origin[2] + ((double)(z0 + (b >> 4)) + 0.5) * G.voxel;
     ++p;
   }
   if (bid == nblocks - 1 && tid == 0) A.ctl[2] = s_prefix + total;
@@ -268,7 +249,7 @@ int launch_free_clear(const FreeGrid& g, hipStream_t s) {
 }
 
 int launch_free_rays(const FreeWork& W, bool spans, hipStream_t s) {
-  const unsigned n_blocks = blocks_of((size_t)std::max<long long>(spans ? W.in.n : W.n, 1));   // (nothing still launches)
+  const unsigned n_blocks = blocks_of((size_t)std::max<long long>(spans ? W.in.n : W.scan.n, 1));   // (nothing still launches)
   if (spans) hipLaunchKernelGGL(k_free_rays, dim3(n_blocks), dim3(256), 0, s, W);
   else hipLaunchKernelGGL(k_free_rays_scan, dim3(n_blocks), dim3(256), 0, s, W);
   const unsigned w_blocks = blocks_of((size_t)std::max<long long>(W.g.nwords, 1));
@@ -277,7 +258,7 @@ int launch_free_rays(const FreeWork& W, bool spans, hipStream_t s) {
 }
 
 void launch_free_points(const FreePointsArgs& A, hipStream_t s) {
-  hipLaunchKernelGGL(k_free_points, dim3(blocks_of((size_t)std::max<long long>(A.n, 1))), dim3(256), 0, s, A);
+  hipLaunchKernelGGL(k_free_points, dim3(blocks_of((size_t)std::max<long long>(A.scan.n, 1))), dim3(256), 0, s, A);
 }
 
 void launch_free_cells(const FreeCellsArgs& A, hipStream_t s) {

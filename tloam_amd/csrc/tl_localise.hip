@@ -4,7 +4,8 @@
 // Launches (no host synchronisation between them; nothing of the closed map, the carve or the surfels is written):
 //   k_loc_prepare   grid x 256   per voxel one 64-byte record {c, n, eligible}: a probe hit then costs one cache line; eligible
 //                                is tl_voxel.hpp's surfel_gate, the gate of the surfels' box read
-//   k_loc_sweep     (grid, B) x 256   per point: transform, quantise, 27 read-only probes of the closed map's slot table, the
+//   k_loc_sweep     (grid, B) x 256   per point: transform, quantise, the 27 read-only probes of the closed map's slot table
+//                                     (tl_voxel.hpp: probe27, the diff's too), the
 //                                     nearest eligible centroid, residual, truncation; the 28 terms, the two counts and the scan's
 //                                     finite points (row slot kLocFinite) summed over the wave by shuffles and over the block's
 //                                     four waves through LDS; one partial row per block
@@ -36,10 +37,10 @@ namespace {
 
 __global__ __launch_bounds__(256) void k_loc_prepare(LocPrepArgs A) {
   const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (id >= A.nv) return;
+  if (id >= A.grid.nv) return;
   LocRecord R;
   long long n;
-  voxel_centroid(A.map, A.origin, A.voxel, (size_t)id, R.c, &n);
+  voxel_centroid(A.grid.map, A.grid.origin, A.grid.voxel, (size_t)id, R.c, &n);
   double ev[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
@@ -74,29 +75,19 @@ __global__ __launch_bounds__(256) void k_loc_sweep(LocSweepArgs W) {
     unsigned q[3];
     int best = -1;
     double bd[3] = {0.0, 0.0, 0.0}, bn[3] = {0.0, 0.0, 0.0};
-    if (W.nv > 0 && vmap_quantise(E, W.origin, W.voxel, &key, q) == kVmapInside) {
-      const long long i0 = key_axis(key, 0), i1 = key_axis(key, 1), i2 = key_axis(key, 2);
-      const long long lim = 1ll << kVmapBits;
+    if (W.grid.nv > 0 && vmap_quantise(E, W.grid.origin, W.grid.voxel, &key, q) == kVmapInside) {
       double bD = HUGE_VAL;
-      for (int dz = -1; dz <= 1; ++dz)
-        for (int dy = -1; dy <= 1; ++dy)
-          for (int dx = -1; dx <= 1; ++dx) {
-            const long long c0 = i0 + dx, c1 = i1 + dy, c2 = i2 + dz;
-            if (c0 <= -lim || c0 >= lim || c1 <= -lim || c1 >= lim || c2 <= -lim || c2 >= lim) continue;   // beyond the grid: no voxel
-            const unsigned long long ck = (unsigned long long)(c0 + lim) | ((unsigned long long)(c1 + lim) << 21) |
-                                          ((unsigned long long)(c2 + lim) << 42);
-            const int id = id_table_find(W.map.ptab, W.map.pmask, W.map.pkey, ck);
-            if (id < 0) continue;
-            const LocRecord* R = W.rec + id;
-            if (!R->eligible) continue;
-            const double d0 = E[0] - R->c[0], d1 = E[1] - R->c[1], d2 = E[2] - R->c[2];
-            const double D = (d0 * d0 + d1 * d1) + d2 * d2;
-            if (D < bD) {
-              best = id; bD = D;
-              bd[0] = d0; bd[1] = d1; bd[2] = d2;
-              bn[0] = R->n[0]; bn[1] = R->n[1]; bn[2] = R->n[2];
-            }
-          }
+      probe27(W.grid.map, key, [&](int id, bool) {
+        const LocRecord* R = W.rec + id;
+        if (!R->eligible) return;
+        const double d0 = E[0] - R->c[0], d1 = E[1] - R->c[1], d2 = E[2] - R->c[2];
+        const double D = (d0 * d0 + d1 * d1) + d2 * d2;
+        if (D < bD) {
+          best = id; bD = D;
+          bd[0] = d0; bd[1] = d1; bd[2] = d2;
+          bn[0] = R->n[0]; bn[1] = R->n[1]; bn[2] = R->n[2];
+        }
+      });
     }
     double r = 0.0;
     if (best >= 0) {
@@ -303,8 +294,8 @@ void launch_reloc_priors(const RelocPriorArgs& A, hipStream_t s) {
 }
 
 void launch_loc_prepare(const LocPrepArgs& A, hipStream_t s) {
-  if (A.nv <= 0) return;
-  hipLaunchKernelGGL(k_loc_prepare, dim3(loc_blocks(A.nv)), dim3(256), 0, s, A);
+  if (A.grid.nv <= 0) return;
+  hipLaunchKernelGGL(k_loc_prepare, dim3(loc_blocks(A.grid.nv)), dim3(256), 0, s, A);
 }
 
 void launch_loc_sweep(const LocSweepArgs& A, int B, hipStream_t s) {

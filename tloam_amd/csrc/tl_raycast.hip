@@ -6,7 +6,7 @@
 //   k_cast_rays     ceil(n / 256) x 256   per ray: the end transformed, the carve's skip rule and set-up (tl_voxel.hpp: ray_begin),
 //                                the walk that stops (ray_first_hit): the start cell, every cell stepped into and the end cell
 //                                looked up in the closed map's slot table (id_table_find, read only); of a voxel one LocRecord
-//                                (and N and the carve's M when min_count > 1 or the gate is on); status (1 B), range (8 B) and
+//                                (and N and the carve's M when min_count > 1 or the gate is on: CarveGate::counts); status (1 B), range (8 B) and
 //                                the optional id (4 B) stored; the four status counts by ballot, steps and tested summed over
 //                                the wave by shuffles, one integer atomic per counter and wave
 // No block waits on another block.  No floating-point atomics: every sum is an integer, so two calls give the same bytes.  Lanes
@@ -14,7 +14,8 @@
 //
 // Compiled with -ffp-contract=off.  The arithmetic of a ray (tests/closed_map_raycast_np.py restates it):
 //   O = (M[12], M[13], M[14]),  E = map_transform_point(M, p);  skip rule, D, DD, L and the walk: tl_carve.hip's header
-//   a visited voxel counts when N >= min_count and, the gate on, not (Mv >= min_miss && (double) Mv > miss_ratio * (double) N)
+//   a visited voxel counts when the carve gate says so (tl_common.hpp: CarveGate, the one definition the carved read, the diff and
+//   the free space share)
 //   R = rec[id]:  u = R.c - O,  tt = ((ux*Dx + uy*Dy) + uz*Dz) / DD,  w = u - tt * D
 //   centroid test: 0 <= tt && tt <= 1 && (wx*wx + wy*wy) + wz*wz <= radius2 -> t = tt
 //   plane test, instead, when planes != 0 && R.eligible && (den = (nx*Dx + ny*Dy) + nz*Dz) != 0:
@@ -30,29 +31,22 @@ namespace {
 
 __global__ __launch_bounds__(256) void k_cast_rays(RaycastWork W) {
   const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
-  const bool live = g < W.n;
+  const bool live = g < W.scan.n;
   int status = TLOAM_RAYCAST_SKIPPED;
   unsigned long long steps = 0ull, tested = 0ull;
   if (live) {
+    const double* M = W.scan.M;
     double Ex, Ey, Ez;
-    map_transform_point(W.M, W.ends[3 * g], W.ends[3 * g + 1], W.ends[3 * g + 2], &Ex, &Ey, &Ez);
-    const double Ox = W.M[12], Oy = W.M[13], Oz = W.M[14];
-    const RayGrid G{W.voxel, {W.origin[0], W.origin[1], W.origin[2]}, W.max_range, 0.0, W.radius2};
+    map_transform_point(M, W.scan.pts[3 * g], W.scan.pts[3 * g + 1], W.scan.pts[3 * g + 2], &Ex, &Ey, &Ez);
+    const double Ox = M[12], Oy = M[13], Oz = M[14];
     RayCells R;
     double range = -1.0;
     int hit = -1;
-    if (ray_begin(G, Ox, Oy, Oz, Ex, Ey, Ez, &R)) {
+    if (ray_begin(W.grid, W.max_range, Ox, Oy, Oz, Ex, Ey, Ez, &R)) {
       double t = 0.0;
       status = TLOAM_RAYCAST_MISS;
-      hit = ray_first_hit(W.map, &R, &steps, [&](int id) -> bool {
-        if (W.min_count > 1 || W.gate) {
-          const long long N = W.map.pn[id];
-          if (N < W.min_count) return false;
-          if (W.gate) {
-            const long long Mv = W.miss[id];
-            if (Mv >= W.min_miss && (double)Mv > W.miss_ratio * (double)N) return false;
-          }
-        }
+      hit = ray_first_hit(W.grid.map, &R, &steps, [&](int id) -> bool {
+        if (!W.gate.counts(W.grid.map, id)) return false;
         const LocRecord* V = W.rec + id;
         const double ux = V->c[0] - Ox, uy = V->c[1] - Oy, uz = V->c[2] - Oz;
         if (W.planes != 0 && V->eligible) {
@@ -87,22 +81,15 @@ __global__ __launch_bounds__(256) void k_cast_rays(RaycastWork W) {
     W.range[g] = range;
     if (W.ids) W.ids[g] = hit;
   }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const unsigned long long bal = __ballot(live && status == k);
-    if ((threadIdx.x & 63) == 0 && bal) atomicAdd(&W.ctl[k], (unsigned long long)__popcll(bal));
-  }
-  steps = wave_sum(steps); tested = wave_sum(tested);
-  if ((threadIdx.x & 63) == 0) {
-    if (steps) atomicAdd(&W.ctl[4], steps);
-    if (tested) atomicAdd(&W.ctl[5], tested);
-  }
+  wave_count_states(live, status, W.ctl);
+  wave_add(&W.ctl[4], steps);
+  wave_add(&W.ctl[5], tested);
 }
 
 }  // namespace
 
 void launch_raycast(const RaycastWork& W, hipStream_t s) {
-  hipLaunchKernelGGL(k_cast_rays, dim3(blocks_of((size_t)std::max<long long>(W.n, 1))), dim3(256), 0, s, W);
+  hipLaunchKernelGGL(k_cast_rays, dim3(blocks_of((size_t)std::max<long long>(W.scan.n, 1))), dim3(256), 0, s, W);
 }
 
 }  // namespace tl

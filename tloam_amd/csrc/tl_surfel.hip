@@ -39,12 +39,12 @@ constexpr double kSurfelWClamp = 1073741824.0;   // 2^30
 __device__ __forceinline__ VmapCell surfel_point(const SurfelWork& W, long long g, const int s_span[2], int* kf, const double** P,
                                                  double E[3], unsigned long long* key, unsigned q[3]) {
   span_point(W.in, g, s_span[0], s_span[1], kf, P, E);
-  return vmap_quantise(E, W.origin, W.voxel, key, q);
+  return vmap_quantise(E, W.grid.origin, W.grid.voxel, key, q);
 }
 
 __global__ __launch_bounds__(256) void k_surfel_clear(SurfelWork W) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
-  for (size_t t = i; t < (size_t)W.nv * kSurfelSums; t += stride) W.sums[t] = 0ull;
+  for (size_t t = i; t < (size_t)W.grid.nv * kSurfelSums; t += stride) W.sums[t] = 0ull;
   for (size_t t = i; t < (size_t)W.in.nkf; t += stride) W.kf_over[t] = 0;
   if (i < 8) W.ctl[i] = 0ull;
 }
@@ -97,13 +97,13 @@ __global__ __launch_bounds__(256) void k_surfel_accum(SurfelWork W) {
     unsigned long long key;
     unsigned q[3];
     if (surfel_point(W, g, s_span, &kf, &P, E, &key, q) == kVmapInside && W.kf_over[kf] == 0) {
-      id = id_table_find(W.map.ptab, W.map.pmask, W.map.pkey, key);
+      id = id_table_find(W.grid.map.ptab, W.grid.map.pmask, W.grid.map.pkey, key);
       ok = id >= 0;
       orphan = !ok;
 #pragma unroll
       for (int a = 0; a < 3; ++a) {
         r[a] = q[a] >> 8;
-        const double t = ((P[12 + a] - E[a]) / W.voxel) * 256.0;
+        const double t = ((P[12 + a] - E[a]) / W.grid.voxel) * 256.0;
         w[a] = (long long)floor(fmin(fmax(t, -kSurfelWClamp), kSurfelWClamp) + 0.5);
       }
     }
@@ -146,7 +146,7 @@ __global__ __launch_bounds__(256) void k_surfel_accum(SurfelWork W) {
   }
 }
 
-// voxel id (< W.nv) solved from its thirteen sums: its normal and variances written (zeros below min_points); true when solved
+// voxel id (< W.grid.nv) solved from its thirteen sums: its normal and variances written (zeros below min_points); true when solved
 __device__ __forceinline__ bool surfel_solve_voxel(const SurfelWork& W, long long id) {
   bool solved = false;
   {
@@ -169,7 +169,7 @@ __device__ __forceinline__ bool surfel_solve_voxel(const SurfelWork& W, long lon
       n[0] = M.v[0][0]; n[1] = M.v[1][0]; n[2] = M.v[2][0];
       const double d = (n[0] * (double)s[10] + n[1] * (double)s[11]) + n[2] * (double)s[12];
       if (d < 0.0) { n[0] = -n[0]; n[1] = -n[1]; n[2] = -n[2]; }
-      const double sc = W.voxel * (1.0 / 65536.0);
+      const double sc = W.grid.voxel * (1.0 / 65536.0);
       const double s2 = sc * sc;
       ev[0] = lam[0] * s2; ev[1] = lam[1] * s2; ev[2] = lam[2] * s2;
     }
@@ -184,7 +184,7 @@ __device__ __forceinline__ bool surfel_solve_voxel(const SurfelWork& W, long lon
 
 __global__ __launch_bounds__(256) void k_surfel_solve(SurfelWork W) {
   const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
-  const bool solved = id < W.nv && surfel_solve_voxel(W, id);
+  const bool solved = id < W.grid.nv && surfel_solve_voxel(W, id);
   const unsigned long long bal = __ballot(solved);
   if ((threadIdx.x & 63) == 0 && bal) atomicAdd(&W.ctl[2], (unsigned long long)__popcll(bal));
 }
@@ -196,7 +196,7 @@ __global__ __launch_bounds__(256) void k_surfel_solve_staged(SurfelWork W, Stage
   bool newly = false;
   if (s <= V.fmask && V.fkey[s] != kFree) {
     const long long id = V.fid[s];
-    if (id >= 0 && id < W.nv) {
+    if (id >= 0 && id < W.grid.nv) {
       const long long before = ((const long long*)W.sums)[(size_t)id * kSurfelSums] - (long long)V.fsum[s];
       newly = surfel_solve_voxel(W, id) && before < (long long)W.min_points;
     }
@@ -229,7 +229,7 @@ __global__ __launch_bounds__(256) void k_surfel_box(SurfelReadArgs A, int nblock
 }  // namespace
 
 int launch_surfels(const SurfelWork& W, hipStream_t s) {
-  const size_t nv = (size_t)std::max<long long>(W.nv, 1);   // (nothing still launches)
+  const size_t nv = (size_t)std::max<long long>(W.grid.nv, 1);   // (nothing still launches)
   const unsigned pt_blocks = blocks_of((size_t)std::max<long long>(W.in.n, 1));
   hipLaunchKernelGGL(k_surfel_clear, dim3(std::min(blocks_of(nv * kSurfelSums), 2048u)), dim3(256), 0, s, W);
   hipLaunchKernelGGL(k_surfel_flag, dim3(pt_blocks), dim3(256), 0, s, W);
@@ -251,7 +251,7 @@ int launch_surfel_solve_staged(const SurfelWork& W, const StagedVoxels& V, hipSt
 }
 
 void launch_surfel_solve(const SurfelWork& W, hipStream_t s) {
-  hipLaunchKernelGGL(k_surfel_solve, dim3(blocks_of((size_t)std::max<long long>(W.nv, 1))), dim3(256), 0, s, W);
+  hipLaunchKernelGGL(k_surfel_solve, dim3(blocks_of((size_t)std::max<long long>(W.grid.nv, 1))), dim3(256), 0, s, W);
 }
 
 void launch_surfel_read(const SurfelReadArgs& A, hipStream_t s) {

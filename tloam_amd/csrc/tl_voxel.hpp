@@ -1,11 +1,15 @@
 // tl_voxel.hpp -- what the device voxel grids share: the submap's down-sample (tl_submap.hip), the
 // global map (tl_map.hip), the merged voxel map (tl_vmap.hip), the closed map (tl_cmap.hip), its carve (tl_carve.hip), its
-// surfels (tl_surfel.hip), the localiser (tl_localise.hip) and the diff (tl_diff.hip).  One definition each of the key hash,
-// the two table inserts and the slot table's lookup, of the wave's integer sum, of the block scans, of the single-pass
+// surfels (tl_surfel.hip), the localiser (tl_localise.hip), the diff (tl_diff.hip), the ray-cast (tl_raycast.hip) and the free
+// space (tl_free.hip).  One definition each of the key hash,
+// the two table inserts and the slot table's lookup, of the wave's integer sum, its add to a control word (wave_add) and the
+// four-state ballot count (wave_count_states), of a cell's key and voxel (cell_key, cell_voxel) and the 27-cell probe round a
+// point's cell (probe27: k_loc_sweep, k_diff_points), of the block scans, of the single-pass
 // look-back with its one bound, of the eight-word post to the host, of the voxel map's key / q arithmetic, its row centroid
 // and its run sums, of the compacting box read's body (k_vmap_box, k_carve_box, k_surfel_box, k_diff_box), of the surfel gate,
 // of an incremental add's numbering and row update (k_vmap_emit / k_vmap_commit, k_ext_emit / k_ext_commit),
-// of the span table's search and its point, and of a ray's walk through the grid (k_carve_rays, k_diff_rays); and of
+// of the span table's search and its point, and of a ray's set-up, step and walks through a map's grid (MapGrid: k_carve_rays,
+// k_diff_rays, k_cast_rays, k_free_rays); the carve gate the queries share is tl_common.hpp's CarveGate; and of
 // PointCloud2::VoxelDownSample's arithmetic for the two units that restate it (the min bound's hand-over and finish, the voxel
 // key of a point, the leader's local sum, the blocks of an emit kernel the device holds at once).
 // Device code, and the launches' blocks_of and emit_resident_blocks.
@@ -70,6 +74,20 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
+}
+// ... and that sum added to a control word: one atomic per wave, none when the sum is zero.  Called by the whole wave.
+__device__ __forceinline__ void wave_add(unsigned long long* ctl_word, unsigned long long v) {
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0 && v) atomicAdd(ctl_word, v);
+}
+// The wave's live lanes counted by `state` (0 .. 3) into ctl[0 .. 3] by ballot: one atomic per state and wave.  Called by the
+// whole wave.
+__device__ __forceinline__ void wave_count_states(bool live, int state, unsigned long long* ctl) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const unsigned long long bal = __ballot(live && state == k);
+    if ((threadIdx.x & 63) == 0 && bal) atomicAdd(&ctl[k], (unsigned long long)__popcll(bal));
+  }
 }
 
 // 256-thread blocks over n items; a launch that runs for nothing too asks for blocks_of(max(n, 1))
@@ -311,6 +329,31 @@ __device__ __forceinline__ long long key_axis(unsigned long long key, int a) {
   return (long long)((key >> (21 * a)) & 0x1fffffull) - (1ll << kVmapBits);
 }
 
+// the key of cell (cx, cy, cz), |c| < 2^kVmapBits on every axis (the pack vmap_quantise forms)
+__device__ __forceinline__ unsigned long long cell_key(int cx, int cy, int cz) {
+  const int lim = 1 << kVmapBits;
+  return (unsigned long long)(cx + lim) | ((unsigned long long)(cy + lim) << 21) | ((unsigned long long)(cz + lim) << 42);
+}
+// the id of the voxel of cell (cx, cy, cz) in a map's slot table (read only); -1: the cell is beyond the grid or has no voxel
+__device__ __forceinline__ int cell_voxel(const VmapTableView& map, int cx, int cy, int cz) {
+  const int lim = 1 << kVmapBits;
+  if (cx <= -lim || cx >= lim || cy <= -lim || cy >= lim || cz <= -lim || cz >= lim) return -1;
+  return id_table_find(map.ptab, map.pmask, map.pkey, cell_key(cx, cy, cz));
+}
+// The 27 cells around the cell of `key`, dz outermost, then dy, dx innermost, each -1 .. 1 (the order decides ties between equal
+// distances: k_loc_sweep, k_diff_points): visit(id, own) for every one of them that has a voxel, own: the cell of `key` itself.
+// (A built map's slot table is always there, all slots free when the map has no voxel: the probes need no guard.)
+template <class Visit>
+__device__ __forceinline__ void probe27(const VmapTableView& map, unsigned long long key, Visit visit) {
+  const int i0 = (int)key_axis(key, 0), i1 = (int)key_axis(key, 1), i2 = (int)key_axis(key, 2);
+  for (int dz = -1; dz <= 1; ++dz)
+    for (int dy = -1; dy <= 1; ++dy)
+      for (int dx = -1; dx <= 1; ++dx) {
+        const int id = cell_voxel(map, i0 + dx, i1 + dy, i2 + dz);
+        if (id >= 0) visit(id, dx == 0 && dy == 0 && dz == 0);
+      }
+}
+
 // c = o + v * ((double) i + ((double) Q / (double) N) * 2^-24), in that order
 __device__ __forceinline__ double centroid(double o, double v, long long i, long long Q, long long N) {
   return o + v * ((double)i + ((double)Q / (double)N) * (1.0 / kVmapQScale));
@@ -487,15 +530,11 @@ __device__ __forceinline__ void span_point(const SpanInput& in, long long g, int
 
 // ---- a ray through a voxel map's grid (the carve, tl_carve.hip; the diff, tl_diff.hip; section 28: the
 // ray-cast, tl_raycast.hip) ----
-// The ray from O to E: the skip rule, the set-up of the walk through the grid's cells and its step exist once (RayCells: ray_begin,
-// ray_key, ray_step); tl_carve.hip's header states their operation order.  The state is held in named scalars (no run-time indexed
+// The ray from O to E through a map's grid (MapGrid): the skip rule, the set-up of the walk through the grid's cells and its step
+// exist once (RayCells: ray_begin, ray_key, ray_step); tl_carve.hip's header states their operation order.  The state is held in named scalars (no run-time indexed
 // array: no scratch).  Two walks run on it: ray_walk visits the start cell and the first n - 1 cells stepped into and puts the
 // miss test to every voxel among them (the carve, the diff); ray_first_hit visits the end cell too and stops at the first voxel
 // its test accepts (the ray-cast).
-struct RayGrid {
-  double voxel, origin[3];
-  double max_range, end_margin, radius2;   // radius2 = radius * radius
-};
 struct RayCells {
   double Dx, Dy, Dz, DD, L;    // D = E - O, DD = |D|^2 summed (x + y) + z, L = sqrt(DD)
   int cx, cy, cz;              // the current cell
@@ -506,8 +545,8 @@ struct RayCells {
   int n;                       // the steps from the start cell to the end cell
 };
 // false: the ray is skipped (E not finite, L > max_range, L == 0, the cell of O or of E beyond the grid)
-__device__ __forceinline__ bool ray_begin(const RayGrid& W, double Ox, double Oy, double Oz, double Ex, double Ey, double Ez,
-                                          RayCells* R) {
+__device__ __forceinline__ bool ray_begin(const MapGrid& W, double max_range, double Ox, double Oy, double Oz, double Ex, double Ey,
+                                          double Ez, RayCells* R) {
   const double kInf = __builtin_huge_val(), kLimit = (double)(1ll << kVmapBits);
   const double Dx = Ex - Ox, Dy = Ey - Oy, Dz = Ez - Oz;
   const double DD = (Dx * Dx + Dy * Dy) + Dz * Dz;
@@ -516,7 +555,7 @@ __device__ __forceinline__ bool ray_begin(const RayGrid& W, double Ox, double Oy
   const double s1x = (Ex - W.origin[0]) / W.voxel, s1y = (Ey - W.origin[1]) / W.voxel, s1z = (Ez - W.origin[2]) / W.voxel;
   const double fx = floor(s0x), fy = floor(s0y), fz = floor(s0z), gx = floor(s1x), gy = floor(s1y), gz = floor(s1z);
   bool ok = __builtin_isfinite(Ex) && __builtin_isfinite(Ey) && __builtin_isfinite(Ez);
-  ok = ok && !(L > W.max_range) && !(L == 0.0);
+  ok = ok && !(L > max_range) && !(L == 0.0);
   ok = ok && fabs(fx) < kLimit && fabs(fy) < kLimit && fabs(fz) < kLimit && fabs(gx) < kLimit && fabs(gy) < kLimit &&
        fabs(gz) < kLimit;
   if (!ok) return false;
@@ -535,10 +574,7 @@ __device__ __forceinline__ bool ray_begin(const RayGrid& W, double Ox, double Oy
   return true;
 }
 // the current cell's key
-__device__ __forceinline__ unsigned long long ray_key(const RayCells& R) {
-  return (unsigned long long)(R.cx + (1 << kVmapBits)) | ((unsigned long long)(R.cy + (1 << kVmapBits)) << 21) |
-         ((unsigned long long)(R.cz + (1 << kVmapBits)) << 42);
-}
+__device__ __forceinline__ unsigned long long ray_key(const RayCells& R) { return cell_key(R.cx, R.cy, R.cz); }
 // into the next cell: the axis of the smallest tMax, a tie going to the lowest axis
 __device__ __forceinline__ void ray_step(RayCells* R) {
   const double kInf = __builtin_huge_val();
@@ -556,18 +592,20 @@ __device__ __forceinline__ void ray_step(RayCells* R) {
   }
 }
 
-// Every visited cell looked up in the map's slot table, the miss test against an occupied cell's centroid.  on_miss(id) is what
-// a miss does; *skipped, *steps, *tested, *misses are set for the ray (a skipped ray: 1, 0, 0, 0).
+// Every visited cell looked up in the map's slot table, the miss test against an occupied cell's centroid (radius2 = radius *
+// radius).  on_miss(id) is what a miss does; *skipped, *steps, *tested, *misses are set for the ray (a skipped ray: 1, 0, 0, 0).
 template <class OnMiss>
-__device__ __forceinline__ void ray_walk(const RayGrid& W, const VmapTableView& map, double Ox, double Oy, double Oz, double Ex,
-                                         double Ey, double Ez, unsigned long long* skipped, unsigned long long* steps,
-                                         unsigned long long* tested, unsigned long long* misses, OnMiss on_miss) {
+__device__ __forceinline__ void ray_walk(const MapGrid& W, double max_range, double end_margin, double radius2, double Ox, double Oy,
+                                         double Oz, double Ex, double Ey, double Ez, unsigned long long* skipped,
+                                         unsigned long long* steps, unsigned long long* tested, unsigned long long* misses,
+                                         OnMiss on_miss) {
+  const VmapTableView& map = W.map;
   RayCells R;
-  if (!ray_begin(W, Ox, Oy, Oz, Ex, Ey, Ez, &R)) {
+  if (!ray_begin(W, max_range, Ox, Oy, Oz, Ex, Ey, Ez, &R)) {
     *skipped = 1ull;
     return;
   }
-  const double tlim = 1.0 - W.end_margin / R.L;
+  const double tlim = 1.0 - end_margin / R.L;
   *steps = (unsigned long long)R.n;
   for (int k = 0; k < R.n; ++k) {
     const int id = id_table_find(map.ptab, map.pmask, map.pkey, ray_key(R));
@@ -579,7 +617,7 @@ __device__ __forceinline__ void ray_walk(const RayGrid& W, const VmapTableView& 
       const double uz = centroid(W.origin[2], W.voxel, R.cz, map.pqz[id], N) - Oz;
       const double tt = ((ux * R.Dx + uy * R.Dy) + uz * R.Dz) / R.DD;
       const double wx = ux - tt * R.Dx, wy = uy - tt * R.Dy, wz = uz - tt * R.Dz;
-      if (0.0 <= tt && tt < tlim && (wx * wx + wy * wy) + wz * wz <= W.radius2) {
+      if (0.0 <= tt && tt < tlim && (wx * wx + wy * wy) + wz * wz <= radius2) {
         (*misses)++;
         on_miss(id);
       }
@@ -590,8 +628,7 @@ __device__ __forceinline__ void ray_walk(const RayGrid& W, const VmapTableView& 
 
 // The walk that stops: the start cell, then every cell stepped into, the end cell included (n + 1 cells), each looked up in the
 // map's slot table; test(id) is put to every voxel among them and the first one it accepts ends the walk.  Returns that voxel's
-// id, or -1 when no visited voxel is accepted; *visited: the cells looked up, the accepted one included.  (W.end_margin and
-// W.radius2 are not read: the test is the caller's.)
+// id, or -1 when no visited voxel is accepted; *visited: the cells looked up, the accepted one included.
 template <class Test>
 __device__ __forceinline__ int ray_first_hit(const VmapTableView& map, RayCells* R, unsigned long long* visited, Test test) {
   unsigned long long seen = 0ull;

@@ -764,6 +764,26 @@ def _lp(a):
     return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int64))
 
 
+def _u8p(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_uint8))
+
+
+def _per_point(n, want_ids):
+    """the per-point outputs of a scan query, never empty -> (bytes (max(n, 1),) uint8, ids (max(n, 1),) int32 or None, cut);
+    cut(a): the first n of `a` as the caller's own copy (None stays None)"""
+    return (np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.int32) if want_ids else None,
+            lambda a: None if a is None else a[:n].copy())
+
+
+def _box(lo, hi):
+    """the two corners of a box read, both or neither -> ((3,) float64, (3,) float64) or (None, None)"""
+    if (lo is None) != (hi is None):
+        raise ValueError("lo and hi go together")
+    if lo is None:
+        return None, None
+    return np.ascontiguousarray(lo, dtype=np.float64).reshape(3), np.ascontiguousarray(hi, dtype=np.float64).reshape(3)
+
+
 def _aos(x):
     return np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1, 3))
 
@@ -1512,11 +1532,7 @@ class HipRegistration:
     def closed_map_read_carved(self, lo=None, hi=None, min_count=1, min_miss=3, miss_ratio=1.0):
         """closed_map_read_box's voxels (lo and hi None: the whole map) without those seen through -- M >= min_miss and
         M > miss_ratio * N -- in id order -> (centroids (m, 3), counts (m,), misses (m,))"""
-        if (lo is None) != (hi is None):
-            raise ValueError("lo and hi go together")
-        if lo is not None:
-            lo = np.ascontiguousarray(lo, dtype=np.float64).reshape(3)
-            hi = np.ascontiguousarray(hi, dtype=np.float64).reshape(3)
+        lo, hi = _box(lo, hi)
         head = (self.h, _dp(lo), _dp(hi), int(min_count), int(min_miss), float(miss_ratio))
         return self._read_box(self.L.tloam_closed_map_read_carved, "tloam_closed_map_read_carved", head,
                               [(3, np.float64), (None, np.int64), (None, np.int64)])
@@ -1560,11 +1576,7 @@ class HipRegistration:
         """closed_map_read_box's voxels (lo and hi None: the whole map) whose surfel is solved with ev2 > 0,
         ev0 <= max_sigma^2 and ev1 - ev0 >= min_planarity * ev2, in id order ->
         (centroids (m, 3), normals (m, 3), variances (m, 3), Ns (m,))"""
-        if (lo is None) != (hi is None):
-            raise ValueError("lo and hi go together")
-        if lo is not None:
-            lo = np.ascontiguousarray(lo, dtype=np.float64).reshape(3)
-            hi = np.ascontiguousarray(hi, dtype=np.float64).reshape(3)
+        lo, hi = _box(lo, hi)
         head = (self.h, _dp(lo), _dp(hi), int(min_count), float(max_sigma), float(min_planarity))
         return self._read_box(self.L.tloam_closed_map_read_surfels_box, "tloam_closed_map_read_surfels_box", head,
                               [(3, np.float64), (3, np.float64), (3, np.float64), (None, np.int64)])
@@ -1660,13 +1672,12 @@ class HipRegistration:
         DIFF_SURFACE, DIFF_OCCUPIED, DIFF_NEW; ids (n,) int32 of the voxel that explained each point, -1 for none, or None
         without want_ids; info dict).  accumulate: the per-voxel counts are added to the stored ones instead of replacing them"""
         pts = _aos(points)
-        labels = np.zeros(max(len(pts), 1), np.uint8)
-        ids = np.zeros(max(len(pts), 1), np.int32) if want_ids else None
+        labels, ids, cut = _per_point(len(pts), want_ids)
         info = ClosedMapDiffInfo()
         self._check(self.L.tloam_closed_map_diff(self.h, _dp(pts), len(pts), _dp(_colmajor(pose)),
-                                                 DIFF_ACCUMULATE if accumulate else 0, labels.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                                 _ip(ids), C.byref(info)), "tloam_closed_map_diff")
-        return labels[: len(pts)].copy(), (ids[: len(pts)].copy() if want_ids else None), info.as_dict()
+                                                 DIFF_ACCUMULATE if accumulate else 0, _u8p(labels), _ip(ids), C.byref(info)),
+                    "tloam_closed_map_diff")
+        return cut(labels), cut(ids), info.as_dict()
 
     def closed_map_diff_info(self) -> dict:
         info = ClosedMapDiffInfo()
@@ -1684,11 +1695,7 @@ class HipRegistration:
         """the voxels (lo and hi None: of the whole map; else with their centroid in [lo, hi]) the diffed scans saw through --
         through >= min_through and through > gone_ratio * hits -- in id order ->
         (centroids (m, 3), counts (m,), through (m,), hits (m,))"""
-        if (lo is None) != (hi is None):
-            raise ValueError("lo and hi go together")
-        if lo is not None:
-            lo = np.ascontiguousarray(lo, dtype=np.float64).reshape(3)
-            hi = np.ascontiguousarray(hi, dtype=np.float64).reshape(3)
+        lo, hi = _box(lo, hi)
         head = (self.h, _dp(lo), _dp(hi), int(min_through), float(gone_ratio))
         return self._read_box(self.L.tloam_closed_map_read_gone, "tloam_closed_map_read_gone", head,
                               [(3, np.float64), (None, np.int64), (None, np.int64), (None, np.int64)])
@@ -1706,14 +1713,12 @@ class HipRegistration:
         along the segment to the first hit, -1.0 without one; ids (n,) int32 of the voxel hit, -1 for none, or None without
         want_ids; info dict)"""
         e = _aos(ends)
-        status = np.zeros(max(len(e), 1), np.uint8)
+        status, ids, cut = _per_point(len(e), want_ids)
         ranges = np.zeros(max(len(e), 1), np.float64)
-        ids = np.zeros(max(len(e), 1), np.int32) if want_ids else None
         info = ClosedMapRaycastInfo()
-        self._check(self.L.tloam_closed_map_raycast(self.h, _dp(e), len(e), _dp(_colmajor(pose)),
-                                                    status.ctypes.data_as(C.POINTER(C.c_uint8)), _dp(ranges), _ip(ids),
-                                                    C.byref(info)), "tloam_closed_map_raycast")
-        return status[: len(e)].copy(), ranges[: len(e)].copy(), (ids[: len(e)].copy() if want_ids else None), info.as_dict()
+        self._check(self.L.tloam_closed_map_raycast(self.h, _dp(e), len(e), _dp(_colmajor(pose)), _u8p(status), _dp(ranges),
+                                                    _ip(ids), C.byref(info)), "tloam_closed_map_raycast")
+        return cut(status), cut(ranges), cut(ids), info.as_dict()
 
     def closed_map_raycast_info(self) -> dict:
         info = ClosedMapRaycastInfo()
@@ -1780,22 +1785,16 @@ class HipRegistration:
         OCCUPANCY_INVALID, OCCUPANCY_UNKNOWN, OCCUPANCY_FREE, OCCUPANCY_OCCUPIED; ids (n,) int32 of the voxel of an OCCUPIED
         point, -1 otherwise, or None without want_ids; counts (4,) int64 of points per state)"""
         pts = _aos(points)
-        state = np.zeros(max(len(pts), 1), np.uint8)
-        ids = np.zeros(max(len(pts), 1), np.int32) if want_ids else None
+        state, ids, cut = _per_point(len(pts), want_ids)
         counts = np.zeros(4, np.int64)
         self._check(self.L.tloam_closed_map_occupancy(self.h, _dp(pts), len(pts), None if pose is None else _dp(_colmajor(pose)),
-                                                      state.ctypes.data_as(C.POINTER(C.c_uint8)), _ip(ids), _lp(counts)),
-                    "tloam_closed_map_occupancy")
-        return state[: len(pts)].copy(), (ids[: len(pts)].copy() if want_ids else None), counts
+                                                      _u8p(state), _ip(ids), _lp(counts)), "tloam_closed_map_occupancy")
+        return cut(state), cut(ids), counts
 
     def closed_map_free_cells(self, lo=None, hi=None):
         """the centres (m, 3) of the FREE cells (lo and hi None: of the whole grid; else with their centre in [lo, hi]), brick
         index ascending, then bit ascending"""
-        if (lo is None) != (hi is None):
-            raise ValueError("lo and hi go together")
-        if lo is not None:
-            lo = np.ascontiguousarray(lo, dtype=np.float64).reshape(3)
-            hi = np.ascontiguousarray(hi, dtype=np.float64).reshape(3)
+        lo, hi = _box(lo, hi)
         return self._read_box(self.L.tloam_closed_map_read_free, "tloam_closed_map_read_free", (self.h, _dp(lo), _dp(hi)),
                               [(3, np.float64)])[0]
 
@@ -1806,7 +1805,7 @@ class HipRegistration:
         nx, ny = C.c_size_t(0), C.c_size_t(0)
         out = np.zeros(max(16 * info["n_bricks"][0] * info["n_bricks"][1], 1), np.uint8)
         self._check(self.L.tloam_closed_map_free_columns(self.h, float(z_lo), float(z_hi), int(min_free),
-                                                         out.ctypes.data_as(C.POINTER(C.c_uint8)), len(out), C.byref(nx), C.byref(ny)),
+                                                         _u8p(out), len(out), C.byref(nx), C.byref(ny)),
                     "tloam_closed_map_free_columns")
         return out[: nx.value * ny.value].reshape(ny.value, nx.value).copy()
 
