@@ -399,7 +399,7 @@ def test_non_finite_points_are_never_matched(hip_module, n_src, n_tgt, over):
     H.close(); Hc.close()
 
 
-@pytest.mark.parametrize("shape", ["small", "kitti", "caps", "noise_free", "m1"])
+@pytest.mark.parametrize("shape", ["small", "kitti", "caps", "noise_free", "m1", *synth.BOUNDARY_SRC])
 def test_device_driven_loop_equals_host_driven_loop(hip_module, monkeypatch, shape):
     """tloam_scan_match enqueues every outer GNC iteration at once -- builders / refresh gated on device flags, the
     plateau break and the loop end decided by the finish kernel -- and waits once.  The stepwise machinery
@@ -416,6 +416,11 @@ def test_device_driven_loop_equals_host_driven_loop(hip_module, monkeypatch, sha
         over = dict(planar_maxnum=90, ground_maxnum=130, edge_maxnum=70, sphere_maxnum=25)
     elif shape == "noise_free":
         sc = synth.make_scene(seed=17, noise=0.0)
+    elif shape in synth.BOUNDARY_SRC:   # each side of the sizes at which the driver launches something else
+        n_src = synth.BOUNDARY_SRC[shape]
+        sc = synth.make_scene(seed=18, n_src=n_src, n_tgt=tuple(max(n, 1500) for n in n_src))
+        if shape.startswith(("lifted", "n131")):
+            over = dict(planar_maxnum=1 << 30, ground_maxnum=1 << 30, edge_maxnum=1 << 30, sphere_maxnum=1 << 30)
     else:
         big = 1 << 30
         sc = synth.make_scene(seed=1, n_src=(50000, 26000, 20000, 4000), n_tgt=(50000, 26000, 20000, 4000))

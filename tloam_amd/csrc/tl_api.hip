@@ -165,7 +165,7 @@ int tloam_get_info(tloam_ctx* c, tloam_ctx_info* out) {
   out->rank = c->rank;
   out->nranks = c->nranks;
   out->loopback = c->loopback ? 1 : 0;
-  out->direct_set = (c->direct && !c->prebuilt) ? 1 : 0;
+  out->direct_set = (c->forms.set == SetForm::DIRECT && !c->prebuilt) ? 1 : 0;
   out->set_stale = c->set_stale ? 1 : 0;
   tlh::comm_rccl_info(c, &out->rccl_comm_count, &out->rccl_comm_rank);
   out->fallbacks_taken = (c->no_scan_1p ? TLOAM_FALLBACK_SCAN : 0) | (c->vox_ticket ? TLOAM_FALLBACK_VOXEL : 0) |
@@ -174,7 +174,7 @@ int tloam_get_info(tloam_ctx* c, tloam_ctx_info* out) {
   out->k3_grid = c->k3_grid;
   out->k3_single = c->k3_single ? 1 : 0;
   out->k3_wide = c->k3_wide ? 1 : 0;
-  out->one_launch_solve = (one_rank(c) && c->k3_single && !c->no_persistent_solve && solve_small_fits(c->k3_grid, c->device_cus)) ? 1 : 0;
+  out->one_launch_solve = c->forms.solve == SolveForm::PERSISTENT ? 1 : 0;
   return TLOAM_OK;
 }
 

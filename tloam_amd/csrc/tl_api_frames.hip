@@ -1,7 +1,6 @@
 // tl_api_frames.hip -- HBM residency of the C ABI (include/tloam_hip.h): setInputSource / setInputTarget
 // (registration.cpp:232-248) through pinned staging, the search grids over the registered targets (the role of
 // KDTreeFlann::SetGeometry, :889-915), frames staged ahead of their solve, and the host's waits on pinned result words.
-#include <chrono>
 #include "tl_ctx.hpp"
 
 using namespace tl;
@@ -205,7 +204,7 @@ int build_grids_over(tloam_ctx* c, GridBuffers& G, const double radius[kKinds], 
   //  frame's sums are added in the order they always were.  Compacted sets are in slot order whatever the grids look like.)
   long long caps = 0;
   for (int k = 0; k < kKinds; ++k) caps += std::max(0, kind_maxnum(c->cfg, k));
-  const bool sparse_ok = !direct_set_size((int)std::min<long long>(caps, INT32_MAX));
+  const bool sparse_ok = caps <= kQuadLimit;
   long long cell_total = 0;
   for (int k = 0; k < kKinds; ++k) {
     const double* lo = boxes[k];
@@ -273,22 +272,15 @@ int build_grids_over(tloam_ctx* c, GridBuffers& G, const double radius[kKinds], 
     const size_t nt = (size_t)n_tab;
     const size_t nt_res = (nt > G.cell_cnt32.cap || nt > G.cell_start.cap) ? 2 * nt + 64 : nt;
     HIPC(c, G.cell_start.reserve(nt_res));
-    const size_t before = G.cell_cnt32.cap;
-    HIPC(c, G.cell_cnt32.reserve(nt_res));
-    if (G.cell_cnt32.cap != before) HIPC(c, hipMemsetAsync(G.cell_cnt32.p, 0, G.cell_cnt32.cap * sizeof(unsigned), c->stream));
+    HIPC(c, G.cell_cnt32.reserve_zeroed(nt_res, c->stream));
     HIPC(c, G.cell_scan32.reserve(nt_res));
     HIPC(c, G.totals32.reserve(1024));
   } else {
     const size_t nc_res = (nc + 1 > G.cell_cnt.cap || nc + kKinds + 1 > G.cell_start.cap) ? 2 * nc + 64 : nc;
     HIPC(c, G.cell_start.reserve(nc_res + kKinds + 1));
-    const size_t before = G.cell_cnt.cap;
-    HIPC(c, G.cell_cnt.reserve(nc_res + 1));
-    if (G.cell_cnt.cap != before)
-      HIPC(c, hipMemsetAsync(G.cell_cnt.p, 0, G.cell_cnt.cap * sizeof(unsigned long long), c->stream));
+    HIPC(c, G.cell_cnt.reserve_zeroed(nc_res + 1, c->stream));
     if (single_pass) {
-      const size_t before1p = G.scan1p.cap;
-      HIPC(c, G.scan1p.reserve(scan_1p_ctl_elems(nc_res + 1)));
-      if (G.scan1p.cap != before1p) HIPC(c, hipMemsetAsync(G.scan1p.p, 0, G.scan1p.cap * sizeof(unsigned long long), c->stream));
+      HIPC(c, G.scan1p.reserve_zeroed(scan_1p_ctl_elems(nc_res + 1), c->stream));   // (control words: zero between launches)
     } else {
       HIPC(c, G.cell_scan.reserve(nc_res + 1));
       HIPC(c, G.scan_tmp.reserve(scan_tmp_elems(nc_res + 1)));
@@ -317,17 +309,18 @@ int build_grids_over(tloam_ctx* c, GridBuffers& G, const double radius[kKinds], 
   if (cell_total == 0) { c->grid_info = I; return TLOAM_OK; }
   if (frame) {  // the start of the scan_match rides on the first launch (the query-tile histogram is sized by the grids)
     const size_t ntiles = (size_t)build_tile_count(out, frame->fi.slot_off);
-    HIPC(c, c->tile_cnt.reserve(ntiles + 1 > c->tile_cnt.cap ? 2 * ntiles + 64 : ntiles + 1));
+    const int rc = reserve_tile_hist(c, ntiles, /*frame_start=*/true);
+    if (rc != TLOAM_OK) return rc;
     frame->fi.tile_cnt = c->tile_cnt.p;
     frame->fi.n_tile_cnt = (int)ntiles + 1;
     frame->consumed = true;
   }
   c->grid_info = I;
   const bool stamp = frame && c->hs_entry > 0.0;   // (TLOAM_HOST_STAMPS: when the frame's FIRST launch went out / had been issued)
-  if (stamp) c->hs[5] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count() - c->hs_entry;
+  if (stamp) c->hs[5] += host_now_us() - c->hs_entry;
   if (tiles > 0) launch_grid_count_all(gs, G.cell_cnt32.p, G.cell_of_pt.p, G.rank_of_pt.p, c->stream, frame);
   else launch_grid_count_all(gs, G.cell_cnt.p, G.cell_of_pt.p, G.rank_of_pt.p, c->stream, frame);
-  if (stamp) c->hs[6] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count() - c->hs_entry;
+  if (stamp) c->hs[6] += host_now_us() - c->hs_entry;
   if (single_pass) {
     // 1 M-class tables: count | scan + finalize in ONE single-pass launch | scatter (three launches and one pass over the table
     // less than tile scan + scan of the totals + add + finalize)

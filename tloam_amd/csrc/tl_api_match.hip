@@ -7,7 +7,6 @@
 // every per-point / per-correspondence computation is a HIP kernel (tl_nn.hip, tl_gn.hip).
 // Helpers first, in namespaces; the four entry points, the only extern "C" of the unit, last.
 #include <atomic>
-#include <chrono>
 
 #include "tl_ctx.hpp"
 
@@ -71,35 +70,37 @@ int ensure_common(tloam_ctx* c) {
   c->cv.seg_n = c->seg_n.p;
   return TLOAM_OK;
 }
+// The query-tile histogram and its scan, ntiles + 1 entries each.  The tile count follows the bounding boxes like the cell tables:
+// a table that has to grow does so with room to spare.  The one size rule of the frame's start (the grid build's first launch, or
+// k_frame_init), which zeroes the histogram, and of the query sort, which counts into it: whoever comes first sizes both tables,
+// so nothing is re-allocated -- and lost -- in between.
+// frame_start: the caller's launch zeroes the entries itself.  Anybody else finds the start already enqueued: a histogram that has
+// to be (re)allocated then is zeroed here.  (Until round 5 it was not, and the sizes asked for at the two places differed by the
+// one element that crosses an allocation step: the counting sort then ranked the queries on what the new block happened to hold
+// and scattered them out of bounds -- a GPU memory fault or a silently wrong query order on the first large frame of a context,
+// whenever the block was not fresh; found by tests/tools/fuzz_call_order.py.)
+int reserve_tile_hist(tloam_ctx* c, size_t ntiles, bool frame_start, size_t* room) {
+  const size_t n = (ntiles + 1 > c->tile_cnt.cap || ntiles + 1 > c->tile_scan.cap) ? 2 * ntiles + 64 : ntiles;
+  if (frame_start) HIPC(c, c->tile_cnt.reserve(n + 1));
+  else HIPC(c, c->tile_cnt.reserve_zeroed(n + 1, c->stream));
+  HIPC(c, c->tile_scan.reserve(n + 1));
+  if (room) *room = n;   // (the tiles asked for: what the sort's other tables follow)
+  return TLOAM_OK;
+}
 // (also called from the grid build when the sort's first pass rides on it: the SAME sizes, so that nothing is re-allocated -- and
 //  lost -- between that pass and the rest of the sort)
 int reserve_query_sort(tloam_ctx* c, const GridView grids[kKinds]) {
   const size_t n_slots = (size_t)c->sv.slot_off[kKinds];
   const size_t ntiles = (size_t)build_tile_count(grids, c->sv.slot_off);
-  // (tile counts follow the bounding boxes like the cell tables: grow with room to spare)
-  const size_t nt_res = (ntiles + 1 > c->tile_cnt.cap || ntiles + 1 > c->tile_scan.cap) ? 2 * ntiles + 64 : ntiles;
-  {
-    // The query-tile histogram is zeroed by the frame's start (k_frame_init / the extra blocks of the grid build's first launch),
-    // which has been enqueued by now: a histogram that has to be re-allocated HERE -- the scan's table was shorter than the
-    // histogram's, or the sizes asked for at the two places differ by the one element that crosses an allocation step -- is
-    // zeroed again.  (Until round 5 it was not: the counting sort then ranked the queries on what the new block happened to
-    // hold and scattered them out of bounds -- a GPU memory fault or a silently wrong query order on the first large frame of a
-    // context, whenever the block was not fresh; found by tests/tools/fuzz_call_order.py.)
-    const size_t before = c->tile_cnt.cap;
-    HIPC(c, c->tile_cnt.reserve(nt_res + 1));
-    if (c->tile_cnt.cap != before)
-      HIPC(c, hipMemsetAsync(c->tile_cnt.p, 0, c->tile_cnt.cap * sizeof(unsigned long long), c->stream));
-  }
-  HIPC(c, c->tile_scan.reserve(nt_res + 1));
+  size_t nt_res = 0;
+  const int rc = reserve_tile_hist(c, ntiles, /*frame_start=*/false, &nt_res);
+  if (rc != TLOAM_OK) return rc;
   HIPC(c, c->tile_fill.reserve(std::max<size_t>((size_t)nt_res, (size_t)n_slots + 1))  /* rank of every slot inside its tile */); HIPC(c, c->tile_of_slot.reserve(n_slots + 1));
   HIPC(c, c->qrec.reserve(n_slots + 1));
   HIPC(c, c->scan_tmp.reserve(scan_tmp_elems(std::max(nt_res + 1, n_slots + 1))));
   c->scan1p_q_use = !c->no_scan_1p && scan_1p_applies(ntiles + 1, c->device_cus);
-  if (c->scan1p_q_use) {
-    const size_t before = c->scan1p_q.cap;
-    HIPC(c, c->scan1p_q.reserve(scan_1p_ctl_elems(nt_res + 1)));
-    if (c->scan1p_q.cap != before) HIPC(c, hipMemsetAsync(c->scan1p_q.p, 0, c->scan1p_q.cap * sizeof(unsigned long long), c->stream));
-  }
+  // (the control words of the single-pass scan read zero between launches: only a (re)allocation has to be cleared)
+  if (c->scan1p_q_use) HIPC(c, c->scan1p_q.reserve_zeroed(scan_1p_ctl_elems(nt_res + 1), c->stream));
   return TLOAM_OK;
 }
 BuildParams build_params(const tloam_ctx* c) {
@@ -122,15 +123,38 @@ void plan_sweeps(tloam_ctx* c) {
   for (int k = 0; k < kKinds; ++k) caps[k] = (int)c->kd[k].c_cap;
   k3_plan(caps, c->device_cus, &c->k3_grid, &c->k3_single, &c->k3_wide);
 }
+// the only reader of the knobs that select forms
+FormsIn forms_in(const tloam_ctx* c) {
+  FormsIn in;
+  in.nranks = c->nranks;
+  in.loopback = c->loopback ? 1 : 0;
+  in.mailbox = c->comm == COMM_MAILBOX ? 1 : 0;
+  in.device_cus = c->device_cus;
+  in.no_persistent_solve = c->no_persistent_solve ? 1 : 0;
+  in.no_direct_set = c->no_direct_set ? 1 : 0;
+  in.no_device_loop = c->no_device_loop ? 1 : 0;
+  in.no_build_reuse = c->dbg_no_build_reuse ? 1 : 0;
+  in.fused_large = c->fused_large ? 1 : 0;
+  in.no_qbin_ride = c->no_qbin_ride ? 1 : 0;
+  in.factor_num = c->cfg.factor_num;
+  in.max_iterations = c->cfg.max_iterations;
+  for (int k = 0; k < kKinds; ++k) {
+    in.maxnum[k] = kind_maxnum(c->cfg, k);
+    in.n_src[k] = (long long)c->kd[k].n_src;
+    in.n_tgt[k] = (long long)c->kd[k].n_tgt;
+    in.seg_cap[k] = (long long)c->kd[k].c_cap;
+  }
+  in.k3_grid = c->k3_grid;
+  in.k3_single = c->k3_single ? 1 : 0;
+  return in;
+}
 double* direct_w_stream(const tloam_ctx* c, int k, int parity) {
   return c->kd[k].c_buf.p + (size_t)(parity ? SS_W2 : SS_W) * c->kd[k].c_stride;
 }
 // the per-block rows of the sweeps (and, below 4096 words, the tagged rows / finish segments of the one-launch Solve): cleared
 // when (re)allocated, so that nothing in them ever carries a valid check word that this context did not write
 int reserve_partials(tloam_ctx* c) {
-  const size_t before = c->partials.cap;
-  HIPC(c, c->partials.reserve(std::max<size_t>((size_t)c->k3_grid * kAccStride, 4096)));
-  if (c->partials.cap != before) HIPC(c, hipMemsetAsync(c->partials.p, 0, c->partials.cap * sizeof(double), c->stream));
+  HIPC(c, c->partials.reserve_zeroed(std::max<size_t>((size_t)c->k3_grid * kAccStride, 4096), c->stream));
   return TLOAM_OK;
 }
 double alg_bytes_of(const int n[kKinds]) {
@@ -142,23 +166,15 @@ double alg_bytes_of(const int n[kKinds]) {
 
 namespace {
 
-// ---- the direct factor set (tl_common.hpp DirectSet) ------------------------------------------------------------------------
-// Which frames take it: one rank, searched one thread per query, all four builders running, and no cap that could bind -- a
-// kind's cap >= its source points ("first N valid in index order", registration.cpp:448 / :538 / :592 / :735, then selects
-// everything valid, whatever the order).  Everything else compacts.
-bool direct_applies(const tloam_ctx* c, size_t n_slots) {
-  if (c->no_direct_set || !one_rank(c) || c->cfg.factor_num != 4 || !direct_set_size((int)std::min<size_t>(n_slots, (size_t)INT32_MAX))) return false;
-  for (int k = 0; k < kKinds; ++k)
-    if ((long long)c->kd[k].n_src > (long long)kind_maxnum(c->cfg, k) || c->kd[k].n_tgt == 0) return false;
-  return true;
-}
+// ---- the direct factor set (tl_common.hpp DirectSet; which frames take it: decide_forms) ------------------------------------
+bool direct(const tloam_ctx* c) { return c->forms.set == SetForm::DIRECT; }
 // the Solve of outer iteration `iter` reads weight stream iter & 1 (c->cv), its finish writes the other one
 void direct_set_parity(tloam_ctx* c, int iter) {
   for (int k = 0; k < kKinds; ++k) c->cv.k[k].w = direct_w_stream(c, k, iter & 1);
 }
 // rows of the hand-over buffer of the finish, compact (riding) or direct
 constexpr size_t kFinRowsDoubles = (size_t)(4 * 256 + 64) * 16;   // the blocks' rows + the rows of their groups of 64
-size_t seg_cap_sum(const tloam_ctx* c) {   // the four segments' capacity: what sizes the finish (finish_wblocks, finish_small_path)
+size_t seg_cap_sum(const tloam_ctx* c) {   // the four segments' capacity: what sizes the finish (finish_wblocks)
   size_t cap = 0;
   for (int k = 0; k < kKinds; ++k) cap += c->kd[k].c_cap;
   return cap;
@@ -254,12 +270,11 @@ HostMirror next_mirror(tloam_ctx* c, int slot = 0) {
   return hm;
 }
 int wait_state(tloam_ctx* c, const HostMirror& hm, int slot = 0) {
-  const auto t0 = std::chrono::steady_clock::now();
   struct Acc {
     tloam_ctx* c;
-    std::chrono::steady_clock::time_point t0;
-    ~Acc() { c->wait_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); }
-  } acc{c, t0};
+    double t0;
+    ~Acc() { c->wait_us += host_now_us() - t0; }
+  } acc{c, host_now_us()};
   if (hm.out) {
     // all three segments of the slot (MirrorSlot), each verified against the number, then the prefix out of them
     const MirrorSlot* ms = c->h_mirror + slot;
@@ -278,10 +293,6 @@ int wait_state(tloam_ctx* c, const HostMirror& hm, int slot = 0) {
   HIPC(c, hipStreamSynchronize(c->stream));
   return TLOAM_OK;
 }
-
-bool solve_small_path(const tloam_ctx* c) {
-  return one_rank(c) && c->k3_single && !c->no_persistent_solve && solve_small_fits(c->k3_grid, c->device_cus);
-}
 }  // namespace
 
 namespace tlh {
@@ -297,13 +308,14 @@ int harvest_k3_events(tloam_ctx* c, int working) {
 }
 // one ceres::Solve on the current correspondence set, device resident: 1 + 4 sweeps at most;
 // sweeps after a tolerance exit are no-op launches (GnState.done).
-// prep: the launch also prepares the factor set (only with solve_small_path and SlotView::flagb, see self_prepare_path)
+// prep: the launch also prepares the factor set (only the one-launch Solve, PrepareForm::IN_SOLVE)
 // finish: ... and finishes the outer iteration, possibly running the following ones too (SolveFinish; needs prep).
 // wp: the weight thresholds of the outer iteration this Solve belongs to (null: a Solve outside scanMatching) -- the
 // one-launch Solve adds up the finish sums of its last evaluation for the finish kernel that follows.
 int enqueue_solve(tloam_ctx* c, bool armed, int sweeps, const WeightParams* wp, const SolvePrep* prep, const SolveFinish* finish) {
   if (!armed) launch_solve_init(c->state.p, c->stream);  // scan_match re-arms the minimiser in its finish kernel
-  if (sweeps > 0 && solve_small_path(c)) {
+  if (sweeps <= 0) return TLOAM_OK;
+  if (c->forms.solve == SolveForm::PERSISTENT) {
     // KITTI-size set: the whole Solve (up to `sweeps` evaluations) is one launch (k_solve_all)
     SolveFinish F;
     if (prep && finish) {
@@ -318,43 +330,48 @@ int enqueue_solve(tloam_ctx* c, bool armed, int sweeps, const WeightParams* wp, 
     c->batch_launches++;
     return TLOAM_OK;
   }
-  // One GN iteration = ONE launch whatever the size of the set (round 4): the streaming sweep's last block folds the rows and
-  // advances the minimiser (k3_sweep_step); with a mailbox it also posts, gathers and advances -- sweep + exchange + step.
-  // RCCL / callback contexts keep sweep | collective | step: the collective is enqueued by the host between two launches.
-  const bool one_launch = c->fused_large && (one_rank(c) ? !c->k3_single : c->comm == COMM_MAILBOX);
   for (int sweep = 0; sweep < sweeps; ++sweep) {
-    if (one_launch) {
-      const int rc = launch_k3_step_timed(c);
-      if (rc != TLOAM_OK) return rc;
-      continue;
-    }
-    if (exchanging(c)) {
-      // sharded GN iteration = 2 launches (+ the collective): the sweep, whose last block folds the rows into the
-      // 48-double buffer (the 42 normal-equation scalars + cost) and -- with the mailbox -- stores it straight into
-      // every rank's buffer over xGMI; then the step, which (mailbox) adds the ranks' rows in rank order itself
-      K3Fuse fuse;
-      memset(&fuse, 0, sizeof(fuse));
-      fuse.ticket = c->k3_ticket.p;
-      fuse.out48 = c->red48.p;
-      if (c->comm == COMM_MAILBOX) fuse.mb = c->mbox;
-      launch_k3_fused(c->cv, c->state.p, c->partials.p, c->k3_grid, c->k3_single, c->k3_wide, false, fuse, c->stream);
-      c->batch_launches++;
-      if (c->comm == COMM_MAILBOX) {
-        launch_gn_step_mbox(c->state.p, c->mbox, c->stream, iter_span_of(c));
-      } else {
-        const int rc = allreduce(c, c->red48.p, kReduceBuf);
-        if (rc != TLOAM_OK) return rc;
-        launch_gn_step(c->state.p, c->red48.p, c->stream, iter_span_of(c));
+    int rc = TLOAM_OK;
+    switch (c->forms.solve) {
+      case SolveForm::PERSISTENT: break;   // (above)
+      case SolveForm::FUSED_LARGE:
+        // One GN iteration = ONE launch whatever the size of the set (round 4): the streaming sweep's last block folds the rows
+        // and advances the minimiser (k3_sweep_step); with a mailbox it also posts, gathers and advances -- sweep + exchange + step
+        rc = launch_k3_step_timed(c);
+        break;
+      case SolveForm::SHARDED_MBOX:
+      case SolveForm::SHARDED_COLLECTIVE: {
+        // sharded GN iteration = 2 launches (+ the collective): the sweep, whose last block folds the rows into the
+        // 48-double buffer (the 42 normal-equation scalars + cost) and -- with the mailbox -- stores it straight into
+        // every rank's buffer over xGMI; then the step, which (mailbox) adds the ranks' rows in rank order itself.
+        // RCCL / callback contexts keep sweep | collective | step: the collective is enqueued by the host between two launches
+        const bool mbox = c->forms.solve == SolveForm::SHARDED_MBOX;
+        K3Fuse fuse;
+        memset(&fuse, 0, sizeof(fuse));
+        fuse.ticket = c->k3_ticket.p;
+        fuse.out48 = c->red48.p;
+        if (mbox) fuse.mb = c->mbox;
+        launch_k3_fused(c->cv, c->state.p, c->partials.p, c->k3_grid, c->k3_single, c->k3_wide, false, fuse, c->stream);
+        c->batch_launches++;
+        if (mbox) {
+          launch_gn_step_mbox(c->state.p, c->mbox, c->stream, iter_span_of(c));
+        } else {
+          rc = allreduce(c, c->red48.p, kReduceBuf);
+          if (rc == TLOAM_OK) launch_gn_step(c->state.p, c->red48.p, c->stream, iter_span_of(c));
+        }
+        break;
       }
-    } else if (c->k3_single) {
-      // KITTI-size set: one launch per GN iteration (k_sweep_step_small)
-      launch_sweep_step_small(c->cv, c->state.p, c->partials.p, c->k3_ticket.p, c->k3_grid, c->stream, iter_span_of(c));
-      c->batch_launches++;
-    } else {
-      const int rc = launch_k3_timed(c, false);
-      if (rc != TLOAM_OK) return rc;
-      launch_reduce_and_step(c->partials.p, c->k3_grid, c->state.p, c->stream, iter_span_of(c));
+      case SolveForm::SMALL_STEP:
+        // KITTI-size set: one launch per GN iteration (k_sweep_step_small)
+        launch_sweep_step_small(c->cv, c->state.p, c->partials.p, c->k3_ticket.p, c->k3_grid, c->stream, iter_span_of(c));
+        c->batch_launches++;
+        break;
+      case SolveForm::SWEEP_REDUCE:
+        rc = launch_k3_timed(c, false);
+        if (rc == TLOAM_OK) launch_reduce_and_step(c->partials.p, c->k3_grid, c->state.p, c->stream, iter_span_of(c));
+        break;
     }
+    if (rc != TLOAM_OK) return rc;
   }
   return TLOAM_OK;
 }
@@ -364,47 +381,51 @@ int enqueue_solve(tloam_ctx* c, bool armed, int sweeps, const WeightParams* wp, 
 //      tloam_scan_match's device-driven loop (every iteration enqueued at once, one host wait per frame) -----------
 namespace {
 constexpr int kMaxOuterFast = kMirrorSlots;   // outer iterations the device-driven loop plans for
-// :976-1020 the four builders (K1 + K2), the flag scan, the index-order caps.  Small single-rank frames: the scan, the
-// caps, the compaction AND the alternative (refresh) are one launch (k_prepare_small) -- `also_refresh` says whether this
-// call stands for both alternatives of a device-gated iteration.
-bool prepare_small_path(const tloam_ctx* c) { return one_rank(c) && prepare_small_fits(c->sv); }
-// the Solve launch that follows prepares the set itself: no k_prepare_small
-bool self_prepare_path(const tloam_ctx* c) { return c->sv.flagb != nullptr && prepare_small_path(c) && solve_small_path(c); }
+// :976-1020 the four builders (K1 + K2), then the flag scan, the index-order caps and the compaction as the frame's prepare form
+// says.  refresh_gate: the call stands for both alternatives of a device-gated iteration (compaction, or the refresh of the
+// unchanged set).
 // ride: the finish of the previous outer iteration rides on this search launch (large single-rank sets, device-driven loop:
 // k_build_finish_large; the search then runs on GnState::spec_build instead of `gate`)
 int enqueue_build(tloam_ctx* c, const BuildParams& bp, const GridView grids[kKinds], bool rebin, const int* gate,
-                  const int* refresh_gate = nullptr, bool prepare_in_solve = false, const FinishLargeArgs* ride = nullptr, int iter = 0) {
+                  const int* refresh_gate = nullptr, const FinishLargeArgs* ride = nullptr, int iter = 0) {
   const size_t n_slots = (size_t)c->sv.slot_off[kKinds];
   // direct set: the search writes the rows itself -- no flag scan, no compaction, no refresh (the Solve reads the live weight stream)
-  const DirectSet ds{c->direct ? 1 : 0, rebin ? 1 : 0, (ride && !rebin) ? 0 : 1, c->direct ? direct_blk_cnt(c, iter) : nullptr,
-                     c->tile_of_slot.p, c->tile_scan.p, c->direct ? c->row_of_pos.p : nullptr};
+  const bool dir = direct(c);
+  const DirectSet ds{dir ? 1 : 0, rebin ? 1 : 0, (ride && !rebin) ? 0 : 1, dir ? direct_blk_cnt(c, iter) : nullptr,
+                     c->tile_of_slot.p, c->tile_scan.p, dir ? c->row_of_pos.p : nullptr};
   if (ride && !rebin) {
     const size_t ntiles = (size_t)build_tile_count(grids, c->sv.slot_off);
-    launch_build_finish_large(c->sv, grids, bp, c->state.p, c->tile_scan.p + ntiles, c->qrec.p, *ride, c->stream, c->direct ? &ds : nullptr);
+    launch_build_finish_large(c->sv, grids, bp, c->state.p, c->tile_scan.p + ntiles, c->qrec.p, *ride, c->stream, dir ? &ds : nullptr);
   } else {
     launch_build(c->sv, grids, bp, c->state.p, c->tile_of_slot.p, c->tile_cnt.p, c->tile_scan.p, c->tile_fill.p,
                  c->qrec.p, c->scan_tmp.p, rebin, c->stream, gate, c->scan1p_q_use ? c->scan1p_q.p : nullptr, c->h_fault.dev + kFaultScan1p,
-                 c->direct ? &c->cv : nullptr, c->direct ? &ds : nullptr, rebin && c->qbin_rode);
+                 dir ? &c->cv : nullptr, dir ? &ds : nullptr, rebin && c->qbin_rode);
     if (rebin) c->qbin_rode = false;   // (consumed: a second sort of this frame -- a re-run -- bins for itself)
   }
-  if (c->direct) return TLOAM_OK;
-  if (prepare_in_solve) return TLOAM_OK;
-  if (prepare_small_path(c)) {
-    launch_prepare_small(c->sv, c->cv, bp, c->seg_n.p, c->state.p, gate, refresh_gate, c->stream);
-    return TLOAM_OK;
-  }
-  if (one_rank(c)) {
-    // single rank: the tile-local scan only -- the compaction adds the tiles' offsets itself -- and ONE launch for both
-    // alternatives of a device-gated iteration (compaction, or the refresh of the unchanged set): two launches less
-    const int tiles = scan_tiles_only(c->flags.p, c->scan.p, n_slots + 1, c->scan_tmp.p, c->stream, gate);
-    if (tiles > 0) {
-      launch_compact(c->sv, c->cv, bp, c->seg_n.p, nullptr, 0, 1, c->state.p, c->stream, gate, refresh_gate, c->scan_tmp.p, tiles);
+  switch (c->forms.prepare) {
+    case PrepareForm::NONE:
+    case PrepareForm::IN_SOLVE:   // (the Solve launch that follows is handed a SolvePrep; tloam_sm_outer, which hands none, prepares)
       return TLOAM_OK;
+    case PrepareForm::SMALL:
+      // small single-rank frames: the scan, the caps, the compaction AND the alternative (refresh) are one launch
+      launch_prepare_small(c->sv, c->cv, bp, c->seg_n.p, c->state.p, gate, refresh_gate, c->stream);
+      return TLOAM_OK;
+    case PrepareForm::TILES: {
+      // single rank: the tile-local scan only -- the compaction adds the tiles' offsets itself -- and ONE launch for both
+      // alternatives of a device-gated iteration (compaction, or the refresh of the unchanged set): two launches less
+      const int tiles = scan_tiles_only(c->flags.p, c->scan.p, n_slots + 1, c->scan_tmp.p, c->stream, gate);
+      if (tiles > 0) {
+        launch_compact(c->sv, c->cv, bp, c->seg_n.p, nullptr, 0, 1, c->state.p, c->stream, gate, refresh_gate, c->scan_tmp.p, tiles);
+        return TLOAM_OK;
+      }
+      break;   // (too few slots for tiles: the full scan)
     }
+    case PrepareForm::FULL: break;
   }
+  const bool sharded = c->forms.prepare == PrepareForm::FULL;   // (not a tile scan that fell through: that is one rank)
   launch_exclusive_scan_u64(c->flags.p, c->scan.p, n_slots + 1, c->scan_tmp.p, c->stream, gate);
   const double* rank_counts = nullptr;
-  if (exchanging(c)) {
+  if (sharded) {
     launch_rank_counts(c->sv, c->rank_counts.p, c->rank, c->nranks, c->stream);
     const int rc = allreduce(c, c->rank_counts.p, c->nranks * kKinds);
     if (rc != TLOAM_OK) return rc;
@@ -412,7 +433,7 @@ int enqueue_build(tloam_ctx* c, const BuildParams& bp, const GridView grids[kKin
   }
   // seg_n: every kind with slots and a positive cap is rewritten by the compaction, the others keep the 0 of
   // k_frame_init; only a sharded rank can find its cap already filled by the lower ranks and write nothing
-  if (exchanging(c)) HIPC(c, hipMemsetAsync(c->seg_n.p, 0, kKinds * sizeof(int), c->stream));
+  if (sharded) HIPC(c, hipMemsetAsync(c->seg_n.p, 0, kKinds * sizeof(int), c->stream));
   launch_compact(c->sv, c->cv, bp, c->seg_n.p, rank_counts, c->rank, c->nranks, c->state.p, c->stream, gate);
   if (refresh_gate) launch_refresh(c->sv, c->cv, c->stream, refresh_gate);
   return TLOAM_OK;
@@ -423,7 +444,7 @@ int planned_sweeps_for(tloam_ctx* c, int iter) {
   const int* hist = &c->planned_sweeps[3 * (size_t)iter];
   int planned = hist[0] == 0 ? kSolveSweeps  // first frame of this context: the full budget
                              : std::min(std::max(std::max(hist[0], hist[1]), std::max(hist[2], 1)), kSolveSweeps);
-  if (solve_small_path(c)) planned = kSolveSweeps;   // one launch runs the Solve to its end: nothing to predict
+  if (c->forms.solve == SolveForm::PERSISTENT) planned = kSolveSweeps;   // one launch runs the Solve to its end: nothing to predict
   if (c->dbg_planned_sweeps > 0) planned = std::min(c->dbg_planned_sweeps, kSolveSweeps);
   return planned;
 }
@@ -457,27 +478,29 @@ int slot_error(tloam_ctx* c, int incomplete, bool* hand_over_timed_out) {
   return TLOAM_OK;
 }
 // :1049-1086 thresholds + weight update, :1091-1094 cost sums, publish (+ device-side loop control when ctl.fast)
-// one 1024-thread block does weights + sums + publish in a single launch
-bool finish_small_path(const tloam_ctx* c) { return one_rank(c) && seg_cap_sum(c) <= 16384; }
 int enqueue_finish(tloam_ctx* c, const WeightParams& wp, const HostMirror& hm, const OuterCtl& ctl, int iter = 0, int built = 1) {
-  if (c->direct) {   // (c->cv carries the weight stream of outer iteration `iter`: direct_set_parity)
-    const FinishLargeArgs fin = direct_finish_args(c, &c->cv, &wp, hm, ctl, iter, /*riding=*/0, built);
-    launch_finish_direct(fin, c->state.p, c->stream);
-    return TLOAM_OK;
-  }
   const int wblocks = finish_wblocks(c);
-  if (finish_small_path(c)) {
-    launch_weights_finish_small(c->cv, c->sv, wp, c->seg_n.p, c->sums16.p, c->state.p, hm, ctl, c->stream);
-    return TLOAM_OK;
-  }
-  launch_weights(c->cv, c->sv, wp, c->wpart.p, wblocks, c->state.p, c->stream);
-  if (exchanging(c)) {
-    launch_outer_finish(c->wpart.p, wblocks, c->seg_n.p, nullptr, c->state.p, c->sums16.p, hm, ctl, c->stream);
-    const int rc = allreduce(c, c->sums16.p, 16);
-    if (rc != TLOAM_OK) return rc;
-    launch_outer_publish(c->sums16.p, c->state.p, hm, c->comm == COMM_MAILBOX ? c->mbox.ctr + 1 : nullptr, c->stream);
-  } else {
-    launch_outer_finish(c->wpart.p, wblocks, c->seg_n.p, c->state.p, c->state.p, c->sums16.p, hm, ctl, c->stream);  // + publish + re-arm
+  switch (c->forms.finish) {
+    case FinishForm::DIRECT: {   // (c->cv carries the weight stream of outer iteration `iter`: direct_set_parity)
+      const FinishLargeArgs fin = direct_finish_args(c, &c->cv, &wp, hm, ctl, iter, /*riding=*/0, built);
+      launch_finish_direct(fin, c->state.p, c->stream);
+      break;
+    }
+    case FinishForm::SMALL:   // one 1024-thread block does weights + sums + publish in a single launch
+      launch_weights_finish_small(c->cv, c->sv, wp, c->seg_n.p, c->sums16.p, c->state.p, hm, ctl, c->stream);
+      break;
+    case FinishForm::LARGE:
+      launch_weights(c->cv, c->sv, wp, c->wpart.p, wblocks, c->state.p, c->stream);
+      launch_outer_finish(c->wpart.p, wblocks, c->seg_n.p, c->state.p, c->state.p, c->sums16.p, hm, ctl, c->stream);  // + publish + re-arm
+      break;
+    case FinishForm::SHARDED: {
+      launch_weights(c->cv, c->sv, wp, c->wpart.p, wblocks, c->state.p, c->stream);
+      launch_outer_finish(c->wpart.p, wblocks, c->seg_n.p, nullptr, c->state.p, c->sums16.p, hm, ctl, c->stream);
+      const int rc = allreduce(c, c->sums16.p, 16);
+      if (rc != TLOAM_OK) return rc;
+      launch_outer_publish(c->sums16.p, c->state.p, hm, c->comm == COMM_MAILBOX ? c->mbox.ctr + 1 : nullptr, c->stream);
+      break;
+    }
   }
   return TLOAM_OK;
 }
@@ -548,7 +571,7 @@ bool pose_moved_since_build(const tloam_ctx* c, int iter) {
 // the host in the loop: one round trip of ~12 us plus ~4 us of launch catch-up per following kernel and per outer
 // iteration on an otherwise idle GPU.)  A Solve that runs out of its planned budget stops the device loop; the host tops
 // it up and re-enters the loop behind the top-up.
-// KITTI-size frames (self_prepare_path + finish in the Solve launch, DeviceLoopPlan::in_launch_finish): a frame is grid
+// KITTI-size frames (RideForm::IN_SOLVE: set prepared and iteration finished in the Solve launch): a frame is grid
 // build + (search + Solve launch) per RUN of outer iterations -- the Solve launch ends its iteration itself and goes on
 // with the next one while the pose stands still.  Only the launches of the first kEnqueueAhead iterations are enqueued up
 // front; the host waits for the result slots IN ORDER and adds a (search, Solve) pair when a slot carries OS_NEEDS_HOST.
@@ -558,11 +581,11 @@ struct DeviceLoopPlan {
   HostMirror hms[kMaxOuterFast];
   // finish-in-the-Solve mode (SolveFinish): the launches of iterations [0, enq_end) are in the stream; a later iteration is
   // enqueued when the device says that it is needed (OS_NEEDS_HOST) -- see scan_match_device_loop
-  bool in_launch_finish = false;
   int enq_end = 0;
   SolveFinish F;
   SolvePrep prep;
 };
+bool in_launch_finish(const tloam_ctx* c) { return c->forms.finish_rides == RideForm::IN_SOLVE; }
 // iterations enqueued ahead of the device's verdicts in finish-in-the-Solve mode: iteration 0 almost always moves the pose
 // (so the search and the Solve of iteration 1 will run), the later ones almost never do (they run inside the launch of
 // iteration 1): launches for them would be no-ops that the frame's successor has to queue behind.
@@ -573,7 +596,7 @@ int enqueue_iterations_in_launch_mode(tloam_ctx* c, int from, int to, const Buil
                                       DeviceLoopPlan& P) {
   GnState* st = c->state.p;
   for (int iter = from; iter < to; ++iter) {
-    int rc = enqueue_build(c, bp, grids, /*rebin=*/iter == 0, iter == 0 ? nullptr : &st->run_build, nullptr, /*prepare_in_solve=*/true);
+    int rc = enqueue_build(c, bp, grids, /*rebin=*/iter == 0, iter == 0 ? nullptr : &st->run_build);
     if (rc != TLOAM_OK) return rc;
     P.prep.run_build = iter == 0 ? nullptr : &st->run_build;
     P.prep.run_refresh = iter == 0 ? nullptr : &st->run_refresh;
@@ -594,30 +617,26 @@ int enqueue_outer_iterations(tloam_ctx* c, int first, double mu, const BuildPara
   GnState* st = c->state.p;
   const int* run_build = &st->run_build;
   const int* run_refresh = &st->run_refresh;
-  // KITTI-size frames: the finish of iteration k-1 does not get a launch of its own, it rides on the correspondence
-  // search of iteration k (k_build_finish_small: they are independent of each other); the last one stands alone
-  const bool ride = prepare_small_path(c) && finish_small_path(c) && build_finish_small_fits(c->sv);
-  // ... and 1 M-class frames the same way with k_weights + k_outer_finish (k_build_finish_large)
-  const bool ride_large = !ride && one_rank(c) && !finish_small_path(c) && build_finish_large_fits(c->sv);
+  // Where the finish of every iteration but the last goes.  ON_SEARCH_SMALL, KITTI-size frames: it does not get a launch of its
+  // own, it rides on the correspondence search of the next iteration (k_build_finish_small: they are independent of each other);
+  // ON_SEARCH_LARGE: 1 M-class frames the same way with k_weights + k_outer_finish (k_build_finish_large)
+  const RideForm rides = c->forms.finish_rides;
   const int wblocks_large = finish_wblocks(c);
-  if (ride_large) HIPC(c, c->fin_rows.reserve((size_t)4 * 256 * 8));
+  if (rides == RideForm::ON_SEARCH_LARGE) HIPC(c, c->fin_rows.reserve((size_t)4 * 256 * 8));
   bool pending = false;   // the finish of the previous iteration has not been enqueued yet (it rides on this search)
-  bool pending_large = false;
   WeightParams wp_prev;
   OuterCtl ctl_prev{0.0, 0, 0};
   int rc = TLOAM_OK;
   // the scan + caps + compaction (or the refresh) of an iteration: a launch of its own (k_prepare_small), or the prologue of
   // the one-launch Solve (SolvePrep)
-  const bool in_solve = self_prepare_path(c);
+  const bool in_solve = c->forms.prepare == PrepareForm::IN_SOLVE;
   SolvePrep prep;
   memset(&prep, 0, sizeof(prep));
   prep.sv = c->sv;
   for (int k = 0; k < kKinds; ++k) prep.maxnum[k] = bp.maxnum[k];
   // ... and the finish of an iteration (weights, sums, loop decisions, result slot): a launch of its own / riding on the next
   // search, or the tail of the one-launch Solve, which then goes on with the next iteration itself while the pose stands still
-  const bool fin_in_solve = in_solve && finish_small_path(c) && M <= kMaxOuterInLaunch;
-  P.in_launch_finish = fin_in_solve;
-  if (fin_in_solve) {
+  if (rides == RideForm::IN_SOLVE) {
     SolveFinish& F = P.F;
     memset(&F, 0, sizeof(F));
     F.enabled = 1;
@@ -639,27 +658,26 @@ int enqueue_outer_iterations(tloam_ctx* c, int first, double mu, const BuildPara
     return enqueue_iterations_in_launch_mode(c, first, std::min(M, first + kEnqueueAhead), bp, grids, P);
   }
   for (int iter = first; iter < M; ++iter) {
-    if (c->direct) direct_set_parity(c, iter);   // what this iteration's Solve (and its finish) read; the search does not care
+    if (direct(c)) direct_set_parity(c, iter);   // what this iteration's Solve (and its finish) read; the search does not care
     if (iter == 0) {
-      rc = enqueue_build(c, bp, grids, /*rebin=*/true, nullptr, nullptr, in_solve);
-    } else if (pending) {
+      rc = enqueue_build(c, bp, grids, /*rebin=*/true, nullptr);
+    } else if (pending && rides == RideForm::ON_SEARCH_SMALL) {
       FinishSmallArgs fin{&c->cv, &wp_prev, c->seg_n.p, c->sums16.p, P.hms[iter - 1], ctl_prev, c->wpart.p, c->k3_ticket.p + 1};
       launch_build_finish_small(c->sv, grids, bp, st, fin, c->stream);
-      if (!in_solve) launch_prepare_small(c->sv, c->cv, bp, c->seg_n.p, st, run_build, run_refresh, c->stream);
-      pending = false;
-    } else if (pending_large) {
+      if (c->forms.prepare == PrepareForm::SMALL) launch_prepare_small(c->sv, c->cv, bp, c->seg_n.p, st, run_build, run_refresh, c->stream);
+    } else if (pending) {   // (ON_SEARCH_LARGE)
       FinishLargeArgs fin{&c->cv, &wp_prev, c->seg_n.p, c->sums16.p, P.hms[iter - 1], ctl_prev, c->fin_rows.p, c->k3_ticket.p + 1,
                           wblocks_large, {}};
       CorrView cv_prev = c->cv;
-      if (c->direct) {   // the finish of iteration iter - 1 reads ITS weight stream and writes this iteration's
+      if (direct(c)) {   // the finish of iteration iter - 1 reads ITS weight stream and writes this iteration's
         for (int k = 0; k < kKinds; ++k) cv_prev.k[k].w = direct_w_stream(c, k, (iter - 1) & 1);
         fin = direct_finish_args(c, &cv_prev, &wp_prev, P.hms[iter - 1], ctl_prev, iter - 1, /*riding=*/1, iter - 1 == 0 ? 1 : -1);
       }
-      rc = enqueue_build(c, bp, grids, /*rebin=*/false, run_build, run_refresh, in_solve, &fin, iter);
-      pending_large = false;
+      rc = enqueue_build(c, bp, grids, /*rebin=*/false, run_build, run_refresh, &fin, iter);
     } else {
-      rc = enqueue_build(c, bp, grids, /*rebin=*/false, run_build, run_refresh, in_solve, nullptr, iter);   // both alternatives, device-gated
+      rc = enqueue_build(c, bp, grids, /*rebin=*/false, run_build, run_refresh, nullptr, iter);   // both alternatives, device-gated
     }
+    pending = false;
     if (rc != TLOAM_OK) return rc;
     prep.run_build = iter == 0 ? nullptr : run_build;   // (the frame's first iteration always builds: no gate)
     prep.run_refresh = iter == 0 ? nullptr : run_refresh;
@@ -671,14 +689,10 @@ int enqueue_outer_iterations(tloam_ctx* c, int first, double mu, const BuildPara
     P.mus[iter] = mu;
     P.hms[iter] = next_mirror(c, iter);
     const OuterCtl ctl{c->cfg.cost_threshold, 1, iter == M - 1 ? 1 : 0};
-    if (ride && iter < M - 1) {
+    if (rides != RideForm::NO && iter < M - 1) {
       wp_prev = weight_params(c, mu, bp);
       ctl_prev = ctl;
       pending = true;
-    } else if (ride_large && iter < M - 1) {
-      wp_prev = weight_params(c, mu, bp);
-      ctl_prev = ctl;
-      pending_large = true;
     } else {
       rc = enqueue_finish(c, weight_params(c, mu, bp), P.hms[iter], ctl, iter, iter == 0 ? 1 : -1);
       if (rc != TLOAM_OK) return rc;
@@ -694,11 +708,11 @@ int enqueue_outer_iterations(tloam_ctx* c, int first, double mu, const BuildPara
 // is there when its last iteration's is, and a launch may have to be added on the way.
 int wait_slots(tloam_ctx* c, const DeviceLoopPlan& P, int iter, bool frame_first) {
   const int M = c->cfg.max_iterations;
-  if (frame_first && !P.in_launch_finish) {
+  if (frame_first && !in_launch_finish(c)) {
     const int rc = wait_state(c, P.hms[M - 1], M - 1);
     if (rc != TLOAM_OK) return rc;
   }
-  if (iter < M - 1 || P.in_launch_finish) return wait_state(c, P.hms[iter], iter);
+  if (iter < M - 1 || in_launch_finish(c)) return wait_state(c, P.hms[iter], iter);
   return TLOAM_OK;
 }
 
@@ -743,7 +757,7 @@ int scan_match_device_loop(tloam_ctx* c, bool* weight_violation) {
       P.solve_start[iter] = c->batch_launches;
       P.planned[iter] = kSolveSweeps;
       const WeightParams wp_top = weight_params(c, P.mus[iter], bp);
-      if (c->direct) direct_set_parity(c, iter);
+      if (direct(c)) direct_set_parity(c, iter);
       rc = enqueue_solve(c, /*armed=*/true, kSolveSweeps, &wp_top);
       if (rc != TLOAM_OK) return rc;
       P.hms[iter] = next_mirror(c, iter);
@@ -774,7 +788,7 @@ int scan_match_device_loop(tloam_ctx* c, bool* weight_violation) {
     if (fin) break;
     // the launch that ran this iteration has ended because the pose moved: the search and the Solve of the next one, unless
     // they are in the stream already
-    if (P.in_launch_finish && needs_host && iter + 1 >= P.enq_end && iter + 1 < M) {
+    if (in_launch_finish(c) && needs_host && iter + 1 >= P.enq_end && iter + 1 < M) {
       const bool trace = getenv("TLOAM_DEBUG_RESUME") != nullptr;   // development aid / test census: how often the host adds a launch
       if (trace) fprintf(stderr, "[tloam resume] outer iteration %d enqueued by the host\n", iter + 1);
       rc = enqueue_iterations_in_launch_mode(c, iter + 1, iter + 2, bp, grids, P);
@@ -783,7 +797,7 @@ int scan_match_device_loop(tloam_ctx* c, bool* weight_violation) {
   }
   rc = harvest_k3_events_multi(c, M, P.solve_start, P.used);
   if (rc != TLOAM_OK) return rc;
-  if (c->direct) {   // what the getters and the timing helpers see: the weights the LAST Solve captured; the current ones: the other stream
+  if (direct(c)) {   // what the getters and the timing helpers see: the weights the LAST Solve captured; the current ones: the other stream
     const int K = std::max(c->stats.outer_iterations, 1);
     direct_set_parity(c, K - 1);
     c->w_parity = K & 1;
@@ -832,10 +846,19 @@ int tloam_sm_begin(tloam_ctx* c, const double predict[16], const double* omega3)
   c->sv.sx = c->sx.p; c->sv.sy = c->sy.p; c->sv.sz = c->sz.p; c->sv.w_src = c->w_src.p;
   c->sv.raw = c->raw.p;
   c->sv.flags = c->flags.p; c->sv.scan = c->scan.p;
-  c->direct = direct_applies(c, off);
   c->set_stale = false;
   c->w_parity = 0;
-  if (c->direct) {
+  // ---- compact segments: at most min(n_src, maxnum) factors per kind (a direct set: one row per source point, which is the same)
+  for (int k = 0; k < kKinds; ++k) {
+    const size_t cap = std::min<size_t>(c->kd[k].n_src, (size_t)std::max(kind_maxnum(c->cfg, k), 0));
+    rc = reserve_seg(c, k, cap);
+    if (rc != TLOAM_OK) return rc;
+  }
+  c->prebuilt = false;
+  plan_sweeps(c);
+  // ---- the frame's shape is known: its launch forms.  Everything below, and every later call of the frame, reads them
+  c->forms = decide_forms(forms_in(c));
+  if (direct(c)) {
     HIPC(c, c->fin_rows.reserve(kFinRowsDoubles));
     c->blk_cnt_n = (off + 63) / 64;   // one-wave blocks of the thread-per-query search (logical: the sorted queries, 64 each)
     HIPC(c, c->blk_cnt.reserve(2 * c->blk_cnt_n * kKinds + 8));
@@ -845,23 +868,11 @@ int tloam_sm_begin(tloam_ctx* c, const double predict[16], const double* omega3)
       HIPC(c, hipMemsetAsync(c->fin_tickets.p, 0, c->fin_tickets.cap * sizeof(int), c->stream));
     }
   }
-  // ---- compact segments: at most min(n_src, maxnum) factors per kind (a direct set: one row per source point, which is the same)
-  for (int k = 0; k < kKinds; ++k) {
-    const size_t cap = std::min<size_t>(c->kd[k].n_src, (size_t)std::max(kind_maxnum(c->cfg, k), 0));
-    rc = reserve_seg(c, k, cap);
-    if (rc != TLOAM_OK) return rc;
-  }
-  c->prebuilt = false;
-  plan_sweeps(c);
-  {
-    // the one-launch Solve compacts the factor set itself when every kind's flag bytes fit a wave (SlotView::flagb)
-    bool fits = solve_small_path(c) && prepare_small_fits(c->sv);
-    for (int k = 0; k < kKinds; ++k) fits = fits && c->kd[k].n_src <= (size_t)kFlagbStride;
-    c->sv.flagb = nullptr;
-    if (fits) {
-      HIPC(c, c->flagb.reserve((size_t)kKinds * kFlagbStride));
-      c->sv.flagb = c->flagb.p;
-    }
+  // the one-launch Solve compacts the factor set itself when every kind's flag bytes fit a wave (SlotView::flagb)
+  c->sv.flagb = nullptr;
+  if (c->forms.prepare == PrepareForm::IN_SOLVE) {
+    HIPC(c, c->flagb.reserve((size_t)kKinds * kFlagbStride));
+    c->sv.flagb = c->flagb.p;
   }
   rc = reserve_partials(c);
   if (rc != TLOAM_OK) return rc;
@@ -874,13 +885,13 @@ int tloam_sm_begin(tloam_ctx* c, const double predict[16], const double* omega3)
   hook.fi.slot_off[kKinds] = c->sv.slot_off[kKinds];
   for (int i = 0; i < 6; ++i) hook.fi.x[i] = x[i];
   hook.fi.no_eval_reuse = c->dbg_no_eval_reuse ? 1 : 0;
-  hook.fi.direct = c->direct ? 1 : 0;
-  if (c->direct) direct_set_parity(c, 0);
+  hook.fi.direct = direct(c) ? 1 : 0;
+  if (direct(c)) direct_set_parity(c, 0);
   // 1 M-class single-rank frames: the first pass of the query sort rides on the last launch of the grid build (QueryBinRide)
   QueryBinRide qbin;
   memset(&qbin, 0, sizeof(qbin));
   c->qbin_rode = false;
-  if (one_rank(c) && !c->no_qbin_ride && direct_set_size((int)std::min<size_t>(off, (size_t)INT32_MAX))) {
+  if (c->forms.qbin_ride) {
     qbin.sv = c->sv;
     qbin.bp = build_params(c);
     qbin.st = c->state.p;
@@ -916,20 +927,19 @@ int tloam_sm_begin(tloam_ctx* c, const double predict[16], const double* omega3)
     GridView gviews[kKinds];
     for (int k = 0; k < kKinds; ++k) gviews[k] = c->kd[k].gv;
     const size_t ntiles = (size_t)build_tile_count(gviews, c->sv.slot_off);
-    HIPC(c, c->tile_cnt.reserve(ntiles + 1 > c->tile_cnt.cap ? 2 * ntiles + 64 : ntiles + 1));   // (room to spare, as build_grids_over)
+    rc = reserve_tile_hist(c, ntiles, /*frame_start=*/true);
+    if (rc != TLOAM_OK) return rc;
     hook.fi.tile_cnt = c->tile_cnt.p;
     hook.fi.n_tile_cnt = (int)ntiles + 1;
     launch_frame_init(hook.fi, hook.b, c->stream);
   }
-  if (c->direct) {
+  if (direct(c)) {
     // a kind whose target cloud has no finite point has no search grid: its queries are not in the sorted order, and the rows of a
     // direct set ARE that order -- such a frame compacts (the frame's start, already enqueued, has set seg_n to the row counts)
-    bool all = true;
-    for (int k = 0; k < kKinds; ++k) all = all && c->kd[k].gv.n > 0;
-    if (!all) {
-      c->direct = false;
-      HIPC(c, hipMemsetAsync(c->seg_n.p, 0, kKinds * sizeof(int), c->stream));
-    }
+    FormsIn in = forms_in(c);
+    for (int k = 0; k < kKinds; ++k) in.has_grid[k] = c->kd[k].gv.n > 0 ? 1 : 0;
+    c->forms = decide_forms(in);
+    if (!direct(c)) HIPC(c, hipMemsetAsync(c->seg_n.p, 0, kKinds * sizeof(int), c->stream));
   }
   c->wait_us = 0.0;
   c->mu = 1.0;  // :961
@@ -967,13 +977,15 @@ int tloam_sm_outer(tloam_ctx* c, int* done, tloam_stats* stats) {
   // neighbour list, fit and gate -- is bit-identical to the previous outer iteration: then only the
   // captured weights and the zeroed side-channel slots of the compact set have to be refreshed.
   const bool same_pose = c->have_build && !pose_moved_since_build(c, iter) && !c->dbg_no_build_reuse;
-  if (c->direct) direct_set_parity(c, iter);
+  if (direct(c)) direct_set_parity(c, iter);
   if (!same_pose) {
-    rc = enqueue_build(c, bp, grids, /*rebin=*/iter == 0, nullptr, nullptr, false, nullptr, iter);
+    rc = enqueue_build(c, bp, grids, /*rebin=*/iter == 0, nullptr, nullptr, nullptr, iter);
     if (rc != TLOAM_OK) return rc;
+    // (the host between the iterations hands the Solve no SolvePrep: a set whose flag bytes fit is prepared like any small one)
+    if (c->forms.prepare == PrepareForm::IN_SOLVE) launch_prepare_small(c->sv, c->cv, bp, c->seg_n.p, c->state.p, nullptr, nullptr, c->stream);
     memcpy(c->build_x, c->stats.se3, sizeof(c->build_x));
     c->have_build = true;
-  } else if (!c->direct) {
+  } else if (!direct(c)) {
     launch_refresh(c->sv, c->cv, c->stream);
   }
   if (iter == 0) c->mu = initial_mu(c);
@@ -1005,7 +1017,7 @@ int tloam_sm_outer(tloam_ctx* c, int* done, tloam_stats* stats) {
   if (rc != TLOAM_OK) return rc;
   bool weight_violation = false;
   const bool fin = account_outer(c, iter, S, mu, sweeps_before, &weight_violation);
-  if (c->direct) c->w_parity = (iter + 1) & 1;   // (c->cv stays on the stream this Solve captured)
+  if (direct(c)) c->w_parity = (iter + 1) & 1;   // (c->cv stays on the stream this Solve captured)
   if (done) *done = fin ? 1 : 0;
   if (stats) *stats = c->stats;
   return weight_violation ? TLOAM_E_WEIGHT_RANGE : TLOAM_OK;  // the iteration is complete either way (:871)
@@ -1024,39 +1036,40 @@ int tloam_scan_match(tloam_ctx* c, const double predict[16], const double* omega
                      double* scan_xyz, size_t n_scan, tloam_stats* stats) {
   if (n_scan > kMaxPoints) return TLOAM_E_INVALID;
   static const bool stamps = getenv("TLOAM_HOST_STAMPS") != nullptr;
-  auto now_us = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double hs0 = stamps ? now_us() : 0.0;
+  const double hs0 = stamps ? host_now_us() : 0.0;
   if (c) c->hs_entry = hs0;
   int rc = tloam_sm_begin(c, predict, omega3);
   if (rc != TLOAM_OK) return rc;
-  const double hs1 = stamps ? now_us() : 0.0;
+  const double hs1 = stamps ? host_now_us() : 0.0;
+  // which bounded wait of the look-back scan ran out, if any (to be read before check_device_faults clears the words)
+  auto scan_fault_raised = [&] { return c->h_fault && __atomic_load_n(&c->h_fault[kFaultScan1p], __ATOMIC_ACQUIRE) != 0u; };
+  // A look-back scan of this frame gave up: the clouds are intact in HBM and check_device_faults has switched the context to the
+  // multi-launch scans -- the frame is run again, once per context.  Otherwise the frame returns rc_in
+  auto rerun_after_scan_fault = [&](bool scan_fault, int rc_in) -> int {
+    if (!scan_fault || c->scan1p_retried) return rc_in;
+    c->scan1p_retried = true;
+    return tloam_scan_match(c, predict, omega3, result, scan_xyz, n_scan, stats);
+  };
   // A frame that fails on the way -- an unwritten result slot, a minimiser that "did not terminate", a time-out inside a launch --
   // may have failed on the garbage a timed-out look-back scan left behind: the frame is closed, the fault words are looked at
   // (check_device_faults moves the context to the forms that wait for nothing and clears them: the NEXT frame is not blamed), and
-  // if it was the scan the frame is run again, once per context, as tloam_sm_end's path does.
+  // if it was the scan the frame is run again, as behind tloam_sm_end.
   auto frame_failed = [&](int rc_in) -> int {
     (void)hipStreamSynchronize(c->stream);
     c->active = false;
-    const bool scan_fault_now = c->h_fault && __atomic_load_n(&c->h_fault[kFaultScan1p], __ATOMIC_ACQUIRE) != 0u;
+    const bool scan_fault = scan_fault_raised();
     (void)check_device_faults(c);
-    if (scan_fault_now && !c->scan1p_retried) {
-      c->scan1p_retried = true;
-      return tloam_scan_match(c, predict, omega3, result, scan_xyz, n_scan, stats);
-    }
-    return rc_in;
+    return rerun_after_scan_fault(scan_fault, rc_in);
   };
   int done = 0;
   bool weight_violation = false;
-  // device-driven outer loop where the stepwise machinery is not asked for: one rank, a pinned mirror, the planned
-  // iterations fit the result slots, no development knob that needs the host between iterations
-  if (one_rank(c) && c->cfg.max_iterations >= 1 && c->cfg.max_iterations <= kMaxOuterFast &&
-      !c->dbg_no_build_reuse && !c->no_device_loop) {
-    const bool persistent = solve_small_path(c);
+  if (c->forms.loop == LoopForm::DEVICE) {   // (else the stepwise machinery below)
     rc = scan_match_device_loop(c, &weight_violation);
-    if (rc == TLOAM_E_HIP && persistent && c->hand_over_timed_out) {
+    if (rc == TLOAM_E_HIP && c->forms.solve == SolveForm::PERSISTENT && c->hand_over_timed_out) {
       // A block of the one-launch Solve was never scheduled beside the others (a device shared with long-running kernels,
       // fewer usable CUs than the attribute says): the waits inside the launch are bounded, the frame is intact in HBM --
-      // solve it again with one launch per GN iteration, and keep this context on that path.
+      // solve it again with one launch per GN iteration, and keep this context on that path (the forms follow from the knob:
+      // tloam_sm_begin decides them again).
       c->no_persistent_solve = true;
       c->persistent_solve_timed_out = true;
       c->fallback_events++;
@@ -1076,12 +1089,11 @@ int tloam_scan_match(tloam_ctx* c, const double predict[16], const double* omega
     if (rc == TLOAM_E_WEIGHT_RANGE) { weight_violation = true; continue; }  // reported after the solve
     if (rc != TLOAM_OK) return frame_failed(rc);
   }
-  const double hs2 = stamps ? now_us() : 0.0;
-  // (which bounded wait ran out, if any: tloam_sm_end's check_device_faults clears the words)
-  const bool scan_fault = c->h_fault && __atomic_load_n(&c->h_fault[kFaultScan1p], __ATOMIC_ACQUIRE) != 0u;
+  const double hs2 = stamps ? host_now_us() : 0.0;
+  const bool scan_fault = scan_fault_raised();   // (tloam_sm_end's check_device_faults clears the words)
   rc = tloam_sm_end(c, result, stats);
   if (stamps && c) {
-    const double hs3 = now_us();
+    const double hs3 = host_now_us();
     if (c->hs_exit > 0.0) c->hs[0] += hs0 - c->hs_exit;   // the caller, between two calls
     c->hs[1] += hs1 - hs0;                                 // sm_begin: set-up + the grid build's launches
     c->hs[2] += hs2 - hs1 - c->wait_us;                    // the loop: enqueueing, bookkeeping (without the wait)
@@ -1095,12 +1107,7 @@ int tloam_scan_match(tloam_ctx* c, const double predict[16], const double* omega
       for (int i = 0; i < 8; ++i) c->hs[i] = 0.0;
     }
   }
-  if (rc == TLOAM_E_HIP && scan_fault && !c->scan1p_retried) {
-    // a look-back scan of this frame gave up (check_device_faults): the clouds are intact in HBM and the context has been
-    // switched to the multi-launch scans -- run the frame again, once
-    c->scan1p_retried = true;
-    return tloam_scan_match(c, predict, omega3, result, scan_xyz, n_scan, stats);
-  }
+  if (rc == TLOAM_E_HIP) return rerun_after_scan_fault(scan_fault, rc);
   if (rc != TLOAM_OK) return rc;
   if (scan_xyz && n_scan > 0) {  // :1126-1128 out_result_.scan_cloud->Transform(curr_frame_pose)
     HIPC(c, c->misc.reserve(3 * n_scan));

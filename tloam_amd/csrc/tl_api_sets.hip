@@ -138,7 +138,7 @@ int tloam_get_correspondences(tloam_ctx* c, int kind, size_t capacity, size_t* n
   if (!c || kind < 0 || kind >= kKinds || !n) return TLOAM_E_INVALID;
   HIPC(c, hipSetDevice(c->device));
   HIPC(c, hipStreamSynchronize(c->stream));
-  const bool direct = c->direct && !c->prebuilt;
+  const bool direct = c->forms.set == SetForm::DIRECT && !c->prebuilt;
   size_t rows;
   if (direct) {
     const int rc = fresh_direct_set(c);
@@ -189,7 +189,7 @@ int tloam_get_weights(tloam_ctx* c, int kind, size_t capacity, size_t* n, double
   *n = m;
   if (m > capacity || !begun) return TLOAM_E_INVALID;
   HIPC(c, hipStreamSynchronize(c->stream));
-  if (c->direct && !c->prebuilt) {   // the current GNC weights live in the rows' weight stream `w_parity`: back to source-index order
+  if (c->forms.set == SetForm::DIRECT && !c->prebuilt) {   // the current GNC weights live in the rows' weight stream `w_parity`: back to source-index order
     if (w && m > 0 && !c->have_build) {   // (no search has run in this frame yet: registration.cpp:931-949, every weight is 1)
       for (size_t i = 0; i < m; ++i) w[i] = 1.0;
     } else if (w && m > 0) {
@@ -260,7 +260,6 @@ int tloam_set_correspondences(tloam_ctx* c, int res_type, size_t n, const double
   if (rc != TLOAM_OK) return rc;
   const int kind = res_kind(res_type);
   if (!c->prebuilt) {
-    c->direct = false;   // a pre-built set is compact
     HIPC(c, hipMemsetAsync(c->seg_n.p, 0, 8 * sizeof(int), c->stream));
     for (int k = 0; k < kKinds; ++k) {
       rc = reserve_seg(c, k, 1);
@@ -304,6 +303,11 @@ int tloam_set_correspondences(tloam_ctx* c, int res_type, size_t n, const double
   const int full[kKinds] = {(int)c->kd[0].pre_n_full, 0, (int)c->kd[2].pre_n_full, (int)c->kd[3].pre_n_full};
   c->k3_alg_bytes = alg_bytes_of(full);
   plan_sweeps(c);
+  {
+    FormsIn in = forms_in(c);   // (a pre-built set has no source slots, whatever clouds are registered: it is compact)
+    for (int k = 0; k < kKinds; ++k) in.n_src[k] = in.n_tgt[k] = 0;
+    c->forms = decide_forms(in);
+  }
   return reserve_partials(c);
 }
 

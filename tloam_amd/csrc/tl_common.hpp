@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "../../include/tloam_hip.h"
+#include "tl_forms.hpp"
 #include "tl_se3.hpp"
 
 namespace tl {
@@ -104,7 +105,6 @@ struct DirectSet {
 constexpr int kDirectBinMax = 1024;
 
 // ---- per-source-slot arrays of one scan_match (concatenated over kinds) ----------------------
-constexpr int kFlagbStride = 4096;   // 64 lanes x 64 slots
 struct SlotView {
   const double *sx, *sy, *sz;  // source points (sensor frame)
   double* w_src;               // GNC weights
@@ -410,7 +410,6 @@ void launch_build(const SlotView& sv, const GridView grids[kKinds], const BuildP
                   double4* qrec, unsigned long long* scan_tmp, bool rebin, hipStream_t s, const int* gate = nullptr,
                   unsigned long long* scan1p_ctl = nullptr, unsigned* scan1p_fault = nullptr, const CorrView* direct_cv = nullptr,
                   const DirectSet* ds = nullptr, bool binned = false);   // binned: the sort's first pass rode on the grid build
-bool direct_set_size(int n_slots);   // frames the thread-per-query search takes (the size class of the direct set)
 int build_tile_count(const GridView grids[kKinds], const int slot_off[kKinds + 1]);  // bins of the query counting sort (per kind: its tiles, or the cells of its tiles)
 // cap + compaction (after the flag scan)
 // refresh_gate != null: the launch also stands for the refresh alternative (see CompactArgs); tiles > 0: `sv.scan` holds
@@ -422,7 +421,6 @@ void launch_rank_counts(const SlotView& sv, double* rank_counts, int rank, int n
 // same correspondences, new outer iteration: re-capture the weights, zero the side-channel slots
 void launch_refresh(const SlotView& sv, const CorrView& cv, hipStream_t s, const int* gate = nullptr);
 // small single-rank frames: flag scan + caps + compaction (run_build, or always if null) or refresh (run_refresh) in ONE launch
-bool prepare_small_fits(const SlotView& sv);
 void launch_prepare_small(const SlotView& sv, const CorrView& cv, const BuildParams& bp, int* seg_n, GnState* st,
                           const int* run_build, const int* run_refresh, hipStream_t s);
 // generic hybrid search (tloam_knn / fitness)
@@ -1153,7 +1151,6 @@ void launch_reduce_and_step(const double* partials, int grid, GnState* st, hipSt
 void launch_sweep_step_small(const CorrView& cv, GnState* st, double* partials, int* ticket, int grid, hipStream_t s,
                              unsigned long long* iter_span = nullptr);
 // sets whose sweep is a grid of a dozen blocks: a whole ceres::Solve (up to max_sweeps evaluations) in ONE launch
-bool solve_small_fits(int grid, int device_cus);
 // The factor set of an outer iteration prepared by the Solve launch itself (no k_prepare_small launch in front of it):
 // flagb == null means "already prepared" (stepwise API, topped-up Solves).
 struct SolvePrep {
@@ -1172,7 +1169,6 @@ struct WeightParams {
 // decisions and writes the result slot; if the loop goes on with an unchanged pose the launch refreshes its correspondences
 // in registers and runs the next Solve as well.  enabled == 0: the launch ends with the Solve and leaves the sums in the
 // state for the finish kernel (GnState::fin_valid).
-constexpr int kMaxOuterInLaunch = 8;
 struct SolveFinish {
   int enabled;
   int have_wp;               // wp[first_iter ..] are set: the launch adds up the finish sums of its Solve(s)
@@ -1196,7 +1192,6 @@ void launch_outer_publish(const double* sums8, GnState* st, HostMirror hm, const
 // KITTI-size frames, device-driven loop: the finish of outer iteration k-1 (the first sixteen blocks) and the
 // correspondence search of iteration k (the other blocks, gated on GnState::spec_build) in ONE launch -- they are
 // independent of each other
-bool build_finish_small_fits(const SlotView& sv);
 struct FinishSmallArgs {
   const CorrView* cv;
   const WeightParams* wp;
@@ -1231,7 +1226,6 @@ struct FinishLargeArgs {
 // the finish of a direct set as a launch of its own (stepwise API, the frame's last outer iteration, a topped-up Solve): the same
 // one-wave blocks as the riding form, bit for bit
 void launch_finish_direct(const FinishLargeArgs& fin, GnState* st, hipStream_t s);
-bool build_finish_large_fits(const SlotView& sv);
 void launch_build_finish_large(const SlotView& sv, const GridView grids[kKinds], const BuildParams& bp, GnState* st,
                                const unsigned long long* n_sorted, const double4* qrec, const FinishLargeArgs& fin, hipStream_t s,
                                const DirectSet* ds = nullptr);

@@ -14,6 +14,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <chrono>
 #include <initializer_list>
 #include <memory>
 #include <new>
@@ -64,6 +65,12 @@ struct DBuf {
     p = q;
     cap = want;
     return hipSuccess;
+  }
+  // ... for a table that must read zero before its first use: zeroed as a whole, on the stream, whenever it is (re)allocated
+  hipError_t reserve_zeroed(size_t n, hipStream_t s) {
+    const size_t before = cap;
+    const hipError_t e = reserve(n);
+    return (e != hipSuccess || cap == before) ? e : hipMemsetAsync(p, 0, cap * sizeof(T), s);
   }
   void release() {   // the early free, for the places that give memory back mid-life
     if (p) (void)hipFree(p);
@@ -683,8 +690,13 @@ struct tloam_ctx {
   bool no_qbin_ride = false;   // TLOAM_NO_QBIN_RIDE: the query sort's first pass as a launch of its own (A/B)
   bool qbin_rode = false;      // this frame's query binning rode on the grid build (launch_build skips its own)
   bool no_direct_set = false;  // TLOAM_NO_DIRECT_SET: large frames compact as the others do (A/B, tests)
-  bool direct = false;         // this frame's set is direct: rows = tile-sorted queries, holes, two weight streams
-  bool set_stale = false;      // ... and its rows hold the geometry of a search whose set was never solved (OS_SET_STALE): rebuilt at
+  // The launch forms of the frame (tl_forms.hpp), written where a factor set's shape becomes known: tloam_sm_begin (and its
+  // demotion of a direct frame without a grid for every kind) and tloam_set_correspondences.  The knobs that only select forms --
+  // no_persistent_solve, no_direct_set, no_device_loop, fused_large, no_qbin_ride -- reach the driver through forms_in alone
+  // (dbg_no_build_reuse too, but it also changes what tloam_sm_outer does inside the host-driven loop).
+  // forms.set == DIRECT: rows = tile-sorted queries, holes, two weight streams
+  tl::FrameForms forms;
+  bool set_stale = false;      // a direct set's rows hold the geometry of a search whose set was never solved (OS_SET_STALE): rebuilt at
                                // x_build before a getter reads them
   int w_parity = 0;            // weight stream the CURRENT GNC weights are in (the captured ones of the last Solve: the other)
   DBuf<GnState> state_scratch; // a copy of the state with T_cur = exp(x_build), for that rebuild
@@ -724,7 +736,7 @@ struct tloam_ctx {
 
 // pinned result slots: one per outer iteration of a device-driven frame (slot 0: stepwise API); the last one also
 // carries the sizes of a submap update back (tl_api_submap.hip)
-constexpr int kMirrorSlots = 8;
+constexpr int kMirrorSlots = tl::kResultSlots;
 constexpr int kFaultWords = 16;
 constexpr int kFaultScan1p = 0, kFaultVoxEmit = 1;   // tloam_ctx::h_fault
 // Points a single cloud / correspondence set / query batch may hold: slots, cells and ranks are 32-bit integers throughout, and the
@@ -738,6 +750,10 @@ namespace tlh {
 // ---- small helpers shared by the API units
 // column-major 4x4 products, sums over k in ascending order, and Eigen::Isometry3d::inverse (R^T, -R^T t): the odometry's
 // prediction, loop verification's T_rel and the pose graph's Z round alike (their units are compiled with -ffp-contract=off)
+// the steady clock in microseconds: the TLOAM_HOST_STAMPS brackets
+static inline double host_now_us() {
+  return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
 static inline void mat_mul(const double A[16], const double B[16], double out[16]) {
   double r[16];
   for (int j = 0; j < 4; ++j)
@@ -868,6 +884,8 @@ void comm_rccl_info(const tloam_ctx* c, int32_t* count, int32_t* user_rank);   /
 int reserve_seg(tloam_ctx* c, int k, size_t n);        // compact correspondence segment of kind k for n factors
 int ensure_common(tloam_ctx* c);                       // the context's small fixed device buffers
 int reserve_query_sort(tloam_ctx* c, const tl::GridView grids[tl::kKinds]);   // the buffers of the frame's query sort, sized by the grids
+int reserve_tile_hist(tloam_ctx* c, size_t ntiles, bool frame_start, size_t* room = nullptr);   // ... its histogram and scan: the one size rule
+tl::FormsIn forms_in(const tloam_ctx* c);              // what decide_forms looks at, from the context (every kind assumed to get a grid)
 // ... and what tl_api_sets.hip shares with the frame:
 constexpr int kSolveSweeps = 5;                        // max_num_iterations 4 -> at most 1 + 4 evaluations per Solve
 tl::BuildParams build_params(const tloam_ctx* c);      // the search's radii, caps and active kinds from the configuration

@@ -574,8 +574,7 @@ __device__ __forceinline__ void fold_rows(const double* __restrict__ partials, i
 // segment checks, then folds them in the order fold_rows uses.  No ordering between any two words is relied on: a
 // segment that has only partly arrived -- or still holds an older launch's sums -- does not check.  All blocks of such a
 // grid are resident at once (a dozen blocks on 256 CUs); the spin is bounded all the same (~1 s, then the Solve is
-// stopped with GnState::comm_error).
-constexpr int kTaggedRows = 16;
+// stopped with GnState::comm_error).  (kTaggedRows = 16: tl_forms.hpp)
 // (The ROW segments below enter their check word by a plain XOR, not through seg_word: their payload is seven fp64 SUMS that
 //  change from one GN iteration to the next.  A segment that mixes old and new words passes only if the words that are still old
 //  changed by the same 64-bit pattern: one such word -> it did not change, the segment reads as what it is; two -> two sums whose
@@ -1603,8 +1602,7 @@ void launch_solve_small(const CorrView& cv, GnState* st, double* partials, int* 
 }
 // The launch spin-waits between its blocks, so all of them must be resident at once: one block per CU (the consumer's step
 // wants ~400 registers: one wave per SIMD), i.e. grid <= the device's CU count -- 256 on an MI355X, fewer on a CU-masked or
-// partitioned device (then the one-launch-per-iteration kernels run instead).
-bool solve_small_fits(int grid, int device_cus) { return grid <= kTaggedRows && grid <= device_cus; }
+// partitioned device (then the one-launch-per-iteration kernels run instead: decide_forms, SolveForm::PERSISTENT).
 void launch_reduce_and_step(const double* partials, int grid, GnState* st, hipStream_t s, unsigned long long* iter_span) {
   hipLaunchKernelGGL(k_reduce_and_step, dim3(1), dim3(kRedThreads), 0, s, partials, grid, st, iter_span);
 }

@@ -839,14 +839,7 @@ __device__ __forceinline__ void store_raw(const SlotView& sv, int slot, const Ra
 //  Replaces the kd-tree walks of registration.cpp:444/:535/:588/:731.
 // ================================================================================================
 constexpr int kTile = 4;        // cells per tile edge
-#ifndef TLOAM_K1_QUAD_LIMIT
-#define TLOAM_K1_QUAD_LIMIT 131072
-#endif
-#ifndef TLOAM_K1_WIDE_LIMIT
-#define TLOAM_K1_WIDE_LIMIT 16384
-#endif
-constexpr int kQuadLimit = TLOAM_K1_QUAD_LIMIT;  // at most this many queries: four lanes per query (latency-bound regime)
-constexpr int kWideLimit = TLOAM_K1_WIDE_LIMIT;   // at most this many: sixteen lanes per query (one row of the 27 cells per lane)
+// (kQuadLimit / kWideLimit, the query counts up to which four / sixteen lanes search a query: tl_forms.hpp)
 
 struct TileMeta {
   int tdim[kKinds][3];
@@ -882,7 +875,6 @@ struct BuildArgs {
   DirectSet ds;     // ds.on: the search writes the factor set itself, row = sorted position (tl_common.hpp DirectSet) ...
   CorrView cv;      // ... into these segments
 };
-bool direct_set_size(int n_slots) { return n_slots > kQuadLimit; }
 
 __device__ __forceinline__ int slot_kind(const SlotView& sv, int slot) {
   int kind = 0;
@@ -1182,7 +1174,7 @@ void launch_build(const SlotView& sv, const GridView grids[kKinds], const BuildP
   A.bp = bp;
   memset(&A.ds, 0, sizeof(A.ds));
   memset(&A.cv, 0, sizeof(A.cv));
-  if (direct_cv && ds && direct_set_size(n)) { A.ds = *ds; A.cv = *direct_cv; }
+  if (direct_cv && ds && n > kQuadLimit) { A.ds = *ds; A.cv = *direct_cv; }
   for (int k = 0; k < kKinds; ++k) A.grid[k] = grids[k];
   const int ntiles = tile_meta(grids, sv.slot_off, &A.tm);   // bins of the counting sort
   // KITTI-size frames (sixteen lanes per query) are searched in SLOT order, unsorted: their target records (2-3 MB)
@@ -1261,7 +1253,6 @@ __global__ __launch_bounds__(64) void k_build_finish_small(BuildArgs A, GnState*
   const double4 q = double4{A.sv.sx[i], A.sv.sy[i], A.sv.sz[i], __longlong_as_double((long long)i)};
   query_one<16>(A, slot_kind(A.sv, i), st->T_cur, q, i, sub, nullptr);
 }
-bool build_finish_small_fits(const SlotView& sv) { return sv.slot_off[kKinds] > 0 && sv.slot_off[kKinds] <= kWideLimit; }
 void launch_build_finish_small(const SlotView& sv, const GridView grids[kKinds], const BuildParams& bp, GnState* st,
                                const FinishSmallArgs& fin, hipStream_t s) {
   const int n = sv.slot_off[kKinds];
@@ -1282,7 +1273,6 @@ void launch_build_finish_small(const SlotView& sv, const GridView grids[kKinds],
                      fin.hm, fin.ctl, W, FinishRide{fin.rows, fin.ticket});
 }
 
-bool build_finish_large_fits(const SlotView& sv) { return sv.slot_off[kKinds] > kQuadLimit; }
 void launch_build_finish_large(const SlotView& sv, const GridView grids[kKinds], const BuildParams& bp, GnState* st,
                                const unsigned long long* n_sorted, const double4* qrec, const FinishLargeArgs& fin, hipStream_t s,
                                const DirectSet* ds) {
@@ -1491,7 +1481,6 @@ __global__ __launch_bounds__(256) void k_prepare_small(PrepareArgs A) {
   seg.w[pos] = A.sv.w_src[slot];  // weight captured by value at construction (registration.hpp:51,76,96)
   seg.cost[pos] = 0.0;            // fresh side-channel slot (registration.cpp:1118-1121)
 }
-bool prepare_small_fits(const SlotView& sv) { return sv.slot_off[kKinds] <= 16384; }
 void launch_prepare_small(const SlotView& sv, const CorrView& cv, const BuildParams& bp, int* seg_n, GnState* st,
                           const int* run_build, const int* run_refresh, hipStream_t s) {
   PrepareArgs A;

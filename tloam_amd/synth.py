@@ -87,6 +87,18 @@ KITTI_SRC = (3000, 4000, 2000, 400)
 KITTI_TGT = (12000, 40000, 30000, 1500)
 SMALL_SRC = (400, 500, 300, 80)            # parity-test size (oracle runs in milliseconds)
 SMALL_TGT = (1600, 4000, 3000, 300)
+# Frames on each side of the sizes at which the driver launches something else (tl_forms.hpp), source points per kind:
+BOUNDARY_SRC = {
+    # a kind's flag bytes (kFlagbStride): the one-launch Solve prepares the set itself | k_prepare_small does
+    "planar4096": (4096, 4000, 2000, 400), "planar4097": (4097, 4000, 2000, 400),
+    # 16384 source points: sixteen lanes per query, k_prepare_small, the finish rides on the search | four lanes, tile scan
+    "n16384": (6000, 7000, 3000, 384), "n16385": (6000, 7000, 3000, 385),
+    # lifted caps: 23 + 20 planar and ground chunks of 128, 16 + 4 edge and sphere chunks of 64 and the idle wave are the 64 waves
+    # of a sixteen-block grid, the largest one-launch Solve | one chunk more: a launch per GN iteration
+    "lifted16": (2944, 2560, 1024, 256), "lifted17": (2945, 2560, 1024, 256),
+    # 131072 source points, caps lifted: four lanes per query, compacted | a thread per query, the direct set
+    "n131072": (50000, 40000, 35000, 6072), "n131073": (50000, 40000, 35000, 6073),
+}
 M1_SRC = (500_000, 260_000, 200_000, 40_000)   # the 1 M-correspondence frame (760k plane : 200k line : 40k point)
 M1_TGT = (500_000, 260_000, 200_000, 40_000)
 
