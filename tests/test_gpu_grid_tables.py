@@ -13,8 +13,8 @@ from tloam_amd import synth
 
 pytestmark = pytest.mark.gpu
 
-CELLS_PER_POINT = 32          # a kind's table: at most max(16 Ki, 32 per point) cells (tl_api_frames.hip)
-SCAN_TILE = 2048              # entries per scan tile (tl_nn.hip)
+CELLS_PER_POINT = 32          # a kind's table: at most max(16 Ki, 32 per point) cells (tl_grid_plan.hpp)
+SCAN_TILE = 2048              # entries per scan tile (tl_grid_plan.hpp)
 
 
 def _box_cloud(rng, lo, extent, n):
@@ -76,6 +76,51 @@ def test_path_edges(hip_module, cells_per_axis, path):
         assert -(-(gi["ncell"][2] + 1) // SCAN_TILE) == 9
     assert H.info()["fallbacks_taken"] == 0
     H.close()
+
+
+@pytest.fixture(scope="module")
+def big_table_context(hip_module):
+    """ONE context for the four builds around 2^21 cells below, which run in the order they are listed: a histogram or a table
+    that one path's layout left wrong shows in the next build."""
+    H, O = _pair(hip_module)
+    yield H, O
+    H.close()
+
+
+# cells per axis at radius 1.0 and the path by table size alone: 1024 scan tiles exactly | 1024 tiles packed but 1025 padded, so
+# neither the single-pass scan (judged on the packed size) nor the tile path (on the padded one) takes it | 129 blocks of 16 Ki
+BIG_TABLES = [("tiles", (126, 130, 128)), ("generic", (150, 341, 41)), ("single_pass", (128, 128, 128)), ("tiles again", (126, 130, 128))]
+
+
+@pytest.mark.parametrize("step,dims", BIG_TABLES, ids=[s for s, _ in BIG_TABLES])
+def test_path_edges_at_two_million_cells(hip_module, big_table_context, step, dims):
+    """One kind of 66 000 points (32 cells per point: the sparse bound does not bind) in a box with two corner points."""
+    reg = hip_module
+    H, O = big_table_context
+    rng = np.random.default_rng(300 + dims[1])
+    lo = np.array([-60.0, -70.0, -20.0])
+    extent = np.array(dims, float) - 0.5
+    tgt = _box_cloud(rng, lo, extent, 66000)
+    q = np.concatenate([tgt[rng.integers(0, len(tgt), 200)] + rng.normal(0, 0.3, (200, 3)),
+                        lo + extent + rng.uniform(40, 60, (50, 3)) * rng.choice([-1.0, 1.0], (50, 3))])
+    _set(H, O, 2, tgt)
+    cnt = _check_knn(H, O, 2, tgt, q, 1.0, 5)
+    assert cnt[:200].max() > 0
+    ncell = dims[0] * dims[1] * dims[2]
+    cus = H.info()["device_cus"]
+    if step.startswith("tiles"):
+        path, width = reg.GRID_SCAN_TILES, 4
+        n_tab = (ncell + 1 + 3) // 4 * 4 + 3 * 4          # the padded table: every kind without a grid still has its 4 entries
+        assert -(-n_tab // SCAN_TILE) == 1024
+    elif step == "single_pass" and 129 <= cus - cus // 16:
+        path, width = reg.GRID_SCAN_SINGLE_PASS, 8
+    else:
+        path, width = reg.GRID_SCAN_GENERIC, 8
+    gi = H.grid_info()
+    print(step, "device_cus", cus, "scan_path", gi["scan_path"], "elem bytes", gi["table_elem_bytes"], "dim", gi["dim"][2], "ncell", gi["ncell"][2])
+    assert gi["scan_path"] == path and gi["table_elem_bytes"] == width
+    assert gi["dim"][2] == list(dims) and gi["ncell"][2] == ncell and gi["n"][2] == 66000
+    assert H.info()["fallbacks_taken"] == 0
 
 
 def _stepwise_against_oracle(H, O, T_pred, empty_kinds=()):

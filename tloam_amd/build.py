@@ -23,6 +23,7 @@ COMMON += os.environ.get("TLOAM_EXTRA_HIPCC_FLAGS", "").split()  # development a
 UNITS = [
     # K1/K2: un-fused fp64 so the discontinuous gates see the oracle's operation order
     ("tl_nn.hip", ["-ffp-contract=off", *PRELOAD]),
+    ("tl_scan.hip", ["-ffp-contract=off", *PRELOAD]),   # the scans: moved out of tl_nn.hip, compiled as it is
     ("tl_submap.hip", ["-ffp-contract=off"]),   # voxel indices / means in the oracle's operation order
     ("tl_feature.hip", ["-ffp-contract=off"]),  # PCA gates (flatness / cvr thresholds) like the oracle
     ("tl_seg.hip", ["-ffp-contract=off"]),      # segmentation: height / plane / voxel / curvature gates as the reference rounds them
@@ -73,7 +74,7 @@ UNITS = [
     ("tl_api_snapshot.hip", []), # the closed map's snapshot: save, probe, load
     ("tl_probe.hip", []),        # read-stream bandwidth probe (the on-box ceiling of the bench's roofline block)
 ]
-HEADERS = ["tl_common.hpp", "tl_forms.hpp", "tl_se3.hpp", "tl_knn.hpp", "tl_walk.hpp", "tl_voxel.hpp", "tl_ctx.hpp", "tl_step.hpp", "tl_finish.hpp", "tl_prep.hpp", "tl_seg.hpp", "tl_extend_host.hpp", "tl_free_box.hpp", os.path.join("..", "..", "include", "tloam_hip.h")]
+HEADERS = ["tl_common.hpp", "tl_forms.hpp", "tl_grid_plan.hpp", "tl_scan.hpp", "tl_se3.hpp", "tl_knn.hpp", "tl_walk.hpp", "tl_voxel.hpp", "tl_ctx.hpp", "tl_step.hpp", "tl_finish.hpp", "tl_prep.hpp", "tl_seg.hpp", "tl_extend_host.hpp", "tl_free_box.hpp", os.path.join("..", "..", "include", "tloam_hip.h")]
 
 
 def _hipcc():

@@ -78,7 +78,7 @@ int feature_pca_run(tloam_ctx* c, const tloam_feature_config& cfg, size_t n, Fea
 int feature_select_launch(tloam_ctx* c, const tloam_feature_config& cfg, size_t n, FeatBuffers& F, const FeatArgs& A) {
   hipError_t e = hipSuccess;
   if ((e = F.flags.reserve(n + 1)) == hipSuccess && (e = F.scan.reserve(n + 1)) == hipSuccess &&
-      (e = F.scan_tmp.reserve(scan_tmp_elems(n + 1))) == hipSuccess && (e = F.f2.reserve(2 * n)) == hipSuccess &&
+      (e = F.scan_tmp.reserve(scan_scratch_elems(n + 1))) == hipSuccess && (e = F.f2.reserve(2 * n)) == hipSuccess &&
       (e = F.gf.reserve(2 * n)) == hipSuccess && (e = F.out.reserve(3 * n + 2)) == hipSuccess &&
       (e = F.idx2.reserve(2 * n)) == hipSuccess && (e = F.gi.reserve(2 * n)) == hipSuccess &&
       (e = F.bkt.reserve(2 * n)) == hipSuccess && (e = F.pos.reserve(2 * n)) == hipSuccess &&

@@ -47,7 +47,7 @@ int wait_segment(tloam_ctx* c, const unsigned long long* seg, unsigned long long
   }
 }
 // After a host synchronisation: did a kernel of this context give up one of its bounded in-launch waits?  The single-pass scans
-// (tl_nn.hip scan1p_tile) and k_vox_emit's look-back (tl_submap.hip) spin on blocks of their own launch, which is only safe
+// (tl_scan.hpp scan1p_tile) and k_vox_emit's look-back (tl_submap.hip) spin on blocks of their own launch, which is only safe
 // while all of them are resident at once; the host only picks those forms where the device's CU count says they are, and
 // should that ever be wrong (a device shared with long-running kernels) the wait runs out after ~1 s, the kernel raises a word
 // in pinned memory and finishes with garbage.  Here the context is switched to the forms that wait for nothing (multi-launch
@@ -173,21 +173,19 @@ void reduce_box_rows(const double* box_rows, double boxes[kKinds][6]) {
     }
   }
 }
-// cells per target point a kind's table may have before its cell grows (never below 16 Ki cells); measured at 16 / 32 / 64:
-// profiles/grid_tables_time.json
-constexpr double kGridCellsPerPoint = 32.0;
+// bounds -> plan -> reserve -> launch.  What a build sizes, lays out, reserves and scans with is tl_grid_plan.hpp's (DESIGN.md
+// section 4, "How a grid's tables are planned"); here the plan is fed, its buffers are held, and its launches go out.
 // known_boxes: the clouds' bounds are already on the host (targets: taken at set_target) -- no launch, no wait
 int build_grids_over(tloam_ctx* c, GridBuffers& G, const double radius[kKinds], const CloudRef clouds[kKinds],
                      GridView out[kKinds], const double (*known_boxes)[6], FrameInitHook* frame) {
   GridSet gs;
   memset(&gs, 0, sizeof(gs));
-  size_t tgt_total = 0;
+  GridPlanIn in;
   for (int k = 0; k < kKinds; ++k) {
-    const bool use = radius[k] > 0.0 && clouds[k].n > 0;
     gs.tx[k] = clouds[k].x; gs.ty[k] = clouds[k].y; gs.tz[k] = clouds[k].z;
-    gs.n[k] = use ? (int)clouds[k].n : 0;
-    gs.tgt_off[k] = (int)tgt_total;
-    tgt_total += (size_t)gs.n[k];
+    in.n[k] = (long long)clouds[k].n;
+    in.radius[k] = radius[k];
+    gs.n[k] = grid_kind_built(in.radius[k], in.n[k]) ? (int)clouds[k].n : 0;   // (the clouds the box launch looks at)
   }
   double boxes[kKinds][6];
   if (known_boxes) {
@@ -199,114 +197,55 @@ int build_grids_over(tloam_ctx* c, GridBuffers& G, const double radius[kKinds], 
     HIPC(c, hipStreamSynchronize(c->stream));
     reduce_box_rows(c->h_bbox, boxes);
   }
+  for (int k = 0; k < kKinds; ++k)
+    for (int a = 0; a < 3; ++a) { in.lo[k][a] = boxes[k][a]; in.hi[k][a] = boxes[k][3 + a]; }
   // (A DIRECT set keeps its rows in the search's own order, which follows the query tiles and with them the grids' dimensions:
   //  a context whose caps admit one -- more rows than the quad search takes -- keeps the radius-sized cells, so that such a
   //  frame's sums are added in the order they always were.  Compacted sets are in slot order whatever the grids look like.)
   long long caps = 0;
   for (int k = 0; k < kKinds; ++k) caps += std::max(0, kind_maxnum(c->cfg, k));
-  const bool sparse_ok = caps <= kQuadLimit;
-  long long cell_total = 0;
+  in.sparse_ok = caps <= kQuadLimit;
+  in.device_cus = c->device_cus;
+  in.single_pass_allowed = !c->no_scan_1p;
+  const GridPlan P = plan_grids(in);
+
+  const GridReservation R = grid_reservation(P, GridCaps{G.cell_start.cap, G.cell_cnt.cap, G.cell_cnt32.cap});
+  auto hold = [&](auto& buf, const GridWant& w) {
+    return w.n == 0 ? hipSuccess : w.zeroed ? buf.reserve_zeroed(w.n, c->stream) : buf.reserve(w.n);
+  };
+  HIPC(c, hold(G.gp, R.gp)); HIPC(c, hold(G.cell_of_pt, R.cell_of_pt)); HIPC(c, hold(G.rank_of_pt, R.rank_of_pt));
+  HIPC(c, hold(G.cell_start, R.cell_start));
+  HIPC(c, hold(G.cell_cnt32, R.cell_cnt32)); HIPC(c, hold(G.cell_scan32, R.cell_scan32)); HIPC(c, hold(G.totals32, R.totals32));
+  HIPC(c, hold(G.cell_cnt, R.cell_cnt));
+  HIPC(c, hold(G.scan1p, R.scan1p));
+  HIPC(c, hold(G.cell_scan, R.cell_scan)); HIPC(c, hold(G.scan_tmp, R.scan_tmp));
+
+  tloam_grid_info I;   // (published once nothing in front of the build's first launch can fail any more)
+  memset(&I, 0, sizeof(I));
+  I.scan_path = (int)P.scan;
+  I.table_elem_bytes = P.elem_bytes;
   for (int k = 0; k < kKinds; ++k) {
-    const double* lo = boxes[k];
-    const double* hi = boxes[k] + 3;
+    const GridPlan::Kind& pk = P.k[k];
+    gs.n[k] = pk.n;
+    gs.tgt_off[k] = pk.tgt_off;
+    gs.cell_base[k] = pk.cell_base;
+    gs.ncell[k] = pk.ncell;
+    gs.inv_cell[k] = pk.inv_cell;
     GridView& g = out[k];
     memset(&g, 0, sizeof(g));
-    // (a cloud without a single finite point has no bounds -- the rows come back as they were initialised, lo > hi -- and
-    //  nothing to search: no grid, like an empty cloud.  Sizing a cell table from such a box was a GPU memory fault until
-    //  round 5: tests/tools/fuzz_call_order.py, a one-point cloud whose point is NaN)
-    if (gs.n[k] > 0 && !(lo[0] <= hi[0] && lo[1] <= hi[1] && lo[2] <= hi[2])) gs.n[k] = 0;
-    if (gs.n[k] == 0) { gs.ncell[k] = 0; gs.dim[k][0] = gs.dim[k][1] = gs.dim[k][2] = 1; gs.inv_cell[k] = 1.0; continue; }
-    double cell = radius[k] * (1.0 + 1e-6);  // every target within `radius` of a query lies in its 27 cells
-    // ... and any larger cell does as well (the walk covers the ball, the search is exact k-NN): a table is bounded by 4e6
-    // cells, and a SPARSE kind's by kGridCellsPerPoint cells per point -- 1500 sphere targets over a street's volume were 42 %
-    // of a frame's table bytes.  The bound trades table bytes against candidates per query, never results.
-    const double sparse_cap = sparse_ok ? std::max(16384.0, kGridCellsPerPoint * (double)gs.n[k]) : 4.0e6;
-    double dims[3];
-    for (;;) {
-      double cells = 1.0;
-      for (int a = 0; a < 3; ++a) {
-        dims[a] = floor((hi[a] - lo[a]) / cell) + 1.0;
-        cells *= dims[a];
-      }
-      if (cells <= 4.0e6 && cells <= sparse_cap) break;
-      cell *= 1.25;
-    }
-    g.cell = cell;
-    g.inv_cell = 1.0 / cell;
-    long long ncell = 1;
-    for (int a = 0; a < 3; ++a) {
-      g.org[a] = lo[a];
-      g.dim[a] = (int)dims[a];
-      ncell *= g.dim[a];
-      gs.org[k][a] = lo[a];
-      gs.dim[k][a] = g.dim[a];
-    }
-    g.n = gs.n[k];
-    gs.inv_cell[k] = g.inv_cell;
-    gs.ncell[k] = ncell;
-    cell_total += ncell;
+    g.gp = G.gp.p + pk.tgt_off;
+    g.cell_start = G.cell_start.p + pk.start_base;
+    for (int a = 0; a < 3; ++a) { gs.org[k][a] = pk.org[a]; gs.dim[k][a] = pk.dim[a]; }
+    if (pk.n == 0) continue;   // (no grid: an empty view)
+    g.cell = pk.cell;
+    g.inv_cell = pk.inv_cell;
+    g.n = pk.n;
+    I.n[k] = pk.n;
+    I.ncell[k] = pk.ncell;
+    I.cell[k] = pk.cell;
+    for (int a = 0; a < 3; ++a) { g.org[a] = pk.org[a]; g.dim[a] = I.dim[k][a] = pk.dim[a]; }
   }
-  const size_t nc = (size_t)std::max<long long>(cell_total, 1);
-  // Which scan the table takes decides its layout.  The frame-size path (32-bit tables) starts kind k's ncell + 1 entries on a
-  // multiple of 4, in the histogram, the scan and cell_start alike: 16-byte accesses, and the terminator falls out of the scan.
-  // Everywhere else the kinds' cells are packed (cell_base[k] = the cells in front) and cell_start carries one terminator per
-  // kind, so its entries of kind k sit k places further on.
-  long long n_tab = 0;   // entries of the padded table
-  for (int k = 0; k < kKinds; ++k) n_tab += (gs.ncell[k] + 1 + 3) & ~3ll;
-  const bool single_pass = !c->no_scan_1p && scan_1p_applies(nc + 1, c->device_cus);
-  const int tiles = (cell_total == 0 || single_pass) ? 0 : grid_table_tiles((size_t)n_tab);
-  {
-    long long at = 0;
-    for (int k = 0; k < kKinds; ++k) {
-      gs.cell_base[k] = at;
-      at += tiles > 0 ? ((gs.ncell[k] + 1 + 3) & ~3ll) : gs.ncell[k];
-    }
-  }
-  HIPC(c, G.gp.reserve(std::max<size_t>(tgt_total, 1))); HIPC(c, G.cell_of_pt.reserve(std::max<size_t>(tgt_total, 1)));
-  HIPC(c, G.rank_of_pt.reserve(tgt_total + 1));
-  // The cell count follows the bounding boxes, which change from frame to frame: a table that has to grow does so with
-  // room to spare (a re-allocation inside scanMatching costs ~0.7 ms -- three times the frame)
-  // The cell histogram of either width is all-zero between builds (the launch that scans it re-zeroes what a build used):
-  // only a (re)allocation has to be cleared
-  if (tiles > 0) {
-    const size_t nt = (size_t)n_tab;
-    const size_t nt_res = (nt > G.cell_cnt32.cap || nt > G.cell_start.cap) ? 2 * nt + 64 : nt;
-    HIPC(c, G.cell_start.reserve(nt_res));
-    HIPC(c, G.cell_cnt32.reserve_zeroed(nt_res, c->stream));
-    HIPC(c, G.cell_scan32.reserve(nt_res));
-    HIPC(c, G.totals32.reserve(1024));
-  } else {
-    const size_t nc_res = (nc + 1 > G.cell_cnt.cap || nc + kKinds + 1 > G.cell_start.cap) ? 2 * nc + 64 : nc;
-    HIPC(c, G.cell_start.reserve(nc_res + kKinds + 1));
-    HIPC(c, G.cell_cnt.reserve_zeroed(nc_res + 1, c->stream));
-    if (single_pass) {
-      HIPC(c, G.scan1p.reserve_zeroed(scan_1p_ctl_elems(nc_res + 1), c->stream));   // (control words: zero between launches)
-    } else {
-      HIPC(c, G.cell_scan.reserve(nc_res + 1));
-      HIPC(c, G.scan_tmp.reserve(scan_tmp_elems(nc_res + 1)));
-    }
-  }
-  for (int k = 0; k < kKinds; ++k) {
-    out[k].gp = G.gp.p + gs.tgt_off[k];
-    out[k].cell_start = G.cell_start.p + gs.cell_base[k] + (tiles > 0 ? 0 : k);
-  }
-  tloam_grid_info I;   // (published once nothing in front of the build's first launch can fail any more)
-  {
-    memset(&I, 0, sizeof(I));
-    for (int k = 0; k < kKinds; ++k) {
-      if (gs.ncell[k] == 0) continue;
-      for (int a = 0; a < 3; ++a) I.dim[k][a] = gs.dim[k][a];
-      I.n[k] = gs.n[k];
-      I.ncell[k] = gs.ncell[k];
-      I.cell[k] = out[k].cell;
-    }
-    I.scan_path = cell_total == 0 ? TLOAM_GRID_SCAN_NONE
-                  : single_pass   ? TLOAM_GRID_SCAN_SINGLE_PASS
-                  : tiles > 0     ? TLOAM_GRID_SCAN_TILES
-                  : nc + 1 <= 16384 ? TLOAM_GRID_SCAN_SMALL : TLOAM_GRID_SCAN_GENERIC;
-    I.table_elem_bytes = cell_total == 0 ? 0 : tiles > 0 ? 4 : 8;
-  }
-  if (cell_total == 0) { c->grid_info = I; return TLOAM_OK; }
+  if (P.scan == GridScan::NONE) { c->grid_info = I; return TLOAM_OK; }
   if (frame) {  // the start of the scan_match rides on the first launch (the query-tile histogram is sized by the grids)
     const size_t ntiles = (size_t)build_tile_count(out, frame->fi.slot_off);
     const int rc = reserve_tile_hist(c, ntiles, /*frame_start=*/true);
@@ -316,38 +255,42 @@ int build_grids_over(tloam_ctx* c, GridBuffers& G, const double radius[kKinds], 
     frame->consumed = true;
   }
   c->grid_info = I;
+  const size_t n_hist = (size_t)P.cell_total + 1;   // entries of the packed histogram
   const bool stamp = frame && c->hs_entry > 0.0;   // (TLOAM_HOST_STAMPS: when the frame's FIRST launch went out / had been issued)
   if (stamp) c->hs[5] += host_now_us() - c->hs_entry;
-  if (tiles > 0) launch_grid_count_all(gs, G.cell_cnt32.p, G.cell_of_pt.p, G.rank_of_pt.p, c->stream, frame);
+  if (P.scan == GridScan::TILES) launch_grid_count_all(gs, G.cell_cnt32.p, G.cell_of_pt.p, G.rank_of_pt.p, c->stream, frame);
   else launch_grid_count_all(gs, G.cell_cnt.p, G.cell_of_pt.p, G.rank_of_pt.p, c->stream, frame);
   if (stamp) c->hs[6] += host_now_us() - c->hs_entry;
-  if (single_pass) {
-    // 1 M-class tables: count | scan + finalize in ONE single-pass launch | scatter (three launches and one pass over the table
-    // less than tile scan + scan of the totals + add + finalize)
-    const QueryBinRide* qbin = nullptr;
-    if (frame && frame->qbin) {
-      // the query sort's buffers, sized exactly as the sort itself will ask for them (nothing may be re-allocated in between)
-      const int rc = reserve_query_sort(c, out);
-      if (rc != TLOAM_OK) return rc;
-      frame->qbin->tile_of_slot = c->tile_of_slot.p;
-      frame->qbin->rank_in_tile = c->tile_fill.p;
-      frame->qbin->tile_cnt = c->tile_cnt.p;
-      // (the frame's start, riding on the first launch above, zeroes the histogram it was handed: the same array only if the
-      //  reservation just made did not move it)
-      if (frame->fi.tile_cnt == c->tile_cnt.p) { qbin = frame->qbin; frame->qbin_done = true; }
+  switch (P.scan) {
+    case GridScan::NONE: break;
+    case GridScan::SINGLE_PASS: {   // count | scan + finalize in ONE single-pass launch | scatter
+      const QueryBinRide* qbin = nullptr;
+      if (frame && frame->qbin) {
+        // the query sort's buffers, sized exactly as the sort itself will ask for them (nothing may be re-allocated in between)
+        const int rc = reserve_query_sort(c, out);
+        if (rc != TLOAM_OK) return rc;
+        frame->qbin->tile_of_slot = c->tile_of_slot.p;
+        frame->qbin->rank_in_tile = c->tile_fill.p;
+        frame->qbin->tile_cnt = c->tile_cnt.p;
+        // (the frame's start, riding on the first launch above, zeroes the histogram it was handed: the same array only if the
+        //  reservation just made did not move it)
+        if (frame->fi.tile_cnt == c->tile_cnt.p) { qbin = frame->qbin; frame->qbin_done = true; }
+      }
+      launch_grid_scan_finalize_scatter_1p(gs, G.cell_cnt.p, n_hist, G.cell_start.p, G.scan1p.p, c->h_fault.dev + kFaultScan1p, G.cell_of_pt.p,
+                                           G.rank_of_pt.p, G.gp.p, c->stream, qbin, out);
+      break;
     }
-    launch_grid_scan_finalize_scatter_1p(gs, G.cell_cnt.p, nc + 1, G.cell_start.p, G.scan1p.p, c->h_fault.dev + kFaultScan1p, G.cell_of_pt.p,
-                                         G.rank_of_pt.p, G.gp.p, c->stream, qbin, out);
-    return TLOAM_OK;
-  }
-  if (tiles > 0) {
-    launch_grid_scan_tiles(G.cell_cnt32.p, G.cell_scan32.p, (size_t)n_tab, G.totals32.p, c->stream);
-    launch_grid_finalize_scatter_all(gs, G.cell_scan32.p, G.totals32.p, tiles, n_tab, G.cell_start.p, G.cell_of_pt.p, G.rank_of_pt.p,
-                                     G.gp.p, c->stream);
-  } else {
-    launch_exclusive_scan_u64(G.cell_cnt.p, G.cell_scan.p, nc + 1, G.scan_tmp.p, c->stream);
-    launch_grid_finalize_all(gs, G.cell_scan.p, G.cell_start.p, G.cell_cnt.p, c->stream);
-    launch_grid_scatter_all(gs, G.cell_of_pt.p, G.cell_scan.p, G.rank_of_pt.p, G.gp.p, c->stream);
+    case GridScan::TILES:   // count | tile scan | finalize + scatter, 32-bit tables
+      launch_grid_scan_tiles(G.cell_cnt32.p, G.cell_scan32.p, (size_t)P.n_tab, G.totals32.p, c->stream);
+      launch_grid_finalize_scatter_all(gs, G.cell_scan32.p, G.totals32.p, P.tiles, P.n_tab, G.cell_start.p, G.cell_of_pt.p, G.rank_of_pt.p,
+                                       G.gp.p, c->stream);
+      break;
+    case GridScan::SMALL:
+    case GridScan::GENERIC:   // count | the one-block or the multi-launch scan | finalize | scatter
+      launch_exclusive_scan_u64(G.cell_cnt.p, G.cell_scan.p, n_hist, G.scan_tmp.p, c->stream);
+      launch_grid_finalize_all(gs, G.cell_scan.p, G.cell_start.p, G.cell_cnt.p, c->stream);
+      launch_grid_scatter_all(gs, G.cell_of_pt.p, G.cell_scan.p, G.rank_of_pt.p, G.gp.p, c->stream);
+      break;
   }
   return TLOAM_OK;
 }

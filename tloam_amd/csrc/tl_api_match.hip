@@ -80,7 +80,7 @@ int ensure_common(tloam_ctx* c) {
 // and scattered them out of bounds -- a GPU memory fault or a silently wrong query order on the first large frame of a context,
 // whenever the block was not fresh; found by tests/tools/fuzz_call_order.py.)
 int reserve_tile_hist(tloam_ctx* c, size_t ntiles, bool frame_start, size_t* room) {
-  const size_t n = (ntiles + 1 > c->tile_cnt.cap || ntiles + 1 > c->tile_scan.cap) ? 2 * ntiles + 64 : ntiles;
+  const size_t n = grown(ntiles, ntiles + 1 > c->tile_cnt.cap || ntiles + 1 > c->tile_scan.cap);
   if (frame_start) HIPC(c, c->tile_cnt.reserve(n + 1));
   else HIPC(c, c->tile_cnt.reserve_zeroed(n + 1, c->stream));
   HIPC(c, c->tile_scan.reserve(n + 1));
@@ -97,10 +97,10 @@ int reserve_query_sort(tloam_ctx* c, const GridView grids[kKinds]) {
   if (rc != TLOAM_OK) return rc;
   HIPC(c, c->tile_fill.reserve(std::max<size_t>((size_t)nt_res, (size_t)n_slots + 1))  /* rank of every slot inside its tile */); HIPC(c, c->tile_of_slot.reserve(n_slots + 1));
   HIPC(c, c->qrec.reserve(n_slots + 1));
-  HIPC(c, c->scan_tmp.reserve(scan_tmp_elems(std::max(nt_res + 1, n_slots + 1))));
-  c->scan1p_q_use = !c->no_scan_1p && scan_1p_applies(ntiles + 1, c->device_cus);
+  HIPC(c, c->scan_tmp.reserve(scan_scratch_elems(std::max(nt_res + 1, n_slots + 1))));
+  c->scan1p_q_use = scan_path(ntiles + 1, c->device_cus, !c->no_scan_1p).path == ScanPath::SINGLE_PASS;
   // (the control words of the single-pass scan read zero between launches: only a (re)allocation has to be cleared)
-  if (c->scan1p_q_use) HIPC(c, c->scan1p_q.reserve_zeroed(scan_1p_ctl_elems(nt_res + 1), c->stream));
+  if (c->scan1p_q_use) HIPC(c, c->scan1p_q.reserve_zeroed(scan_ctl_elems(nt_res + 1), c->stream));
   return TLOAM_OK;
 }
 BuildParams build_params(const tloam_ctx* c) {
@@ -842,7 +842,7 @@ int tloam_sm_begin(tloam_ctx* c, const double predict[16], const double* omega3)
   HIPC(c, c->sx.reserve(ns)); HIPC(c, c->sy.reserve(ns)); HIPC(c, c->sz.reserve(ns)); HIPC(c, c->w_src.reserve(ns));
   HIPC(c, c->raw.reserve(ns * 8));
   HIPC(c, c->flags.reserve(ns + 1)); HIPC(c, c->scan.reserve(ns + 1));
-  HIPC(c, c->scan_tmp.reserve(scan_tmp_elems(ns + 1)));
+  HIPC(c, c->scan_tmp.reserve(scan_scratch_elems(ns + 1)));
   c->sv.sx = c->sx.p; c->sv.sy = c->sy.p; c->sv.sz = c->sz.p; c->sv.w_src = c->w_src.p;
   c->sv.raw = c->raw.p;
   c->sv.flags = c->flags.p; c->sv.scan = c->scan.p;

@@ -16,11 +16,13 @@
 
 #include "../../include/tloam_hip.h"
 #include "tl_forms.hpp"
+#include "tl_grid_plan.hpp"
 #include "tl_se3.hpp"
 
 namespace tl {
 
 constexpr int kKinds = 4;
+static_assert(kKinds == kGridKinds, "tl_grid_plan.hpp plans one grid per kind");
 constexpr int kAccN = 28;        // 21 upper-triangular H + 6 g + 1 cost
 constexpr int kAccStride = 32;   // padded row of the partials buffer
 constexpr int kReduceBuf = 48;   // the all-reduced buffer: 28 used + per-kind tail
@@ -244,8 +246,7 @@ struct ScanTemp;  // opaque
 // AoS double[3] -> SoA, for a sub-range
 void launch_aos_to_soa(const double* aos, size_t n, double* x, double* y, double* z, hipStream_t s);
 
-// exclusive scan of u64 values; tmp must hold scan_tmp_elems(n) u64
-size_t scan_tmp_elems(size_t n);
+// exclusive scan of u64 values (tl_scan.hip); tmp must hold scan_scratch_elems(n) u64 (tl_grid_plan.hpp)
 // gate != nullptr: a device flag; the launches do nothing where it reads 0
 void launch_exclusive_scan_u64(const unsigned long long* in, unsigned long long* out, size_t n,
                                unsigned long long* tmp, hipStream_t s, const int* gate = nullptr);
@@ -258,8 +259,8 @@ struct GridSet {
   const double* tz[kKinds];
   int n[kKinds];
   int tgt_off[kKinds];          // offset of the kind's points in the concatenated point arrays
-  long long cell_base[kKinds];  // offset of the kind's cells in the concatenated cell arrays (cell_start: + kind, except on the
-                                // frame-size path -- see launch_grid_finalize_scatter_all)
+  long long cell_base[kKinds];  // offset of the kind's cells in the concatenated cell arrays (cell_start: + kind in the packed
+                                // layout -- GridPlan::Kind::start_base, tl_grid_plan.hpp)
   long long ncell[kKinds];
   double org[kKinds][3];
   double inv_cell[kKinds];
@@ -374,26 +375,23 @@ void launch_grid_count_all(const GridSet& gs, T* cell_cnt, int* cell_of_pt, int*
                            const FrameInitHook* frame = nullptr);
 void launch_grid_finalize_all(const GridSet& gs, const unsigned long long* cell_scan, int* cell_start,
                               unsigned long long* cell_cnt /* re-zeroed */, hipStream_t s);
-// medium-size scans: tile-local scan only (returns the tile count, 0 = not applicable), the consumer adds the tiles' offsets
-// itself
+// medium-size scans (scan_path: TILES): tile-local scan only (returns the tile count, 0 = not applicable), the consumer adds the
+// tiles' offsets itself
 int scan_tiles_only(const unsigned long long* in, unsigned long long* out, size_t n, unsigned long long* totals, hipStream_t s,
                     const int* gate = nullptr);
-// The frame-size grid build (a table of more than 16 Ki entries and at most 1024 scan tiles, grid_table_tiles(n) > 0): 32-bit
+// The frame-size grid build (GridScan::TILES: a padded table of more than 16 Ki entries and at most 1024 scan tiles): 32-bit
 // histogram, tile-local scan that leaves the histogram empty again, then finalize + scatter in ONE launch -- three launches per
 // build.  The table's layout differs from the other paths': kind k's ncell + 1 entries start at cell_base[k], a MULTIPLE OF 4,
 // in the histogram, the scan and cell_start alike (n_tab = the padded total, a multiple of 4; totals: 1024 entries).
-int grid_table_tiles(size_t n_tab);
 void launch_grid_scan_tiles(unsigned* cell_cnt /* re-zeroed */, unsigned* cell_scan, size_t n_tab, unsigned* totals, hipStream_t s);
 void launch_grid_finalize_scatter_all(const GridSet& gs, const unsigned* cell_scan, const unsigned* totals, int tiles, long long n_tab,
                                       int* cell_start, const int* cell_of_pt, const int* rank_of_pt, double4* gp, hipStream_t s);
 void launch_grid_scatter_all(const GridSet& gs, const int* cell_of_pt, const unsigned long long* cell_scan,
                              const int* rank_of_pt, double4* gp, hipStream_t s);
 // large tables (more than 1024 scan tiles: the 1 M-class frames): ONE single-pass launch scans the histogram, writes cell_start
-// and re-zeroes the histogram (no scan array), then the scatter -- count | scan + finalize | scatter.  ctl: scan_1p_ctl_elems(n)
-// words, zero when allocated (k_scan_1p, tl_nn.hip).  Only where every block of the launch is resident at once on THIS device
-// (scan_1p_applies: tiles <= device_cus); fault: pinned host word the kernel raises if its bounded look-back times out
-size_t scan_1p_ctl_elems(size_t n);
-bool scan_1p_applies(size_t n, int device_cus);
+// and re-zeroes the histogram (no scan array), then the scatter -- count | scan + finalize | scatter.  ctl: scan_ctl_elems(n)
+// words, zero when allocated (k_scan_1p, tl_scan.hip).  Only where every block of the launch is resident at once on THIS device
+// (scan_path: SINGLE_PASS); fault: pinned host word the kernel raises if its bounded look-back times out
 void launch_scan_counts_1p(const unsigned long long* in, unsigned long long* out, size_t n, unsigned long long* ctl, unsigned* fault,
                            hipStream_t s);
 void launch_grid_scan_finalize_scatter_1p(const GridSet& gs, unsigned long long* cell_cnt, size_t ncells_plus_1, int* cell_start,
@@ -402,8 +400,8 @@ void launch_grid_scan_finalize_scatter_1p(const GridSet& gs, unsigned long long*
 
 // start-of-frame initialisation, one launch
 // K1+K2: per source slot kNN + fit + gates -> raw records + flags
-// scan1p_ctl: control words of the single-pass scan of the query-sort histogram (large frames; the caller has checked
-// scan_1p_applies), or null: the multi-launch scan; scan1p_fault: see launch_scan_counts_1p
+// scan1p_ctl: control words of the single-pass scan of the query-sort histogram (large frames; the caller has asked
+// scan_path), or null: the multi-launch scan; scan1p_fault: see launch_scan_counts_1p
 // direct_cv != null: the search writes the DIRECT set (DirectSet) -- st is then written (x_build) where ds.set_x_build says so
 void launch_build(const SlotView& sv, const GridView grids[kKinds], const BuildParams& bp, GnState* st,
                   int* tile_of_slot, unsigned long long* tile_cnt, unsigned long long* tile_scan, int* tile_fill,

@@ -593,7 +593,7 @@ struct tloam_ctx {
   DBuf<double> fit_x, fit_y, fit_z;  // getFitnessScore scratch
   DBuf<unsigned long long> flags, scan, scan_tmp, tile_cnt, tile_scan;
   DBuf<unsigned long long> scan1p_q;   // control words of the single-pass scan of the query-sort histogram, zero when allocated
-  bool scan1p_q_use = false;           // ... and whether this frame's query sort takes it (outer_reserve: scan_1p_applies on this device)
+  bool scan1p_q_use = false;           // ... and whether this frame's query sort takes it (reserve_query_sort: scan_path on this device)
   bool grids_ahead = false;    // the search grids in `grids_next` were built over the registered targets at hand-over (tloam_set_target_frame) and are still theirs
   // ... which is also CHECKED: every path that changes a registered target cloud advances tgt_gen, the grids built ahead remember
   // the generation they were built over, and tloam_sm_begin swaps them in only if that is still the current one

@@ -25,6 +25,7 @@
 #include "tl_common.hpp"
 #include "tl_knn.hpp"
 #include "tl_finish.hpp"
+#include "tl_scan.hpp"
 
 namespace tl {
 
@@ -49,349 +50,11 @@ void launch_aos_to_soa(const double* aos, size_t n, double* x, double* y, double
 }
 
 // ================================================================================================
-//  exclusive scan of u64 (block-local scan + recursive scan of block totals + add)
+//  grid build (the scans: tl_scan.hip; what a build sizes, lays out and launches: tl_grid_plan.hpp)
 // ================================================================================================
-constexpr int kScanThreads = 256;
-constexpr int kScanItems = 8;
-constexpr int kScanTile = kScanThreads * kScanItems;   // 2048 elements per block, 512 per wave
-constexpr int kScanPer = 4;                            // consecutive elements per lane within a row
-constexpr int kScanRowElems = 64 * kScanPer;           // 256 elements = 2 KiB per wave row
-constexpr int kScanRows = kScanTile / (kScanThreads / 64) / kScanRowElems;   // rows per wave (2)
 // tuning numbers of the frame-size grid build (profiles/grid_tables_time.json has what was measured beside them)
 constexpr int kGridFinCellsPerBlock = 4096;     // table entries per finalize block: four 16-byte accesses per lane
 constexpr int kGridScatterPtsPerBlock = 256;    // points of the largest kind per scatter block: one per lane
-
-typedef unsigned long long u64x2 __attribute__((ext_vector_type(2), aligned(8)));   // (8-byte aligned: any element of a u64 array)
-typedef unsigned u32x4 __attribute__((ext_vector_type(4), aligned(16)));              // (the 32-bit tables: every row starts on 16 bytes)
-// a lane's four consecutive elements of a row, in 16-byte accesses: two for u64, ONE for 32-bit counts -- what the CU's L1 is
-// asked for is accesses per lane, not bytes (64 eight-byte loads per thread of a 16 Ki tile were half of what the single-pass
-// scans waited for)
-__device__ __forceinline__ void scan_load4(const unsigned long long* __restrict__ p, unsigned long long (&a)[4]) {
-  const u64x2* __restrict__ q = reinterpret_cast<const u64x2*>(p);
-  const u64x2 lo = q[0], hi = q[1];
-  a[0] = lo.x; a[1] = lo.y; a[2] = hi.x; a[3] = hi.y;
-}
-__device__ __forceinline__ void scan_load4(const unsigned* __restrict__ p, unsigned (&a)[4]) {
-  const u32x4 v = *reinterpret_cast<const u32x4*>(p);
-  a[0] = v.x; a[1] = v.y; a[2] = v.z; a[3] = v.w;
-}
-__device__ __forceinline__ void scan_store4(unsigned long long* __restrict__ p, unsigned long long r0, unsigned long long r1,
-                                            unsigned long long r2, unsigned long long r3) {
-  u64x2* __restrict__ q = reinterpret_cast<u64x2*>(p);
-  q[0] = u64x2{r0, r1};
-  q[1] = u64x2{r2, r3};
-}
-__device__ __forceinline__ void scan_store4(unsigned* __restrict__ p, unsigned r0, unsigned r1, unsigned r2, unsigned r3) {
-  *reinterpret_cast<u32x4*>(p) = u32x4{r0, r1, r2, r3};
-}
-// Wave-level exclusive scan of ROWS x 256 consecutive elements starting at `wbase`: lane l holds the four
-// elements 4l .. 4l+3 of each row, so a wave instruction covers 1-2 KiB (8-16 cache lines) and one shuffle scan
-// serves 256 elements.  The fully blocked layout (8-16 consecutive elements per thread) made every wave
-// instruction touch 32-64 different lines, serialised by the texture addresser: 11.9 us for a 9.4 k-element
-// scan.  Returns the wave total; out[row i, 4l + j] = ex[i] + a[i][0] + .. + a[i][j-1].
-// T: unsigned long long (flag scans, the single-pass count scans) or unsigned (the frame-size cell tables: a count never
-// exceeds 2^28 points and the four kinds of a frame share one 2^28 slot space, so every prefix fits 32 bits).
-template <int ROWS, typename T>
-__device__ __forceinline__ T wave_scan_rows(const T* __restrict__ in, size_t n, size_t wbase, int lane, T (&ex)[ROWS],
-                                            T (&a)[ROWS][kScanPer]) {
-  static_assert(kScanPer == 4, "a lane's elements of a row are loaded in 16-byte accesses");
-  if (wbase + (size_t)ROWS * kScanRowElems <= n) {
-    // a wave whose rows all lie inside the array (every wave but the last)
-#pragma unroll
-    for (int i = 0; i < ROWS; ++i) scan_load4(in + wbase + (size_t)i * kScanRowElems + (size_t)lane * kScanPer, a[i]);
-  } else {
-#pragma unroll
-    for (int i = 0; i < ROWS; ++i)
-#pragma unroll
-      for (int j = 0; j < kScanPer; ++j) {  // unconditional (clamped) loads: all in flight together
-        const size_t idx = wbase + (size_t)i * kScanRowElems + (size_t)lane * kScanPer + j;
-        const T x = in[idx < n ? idx : n - 1];
-        a[i][j] = idx < n ? x : T(0);
-      }
-  }
-  T carry = 0;
-#pragma unroll
-  for (int i = 0; i < ROWS; ++i) {
-    T s = 0;
-#pragma unroll
-    for (int j = 0; j < kScanPer; ++j) s += a[i][j];
-    T inc = s;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const T t = __shfl_up(inc, off, 64);
-      if (lane >= off) inc += t;
-    }
-    ex[i] = carry + inc - s;
-    carry += __shfl(inc, 63, 64);
-  }
-  return carry;
-}
-template <int ROWS, typename T>
-__device__ __forceinline__ void wave_store_rows(T* __restrict__ out, size_t n, size_t wbase, int lane, T add, const T (&ex)[ROWS],
-                                                const T (&a)[ROWS][kScanPer]) {
-  if (wbase + (size_t)ROWS * kScanRowElems <= n) {   // (as the loads: 16-byte stores)
-#pragma unroll
-    for (int i = 0; i < ROWS; ++i) {
-      const T r0 = add + ex[i], r1 = r0 + a[i][0], r2 = r1 + a[i][1], r3 = r2 + a[i][2];
-      scan_store4(out + wbase + (size_t)i * kScanRowElems + (size_t)lane * kScanPer, r0, r1, r2, r3);
-    }
-    return;
-  }
-#pragma unroll
-  for (int i = 0; i < ROWS; ++i) {
-    T run = add + ex[i];
-#pragma unroll
-    for (int j = 0; j < kScanPer; ++j) {
-      const size_t idx = wbase + (size_t)i * kScanRowElems + (size_t)lane * kScanPer + j;
-      if (idx < n) out[idx] = run;
-      run += a[i][j];
-    }
-  }
-}
-// the rows a wave has just scanned, left all-zero (a histogram emptied for the next build while its lines are in hand)
-template <int ROWS, typename T>
-__device__ __forceinline__ void wave_zero_rows(T* __restrict__ p, size_t n, size_t wbase, int lane) {
-  if (wbase + (size_t)ROWS * kScanRowElems <= n) {
-#pragma unroll
-    for (int i = 0; i < ROWS; ++i) scan_store4(p + wbase + (size_t)i * kScanRowElems + (size_t)lane * kScanPer, T(0), T(0), T(0), T(0));
-    return;
-  }
-#pragma unroll
-  for (int i = 0; i < ROWS; ++i)
-#pragma unroll
-    for (int j = 0; j < kScanPer; ++j) {
-      const size_t idx = wbase + (size_t)i * kScanRowElems + (size_t)lane * kScanPer + j;
-      if (idx < n) p[idx] = T(0);
-    }
-}
-
-// tile-local exclusive scans + the tiles' totals.  REZERO: the tile of `in` is left all-zero once it has been read -- the cell
-// histogram of a grid build, empty again for the next one (`in` is then written through and promises no aliasing).
-template <typename T, bool REZERO> struct ScanIn { typedef const T* __restrict__ type; };
-template <typename T> struct ScanIn<T, true> { typedef T* type; };
-template <typename T, bool REZERO>
-__global__ __launch_bounds__(kScanThreads) void k_scan_tile(typename ScanIn<T, REZERO>::type in, T* __restrict__ out, size_t n,
-                                                            T* __restrict__ tile_total, const int* __restrict__ gate) {
-  __shared__ T wave_tot[kScanThreads / 64];
-  if (gate && *gate == 0) return;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const size_t wbase = (size_t)blockIdx.x * kScanTile + (size_t)wave * (kScanRows * kScanRowElems);
-  T ex[kScanRows], a[kScanRows][kScanPer];
-  const T tot = wave_scan_rows<kScanRows>(in, n, wbase, lane, ex, a);
-  if constexpr (REZERO) wave_zero_rows<kScanRows>(in, n, wbase, lane);
-  if (lane == 0) wave_tot[wave] = tot;
-  __syncthreads();
-  T wave_off = 0;
-  for (int w = 0; w < wave; ++w) wave_off += wave_tot[w];
-  wave_store_rows<kScanRows>(out, n, wbase, lane, wave_off, ex, a);
-  if (threadIdx.x == kScanThreads - 1) tile_total[blockIdx.x] = wave_off + tot;
-}
-// exclusive prefix of (<= 1024) tile totals into LDS, by a block of 256 threads: 4 consecutive tiles per thread.  Ends with a
-// barrier: toff[] may be read on return.
-template <typename T>
-__device__ __forceinline__ void tile_offsets_to_lds(const T* __restrict__ totals, int tiles, T (&toff)[1024], T (&wtot)[4]) {
-  const int t0 = threadIdx.x * 4;
-  T v[4], run = 0;
-#pragma unroll
-  for (int u = 0; u < 4; ++u) { v[u] = (t0 + u < tiles) ? totals[t0 + u] : T(0); run += v[u]; }
-  T incl = run;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const T o = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += o;
-  }
-  if (lane == 63) wtot[wave] = incl;
-  __syncthreads();
-  T pre = incl - run;
-  for (int w = 0; w < wave; ++w) pre += wtot[w];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) { toff[t0 + u] = pre; pre += v[u]; }
-  __syncthreads();
-}
-__global__ __launch_bounds__(kScanThreads) void k_scan_add(unsigned long long* __restrict__ out, size_t n,
-                                                           const unsigned long long* __restrict__ tile_off,
-                                                           const int* __restrict__ gate) {
-  if (gate && *gate == 0) return;
-  const unsigned long long add = tile_off[blockIdx.x];
-  const size_t base = (size_t)blockIdx.x * kScanTile + threadIdx.x;
-#pragma unroll
-  for (int i = 0; i < kScanItems; ++i)
-    if (base + (size_t)i * kScanThreads < n) out[base + (size_t)i * kScanThreads] += add;
-}
-// small inputs (<= 16 Ki elements, e.g. the flag scan of a KITTI-size frame): ONE block of 1024 threads, a
-// single pass with every load in flight at once
-constexpr int kSmallThreads = 1024;
-constexpr int kSmallRows = 4;                                   // 1024 elements per wave
-constexpr int kSmallTile = (kSmallThreads / 64) * kSmallRows * kScanRowElems;  // 16384
-__global__ __launch_bounds__(kSmallThreads) void k_scan_small(const unsigned long long* __restrict__ in,
-                                                              unsigned long long* __restrict__ out, size_t n,
-                                                              const int* __restrict__ gate) {
-  __shared__ unsigned long long wave_tot[kSmallThreads / 64];
-  __shared__ unsigned long long carry_s;
-  if (gate && *gate == 0) return;
-  if (threadIdx.x == 0) carry_s = 0ull;
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (size_t tile0 = 0; tile0 < n; tile0 += kSmallTile) {
-    const size_t wbase = tile0 + (size_t)wave * (kSmallRows * kScanRowElems);
-    unsigned long long ex[kSmallRows], a[kSmallRows][kScanPer];
-    const unsigned long long tot = wave_scan_rows<kSmallRows>(in, n, wbase, lane, ex, a);
-    if (lane == 0) wave_tot[wave] = tot;
-    __syncthreads();
-    unsigned long long wave_off = carry_s;
-    for (int w = 0; w < wave; ++w) wave_off += wave_tot[w];
-    wave_store_rows<kSmallRows>(out, n, wbase, lane, wave_off, ex, a);
-    __syncthreads();
-    if (threadIdx.x == kSmallThreads - 1) carry_s = wave_off + tot;
-    __syncthreads();
-  }
-}
-// medium inputs: every block sums the totals of the tiles before it itself (<= 1024 loads) -- two
-// launches instead of three
-__global__ __launch_bounds__(kScanThreads) void k_scan_add_direct(unsigned long long* __restrict__ out, size_t n,
-                                                                  const unsigned long long* __restrict__ tile_total,
-                                                                  const int* __restrict__ gate) {
-  __shared__ unsigned long long red[kScanThreads / 64];
-  if (gate && *gate == 0) return;
-  unsigned long long acc = 0;
-  for (int t = threadIdx.x; t < (int)blockIdx.x; t += kScanThreads) acc += tile_total[t];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  unsigned long long add = 0;
-  for (int w = 0; w < kScanThreads / 64; ++w) add += red[w];
-  const size_t base = (size_t)blockIdx.x * kScanTile + threadIdx.x;
-#pragma unroll
-  for (int i = 0; i < kScanItems; ++i)
-    if (base + (size_t)i * kScanThreads < n) out[base + (size_t)i * kScanThreads] += add;
-}
-size_t scan_tmp_elems(size_t n) {
-  size_t total = 0;
-  while (n > 1) {
-    const size_t tiles = (n + kScanTile - 1) / kScanTile;
-    total += 2 * tiles;
-    if (tiles == 1) break;
-    n = tiles;
-  }
-  return total + 16;
-}
-void launch_exclusive_scan_u64(const unsigned long long* in, unsigned long long* out, size_t n,
-                               unsigned long long* tmp, hipStream_t s, const int* gate) {
-  if (n == 0) return;
-  const size_t tiles = (n + kScanTile - 1) / kScanTile;
-  if (n <= (size_t)kSmallTile) {
-    hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(kSmallThreads), 0, s, in, out, n, gate);
-    return;
-  }
-  unsigned long long* totals = tmp;
-  unsigned long long* totals_scan = tmp + tiles;
-  hipLaunchKernelGGL((k_scan_tile<unsigned long long, false>), dim3((unsigned)tiles), dim3(kScanThreads), 0, s, in, out, n, totals, gate);
-  if (tiles <= 1024) {
-    hipLaunchKernelGGL(k_scan_add_direct, dim3((unsigned)tiles), dim3(kScanThreads), 0, s, out, n, totals, gate);
-  } else {
-    launch_exclusive_scan_u64(totals, totals_scan, tiles, tmp + 2 * tiles, s, gate);
-    hipLaunchKernelGGL(k_scan_add, dim3((unsigned)tiles), dim3(kScanThreads), 0, s, out, n, totals_scan, gate);
-  }
-}
-
-// ---- single-pass scan of large COUNT arrays (round 4) --------------------------------------------------------------------------
-// The 1 M-class frames scan two histograms of ~3 M entries per frame (cells of the target grids, bins of the query sort): tile
-// scan + scan of the tile totals + add = three launches and two passes over the array.  Here ONE launch, one pass: a block
-// scans its tile, publishes the tile's total in a status word, looks back over the words of the blocks in front of it (a wave
-// reads 64 of them at a time) until it meets one that already carries its inclusive prefix, publishes its own, and emits its
-// elements with the prefix added.  At most one block per CU OF THIS DEVICE (scan_1p_applies looks at the context's CU count: a
-// partitioned or CU-masked part takes the multi-launch scan), so every block is resident at once and a block only ever waits
-// for blocks that are running; the wait is bounded all the same (~1 s of the wall clock, then the block raises Scan1p::fault --
-// a word in pinned host memory -- and goes on with what it has: the host discards the frame's result, switches the context to
-// the multi-launch scans and runs the frame again, tl_api.hip check_device_faults).  Status word: [63:62] 0 nothing |
-// 1 the tile's own total | 2 inclusive prefix, [61:32] the launch's epoch -- a word of an earlier launch reads as "nothing",
-// so the array is never cleared (it is zeroed when it is allocated) --, [31:0] the value: totals below 2^32, i.e. counts.
-// Tiles of 16 Ki elements (64 per thread, in registers): ~200 blocks for 3.2 M entries, all resident at once, so that the
-// look-back is three or four reads of 64 status words -- with 2 Ki tiles (1563 blocks, not all resident) the prefix crept from
-// block to block at a coherence-point round trip per hop and the launch took 52-57 us, longer than the three launches it replaced.
-constexpr int kRows1p = 16;                                                  // rows of 256 elements per wave
-constexpr int kTile1p = (kScanThreads / 64) * kRows1p * kScanRowElems;       // 16384 elements per block
-struct Scan1p {
-  unsigned long long* status;   // [tiles]
-  unsigned epoch;               // 1 .. 2^30 - 1, different from the previous launch's on the same status array
-  unsigned* fault;              // pinned host word raised when the look-back timed out (null: nobody to tell)
-};
-// returns the block's place (tile index); ex / a as wave_scan_rows leaves them, *base = sum of everything in front of this wave
-__device__ __forceinline__ int scan1p_tile(const unsigned long long* __restrict__ in, size_t n, const Scan1p& C,
-                                           unsigned long long (&ex)[kRows1p], unsigned long long (&a)[kRows1p][kScanPer],
-                                           unsigned long long* base, size_t* wbase_out) {
-  __shared__ unsigned long long wave_tot[kScanThreads / 64];
-  __shared__ unsigned long long s_prefix;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  // The block's place is its index: the launcher only uses this kernel when the grid is at most one block per CU of the
-  // device in use (scan_1p_applies), so every block is resident as soon as the device has room for it and nobody waits for a
-  // block that cannot start.  (Places handed out by an atomic counter -- the usual guard -- cost ~10 us here: ~200 returning atomics on
-  // one address are served one after the other at the memory side, ~50 ns each.)
-  const int bid = (int)blockIdx.x;
-  const size_t wbase = (size_t)bid * kTile1p + (size_t)wave * (kRows1p * kScanRowElems);
-  const unsigned long long tot = wave_scan_rows<kRows1p>(in, n, wbase, lane, ex, a);
-  if (lane == 0) wave_tot[wave] = tot;
-  __syncthreads();
-  unsigned long long wave_off = 0, block_total = 0;
-#pragma unroll
-  for (int w = 0; w < kScanThreads / 64; ++w) {
-    if (w < wave) wave_off += wave_tot[w];
-    block_total += wave_tot[w];
-  }
-  const unsigned long long tag = (unsigned long long)C.epoch << 32;
-  if (wave == 0) {
-    unsigned long long prefix = 0ull;
-    if (bid == 0) {
-      if (lane == 0) __hip_atomic_store(&C.status[0], (2ull << 62) | tag | block_total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-      if (lane == 0) __hip_atomic_store(&C.status[bid], (1ull << 62) | tag | block_total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const unsigned long long t0 = wall_clock64();
-      unsigned spins = 0;
-      for (int top = bid - 1;;) {   // lanes look at blocks top, top - 1, ..., top - 63
-        const int p = top - lane;
-        unsigned long long w = 0ull;
-        if (p >= 0) w = __hip_atomic_load(&C.status[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const bool mine = p >= 0 && ((w >> 32) & 0x3fffffffull) == (unsigned long long)C.epoch;
-        const unsigned st = mine ? (unsigned)(w >> 62) : 0u;
-        const unsigned long long have = __ballot(p < 0 || st != 0u);          // (lanes past block 0 count as ready, value 0)
-        const unsigned long long full = __ballot(p >= 0 && st == 2u);
-        // the nearest block that carries an inclusive prefix, provided every block nearer than it has published its total
-        const int first_full = full ? __ffsll((long long)full) - 1 : 64;
-        const unsigned long long need = first_full >= 63 ? ~0ull : ((2ull << first_full) - 1ull);
-        if ((have & need) != need) {   // somebody in the window is not there yet
-          if ((++spins & 63u) == 0 && wall_clock64() - t0 > 100000000ull) {   // ~1 s: a block in front never started
-            if (lane == 0 && C.fault) { __hip_atomic_store(C.fault, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); __threadfence_system(); }
-            break;
-          }
-          __builtin_amdgcn_s_sleep(1);
-          continue;
-        }
-        unsigned long long v = (p >= 0 && lane <= first_full) ? (w & 0xffffffffull) : 0ull;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-        prefix += __shfl(v, 0, 64);
-        if (first_full < 64 || top - 64 < 0) break;
-        top -= 64;
-      }
-      if (lane == 0)
-        __hip_atomic_store(&C.status[bid], (2ull << 62) | tag | (prefix + block_total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (lane == 0) s_prefix = prefix;
-  }
-  __syncthreads();
-  *base = s_prefix + wave_off;
-  *wbase_out = wbase;
-  return bid;
-}
-__global__ __launch_bounds__(kScanThreads) void k_scan_1p(const unsigned long long* __restrict__ in, unsigned long long* __restrict__ out,
-                                                          size_t n, Scan1p C) {
-  unsigned long long ex[kRows1p], a[kRows1p][kScanPer], base;
-  size_t wbase;
-  (void)scan1p_tile(in, n, C, ex, a, &base, &wbase);
-  wave_store_rows<kRows1p>(out, n, wbase, threadIdx.x & 63, base, ex, a);
-}
 // the scan of the concatenated cell histogram AND what k_grid_finalize_all does with it: cell_start of every kind (relative to the
 // kind's own point block, with its terminator), the histogram left empty for the next build.  No cell_scan array is written.
 __global__ __launch_bounds__(kScanThreads) void k_grid_scan_finalize_1p(GridSet gs, unsigned long long* __restrict__ cell_cnt, size_t n,
@@ -400,6 +63,7 @@ __global__ __launch_bounds__(kScanThreads) void k_grid_scan_finalize_1p(GridSet 
   size_t wbase;
   const int bid = scan1p_tile(cell_cnt, n, C, ex, a, &base, &wbase);
   const int lane = threadIdx.x & 63;
+  // (entry e of the packed table, a cell of kind k, is cell_start[e + k]: GridPlan::Kind::start_base, tl_grid_plan.hpp)
   if (bid == 0 && threadIdx.x < kKinds && gs.ncell[threadIdx.x] == 0)   // a kind without a grid: just its terminator
     cell_start[gs.cell_base[threadIdx.x] + threadIdx.x] = gs.n[threadIdx.x];
   typedef int int4s __attribute__((ext_vector_type(4), aligned(4)));
@@ -447,7 +111,7 @@ __global__ void k_grid_scatter_start_all(GridSet gs, const int* __restrict__ cel
                                          const int* __restrict__ rank_of_pt, double4* __restrict__ gp) {
   const int k = blockIdx.y;
   const int n = gs.n[k];
-  const long long base = gs.cell_base[k] + k;
+  const long long base = gs.cell_base[k] + k;   // (GridPlan::Kind::start_base of the packed layout, tl_grid_plan.hpp)
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     const int c = cell_of_pt[gs.tgt_off[k] + i];
     const int pos = cell_start[base + c] + rank_of_pt[gs.tgt_off[k] + i];
@@ -455,72 +119,21 @@ __global__ void k_grid_scatter_start_all(GridSet gs, const int* __restrict__ cel
         double4{gs.tx[k][i], gs.ty[k][i], gs.tz[k][i], __longlong_as_double((long long)i)};
   }
 }
-static unsigned next_scan_epoch() {   // process-wide (contexts on different host threads share it): any two launches differ
-  static std::atomic<unsigned> e{0};
-  return e.fetch_add(1u, std::memory_order_relaxed) % 0x3ffffffeu + 1u;
+// A point into a thread's box.  Only FINITE coordinates extend it: fmin / fmax already pass over a NaN, an infinite one would make
+// the box -- and with it the cell size -- infinite.  Such a point still gets a (boundary) cell and is simply never anybody's
+// neighbour: its distance to every query is inf or NaN, as in the reference's kd-tree (tests/test_gpu_parity.py).
+__device__ __forceinline__ void box_add_finite(double (&lo)[3], double (&hi)[3], double a, double b, double c) {
+  if (!(fabs(a) < __builtin_inf())) a = __builtin_nan("");
+  if (!(fabs(b) < __builtin_inf())) b = __builtin_nan("");
+  if (!(fabs(c) < __builtin_inf())) c = __builtin_nan("");
+  lo[0] = fmin(lo[0], a); hi[0] = fmax(hi[0], a);
+  lo[1] = fmin(lo[1], b); hi[1] = fmax(hi[1], b);
+  lo[2] = fmin(lo[2], c); hi[2] = fmax(hi[2], c);
 }
-size_t scan_1p_ctl_elems(size_t n) { return (n + kTile1p - 1) / kTile1p + 8; }
-// arrays of more than 1024 small tiles (the 1 M-class frames; smaller ones use the fused / two-launch forms) whose 16 Ki tiles
-// number at most the device's CUs: k_scan_1p holds its 64 elements per thread in registers (256 VGPRs + 76 AGPRs: one wave per
-// SIMD, i.e. ONE block per CU), so a grid of up to one block per CU is resident at once on an otherwise idle device -- and on a
-// busy one a block still only waits for blocks of lower index, which the dispatcher started earlier (a CPX partition or a
-// CU-masked device reports fewer CUs and gets the multi-launch scan; round 4 stopped at 240 tiles).  The wait is bounded either way.
-bool scan_1p_applies(size_t n, int device_cus) {
-  // (a sixteenth of the CUs to spare for whatever else runs on the device -- another context's stream, another rank: the look-back
-  //  waits for blocks that have to be running; as vox_emit_resident_blocks)
-  return (n + kScanTile - 1) / kScanTile > 1024 && (long long)((n + kTile1p - 1) / kTile1p) <= (long long)(device_cus - device_cus / 16);
-}
-void launch_scan_counts_1p(const unsigned long long* in, unsigned long long* out, size_t n, unsigned long long* ctl, unsigned* fault,
-                           hipStream_t s) {
-  const size_t tiles = (n + kTile1p - 1) / kTile1p;
-  Scan1p C{ctl, next_scan_epoch(), fault};
-  hipLaunchKernelGGL(k_scan_1p, dim3((unsigned)tiles), dim3(kScanThreads), 0, s, in, out, n, C);
-}
-
-// first half of the medium-size scan only: tile-local exclusive scans + per-tile totals (the consumer adds the tiles'
-// offsets itself, see k_compact and k_grid_finalize_scatter_all).  Returns the number of tiles; 0 = not applicable (use the full scan).
-static int scan_tile_count(size_t n) {
-  const size_t tiles = (n + kScanTile - 1) / kScanTile;
-  return (n <= (size_t)kSmallTile || tiles > 1024) ? 0 : (int)tiles;
-}
-int scan_tiles_only(const unsigned long long* in, unsigned long long* out, size_t n, unsigned long long* totals, hipStream_t s,
-                    const int* gate) {
-  const int tiles = scan_tile_count(n);
-  if (tiles > 0)
-    hipLaunchKernelGGL((k_scan_tile<unsigned long long, false>), dim3((unsigned)tiles), dim3(kScanThreads), 0, s, in, out, n, totals, gate);
-  return tiles;
-}
-int grid_table_tiles(size_t n) { return scan_tile_count(n); }
-void launch_grid_scan_tiles(unsigned* cell_cnt, unsigned* cell_scan, size_t n, unsigned* totals, hipStream_t s) {
-  hipLaunchKernelGGL((k_scan_tile<unsigned, true>), dim3((unsigned)scan_tile_count(n)), dim3(kScanThreads), 0, s, cell_cnt, cell_scan, n,
-                     totals, (const int*)nullptr);
-}
-
-// ================================================================================================
-//  grid build
-// ================================================================================================
-// per-block min/max of every kind's cloud (blockIdx.y = kind); the host finishes over 64 rows of 6 (`out` may
-// be pinned host memory: the rows then need no copy kernel)
-__global__ __launch_bounds__(256) void k_bbox_all(GridSet gs, double* __restrict__ out) {
+// the threads' boxes of a block of 256 -> row blockIdx.x of kind k: (lo[3], hi[3]); the host finishes over 64 rows of 6 per kind
+// (reduce_box_rows; `out` may be pinned host memory: the rows then need no copy kernel)
+__device__ __forceinline__ void block_box_rows(double (&lo)[3], double (&hi)[3], int k, double* __restrict__ out) {
   __shared__ double red[4][6];
-  const int k = blockIdx.y;
-  const double* __restrict__ x = gs.tx[k];
-  const double* __restrict__ y = gs.ty[k];
-  const double* __restrict__ z = gs.tz[k];
-  const int n = gs.n[k];
-  double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-    // only FINITE coordinates extend the box: fmin / fmax already pass over a NaN, an infinite one would make the box -- and
-    // with it the cell size -- infinite.  Such a point still gets a (boundary) cell and is simply never anybody's neighbour:
-    // its distance to every query is inf or NaN, as in the reference's kd-tree (tests/test_gpu_parity.py).
-    double a = x[i], b = y[i], c = z[i];
-    if (!(fabs(a) < __builtin_inf())) a = __builtin_nan("");
-    if (!(fabs(b) < __builtin_inf())) b = __builtin_nan("");
-    if (!(fabs(c) < __builtin_inf())) c = __builtin_nan("");
-    lo[0] = fmin(lo[0], a); hi[0] = fmax(hi[0], a);
-    lo[1] = fmin(lo[1], b); hi[1] = fmax(hi[1], b);
-    lo[2] = fmin(lo[2], c); hi[2] = fmax(hi[2], c);
-  }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
 #pragma unroll
@@ -541,10 +154,20 @@ __global__ __launch_bounds__(256) void k_bbox_all(GridSet gs, double* __restrict
     out[((size_t)k * gridDim.x + blockIdx.x) * 6 + threadIdx.x] = v;
   }
 }
+// per-block min/max of every kind's cloud (blockIdx.y = kind)
+__global__ __launch_bounds__(256) void k_bbox_all(GridSet gs, double* __restrict__ out) {
+  const int k = blockIdx.y;
+  const double* __restrict__ x = gs.tx[k];
+  const double* __restrict__ y = gs.ty[k];
+  const double* __restrict__ z = gs.tz[k];
+  const int n = gs.n[k];
+  double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) box_add_finite(lo, hi, x[i], y[i], z[i]);
+  block_box_rows(lo, hi, k, out);
+}
 // setInputTarget of a whole Frame: AoS -> SoA of the four clouds AND their bounding-box rows in ONE launch (four conversion
-// launches and k_bbox_all otherwise).  Same rows as k_bbox_all: 64 per kind, finite coordinates only.
+// launches and k_bbox_all otherwise).  Same rows as k_bbox_all.
 __global__ __launch_bounds__(256) void k_ingest_targets(IngestArgs A, double* __restrict__ out) {
-  __shared__ double red[4][6];
   const int k = blockIdx.y;
   const double* __restrict__ aos = A.aos[k];
   double* __restrict__ x = A.x[k];
@@ -553,34 +176,11 @@ __global__ __launch_bounds__(256) void k_ingest_targets(IngestArgs A, double* __
   const int n = A.n[k];
   double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-    double a = aos[3 * (size_t)i], b = aos[3 * (size_t)i + 1], c = aos[3 * (size_t)i + 2];
+    const double a = aos[3 * (size_t)i], b = aos[3 * (size_t)i + 1], c = aos[3 * (size_t)i + 2];
     x[i] = a; y[i] = b; z[i] = c;
-    if (!(fabs(a) < __builtin_inf())) a = __builtin_nan("");
-    if (!(fabs(b) < __builtin_inf())) b = __builtin_nan("");
-    if (!(fabs(c) < __builtin_inf())) c = __builtin_nan("");
-    lo[0] = fmin(lo[0], a); hi[0] = fmax(hi[0], a);
-    lo[1] = fmin(lo[1], b); hi[1] = fmax(hi[1], b);
-    lo[2] = fmin(lo[2], c); hi[2] = fmax(hi[2], c);
+    box_add_finite(lo, hi, a, b, c);
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      lo[a] = fmin(lo[a], __shfl_down(lo[a], off, 64));
-      hi[a] = fmax(hi[a], __shfl_down(hi[a], off, 64));
-    }
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { red[wave][a] = lo[a]; red[wave][3 + a] = hi[a]; }
-  }
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    double v = red[0][threadIdx.x];
-    for (int w = 1; w < 4; ++w) v = (threadIdx.x < 3) ? fmin(v, red[w][threadIdx.x]) : fmax(v, red[w][threadIdx.x]);
-    out[((size_t)k * gridDim.x + blockIdx.x) * 6 + threadIdx.x] = v;
-  }
+  block_box_rows(lo, hi, k, out);
 }
 void launch_ingest_targets(const IngestArgs& A, double* out, hipStream_t s) {
   hipLaunchKernelGGL(k_ingest_targets, dim3(64, kKinds), dim3(256), 0, s, A, out);
@@ -617,10 +217,12 @@ static int max_n(const GridSet& gs) {
   for (int k = 0; k < kKinds; ++k) m = std::max(m, gs.n[k]);
   return m;
 }
+// blocks of 256 per kind for the passes over the points: one point of the largest kind per thread up to 1 M points -- every
+// atomic / scattered store of the pass in flight at once
+static int grid_point_blocks(const GridSet& gs) { return std::min((max_n(gs) + 255) / 256, 4096); }
 template <typename T>
 void launch_grid_count_all(const GridSet& gs, T* cell_cnt, int* cell_of_pt, int* rank_of_pt, hipStream_t s, const FrameInitHook* frame) {
-  int blocks = (max_n(gs) + 255) / 256;
-  if (blocks > 4096) blocks = 4096;   // (1 M points: one point per thread -- every atomic / scattered store of the pass in flight at once)
+  const int blocks = grid_point_blocks(gs);
   FrameInit fi;
   FrameInitBufs fb;
   memset(&fi, 0, sizeof(fi));
@@ -631,8 +233,8 @@ void launch_grid_count_all(const GridSet& gs, T* cell_cnt, int* cell_of_pt, int*
 }
 template void launch_grid_count_all<unsigned>(const GridSet&, unsigned*, int*, int*, hipStream_t, const FrameInitHook*);
 template void launch_grid_count_all<unsigned long long>(const GridSet&, unsigned long long*, int*, int*, hipStream_t, const FrameInitHook*);
-// cell_start of kind k lives at cell_start[cell_base[k] + k ...] (ncell + 1 entries per kind), relative to the
-// kind's own point block
+// cell_start of kind k lives at cell_start[cell_base[k] + k ...] (GridPlan::Kind::start_base of the packed layout,
+// tl_grid_plan.hpp; ncell + 1 entries per kind), relative to the kind's own point block
 __global__ void k_grid_finalize_all(GridSet gs, const unsigned long long* __restrict__ cell_scan,
                                     int* __restrict__ cell_start, unsigned long long* __restrict__ cell_cnt) {
   const int k = blockIdx.y;
@@ -682,7 +284,7 @@ __global__ __launch_bounds__(256) void k_grid_finalize_scatter_all(GridSet gs, G
                                                                    int fin_blocks, int sc_blocks, int* __restrict__ cell_start,
                                                                    const int* __restrict__ cell_of_pt,
                                                                    const int* __restrict__ rank_of_pt, double4* __restrict__ gp) {
-  __shared__ unsigned toff[1024];
+  __shared__ unsigned toff[kScanLdsTiles];
   __shared__ unsigned wtot[4];
   tile_offsets_to_lds(totals, tiles, toff, wtot);
   if ((int)blockIdx.x < fin_blocks) {
@@ -720,8 +322,7 @@ void launch_grid_finalize_scatter_all(const GridSet& gs, const unsigned* cell_sc
 }
 void launch_grid_scatter_all(const GridSet& gs, const int* cell_of_pt, const unsigned long long* cell_scan,
                              const int* rank_of_pt, double4* gp, hipStream_t s) {
-  int blocks = (max_n(gs) + 255) / 256;
-  if (blocks > 4096) blocks = 4096;   // (1 M points: one point per thread -- every atomic / scattered store of the pass in flight at once)
+  const int blocks = grid_point_blocks(gs);
   hipLaunchKernelGGL(k_grid_scatter_all, dim3(blocks, kKinds), dim3(256), 0, s, gs, cell_of_pt, cell_scan, rank_of_pt, gp);
 }
 
@@ -954,7 +555,7 @@ __global__ __launch_bounds__(256) void k_grid_scatter_qbin(GridSet gs, const int
   }
   const int k = role;
   const int n = gs.n[k];
-  const long long base = gs.cell_base[k] + k;
+  const long long base = gs.cell_base[k] + k;   // (GridPlan::Kind::start_base of the packed layout, tl_grid_plan.hpp)
   for (int i = bx * (int)blockDim.x + (int)threadIdx.x; i < n; i += gx * (int)blockDim.x) {
     const int c = cell_of_pt[gs.tgt_off[k] + i];
     const int pos = cell_start[base + c] + rank_of_pt[gs.tgt_off[k] + i];
@@ -1143,11 +744,10 @@ void launch_finish_direct(const FinishLargeArgs& fin, GnState* st, hipStream_t s
 void launch_grid_scan_finalize_scatter_1p(const GridSet& gs, unsigned long long* cell_cnt, size_t ncells_plus_1, int* cell_start,
                                           unsigned long long* ctl, unsigned* fault, const int* cell_of_pt, const int* rank_of_pt, double4* gp,
                                           hipStream_t s, const QueryBinRide* qbin, const GridView* views) {
-  const size_t tiles = (ncells_plus_1 + kTile1p - 1) / kTile1p;
+  const size_t tiles = scan_1p_tiles(ncells_plus_1);
   Scan1p C{ctl, next_scan_epoch(), fault};
   hipLaunchKernelGGL(k_grid_scan_finalize_1p, dim3((unsigned)tiles), dim3(kScanThreads), 0, s, gs, cell_cnt, ncells_plus_1, cell_start, C);
-  int blocks = (max_n(gs) + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
+  const int blocks = grid_point_blocks(gs);
   if (qbin && views) {   // the query sort's first pass as extra rows of this launch (QueryBinRide)
     BuildArgs A;
     memset(&A, 0, sizeof(A));
@@ -1187,7 +787,7 @@ void launch_build(const SlotView& sv, const GridView grids[kKinds], const BuildP
     // the pose moves by centimetres.
     // (tile_cnt[0 .. ntiles] was zeroed by k_frame_init -- one launch less at the start of every frame)
     if (!binned) hipLaunchKernelGGL(k_query_bin, dim3((n + 255) / 256), dim3(256), 0, s, A, st, tile_of_slot, tile_fill, tile_cnt);
-    if (scan1p_ctl) launch_scan_counts_1p(tile_cnt, tile_scan, (size_t)ntiles + 1, scan1p_ctl, scan1p_fault, s);   // (the caller has checked scan_1p_applies)
+    if (scan1p_ctl) launch_scan_counts_1p(tile_cnt, tile_scan, (size_t)ntiles + 1, scan1p_ctl, scan1p_fault, s);   // (the caller has asked scan_path)
     else launch_exclusive_scan_u64(tile_cnt, tile_scan, (size_t)ntiles + 1, scan_tmp, s);
     hipLaunchKernelGGL(k_query_scatter, dim3((n + 255) / 256), dim3(256), 0, s, sv, tile_of_slot, tile_scan,
                        tile_fill, qrec);
@@ -1323,7 +923,7 @@ struct CompactArgs {
   int tiles;                          // the tile offsets itself: no k_scan_add_direct launch; <= 1024)
 };
 __global__ __launch_bounds__(256) void k_compact(CompactArgs A) {
-  __shared__ unsigned long long toff[1024];
+  __shared__ unsigned long long toff[kScanLdsTiles];
   __shared__ unsigned long long wtot[4];
   if (A.gate && *A.gate == 0) {
     if (A.refresh_gate && *A.refresh_gate != 0) {   // the set of the previous iteration: new captured weights, zeroed slots
