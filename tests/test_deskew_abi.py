@@ -1,11 +1,8 @@
 """The deskew of the odometry frame without a GPU: the ctypes mirrors of tloam_deskew_config / _info
 against the C header, the defaults, the new entry points in the built library, properties of the numpy restatement
 (tests/deskew_np.py) the device is checked against, and the swept-scan generator (tloam_amd/synth_sweep.py)."""
-import ctypes as C
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 import pytest
@@ -13,43 +10,22 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
+import abi_kit  # noqa: E402
 import deskew_np as D  # noqa: E402
 from tloam_amd import registration as reg  # noqa: E402
 from tloam_amd import synth_hdl64 as G  # noqa: E402
 from tloam_amd import synth_sweep as SW  # noqa: E402
 from tloam_amd.synth import se3_exp_np  # noqa: E402
 
-ROOT = os.path.dirname(HERE)
 DESKEW_SYMBOLS = ("tloam_deskew_default_config", "tloam_deskew_configure", "tloam_deskew_get_info",
                   "tloam_odometry_frame_timed", "tloam_deskew_scan")
 XI = np.array([0.8, 0.05, -0.02, 0.004, -0.006, 0.03])   # a frame's motion: 0.8 m and 0.03 rad of yaw
 
 
 def test_deskew_struct_layout_matches_the_c_header():
-    src = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "tloam_hip.h"
-int main(void) {
-  printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(tloam_deskew_config),
-         offsetof(tloam_deskew_config, enabled), offsetof(tloam_deskew_config, time_source),
-         offsetof(tloam_deskew_config, direction), offsetof(tloam_deskew_config, reserved0),
-         offsetof(tloam_deskew_config, start_azimuth), offsetof(tloam_deskew_config, ref_fraction),
-         sizeof(tloam_deskew_info), offsetof(tloam_deskew_info, frames_deskewed), offsetof(tloam_deskew_info, last_frame),
-         offsetof(tloam_deskew_info, last_twist), offsetof(tloam_deskew_info, last_max_shift),
-         offsetof(tloam_deskew_info, next_motion_colmajor));
-  return 0;
-}'''
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c"); exe = os.path.join(d, "t")
-        open(c, "w").write(src)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        vals = list(map(int, subprocess.check_output([exe]).split()))
-    M, I = reg.DeskewConfig, reg.DeskewInfo
-    assert vals == [C.sizeof(M), M.enabled.offset, M.time_source.offset, M.direction.offset, M.reserved0.offset,
-                    M.start_azimuth.offset, M.ref_fraction.offset, C.sizeof(I), I.frames_deskewed.offset,
-                    I.last_frame.offset, I.last_twist.offset, I.last_max_shift.offset, I.next_motion_colmajor.offset]
-    assert vals[:7] == [32, 0, 4, 8, 12, 16, 24] and vals[7] == 200
+    """(every field of both mirrors against the header: tests/test_abi_header.py)"""
+    assert abi_kit.sizes("tloam_deskew_config", "tloam_deskew_info") == [32, 200]
+    assert abi_kit.offsets("tloam_deskew_config") == [0, 4, 8, 12, 16, 24]
 
 
 def test_deskew_defaults():
@@ -62,13 +38,7 @@ def test_deskew_defaults():
 
 
 def test_deskew_symbols_are_exported():
-    L = reg.load_library()
-    for name in DESKEW_SYMBOLS:
-        assert name in reg.EXPORTED_SYMBOLS
-        getattr(L, name)
-    out = subprocess.check_output(["nm", "-D", "--defined-only", reg.LIB_PATH], text=True)
-    exported = {line.split()[-1] for line in out.splitlines() if line.strip()}
-    assert set(DESKEW_SYMBOLS) <= exported
+    abi_kit.assert_exported(DESKEW_SYMBOLS)
 
 
 def scan_like(rng, n):

@@ -3,7 +3,6 @@ the C header, the defaults, the new entry points in the built library, null argu
 T_rel.  Everything that needs a context needs a device: tests/test_gpu_loop.py."""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -14,8 +13,8 @@ from tloam_amd import registration as reg
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
+import abi_kit  # noqa: E402
 import loop_np as LN  # noqa: E402
-from test_place_abi import _probe  # noqa: E402
 
 LOOP_SYMBOLS = ("tloam_loop_default_config", "tloam_loop_configure", "tloam_loop_get_info", "tloam_place_set_keyframe_clouds",
                 "tloam_place_read_keyframe_clouds", "tloam_loop_verify_pending", "tloam_loop_verify_pair",
@@ -23,12 +22,8 @@ LOOP_SYMBOLS = ("tloam_loop_default_config", "tloam_loop_configure", "tloam_loop
 
 
 def test_loop_struct_layouts_match_the_c_header():
-    structs = {"tloam_loop_config": reg.LoopConfig, "tloam_loop_info": reg.LoopInfo, "tloam_loop_constraint": reg.LoopConstraint}
-    want = []
-    for cls in structs.values():
-        want.append(C.sizeof(cls))
-        want += [getattr(cls, f).offset for f, _ in cls._fields_]
-    assert _probe(structs) == want
+    """(every field of the three mirrors against the header: tests/test_abi_header.py)"""
+    assert abi_kit.sizes("tloam_loop_config", "tloam_loop_info", "tloam_loop_constraint") == [152, 32, 632]
     assert C.sizeof(reg.LoopConfig) == 152 and C.sizeof(reg.LoopInfo) == 32 and C.sizeof(reg.LoopConstraint) == 632
     assert reg.LoopConfig.inlier_dist.offset == 16 and reg.LoopConfig.coarse.offset == 48   # explicit padding
 
@@ -52,13 +47,7 @@ def test_loop_defaults():
 
 
 def test_loop_symbols_are_exported():
-    L = reg.load_library()
-    for name in LOOP_SYMBOLS:
-        assert name in reg.EXPORTED_SYMBOLS
-        getattr(L, name)
-    out = subprocess.check_output(["nm", "-D", "--defined-only", reg.LIB_PATH], text=True)
-    exported = {line.split()[-1] for line in out.splitlines() if line.strip()}
-    assert set(LOOP_SYMBOLS) <= exported
+    abi_kit.assert_exported(LOOP_SYMBOLS)
 
 
 def test_null_arguments_are_refused():

@@ -1,43 +1,22 @@
 """The ctypes mirrors of tloam_map_config / tloam_map_info against the C header, the map's defaults against the reference's
 configuration, the new entry points in the built library, and the PCD export round trip (no GPU needed)."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+import abi_kit
 from tloam_amd import map_io
 from tloam_amd import registration as reg
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MAP_SYMBOLS = ("tloam_map_default_config", "tloam_map_configure", "tloam_map_get_info", "tloam_map_read",
                "tloam_registered_scan")
 
 
 def test_map_struct_layout_matches_the_c_header():
-    src = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "tloam_hip.h"
-int main(void) {
-  printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(tloam_map_config), offsetof(tloam_map_config, enabled),
-         offsetof(tloam_map_config, voxel), offsetof(tloam_map_config, reserve_points), sizeof(tloam_map_info),
-         offsetof(tloam_map_info, n_points), offsetof(tloam_map_info, n_frames), offsetof(tloam_map_info, last_first),
-         offsetof(tloam_map_info, last_count), offsetof(tloam_map_info, capacity_points),
-         offsetof(tloam_map_info, overflow_frames));
-  return 0;
-}'''
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c"); exe = os.path.join(d, "t")
-        open(c, "w").write(src)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        vals = list(map(int, subprocess.check_output([exe]).split()))
-    M, I = reg.MapConfig, reg.MapInfo
-    assert vals == [C.sizeof(M), M.enabled.offset, M.voxel.offset, M.reserve_points.offset, C.sizeof(I), I.n_points.offset,
-                    I.n_frames.offset, I.last_first.offset, I.last_count.offset, I.capacity_points.offset,
-                    I.overflow_frames.offset]
+    """(every field of every mirror against the header: tests/test_abi_header.py)"""
+    for name, S in (("tloam_map_config", reg.MapConfig), ("tloam_map_info", reg.MapInfo)):
+        assert abi_kit.sizes(name) == [C.sizeof(S)] and abi_kit.offsets(name) == [getattr(S, f).offset for f, _ in S._fields_]
 
 
 def test_map_defaults_are_the_reference_configuration():
@@ -52,13 +31,7 @@ def test_map_defaults_are_the_reference_configuration():
 
 
 def test_map_symbols_are_exported():
-    L = reg.load_library()
-    for name in MAP_SYMBOLS:
-        assert name in reg.EXPORTED_SYMBOLS
-        getattr(L, name)
-    out = subprocess.check_output(["nm", "-D", "--defined-only", reg.LIB_PATH], text=True)
-    exported = {line.split()[-1] for line in out.splitlines() if line.strip()}
-    assert set(MAP_SYMBOLS) <= exported
+    abi_kit.assert_exported(MAP_SYMBOLS)
 
 
 @pytest.mark.parametrize("ascii", (False, True))

@@ -3,42 +3,20 @@ C header, the defaults (and the restatement's), the new entry points in the buil
 configurations need a context, hence a device: tests/test_gpu_place.py."""
 import ctypes as C
 import os
-import subprocess
-import tempfile
 
 import pytest
 
+import abi_kit
 from tloam_amd import registration as reg
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 PLACE_SYMBOLS = ("tloam_place_default_config", "tloam_place_configure", "tloam_place_get_info", "tloam_place_read_keyframes",
                  "tloam_place_read_loops", "tloam_place_add_scan", "tloam_place_describe")
 
 
-def _probe(structs):
-    """sizeof and offsetof of every field of `structs` ({C name: ctypes class}) as the C compiler lays them out"""
-    lines = []
-    for cname, cls in structs.items():
-        lines.append(f'  printf("%zu\\n", sizeof({cname}));')
-        for f, _ in cls._fields_:
-            lines.append(f'  printf("%zu\\n", offsetof({cname}, {f}));')
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "tloam_hip.h"\nint main(void) {\n' + "\n".join(lines) + "\n  return 0;\n}\n"
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c"); exe = os.path.join(d, "t")
-        open(c, "w").write(src)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        return list(map(int, subprocess.check_output([exe]).split()))
-
-
 def test_place_struct_layouts_match_the_c_header():
-    structs = {"tloam_place_config": reg.PlaceConfig, "tloam_place_info": reg.PlaceInfo, "tloam_place_loop": reg.PlaceLoop}
-    want = []
-    for cls in structs.values():
-        want.append(C.sizeof(cls))
-        want += [getattr(cls, f).offset for f, _ in cls._fields_]
-    got = _probe(structs)
-    assert got == want
+    """(every field of the three mirrors against the header: tests/test_abi_header.py)"""
+    assert abi_kit.sizes("tloam_place_config", "tloam_place_info", "tloam_place_loop") == [72, 32, 56]
     assert C.sizeof(reg.PlaceConfig) == 72 and C.sizeof(reg.PlaceInfo) == 32 and C.sizeof(reg.PlaceLoop) == 56
     assert reg.PlaceConfig.max_radius.offset == 24 and reg.PlaceConfig.reserve_keyframes.offset == 64   # explicit padding
 
@@ -64,13 +42,7 @@ def test_place_defaults_match_the_restatement():
 
 
 def test_place_symbols_are_exported():
-    L = reg.load_library()
-    for name in PLACE_SYMBOLS:
-        assert name in reg.EXPORTED_SYMBOLS
-        getattr(L, name)
-    out = subprocess.check_output(["nm", "-D", "--defined-only", reg.LIB_PATH], text=True)
-    exported = {line.split()[-1] for line in out.splitlines() if line.strip()}
-    assert set(PLACE_SYMBOLS) <= exported
+    abi_kit.assert_exported(PLACE_SYMBOLS)
 
 
 def test_null_arguments_are_refused():

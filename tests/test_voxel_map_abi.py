@@ -1,11 +1,8 @@
 """The merged voxel map without a GPU: the ctypes mirrors of tloam_voxel_map_config / _info against the C
 header, the defaults, the new entry points in the built library, properties of the int64 restatement (tests/voxel_map_np.py)
 the device is checked against, and the voxel PCD round trip."""
-import ctypes as C
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 import pytest
@@ -13,40 +10,19 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
+import abi_kit  # noqa: E402
 import voxel_map_np as V  # noqa: E402
 from tloam_amd import map_io  # noqa: E402
 from tloam_amd import registration as reg  # noqa: E402
 
-ROOT = os.path.dirname(HERE)
 VMAP_SYMBOLS = ("tloam_voxel_map_default_config", "tloam_voxel_map_configure", "tloam_voxel_map_get_info",
                 "tloam_voxel_map_read", "tloam_voxel_map_read_box")
 
 
 def test_voxel_map_struct_layout_matches_the_c_header():
-    src = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "tloam_hip.h"
-int main(void) {
-  printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(tloam_voxel_map_config),
-         offsetof(tloam_voxel_map_config, enabled), offsetof(tloam_voxel_map_config, reserved0),
-         offsetof(tloam_voxel_map_config, voxel), offsetof(tloam_voxel_map_config, origin),
-         offsetof(tloam_voxel_map_config, reserve_voxels), sizeof(tloam_voxel_map_info),
-         offsetof(tloam_voxel_map_info, n_voxels), offsetof(tloam_voxel_map_info, n_points),
-         offsetof(tloam_voxel_map_info, n_frames), offsetof(tloam_voxel_map_info, last_new),
-         offsetof(tloam_voxel_map_info, capacity_voxels), offsetof(tloam_voxel_map_info, overflow_frames));
-  return 0;
-}'''
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c"); exe = os.path.join(d, "t")
-        open(c, "w").write(src)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        vals = list(map(int, subprocess.check_output([exe]).split()))
-    M, I = reg.VoxelMapConfig, reg.VoxelMapInfo
-    assert vals == [C.sizeof(M), M.enabled.offset, M.reserved0.offset, M.voxel.offset, M.origin.offset,
-                    M.reserve_voxels.offset, C.sizeof(I), I.n_voxels.offset, I.n_points.offset, I.n_frames.offset,
-                    I.last_new.offset, I.capacity_voxels.offset, I.overflow_frames.offset]
-    assert vals[:6] == [48, 0, 4, 8, 16, 40] and vals[6] == 48
+    """(every field of both mirrors against the header: tests/test_abi_header.py)"""
+    assert abi_kit.sizes("tloam_voxel_map_config", "tloam_voxel_map_info") == [48, 48]
+    assert abi_kit.offsets("tloam_voxel_map_config") == [0, 4, 8, 16, 40]
 
 
 def test_voxel_map_defaults():
@@ -59,13 +35,7 @@ def test_voxel_map_defaults():
 
 
 def test_voxel_map_symbols_are_exported():
-    L = reg.load_library()
-    for name in VMAP_SYMBOLS:
-        assert name in reg.EXPORTED_SYMBOLS
-        getattr(L, name)
-    out = subprocess.check_output(["nm", "-D", "--defined-only", reg.LIB_PATH], text=True)
-    exported = {line.split()[-1] for line in out.splitlines() if line.strip()}
-    assert set(VMAP_SYMBOLS) <= exported
+    abi_kit.assert_exported(VMAP_SYMBOLS)
 
 
 def cloud(rng, n, spread=20.0):
