@@ -580,7 +580,8 @@ __global__ __launch_bounds__(256) void k_query_scatter(SlotView sv, const int* _
 //   LPQ = 1: the lane resolves the nine (z,y) rows of the 27-cell neighbourhood (one 16-byte cell-table
 //            request per row, all in flight) and walks them as one candidate stream, four records per trip.
 //   LPQ = 4 / 16: smaller frames are latency-bound (a ~35-candidate dependent chain per query), so 4 (16)
-//            adjacent lanes split the nine rows -- three (at most one) each --, walk them in parallel and merge
+//            adjacent lanes resolve the nine rows -- three (at most one) each --, walk them (LPQ = 4: each lane its
+//            own rows; LPQ = 16: the rows as one run of 16-byte pieces over the sixteen lanes, tl_walk.hpp) and merge
 //            their packed-key lists with two (four) xor-shuffle rounds; lane 0 of the group finishes the fit.
 #ifdef TLOAM_K1_PROF   // development aid (scripts/k1_prof.py): wall-clock stamps of one wave of the sixteen-lane search
 __device__ unsigned long long g_k1_prof[64];

@@ -4,8 +4,12 @@
 //   LPQ = 1: the lane resolves the nine (z,y) rows of the 27-cell neighbourhood (one 16-byte cell-table
 //            request per row, all in flight) and walks them as one candidate stream, four records per trip.
 //   LPQ = 4 / 16: smaller frames are latency-bound (a ~35-candidate dependent chain per query), so 4 (16)
-//            adjacent lanes split the nine rows -- three (at most one) each --, walk them in parallel and merge
-//            their packed-key lists with two (four) xor-shuffle rounds; lane 0 of the group finishes the fit.
+//            adjacent lanes resolve the nine rows -- three (at most one) each -- and merge their packed-key
+//            lists with two (four) xor-shuffle rounds; lane 0 of the group finishes the fit.
+//            LPQ = 4 walks row-owner: every lane its own three rows, two records of each per trip.
+//            LPQ = 16 walks the query's rows as ONE run of 16-byte pieces (two per record) dealt to the sixteen
+//            lanes in order, so that the lanes of a load instruction cover contiguous bytes: 32 records per trip,
+//            the lane pair joins a record's halves, the even lane inserts it.
 #pragma once
 
 #include "tl_common.hpp"
@@ -16,6 +20,14 @@
 #endif
 
 namespace tl {
+
+// A DPP move inside the sixteen-lane row (one query's lanes at LPQ = 16): CTRL 0x111 .. 0x11F = row_shr:1 .. 15,
+// 0x150 .. 0x15F = row_newbcast:0 .. 15 (the value of that lane of the row), 0xB1 = quad_perm:[1,0,3,2] (the lane pair
+// swapped); a lane without a source reads 0.
+template <int CTRL>
+__device__ __forceinline__ int row_dpp(int v) {
+  return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true);
+}
 
 template <int K, int LPQ>
 __device__ __forceinline__ void knn_rows(const GridView& g, const PtsGlobal& pts, Vec3 pw, int sub, TopK<K>& tk,
@@ -147,28 +159,79 @@ __device__ __forceinline__ void knn_rows(const GridView& g, const PtsGlobal& pts
     int len = 0;
 #pragma unroll
     for (int i = 0; i < NR; ++i) len = max(len, re[i] - rs[i]);
-    // kU steps per trip: candidates s .. s + kU - 1 of each of this lane's rows are requested together (the walk of a
-    // small frame is a latency chain: one record round trip per trip, so the trip carries as many as the rows allow)
-#ifndef TLOAM_K1_WIDE_KU
-#define TLOAM_K1_WIDE_KU 4
-#endif
-    constexpr int kU = (NR == 1) ? TLOAM_K1_WIDE_KU : 2;
+    if constexpr (NR == 1) {
+      // PIECE walk (LPQ = 16).  The query's candidates -- its rows one after the other, T records -- are cut into 16-byte
+      // pieces (piece p: record p >> 1, half p & 1) and piece t * 64 + u * 16 + sub is loaded by lane `sub` in instruction
+      // u of trip t: the sixteen lanes of one load instruction cover 256 contiguous bytes of a row (a row boundary starts
+      // a new run), where a row-owner lane's eight instructions per trip (four records x two halves) each looked the
+      // same one or two lines up again.  A trip is 32 records; the lane pair (2i, 2i + 1) joins the halves of its record
+      // and the even lane inserts it -- same distance, same index, same key as a row-owner walk would insert, and the
+      // kept list is a sorted set of distinct keys, so the order of insertion does not show.
+      //
+      // Row table: the exclusive prefix of the nine row lengths by four row_shr steps inside the sixteen-lane DPP row (no
+      // LDS, no barrier); lane k keeps (prefix, start - prefix) of row k, the lanes behind the rows hold prefix = T.  A
+      // piece finds its row by a BINARY SEARCH BY SHUFFLE over the sixteen prefixes (four steps, then one shuffle for the
+      // offset): two registers live across the loop and the kernel's 84 VGPRs unchanged, where nine broadcasts of the
+      // pairs to every lane held seventeen (90 VGPRs) for the same kernel time (CHANGELOG).
+      const int ln = re[0] - rs[0];   // (0 on the lanes without a row)
+      int inc = ln;
+      inc += row_dpp<0x111>(inc);   // row_shr:1
+      inc += row_dpp<0x112>(inc);   // row_shr:2
+      inc += row_dpp<0x114>(inc);   // row_shr:4
+      inc += row_dpp<0x118>(inc);   // row_shr:8
+      const int pre_own = inc - ln, off_own = rs[0] - pre_own;
+      int T = row_dpp<0x15F>(inc);   // row_newbcast:15 -- the query's candidate count
 #ifdef TLOAM_K1_DBG_NOWALK  // timing experiment only
-    len = 0;
+      T = 0;
 #endif
-    for (int s = 0; s < len; s += kU) {
-      double4 c[kU][NR];
+      constexpr int kPc = 4;   // load instructions per trip: 4 x 16 pieces = 32 records
+      const bool even = (sub & 1) == 0;
+      const char* const half0 = reinterpret_cast<const char*>(pts.p) + (sub & 1) * 16;
+      // (T is the same on the sixteen lanes of a query; the wave runs the longest of its queries' trip counts)
+      for (int b = 0; b < T; b += 8 * kPc) {
+        int jp[kPc];
+        bool vp[kPc];
+        double2 c[kPc];
 #pragma unroll
-      for (int u = 0; u < kU; ++u)
+        for (int u = 0; u < kPc; ++u) {
+          const int rec = b + u * 8 + (sub >> 1);   // the record of piece t * 64 + u * 16 + sub, t = b / 32
+          int row = 0;   // the last row that starts at or before it (empty rows are stepped over; past the end: lane 15)
 #pragma unroll
-        for (int i = 0; i < NR; ++i) c[u][i] = pts.p[(rs[i] + s + u < re[i]) ? rs[i] + s + u : 0];
-#pragma unroll
-      for (int u = 0; u < kU; ++u)
-#pragma unroll
-        for (int i = 0; i < NR; ++i) {
-          const bool v = rs[i] + s + u < re[i];
-          key_insert<K + 1>(L, key_pack(sqdist(pw.x, pw.y, pw.z, c[u][i].x, c[u][i].y, c[u][i].z), rs[i] + s + u, keep_mask, v));
+          for (int st = 8; st >= 1; st >>= 1) row += (__shfl(pre_own, row + st, 16) <= rec) ? st : 0;
+          const int o = __shfl(off_own, row, 16);   // (by every lane, outside the select below: a shuffle reads active lanes only)
+          vp[u] = rec < T;
+          jp[u] = vp[u] ? rec + o : 0;   // a piece past the end loads record 0
         }
+#pragma unroll
+        for (int u = 0; u < kPc; ++u) c[u] = *reinterpret_cast<const double2*>(half0 + (size_t)jp[u] * sizeof(double4));
+#pragma unroll
+        for (int u = 0; u < kPc; ++u) {
+          // the odd lane holds (z, index): its z goes to the even lane (quad_perm [1,0,3,2]), which holds (x, y)
+          const double z = __hiloint2double(row_dpp<0xB1>(__double2hiint(c[u].x)), row_dpp<0xB1>(__double2loint(c[u].x)));
+          key_insert<K + 1>(L, key_pack(sqdist(pw.x, pw.y, pw.z, c[u].x, c[u].y, z), jp[u], keep_mask, vp[u] && even));
+        }
+      }
+    } else {
+      // ROW-OWNER walk (LPQ = 4: three rows per lane).  kU steps per trip: candidates s .. s + kU - 1 of each of this
+      // lane's rows are requested together (one record round trip per trip, so the trip carries as many as the rows allow)
+      constexpr int kU = 2;
+#ifdef TLOAM_K1_DBG_NOWALK  // timing experiment only
+      len = 0;
+#endif
+      for (int s = 0; s < len; s += kU) {
+        double4 c[kU][NR];
+#pragma unroll
+        for (int u = 0; u < kU; ++u)
+#pragma unroll
+          for (int i = 0; i < NR; ++i) c[u][i] = pts.p[(rs[i] + s + u < re[i]) ? rs[i] + s + u : 0];
+#pragma unroll
+        for (int u = 0; u < kU; ++u)
+#pragma unroll
+          for (int i = 0; i < NR; ++i) {
+            const bool v = rs[i] + s + u < re[i];
+            key_insert<K + 1>(L, key_pack(sqdist(pw.x, pw.y, pw.z, c[u][i].x, c[u][i].y, c[u][i].z), rs[i] + s + u, keep_mask, v));
+          }
+      }
     }
     TL_K1_STAMP(3)
     // merge across the quad: after xor-1 and xor-2 every lane holds the global list (the lanes' candidate
@@ -187,7 +250,7 @@ __device__ __forceinline__ void knn_rows(const GridView& g, const PtsGlobal& pts
     if (!keys_ambiguous<K + 1>(L, keep_mask)) {  // (the same verdict on all lanes of the quad)
       keys_unpack<K, K + 1>(L, pts, pw.x, pw.y, pw.z, keep_mask, tk, xyz);
       TL_K1_STAMP(5)
-    } else {  // redo with the exact (d, original index) order
+    } else {  // redo with the exact (d, original index) order (rare: it stays a row-owner loop at LPQ = 16 too, a record per lane and trip)
       for (int s = 0; s < len; ++s) {
         double4 c[NR];
 #pragma unroll
