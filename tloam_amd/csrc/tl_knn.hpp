@@ -125,17 +125,41 @@ struct NbrXyz {
 };
 // the first K entries as a (distance, position) list: the distance is recomputed from the record, exactly as
 // the scan computed it before truncation (xyz: the records' coordinates are kept as well)
+// REQUEST, THEN USE: the records of a group of at most kUnpackGroup entries are all requested before the first is used (K = 1 and
+// K = 5 are one group, the PCA's K = 20 four: its registers do not grow by the whole list's records), and the distance is
+// computed from the loaded values before `have` selects -- an absent entry loads record 0 and yields +inf / -1.  Written as
+// `have ? sqdist(record) : inf` per entry the select became a branch around each entry's arithmetic with a full wait on its own
+// load in front: K dependent round trips for K independent loads.
+constexpr int kUnpackGroup = 5;
 template <int K, int N>
 __device__ __forceinline__ void keys_unpack(const KeyList<N>& L, const PtsGlobal& pts, double qx, double qy, double qz,
                                             unsigned keep_mask, TopK<K>& tk, NbrXyz<K>* xyz = nullptr) {
 #pragma unroll
-  for (int m = 0; m < K; ++m) {
-    const bool have = L.k[m] < __builtin_inf();
-    const int j = have ? (int)((unsigned)__double2loint(L.k[m]) & ~keep_mask) : 0;
-    const double4 p = pts.p[j];
-    tk.d[m] = have ? sqdist(qx, qy, qz, p.x, p.y, p.z) : __builtin_inf();
-    tk.j[m] = have ? j : -1;
-    if (xyz) { xyz->x[m] = p.x; xyz->y[m] = p.y; xyz->z[m] = p.z; }
+  for (int m0 = 0; m0 < K; m0 += kUnpackGroup) {
+    constexpr int G = K < kUnpackGroup ? K : kUnpackGroup;
+    bool have[G];
+    int j[G];
+    double4 p[G];
+#pragma unroll
+    for (int u = 0; u < G; ++u) {
+      if (m0 + u < K) {
+        have[u] = L.k[m0 + u] < __builtin_inf();
+        j[u] = have[u] ? (int)((unsigned)__double2loint(L.k[m0 + u]) & ~keep_mask) : 0;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < G; ++u)
+      if (m0 + u < K) p[u] = pts.p[j[u]];
+#pragma unroll
+    for (int u = 0; u < G; ++u) {
+      if (m0 + u < K) {
+        const int m = m0 + u;
+        const double d = sqdist(qx, qy, qz, p[u].x, p[u].y, p[u].z);
+        tk.d[m] = have[u] ? d : __builtin_inf();
+        tk.j[m] = have[u] ? j[u] : -1;
+        if (xyz) { xyz->x[m] = p[u].x; xyz->y[m] = p[u].y; xyz->z[m] = p[u].z; }
+      }
+    }
   }
 }
 // the same from the point source (lists that were NOT unpacked from keys: the exact redo of an ambiguous query)

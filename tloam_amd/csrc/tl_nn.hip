@@ -412,24 +412,31 @@ __device__ __forceinline__ void finish_knn5_kept(int kind, const TopK<5>& tk, co
 }
 
 // the (counted | valid << 32) flag of a slot, and its one-byte twin for the self-compacting Solve (SlotView::flagb)
-__device__ __forceinline__ void store_flag(const SlotView& sv, int slot, unsigned long long flag) {
-  sv.flags[slot] = flag;
-  if (sv.flagb) {
-    int kind = 0;
-#pragma unroll
-    for (int k = 1; k < kKinds; ++k) kind += (slot >= sv.slot_off[k]) ? 1 : 0;
-    sv.flagb[kind * kFlagbStride + (slot - sv.slot_off[kind])] =
+// (the slot's kind and that kind's first slot given: the sixteen-lane search holds both in scalar registers)
+__device__ __forceinline__ void store_flag_at(unsigned long long* flags, unsigned char* flagb, int slot, int kind, int kind_off,
+                                              unsigned long long flag) {
+  flags[slot] = flag;
+  if (flagb)
+    flagb[kind * kFlagbStride + (slot - kind_off)] =
         (unsigned char)(((flag >> 32) != 0ull ? 1 : 0) | ((flag & 0xffffffffull) != 0ull ? 2 : 0));
-  }
 }
-__device__ __forceinline__ void store_raw(const SlotView& sv, int slot, const RawRec& r) {
-  store_flag(sv, slot, r.flag);
+__device__ __forceinline__ void store_flag(const SlotView& sv, int slot, unsigned long long flag) {
+  int kind = 0;
+#pragma unroll
+  for (int k = 1; k < kKinds; ++k) kind += (slot >= sv.slot_off[k]) ? 1 : 0;
+  store_flag_at(sv.flags, sv.flagb, slot, kind, sv.slot_off[kind], flag);
+}
+__device__ __forceinline__ void store_raw_rec(double* raw, int slot, const RawRec& r) {
   if ((r.flag >> 32) == 0ull) return;  // no factor: the compaction never looks at the record
-  double2* q = reinterpret_cast<double2*>(sv.raw + (size_t)slot * 8);
+  double2* q = reinterpret_cast<double2*>(raw + (size_t)slot * 8);
   q[0] = double2{r.a[0], r.a[1]};
   q[1] = double2{r.a[2], r.b[0]};
   q[2] = double2{r.b[1], r.b[2]};
   q[3] = double2{r.d, 0.0};
+}
+__device__ __forceinline__ void store_raw(const SlotView& sv, int slot, const RawRec& r) {
+  store_flag(sv, slot, r.flag);
+  store_raw_rec(sv.raw, slot, r);
 }
 
 // ================================================================================================
@@ -472,10 +479,62 @@ struct BuildArgs {
   GridView grid[kKinds];
   BuildParams bp;
   TileMeta tm;
-  int identity_n;   // > 0: no query sort -- query i is source slot i, identity_n of them
   DirectSet ds;     // ds.on: the search writes the factor set itself, row = sorted position (tl_common.hpp DirectSet) ...
   CorrView cv;      // ... into these segments
 };
+
+// The sixteen-lane search (k_build_sorted<16>, the search part of k_build_finish_small) has arguments of its own: what it reads
+// and nothing else, laid out so that a wave asks for ALL of it in its first instructions (wide_search_block).
+//   * WideHead: what addresses are formed from -- the state, the gate, the source coordinates -- and the slot ranges, two to a
+//     dword (a sixteen-lane frame has at most kWideLimit slots).  The kernels take its members as their LEADING SCALAR
+//     arguments, twelve dwords that arrive preloaded in SGPRs (a struct passed by value is never preloaded, wherever it stands):
+//     query i is slot i, so its kind and its wave's kinds follow from registers alone and nothing is loaded to know them.
+//   * WideRest, one struct behind them: per kind the grid header with the kind's radius and activity (contiguous: one scalar
+//     load at an offset by kind), the edge threshold and the output pointers.
+static_assert(kWideLimit <= 0xffff, "WideHead packs the slot ranges of a sixteen-lane frame into 16 bits each");
+struct WideHead {
+  GnState* st;
+  const int* gate;              // k_build_sorted<16>: the pose-moved word of the device-driven loop, or null (always run)
+  const double *sx, *sy, *sz;   // source points (sensor frame)
+  unsigned off12, off3n;        // slot_off[1] | slot_off[2] << 16,  slot_off[3] | slot_off[4] << 16  (slot_off[0] is 0)
+  __device__ __forceinline__ int n() const { return (int)(off3n >> 16); }
+  __device__ __forceinline__ int kind_of(int slot) const {
+    return (slot >= (int)(off12 & 0xffffu) ? 1 : 0) + (slot >= (int)(off12 >> 16) ? 1 : 0) + (slot >= (int)(off3n & 0xffffu) ? 1 : 0);
+  }
+  __device__ __forceinline__ int first_slot(int kind) const {
+    return kind == 0 ? 0 : (int)(kind == 1 ? (off12 & 0xffffu) : (kind == 2 ? (off12 >> 16) : (off3n & 0xffffu)));
+  }
+};
+struct WideKind {
+  GridView g;
+  double radius;
+  int active, pad;
+};
+struct WideTail {
+  double edge_dir_thres;
+  unsigned long long* flags;
+  unsigned char* flagb;
+  double* raw;
+};
+struct WideRest {
+  WideKind kind[kKinds];
+  WideTail t;
+};
+static WideHead wide_head(const SlotView& sv, GnState* st, const int* gate) {
+  return WideHead{st, gate, sv.sx, sv.sy, sv.sz, (unsigned)sv.slot_off[1] | ((unsigned)sv.slot_off[2] << 16),
+                  (unsigned)sv.slot_off[3] | ((unsigned)sv.slot_off[4] << 16)};
+}
+static WideRest wide_rest(const SlotView& sv, const GridView grids[kKinds], const BuildParams& bp) {
+  WideRest R;
+  memset(&R, 0, sizeof(R));
+  for (int k = 0; k < kKinds; ++k) {
+    R.kind[k].g = grids[k];
+    R.kind[k].radius = bp.radius[k];
+    R.kind[k].active = bp.active[k];
+  }
+  R.t = WideTail{bp.edge_dir_thres, sv.flags, sv.flagb, sv.raw};
+  return R;
+}
 
 __device__ __forceinline__ int slot_kind(const SlotView& sv, int slot) {
   int kind = 0;
@@ -598,6 +657,7 @@ __device__ __forceinline__ int k1_prof_which() {   // four sampled one-wave work
 #include "tl_walk.hpp"   // knn_rows (shared with the PCA pass of tl_feature.hip)
 namespace tl {
 
+// (LPQ = 1 and 4, the tile-sorted forms; the sixteen-lane search has its own body, wide_query, with the kind in a scalar register)
 template <int LPQ>
 __device__ __forceinline__ bool query_one(const BuildArgs& A, int kind, const Pose& T, const double4& q, int slot,
                                           int sub, int2* __restrict__ lds_rows, int pos = 0) {
@@ -657,7 +717,7 @@ __device__ __forceinline__ void build_sorted_block(const BuildArgs& A, const GnS
   const int lb0 = ((in_xcd / kXcdChunk) * 8 + xcd) * kXcdChunk + in_xcd % kXcdChunk;  // grid: a multiple of 8 chunks
   // ... and BACK TO FRONT: the sorted list ends with the edge kind (most candidates, eigen solve per query); the
   // expensive blocks are dispatched first so that the cheap ones fill the tail (longest-processing-time first)
-  const int ns = A.identity_n ? A.identity_n : (int)*n_sorted;
+  const int ns = (int)*n_sorted;
   const int nblk = (int)(((long long)ns * LPQ + 63) / 64);
   if (lb0 >= nblk) return;  // whole block past the end (grid rounded up)
   const int lb = nblk - 1 - lb0;
@@ -669,7 +729,7 @@ __device__ __forceinline__ void build_sorted_block(const BuildArgs& A, const GnS
   if (ns <= 0) return;
   const bool live = i < ns;
   const int qi = live ? i : ns - 1;
-  const double4 q = A.identity_n ? double4{A.sv.sx[qi], A.sv.sy[qi], A.sv.sz[qi], __longlong_as_double((long long)qi)} : qrec[qi];
+  const double4 q = qrec[qi];
   const int slot = (int)__double_as_longlong(q.w);
   const int kind = slot_kind(A.sv, slot);
   int row_pos = qi;
@@ -699,14 +759,127 @@ __device__ __forceinline__ void build_sorted_block(const BuildArgs& A, const GnS
     }
   }
 }
+// ---- the sixteen-lane search (KITTI-size frames, slot order: query i is source slot i) ------------------------------------
+// One query of kind `kind` -- the same on every lane that is here, so the kind's header H, the radius and the output pointers sit
+// in scalar registers; T and q were requested at the wave's entry.
+__device__ __forceinline__ void wide_query(const WideTail& R, const WideKind& H, int kind, int kind_off, const Pose& T, const Vec3& q, int slot, int sub) {
+  constexpr int LPQ = 16;   // (TL_K1_STAMP)
+  if (!H.active || H.g.n <= 0) {   // inactive kind / empty target: no factor, nothing counted -- but the sphere builder's counter
+    if (sub == 0) store_flag_at(R.flags, R.flagb, slot, kind, kind_off, (H.active && kind == TLOAM_KIND_SPHERE) ? 1ull : 0ull);
+    return;
+  }
+  TL_K1_STAMP(0)
+  const Vec3 pw = act(T, q);
+  const PtsGlobal pts{H.g.gp};
+  RawRec rec;
+  rec.a[0] = rec.a[1] = rec.a[2] = rec.b[0] = rec.b[1] = rec.b[2] = rec.d = 0.0;
+  rec.flag = 0ull;
+  // (the neighbours' coordinates stay in registers from the records the walk's list was unpacked from: the fits do not fetch them again)
+  if (kind == TLOAM_KIND_SPHERE) {
+    TopK<1> tk;
+    NbrXyz<1> c;
+    knn_rows<1, LPQ>(H.g, pts, pw, sub, tk, nullptr, H.radius, &c);
+    if (sub == 0) finish_sphere_xyz(tk, c.x[0], c.y[0], c.z[0], H.radius, rec);
+  } else {
+    TopK<5> tk;
+    NbrXyz<5> c;
+    knn_rows<5, LPQ>(H.g, pts, pw, sub, tk, nullptr, H.radius, &c);
+#ifdef TLOAM_K1_DBG_NOFIT   // timing experiment only: the walk without the per-query fit
+    if (sub == 0) { rec.a[0] = tk.d[0] + tk.d[4]; rec.flag = (tk.j[4] >= 0) ? ((1ull << 32) | 1ull) : 0ull; }
+#else
+    if (sub == 0) finish_knn5_kept(kind, tk, c, H.radius, R.edge_dir_thres, rec);
+#endif
+  }
+  TL_K1_STAMP(6)
+  if (sub == 0) {
+    store_flag_at(R.flags, R.flagb, slot, kind, kind_off, rec.flag);
+    store_raw_rec(R.raw, slot, rec);
+  }
+  TL_K1_STAMP(7)
+}
+// `v` is in a scalar register at this point of the program: the load that produces it cannot be moved behind it.  (Left alone the
+// compiler sinks every scalar load into the branch that first uses it, and each then waits for a round trip of its own.)
+template <class V>
+__device__ __forceinline__ void arrived_s(const V& v) { asm volatile("" ::"s"(v)); }
+__device__ __forceinline__ void arrived_s(const WideKind& H) {
+  arrived_s(H.g.gp); arrived_s(H.g.cell_start); arrived_s(H.g.org[0]); arrived_s(H.g.org[1]); arrived_s(H.g.org[2]);
+  arrived_s(H.g.inv_cell); arrived_s(H.g.cell); arrived_s(H.g.dim[0]); arrived_s(H.g.dim[1]); arrived_s(H.g.dim[2]);
+  arrived_s(H.g.n); arrived_s(H.radius); arrived_s(H.active);
+}
+// Waves of the search: every kind's slots are cut into waves of four on their own, so a wave's queries are always of ONE kind (the
+// kind's header sits in scalar registers) and the last wave of a kind holds one to four of them.
+static unsigned wide_waves(const int slot_off[kKinds + 1]) {
+  unsigned w = 0;
+  for (int k = 0; k < kKinds; ++k) w += (unsigned)(slot_off[k + 1] - slot_off[k] + 3) / 4;
+  return w;
+}
+// The work of block `b` of the search.  RIDE: the search rides behind a finish (k_build_finish_small) and runs on the minimiser's
+// spec_build unless the loop has stopped; else on the gate word, if there is one.
+// ENTRY IN ONE ROUND: which queries the wave holds and of which kind follows from the preloaded registers, so the gate word(s), the
+// pose, the query's coordinates, the kind's header and the output pointers are all requested before the first of them is used --
+// the early-outs below test values that came with everything else.  (Spelled one after the other -- `if (gate && *gate == 0)`,
+// then the pose, then `A.grid[kind]` with the kind in a vector register -- the entry was eight dependent round trips.)
+template <bool RIDE>
+__device__ __forceinline__ void wide_search_block(const WideHead& A, const WideRest& R, int b) {
+  // block order: chunks of kXcdChunk blocks dealt to the XCDs, back to front (edge kind first) -- see build_sorted_block
+  constexpr int kXcdChunk = 16;
+  const int xcd = b & 7, in_xcd = b >> 3;
+  const int lb0 = ((in_xcd / kXcdChunk) * 8 + xcd) * kXcdChunk + in_xcd % kXcdChunk;
+  // the waves of the four kinds (wide_waves)
+  const int o1 = A.first_slot(1), o2 = A.first_slot(2), o3 = A.first_slot(3), n = A.n();
+  const int w1 = (o1 + 3) >> 2, w2 = w1 + ((o2 - o1 + 3) >> 2), w3 = w2 + ((o3 - o2 + 3) >> 2), nblk = w3 + ((n - o3 + 3) >> 2);
+  if (lb0 >= nblk) return;   // whole block past the end (grid rounded up)
+  const int lb = nblk - 1 - lb0;
+  const int k = (lb >= w1 ? 1 : 0) + (lb >= w2 ? 1 : 0) + (lb >= w3 ? 1 : 0);
+  const int k_first = A.first_slot(k), k_end = k == 3 ? n : A.first_slot(k + 1);
+  const int slot0 = k_first + (lb - (k == 0 ? 0 : (k == 1 ? w1 : (k == 2 ? w2 : w3)))) * 4;   // < k_end: a kind without slots has no wave
+  const int i = slot0 + ((int)threadIdx.x >> 4), sub = (int)threadIdx.x & 15;
+  const int qi = min(i, k_end - 1);   // (the lanes behind the kind's last query ask for its coordinates and leave below)
+  // ---- the requests
+  int word0, stop = 0;   // the gate's word(s)
+  if (RIDE) {
+    // (`stop` may be written by this launch's own finish while it is read here: either value is fine -- see k_build_finish_small --
+    //  but the access is made an atomic one so that it is not a data race)
+    word0 = A.st->spec_build;
+    stop = __hip_atomic_load(&A.st->stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  } else {
+    // no gate = always run: the word is then read from an address that is valid anyway and not looked at, so that no branch on
+    // the pointer stands in front of the other requests
+    const int* const word = A.gate ? A.gate : reinterpret_cast<const int*>(A.st);
+    word0 = *word;
+  }
+  const Pose T = A.st->T_cur;  // exp(se3_pose_)  registration.cpp:434/:524/:578/:721
+  const Vec3 q{A.sx[qi], A.sy[qi], A.sz[qi]};
+  const WideKind H = R.kind[k];
+  const WideTail O = R.t;
+  // ---- ... and their use
+  arrived_s(word0);
+  arrived_s(T.qw); arrived_s(T.qx); arrived_s(T.qy); arrived_s(T.qz); arrived_s(T.tx); arrived_s(T.ty); arrived_s(T.tz);
+  arrived_s(H);
+  arrived_s(O.edge_dir_thres); arrived_s(O.flags); arrived_s(O.flagb); arrived_s(O.raw);
+  // RIDE: the minimiser ended somewhere else than x_build and no earlier iteration has stopped the loop; else, device-driven
+  // outer loop: the pose did not move, the set is only refreshed
+  if (RIDE ? (word0 == 0 || stop != 0) : (A.gate != nullptr && word0 == 0)) return;
+  if (i >= k_end) return;
+  wide_query(O, H, k, k_first, T, q, i, sub);
+}
+
+// <16>: WideHead's members (preloaded), then WideRest
+template <int LPQ>
+__global__ __launch_bounds__(64) void k_build_sorted(GnState* st, const int* gate, const double* sx, const double* sy, const double* sz,
+                                                     unsigned off12, unsigned off3n, WideRest R) {
+  static_assert(LPQ == 16, "the slot-order form of the search");
+#ifdef TLOAM_K1_PROF
+  if (threadIdx.x == 0 && blockIdx.x == 0) g_k1_prof[15] = wall_clock64();   // (about when the launch starts)
+#endif
+  wide_search_block<false>(WideHead{st, gate, sx, sy, sz, off12, off3n}, R, (int)blockIdx.x);
+}
+// <4>, <1>: the tile-sorted forms
 template <int LPQ>
 __global__ __launch_bounds__(64) void k_build_sorted(BuildArgs A, const GnState* __restrict__ st,
                                                      const unsigned long long* __restrict__ n_sorted,
                                                      const double4* __restrict__ qrec, const int* __restrict__ gate, GnState* st_w) {
   if (gate && *gate == 0) return;  // device-driven outer loop: the pose did not move, the set is only refreshed
-#ifdef TLOAM_K1_PROF
-  if (LPQ == 16 && threadIdx.x == 0 && blockIdx.x == 0) g_k1_prof[15] = wall_clock64();   // (about when the launch starts)
-#endif
   __shared__ int2 lds_rows[LPQ == 1 ? 9 * 64 : 1];
   // a direct set is built at the pose this search runs at (what the compaction records for a compact set)
   if (LPQ == 1 && A.ds.on && A.ds.set_x_build && blockIdx.x == 0 && threadIdx.x < 6) st_w->x_build[threadIdx.x] = st->x[threadIdx.x];
@@ -770,6 +943,17 @@ void launch_build(const SlotView& sv, const GridView grids[kKinds], const BuildP
                   unsigned long long* scan1p_ctl, unsigned* scan1p_fault, const CorrView* direct_cv, const DirectSet* ds, bool binned) {
   const int n = sv.slot_off[kKinds];
   if (n <= 0) return;
+  auto grid8 = [](long long threads) { return (unsigned)(((threads + 63) / 64 + 127) / 128 * 128); };  // 8 XCDs x kXcdChunk
+  // KITTI-size frames (sixteen lanes per query) are searched in SLOT order, unsorted: their target records (2-3 MB)
+  // stay L2-resident whatever the order, and the sort's three launches (bin, scan, scatter: 13 us of a 270 us frame)
+  // cost more than its locality saves -- measured with randomly ordered source clouds, the worst case: 0.273 -> 0.261 ms.
+  // The form has arguments of its own (WideHead, WideRest).
+  if (n <= kWideLimit) {
+    const WideHead h = wide_head(sv, st, gate);
+    hipLaunchKernelGGL(k_build_sorted<16>, dim3(grid8(64LL * wide_waves(sv.slot_off))), dim3(64), 0, s, h.st, h.gate, h.sx, h.sy, h.sz, h.off12, h.off3n,
+                       wide_rest(sv, grids, bp));
+    return;
+  }
   BuildArgs A;
   A.sv = sv;
   A.bp = bp;
@@ -778,11 +962,7 @@ void launch_build(const SlotView& sv, const GridView grids[kKinds], const BuildP
   if (direct_cv && ds && n > kQuadLimit) { A.ds = *ds; A.cv = *direct_cv; }
   for (int k = 0; k < kKinds; ++k) A.grid[k] = grids[k];
   const int ntiles = tile_meta(grids, sv.slot_off, &A.tm);   // bins of the counting sort
-  // KITTI-size frames (sixteen lanes per query) are searched in SLOT order, unsorted: their target records (2-3 MB)
-  // stay L2-resident whatever the order, and the sort's three launches (bin, scan, scatter: 13 us of a 270 us frame)
-  // cost more than its locality saves -- measured with randomly ordered source clouds, the worst case: 0.273 -> 0.261 ms.
-  A.identity_n = (n <= kWideLimit) ? n : 0;
-  if (rebin && !A.identity_n) {
+  if (rebin) {
     // The processing ORDER only buys locality -- every query still searches its own exact 27 cells --
     // so the tile sort is done once per frame (first outer iteration, predicted pose) and reused while
     // the pose moves by centimetres.
@@ -795,12 +975,9 @@ void launch_build(const SlotView& sv, const GridView grids[kKinds], const BuildP
   }
   // every slot with a tile is in qrec[0 .. n_binned); n_binned <= n is only known on the device, so the
   // launch covers n positions and the kernel bounds itself by the scanned total
-  auto grid8 = [](long long threads) { return (unsigned)(((threads + 63) / 64 + 127) / 128 * 128); };  // 8 XCDs x kXcdChunk
   // lanes per query: the smaller the frame, the more the build is a latency chain per query and the more lanes
   // pay (KITTI-size 9.4 k queries: 0.371-0.378 ms per frame with 4, 0.36 with 8, 0.348-0.36 with 16)
-  if (n <= kWideLimit)
-    hipLaunchKernelGGL(k_build_sorted<16>, dim3(grid8(16LL * n)), dim3(64), 0, s, A, st, tile_scan + ntiles, qrec, gate, st);
-  else if (n <= kQuadLimit)
+  if (n <= kQuadLimit)
     hipLaunchKernelGGL(k_build_sorted<4>, dim3(grid8(4LL * n)), dim3(64), 0, s, A, st, tile_scan + ntiles, qrec, gate, st);
   else
     hipLaunchKernelGGL(k_build_sorted<1>, dim3(grid8(n)), dim3(64), 0, s, A, st, tile_scan + ntiles, qrec, gate, st);
@@ -830,48 +1007,27 @@ void launch_weights_finish_small(const CorrView& cv, const SlotView& sv, const W
 // EARLIER iteration has stopped the loop; when this finish stops the loop (plateau, last iteration) or finds the Solve
 // unfinished, the records written here are simply never compacted (k_prepare_small is gated on run_build).
 constexpr int kFinishBlocks = 16;
-__global__ __launch_bounds__(64) void k_build_finish_small(BuildArgs A, GnState* st, const int* __restrict__ seg_n,
-                                                           double* __restrict__ sums16, HostMirror hm, OuterCtl ctl,
-                                                           WeightArgs W, FinishRide R) {
+// (arguments: WideHead's members without the gate, and seg_n -- twelve preloaded dwords --, then WideRest and the finish's)
+__global__ __launch_bounds__(64) void k_build_finish_small(GnState* st, const double* sx, const double* sy, const double* sz, unsigned off12,
+                                                           unsigned off3n, const int* __restrict__ seg_n, WideRest S,
+                                                           double* __restrict__ sums16, HostMirror hm, OuterCtl ctl, WeightArgs W,
+                                                           FinishRide R) {
   if (blockIdx.x < kFinishBlocks) {
     weights_finish_small_ride(st, seg_n, sums16, hm, ctl, W, R, (int)blockIdx.x);
     return;
   }
-  // (`stop` may be written by this launch's own finish while it is read here: either value is fine -- see above -- but
-  //  the access is made an atomic one so that it is not a data race)
-  if (st->spec_build == 0 || __hip_atomic_load(&st->stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return;
-  // block order as in k_build_sorted: chunks of kXcdChunk blocks dealt to the XCDs, back to front (edge kind first)
-  constexpr int kXcdChunk = 16;
-  const int b = (int)blockIdx.x - kFinishBlocks;
-  const int xcd = b & 7, in_xcd = b >> 3;
-  const int lb0 = ((in_xcd / kXcdChunk) * 8 + xcd) * kXcdChunk + in_xcd % kXcdChunk;
-  const int n = A.identity_n;
-  const int nblk = (int)(((long long)n * 16 + 63) / 64);
-  if (lb0 >= nblk) return;
-  const int t = (nblk - 1 - lb0) * 64 + (int)threadIdx.x;
-  const int i = t >> 4, sub = t & 15;
-  if (i >= n) return;
-  const double4 q = double4{A.sv.sx[i], A.sv.sy[i], A.sv.sz[i], __longlong_as_double((long long)i)};
-  query_one<16>(A, slot_kind(A.sv, i), st->T_cur, q, i, sub, nullptr);
+  wide_search_block<true>(WideHead{st, nullptr, sx, sy, sz, off12, off3n}, S, (int)blockIdx.x - kFinishBlocks);
 }
 void launch_build_finish_small(const SlotView& sv, const GridView grids[kKinds], const BuildParams& bp, GnState* st,
                                const FinishSmallArgs& fin, hipStream_t s) {
-  const int n = sv.slot_off[kKinds];
-  BuildArgs A;
-  A.sv = sv;
-  A.bp = bp;
-  for (int k = 0; k < kKinds; ++k) A.grid[k] = grids[k];
-  memset(&A.tm, 0, sizeof(A.tm));   // slot order: no tiles
-  memset(&A.ds, 0, sizeof(A.ds));
-  memset(&A.cv, 0, sizeof(A.cv));
-  A.identity_n = n;
   WeightArgs W;
   W.cv = *fin.cv;
   W.sv = sv;
   W.wp = *fin.wp;
-  const unsigned build_blocks = (unsigned)(((16LL * n + 63) / 64 + 127) / 128 * 128);  // 8 XCDs x kXcdChunk, as launch_build
-  hipLaunchKernelGGL(k_build_finish_small, dim3(kFinishBlocks + build_blocks), dim3(64), 0, s, A, st, fin.seg_n, fin.sums16,
-                     fin.hm, fin.ctl, W, FinishRide{fin.rows, fin.ticket});
+  const unsigned build_blocks = (wide_waves(sv.slot_off) + 127) / 128 * 128;  // 8 XCDs x kXcdChunk, as launch_build
+  const WideHead h = wide_head(sv, st, nullptr);
+  hipLaunchKernelGGL(k_build_finish_small, dim3(kFinishBlocks + build_blocks), dim3(64), 0, s, h.st, h.sx, h.sy, h.sz, h.off12, h.off3n, fin.seg_n,
+                     wide_rest(sv, grids, bp), fin.sums16, fin.hm, fin.ctl, W, FinishRide{fin.rows, fin.ticket});
 }
 
 void launch_build_finish_large(const SlotView& sv, const GridView grids[kKinds], const BuildParams& bp, GnState* st,
@@ -883,7 +1039,6 @@ void launch_build_finish_large(const SlotView& sv, const GridView grids[kKinds],
   A.bp = bp;
   for (int k = 0; k < kKinds; ++k) A.grid[k] = grids[k];
   (void)tile_meta(grids, sv.slot_off, &A.tm);   // (as launch_build: the tile metadata of the sorted query order)
-  A.identity_n = 0;
   memset(&A.ds, 0, sizeof(A.ds));
   memset(&A.cv, 0, sizeof(A.cv));
   if (ds) { A.ds = *ds; A.cv = *fin.cv; }
