@@ -1464,6 +1464,90 @@ int tloam_closed_map_read_free(tloam_ctx* ctx, const double* lo_or_null, const d
 int tloam_closed_map_free_columns(tloam_ctx* ctx, double z_lo, double z_hi, int64_t min_free, uint8_t* state_out, size_t capacity,
                                   size_t* nx, size_t* ny);
 
+/* ---- clearance for the closed map: a truncated distance field over the free-space box, and path checks (additive to ABI 8) ----
+ * A dense field over the free-space grid's box: nx = 4 n_bricks[0], ny = 4 n_bricks[1], nz = 4 n_bricks[2] cells, one uint16 a
+ * cell, row-major [z][y][x], x fastest, element (x, y, z) the cell lo_cells + (x, y, z).  The value is d2, the squared distance
+ * IN CELLS, between integer cell coordinates, from the cell to the nearest obstacle cell.  Truncated: with
+ * R = (int) ceil(max_distance / voxel), formed on the host in double, a value <= R * R is stored exact and anything larger is
+ * TLOAM_CLEARANCE_BEYOND.  R must lie in 1 .. 128.
+ * Obstacle cells: the states are tloam_closed_map_occupancy's at the moment of the build, under the free configuration's
+ * min_count / min_miss / miss_ratio / carve_gate.  An OCCUPIED cell is an obstacle.  With unknown_is_obstacle an UNKNOWN cell is
+ * one too, and everything outside the box is unknown (the nearest outside cell of an inside cell lies in the layer next to the
+ * box).  Without it nothing outside the box contributes: the values within R cells of a face of the box are then upper bounds.
+ * Metric meaning: voxel * sqrt(d2) is the distance between the two cells' centres; any point of the cell is at least
+ * voxel * (sqrt(d2) - sqrt(3)) from any point of the obstacle cell.  That margin is the planner's to take.
+ * The field is built by tloam_closed_map_clearance_build and is dropped by whatever changes what it was built from: everything
+ * that drops the free-space grid, tloam_closed_map_free_reset, tloam_closed_map_free_add_keyframes / _free_add_scan (once their
+ * arguments and the grid have been accepted: whether or not the add then succeeds), a successful tloam_closed_map_extend,
+ * tloam_closed_map_carve, the carve's configure, tloam_closed_map_clearance_configure.  After a drop every read of
+ * the field is TLOAM_E_NOT_READY until the next build.  It is not saved in a snapshot; nothing else in the context changes by a
+ * bit.  All values are integers: two builds, and two contexts, give the same bytes.
+ * Every call here on a context with nranks > 1: TLOAM_E_INVALID. */
+#define TLOAM_CLEARANCE_BEYOND 0xFFFF    /* no obstacle within R cells */
+#define TLOAM_CLEARANCE_OUTSIDE 0xFFFE   /* a queried cell outside the box (unknown_is_obstacle 0), or an INVALID point */
+#define TLOAM_CLEARANCE_SKIPPED 0        /* the segment is one ray_begin refuses (the ray-cast's skip rule, max_range = max_segment) */
+#define TLOAM_CLEARANCE_CLEAR 1          /* every visited cell has d2 >= need */
+#define TLOAM_CLEARANCE_BLOCKED 2        /* the walk met a cell with d2 < need */
+#define TLOAM_CLEARANCE_LEFT_BOX 3       /* unknown_is_obstacle 0: the walk met a cell outside the box (status "OUTSIDE") */
+typedef struct tloam_closed_map_clearance_config {   /* the defaults are choices, not measurements */
+  double max_distance;          /* 4.0: the truncation (m); > 0, finite; R = ceil(max_distance / voxel) is checked at the build */
+  double max_segment;           /* 120: a longer segment is skipped (m); > 0, finite */
+  int64_t max_bytes;            /* 1 GiB: a build whose field (both of its buffers) needs more is refused; >= 2 */
+  int32_t unknown_is_obstacle;  /* 1; 0: only OCCUPIED cells are obstacles */
+  int32_t reserved0;
+} tloam_closed_map_clearance_config;
+void tloam_closed_map_clearance_default_config(tloam_closed_map_clearance_config* cfg);
+/* cfg NULL: the defaults.  A value out of its range (NaN too): TLOAM_E_INVALID, and the old configuration stays.  Drops the
+ * field, not the free-space grid; persists across tloam_odometry_reset. */
+int tloam_closed_map_clearance_configure(tloam_ctx* ctx, const tloam_closed_map_clearance_config* cfg);
+typedef struct tloam_closed_map_clearance_info {
+  int64_t lo_cells[3];      /* the box: its lowest cell per axis ... */
+  int64_t n_cells[3];       /* ... its cells per axis (nx, ny, nz) ... */
+  int64_t bytes;            /* ... and what the field holds on the device: 2 buffers * 2 bytes * nx * ny * nz */
+  int64_t obstacle_cells;   /* cells with d2 == 0 */
+  int64_t finite_cells;     /* cells with d2 != TLOAM_CLEARANCE_BEYOND */
+  int64_t sum_d2;           /* over the finite cells */
+  int64_t max_d2;           /* over the finite cells (0 when there is none) */
+  int32_t radius_cells;     /* R */
+  int32_t launches;         /* kernel launches of the build: the same for every input */
+} tloam_closed_map_clearance_info;
+/* Resolves the states, runs the three passes, counts; one wait.  TLOAM_E_NOT_READY without a built map and a free-space grid, or
+ * with carve_gate set on a map that is not carved; TLOAM_E_INVALID for R outside 1 .. 128 or a field of more than max_bytes.  A
+ * refused build leaves the previous field as it was. */
+int tloam_closed_map_clearance_build(tloam_ctx* ctx, tloam_closed_map_clearance_info* info_or_null);
+/* All zero when there is no field. */
+int tloam_closed_map_get_clearance_info(tloam_ctx* ctx, tloam_closed_map_clearance_info* info);
+/* The field's values [first, first + count) as they stand (tloam_closed_map_read_free_words' conventions). */
+int tloam_closed_map_read_clearance(tloam_ctx* ctx, size_t first, size_t count, uint16_t* d2);
+/* Per point (pose NULL: in the map frame; else in the sensor frame of pose_colmajor): state_out [n] as tloam_closed_map_occupancy
+ * gives it, d2_out [n] the value of the point's cell -- a cell outside the box gives 0 with unknown_is_obstacle, else
+ * TLOAM_CLEARANCE_OUTSIDE; an INVALID point gives TLOAM_CLEARANCE_OUTSIDE --, distance_out [n] when not NULL
+ * voxel * sqrt((double) d2), +inf for BEYOND and NaN for OUTSIDE, counts_out [4] when not NULL (points per state).  One launch,
+ * one wait. */
+int tloam_closed_map_clearance_points(tloam_ctx* ctx, const double* points_aos, size_t n, const double* pose_colmajor_or_null,
+                                      uint8_t* state_out, uint16_t* d2_out, double* distance_out_or_null,
+                                      int64_t* counts_out_or_null);
+/* The batched edge check: is the segment starts[i] -> ends[i] clear for a body of `radius` (m)?  need = (int64) ceil(q * q) with
+ * q = radius / voxel, formed on the host in double in that order; radius must be finite and >= 0, and need <= R * R + 1 (the
+ * field cannot vouch for more than R cells): else TLOAM_E_INVALID.  The walk is the ray-cast's (set-up, skip rule and stepping,
+ * max_range = max_segment): the start cell and every cell stepped into, the end cell included.  Each visited cell has the free
+ * walk's t_in (0 for the start cell, else the tMax of the axis the step into it took, read before the step) and a d2 read as
+ * tloam_closed_map_clearance_points reads it.  The walk stops at the first cell outside the box when unknown_is_obstacle is 0
+ * (LEFT_BOX; that cell does not enter min_d2) and at the first cell with d2 < need (BLOCKED); else it runs to the end (CLEAR).
+ * status_out [n]; min_d2_out [n] the minimum of d2 over the visited cells, the stopping one included (BEYOND when none entered;
+ * TLOAM_CLEARANCE_OUTSIDE for SKIPPED); t_block_out [n] when not NULL the stopping cell's t_in, -1.0 for CLEAR and SKIPPED;
+ * counts_out [4] when not NULL (segments per status).  need == 0 never blocks: the call then reports the path's minimum
+ * clearance.  One launch, one wait. */
+int tloam_closed_map_clearance_segments(tloam_ctx* ctx, const double* starts_aos, const double* ends_aos, size_t n,
+                                        const double* pose_colmajor_or_null, double radius, uint8_t* status_out,
+                                        uint16_t* min_d2_out, double* t_block_out_or_null, int64_t* counts_out_or_null);
+/* The 2-D field over tloam_closed_map_free_columns' states (the same band, min_free, sizes and capacity convention): a column's
+ * d2 to the nearest OCCUPIED (with unknown_is_obstacle: or UNKNOWN, or outside) column, under the same R.  Computed per call from
+ * the free-space grid, not stored: it needs no built field.  state_out [*ny * *nx] when not NULL, d2_out [*ny * *nx].  Its two
+ * layers (4 bytes a column) are held to max_bytes as the field is: more is TLOAM_E_INVALID. */
+int tloam_closed_map_clearance_columns(tloam_ctx* ctx, double z_lo, double z_hi, int64_t min_free, uint8_t* state_out_or_null,
+                                       uint16_t* d2_out, size_t capacity, size_t* nx, size_t* ny);
+
 /* ---- the closed map's snapshot: a built closed map out of a context and into a fresh one (additive to ABI 8) ------
  * A memory blob; the library opens no files.  It holds, exactly, everything a context needs to answer every read of the closed
  * map and every localisation in it with the bytes of the context that saved: the place, loop, closed map, carve and surfel

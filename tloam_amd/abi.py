@@ -280,6 +280,28 @@ class FreeInfo(Struct):
 OCCUPANCY_INVALID, OCCUPANCY_UNKNOWN, OCCUPANCY_FREE, OCCUPANCY_OCCUPIED = 0, 1, 2, 3   # TLOAM_OCCUPANCY_*
 
 
+class ClearanceConfig(Struct):
+    """tloam_closed_map_clearance_config: the truncation distance of the field (R = ceil(max_distance / voxel) cells, 1 .. 128,
+    checked at the build), the longest segment a path check walks, the most bytes the field's two buffers may take, and whether
+    an UNKNOWN cell (and everything outside the box) is an obstacle.  The defaults are choices, not
+    measurements."""
+    _c_name_ = "tloam_closed_map_clearance_config"
+    _fields_ = [("max_distance", C.c_double), ("max_segment", C.c_double), ("max_bytes", C.c_int64),
+                ("unknown_is_obstacle", C.c_int32), ("reserved0", C.c_int32)]
+
+
+class ClearanceInfo(Struct):
+    """tloam_closed_map_clearance_info."""
+    _c_name_ = "tloam_closed_map_clearance_info"
+    _fields_ = [("lo_cells", C.c_int64 * 3), ("n_cells", C.c_int64 * 3), ("bytes", C.c_int64), ("obstacle_cells", C.c_int64),
+                ("finite_cells", C.c_int64), ("sum_d2", C.c_int64), ("max_d2", C.c_int64), ("radius_cells", C.c_int32),
+                ("launches", C.c_int32)]
+
+
+CLEARANCE_BEYOND, CLEARANCE_OUTSIDE = 0xFFFF, 0xFFFE   # TLOAM_CLEARANCE_BEYOND, _OUTSIDE
+CLEARANCE_SKIPPED, CLEARANCE_CLEAR, CLEARANCE_BLOCKED, CLEARANCE_LEFT_BOX = 0, 1, 2, 3   # a segment's status
+
+
 SNAPSHOT_CLOUDS = 1   # TLOAM_SNAPSHOT_CLOUDS: the keyframes' eight clouds go into the snapshot too
 
 
@@ -676,6 +698,17 @@ def _signatures():
         "tloam_closed_map_read_free": (C.c_int, [vp, dp, dp, sz, C.POINTER(sz), dp]),
         "tloam_closed_map_free_columns": (C.c_int, [vp, C.c_double, C.c_double, C.c_int64, C.POINTER(C.c_uint8), sz, C.POINTER(sz),
                                                     C.POINTER(sz)]),
+        "tloam_closed_map_clearance_default_config": (None, [C.POINTER(ClearanceConfig)]),
+        "tloam_closed_map_clearance_configure": (C.c_int, [vp, C.POINTER(ClearanceConfig)]),
+        "tloam_closed_map_clearance_build": (C.c_int, [vp, C.POINTER(ClearanceInfo)]),
+        "tloam_closed_map_get_clearance_info": (C.c_int, [vp, C.POINTER(ClearanceInfo)]),
+        "tloam_closed_map_read_clearance": (C.c_int, [vp, sz, sz, C.POINTER(C.c_uint16)]),
+        "tloam_closed_map_clearance_points": (C.c_int, [vp, dp, sz, dp, C.POINTER(C.c_uint8), C.POINTER(C.c_uint16), dp,
+                                                        C.POINTER(C.c_int64)]),
+        "tloam_closed_map_clearance_segments": (C.c_int, [vp, dp, dp, sz, dp, C.c_double, C.POINTER(C.c_uint8),
+                                                          C.POINTER(C.c_uint16), dp, C.POINTER(C.c_int64)]),
+        "tloam_closed_map_clearance_columns": (C.c_int, [vp, C.c_double, C.c_double, C.c_int64, C.POINTER(C.c_uint8),
+                                                         C.POINTER(C.c_uint16), sz, C.POINTER(sz), C.POINTER(sz)]),
         "tloam_closed_map_read_gone": (C.c_int, [vp, dp, dp, C.c_int64, C.c_double, sz, C.POINTER(sz), dp, C.POINTER(C.c_int64),
                                                  C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
         "tloam_closed_map_save_size": (C.c_int, [vp, C.c_int, C.POINTER(sz)]),

@@ -13,15 +13,7 @@
 
 using namespace tl;
 
-namespace {
-
-using FreeState = CmapState::FreeState;
-
-bool free_config_ok(const tloam_closed_map_free_config& m) {
-  return m.max_range > 0.0 && std::isfinite(m.max_range) && m.end_margin >= 0.0 && std::isfinite(m.end_margin) && m.max_bytes >= 8 &&
-         m.min_count >= 1 && m.min_miss >= 0 && m.miss_ratio == m.miss_ratio && m.ray_mask >= 0 && m.ray_mask <= 0xFF &&
-         (m.carve_gate == 0 || m.carve_gate == 1);
-}
+namespace tlh {
 
 // the context and the grid checked for a call that needs one
 int free_ready(const tloam_ctx* c) {
@@ -37,14 +29,26 @@ int free_read_ready(const tloam_ctx* c) {
   return c->cmap.free.cfg.carve_gate && !c->cmap.carved ? TLOAM_E_NOT_READY : TLOAM_OK;
 }
 
-FreeQuery free_query(const CmapState& M) {
-  const FreeState& F = M.free;
+tl::FreeQuery free_query(const CmapState& M) {
+  const CmapState::FreeState& F = M.free;
   FreeQuery q;
   memset(&q, 0, sizeof(q));
   q.grid = map_grid_of(M);
   q.gate = CarveGate{(const long long*)M.miss.p, F.cfg.min_count, F.cfg.min_miss, F.cfg.miss_ratio, F.cfg.carve_gate, 0};
   q.g = F.grid;
   return q;
+}
+
+}  // namespace tlh
+
+namespace {
+
+using FreeState = CmapState::FreeState;
+
+bool free_config_ok(const tloam_closed_map_free_config& m) {
+  return m.max_range > 0.0 && std::isfinite(m.max_range) && m.end_margin >= 0.0 && std::isfinite(m.end_margin) && m.max_bytes >= 8 &&
+         m.min_count >= 1 && m.min_miss >= 0 && m.miss_ratio == m.miss_ratio && m.ray_mask >= 0 && m.ray_mask <= 0xFF &&
+         (m.carve_gate == 0 || m.carve_gate == 1);
 }
 
 // what an add leaves in the info: the last add's counters, the grid's totals
@@ -120,7 +124,8 @@ int tloam_closed_map_free_reset(tloam_ctx* c, const int64_t* lo_cells, const int
   g.words = F.words.p;
   for (int a = 0; a < 3; ++a) { g.blo[a] = (int)B.blo[a]; g.nb[a] = (int)B.nb[a]; }
   g.nwords = (long long)B.words;
-  // from here on the previous grid is gone
+  // from here on the previous grid is gone, and the clearance built from it
+  F.clear.drop();
   F.have = false;
   F.info = tloam_closed_map_free_info{};
   F.grid = g;
@@ -145,6 +150,7 @@ int tloam_closed_map_free_add_keyframes(tloam_ctx* c, tloam_closed_map_free_info
   if (M.detached) return TLOAM_E_NOT_READY;   // (loaded without its clouds: DESIGN.md 25)
   FreeState& F = M.free;
   const tloam_closed_map_free_config& g = F.cfg;
+  F.clear.drop();   // (the clearance was built from the grid as it was)
   CmapPassOut R;
   const int rc = cmap_pass<FreeWork>(
       c, g.ray_mask ? g.ray_mask : M.cfg.cloud_mask, F.ctl,
@@ -175,6 +181,7 @@ int tloam_closed_map_free_add_scan(tloam_ctx* c, const double* points_aos, size_
   if (!pose_finite_rigid(pose)) return TLOAM_E_INVALID;
   CmapState& M = c->cmap;
   FreeState& F = M.free;
+  F.clear.drop();   // (the clearance was built from the grid as it was)
   unsigned long long ctl[kFreeCtl];
   int launches = 0, prepared = 0;
   const int rc = cmap_scan_call(

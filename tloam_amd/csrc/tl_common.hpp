@@ -965,6 +965,58 @@ struct FreeColumnsArgs {
 };
 void launch_free_columns(const FreeColumnsArgs& A, hipStream_t s);
 
+// ---- the closed map's clearance (tl_clear.hip): a dense field of uint16 over the free-space grid's box,
+// [z][y][x], x fastest: d2, the squared distance in cells to the nearest obstacle cell, exact up to R * R, kClearBeyond above.
+// Nothing of the closed map, the carve, the surfels, the diff or the free-space grid is written
+constexpr int kClearCtl = 8;     // control words: [0] obstacle cells, [1] finite cells, [2] the sum of d2, [3] the largest d2;
+                                 // of a query [0..3] the points per state / the segments per status
+constexpr unsigned short kClearBeyond = 0xFFFF, kClearOutside = 0xFFFE;
+constexpr int kClearTile = 64;   // outputs along the pass axis per block of k_clear_axis: its LDS strip is kClearTile + 2 R rows
+struct ClearField {
+  const unsigned short* d2;   // [n[2]][n[1]][n[0]] (null: none -- the seed and the passes take their buffers beside this)
+  int lo[3];                  // the lowest cell of the box per axis
+  int n[3];                   // cells per axis, each a multiple of 4
+  long long cells;
+  int R, wrap;                // wrap: unknown_is_obstacle -- an UNKNOWN cell and everything outside the box is an obstacle
+};
+struct ClearBuildArgs {
+  FreeQuery q;
+  ClearField f;               // (f.d2 is not read)
+  unsigned short *out, *tmp;  // [cells] each: seed -> tmp, x: tmp -> out, y: out -> tmp, z: tmp -> out
+  unsigned long long* ctl;    // [kClearCtl], zero before the launches
+};
+int launch_clear_build(const ClearBuildArgs& A, hipStream_t s);   // seed | voxels | x | y | z | count; returns the launches
+struct ClearPointsArgs {
+  FreeQuery q;
+  ClearField f;
+  ScanAt scan;                // the points, and the pose when `posed`
+  int posed, reserved0;
+  unsigned char* state;       // [n]
+  unsigned short* d2;         // [n]
+  double* distance;           // [n] or null
+  unsigned long long* ctl;    // [0..3] points per state, zero before the launch
+};
+void launch_clear_points(const ClearPointsArgs& A, hipStream_t s);
+struct ClearSegmentsArgs {
+  MapGrid grid;               // the closed map's grid (its table is not read)
+  ClearField f;
+  ScanAt scan;                // the segments' ends, and the pose when `posed`
+  const double* starts;       // [3 n] AoS
+  int posed, need;            // need: a cell with d2 < need blocks
+  double max_segment;
+  unsigned char* status;      // [n]
+  unsigned short* min_d2;     // [n]
+  double* t_block;            // [n] or null
+  unsigned long long* ctl;    // [0..3] segments per status, zero before the launch
+};
+void launch_clear_segments(const ClearSegmentsArgs& A, hipStream_t s);
+struct ClearColumnsArgs {
+  const unsigned char* state; // [ny][nx] of k_free_columns
+  int nx, ny, R, wrap;
+  unsigned short *out, *tmp;  // [ny][nx] each: seed -> out, x: out -> tmp, y: tmp -> out
+};
+int launch_clear_columns(const ClearColumnsArgs& A, hipStream_t s);   // seed | x | y; returns the launches
+
 // ---- deskew of a scan under constant velocity (tl_deskew.hip) -------------
 struct DeskewArgs {
   const double* in;               // AoS xyz [3n]

@@ -470,6 +470,7 @@ struct CmapState {
   void drop_carve() {
     carved = false;
     carve_info = tloam_closed_map_carve_info{};
+    free.clear.drop();             // the clearance may have been built under the gate
   }
   // the surfels (tl_api_surfel.hip): their configuration, the thirteen sums, the normals and the variances
   // in id order beside the rows (allocated by the first pass, for the rows' capacity), what the last pass reports, the box read's
@@ -544,11 +545,31 @@ struct CmapState {
     tl::FreeGrid grid{};
     bool have = false;             // a reset has succeeded since the last drop
     tloam_closed_map_free_info info{};
+    // the clearance (tl_api_clear.hip): its configuration, the field and the buffer its passes alternate
+    // with, what the last build reports, a segment call's starts and outputs and a column call's two layers (grow-only scratch;
+    // the other outputs: scan_u8).  The field belongs to the grid and the map it was built from: whatever changes either drops it
+    struct ClearState {
+      tloam_closed_map_clearance_config cfg;   // tloam_closed_map_clearance_default_config until configured
+      ClearState() { tloam_closed_map_clearance_default_config(&cfg); }
+      DBuf<unsigned short> d2, tmp, out_u16, col_a, col_b;
+      DBuf<double> starts, out_f64;
+      tl::ClearField field{};
+      bool have = false;           // a build has succeeded since the last drop
+      tloam_closed_map_clearance_info info{};
+      void drop() {
+        have = false;
+        info = tloam_closed_map_clearance_info{};
+        field = tl::ClearField{};
+        d2.release();              // (hipFree waits for the launches that use them)
+        tmp.release();
+      }
+    } clear;
     void drop() {
       have = false;
       info = tloam_closed_map_free_info{};
       grid = tl::FreeGrid{};
       words.release();             // (hipFree waits for the launches that use it)
+      clear.drop();
     }
   } free;
   void drop() {   // the closed map goes, and the carve's counts, the surfels, the diff's counts, the last ray-cast's info and the free-space
@@ -1118,6 +1139,11 @@ bool loop_config_valid(const tloam_loop_config& cfg);               // tl_api_lo
 bool cmap_config_valid(const tloam_closed_map_config& cfg);         // tl_api_cmap.hip
 size_t cmap_default_reserve();
 bool carve_config_valid(const tloam_closed_map_carve_config& cfg);  // tl_api_carve.hip
+// tl_api_free.hip, for the clearance built from the grid (tl_api_clear.hip): the context and the grid checked for a call that
+// needs one, the same for a read (which resolves occupancy: the gate needs the carve's counts), and what a read resolves it with
+int free_ready(const tloam_ctx* c);
+int free_read_ready(const tloam_ctx* c);
+tl::FreeQuery free_query(const CmapState& M);
 // tl_api_localise.hip: the localiser's voxel records {c, n, eligible} sized and, when they are stale, their rebuild enqueued
 // (*prepared = 1; k_loc_prepare).  cmap_scan_call sets CmapState::loc_ready once the call that asked for them has succeeded
 int loc_records_prepare(tloam_ctx* c, int* prepared);

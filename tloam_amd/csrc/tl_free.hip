@@ -47,16 +47,6 @@ __device__ __forceinline__ void free_flush(const FreeGrid& g, long long idx, uns
   if ((w & bits) != bits) (void)__hip_atomic_fetch_or(&g.words[idx], bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// the brick word of cell (cx, cy, cz), -1 outside the box
-__device__ __forceinline__ long long free_brick(const FreeGrid& g, int cx, int cy, int cz) {
-  const unsigned bx = (unsigned)((cx >> 2) - g.blo[0]), by = (unsigned)((cy >> 2) - g.blo[1]), bz = (unsigned)((cz >> 2) - g.blo[2]);
-  if (!(bx < (unsigned)g.nb[0] && by < (unsigned)g.nb[1] && bz < (unsigned)g.nb[2])) return -1;
-  return ((long long)bz * g.nb[1] + (long long)by) * g.nb[0] + (long long)bx;
-}
-__device__ __forceinline__ unsigned long long free_bit(int cx, int cy, int cz) {
-  return 1ull << (((cz & 3) << 4) | ((cy & 3) << 2) | (cx & 3));
-}
-
 // one ray from O to E: *skipped, *marked, *outside are set for it (a skipped ray: 1, 0, 0)
 __device__ __forceinline__ void free_ray(const FreeWork& W, double Ox, double Oy, double Oz, double Ex, double Ey, double Ez,
                                          unsigned long long* skipped, unsigned long long* marked, unsigned long long* outside) {
@@ -83,9 +73,7 @@ __device__ __forceinline__ void free_ray(const FreeWork& W, double Ox, double Oy
     } else {
       ++out;
     }
-    const bool y = R.ty < R.tx;            // the axis ray_step is about to take, and its tMax before the step
-    const bool z = R.tz < (y ? R.ty : R.tx);
-    t_in = z ? R.tz : y ? R.ty : R.tx;
+    t_in = ray_next_t(R);
     ray_step(&R);
   }
   free_flush(W.g, cur, bits);
@@ -139,12 +127,6 @@ __global__ __launch_bounds__(256) void k_free_count(FreeWork W) {
   wave_add(&W.ctl[4], bricks);
 }
 
-// the id of the voxel of cell (cx, cy, cz) when it has one that counts, else -1
-__device__ __forceinline__ int free_counting_voxel(const FreeQuery& q, int cx, int cy, int cz) {
-  const int id = cell_voxel(q.grid.map, cx, cy, cz);
-  return id >= 0 && q.gate.counts(q.grid.map, id) ? id : -1;
-}
-
 __global__ __launch_bounds__(256) void k_free_points(FreePointsArgs A) {
   const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
   const bool live = g < A.scan.n;
@@ -157,14 +139,7 @@ __global__ __launch_bounds__(256) void k_free_points(FreePointsArgs A) {
     int id = -1;
     if (vmap_quantise(E, A.q.grid.origin, A.q.grid.voxel, &key, qq) == kVmapInside) {
       const int cx = (int)key_axis(key, 0), cy = (int)key_axis(key, 1), cz = (int)key_axis(key, 2);
-      id = free_counting_voxel(A.q, cx, cy, cz);
-      if (id >= 0) {
-        state = TLOAM_OCCUPANCY_OCCUPIED;
-      } else {
-        const long long idx = free_brick(A.q.g, cx, cy, cz);
-        const bool seen = idx >= 0 && (A.q.g.words[idx] & free_bit(cx, cy, cz)) != 0ull;
-        state = seen ? TLOAM_OCCUPANCY_FREE : TLOAM_OCCUPANCY_UNKNOWN;
-      }
+      state = free_cell_state(A.q, cx, cy, cz, &id);
     }
     A.state[g] = (unsigned char)state;
     if (A.ids) A.ids[g] = id;

@@ -592,6 +592,14 @@ __device__ __forceinline__ void ray_step(RayCells* R) {
   }
 }
 
+// the tMax of the axis ray_step is about to take (its axis choice: the smallest, a tie going to the lowest axis), read before
+// the step: the entry parameter t_in of the cell the step leads into (the free walk, tl_free.hip; the clearance's segments)
+__device__ __forceinline__ double ray_next_t(const RayCells& R) {
+  const bool y = R.ty < R.tx;
+  const bool z = R.tz < (y ? R.ty : R.tx);
+  return z ? R.tz : y ? R.ty : R.tx;
+}
+
 // Every visited cell looked up in the map's slot table, the miss test against an occupied cell's centroid (radius2 = radius *
 // radius).  on_miss(id) is what a miss does; *skipped, *steps, *tested, *misses are set for the ray (a skipped ray: 1, 0, 0, 0).
 template <class OnMiss>
@@ -644,6 +652,30 @@ __device__ __forceinline__ int ray_first_hit(const VmapTableView& map, RayCells*
   }
   *visited = seen;
   return got;
+}
+
+// ---- the free-space grid's cells (tl_free.hip; section 30: the clearance built from them, tl_clear.hip) ----
+// the brick word of cell (cx, cy, cz), -1 outside the box
+__device__ __forceinline__ long long free_brick(const FreeGrid& g, int cx, int cy, int cz) {
+  const unsigned bx = (unsigned)((cx >> 2) - g.blo[0]), by = (unsigned)((cy >> 2) - g.blo[1]), bz = (unsigned)((cz >> 2) - g.blo[2]);
+  if (!(bx < (unsigned)g.nb[0] && by < (unsigned)g.nb[1] && bz < (unsigned)g.nb[2])) return -1;
+  return ((long long)bz * g.nb[1] + (long long)by) * g.nb[0] + (long long)bx;
+}
+__device__ __forceinline__ unsigned long long free_bit(int cx, int cy, int cz) {
+  return 1ull << (((cz & 3) << 4) | ((cy & 3) << 2) | (cx & 3));
+}
+// the id of the voxel of cell (cx, cy, cz) when it has one that counts, else -1
+__device__ __forceinline__ int free_counting_voxel(const FreeQuery& q, int cx, int cy, int cz) {
+  const int id = cell_voxel(q.grid.map, cx, cy, cz);
+  return id >= 0 && q.gate.counts(q.grid.map, id) ? id : -1;
+}
+// the occupancy of cell (cx, cy, cz), |c| < 2^kVmapBits (TLOAM_OCCUPANCY_*: never INVALID); *id: its counting voxel or -1
+__device__ __forceinline__ int free_cell_state(const FreeQuery& q, int cx, int cy, int cz, int* id) {
+  *id = free_counting_voxel(q, cx, cy, cz);
+  if (*id >= 0) return TLOAM_OCCUPANCY_OCCUPIED;
+  const long long idx = free_brick(q.g, cx, cy, cz);
+  const bool seen = idx >= 0 && (q.g.words[idx] & free_bit(cx, cy, cz)) != 0ull;
+  return seen ? TLOAM_OCCUPANCY_FREE : TLOAM_OCCUPANCY_UNKNOWN;
 }
 
 }  // namespace tl

@@ -337,3 +337,69 @@ def write_free_pcd(path: str, H, lo=None, hi=None, ascii: bool = False) -> int:
     cen = H.closed_map_free_cells(lo, hi)
     write_pcd(path, cen, ascii=ascii)
     return len(cen)
+
+
+# ---- the closed map's clearance: the free cells with their distance to the nearest obstacle
+_CLEAR_FIELDS = ("x", "y", "z", "distance")
+
+
+def write_clearance_pcd(path: str, H, lo=None, hi=None, ascii: bool = False) -> int:
+    """Writes the centres `H.closed_map_free_cells` reads (a HipRegistration after closed_map_clearance_build) with
+    voxel * sqrt(d2) of each as a fourth field, `distance` (inf beyond the field's radius), as PCD v0.7, four float64 (`F 8`)
+    -> the cells written."""
+    cen = H.closed_map_free_cells(lo, hi)
+    n = len(cen)
+    dist = H.closed_map_clearance_points(cen)[2] if n else np.zeros(0)
+    rec = np.ascontiguousarray(np.concatenate([cen.reshape(n, 3), dist.reshape(n, 1)], axis=1), dtype="<f8")
+    header = ("# .PCD v0.7 - Point Cloud Data file format\n"
+              "VERSION 0.7\n"
+              "FIELDS x y z distance\n"
+              "SIZE 8 8 8 8\n"
+              "TYPE F F F F\n"
+              "COUNT 1 1 1 1\n"
+              f"WIDTH {n}\n"
+              "HEIGHT 1\n"
+              "VIEWPOINT 0 0 0 1 0 0 0\n"
+              f"POINTS {n}\n"
+              f"DATA {'ascii' if ascii else 'binary'}\n")
+    with open(path, "wb") as fh:
+        fh.write(header.encode("ascii"))
+        if ascii:
+            fh.write("".join(" ".join(f"{v:.17g}" for v in row) + "\n" for row in rec.tolist()).encode("ascii"))
+        else:
+            fh.write(rec.tobytes())
+    return n
+
+
+def read_clearance_pcd(path: str):
+    """Reads a file of write_clearance_pcd (DATA ascii or binary) -> (centres (n, 3) float64, distance (n,) float64)."""
+    with open(path, "rb") as fh:
+        raw = fh.read()
+    head, pos = {}, 0
+    while True:
+        end = raw.index(b"\n", pos)
+        line = raw[pos:end].decode("ascii").strip()
+        pos = end + 1
+        if not line or line.startswith("#"):
+            continue
+        key, _, val = line.partition(" ")
+        head[key.upper()] = val.split()
+        if key.upper() == "DATA":
+            break
+    if tuple(head.get("FIELDS", ())) != _CLEAR_FIELDS or head.get("SIZE") != ["8"] * 4 or head.get("TYPE") != ["F"] * 4:
+        raise ValueError(f"{path}: only FIELDS x y z distance with SIZE 8 / TYPE F are read")
+    n = int(head["POINTS"][0])
+    kind = head["DATA"][0]
+    if kind == "binary":
+        body = raw[pos: pos + 32 * n]
+        if len(body) != 32 * n:
+            raise ValueError(f"{path}: {len(body)} bytes of data for {n} cells")
+        rec = np.frombuffer(body, dtype="<f8").reshape(n, 4)
+    elif kind == "ascii":
+        rows = raw[pos:].split()
+        if len(rows) != 4 * n:
+            raise ValueError(f"{path}: {len(rows)} values for {n} cells")
+        rec = np.array([float(v) for v in rows], dtype=np.float64).reshape(n, 4)
+    else:
+        raise ValueError(f"{path}: DATA {kind} is not supported")
+    return np.ascontiguousarray(rec[:, :3]), np.ascontiguousarray(rec[:, 3])

@@ -39,6 +39,10 @@ def _u8p(a):
     return None if a is None else a.ctypes.data_as(C.POINTER(C.c_uint8))
 
 
+def _u16p(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_uint16))
+
+
 def _per_point(n, want_ids):
     """the per-point outputs of a scan query, never empty -> (bytes (max(n, 1),) uint8, ids (max(n, 1),) int32 or None, cut);
     cut(a): the first n of `a` as the caller's own copy (None stays None)"""
@@ -95,6 +99,7 @@ _CONFIGS = {
     ClosedMapDiffConfig: ("tloam_closed_map_diff_default_config", {}),
     ClosedMapRaycastConfig: ("tloam_closed_map_raycast_default_config", {}),
     FreeConfig: ("tloam_closed_map_free_default_config", {}),
+    ClearanceConfig: ("tloam_closed_map_clearance_default_config", {}),
 }
 
 
@@ -1031,6 +1036,69 @@ class HipRegistration:
                    C.byref(ny))
         return out[: nx.value * ny.value].reshape(ny.value, nx.value).copy()
 
+    # ---- clearance for the closed map: a truncated distance field over the free-space box, and path checks
+    def closed_map_clearance_configure(self, cfg: ClearanceConfig | None = None, **over):
+        """the clearance's configuration (default_closed_map_clearance_config(**over) when cfg is None); drops the field, not the
+        free-space grid.  Kept across odometry_reset; a refused configuration leaves the old one."""
+        self._configure(ClearanceConfig, "tloam_closed_map_clearance_configure", cfg, over)
+
+    def closed_map_clearance_build(self) -> dict:
+        """builds the field over the free-space grid's box from the occupancy as it stands -> info dict"""
+        return self._info(ClearanceInfo, "tloam_closed_map_clearance_build")
+
+    def closed_map_clearance_info(self) -> dict:
+        return self._info(ClearanceInfo, "tloam_closed_map_get_clearance_info")
+
+    def closed_map_clearance_field(self):
+        """the whole field -> (nz, ny, nx) uint16: d2 in cells, CLEARANCE_BEYOND beyond radius_cells"""
+        nx, ny, nz = self.closed_map_clearance_info()["n_cells"]
+        d2 = np.zeros(max(nx * ny * nz, 1), np.uint16)
+        self._call("tloam_closed_map_read_clearance", 0, nx * ny * nz, _u16p(d2))
+        return d2[: nx * ny * nz].reshape(nz, ny, nx).copy()
+
+    def closed_map_clearance_points(self, points, pose=None, want_distance=True):
+        """the clearance of `points` (n, 3; in the map frame, or with `pose` (4 x 4) in its sensor frame) -> (states (n,) uint8 as
+        closed_map_occupancy, d2 (n,) uint16, distance (n,) float64 = voxel * sqrt(d2) -- inf for CLEARANCE_BEYOND, NaN for
+        CLEARANCE_OUTSIDE -- or None without want_distance, counts (4,) int64 of points per state)"""
+        pts = _aos(points)
+        n = len(pts)
+        state, _, cut = _per_point(n, False)
+        d2 = np.zeros(max(n, 1), np.uint16)
+        dist = np.zeros(max(n, 1), np.float64) if want_distance else None
+        counts = np.zeros(4, np.int64)
+        self._call("tloam_closed_map_clearance_points", _dp(pts), n, None if pose is None else _dp(_colmajor(pose)), _u8p(state),
+                   _u16p(d2), _dp(dist), _lp(counts))
+        return cut(state), cut(d2), cut(dist), counts
+
+    def closed_map_clearance_segments(self, starts, ends, radius, pose=None):
+        """is each segment starts[i] -> ends[i] ((n, 3) each; map frame, or the sensor frame of `pose`) clear for a body of
+        `radius` metres? -> (status (n,) uint8: CLEARANCE_SKIPPED, _CLEAR, _BLOCKED, _LEFT_BOX; min_d2 (n,) uint16 over the cells
+        walked; t_block (n,) float64, the parameter along the segment where the walk stopped, -1 when it did not; counts (4,)
+        int64 of segments per status).  radius 0 never blocks: min_d2 is then the path's clearance."""
+        a, b = _aos(starts), _aos(ends)
+        if len(a) != len(b):
+            raise ValueError(f"{len(a)} starts, {len(b)} ends")
+        n = len(a)
+        status, _, cut = _per_point(n, False)
+        d2 = np.zeros(max(n, 1), np.uint16)
+        t = np.zeros(max(n, 1), np.float64)
+        counts = np.zeros(4, np.int64)
+        self._call("tloam_closed_map_clearance_segments", _dp(a), _dp(b), n, None if pose is None else _dp(_colmajor(pose)),
+                   float(radius), _u8p(status), _u16p(d2), _dp(t), _lp(counts))
+        return cut(status), cut(d2), cut(t), counts
+
+    def closed_map_clearance_columns(self, z_lo, z_hi, min_free=1):
+        """the 2-D field over closed_map_free_columns' grid -> (states (ny, nx) uint8, d2 (ny, nx) uint16 in cells to the nearest
+        obstacle column); computed per call from the free-space grid"""
+        nb = self.closed_map_free_info()["n_bricks"]
+        nx, ny = C.c_size_t(0), C.c_size_t(0)
+        m = max(16 * nb[0] * nb[1], 1)
+        state, d2 = np.zeros(m, np.uint8), np.zeros(m, np.uint16)
+        self._call("tloam_closed_map_clearance_columns", float(z_lo), float(z_hi), int(min_free), _u8p(state), _u16p(d2), m,
+                   C.byref(nx), C.byref(ny))
+        shape = (ny.value, nx.value)
+        return state[: shape[0] * shape[1]].reshape(shape).copy(), d2[: shape[0] * shape[1]].reshape(shape).copy()
+
     def fitness(self):
         f, r = C.c_double(0), C.c_double(0)
         rc = self.L.tloam_fitness(self.h, C.byref(f), C.byref(r))
@@ -1264,6 +1332,12 @@ def default_closed_map_free_config(**over) -> FreeConfig:
     """tloam_closed_map_free_default_config (max_range 60, end_margin 1, ray_mask 0: the build's, max_bytes 1 GiB, min_count 1,
     min_miss 3, miss_ratio 1, carve_gate 0) with keyword overrides; an unknown field raises"""
     return _default(FreeConfig, over)
+
+
+def default_closed_map_clearance_config(**over) -> ClearanceConfig:
+    """tloam_closed_map_clearance_default_config (max_distance 4, max_segment 120, max_bytes 1 GiB, unknown_is_obstacle 1) with
+    keyword overrides; an unknown field raises"""
+    return _default(ClearanceConfig, over)
 
 
 def default_closed_map_diff_config(**over) -> ClosedMapDiffConfig:
