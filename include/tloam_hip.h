@@ -1548,6 +1548,111 @@ int tloam_closed_map_clearance_segments(tloam_ctx* ctx, const double* starts_aos
 int tloam_closed_map_clearance_columns(tloam_ctx* ctx, double z_lo, double z_hi, int64_t min_free, uint8_t* state_out_or_null,
                                        uint16_t* d2_out, size_t capacity, size_t* nx, size_t* ny);
 
+/* ---- the route through the closed map: a cost-to-go field from goals, its reads and paths (additive to ABI 8) -------
+ * A dense field over the built clearance field's box (nx, ny, nz cells, row-major [z][y][x], x fastest, element (x, y, z) the
+ * cell lo_cells + (x, y, z)), one uint32 a cell: the least total weight of a chain of moves from the cell to any accepted goal.
+ * Traversable cells: need = (int64) ceil(q * q) with q = radius / voxel, formed on the host in double in that order
+ * (tloam_closed_map_clearance_segments' need, by the same function); radius must be finite and >= 0 and need <= R * R + 1, else
+ * TLOAM_E_INVALID.  A cell is traversable iff its d2 >= max(need, 1); TLOAM_CLEARANCE_BEYOND passes every need.  An UNKNOWN
+ * cell is traversable or not through unknown_is_obstacle at the clearance build alone, which made its d2 zero or not.  Nothing
+ * outside the box is traversable, whatever unknown_is_obstacle says.
+ * Moves: 26-connected, allowed between any two traversable cells that differ by at most one on every axis, WITH NO FURTHER
+ * CORNER RULE: a diagonal move is allowed when the face-adjacent cells it passes between are not traversable.  A planner
+ * confirms a path with tloam_closed_map_clearance_segments.  Weights: the 3-4-5 chamfer, 3 for a face step, 4 for an edge step,
+ * 5 for a vertex step.  The value is 0 at an accepted goal's cell, TLOAM_ROUTE_UNREACHED at a traversable cell no goal reaches
+ * and TLOAM_ROUTE_BLOCKED at a cell that is not traversable.  A build is refused (TLOAM_E_INVALID) when
+ * 5 * cells >= TLOAM_ROUTE_OUTSIDE: no cost can meet a sentinel.
+ * Metric length: voxel * (double) cost / 3.0, in that order.  The 3-4-5 mask is Borgefors' ("Distance transformations in
+ * arbitrary dimensions", CVGIP 27, 1984; "Distance transformations in digital images", CVGIP 34, 1986).  Over free space a
+ * displacement (a >= b >= c >= 0) costs 3 a + b + c, so cost / 3 lies between 0.9428 (= (4 / 3) / sqrt(2), the face diagonal)
+ * and 1.1055 (= sqrt(11 / 9), at b = c = a / 3) times the Euclidean length; with 3 and 4 alone in a plane between 0.9428 and
+ * 1.0541 (= sqrt(10 / 9)).  Along the axes it is exact.  DESIGN.md section 31 has the two lines of the derivation.
+ * Goals: n >= 1 points, in the map frame (pose NULL) or in the sensor frame of pose_colmajor.  A goal whose cell is traversable
+ * is accepted, duplicates each counted; any other -- outside the box, an INVALID point, a cell that is not traversable -- is
+ * rejected.  With no goal accepted the build is TLOAM_OK and every traversable cell is TLOAM_ROUTE_UNREACHED.
+ * The field is built by tloam_closed_map_route_build and dropped with the clearance field (everything that drops it), by a
+ * successful tloam_closed_map_clearance_build (the field it was built from is replaced) and by
+ * tloam_closed_map_route_configure.  After a drop every read is TLOAM_E_NOT_READY until the next build.  It is not saved in a
+ * snapshot; nothing else in the context changes by a bit.
+ * The field is the unique fixpoint of min-plus relaxation, so every byte of it, and every info field but the four marked
+ * DIAGNOSTIC below, is the same for two builds and for two contexts.  tile_updates, rounds, launches and waits depend on the
+ * order in which the device's blocks saw each other's values and MAY DIFFER FROM RUN TO RUN.
+ * Every call here on a context with nranks > 1: TLOAM_E_INVALID. */
+#define TLOAM_ROUTE_UNREACHED 0xFFFFFFFFu   /* a traversable cell no accepted goal reaches */
+#define TLOAM_ROUTE_BLOCKED 0xFFFFFFFEu     /* a cell that is not traversable */
+#define TLOAM_ROUTE_OUTSIDE 0xFFFFFFFDu     /* a queried cell outside the box, or an INVALID point */
+#define TLOAM_ROUTE_PATH_OUTSIDE 0          /* the start is outside the box or INVALID: no waypoint */
+#define TLOAM_ROUTE_PATH_REACHED 1          /* the path ends at a cell of cost 0 */
+#define TLOAM_ROUTE_PATH_UNREACHED 2        /* the start's cell is TLOAM_ROUTE_UNREACHED: no waypoint */
+#define TLOAM_ROUTE_PATH_BLOCKED 3          /* the start's cell is TLOAM_ROUTE_BLOCKED: no waypoint */
+#define TLOAM_ROUTE_PATH_TRUNCATED 4        /* the path has more than max_cells cells: the first max_cells are written */
+typedef struct tloam_closed_map_route_config {   /* choices, not measurements */
+  int64_t max_bytes;         /* 1 GiB: a build whose field and tile flags need more is refused; >= 4 */
+  int32_t max_rounds;        /* 65536: a build that needs more rounds fails; >= 1 */
+  int32_t rounds_per_wait;   /* 16: rounds enqueued between two waits of the host; 1 .. 1024 */
+} tloam_closed_map_route_config;
+void tloam_closed_map_route_default_config(tloam_closed_map_route_config* cfg);
+/* cfg NULL: the defaults.  A value out of its range: TLOAM_E_INVALID, and the old configuration stays.  Drops the route field
+ * only; persists across tloam_odometry_reset. */
+int tloam_closed_map_route_configure(tloam_ctx* ctx, const tloam_closed_map_route_config* cfg);
+typedef struct tloam_closed_map_route_info {
+  int64_t lo_cells[3];         /* the box: its lowest cell per axis ... */
+  int64_t n_cells[3];          /* ... its cells per axis (nx, ny, nz) ... */
+  int64_t bytes;               /* ... and what the field holds on the device: 4 bytes a cell and 8 bytes a tile of flags */
+  int64_t need;                /* a cell is traversable iff d2 >= max(need, 1) */
+  int64_t goals_accepted;
+  int64_t goals_rejected;
+  int64_t traversable_cells;   /* cells whose value is not TLOAM_ROUTE_BLOCKED */
+  int64_t reached_cells;       /* cells with a cost */
+  int64_t sum_cost;            /* over the reached cells */
+  int64_t max_cost;            /* over the reached cells (0 when there is none) */
+  int64_t tile_updates;        /* DIAGNOSTIC: tiles relaxed, over all rounds */
+  int32_t rounds;              /* DIAGNOSTIC: rounds that ran until one marked nothing */
+  int32_t launches;            /* DIAGNOSTIC: kernel launches of the build */
+  int32_t waits;               /* DIAGNOSTIC: waits of the host */
+  int32_t reserved0;
+} tloam_closed_map_route_info;
+/* Seeds the field from the clearance field and the goals, relaxes it in rounds (rounds_per_wait launches between two waits)
+ * until a round lowers nothing, counts.  TLOAM_E_NOT_READY without a built clearance field; TLOAM_E_INVALID for n == 0, a NULL
+ * goals, a bad pose, a bad radius, a field and flags of more than max_bytes or 5 * cells >= TLOAM_ROUTE_OUTSIDE: a refused
+ * build leaves the previous route field as it was.  A failure after the first launch drains the stream and drops the field;
+ * running out of max_rounds drops the field and returns TLOAM_E_HIP, tloam_last_error naming the cap. */
+int tloam_closed_map_route_build(tloam_ctx* ctx, const double* goals_aos, size_t n, const double* pose_colmajor_or_null,
+                                 double radius, tloam_closed_map_route_info* info_or_null);
+/* All zero when there is no field. */
+int tloam_closed_map_get_route_info(tloam_ctx* ctx, tloam_closed_map_route_info* info);
+/* The field's values [first, first + count) as they stand (tloam_closed_map_read_clearance's conventions). */
+int tloam_closed_map_read_route(tloam_ctx* ctx, size_t first, size_t count, uint32_t* cost);
+/* Per point (pose NULL: in the map frame; else in the sensor frame of pose_colmajor): cost_out [n] the value of the point's
+ * cell, TLOAM_ROUTE_OUTSIDE for a cell outside the box or an INVALID point; distance_out [n] when not NULL
+ * voxel * (double) cost / 3.0, +inf for UNREACHED and NaN for BLOCKED and OUTSIDE; counts_out [4] when not NULL: points reached /
+ * unreached / blocked / outside.  One launch, one wait. */
+int tloam_closed_map_route_points(tloam_ctx* ctx, const double* points_aos, size_t n, const double* pose_colmajor_or_null,
+                                  uint32_t* cost_out, double* distance_out_or_null, int64_t* counts_out_or_null);
+/* Per start a path descended from the field.  The first waypoint is the start's own cell.  From a cell of cost k > 0 the next
+ * cell is the first neighbour, in the order dz outermost, then dy, then dx, each running -1, 0, 1, whose value c satisfies
+ * c + w == k, w the weight of that step; the path ends at cost 0.  status_out [n] TLOAM_ROUTE_PATH_*; n_cells_out [n] the
+ * waypoints written (0 for OUTSIDE, UNREACHED and BLOCKED); cost_out [n] the value of the start's cell as
+ * tloam_closed_map_route_points gives it; centres_aos_out [n * max_cells * 3] the waypoint j of start i at
+ * centres[i * max_cells + j], a cell's centre o + (c + 0.5) * v as tloam_closed_map_read_free forms it, entries past n_cells
+ * zero.  TRUNCATED: the path has more than max_cells cells and its first max_cells are written; a whole path has at most
+ * cost / 3 + 1 cells, so a caller can size max_cells from cost_out.  The walk takes at most max_cells steps and stops as
+ * TRUNCATED when no neighbour satisfies the rule: a damaged field cannot make it loop.  max_cells >= 1, and
+ * n * max_cells * 24 bytes is held to max_bytes: else TLOAM_E_INVALID.  One launch, one wait. */
+int tloam_closed_map_route_paths(tloam_ctx* ctx, const double* starts_aos, size_t n, const double* pose_colmajor_or_null,
+                                 size_t max_cells, uint8_t* status_out, int32_t* n_cells_out, uint32_t* cost_out,
+                                 double* centres_aos_out);
+/* The 2-D form for a ground vehicle, over tloam_closed_map_clearance_columns' layer (the same band, min_free, sizes, capacity
+ * convention, R and unknown_is_obstacle): 8-connected, weights 3 and 4, a column traversable iff its d2 >= max(need, 1).  A goal
+ * must be a valid point and is placed by its x and y alone.  Computed per call by the relaxation of the 3-D field with nz = 1,
+ * not stored: it needs no built field and leaves a built one alone.  state_out [*ny * *nx] and d2_out [*ny * *nx] when not
+ * NULL, cost_out [*ny * *nx]; info_or_null as the build's (lo_cells[2] = 0, n_cells[2] = 1).  The layers (4 bytes a column of
+ * d2, then 4 bytes a column of cost and the tile flags) are held to the two max_bytes.  Descending the layer is the caller's. */
+int tloam_closed_map_route_columns(tloam_ctx* ctx, double z_lo, double z_hi, int64_t min_free, const double* goals_aos, size_t n,
+                                   const double* pose_colmajor_or_null, double radius, uint8_t* state_out_or_null,
+                                   uint16_t* d2_out_or_null, uint32_t* cost_out, size_t capacity, size_t* nx, size_t* ny,
+                                   tloam_closed_map_route_info* info_or_null);
+
 /* ---- the closed map's snapshot: a built closed map out of a context and into a fresh one (additive to ABI 8) ------
  * A memory blob; the library opens no files.  It holds, exactly, everything a context needs to answer every read of the closed
  * map and every localisation in it with the bytes of the context that saved: the place, loop, closed map, carve and surfel

@@ -302,6 +302,28 @@ CLEARANCE_BEYOND, CLEARANCE_OUTSIDE = 0xFFFF, 0xFFFE   # TLOAM_CLEARANCE_BEYOND,
 CLEARANCE_SKIPPED, CLEARANCE_CLEAR, CLEARANCE_BLOCKED, CLEARANCE_LEFT_BOX = 0, 1, 2, 3   # a segment's status
 
 
+class RouteConfig(Struct):
+    """tloam_closed_map_route_config: the most bytes the cost field and its tile flags may take, the most rounds of the tiled
+    relaxation a build may run, and how many rounds are enqueued between two waits of the host.  The
+    defaults are choices, not measurements."""
+    _c_name_ = "tloam_closed_map_route_config"
+    _fields_ = [("max_bytes", C.c_int64), ("max_rounds", C.c_int32), ("rounds_per_wait", C.c_int32)]
+
+
+class RouteInfo(Struct):
+    """tloam_closed_map_route_info; tile_updates, rounds, launches and waits are diagnostics that may differ from run to run."""
+    _c_name_ = "tloam_closed_map_route_info"
+    _fields_ = [("lo_cells", C.c_int64 * 3), ("n_cells", C.c_int64 * 3), ("bytes", C.c_int64), ("need", C.c_int64),
+                ("goals_accepted", C.c_int64), ("goals_rejected", C.c_int64), ("traversable_cells", C.c_int64),
+                ("reached_cells", C.c_int64), ("sum_cost", C.c_int64), ("max_cost", C.c_int64), ("tile_updates", C.c_int64),
+                ("rounds", C.c_int32), ("launches", C.c_int32), ("waits", C.c_int32), ("reserved0", C.c_int32)]
+
+
+ROUTE_UNREACHED, ROUTE_BLOCKED, ROUTE_OUTSIDE = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD   # TLOAM_ROUTE_UNREACHED, _BLOCKED, _OUTSIDE
+ROUTE_PATH_OUTSIDE, ROUTE_PATH_REACHED, ROUTE_PATH_UNREACHED, ROUTE_PATH_BLOCKED, ROUTE_PATH_TRUNCATED = 0, 1, 2, 3, 4
+ROUTE_DIAGNOSTICS = ("tile_updates", "rounds", "launches", "waits")   # the info fields that may differ from run to run
+
+
 SNAPSHOT_CLOUDS = 1   # TLOAM_SNAPSHOT_CLOUDS: the keyframes' eight clouds go into the snapshot too
 
 
@@ -709,6 +731,17 @@ def _signatures():
                                                           C.POINTER(C.c_uint16), dp, C.POINTER(C.c_int64)]),
         "tloam_closed_map_clearance_columns": (C.c_int, [vp, C.c_double, C.c_double, C.c_int64, C.POINTER(C.c_uint8),
                                                          C.POINTER(C.c_uint16), sz, C.POINTER(sz), C.POINTER(sz)]),
+        "tloam_closed_map_route_default_config": (None, [C.POINTER(RouteConfig)]),
+        "tloam_closed_map_route_configure": (C.c_int, [vp, C.POINTER(RouteConfig)]),
+        "tloam_closed_map_route_build": (C.c_int, [vp, dp, sz, dp, C.c_double, C.POINTER(RouteInfo)]),
+        "tloam_closed_map_get_route_info": (C.c_int, [vp, C.POINTER(RouteInfo)]),
+        "tloam_closed_map_read_route": (C.c_int, [vp, sz, sz, C.POINTER(C.c_uint32)]),
+        "tloam_closed_map_route_points": (C.c_int, [vp, dp, sz, dp, C.POINTER(C.c_uint32), dp, C.POINTER(C.c_int64)]),
+        "tloam_closed_map_route_paths": (C.c_int, [vp, dp, sz, dp, sz, C.POINTER(C.c_uint8), C.POINTER(C.c_int32),
+                                                   C.POINTER(C.c_uint32), dp]),
+        "tloam_closed_map_route_columns": (C.c_int, [vp, C.c_double, C.c_double, C.c_int64, dp, sz, dp, C.c_double,
+                                                     C.POINTER(C.c_uint8), C.POINTER(C.c_uint16), C.POINTER(C.c_uint32), sz,
+                                                     C.POINTER(sz), C.POINTER(sz), C.POINTER(RouteInfo)]),
         "tloam_closed_map_read_gone": (C.c_int, [vp, dp, dp, C.c_int64, C.c_double, sz, C.POINTER(sz), dp, C.POINTER(C.c_int64),
                                                  C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
         "tloam_closed_map_save_size": (C.c_int, [vp, C.c_int, C.POINTER(sz)]),

@@ -95,6 +95,7 @@ int tloam_closed_map_clearance_build(tloam_ctx* c, tloam_closed_map_clearance_in
   // from here on the previous field is gone
   C.have = false;
   C.info = tloam_closed_map_clearance_info{};
+  C.route.drop();   // (the route was built from the field this build replaces: DESIGN.md section 31)
   hipError_t e = hipMemsetAsync(M.scan_ctl.p, 0, sizeof(unsigned long long) * kClearCtl, c->stream);
   int launches = 0;
   if (e == hipSuccess) {

@@ -1017,6 +1017,61 @@ struct ClearColumnsArgs {
 };
 int launch_clear_columns(const ClearColumnsArgs& A, hipStream_t s);   // seed | x | y; returns the launches
 
+// ---- the route through the closed map (tl_route.hip): a dense field of uint32 over the clearance field's
+// box (or over a column layer: n[2] = 1), [z][y][x], x fastest: the least 3-4-5 chamfer weight to an accepted goal over the
+// traversable cells.  Nothing but the field, its tile flags and the control words is written
+constexpr unsigned kRouteUnreached = 0xFFFFFFFFu, kRouteBlocked = 0xFFFFFFFEu, kRouteOutside = 0xFFFFFFFDu;
+constexpr int kRouteMaxBatch = 1024;             // the most rounds between two waits (rounds_per_wait's range)
+constexpr int kRouteCtl = kRouteMaxBatch + 8;    // control words: [0] goals accepted, [1] rejected, [2] tiles the goals marked;
+                                                 // [4] traversable cells, [5] reached cells, [6] the sum, [7] the largest cost;
+                                                 // [8 + k] the tiles round k of a batch marked
+struct RouteField {
+  unsigned* cost;             // [n[2]][n[1]][n[0]]
+  int lo[3];                  // the lowest cell of the box per axis
+  int n[3];                   // cells per axis
+  int tiles[3];               // tiles per axis (tl_route_box.hpp's kTileX x kTileY x kTileZ, the last of an axis partial)
+  int reserved0;
+  long long cells;
+};
+struct RouteSeedArgs {
+  RouteField f;
+  const unsigned short* d2;   // the clearance (field or column layer) over the same box
+  int need;                   // max(need, 1): a cell with d2 >= need is traversable
+  int flat;                   // 1: the column form -- a goal is placed by x and y, its z cell is lo[2]
+  double voxel, origin[3];
+  ScanAt goals;               // the goals, and the pose when `posed`
+  int posed, reserved0;
+  unsigned* next;             // [tiles] the flags of the first round, zero before the launches
+  unsigned long long* ctl;    // [kRouteCtl], zero before the launches
+};
+void launch_route_seed(const RouteSeedArgs& A, hipStream_t s);   // seed | goals: two launches
+// One round: a block a tile, the tiles flagged in `now` relaxed (and their flags taken down), their neighbours flagged in `next`,
+// the fresh flags counted into *marks
+void launch_route_round(const RouteField& f, unsigned* now, unsigned* next, unsigned long long* marks, hipStream_t s);
+void launch_route_count(const RouteField& f, unsigned long long* ctl, hipStream_t s);
+struct RoutePointsArgs {
+  RouteField f;
+  double voxel, origin[3];
+  ScanAt scan;                // the points, and the pose when `posed`
+  int posed, reserved0;
+  unsigned* cost;             // [n]
+  double* distance;           // [n] or null
+  unsigned long long* ctl;    // [0..3] points reached / unreached / blocked / outside, zero before the launch
+};
+void launch_route_points(const RoutePointsArgs& A, hipStream_t s);
+struct RoutePathsArgs {
+  RouteField f;
+  double voxel, origin[3];
+  ScanAt scan;                // the starts, and the pose when `posed`
+  int posed, reserved0;
+  long long max_cells;
+  unsigned char* status;      // [n]
+  int* n_cells;               // [n]
+  unsigned* cost;             // [n]
+  double* centres;            // [n * max_cells * 3], zero before the launch
+};
+void launch_route_paths(const RoutePathsArgs& A, hipStream_t s);
+
 // ---- deskew of a scan under constant velocity (tl_deskew.hip) -------------
 struct DeskewArgs {
   const double* in;               // AoS xyz [3n]

@@ -556,12 +556,34 @@ struct CmapState {
       tl::ClearField field{};
       bool have = false;           // a build has succeeded since the last drop
       tloam_closed_map_clearance_info info{};
+      // the route (tl_api_route.hip): its configuration, the cost field with its two arrays of tile flags
+      // and the control words of a build, what the last build reports, a query's outputs and a column call's layer (grow-only
+      // scratch).  The field belongs to the clearance field it was built from and goes with it
+      struct RouteState {
+        tloam_closed_map_route_config cfg;   // tloam_closed_map_route_default_config until configured
+        RouteState() { tloam_closed_map_route_default_config(&cfg); }
+        DBuf<unsigned> cost, flags, out_u32, col_cost, col_flags;
+        DBuf<unsigned long long> ctl;
+        DBuf<int> out_i32;
+        DBuf<double> out_f64;
+        tl::RouteField field{};
+        bool have = false;           // a build has succeeded since the last drop
+        tloam_closed_map_route_info info{};
+        void drop() {
+          have = false;
+          info = tloam_closed_map_route_info{};
+          field = tl::RouteField{};
+          cost.release();            // (hipFree waits for the launches that use them)
+          flags.release();
+        }
+      } route;
       void drop() {
         have = false;
         info = tloam_closed_map_clearance_info{};
         field = tl::ClearField{};
         d2.release();              // (hipFree waits for the launches that use them)
         tmp.release();
+        route.drop();
       }
     } clear;
     void drop() {

@@ -403,3 +403,93 @@ def read_clearance_pcd(path: str):
     else:
         raise ValueError(f"{path}: DATA {kind} is not supported")
     return np.ascontiguousarray(rec[:, :3]), np.ascontiguousarray(rec[:, 3])
+
+
+# ---- the route through the closed map: the reached free cells with their cost-to-go, and descended paths
+def _write_xyz_and_one(path: str, name: str, rec, ascii: bool) -> None:
+    """rows of x y z and one more float64 field `name` as PCD v0.7 (`F 8` each), DATA binary or ascii (17 significant digits)"""
+    n = len(rec)
+    header = ("# .PCD v0.7 - Point Cloud Data file format\n"
+              "VERSION 0.7\n"
+              f"FIELDS x y z {name}\n"
+              "SIZE 8 8 8 8\n"
+              "TYPE F F F F\n"
+              "COUNT 1 1 1 1\n"
+              f"WIDTH {n}\n"
+              "HEIGHT 1\n"
+              "VIEWPOINT 0 0 0 1 0 0 0\n"
+              f"POINTS {n}\n"
+              f"DATA {'ascii' if ascii else 'binary'}\n")
+    with open(path, "wb") as fh:
+        fh.write(header.encode("ascii"))
+        if ascii:
+            fh.write("".join(" ".join(f"{v:.17g}" for v in row) + "\n" for row in rec.tolist()).encode("ascii"))
+        else:
+            fh.write(rec.tobytes())
+
+
+def _read_xyz_and_one(path: str, name: str):
+    """a file of _write_xyz_and_one -> (n, 4) float64"""
+    with open(path, "rb") as fh:
+        raw = fh.read()
+    head, pos = {}, 0
+    while True:
+        end = raw.index(b"\n", pos)
+        line = raw[pos:end].decode("ascii").strip()
+        pos = end + 1
+        if not line or line.startswith("#"):
+            continue
+        key, _, val = line.partition(" ")
+        head[key.upper()] = val.split()
+        if key.upper() == "DATA":
+            break
+    if head.get("FIELDS") != ["x", "y", "z", name] or head.get("SIZE") != ["8"] * 4 or head.get("TYPE") != ["F"] * 4:
+        raise ValueError(f"{path}: only FIELDS x y z {name} with SIZE 8 / TYPE F are read")
+    n = int(head["POINTS"][0])
+    kind = head["DATA"][0]
+    if kind == "binary":
+        body = raw[pos: pos + 32 * n]
+        if len(body) != 32 * n:
+            raise ValueError(f"{path}: {len(body)} bytes of data for {n} points")
+        return np.frombuffer(body, dtype="<f8").reshape(n, 4)
+    if kind == "ascii":
+        rows = raw[pos:].split()
+        if len(rows) != 4 * n:
+            raise ValueError(f"{path}: {len(rows)} values for {n} points")
+        return np.array([float(v) for v in rows], dtype=np.float64).reshape(n, 4)
+    raise ValueError(f"{path}: DATA {kind} is not supported")
+
+
+def write_route_pcd(path: str, H, lo=None, hi=None, ascii: bool = False) -> int:
+    """Writes the centres `H.closed_map_free_cells` reads (a HipRegistration after closed_map_route_build) that a goal reaches,
+    with voxel * cost / 3 of each as a fourth field, `route` (metres to the nearest goal along the 3-4-5 chamfer), as PCD v0.7,
+    four float64 (`F 8`) -> the cells written."""
+    cen = H.closed_map_free_cells(lo, hi)
+    dist = H.closed_map_route_points(cen)[1] if len(cen) else np.zeros(0)
+    keep = np.isfinite(dist)
+    rec = np.ascontiguousarray(np.concatenate([cen.reshape(-1, 3)[keep], dist[keep].reshape(-1, 1)], axis=1), dtype="<f8")
+    _write_xyz_and_one(path, "route", rec, ascii)
+    return len(rec)
+
+
+def read_route_pcd(path: str):
+    """Reads a file of write_route_pcd (DATA ascii or binary) -> (centres (n, 3) float64, route (n,) float64)."""
+    rec = _read_xyz_and_one(path, "route")
+    return np.ascontiguousarray(rec[:, :3]), np.ascontiguousarray(rec[:, 3])
+
+
+def write_route_paths_pcd(path: str, H, starts, max_cells: int, pose=None, ascii: bool = False) -> int:
+    """Writes the waypoints of `H.closed_map_route_paths(starts, max_cells, pose)`, path after path, each with the index of its
+    start as a fourth field, `path` (float64 like the rest: `F 8`); a start without a path writes nothing -> the waypoints
+    written."""
+    _, count, _, centres = H.closed_map_route_paths(starts, max_cells, pose)
+    rows = [np.concatenate([centres[i, :count[i]], np.full((count[i], 1), float(i))], axis=1) for i in range(len(count)) if count[i]]
+    rec = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, 4)), dtype="<f8")
+    _write_xyz_and_one(path, "path", rec, ascii)
+    return len(rec)
+
+
+def read_route_paths_pcd(path: str):
+    """Reads a file of write_route_paths_pcd -> (waypoints (n, 3) float64, path index (n,) int64)."""
+    rec = _read_xyz_and_one(path, "path")
+    return np.ascontiguousarray(rec[:, :3]), rec[:, 3].astype(np.int64)

@@ -43,6 +43,10 @@ def _u16p(a):
     return None if a is None else a.ctypes.data_as(C.POINTER(C.c_uint16))
 
 
+def _u32p(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_uint32))
+
+
 def _per_point(n, want_ids):
     """the per-point outputs of a scan query, never empty -> (bytes (max(n, 1),) uint8, ids (max(n, 1),) int32 or None, cut);
     cut(a): the first n of `a` as the caller's own copy (None stays None)"""
@@ -100,6 +104,7 @@ _CONFIGS = {
     ClosedMapRaycastConfig: ("tloam_closed_map_raycast_default_config", {}),
     FreeConfig: ("tloam_closed_map_free_default_config", {}),
     ClearanceConfig: ("tloam_closed_map_clearance_default_config", {}),
+    RouteConfig: ("tloam_closed_map_route_default_config", {}),
 }
 
 
@@ -1099,6 +1104,75 @@ class HipRegistration:
         shape = (ny.value, nx.value)
         return state[: shape[0] * shape[1]].reshape(shape).copy(), d2[: shape[0] * shape[1]].reshape(shape).copy()
 
+    # ---- the route through the closed map: a cost-to-go field from goals over the clearance field, and paths
+    def closed_map_route_configure(self, cfg: RouteConfig | None = None, **over):
+        """the route's configuration (default_closed_map_route_config(**over) when cfg is None); drops the route field only.
+        Kept across odometry_reset; a refused configuration leaves the old one."""
+        self._configure(RouteConfig, "tloam_closed_map_route_configure", cfg, over)
+
+    def closed_map_route_build(self, goals, radius=0.0, pose=None) -> dict:
+        """builds the cost-to-go field towards `goals` ((n, 3); map frame, or the sensor frame of `pose`) over the cells a body
+        of `radius` metres may occupy -> info dict (its ROUTE_DIAGNOSTICS fields may differ from run to run)"""
+        pts = _aos(goals)
+        info = RouteInfo()
+        self._call("tloam_closed_map_route_build", _dp(pts), len(pts), None if pose is None else _dp(_colmajor(pose)),
+                   float(radius), C.byref(info))
+        return info.as_dict()
+
+    def closed_map_route_info(self) -> dict:
+        return self._info(RouteInfo, "tloam_closed_map_get_route_info")
+
+    def closed_map_route_field(self):
+        """the whole field -> (nz, ny, nx) uint32: the 3-4-5 chamfer cost to the nearest accepted goal, ROUTE_UNREACHED,
+        ROUTE_BLOCKED; voxel * cost / 3.0 is metres"""
+        nx, ny, nz = self.closed_map_route_info()["n_cells"]
+        cost = np.zeros(max(nx * ny * nz, 1), np.uint32)
+        self._call("tloam_closed_map_read_route", 0, nx * ny * nz, _u32p(cost))
+        return cost[: nx * ny * nz].reshape(nz, ny, nx).copy()
+
+    def closed_map_route_points(self, points, pose=None, want_distance=True):
+        """the cost-to-go of `points` (n, 3; map frame, or the sensor frame of `pose`) -> (cost (n,) uint32 -- ROUTE_OUTSIDE for a
+        cell outside the box or an invalid point --, distance (n,) float64 = voxel * cost / 3.0 -- inf for ROUTE_UNREACHED, NaN
+        for ROUTE_BLOCKED and ROUTE_OUTSIDE -- or None without want_distance, counts (4,) int64: reached, unreached, blocked,
+        outside)"""
+        pts = _aos(points)
+        n = len(pts)
+        cost = np.zeros(max(n, 1), np.uint32)
+        dist = np.zeros(max(n, 1), np.float64) if want_distance else None
+        counts = np.zeros(4, np.int64)
+        self._call("tloam_closed_map_route_points", _dp(pts), n, None if pose is None else _dp(_colmajor(pose)), _u32p(cost),
+                   _dp(dist), _lp(counts))
+        return cost[:n].copy(), None if dist is None else dist[:n].copy(), counts
+
+    def closed_map_route_paths(self, starts, max_cells, pose=None):
+        """a path per start ((n, 3); map frame, or the sensor frame of `pose`) descended from the field -> (status (n,) uint8:
+        ROUTE_PATH_*; n_cells (n,) int32 waypoints written; cost (n,) uint32 of the start's cell; centres (n, max_cells, 3)
+        float64, the cell centres, zero past n_cells).  A whole path has at most cost // 3 + 1 cells."""
+        pts = _aos(starts)
+        n, m = len(pts), int(max_cells)
+        status, _, cut = _per_point(n, False)
+        cells, cost = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint32)
+        centres = np.zeros((max(n, 1), max(m, 1), 3), np.float64)
+        self._call("tloam_closed_map_route_paths", _dp(pts), n, None if pose is None else _dp(_colmajor(pose)), m, _u8p(status),
+                   _ip(cells), _u32p(cost), _dp(centres))
+        return cut(status), cut(cells), cut(cost), centres[:n].copy()
+
+    def closed_map_route_columns(self, z_lo, z_hi, goals, radius=0.0, min_free=1, pose=None):
+        """the 2-D cost-to-go over closed_map_clearance_columns' layer, 8-connected with weights 3 and 4, goals placed by x and y
+        -> (states (ny, nx) uint8, d2 (ny, nx) uint16, cost (ny, nx) uint32, info dict); computed per call, not stored"""
+        pts = _aos(goals)
+        nb = self.closed_map_free_info()["n_bricks"]
+        nx, ny = C.c_size_t(0), C.c_size_t(0)
+        m = max(16 * nb[0] * nb[1], 1)
+        state, d2, cost = np.zeros(m, np.uint8), np.zeros(m, np.uint16), np.zeros(m, np.uint32)
+        info = RouteInfo()
+        self._call("tloam_closed_map_route_columns", float(z_lo), float(z_hi), int(min_free), _dp(pts), len(pts),
+                   None if pose is None else _dp(_colmajor(pose)), float(radius), _u8p(state), _u16p(d2), _u32p(cost), m,
+                   C.byref(nx), C.byref(ny), C.byref(info))
+        shape = (ny.value, nx.value)
+        k = shape[0] * shape[1]
+        return state[:k].reshape(shape).copy(), d2[:k].reshape(shape).copy(), cost[:k].reshape(shape).copy(), info.as_dict()
+
     def fitness(self):
         f, r = C.c_double(0), C.c_double(0)
         rc = self.L.tloam_fitness(self.h, C.byref(f), C.byref(r))
@@ -1332,6 +1406,11 @@ def default_closed_map_free_config(**over) -> FreeConfig:
     """tloam_closed_map_free_default_config (max_range 60, end_margin 1, ray_mask 0: the build's, max_bytes 1 GiB, min_count 1,
     min_miss 3, miss_ratio 1, carve_gate 0) with keyword overrides; an unknown field raises"""
     return _default(FreeConfig, over)
+
+
+def default_closed_map_route_config(**over) -> RouteConfig:
+    """tloam_closed_map_route_default_config (max_bytes 1 GiB, max_rounds 65536, rounds_per_wait 16) with keyword overrides"""
+    return _default(RouteConfig, over)
 
 
 def default_closed_map_clearance_config(**over) -> ClearanceConfig:
