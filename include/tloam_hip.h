@@ -1653,6 +1653,120 @@ int tloam_closed_map_route_columns(tloam_ctx* ctx, double z_lo, double z_hi, int
                                    uint16_t* d2_out_or_null, uint32_t* cost_out, size_t capacity, size_t* nx, size_t* ny,
                                    tloam_closed_map_route_info* info_or_null);
 
+/* ---- the frontiers of the closed map: where free space meets the unknown, clustered (additive to ABI 8) -------
+ * A dense field over the free-space grid's box (nx = 4 nbx, ny, nz cells, row-major [z][y][x], x fastest, element (x, y, z) the
+ * cell lo_cells + (x, y, z): the clearance's and the route's cells), one uint32 a cell.  The states are tloam_closed_map_occupancy's
+ * at the moment of the build, under the free configuration's min_count, min_miss, miss_ratio and carve_gate; a built clearance
+ * field is not needed.  A FRONTIER CELL is a FREE cell with at least one of its six face neighbours INSIDE THE BOX UNKNOWN; cells
+ * outside the box contribute nothing, neither as unknown neighbours nor to connectivity.  The automatic box of
+ * tloam_closed_map_free_reset reaches one cell beyond every ray, so no frontier is lost at its faces; A BOX GIVEN BY THE CALLER IS
+ * A REGION OF INTEREST WHOSE FACES MAKE NO FRONTIER.  A CLUSTER is a 26-connected component of the frontier cells; its root is
+ * the least linear index (z * ny + y) * nx + x among its cells.  A cell's value is its cluster's root when it is a frontier cell,
+ * else one of the three state sentinels below: the field doubles as the dense state array of the box.  A build is refused
+ * (TLOAM_E_INVALID) when cells >= TLOAM_FRONTIER_OUTSIDE (an index would meet a sentinel) or when the field and its tile flags
+ * are more than max_bytes.
+ * Kept clusters: those with cells >= min_cells, listed in ascending root.  Every component is counted in the info; only the kept
+ * ones are listed, costed and indexed.  A cluster's centroid is the caller's: o + (lo_cells + sum / cells + 0.5) * v per axis, in
+ * double, in that order (sum and cells converted to double first).
+ * The field is built by tloam_closed_map_frontier_build and dropped by everything that drops the clearance field because the
+ * grid or the map's counting voxels changed (tloam_closed_map_free_configure, _free_reset, _free_add_keyframes, _free_add_scan,
+ * a successful tloam_closed_map_extend, whatever drops the carve or the closed map) and by tloam_closed_map_frontier_configure;
+ * the clearance's and the route's configure and build leave it alone.  After a drop every read is TLOAM_E_NOT_READY until the
+ * next build.  It is not saved in a snapshot; nothing else in the context changes by a bit.
+ * The labelling by least index is the unique fixpoint of a min-propagation, so every byte of every output, and every info field
+ * but the four marked DIAGNOSTIC below, is the same for two builds and for two contexts.
+ * Every call here on a context with nranks > 1: TLOAM_E_INVALID. */
+#define TLOAM_FRONTIER_FREE 0xFFFFFFFFu       /* a FREE cell that is no frontier cell */
+#define TLOAM_FRONTIER_UNKNOWN 0xFFFFFFFEu    /* an UNKNOWN cell */
+#define TLOAM_FRONTIER_OCCUPIED 0xFFFFFFFDu   /* an OCCUPIED cell */
+#define TLOAM_FRONTIER_OUTSIDE 0xFFFFFFFCu    /* a queried cell outside the box, or an INVALID point */
+#define TLOAM_FRONTIER_ALL 0xFFFFFFFFu        /* tloam_closed_map_read_frontier_cells: the cells of every kept cluster */
+typedef struct tloam_closed_map_frontier_config {   /* choices, not measurements */
+  int64_t max_bytes;         /* 1 GiB: a build whose field, tile flags and cluster table need more is refused; >= 4 */
+  int32_t min_cells;         /* 8: a cluster of fewer cells is counted but not kept; >= 1 */
+  int32_t reach;             /* 2: tloam_closed_map_frontier_costs looks this many cells around a cluster's cells; 0 .. 4 */
+  int32_t max_rounds;        /* 65536: a build that needs more rounds fails; >= 1 */
+  int32_t rounds_per_wait;   /* 16: rounds enqueued between two waits of the host; 1 .. 1024 */
+} tloam_closed_map_frontier_config;
+void tloam_closed_map_frontier_default_config(tloam_closed_map_frontier_config* cfg);
+/* cfg NULL: the defaults.  A value out of its range: TLOAM_E_INVALID, and the old configuration stays.  Drops the frontier field
+ * only; persists across tloam_odometry_reset. */
+int tloam_closed_map_frontier_configure(tloam_ctx* ctx, const tloam_closed_map_frontier_config* cfg);
+typedef struct tloam_closed_map_frontier_cluster {   /* 64 bytes */
+  int64_t sum[3];            /* the sums of the cells' box-local x, y, z */
+  int32_t lo[3];             /* the inclusive box of the cluster in absolute cells: its lowest ... */
+  int32_t hi[3];             /* ... and its highest cell per axis */
+  uint32_t root;             /* the least linear index among the cluster's cells: its label in the field */
+  uint32_t cells;
+  uint32_t unknown_faces;    /* (cell, face) pairs of the cluster that face an UNKNOWN cell: the size of the opening */
+  uint32_t reserved;         /* 0 */
+} tloam_closed_map_frontier_cluster;
+typedef struct tloam_closed_map_frontier_info {
+  int64_t lo_cells[3];         /* the box: its lowest cell per axis ... */
+  int64_t n_cells[3];          /* ... its cells per axis (nx, ny, nz) ... */
+  int64_t bytes;               /* ... and what the field holds on the device: 4 bytes a cell and 8 bytes a tile of flags */
+  int64_t free_cells;          /* cells in state FREE, frontier cells among them (the grid's own free_cells is a popcount that
+                                  includes bits under counting voxels) */
+  int64_t unknown_cells;
+  int64_t occupied_cells;      /* the three sum to the box */
+  int64_t frontier_cells;
+  int64_t clusters;            /* all components */
+  int64_t clusters_kept;       /* those with cells >= min_cells */
+  int64_t cells_kept;          /* the frontier cells of the kept clusters */
+  int64_t largest;             /* the cells of the largest component (0 when there is none) */
+  int64_t unknown_faces;       /* over all frontier cells */
+  int64_t tile_updates;        /* DIAGNOSTIC: tiles relaxed, over all rounds */
+  int32_t rounds;              /* DIAGNOSTIC: rounds that ran until one marked nothing */
+  int32_t launches;            /* DIAGNOSTIC: kernel launches of the build */
+  int32_t waits;               /* DIAGNOSTIC: waits of the host */
+  int32_t reserved0;
+} tloam_closed_map_frontier_info;
+/* Resolves the states of the box, marks the frontier cells, labels them in rounds (rounds_per_wait launches between two waits)
+ * until a round lowers nothing, counts and gathers the clusters.  TLOAM_E_NOT_READY exactly where
+ * tloam_closed_map_clearance_build has it: no built map, no grid, or the gate on and not carved.  TLOAM_E_INVALID for a box the
+ * contract above refuses: a refused build leaves the previous field as it was.  A failure after the first launch drains the
+ * stream and drops the field; running out of max_rounds drops the field and returns TLOAM_E_HIP, tloam_last_error naming the cap,
+ * and so does a cluster table (136 bytes a component) that does not fit under max_bytes beside the field once the roots are
+ * counted. */
+int tloam_closed_map_frontier_build(tloam_ctx* ctx, tloam_closed_map_frontier_info* info_or_null);
+/* All zero when there is no field. */
+int tloam_closed_map_get_frontier_info(tloam_ctx* ctx, tloam_closed_map_frontier_info* info);
+/* The field's values [first, first + count) as they stand (tloam_closed_map_read_route's conventions). */
+int tloam_closed_map_read_frontier(tloam_ctx* ctx, size_t first, size_t count, uint32_t* label);
+/* The kept clusters in ascending root.  *n_out: their number, always; more than capacity: TLOAM_E_INVALID and nothing written;
+ * clusters_out NULL: the number alone (tloam_closed_map_read_box's capacity convention). */
+int tloam_closed_map_frontier_clusters(tloam_ctx* ctx, size_t capacity, tloam_closed_map_frontier_cluster* clusters_out,
+                                       size_t* n_out);
+/* The centres o + (c + 0.5) * v of the frontier cells of the kept cluster of root `root_or_all`, or with TLOAM_FRONTIER_ALL of
+ * every kept cluster, in ascending linear index; roots_out [n] when not NULL the root of each.  The same capacity convention.  A
+ * root that is not a kept cluster's: *n_out = 0 and TLOAM_OK. */
+int tloam_closed_map_read_frontier_cells(tloam_ctx* ctx, uint32_t root_or_all, size_t capacity, double* centres_aos_out,
+                                         uint32_t* roots_out_or_null, size_t* n_out);
+/* Per point (pose NULL: in the map frame; else in the sensor frame of pose_colmajor): label_out [n] the value of the point's
+ * cell, TLOAM_FRONTIER_OUTSIDE for a cell outside the box or an INVALID point; cluster_out [n] when not NULL the index of the
+ * cell's cluster in the kept list, else -1; counts_out [5] when not NULL: points frontier / free / unknown / occupied / outside.
+ * One launch, one wait. */
+int tloam_closed_map_frontier_points(tloam_ctx* ctx, const double* points_aos, size_t n, const double* pose_colmajor_or_null,
+                                     uint32_t* label_out, int32_t* cluster_out_or_null, int64_t* counts_out_or_null);
+/* The join with the route: TLOAM_E_NOT_READY without a frontier field or without a route field (both lie over the grid's box).
+ * Per kept cluster the minimum, over its cells c and over the cells u of the box with max |u - c| <= reach per axis whose route
+ * value is a cost (below TLOAM_ROUTE_OUTSIDE), of the key (cost(u) << 32) | linear(u): cost_out [n] the key's high half,
+ * approach_aos_out [3 n] when not NULL the centre of the key's cell; TLOAM_ROUTE_UNREACHED and three NaN when there is none.
+ * reach is there because with unknown_is_obstacle = 1 a frontier cell has d2 = 1 and is BLOCKED for any body wider than a voxel:
+ * the nearest cell the body can stand in is a few cells back.  THE ROUTE'S MOVES ARE SYMMETRIC: a route built from the robot's
+ * cell as the one goal gives the robot's cost to every cluster.  Computed per call, not stored; the capacity convention of
+ * tloam_closed_map_frontier_clusters.  One launch, one wait. */
+int tloam_closed_map_frontier_costs(tloam_ctx* ctx, size_t capacity, uint32_t* cost_out, double* approach_aos_out_or_null,
+                                    size_t* n_out);
+/* The 2-D form over tloam_closed_map_free_columns' layer (the same band and min_free): the same kernels with nz = 1, so 4 face
+ * neighbours and 8-connectivity remain; sum[2] = 0 and lo[2] = hi[2] = the box's lowest z cell.  label_out [ny * nx] (16 nbx nby
+ * values: the caller sizes it from the grid's info) when not NULL; the kept clusters by the capacity convention above;
+ * info_or_null as the build's (n_cells[2] = 1).  Computed per call, not stored: it needs no built field and leaves a built one
+ * alone.  No cost join: the caller's. */
+int tloam_closed_map_frontier_columns(tloam_ctx* ctx, double z_lo, double z_hi, int64_t min_free, uint32_t* label_out_or_null,
+                                      size_t capacity, tloam_closed_map_frontier_cluster* clusters_out, size_t* n_out,
+                                      tloam_closed_map_frontier_info* info_or_null);
+
 /* ---- the closed map's snapshot: a built closed map out of a context and into a fresh one (additive to ABI 8) ------
  * A memory blob; the library opens no files.  It holds, exactly, everything a context needs to answer every read of the closed
  * map and every localisation in it with the bytes of the context that saved: the place, loop, closed map, carve and surfel

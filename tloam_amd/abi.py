@@ -324,6 +324,41 @@ ROUTE_PATH_OUTSIDE, ROUTE_PATH_REACHED, ROUTE_PATH_UNREACHED, ROUTE_PATH_BLOCKED
 ROUTE_DIAGNOSTICS = ("tile_updates", "rounds", "launches", "waits")   # the info fields that may differ from run to run
 
 
+class FrontierConfig(Struct):
+    """tloam_closed_map_frontier_config: the most bytes the label field, its tile flags and the cluster table may take, the
+    fewest cells of a kept cluster, how many cells around a cluster's cells the cost join looks, the most rounds of the tiled
+    labelling and how many rounds are enqueued between two waits of the host.  The defaults are choices,
+    not measurements."""
+    _c_name_ = "tloam_closed_map_frontier_config"
+    _fields_ = [("max_bytes", C.c_int64), ("min_cells", C.c_int32), ("reach", C.c_int32), ("max_rounds", C.c_int32),
+                ("rounds_per_wait", C.c_int32)]
+
+
+class FrontierCluster(Struct):
+    """tloam_closed_map_frontier_cluster: 64 bytes, no implicit padding"""
+    _c_name_ = "tloam_closed_map_frontier_cluster"
+    _fields_ = [("sum", C.c_int64 * 3), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("root", C.c_uint32), ("cells", C.c_uint32),
+                ("unknown_faces", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class FrontierInfo(Struct):
+    """tloam_closed_map_frontier_info; tile_updates, rounds, launches and waits are diagnostics that may differ from run to run."""
+    _c_name_ = "tloam_closed_map_frontier_info"
+    _fields_ = [("lo_cells", C.c_int64 * 3), ("n_cells", C.c_int64 * 3), ("bytes", C.c_int64), ("free_cells", C.c_int64),
+                ("unknown_cells", C.c_int64), ("occupied_cells", C.c_int64), ("frontier_cells", C.c_int64), ("clusters", C.c_int64),
+                ("clusters_kept", C.c_int64), ("cells_kept", C.c_int64), ("largest", C.c_int64), ("unknown_faces", C.c_int64),
+                ("tile_updates", C.c_int64), ("rounds", C.c_int32), ("launches", C.c_int32), ("waits", C.c_int32),
+                ("reserved0", C.c_int32)]
+
+
+# TLOAM_FRONTIER_FREE, _UNKNOWN, _OCCUPIED, _OUTSIDE, _ALL
+FRONTIER_FREE, FRONTIER_UNKNOWN, FRONTIER_OCCUPIED, FRONTIER_OUTSIDE, FRONTIER_ALL = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD, 0xFFFFFFFC, 0xFFFFFFFF
+FRONTIER_DIAGNOSTICS = ("tile_updates", "rounds", "launches", "waits")   # the info fields that may differ from run to run
+# a cluster record as numpy reads an array of them
+FRONTIER_CLUSTER_DTYPE = [("sum", "<i8", 3), ("lo", "<i4", 3), ("hi", "<i4", 3), ("root", "<u4"), ("cells", "<u4"),
+                          ("unknown_faces", "<u4"), ("reserved", "<u4")]
+
+
 SNAPSHOT_CLOUDS = 1   # TLOAM_SNAPSHOT_CLOUDS: the keyframes' eight clouds go into the snapshot too
 
 
@@ -742,6 +777,18 @@ def _signatures():
         "tloam_closed_map_route_columns": (C.c_int, [vp, C.c_double, C.c_double, C.c_int64, dp, sz, dp, C.c_double,
                                                      C.POINTER(C.c_uint8), C.POINTER(C.c_uint16), C.POINTER(C.c_uint32), sz,
                                                      C.POINTER(sz), C.POINTER(sz), C.POINTER(RouteInfo)]),
+        "tloam_closed_map_frontier_default_config": (None, [C.POINTER(FrontierConfig)]),
+        "tloam_closed_map_frontier_configure": (C.c_int, [vp, C.POINTER(FrontierConfig)]),
+        "tloam_closed_map_frontier_build": (C.c_int, [vp, C.POINTER(FrontierInfo)]),
+        "tloam_closed_map_get_frontier_info": (C.c_int, [vp, C.POINTER(FrontierInfo)]),
+        "tloam_closed_map_read_frontier": (C.c_int, [vp, sz, sz, C.POINTER(C.c_uint32)]),
+        "tloam_closed_map_frontier_clusters": (C.c_int, [vp, sz, C.c_void_p, C.POINTER(sz)]),
+        "tloam_closed_map_read_frontier_cells": (C.c_int, [vp, C.c_uint32, sz, dp, C.POINTER(C.c_uint32), C.POINTER(sz)]),
+        "tloam_closed_map_frontier_points": (C.c_int, [vp, dp, sz, dp, C.POINTER(C.c_uint32), C.POINTER(C.c_int32),
+                                                       C.POINTER(C.c_int64)]),
+        "tloam_closed_map_frontier_costs": (C.c_int, [vp, sz, C.POINTER(C.c_uint32), dp, C.POINTER(sz)]),
+        "tloam_closed_map_frontier_columns": (C.c_int, [vp, C.c_double, C.c_double, C.c_int64, C.POINTER(C.c_uint32), sz, C.c_void_p,
+                                                        C.POINTER(sz), C.POINTER(FrontierInfo)]),
         "tloam_closed_map_read_gone": (C.c_int, [vp, dp, dp, C.c_int64, C.c_double, sz, C.POINTER(sz), dp, C.POINTER(C.c_int64),
                                                  C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
         "tloam_closed_map_save_size": (C.c_int, [vp, C.c_int, C.POINTER(sz)]),

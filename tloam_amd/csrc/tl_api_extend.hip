@@ -273,7 +273,7 @@ int tloam_closed_map_extend(tloam_ctx* c, int pose_source, const double* poses, 
   M.poses.insert(M.poses.end(), used.begin(), used.end());
   M.drop_localise();   // the voxel records are those of the map before
   M.drop_diff();
-  M.free.clear.drop();   // the clearance was built from the voxels of the map before (the free-space grid stays)
+  M.free.drop_fields();   // the clearance and the frontiers were built from the voxels of the map before (the free-space grid stays)
   M.extend_info = E;
   if (info) *info = E;
   return TLOAM_OK;

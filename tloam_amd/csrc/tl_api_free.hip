@@ -124,8 +124,8 @@ int tloam_closed_map_free_reset(tloam_ctx* c, const int64_t* lo_cells, const int
   g.words = F.words.p;
   for (int a = 0; a < 3; ++a) { g.blo[a] = (int)B.blo[a]; g.nb[a] = (int)B.nb[a]; }
   g.nwords = (long long)B.words;
-  // from here on the previous grid is gone, and the clearance built from it
-  F.clear.drop();
+  // from here on the previous grid is gone, and what was built from it
+  F.drop_fields();
   F.have = false;
   F.info = tloam_closed_map_free_info{};
   F.grid = g;
@@ -150,7 +150,7 @@ int tloam_closed_map_free_add_keyframes(tloam_ctx* c, tloam_closed_map_free_info
   if (M.detached) return TLOAM_E_NOT_READY;   // (loaded without its clouds: DESIGN.md 25)
   FreeState& F = M.free;
   const tloam_closed_map_free_config& g = F.cfg;
-  F.clear.drop();   // (the clearance was built from the grid as it was)
+  F.drop_fields();   // (the clearance and the frontiers were built from the grid as it was)
   CmapPassOut R;
   const int rc = cmap_pass<FreeWork>(
       c, g.ray_mask ? g.ray_mask : M.cfg.cloud_mask, F.ctl,
@@ -181,7 +181,7 @@ int tloam_closed_map_free_add_scan(tloam_ctx* c, const double* points_aos, size_
   if (!pose_finite_rigid(pose)) return TLOAM_E_INVALID;
   CmapState& M = c->cmap;
   FreeState& F = M.free;
-  F.clear.drop();   // (the clearance was built from the grid as it was)
+  F.drop_fields();   // (the clearance and the frontiers were built from the grid as it was)
   unsigned long long ctl[kFreeCtl];
   int launches = 0, prepared = 0;
   const int rc = cmap_scan_call(

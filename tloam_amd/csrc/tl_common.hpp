@@ -1072,6 +1072,87 @@ struct RoutePathsArgs {
 };
 void launch_route_paths(const RoutePathsArgs& A, hipStream_t s);
 
+// ---- the frontiers of the closed map (tl_frontier.hip): a dense field of uint32 over the free-space
+// grid's box (or over a column layer: n[2] = 1), [z][y][x], x fastest: a frontier cell's value is the least linear index of its
+// 26-connected component of frontier cells, every other cell's its state's sentinel.  Nothing but the field, its tile flags, the
+// cluster table and the control words is written
+constexpr unsigned kFrontFree = 0xFFFFFFFFu, kFrontUnknown = 0xFFFFFFFEu, kFrontOccupied = 0xFFFFFFFDu, kFrontOutside = 0xFFFFFFFCu;
+constexpr int kFrontRounds0 = 32;                      // the first of the rounds' control words
+constexpr int kFrontCtl = kRouteMaxBatch + kFrontRounds0;
+// control words: [0] tiles the frontier cells marked, [1] the unknown faces; [2] free, [3] unknown, [4] occupied, [5] frontier
+// cells, [6] roots; [8] the roots' start tickets, [9] their look-back's fault, [10] roots written; [12] [13] [14] the same of the
+// kept list; [15] cells kept, [16] the largest component; [20] [21] [22] the same three of a cells read; [24 .. 28] the points of
+// a query per kind; [kFrontRounds0 + k] the tiles round k of a batch marked
+struct FrontField {
+  unsigned* label;            // [n[2]][n[1]][n[0]]
+  int lo[3];                  // the lowest cell of the box per axis
+  int n[3];                   // cells per axis, n[0] a multiple of 4
+  int tiles[3];               // tiles per axis (tl_frontier_box.hpp's kTileX x kTileY x kTileZ, the last of an axis partial)
+  int reserved0;
+  long long cells;
+};
+struct FrontTable {           // the clusters of a field, ascending in root
+  const unsigned* roots;      // [nroots]
+  const int* kept_of;         // [nroots] a component's index in the kept list, -1 when it is not kept
+  long long nroots;
+};
+struct FrontSeedArgs {
+  FreeQuery q;                // the 3-D form: brick words, then the counting voxel rows
+  const unsigned char* state; // the column form: [n[1]][n[0]] of k_free_columns (null: the 3-D form)
+  FrontField f;
+  unsigned* next;             // [tiles] the flags of the first round, zero before the launches
+  unsigned long long* ctl;    // [kFrontCtl], zero before the launches
+};
+int launch_front_seed(const FrontSeedArgs& A, hipStream_t s);   // states (| voxels) | mark; returns the launches
+// One round: k_route_round's form with min over the 26 neighbours that are frontier cells
+void launch_front_round(const FrontField& f, unsigned* now, unsigned* next, unsigned long long* marks, hipStream_t s);
+void launch_front_count(const FrontField& f, unsigned long long* ctl, hipStream_t s);
+struct FrontGatherArgs {
+  FrontField f;
+  unsigned* roots;                             // [nroots] out, ascending
+  tloam_closed_map_frontier_cluster* rec;      // [nroots] out
+  tloam_closed_map_frontier_cluster* kept_rec; // [nroots] out: the records with cells >= min_cells, in order
+  int* kept_of;                                // [nroots] out
+  long long nroots;
+  unsigned min_cells;
+  int reserved0;
+  unsigned long long* look;   // [blocks_of(cells / 4) + 1 + blocks_of(nroots) + 1], zero before the launches
+  unsigned long long* ctl;
+};
+int launch_front_gather(const FrontGatherArgs& A, hipStream_t s);   // roots | accumulate | keep; returns the launches
+struct FrontCellsArgs {
+  FrontField f;
+  FrontTable t;
+  unsigned root;              // kFrontFree: the cells of every kept cluster
+  int reserved0;
+  double voxel, origin[3];
+  long long m;                // the cells the host counted: nothing is written past them
+  double* centres;            // [3 m] out
+  unsigned* roots_out;        // [m] out
+  unsigned long long* look;   // [blocks_of(cells / 4) + 1], zero before the launch
+  unsigned long long* ctl;    // [20 .. 22] zero before the launch
+};
+void launch_front_cells(const FrontCellsArgs& A, hipStream_t s);
+struct FrontPointsArgs {
+  FrontField f;
+  FrontTable t;
+  double voxel, origin[3];
+  ScanAt scan;                // the points, and the pose when `posed`
+  int posed, reserved0;
+  unsigned* label;            // [n]
+  int* cluster;               // [n] or null
+  unsigned long long* ctl;    // [0 .. 4] points frontier / free / unknown / occupied / outside, zero before the launch
+};
+void launch_front_points(const FrontPointsArgs& A, hipStream_t s);
+struct FrontCostsArgs {
+  FrontField f;
+  FrontTable t;
+  const unsigned* cost;       // the route field over the same box
+  int reach, reserved0;
+  unsigned long long* keys;   // [kept] all ones before the launch: min (cost << 32 | linear)
+};
+void launch_front_costs(const FrontCostsArgs& A, hipStream_t s);
+
 // ---- deskew of a scan under constant velocity (tl_deskew.hip) -------------
 struct DeskewArgs {
   const double* in;               // AoS xyz [3n]

@@ -470,7 +470,7 @@ struct CmapState {
   void drop_carve() {
     carved = false;
     carve_info = tloam_closed_map_carve_info{};
-    free.clear.drop();             // the clearance may have been built under the gate
+    free.drop_fields();            // the clearance and the frontiers may have been built under the gate (DESIGN.md sections 30, 32)
   }
   // the surfels (tl_api_surfel.hip): their configuration, the thirteen sums, the normals and the variances
   // in id order beside the rows (allocated by the first pass, for the rows' capacity), what the last pass reports, the box read's
@@ -586,12 +586,50 @@ struct CmapState {
         route.drop();
       }
     } clear;
+    // the frontiers (tl_api_frontier.hip): their configuration, the label field with its two arrays of
+    // tile flags, the cluster table (roots, records, the kept list's records, a component's kept index) and the look-back words
+    // of its compactions, the control words, what the last build reports and its kept list on the host, a query's outputs and a
+    // column call's own field and table (grow-only scratch).  The field belongs to the grid and the map's counting voxels, not to
+    // the clearance: whatever changes either drops it (drop_fields below), the clearance's and the route's calls leave it alone
+    struct FrontierState {
+      tloam_closed_map_frontier_config cfg;   // tloam_closed_map_frontier_default_config until configured
+      FrontierState() { tloam_closed_map_frontier_default_config(&cfg); }
+      struct Bufs {
+        DBuf<unsigned> label, flags, roots;
+        DBuf<tloam_closed_map_frontier_cluster> rec, kept_rec;
+        DBuf<int> kept_of;
+        DBuf<unsigned long long> look;
+        void release() { label.release(); flags.release(); roots.release(); rec.release(); kept_rec.release(); kept_of.release(); look.release(); }
+      } own, col;
+      DBuf<unsigned long long> ctl, keys;
+      DBuf<unsigned> out_u32;
+      DBuf<int> out_i32;
+      DBuf<double> out_f64;
+      tl::FrontField field{};
+      tl::FrontTable table{};
+      std::vector<tloam_closed_map_frontier_cluster> kept;   // the kept list as the build read it back
+      bool have = false;           // a build has succeeded since the last drop
+      tloam_closed_map_frontier_info info{};
+      void drop() {
+        have = false;
+        info = tloam_closed_map_frontier_info{};
+        field = tl::FrontField{};
+        table = tl::FrontTable{};
+        kept.clear();
+        own.release();             // (hipFree waits for the launches that use them)
+      }
+    } frontier;
+    // what was built from the grid and the map's counting voxels goes when either changes: the one list
+    void drop_fields() {
+      clear.drop();
+      frontier.drop();
+    }
     void drop() {
       have = false;
       info = tloam_closed_map_free_info{};
       grid = tl::FreeGrid{};
       words.release();             // (hipFree waits for the launches that use it)
-      clear.drop();
+      drop_fields();
     }
   } free;
   void drop() {   // the closed map goes, and the carve's counts, the surfels, the diff's counts, the last ray-cast's info and the free-space

@@ -493,3 +493,94 @@ def read_route_paths_pcd(path: str):
     """Reads a file of write_route_paths_pcd -> (waypoints (n, 3) float64, path index (n,) int64)."""
     rec = _read_xyz_and_one(path, "path")
     return np.ascontiguousarray(rec[:, :3]), rec[:, 3].astype(np.int64)
+
+
+# ---- the frontiers of the closed map (DESIGN.md section 32): the kept clusters' cells with their cluster index, and the clusters
+def _write_xyz_and_fields(path: str, names, rec, ascii: bool) -> None:
+    """rows of x y z and the float64 fields `names` as PCD v0.7 (`F 8` each), DATA binary or ascii (17 significant digits)"""
+    n, k = len(rec), 3 + len(names)
+    header = ("# .PCD v0.7 - Point Cloud Data file format\n"
+              "VERSION 0.7\n"
+              f"FIELDS x y z {' '.join(names)}\n"
+              f"SIZE {' '.join(['8'] * k)}\n"
+              f"TYPE {' '.join(['F'] * k)}\n"
+              f"COUNT {' '.join(['1'] * k)}\n"
+              f"WIDTH {n}\n"
+              "HEIGHT 1\n"
+              "VIEWPOINT 0 0 0 1 0 0 0\n"
+              f"POINTS {n}\n"
+              f"DATA {'ascii' if ascii else 'binary'}\n")
+    with open(path, "wb") as fh:
+        fh.write(header.encode("ascii"))
+        if ascii:
+            fh.write("".join(" ".join(f"{v:.17g}" for v in row) + "\n" for row in rec.tolist()).encode("ascii"))
+        else:
+            fh.write(rec.tobytes())
+
+
+def _read_xyz_and_fields(path: str, names):
+    """a file of _write_xyz_and_fields -> (n, 3 + len(names)) float64"""
+    with open(path, "rb") as fh:
+        raw = fh.read()
+    head, pos, k = {}, 0, 3 + len(names)
+    while True:
+        end = raw.index(b"\n", pos)
+        line = raw[pos:end].decode("ascii").strip()
+        pos = end + 1
+        if not line or line.startswith("#"):
+            continue
+        key, _, val = line.partition(" ")
+        head[key.upper()] = val.split()
+        if key.upper() == "DATA":
+            break
+    if head.get("FIELDS") != ["x", "y", "z", *names] or head.get("SIZE") != ["8"] * k or head.get("TYPE") != ["F"] * k:
+        raise ValueError(f"{path}: only FIELDS x y z {' '.join(names)} with SIZE 8 / TYPE F are read")
+    n = int(head["POINTS"][0])
+    kind = head["DATA"][0]
+    if kind == "binary":
+        body = raw[pos: pos + 8 * k * n]
+        if len(body) != 8 * k * n:
+            raise ValueError(f"{path}: {len(body)} bytes of data for {n} points")
+        return np.frombuffer(body, dtype="<f8").reshape(n, k)
+    if kind == "ascii":
+        rows = raw[pos:].split()
+        if len(rows) != k * n:
+            raise ValueError(f"{path}: {len(rows)} values for {n} points")
+        return np.array([float(v) for v in rows], dtype=np.float64).reshape(n, k)
+    raise ValueError(f"{path}: DATA {kind} is not supported")
+
+
+def write_frontier_pcd(path: str, H, ascii: bool = False) -> int:
+    """Writes the centres of the frontier cells of the kept clusters (a HipRegistration after closed_map_frontier_build), ascending
+    in linear index, each with the index of its cluster in the kept list as a fourth field, `cluster` (float64 like the rest:
+    `F 8`), as PCD v0.7 -> the cells written."""
+    cen, roots = H.closed_map_frontier_cells()
+    kept = H.closed_map_frontier_clusters()[0]["root"]
+    index = np.searchsorted(kept, roots).astype(np.float64)
+    rec = np.ascontiguousarray(np.concatenate([cen.reshape(-1, 3), index.reshape(-1, 1)], axis=1), dtype="<f8")
+    _write_xyz_and_fields(path, ["cluster"], rec, ascii)
+    return len(rec)
+
+
+def read_frontier_pcd(path: str):
+    """Reads a file of write_frontier_pcd (DATA ascii or binary) -> (centres (n, 3) float64, cluster index (n,) int64)."""
+    rec = _read_xyz_and_fields(path, ["cluster"])
+    return np.ascontiguousarray(rec[:, :3]), rec[:, 3].astype(np.int64)
+
+
+def write_frontier_clusters_pcd(path: str, H, with_cost: bool = True, ascii: bool = False) -> int:
+    """Writes the centroids of the kept clusters with `cells`, `unknown_faces` and `cost` (closed_map_frontier_costs' -- it needs a
+    built route field --, or with_cost False: NaN) as PCD v0.7, six float64 (`F 8`) -> the clusters written."""
+    rec, cen = H.closed_map_frontier_clusters()
+    cost = H.closed_map_frontier_costs()[0].astype(np.float64) if with_cost else np.full(len(rec), np.nan)
+    rows = np.concatenate([cen.reshape(-1, 3), rec["cells"].astype(np.float64).reshape(-1, 1),
+                           rec["unknown_faces"].astype(np.float64).reshape(-1, 1), cost.reshape(-1, 1)], axis=1)
+    _write_xyz_and_fields(path, ["cells", "unknown_faces", "cost"], np.ascontiguousarray(rows, dtype="<f8"), ascii)
+    return len(rows)
+
+
+def read_frontier_clusters_pcd(path: str):
+    """Reads a file of write_frontier_clusters_pcd -> (centroids (k, 3) float64, cells (k,) int64, unknown_faces (k,) int64,
+    cost (k,) float64)."""
+    rec = _read_xyz_and_fields(path, ["cells", "unknown_faces", "cost"])
+    return np.ascontiguousarray(rec[:, :3]), rec[:, 3].astype(np.int64), rec[:, 4].astype(np.int64), np.ascontiguousarray(rec[:, 5])

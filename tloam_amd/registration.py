@@ -105,6 +105,7 @@ _CONFIGS = {
     FreeConfig: ("tloam_closed_map_free_default_config", {}),
     ClearanceConfig: ("tloam_closed_map_clearance_default_config", {}),
     RouteConfig: ("tloam_closed_map_route_default_config", {}),
+    FrontierConfig: ("tloam_closed_map_frontier_default_config", {}),
 }
 
 
@@ -706,7 +707,7 @@ class HipRegistration:
     def closed_map_configure(self, cfg: ClosedMapConfig | None = None, **over):
         """the closed map's configuration (default_closed_map_config(**over) when cfg is None); empties it.  Kept across
         odometry_reset."""
-        self._configure(ClosedMapConfig, "tloam_closed_map_configure", cfg, over)
+        self._cmap_cfg = self._configure(ClosedMapConfig, "tloam_closed_map_configure", cfg, over)
 
     def closed_map_build(self, pose_source=1, poses=None) -> dict:
         """builds the closed map from every keyframe's stored clouds, replacing the previous one -> info dict.  pose_source 0: the
@@ -774,6 +775,8 @@ class HipRegistration:
         self._call("tloam_closed_map_load", blob, len(blob), C.byref(info))
         # (the keyframe getters size their outputs by the place configuration's layout, which is now the snapshot's)
         self._place_cfg = default_place_config(enabled=1, n_rings=int(info.n_rings), n_sectors=int(info.n_sectors))
+        # (... and the frontier clusters' centroids are formed from the grid, which is now the snapshot's too)
+        self._cmap_cfg = default_closed_map_config(voxel=float(info.voxel), origin=tuple(float(v) for v in info.origin))
         return info.as_dict()
 
     # ---- the carve of the closed map: per voxel, the rays that passed through it
@@ -1173,8 +1176,108 @@ class HipRegistration:
         k = shape[0] * shape[1]
         return state[:k].reshape(shape).copy(), d2[:k].reshape(shape).copy(), cost[:k].reshape(shape).copy(), info.as_dict()
 
+    # ---- the frontiers of the closed map: where free space meets the unknown, clustered
+    def closed_map_frontier_configure(self, cfg: FrontierConfig | None = None, **over):
+        """the frontiers' configuration (default_closed_map_frontier_config(**over) when cfg is None); drops the frontier field
+        only.  Kept across odometry_reset; a refused configuration leaves the old one."""
+        self._configure(FrontierConfig, "tloam_closed_map_frontier_configure", cfg, over)
+
+    def closed_map_frontier_build(self) -> dict:
+        """labels the frontier cells of the free-space grid's box by cluster and gathers the clusters -> info dict (its
+        FRONTIER_DIAGNOSTICS fields may differ from run to run)"""
+        return self._info(FrontierInfo, "tloam_closed_map_frontier_build")
+
+    def closed_map_frontier_info(self) -> dict:
+        return self._info(FrontierInfo, "tloam_closed_map_get_frontier_info")
+
+    def closed_map_frontier_field(self):
+        """the whole field -> (nz, ny, nx) uint32: a frontier cell's cluster root, else FRONTIER_FREE, FRONTIER_UNKNOWN or
+        FRONTIER_OCCUPIED"""
+        nx, ny, nz = self.closed_map_frontier_info()["n_cells"]
+        label = np.zeros(max(nx * ny * nz, 1), np.uint32)
+        self._call("tloam_closed_map_read_frontier", 0, nx * ny * nz, _u32p(label))
+        return label[: nx * ny * nz].reshape(nz, ny, nx).copy()
+
+    def _probe_count(self, name, *args):
+        """the first of a capacity-convention getter's two calls: capacity 0 and no outputs -> the count (a short capacity, -1,
+        with n > 0 is its answer)"""
+        n = C.c_size_t(0)
+        rc = getattr(self.L, name)(self.h, *args, C.byref(n))
+        if rc not in (0, -1) or (rc == -1 and n.value == 0):
+            self._check(rc, name)
+        return n.value
+
+    def _frontier_centroids(self, rec, box_lo):
+        """o + (lo_cells + sum / cells + 0.5) * v per axis, in double, in that order"""
+        cfg = getattr(self, "_cmap_cfg", None) or default_closed_map_config()
+        o, v = np.array(list(cfg.origin), np.float64), np.float64(cfg.voxel)
+        mean = rec["sum"].astype(np.float64) / rec["cells"].astype(np.float64)[:, None]
+        return o + ((np.asarray(box_lo, np.int64).astype(np.float64) + mean) + 0.5) * v
+
+    def closed_map_frontier_clusters(self):
+        """the kept clusters in ascending root -> (records (k,) of FRONTIER_CLUSTER_DTYPE, centroids (k, 3) float64)"""
+        m = self._probe_count("tloam_closed_map_frontier_clusters", 0, None)
+        rec = np.zeros(max(m, 1), FRONTIER_CLUSTER_DTYPE)
+        if m:
+            n = C.c_size_t(0)
+            self._call("tloam_closed_map_frontier_clusters", m, rec.ctypes.data, C.byref(n))
+        rec = rec[:m].copy()
+        return rec, self._frontier_centroids(rec, self.closed_map_frontier_info()["lo_cells"])
+
+    def closed_map_frontier_cells(self, root=FRONTIER_ALL):
+        """the frontier cells of the kept cluster of root `root` (FRONTIER_ALL: of every kept cluster), ascending in linear index
+        -> (centres (m, 3) float64, roots (m,) uint32); a root that is no kept cluster's gives none"""
+        m = self._probe_count("tloam_closed_map_read_frontier_cells", int(root), 0, None, None)
+        cen, roots = np.zeros((max(m, 1), 3), np.float64), np.zeros(max(m, 1), np.uint32)
+        if m:
+            n = C.c_size_t(0)
+            self._call("tloam_closed_map_read_frontier_cells", int(root), m, _dp(cen), _u32p(roots), C.byref(n))
+        return cen[:m].copy(), roots[:m].copy()
+
+    def closed_map_frontier_points(self, points, pose=None):
+        """the frontier field at `points` (n, 3; map frame, or the sensor frame of `pose`) -> (label (n,) uint32 --
+        FRONTIER_OUTSIDE for a cell outside the box or an invalid point --, cluster (n,) int32: the index in the kept list or -1,
+        counts (5,) int64: frontier, free, unknown, occupied, outside)"""
+        pts = _aos(points)
+        n = len(pts)
+        label, cluster = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.int32)
+        counts = np.zeros(5, np.int64)
+        self._call("tloam_closed_map_frontier_points", _dp(pts), n, None if pose is None else _dp(_colmajor(pose)), _u32p(label),
+                   _ip(cluster), _lp(counts))
+        return label[:n].copy(), cluster[:n].copy(), counts
+
+    def closed_map_frontier_costs(self):
+        """the join with the built route field -> (cost (k,) uint32 per kept cluster: the least route cost within `reach` cells
+        of its cells, ROUTE_UNREACHED without one; approach (k, 3) float64: the centre of that cell, NaN without one).  A route
+        built from the robot's cell as the one goal gives the robot's cost to every cluster: the route's moves are symmetric."""
+        m = self._probe_count("tloam_closed_map_frontier_costs", 0, None, None)
+        cost, approach = np.zeros(max(m, 1), np.uint32), np.zeros((max(m, 1), 3), np.float64)
+        if m:
+            n = C.c_size_t(0)
+            self._call("tloam_closed_map_frontier_costs", m, _u32p(cost), _dp(approach), C.byref(n))
+        return cost[:m].copy(), approach[:m].copy()
+
+    def closed_map_frontier_columns(self, z_lo, z_hi, min_free=1):
+        """the 2-D frontiers over closed_map_free_columns' layer, 4 face neighbours and 8-connectivity -> (label (ny, nx) uint32,
+        kept records, centroids (k, 3) -- their z the box's lowest layer of cells --, info dict); computed per call, not stored"""
+        nb = self.closed_map_free_info()["n_bricks"]
+        nx, ny = 4 * nb[0], 4 * nb[1]
+        label = np.zeros(max(nx * ny, 1), np.uint32)
+        info, n = FrontierInfo(), C.c_size_t(0)
+        args = (float(z_lo), float(z_hi), int(min_free))
+        rc = self.L.tloam_closed_map_frontier_columns(self.h, *args, _u32p(label), 0, None, C.byref(n), C.byref(info))
+        if rc not in (0, -1) or (rc == -1 and n.value == 0):
+            self._check(rc, "tloam_closed_map_frontier_columns")
+        m = n.value
+        rec = np.zeros(max(m, 1), FRONTIER_CLUSTER_DTYPE)
+        if m:
+            self._call("tloam_closed_map_frontier_columns", *args, _u32p(label), m, rec.ctypes.data, C.byref(n), C.byref(info))
+        rec = rec[:m].copy()
+        return label[: nx * ny].reshape(ny, nx).copy(), rec, self._frontier_centroids(rec, info.as_dict()["lo_cells"]), info.as_dict()
+
     def fitness(self):
         f, r = C.c_double(0), C.c_double(0)
+
         rc = self.L.tloam_fitness(self.h, C.byref(f), C.byref(r))
         return rc, f.value, r.value
 
@@ -1406,6 +1509,12 @@ def default_closed_map_free_config(**over) -> FreeConfig:
     """tloam_closed_map_free_default_config (max_range 60, end_margin 1, ray_mask 0: the build's, max_bytes 1 GiB, min_count 1,
     min_miss 3, miss_ratio 1, carve_gate 0) with keyword overrides; an unknown field raises"""
     return _default(FreeConfig, over)
+
+
+def default_closed_map_frontier_config(**over) -> FrontierConfig:
+    """tloam_closed_map_frontier_default_config (max_bytes 1 GiB, min_cells 8, reach 2, max_rounds 65536, rounds_per_wait 16)
+    with keyword overrides"""
+    return _default(FrontierConfig, over)
 
 
 def default_closed_map_route_config(**over) -> RouteConfig:
