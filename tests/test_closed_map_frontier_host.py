@@ -1,4 +1,4 @@
-"""The host arithmetic of the frontier field (tloam_amd/csrc/tl_frontier_box.hpp) under the host
+"""The host arithmetic of the frontier field (tloam_amd/csrc/tl_tile_box.hpp) under the host
 sanitizers, without a GPU: a stand-alone program (tests/host/frontier_box_main.cpp, its own main, no HIP) built with
 -fsanitize=address,undefined and run as a child process."""
 import os

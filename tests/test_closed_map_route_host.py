@@ -1,4 +1,4 @@
-"""The host arithmetic of the route field (tloam_amd/csrc/tl_route_box.hpp) under the host sanitizers,
+"""The host arithmetic of the route field (tloam_amd/csrc/tl_tile_box.hpp) under the host sanitizers,
 without a GPU: a stand-alone program (tests/host/route_box_main.cpp, its own main, no HIP) built with
 -fsanitize=address,undefined and run as a child process."""
 import os

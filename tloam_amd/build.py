@@ -80,7 +80,7 @@ UNITS = [
     ("tl_api_snapshot.hip", []), # the closed map's snapshot: save, probe, load
     ("tl_probe.hip", []),        # read-stream bandwidth probe (the on-box ceiling of the bench's roofline block)
 ]
-HEADERS = ["tl_common.hpp", "tl_forms.hpp", "tl_grid_plan.hpp", "tl_scan.hpp", "tl_se3.hpp", "tl_knn.hpp", "tl_walk.hpp", "tl_voxel.hpp", "tl_ctx.hpp", "tl_step.hpp", "tl_finish.hpp", "tl_prep.hpp", "tl_seg.hpp", "tl_extend_host.hpp", "tl_free_box.hpp", "tl_clear_box.hpp", "tl_route_box.hpp", "tl_frontier_box.hpp", os.path.join("..", "..", "include", "tloam_hip.h")]
+HEADERS = ["tl_common.hpp", "tl_forms.hpp", "tl_grid_plan.hpp", "tl_scan.hpp", "tl_se3.hpp", "tl_knn.hpp", "tl_walk.hpp", "tl_voxel.hpp", "tl_ctx.hpp", "tl_step.hpp", "tl_finish.hpp", "tl_prep.hpp", "tl_seg.hpp", "tl_extend_host.hpp", "tl_free_box.hpp", "tl_clear_box.hpp", "tl_tile_box.hpp", "tl_tile.hpp", os.path.join("..", "..", "include", "tloam_hip.h")]
 
 
 def _hipcc():

@@ -1,6 +1,6 @@
 // tl_api_frontier.hip -- C ABI of the closed map's frontiers (include/tloam_hip.h: tloam_closed_map_frontier_*, _get_frontier_info,
 // _read_frontier, _read_frontier_cells; kernels in tl_frontier.hip; the tile, byte and table arithmetic in
-// tl_frontier_box.hpp).
+// tl_tile_box.hpp).
 //
 // The field is a FrontierState inside the free space's FreeState, beside the clearance's: a build resolves the states of the
 // grid's box as the occupancy query does (free_query: the one carve gate), marks the frontier cells, enqueues rounds_per_wait
@@ -12,7 +12,6 @@
 
 #include "tl_ctx.hpp"
 #include "tl_free_box.hpp"
-#include "tl_frontier_box.hpp"
 
 using namespace tl;
 
@@ -23,7 +22,7 @@ using FrontierState = FreeState::FrontierState;
 
 bool frontier_config_ok(const tloam_closed_map_frontier_config& m) {
   return m.max_bytes >= 4 && m.min_cells >= 1 && m.reach >= 0 && m.reach <= 4 && m.max_rounds >= 1 && m.rounds_per_wait >= 1 &&
-         m.rounds_per_wait <= kRouteMaxBatch;
+         m.rounds_per_wait <= kTileMaxBatch;
 }
 
 // the context, the grid and the field checked for a query of the field
@@ -36,23 +35,14 @@ int frontier_ready(const tloam_ctx* c) {
 // blocks of 256 threads over n items, as the launches count them (tl_voxel.hpp's blocks_of)
 size_t blocks256(size_t n) { return (n + 255) / 256; }
 
-FrontField field_of(const tlfr::FrontierBox& B, const int lo[3], unsigned* label) {
-  FrontField f;
-  memset(&f, 0, sizeof(f));
-  f.label = label;
-  for (int a = 0; a < 3; ++a) { f.lo[a] = lo[a]; f.n[a] = (int)B.n[a]; f.tiles[a] = (int)B.tiles[a]; }
-  f.cells = (long long)B.cells;
-  return f;
-}
-
 // What a build and a column call share, the field and the flags reserved and the seed's arguments filled but for its flags and
 // control words: the states and the marks, the rounds in batches of rounds_per_wait with one wait each, the count, the cluster
 // table sized from the count and gathered.  *info, *table and *kept filled on TLOAM_OK; on a failure launches may be in flight:
 // the caller drains the stream.
-int frontier_run(tloam_ctx* c, const char* who, FrontSeedArgs S, const tlfr::FrontierBox& B, FrontierState::Bufs& U,
+int frontier_run(tloam_ctx* c, const char* who, FrontSeedArgs S, const tlt::TileBox& B, FrontierState::Bufs& U,
                  tloam_closed_map_frontier_info* info, FrontTable* table, std::vector<tloam_closed_map_frontier_cluster>* kept) {
   FrontierState& Fr = c->cmap.free.frontier;
-  const FrontField& f = S.f;
+  const TileField& f = S.f;
   unsigned long long* ctl = Fr.ctl.p;
   const size_t ntiles = (size_t)B.ntiles;
   HIPC(c, hipMemsetAsync(U.flags.p, 0, sizeof(unsigned) * 2 * ntiles, c->stream));
@@ -61,37 +51,13 @@ int frontier_run(tloam_ctx* c, const char* who, FrontSeedArgs S, const tlfr::Fro
   S.ctl = ctl;
   int launches = launch_front_seed(S, c->stream);
   HIPC(c, hipGetLastError());
-  unsigned* now = U.flags.p;        // the frontier cells' marks are the first round's tiles
-  unsigned* next = U.flags.p + ntiles;
-  unsigned long long head[2] = {0ull, 0ull};
-  unsigned long long marks[kRouteMaxBatch];
-  int64_t rounds = 0, enqueued = 0, updates = 0;
-  int waits = 0;
-  bool done = false;
-  while (!done) {
-    const int batch = (int)std::min<int64_t>(Fr.cfg.rounds_per_wait, (int64_t)Fr.cfg.max_rounds - enqueued);
-    if (batch <= 0) {
-      c->last_error = std::string(who) + ": the labels had not settled after max_rounds = " + std::to_string(Fr.cfg.max_rounds) + " rounds";
-      return TLOAM_E_HIP;
-    }
-    if (enqueued) HIPC(c, hipMemsetAsync(ctl + kFrontRounds0, 0, sizeof(unsigned long long) * batch, c->stream));
-    for (int k = 0; k < batch; ++k) {
-      launch_front_round(f, now, next, ctl + kFrontRounds0 + k, c->stream);
-      std::swap(now, next);
-    }
-    HIPC(c, hipGetLastError());
-    if (!enqueued) HIPC(c, hipMemcpyAsync(head, ctl, sizeof(head), hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipMemcpyAsync(marks, ctl + kFrontRounds0, sizeof(unsigned long long) * batch, hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipStreamSynchronize(c->stream));
-    ++waits;
-    enqueued += batch;
-    for (int k = 0; k < batch && !done; ++k) {
-      ++rounds;
-      updates += (int64_t)marks[k];
-      done = marks[k] == 0ull;   // a round that marked nothing: the rounds after it found no flag up
-    }
-  }
-  launches += (int)enqueued;
+  unsigned long long head[2] = {0ull, 0ull};   // the frontier cells' marks are the first round's tiles
+  TileRounds r;
+  const int rc = tile_rounds(c, who, "labels", Fr.cfg.max_rounds, Fr.cfg.rounds_per_wait, f, U.flags.p, ntiles, ctl + kFrontRounds0,
+                             launch_front_round, ctl, head, 2, &r);
+  if (rc != TLOAM_OK) return rc;
+  int waits = r.waits;
+  launches += (int)r.enqueued;
   launch_front_count(f, ctl, c->stream);
   ++launches;
   HIPC(c, hipGetLastError());
@@ -101,7 +67,7 @@ int frontier_run(tloam_ctx* c, const char* who, FrontSeedArgs S, const tlfr::Fro
   ++waits;
   const size_t nroots = (size_t)w[4];
   uint64_t table_bytes = 0;
-  if (!tlfr::table_room(nroots, B.bytes, Fr.cfg.max_bytes, &table_bytes)) {
+  if (!tlt::table_room(nroots, B.bytes, Fr.cfg.max_bytes, &table_bytes)) {
     c->last_error = std::string(who) + ": the table of " + std::to_string(nroots) + " clusters does not fit under max_bytes = " +
                     std::to_string(Fr.cfg.max_bytes) + " beside the field";
     return TLOAM_E_HIP;
@@ -164,8 +130,8 @@ int frontier_run(tloam_ctx* c, const char* who, FrontSeedArgs S, const tlfr::Fro
   info->cells_kept = (int64_t)g[7];
   info->largest = (int64_t)g[8];
   info->unknown_faces = (int64_t)head[1];
-  info->tile_updates = (int64_t)head[0] + updates;
-  info->rounds = (int32_t)rounds;
+  info->tile_updates = (int64_t)head[0] + r.updates;
+  info->rounds = (int32_t)r.rounds;
   info->launches = launches;
   info->waits = waits;
   return TLOAM_OK;
@@ -218,8 +184,8 @@ int tloam_closed_map_frontier_build(tloam_ctx* c, tloam_closed_map_frontier_info
   FreeState& F = M.free;
   FrontierState& Fr = F.frontier;
   const int64_t cells[3] = {4 * (int64_t)F.grid.nb[0], 4 * (int64_t)F.grid.nb[1], 4 * (int64_t)F.grid.nb[2]};
-  tlfr::FrontierBox B;
-  if (!tlfr::make_frontier(cells, Fr.cfg.max_bytes, &B)) return TLOAM_E_INVALID;
+  tlt::TileBox B;
+  if (!tlt::make_box(cells, Fr.cfg.max_bytes, tlt::kFrontCellsBelow, &B)) return TLOAM_E_INVALID;
   HIPC(c, hipSetDevice(c->device));
   if (Fr.own.label.cap < (size_t)B.cells || Fr.own.flags.cap < 2 * (size_t)B.ntiles || Fr.ctl.cap < (size_t)kFrontCtl)
     HIPC(c, hipStreamSynchronize(c->stream));
@@ -234,7 +200,7 @@ int tloam_closed_map_frontier_build(tloam_ctx* c, tloam_closed_map_frontier_info
   // from here on the previous field is gone
   Fr.have = false;
   Fr.info = tloam_closed_map_frontier_info{};
-  Fr.field = FrontField{};
+  Fr.field = TileField{};
   Fr.table = FrontTable{};
   Fr.kept.clear();
   tloam_closed_map_frontier_info got;
@@ -262,7 +228,7 @@ int tloam_closed_map_read_frontier(tloam_ctx* c, size_t first, size_t count, uin
   if (count == 0) return TLOAM_OK;
   if (!label) return TLOAM_E_INVALID;
   HIPC(c, hipSetDevice(c->device));
-  HIPC(c, hipMemcpyAsync(label, Fr.field.label + first, sizeof(uint32_t) * count, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipMemcpyAsync(label, Fr.field.v + first, sizeof(uint32_t) * count, hipMemcpyDeviceToHost, c->stream));
   HIPC(c, hipStreamSynchronize(c->stream));
   return TLOAM_OK;
 }
@@ -379,8 +345,8 @@ int tloam_closed_map_frontier_costs(tloam_ctx* c, size_t capacity, uint32_t* cos
   FreeState& F = M.free;
   FrontierState& Fr = F.frontier;
   if (!F.clear.have || !F.clear.route.have) return TLOAM_E_NOT_READY;
-  const RouteField& R = F.clear.route.field;
-  const FrontField& f = Fr.field;
+  const TileField& R = F.clear.route.field;
+  const TileField& f = Fr.field;
   // both fields lie over the grid's box as it is: whatever changes the grid drops both
   if (R.cells != f.cells || R.lo[0] != f.lo[0] || R.lo[1] != f.lo[1] || R.lo[2] != f.lo[2] || R.n[0] != f.n[0] || R.n[1] != f.n[1] ||
       R.n[2] != f.n[2]) {
@@ -400,7 +366,7 @@ int tloam_closed_map_frontier_costs(tloam_ctx* c, size_t capacity, uint32_t* cos
   memset(&A, 0, sizeof(A));
   A.f = f;
   A.t = Fr.table;
-  A.cost = R.cost;
+  A.cost = R.v;
   A.reach = Fr.cfg.reach;
   A.keys = Fr.keys.p;
   launch_front_costs(A, c->stream);
@@ -438,8 +404,8 @@ int tloam_closed_map_frontier_columns(tloam_ctx* c, double z_lo, double z_hi, in
   if (!tlf::z_band(z_lo, z_hi, M.cfg.origin[2], M.cfg.voxel, F.grid.blo[2], F.grid.nb[2], &z0, &z1)) return TLOAM_E_INVALID;
   const size_t cx = 4 * (size_t)F.grid.nb[0], cy = 4 * (size_t)F.grid.nb[1], cols = cx * cy;   // (nb <= 2^19 each: no overflow)
   const int64_t cells[3] = {(int64_t)cx, (int64_t)cy, 1};
-  tlfr::FrontierBox B;
-  if (!tlfr::make_frontier(cells, Fr.cfg.max_bytes, &B)) return TLOAM_E_INVALID;
+  tlt::TileBox B;
+  if (!tlt::make_box(cells, Fr.cfg.max_bytes, tlt::kFrontCellsBelow, &B)) return TLOAM_E_INVALID;
   HIPC(c, hipSetDevice(c->device));
   if (M.scan_u8.cap < cols || Fr.col.label.cap < cols || Fr.col.flags.cap < 2 * (size_t)B.ntiles || Fr.ctl.cap < (size_t)kFrontCtl)
     HIPC(c, hipStreamSynchronize(c->stream));

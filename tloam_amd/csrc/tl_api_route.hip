@@ -1,5 +1,5 @@
 // tl_api_route.hip -- C ABI of the route through the closed map (include/tloam_hip.h: tloam_closed_map_route_*, _get_route_info,
-// _read_route; kernels in tl_route.hip; the tile, byte and bound arithmetic in tl_route_box.hpp; need in
+// _read_route; kernels in tl_route.hip; the tile, byte and bound arithmetic in tl_tile_box.hpp; need in
 // tl_clear_box.hpp, the one function the clearance's segments use).
 //
 // The field is a RouteState inside the clearance's ClearState: a build seeds it from the clearance field and the goals, enqueues
@@ -12,7 +12,6 @@
 #include "tl_clear_box.hpp"
 #include "tl_ctx.hpp"
 #include "tl_free_box.hpp"
-#include "tl_route_box.hpp"
 
 using namespace tl;
 
@@ -22,7 +21,7 @@ using ClearState = CmapState::FreeState::ClearState;
 using RouteState = ClearState::RouteState;
 
 bool route_config_ok(const tloam_closed_map_route_config& m) {
-  return m.max_bytes >= 4 && m.max_rounds >= 1 && m.rounds_per_wait >= 1 && m.rounds_per_wait <= kRouteMaxBatch;
+  return m.max_bytes >= 4 && m.max_rounds >= 1 && m.rounds_per_wait >= 1 && m.rounds_per_wait <= kTileMaxBatch;
 }
 
 // the context, the grid, the clearance field and the route field checked for a query of the route
@@ -32,19 +31,10 @@ int route_ready(const tloam_ctx* c) {
   return c->cmap.free.clear.have && c->cmap.free.clear.route.have ? TLOAM_OK : TLOAM_E_NOT_READY;
 }
 
-RouteField field_of(const tlr::RouteBox& B, const int lo[3], unsigned* cost) {
-  RouteField f;
-  memset(&f, 0, sizeof(f));
-  f.cost = cost;
-  for (int a = 0; a < 3; ++a) { f.lo[a] = lo[a]; f.n[a] = (int)B.n[a]; f.tiles[a] = (int)B.tiles[a]; }
-  f.cells = (long long)B.cells;
-  return f;
-}
-
 // What a build and a column call share, their buffers reserved and their arguments checked: the goals uploaded, the seed, the
 // rounds in batches of rounds_per_wait with one wait each, the count.  *info filled on TLOAM_OK; on a failure launches may be
 // in flight: the caller drains the stream.
-int route_run(tloam_ctx* c, const char* who, const RouteField& f, const tlr::RouteBox& B, const unsigned short* d2, int64_t need,
+int route_run(tloam_ctx* c, const char* who, const TileField& f, const tlt::TileBox& B, const unsigned short* d2, int64_t need,
               bool flat, unsigned* flags, const double* goals_aos, size_t n, const double* pose, tloam_closed_map_route_info* info) {
   CmapState& M = c->cmap;
   RouteState& Rt = M.free.clear.route;
@@ -69,42 +59,16 @@ int route_run(tloam_ctx* c, const char* who, const RouteField& f, const tlr::Rou
   S.ctl = ctl;
   launch_route_seed(S, c->stream);
   HIPC(c, hipGetLastError());
-  unsigned* now = flags;            // the goals' marks are the first round's tiles
-  unsigned* next = flags + ntiles;
-  unsigned long long head[8] = {0};
-  unsigned long long marks[kRouteMaxBatch];
-  int64_t rounds = 0, enqueued = 0, updates = 0;
-  int waits = 0;
-  bool done = false;
-  while (!done) {
-    const int batch = (int)std::min<int64_t>(Rt.cfg.rounds_per_wait, (int64_t)Rt.cfg.max_rounds - enqueued);
-    if (batch <= 0) {
-      c->last_error = std::string(who) + ": the field had not settled after max_rounds = " + std::to_string(Rt.cfg.max_rounds) + " rounds";
-      return TLOAM_E_HIP;
-    }
-    if (enqueued) HIPC(c, hipMemsetAsync(ctl + 8, 0, sizeof(unsigned long long) * batch, c->stream));
-    for (int k = 0; k < batch; ++k) {
-      launch_route_round(f, now, next, ctl + 8 + k, c->stream);
-      std::swap(now, next);
-    }
-    HIPC(c, hipGetLastError());
-    if (!enqueued) HIPC(c, hipMemcpyAsync(head, ctl, sizeof(head), hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipMemcpyAsync(marks, ctl + 8, sizeof(unsigned long long) * batch, hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipStreamSynchronize(c->stream));
-    ++waits;
-    enqueued += batch;
-    for (int k = 0; k < batch && !done; ++k) {
-      ++rounds;
-      updates += (int64_t)marks[k];
-      done = marks[k] == 0ull;   // a round that marked nothing: the rounds after it found no flag up
-    }
-  }
+  unsigned long long head[8] = {0};   // the goals' marks are the first round's tiles
+  TileRounds r;
+  const int rc = tile_rounds(c, who, "field", Rt.cfg.max_rounds, Rt.cfg.rounds_per_wait, f, flags, ntiles, ctl + 8, launch_route_round,
+                             ctl, head, 8, &r);
+  if (rc != TLOAM_OK) return rc;
   launch_route_count(f, ctl + 4, c->stream);
   HIPC(c, hipGetLastError());
   unsigned long long w[4];
   HIPC(c, hipMemcpyAsync(w, ctl + 4, sizeof(w), hipMemcpyDeviceToHost, c->stream));
   HIPC(c, hipStreamSynchronize(c->stream));
-  ++waits;
   *info = tloam_closed_map_route_info{};
   for (int a = 0; a < 3; ++a) { info->lo_cells[a] = f.lo[a]; info->n_cells[a] = B.n[a]; }
   info->bytes = (int64_t)B.bytes;
@@ -115,10 +79,10 @@ int route_run(tloam_ctx* c, const char* who, const RouteField& f, const tlr::Rou
   info->reached_cells = (int64_t)w[1];
   info->sum_cost = (int64_t)w[2];
   info->max_cost = (int64_t)w[3];
-  info->tile_updates = (int64_t)head[2] + updates;
-  info->rounds = (int32_t)rounds;
-  info->launches = (int32_t)(2 + enqueued + 1);
-  info->waits = waits;
+  info->tile_updates = (int64_t)head[2] + r.updates;
+  info->rounds = (int32_t)r.rounds;
+  info->launches = (int32_t)(2 + r.enqueued + 1);
+  info->waits = r.waits + 1;   // the rounds', and the count's
   return TLOAM_OK;
 }
 
@@ -163,8 +127,8 @@ int tloam_closed_map_route_build(tloam_ctx* c, const double* goals_aos, size_t n
   int64_t need = 0;
   if (!tlc::need_d2(radius, M.cfg.voxel, C.field.R, &need)) return TLOAM_E_INVALID;
   const int64_t cells[3] = {C.field.n[0], C.field.n[1], C.field.n[2]};
-  tlr::RouteBox B;
-  if (!tlr::make_route(cells, Rt.cfg.max_bytes, &B)) return TLOAM_E_INVALID;
+  tlt::TileBox B;
+  if (!tlt::make_box(cells, Rt.cfg.max_bytes, tlt::kRouteCellsBelow, &B)) return TLOAM_E_INVALID;
   HIPC(c, hipSetDevice(c->device));
   if (Rt.cost.cap < (size_t)B.cells || Rt.flags.cap < 2 * (size_t)B.ntiles || Rt.ctl.cap < (size_t)kRouteCtl || M.loc_pts.cap < 3 * n)
     HIPC(c, hipStreamSynchronize(c->stream));
@@ -172,11 +136,11 @@ int tloam_closed_map_route_build(tloam_ctx* c, const double* goals_aos, size_t n
   HIPC(c, Rt.flags.reserve(2 * (size_t)B.ntiles));
   HIPC(c, Rt.ctl.reserve(kRouteCtl));
   HIPC(c, M.loc_pts.reserve(3 * n));
-  const RouteField f = field_of(B, C.field.lo, Rt.cost.p);
+  const TileField f = field_of(B, C.field.lo, Rt.cost.p);
   // from here on the previous field is gone
   Rt.have = false;
   Rt.info = tloam_closed_map_route_info{};
-  Rt.field = RouteField{};
+  Rt.field = TileField{};
   tloam_closed_map_route_info got;
   const int rc = route_run(c, "tloam_closed_map_route_build", f, B, C.field.d2, need, false, Rt.flags.p, goals_aos, n, pose, &got);
   if (rc != TLOAM_OK) {
@@ -200,7 +164,7 @@ int tloam_closed_map_read_route(tloam_ctx* c, size_t first, size_t count, uint32
   if (count == 0) return TLOAM_OK;
   if (!cost) return TLOAM_E_INVALID;
   HIPC(c, hipSetDevice(c->device));
-  HIPC(c, hipMemcpyAsync(cost, Rt.field.cost + first, sizeof(uint32_t) * count, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipMemcpyAsync(cost, Rt.field.v + first, sizeof(uint32_t) * count, hipMemcpyDeviceToHost, c->stream));
   HIPC(c, hipStreamSynchronize(c->stream));
   return TLOAM_OK;
 }
@@ -258,7 +222,7 @@ int tloam_closed_map_route_paths(tloam_ctx* c, const double* starts_aos, size_t 
   CmapState& M = c->cmap;
   RouteState& Rt = M.free.clear.route;
   uint64_t waypoints = 0;
-  if (!tlr::path_room(n, max_cells, Rt.cfg.max_bytes, &waypoints)) return TLOAM_E_INVALID;
+  if (!tlt::path_room(n, max_cells, Rt.cfg.max_bytes, &waypoints)) return TLOAM_E_INVALID;
   int prepared = 0;
   return cmap_scan_call(
       c, CmapScanCall{starts_aos, n, pose, false, nullptr, 0, nullptr}, &prepared,
@@ -320,8 +284,8 @@ int tloam_closed_map_route_columns(tloam_ctx* c, double z_lo, double z_hi, int64
   if (!tlc::need_d2(radius, M.cfg.voxel, R, &need)) return TLOAM_E_INVALID;
   if (cols > (uint64_t)C.cfg.max_bytes / 4u) return TLOAM_E_INVALID;   // the clearance's two layers, as its column call holds them
   const int64_t cells[3] = {(int64_t)cx, (int64_t)cy, 1};
-  tlr::RouteBox B;
-  if (!tlr::make_route(cells, Rt.cfg.max_bytes, &B)) return TLOAM_E_INVALID;
+  tlt::TileBox B;
+  if (!tlt::make_box(cells, Rt.cfg.max_bytes, tlt::kRouteCellsBelow, &B)) return TLOAM_E_INVALID;
   HIPC(c, hipSetDevice(c->device));
   if (M.scan_u8.cap < cols || C.col_a.cap < cols || C.col_b.cap < cols || Rt.col_cost.cap < cols || Rt.col_flags.cap < 2 * (size_t)B.ntiles ||
       Rt.ctl.cap < (size_t)kRouteCtl || M.loc_pts.cap < 3 * n)
@@ -353,7 +317,7 @@ int tloam_closed_map_route_columns(tloam_ctx* c, double z_lo, double z_hi, int64
   A.tmp = C.col_b.p;
   (void)launch_clear_columns(A, c->stream);
   const int lo[3] = {4 * F.grid.blo[0], 4 * F.grid.blo[1], 0};
-  const RouteField f = field_of(B, lo, Rt.col_cost.p);
+  const TileField f = field_of(B, lo, Rt.col_cost.p);
   tloam_closed_map_route_info got;
   int rc = TLOAM_OK;
   hipError_t e = hipGetLastError();

@@ -204,46 +204,19 @@ __global__ __launch_bounds__(256) void k_clear_axis(const unsigned short* __rest
   }
 }
 
-__device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = max(v, (unsigned long long)__shfl_xor(v, off, 64));
-  return v;
-}
-
 __global__ __launch_bounds__(256) void k_clear_count(const unsigned short* __restrict__ d2, long long cells, unsigned long long* ctl) {
   const long long groups = cells >> 2, stride = (long long)gridDim.x * 256;
-  unsigned long long obstacles = 0ull, finite = 0ull, sum = 0ull, most = 0ull;
+  unsigned long long c[4] = {0ull, 0ull, 0ull, 0ull};   // obstacles, finite cells, their sum; the largest
   for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < groups; t += stride) {
     const uint2 v = reinterpret_cast<const uint2*>(d2)[t];
     const unsigned c0 = cell_of(v, 0), c1 = cell_of(v, 1), c2 = cell_of(v, 2), c3 = cell_of(v, 3);
-    obstacles += (c0 == 0u) + (c1 == 0u) + (c2 == 0u) + (c3 == 0u);
+    c[0] += (c0 == 0u) + (c1 == 0u) + (c2 == 0u) + (c3 == 0u);
     const unsigned f0 = c0 != kInf16 ? c0 : 0u, f1 = c1 != kInf16 ? c1 : 0u, f2 = c2 != kInf16 ? c2 : 0u, f3 = c3 != kInf16 ? c3 : 0u;
-    finite += (c0 != kInf16) + (c1 != kInf16) + (c2 != kInf16) + (c3 != kInf16);
-    sum += (unsigned long long)f0 + f1 + f2 + f3;
-    most = max(most, (unsigned long long)max(max(f0, f1), max(f2, f3)));
+    c[1] += (c0 != kInf16) + (c1 != kInf16) + (c2 != kInf16) + (c3 != kInf16);
+    c[2] += (unsigned long long)f0 + f1 + f2 + f3;
+    c[3] = max(c[3], (unsigned long long)max(max(f0, f1), max(f2, f3)));
   }
-  // the block's four waves through LDS, then one atomic per counter and BLOCK: one per wave (as k_free_count, whose grid is 64
-  // times smaller) was 8192 waves' atomics on four words and cost more than the three passes together
-  __shared__ unsigned long long s_part[4][4];
-  obstacles = wave_sum(obstacles);
-  finite = wave_sum(finite);
-  sum = wave_sum(sum);
-  most = wave_max(most);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    s_part[wave][0] = obstacles;
-    s_part[wave][1] = finite;
-    s_part[wave][2] = sum;
-    s_part[wave][3] = most;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    const unsigned long long v = s_part[0][threadIdx.x] + s_part[1][threadIdx.x] + s_part[2][threadIdx.x] + s_part[3][threadIdx.x];
-    if (v) atomicAdd(&ctl[threadIdx.x], v);
-  } else if (threadIdx.x == 3) {
-    const unsigned long long v = max(max(s_part[0][3], s_part[1][3]), max(s_part[2][3], s_part[3][3]));
-    if (v) atomicMax(&ctl[3], v);
-  }
+  block_fold<3, 1>(c, ctl);
 }
 
 __global__ __launch_bounds__(256) void k_clear_points(ClearPointsArgs A) {

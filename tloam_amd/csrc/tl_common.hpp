@@ -1017,24 +1017,28 @@ struct ClearColumnsArgs {
 };
 int launch_clear_columns(const ClearColumnsArgs& A, hipStream_t s);   // seed | x | y; returns the launches
 
+// ---- a dense field of uint32 over a box of cells, [z][y][x], x fastest, relaxed in tiles to a min-fixpoint by rounds (the
+// engine: tl_tile.hpp; its host runner: tl_ctx.hpp's tile_rounds; the box arithmetic: tl_tile_box.hpp): the route's costs and
+// the frontiers' labels
+constexpr int kTileMaxBatch = 1024;             // the most rounds between two waits (rounds_per_wait's range)
+struct TileField {
+  unsigned* v;                // [n[2]][n[1]][n[0]]
+  int lo[3];                  // the lowest cell of the box per axis
+  int n[3];                   // cells per axis (the frontiers': n[0] a multiple of 4)
+  int tiles[3];               // tiles per axis (tl_tile_box.hpp's kTileX x kTileY x kTileZ, the last of an axis partial)
+  int reserved0;
+  long long cells;
+};
+
 // ---- the route through the closed map (tl_route.hip): a dense field of uint32 over the clearance field's
 // box (or over a column layer: n[2] = 1), [z][y][x], x fastest: the least 3-4-5 chamfer weight to an accepted goal over the
 // traversable cells.  Nothing but the field, its tile flags and the control words is written
 constexpr unsigned kRouteUnreached = 0xFFFFFFFFu, kRouteBlocked = 0xFFFFFFFEu, kRouteOutside = 0xFFFFFFFDu;
-constexpr int kRouteMaxBatch = 1024;             // the most rounds between two waits (rounds_per_wait's range)
-constexpr int kRouteCtl = kRouteMaxBatch + 8;    // control words: [0] goals accepted, [1] rejected, [2] tiles the goals marked;
+constexpr int kRouteCtl = kTileMaxBatch + 8;     // control words: [0] goals accepted, [1] rejected, [2] tiles the goals marked;
                                                  // [4] traversable cells, [5] reached cells, [6] the sum, [7] the largest cost;
                                                  // [8 + k] the tiles round k of a batch marked
-struct RouteField {
-  unsigned* cost;             // [n[2]][n[1]][n[0]]
-  int lo[3];                  // the lowest cell of the box per axis
-  int n[3];                   // cells per axis
-  int tiles[3];               // tiles per axis (tl_route_box.hpp's kTileX x kTileY x kTileZ, the last of an axis partial)
-  int reserved0;
-  long long cells;
-};
 struct RouteSeedArgs {
-  RouteField f;
+  TileField f;
   const unsigned short* d2;   // the clearance (field or column layer) over the same box
   int need;                   // max(need, 1): a cell with d2 >= need is traversable
   int flat;                   // 1: the column form -- a goal is placed by x and y, its z cell is lo[2]
@@ -1047,10 +1051,10 @@ struct RouteSeedArgs {
 void launch_route_seed(const RouteSeedArgs& A, hipStream_t s);   // seed | goals: two launches
 // One round: a block a tile, the tiles flagged in `now` relaxed (and their flags taken down), their neighbours flagged in `next`,
 // the fresh flags counted into *marks
-void launch_route_round(const RouteField& f, unsigned* now, unsigned* next, unsigned long long* marks, hipStream_t s);
-void launch_route_count(const RouteField& f, unsigned long long* ctl, hipStream_t s);
+void launch_route_round(const TileField& f, unsigned* now, unsigned* next, unsigned long long* marks, hipStream_t s);
+void launch_route_count(const TileField& f, unsigned long long* ctl, hipStream_t s);
 struct RoutePointsArgs {
-  RouteField f;
+  TileField f;
   double voxel, origin[3];
   ScanAt scan;                // the points, and the pose when `posed`
   int posed, reserved0;
@@ -1060,7 +1064,7 @@ struct RoutePointsArgs {
 };
 void launch_route_points(const RoutePointsArgs& A, hipStream_t s);
 struct RoutePathsArgs {
-  RouteField f;
+  TileField f;
   double voxel, origin[3];
   ScanAt scan;                // the starts, and the pose when `posed`
   int posed, reserved0;
@@ -1078,19 +1082,11 @@ void launch_route_paths(const RoutePathsArgs& A, hipStream_t s);
 // cluster table and the control words is written
 constexpr unsigned kFrontFree = 0xFFFFFFFFu, kFrontUnknown = 0xFFFFFFFEu, kFrontOccupied = 0xFFFFFFFDu, kFrontOutside = 0xFFFFFFFCu;
 constexpr int kFrontRounds0 = 32;                      // the first of the rounds' control words
-constexpr int kFrontCtl = kRouteMaxBatch + kFrontRounds0;
+constexpr int kFrontCtl = kTileMaxBatch + kFrontRounds0;
 // control words: [0] tiles the frontier cells marked, [1] the unknown faces; [2] free, [3] unknown, [4] occupied, [5] frontier
 // cells, [6] roots; [8] the roots' start tickets, [9] their look-back's fault, [10] roots written; [12] [13] [14] the same of the
 // kept list; [15] cells kept, [16] the largest component; [20] [21] [22] the same three of a cells read; [24 .. 28] the points of
 // a query per kind; [kFrontRounds0 + k] the tiles round k of a batch marked
-struct FrontField {
-  unsigned* label;            // [n[2]][n[1]][n[0]]
-  int lo[3];                  // the lowest cell of the box per axis
-  int n[3];                   // cells per axis, n[0] a multiple of 4
-  int tiles[3];               // tiles per axis (tl_frontier_box.hpp's kTileX x kTileY x kTileZ, the last of an axis partial)
-  int reserved0;
-  long long cells;
-};
 struct FrontTable {           // the clusters of a field, ascending in root
   const unsigned* roots;      // [nroots]
   const int* kept_of;         // [nroots] a component's index in the kept list, -1 when it is not kept
@@ -1099,16 +1095,16 @@ struct FrontTable {           // the clusters of a field, ascending in root
 struct FrontSeedArgs {
   FreeQuery q;                // the 3-D form: brick words, then the counting voxel rows
   const unsigned char* state; // the column form: [n[1]][n[0]] of k_free_columns (null: the 3-D form)
-  FrontField f;
+  TileField f;
   unsigned* next;             // [tiles] the flags of the first round, zero before the launches
   unsigned long long* ctl;    // [kFrontCtl], zero before the launches
 };
 int launch_front_seed(const FrontSeedArgs& A, hipStream_t s);   // states (| voxels) | mark; returns the launches
 // One round: k_route_round's form with min over the 26 neighbours that are frontier cells
-void launch_front_round(const FrontField& f, unsigned* now, unsigned* next, unsigned long long* marks, hipStream_t s);
-void launch_front_count(const FrontField& f, unsigned long long* ctl, hipStream_t s);
+void launch_front_round(const TileField& f, unsigned* now, unsigned* next, unsigned long long* marks, hipStream_t s);
+void launch_front_count(const TileField& f, unsigned long long* ctl, hipStream_t s);
 struct FrontGatherArgs {
-  FrontField f;
+  TileField f;
   unsigned* roots;                             // [nroots] out, ascending
   tloam_closed_map_frontier_cluster* rec;      // [nroots] out
   tloam_closed_map_frontier_cluster* kept_rec; // [nroots] out: the records with cells >= min_cells, in order
@@ -1121,7 +1117,7 @@ struct FrontGatherArgs {
 };
 int launch_front_gather(const FrontGatherArgs& A, hipStream_t s);   // roots | accumulate | keep; returns the launches
 struct FrontCellsArgs {
-  FrontField f;
+  TileField f;
   FrontTable t;
   unsigned root;              // kFrontFree: the cells of every kept cluster
   int reserved0;
@@ -1134,7 +1130,7 @@ struct FrontCellsArgs {
 };
 void launch_front_cells(const FrontCellsArgs& A, hipStream_t s);
 struct FrontPointsArgs {
-  FrontField f;
+  TileField f;
   FrontTable t;
   double voxel, origin[3];
   ScanAt scan;                // the points, and the pose when `posed`
@@ -1145,7 +1141,7 @@ struct FrontPointsArgs {
 };
 void launch_front_points(const FrontPointsArgs& A, hipStream_t s);
 struct FrontCostsArgs {
-  FrontField f;
+  TileField f;
   FrontTable t;
   const unsigned* cost;       // the route field over the same box
   int reach, reserved0;

@@ -24,6 +24,7 @@
 
 #include "tl_common.hpp"
 #include "tl_seg.hpp"
+#include "tl_tile_box.hpp"
 
 
 namespace tlh {
@@ -566,13 +567,13 @@ struct CmapState {
         DBuf<unsigned long long> ctl;
         DBuf<int> out_i32;
         DBuf<double> out_f64;
-        tl::RouteField field{};
+        tl::TileField field{};
         bool have = false;           // a build has succeeded since the last drop
         tloam_closed_map_route_info info{};
         void drop() {
           have = false;
           info = tloam_closed_map_route_info{};
-          field = tl::RouteField{};
+          field = tl::TileField{};
           cost.release();            // (hipFree waits for the launches that use them)
           flags.release();
         }
@@ -605,7 +606,7 @@ struct CmapState {
       DBuf<unsigned> out_u32;
       DBuf<int> out_i32;
       DBuf<double> out_f64;
-      tl::FrontField field{};
+      tl::TileField field{};
       tl::FrontTable table{};
       std::vector<tloam_closed_map_frontier_cluster> kept;   // the kept list as the build read it back
       bool have = false;           // a build has succeeded since the last drop
@@ -613,7 +614,7 @@ struct CmapState {
       void drop() {
         have = false;
         info = tloam_closed_map_frontier_info{};
-        field = tl::FrontField{};
+        field = tl::TileField{};
         table = tl::FrontTable{};
         kept.clear();
         own.release();             // (hipFree waits for the launches that use them)
@@ -1271,6 +1272,61 @@ int cmap_scan_call(tloam_ctx* c, const CmapScanCall& q, int* prepared, Rooms roo
   if (rc != TLOAM_OK) (void)hipStreamSynchronize(c->stream);   // nothing of the call stays in flight
   if (q.records) M.loc_ready = rc == TLOAM_OK;                  // (a failed call's records are rebuilt by the next)
   return rc;
+}
+// the field over box B, its lowest cell at `lo`, its words at v
+inline tl::TileField field_of(const tlt::TileBox& B, const int lo[3], unsigned* v) {
+  tl::TileField f;
+  memset(&f, 0, sizeof(f));
+  f.v = v;
+  for (int a = 0; a < 3; ++a) { f.lo[a] = lo[a]; f.n[a] = (int)B.n[a]; f.tiles[a] = (int)B.tiles[a]; }
+  f.cells = (long long)B.cells;
+  return f;
+}
+// The rounds of a tiled field (tl_tile.hpp: the route's costs, the frontiers' labels) after its seed has flagged the first
+// round's tiles in flags[0 .. ntiles) (flags[ntiles .. 2 ntiles) zero): batches of min(rounds_per_wait, what max_rounds leaves)
+// launches of launch_round(f, now, next, marks, stream), `now` and `next` swapped after each, round k of a batch counting its
+// fresh marks into ctl_rounds[k] (zero before the first batch by the caller's memset, zeroed here before every later one); the
+// batch's counters read back -- with the first batch also head[0 .. n_head) from head_dev, what the seed counted -- and one wait a
+// batch.  The first round that marked nothing ends it: the rounds after it found no flag up.  When max_rounds are enqueued and
+// none has: last_error "<who>: the <noun> had not settled after max_rounds = ..." and TLOAM_E_HIP.  On a failure launches may
+// be in flight: the caller drains the stream.
+struct TileRounds {
+  int64_t rounds, enqueued, updates;   // rounds counted up to the first that marked nothing, launches enqueued, tiles marked
+  int waits;
+};
+template <class Launch>
+int tile_rounds(tloam_ctx* c, const char* who, const char* noun, int64_t max_rounds, int64_t rounds_per_wait, const tl::TileField& f,
+                unsigned* flags, size_t ntiles, unsigned long long* ctl_rounds, Launch launch_round, const unsigned long long* head_dev,
+                unsigned long long* head, size_t n_head, TileRounds* out) {
+  unsigned* now = flags;            // the seed's marks are the first round's tiles
+  unsigned* next = flags + ntiles;
+  unsigned long long marks[tl::kTileMaxBatch];
+  *out = TileRounds{};
+  bool done = false;
+  while (!done) {
+    const int batch = (int)std::min<int64_t>(rounds_per_wait, max_rounds - out->enqueued);
+    if (batch <= 0) {
+      c->last_error = std::string(who) + ": the " + noun + " had not settled after max_rounds = " + std::to_string(max_rounds) + " rounds";
+      return TLOAM_E_HIP;
+    }
+    if (out->enqueued) HIPC(c, hipMemsetAsync(ctl_rounds, 0, sizeof(unsigned long long) * batch, c->stream));
+    for (int k = 0; k < batch; ++k) {
+      launch_round(f, now, next, ctl_rounds + k, c->stream);
+      std::swap(now, next);
+    }
+    HIPC(c, hipGetLastError());
+    if (!out->enqueued) HIPC(c, hipMemcpyAsync(head, head_dev, sizeof(unsigned long long) * n_head, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(marks, ctl_rounds, sizeof(unsigned long long) * batch, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    ++out->waits;
+    out->enqueued += batch;
+    for (int k = 0; k < batch && !done; ++k) {
+      ++out->rounds;
+      out->updates += (int64_t)marks[k];
+      done = marks[k] == 0ull;   // a round that marked nothing: the rounds after it found no flag up
+    }
+  }
+  return TLOAM_OK;
 }
 // tl_api_deskew.hip: the frame's deskew -- sized and its times uploaded after the scan's upload, launched after the segmentation's
 // (the refused-time flag read with the frame's first wait), committed when the frame ends

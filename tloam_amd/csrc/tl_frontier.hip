@@ -12,13 +12,10 @@
 //   k_front_mark      grid x 256   a thread per cell: a kFrontFree cell with a kFrontUnknown face neighbour becomes its own index
 //                                  and flags its tile.  A neighbour already rewritten to an index was FREE; only equality with
 //                                  kFrontUnknown is tested and an UNKNOWN cell never changes: race-free in meaning
-//   k_front_round     tiles x 256  k_route_round's form: a block per tile of 32 x 8 x 4 cells, gone at once when its flag in `now`
-//                                  is down.  Else the tile and a halo of one cell are staged in LDS, everything that is no
-//                                  frontier cell (and what is outside the box) as kInf; a thread owns the four cells of a column
-//                                  along z and keeps which of them are frontier cells in a register mask.  It relaxes them in
-//                                  place, min over the 26 neighbours, to the tile's fixpoint or kFrontIters passes; on the cap
-//                                  the tile flags itself.  Only cells that fell are written back; each neighbouring tile that
-//                                  holds a cell next to one that fell is flagged in `next`; one atomic a block on the counter
+//   k_front_round     tiles x 256  one round of the tile engine (tl_tile.hpp's tile_round, which states the round and why any
+//                                  schedule gives the same bytes) under FrontRound: everything that is no frontier cell (and
+//                                  what is outside the box) is kInf in LDS, a move adds nothing, and a cell may fall when it
+//                                  is a frontier cell: its word in LDS is not kInf
 //   k_front_count     grid x 256   cells per state, frontier cells, roots (label == own index): k_clear_count's per-block form
 //   k_front_roots     grid x 256   the roots compacted in ascending order (block_packed_scan, lookback_prefix, as k_free_cells),
 //                                  each with an empty record
@@ -30,50 +27,39 @@
 //   k_front_points    grid x 256   a thread per point: the cell's value and its kept cluster
 //   k_front_costs     grid x 256   a thread per cell: a kept cluster's cell scans the route field within `reach` cells and lowers
 //                                  its cluster's key, (cost << 32) | linear, by one 64-bit unsigned atomicMin
-// Why any schedule gives the same bytes: a label only ever falls, and only to the label of a neighbouring frontier cell, which
-// is the index of a cell of the same component: it never goes below the component's least index.  A halo value read while its
-// owner lowers it may be old; it is then an upper bound, and the owner's mark runs the reader again in the next round.  The host
-// stops when a round marked nothing: no label can fall, every cell then holds the minimum over its component, and that fixpoint
-// is unique.  No block waits on another in the rounds: no spin, no CAS loop, no grid barrier; the only wait is the bounded
-// look-back of the three compactions (tl_voxel.hpp).  All integer but the centres; no run-time indexed private arrays, no scratch.
+// The operator is monotone and bounded below: a label only ever falls, and only to the label of a neighbouring frontier cell,
+// which is the index of a cell of the same component, so it never goes below the component's least index; at the fixpoint every
+// cell holds the minimum over its component, and that is unique.  No block waits on another in the rounds: no spin, no CAS loop,
+// no grid barrier; the only wait is the bounded look-back of the three compactions (tl_voxel.hpp).  All integer but the centres;
+// no run-time indexed private arrays, no scratch.
 // Compiled with -ffp-contract=off (tl_voxel.hpp asks for it: the points go through vmap_quantise).
 #include <algorithm>
 
-#include "tl_frontier_box.hpp"
+#include "tl_tile.hpp"
 #include "tl_voxel.hpp"
 
 namespace tl {
 namespace {
 
-constexpr int TX = tlfr::kTileX, TY = tlfr::kTileY, TZ = tlfr::kTileZ;
-constexpr int HX = TX + 2, HY = TY + 2, HZ = TZ + 2, kHalo = HX * HY * HZ;
-static_assert(TX * TY == 256 && TZ == 4, "a thread per column of four cells");
 constexpr unsigned kInf = 0xFFFFFFFFu;   // everything that is no frontier cell inside LDS: min never takes it
-constexpr int kFrontIters = 64;          // passes over a tile in LDS before it hands itself to the next round
+struct FrontRound {
+  static constexpr unsigned kNothing = kInf;
+  static constexpr unsigned kSentinel = kFrontOutside;
+  static constexpr int kPasses = 64;
+  static constexpr bool kLiveFromField = false;
+  static constexpr unsigned weight(int) { return 0u; }
+};
 
-// the index of cell (cx, cy, cz) in the field, -1 outside the box
-__device__ __forceinline__ long long front_index(const FrontField& f, int cx, int cy, int cz) {
-  const unsigned x = (unsigned)(cx - f.lo[0]), y = (unsigned)(cy - f.lo[1]), z = (unsigned)(cz - f.lo[2]);
-  if (!(x < (unsigned)f.n[0] && y < (unsigned)f.n[1] && z < (unsigned)f.n[2])) return -1;
-  return ((long long)z * f.n[1] + (long long)y) * f.n[0] + (long long)x;
-}
-// index -> box-local (x, y, z)
-__device__ __forceinline__ void front_xyz(const FrontField& f, long long idx, int* x, int* y, int* z) {
-  const long long row = idx / f.n[0];
-  *x = (int)(idx - row * f.n[0]);
-  *z = (int)(row / f.n[1]);
-  *y = (int)(row - (long long)*z * f.n[1]);
-}
 // the face neighbours of cell idx = (x, y, z), inside the box, that are UNKNOWN
-__device__ __forceinline__ unsigned front_faces(const FrontField& f, long long idx, int x, int y, int z) {
+__device__ __forceinline__ unsigned front_faces(const TileField& f, long long idx, int x, int y, int z) {
   const long long nx = f.n[0], plane = nx * f.n[1];
   unsigned faces = 0u;
-  if (x > 0 && f.label[idx - 1] == kFrontUnknown) ++faces;
-  if (x + 1 < f.n[0] && f.label[idx + 1] == kFrontUnknown) ++faces;
-  if (y > 0 && f.label[idx - nx] == kFrontUnknown) ++faces;
-  if (y + 1 < f.n[1] && f.label[idx + nx] == kFrontUnknown) ++faces;
-  if (z > 0 && f.label[idx - plane] == kFrontUnknown) ++faces;
-  if (z + 1 < f.n[2] && f.label[idx + plane] == kFrontUnknown) ++faces;
+  if (x > 0 && f.v[idx - 1] == kFrontUnknown) ++faces;
+  if (x + 1 < f.n[0] && f.v[idx + 1] == kFrontUnknown) ++faces;
+  if (y > 0 && f.v[idx - nx] == kFrontUnknown) ++faces;
+  if (y + 1 < f.n[1] && f.v[idx + nx] == kFrontUnknown) ++faces;
+  if (z > 0 && f.v[idx - plane] == kFrontUnknown) ++faces;
+  if (z + 1 < f.n[2] && f.v[idx + plane] == kFrontUnknown) ++faces;
   return faces;
 }
 // the slot of root `v` in the ascending list, -1 when it is none: at most 33 halvings
@@ -87,23 +73,6 @@ __device__ __forceinline__ long long front_slot(const unsigned* roots, long long
   return lo < nroots && roots[lo] == v ? lo : -1;
 }
 
-// the block's sums of up to four counters through LDS, one atomic per counter and block (k_clear_count's form)
-template <int N>
-__device__ __forceinline__ void block_add(unsigned long long (&v)[N], unsigned long long* const (&ctl)[N]) {
-  __shared__ unsigned long long s_part[4][N];
-  const int wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < N; ++k) {
-    const unsigned long long w = wave_sum(v[k]);
-    if ((threadIdx.x & 63) == 0) s_part[wave][k] = w;
-  }
-  __syncthreads();
-  if (threadIdx.x < N) {
-    const unsigned long long w = s_part[0][threadIdx.x] + s_part[1][threadIdx.x] + s_part[2][threadIdx.x] + s_part[3][threadIdx.x];
-    if (w) atomicAdd(ctl[threadIdx.x], w);
-  }
-}
-
 __global__ __launch_bounds__(256) void k_front_seed(FrontSeedArgs A) {
   const FreeGrid& g = A.q.g;
   const long long groups = A.f.cells >> 2, stride = (long long)gridDim.x * 256;
@@ -115,8 +84,8 @@ __global__ __launch_bounds__(256) void k_front_seed(FrontSeedArgs A) {
     const int y = (int)(row - z * ny);
     const unsigned long long w = g.words[((z >> 2) * g.nb[1] + (y >> 2)) * g.nb[0] + bx];
     const unsigned bits = (unsigned)(w >> ((((int)z & 3) << 4) | ((y & 3) << 2))) & 0xFu;
-    reinterpret_cast<uint4*>(A.f.label)[t] = make_uint4(bits & 1u ? kFrontFree : kFrontUnknown, bits & 2u ? kFrontFree : kFrontUnknown,
-                                                        bits & 4u ? kFrontFree : kFrontUnknown, bits & 8u ? kFrontFree : kFrontUnknown);
+    reinterpret_cast<uint4*>(A.f.v)[t] = make_uint4(bits & 1u ? kFrontFree : kFrontUnknown, bits & 2u ? kFrontFree : kFrontUnknown,
+                                                    bits & 4u ? kFrontFree : kFrontUnknown, bits & 8u ? kFrontFree : kFrontUnknown);
   }
 }
 
@@ -126,8 +95,8 @@ __global__ __launch_bounds__(256) void k_front_voxels(FrontSeedArgs A) {
   const VmapTableView& map = A.q.grid.map;
   if (!A.q.gate.counts(map, (int)id)) return;
   const unsigned long long key = map.pkey[id];
-  const long long idx = front_index(A.f, (int)key_axis(key, 0), (int)key_axis(key, 1), (int)key_axis(key, 2));
-  if (idx >= 0) A.f.label[idx] = kFrontOccupied;
+  const long long idx = tile_index(A.f, (int)key_axis(key, 0), (int)key_axis(key, 1), (int)key_axis(key, 2));
+  if (idx >= 0) A.f.v[idx] = kFrontOccupied;
 }
 
 __device__ __forceinline__ unsigned state_label(unsigned s) {
@@ -138,118 +107,33 @@ __global__ __launch_bounds__(256) void k_front_col_seed(FrontSeedArgs A) {
   const long long groups = A.f.cells >> 2, stride = (long long)gridDim.x * 256;
   for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < groups; t += stride) {
     const unsigned v = reinterpret_cast<const unsigned*>(A.state)[t];
-    reinterpret_cast<uint4*>(A.f.label)[t] =
+    reinterpret_cast<uint4*>(A.f.v)[t] =
         make_uint4(state_label(v & 0xFFu), state_label((v >> 8) & 0xFFu), state_label((v >> 16) & 0xFFu), state_label(v >> 24));
   }
 }
 
 __global__ __launch_bounds__(256) void k_front_mark(FrontSeedArgs A) {
-  const FrontField& f = A.f;
+  const TileField& f = A.f;
   const long long stride = (long long)gridDim.x * 256;
   unsigned long long v[2] = {0ull, 0ull};   // fresh tile marks, unknown faces
   for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < f.cells; idx += stride) {
-    if (f.label[idx] != kFrontFree) continue;   // (this cell's word: only this thread writes it)
+    if (f.v[idx] != kFrontFree) continue;   // (this cell's word: only this thread writes it)
     int x, y, z;
-    front_xyz(f, idx, &x, &y, &z);
+    tile_xyz(f, idx, &x, &y, &z);
     const unsigned faces = front_faces(f, idx, x, y, z);
     if (faces == 0u) continue;
-    f.label[idx] = (unsigned)idx;
+    f.v[idx] = (unsigned)idx;
     v[1] += faces;
-    unsigned* flag = &A.next[((long long)(z / TZ) * f.tiles[1] + y / TY) * f.tiles[0] + x / TX];
+    unsigned* flag = &A.next[tile_of(f, x, y, z)];
     // (a flag read as down may be up by now: the atomic decides who counts the mark)
     if (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u && atomicOr(flag, 1u) == 0u) v[0] += 1ull;
   }
-  unsigned long long* const ctl[2] = {&A.ctl[0], &A.ctl[1]};
-  block_add(v, ctl);
+  block_fold<2, 0>(v, A.ctl);
 }
 
-// min(cur, neighbour) over the 26 neighbours of the cell at s[at]: what is no frontier cell reads kInf
-__device__ __forceinline__ unsigned relax_cell(const unsigned* s, int at, unsigned cur) {
-  unsigned best = cur;
-#pragma unroll
-  for (int dz = -1; dz <= 1; ++dz)
-#pragma unroll
-    for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-      for (int dx = -1; dx <= 1; ++dx) {
-        if (dz == 0 && dy == 0 && dx == 0) continue;
-        best = min(best, s[at + (dz * HY + dy) * HX + dx]);
-      }
-  return best;
-}
-
-// the neighbouring tiles, as bits dz * 9 + dy * 3 + dx of (-1, 0, 1) + 1 each, that hold a cell next to cell (x, y, z) of a tile
-__device__ __forceinline__ unsigned tiles_next_to(int x, int y, int z) {
-  const unsigned ax = (x == 0 ? 1u : 0u) | 2u | (x == TX - 1 ? 4u : 0u);
-  const unsigned ay = (y == 0 ? 1u : 0u) | 2u | (y == TY - 1 ? 4u : 0u);
-  const unsigned az = (z == 0 ? 1u : 0u) | 2u | (z == TZ - 1 ? 4u : 0u);
-  const unsigned m9 = (ay & 1u ? ax : 0u) | (ax << 3) | (ay & 4u ? ax << 6 : 0u);
-  return (az & 1u ? m9 : 0u) | (m9 << 9) | (az & 4u ? m9 << 18 : 0u);
-}
-
-__global__ __launch_bounds__(256) void k_front_round(FrontField f, unsigned* __restrict__ now, unsigned* __restrict__ next,
+__global__ __launch_bounds__(256) void k_front_round(TileField f, unsigned* __restrict__ now, unsigned* __restrict__ next,
                                                      unsigned long long* __restrict__ marks) {
-  __shared__ unsigned s[kHalo];
-  __shared__ unsigned s_mask;
-  const long long tile = blockIdx.x;
-  if (now[tile] == 0u) return;   // (the block's own flag: nobody writes it in this launch before the barrier below)
-  const int tx = (int)(tile % f.tiles[0]);
-  const long long rest = tile / f.tiles[0];
-  const int ty = (int)(rest % f.tiles[1]), tz = (int)(rest / f.tiles[1]);
-  const int x0 = tx * TX, y0 = ty * TY, z0 = tz * TZ;
-  for (int i = threadIdx.x; i < kHalo; i += 256) {
-    const int lx = i % HX, r = i / HX, ly = r % HY, lz = r / HY;
-    const int gx = x0 + lx - 1, gy = y0 + ly - 1, gz = z0 + lz - 1;
-    unsigned v = kInf;
-    if ((unsigned)gx < (unsigned)f.n[0] && (unsigned)gy < (unsigned)f.n[1] && (unsigned)gz < (unsigned)f.n[2]) {
-      v = f.label[((long long)gz * f.n[1] + gy) * f.n[0] + gx];
-      if (v >= kFrontOutside) v = kInf;
-    }
-    s[i] = v;
-  }
-  if (threadIdx.x == 0) s_mask = 0u;
-  __syncthreads();
-  if (threadIdx.x == 0) now[tile] = 0u;   // taken down: the array is all zero when it becomes `next`
-  // this thread's column: the cells (x, y, 0 .. 3) of the tile; which of them are frontier cells (what is outside the box is kInf)
-  const int x = threadIdx.x & (TX - 1), y = threadIdx.x >> 5;
-  const long long plane = (long long)f.n[0] * f.n[1];
-  const long long g0 = ((long long)z0 * f.n[1] + (y0 + y)) * f.n[0] + (x0 + x);
-  constexpr int kLayer = HY * HX;
-  const int at = (HY + y + 1) * HX + x + 1;   // the column's cell z = 0 in the halo
-  const unsigned o0 = s[at], o1 = s[at + kLayer], o2 = s[at + 2 * kLayer], o3 = s[at + 3 * kLayer];
-  const unsigned front = (o0 != kInf ? 1u : 0u) | (o1 != kInf ? 2u : 0u) | (o2 != kInf ? 4u : 0u) | (o3 != kInf ? 8u : 0u);
-  unsigned c0 = o0, c1 = o1, c2 = o2, c3 = o3;
-  int again = 0;
-  for (int it = 0; it < kFrontIters; ++it) {
-    int fell = 0;
-    // in place: a neighbour read while its owner writes it is the old or the new value, both upper bounds
-    if (front & 1u) { const unsigned b = relax_cell(s, at, c0); if (b < c0) { c0 = b; s[at] = b; fell = 1; } }
-    if (front & 2u) { const unsigned b = relax_cell(s, at + kLayer, c1); if (b < c1) { c1 = b; s[at + kLayer] = b; fell = 1; } }
-    if (front & 4u) { const unsigned b = relax_cell(s, at + 2 * kLayer, c2); if (b < c2) { c2 = b; s[at + 2 * kLayer] = b; fell = 1; } }
-    if (front & 8u) { const unsigned b = relax_cell(s, at + 3 * kLayer, c3); if (b < c3) { c3 = b; s[at + 3 * kLayer] = b; fell = 1; } }
-    again = __syncthreads_or(fell);
-    if (!again) break;
-  }
-  unsigned m = 0u;
-  if (c0 < o0) { f.label[g0] = c0; m |= tiles_next_to(x, y, 0); }
-  if (c1 < o1) { f.label[g0 + plane] = c1; m |= tiles_next_to(x, y, 1); }
-  if (c2 < o2) { f.label[g0 + 2 * plane] = c2; m |= tiles_next_to(x, y, 2); }
-  if (c3 < o3) { f.label[g0 + 3 * plane] = c3; m |= tiles_next_to(x, y, 3); }
-  m &= ~(1u << 13);                                   // (the tile itself: only the cap below flags it)
-  if (again && threadIdx.x == 0) m |= 1u << 13;       // the cap was met with cells still falling
-  if (m) atomicOr(&s_mask, m);
-  __syncthreads();
-  if (threadIdx.x < 64) {                             // the first wave: a lane per direction
-    bool fresh = false;
-    const int d = threadIdx.x;
-    if (d < 27 && (s_mask >> d & 1u)) {
-      const int nx = tx + d % 3 - 1, ny = ty + d / 3 % 3 - 1, nz = tz + d / 9 - 1;
-      if ((unsigned)nx < (unsigned)f.tiles[0] && (unsigned)ny < (unsigned)f.tiles[1] && (unsigned)nz < (unsigned)f.tiles[2])
-        fresh = atomicOr(&next[((long long)nz * f.tiles[1] + ny) * f.tiles[0] + nx], 1u) == 0u;
-    }
-    const unsigned long long bal = __ballot(fresh);
-    if (threadIdx.x == 0 && bal) atomicAdd(marks, (unsigned long long)__popcll(bal));
-  }
+  tile_round<FrontRound>(f, now, next, marks);
 }
 
 __device__ __forceinline__ void count_cell(unsigned v, unsigned own, unsigned long long (&c)[5]) {
@@ -271,8 +155,7 @@ __global__ __launch_bounds__(256) void k_front_count(const unsigned* __restrict_
     count_cell(v.z, own + 2u, c);
     count_cell(v.w, own + 3u, c);
   }
-  unsigned long long* const out[5] = {&ctl[2], &ctl[3], &ctl[4], &ctl[5], &ctl[6]};
-  block_add(c, out);
+  block_fold<5, 0>(c, ctl + 2);
 }
 
 __global__ __launch_bounds__(256) void k_front_roots(FrontGatherArgs A, int nblocks) {
@@ -284,7 +167,7 @@ __global__ __launch_bounds__(256) void k_front_roots(FrontGatherArgs A, int nblo
   const unsigned own = (unsigned)(4 * t);
   unsigned pass = 0u;
   if (t < (A.f.cells >> 2)) {
-    const uint4 v = reinterpret_cast<const uint4*>(A.f.label)[t];
+    const uint4 v = reinterpret_cast<const uint4*>(A.f.v)[t];
     pass = (v.x == own ? 1u : 0u) | (v.y == own + 1u ? 2u : 0u) | (v.z == own + 2u ? 4u : 0u) | (v.w == own + 3u ? 8u : 0u);
   }
   unsigned long long before, total;
@@ -312,36 +195,22 @@ __global__ __launch_bounds__(256) void k_front_roots(FrontGatherArgs A, int nblo
   if (bid == nblocks - 1 && threadIdx.x == 0) A.ctl[10] = s_prefix + total;
 }
 
-// inclusive prefix sum of `v` over the wave's lanes, and the sum over lanes [head_lane, this lane] from it (k_surfel_accum's)
-__device__ __forceinline__ unsigned wave_scan(unsigned v, int lane) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const unsigned o = __shfl_up(v, off, 64);
-    if (lane >= off) v += o;
-  }
-  return v;
-}
-__device__ __forceinline__ unsigned run_sum(unsigned incl, int head_lane) {
-  const unsigned below = __shfl(incl, head_lane > 0 ? head_lane - 1 : 0, 64);
-  return incl - (head_lane > 0 ? below : 0u);
-}
-
 __global__ __launch_bounds__(256) void k_front_accum(FrontGatherArgs A) {
-  const FrontField& f = A.f;
+  const TileField& f = A.f;
   const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
   const int lane = threadIdx.x & 63;
   unsigned id = kInf;
   int x = 0, y = 0, z = 0;
   bool ok = false;
   if (g < f.cells) {
-    id = f.label[g];
+    id = f.v[g];
     ok = id < kFrontOutside;
   }
   const unsigned long long okb = __ballot(ok);
   if (okb == 0ull) return;   // (wave-uniform)
   unsigned cnt = ok ? 1u : 0u, sx = 0u, faces = 0u;
   if (ok) {
-    front_xyz(f, g, &x, &y, &z);
+    tile_xyz(f, g, &x, &y, &z);
     sx = (unsigned)x;
     faces = front_faces(f, g, x, y, z);
   }
@@ -394,8 +263,7 @@ __global__ __launch_bounds__(256) void k_front_keep(FrontGatherArgs A, unsigned 
   if (bid == nblocks - 1 && threadIdx.x == 0) A.ctl[14] = s_prefix + total;
   // the cells kept: the block's sum, one atomic; the largest component: a wave's, then one atomicMax a wave that has one
   unsigned long long v[1] = {keep ? (unsigned long long)cells : 0ull};
-  unsigned long long* const out[1] = {&A.ctl[15]};
-  block_add(v, out);
+  block_fold<1, 0>(v, &A.ctl[15]);
   unsigned most = cells;
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) most = max(most, (unsigned)__shfl_xor(most, off, 64));
@@ -407,12 +275,12 @@ __global__ __launch_bounds__(256) void k_front_cells(FrontCellsArgs A, int nbloc
   __shared__ unsigned long long s_prefix;
   __shared__ int s_bid;
   const int bid = block_ticket(&A.ctl[20], &s_bid);
-  const FrontField& f = A.f;
+  const TileField& f = A.f;
   const long long t = (long long)bid * 256 + threadIdx.x;
   unsigned pass = 0u;
   uint4 v = make_uint4(kInf, kInf, kInf, kInf);
   if (t < (f.cells >> 2)) {
-    v = reinterpret_cast<const uint4*>(f.label)[t];
+    v = reinterpret_cast<const uint4*>(f.v)[t];
     if (A.root != kFrontFree) {
       pass = (v.x == A.root ? 1u : 0u) | (v.y == A.root ? 2u : 0u) | (v.z == A.root ? 4u : 0u) | (v.w == A.root ? 8u : 0u);
     } else {
@@ -430,7 +298,7 @@ __global__ __launch_bounds__(256) void k_front_cells(FrontCellsArgs A, int nbloc
   if (p + (size_t)__popc(pass) > (size_t)A.m) pass = 0u;   // (a timed-out look-back must not write past the outputs)
   if (pass) {
     int x, y, z;
-    front_xyz(f, 4 * t, &x, &y, &z);   // (n[0] is a multiple of 4: the four cells share a row)
+    tile_xyz(f, 4 * t, &x, &y, &z);   // (n[0] is a multiple of 4: the four cells share a row)
     const double py = A.origin[1] + ((double)(f.lo[1] + y) + 0.5) * A.voxel, pz = A.origin[2] + ((double)(f.lo[2] + z) + 0.5) * A.voxel;
     if (pass & 1u) { A.centres[3 * p] = A.origin[0] + ((double)(f.lo[0] + x) + 0.5) * A.voxel; A.centres[3 * p + 1] = py; A.centres[3 * p + 2] = pz; A.roots_out[p] = v.x; ++p; }
     if (pass & 2u) { A.centres[3 * p] = A.origin[0] + ((double)(f.lo[0] + x + 1) + 0.5) * A.voxel; A.centres[3 * p + 1] = py; A.centres[3 * p + 2] = pz; A.roots_out[p] = v.y; ++p; }
@@ -447,13 +315,10 @@ __global__ __launch_bounds__(256) void k_front_points(FrontPointsArgs A) {
   if (live) {
     unsigned v = kFrontOutside;
     int cluster = -1;
-    double E[3] = {A.scan.pts[3 * g], A.scan.pts[3 * g + 1], A.scan.pts[3 * g + 2]};
-    if (A.posed) map_transform_point(A.scan.M, E[0], E[1], E[2], &E[0], &E[1], &E[2]);
-    unsigned long long key;
-    unsigned qq[3];
-    if (vmap_quantise(E, A.origin, A.voxel, &key, qq) == kVmapInside) {
-      const long long idx = front_index(A.f, (int)key_axis(key, 0), (int)key_axis(key, 1), (int)key_axis(key, 2));
-      if (idx >= 0) v = A.f.label[idx];
+    int cx, cy, cz;
+    if (route_cell(A.scan, A.posed, A.origin, A.voxel, g, &cx, &cy, &cz)) {
+      const long long idx = tile_index(A.f, cx, cy, cz);
+      if (idx >= 0) v = A.f.v[idx];
     }
     if (v < kFrontOutside) {
       const long long s = front_slot(A.t.roots, A.t.nroots, v);
@@ -471,17 +336,17 @@ __global__ __launch_bounds__(256) void k_front_points(FrontPointsArgs A) {
 }
 
 __global__ __launch_bounds__(256) void k_front_costs(FrontCostsArgs A) {
-  const FrontField& f = A.f;
+  const TileField& f = A.f;
   const long long stride = (long long)gridDim.x * 256;
   for (long long g = (long long)blockIdx.x * 256 + threadIdx.x; g < f.cells; g += stride) {
-    const unsigned v = f.label[g];
+    const unsigned v = f.v[g];
     if (v >= kFrontOutside) continue;
     const long long s = front_slot(A.t.roots, A.t.nroots, v);
     if (s < 0) continue;
     const int k = A.t.kept_of[s];
     if (k < 0) continue;
     int x, y, z;
-    front_xyz(f, g, &x, &y, &z);
+    tile_xyz(f, g, &x, &y, &z);
     const int xa = max(x - A.reach, 0), xb = min(x + A.reach, f.n[0] - 1);
     const int ya = max(y - A.reach, 0), yb = min(y + A.reach, f.n[1] - 1);
     const int za = max(z - A.reach, 0), zb = min(z + A.reach, f.n[2] - 1);
@@ -514,13 +379,13 @@ int launch_front_seed(const FrontSeedArgs& A, hipStream_t s) {
   return launches;
 }
 
-void launch_front_round(const FrontField& f, unsigned* now, unsigned* next, unsigned long long* marks, hipStream_t s) {
-  const long long tiles = (long long)f.tiles[0] * f.tiles[1] * f.tiles[2];   // (< 2^27: tl_frontier_box.hpp)
+void launch_front_round(const TileField& f, unsigned* now, unsigned* next, unsigned long long* marks, hipStream_t s) {
+  const long long tiles = (long long)f.tiles[0] * f.tiles[1] * f.tiles[2];   // (< 2^27: tl_tile_box.hpp)
   hipLaunchKernelGGL(k_front_round, dim3((unsigned)tiles), dim3(256), 0, s, f, now, next, marks);
 }
 
-void launch_front_count(const FrontField& f, unsigned long long* ctl, hipStream_t s) {
-  hipLaunchKernelGGL(k_front_count, dim3(std::min(blocks_of((size_t)(f.cells >> 2)), 512u)), dim3(256), 0, s, f.label, f.cells, ctl);
+void launch_front_count(const TileField& f, unsigned long long* ctl, hipStream_t s) {
+  hipLaunchKernelGGL(k_front_count, dim3(std::min(blocks_of((size_t)(f.cells >> 2)), 512u)), dim3(256), 0, s, f.v, f.cells, ctl);
 }
 
 int launch_front_gather(const FrontGatherArgs& A, hipStream_t s) {

@@ -62,24 +62,6 @@ __global__ __launch_bounds__(256) void k_surfel_flag(SurfelWork W) {
   if (surfel_point(W, g, s_span, &kf, &P, E, &key, q) == kVmapBeyond) W.kf_over[kf] = 1;
 }
 
-// inclusive prefix sum of `v` over the wave's lanes
-template <typename T>
-__device__ __forceinline__ T wave_scan(T v, int lane) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const T o = __shfl_up(v, off, 64);
-    if (lane >= off) v += o;
-  }
-  return v;
-}
-
-// the sum of `v` over lanes [head_lane, this lane] from its inclusive prefix sum
-template <typename T>
-__device__ __forceinline__ T run_sum(T incl, int head_lane) {
-  const T below = __shfl(incl, head_lane > 0 ? head_lane - 1 : 0, 64);
-  return incl - (head_lane > 0 ? below : (T)0);
-}
-
 template <bool kRuns>
 __global__ __launch_bounds__(256) void k_surfel_accum(SurfelWork W) {
   __shared__ int s_span[2];

@@ -3,7 +3,9 @@
 // surfels (tl_surfel.hip), the localiser (tl_localise.hip), the diff (tl_diff.hip), the ray-cast (tl_raycast.hip) and the free
 // space (tl_free.hip).  One definition each of the key hash,
 // the two table inserts and the slot table's lookup, of the wave's integer sum, its add to a control word (wave_add) and the
-// four-state ballot count (wave_count_states), of a cell's key and voxel (cell_key, cell_voxel) and the 27-cell probe round a
+// four-state ballot count (wave_count_states), of the wave's maximum and a block's counters folded with one atomic each a block
+// (wave_max, block_fold: k_clear_count, k_route_count, the frontiers' counts), of a wave's prefix sum and a run's sum from it
+// (wave_scan, run_sum: k_surfel_accum, k_front_accum), of a query point's cell (route_cell), of a cell's key and voxel (cell_key, cell_voxel) and the 27-cell probe round a
 // point's cell (probe27: k_loc_sweep, k_diff_points), of the block scans, of the single-pass
 // look-back with its one bound, of the eight-word post to the host, of the voxel map's key / q arithmetic, its row centroid
 // and its run sums, of the compacting box read's body (k_vmap_box, k_carve_box, k_surfel_box, k_diff_box), of the surfel gate,
@@ -79,6 +81,36 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
 __device__ __forceinline__ void wave_add(unsigned long long* ctl_word, unsigned long long v) {
   v = wave_sum(v);
   if ((threadIdx.x & 63) == 0 && v) atomicAdd(ctl_word, v);
+}
+// the largest `v` over the wave's 64 lanes, in every lane
+__device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = max(v, (unsigned long long)__shfl_xor(v, off, 64));
+  return v;
+}
+// A block's (256 threads) counters folded into ctl[0 .. NSUM + NMAX): the sums of v[0 .. NSUM) and the maxima of v[NSUM ..), the
+// four waves' partials through LDS, one barrier, then one atomic per counter and BLOCK, none for a zero.  Per block and not per
+// wave (wave_add): one per wave (as k_free_count, whose grid is 64 times smaller) was 8192 waves' atomics on k_clear_count's
+// four words and cost more than the clearance's three passes together.  Called by the whole block, once
+// a kernel (the LDS is its own).
+template <int NSUM, int NMAX>
+__device__ __forceinline__ void block_fold(unsigned long long (&v)[NSUM + NMAX], unsigned long long* ctl) {
+  __shared__ unsigned long long s_part[4][NSUM + NMAX];
+  const int wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < NSUM + NMAX; ++k) {
+    const unsigned long long w = k < NSUM ? wave_sum(v[k]) : wave_max(v[k]);
+    if ((threadIdx.x & 63) == 0) s_part[wave][k] = w;
+  }
+  __syncthreads();
+  const int k = threadIdx.x;
+  if (k < NSUM) {
+    const unsigned long long w = s_part[0][k] + s_part[1][k] + s_part[2][k] + s_part[3][k];
+    if (w) atomicAdd(&ctl[k], w);
+  } else if (k < NSUM + NMAX) {
+    const unsigned long long w = max(max(s_part[0][k], s_part[1][k]), max(s_part[2][k], s_part[3][k]));
+    if (w) atomicMax(&ctl[k], w);
+  }
 }
 // The wave's live lanes counted by `state` (0 .. 3) into ctl[0 .. 3] by ballot: one atomic per state and wave.  Called by the
 // whole wave.
@@ -329,6 +361,21 @@ __device__ __forceinline__ long long key_axis(unsigned long long key, int a) {
   return (long long)((key >> (21 * a)) & 0x1fffffull) - (1ll << kVmapBits);
 }
 
+// a query's point (point g of the scan, through its pose when `posed`) -> its cell; false: an INVALID point (the route's and the
+// frontiers' point queries, the route's goals and starts)
+__device__ __forceinline__ bool route_cell(const ScanAt& scan, int posed, const double origin[3], double voxel, long long g,
+                                           int* cx, int* cy, int* cz) {
+  double E[3] = {scan.pts[3 * g], scan.pts[3 * g + 1], scan.pts[3 * g + 2]};
+  if (posed) map_transform_point(scan.M, E[0], E[1], E[2], &E[0], &E[1], &E[2]);
+  unsigned long long key;
+  unsigned qq[3];
+  if (vmap_quantise(E, origin, voxel, &key, qq) != kVmapInside) return false;
+  *cx = (int)key_axis(key, 0);
+  *cy = (int)key_axis(key, 1);
+  *cz = (int)key_axis(key, 2);
+  return true;
+}
+
 // the key of cell (cx, cy, cz), |c| < 2^kVmapBits on every axis (the pack vmap_quantise forms)
 __device__ __forceinline__ unsigned long long cell_key(int cx, int cy, int cz) {
   const int lim = 1 << kVmapBits;
@@ -417,6 +464,23 @@ __device__ __forceinline__ void voxel_box_body(const VmapReadArgs& R, bool boxed
 __device__ __forceinline__ bool surfel_gate(long long ns, const double ev[3], int min_points, double max_sigma2,
                                             double min_planarity) {
   return ns >= (long long)min_points && ev[2] > 0.0 && ev[0] <= max_sigma2 && (ev[1] - ev[0]) >= min_planarity * ev[2];
+}
+
+// inclusive prefix sum of `v` over the wave's lanes (k_surfel_accum's moments, k_front_accum's counts)
+template <typename T>
+__device__ __forceinline__ T wave_scan(T v, int lane) {
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const T o = __shfl_up(v, off, 64);
+    if (lane >= off) v += o;
+  }
+  return v;
+}
+// the sum of `v` over lanes [head_lane, this lane] from its inclusive prefix sum
+template <typename T>
+__device__ __forceinline__ T run_sum(T incl, int head_lane) {
+  const T below = __shfl(incl, head_lane > 0 ? head_lane - 1 : 0, 64);
+  return incl - (head_lane > 0 ? below : (T)0);
 }
 
 // Runs of equal keys among a wave's consecutive `ok` lanes (neighbouring returns of a ring share their voxel), summed by
