@@ -1767,6 +1767,97 @@ int tloam_closed_map_frontier_columns(tloam_ctx* ctx, double z_lo, double z_hi, 
                                       size_t capacity, tloam_closed_map_frontier_cluster* clusters_out, size_t* n_out,
                                       tloam_closed_map_frontier_info* info_or_null);
 
+/* ---- the view gain of the closed map: the unknown cells seen from candidate poses (additive to ABI 8) -------
+ * How much would be learnt from a pose: a sensor's firing pattern cast through the box from the pose, the DISTINCT UNKNOWN cells
+ * its rays cross before an OCCUPIED cell or the box stops them, counted.  THE STATE SOURCE is the built frontier field
+ * (tloam_closed_map_frontier_build), its values at the moment of the call: a value below TLOAM_FRONTIER_OUTSIDE is a frontier
+ * label and counts as free, TLOAM_FRONTIER_FREE is free, TLOAM_FRONTIER_UNKNOWN unknown, TLOAM_FRONTIER_OCCUPIED occupied; a cell
+ * outside the box is outside.  Without a frontier field every call here but the configuration's and the info's is
+ * TLOAM_E_NOT_READY.  Nothing is stored beyond the configuration and the last info; whatever drops the frontier field clears the
+ * info; the frontier field, the route, the clearance, the grid, the map and the snapshot do not change by a bit.
+ * A VIEW is a pose matrix M_v (column-major, finite and rigid) and the segment ends p_r in the sensor frame, shared by all
+ * views.  Ray (v, r) runs from O = (M_v[12], M_v[13], M_v[14]) to E = M_v p_r, formed as the ray-cast forms it; skip rule, set-up
+ * and stepping are the ray-cast's (the carve's) under THIS configuration's max_range.  VISITED are the start cell, then every cell
+ * stepped into, THE END CELL INCLUDED (n + 1 cells, the ray-cast's convention).  Per visited cell, in visiting order, the first
+ * rule that applies decides: outside the box -- the walk ends, the ray counts in rays_left_box; OCCUPIED -- the walk ends, the
+ * ray counts in rays_occupied; UNKNOWN -- the cell's bit is set in the view's window, unknown_visits is incremented, the walk
+ * goes on: UNKNOWN SPACE IS TRANSPARENT, the usual optimistic model (a ray is not stopped by what is not known to be there);
+ * free, or a frontier label -- free_visits is incremented, the walk goes on.  A ray that passes its end cell counts in
+ * rays_ended, a skipped ray in rays_skipped and visits nothing; steps counts the cells visited, the stopping cell included.
+ * There is no special case for a bad origin: a view whose origin cell is outside the box ends every ray that is not skipped at
+ * its first cell, and with a NaN translation every ray is skipped.
+ * THE WINDOW: W = (int) ceil(max_range / voxel) + 1, formed on the host in double, S = 2 W + 1; the cells c with |c - c_O| <= W
+ * per axis, c_O = floor((O - o) / v); a cell's bit index is ((dz * S) + dy) * S + dx with d = c - c_O + W, the bits packed in
+ * ceil(S^3 / 32) 32-bit words.  Every visited cell of a ray that is not skipped lies inside it (the walk is monotone per axis
+ * between the start and the end cell, |floor(s1) - floor(s0)| <= ceil(|s1 - s0|), and the + 1 absorbs the rounding of
+ * (E - o) / v); a visited cell beyond it would set no bit and count in the info's beyond_window, which stays 0.
+ * Two forms compute the same bytes: the LDS form, one block a view with the window in the CU's LDS, and the global form, the
+ * windows of a chunk of views in device memory under max_bytes, a view's rays over several blocks.  Everything is an integer, OR
+ * and sum are order-free: two calls, two contexts and the two forms give the same bytes.
+ * Every call here on a context with nranks > 1: TLOAM_E_INVALID.  A refused call leaves every output buffer and all state as
+ * it was. */
+typedef struct tloam_closed_map_view_config {   /* choices, not measurements */
+  double max_range;          /* 20: a ray longer than this is skipped, and the window is sized by it; > 0, finite */
+  int64_t max_bytes;         /* 256 MiB: the global form's windows of one chunk; >= 4 */
+  int32_t lds_bytes;         /* 131072: the largest window the LDS form takes; 0 up to what the device reports as the most
+                                shared memory of a block less the kernel's static use */
+  int32_t form;              /* 0 auto: the LDS form when the window fits lds_bytes, else the global one; 1 the LDS form: a
+                                window that does not fit is TLOAM_E_INVALID at the call; 2 the global form */
+} tloam_closed_map_view_config;
+void tloam_closed_map_view_default_config(tloam_closed_map_view_config* cfg);
+/* cfg NULL: the defaults.  A value out of its range: TLOAM_E_INVALID, and the old configuration stays.  Clears the last info
+ * only; persists across tloam_odometry_reset. */
+int tloam_closed_map_view_configure(tloam_ctx* ctx, const tloam_closed_map_view_config* cfg);
+typedef struct tloam_closed_map_view_record {   /* 64 bytes */
+  int64_t unknown_cells;     /* the popcount of the window: THE GAIN */
+  int64_t unknown_visits;    /* UNKNOWN cells crossed, with multiplicity */
+  int64_t free_visits;       /* free or frontier cells crossed */
+  int64_t steps;             /* cells visited, the stopping cell included */
+  int32_t rays_skipped;
+  int32_t rays_occupied;     /* rays stopped by an OCCUPIED cell */
+  int32_t rays_left_box;     /* rays stopped by leaving the box */
+  int32_t rays_ended;        /* rays that passed their end cell */
+  uint32_t origin_label;     /* the field's value at c_O; TLOAM_FRONTIER_OUTSIDE outside the box or for an invalid origin */
+  uint32_t reserved0;        /* 0 */
+  int64_t reserved1;         /* 0 */
+} tloam_closed_map_view_record;
+typedef struct tloam_closed_map_view_info {   /* of the last call */
+  int64_t views;
+  int64_t rays;                /* per view */
+  int64_t window_side;         /* S */
+  int64_t window_bytes;        /* 4 * ceil(S^3 / 32) */
+  int64_t chunks;              /* the global form's chunks of views; 1 in the LDS form */
+  int64_t steps;               /* summed over the views, as the next two */
+  int64_t unknown_visits;
+  int64_t unknown_cells;
+  int64_t beyond_window;       /* visited cells beyond their window: 0 */
+  int32_t form;                /* DIAGNOSTIC: the form that ran, 1 or 2 */
+  int32_t blocks_per_view;     /* DIAGNOSTIC */
+  int32_t launches;            /* DIAGNOSTIC: kernel launches of the call */
+  int32_t waits;               /* DIAGNOSTIC: waits of the host */
+} tloam_closed_map_view_info;
+/* The gain of V >= 1 views under R >= 1 shared ends: poses_colmajor [16 V], ends_aos [3 R], gain_out [V].  NULLs, a pose that
+ * is not finite and rigid, R beyond 2^28 or V * R beyond int64: TLOAM_E_INVALID; so is a window the LDS form is asked for and
+ * cannot take, and a single window above max_bytes in the global form.  The ends and the poses are uploaded; the LDS form is one
+ * launch, the global form per chunk of views a memset of its windows and counters and two launches (rays, count); one wait. */
+int tloam_closed_map_view_gain(tloam_ctx* ctx, const double* poses_colmajor, size_t n_views, const double* ends_aos, size_t n_rays,
+                               tloam_closed_map_view_record* gain_out, tloam_closed_map_view_info* info_or_null);
+/* One view: the centres o + (c + 0.5) * v of the distinct UNKNOWN cells it sees, ascending in window bit index, by
+ * tloam_closed_map_read_box's capacity convention (*n_out: their number, always; more than capacity: TLOAM_E_INVALID and nothing
+ * written; centres_aos_out NULL: the number alone); gain_out_or_null: the view's record.  What a viewer draws. */
+int tloam_closed_map_view_cells(tloam_ctx* ctx, const double* pose_colmajor, const double* ends_aos, size_t n_rays, size_t capacity,
+                                double* centres_aos_out, size_t* n_out, tloam_closed_map_view_record* gain_out_or_null);
+/* The explorer's one call: per kept cluster tloam_closed_map_frontier_costs' cost and approach point, and the gain of the view
+ * with the identity rotation at the approach point.  TLOAM_E_NOT_READY exactly where tloam_closed_map_frontier_costs has it.  A
+ * cluster without an approach point has three NaN for one: every ray of its view is skipped and its origin_label is
+ * TLOAM_FRONTIER_OUTSIDE.  The capacity convention of tloam_closed_map_frontier_clusters (all three outputs NULL: the number
+ * alone).  Two waits. */
+int tloam_closed_map_frontier_gains(tloam_ctx* ctx, const double* ends_aos, size_t n_rays, size_t capacity,
+                                    tloam_closed_map_view_record* gain_out, uint32_t* cost_out, double* approach_aos_out_or_null,
+                                    size_t* n_out);
+/* All zero when there has been no call since the frontier field was last dropped. */
+int tloam_closed_map_get_view_info(tloam_ctx* ctx, tloam_closed_map_view_info* info);
+
 /* ---- the closed map's snapshot: a built closed map out of a context and into a fresh one (additive to ABI 8) ------
  * A memory blob; the library opens no files.  It holds, exactly, everything a context needs to answer every read of the closed
  * map and every localisation in it with the bytes of the context that saved: the place, loop, closed map, carve and surfel

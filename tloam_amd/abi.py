@@ -359,6 +359,39 @@ FRONTIER_CLUSTER_DTYPE = [("sum", "<i8", 3), ("lo", "<i4", 3), ("hi", "<i4", 3),
                           ("unknown_faces", "<u4"), ("reserved", "<u4")]
 
 
+class ViewConfig(Struct):
+    """tloam_closed_map_view_config: the longest ray of a view (it sizes the bit window too), the most bytes the global form's
+    windows of one chunk may take, the largest window the LDS form takes and which form runs -- 0 auto, 1 LDS, 2 global
+    (DESIGN.md section 33).  The defaults are choices, not measurements."""
+    _c_name_ = "tloam_closed_map_view_config"
+    _fields_ = [("max_range", C.c_double), ("max_bytes", C.c_int64), ("lds_bytes", C.c_int32), ("form", C.c_int32)]
+
+
+class ViewRecord(Struct):
+    """tloam_closed_map_view_record: a view's gain and counts, 64 bytes, no implicit padding"""
+    _c_name_ = "tloam_closed_map_view_record"
+    _fields_ = [("unknown_cells", C.c_int64), ("unknown_visits", C.c_int64), ("free_visits", C.c_int64), ("steps", C.c_int64),
+                ("rays_skipped", C.c_int32), ("rays_occupied", C.c_int32), ("rays_left_box", C.c_int32), ("rays_ended", C.c_int32),
+                ("origin_label", C.c_uint32), ("reserved0", C.c_uint32), ("reserved1", C.c_int64)]
+
+
+class ViewInfo(Struct):
+    """tloam_closed_map_view_info, of the last call; form, blocks_per_view, launches and waits are diagnostics."""
+    _c_name_ = "tloam_closed_map_view_info"
+    _fields_ = [("views", C.c_int64), ("rays", C.c_int64), ("window_side", C.c_int64), ("window_bytes", C.c_int64),
+                ("chunks", C.c_int64), ("steps", C.c_int64), ("unknown_visits", C.c_int64), ("unknown_cells", C.c_int64),
+                ("beyond_window", C.c_int64), ("form", C.c_int32), ("blocks_per_view", C.c_int32), ("launches", C.c_int32),
+                ("waits", C.c_int32)]
+
+
+VIEW_FORM_AUTO, VIEW_FORM_LDS, VIEW_FORM_GLOBAL = 0, 1, 2
+VIEW_DIAGNOSTICS = ("chunks", "form", "blocks_per_view", "launches", "waits")   # the info fields that depend on the form that ran
+# a view's record as numpy reads an array of them
+VIEW_GAIN_DTYPE = [("unknown_cells", "<i8"), ("unknown_visits", "<i8"), ("free_visits", "<i8"), ("steps", "<i8"),
+                   ("rays_skipped", "<i4"), ("rays_occupied", "<i4"), ("rays_left_box", "<i4"), ("rays_ended", "<i4"),
+                   ("origin_label", "<u4"), ("reserved0", "<u4"), ("reserved1", "<i8")]
+
+
 SNAPSHOT_CLOUDS = 1   # TLOAM_SNAPSHOT_CLOUDS: the keyframes' eight clouds go into the snapshot too
 
 
@@ -789,6 +822,12 @@ def _signatures():
         "tloam_closed_map_frontier_costs": (C.c_int, [vp, sz, C.POINTER(C.c_uint32), dp, C.POINTER(sz)]),
         "tloam_closed_map_frontier_columns": (C.c_int, [vp, C.c_double, C.c_double, C.c_int64, C.POINTER(C.c_uint32), sz, C.c_void_p,
                                                         C.POINTER(sz), C.POINTER(FrontierInfo)]),
+        "tloam_closed_map_view_default_config": (None, [C.POINTER(ViewConfig)]),
+        "tloam_closed_map_view_configure": (C.c_int, [vp, C.POINTER(ViewConfig)]),
+        "tloam_closed_map_view_gain": (C.c_int, [vp, dp, sz, dp, sz, C.c_void_p, C.POINTER(ViewInfo)]),
+        "tloam_closed_map_view_cells": (C.c_int, [vp, dp, dp, sz, sz, dp, C.POINTER(sz), C.c_void_p]),
+        "tloam_closed_map_frontier_gains": (C.c_int, [vp, dp, sz, sz, C.c_void_p, C.POINTER(C.c_uint32), dp, C.POINTER(sz)]),
+        "tloam_closed_map_get_view_info": (C.c_int, [vp, C.POINTER(ViewInfo)]),
         "tloam_closed_map_read_gone": (C.c_int, [vp, dp, dp, C.c_int64, C.c_double, sz, C.POINTER(sz), dp, C.POINTER(C.c_int64),
                                                  C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
         "tloam_closed_map_save_size": (C.c_int, [vp, C.c_int, C.POINTER(sz)]),

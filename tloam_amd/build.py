@@ -42,6 +42,7 @@ UNITS = [
     ("tl_clear.hip", ["-ffp-contract=off"]),    # the closed map's clearance: integer passes, and the segments' ray walk as DESIGN.md 30 states
     ("tl_route.hip", ["-ffp-contract=off"]),    # the route through the closed map: integer relaxation; the points' cells as DESIGN.md 31 states
     ("tl_frontier.hip", ["-ffp-contract=off"]), # the closed map's frontiers: integer labelling; the points' cells and the centres as DESIGN.md 32 states
+    ("tl_view.hip", ["-ffp-contract=off"]),     # the closed map's view gain: the rays' ends and the walk as DESIGN.md 33 states (tl_voxel.hpp asks for the flag)
     ("tl_deskew.hip", ["-ffp-contract=off"]),   # the deskew: sweep time, exp(s xi) and the point action as DESIGN.md 15 states
     ("tl_place.hip", ["-ffp-contract=off"]),    # place recognition: Scan Context bins, keys and shift distances as DESIGN.md 16 states
     ("tl_loop.hip", ["-ffp-contract=off"]),     # loop verification: the target's transform and the score's distances as DESIGN.md 17 states
@@ -77,10 +78,11 @@ UNITS = [
     ("tl_api_clear.hip", ["-ffp-contract=off"]),      # the closed map's clearance: R and need formed on the host in double
     ("tl_api_route.hip", ["-ffp-contract=off"]),      # the route through the closed map: need formed on the host in double
     ("tl_api_frontier.hip", ["-ffp-contract=off"]),   # the closed map's frontiers: the approach points formed on the host in double
+    ("tl_api_view.hip", ["-ffp-contract=off"]),       # the closed map's view gain: the window's side and the approach poses formed on the host in double
     ("tl_api_snapshot.hip", []), # the closed map's snapshot: save, probe, load
     ("tl_probe.hip", []),        # read-stream bandwidth probe (the on-box ceiling of the bench's roofline block)
 ]
-HEADERS = ["tl_common.hpp", "tl_forms.hpp", "tl_grid_plan.hpp", "tl_scan.hpp", "tl_se3.hpp", "tl_knn.hpp", "tl_walk.hpp", "tl_voxel.hpp", "tl_ctx.hpp", "tl_step.hpp", "tl_finish.hpp", "tl_prep.hpp", "tl_seg.hpp", "tl_extend_host.hpp", "tl_free_box.hpp", "tl_clear_box.hpp", "tl_tile_box.hpp", "tl_tile.hpp", os.path.join("..", "..", "include", "tloam_hip.h")]
+HEADERS = ["tl_common.hpp", "tl_forms.hpp", "tl_grid_plan.hpp", "tl_scan.hpp", "tl_se3.hpp", "tl_knn.hpp", "tl_walk.hpp", "tl_voxel.hpp", "tl_ctx.hpp", "tl_step.hpp", "tl_finish.hpp", "tl_prep.hpp", "tl_seg.hpp", "tl_extend_host.hpp", "tl_free_box.hpp", "tl_clear_box.hpp", "tl_tile_box.hpp", "tl_tile.hpp", "tl_view_box.hpp", os.path.join("..", "..", "include", "tloam_hip.h")]
 
 
 def _hipcc():

@@ -200,6 +200,7 @@ int tloam_closed_map_frontier_build(tloam_ctx* c, tloam_closed_map_frontier_info
   // from here on the previous field is gone
   Fr.have = false;
   Fr.info = tloam_closed_map_frontier_info{};
+  Fr.view.info = tloam_closed_map_view_info{};   // (the last view call was of that field)
   Fr.field = TileField{};
   Fr.table = FrontTable{};
   Fr.kept.clear();

@@ -1149,6 +1149,35 @@ struct FrontCostsArgs {
 };
 void launch_front_costs(const FrontCostsArgs& A, hipStream_t s);
 
+// ---- the view gain of the closed map (tl_view.hip): per view the distinct UNKNOWN cells of the frontier
+// field its rays cross, as the popcount of a bit window round the view's origin cell.  Nothing but the records, the windows and
+// the counters is written
+constexpr int kViewCounters = 8;   // a view's counters: unknown visits, free visits, steps, rays skipped / occupied / left the
+                                   // box / ended, cells beyond the window
+constexpr int kViewLdsThreads = 1024, kViewThreads = 256;
+struct ViewArgs {
+  TileField f;                // the frontier field: the states
+  MapGrid grid;               // the map's grid: origin and voxel (ray_begin)
+  double max_range;
+  const double* poses;        // [16 views of the call] column-major, as they stand
+  const double* ends;         // [3 rays] sensor frame
+  long long rays;
+  long long words;            // of one window: ceil(S^3 / 32)
+  int W, S;
+  long long view0;            // the first view of this launch (a chunk's); block b of the LDS form is view view0 + b
+  int bpv, reserved0;         // the global form: blocks a view
+  unsigned* win;              // the global form: [views of the chunk][words], zero before the ray launch
+  unsigned long long* cnt;    // the global form: [views of the chunk][kViewCounters], zero before the ray launch
+  tloam_closed_map_view_record* out;   // [views of the call]
+  unsigned long long* beyond;        // [views of the call] a view's visited cells beyond its window
+  double* centres;            // the cells form: [3 capacity] out, ascending in bit index (null: none)
+  long long capacity;
+};
+size_t view_lds_static();                                      // the LDS form's static shared memory, bytes
+hipError_t launch_view_lds(const ViewArgs& A, long long views, bool cells, hipStream_t s);   // one launch
+void launch_view_rays(const ViewArgs& A, long long views, hipStream_t s);                    // the global form: the rays ...
+void launch_view_count(const ViewArgs& A, long long views, bool cells, hipStream_t s);       // ... then the popcount and the records
+
 // ---- deskew of a scan under constant velocity (tl_deskew.hip) -------------
 struct DeskewArgs {
   const double* in;               // AoS xyz [3n]

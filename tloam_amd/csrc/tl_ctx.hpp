@@ -611,13 +611,27 @@ struct CmapState {
       std::vector<tloam_closed_map_frontier_cluster> kept;   // the kept list as the build read it back
       bool have = false;           // a build has succeeded since the last drop
       tloam_closed_map_frontier_info info{};
+      // the view gain (tl_api_view.hip): its configuration, the uploaded poses, the records, the views'
+      // beyond-window counts, the global form's windows and counters, the cells form's centres (grow-only scratch) and what the
+      // last call reports.  It reads the field as the dense state array of the box: nothing is stored, the info goes with the field
+      struct ViewState {
+        tloam_closed_map_view_config cfg;   // tloam_closed_map_view_default_config until configured
+        ViewState() { tloam_closed_map_view_default_config(&cfg); }
+        DBuf<double> poses, out_f64;
+        DBuf<tloam_closed_map_view_record> rec;
+        DBuf<unsigned long long> beyond, cnt;
+        DBuf<unsigned> win;
+        tloam_closed_map_view_info info{};
+      } view;
       void drop() {
         have = false;
         info = tloam_closed_map_frontier_info{};
+        view.info = tloam_closed_map_view_info{};
         field = tl::TileField{};
         table = tl::FrontTable{};
         kept.clear();
         own.release();             // (hipFree waits for the launches that use them)
+        view.win.release();
       }
     } frontier;
     // what was built from the grid and the map's counting voxels goes when either changes: the one list

@@ -584,3 +584,17 @@ def read_frontier_clusters_pcd(path: str):
     cost (k,) float64)."""
     rec = _read_xyz_and_fields(path, ["cells", "unknown_faces", "cost"])
     return np.ascontiguousarray(rec[:, :3]), rec[:, 3].astype(np.int64), rec[:, 4].astype(np.int64), np.ascontiguousarray(rec[:, 5])
+
+
+def write_view_pcd(path: str, H, pose, ends, ascii: bool = False) -> int:
+    """Writes the centres of the distinct UNKNOWN cells one view sees (a HipRegistration after closed_map_frontier_build; `pose`
+    4 x 4, `ends` (r, 3) in the sensor frame: closed_map_view_cells), ascending in window bit index, as PCD v0.7 -> the cells
+    written: the view's gain."""
+    cen, _ = H.closed_map_view_cells(pose, ends)
+    write_pcd(path, cen, ascii=ascii)
+    return len(cen)
+
+
+def read_view_pcd(path: str) -> np.ndarray:
+    """Reads a file of write_view_pcd (DATA ascii or binary) -> centres (n, 3) float64."""
+    return read_pcd(path)

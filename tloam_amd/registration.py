@@ -106,6 +106,7 @@ _CONFIGS = {
     ClearanceConfig: ("tloam_closed_map_clearance_default_config", {}),
     RouteConfig: ("tloam_closed_map_route_default_config", {}),
     FrontierConfig: ("tloam_closed_map_frontier_default_config", {}),
+    ViewConfig: ("tloam_closed_map_view_default_config", {}),
 }
 
 
@@ -1275,6 +1276,55 @@ class HipRegistration:
         rec = rec[:m].copy()
         return label[: nx * ny].reshape(ny, nx).copy(), rec, self._frontier_centroids(rec, info.as_dict()["lo_cells"]), info.as_dict()
 
+    # ---- the view gain of the closed map: the unknown cells seen from candidate poses
+    def closed_map_view_configure(self, cfg: ViewConfig | None = None, **over):
+        """the view gain's configuration (default_closed_map_view_config(**over) when cfg is None); clears the last info only.
+        Kept across odometry_reset; a refused configuration leaves the old one."""
+        self._configure(ViewConfig, "tloam_closed_map_view_configure", cfg, over)
+
+    def closed_map_view_gain(self, poses, ends):
+        """the gain of the views at `poses` ((v, 4, 4) or one 4 x 4) under the shared segment ends `ends` ((r, 3), sensor frame)
+        against the built frontier field -> records (v,) of VIEW_GAIN_DTYPE: `unknown_cells` is the gain, the distinct UNKNOWN
+        cells the view's rays cross before an OCCUPIED cell or the box stops them"""
+        P = np.asarray(poses, np.float64).reshape(-1, 4, 4)
+        flat = np.ascontiguousarray(P.transpose(0, 2, 1)).reshape(-1)
+        e = _aos(ends)
+        rec = np.zeros(max(len(P), 1), VIEW_GAIN_DTYPE)
+        self._call("tloam_closed_map_view_gain", _dp(flat), len(P), _dp(e), len(e), rec.ctypes.data, None)
+        return rec[: len(P)].copy()
+
+    def closed_map_view_cells(self, pose, ends):
+        """one view's seen cells -> (centres (m, 3) float64 of the distinct UNKNOWN cells, ascending in window bit index, the
+        view's record (1,) of VIEW_GAIN_DTYPE)"""
+        flat, e = _colmajor(pose), _aos(ends)
+        rec = np.zeros(1, VIEW_GAIN_DTYPE)
+        n = C.c_size_t(0)
+        rc = self.L.tloam_closed_map_view_cells(self.h, _dp(flat), _dp(e), len(e), 0, None, C.byref(n), rec.ctypes.data)
+        if rc not in (0, -1) or (rc == -1 and n.value == 0):
+            self._check(rc, "tloam_closed_map_view_cells")
+        m = n.value
+        cen = np.zeros((max(m, 1), 3), np.float64)
+        if m:
+            self._call("tloam_closed_map_view_cells", _dp(flat), _dp(e), len(e), m, _dp(cen), C.byref(n), rec.ctypes.data)
+        return cen[:m].copy(), rec
+
+    def closed_map_frontier_gains(self, ends):
+        """the explorer's one call: per kept cluster the view gain at its approach point (identity rotation) beside
+        closed_map_frontier_costs' cost and approach point -> (records (k,) of VIEW_GAIN_DTYPE, cost (k,) uint32, approach (k, 3)
+        float64); a cluster without an approach point has every ray skipped"""
+        e = _aos(ends)
+        m = self._probe_count("tloam_closed_map_frontier_gains", _dp(e), len(e), 0, None, None, None)
+        rec, cost, approach = np.zeros(max(m, 1), VIEW_GAIN_DTYPE), np.zeros(max(m, 1), np.uint32), np.zeros((max(m, 1), 3), np.float64)
+        if m:
+            n = C.c_size_t(0)
+            self._call("tloam_closed_map_frontier_gains", _dp(e), len(e), m, rec.ctypes.data, _u32p(cost), _dp(approach), C.byref(n))
+        return rec[:m].copy(), cost[:m].copy(), approach[:m].copy()
+
+    def closed_map_view_info(self) -> dict:
+        """of the last view call (its VIEW_DIAGNOSTICS fields depend on the form that ran); all zero when there has been none
+        since the frontier field was last dropped"""
+        return self._info(ViewInfo, "tloam_closed_map_get_view_info")
+
     def fitness(self):
         f, r = C.c_double(0), C.c_double(0)
 
@@ -1515,6 +1565,12 @@ def default_closed_map_frontier_config(**over) -> FrontierConfig:
     """tloam_closed_map_frontier_default_config (max_bytes 1 GiB, min_cells 8, reach 2, max_rounds 65536, rounds_per_wait 16)
     with keyword overrides"""
     return _default(FrontierConfig, over)
+
+
+def default_closed_map_view_config(**over) -> ViewConfig:
+    """tloam_closed_map_view_default_config (max_range 20, max_bytes 256 MiB, lds_bytes 131072, form 0: auto) with keyword
+    overrides"""
+    return _default(ViewConfig, over)
 
 
 def default_closed_map_route_config(**over) -> RouteConfig:
